@@ -22,7 +22,7 @@ Bloom across tile borders: `--mode halo` (default) shades interior + 4 px and ex
 The only other collective is the 256-bin histogram all-reduce (on its own communicator).  `value` counts interior pixels.
 `host_graph` = the same frames driven by the C++ pass graph (libpbr_host.so: RenderScheduler -> FrameGraph -> passes -> C ABI).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -60,6 +60,8 @@ ENV_SIZE, LUT_RES, N_LIGHTS = 512, 512, 256
 ROUGH_MIN = 48                  # synth.gbuffer_tile default; see config.workload
 CFG5_FRAME = (7680, 4320)       # BASELINE.json configs[4]
 CFG5_GRID = {8: (4, 2)}         # (cols, rows): "tiled 2x4" = 2 rows of 4 tiles; other N: the most square grid
+DUMP_SAMPLE_PX = 1 << 20        # --dump-outputs: interior pixels sampled over all ranks (HDR + LDR as float32: 32 MB in all)
+DUMP_SEED = 12345
 
 
 DRY = False   # --dry-run: no device call is made anywhere below (bench_dryrun.py)
@@ -111,7 +113,14 @@ def parse():
                    help="dry run only, fault injection: '<rank>:<mode>/<transport>' — that rank's set-up of that candidate raises; '<rank>:miscount' — its first "
                         "verification frame counts one pixel too many (every rank must fall back together); '<rank>:hang' — it never arrives at its first "
                         "all-reduce (the watchdog's --deadline must end the launch)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the headline's last timed frame computed as DIR/<name>.npy (float32): the adapted "
+                        "luminance and the bloomed HDR / tone-mapped LDR images at a fixed, seeded sample of interior pixels (frame_outputs); "
+                        "with N > 1 every rank writes its own tile's, as <name>_rank<r>.npy")
+    a = p.parse_args()
+    if a.dump_outputs and a.dry_run:
+        p.error("--dump-outputs needs device outputs: a --dry-run computes none")
+    return a
 
 
 def spawn_ranks(a):
@@ -534,8 +543,30 @@ def verify_frame(job, fr):
     fr.set_prev_luminance(0.18)
 
 
-def run_workload(job, name, scaling, make_spec, full_w, full_h, cols, rows, steps, warmup, settle, want_stage_timing):
-    """Set up, verify and time one workload on all ranks.  Returns a dict (rank 0 reports it)."""
+def frame_outputs(frame, world):
+    """What a caller of DeferredFrame.render() holds after the frame, as float32 arrays: the adapted luminance, and the bloomed HDR
+    and tone-mapped LDR images of this rank's interior at a fixed, seeded sample of pixels (the whole 4K images in float32 would be
+    265 MB).  The sample depends on the tile's size only, so runs with the same arguments dump the same pixels."""
+    s = frame.spec
+    n = s.w * s.h
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_SAMPLE_PX // world), replace=False))
+    y, x = idx // s.w, idx % s.w
+    hdr_idx = torch.from_numpy((y + s.siy) * s.sw + (x + s.six)).to(frame.hdr.device)
+    hdr = frame.hdr.view(-1, 4)[hdr_idx].float().cpu().numpy()                          # fp16 -> fp32 is exact
+    ldr = frame.ldr.view(-1)[torch.from_numpy(idx).to(frame.ldr.device)].cpu().numpy().view(np.uint32)
+    ldr = ((ldr[:, None] >> np.array([0, 8, 16, 24], dtype=np.uint32)) & 255).astype(np.float32)   # packed RGBA8 -> bytes
+    return {"avg_luminance": frame.avg.cpu().numpy().astype(np.float32), "hdr": hdr, "ldr": ldr}
+
+
+def write_outputs(d, outputs, rank, world):
+    os.makedirs(d, exist_ok=True)
+    for k, v in outputs.items():
+        np.save(os.path.join(d, f"{k}_rank{rank}.npy" if world > 1 else f"{k}.npy"), v)
+
+
+def run_workload(job, name, scaling, make_spec, full_w, full_h, cols, rows, steps, warmup, settle, want_stage_timing, want_outputs=False):
+    """Set up, verify and time one workload on all ranks.  Returns a dict (rank 0 reports it); with want_outputs, its "outputs"
+    are frame_outputs() of the last timed frame."""
     a, ctx, dist, rank, world, rehearsal = job.a, job.ctx, job.dist, job.rank, job.world, job.rehearsal
     cam = scene.Camera.reference_default(full_w, full_h)
     g = scene.make_global(cam, full_w, full_h, sh_pack=job.sh, delta_time=1.0 / 60.0)
@@ -607,6 +638,7 @@ def run_workload(job, name, scaling, make_spec, full_w, full_h, cols, rows, step
     shade_events = [] if (want_stage_timing and not a.no_kernel_timing) else None
     dt = timed(settle, warmup, steps, shade_events)
     ms_per_step = dt / steps * 1e3
+    outputs = frame_outputs(frame, world) if want_outputs else None   # before the variants below render more frames
 
     # ---- the same frames with the tail beside the next frame's shade (multi-GPU, C-ABI collectives): hides the all-reduce's
     # latency.  Checked on every rank against the plain order (three frames each: same adapted luminance, same LDR image).
@@ -684,7 +716,7 @@ def run_workload(job, name, scaling, make_spec, full_w, full_h, cols, rows, step
     res = {"name": name, "scaling": scaling, "frame_obj": frame, "g": g, "lights": lights, "gb_np": gb_np, "spec": spec, "cols": cols, "rows": rows,
            "ms_per_step": ms_per_step, "value": total_px / (ms_per_step * 1e-3) / 1e6, "ms_overlapped": ms_overlapped,
            "mode": mode, "transport": transport, "notes": notes, "lights_px": lp, "shade_events": shade_events, "total_px": total_px,
-           "overlap_n1": overlap_n1}
+           "overlap_n1": overlap_n1, "outputs": outputs}
     return res
 
 
@@ -1156,7 +1188,9 @@ def main():
         primary = ("weak", lambda r, halo: tile_for_rank(r, world, tw, th, layout=(cols, rows), halo=halo), cols * tw, rows * th, cols, rows)
 
     res = run_workload(job, "headline", primary[0], primary[1], primary[2], primary[3], primary[4], primary[5], a.steps, a.warmup, a.settle,
-                       want_stage_timing=True)
+                       want_stage_timing=True, want_outputs=bool(a.dump_outputs))
+    if a.dump_outputs:
+        write_outputs(a.dump_outputs, res["outputs"], rank, world)
     frame, spec, g, lights = res["frame_obj"], res["spec"], res["g"], res["lights"]
     out = {
         "metric": "shaded Mpixel/s at 4K G-buffer (full deferred frame: clustered shade + bloom + auto-exposure + ACES)",

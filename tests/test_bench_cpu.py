@@ -114,3 +114,47 @@ def test_bench_n8_dry_run_a_rank_that_never_arrives_ends_the_launch_at_the_deadl
     r, lines, d = _dry_run(["--dry-fail", "5:hang", "--deadline", "15", "--no-cfg5"], timeout=240)
     assert r.returncode != 0 and time.monotonic() - t0 < 180
     assert "did not finish before its deadline" in r.stderr and lines == []
+
+
+def test_dump_outputs_sample_the_interior_at_fixed_pixels(tmp_path):
+    """`bench.py --dump-outputs`: frame_outputs() reads the frame's INTERIOR (not the apron of the shaded rectangle around it) at a seeded
+    sample of pixels that is the same on every call, HDR and LDR at the same pixels, all in float32 and within 64 MB at the 4K headline."""
+    import types
+    import torch
+    import bench
+    from direct12pbrrenderer_amd.pipeline import TileSpec
+    spec = TileSpec(256, 128, 640, 384, 1280, 768, apron=256)        # apron mode: the interior sits at (256, 128) inside S
+    assert (spec.six, spec.siy) == (256, 128) and (spec.sw, spec.sh) == (1152, 768)
+    sy, sx = np.meshgrid(np.arange(spec.sh), np.arange(spec.sw), indexing="ij")
+    hdr = np.stack([sx, sy, np.full_like(sx, 3), np.ones_like(sx)], -1).astype(np.float16)     # every S texel holds its own coordinates
+    iy, ix = np.meshgrid(np.arange(spec.h), np.arange(spec.w), indexing="ij")
+    ldr = ((ix & 255) | ((iy & 255) << 8) | ((ix >> 8) << 16) | ((iy >> 8) << 20) | (7 << 24)).astype(np.uint32)
+    fr = types.SimpleNamespace(spec=spec, hdr=torch.from_numpy(hdr), ldr=torch.from_numpy(ldr.view(np.int32)), avg=torch.tensor([0.25]))
+    world = 4                                                          # 2^20 / 4 = 262144 > 640 x 384: every pixel
+    out = bench.frame_outputs(fr, world)
+    assert set(out) == {"avg_luminance", "hdr", "ldr"} and all(v.dtype == np.float32 for v in out.values())
+    assert out["hdr"].shape == out["ldr"].shape == (spec.w * spec.h, 4) and out["avg_luminance"].tolist() == [0.25]
+    world = 8                                                          # 131072 of 245760 pixels
+    out = bench.frame_outputs(fr, world)
+    again = bench.frame_outputs(fr, world)
+    assert all(np.array_equal(out[k], again[k]) for k in out)
+    h, l = out["hdr"], out["ldr"]
+    assert h.shape == l.shape == (bench.DUMP_SAMPLE_PX // world, 4)
+    x, y = h[:, 0] - spec.six, h[:, 1] - spec.siy
+    assert (x >= 0).all() and (x < spec.w).all() and (y >= 0).all() and (y < spec.h).all() and (h[:, 2:] == (3, 1)).all()
+    flat = y.astype(np.int64) * spec.w + x.astype(np.int64)
+    assert (np.diff(flat) > 0).all()                                   # distinct pixels, in memory order
+    assert np.array_equal(l[:, 0] + 256 * (l[:, 2] % 16), x) and np.array_equal(l[:, 1] + 256 * (l[:, 2] // 16), y) and (l[:, 3] == 7).all()
+    assert 2 * bench.DUMP_SAMPLE_PX * 4 * 4 + 4 <= 64 << 20            # HDR + LDR samples + the luminance, summed over all ranks
+    bench.write_outputs(str(tmp_path / "d"), out, 0, 1)
+    bench.write_outputs(str(tmp_path / "d"), out, 1, 2)
+    assert sorted(os.listdir(tmp_path / "d")) == ["avg_luminance.npy", "avg_luminance_rank1.npy", "hdr.npy", "hdr_rank1.npy", "ldr.npy", "ldr_rank1.npy"]
+    assert np.array_equal(np.load(tmp_path / "d" / "hdr_rank1.npy"), h)
+
+
+def test_dump_outputs_refuses_a_dry_run():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--dump-outputs", "x"], capture_output=True,
+                       text=True, cwd=ROOT, env=dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES=""))
+    assert r.returncode == 2 and "--dump-outputs needs device outputs" in r.stderr and r.stdout.strip() == ""
+    assert not os.path.exists(os.path.join(ROOT, "x"))

@@ -64,3 +64,29 @@ def test_bench_prints_one_json_line(extra, n):
         hg = rec["host_graph"]
         assert "error" not in hg and hg["fused_throughput_ms"] > 0 and "rehearsal" in hg, hg
         assert "error" not in c5["host_graph"] and c5["host_graph"]["fused_throughput_ms"] > 0, c5["host_graph"]
+
+
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """`--dump-outputs DIR`: the last timed frame's outputs (bench.frame_outputs) as float32 .npy files within 64 MB; two runs with the same
+    arguments render the same inputs and dump the same arrays, bit for bit (no atomics on floats anywhere in the frame)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        cmd = ["timeout", "-k", "10", "250", sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--settle", "3",
+               "--no-cpu-baseline", "--no-kernel-timing", "--no-host-graph", "--no-shade-paths", "--no-configs", "--no-tail-overlap", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads(r.stdout.splitlines()[-1])
+        assert rec["steps"] == 4 and rec["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["avg_luminance.npy", "hdr.npy", "ldr.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = dumps
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["hdr"].shape == a["ldr"].shape == (1 << 20, 4) and a["avg_luminance"].shape == (1,)
+    assert np.isfinite(a["hdr"]).all() and (a["hdr"][:, :3] >= 0).all() and a["hdr"][:, :3].max() > 0 and a["avg_luminance"][0] > 0
+    assert (a["ldr"] >= 0).all() and (a["ldr"] <= 255).all() and a["ldr"][:, :3].max() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
