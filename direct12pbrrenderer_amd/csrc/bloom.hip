@@ -620,32 +620,12 @@ __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ 
     }
 }
 
-// ---------------------------------------------------------------- 2x-up levels of large images: 128-wide tiles
-// The same passes as k_blur_hv<M_UP, ...> (bit-identical results), remapped so that the LDS carries half the traffic
-// per output — in k_blur_hv the H pass's nine ds_reads per output and the V pass's nine keep the LDS pipe as busy as
-// the VALU (~5K cycles each per tile) and the two serialise:
-//   * H pass: a lane owns the column PAIR (2p, 2p+1) of its wave's rows.  The two 2x-up samples of a pair blend the
-//     three level texels p-1, p, p+1 (3 loads per two samples instead of 4), a sample line is 68 float2 entries per
-//     channel, and the two outputs of a lane tap the five entries lane .. lane+4: 15 ds_read_b64 per two outputs
-//     instead of 18 ds_read_b96.
-//   * V pass: a thread owns a column and TH/4 CONSECUTIVE rows, so the rows it taps overlap: TH/4 + 8 reads of the
-//     fp16 tile for TH/4 outputs instead of nine per output.
-// One block (512 threads, 8 waves) = one 128 x TH tile.  Operation order per sample / tap is k_blur_hv's.
+// ---------------------------------------------------------------- 2x-up levels of large images: k_blur_up_poly
 // texel `byte_off / 8` of a half4 image: a (wave-uniform or not) base + an UNSIGNED 32-bit byte offset, the form that loads as
 // `global_load_dwordx2 v, v_off, s[base]` — a signed index makes every load pay a 64-bit vector add (slow issue class, §4.7).
 // Images here are < 4 GiB (8 192^2 half4 = 512 MB).
 __device__ __forceinline__ H4 ld_h4(const void* base, uint32_t byte_off) {
     return *reinterpret_cast<const H4*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-__device__ __forceinline__ void pair_tap_up(const pbr_half* __restrict__ in, int iw, int cm, int c0, int cp, int ay0, int ay1, float fy,
-                                            V3& even, V3& odd) {
-    const uint32_t ra = (uint32_t)(ay0 * iw) * 8u, rb = (uint32_t)(ay1 * iw) * 8u, om = (uint32_t)cm * 8u, o0 = (uint32_t)c0 * 8u, op = (uint32_t)cp * 8u;
-    const V3 am = h3f(ld_h4(in, ra + om)), a0 = h3f(ld_h4(in, ra + o0)), ap = h3f(ld_h4(in, ra + op));
-    const V3 bm = h3f(ld_h4(in, rb + om)), b0 = h3f(ld_h4(in, rb + o0)), bp = h3f(ld_h4(in, rb + op));
-    const float wy0 = 1.0f - fy;
-    // even column 2p: taps (p-1, p), second-tap weight 3/4; odd column 2p+1: (p, p+1), 1/4 (tap1d<M_UP>; finish_tap2_rgb)
-    even = fma3(fma3(b0, 0.75f, bm * 0.25f), fy, fma3(a0, 0.75f, am * 0.25f) * wy0);
-    odd = fma3(fma3(bp, 0.25f, b0 * 0.75f), fy, fma3(ap, 0.25f, a0 * 0.75f) * wy0);
 }
 // the nine taps of the two outputs of a lane from the five pair entries e[0..4] of one channel
 __device__ __forceinline__ void gauss9_pair(const float2* e, float& ge, float& go) {
@@ -656,234 +636,22 @@ __device__ __forceinline__ void gauss9_pair(const float2* e, float& ge, float& g
     ge = a; go = b;
 }
 
-#ifdef PBR_DEBUG_KNOBS   // ---- k_blur_up_wide: the shader-order (bit-exact) 2x-up kernel of round 3, superseded by k_blur_up_poly.  Only the knobs
-// build carries it (PBR_BLOOM_POLY=0): as the A/B partner and as the bit-exact checker of the wide path (tests/test_gpu_parity.py)
-#ifdef PBR_BLOOM_TIMING   // experiment only (-DPBR_BLOOM_TIMING=<n>, tools/debug/tail_timing.py): shader-clock stamps of wave 0 of every block's n-th tile
-__device__ unsigned long long g_tail_stamp[8 * 4096];
-#define TSTAMP(i) do { if (TAIL == 2 && t == 0 && tile == (int)blockIdx.x + PBR_BLOOM_TIMING * (int)gridDim.x && blockIdx.x < 4096) g_tail_stamp[blockIdx.x * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
-#define TWAIT_VM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-extern "C" int pbr_debug_tail_stamps(unsigned long long* host, int n) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_tail_stamp), sizeof(unsigned long long) * n); }
-#else
-#define TSTAMP(i) do {} while (0)
-#define TWAIT_VM() do {} while (0)
-#endif
-template <bool DUAL, int TAIL, int TH>
-__global__ __launch_bounds__(512, TH == 16 ? 6 : 4) void k_blur_up_wide(const pbr_half* __restrict__ in, int iw, int ih,
-                                                          const pbr_half* __restrict__ in2,   // DUAL: ow x oh, same-size
-                                                          pbr_half* __restrict__ out, int ow, int oh, int out_pitch,
-                                                          int tiles_x, int n_tiles,
-                                                          TailRect tr, float min_log, float inv_range,
-                                                          uint32_t* __restrict__ hist) {
-    constexpr int TW = 128, NP = TW / 2 + 4, SR = TH + 8, NT = 512, NW = NT / 64;
-    constexpr int PER_T = SR / NW;      // H rows per wave
-    constexpr int PER_O = TH / 4;       // V outputs per thread: column t & 127, rows (t >> 7) * PER_O ..
-    static_assert(SR % NW == 0 && TH % 4 == 0 && PER_T * 4 <= 64, "rows must split evenly over the waves; one halo pair per lane");
-    __shared__ float2 sLine[DUAL ? 2 : 1][NW][3][NP];
-    __shared__ H4 sT[SR][TW];
-    __shared__ uint32_t sh_hist[TAIL == 2 ? NW : 1][TAIL == 2 ? PBR_HISTOGRAM_BINS : 1];
-    const int t = threadIdx.x, lane = t & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int vc = t & 127, vg = __builtin_amdgcn_readfirstlane(t >> 7);
-    if (TAIL == 2) {
-        for (int i = t; i < NW * PBR_HISTOGRAM_BINS; i += NT) (&sh_hist[0][0])[i] = 0u;
-    }
-    // (read at a texel the launch's rectangle depends on: see k_blur_hv)
-    const size_t a_at = (size_t)min(tr.my0 >> 1, ih - 1) * iw + min(tr.mx0 >> 1, iw - 1);
-    float alpha_h = gauss9_const((float)reinterpret_cast<const H4*>(in)[a_at].w);
-    if (DUAL) alpha_h = alpha_h + gauss9_const((float)reinterpret_cast<const H4*>(in2)[(size_t)min(tr.my0, oh - 1) * ow + min(tr.mx0, ow - 1)].w);
-    const h16 alpha_t = to_half_rn(alpha_h);
-    const float alpha_v = gauss9_const((float)alpha_t);
-    const float a0w = (float)to_half_rn(alpha_v);   // alpha of the A0 texel the separate V pass would have stored
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int x0 = (tr.tx0 + tile % tiles_x) * TW, y0 = (tr.ty0 + tile / tiles_x) * TH;   // (TAIL 0 without a rectangle: tx0 = ty0 = 0)
-    const int xv = x0 + vc, rbase = vg * PER_O;
-    TSTAMP(0);
-    H4 hdr_in[PER_O];
-    const bool in_mx = TAIL != 0 && xv >= tr.mx0 && xv < tr.mx1;
-    // this thread's HDR texels (dereferenced only inside the merge rect): row k of the thread = a wave-uniform base + the lane's
-    // unsigned byte offset
-    char* const hdr_row0 = reinterpret_cast<char*>(out) + (ptrdiff_t)(y0 + rbase - tr.by) * out_pitch * 8;
-    const uint32_t hdr_x = (uint32_t)(xv - tr.bx) * 8u;
-    const size_t hdr_pitch = (size_t)out_pitch * 8u;
-    // sample positions: columns x0-4 .. x0+131 = pair entries 0..67 (entry q = level texel pair index x0/2 - 2 + q),
-    // rows clamp(y0-4+r).  Main entry of a row: q = lane; the four halo entries 64..67 of the wave's PER_T rows are one
-    // extra tap: lane -> (row lane / 4, entry 64 + lane % 4).
-    const int r0 = wv * PER_T, first = y0 - 4 + r0;
-    const int pp = (x0 >> 1) - 2 + lane;
-    const int cm = clampi(pp - 1, 0, iw - 1), c0 = clampi(pp, 0, iw - 1), cp = clampi(pp + 1, 0, iw - 1);
-    const bool has_halo = lane < PER_T * 4;
-    const int hk = lane >> 2, hq = 64 + (lane & 3);
-    {
-        V3 sE[PER_T], sO[PER_T], hE = v3(0.0f, 0.0f, 0.0f), hO = hE;
-        H4 upE[DUAL ? PER_T : 1], upO[DUAL ? PER_T : 1], hupE{}, hupO{};
-        const int sxe = clampi(x0 - 4 + 2 * lane, 0, ow - 1), sxo = clampi(x0 - 3 + 2 * lane, 0, ow - 1);
-        const bool shared_rows = first >= 1 && first + PER_T - 1 <= oh - 2;   // see k_blur_hv
-        if (shared_rows) {
-            constexpr int NR = PER_T / 2 + 2;
-            const int base = (first >> 1) - 1 + (first & 1);
-            V3 hrE[NR], hrO[NR];
-            const uint32_t om = (uint32_t)cm * 8u, o0 = (uint32_t)c0 * 8u, op = (uint32_t)cp * 8u;
-#pragma unroll
-            for (int j = 0; j < NR; j++) {
-                const char* row = reinterpret_cast<const char*>(in) + (size_t)min(base + j, ih - 1) * iw * 8u;   // wave-uniform: a scalar base
-                const V3 tm = h3f(ld_h4(row, om)), t0 = h3f(ld_h4(row, o0)), tp = h3f(ld_h4(row, op));
-                hrE[j] = fma3(t0, 0.75f, tm * 0.25f);
-                hrO[j] = fma3(tp, 0.25f, t0 * 0.75f);
-            }
-            auto blend = [&](auto parity) {
-                constexpr int P = decltype(parity)::value;
-#pragma unroll
-                for (int k = 0; k < PER_T; k++) {
-                    const int odd = (P + k) & 1;
-                    const int i0 = (P + k + 1) / 2 - P;
-                    const float fyk = odd ? 0.25f : 0.75f, wy0 = 1.0f - fyk;
-                    sE[k] = fma3(hrE[i0 + 1], fyk, hrE[i0] * wy0);
-                    sO[k] = fma3(hrO[i0 + 1], fyk, hrO[i0] * wy0);
-                }
-            };
-            if (first & 1) blend(std::integral_constant<int, 1>{}); else blend(std::integral_constant<int, 0>{});
-        } else {
-#pragma unroll
-            for (int k = 0; k < PER_T; k++) {
-                const int jj = clampi(first + k, 0, oh - 1);
-                int ay0, ay1; float fy;
-                tap1d<M_UP>(jj, ih, ay0, ay1, fy);
-                pair_tap_up(in, iw, cm, c0, cp, ay0, ay1, fy, sE[k], sO[k]);
-            }
-        }
-        if (DUAL) {
-#pragma unroll
-            for (int k = 0; k < PER_T; k++) {
-                const char* row = reinterpret_cast<const char*>(in2) + (size_t)clampi(first + k, 0, oh - 1) * ow * 8u;   // wave-uniform
-                upE[k] = ld_h4(row, (uint32_t)sxe * 8u); upO[k] = ld_h4(row, (uint32_t)sxo * 8u);
-            }
-        }
-        if (has_halo) {
-            const int jj = clampi(first + hk, 0, oh - 1);
-            const int hp = (x0 >> 1) - 2 + hq;
-            int ay0, ay1; float fy;
-            tap1d<M_UP>(jj, ih, ay0, ay1, fy);
-            pair_tap_up(in, iw, clampi(hp - 1, 0, iw - 1), clampi(hp, 0, iw - 1), clampi(hp + 1, 0, iw - 1), ay0, ay1, fy, hE, hO);
-            if (DUAL) {
-                const uint32_t row = (uint32_t)(jj * ow) * 8u;
-                hupE = ld_h4(in2, row + (uint32_t)clampi(x0 - 4 + 2 * hq, 0, ow - 1) * 8u); hupO = ld_h4(in2, row + (uint32_t)clampi(x0 - 3 + 2 * hq, 0, ow - 1) * 8u);
-            }
-        }
-        // the HDR texels of the merge: issued AFTER the level's texels (loads return in order, and the samples below wait
-        // for the level's only), consumed after the H pass
-        if (TAIL != 0) {
-#pragma unroll
-            for (int k = 0; k < PER_O; k++) {
-                const int y = y0 + rbase + k;
-                if (in_mx && y >= tr.my0 && y < tr.my1) hdr_in[k] = ld_h4(hdr_row0 + k * hdr_pitch, hdr_x);
-            }
-        }
-        TSTAMP(1);
-        TWAIT_VM();
-        TSTAMP(2);
-        float2 (*line)[NP] = sLine[0][wv];
-        float2 (*line2)[NP] = sLine[DUAL ? 1 : 0][wv];
-#pragma unroll
-        for (int k = 0; k < PER_T; k++) {
-            line[0][lane] = make_float2(sE[k].x, sO[k].x); line[1][lane] = make_float2(sE[k].y, sO[k].y); line[2][lane] = make_float2(sE[k].z, sO[k].z);
-            if (DUAL) {
-                line2[0][lane] = make_float2((float)upE[k].x, (float)upO[k].x); line2[1][lane] = make_float2((float)upE[k].y, (float)upO[k].y);
-                line2[2][lane] = make_float2((float)upE[k].z, (float)upO[k].z);
-            }
-            if (has_halo && hk == k) {
-                line[0][hq] = make_float2(hE.x, hO.x); line[1][hq] = make_float2(hE.y, hO.y); line[2][hq] = make_float2(hE.z, hO.z);
-                if (DUAL) {
-                    line2[0][hq] = make_float2((float)hupE.x, (float)hupO.x); line2[1][hq] = make_float2((float)hupE.y, (float)hupO.y);
-                    line2[2][hq] = make_float2((float)hupE.z, (float)hupO.z);
-                }
-            }
-            wave_sync();
-            V3 gE, gO;
-            gauss9_pair(line[0] + lane, gE.x, gO.x); gauss9_pair(line[1] + lane, gE.y, gO.y); gauss9_pair(line[2] + lane, gE.z, gO.z);
-            if (DUAL) {   // bloom_upsample_add: lower first, then upper
-                V3 uE, uO;
-                gauss9_pair(line2[0] + lane, uE.x, uO.x); gauss9_pair(line2[1] + lane, uE.y, uO.y); gauss9_pair(line2[2] + lane, uE.z, uO.z);
-                gE = gE + uE; gO = gO + uO;
-            }
-            wave_sync();
-            struct alignas(16) H8 { H4 a, b; } th;   // the H pass's fp16 store, both columns of the lane
-            th.a.x = to_half_rn(gE.x); th.a.y = to_half_rn(gE.y); th.a.z = to_half_rn(gE.z); th.a.w = alpha_t;
-            th.b.x = to_half_rn(gO.x); th.b.y = to_half_rn(gO.y); th.b.z = to_half_rn(gO.z); th.b.w = alpha_t;
-            *reinterpret_cast<H8*>(&sT[r0 + k][2 * lane]) = th;
-        }
-    }
-    TSTAMP(3);
-    __syncthreads();
-    TSTAMP(4);
-    // ---- V-gauss over a sliding window of the fp16 tile + tail
-    {
-        // (the compiler folds the window's fp16 -> fp32 converts into one v_fma_mix_f32 per tap; converting the window once and
-        //  tapping with plain FMAs — 4.5 + n x 2.7 against n x 4.6 issue cycles, DESIGN 4.7 — was measured: 216 fewer slow-class
-        //  instructions per thread and tile, the launch's time unchanged, profiles/r03_n_bloom_tail_experiments.md)
-        H4 win[PER_O + 8];
-#pragma unroll
-        for (int i = 0; i < PER_O + 8; i++) win[i] = sT[rbase + i][vc];
-#pragma unroll
-        for (int k = 0; k < PER_O; k++) {
-            const int y = y0 + rbase + k;
-            if (xv >= ow || y >= oh) continue;
-            V3 a3 = v3(0.0f, 0.0f, 0.0f);
-#pragma unroll
-            for (int i = 0; i < 9; i++) a3 = fma3(h3f(win[k + i]), c_gauss[i], a3);
-            const F4 a = f4(a3.x, a3.y, a3.z, alpha_v);
-            if (TAIL == 0) {
-                store_h4(out + 4 * ((size_t)y * out_pitch + xv), a);
-            } else {
-                if (!(in_mx && y >= tr.my0 && y < tr.my1)) continue;
-                // A0 texel as the separate V pass would have stored it (fp16), then the merge's fp16 sum
-                const half2v a01 = round_h2(a3.x, a3.y);
-                const h16 a2 = to_half_rn(a3.z);
-                const F4 s = h4f(hdr_in[k]);
-                struct alignas(8) O4 { half2v lo, hi; } o;
-                o.lo = round_h2(s.x + (float)a01.x, s.y + (float)a01.y);
-                o.hi = round_h2(s.z + (float)a2, s.w + a0w);
-                *reinterpret_cast<O4*>(hdr_row0 + k * hdr_pitch + hdr_x) = o;
-                if (TAIL == 2) {   // plain per-lane LDS atomics: wave-aggregating equal bins first (exposure.hip) costs more VALU here than it saves
-                    if (xv >= tr.hx0 && xv < tr.hx1 && y >= tr.hy0 && y < tr.hy1)
-                        atomicAdd(&sh_hist[wv][luminance_bin_exact((float)o.lo.x, (float)o.lo.y, (float)o.hi.x, min_log, inv_range)], 1u);
-                }
-            }
-        }
-    }
-    TSTAMP(5);
-    if (tile + (int)gridDim.x < n_tiles) __syncthreads();   // the next tile overwrites sT
-    TSTAMP(6);
-    }
-    if (TAIL == 2) {
-        __syncthreads();
-        for (int i = t; i < PBR_HISTOGRAM_BINS; i += NT) {
-            uint32_t sum = 0;
-#pragma unroll
-            for (int w2 = 0; w2 < NW; w2++) sum += sh_hist[w2][i];
-            if (sum) atomicAdd(&hist[i], sum);
-        }
-    }
-}
-#endif   // PBR_DEBUG_KNOBS (k_blur_up_wide)
-
-// ---------------------------------------------------------------- 2x-up levels, POLYPHASE form (round 4)
-// k_blur_up_wide evaluates what the shader evaluates: every one of the nine taps of a fine-grid output is a bilinear 2x-up
+// k_blur_up_poly: the passes of k_blur_hv<M_UP, ...> on 128 x TH tiles, one block (512 threads, 8 waves) per tile, rearranged so
+// that the 2x upsample costs little.  The shader evaluates every one of the nine taps of a fine-grid output as a bilinear 2x-up
 // sample of the coarse level (weights 1/4 | 3/4 in x and in y), 9 taps x (TH + 8) fine rows.  The upsample and the blur are both
 // linear and the upsample's weights are periodic, so the H blur of the upsampled row is two FIXED six-tap filters on the COARSE
 // row — even outputs 2p tap c[p-3 .. p+2], odd outputs 2p+1 tap c[p-2 .. p+3] (coefficients below) — and the y half of the
 // bilinear sample commutes with the H blur: filter the ~TH/2 + 6 coarse rows once, THEN blend neighbouring filtered rows with
 // 1/4 | 3/4 into the fine rows.  Per fine output and channel that is ~6 x 22/40 + 2 multiply-adds for the H pass instead of
-// 9 + the four of the bilinear sample, a lane loads ONE coarse texel per coarse row (k_blur_up_wide: three per row for its
-// column pair) and reads seven 8-byte LDS entries per coarse row instead of fifteen per fine row.
+// 9 + the four of the bilinear sample; a lane loads ONE coarse texel per coarse row and reads seven 8-byte LDS entries per coarse row.
+//   * DUAL: a lane owns the fine column PAIR (2p, 2p+1) of the same-size input's row, held in LDS as float2 pairs; its two outputs
+//     tap the five entries lane .. lane+4 (gauss9_pair).
+//   * V pass: a thread owns a column and TH/4 CONSECUTIVE rows, so the rows it taps overlap: TH/4 + 8 reads of the fp16 tile
+//     for TH/4 outputs instead of nine per output.
 // Not the shader's operation order, hence not bit-identical to the oracle: the fp32 value in front of the H pass's fp16 store
 // differs by a few fp32 ulps, i.e. the stored fp16 texel differs by one fp16 ULP on ~5e-5 of the texels (SURVEY 8c allows <= 1
 // fp16 ULP per bloom stage; tests/test_gpu_parity.py holds every stage to that and the whole chain to <= 2).  The sum is rounded to
-// fp16 exactly where bloom_upsample_add / blur_horizontal store it, the V pass and the tail are k_blur_up_wide's, unchanged.
+// fp16 exactly where bloom_upsample_add / blur_horizontal store it; the V pass and the tail take k_blur_hv's operation order.
 // Clamp addressing: a tap outside the coarse level reads the edge texel — the same linear map as the shader's clamp of the
 // sample position (every fine position outside the level samples the pure edge texel either way).
 namespace poly {
@@ -907,7 +675,7 @@ __global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restr
     constexpr int PER_O = TH / 4;                     // V outputs per thread: column t & 127, rows (t >> 7) * PER_O ..
     static_assert(TH % 4 == 0 && (PPW + 1) * 6 <= 64 && 2 * PPW * 4 <= 64, "one halo entry per lane");
     __shared__ H4 sLineC[NW][NC + 2];                 // one coarse row per wave at a time: entry e = coarse column x0 / 2 - 3 + e
-    __shared__ float2 sLineU[DUAL ? NW : 1][3][NP];   // DUAL: the same-size input's fine row as column pairs (k_blur_up_wide's line)
+    __shared__ float2 sLineU[DUAL ? NW : 1][3][NP];   // DUAL: the same-size input's fine row as column pairs (gauss9_pair)
     __shared__ H4 sT[SR][TW];
     __shared__ uint32_t sh_hist[TAIL == 2 ? NW : 1][TAIL == 2 ? PBR_HISTOGRAM_BINS : 1];
     // two blocks (2 x 8 waves = the 4 waves per SIMD of the launch bounds) must fit a CU's 160 KiB of LDS: an instantiation that does not
@@ -1035,7 +803,7 @@ __global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restr
         }
     }
     __syncthreads();
-    // ---- V-gauss over a sliding window of the fp16 tile + tail (k_blur_up_wide's)
+    // ---- V-gauss over a sliding window of the fp16 tile + tail (k_blur_hv's operation order)
     {
         H4 win[PER_O + 8];
 #pragma unroll
@@ -1089,7 +857,6 @@ static int blur_h_rows(uint32_t ow, uint32_t oh) {
 // fast-path preconditions: the level below is exactly half, and the size keeps every snapped sample coordinate
 // on its dyadic value (coordinate error ~4 * 2^-24 * size must stay below half a 1/256 step)
 static bool exact_half(uint32_t n) { return (n & 1u) == 0u && n <= 8192u; }
-static bool force_staged() { static const bool v = pbr::knob_set("PBR_BLOOM_STAGED"); return v; }   // A/B switch (knobs build only)
 
 template <int MODE, bool DUAL, int TAIL>
 static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint32_t ih, const pbr_half* in2,
@@ -1109,38 +876,19 @@ static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint3
     static const int hist_blocks = pbr::knob_int("PBR_BLOOM_HIST_BLOCKS", 1024);
     auto even_blocks = [](int n_tiles) { const int per = (n_tiles + hist_blocks - 1) / hist_blocks; return (n_tiles + per - 1) / per; };
     if constexpr (MODE == M_UP) {
-        // 2x-up levels big enough to fill the chip with 128 x 32 tiles: the two-columns-per-lane kernel (PBR_BLOOM_WIDE=0|1 forces)
+        // 2x-up levels big enough to fill the chip with 128 x 32 tiles: k_blur_up_poly, two columns per lane (PBR_BLOOM_WIDE=0|1 forces)
         static const int wide_forced = pbr::knob_int("PBR_BLOOM_WIDE", -1);
-#ifdef PBR_DEBUG_KNOBS
-        static const int wide_th = pbr::knob_int("PBR_BLOOM_WIDE_TH", 32);   // experiment (knobs build): 128 x 16 tiles at 6 waves per SIMD — 53.4 us against 49.2
-#endif
         const int wtx0 = tr.mx0 / 128, wty0 = tr.my0 / 32;
         const int wtiles_x = (tr.mx1 + 127) / 128 - wtx0, wn = wtiles_x * ((tr.my1 + 31) / 32 - wty0);
         if (wide_forced >= 0 ? wide_forced == 1 : (wn >= 400 && !ctx->bloom_shader_order)) {
             tr.tx0 = wtx0; tr.ty0 = wty0;
-#ifdef PBR_DEBUG_KNOBS   // the shader-order (bit-identical) kernel of round 3: A/B partner and checker, PBR_BLOOM_POLY=0
-            static const bool poly_off = pbr::knob_int("PBR_BLOOM_POLY", 1) == 0;
-            if (poly_off && wide_th == 16) {
-                tr.ty0 = tr.my0 / 16;
-                const int wn16 = wtiles_x * ((tr.my1 + 15) / 16 - tr.ty0);
-                hipLaunchKernelGGL((k_blur_up_wide<DUAL, TAIL, 16>), dim3(TAIL == 2 ? even_blocks(wn16) : wn16), dim3(512), 0, ctx->stream,
-                                   in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, wtiles_x, wn16, tr, min_log, inv_range, hist);
-                return launched(ctx, "k_blur_up_wide<16>");
-            }
-            if (poly_off) {
-                hipLaunchKernelGGL((k_blur_up_wide<DUAL, TAIL, 32>), dim3(TAIL == 2 ? even_blocks(wn) : wn), dim3(512), 0, ctx->stream,
-                                   in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, wtiles_x, wn, tr, min_log, inv_range, hist);
-                return launched(ctx, "k_blur_up_wide");
-            }
-#endif
             hipLaunchKernelGGL((k_blur_up_poly<DUAL, TAIL, 32>), dim3(TAIL == 2 ? even_blocks(wn) : wn), dim3(512), 0, ctx->stream,
                                in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, wtiles_x, wn, tr, min_log, inv_range, hist);
             return launched(ctx, "k_blur_up_poly");
         }
     }
-    // 64 x 32 tiles (512 threads) when the level is large enough to fill the chip that way, 64 x 16 below (PBR_BLOOM_TILE=16: on 4 waves)
-    static const int forced = pbr::knob_int("PBR_BLOOM_TILE", 0);
-    const bool big = forced ? forced == 32 : (uint64_t)((tr.mx1 + 63) / 64 - tr.mx0 / 64) * ((tr.my1 + 31) / 32 - tr.my0 / 32) >= 900;
+    // 64 x 32 tiles (512 threads) when the level is large enough to fill the chip that way, 64 x 16 below
+    const bool big = (uint64_t)((tr.mx1 + 63) / 64 - tr.mx0 / 64) * ((tr.my1 + 31) / 32 - tr.my0 / 32) >= 900;
     // tiles that intersect the merge rect (TAIL 0 has no rect: every tile of the level)
     const int th = big ? 32 : 16;
     tr.tx0 = tr.mx0 / 64; tr.ty0 = tr.my0 / th;
@@ -1150,13 +898,10 @@ static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint3
     if (big) {
         hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 32, 512>), dim3(blocks), dim3(512), 0, ctx->stream,
                            in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, hist);
-    } else if (forced != 16) {
+    } else {
         // small levels are latency-bound (one tile's dependent chain + the launch): 64 x 16 tiles on EIGHT waves — 3 H rows per
         // wave, 2 outputs per thread — shorten the chain; the five small launches of a 4K frame take ~5 us less together
         hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 16, 512>), dim3(blocks), dim3(512), 0, ctx->stream,
-                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, hist);
-    } else {
-        hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 16, 256>), dim3(blocks), dim3(256), 0, ctx->stream,
                            in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, hist);
     }
     return launched(ctx, "k_blur_hv");
@@ -1169,7 +914,7 @@ static pbr_status prefilter_launch(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w
                                    pbr_half* out, const OutRect* rcs, int n, float threshold, float knee) {
     const uint32_t ow = w >> 1, oh = h >> 1;
     const float tx = 1.0f / (float)ow, ty = 1.0f / (float)oh;   // DeferredPipeline.cpp:418
-    if (exact_half(w) && exact_half(h) && !force_staged()) {   // shared-sample kernel (bit-identical), all rectangles in one launch
+    if (exact_half(w) && exact_half(h)) {   // shared-sample kernel (bit-identical), all rectangles in one launch
         OutRects rs{};
         rs.n = n; rs.ox = rcs[0].ox; rs.oy = rcs[0].oy; rs.pitch = rcs[0].pitch;
         int blocks = 0;
@@ -1277,7 +1022,6 @@ pbr_status pbr_bloom_up_level(pbr_ctx* ctx, const pbr_half* upper, const pbr_hal
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, lower && out && out != lower && out != upper, "pbr_bloom_up_level: null pointer / out aliases an input");
     PBR_REQUIRE(ctx, lw >= 1 && lh >= 1 && ow == 2 * lw && oh == 2 * lh && exact_half(ow) && exact_half(oh), "pbr_bloom_up_level: out must be exactly twice lower, even, <= 8192");
-    if (force_staged()) return pbr::fail(ctx, PBR_ERR_UNSUPPORTED, "pbr_bloom_up_level: PBR_BLOOM_STAGED is set");
     if (upper) return launch_hv<M_UP, true, 0>(ctx, lower, lw, lh, upper, out, ow, oh, ow, nullptr, 0.0f, 0.0f, nullptr);
     return launch_hv<M_UP, false, 0>(ctx, lower, lw, lh, nullptr, out, ow, oh, ow, nullptr, 0.0f, 0.0f, nullptr);
 }
@@ -1316,7 +1060,7 @@ static pbr_status bloom_pyramid(pbr_ctx* ctx, uint32_t w, uint32_t h, pbr_half* 
     // staged kernels run.  1920x1080, for instance, is exact down to 240x135 and staged for 135 -> 67.  Fused up-levels
     // write chain B (a block must not overwrite what its neighbours still read), so `res` tracks where the finished
     // level below lives.  Chain contents after the call are scratch.
-    auto exact = [&](uint32_t l) { return !force_staged() && exact_half(W(l)) && exact_half(H(l)); };
+    auto exact = [&](uint32_t l) { return exact_half(W(l)) && exact_half(H(l)); };
     for (uint32_t i = 0; i < PBR_BLOOM_STEP; i++) {   // downsample
         const uint32_t up = i + 1, lo = i + 2;
         if (exact(up)) {
@@ -1368,7 +1112,7 @@ static pbr_status bloom_impl(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h
     if ((r = pbr_bloom_prefilter(ctx, hdr, w, h, pitch, A + 4 * pbr_bloom_level_offset(w, h, 1), threshold, knee))) return r;
     const pbr_half* res = nullptr;
     if ((r = bloom_pyramid(ctx, w, h, A, B, &res))) return r;
-    if (!force_staged() && exact_half(w) && exact_half(h)) {   // H + V + merge (+ histogram) in one kernel
+    if (exact_half(w) && exact_half(h)) {   // H + V + merge (+ histogram) in one kernel
         if (hist256) return launch_hv<M_UP, false, 2>(ctx, res, w >> 1, h >> 1, nullptr, hdr, w, h, pitch, hist_rect, min_log, inv_range, hist256);
         return launch_hv<M_UP, false, 1>(ctx, res, w >> 1, h >> 1, nullptr, hdr, w, h, pitch, nullptr, 0.0f, 0.0f, nullptr);
     }
@@ -1411,7 +1155,7 @@ pbr_status pbr_bloom_tiled(pbr_ctx* ctx, pbr_half* hdr, uint32_t hdr_pitch, cons
     PBR_REQUIRE(ctx, merge_rect[2] >= 1 && merge_rect[3] >= 1 && merge_rect[0] >= hdr_rect[0] && merge_rect[1] >= hdr_rect[1] &&
                      merge_rect[0] + merge_rect[2] <= hdr_rect[0] + hdr_rect[2] && merge_rect[1] + merge_rect[3] <= hdr_rect[1] + hdr_rect[3],
                 "pbr_bloom_tiled: merge_rect outside hdr_rect");
-    if (force_staged() || !exact_half(ew) || !exact_half(eh))
+    if (!exact_half(ew) || !exact_half(eh))
         return pbr::fail(ctx, PBR_ERR_UNSUPPORTED, "pbr_bloom_tiled: the extended tile must be even and <= 8192 on a side");
     const pbr_half* res = nullptr;
     pbr_status r;

@@ -33,7 +33,7 @@ __device__ __forceinline__ float fma_sat(float a, float b, float c) {
     asm("v_fma_f32 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-// The sample loop of one LUT texel.  Same estimator as IntegrateBRDF (brdf.hlsli:137-167 — restated in oracle/pbr_oracle.cpp
+// The sample loop of one LUT texel.  Same estimator as IntegrateBRDF (precompute_brdf.hlsl:20-62 — restated in oracle/pbr_oracle.cpp
 // orc_brdf_lut), arranged for what gfx950 issues fast (fp32 mul / add / fma ~2.7 cycles per wave, v_max / v_min ~4.6,
 // transcendentals 8.5); each step stays within a few 1e-7 relative of the shader's expression, three orders below the fp16
 // rounding of the result (every texel within 1 fp16 ULP of the oracle: tests/test_gpu_parity.py):
@@ -196,44 +196,21 @@ __global__ __launch_bounds__(256) void k_prefilter_env(const float* __restrict__
     prefilter_block(tab, sky, sky_size, sky_mips, size, s, roughness, out, blockIdx.x);
 }
 
-#ifdef PBR_DEBUG_KNOBS   // measured alternative of round 1 (PBR_PREFILTER_SEQ=1): only the knobs build carries it
-// All mips in ONE launch.  A thread walks its 1 024 samples one after the other (the reference's running sum), so a
-// dispatch lasts as long as that serial chain whatever the mip's size — five dispatches in a row cost five chains
-// with a mostly idle chip (mip 4 is 96 waves).  Run together the mips overlap: blocks are ordered mip 1, 2, ..,
-// mips-1, then mip 0 (roughness 0: one fetch per texel) so the long chains start first.  Same arithmetic per texel.
-__global__ __launch_bounds__(256) void k_prefilter_env_all(const float* __restrict__ sky, uint32_t sky_size, uint32_t sky_mips,
-                                                             uint32_t size, uint32_t mips, pbr_half* __restrict__ out) {
-    __shared__ float4 tab[PBR_SAMPLE_COUNT];
-    uint32_t b = blockIdx.x, mip = 0;
-    for (uint32_t k = 0; k < mips; k++) {
-        const uint32_t m = (k + 1 < mips) ? k + 1 : 0;   // order 1, 2, .., mips-1, 0
-        const uint32_t sm = size >> m;
-        const uint32_t nb = (uint32_t)(((size_t)6 * sm * sm + 255) / 256);
-        if (b < nb) { mip = m; break; }
-        b -= nb;
-    }
-    const float roughness = mips > 1 ? (float)mip / (float)(mips - 1) : 0.0f;   // DeferredPipeline.cpp:99
-    prefilter_block(tab, sky, sky_size, sky_mips, size, size >> mip, roughness, out + 4 * cube_mip_offset(size, mip), b);
-}
-#endif
-
-// ---------------------------------------------------------------------------- wave-parallel prefilter (pbr_prefilter_env)
-// The same integral, mapped the way the hardware likes it:
-//  * ONE WAVE PER OUTPUT TEXEL: the 64 lanes take the texel's samples 64 at a time (<= 16 trips instead of a 1 024-step
-//    dependent chain), keep per-lane partial sums and combine them with a fixed xor-shuffle tree — deterministic, but
-//    not the shader's strictly sequential fp32 sum (SURVEY 8c allows <= 1 fp16 ULP or 1e-3 for this output; the
-//    sequential kernel above remains what pbr_prefilter_env_mip runs, one reference dispatch at a time).  N, T, B of the
-//    texel are wave-uniform.  mip 4 is 6 144 waves instead of 96.
+// ---------------------------------------------------------------------------- table-driven prefilter (pbr_prefilter_env)
+// The same integral, mapped the way the hardware likes it (pbr_prefilter_env_mip keeps the sequential kernel above, one
+// reference dispatch at a time):
+//  * ONE LANE PER OUTPUT TEXEL: the 64 lanes of a wave are 64 neighbouring texels and all of them take sample j at the same
+//    time.  Neighbouring texels reflect the same tangent-space direction into neighbouring source positions, so a wave's
+//    fetches of one sample fall into a few cache lines (a wave per texel scatters over the whole lobe: 2.4x slower, EXPERIMENTS.md).
+//    The sum runs in sample order like the shader's.
 //  * the sample set of a mip is a TABLE built on the host with the oracle's own libm calls: with V = N the half vector
 //    in tangent space depends only on (i, roughness), and so do the reflected direction L_t = (2 hz hx, 2 hz hy,
 //    2 hz^2 - 1), the weight N.L = L_t.z and the source LOD.  Samples with N.L <= 0 are dropped when the table is built
 //    (a quarter of them at roughness 0.75, half at 1) and the weight sum is one number per mip.  The loop keeps no
 //    normalize, no sqrt, no log2: L = T lx + B ly + N lz.
-//  * the source cube is sampled from a PADDED copy (every face of every mip with the 1-texel border the seamless rule
-//    selects, like the shade's env chain): the trilinear fetch is branch-free, 8 x 16-byte loads per sample.
-//  * roughness 0 (mip 0) degenerates to one bilinear fetch per texel: its own thread-per-texel kernel.
-constexpr int PF_TEXELS_PER_WAVE = 8;
-constexpr int PF_TEXELS_PER_BLOCK = 4 * PF_TEXELS_PER_WAVE;
+//  * the source cube is sampled from PADDED copies (every face of every mip with the 1-texel border the seamless rule
+//    selects, like the shade's env chain, k_cube_pad_chain): the fetch is branch-free.
+//  * roughness 0 (mip 0) degenerates to one bilinear fetch per texel: its own thread-per-texel kernel, k_prefilter_mip0.
 struct PfLaunch {
     uint32_t first_block[17];   // first block of output mip m (m = 1 .. mips-1), [mips] = total
     uint32_t count[16];         // valid samples of mip m
@@ -272,93 +249,12 @@ __device__ __forceinline__ V3 padded_trilinear(const float4* __restrict__ sky, c
     return v3(__builtin_fmaf(b.x, f, a.x * w0), __builtin_fmaf(b.y, f, a.y * w0), __builtin_fmaf(b.z, f, a.z * w0));
 }
 
-#ifdef PBR_DEBUG_KNOBS   // the wave-per-texel mapping: only the knobs build can select it (PBR_PREFILTER_WAVE=1); measured 2.4x slower than lane-per-texel
-__global__ __launch_bounds__(256) void k_prefilter_fast(const float4* __restrict__ sky_padded, const float4* __restrict__ tables,
-                                                          PfLaunch pl, pbr_half* __restrict__ out) {
-    __shared__ float4 tab[PBR_SAMPLE_COUNT];
-    uint32_t mip = 1;
-    while (mip + 1 < pl.mips && blockIdx.x >= pl.first_block[mip + 1]) mip++;
-    const uint32_t count = pl.count[mip];
-    for (uint32_t i = threadIdx.x; i < count; i += 256) tab[i] = tables[(size_t)mip * PBR_SAMPLE_COUNT + i];
-    __syncthreads();
-    const uint32_t s = pl.size >> mip;
-    const uint32_t n = 6u * s * s;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x - pl.first_block[mip]) * 4u + (threadIdx.x >> 6));
-    pbr_half* out_mip = out + 4 * cube_mip_offset(pl.size, mip);
-    for (uint32_t k = 0; k < (uint32_t)PF_TEXELS_PER_WAVE; k++) {
-        const uint32_t t = wave * PF_TEXELS_PER_WAVE + k;
-        if (t >= n) break;
-        const uint32_t x = t % s, y = (t / s) % s, face = t / (s * s);
-        const float u = (float)x / (float)s, v = (float)y / (float)s;   // texel corner (Q8)
-        const V3 N = normalize3_exact(cube_dir_raw(face, 2.0f * u - 1.0f, 2.0f * v - 1.0f));
-        const V3 up = fabsf(N.z) < 0.999f ? v3(0.0f, 0.0f, 1.0f) : v3(1.0f, 0.0f, 0.0f);
-        const V3 T = normalize3_exact(cross3(N, up));
-        const V3 Bt = cross3(N, T);
-        float cr = 0.0f, cg = 0.0f, cb = 0.0f;
-        for (uint32_t j = lane; j < count; j += 64u) {
-            const float4 e = tab[j];
-            const V3 L = T * e.x + Bt * e.y + N * e.z;
-            const V3 c = padded_trilinear(sky_padded, pl, L, e.w);
-            cr += c.x * e.z; cg += c.y * e.z; cb += c.z * e.z;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {   // fixed combine order
-            cr += __shfl_xor(cr, off, 64); cg += __shfl_xor(cg, off, 64); cb += __shfl_xor(cb, off, 64);
-        }
-        if (lane == 0) {
-            const float w = pl.wsum[mip];   // 0 samples -> 0/0 = NaN like the reference
-            store_h4(out_mip + 4 * (size_t)t, f4(cr / w, cg / w, cb / w, 1.0f));
-        }
-    }
-}
-#endif
-
-#ifdef PBR_DEBUG_KNOBS
-// The same table-driven, branch-free inner loop with the OTHER mapping: one lane per output texel, the 64 lanes of a
-// wave are 64 neighbouring texels and all of them take sample j at the same time.  Neighbouring texels reflect the same
-// tangent-space direction into neighbouring source positions, so a wave's 8 x 64 texel fetches fall into a few dozen
-// cache lines (measured: 2.4x faster than the wave-per-texel mapping, whose 64 lanes scatter over the whole lobe and
-// pull ~256 lines per trip through a 32 KB L1).  The sum runs in sample order like the shader's.  This is what
-// pbr_prefilter_env launches; k_prefilter_fast stays selectable (PBR_PREFILTER_WAVE=1) as the measured alternative.
-// Round-2 kernel, superseded by k_prefilter_foot<false>: only the knobs build carries it (PBR_PREFILTER_F32=1), as the measured A/B partner.
-__global__ __launch_bounds__(256) void k_prefilter_tex(const float4* __restrict__ sky_padded, const float4* __restrict__ tables,
-                                                         PfLaunch pl, pbr_half* __restrict__ out) {
-    __shared__ float4 tab[PBR_SAMPLE_COUNT];
-    uint32_t mip = 1;
-    while (mip + 1 < pl.mips && blockIdx.x >= pl.first_block[mip + 1]) mip++;
-    const uint32_t count = pl.count[mip];
-    for (uint32_t i = threadIdx.x; i < count; i += 256) tab[i] = tables[(size_t)mip * PBR_SAMPLE_COUNT + i];
-    __syncthreads();
-    const uint32_t s = pl.size >> mip;
-    const uint32_t n = 6u * s * s;
-    const uint32_t t = (blockIdx.x - pl.first_block[mip]) * 256u + threadIdx.x;
-    if (t >= n) return;
-    const uint32_t x = t % s, y = (t / s) % s, face = t / (s * s);
-    const float u = (float)x / (float)s, v = (float)y / (float)s;   // texel corner (Q8)
-    const V3 N = normalize3_exact(cube_dir_raw(face, 2.0f * u - 1.0f, 2.0f * v - 1.0f));
-    const V3 up = fabsf(N.z) < 0.999f ? v3(0.0f, 0.0f, 1.0f) : v3(1.0f, 0.0f, 0.0f);
-    const V3 T = normalize3_exact(cross3(N, up));
-    const V3 Bt = cross3(N, T);
-    float cr = 0.0f, cg = 0.0f, cb = 0.0f;
-#pragma unroll 2
-    for (uint32_t j = 0; j < count; j++) {
-        const float4 e = tab[j];   // wave-uniform: one broadcast LDS read
-        const V3 L = T * e.x + Bt * e.y + N * e.z;
-        const V3 c = padded_trilinear(sky_padded, pl, L, e.w);
-        cr += c.x * e.z; cg += c.y * e.z; cb += c.z * e.z;
-    }
-    const float w = pl.wsum[mip];   // 0 samples -> 0/0 = NaN like the reference
-    store_h4(out + 4 * (cube_mip_offset(pl.size, mip) + (size_t)t), f4(cr / w, cg / w, cb / w, 1.0f));
-}
-#endif
-
-// ---- the same table-driven, texel-per-lane loop on a HALF-precision padded copy of the source chain (what pbr_prefilter_env
-// launches for mips >= 1).  Counters of k_prefilter_tex (profiles/r03_*): VALU busy ~100 % (168 instructions per sample) AND
-// the texture addresser 74 % busy — eight 16-byte gathers per lane and sample move 128 B through a 64 B / clk path.  Here:
+// ---- k_prefilter_foot: the table-driven, texel-per-lane loop for mips >= 1, on a HALF-precision padded copy of the source chain
+// when that copy is exact and on the padded fp32 chain otherwise.  A trilinear sample of the fp32 chain is eight 16-byte gathers
+// per lane (128 B through the texture addresser's 64 B / clk path: round 3 measured it 74 % busy beside ~100 % VALU); here:
 //  * the source chain is copied once per call as half4 with its seam borders (k_cube_pad_chain): a trilinear sample is FOUR
 //    16-byte loads = 64 B.  The copy is used ONLY WHEN IT IS EXACT: k_cube_pad_chain raises a flag when any texel does not
-//    survive the conversion bit for bit, and then this kernel returns at once and k_prefilter_tex (fp32 chain) does the work —
+//    survive the conversion bit for bit, and then the HALF instance returns at once and the fp32 instance does the work —
 //    decided on the device, no host round trip.  The reference's sky textures are BC6H_UF16 on disk (BasicStorage.h:10-11,
 //    TextureCompression.cpp:95-110): every texel of every mip it can feed this pass IS a half value, so its inputs take this
 //    path; an arbitrary fp32 cube keeps the fp32 path and its result.
@@ -825,16 +721,6 @@ pbr_status pbr_prefilter_env(pbr_ctx* ctx, const pbr_cube_f32* sky, uint32_t siz
     PBR_REQUIRE(ctx, size >= 1 && mips >= 1 && mips <= 16 && (size >> (mips - 1)) >= 1, "pbr_prefilter_env: bad output size/mips");
     PBR_REQUIRE(ctx, sky && sky->data && sky->size >= 1 && sky->mips >= 1 && (sky->size >> (sky->mips - 1)) >= 1, "pbr_prefilter_env: bad sky cube");
     PBR_REQUIRE(ctx, size <= 8192, "pbr_prefilter_env: bad output size/mips");
-#ifdef PBR_DEBUG_KNOBS
-    static const bool sequential = pbr::knob_set("PBR_PREFILTER_SEQ");   // A/B switch: the thread-per-texel kernel, all mips in one launch
-    if (sequential) {
-        size_t blocks = 0;
-        for (uint32_t m = 0; m < mips; m++) blocks += ((size_t)6 * (size >> m) * (size >> m) + 255) / 256;
-        PBR_REQUIRE(ctx, blocks <= 0x7FFFFFFFull, "pbr_prefilter_env: cube too large");
-        hipLaunchKernelGGL(k_prefilter_env_all, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sky->data, sky->size, sky->mips, size, mips, out);
-        return launched(ctx, "k_prefilter_env_all");
-    }
-#endif
     // ---- padded source chain (stream-ordered scratch) + per-mip sample tables (kept on the device)
     PfLaunch pl{};
     pl.mips = mips; pl.size = size; pl.sky_size = sky->size; pl.sky_mips = sky->mips;
@@ -846,15 +732,6 @@ pbr_status pbr_prefilter_env(pbr_ctx* ctx, const pbr_cube_f32* sky, uint32_t siz
     // the kernels address the padded chains with 32-bit byte offsets: sky cubes up to 4096^2 with a full mip chain (2.1 GiB padded);
     // larger ones go through pbr_prefilter_env_mip, one reference dispatch at a time
     PBR_REQUIRE(ctx, padded_texels * 16u < (1ull << 32), "pbr_prefilter_env: sky cube too large (padded fp32 chain must stay below 4 GiB; use pbr_prefilter_env_mip)");
-    // which kernel samples mips >= 1: k_prefilter_foot on the half / fp32 padded chains.  Knobs build only: PBR_PREFILTER_WAVE=1 (the
-    // wave-per-texel mapping) and PBR_PREFILTER_F32=1 (the round-2 kernel on the padded fp32 chain) stay selectable as A/B partners
-    bool wave_per_texel = false, force_f32 = false;
-#ifdef PBR_DEBUG_KNOBS
-    static const bool k_wave = pbr::knob_set("PBR_PREFILTER_WAVE"), k_f32 = pbr::knob_set("PBR_PREFILTER_F32");
-    wave_per_texel = k_wave; force_f32 = k_f32 && !k_wave;
-#endif
-    const bool use_foot = !force_f32 && !wave_per_texel;
-    const uint32_t per_block = wave_per_texel ? (uint32_t)PF_TEXELS_PER_BLOCK : use_foot ? PF_FOOT_BLOCK : 256u;
     // The sample tables depend on (size, mips, sky mips) only: built on the host and uploaded when that key changes, then reused
     // (a renderer prefilters the same shapes again and again; the build is ~0.1 ms of libm and the upload a blocking copy).  A new key
     // takes a NEW device buffer — hipFree of the old one waits for whatever still reads it, whichever stream that is on.
@@ -879,7 +756,7 @@ pbr_status pbr_prefilter_env(pbr_ctx* ctx, const pbr_cube_f32* sky, uint32_t siz
         pl.wsum[m] = ctx->pf_wsum[m];
         pl.first_block[m] = blocks;
         const uint32_t sm = size >> m;
-        blocks += (6u * sm * sm + per_block - 1) / per_block;
+        blocks += (6u * sm * sm + PF_FOOT_BLOCK - 1) / PF_FOOT_BLOCK;
     }
     pl.first_block[mips] = blocks;
     const size_t foot_texels = padded_texels + 1;   // the half4 copy has the padded fp32 chain's layout (+ 1: the last row pair reads 8 bytes past a texel)
@@ -887,10 +764,10 @@ pbr_status pbr_prefilter_env(pbr_ctx* ctx, const pbr_cube_f32* sky, uint32_t siz
     // belongs to the CALL (round 3 kept one per context behind the cached tables: two calls of one context on different streams
     // could race on it — ADVICE r03); it is zeroed in stream order in front of the kernel that raises it.
     char* block = nullptr;
-    PBR_HIP(ctx, hipMallocAsync((void**)&block, 16 + padded_texels * 16 + (use_foot ? foot_texels * 8 : 0), ctx->stream));
+    PBR_HIP(ctx, hipMallocAsync((void**)&block, 16 + padded_texels * 16 + foot_texels * 8, ctx->stream));
     uint32_t* lossy = reinterpret_cast<uint32_t*>(block);   // 1 = the half copy is not exact
     float4* padded = reinterpret_cast<float4*>(block + 16);
-    pbr_half* foot = use_foot ? reinterpret_cast<pbr_half*>(padded + padded_texels) : nullptr;
+    pbr_half* foot = reinterpret_cast<pbr_half*>(padded + padded_texels);
     pbr_status r = PBR_OK;
     {
         const hipError_t e = hipMemsetAsync(lossy, 0, 16, ctx->stream);
@@ -914,18 +791,13 @@ pbr_status pbr_prefilter_env(pbr_ctx* ctx, const pbr_cube_f32* sky, uint32_t siz
         hipLaunchKernelGGL(k_cube_pad_chain, dim3((unsigned)pad_blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(sky->data), padded, foot, pp, lossy);
         r = launched(ctx, "k_cube_pad_chain");
     }
-    if (r == PBR_OK && blocks) {
-#ifdef PBR_DEBUG_KNOBS
-        if (wave_per_texel) hipLaunchKernelGGL(k_prefilter_fast, dim3(blocks), dim3(256), 0, ctx->stream, padded, tables, pl, out);
-        else if (force_f32) hipLaunchKernelGGL(k_prefilter_tex, dim3(blocks), dim3(256), 0, ctx->stream, padded, tables, pl, out);
-        else
-#endif
-        {   // both instances; the flag k_cube_pad_chain wrote picks the one that works, the other returns at once
-            hipLaunchKernelGGL(k_prefilter_foot<true>, dim3(blocks), dim3(PF_FOOT_BLOCK), 0, ctx->stream, (const void*)foot, fo, tables, pl, out, lossy);
-            r = launched(ctx, "k_prefilter_foot<half>");
-            if (r == PBR_OK) hipLaunchKernelGGL(k_prefilter_foot<false>, dim3(blocks), dim3(PF_FOOT_BLOCK), 0, ctx->stream, (const void*)padded, fo, tables, pl, out, lossy);
+    if (r == PBR_OK && blocks) {   // both instances; the flag k_cube_pad_chain wrote picks the one that works, the other returns at once
+        hipLaunchKernelGGL(k_prefilter_foot<true>, dim3(blocks), dim3(PF_FOOT_BLOCK), 0, ctx->stream, (const void*)foot, fo, tables, pl, out, lossy);
+        r = launched(ctx, "k_prefilter_foot<half>");
+        if (r == PBR_OK) {
+            hipLaunchKernelGGL(k_prefilter_foot<false>, dim3(blocks), dim3(PF_FOOT_BLOCK), 0, ctx->stream, (const void*)padded, fo, tables, pl, out, lossy);
+            r = launched(ctx, "k_prefilter_foot<f32>");
         }
-        if (r == PBR_OK) r = launched(ctx, "k_prefilter_*");
     }
     if (r == PBR_OK) {
         const size_t n0 = (size_t)6 * size * size;

@@ -583,7 +583,6 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
         const int n_cl = min(tiles_x * (tile_y1 - tile_y0 + 1) * PBR_CLUSTER_Z, max_clusters);   // host sized the LDS for the worst case
         {
             static_assert(PBR_CLUSTER_Z == 8 && PBR_MAX_LIGHTS_PER_CLUSTER == 32, "staging map");
-#ifndef PBR_EXP_STAGE_R5   // (round 5's form below: a thread per entry, n_cl / 8 rounds of ~40 instructions; kept for A/B builds)
             // A thread owns FOUR consecutive entries of cluster (tid >> 3) + 32 k: one 16-byte load of indices per thread and round,
             // n_cl / 32 rounds.  The prologue is instruction issue, not latency: a new block's waves share their SIMDs with four blocks in
             // the middle of their pixel work, and ~700 prologue instructions per thread were 6 % of a 256-light block's work, 15 % of a
@@ -608,20 +607,6 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
                 }
                 if (part == 0) *reinterpret_cast<uint2*>(l) = make_uint2((uint32_t)max((cnt + 1) & ~1, 2), 0u);
             }
-#else
-            // a thread owns entry (tid & 31) of cluster (tid >> 5) + 8 k: no division by the list stride, one index load per entry (round 5)
-            const int j = threadIdx.x & 31;
-            for (int c = threadIdx.x >> 5; c < n_cl; c += SHADE_BLOCK / 32) {
-                const int z = c & 7, t = c >> 3;
-                const int ty_ = t / tiles_x, cx = tile_x0 + (t - ty_ * tiles_x), cy = tile_y0 + ty_;
-                const pbr_cluster* cl = p.clusters + (z + cx * PBR_CLUSTER_Z + cy * PBR_CLUSTER_X * PBR_CLUSTER_Z);
-                const int cnt = n_lights > 0 ? min(max(cl->NumLights, 0), PBR_MAX_LIGHTS_PER_CLUSTER) : 0;
-                uint32_t* l = lists + c * LIST_STRIDE;
-                const int li = j < cnt ? min(max(cl->LightIndex[j], 0), n_lights - 1) : n_lights;   // never index past the staged table
-                l[2 + j] = lds_base + 4u * (uint32_t)li;
-                if (j < 2) l[j] = j == 0 ? (uint32_t)max((cnt + 1) & ~1, 2) : 0u;
-            }
-#endif
         }
     }
     // per-row terms of the block's <= SHADE_ROWS rows (vs_main :91-95, ClusterIndex clustered.hlsli:47): {v, cvv.y, cluster row}
@@ -757,10 +742,7 @@ static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile
     const bool staged = span_x * span_y <= (uint32_t)MAX_STAGED_TILES &&   // (no lights at all: every list is one null pair)
                         plane_bytes + (size_t)span_x * span_y * PBR_CLUSTER_Z * LIST_STRIDE * sizeof(uint32_t) <= 65536;
     const int max_clusters = staged ? (int)(span_x * span_y) * PBR_CLUSTER_Z : 0;
-    // (PBR_SHADE_LDS_PAD, knobs build: KiB of LDS a block asks for beyond its tables — 18 caps a compute unit at four 96-register blocks and leaves
-    //  128 registers per SIMD + 28 KiB of LDS free: the hole of the round-6 co-residency experiment, EXPERIMENTS.md)
-    static const size_t lds_pad = (size_t)pbr::knob_int("PBR_SHADE_LDS_PAD", 0) * 1024;
-    const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t) + (lds_pad <= 40960 ? lds_pad : 0);
+    const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t);
     const dim3 blk(SHADE_BLOCK);
     if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc);
     else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc);

@@ -1,8 +1,16 @@
 """Shared deterministic test scenes (inputs are regenerated from seeds; goldens hold outputs only)."""
+import contextlib
+import os
+import subprocess
+import sys
+
 import numpy as np
 
 from direct12pbrrenderer_amd import scene, synth
 from direct12pbrrenderer_amd.structs import Tile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KNOBS_LIB = os.path.join(ROOT, "direct12pbrrenderer_amd", "libpbr_hip_knobs.so")
 
 SKY_SIZE = 16
 SKY_MIPS = 5
@@ -13,9 +21,36 @@ LUT_RES = 32
 
 def host_lib_path():
     """libpbr_host.so; PBR_TEST_HOST_LIB points the CPU tests at the sanitizer build (tools/asan_cpu.sh)."""
-    import os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    return os.environ.get("PBR_TEST_HOST_LIB") or os.path.join(root, "direct12pbrrenderer_amd", "libpbr_host.so")
+    return os.environ.get("PBR_TEST_HOST_LIB") or os.path.join(ROOT, "direct12pbrrenderer_amd", "libpbr_host.so")
+
+
+def run_child(code, knobs=None, clear=(), timeout_s=600):
+    """Run the Python source `code` in a fresh process under `timeout -k 10 timeout_s` and return the CompletedProcess (text output
+    captured).  The PBR_* switches are read once per process and only by the knobs build, hence the child: the variables in `clear` and
+    PBR_HIP_LIB are removed from its environment; with `knobs` they are set and PBR_HIP_LIB points at libpbr_hip_knobs.so."""
+    env = dict(os.environ)
+    for k in (*clear, "PBR_HIP_LIB"):
+        env.pop(k, None)
+    if knobs:
+        assert os.path.exists(KNOBS_LIB), "build with make -C direct12pbrrenderer_amd/csrc (target knobs)"
+        env.update(knobs)
+        env["PBR_HIP_LIB"] = KNOBS_LIB
+    return subprocess.run(["timeout", "-k", "10", str(timeout_s), sys.executable, "-c", code], capture_output=True, text=True, env=env)
+
+
+@contextlib.contextmanager
+def environ(values):
+    """Set the variables of `values` in os.environ for the duration of the block (child processes inherit them), then restore them."""
+    saved = {k: os.environ.get(k) for k in values}
+    os.environ.update(values)
+    try:
+        yield
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def small_ibl(orc):
@@ -69,7 +104,6 @@ def oracle_bloom_from_level1(orc, a1):
 def reference_scene_lights():
     """The 8 `mSceneLight` records of the reference's Asset/Scene/main.json (tests/golden/scene_lights.npz, written by
     tests/golden/make_scene_lights.py in the build container)."""
-    import os
     return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "scene_lights.npz"))
 
 

@@ -1040,33 +1040,25 @@ print("wide bloom ok")
 
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize("knobs,exact,sizes", [
-    ({"PBR_BLOOM_WIDE": "1"}, False, [(2048, 64), (1040, 48), (512, 288), (304, 176), (320, 180), (96, 32), (400, 304), (160, 2080)]),
-    ({"PBR_BLOOM_WIDE": "1", "PBR_BLOOM_POLY": "0"}, True, [(2048, 64), (1040, 48), (512, 288), (304, 176), (320, 180), (96, 32), (400, 304), (160, 2080)]),
-    ({"PBR_BLOOM_WIDE": "0"}, True, [(512, 288), (2080, 1296)]),
-    ({}, False, [(2080, 1296), (3328, 2048)]),
+@pytest.mark.parametrize("knobs,exact,sizes", [   # ids as before a fourth row (knobs1) was retired, so that each id keeps naming the same case
+    pytest.param({"PBR_BLOOM_WIDE": "1"}, False, [(2048, 64), (1040, 48), (512, 288), (304, 176), (320, 180), (96, 32), (400, 304), (160, 2080)],
+                 id="knobs0-False-sizes0"),
+    pytest.param({"PBR_BLOOM_WIDE": "0"}, True, [(512, 288), (2080, 1296)], id="knobs2-True-sizes2"),
+    pytest.param({}, False, [(2080, 1296), (3328, 2048)], id="knobs3-False-sizes3"),
 ])
 def test_bloom_2x_up_levels_polyphase_and_shader_order(knobs, exact, sizes):
     """The 2x-up levels of the bloom pyramid against the oracle's staged chain.  Large levels (>= 400 tiles of 128 x 32) run
     k_blur_up_poly, the polyphase form (two six-tap filters on the coarse row, then the 1/4 | 3/4 row blend): held to SURVEY 8c's
     bloom-stage tolerance — each level as a stage (pbr_bloom_up_level, on the oracle's own inputs) <= 1 fp16 ULP, the whole chain
-    <= 2 ULP end to end with >= 99.8 % of the texels identical — where round 3 demanded bit-exactness.  The shader-order kernels
-    stay the bit-exact checker: k_blur_up_wide (knobs build, PBR_BLOOM_POLY=0) and k_blur_hv (PBR_BLOOM_WIDE=0), bit for bit.
-    Forced on at small and ragged sizes every M_UP level of the pyramid runs the wide kernels: widths below one tile, widths that
+    <= 2 ULP end to end with >= 99.8 % of the texels identical — where round 3 demanded bit-exactness.  The bit-exact checker is k_blur_hv,
+    the shader-order kernel (knobs build, PBR_BLOOM_WIDE=0): bit for bit.
+    Forced on at small and ragged sizes every M_UP level of the pyramid runs the polyphase kernel: widths below one tile, widths that
     are no multiple of 128, a 5-texel-wide level, image edges inside the first and last rows of waves.  Product library, chosen by
     the threshold — 2080x1296: the final level only; 3328x2048: level 1 (DUAL instance) as well.  The switches are read once per
     process and exist in the knobs build only (the product library never reads the environment), hence the child process."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ)
-    for k in ("PBR_BLOOM_WIDE", "PBR_BLOOM_POLY"):
-        env.pop(k, None)
-    if knobs:
-        env.update(knobs)
-        env["PBR_HIP_LIB"] = os.path.join(root, "direct12pbrrenderer_amd", "libpbr_hip_knobs.so")
-        assert os.path.exists(env["PBR_HIP_LIB"]), "build with make -C direct12pbrrenderer_amd/csrc (target knobs)"
-    r = subprocess.run(["timeout", "-k", "10", "800", sys.executable, "-c", _WIDE_BLOOM % (root, os.path.join(root, "tests"), exact, sizes)],
-                       capture_output=True, text=True, env=env)
+    import os
+    root = common.ROOT
+    r = common.run_child(_WIDE_BLOOM % (root, os.path.join(root, "tests"), exact, sizes), knobs, clear=("PBR_BLOOM_WIDE",), timeout_s=800)
     assert r.returncode == 0 and "wide bloom ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
 
 
@@ -1414,19 +1406,13 @@ def test_deferred_shade_output_does_not_depend_on_the_launch_schedule():
     (rows by rule) and by the knobs build with every row count forced (PBR_SHADE_ROWS_BIG = 1 .. 8, and another two-zone split) are
     bit-identical — odd sizes (last block row / column partial), a tile of a larger frame (global pixel coordinates), 0 / 1 / 256 lights;
     and the product's frames agree with the oracle.  Own processes: the knobs are read once per process."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import os
+    root = common.ROOT
     cases = [(321, 187, None, 0, 0, 256), (1441, 97, None, 0, 0, 256), (257, 64, (1440, 960), 1100, 850, 256), (640, 360, None, 0, 0, 1), (96, 33, None, 0, 0, 0)]
 
     def run(env_extra, check):
-        env = dict(os.environ)
-        for k in ("PBR_SHADE_ROWS_BIG", "PBR_SHADE_ROWS_SMALL", "PBR_SHADE_BIGFRAC", "PBR_HIP_LIB"):
-            env.pop(k, None)
-        if env_extra:
-            env.update(env_extra)
-            env["PBR_HIP_LIB"] = os.path.join(root, "direct12pbrrenderer_amd", "libpbr_hip_knobs.so")
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable, "-c", _SHADE_SCHEDULE % (root, os.path.join(root, "tests"), cases, check)],
-                           capture_output=True, text=True, env=env)
+        r = common.run_child(_SHADE_SCHEDULE % (root, os.path.join(root, "tests"), cases, check), env_extra,
+                             clear=("PBR_SHADE_ROWS_BIG", "PBR_SHADE_ROWS_SMALL", "PBR_SHADE_BIGFRAC"), timeout_s=600)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("shade schedule")]
         assert r.returncode == 0 and lines, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
         return lines[-1]

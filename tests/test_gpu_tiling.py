@@ -105,20 +105,10 @@ def test_ranks_match_single_gpu_frame(ctx, ibl, world, layout, halo, tile_w, til
     from direct12pbrrenderer_amd.pipeline import TileSpec, grid_for_world
     cols, rows = grid_for_world(world, layout)
     poly, overlap = overlap == "poly", overlap is True
-    saved = {k: os.environ.get(k) for k in ("PBR_HIP_LIB", "PBR_BLOOM_WIDE")}
-    if poly:   # spawned ranks inherit the environment; this process has loaded the product library long ago
-        os.environ["PBR_HIP_LIB"] = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "direct12pbrrenderer_amd", "libpbr_hip_knobs.so")
-        os.environ["PBR_BLOOM_WIDE"] = "1"
-    try:
-        with tempfile.TemporaryDirectory() as d:
-            mp.spawn(_worker, args=(world, _free_port(), d, layout, halo, tile_w, tile_h, overlap), nprocs=world, join=True)
-            ranks = [dict(np.load(os.path.join(d, f"rank{r}.npz"))) for r in range(world)]
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    # poly: spawned ranks inherit the environment; this process has loaded the product library long ago
+    with common.environ({"PBR_HIP_LIB": common.KNOBS_LIB, "PBR_BLOOM_WIDE": "1"} if poly else {}), tempfile.TemporaryDirectory() as d:
+        mp.spawn(_worker, args=(world, _free_port(), d, layout, halo, tile_w, tile_h, overlap), nprocs=world, join=True)
+        ranks = [dict(np.load(os.path.join(d, f"rank{r}.npz"))) for r in range(world)]
     W, H = tile_w * cols, tile_h * rows
     fr = _frame(ctx, TileSpec(0, 0, W, H, W, H, 0), _ibl_dev(ctx, ibl), ibl[3])
     full_hdr = fr.hdr_interior()
@@ -176,17 +166,8 @@ def test_tiled_bloom_up_pass_rectangles_leave_the_merged_interior_bit_identical(
     rectangles and merge rectangles: the HDR buffer and the interior's histogram of the product library equal, bit for bit, those of the
     knobs build with the rectangles switched off (PBR_BLOOM_SHRINK=0: every level on the whole extended tile) — with chain B pre-filled
     with a sentinel, so a level that reads a texel its producer skipped cannot pass by luck.  Own processes (knobs are read once)."""
-    import subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
     def run(env_extra):
-        env = dict(os.environ)
-        for k in ("PBR_BLOOM_SHRINK", "PBR_HIP_LIB"):
-            env.pop(k, None)
-        if env_extra:
-            env.update(env_extra)
-            env["PBR_HIP_LIB"] = os.path.join(root, "direct12pbrrenderer_amd", "libpbr_hip_knobs.so")
-        r = subprocess.run(["timeout", "-k", "10", "500", sys.executable, "-c", _SHRINK % (root, 40)], capture_output=True, text=True, env=env)
+        r = common.run_child(_SHRINK % (common.ROOT, 40), env_extra, clear=("PBR_BLOOM_SHRINK",), timeout_s=500)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("tiled bloom")]
         assert r.returncode == 0 and lines, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
         return lines[-1].split()
