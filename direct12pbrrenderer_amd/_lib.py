@@ -6,7 +6,7 @@ symbol cannot be resolved this module raises — it never substitutes another im
 import ctypes as C
 import os
 
-from .structs import CubeF32, GBuffer, Global, HaloPeer, Tile
+from .structs import CubeF32, GBuffer, Global, HaloPeer, Tile, View
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB", os.path.join(_HERE, "libpbr_hip.so"))   # override = experiments only
@@ -65,6 +65,11 @@ SIGNATURES = {
     "pbr_lum_average": (_int, [_vp, _vp, _u32, _f32, _f32, _f32, _vp]),
     "pbr_tonemap": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32]),
     "pbr_average_tonemap": (_int, [_vp, _vp, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32]),
+    "pbr_clustered_views": (_int, [_vp, C.POINTER(View), _u32]),
+    "pbr_deferred_shade_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32]),
+    "pbr_bloom_histogram_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _u32, _f32, _f32, _f32, _f32]),
+    "pbr_lum_average_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _f32, _f32]),
+    "pbr_tonemap_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _u32]),
     "pbr_comm_unique_id": (_int, [_vp]),
     "pbr_comm_init": (_int, [_vp, _int, _int, _vp]),
     "pbr_allreduce_hist": (_int, [_vp, _vp]),

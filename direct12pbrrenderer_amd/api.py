@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from .structs import (BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, CubeF32, GBuffer, Global, HaloPeer, Tile, bloom_chain_texels, cube_texels, env_padded_texels)
+                      NUM_CLUSTERS, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, cube_texels, env_padded_texels)
 
 
 class PbrError(RuntimeError):
@@ -311,6 +311,24 @@ class PbrContext:
         """pbr_lum_average + pbr_tonemap as one launch: avg_out != avg_in, hist_clear != hist (see pbr_hip.h)"""
         self._check(self.lib.pbr_average_tonemap(self.h, _ptr(hist), pixel_count, min_log, log_range, dt, _ptr(avg_in), _ptr(avg_out),
                                                  _ptr(hist_clear) if hist_clear is not None else None, _ptr(hdr), w, h, pitch, _ptr(out), out_pitch))
+
+    # ---- multi-view calls: `views` is a ctypes array of View (structs.View), n <= MAX_VIEWS equal-sized whole frames
+    def clustered_views(self, views, n):
+        self._check(self.lib.pbr_clustered_views(self.h, views, n))
+
+    def deferred_shade_views(self, views, n, w, h, lut, lut_res, env, env_size, env_mips):
+        """env: the PADDED chain from env_pad(); SkyBoxSH must be the same in every view"""
+        self._check(self.lib.pbr_deferred_shade_views(self.h, views, n, w, h, _ptr(lut), lut_res, _ptr(env), env_size, env_mips))
+
+    def bloom_histogram_views(self, views, n, w, h, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE,
+                              min_log=MIN_LOG_LUMINANCE, inv_range=INV_LOG_LUMINANCE_RANGE):
+        self._check(self.lib.pbr_bloom_histogram_views(self.h, views, n, w, h, threshold, knee, min_log, inv_range))
+
+    def lum_average_views(self, views, n, pixel_count, min_log=MIN_LOG_LUMINANCE, log_range=LOG_LUMINANCE_RANGE):
+        self._check(self.lib.pbr_lum_average_views(self.h, views, n, pixel_count, min_log, log_range))
+
+    def tonemap_views(self, views, n, w, h):
+        self._check(self.lib.pbr_tonemap_views(self.h, views, n, w, h))
 
     def membench_read(self, buf, sink, blocks):
         """One streaming-read pass over `buf` (measurement aid: the device's achievable HBM-read bandwidth)."""

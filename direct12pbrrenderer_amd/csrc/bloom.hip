@@ -287,8 +287,23 @@ __global__ __launch_bounds__(256) void k_bloom_merge(pbr_half* __restrict__ hdr,
 // Results are bit-identical to the staged kernels above (tests/test_gpu_parity.py), which remain the generic path.
 
 constexpr int PF_TW = 64, PF_TH = 16;
-__global__ __launch_bounds__(256) void k_bloom_prefilter_2x(const pbr_half* __restrict__ hdr, int w, int h, int pitch,
-                                                              pbr_half* __restrict__ out, OutRects rs, float threshold, float knee) {
+// Multi-view frames (pbr_bloom_histogram_views): the fused kernels take a view table and run view blockIdx.y of it in place of their own
+// pointers (NoViews, an empty argument in a padding hole of the argument block: the single-view kernel, its arguments where they were).  Sizes and rectangles are the views' common ones.
+struct PrefilterViews { const pbr_half* hdr[PBR_MAX_VIEWS]; pbr_half* out[PBR_MAX_VIEWS]; int pitch[PBR_MAX_VIEWS]; };
+struct LevelViews {
+    const pbr_half* in[PBR_MAX_VIEWS];
+    const pbr_half* in2[PBR_MAX_VIEWS];
+    pbr_half* out[PBR_MAX_VIEWS];
+    uint32_t* hist[PBR_MAX_VIEWS];
+    int out_pitch[PBR_MAX_VIEWS];
+};
+template <class VS = NoViews>
+__global__ __launch_bounds__(256) void k_bloom_prefilter_2x(const pbr_half* __restrict__ hdr_, int w, int h, int pitch_, VS vs,
+                                                              pbr_half* __restrict__ out_, OutRects rs, float threshold, float knee) {
+    const pbr_half* __restrict__ hdr = hdr_;
+    pbr_half* __restrict__ out = out_;
+    int pitch = pitch_;
+    if constexpr (!std::is_same_v<VS, NoViews>) { hdr = vs.hdr[blockIdx.y]; out = vs.out[blockIdx.y]; pitch = vs.pitch[blockIdx.y]; }
     __shared__ float4 pos[PF_TH + 2][PF_TW + 2];   // (colour * weight, weight) of every sample position the tile touches
     const int tid = threadIdx.x;
     int r = 0;
@@ -442,13 +457,22 @@ __device__ __forceinline__ float gauss9_const(float c) {   // the nine fused mad
 // is all its HDR buffer covers beyond a 4-pixel rim.
 struct TailRect { int tx0, ty0, mx0, my0, mx1, my1, bx, by, hx0, hy0, hx1, hy1; };
 
-template <int MODE, bool DUAL, int TAIL, int TH, int NT>   // TAIL 0: store; 1: merge into hdr; 2: merge + histogram
-__global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ in, int iw, int ih,
-                                                 const pbr_half* __restrict__ in2,   // DUAL: ow x oh, same-size
-                                                 pbr_half* __restrict__ out, int ow, int oh, int out_pitch,
+template <int MODE, bool DUAL, int TAIL, int TH, int NT, class VS = NoViews>   // TAIL 0: store; 1: merge into hdr; 2: merge + histogram
+__global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ in_, int iw, int ih,
+                                                 const pbr_half* __restrict__ in2_,   // DUAL: ow x oh, same-size
+                                                 pbr_half* __restrict__ out_, int ow, int oh, int out_pitch_,
                                                  int tiles_x, int n_tiles,
-                                                 TailRect tr, float min_log, float inv_range,
-                                                 uint32_t* __restrict__ hist) {
+                                                 TailRect tr, float min_log, float inv_range, VS vs,
+                                                 uint32_t* __restrict__ hist_) {
+    const pbr_half* __restrict__ in = in_;
+    const pbr_half* __restrict__ in2 = in2_;
+    pbr_half* __restrict__ out = out_;
+    uint32_t* __restrict__ hist = hist_;
+    int out_pitch = out_pitch_;
+    if constexpr (!std::is_same_v<VS, NoViews>) {   // LevelViews: view blockIdx.y
+        const int v = blockIdx.y;
+        in = vs.in[v]; in2 = vs.in2[v]; out = vs.out[v]; hist = vs.hist[v]; out_pitch = vs.out_pitch[v];
+    }
     constexpr int TW = 64, SW = TW + 8, SR = TH + 8;
     constexpr int NW = NT / 64;
     constexpr int PER_T = SR / NW;                      // sampled / H-gaussed rows per wave: rows wv*PER_T .. +PER_T-1
@@ -662,13 +686,22 @@ constexpr double g(int k) { return (k < -4 || k > 4) ? 0.0 : G[k + 4]; }
 constexpr float E(int j) { return (float)(0.75 * g(2 * j) + 0.25 * g(2 * j + 2) + 0.75 * g(2 * j + 1) + 0.25 * g(2 * j - 1)); }
 }  // namespace poly
 
-template <bool DUAL, int TAIL, int TH>
-__global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restrict__ in, int iw, int ih,
-                                                          const pbr_half* __restrict__ in2,   // DUAL: ow x oh, same-size
-                                                          pbr_half* __restrict__ out, int ow, int oh, int out_pitch,
+template <bool DUAL, int TAIL, int TH, class VS = NoViews>
+__global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restrict__ in_, int iw, int ih,
+                                                          const pbr_half* __restrict__ in2_,   // DUAL: ow x oh, same-size
+                                                          pbr_half* __restrict__ out_, int ow, int oh, int out_pitch_,
                                                           int tiles_x, int n_tiles,
-                                                          TailRect tr, float min_log, float inv_range,
-                                                          uint32_t* __restrict__ hist) {
+                                                          TailRect tr, float min_log, float inv_range, VS vs,
+                                                          uint32_t* __restrict__ hist_) {
+    const pbr_half* __restrict__ in = in_;
+    const pbr_half* __restrict__ in2 = in2_;
+    pbr_half* __restrict__ out = out_;
+    uint32_t* __restrict__ hist = hist_;
+    int out_pitch = out_pitch_;
+    if constexpr (!std::is_same_v<VS, NoViews>) {   // LevelViews: view blockIdx.y
+        const int v = blockIdx.y;
+        in = vs.in[v]; in2 = vs.in2[v]; out = vs.out[v]; hist = vs.hist[v]; out_pitch = vs.out_pitch[v];
+    }
     constexpr int TW = 128, NP = TW / 2 + 4, NC = TW / 2 + 6, SR = TH + 8, NT = 512, NW = NT / 64;
     constexpr int NPAIR = TH / 2 + 5;                 // coarse row pairs (m, m + 1) whose two blends (fine rows 2m + 1, 2m + 2) the tile's SR rows need
     constexpr int PPW = (NPAIR + NW - 1) / NW;        // pairs per wave; wave w: pairs w * PPW .. (the last waves may hold fewer, or none)
@@ -862,9 +895,13 @@ template <int MODE, bool DUAL, int TAIL>
 static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint32_t ih, const pbr_half* in2,
                             pbr_half* out, uint32_t ow, uint32_t oh, uint32_t out_pitch,
                             const uint32_t* rect, float min_log, float inv_range, uint32_t* hist,
-                            const uint32_t* merge_rect = nullptr, const uint32_t* buf_origin = nullptr) {
+                            const uint32_t* merge_rect = nullptr, const uint32_t* buf_origin = nullptr,
+                            const LevelViews* views = nullptr, uint32_t nv = 0) {
     // rect: histogram rect {x,y,w,h}; merge_rect: HDR texels to merge (default: the whole level); buf_origin: level
-    // coordinates of out[0] (default 0,0)
+    // coordinates of out[0] (default 0,0).  views: nv views of this level (pointer arguments unused) — the kernel choice is the one
+    // a single view of the level gets; grid (blocks, nv)
+    // (the instances pbr_bloom_histogram_views runs: the 2x-down pairs, the dual up-levels and the merge + histogram tail)
+    constexpr bool VIEWS_OK = TAIL != 1 && (MODE != M_UP || DUAL || TAIL == 2);
     TailRect tr;
     tr.hx0 = rect ? (int)rect[0] : 0; tr.hy0 = rect ? (int)rect[1] : 0;
     tr.hx1 = rect ? (int)(rect[0] + rect[2]) : 0; tr.hy1 = rect ? (int)(rect[1] + rect[3]) : 0;
@@ -874,7 +911,9 @@ static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint3
     // histogram instance: ~1024 blocks that each walk the same number of tiles (an uneven split leaves the chip
     // half empty for the last round; one block per tile costs 256 contended global atomics per tile)
     static const int hist_blocks = pbr::knob_int("PBR_BLOOM_HIST_BLOCKS", 1024);
-    auto even_blocks = [](int n_tiles) { const int per = (n_tiles + hist_blocks - 1) / hist_blocks; return (n_tiles + per - 1) / per; };
+    // (views: ~1024 blocks over the whole batch, each walking one view's tiles)
+    const int nvb = views ? (int)nv : 1;
+    auto even_blocks = [nvb](int n_tiles) { const int per = (n_tiles * nvb + hist_blocks - 1) / hist_blocks; return (n_tiles + per - 1) / per; };
     if constexpr (MODE == M_UP) {
         // 2x-up levels big enough to fill the chip with 128 x 32 tiles: k_blur_up_poly, two columns per lane (PBR_BLOOM_WIDE=0|1 forces)
         static const int wide_forced = pbr::knob_int("PBR_BLOOM_WIDE", -1);
@@ -882,8 +921,16 @@ static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint3
         const int wtiles_x = (tr.mx1 + 127) / 128 - wtx0, wn = wtiles_x * ((tr.my1 + 31) / 32 - wty0);
         if (wide_forced >= 0 ? wide_forced == 1 : (wn >= 400 && !ctx->bloom_shader_order)) {
             tr.tx0 = wtx0; tr.ty0 = wty0;
-            hipLaunchKernelGGL((k_blur_up_poly<DUAL, TAIL, 32>), dim3(TAIL == 2 ? even_blocks(wn) : wn), dim3(512), 0, ctx->stream,
-                               in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, wtiles_x, wn, tr, min_log, inv_range, hist);
+            const int wb = TAIL == 2 ? even_blocks(wn) : wn;
+            if constexpr (VIEWS_OK) {
+                if (views) {
+                    hipLaunchKernelGGL((k_blur_up_poly<DUAL, TAIL, 32, LevelViews>), dim3(wb, nv), dim3(512), 0, ctx->stream,
+                                       nullptr, (int)iw, (int)ih, nullptr, nullptr, (int)ow, (int)oh, 0, wtiles_x, wn, tr, min_log, inv_range, *views, nullptr);
+                    return launched(ctx, "k_blur_up_poly<views>");
+                }
+            }
+            hipLaunchKernelGGL((k_blur_up_poly<DUAL, TAIL, 32>), dim3(wb), dim3(512), 0, ctx->stream,
+                               in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, wtiles_x, wn, tr, min_log, inv_range, NoViews{}, hist);
             return launched(ctx, "k_blur_up_poly");
         }
     }
@@ -895,14 +942,25 @@ static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint3
     const int tiles_x = (tr.mx1 + 63) / 64 - tr.tx0;
     const int n_tiles = tiles_x * ((tr.my1 + th - 1) / th - tr.ty0);
     const int blocks = TAIL == 2 ? even_blocks(n_tiles) : n_tiles;
+    if constexpr (VIEWS_OK) {
+        if (views) {
+            if (big)
+                hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 32, 512, LevelViews>), dim3(blocks, nv), dim3(512), 0, ctx->stream,
+                                   nullptr, (int)iw, (int)ih, nullptr, nullptr, (int)ow, (int)oh, 0, tiles_x, n_tiles, tr, min_log, inv_range, *views, nullptr);
+            else
+                hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 16, 512, LevelViews>), dim3(blocks, nv), dim3(512), 0, ctx->stream,
+                                   nullptr, (int)iw, (int)ih, nullptr, nullptr, (int)ow, (int)oh, 0, tiles_x, n_tiles, tr, min_log, inv_range, *views, nullptr);
+            return launched(ctx, "k_blur_hv<views>");
+        }
+    }
     if (big) {
         hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 32, 512>), dim3(blocks), dim3(512), 0, ctx->stream,
-                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, hist);
+                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, NoViews{}, hist);
     } else {
         // small levels are latency-bound (one tile's dependent chain + the launch): 64 x 16 tiles on EIGHT waves — 3 H rows per
         // wave, 2 outputs per thread — shorten the chain; the five small launches of a 4K frame take ~5 us less together
         hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 16, 512>), dim3(blocks), dim3(512), 0, ctx->stream,
-                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, hist);
+                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, NoViews{}, hist);
     }
     return launched(ctx, "k_blur_hv");
 }
@@ -925,7 +983,7 @@ static pbr_status prefilter_launch(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w
             blocks += rs.tiles_x[r] * ((rcs[r].y1 - rcs[r].y0 + PF_TH - 1) / PF_TH);
         }
         rs.first[n] = blocks;
-        hipLaunchKernelGGL(k_bloom_prefilter_2x, dim3(blocks), dim3(256), 0, ctx->stream, hdr, (int)w, (int)h, (int)pitch, out, rs, threshold, knee);
+        hipLaunchKernelGGL(k_bloom_prefilter_2x<NoViews>, dim3(blocks), dim3(256), 0, ctx->stream, hdr, (int)w, (int)h, (int)pitch, NoViews{}, out, rs, threshold, knee);
         return launched(ctx, "k_bloom_prefilter_2x");
     }
     for (int r = 0; r < n; r++) {
@@ -1138,6 +1196,111 @@ pbr_status pbr_bloom_histogram(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t
     PBR_REQUIRE(ctx, rect && hist256, "pbr_bloom_histogram: null pointer");
     PBR_REQUIRE(ctx, rect[2] >= 1 && rect[3] >= 1 && rect[0] + rect[2] <= w && rect[1] + rect[3] <= h, "pbr_bloom_histogram: rect outside the image");
     return bloom_impl(ctx, hdr, w, h, pitch, A, B, threshold, knee, rect, min_log, inv_range, hist256);
+}
+
+// BloomPass::Execute + the histogram dispatch for up to PBR_MAX_VIEWS whole frames of one size.  Every level takes the kernel a single view
+// of that size takes (bloom_impl / bloom_pyramid): fused levels (exact halves) run all views in one launch, grid (blocks of one view,
+// views); staged levels (not an exact half, e.g. 1920x1080 from level 3 down) run the single-view staged kernels once per view.
+pbr_status pbr_bloom_histogram_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h,
+                                     float threshold, float knee, float min_log, float inv_range) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, views_count_ok(views, n), "pbr_bloom_histogram_views: need 1 .. PBR_MAX_VIEWS views");
+    PBR_REQUIRE(ctx, (w >> (PBR_BLOOM_MIPS - 1)) >= 1 && (h >> (PBR_BLOOM_MIPS - 1)) >= 1, "pbr_bloom_histogram_views: image too small for 5 mips");
+    PBR_REQUIRE(ctx, w <= 65535 && h <= 65535, "pbr_bloom_histogram_views: bad size");
+    for (uint32_t i = 0; i < n; i++) {
+        const pbr_view& v = views[i];
+        PBR_REQUIRE(ctx, v.hdr && v.chain_a && v.chain_b && v.hist256, "pbr_bloom_histogram_views: null pointer");
+        PBR_REQUIRE(ctx, v.hdr_pitch >= w, "pbr_bloom_histogram_views: bad size");
+    }
+    const size_t chain_bytes = pbr_bloom_chain_texels(w, h) * 8u;
+    PBR_REQUIRE(ctx, views_disjoint(views, n, 4, [&](const pbr_view& v, int k, uintptr_t& lo, uintptr_t& hi) {
+                    if (k == 0) { lo = addr(v.hdr); hi = lo + ((size_t)v.hdr_pitch * (h - 1) + w) * 8u; }
+                    else if (k == 1) { lo = addr(v.chain_a); hi = lo + chain_bytes; }
+                    else if (k == 2) { lo = addr(v.chain_b); hi = lo + chain_bytes; }
+                    else { lo = addr(v.hist256); hi = lo + PBR_HISTOGRAM_BINS * sizeof(uint32_t); } }),
+                "pbr_bloom_histogram_views: two views share an HDR target, a bloom chain or a histogram");
+    auto W = [&](uint32_t l) { return w >> l; };
+    auto H = [&](uint32_t l) { return h >> l; };
+    auto off = [&](uint32_t l) { return (size_t)4 * pbr_bloom_level_offset(w, h, l); };
+    auto exact = [&](uint32_t l) { return exact_half(W(l)) && exact_half(H(l)); };
+    const uint32_t rect[4] = {0, 0, w, h};
+    pbr_status r;
+    // prefilter: hdr -> level 1 of chain A
+    if (exact(0)) {
+        PrefilterViews pv{};
+        for (uint32_t i = 0; i < n; i++) { pv.hdr[i] = views[i].hdr; pv.out[i] = views[i].chain_a + off(1); pv.pitch[i] = (int)views[i].hdr_pitch; }
+        OutRects rs{};
+        rs.n = 1; rs.ox = 0; rs.oy = 0; rs.pitch = (int)W(1);
+        rs.x0[0] = 0; rs.y0[0] = 0; rs.x1[0] = (int)W(1); rs.y1[0] = (int)H(1);
+        rs.tiles_x[0] = ((int)W(1) + PF_TW - 1) / PF_TW;
+        rs.first[0] = 0; rs.first[1] = rs.tiles_x[0] * (((int)H(1) + PF_TH - 1) / PF_TH);
+        hipLaunchKernelGGL(k_bloom_prefilter_2x<PrefilterViews>, dim3(rs.first[1], n), dim3(256), 0, ctx->stream,
+                           nullptr, (int)w, (int)h, 0, pv, nullptr, rs, threshold, knee);
+        if ((r = launched(ctx, "k_bloom_prefilter_2x<views>"))) return r;
+    } else {
+        for (uint32_t i = 0; i < n; i++)
+            if ((r = pbr_bloom_prefilter(ctx, views[i].hdr, w, h, views[i].hdr_pitch, views[i].chain_a + off(1), threshold, knee))) return r;
+    }
+    // the pyramid (bloom_pyramid's schedule; `res_in_b`: the finished level below lives in chain B)
+    LevelViews lv{};
+    auto level = [&](auto in_of, auto in2_of, auto out_of) {
+        for (uint32_t i = 0; i < n; i++) {
+            lv.in[i] = in_of(views[i]); lv.in2[i] = in2_of(views[i]); lv.out[i] = out_of(views[i]);
+            lv.hist[i] = nullptr; lv.out_pitch[i] = 0;
+        }
+        return &lv;
+    };
+    auto none = [](const pbr_view&) { return (const pbr_half*)nullptr; };
+    for (uint32_t k = 0; k < PBR_BLOOM_STEP; k++) {   // downsample
+        const uint32_t up = k + 1, lo = k + 2;
+        if (exact(up)) {
+            const LevelViews* q = level([&](const pbr_view& v) { return (const pbr_half*)v.chain_a + off(up); }, none,
+                                        [&](const pbr_view& v) { return v.chain_a + off(lo); });
+            for (uint32_t i = 0; i < n; i++) lv.out_pitch[i] = (int)W(lo);
+            if ((r = launch_hv<M_DOWN, false, 0>(ctx, nullptr, W(up), H(up), nullptr, nullptr, W(lo), H(lo), W(lo), nullptr, 0.0f, 0.0f, nullptr,
+                                                 nullptr, nullptr, q, n))) return r;
+        } else {
+            for (uint32_t i = 0; i < n; i++) {
+                pbr_half* A = views[i].chain_a; pbr_half* B = views[i].chain_b;
+                if ((r = pbr_blur_h(ctx, A + off(up), W(up), H(up), B + off(lo), W(lo), H(lo)))) return r;
+                if ((r = pbr_blur_v(ctx, B + off(lo), W(lo), H(lo), A + off(lo), W(lo), H(lo)))) return r;
+            }
+        }
+    }
+    bool res_in_b = false;
+    uint32_t res_level = PBR_BLOOM_MIPS - 1;
+    auto res_of = [&](const pbr_view& v) { return (const pbr_half*)(res_in_b ? v.chain_b : v.chain_a) + off(res_level); };
+    for (int k = PBR_BLOOM_STEP - 1; k >= 0; k--) {   // upsample: V(H(lower) + H(upper))
+        const uint32_t up = (uint32_t)k + 1;
+        if (exact(up)) {
+            const LevelViews* q = level(res_of, [&](const pbr_view& v) { return (const pbr_half*)v.chain_a + off(up); },
+                                        [&](const pbr_view& v) { return v.chain_b + off(up); });
+            for (uint32_t i = 0; i < n; i++) lv.out_pitch[i] = (int)W(up);
+            if ((r = launch_hv<M_UP, true, 0>(ctx, nullptr, W(up + 1), H(up + 1), nullptr, nullptr, W(up), H(up), W(up), nullptr, 0.0f, 0.0f, nullptr,
+                                              nullptr, nullptr, q, n))) return r;
+            res_in_b = true;
+        } else {
+            for (uint32_t i = 0; i < n; i++) {
+                pbr_half* A = views[i].chain_a; pbr_half* B = views[i].chain_b;
+                if ((r = pbr_bloom_upsample_add(ctx, A + off(up), W(up), H(up), res_of(views[i]), W(up + 1), H(up + 1), B + off(up)))) return r;
+                if ((r = pbr_blur_v(ctx, B + off(up), W(up), H(up), A + off(up), W(up), H(up)))) return r;
+            }
+            res_in_b = false;
+        }
+        res_level = up;
+    }
+    // level 0: H + V + merge + histogram
+    if (exact(0)) {
+        const LevelViews* q = level(res_of, none, [&](const pbr_view& v) { return v.hdr; });
+        for (uint32_t i = 0; i < n; i++) { lv.hist[i] = views[i].hist256; lv.out_pitch[i] = (int)views[i].hdr_pitch; }
+        return launch_hv<M_UP, false, 2>(ctx, nullptr, w >> 1, h >> 1, nullptr, nullptr, w, h, 0, rect, min_log, inv_range, nullptr, nullptr, nullptr, q, n);
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        pbr_half* b0 = views[i].chain_b;
+        if ((r = pbr_blur_h(ctx, res_of(views[i]), w >> 1, h >> 1, b0, w, h))) return r;
+        if ((r = bloom_final(ctx, b0, views[i].hdr, w, h, views[i].hdr_pitch, rect, min_log, inv_range, views[i].hist256))) return r;
+    }
+    return PBR_OK;
 }
 
 // Multi-GPU halo path (SURVEY 8e option 2): BloomPass::Execute minus the prefilter, on the extended rectangle E

@@ -8,6 +8,7 @@
 // "first 32 hits in ascending light index" order exactly.
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
+#include <type_traits>
 
 using namespace pbr;
 
@@ -66,11 +67,29 @@ __device__ __forceinline__ bool light_hits(const ClusterParams& p, const pbr_lig
     return (dx * dx + dy * dy) + dz * dz < radius * radius;
 }
 
+// pbr_clustered_views: the cull with a view dimension — grid (3072/4, views), each view's parameters by value in ClusterViews
+struct ClusterView {
+    ClusterParams p;
+    const pbr_light* lights;
+    int n;
+    pbr_cluster* clusters;
+};
+struct ClusterViews { ClusterView v[PBR_MAX_VIEWS]; };
+static_assert(sizeof(ClusterViews) <= 4096 - 256, "k_cluster_cull<.., ClusterViews>: kernel arguments over 4 KiB");
+
 // grid 3072/4 x block 256 (4 waves, one cluster per wave).  BUILD: both dispatches of ClusteredPass::Execute in one
 // launch — the wave computes its cluster's bounds itself (every lane the same values) instead of reading them back.
-template <bool BUILD>
-__global__ __launch_bounds__(256) void k_cluster_cull(ClusterParams p, const pbr_light* __restrict__ lights, int n,
-                                                        pbr_cluster* __restrict__ clusters) {
+// VS = ClusterViews: view blockIdx.y of `vs` instead of (p_, lights_, n_, clusters_); NoViews (an empty argument): the single-view kernel.
+template <bool BUILD, class VS = NoViews>
+__global__ __launch_bounds__(256) void k_cluster_cull(ClusterParams p_, const pbr_light* __restrict__ lights_, int n_, VS vs,
+                                                        pbr_cluster* __restrict__ clusters_) {
+    constexpr bool MV = !std::is_same_v<VS, NoViews>;
+    const ClusterView* view = nullptr;
+    if constexpr (MV) view = &vs.v[blockIdx.y];
+    const ClusterParams& p = MV ? view->p : p_;
+    const pbr_light* __restrict__ lights = MV ? view->lights : lights_;
+    const int n = MV ? view->n : n_;
+    pbr_cluster* __restrict__ clusters = MV ? view->clusters : clusters_;
     const int lane = threadIdx.x & 63;
     const int ci = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ci >= PBR_NUM_CLUSTERS) return;   // wave-uniform
@@ -122,7 +141,7 @@ pbr_status pbr_cluster_cull(pbr_ctx* ctx, const pbr_global* g, const pbr_light* 
     PBR_REQUIRE(ctx, n >= 0 && n <= PBR_MAX_SCENE_LIGHTS, "pbr_cluster_cull: light count out of [0, 1024]");
     PBR_REQUIRE(ctx, n == 0 || lights != nullptr, "pbr_cluster_cull: null lights");
     if (n == 0) return PBR_OK;
-    hipLaunchKernelGGL(k_cluster_cull<false>, dim3(PBR_NUM_CLUSTERS / 4), dim3(256), 0, ctx->stream, make_params(g), lights, n, clusters);
+    hipLaunchKernelGGL(k_cluster_cull<false>, dim3(PBR_NUM_CLUSTERS / 4), dim3(256), 0, ctx->stream, make_params(g), lights, n, NoViews{}, clusters);
     return launched(ctx, "k_cluster_cull");
 }
 
@@ -132,8 +151,28 @@ pbr_status pbr_clustered(pbr_ctx* ctx, const pbr_global* g, const pbr_light* lig
     PBR_REQUIRE(ctx, g->Near > 0.0f && g->Far > g->Near, "pbr_clustered: need 0 < Near < Far");
     PBR_REQUIRE(ctx, n >= 0 && n <= PBR_MAX_SCENE_LIGHTS, "pbr_clustered: light count out of [0, 1024]");
     PBR_REQUIRE(ctx, n == 0 || lights != nullptr, "pbr_clustered: null lights");
-    hipLaunchKernelGGL(k_cluster_cull<true>, dim3(PBR_NUM_CLUSTERS / 4), dim3(256), 0, ctx->stream, make_params(g), lights, n, clusters);
+    hipLaunchKernelGGL(k_cluster_cull<true>, dim3(PBR_NUM_CLUSTERS / 4), dim3(256), 0, ctx->stream, make_params(g), lights, n, NoViews{}, clusters);
     return launched(ctx, "k_cluster_cull<build>");
+}
+
+pbr_status pbr_clustered_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, views_count_ok(views, n), "pbr_clustered_views: need 1 .. PBR_MAX_VIEWS views");
+    ClusterViews vs{};
+    for (uint32_t i = 0; i < n; i++) {
+        const pbr_view& v = views[i];
+        PBR_REQUIRE(ctx, v.clusters, "pbr_clustered_views: null clusters");
+        PBR_REQUIRE(ctx, v.g.Near > 0.0f && v.g.Far > v.g.Near, "pbr_clustered_views: need 0 < Near < Far");
+        PBR_REQUIRE(ctx, v.num_lights >= 0 && v.num_lights <= PBR_MAX_SCENE_LIGHTS, "pbr_clustered_views: light count out of [0, 1024]");
+        PBR_REQUIRE(ctx, v.num_lights == 0 || v.lights != nullptr, "pbr_clustered_views: null lights");
+        vs.v[i] = ClusterView{make_params(&v.g), v.lights, v.num_lights, v.clusters};
+    }
+    PBR_REQUIRE(ctx, views_disjoint(views, n, 1, [](const pbr_view& v, int, uintptr_t& lo, uintptr_t& hi) {
+                    lo = addr(v.clusters); hi = lo + (size_t)PBR_NUM_CLUSTERS * sizeof(pbr_cluster); }),
+                "pbr_clustered_views: two views share a cluster buffer");
+    hipLaunchKernelGGL((k_cluster_cull<true, ClusterViews>), dim3(PBR_NUM_CLUSTERS / 4, n), dim3(256), 0, ctx->stream,
+                       ClusterParams{}, (const pbr_light*)nullptr, 0, vs, (pbr_cluster*)nullptr);
+    return launched(ctx, "k_cluster_cull<views>");
 }
 
 }  // extern "C"

@@ -110,6 +110,17 @@ __global__ __launch_bounds__(256) void k_lum_average(uint32_t* __restrict__ hist
     if (threadIdx.x == 0) avg[0] = r;
 }
 
+// pbr_lum_average_views: one block per view (grid n), each view's histogram, cell and DeltaTime by value
+struct AverageViews { uint32_t* hist[PBR_MAX_VIEWS]; float* avg[PBR_MAX_VIEWS]; float delta_time[PBR_MAX_VIEWS]; };
+__global__ __launch_bounds__(256) void k_lum_average_views(AverageViews vs, uint32_t pixel_count, float min_log, float range) {
+    __shared__ float sh[PBR_HISTOGRAM_BINS];
+    uint32_t* hist = vs.hist[blockIdx.x];
+    float* avg = vs.avg[blockIdx.x];
+    const float r = adapted_luminance(sh, hist, pixel_count, min_log, range, vs.delta_time[blockIdx.x], avg[0]);
+    hist[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) avg[0] = r;
+}
+
 // hdr_tone_mapping.hlsl:27-36.  The result is quantised to 8 bits (tolerance 1 LSB), so the fast
 // reciprocal / log / exp instructions are used throughout: the pass must stay HBM-bound (12 B/pixel),
 // and three IEEE divisions + a libm pow per channel would make it VALU-bound.
@@ -192,6 +203,19 @@ __global__ __launch_bounds__(256) void k_tonemap(const pbr_half* __restrict__ hd
     tonemap_pixels(hdr, w, h, pitch, avg[0], out, out_pitch, aligned);
 }
 
+// pbr_tonemap_views: k_tonemap with a view dimension (grid (blocks, n)); `aligned` is each view's own, as its single-view call decides it
+struct TonemapViews {
+    const pbr_half* hdr[PBR_MAX_VIEWS];
+    const float* avg[PBR_MAX_VIEWS];
+    uint32_t* out[PBR_MAX_VIEWS];
+    uint32_t pitch[PBR_MAX_VIEWS], out_pitch[PBR_MAX_VIEWS];
+    bool aligned[PBR_MAX_VIEWS];
+};
+__global__ __launch_bounds__(256) void k_tonemap_views(TonemapViews vs, uint32_t w, uint32_t h) {
+    const uint32_t v = blockIdx.y;
+    tonemap_pixels(vs.hdr[v], w, h, vs.pitch[v], vs.avg[v][0], vs.out[v], vs.out_pitch[v], vs.aligned[v]);
+}
+
 // hdr_average_histogram.hlsl + hdr_tone_mapping.hlsl in ONE launch (round 4).  The average is a 256-bin reduction — microseconds of
 // work behind a launch of its own (4.7 us + a dependency gap in the 4K frame): here every block of the tone-map re-derives it from the
 // bins with the same fixed-order LDS tree (bit-identical in every block), then tone-maps its pixels.  Nothing the blocks read is
@@ -268,6 +292,44 @@ pbr_status pbr_average_tonemap(pbr_ctx* ctx, const uint32_t* hist256, uint32_t p
     hipLaunchKernelGGL(k_average_tonemap, dim3(blocks), dim3(256), 0, ctx->stream, hist256, pixel_count, min_log, range, delta_time, avg_in, avg_out,
                        hist_clear256, hdr, w, h, pitch, rgba8, out_pitch, aligned);
     return launched(ctx, "k_average_tonemap");
+}
+
+pbr_status pbr_lum_average_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t pixel_count, float min_log, float range) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, views_count_ok(views, n), "pbr_lum_average_views: need 1 .. PBR_MAX_VIEWS views");
+    AverageViews vs{};
+    for (uint32_t i = 0; i < n; i++) {
+        PBR_REQUIRE(ctx, views[i].hist256 && views[i].avg, "pbr_lum_average_views: null pointer");
+        vs.hist[i] = views[i].hist256; vs.avg[i] = views[i].avg; vs.delta_time[i] = views[i].g.DeltaTime;
+    }
+    PBR_REQUIRE(ctx, views_disjoint(views, n, 2, [](const pbr_view& v, int k, uintptr_t& lo, uintptr_t& hi) {
+                    if (k == 0) { lo = addr(v.hist256); hi = lo + PBR_HISTOGRAM_BINS * sizeof(uint32_t); }
+                    else { lo = addr(v.avg); hi = lo + sizeof(float); } }),
+                "pbr_lum_average_views: two views share a histogram or luminance cell");
+    hipLaunchKernelGGL(k_lum_average_views, dim3(n), dim3(256), 0, ctx->stream, vs, pixel_count, min_log, range);
+    return launched(ctx, "k_lum_average_views");
+}
+
+pbr_status pbr_tonemap_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, views_count_ok(views, n), "pbr_tonemap_views: need 1 .. PBR_MAX_VIEWS views");
+    PBR_REQUIRE(ctx, w && h && w <= 65535 && h <= 65535, "pbr_tonemap_views: bad size");
+    TonemapViews vs{};
+    for (uint32_t i = 0; i < n; i++) {
+        const pbr_view& v = views[i];
+        PBR_REQUIRE(ctx, v.hdr && v.avg && v.rgba8, "pbr_tonemap_views: null pointer");
+        PBR_REQUIRE(ctx, v.hdr_pitch >= w && v.out_pitch >= w, "pbr_tonemap_views: bad size");
+        vs.hdr[i] = v.hdr; vs.avg[i] = v.avg; vs.out[i] = v.rgba8; vs.pitch[i] = v.hdr_pitch; vs.out_pitch[i] = v.out_pitch;
+        vs.aligned[i] = (((uintptr_t)v.hdr & 15u) == 0u) && (((uintptr_t)v.rgba8 & 7u) == 0u) && (((v.hdr_pitch | v.out_pitch) & 1u) == 0u);
+    }
+    PBR_REQUIRE(ctx, views_disjoint(views, n, 1, [&](const pbr_view& v, int, uintptr_t& lo, uintptr_t& hi) {
+                    lo = addr(v.rgba8); hi = lo + ((size_t)v.out_pitch * (h - 1) + w) * sizeof(uint32_t); }),
+                "pbr_tonemap_views: two views share an LDR target");
+    size_t pairs = (size_t)((w + 1) / 2) * h;   // per view, as pbr_tonemap
+    unsigned blocks = (unsigned)((pairs + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(k_tonemap_views, dim3(blocks, n), dim3(256), 0, ctx->stream, vs, w, h);
+    return launched(ctx, "k_tonemap_views");
 }
 
 }  // extern "C"

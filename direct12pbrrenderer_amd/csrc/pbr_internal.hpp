@@ -72,6 +72,26 @@ inline int knob_int(const char* name, int dflt) { const char* v = knob_text(name
 inline float knob_float(const char* name, float dflt) { const char* v = knob_text(name); return v ? (float)atof(v) : dflt; }
 inline bool knob_set(const char* name) { return knob_text(name) != nullptr; }
 
+// Multi-view calls (pbr_*_views): the view count, and no byte of one view's outputs inside another view's.  range(view, k, lo, hi)
+// gives the byte range [lo, hi) of output k < n_out of a view (null pointers are checked before).
+inline bool views_count_ok(const pbr_view* v, uint32_t n) { return v != nullptr && n >= 1 && n <= (uint32_t)PBR_MAX_VIEWS; }
+template <class F>
+inline bool views_disjoint(const pbr_view* v, uint32_t n, int n_out, F range) {
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t j = i + 1; j < n; j++)
+            for (int a = 0; a < n_out; a++)
+                for (int b = 0; b < n_out; b++) {
+                    uintptr_t a0, a1, b0, b1;
+                    range(v[i], a, a0, a1);
+                    range(v[j], b, b0, b1);
+                    if (a0 < b1 && b0 < a1) return false;
+                }
+    return true;
+}
+inline uintptr_t addr(const void* p) { return (uintptr_t)p; }
+// the view argument of a single-view kernel instantiation: empty; placed in a padding hole of the argument block, it moves no argument
+struct NoViews {};
+
 }  // namespace pbr
 
 #define PBR_REQUIRE(ctx, cond, msg) \

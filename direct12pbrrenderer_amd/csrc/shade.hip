@@ -15,6 +15,7 @@
 //    16-byte load;
 //  * with 256 lights the kernel is FP32-VALU-issue-bound (46 packed + 4 transcendental + 2 plain instructions per pair
 //    of lights, ~500 per pixel around the loop), not HBM-bound.
+#include <cstring>
 #include <type_traits>
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
@@ -522,17 +523,52 @@ extern "C" int pbr_debug_shade_stamps_reset() {
 // grid: rc.first[rc.n] blocks of 256 threads, dispatched in index order (the hardware's dispatcher is the work queue: a software queue
 // of persistent blocks was built and measured in round 6 and lost to it at every size — EXPERIMENTS.md).
 // dynamic LDS: 9 planes * LSTRIDE floats of light data, then (STAGED_LISTS) max_clusters * 136 B of light lists.
-template <bool STAGED_LISTS, int LSTRIDE, bool F32OUT>
 #ifndef SHADE_MIN_WAVES
 #define SHADE_MIN_WAVES 5   // 96 VGPRs; 2 dwords of scratch per lane are spilled OUTSIDE the light loop.  Best of 4..8 measured (tools/probe_shade.py)
 #endif
 // (an exact register budget cannot be asked for: `amdgpu_num_vgpr(104)` is ignored beside the waves-per-EU bound on gfx950 — round 6, EXPERIMENTS.md)
-__global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade(ShadeParams p, int n_lights, int max_clusters, ShadeRects rc) {
+// Multi-view shade (pbr_deferred_shade_views): k_deferred_shade<.., ShadeViews>, grid (blocks of ONE view, views).  p_ holds what the views
+// share (size, LUT, env chain, SH pack); a view's camera, planes, clusters, lights and target come from its ShadeView.
+struct ShadeView {
+    float InvView[9], CameraPos[3];
+    float Near, Far, near_width, near_height, log_far_near, inv_near, slice_k;
+    const uint32_t* A;
+    const uint32_t* B;
+    const uint32_t* C;
+    const float* depth;
+    const uint8_t* stencil;
+    const pbr_cluster* clusters;
+    const pbr_light* lights;
+    pbr_half* hdr;
+    uint32_t pitch, hdr_pitch;
+    int n_lights;
+};
+struct ShadeViews { ShadeView v[PBR_MAX_VIEWS]; };
+static_assert(sizeof(ShadeParams) + sizeof(ShadeViews) + sizeof(ShadeRects) + 16 <= 4096 - 256, "k_deferred_shade<.., ShadeViews>: kernel arguments over 4 KiB");
+
+template <bool STAGED_LISTS, int LSTRIDE, bool F32OUT, class VS = NoViews>
+__global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade(ShadeParams p_, int n_lights_, int max_clusters, ShadeRects rc, VS vs) {
+    constexpr bool MV = !std::is_same_v<VS, NoViews>;   // VS = ShadeViews: view blockIdx.y of vs; NoViews (empty): the single-view kernel
+    ShadeParams q;                                      // MV: p_ with the view's fields
+    int n_views_lights = 0;
+    if constexpr (MV) {
+        const ShadeView& v = vs.v[blockIdx.y];
+        q = p_;
+        for (int i = 0; i < 9; i++) q.InvView[i] = v.InvView[i];
+        for (int i = 0; i < 3; i++) q.CameraPos[i] = v.CameraPos[i];
+        q.Near = v.Near; q.Far = v.Far; q.near_width = v.near_width; q.near_height = v.near_height;
+        q.log_far_near = v.log_far_near; q.inv_near = v.inv_near; q.slice_k = v.slice_k;
+        q.A = v.A; q.B = v.B; q.C = v.C; q.depth = v.depth; q.stencil = v.stencil; q.pitch = v.pitch;
+        q.clusters = v.clusters; q.lights = v.lights; q.hdr = v.hdr; q.hdr_pitch = v.hdr_pitch;
+        n_views_lights = v.n_lights;
+    }
+    const ShadeParams& p = MV ? q : p_;
+    const int n_lights = MV ? n_views_lights : n_lights_;
     extern __shared__ float4 lds_raw[];
     __shared__ uint32_t s_mip_off[16];
     const unsigned long long t_start = SHADE_NOW();
     (void)t_start;
-    if (threadIdx.x < 16) s_mip_off[threadIdx.x] = p.env_mip_off[threadIdx.x];
+    if (threadIdx.x < 16) s_mip_off[threadIdx.x] = p_.env_mip_off[threadIdx.x];   // (p_: a per-lane index into the local copy would live in scratch)
     float* llds = reinterpret_cast<float*>(lds_raw);
     uint32_t* lists = reinterpret_cast<uint32_t*>(llds + ((LIGHT_PLANES * LSTRIDE + 1) & ~1));   // 8-byte aligned
     int my_safe = 1, my_same = 1;
@@ -654,6 +690,31 @@ pbr_status pbr_env_pad(pbr_ctx* ctx, const pbr_half* env, uint32_t size, uint32_
 
 }  // extern "C"
 
+// the camera's part of ShadeParams (host libm, once per call)
+static void camera_params(const pbr_global* g, ShadeParams& p) {
+    p.sh = g->SkyBoxSH;
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) p.InvView[r * 3 + c] = g->InvView[r * 4 + c];
+    for (int i = 0; i < 3; i++) p.CameraPos[i] = g->CameraPos[i];
+    p.Near = g->Near; p.Far = g->Far;
+    p.near_height = 2.0f * g->Near * tanf(g->Fov / 2.0f);
+    p.near_width = p.near_height * g->Ratio;
+    p.log_far_near = logf(g->Far / g->Near);
+    p.inv_near = (float)(1.0 / (double)g->Near);
+    p.slice_k = (float)((double)PBR_CLUSTER_Z / log2((double)g->Far / (double)g->Near));
+}
+
+// Rows of a long block for a launch of `row_segments` 256-pixel row pieces (see shade_launch)
+static uint32_t shade_rows_big(const pbr_ctx* ctx, uint64_t row_segments) {
+    uint32_t rows_big = (uint32_t)SHADE_ROWS;
+    const uint64_t slots = (uint64_t)ctx->cu_count * SHADE_MIN_WAVES;
+    if (row_segments * 10 < slots * 13 * SHADE_ROWS) {
+        const uint32_t rws = (uint32_t)((row_segments * 10 + slots * 8) / (slots * 16));   // round(row_segments / (1.6 slots))
+        rows_big = rws < 2 ? 2u : (rws > (uint32_t)SHADE_ROWS ? (uint32_t)SHADE_ROWS : rws);
+    }
+    return rows_big;
+}
+
 template <bool F32OUT>
 static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
                                const pbr_half* lut, uint32_t lut_res,
@@ -678,16 +739,7 @@ static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile
     PBR_REQUIRE(ctx, num_lights >= 0 && num_lights <= PBR_MAX_SCENE_LIGHTS, "pbr_deferred_shade: light count out of [0, 1024]");
     PBR_REQUIRE(ctx, num_lights == 0 || lights != nullptr, "pbr_deferred_shade: null lights");
     ShadeParams p;
-    p.sh = g->SkyBoxSH;
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) p.InvView[r * 3 + c] = g->InvView[r * 4 + c];
-    for (int i = 0; i < 3; i++) p.CameraPos[i] = g->CameraPos[i];
-    p.Near = g->Near; p.Far = g->Far;
-    p.near_height = 2.0f * g->Near * tanf(g->Fov / 2.0f);
-    p.near_width = p.near_height * g->Ratio;
-    p.log_far_near = logf(g->Far / g->Near);
-    p.inv_near = (float)(1.0 / (double)g->Near);
-    p.slice_k = (float)((double)PBR_CLUSTER_Z / log2((double)g->Far / (double)g->Near));
+    camera_params(g, p);
     p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h; p.full_w = tile->full_w; p.full_h = tile->full_h;
     p.A = gb->A; p.B = gb->B; p.C = gb->C; p.depth = gb->depth; p.stencil = gb->stencil; p.pitch = gb->pitch;
     p.lut = lut; p.lut_res = lut_res; p.env = env; p.env_size = env_size; p.env_mips = env_mips;
@@ -706,15 +758,11 @@ static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile
     // measure best there.  Smaller targets get the row count that makes ~1.6 generations — one generation and a bit (1.1) is the worst
     // place to be: the launch then lasts two block lifetimes for one block's worth of work per slot.  Measured (profiles/r06_j_rows_*,
     // r06_g_*): 1440x960 (the reference's own target, 0.56 generations at 8 rows) 3 rows -10 %; 1920x1080 (0.84) 4 rows -0.5 ... -2.4 %.
-    uint32_t rows_big = (uint32_t)SHADE_ROWS;
+    uint32_t rows_big;
     {
         uint64_t row_segments = 0;   // 256-pixel row pieces of the launch
         for (uint32_t r = 0; r < n_rects; r++) row_segments += (uint64_t)((rects[r][2] + SHADE_BLOCK - 1) / SHADE_BLOCK) * rects[r][3];
-        const uint64_t slots = (uint64_t)ctx->cu_count * SHADE_MIN_WAVES;
-        if (row_segments * 10 < slots * 13 * SHADE_ROWS) {
-            const uint32_t rws = (uint32_t)((row_segments * 10 + slots * 8) / (slots * 16));   // round(row_segments / (1.6 slots))
-            rows_big = rws < 2 ? 2u : (rws > (uint32_t)SHADE_ROWS ? (uint32_t)SHADE_ROWS : rws);
-        }
+        rows_big = shade_rows_big(ctx, row_segments);
         if (rows_big_cfg >= 1 && rows_big_cfg <= (uint32_t)SHADE_ROWS) rows_big = rows_big_cfg;
     }
     ShadeRects rc{};
@@ -744,10 +792,10 @@ static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile
     const int max_clusters = staged ? (int)(span_x * span_y) * PBR_CLUSTER_Z : 0;
     const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t);
     const dim3 blk(SHADE_BLOCK);
-    if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc);
-    else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc);
-    else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc);
-    else hipLaunchKernelGGL((k_deferred_shade<false, PBR_MAX_SCENE_LIGHTS + 1, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc);
+    if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, NoViews{});
+    else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, NoViews{});
+    else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, NoViews{});
+    else hipLaunchKernelGGL((k_deferred_shade<false, PBR_MAX_SCENE_LIGHTS + 1, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, NoViews{});
     return launched(ctx, "k_deferred_shade");
 }
 
@@ -781,6 +829,89 @@ pbr_status pbr_deferred_shade_f32(pbr_ctx* ctx, const pbr_global* g, const pbr_t
                                   float* hdr_f32, uint32_t hdr_pitch) {
     if (ctx && hdr_f32 && ((uintptr_t)hdr_f32 & 15u) != 0) return pbr::fail(ctx, PBR_ERR_INVALID, "pbr_deferred_shade_f32: output must be 16-byte aligned");
     return shade_launch<true>(ctx, g, tile, gb, lut, lut_res, env, env_size, env_mips, clusters, lights, num_lights, nullptr, hdr_f32, hdr_pitch);
+}
+
+// DeferredShadingPass::Execute for up to PBR_MAX_VIEWS whole frames in ONE launch.  Per view exactly pbr_deferred_shade's pixels: the
+// block shape does not enter a pixel's result, and the staged-list decision depends on the frame size alone.  What the batch changes:
+// the long blocks' row count is sized for the whole launch (row pieces of every view), and the LDS light stride is the batch's
+// largest (a layout, not a result).
+pbr_status pbr_deferred_shade_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h,
+                                    const pbr_half* lut, uint32_t lut_res,
+                                    const pbr_half* env, uint32_t env_size, uint32_t env_mips) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, views_count_ok(views, n), "pbr_deferred_shade_views: need 1 .. PBR_MAX_VIEWS views");
+    PBR_REQUIRE(ctx, lut && env, "pbr_deferred_shade_views: null pointer");
+    PBR_REQUIRE(ctx, w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "pbr_deferred_shade_views: bad frame size");
+    PBR_REQUIRE(ctx, lut_res >= 1 && env_size >= 1 && env_mips >= 1 && env_mips <= 16 && (env_size >> (env_mips - 1)) >= 1, "pbr_deferred_shade_views: bad LUT/env size");
+    PBR_REQUIRE(ctx, lut_res <= 16384 && (uint64_t)pbr_env_padded_texels(env_size, env_mips) * 8u < (1ull << 32),
+                "pbr_deferred_shade_views: LUT larger than 16384^2 or padded env chain of 4 GiB or more (32-bit texture offsets)");
+    PBR_REQUIRE(ctx, ((uintptr_t)env & 7u) == 0 && ((uintptr_t)lut & 3u) == 0, "pbr_deferred_shade_views: env must be 8-byte and lut 4-byte aligned");
+    ShadeParams p;
+    camera_params(&views[0].g, p);
+    p.x0 = 0; p.y0 = 0; p.w = w; p.h = h; p.full_w = w; p.full_h = h;
+    p.lut = lut; p.lut_res = lut_res; p.env = env; p.env_size = env_size; p.env_mips = env_mips;
+    for (uint32_t m = 0; m < 16; m++) p.env_mip_off[m] = (uint32_t)env_padded_mip_offset(env_size, m < env_mips ? m : env_mips - 1);
+    p.A = p.B = p.C = nullptr; p.depth = nullptr; p.stencil = nullptr; p.pitch = 0;
+    p.clusters = nullptr; p.lights = nullptr; p.hdr = nullptr; p.hdr_pitch = 0; p.hdr_f32 = nullptr;
+    ShadeViews vs{};
+    int max_lights = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const pbr_view& v = views[i];
+        const pbr_global* g = &v.g;
+        PBR_REQUIRE(ctx, v.clusters && v.hdr, "pbr_deferred_shade_views: null pointer");
+        PBR_REQUIRE(ctx, v.gb.A && v.gb.B && v.gb.C && v.gb.depth && v.gb.stencil, "pbr_deferred_shade_views: null G-buffer plane");
+        PBR_REQUIRE(ctx, v.gb.pitch >= w && v.hdr_pitch >= w, "pbr_deferred_shade_views: pitch < width");
+        PBR_REQUIRE(ctx, (uint64_t)v.gb.pitch * h * 4u < (1ull << 32) && (uint64_t)v.hdr_pitch * h * 16u < (1ull << 32),
+                    "pbr_deferred_shade_views: frame too large for 32-bit plane offsets (pitch x rows x 16 bytes must stay below 4 GiB)");
+        PBR_REQUIRE(ctx, g->Near > 0.0f && g->Far > g->Near, "pbr_deferred_shade_views: need 0 < Near < Far");
+        PBR_REQUIRE(ctx, v.num_lights >= 0 && v.num_lights <= PBR_MAX_SCENE_LIGHTS, "pbr_deferred_shade_views: light count out of [0, 1024]");
+        PBR_REQUIRE(ctx, v.num_lights == 0 || v.lights != nullptr, "pbr_deferred_shade_views: null lights");
+        PBR_REQUIRE(ctx, memcmp(&g->SkyBoxSH, &views[0].g.SkyBoxSH, sizeof(pbr_sh_pack)) == 0, "pbr_deferred_shade_views: SkyBoxSH differs between views");
+        ShadeParams c;
+        camera_params(g, c);
+        ShadeView& d = vs.v[i];
+        for (int k = 0; k < 9; k++) d.InvView[k] = c.InvView[k];
+        for (int k = 0; k < 3; k++) d.CameraPos[k] = c.CameraPos[k];
+        d.Near = c.Near; d.Far = c.Far; d.near_width = c.near_width; d.near_height = c.near_height;
+        d.log_far_near = c.log_far_near; d.inv_near = c.inv_near; d.slice_k = c.slice_k;
+        d.A = v.gb.A; d.B = v.gb.B; d.C = v.gb.C; d.depth = v.gb.depth; d.stencil = v.gb.stencil; d.pitch = v.gb.pitch;
+        d.clusters = v.clusters; d.lights = v.lights; d.hdr = v.hdr; d.hdr_pitch = v.hdr_pitch; d.n_lights = v.num_lights;
+        max_lights = v.num_lights > max_lights ? v.num_lights : max_lights;
+    }
+    PBR_REQUIRE(ctx, views_disjoint(views, n, 1, [&](const pbr_view& v, int, uintptr_t& lo, uintptr_t& hi) {
+                    lo = addr(v.hdr); hi = lo + ((size_t)v.hdr_pitch * (h - 1) + w) * 8u; }),
+                "pbr_deferred_shade_views: two views share an HDR target");
+    // the schedule of shade_launch for one rectangle {0, 0, w, h}, rows_big counted over the whole batch
+    static const float big_frac = pbr::knob_float("PBR_SHADE_BIGFRAC", 0.92f);
+    static const uint32_t rows_small_cfg = (uint32_t)pbr::knob_int("PBR_SHADE_ROWS_SMALL", 1);
+    static const uint32_t rows_big_cfg = (uint32_t)pbr::knob_int("PBR_SHADE_ROWS_BIG", 0);
+    const uint32_t rows_small = rows_small_cfg >= 1 && rows_small_cfg <= (uint32_t)SHADE_ROWS ? rows_small_cfg : 1u;
+    uint32_t rows_big = shade_rows_big(ctx, (uint64_t)((w + SHADE_BLOCK - 1) / SHADE_BLOCK) * h * n);
+    if (rows_big_cfg >= 1 && rows_big_cfg <= (uint32_t)SHADE_ROWS) rows_big = rows_big_cfg;
+    ShadeRects rc{};
+    rc.n = 1; rc.rows_big = rows_big; rc.rows_small = rows_small < rows_big ? rows_small : rows_big;
+    rc.x0[0] = 0; rc.y0[0] = 0; rc.w[0] = w; rc.h[0] = h;
+    rc.cols[0] = (w + SHADE_BLOCK - 1) / SHADE_BLOCK;
+    rc.nb_big[0] = (uint32_t)((float)(h / rows_big) * fminf(fmaxf(big_frac, 0.0f), 1.0f));
+    const uint32_t rest = h - rc.nb_big[0] * rows_big;
+    rc.first[0] = 0;
+    rc.first[1] = rc.cols[0] * (rc.nb_big[0] + (rest + rc.rows_small - 1) / rc.rows_small);
+    const dim3 grid(rc.first[1], n);
+    // staged lists and LDS size as shade_launch decides them for a frame of this size (the stride: the batch's largest light count)
+    const uint32_t span_x = (uint32_t)((uint64_t)(SHADE_BLOCK - 1) * PBR_CLUSTER_X / w) + 2;
+    const uint32_t span_y = (uint32_t)((uint64_t)(SHADE_ROWS - 1) * PBR_CLUSTER_Y / h) + 2;
+    const int lstride = max_lights <= 256 ? 257 : PBR_MAX_SCENE_LIGHTS + 1;
+    const size_t plane_bytes = (size_t)((LIGHT_PLANES * lstride + 1) & ~1) * sizeof(float);
+    const bool staged = span_x * span_y <= (uint32_t)MAX_STAGED_TILES &&
+                        plane_bytes + (size_t)span_x * span_y * PBR_CLUSTER_Z * LIST_STRIDE * sizeof(uint32_t) <= 65536;
+    const int max_clusters = staged ? (int)(span_x * span_y) * PBR_CLUSTER_Z : 0;
+    const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t);
+    const dim3 blk(SHADE_BLOCK);
+    if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, false, ShadeViews>), grid, blk, lds, ctx->stream, p, 0, max_clusters, rc, vs);
+    else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, false, ShadeViews>), grid, blk, lds, ctx->stream, p, 0, max_clusters, rc, vs);
+    else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, false, ShadeViews>), grid, blk, lds, ctx->stream, p, 0, 0, rc, vs);
+    else hipLaunchKernelGGL((k_deferred_shade<false, PBR_MAX_SCENE_LIGHTS + 1, false, ShadeViews>), grid, blk, lds, ctx->stream, p, 0, 0, rc, vs);
+    return launched(ctx, "k_deferred_shade<views>");
 }
 
 }  // extern "C"

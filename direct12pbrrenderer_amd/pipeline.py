@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .api import PbrContext
-from .structs import (ENV_MIPS, HISTOGRAM_BINS, Global, Tile)
+from .structs import (ENV_MIPS, HISTOGRAM_BINS, MAX_VIEWS, GBuffer, Global, Tile, View)
 
 # bloom's cumulative support is ~220 full-res pixels (3 down + 3 up levels of a radius-4 kernel on
 # a 2x pyramid); 256 also keeps every mip of the extended tile on the full frame's texel grid
@@ -552,3 +552,122 @@ class DeferredFrame:
 
     def ldr_numpy(self):
         return self.ldr.cpu().numpy().view(np.uint32)
+
+
+class MultiViewFrame:
+    """N camera views of one scene, w x h whole frames each, rendered as ONE chain of launches per MAX_VIEWS views (the pbr_*_views
+    entry points): clustered -> [sky] -> shade -> bloom + histogram -> average -> tone-map, the frame graph's order.  View v gets the
+    bits a DeferredFrame with the same inputs gets.  The views share the LUT, the env chain and the sky's SH pack (globals[v].SkyBoxSH);
+    each has its own camera (globals[v], DeltaTime included), light array, G-buffer and targets."""
+
+    def __init__(self, ctx: PbrContext, w, h, globals, lights_per_view, lut, lut_res, env, env_size, env_mips=ENV_MIPS, sky=None):
+        """globals: one Global per view; lights_per_view: one LIGHT_DTYPE array per view; env: the plain prefiltered chain (padded
+        here once); sky: optional (cube tensor, size, mips), resolved per view on stencil == 0 pixels before the shade."""
+        if len(globals) != len(lights_per_view) or not globals:
+            raise ValueError("one Global and one light array per view")
+        self.ctx, self.w, self.h, self.n = ctx, int(w), int(h), len(globals)
+        self.sky = sky
+        self.lut, self.lut_res, self.env_size, self.env_mips = lut, lut_res, env_size, env_mips
+        self.env = ctx.env_pad(env, env_size, env_mips)
+        self.n_lights = [int(len(l)) for l in lights_per_view]
+        self.lights = [ctx.upload(l) if len(l) else None for l in lights_per_view]
+        self.clusters = [ctx.alloc_clusters() for _ in range(self.n)]
+        self.hdrs = [ctx.zeros((self.h, self.w, 4), torch.float16) for _ in range(self.n)]
+        self.chain_a = [ctx.alloc_bloom_chain(self.w, self.h) for _ in range(self.n)]
+        self.chain_b = [ctx.alloc_bloom_chain(self.w, self.h) for _ in range(self.n)]
+        self.hist = [ctx.zeros((HISTOGRAM_BINS,), torch.int32) for _ in range(self.n)]
+        self.avg = [ctx.zeros((1,), torch.float32) for _ in range(self.n)]
+        self.ldr = [ctx.zeros((self.h, self.w), torch.int32) for _ in range(self.n)]
+        self.gb = None
+        self.tile = Tile(0, 0, self.w, self.h, self.w, self.h)
+        self.globals = list(globals)
+        self._batches = None
+
+    def upload_gbuffers(self, gbs):
+        """gbs: one dict of numpy planes (h x w) per view."""
+        if len(gbs) != self.n:
+            raise ValueError(f"{len(gbs)} G-buffers for {self.n} views")
+        for gb in gbs:
+            assert gb["A"].shape == (self.h, self.w)
+        self.gb = [{k: self.ctx.upload(v) for k, v in gb.items()} for gb in gbs]
+        self._build()
+
+    def set_globals(self, globals):
+        """new cameras / DeltaTime for the following frames"""
+        if len(globals) != self.n:
+            raise ValueError(f"{len(globals)} cameras for {self.n} views")
+        self.globals = list(globals)
+        if self.gb is not None:
+            self._build()
+
+    def set_prev_luminance(self, values):
+        vals = [float(values)] * self.n if np.isscalar(values) else [float(v) for v in values]
+        if len(vals) != self.n:
+            raise ValueError(f"{len(vals)} luminance values for {self.n} views")
+        for a, v in zip(self.avg, vals):
+            a.fill_(v)
+
+    def _view(self, v):
+        gb = self.gb[v]
+        return View(self.globals[v], GBuffer(gb["A"].data_ptr(), gb["B"].data_ptr(), gb["C"].data_ptr(), gb["depth"].data_ptr(),
+                                             gb["stencil"].data_ptr(), self.w),
+                    self.lights[v].data_ptr() if self.lights[v] is not None else None, self.n_lights[v], self.clusters[v].data_ptr(),
+                    self.hdrs[v].data_ptr(), self.w, self.chain_a[v].data_ptr(), self.chain_b[v].data_ptr(), self.hist[v].data_ptr(),
+                    self.avg[v].data_ptr(), self.ldr[v].data_ptr(), self.w)
+
+    def _build(self):
+        """the View arrays of the calls: MAX_VIEWS views per call"""
+        self._batches = []
+        for b0 in range(0, self.n, MAX_VIEWS):
+            idx = list(range(b0, min(b0 + MAX_VIEWS, self.n)))
+            self._batches.append(((View * len(idx))(*[self._view(v) for v in idx]), len(idx), idx))
+
+    # ---- the frame's stages, each one call per MAX_VIEWS views
+    def _calls(self):
+        if self._batches is None:
+            raise RuntimeError("upload_gbuffers() first")
+        return self._batches
+
+    def clustered(self):
+        for arr, n, _ in self._calls():
+            self.ctx.clustered_views(arr, n)
+
+    def skybox(self):
+        """the sky resolve stays one launch per view"""
+        cube, size, mips = self.sky
+        for v in range(self.n):
+            self.ctx.skybox(self.globals[v], self.tile, cube, size, mips, self.gb[v]["stencil"], self.w, self.hdrs[v], self.w)
+
+    def shade(self):
+        for arr, n, _ in self._calls():
+            self.ctx.deferred_shade_views(arr, n, self.w, self.h, self.lut, self.lut_res, self.env, self.env_size, self.env_mips)
+
+    def bloom_histogram(self):
+        for arr, n, _ in self._calls():
+            self.ctx.bloom_histogram_views(arr, n, self.w, self.h)
+
+    def average(self):
+        for arr, n, _ in self._calls():
+            self.ctx.lum_average_views(arr, n, self.w * self.h)
+
+    def tonemap(self):
+        for arr, n, _ in self._calls():
+            self.ctx.tonemap_views(arr, n, self.w, self.h)
+
+    def render(self):
+        """One frame of every view: clustered -> [sky] -> shade -> bloom + histogram -> average -> tone-map."""
+        self.clustered()
+        if self.sky is not None:
+            self.skybox()
+        self.shade()
+        self.bloom_histogram()
+        self.average()
+        self.tonemap()
+
+    # ---- read-back helpers for tests
+    def hdr(self, v):
+        """view v's HDR target (h x w x 4 fp16 device tensor)"""
+        return self.hdrs[v]
+
+    def ldr_numpy(self, v):
+        return self.ldr[v].cpu().numpy().view(np.uint32)

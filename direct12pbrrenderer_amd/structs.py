@@ -66,6 +66,28 @@ class GBuffer(C.Structure):
     ]
 
 
+MAX_VIEWS = 16                                        # PBR_MAX_VIEWS (include/pbr_hip.h)
+
+
+class View(C.Structure):
+    """pbr_view: the per-view camera and device buffers of a multi-view call (include/pbr_hip.h)."""
+    _fields_ = [
+        ("g", Global),
+        ("gb", GBuffer),
+        ("lights", C.c_void_p),
+        ("num_lights", C.c_int32),
+        ("clusters", C.c_void_p),
+        ("hdr", C.c_void_p),
+        ("hdr_pitch", C.c_uint32),
+        ("chain_a", C.c_void_p),
+        ("chain_b", C.c_void_p),
+        ("hist256", C.c_void_p),
+        ("avg", C.c_void_p),
+        ("rgba8", C.c_void_p),
+        ("out_pitch", C.c_uint32),
+    ]
+
+
 class HaloPeer(C.Structure):
     """pbr_halo_peer: rectangles {x, y, w, h} of the level-1 plane exchanged with rank `rank`."""
     _fields_ = [("rank", C.c_int32), ("send", C.c_uint32 * 4), ("recv", C.c_uint32 * 4)]

@@ -362,6 +362,49 @@ pbr_status pbr_tonemap(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h
 pbr_status pbr_average_tonemap(pbr_ctx* ctx, const uint32_t* hist256, uint32_t pixel_count, float min_log, float range, float delta_time,
                                const float* avg_in, float* avg_out, uint32_t* hist_clear256,
                                const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch, uint32_t* rgba8, uint32_t out_pitch);
+
+/* ---- multi-view frames (new): N camera views of one scene per launch -------------------------------------------------- */
+/* The reference renders one camera per FrameGraph; these entry points run the per-frame dispatches of up to PBR_MAX_VIEWS
+ * equal-sized whole frames (w x h each, no tiles) as ONE launch chain (the view index in the grid; the average: one block per view).  Every view
+ * gets exactly the bits its own single-view call would give: each kernel choice (exact-half vs staged bloom levels, polyphase
+ * vs k_blur_hv, 16- vs 32-row tiles, staged cluster lists) follows one view's size, never the batch's.  Bloom levels that are
+ * not an exact half (1920 x 1080 from level 3 down) run the staged single-view kernels once per view.
+ * Shared by all views of a call: the size, the LUT, the padded env chain and the sky's SH pack (SkyBoxSH must be equal).
+ * Errors (PBR_ERR_INVALID, nothing enqueued): n == 0 or n > PBR_MAX_VIEWS, a null pointer the call uses, SkyBoxSH that
+ * differs between views, two views whose output buffers overlap, and every limit of the single-view call. */
+#define PBR_MAX_VIEWS 16
+typedef struct pbr_view {
+    pbr_global       g;          /* camera, DeltaTime; SkyBoxSH must be the same in every view of a call */
+    pbr_gbuffer      gb;         /* device planes of w x h pixels */
+    const pbr_light* lights;     /* device, num_lights <= 1024 records; may alias another view's */
+    int32_t          num_lights;
+    pbr_cluster*     clusters;   /* device, PBR_NUM_CLUSTERS */
+    pbr_half*        hdr;        /* device, w x h half4, pitch hdr_pitch pixels */
+    uint32_t         hdr_pitch;
+    pbr_half*        chain_a;    /* device, pbr_bloom_chain_texels(w, h) half4 each (scratch) */
+    pbr_half*        chain_b;
+    uint32_t*        hist256;    /* device, 256 bins */
+    float*           avg;        /* device, the adapted-luminance cell */
+    uint32_t*        rgba8;      /* device, w x h RGBA8, pitch out_pitch pixels */
+    uint32_t         out_pitch;
+} pbr_view;
+
+/* ClusteredPass::Execute (DeferredPipeline.cpp:253-256) per view: pbr_clustered on every view (g, lights, num_lights, clusters). */
+pbr_status pbr_clustered_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n);
+/* DeferredShadingPass::Execute (DeferredPipeline.cpp:187-206) per view: pbr_deferred_shade of the whole w x h frame
+ * (g, gb, clusters, lights, num_lights -> hdr). */
+pbr_status pbr_deferred_shade_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h,
+                                    const pbr_half* lut, uint32_t lut_res,
+                                    const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips);
+/* BloomPass::Execute (DeferredPipeline.cpp:400-570) + the histogram dispatch (:276-298) per view: pbr_bloom_histogram of the
+ * whole frame (hdr, chain_a, chain_b -> hist256, which it ADDS into). */
+pbr_status pbr_bloom_histogram_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h,
+                                     float threshold, float knee, float min_log, float inv_range);
+/* hdr_average_histogram.hlsl (DeferredPipeline.cpp:300-317) per view: pbr_lum_average(hist256, pixel_count, g.DeltaTime, avg). */
+pbr_status pbr_lum_average_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t pixel_count, float min_log, float range);
+/* hdr_tone_mapping.hlsl (DeferredPipeline.cpp:320-336) per view: pbr_tonemap(hdr, avg -> rgba8) of the whole frame. */
+pbr_status pbr_tonemap_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h);
+
 /* ---- multi-GPU (new) -------------------------------------------------------------- */
 /* RCCL communicator over the ranks of one node.  unique_id: 128 bytes from
  * pbr_comm_unique_id() on rank 0, broadcast by the caller (e.g. torch.distributed store). */
