@@ -891,17 +891,23 @@ static int blur_h_rows(uint32_t ow, uint32_t oh) {
 // on its dyadic value (coordinate error ~4 * 2^-24 * size must stay below half a 1/256 step)
 static bool exact_half(uint32_t n) { return (n & 1u) == 0u && n <= 8192u; }
 
-template <int MODE, bool DUAL, int TAIL>
-static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint32_t ih, const pbr_half* in2,
-                            pbr_half* out, uint32_t ow, uint32_t oh, uint32_t out_pitch,
-                            const uint32_t* rect, float min_log, float inv_range, uint32_t* hist,
-                            const uint32_t* merge_rect = nullptr, const uint32_t* buf_origin = nullptr,
-                            const LevelViews* views = nullptr, uint32_t nv = 0) {
-    // rect: histogram rect {x,y,w,h}; merge_rect: HDR texels to merge (default: the whole level); buf_origin: level
-    // coordinates of out[0] (default 0,0).  views: nv views of this level (pointer arguments unused) — the kernel choice is the one
-    // a single view of the level gets; grid (blocks, nv)
-    // (the instances pbr_bloom_histogram_views runs: the 2x-down pairs, the dual up-levels and the merge + histogram tail)
-    constexpr bool VIEWS_OK = TAIL != 1 && (MODE != M_UP || DUAL || TAIL == 2);
+// One fused level (k_blur_hv / k_blur_up_poly) of nv views.  lv holds each view's input, second input (DUAL), output, output pitch and
+// histogram.  MV = false: one view, the single-view kernel with view 0's pointers as its own arguments; MV: the view-table instance,
+// grid (blocks, nv), whose kernel choice is the one a single view of the level gets.
+// rect: histogram rect {x,y,w,h}; merge_rect: HDR texels to merge (default: the whole level); buf_origin: level coordinates of out[0]
+// (default 0,0).
+template <int MODE, bool DUAL, int TAIL, bool MV = false>
+static pbr_status launch_hv(pbr_ctx* ctx, const LevelViews& lv, uint32_t nv, uint32_t iw, uint32_t ih, uint32_t ow, uint32_t oh,
+                            const uint32_t* rect, float min_log, float inv_range,
+                            const uint32_t* merge_rect = nullptr, const uint32_t* buf_origin = nullptr) {
+    using VS = std::conditional_t<MV, LevelViews, NoViews>;
+    VS vs{};
+    if constexpr (MV) vs = lv;
+    const pbr_half* in = MV ? nullptr : lv.in[0];   // (MV: the pointer arguments are unused)
+    const pbr_half* in2 = MV ? nullptr : lv.in2[0];
+    pbr_half* out = MV ? nullptr : lv.out[0];
+    uint32_t* hist = MV ? nullptr : lv.hist[0];
+    const int out_pitch = MV ? 0 : lv.out_pitch[0];
     TailRect tr;
     tr.hx0 = rect ? (int)rect[0] : 0; tr.hy0 = rect ? (int)rect[1] : 0;
     tr.hx1 = rect ? (int)(rect[0] + rect[2]) : 0; tr.hy1 = rect ? (int)(rect[1] + rect[3]) : 0;
@@ -912,8 +918,7 @@ static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint3
     // half empty for the last round; one block per tile costs 256 contended global atomics per tile)
     static const int hist_blocks = pbr::knob_int("PBR_BLOOM_HIST_BLOCKS", 1024);
     // (views: ~1024 blocks over the whole batch, each walking one view's tiles)
-    const int nvb = views ? (int)nv : 1;
-    auto even_blocks = [nvb](int n_tiles) { const int per = (n_tiles * nvb + hist_blocks - 1) / hist_blocks; return (n_tiles + per - 1) / per; };
+    auto even_blocks = [nv](int n_tiles) { const int per = (n_tiles * (int)nv + hist_blocks - 1) / hist_blocks; return (n_tiles + per - 1) / per; };
     if constexpr (MODE == M_UP) {
         // 2x-up levels big enough to fill the chip with 128 x 32 tiles: k_blur_up_poly, two columns per lane (PBR_BLOOM_WIDE=0|1 forces)
         static const int wide_forced = pbr::knob_int("PBR_BLOOM_WIDE", -1);
@@ -922,16 +927,9 @@ static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint3
         if (wide_forced >= 0 ? wide_forced == 1 : (wn >= 400 && !ctx->bloom_shader_order)) {
             tr.tx0 = wtx0; tr.ty0 = wty0;
             const int wb = TAIL == 2 ? even_blocks(wn) : wn;
-            if constexpr (VIEWS_OK) {
-                if (views) {
-                    hipLaunchKernelGGL((k_blur_up_poly<DUAL, TAIL, 32, LevelViews>), dim3(wb, nv), dim3(512), 0, ctx->stream,
-                                       nullptr, (int)iw, (int)ih, nullptr, nullptr, (int)ow, (int)oh, 0, wtiles_x, wn, tr, min_log, inv_range, *views, nullptr);
-                    return launched(ctx, "k_blur_up_poly<views>");
-                }
-            }
-            hipLaunchKernelGGL((k_blur_up_poly<DUAL, TAIL, 32>), dim3(wb), dim3(512), 0, ctx->stream,
-                               in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, wtiles_x, wn, tr, min_log, inv_range, NoViews{}, hist);
-            return launched(ctx, "k_blur_up_poly");
+            hipLaunchKernelGGL((k_blur_up_poly<DUAL, TAIL, 32, VS>), dim3(wb, nv), dim3(512), 0, ctx->stream,
+                               in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, out_pitch, wtiles_x, wn, tr, min_log, inv_range, vs, hist);
+            return launched(ctx, MV ? "k_blur_up_poly<views>" : "k_blur_up_poly");
         }
     }
     // 64 x 32 tiles (512 threads) when the level is large enough to fill the chip that way, 64 x 16 below
@@ -942,48 +940,42 @@ static pbr_status launch_hv(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint3
     const int tiles_x = (tr.mx1 + 63) / 64 - tr.tx0;
     const int n_tiles = tiles_x * ((tr.my1 + th - 1) / th - tr.ty0);
     const int blocks = TAIL == 2 ? even_blocks(n_tiles) : n_tiles;
-    if constexpr (VIEWS_OK) {
-        if (views) {
-            if (big)
-                hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 32, 512, LevelViews>), dim3(blocks, nv), dim3(512), 0, ctx->stream,
-                                   nullptr, (int)iw, (int)ih, nullptr, nullptr, (int)ow, (int)oh, 0, tiles_x, n_tiles, tr, min_log, inv_range, *views, nullptr);
-            else
-                hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 16, 512, LevelViews>), dim3(blocks, nv), dim3(512), 0, ctx->stream,
-                                   nullptr, (int)iw, (int)ih, nullptr, nullptr, (int)ow, (int)oh, 0, tiles_x, n_tiles, tr, min_log, inv_range, *views, nullptr);
-            return launched(ctx, "k_blur_hv<views>");
-        }
-    }
     if (big) {
-        hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 32, 512>), dim3(blocks), dim3(512), 0, ctx->stream,
-                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, NoViews{}, hist);
+        hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 32, 512, VS>), dim3(blocks, nv), dim3(512), 0, ctx->stream,
+                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, vs, hist);
     } else {
         // small levels are latency-bound (one tile's dependent chain + the launch): 64 x 16 tiles on EIGHT waves — 3 H rows per
         // wave, 2 outputs per thread — shorten the chain; the five small launches of a 4K frame take ~5 us less together
-        hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 16, 512>), dim3(blocks), dim3(512), 0, ctx->stream,
-                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, (int)out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, NoViews{}, hist);
+        hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 16, 512, VS>), dim3(blocks, nv), dim3(512), 0, ctx->stream,
+                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, vs, hist);
     }
-    return launched(ctx, "k_blur_hv");
+    return launched(ctx, MV ? "k_blur_hv<views>" : "k_blur_hv");
+}
+
+// the shared-sample prefilter's rectangle table (rcs: n output rectangles sharing one destination offset / pitch)
+static OutRects out_rects(const OutRect* rcs, int n) {
+    OutRects rs{};
+    rs.n = n; rs.ox = rcs[0].ox; rs.oy = rcs[0].oy; rs.pitch = rcs[0].pitch;
+    int blocks = 0;
+    for (int r = 0; r < n; r++) {
+        rs.x0[r] = rcs[r].x0; rs.y0[r] = rcs[r].y0; rs.x1[r] = rcs[r].x1; rs.y1[r] = rcs[r].y1;
+        rs.tiles_x[r] = (rcs[r].x1 - rcs[r].x0 + PF_TW - 1) / PF_TW;
+        rs.first[r] = blocks;
+        blocks += rs.tiles_x[r] * ((rcs[r].y1 - rcs[r].y0 + PF_TH - 1) / PF_TH);
+    }
+    rs.first[n] = blocks;
+    return rs;
 }
 
 extern "C" {
 
-// rcs: n output rectangles sharing one destination offset / pitch
 static pbr_status prefilter_launch(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
                                    pbr_half* out, const OutRect* rcs, int n, float threshold, float knee) {
     const uint32_t ow = w >> 1, oh = h >> 1;
     const float tx = 1.0f / (float)ow, ty = 1.0f / (float)oh;   // DeferredPipeline.cpp:418
     if (exact_half(w) && exact_half(h)) {   // shared-sample kernel (bit-identical), all rectangles in one launch
-        OutRects rs{};
-        rs.n = n; rs.ox = rcs[0].ox; rs.oy = rcs[0].oy; rs.pitch = rcs[0].pitch;
-        int blocks = 0;
-        for (int r = 0; r < n; r++) {
-            rs.x0[r] = rcs[r].x0; rs.y0[r] = rcs[r].y0; rs.x1[r] = rcs[r].x1; rs.y1[r] = rcs[r].y1;
-            rs.tiles_x[r] = (rcs[r].x1 - rcs[r].x0 + PF_TW - 1) / PF_TW;
-            rs.first[r] = blocks;
-            blocks += rs.tiles_x[r] * ((rcs[r].y1 - rcs[r].y0 + PF_TH - 1) / PF_TH);
-        }
-        rs.first[n] = blocks;
-        hipLaunchKernelGGL(k_bloom_prefilter_2x<NoViews>, dim3(blocks), dim3(256), 0, ctx->stream, hdr, (int)w, (int)h, (int)pitch, NoViews{}, out, rs, threshold, knee);
+        const OutRects rs = out_rects(rcs, n);
+        hipLaunchKernelGGL(k_bloom_prefilter_2x<NoViews>, dim3(rs.first[n]), dim3(256), 0, ctx->stream, hdr, (int)w, (int)h, (int)pitch, NoViews{}, out, rs, threshold, knee);
         return launched(ctx, "k_bloom_prefilter_2x");
     }
     for (int r = 0; r < n; r++) {
@@ -1080,8 +1072,10 @@ pbr_status pbr_bloom_up_level(pbr_ctx* ctx, const pbr_half* upper, const pbr_hal
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, lower && out && out != lower && out != upper, "pbr_bloom_up_level: null pointer / out aliases an input");
     PBR_REQUIRE(ctx, lw >= 1 && lh >= 1 && ow == 2 * lw && oh == 2 * lh && exact_half(ow) && exact_half(oh), "pbr_bloom_up_level: out must be exactly twice lower, even, <= 8192");
-    if (upper) return launch_hv<M_UP, true, 0>(ctx, lower, lw, lh, upper, out, ow, oh, ow, nullptr, 0.0f, 0.0f, nullptr);
-    return launch_hv<M_UP, false, 0>(ctx, lower, lw, lh, nullptr, out, ow, oh, ow, nullptr, 0.0f, 0.0f, nullptr);
+    LevelViews lv{};
+    lv.in[0] = lower; lv.in2[0] = upper; lv.out[0] = out; lv.out_pitch[0] = (int)ow;
+    if (upper) return launch_hv<M_UP, true, 0>(ctx, lv, 1, lw, lh, ow, oh, nullptr, 0.0f, 0.0f);
+    return launch_hv<M_UP, false, 0>(ctx, lv, 1, lw, lh, ow, oh, nullptr, 0.0f, 0.0f);
 }
 
 static pbr_status bloom_final(pbr_ctx* ctx, const pbr_half* b0, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
@@ -1100,42 +1094,70 @@ static pbr_status bloom_final(pbr_ctx* ctx, const pbr_half* b0, pbr_half* hdr, u
     return launched(ctx, "k_blur_v_merge");
 }
 
-// Levels 1..4 of BloomPass::Execute from a filled level 1 of chain A: the three downsample pairs and the three
-// upsample-add pairs (DeferredPipeline.cpp:428-540).  *res = where the finished level 1 lives (chain A or B).
-// need0 (optional): the rectangle {x, y, w, h} of level 0 the caller will merge.  The up-pass of level l is then run only on the tiles
-// of level l the finished image inside need0 depends on — the rectangle shrinks towards need0 / 2^l as the remaining filter support
-// does (a tiled frame's bloom works on the tile +- 256 px, but only the DOWN-pass needs that apron in full: SURVEY 8e's "cheaper
-// apron").  Whole tiles are computed, so every texel inside the rectangles is what the full pass computes: the merged interior is
-// bit-identical.  Texels of the up-levels outside them are left as they were (the chains are scratch).
-static pbr_status bloom_pyramid(pbr_ctx* ctx, uint32_t w, uint32_t h, pbr_half* A, pbr_half* B, const pbr_half** res_out, const uint32_t* need0 = nullptr) {
-    auto a = [&](uint32_t l) { return A + 4 * pbr_bloom_level_offset(w, h, l); };
-    auto b = [&](uint32_t l) { return B + 4 * pbr_bloom_level_offset(w, h, l); };
+}  // extern "C"
+
+// One view of a bloom pass: its HDR target (w x h, pitch), the two chains and its histogram (null: no histogram)
+struct BloomView { pbr_half* hdr; uint32_t pitch; pbr_half* A; pbr_half* B; uint32_t* hist; };
+
+// BloomPass::Execute (DeferredPipeline.cpp:400-570; schedule comment :379-399) + the histogram dispatch of AutoExposurePass::Execute
+// (DeferredPipeline.cpp:276-298) on n views of one size: the prefilter into level 1 of chain A (if `prefilter`), the three downsample
+// pairs, the three upsample-add pairs and the level-0 H + V + merge (+ histogram of hist_rect).  MV = false: one view on the single-view
+// kernels; MV: up to PBR_MAX_VIEWS views, every fused kernel in one launch with the view table (grid (blocks of one view, views)).
+//
+// Per level pair: where level l+1 is exactly half of level l (and both fit the fast path's size limit) the H and V pass run as one
+// kernel and the H result (chain B of the reference schedule) is never written; elsewhere the two staged kernels run, once per view.
+// 1920x1080, for instance, is exact down to 240x135 and staged for 135 -> 67.  Fused up-levels write chain B (a block must not
+// overwrite what its neighbours still read), so `res_in_b` tracks where the finished level below lives.  Chain contents after the call
+// are scratch.
+//
+// merge0 (one view, exact level 0 only): the rectangle {x, y, w, h} of level 0 to merge; origin: its level coordinates of hdr[0].  The
+// up-pass of level l is then run only on the tiles of level l the finished image inside merge0 depends on — the rectangle shrinks
+// towards merge0 / 2^l as the remaining filter support does (a tiled frame's bloom works on the tile +- 256 px, but only the DOWN-pass
+// needs that apron in full: SURVEY 8e's "cheaper apron").  Whole tiles are computed, so every texel inside the rectangles is what the
+// full pass computes: the merged interior is bit-identical.  Texels of the up-levels outside them are left as they were.
+template <bool MV>
+static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint32_t w, uint32_t h, bool prefilter, float threshold, float knee,
+                             const uint32_t* hist_rect, float min_log, float inv_range, const uint32_t* merge0 = nullptr, const uint32_t* origin = nullptr) {
     auto W = [&](uint32_t l) { return w >> l; };
     auto H = [&](uint32_t l) { return h >> l; };
-    pbr_status r;
-    // Per level pair: where level l+1 is exactly half of level l (and both fit the fast path's size limit) the H and V
-    // pass run as one kernel and the H result (chain B of the reference schedule) is never written; elsewhere the two
-    // staged kernels run.  1920x1080, for instance, is exact down to 240x135 and staged for 135 -> 67.  Fused up-levels
-    // write chain B (a block must not overwrite what its neighbours still read), so `res` tracks where the finished
-    // level below lives.  Chain contents after the call are scratch.
+    auto off = [&](uint32_t l) { return (size_t)4 * pbr_bloom_level_offset(w, h, l); };
     auto exact = [&](uint32_t l) { return exact_half(W(l)) && exact_half(H(l)); };
-    for (uint32_t i = 0; i < PBR_BLOOM_STEP; i++) {   // downsample
-        const uint32_t up = i + 1, lo = i + 2;
-        if (exact(up)) {
-            if ((r = launch_hv<M_DOWN, false, 0>(ctx, a(up), W(up), H(up), nullptr, a(lo), W(lo), H(lo), W(lo), nullptr, 0.0f, 0.0f, nullptr))) return r;
+    pbr_status r;
+    if (prefilter) {   // hdr -> level 1 of chain A
+        const OutRect whole{0, 0, (int)W(1), (int)H(1), 0, 0, (int)W(1)};
+        if (MV && exact(0)) {
+            PrefilterViews pv{};
+            for (uint32_t i = 0; i < n; i++) { pv.hdr[i] = v[i].hdr; pv.out[i] = v[i].A + off(1); pv.pitch[i] = (int)v[i].pitch; }
+            const OutRects rs = out_rects(&whole, 1);
+            hipLaunchKernelGGL(k_bloom_prefilter_2x<PrefilterViews>, dim3(rs.first[1], n), dim3(256), 0, ctx->stream,
+                               nullptr, (int)w, (int)h, 0, pv, nullptr, rs, threshold, knee);
+            if ((r = launched(ctx, "k_bloom_prefilter_2x<views>"))) return r;
         } else {
-            if ((r = pbr_blur_h(ctx, a(up), W(up), H(up), b(lo), W(lo), H(lo)))) return r;
-            if ((r = pbr_blur_v(ctx, b(lo), W(lo), H(lo), a(lo), W(lo), H(lo)))) return r;
+            for (uint32_t i = 0; i < n; i++)
+                if ((r = prefilter_launch(ctx, v[i].hdr, w, h, v[i].pitch, v[i].A + off(1), &whole, 1, threshold, knee))) return r;
         }
     }
-    // rectangles of the up-levels (level coordinates): level 1's result is read by the merge within need0 / 2 +- 3 texels (nine taps one
+    for (uint32_t k = 0; k < PBR_BLOOM_STEP; k++) {   // downsample
+        const uint32_t up = k + 1, lo = k + 2;
+        if (exact(up)) {
+            LevelViews lv{};
+            for (uint32_t i = 0; i < n; i++) { lv.in[i] = v[i].A + off(up); lv.out[i] = v[i].A + off(lo); lv.out_pitch[i] = (int)W(lo); }
+            if ((r = launch_hv<M_DOWN, false, 0, MV>(ctx, lv, n, W(up), H(up), W(lo), H(lo), nullptr, 0.0f, 0.0f))) return r;
+        } else {
+            for (uint32_t i = 0; i < n; i++) {
+                if ((r = pbr_blur_h(ctx, v[i].A + off(up), W(up), H(up), v[i].B + off(lo), W(lo), H(lo)))) return r;
+                if ((r = pbr_blur_v(ctx, v[i].B + off(lo), W(lo), H(lo), v[i].A + off(lo), W(lo), H(lo)))) return r;
+            }
+        }
+    }
+    // rectangles of the up-levels (level coordinates): level 1's result is read by the merge within merge0 / 2 +- 3 texels (nine taps one
     // level-0 texel apart + the bilinear footprint); level l's up-pass reads the level below within +- 4 of its own taps, halved, + the
     // bilinear footprint.  Margins are rounded up: a superset costs a tile at most
     uint32_t need[PBR_BLOOM_MIPS][4];
     static const bool shrink = pbr::knob_int("PBR_BLOOM_SHRINK", 1) != 0;
-    const bool use_need = need0 != nullptr && shrink;
+    const bool use_need = merge0 != nullptr && shrink;
     if (use_need) {
-        int x0 = (int)need0[0], y0 = (int)need0[1], x1 = (int)(need0[0] + need0[2]), y1 = (int)(need0[1] + need0[3]);
+        int x0 = (int)merge0[0], y0 = (int)merge0[1], x1 = (int)(merge0[0] + merge0[2]), y1 = (int)(merge0[1] + merge0[3]);
         for (uint32_t l = 1; l < PBR_BLOOM_MIPS; l++) {
             x0 = (x0 - 4) / 2 - 2; y0 = (y0 - 4) / 2 - 2; x1 = (x1 + 4 + 1) / 2 + 2; y1 = (y1 + 4 + 1) / 2 + 2;   // (C division of a negative numerator rounds towards 0: clipped below anyway)
             const int cx0 = x0 < 0 ? 0 : x0, cy0 = y0 < 0 ? 0 : y0, cx1 = x1 > (int)W(l) ? (int)W(l) : x1, cy1 = y1 > (int)H(l) ? (int)H(l) : y1;
@@ -1143,22 +1165,42 @@ static pbr_status bloom_pyramid(pbr_ctx* ctx, uint32_t w, uint32_t h, pbr_half* 
             x0 = cx0; y0 = cy0; x1 = cx1; y1 = cy1;
         }
     }
-    const pbr_half* res = a(PBR_BLOOM_MIPS - 1);
-    for (int i = PBR_BLOOM_STEP - 1; i >= 0; i--) {   // upsample: V(H(lower) + H(upper))
-        const uint32_t up = (uint32_t)i + 1;
+    bool res_in_b = false;
+    uint32_t res_level = PBR_BLOOM_MIPS - 1;
+    auto res = [&](uint32_t i) { return (const pbr_half*)(res_in_b ? v[i].B : v[i].A) + off(res_level); };
+    for (int k = PBR_BLOOM_STEP - 1; k >= 0; k--) {   // upsample: V(H(lower) + H(upper))
+        const uint32_t up = (uint32_t)k + 1;
         if (exact(up)) {
-            if ((r = launch_hv<M_UP, true, 0>(ctx, res, W(up + 1), H(up + 1), a(up), b(up), W(up), H(up), W(up), nullptr, 0.0f, 0.0f, nullptr,
-                                              use_need ? need[up] : nullptr))) return r;
-            res = b(up);
+            LevelViews lv{};
+            for (uint32_t i = 0; i < n; i++) { lv.in[i] = res(i); lv.in2[i] = v[i].A + off(up); lv.out[i] = v[i].B + off(up); lv.out_pitch[i] = (int)W(up); }
+            if ((r = launch_hv<M_UP, true, 0, MV>(ctx, lv, n, W(up + 1), H(up + 1), W(up), H(up), nullptr, 0.0f, 0.0f,
+                                                  use_need ? need[up] : nullptr))) return r;
+            res_in_b = true;
         } else {
-            if ((r = pbr_bloom_upsample_add(ctx, a(up), W(up), H(up), res, W(up + 1), H(up + 1), b(up)))) return r;
-            if ((r = pbr_blur_v(ctx, b(up), W(up), H(up), a(up), W(up), H(up)))) return r;
-            res = a(up);
+            for (uint32_t i = 0; i < n; i++) {
+                if ((r = pbr_bloom_upsample_add(ctx, v[i].A + off(up), W(up), H(up), res(i), W(up + 1), H(up + 1), v[i].B + off(up)))) return r;
+                if ((r = pbr_blur_v(ctx, v[i].B + off(up), W(up), H(up), v[i].A + off(up), W(up), H(up)))) return r;
+            }
+            res_in_b = false;
         }
+        res_level = up;
     }
-    *res_out = res;
+    if (exact(0)) {   // H + V + merge (+ histogram) in one kernel
+        LevelViews lv{};
+        for (uint32_t i = 0; i < n; i++) { lv.in[i] = res(i); lv.out[i] = v[i].hdr; lv.out_pitch[i] = (int)v[i].pitch; lv.hist[i] = v[i].hist; }
+        if constexpr (!MV)
+            if (!v[0].hist) return launch_hv<M_UP, false, 1>(ctx, lv, 1, w >> 1, h >> 1, w, h, nullptr, 0.0f, 0.0f, merge0, origin);
+        return launch_hv<M_UP, false, 2, MV>(ctx, lv, n, w >> 1, h >> 1, w, h, hist_rect, min_log, inv_range, merge0, origin);
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        if ((r = pbr_blur_h(ctx, res(i), w >> 1, h >> 1, v[i].B, w, h))) return r;   // level 0 of chain B
+        // A0 = V(B0); S += A0 [; histogram(S)] in one pass — chain A level 0 is not materialised
+        if ((r = bloom_final(ctx, v[i].B, v[i].hdr, w, h, v[i].pitch, hist_rect, min_log, inv_range, v[i].hist))) return r;
+    }
     return PBR_OK;
 }
+
+extern "C" {
 
 static pbr_status bloom_impl(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch, pbr_half* A, pbr_half* B,
                              float threshold, float knee, const uint32_t* hist_rect, float min_log, float inv_range, uint32_t* hist256) {
@@ -1166,29 +1208,19 @@ static pbr_status bloom_impl(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h
     // BloomStep < CalculateMaxMipLevels (DeferredPipeline.cpp:343): every level must be >= 1 texel
     PBR_REQUIRE(ctx, (w >> (PBR_BLOOM_MIPS - 1)) >= 1 && (h >> (PBR_BLOOM_MIPS - 1)) >= 1, "pbr_bloom: image too small for 5 mips");
     PBR_REQUIRE(ctx, w <= 65535 && h <= 65535 && pitch >= w, "pbr_bloom: bad size");
-    pbr_status r;
-    if ((r = pbr_bloom_prefilter(ctx, hdr, w, h, pitch, A + 4 * pbr_bloom_level_offset(w, h, 1), threshold, knee))) return r;
-    const pbr_half* res = nullptr;
-    if ((r = bloom_pyramid(ctx, w, h, A, B, &res))) return r;
-    if (exact_half(w) && exact_half(h)) {   // H + V + merge (+ histogram) in one kernel
-        if (hist256) return launch_hv<M_UP, false, 2>(ctx, res, w >> 1, h >> 1, nullptr, hdr, w, h, pitch, hist_rect, min_log, inv_range, hist256);
-        return launch_hv<M_UP, false, 1>(ctx, res, w >> 1, h >> 1, nullptr, hdr, w, h, pitch, nullptr, 0.0f, 0.0f, nullptr);
-    }
-    pbr_half* b0 = B;   // level 0 of chain B
-    if ((r = pbr_blur_h(ctx, res, w >> 1, h >> 1, b0, w, h))) return r;
-    // A0 = V(B0); S += A0 [; histogram(S)] in one pass — chain A level 0 is not materialised
-    return bloom_final(ctx, b0, hdr, w, h, pitch, hist_rect, min_log, inv_range, hist256);
+    const BloomView v{hdr, pitch, A, B, hist256};
+    return bloom_pass<false>(ctx, &v, 1, w, h, true, threshold, knee, hist_rect, min_log, inv_range);
 }
 
-// BloomPass::Execute (DeferredPipeline.cpp:400-570; schedule comment :379-399)
+// BloomPass::Execute
 pbr_status pbr_bloom(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
                      pbr_half* A, pbr_half* B, float threshold, float knee) {
     if (!ctx) return PBR_ERR_INVALID;
     return bloom_impl(ctx, hdr, w, h, pitch, A, B, threshold, knee, nullptr, 0.0f, 0.0f, nullptr);
 }
 
-// BloomPass::Execute followed by the luminance-histogram dispatch of AutoExposurePass::Execute
-// (DeferredPipeline.cpp:276-298) on the pixels of `rect` = {x, y, w, h} of the bloomed image.
+// BloomPass::Execute followed by the luminance-histogram dispatch of AutoExposurePass::Execute on the pixels of `rect` = {x, y, w, h}
+// of the bloomed image.
 pbr_status pbr_bloom_histogram(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
                                pbr_half* A, pbr_half* B, float threshold, float knee,
                                const uint32_t rect[4], float min_log, float inv_range, uint32_t* hist256) {
@@ -1198,19 +1230,21 @@ pbr_status pbr_bloom_histogram(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t
     return bloom_impl(ctx, hdr, w, h, pitch, A, B, threshold, knee, rect, min_log, inv_range, hist256);
 }
 
-// BloomPass::Execute + the histogram dispatch for up to PBR_MAX_VIEWS whole frames of one size.  Every level takes the kernel a single view
-// of that size takes (bloom_impl / bloom_pyramid): fused levels (exact halves) run all views in one launch, grid (blocks of one view,
-// views); staged levels (not an exact half, e.g. 1920x1080 from level 3 down) run the single-view staged kernels once per view.
+// pbr_bloom_histogram for up to PBR_MAX_VIEWS whole frames of one size: every level takes the kernel a single view of that size takes
+// (bloom_pass); fused levels run all views in one launch, staged levels (not an exact half, e.g. 1920x1080 from level 3 down) run the
+// single-view staged kernels once per view.
 pbr_status pbr_bloom_histogram_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h,
                                      float threshold, float knee, float min_log, float inv_range) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, views_count_ok(views, n), "pbr_bloom_histogram_views: need 1 .. PBR_MAX_VIEWS views");
     PBR_REQUIRE(ctx, (w >> (PBR_BLOOM_MIPS - 1)) >= 1 && (h >> (PBR_BLOOM_MIPS - 1)) >= 1, "pbr_bloom_histogram_views: image too small for 5 mips");
     PBR_REQUIRE(ctx, w <= 65535 && h <= 65535, "pbr_bloom_histogram_views: bad size");
+    BloomView bv[PBR_MAX_VIEWS];
     for (uint32_t i = 0; i < n; i++) {
         const pbr_view& v = views[i];
         PBR_REQUIRE(ctx, v.hdr && v.chain_a && v.chain_b && v.hist256, "pbr_bloom_histogram_views: null pointer");
         PBR_REQUIRE(ctx, v.hdr_pitch >= w, "pbr_bloom_histogram_views: bad size");
+        bv[i] = BloomView{v.hdr, v.hdr_pitch, v.chain_a, v.chain_b, v.hist256};
     }
     const size_t chain_bytes = pbr_bloom_chain_texels(w, h) * 8u;
     PBR_REQUIRE(ctx, views_disjoint(views, n, 4, [&](const pbr_view& v, int k, uintptr_t& lo, uintptr_t& hi) {
@@ -1219,88 +1253,8 @@ pbr_status pbr_bloom_histogram_views(pbr_ctx* ctx, const pbr_view* views, uint32
                     else if (k == 2) { lo = addr(v.chain_b); hi = lo + chain_bytes; }
                     else { lo = addr(v.hist256); hi = lo + PBR_HISTOGRAM_BINS * sizeof(uint32_t); } }),
                 "pbr_bloom_histogram_views: two views share an HDR target, a bloom chain or a histogram");
-    auto W = [&](uint32_t l) { return w >> l; };
-    auto H = [&](uint32_t l) { return h >> l; };
-    auto off = [&](uint32_t l) { return (size_t)4 * pbr_bloom_level_offset(w, h, l); };
-    auto exact = [&](uint32_t l) { return exact_half(W(l)) && exact_half(H(l)); };
     const uint32_t rect[4] = {0, 0, w, h};
-    pbr_status r;
-    // prefilter: hdr -> level 1 of chain A
-    if (exact(0)) {
-        PrefilterViews pv{};
-        for (uint32_t i = 0; i < n; i++) { pv.hdr[i] = views[i].hdr; pv.out[i] = views[i].chain_a + off(1); pv.pitch[i] = (int)views[i].hdr_pitch; }
-        OutRects rs{};
-        rs.n = 1; rs.ox = 0; rs.oy = 0; rs.pitch = (int)W(1);
-        rs.x0[0] = 0; rs.y0[0] = 0; rs.x1[0] = (int)W(1); rs.y1[0] = (int)H(1);
-        rs.tiles_x[0] = ((int)W(1) + PF_TW - 1) / PF_TW;
-        rs.first[0] = 0; rs.first[1] = rs.tiles_x[0] * (((int)H(1) + PF_TH - 1) / PF_TH);
-        hipLaunchKernelGGL(k_bloom_prefilter_2x<PrefilterViews>, dim3(rs.first[1], n), dim3(256), 0, ctx->stream,
-                           nullptr, (int)w, (int)h, 0, pv, nullptr, rs, threshold, knee);
-        if ((r = launched(ctx, "k_bloom_prefilter_2x<views>"))) return r;
-    } else {
-        for (uint32_t i = 0; i < n; i++)
-            if ((r = pbr_bloom_prefilter(ctx, views[i].hdr, w, h, views[i].hdr_pitch, views[i].chain_a + off(1), threshold, knee))) return r;
-    }
-    // the pyramid (bloom_pyramid's schedule; `res_in_b`: the finished level below lives in chain B)
-    LevelViews lv{};
-    auto level = [&](auto in_of, auto in2_of, auto out_of) {
-        for (uint32_t i = 0; i < n; i++) {
-            lv.in[i] = in_of(views[i]); lv.in2[i] = in2_of(views[i]); lv.out[i] = out_of(views[i]);
-            lv.hist[i] = nullptr; lv.out_pitch[i] = 0;
-        }
-        return &lv;
-    };
-    auto none = [](const pbr_view&) { return (const pbr_half*)nullptr; };
-    for (uint32_t k = 0; k < PBR_BLOOM_STEP; k++) {   // downsample
-        const uint32_t up = k + 1, lo = k + 2;
-        if (exact(up)) {
-            const LevelViews* q = level([&](const pbr_view& v) { return (const pbr_half*)v.chain_a + off(up); }, none,
-                                        [&](const pbr_view& v) { return v.chain_a + off(lo); });
-            for (uint32_t i = 0; i < n; i++) lv.out_pitch[i] = (int)W(lo);
-            if ((r = launch_hv<M_DOWN, false, 0>(ctx, nullptr, W(up), H(up), nullptr, nullptr, W(lo), H(lo), W(lo), nullptr, 0.0f, 0.0f, nullptr,
-                                                 nullptr, nullptr, q, n))) return r;
-        } else {
-            for (uint32_t i = 0; i < n; i++) {
-                pbr_half* A = views[i].chain_a; pbr_half* B = views[i].chain_b;
-                if ((r = pbr_blur_h(ctx, A + off(up), W(up), H(up), B + off(lo), W(lo), H(lo)))) return r;
-                if ((r = pbr_blur_v(ctx, B + off(lo), W(lo), H(lo), A + off(lo), W(lo), H(lo)))) return r;
-            }
-        }
-    }
-    bool res_in_b = false;
-    uint32_t res_level = PBR_BLOOM_MIPS - 1;
-    auto res_of = [&](const pbr_view& v) { return (const pbr_half*)(res_in_b ? v.chain_b : v.chain_a) + off(res_level); };
-    for (int k = PBR_BLOOM_STEP - 1; k >= 0; k--) {   // upsample: V(H(lower) + H(upper))
-        const uint32_t up = (uint32_t)k + 1;
-        if (exact(up)) {
-            const LevelViews* q = level(res_of, [&](const pbr_view& v) { return (const pbr_half*)v.chain_a + off(up); },
-                                        [&](const pbr_view& v) { return v.chain_b + off(up); });
-            for (uint32_t i = 0; i < n; i++) lv.out_pitch[i] = (int)W(up);
-            if ((r = launch_hv<M_UP, true, 0>(ctx, nullptr, W(up + 1), H(up + 1), nullptr, nullptr, W(up), H(up), W(up), nullptr, 0.0f, 0.0f, nullptr,
-                                              nullptr, nullptr, q, n))) return r;
-            res_in_b = true;
-        } else {
-            for (uint32_t i = 0; i < n; i++) {
-                pbr_half* A = views[i].chain_a; pbr_half* B = views[i].chain_b;
-                if ((r = pbr_bloom_upsample_add(ctx, A + off(up), W(up), H(up), res_of(views[i]), W(up + 1), H(up + 1), B + off(up)))) return r;
-                if ((r = pbr_blur_v(ctx, B + off(up), W(up), H(up), A + off(up), W(up), H(up)))) return r;
-            }
-            res_in_b = false;
-        }
-        res_level = up;
-    }
-    // level 0: H + V + merge + histogram
-    if (exact(0)) {
-        const LevelViews* q = level(res_of, none, [&](const pbr_view& v) { return v.hdr; });
-        for (uint32_t i = 0; i < n; i++) { lv.hist[i] = views[i].hist256; lv.out_pitch[i] = (int)views[i].hdr_pitch; }
-        return launch_hv<M_UP, false, 2>(ctx, nullptr, w >> 1, h >> 1, nullptr, nullptr, w, h, 0, rect, min_log, inv_range, nullptr, nullptr, nullptr, q, n);
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        pbr_half* b0 = views[i].chain_b;
-        if ((r = pbr_blur_h(ctx, res_of(views[i]), w >> 1, h >> 1, b0, w, h))) return r;
-        if ((r = bloom_final(ctx, b0, views[i].hdr, w, h, views[i].hdr_pitch, rect, min_log, inv_range, views[i].hist256))) return r;
-    }
-    return PBR_OK;
+    return bloom_pass<true>(ctx, bv, n, w, h, true, threshold, knee, rect, min_log, inv_range);
 }
 
 // Multi-GPU halo path (SURVEY 8e option 2): BloomPass::Execute minus the prefilter, on the extended rectangle E
@@ -1320,12 +1274,9 @@ pbr_status pbr_bloom_tiled(pbr_ctx* ctx, pbr_half* hdr, uint32_t hdr_pitch, cons
                 "pbr_bloom_tiled: merge_rect outside hdr_rect");
     if (!exact_half(ew) || !exact_half(eh))
         return pbr::fail(ctx, PBR_ERR_UNSUPPORTED, "pbr_bloom_tiled: the extended tile must be even and <= 8192 on a side");
-    const pbr_half* res = nullptr;
-    pbr_status r;
-    if ((r = bloom_pyramid(ctx, ew, eh, A, B, &res, merge_rect))) return r;
+    const BloomView v{hdr, hdr_pitch, A, B, hist256};
     const uint32_t origin[2] = {hdr_rect[0], hdr_rect[1]};
-    if (hist256) return launch_hv<M_UP, false, 2>(ctx, res, ew >> 1, eh >> 1, nullptr, hdr, ew, eh, hdr_pitch, merge_rect, min_log, inv_range, hist256, merge_rect, origin);
-    return launch_hv<M_UP, false, 1>(ctx, res, ew >> 1, eh >> 1, nullptr, hdr, ew, eh, hdr_pitch, nullptr, 0.0f, 0.0f, nullptr, merge_rect, origin);
+    return bloom_pass<false>(ctx, &v, 1, ew, eh, false, 0.0f, 0.0f, merge_rect, min_log, inv_range, merge_rect, origin);
 }
 
 }  // extern "C"

@@ -124,6 +124,16 @@ static ClusterParams make_params(const pbr_global* g) {
     return p;
 }
 
+// the cull's arguments (nullptr: usable; the caller refuses under its own name).  build: k_cluster_cull<true>, which also makes the
+// cluster boxes from g's Near / Far (pbr_cluster_cull continues from the boxes pbr_cluster_build made)
+static const char* cull_args_bad(const pbr_global* g, bool build, const pbr_light* lights, int n) {
+    if (build && !(g->Near > 0.0f && g->Far > g->Near)) return "need 0 < Near < Far";
+    // ClusteredPass::Execute asserts GetLightCount() <= MaxSceneLights (DeferredPipeline.cpp:222)
+    if (!(n >= 0 && n <= PBR_MAX_SCENE_LIGHTS)) return "light count out of [0, 1024]";
+    if (!(n == 0 || lights != nullptr)) return "null lights";
+    return nullptr;
+}
+
 extern "C" {
 
 pbr_status pbr_cluster_build(pbr_ctx* ctx, const pbr_global* g, pbr_cluster* clusters) {
@@ -137,9 +147,7 @@ pbr_status pbr_cluster_build(pbr_ctx* ctx, const pbr_global* g, pbr_cluster* clu
 pbr_status pbr_cluster_cull(pbr_ctx* ctx, const pbr_global* g, const pbr_light* lights, int n, pbr_cluster* clusters) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, g && clusters, "pbr_cluster_cull: null pointer");
-    // ClusteredPass::Execute asserts GetLightCount() <= MaxSceneLights (DeferredPipeline.cpp:222)
-    PBR_REQUIRE(ctx, n >= 0 && n <= PBR_MAX_SCENE_LIGHTS, "pbr_cluster_cull: light count out of [0, 1024]");
-    PBR_REQUIRE(ctx, n == 0 || lights != nullptr, "pbr_cluster_cull: null lights");
+    PBR_CHECK(ctx, "pbr_cluster_cull", cull_args_bad(g, false, lights, n));
     if (n == 0) return PBR_OK;
     hipLaunchKernelGGL(k_cluster_cull<false>, dim3(PBR_NUM_CLUSTERS / 4), dim3(256), 0, ctx->stream, make_params(g), lights, n, NoViews{}, clusters);
     return launched(ctx, "k_cluster_cull");
@@ -148,9 +156,7 @@ pbr_status pbr_cluster_cull(pbr_ctx* ctx, const pbr_global* g, const pbr_light* 
 pbr_status pbr_clustered(pbr_ctx* ctx, const pbr_global* g, const pbr_light* lights, int n, pbr_cluster* clusters) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, g && clusters, "pbr_clustered: null pointer");
-    PBR_REQUIRE(ctx, g->Near > 0.0f && g->Far > g->Near, "pbr_clustered: need 0 < Near < Far");
-    PBR_REQUIRE(ctx, n >= 0 && n <= PBR_MAX_SCENE_LIGHTS, "pbr_clustered: light count out of [0, 1024]");
-    PBR_REQUIRE(ctx, n == 0 || lights != nullptr, "pbr_clustered: null lights");
+    PBR_CHECK(ctx, "pbr_clustered", cull_args_bad(g, true, lights, n));
     hipLaunchKernelGGL(k_cluster_cull<true>, dim3(PBR_NUM_CLUSTERS / 4), dim3(256), 0, ctx->stream, make_params(g), lights, n, NoViews{}, clusters);
     return launched(ctx, "k_cluster_cull<build>");
 }
@@ -162,9 +168,7 @@ pbr_status pbr_clustered_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n) 
     for (uint32_t i = 0; i < n; i++) {
         const pbr_view& v = views[i];
         PBR_REQUIRE(ctx, v.clusters, "pbr_clustered_views: null clusters");
-        PBR_REQUIRE(ctx, v.g.Near > 0.0f && v.g.Far > v.g.Near, "pbr_clustered_views: need 0 < Near < Far");
-        PBR_REQUIRE(ctx, v.num_lights >= 0 && v.num_lights <= PBR_MAX_SCENE_LIGHTS, "pbr_clustered_views: light count out of [0, 1024]");
-        PBR_REQUIRE(ctx, v.num_lights == 0 || v.lights != nullptr, "pbr_clustered_views: null lights");
+        PBR_CHECK(ctx, "pbr_clustered_views", cull_args_bad(&v.g, true, v.lights, v.num_lights));
         vs.v[i] = ClusterView{make_params(&v.g), v.lights, v.num_lights, v.clusters};
     }
     PBR_REQUIRE(ctx, views_disjoint(views, n, 1, [](const pbr_view& v, int, uintptr_t& lo, uintptr_t& hi) {

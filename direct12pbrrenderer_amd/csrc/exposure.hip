@@ -239,6 +239,17 @@ __global__ __launch_bounds__(256) void k_average_tonemap(const uint32_t* __restr
     tonemap_pixels(hdr, w, h, pitch, s_avg, out, out_pitch, aligned);
 }
 
+// the tone-map's persistent grid for a w x h frame (per view): a block per 256 pixel pairs, at most 2048
+static unsigned tonemap_blocks(uint32_t w, uint32_t h) {
+    const size_t pairs = (size_t)((w + 1) / 2) * h;
+    const unsigned blocks = (unsigned)((pairs + 255) / 256);
+    return blocks > 2048 ? 2048 : blocks;
+}
+// the 16-byte load / 8-byte store path of tonemap_pixels: both targets aligned to it and both pitches even
+static bool tonemap_aligned(const pbr_half* hdr, uint32_t pitch, const uint32_t* rgba8, uint32_t out_pitch) {
+    return (((uintptr_t)hdr & 15u) == 0u) && (((uintptr_t)rgba8 & 7u) == 0u) && (((pitch | out_pitch) & 1u) == 0u);
+}
+
 extern "C" {
 
 pbr_status pbr_lum_histogram(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
@@ -269,12 +280,8 @@ pbr_status pbr_tonemap(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, hdr && avg && rgba8, "pbr_tonemap: null pointer");
     PBR_REQUIRE(ctx, w && h && w <= 65535 && h <= 65535 && pitch >= w && out_pitch >= w, "pbr_tonemap: bad size");
-    size_t pairs = (size_t)((w + 1) / 2) * h;
-    unsigned blocks = (unsigned)((pairs + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    dim3 grid(blocks);
-    const bool aligned = (((uintptr_t)hdr & 15u) == 0u) && (((uintptr_t)rgba8 & 7u) == 0u) && (((pitch | out_pitch) & 1u) == 0u);
-    hipLaunchKernelGGL(k_tonemap, grid, dim3(256), 0, ctx->stream, hdr, w, h, pitch, avg, rgba8, out_pitch, aligned);
+    hipLaunchKernelGGL(k_tonemap, dim3(tonemap_blocks(w, h)), dim3(256), 0, ctx->stream, hdr, w, h, pitch, avg, rgba8, out_pitch,
+                       tonemap_aligned(hdr, pitch, rgba8, out_pitch));
     return launched(ctx, "k_tonemap");
 }
 
@@ -285,12 +292,8 @@ pbr_status pbr_average_tonemap(pbr_ctx* ctx, const uint32_t* hist256, uint32_t p
     PBR_REQUIRE(ctx, hist256 && avg_in && avg_out && hdr && rgba8, "pbr_average_tonemap: null pointer");
     PBR_REQUIRE(ctx, avg_in != avg_out && hist_clear256 != hist256, "pbr_average_tonemap: avg_out must differ from avg_in and hist_clear256 from hist256 (every block reads them)");
     PBR_REQUIRE(ctx, w && h && w <= 65535 && h <= 65535 && pitch >= w && out_pitch >= w, "pbr_average_tonemap: bad size");
-    size_t pairs = (size_t)((w + 1) / 2) * h;
-    unsigned blocks = (unsigned)((pairs + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    const bool aligned = (((uintptr_t)hdr & 15u) == 0u) && (((uintptr_t)rgba8 & 7u) == 0u) && (((pitch | out_pitch) & 1u) == 0u);
-    hipLaunchKernelGGL(k_average_tonemap, dim3(blocks), dim3(256), 0, ctx->stream, hist256, pixel_count, min_log, range, delta_time, avg_in, avg_out,
-                       hist_clear256, hdr, w, h, pitch, rgba8, out_pitch, aligned);
+    hipLaunchKernelGGL(k_average_tonemap, dim3(tonemap_blocks(w, h)), dim3(256), 0, ctx->stream, hist256, pixel_count, min_log, range, delta_time,
+                       avg_in, avg_out, hist_clear256, hdr, w, h, pitch, rgba8, out_pitch, tonemap_aligned(hdr, pitch, rgba8, out_pitch));
     return launched(ctx, "k_average_tonemap");
 }
 
@@ -320,15 +323,12 @@ pbr_status pbr_tonemap_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, ui
         PBR_REQUIRE(ctx, v.hdr && v.avg && v.rgba8, "pbr_tonemap_views: null pointer");
         PBR_REQUIRE(ctx, v.hdr_pitch >= w && v.out_pitch >= w, "pbr_tonemap_views: bad size");
         vs.hdr[i] = v.hdr; vs.avg[i] = v.avg; vs.out[i] = v.rgba8; vs.pitch[i] = v.hdr_pitch; vs.out_pitch[i] = v.out_pitch;
-        vs.aligned[i] = (((uintptr_t)v.hdr & 15u) == 0u) && (((uintptr_t)v.rgba8 & 7u) == 0u) && (((v.hdr_pitch | v.out_pitch) & 1u) == 0u);
+        vs.aligned[i] = tonemap_aligned(v.hdr, v.hdr_pitch, v.rgba8, v.out_pitch);
     }
     PBR_REQUIRE(ctx, views_disjoint(views, n, 1, [&](const pbr_view& v, int, uintptr_t& lo, uintptr_t& hi) {
                     lo = addr(v.rgba8); hi = lo + ((size_t)v.out_pitch * (h - 1) + w) * sizeof(uint32_t); }),
                 "pbr_tonemap_views: two views share an LDR target");
-    size_t pairs = (size_t)((w + 1) / 2) * h;   // per view, as pbr_tonemap
-    unsigned blocks = (unsigned)((pairs + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_tonemap_views, dim3(blocks, n), dim3(256), 0, ctx->stream, vs, w, h);
+    hipLaunchKernelGGL(k_tonemap_views, dim3(tonemap_blocks(w, h), n), dim3(256), 0, ctx->stream, vs, w, h);
     return launched(ctx, "k_tonemap_views");
 }
 

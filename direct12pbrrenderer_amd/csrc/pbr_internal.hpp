@@ -41,6 +41,11 @@ inline pbr_status fail(pbr_ctx* ctx, pbr_status code, const char* what) {
     if (ctx) ctx->err = what;
     return code;
 }
+// a check shared by several entry points returns what is wrong (nullptr: nothing) and the caller refuses under its own name
+inline pbr_status refuse(pbr_ctx* ctx, const char* who, const char* why) {
+    if (ctx) ctx->err = std::string(who) + ": " + why;
+    return PBR_ERR_INVALID;
+}
 inline pbr_status hip_fail(pbr_ctx* ctx, hipError_t e, const char* where) {
     if (ctx) {
         ctx->err = std::string(where) + ": " + hipGetErrorString(e);
@@ -96,5 +101,7 @@ struct NoViews {};
 
 #define PBR_REQUIRE(ctx, cond, msg) \
     do { if (!(cond)) return pbr::fail((ctx), PBR_ERR_INVALID, msg); } while (0)
+#define PBR_CHECK(ctx, who, check) \
+    do { if (const char* why__ = (check)) return pbr::refuse((ctx), (who), why__); } while (0)
 #define PBR_HIP(ctx, call) \
     do { hipError_t e__ = (call); if (e__ != hipSuccess) return pbr::hip_fail((ctx), e__, #call); } while (0)

@@ -704,15 +704,100 @@ static void camera_params(const pbr_global* g, ShadeParams& p) {
     p.slice_k = (float)((double)PBR_CLUSTER_Z / log2((double)g->Far / (double)g->Near));
 }
 
-// Rows of a long block for a launch of `row_segments` 256-pixel row pieces (see shade_launch)
-static uint32_t shade_rows_big(const pbr_ctx* ctx, uint64_t row_segments) {
+// what every target of a launch shares: the camera of g (a view table replaces it per view), LUT and padded env chain; the rest is zero
+static ShadeParams shade_params(const pbr_global* g, const pbr_half* lut, uint32_t lut_res, const pbr_half* env, uint32_t env_size, uint32_t env_mips) {
+    ShadeParams p{};
+    camera_params(g, p);
+    p.lut = lut; p.lut_res = lut_res; p.env = env; p.env_size = env_size; p.env_mips = env_mips;
+    for (uint32_t m = 0; m < 16; m++) p.env_mip_off[m] = (uint32_t)env_padded_mip_offset(env_size, m < env_mips ? m : env_mips - 1);
+    return p;
+}
+
+// The checks of a shade launch return what is wrong (nullptr: nothing).  The LUT and padded env chain every target reads:
+static const char* shade_tables_bad(const pbr_half* lut, uint32_t lut_res, const pbr_half* env, uint32_t env_size, uint32_t env_mips) {
+    if (!lut || !env) return "null pointer";
+    if (!(lut_res >= 1 && env_size >= 1 && env_mips >= 1 && env_mips <= 16 && (env_size >> (env_mips - 1)) >= 1)) return "bad LUT/env size";
+    if (!(lut_res <= 16384 && (uint64_t)pbr_env_padded_texels(env_size, env_mips) * 8u < (1ull << 32)))
+        return "LUT larger than 16384^2 or padded env chain of 4 GiB or more (32-bit texture offsets)";
+    if (((uintptr_t)env & 7u) != 0 || ((uintptr_t)lut & 3u) != 0) return "env must be 8-byte and lut 4-byte aligned";
+    return nullptr;
+}
+
+// one target of w x h pixels: its G-buffer, clusters, output, camera range and lights
+static const char* shade_target_bad(const pbr_global* g, const pbr_gbuffer& gb, const pbr_cluster* clusters, const void* out, uint32_t out_pitch,
+                                    uint32_t w, uint32_t h, const pbr_light* lights, int num_lights) {
+    if (!clusters || !out) return "null pointer";
+    if (!(gb.A && gb.B && gb.C && gb.depth && gb.stencil)) return "null G-buffer plane";
+    if (!(gb.pitch >= w && out_pitch >= w)) return "pitch < width";
+    // the kernel addresses every plane with 32-bit byte offsets (16 B per pixel for the fp32 probe's output)
+    if (!((uint64_t)gb.pitch * h * 4u < (1ull << 32) && (uint64_t)out_pitch * h * 16u < (1ull << 32)))
+        return "target too large for 32-bit plane offsets (pitch x rows x 16 bytes must stay below 4 GiB)";
+    if (!(g->Near > 0.0f && g->Far > g->Near)) return "need 0 < Near < Far";
+    if (!(num_lights >= 0 && num_lights <= PBR_MAX_SCENE_LIGHTS)) return "light count out of [0, 1024]";
+    if (!(num_lights == 0 || lights != nullptr)) return "null lights";
+    return nullptr;
+}
+
+// The schedule (see the kernel) of `rects` (tile-local {x, y, w, h}, checked): long blocks first, short ones for the tail.
+// rc.first[rc.n] is the block count of one view; the long blocks' row count is sized for the row pieces of all n_views views.
+static ShadeRects shade_schedule(const pbr_ctx* ctx, const uint32_t (*rects)[4], uint32_t n_rects, uint32_t n_views) {
+    static const float big_frac = pbr::knob_float("PBR_SHADE_BIGFRAC", 0.92f);   // re-swept after the per-pixel trims (the knobs build): 0.9-0.95 with 1-row tail blocks beats 0.85 / 2 by ~0.4 %
+    static const uint32_t rows_small_cfg = (uint32_t)pbr::knob_int("PBR_SHADE_ROWS_SMALL", 1);
+    static const uint32_t rows_big_cfg = (uint32_t)pbr::knob_int("PBR_SHADE_ROWS_BIG", 0);   // 0: by target size (below)
+    const uint32_t rows_small = rows_small_cfg >= 1 && rows_small_cfg <= (uint32_t)SHADE_ROWS ? rows_small_cfg : 1u;
+    // Rows of a long block.  SHADE_ROWS (8) wherever that gives at least ~1.3 generations of the blocks the device holds at once
+    // (compute units x 5): the tables a block stages are amortised best, and 4K (3.2 generations), a cfg5 rank's tile (1.7) and 8K
+    // measure best there.  Smaller targets get the row count that makes ~1.6 generations — one generation and a bit (1.1) is the worst
+    // place to be: the launch then lasts two block lifetimes for one block's worth of work per slot.  Measured (profiles/r06_j_rows_*,
+    // r06_g_*): 1440x960 (the reference's own target, 0.56 generations at 8 rows) 3 rows -10 %; 1920x1080 (0.84) 4 rows -0.5 ... -2.4 %.
+    uint64_t row_segments = 0;   // 256-pixel row pieces of the launch
+    for (uint32_t r = 0; r < n_rects; r++) row_segments += (uint64_t)((rects[r][2] + SHADE_BLOCK - 1) / SHADE_BLOCK) * rects[r][3];
+    row_segments *= n_views;
     uint32_t rows_big = (uint32_t)SHADE_ROWS;
     const uint64_t slots = (uint64_t)ctx->cu_count * SHADE_MIN_WAVES;
     if (row_segments * 10 < slots * 13 * SHADE_ROWS) {
         const uint32_t rws = (uint32_t)((row_segments * 10 + slots * 8) / (slots * 16));   // round(row_segments / (1.6 slots))
         rows_big = rws < 2 ? 2u : (rws > (uint32_t)SHADE_ROWS ? (uint32_t)SHADE_ROWS : rws);
     }
-    return rows_big;
+    if (rows_big_cfg >= 1 && rows_big_cfg <= (uint32_t)SHADE_ROWS) rows_big = rows_big_cfg;
+    ShadeRects rc{};
+    rc.n = n_rects; rc.rows_big = rows_big; rc.rows_small = rows_small < rows_big ? rows_small : rows_big;
+    uint32_t blocks = 0;
+    for (uint32_t r = 0; r < n_rects; r++) {
+        const uint32_t* q = rects[r];
+        rc.x0[r] = q[0]; rc.y0[r] = q[1]; rc.w[r] = q[2]; rc.h[r] = q[3];
+        rc.cols[r] = (q[2] + SHADE_BLOCK - 1) / SHADE_BLOCK;
+        rc.nb_big[r] = (uint32_t)((float)(q[3] / rows_big) * fminf(fmaxf(big_frac, 0.0f), 1.0f));
+        const uint32_t rest = q[3] - rc.nb_big[r] * rows_big;
+        rc.first[r] = blocks;
+        blocks += rc.cols[r] * (rc.nb_big[r] + (rest + rc.rows_small - 1) / rc.rows_small);
+    }
+    rc.first[n_rects] = blocks;
+    return rc;
+}
+
+// One launch of the schedule rc over n_views views (grid: rc's blocks x n_views) of a p.full_w x p.full_h frame whose views hold at most
+// max_lights lights.  VS = NoViews: p is the one view's, num_lights its light count; VS = ShadeViews: every view's own fields come from vs.
+template <bool F32OUT, class VS>
+static pbr_status shade_dispatch(pbr_ctx* ctx, const ShadeParams& p, int num_lights, int max_lights, const ShadeRects& rc, uint32_t n_views, const VS& vs) {
+    // A block covers 256 x 8 pixels.  It can stage its cluster lists when that rectangle spans at most
+    // MAX_STAGED_TILES cluster tiles: a tile is full_w/24 x full_h/16 pixels, +1 per axis for straddling.
+    // The staged-list decision depends on the frame size alone; the light stride of a batch is its largest view's (a layout, not a result).
+    const uint32_t span_x = (uint32_t)((uint64_t)(SHADE_BLOCK - 1) * PBR_CLUSTER_X / p.full_w) + 2;
+    const uint32_t span_y = (uint32_t)((uint64_t)(SHADE_ROWS - 1) * PBR_CLUSTER_Y / p.full_h) + 2;
+    const int lstride = max_lights <= 256 ? 257 : PBR_MAX_SCENE_LIGHTS + 1;   // odd strides: no ds_read2 merging of two planes of one light, conflict-free planes
+    const size_t plane_bytes = (size_t)((LIGHT_PLANES * lstride + 1) & ~1) * sizeof(float);
+    // staged lists must also fit the 64 KiB a block may ask for (1 024 lights: 36 KiB of planes leave room for 8 tiles)
+    const bool staged = span_x * span_y <= (uint32_t)MAX_STAGED_TILES &&   // (no lights at all: every list is one null pair)
+                        plane_bytes + (size_t)span_x * span_y * PBR_CLUSTER_Z * LIST_STRIDE * sizeof(uint32_t) <= 65536;
+    const int max_clusters = staged ? (int)(span_x * span_y) * PBR_CLUSTER_Z : 0;
+    const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t);
+    const dim3 grid(rc.first[rc.n], n_views), blk(SHADE_BLOCK);
+    if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, F32OUT, VS>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
+    else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, F32OUT, VS>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
+    else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, F32OUT, VS>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, vs);
+    else hipLaunchKernelGGL((k_deferred_shade<false, PBR_MAX_SCENE_LIGHTS + 1, F32OUT, VS>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, vs);
+    return launched(ctx, std::is_same_v<VS, NoViews> ? "k_deferred_shade" : "k_deferred_shade<views>");
 }
 
 template <bool F32OUT>
@@ -723,80 +808,24 @@ static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile
                                pbr_half* hdr, float* hdr_f32, uint32_t hdr_pitch,
                                const uint32_t (*rects)[4] = nullptr, uint32_t n_rects = 0) {
     if (!ctx) return PBR_ERR_INVALID;
-    PBR_REQUIRE(ctx, g && tile && gb && lut && env && clusters && (F32OUT ? (const void*)hdr_f32 : (const void*)hdr), "pbr_deferred_shade: null pointer");
-    PBR_REQUIRE(ctx, gb->A && gb->B && gb->C && gb->depth && gb->stencil, "pbr_deferred_shade: null G-buffer plane");
+    const char* who = "pbr_deferred_shade";
+    PBR_REQUIRE(ctx, g && tile && gb, "pbr_deferred_shade: null pointer");
     PBR_REQUIRE(ctx, tile->w >= 1 && tile->h >= 1 && tile->w <= 65535 && tile->h <= 65535, "pbr_deferred_shade: bad tile size");
     PBR_REQUIRE(ctx, tile->x0 + tile->w <= tile->full_w && tile->y0 + tile->h <= tile->full_h, "pbr_deferred_shade: tile outside frame");
-    PBR_REQUIRE(ctx, gb->pitch >= tile->w && hdr_pitch >= tile->w, "pbr_deferred_shade: pitch < width");
-    // the kernel addresses every plane with 32-bit byte offsets (16 B per pixel for the fp32 probe's output)
-    PBR_REQUIRE(ctx, (uint64_t)gb->pitch * tile->h * 4u < (1ull << 32) && (uint64_t)hdr_pitch * tile->h * 16u < (1ull << 32),
-                "pbr_deferred_shade: tile too large for 32-bit plane offsets (pitch x rows x 16 bytes must stay below 4 GiB)");
-    PBR_REQUIRE(ctx, lut_res >= 1 && env_size >= 1 && env_mips >= 1 && env_mips <= 16 && (env_size >> (env_mips - 1)) >= 1, "pbr_deferred_shade: bad LUT/env size");
-    PBR_REQUIRE(ctx, lut_res >= 1 && lut_res <= 16384 && (uint64_t)pbr_env_padded_texels(env_size, env_mips) * 8u < (1ull << 32),
-                "pbr_deferred_shade: LUT larger than 16384^2 or padded env chain of 4 GiB or more (32-bit texture offsets)");
-    PBR_REQUIRE(ctx, ((uintptr_t)env & 7u) == 0 && ((uintptr_t)lut & 3u) == 0, "pbr_deferred_shade: env must be 8-byte and lut 4-byte aligned");
-    PBR_REQUIRE(ctx, g->Near > 0.0f && g->Far > g->Near, "pbr_deferred_shade: need 0 < Near < Far");
-    PBR_REQUIRE(ctx, num_lights >= 0 && num_lights <= PBR_MAX_SCENE_LIGHTS, "pbr_deferred_shade: light count out of [0, 1024]");
-    PBR_REQUIRE(ctx, num_lights == 0 || lights != nullptr, "pbr_deferred_shade: null lights");
-    ShadeParams p;
-    camera_params(g, p);
-    p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h; p.full_w = tile->full_w; p.full_h = tile->full_h;
-    p.A = gb->A; p.B = gb->B; p.C = gb->C; p.depth = gb->depth; p.stencil = gb->stencil; p.pitch = gb->pitch;
-    p.lut = lut; p.lut_res = lut_res; p.env = env; p.env_size = env_size; p.env_mips = env_mips;
-    for (uint32_t m = 0; m < 16; m++) p.env_mip_off[m] = (uint32_t)env_padded_mip_offset(env_size, m < env_mips ? m : env_mips - 1);
-    p.clusters = clusters; p.lights = lights; p.hdr = hdr; p.hdr_pitch = hdr_pitch; p.hdr_f32 = hdr_f32;
-    // schedule (see the kernel): long blocks first, short ones for the tail
-    static const float big_frac = pbr::knob_float("PBR_SHADE_BIGFRAC", 0.92f);   // re-swept after the per-pixel trims (the knobs build): 0.9-0.95 with 1-row tail blocks beats 0.85 / 2 by ~0.4 %
-    static const uint32_t rows_small_cfg = (uint32_t)pbr::knob_int("PBR_SHADE_ROWS_SMALL", 1);
-    static const uint32_t rows_big_cfg = (uint32_t)pbr::knob_int("PBR_SHADE_ROWS_BIG", 0);   // 0: by target size (below)
-    const uint32_t rows_small = rows_small_cfg >= 1 && rows_small_cfg <= (uint32_t)SHADE_ROWS ? rows_small_cfg : 1u;
+    PBR_CHECK(ctx, who, shade_target_bad(g, *gb, clusters, F32OUT ? (const void*)hdr_f32 : (const void*)hdr, hdr_pitch, tile->w, tile->h, lights, num_lights));
+    PBR_CHECK(ctx, who, shade_tables_bad(lut, lut_res, env, env_size, env_mips));
     const uint32_t whole[1][4] = {{0, 0, tile->w, tile->h}};
     if (!rects) { rects = whole; n_rects = 1; }
     PBR_REQUIRE(ctx, n_rects >= 1 && n_rects <= (uint32_t)SHADE_MAX_RECTS, "pbr_deferred_shade: 1 .. 5 rectangles");
-    // Rows of a long block.  SHADE_ROWS (8) wherever that gives at least ~1.3 generations of the blocks the device holds at once
-    // (compute units x 5): the tables a block stages are amortised best, and 4K (3.2 generations), a cfg5 rank's tile (1.7) and 8K
-    // measure best there.  Smaller targets get the row count that makes ~1.6 generations — one generation and a bit (1.1) is the worst
-    // place to be: the launch then lasts two block lifetimes for one block's worth of work per slot.  Measured (profiles/r06_j_rows_*,
-    // r06_g_*): 1440x960 (the reference's own target, 0.56 generations at 8 rows) 3 rows -10 %; 1920x1080 (0.84) 4 rows -0.5 ... -2.4 %.
-    uint32_t rows_big;
-    {
-        uint64_t row_segments = 0;   // 256-pixel row pieces of the launch
-        for (uint32_t r = 0; r < n_rects; r++) row_segments += (uint64_t)((rects[r][2] + SHADE_BLOCK - 1) / SHADE_BLOCK) * rects[r][3];
-        rows_big = shade_rows_big(ctx, row_segments);
-        if (rows_big_cfg >= 1 && rows_big_cfg <= (uint32_t)SHADE_ROWS) rows_big = rows_big_cfg;
-    }
-    ShadeRects rc{};
-    rc.n = n_rects; rc.rows_big = rows_big; rc.rows_small = rows_small < rows_big ? rows_small : rows_big;
-    uint32_t blocks = 0;
     for (uint32_t r = 0; r < n_rects; r++) {
         const uint32_t* q = rects[r];
         PBR_REQUIRE(ctx, q[2] >= 1 && q[3] >= 1 && q[0] + q[2] <= tile->w && q[1] + q[3] <= tile->h, "pbr_deferred_shade: rectangle outside the tile");
-        rc.x0[r] = q[0]; rc.y0[r] = q[1]; rc.w[r] = q[2]; rc.h[r] = q[3];
-        rc.cols[r] = (q[2] + SHADE_BLOCK - 1) / SHADE_BLOCK;
-        rc.nb_big[r] = (uint32_t)((float)(q[3] / rows_big) * fminf(fmaxf(big_frac, 0.0f), 1.0f));
-        const uint32_t rest = q[3] - rc.nb_big[r] * rows_big;
-        rc.first[r] = blocks;
-        blocks += rc.cols[r] * (rc.nb_big[r] + (rest + rc.rows_small - 1) / rc.rows_small);
     }
-    rc.first[n_rects] = blocks;
-    dim3 grid(blocks);
-    // A block covers 256 x 8 pixels.  It can stage its cluster lists when that rectangle spans at most
-    // MAX_STAGED_TILES cluster tiles: a tile is full_w/24 x full_h/16 pixels, +1 per axis for straddling.
-    const uint32_t span_x = (uint32_t)((uint64_t)(SHADE_BLOCK - 1) * PBR_CLUSTER_X / tile->full_w) + 2;
-    const uint32_t span_y = (uint32_t)((uint64_t)(SHADE_ROWS - 1) * PBR_CLUSTER_Y / tile->full_h) + 2;
-    const int lstride = num_lights <= 256 ? 257 : PBR_MAX_SCENE_LIGHTS + 1;   // odd strides: no ds_read2 merging of two planes of one light, conflict-free planes
-    const size_t plane_bytes = (size_t)((LIGHT_PLANES * lstride + 1) & ~1) * sizeof(float);
-    // staged lists must also fit the 64 KiB a block may ask for (1 024 lights: 36 KiB of planes leave room for 8 tiles)
-    const bool staged = span_x * span_y <= (uint32_t)MAX_STAGED_TILES &&   // (no lights at all: every list is one null pair)
-                        plane_bytes + (size_t)span_x * span_y * PBR_CLUSTER_Z * LIST_STRIDE * sizeof(uint32_t) <= 65536;
-    const int max_clusters = staged ? (int)(span_x * span_y) * PBR_CLUSTER_Z : 0;
-    const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t);
-    const dim3 blk(SHADE_BLOCK);
-    if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, NoViews{});
-    else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, NoViews{});
-    else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, NoViews{});
-    else hipLaunchKernelGGL((k_deferred_shade<false, PBR_MAX_SCENE_LIGHTS + 1, F32OUT>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, NoViews{});
-    return launched(ctx, "k_deferred_shade");
+    ShadeParams p = shade_params(g, lut, lut_res, env, env_size, env_mips);
+    p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h; p.full_w = tile->full_w; p.full_h = tile->full_h;
+    p.A = gb->A; p.B = gb->B; p.C = gb->C; p.depth = gb->depth; p.stencil = gb->stencil; p.pitch = gb->pitch;
+    p.clusters = clusters; p.lights = lights; p.hdr = hdr; p.hdr_pitch = hdr_pitch; p.hdr_f32 = hdr_f32;
+    return shade_dispatch<F32OUT>(ctx, p, num_lights, num_lights, shade_schedule(ctx, rects, n_rects, 1), 1, NoViews{});
 }
 
 extern "C" {
@@ -839,36 +868,18 @@ pbr_status pbr_deferred_shade_views(pbr_ctx* ctx, const pbr_view* views, uint32_
                                     const pbr_half* lut, uint32_t lut_res,
                                     const pbr_half* env, uint32_t env_size, uint32_t env_mips) {
     if (!ctx) return PBR_ERR_INVALID;
+    const char* who = "pbr_deferred_shade_views";
     PBR_REQUIRE(ctx, views_count_ok(views, n), "pbr_deferred_shade_views: need 1 .. PBR_MAX_VIEWS views");
-    PBR_REQUIRE(ctx, lut && env, "pbr_deferred_shade_views: null pointer");
     PBR_REQUIRE(ctx, w >= 1 && h >= 1 && w <= 65535 && h <= 65535, "pbr_deferred_shade_views: bad frame size");
-    PBR_REQUIRE(ctx, lut_res >= 1 && env_size >= 1 && env_mips >= 1 && env_mips <= 16 && (env_size >> (env_mips - 1)) >= 1, "pbr_deferred_shade_views: bad LUT/env size");
-    PBR_REQUIRE(ctx, lut_res <= 16384 && (uint64_t)pbr_env_padded_texels(env_size, env_mips) * 8u < (1ull << 32),
-                "pbr_deferred_shade_views: LUT larger than 16384^2 or padded env chain of 4 GiB or more (32-bit texture offsets)");
-    PBR_REQUIRE(ctx, ((uintptr_t)env & 7u) == 0 && ((uintptr_t)lut & 3u) == 0, "pbr_deferred_shade_views: env must be 8-byte and lut 4-byte aligned");
-    ShadeParams p;
-    camera_params(&views[0].g, p);
-    p.x0 = 0; p.y0 = 0; p.w = w; p.h = h; p.full_w = w; p.full_h = h;
-    p.lut = lut; p.lut_res = lut_res; p.env = env; p.env_size = env_size; p.env_mips = env_mips;
-    for (uint32_t m = 0; m < 16; m++) p.env_mip_off[m] = (uint32_t)env_padded_mip_offset(env_size, m < env_mips ? m : env_mips - 1);
-    p.A = p.B = p.C = nullptr; p.depth = nullptr; p.stencil = nullptr; p.pitch = 0;
-    p.clusters = nullptr; p.lights = nullptr; p.hdr = nullptr; p.hdr_pitch = 0; p.hdr_f32 = nullptr;
+    PBR_CHECK(ctx, who, shade_tables_bad(lut, lut_res, env, env_size, env_mips));
     ShadeViews vs{};
     int max_lights = 0;
     for (uint32_t i = 0; i < n; i++) {
         const pbr_view& v = views[i];
-        const pbr_global* g = &v.g;
-        PBR_REQUIRE(ctx, v.clusters && v.hdr, "pbr_deferred_shade_views: null pointer");
-        PBR_REQUIRE(ctx, v.gb.A && v.gb.B && v.gb.C && v.gb.depth && v.gb.stencil, "pbr_deferred_shade_views: null G-buffer plane");
-        PBR_REQUIRE(ctx, v.gb.pitch >= w && v.hdr_pitch >= w, "pbr_deferred_shade_views: pitch < width");
-        PBR_REQUIRE(ctx, (uint64_t)v.gb.pitch * h * 4u < (1ull << 32) && (uint64_t)v.hdr_pitch * h * 16u < (1ull << 32),
-                    "pbr_deferred_shade_views: frame too large for 32-bit plane offsets (pitch x rows x 16 bytes must stay below 4 GiB)");
-        PBR_REQUIRE(ctx, g->Near > 0.0f && g->Far > g->Near, "pbr_deferred_shade_views: need 0 < Near < Far");
-        PBR_REQUIRE(ctx, v.num_lights >= 0 && v.num_lights <= PBR_MAX_SCENE_LIGHTS, "pbr_deferred_shade_views: light count out of [0, 1024]");
-        PBR_REQUIRE(ctx, v.num_lights == 0 || v.lights != nullptr, "pbr_deferred_shade_views: null lights");
-        PBR_REQUIRE(ctx, memcmp(&g->SkyBoxSH, &views[0].g.SkyBoxSH, sizeof(pbr_sh_pack)) == 0, "pbr_deferred_shade_views: SkyBoxSH differs between views");
+        PBR_CHECK(ctx, who, shade_target_bad(&v.g, v.gb, v.clusters, v.hdr, v.hdr_pitch, w, h, v.lights, v.num_lights));
+        PBR_REQUIRE(ctx, memcmp(&v.g.SkyBoxSH, &views[0].g.SkyBoxSH, sizeof(pbr_sh_pack)) == 0, "pbr_deferred_shade_views: SkyBoxSH differs between views");
         ShadeParams c;
-        camera_params(g, c);
+        camera_params(&v.g, c);
         ShadeView& d = vs.v[i];
         for (int k = 0; k < 9; k++) d.InvView[k] = c.InvView[k];
         for (int k = 0; k < 3; k++) d.CameraPos[k] = c.CameraPos[k];
@@ -881,37 +892,10 @@ pbr_status pbr_deferred_shade_views(pbr_ctx* ctx, const pbr_view* views, uint32_
     PBR_REQUIRE(ctx, views_disjoint(views, n, 1, [&](const pbr_view& v, int, uintptr_t& lo, uintptr_t& hi) {
                     lo = addr(v.hdr); hi = lo + ((size_t)v.hdr_pitch * (h - 1) + w) * 8u; }),
                 "pbr_deferred_shade_views: two views share an HDR target");
-    // the schedule of shade_launch for one rectangle {0, 0, w, h}, rows_big counted over the whole batch
-    static const float big_frac = pbr::knob_float("PBR_SHADE_BIGFRAC", 0.92f);
-    static const uint32_t rows_small_cfg = (uint32_t)pbr::knob_int("PBR_SHADE_ROWS_SMALL", 1);
-    static const uint32_t rows_big_cfg = (uint32_t)pbr::knob_int("PBR_SHADE_ROWS_BIG", 0);
-    const uint32_t rows_small = rows_small_cfg >= 1 && rows_small_cfg <= (uint32_t)SHADE_ROWS ? rows_small_cfg : 1u;
-    uint32_t rows_big = shade_rows_big(ctx, (uint64_t)((w + SHADE_BLOCK - 1) / SHADE_BLOCK) * h * n);
-    if (rows_big_cfg >= 1 && rows_big_cfg <= (uint32_t)SHADE_ROWS) rows_big = rows_big_cfg;
-    ShadeRects rc{};
-    rc.n = 1; rc.rows_big = rows_big; rc.rows_small = rows_small < rows_big ? rows_small : rows_big;
-    rc.x0[0] = 0; rc.y0[0] = 0; rc.w[0] = w; rc.h[0] = h;
-    rc.cols[0] = (w + SHADE_BLOCK - 1) / SHADE_BLOCK;
-    rc.nb_big[0] = (uint32_t)((float)(h / rows_big) * fminf(fmaxf(big_frac, 0.0f), 1.0f));
-    const uint32_t rest = h - rc.nb_big[0] * rows_big;
-    rc.first[0] = 0;
-    rc.first[1] = rc.cols[0] * (rc.nb_big[0] + (rest + rc.rows_small - 1) / rc.rows_small);
-    const dim3 grid(rc.first[1], n);
-    // staged lists and LDS size as shade_launch decides them for a frame of this size (the stride: the batch's largest light count)
-    const uint32_t span_x = (uint32_t)((uint64_t)(SHADE_BLOCK - 1) * PBR_CLUSTER_X / w) + 2;
-    const uint32_t span_y = (uint32_t)((uint64_t)(SHADE_ROWS - 1) * PBR_CLUSTER_Y / h) + 2;
-    const int lstride = max_lights <= 256 ? 257 : PBR_MAX_SCENE_LIGHTS + 1;
-    const size_t plane_bytes = (size_t)((LIGHT_PLANES * lstride + 1) & ~1) * sizeof(float);
-    const bool staged = span_x * span_y <= (uint32_t)MAX_STAGED_TILES &&
-                        plane_bytes + (size_t)span_x * span_y * PBR_CLUSTER_Z * LIST_STRIDE * sizeof(uint32_t) <= 65536;
-    const int max_clusters = staged ? (int)(span_x * span_y) * PBR_CLUSTER_Z : 0;
-    const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t);
-    const dim3 blk(SHADE_BLOCK);
-    if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, false, ShadeViews>), grid, blk, lds, ctx->stream, p, 0, max_clusters, rc, vs);
-    else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, false, ShadeViews>), grid, blk, lds, ctx->stream, p, 0, max_clusters, rc, vs);
-    else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, false, ShadeViews>), grid, blk, lds, ctx->stream, p, 0, 0, rc, vs);
-    else hipLaunchKernelGGL((k_deferred_shade<false, PBR_MAX_SCENE_LIGHTS + 1, false, ShadeViews>), grid, blk, lds, ctx->stream, p, 0, 0, rc, vs);
-    return launched(ctx, "k_deferred_shade<views>");
+    ShadeParams p = shade_params(&views[0].g, lut, lut_res, env, env_size, env_mips);
+    p.w = p.full_w = w; p.h = p.full_h = h;
+    const uint32_t whole[1][4] = {{0, 0, w, h}};
+    return shade_dispatch<false>(ctx, p, 0, max_lights, shade_schedule(ctx, whole, 1, n), n, vs);
 }
 
 }  // extern "C"

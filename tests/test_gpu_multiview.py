@@ -73,7 +73,8 @@ def bits(t):
     return t.contiguous().view(torch.int16).cpu().numpy() if t.dtype == torch.float16 else t.contiguous().view(torch.int32).cpu().numpy()
 
 
-@pytest.mark.parametrize("W,H,n_views", [(1440, 960, 4), (1920, 1080, 3), (3840, 2160, 2), (256, 144, 5)])
+# 1279x719: level 0 is not an exact half, so the prefilter and the level-0 tail take the staged kernels, once per view
+@pytest.mark.parametrize("W,H,n_views", [(1440, 960, 4), (1920, 1080, 3), (3840, 2160, 2), (256, 144, 5), (1279, 719, 2)])
 def test_views_bit_identical_to_single_views(ctx, ibl, W, H, n_views):
     mv, singles = make_pair(ctx, ibl, W, H, n_views)
     # stage by stage: the histogram is cleared by the average, so it is compared before it

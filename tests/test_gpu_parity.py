@@ -1402,7 +1402,7 @@ print("shade schedule", " ".join(out))
 @pytest.mark.timeout(900)
 def test_deferred_shade_output_does_not_depend_on_the_launch_schedule():
     """Round 6: the shade sizes its blocks by the render target (rows per long block: 8 where that makes >= 1.3 generations of resident
-    blocks, 2 .. 7 below — shade.hip, shade_launch).  Per-pixel arithmetic must not know: the same frames shaded by the product library
+    blocks, 2 .. 7 below — shade.hip, shade_schedule).  Per-pixel arithmetic must not know: the same frames shaded by the product library
     (rows by rule) and by the knobs build with every row count forced (PBR_SHADE_ROWS_BIG = 1 .. 8, and another two-zone split) are
     bit-identical — odd sizes (last block row / column partial), a tile of a larger frame (global pixel coordinates), 0 / 1 / 256 lights;
     and the product's frames agree with the oracle.  Own processes: the knobs are read once per process."""

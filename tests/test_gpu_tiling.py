@@ -162,7 +162,7 @@ print("tiled bloom", " ".join(out))
 @pytest.mark.timeout(600)
 def test_tiled_bloom_up_pass_rectangles_leave_the_merged_interior_bit_identical():
     """Round 6: pbr_bloom_tiled runs the up-pass of levels 1-3 only on the rectangles the merged interior depends on (bloom.hip,
-    bloom_pyramid(need0): need / 2 +- margins per level, clipped, whole tiles).  40 random extended tiles (128 .. 1264 on a side, multiples of 16), shaded
+    bloom_pass(merge0): need / 2 +- margins per level, clipped, whole tiles).  40 random extended tiles (128 .. 1264 on a side, multiples of 16), shaded
     rectangles and merge rectangles: the HDR buffer and the interior's histogram of the product library equal, bit for bit, those of the
     knobs build with the rectangles switched off (PBR_BLOOM_SHRINK=0: every level on the whole extended tile) — with chain B pre-filled
     with a sentinel, so a level that reads a texel its producer skipped cannot pass by luck.  Own processes (knobs are read once)."""
