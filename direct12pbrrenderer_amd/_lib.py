@@ -50,6 +50,10 @@ SIGNATURES = {
                                       _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32]),
     "pbr_skybox": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(CubeF32), _vp, _u32, _vp, _u32]),
     "pbr_gbuffer_encode": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "pbr_gbuffer_raster_scratch_bytes": (_sz, [_u32, _u32, _u32]),
+    "pbr_gbuffer_raster_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
+    "pbr_gbuffer_raster": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
+                                  _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz]),
     "pbr_bloom_prefilter": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _f32, _f32]),
     "pbr_blur_h": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),
     "pbr_blur_v": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),

@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from .structs import (BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, cube_texels, env_padded_texels)
+                      NUM_CLUSTERS, DRAW_DTYPE, VERTEX_DTYPE, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, cube_texels, env_padded_texels)
 
 
 class PbrError(RuntimeError):
@@ -135,7 +135,7 @@ class PbrContext:
 
     def upload(self, arr):
         arr = np.ascontiguousarray(arr)
-        if arr.dtype in (LIGHT_DTYPE, CLUSTER_DTYPE):
+        if arr.dtype in (LIGHT_DTYPE, CLUSTER_DTYPE, VERTEX_DTYPE, DRAW_DTYPE):
             arr = arr.view(np.uint8)
         if arr.dtype == np.uint32:
             return torch.from_numpy(arr.view(np.int32)).to(self.torch_device)
@@ -245,6 +245,25 @@ class PbrContext:
         """gbuffer.hlsl::ps_main on per-pixel material planes (float4 each) -> RGBA8 G-buffer planes."""
         self._check(self.lib.pbr_gbuffer_encode(self.h, _ptr(m0), _ptr(m1), _ptr(m2), w, h, pitch,
                                                 _ptr(A), _ptr(B), _ptr(Cc)))
+
+    # ---- G-buffer rasterization ----------------------------------------------------------------
+    def raster_scratch_bytes(self, w, h, n_triangles, minimum=False):
+        """pbr_gbuffer_raster_scratch_bytes (recommended) or, minimum=True, pbr_gbuffer_raster_min_scratch_bytes for a w x h tile"""
+        fn = self.lib.pbr_gbuffer_raster_min_scratch_bytes if minimum else self.lib.pbr_gbuffer_raster_scratch_bytes
+        return int(fn(int(w), int(h), int(n_triangles)))
+
+    def alloc_raster_scratch(self, w, h, n_triangles, minimum=False, extra=0):
+        """device scratch for gbuffer_raster (uint8; 256-byte aligned like every torch allocation)"""
+        return self.empty((self.raster_scratch_bytes(w, h, n_triangles, minimum) + int(extra),), torch.uint8)
+
+    def gbuffer_raster(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
+                       A, B, Cc, depth, stencil, pitch, scratch, scratch_bytes=None):
+        """pbr_gbuffer_raster: draws (device structs.DRAW_DTYPE records) of the vertex / index buffers (device VERTEX_DTYPE records,
+        uint32 indices) -> the tile's five G-buffer planes.  max_triangles = sum of index_count // 3; scratch from alloc_raster_scratch."""
+        nbytes = scratch.numel() * scratch.element_size() if scratch_bytes is None else int(scratch_bytes)
+        self._check(self.lib.pbr_gbuffer_raster(self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices),
+                                                int(n_indices), _ptr(draws), int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc),
+                                                _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch), nbytes))
 
     def bloom_prefilter(self, hdr, w, h, pitch, out, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE):
         self._check(self.lib.pbr_bloom_prefilter(self.h, _ptr(hdr), w, h, pitch, _ptr(out), threshold, knee))

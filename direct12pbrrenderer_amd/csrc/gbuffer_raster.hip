@@ -1,0 +1,511 @@
+// gbuffer_raster.hip — GBufferPass::Execute + DrawModel (DeferredPipeline.cpp:138-185) with constant per-draw materials:
+// gbuffer.hlsl's vertex shader (:71-86), the fixed-function stages of DefaultOpaque (back faces culled, FrontCounterClockwise =
+// FALSE; depth LESS with write; stencil ALWAYS, INCR_SAT on depth pass) and ps_main's Use*Map == false branches (:88-149).
+//
+// A sort-middle pipeline in the style of Laine & Karras ("High-Performance Software Rasterization on GPUs", HPG 2011), six
+// launches on the caller's scratch:
+//   k_rs_clear   zero the per-bin counters
+//   k_rs_prep    one block: the first triangle of every draw (exclusive scan of index_count / 3) and the triangle count
+//   k_rs_setup   lane = triangle: vertex stage, near / guard-band clip, viewport, 16.8 snap, cull, bounding box; bin counts
+//   k_rs_scan    one wave: every bin's list offset in the pool, in raster order; a list that does not fit takes none
+//   k_rs_fill    lane = triangle: its id into the list of every bin its box touches (any order: k_rs_raster sorts)
+//   k_rs_raster  block = 16 x 16-pixel bin, lane = pixel: depth, stencil and the winning triangle in registers while the bin's
+//                triangles are walked in draw order, then the winner's attributes and the G-buffer encode (gbuffer_encode.hpp)
+// A bin whose list is not in the pool (or is longer than LIST_CAP) walks every triangle record in draw order instead and tests
+// its box: the same triangles in the same order, so the same bits, only slower.
+//
+// Coverage: exact 64-bit integer edge functions on 16.8 fixed-point vertices at pixel centres, top-left rule.  Depth: z / w of
+// the snapped vertices interpolated linearly in screen space (fp64, rounded once to fp32), clamped to [0, 1].  Normals: the
+// triangle's perspective-correct barycentrics from its 2D homogeneous edge planes (Olano & Greer 1997), so a clipped polygon
+// resolves against the triangle it came from.  Built with -ffp-contract=off: tests/raster_ref.py restates every step in the
+// same operation order.
+#include "pbr_internal.hpp"
+#include "pbr_device.hpp"
+
+using namespace pbr;
+
+namespace {
+
+#include "gbuffer_encode.hpp"
+
+constexpr uint32_t BIN = 16;               // bin edge in pixels: 256 lanes, one per pixel
+constexpr uint32_t LIST_CAP = 2048;        // longest bin list sorted in LDS
+constexpr float GUARD = 128.0f;            // guard band: |x|, |y| <= GUARD * w (clip space) needs no x / y clipping
+constexpr uint32_t MAX_POLY = 8;           // a triangle clipped by five planes
+constexpr uint32_t NONE = 0xffffffffu;
+
+// raster record: the clipped, snapped polygon (a fan from vertex 0) in global 16.8 fixed point
+struct alignas(16) RsTri {
+    uint32_t n;                            // vertices; 0 = nothing to rasterize
+    uint32_t lo, hi;                       // pixel bounding box clamped to the tile, global pixels x | y << 16, inclusive
+    uint32_t pad;
+    int32_t X[MAX_POLY], Y[MAX_POLY];
+    float Z[MAX_POLY];
+};
+static_assert(sizeof(RsTri) == 112, "raster record layout");
+// resolve record: lambda_i(px, py) = (c[3i] * px + c[3i+1] * py) + c[3i+2] (screen pixels), normal_ws of vertex i = n[3i..3i+2]
+struct RsAttr {
+    float c[9];
+    float n[9];
+    uint32_t draw;
+    uint32_t pad;
+};
+static_assert(sizeof(RsAttr) == 80, "resolve record layout");
+
+// scratch layout (byte offsets, 256-aligned); everything up to `pool` is the minimum
+struct Layout {
+    size_t draw_base, count, cursor, offset, tris, attrs, pool;
+    uint32_t nbx, nby;
+};
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline Layout layout(uint32_t w, uint32_t h, uint32_t n_triangles) {
+    Layout L;
+    L.nbx = (w + BIN - 1) / BIN;
+    L.nby = (h + BIN - 1) / BIN;
+    const size_t bins = (size_t)L.nbx * L.nby;
+    L.draw_base = 256;                                           // [0, 256): header, word 0 = triangle count
+    L.count = L.draw_base + align256(((size_t)PBR_RASTER_MAX_DRAWS + 1) * 4);
+    L.cursor = L.count + align256(bins * 4);
+    L.offset = L.cursor + align256(bins * 4);
+    L.tris = L.offset + align256(bins * 4);
+    L.attrs = L.tris + align256((size_t)n_triangles * sizeof(RsTri));
+    L.pool = L.attrs + align256((size_t)n_triangles * sizeof(RsAttr));
+    return L;
+}
+
+struct RsParams {
+    float View[16], Projection[16];
+    float half_w, half_h;
+    uint32_t x0, y0, w, h;
+    uint32_t nbx;
+    uint32_t n_vertices, n_indices, n_draws;
+    uint32_t pitch;
+    uint32_t pool_cap;                     // entries of the list pool
+};
+
+struct ClipV { float x, y, z, w; };
+
+// row r of a row-major matrix times (x, y, z, w): mul(M, v), summed left to right
+__device__ __forceinline__ float row4(const float* m, float x, float y, float z, float w) {
+    return ((m[0] * x + m[1] * y) + m[2] * z) + m[3] * w;
+}
+// clip planes: 0 near (z >= 0), 1-4 the guard band (x >= -G w, x <= G w, y >= -G w, y <= G w); inside <=> d >= 0
+__device__ __forceinline__ float plane_d(const ClipV& v, uint32_t pl) {
+    switch (pl) {
+        case 0: return v.z;
+        case 1: return v.x + GUARD * v.w;
+        case 2: return GUARD * v.w - v.x;
+        case 3: return v.y + GUARD * v.w;
+        default: return GUARD * v.w - v.y;
+    }
+}
+
+// exclusive scan over a block of 1024 lanes; `total` = the block's sum
+__device__ uint64_t block_scan_1024(uint64_t v, uint64_t* lds, uint64_t& total) {
+    const uint32_t t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024u; off <<= 1) {
+        const uint64_t a = t >= off ? lds[t - off] : 0;
+        __syncthreads();
+        lds[t] += a;
+        __syncthreads();
+    }
+    total = lds[1023];
+    const uint64_t incl = lds[t];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(256) void k_rs_clear(uint32_t* __restrict__ count, uint32_t* __restrict__ cursor, uint32_t n) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        count[i] = 0;
+        cursor[i] = 0;
+    }
+}
+
+// draw_base[d] = first triangle id of draw d (index_count / 3 triangles each, in draw order), clamped to max_tris;
+// hdr[0] = the number of triangles rasterized (ids >= max_tris are not)
+__global__ __launch_bounds__(1024) void k_rs_prep(const pbr_draw* __restrict__ draws, uint32_t n_draws, uint32_t max_tris,
+                                                  uint32_t* __restrict__ draw_base, uint32_t* __restrict__ hdr) {
+    __shared__ uint64_t lds[1024];
+    const uint32_t per = (n_draws + 1023u) / 1024u;
+    const uint32_t b = min(threadIdx.x * per, n_draws), e = min(b + per, n_draws);
+    uint64_t s = 0;
+    for (uint32_t d = b; d < e; d++) s += draws[d].index_count / 3u;
+    uint64_t total;
+    uint64_t run = block_scan_1024(s, lds, total);
+    for (uint32_t d = b; d < e; d++) {
+        draw_base[d] = (uint32_t)min(run, (uint64_t)max_tris);
+        run += draws[d].index_count / 3u;
+    }
+    if (threadIdx.x == 0) {
+        const uint32_t n = (uint32_t)min(total, (uint64_t)max_tris);
+        draw_base[n_draws] = n;
+        hdr[0] = n;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* __restrict__ vtx, const uint32_t* __restrict__ idx,
+                                                  const pbr_draw* __restrict__ draws, const uint32_t* __restrict__ draw_base,
+                                                  const uint32_t* __restrict__ hdr, RsTri* __restrict__ tris,
+                                                  RsAttr* __restrict__ attrs, uint32_t* __restrict__ bin_count) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= hdr[0]) return;
+    uint32_t lo = 0, hi = p.n_draws - 1;        // the draw: the last d with draw_base[d] <= t
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (draw_base[mid] <= t) lo = mid; else hi = mid - 1u;
+    }
+    const pbr_draw& d = draws[lo];
+    RsTri rec;
+    rec.n = 0; rec.lo = 0; rec.hi = 0; rec.pad = 0;
+    RsAttr at;
+    for (int i = 0; i < 9; i++) { at.c[i] = 0.0f; at.n[i] = 0.0f; }
+    at.draw = lo; at.pad = 0;
+    // guard (device data): a draw range past n_indices, or an index (+ base_vertex) outside [0, n_vertices): the triangle is dropped
+    const uint64_t first = (uint64_t)d.first_index + 3ull * (t - draw_base[lo]);
+    bool ok = (uint64_t)d.first_index + d.index_count <= p.n_indices;
+    int64_t vi[3] = {0, 0, 0};
+    for (int k = 0; k < 3 && ok; k++) {
+        vi[k] = (int64_t)idx[first + k] + d.base_vertex;
+        ok = vi[k] >= 0 && vi[k] < (int64_t)p.n_vertices;
+    }
+    ClipV c[3];
+    if (ok) {
+        for (int k = 0; k < 3; k++) {
+            const pbr_vertex& v = vtx[vi[k]];
+            // gbuffer.hlsl:77-82: position_ws = Model (p, 1); normal_ws = transpose(InvModel) (n, 0); clip = Projection (View position_ws)
+            float pw[4], pv[4];
+            for (int r = 0; r < 4; r++) pw[r] = row4(d.Model + 4 * r, v.position[0], v.position[1], v.position[2], 1.0f);
+            for (int r = 0; r < 4; r++) pv[r] = row4(p.View + 4 * r, pw[0], pw[1], pw[2], pw[3]);
+            c[k].x = row4(p.Projection + 0, pv[0], pv[1], pv[2], pv[3]);
+            c[k].y = row4(p.Projection + 4, pv[0], pv[1], pv[2], pv[3]);
+            c[k].z = row4(p.Projection + 8, pv[0], pv[1], pv[2], pv[3]);
+            c[k].w = row4(p.Projection + 12, pv[0], pv[1], pv[2], pv[3]);
+            for (int i = 0; i < 3; i++)
+                at.n[3 * k + i] = ((d.InvModel[i] * v.normal[0] + d.InvModel[4 + i] * v.normal[1]) + d.InvModel[8 + i] * v.normal[2]) +
+                                  d.InvModel[12 + i] * 0.0f;
+        }
+        // the triangle's 2D homogeneous screen vertices (sx / w, sy / w = the viewport transform) and their edge planes
+        float sx[3], sy[3], sw[3];
+        for (int k = 0; k < 3; k++) {
+            sx[k] = (c[k].x + c[k].w) * p.half_w;
+            sy[k] = (c[k].w - c[k].y) * p.half_h;
+            sw[k] = c[k].w;
+        }
+        for (int i = 0; i < 3; i++) {
+            const int j = (i + 1) % 3, k = (i + 2) % 3;
+            at.c[3 * i + 0] = sy[j] * sw[k] - sw[j] * sy[k];
+            at.c[3 * i + 1] = sw[j] * sx[k] - sx[j] * sw[k];
+            at.c[3 * i + 2] = sx[j] * sy[k] - sy[j] * sx[k];
+        }
+    }
+    attrs[t] = at;
+    if (ok) {
+        // clip against the near plane and, outside the guard band, its four planes (Sutherland-Hodgman; a plane no vertex is
+        // outside of is skipped).  A new vertex is computed from its edge's inside endpoint towards the outside one, so two
+        // triangles that share the edge get the same point.
+        ClipV poly[MAX_POLY], tmp[MAX_POLY];
+        uint32_t n = 3;
+        poly[0] = c[0]; poly[1] = c[1]; poly[2] = c[2];
+        for (uint32_t pl = 0; pl < 5 && n >= 3; pl++) {
+            bool any_out = false;
+            for (uint32_t i = 0; i < n; i++) any_out |= !(plane_d(poly[i], pl) >= 0.0f);
+            if (!any_out) continue;
+            // in exact arithmetic a plane adds at most one vertex (3 + 5 = MAX_POLY); rounding near a plane can make more sign
+            // changes: such a polygon is dropped (m counts on, nothing is written past MAX_POLY)
+            uint32_t m = 0;
+            for (uint32_t i = 0; i < n; i++) {
+                const ClipV a = poly[i], b = poly[i + 1 == n ? 0 : i + 1];
+                const float da = plane_d(a, pl), db = plane_d(b, pl);
+                const bool ia = da >= 0.0f, ib = db >= 0.0f;
+                if (ia) {
+                    if (m < MAX_POLY) tmp[m] = a;
+                    m++;
+                }
+                if (ia != ib) {
+                    const ClipV in = ia ? a : b, out = ia ? b : a;
+                    const float din = ia ? da : db, dout = ia ? db : da;
+                    const float s = din / (din - dout);
+                    if (m < MAX_POLY)
+                        tmp[m] = ClipV{in.x + (out.x - in.x) * s, in.y + (out.y - in.y) * s, in.z + (out.z - in.z) * s,
+                                       in.w + (out.w - in.w) * s};
+                    m++;
+                }
+            }
+            n = m <= MAX_POLY ? m : 0;
+            for (uint32_t i = 0; i < n; i++) poly[i] = tmp[i];
+        }
+        // viewport (0, 0, full_w, full_h), snap to 1/256 pixel (round to nearest even), depth z / w
+        bool good = n >= 3;
+        for (uint32_t i = 0; i < n && good; i++) {
+            const float xn = poly[i].x / poly[i].w, yn = poly[i].y / poly[i].w;
+            good = poly[i].w > 0.0f && fabsf(xn) <= 2.0f * GUARD && fabsf(yn) <= 2.0f * GUARD;
+            if (good) {
+                rec.X[i] = (int32_t)rintf(((xn + 1.0f) * p.half_w) * 256.0f);
+                rec.Y[i] = (int32_t)rintf(((1.0f - yn) * p.half_h) * 256.0f);
+                rec.Z[i] = poly[i].z / poly[i].w;
+            }
+        }
+        // something to draw: a front-facing (clockwise in y-down screen space) fan triangle of non-zero area
+        bool front = false;
+        for (uint32_t k = 1; good && k + 1 < n; k++) {
+            const int64_t area = (int64_t)(rec.X[k] - rec.X[0]) * (rec.Y[k + 1] - rec.Y[0]) -
+                                 (int64_t)(rec.Y[k] - rec.Y[0]) * (rec.X[k + 1] - rec.X[0]);
+            front |= area > 0;
+        }
+        if (good && front) {
+            int32_t x0 = rec.X[0], x1 = rec.X[0], y0 = rec.Y[0], y1 = rec.Y[0];
+            for (uint32_t i = 1; i < n; i++) {
+                x0 = min(x0, rec.X[i]); x1 = max(x1, rec.X[i]);
+                y0 = min(y0, rec.Y[i]); y1 = max(y1, rec.Y[i]);
+            }
+            // pixels whose centre (256 x + 128) lies in [x0, x1], clamped to the tile
+            const int64_t px0 = max(-((128 - (int64_t)x0) >> 8), (int64_t)p.x0), px1 = min(((int64_t)x1 - 128) >> 8, (int64_t)(p.x0 + p.w) - 1);
+            const int64_t py0 = max(-((128 - (int64_t)y0) >> 8), (int64_t)p.y0), py1 = min(((int64_t)y1 - 128) >> 8, (int64_t)(p.y0 + p.h) - 1);
+            if (px0 <= px1 && py0 <= py1) {
+                rec.n = n;
+                rec.lo = (uint32_t)px0 | ((uint32_t)py0 << 16);
+                rec.hi = (uint32_t)px1 | ((uint32_t)py1 << 16);
+                for (uint32_t by = ((uint32_t)py0 - p.y0) / BIN; by <= ((uint32_t)py1 - p.y0) / BIN; by++)
+                    for (uint32_t bx = ((uint32_t)px0 - p.x0) / BIN; bx <= ((uint32_t)px1 - p.x0) / BIN; bx++)
+                        atomicAdd(&bin_count[by * p.nbx + bx], 1u);
+            }
+        }
+    }
+    tris[t] = rec;
+}
+
+// offset[b] = start of bin b's list in the pool, or NONE: bins in raster order take the pool's next entries while their list
+// fits; a list that does not fit, or is longer than LIST_CAP, gets NONE and takes nothing (a later, shorter list may still fit).
+// One wave: a shuffle scan of 64 counts at a time, restarted behind each list that is refused.
+__global__ __launch_bounds__(64) void k_rs_scan(const uint32_t* __restrict__ count, uint32_t n_bins, uint32_t pool_cap,
+                                                uint32_t* __restrict__ offset) {
+    const uint32_t lane = threadIdx.x;
+    unsigned long long run = 0;
+    for (uint32_t base = 0; base < n_bins;) {
+        const uint32_t i = base + lane;
+        const unsigned long long c = i < n_bins ? count[i] : 0ull;
+        unsigned long long inc = c;
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const unsigned long long y = __shfl_up(inc, off);
+            if (lane >= off) inc += y;
+        }
+        const bool refused = c != 0 && (c > LIST_CAP || run + inc > pool_cap);
+        const unsigned long long mask = __ballot(refused);
+        const uint32_t stop = mask ? (uint32_t)__ffsll(mask) - 1u : 64u;   // lanes below `stop` fit
+        if (i < n_bins && lane < stop) offset[i] = (uint32_t)(run + inc - c);
+        if (i < n_bins && lane == stop) offset[i] = NONE;
+        if (stop > 0) run += __shfl(inc, (int)stop - 1);
+        base += stop < 64u ? stop + 1u : 64u;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rs_fill(RsParams p, const uint32_t* __restrict__ hdr, const RsTri* __restrict__ tris,
+                                                 const uint32_t* __restrict__ offset, uint32_t* __restrict__ cursor,
+                                                 uint32_t* __restrict__ pool) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= hdr[0]) return;
+    const RsTri& r = tris[t];
+    if (r.n == 0) return;
+    const uint32_t px0 = (r.lo & 0xffffu) - p.x0, py0 = (r.lo >> 16) - p.y0, px1 = (r.hi & 0xffffu) - p.x0, py1 = (r.hi >> 16) - p.y0;
+    for (uint32_t by = py0 / BIN; by <= py1 / BIN; by++)
+        for (uint32_t bx = px0 / BIN; bx <= px1 / BIN; bx++) {
+            const uint32_t b = by * p.nbx + bx, off = offset[b];
+            if (off != NONE) pool[off + atomicAdd(&cursor[b], 1u)] = t;
+        }
+}
+
+// edge a -> b at P: (Xb - Xa)(PY - Ya) - (Yb - Ya)(PX - Xa); > 0 inside a front-facing triangle.  On the edge (0) a pixel centre is
+// covered only by a top edge (horizontal, dx > 0) or a left edge (dy < 0): covered <=> E >= bias, bias = 0 there and 1 elsewhere.
+__device__ __forceinline__ int64_t edge_fn(int32_t xa, int32_t ya, int32_t xb, int32_t yb, int64_t PX, int64_t PY) {
+    return (int64_t)(xb - xa) * (PY - ya) - (int64_t)(yb - ya) * (PX - xa);
+}
+__device__ __forceinline__ int64_t edge_bias(int32_t xa, int32_t ya, int32_t xb, int32_t yb) {
+    const int32_t dx = xb - xa, dy = yb - ya;
+    return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1;
+}
+
+__global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* __restrict__ draws, const uint32_t* __restrict__ hdr,
+                                                   const RsTri* __restrict__ tris, const RsAttr* __restrict__ attrs,
+                                                   const uint32_t* __restrict__ count, const uint32_t* __restrict__ offset,
+                                                   const uint32_t* __restrict__ pool, uint32_t* __restrict__ A, uint32_t* __restrict__ B,
+                                                   uint32_t* __restrict__ C, float* __restrict__ depth, uint8_t* __restrict__ stencil) {
+    __shared__ uint32_t list[LIST_CAP];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lx = blockIdx.x * BIN + (tid & (BIN - 1)), ly = blockIdx.y * BIN + tid / BIN;
+    const bool inside = lx < p.w && ly < p.h;
+    const uint32_t gx = p.x0 + lx, gy = p.y0 + ly;
+    const int64_t PX = (int64_t)gx * 256 + 128, PY = (int64_t)gy * 256 + 128;
+    float zbuf = 1.0f;
+    uint32_t sten = 0, win = NONE;
+
+    // one triangle, every fan triangle of its polygon (t is uniform across the block)
+    auto fragment = [&](uint32_t t) {
+        const RsTri& r = tris[t];
+        const uint32_t n = r.n;
+        const int32_t X0 = r.X[0], Y0 = r.Y[0];
+        const float Z0 = r.Z[0];
+        for (uint32_t k = 1; k + 1 < n; k++) {
+            const int32_t X1 = r.X[k], Y1 = r.Y[k], X2 = r.X[k + 1], Y2 = r.Y[k + 1];
+            const int64_t area = (int64_t)(X1 - X0) * (Y2 - Y0) - (int64_t)(Y1 - Y0) * (X2 - X0);
+            if (area <= 0) continue;             // back-facing or zero area
+            const int64_t w0 = edge_fn(X1, Y1, X2, Y2, PX, PY), w1 = edge_fn(X2, Y2, X0, Y0, PX, PY), w2 = edge_fn(X0, Y0, X1, Y1, PX, PY);
+            if (inside && w0 >= edge_bias(X1, Y1, X2, Y2) && w1 >= edge_bias(X2, Y2, X0, Y0) && w2 >= edge_bias(X0, Y0, X1, Y1)) {
+                const double z0 = (double)Z0;
+                const double zd = z0 + ((double)w1 * ((double)r.Z[k] - z0) + (double)w2 * ((double)r.Z[k + 1] - z0)) / (double)area;
+                float z = (float)zd;
+                z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;
+                if (z < zbuf) {                  // LESS: strictly nearer than every earlier fragment
+                    zbuf = z;
+                    win = t;
+                    sten = sten < 255u ? sten + 1u : 255u;   // INCR_SAT
+                }
+            }
+        }
+    };
+
+    const uint32_t b = blockIdx.y * p.nbx + blockIdx.x;
+    const uint32_t cnt = count[b], off = offset[b];
+    if (cnt != 0) {
+        if (off != NONE && cnt <= LIST_CAP) {
+            // the bin's list into LDS and sorted (bitonic): draw order
+            uint32_t np2 = 1;
+            while (np2 < cnt) np2 <<= 1;
+            for (uint32_t i = tid; i < np2; i += 256u) list[i] = i < cnt ? pool[off + i] : NONE;
+            __syncthreads();
+            for (uint32_t k = 2; k <= np2; k <<= 1)
+                for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                    for (uint32_t i = tid; i < np2; i += 256u) {
+                        const uint32_t l = i ^ j;
+                        if (l > i) {
+                            const uint32_t a = list[i], c = list[l];
+                            if ((a > c) == ((i & k) == 0)) { list[i] = c; list[l] = a; }
+                        }
+                    }
+                    __syncthreads();
+                }
+            for (uint32_t i = 0; i < cnt; i++) fragment(__builtin_amdgcn_readfirstlane(list[i]));
+        } else {
+            // fallback: every triangle record in draw order, 256 box tests at a time
+            const uint32_t rx0 = p.x0 + blockIdx.x * BIN, ry0 = p.y0 + blockIdx.y * BIN;
+            const uint32_t rx1 = min(rx0 + BIN, p.x0 + p.w) - 1u, ry1 = min(ry0 + BIN, p.y0 + p.h) - 1u;
+            const uint32_t total = hdr[0];
+            for (uint32_t base = 0; base < total; base += 256u) {
+                const uint32_t t = base + tid;
+                uint32_t hit = 0;
+                if (t < total) {
+                    const RsTri& r = tris[t];
+                    hit = r.n != 0 && (r.lo & 0xffffu) <= rx1 && (r.hi & 0xffffu) >= rx0 && (r.lo >> 16) <= ry1 && (r.hi >> 16) >= ry0;
+                }
+                list[tid] = hit;
+                __syncthreads();
+                const uint32_t m = min(256u, total - base);
+                for (uint32_t j = 0; j < m; j++)
+                    if (list[j]) fragment(base + j);
+                __syncthreads();
+            }
+        }
+    }
+    // resolve: the winner's perspective-correct normal and its draw's constants -> ps_main's outputs
+    uint32_t qa = 0, qb = 0, qc = 0;
+    if (win != NONE) {
+        const RsAttr& at = attrs[win];
+        const pbr_draw& d = draws[at.draw];
+        const float fx = (float)gx + 0.5f, fy = (float)gy + 0.5f;
+        const float l0 = (at.c[0] * fx + at.c[1] * fy) + at.c[2];
+        const float l1 = (at.c[3] * fx + at.c[4] * fy) + at.c[5];
+        const float l2 = (at.c[6] * fx + at.c[7] * fy) + at.c[8];
+        const float inv = 1.0f / ((l0 + l1) + l2);
+        // gbuffer.hlsl:99-146, the Use*Map == false branches: AO = 0 (the reference's value without an AO map)
+        const float4 a = make_float4(d.Albedo[0], d.Albedo[1], d.Albedo[2], d.Emission);
+        const float4 b = make_float4(((l0 * at.n[0] + l1 * at.n[3]) + l2 * at.n[6]) * inv, ((l0 * at.n[1] + l1 * at.n[4]) + l2 * at.n[7]) * inv,
+                                     ((l0 * at.n[2] + l1 * at.n[5]) + l2 * at.n[8]) * inv, d.Roughness);
+        const float4 c = make_float4(d.Metallic, 0.0f, 0.0f, 0.0f);
+        PBR_GBUFFER_ENCODE(a, b, c, pa, pb, pc)
+        qa = pa; qb = pb; qc = pc;
+    }
+    if (inside) {
+        const size_t i = (size_t)ly * p.pitch + lx;
+        A[i] = qa;
+        B[i] = qb;
+        C[i] = qc;
+        depth[i] = zbuf;
+        stencil[i] = (uint8_t)sten;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
+    return layout(w, h, n_triangles).pool;
+}
+
+size_t pbr_gbuffer_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
+    const Layout L = layout(w, h, n_triangles);
+    return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
+}
+
+pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                              void* scratch, size_t scratch_bytes) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, g && tile && vertices && indices && draws && A && B && C && depth && stencil && scratch,
+                "pbr_gbuffer_raster: null pointer");
+    PBR_REQUIRE(ctx, n_vertices && n_indices && n_draws && max_triangles, "pbr_gbuffer_raster: empty vertex / index / draw list");
+    PBR_REQUIRE(ctx, n_draws <= PBR_RASTER_MAX_DRAWS && max_triangles <= PBR_RASTER_MAX_TRIANGLES,
+                "pbr_gbuffer_raster: more draws or triangles than the limits");
+    PBR_REQUIRE(ctx, tile->w && tile->h && tile->full_w && tile->full_h && tile->full_w <= PBR_RASTER_MAX_SIZE &&
+                tile->full_h <= PBR_RASTER_MAX_SIZE && (uint64_t)tile->x0 + tile->w <= tile->full_w &&
+                (uint64_t)tile->y0 + tile->h <= tile->full_h, "pbr_gbuffer_raster: bad tile");
+    PBR_REQUIRE(ctx, pitch >= tile->w, "pbr_gbuffer_raster: pitch < tile width");
+    PBR_REQUIRE(ctx, ((pbr::addr(vertices) | pbr::addr(indices) | pbr::addr(draws) | pbr::addr(A) | pbr::addr(B) | pbr::addr(C) |
+                       pbr::addr(depth)) & 3u) == 0 && (pbr::addr(scratch) & 15u) == 0,
+                "pbr_gbuffer_raster: unaligned buffer");
+    const Layout L = layout(tile->w, tile->h, max_triangles);
+    PBR_REQUIRE(ctx, scratch_bytes >= L.pool, "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_min_scratch_bytes");
+
+    RsParams p;
+    for (int i = 0; i < 16; i++) { p.View[i] = g->View[i]; p.Projection[i] = g->Projection[i]; }
+    p.half_w = 0.5f * (float)tile->full_w;
+    p.half_h = 0.5f * (float)tile->full_h;
+    p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h;
+    p.nbx = L.nbx;
+    p.n_vertices = n_vertices; p.n_indices = n_indices; p.n_draws = n_draws;
+    p.pitch = pitch;
+    const size_t pool_entries = (scratch_bytes - L.pool) / 4;
+    p.pool_cap = (uint32_t)min(pool_entries, (size_t)0xfffffffeu);
+
+    char* s = static_cast<char*>(scratch);
+    uint32_t* hdr = reinterpret_cast<uint32_t*>(s);
+    uint32_t* draw_base = reinterpret_cast<uint32_t*>(s + L.draw_base);
+    uint32_t* count = reinterpret_cast<uint32_t*>(s + L.count);
+    uint32_t* cursor = reinterpret_cast<uint32_t*>(s + L.cursor);
+    uint32_t* offset = reinterpret_cast<uint32_t*>(s + L.offset);
+    RsTri* tris = reinterpret_cast<RsTri*>(s + L.tris);
+    RsAttr* attrs = reinterpret_cast<RsAttr*>(s + L.attrs);
+    uint32_t* pool = reinterpret_cast<uint32_t*>(s + L.pool);
+    const uint32_t n_bins = L.nbx * L.nby;
+    const uint32_t tri_blocks = (max_triangles + 255u) / 256u;
+
+    hipLaunchKernelGGL(k_rs_clear, dim3(min((n_bins + 255u) / 256u, 1024u)), dim3(256), 0, ctx->stream, count, cursor, n_bins);
+    if (pbr_status st = pbr::launched(ctx, "k_rs_clear")) return st;
+    hipLaunchKernelGGL(k_rs_prep, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr);
+    if (pbr_status st = pbr::launched(ctx, "k_rs_prep")) return st;
+    hipLaunchKernelGGL(k_rs_setup, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, draw_base, hdr, tris, attrs, count);
+    if (pbr_status st = pbr::launched(ctx, "k_rs_setup")) return st;
+    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(64), 0, ctx->stream, count, n_bins, p.pool_cap, offset);
+    if (pbr_status st = pbr::launched(ctx, "k_rs_scan")) return st;
+    hipLaunchKernelGGL(k_rs_fill, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, hdr, tris, offset, cursor, pool);
+    if (pbr_status st = pbr::launched(ctx, "k_rs_fill")) return st;
+    hipLaunchKernelGGL(k_rs_raster, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs, count, offset, pool,
+                       A, B, C, depth, stencil);
+    return pbr::launched(ctx, "k_rs_raster");
+}
+
+}  // extern "C"

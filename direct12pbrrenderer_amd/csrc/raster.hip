@@ -68,15 +68,8 @@ __global__ __launch_bounds__(256) void k_skybox(SkyParams p, const float* __rest
     store_h4(hdr + 4 * ((size_t)py * p.hdr_pitch + px), f4(c.x, c.y, c.z, 1.0f));
 }
 
-__device__ __forceinline__ uint32_t unorm8(float x) { return (uint32_t)floorf(saturatef(x) * 255.0f + 0.5f); }
-__device__ __forceinline__ float sign_custom(float x) { return x < 0.0f ? -1.0f : 1.0f; }
-// decode_gamma (global.hlsli:73-77): pow(c, 2.2) the way the shader compiler lowers it, exp2(2.2 * log2(c)) on
-// the transcendental unit (v_log_f32 / v_exp_f32, 1 ULP each).  The result only feeds an 8-bit UNORM target:
-// relative error < 1e-6 moves a value across a rounding boundary on ~1e-4 of the texels (by one step).
-// pow(0) = 0, pow(negative) = NaN -> saturate -> 0, like the libm formulation.
-__device__ __forceinline__ float decode_gamma(float c) {
-    return __builtin_amdgcn_exp2f(2.2f * __builtin_amdgcn_logf(c));
-}
+// unorm8, decode_gamma, pack_normal: shared with the rasterizer's resolve (gbuffer_raster.hip)
+#include "gbuffer_encode.hpp"
 
 __global__ __launch_bounds__(256) void k_gbuffer_encode(const float4* __restrict__ m0, const float4* __restrict__ m1,
                                                         const float4* __restrict__ m2, uint32_t w, uint32_t h,
@@ -87,21 +80,7 @@ __global__ __launch_bounds__(256) void k_gbuffer_encode(const float4* __restrict
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * pitch + x;
     const float4 a = m0[i], b = m1[i], c = m2[i];
-    // decode_gamma, global.hlsli:73-77
-    const uint32_t pa = unorm8(decode_gamma(a.x)) | (unorm8(decode_gamma(a.y)) << 8) | (unorm8(decode_gamma(a.z)) << 16) |
-                        (unorm8(a.w) << 24);
-    // pack_normal(normalize(n)), global.hlsli:117-128
-    V3 n = normalize3_exact(v3(b.x, b.y, b.z));
-    const float sum = fabsf(n.x) + fabsf(n.y) + fabsf(n.z);
-    float dx = n.x / sum, dy = n.y / sum;
-    const float dz = n.z / sum;
-    if (dz < 0.0f) {
-        const float nx = sign_custom(dx) * (1.0f - fabsf(dy));
-        const float ny = sign_custom(dy) * (1.0f - fabsf(dx));
-        dx = nx; dy = ny;
-    }
-    const uint32_t pb = unorm8(dx * 0.5f + 0.5f) | (unorm8(dy * 0.5f + 0.5f) << 8) | (255u << 16);
-    const uint32_t pc = unorm8(b.w) | (unorm8(c.x) << 8) | (unorm8(c.y) << 16);
+    PBR_GBUFFER_ENCODE(a, b, c, pa, pb, pc)
     A[i] = pa; B[i] = pb; C[i] = pc;
 }
 

@@ -26,6 +26,7 @@ SIGNATURES = {
     "pbrh_light_buffer": (_int, [_u32, _u32, _vp, _vp, _int, _vp, _int]),
     "pbrh_set_gbuffer": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pbrh_set_materials": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "pbrh_set_meshes": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32]),
     "pbrh_set_initial_luminance": (_int, [_vp, C.c_float]),
     "pbrh_set_tile": (_int, [_vp] + [_u32] * 8),
     "pbrh_comm_init": (_int, [_vp, _int, _int, _vp]),
@@ -121,6 +122,15 @@ class HostRenderer:
     def set_gbuffer(self, gb):
         planes = [np.ascontiguousarray(gb[k]) for k in ("A", "B", "C", "depth", "stencil")]
         self._check(self.lib.pbrh_set_gbuffer(self.h, *[p.ctypes.data for p in planes]))
+
+    def set_meshes(self, vertices, indices, draws):
+        """constant-material meshes (structs.VERTEX_DTYPE, uint32 indices, structs.DRAW_DTYPE records): GBufferPass rasterizes them
+        every frame (pbr_gbuffer_raster) instead of uploading planes"""
+        from .structs import DRAW_DTYPE, VERTEX_DTYPE
+        v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
+        i = np.ascontiguousarray(indices, dtype=np.uint32)
+        d = np.ascontiguousarray(draws, dtype=DRAW_DTYPE)
+        self._check(self.lib.pbrh_set_meshes(self.h, v.ctypes.data, len(v), i.ctypes.data, len(i), d.ctypes.data, len(d)))
 
     def set_initial_luminance(self, v):
         self._check(self.lib.pbrh_set_initial_luminance(self.h, float(v)))

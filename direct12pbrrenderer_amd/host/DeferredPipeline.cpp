@@ -91,8 +91,41 @@ GBufferPass::GBufferPass(RenderSize s) {
     mShadingState.SetShader("gbuffer.hlsl", false);
 }
 
+void GBufferPass::UploadMeshes(FGContext* context, MeshSource& meshes, uint32 w, uint32 h) {
+    if (context->CommandList->FramesInFlight() > 1) context->CommandList->WaitIdle();   // earlier frames still read the buffers
+    uint64_t tris = 0;
+    for (const pbr_draw& d : meshes.Draws) tris += d.index_count / 3u;
+    if (tris == 0 || tris > PBR_RASTER_MAX_TRIANGLES) throw HipException("GBufferPass: the draws hold no triangles, or more than PBR_RASTER_MAX_TRIANGLES");
+    auto upload = [](std::unique_ptr<DeviceStructuredBuffer>& buf, const void* data, size_t bytes, uint32 stride) {
+        if (bytes > 0xffffffffu) throw HipException("GBufferPass: mesh buffer larger than 4 GiB");
+        buf = std::make_unique<DeviceStructuredBuffer>((uint32)bytes, stride);
+        buf->Commit(data, bytes);
+    };
+    upload(mVertices, meshes.Vertices.data(), meshes.Vertices.size() * sizeof(pbr_vertex), sizeof(pbr_vertex));
+    upload(mIndices, meshes.Indices.data(), meshes.Indices.size() * sizeof(uint32_t), sizeof(uint32_t));
+    upload(mDraws, meshes.Draws.data(), meshes.Draws.size() * sizeof(pbr_draw), sizeof(pbr_draw));
+    mMaxTriangles = (uint32)tris;
+    const size_t scratch = pbr_gbuffer_raster_scratch_bytes(w, h, mMaxTriangles);
+    if (scratch > 0xffffffffu) throw HipException("GBufferPass: raster scratch larger than 4 GiB");
+    mRasterScratch = std::make_unique<DeviceStructuredBuffer>((uint32)scratch, 4);
+    meshes.Dirty = false;
+}
+
 void GBufferPass::Execute(FGContext* context) {
     PIXScope(context->CommandList, "Gbuffer Pass");
+    MeshSource& meshes = context->Scene->Meshes();
+    if (!meshes.Empty()) {   // DrawModel per draw (DeferredPipeline.cpp:138-185): gbuffer.hlsl + DefaultOpaque, in draw order
+        auto* a = As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::GBufferA));
+        auto* b = As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::GBufferB));
+        auto* c = As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::GBufferC));
+        auto* ds = As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::DepthStencil));
+        if (meshes.Dirty || !mRasterScratch) UploadMeshes(context, meshes, a->Width(), a->Height());
+        context->CommandList->RasterGBuffer(&mShadingState, (const pbr_vertex*)mVertices->DevicePtr(), (uint32)meshes.Vertices.size(),
+                                            (const uint32_t*)mIndices->DevicePtr(), (uint32)meshes.Indices.size(),
+                                            (const pbr_draw*)mDraws->DevicePtr(), (uint32)meshes.Draws.size(), mMaxTriangles,
+                                            a, b, c, ds, mRasterScratch->DevicePtr(), mRasterScratch->Size());
+        return;
+    }
     GBufferSource& src = context->Scene->GBuffer();
     if (!src.Dirty) return;   // the planes a rasterizer would have left in device memory are still there
     src.Dirty = false;

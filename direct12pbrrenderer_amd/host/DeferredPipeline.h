@@ -3,9 +3,9 @@
 // Same classes, resource names, constants and declared reads/writes as
 // Engine/Include/Renderer/Pipeline/DeferredPipeline.h (line references per class); Execute bodies
 // in DeferredPipeline.cpp bind by the reference's shader resource names and dispatch with the
-// reference's thread-group counts.  GBufferPass / SkyboxPass are raster passes; rasterization is out
-// of scope, their per-pixel work is not: GBufferPass uploads either the encoded G-buffer
-// planes or the rasterizer's per-pixel material attributes and encodes them with gbuffer.hlsl's
+// reference's thread-group counts.  GBufferPass / SkyboxPass are raster passes: GBufferPass rasterizes the
+// scene's constant-material meshes (pbr_gbuffer_raster) or, without meshes, uploads either the encoded
+// G-buffer planes or a rasterizer's per-pixel material attributes and encodes them with gbuffer.hlsl's
 // pixel-shader math; SkyboxPass resolves the sky on the pixels geometry left uncovered.
 #pragma once
 #include "FrameGraph.h"
@@ -63,14 +63,18 @@ protected:
     bool mReady;
 };
 
-class GBufferPass : public GraphicsPass {   // :101-137 (rasterization out of scope; ps_main's encode is pbr_gbuffer_encode)
+class GBufferPass : public GraphicsPass {   // :101-137 (meshes: pbr_gbuffer_raster; uploaded planes: pbr_gbuffer_encode)
 public:
     explicit GBufferPass(RenderSize s);
     const char* Name() const override { return "GBuffer"; }
     void Execute(FGContext* context) override;
 protected:
+    void UploadMeshes(FGContext* context, MeshSource& meshes, uint32 w, uint32 h);
     ShadingState mShadingState;
     std::unique_ptr<DeviceStructuredBuffer> mMaterialPlanes;   // device copy of GBufferSource::M0..M2
+    // device copies of MeshSource and the raster's scratch (sized for the render target and the draws' triangles)
+    std::unique_ptr<DeviceStructuredBuffer> mVertices, mIndices, mDraws, mRasterScratch;
+    uint32 mMaxTriangles = 0;
 };
 
 class DeferredShadingPass : public GraphicsPass {   // :139-190

@@ -108,6 +108,17 @@ struct GBufferSource {
     bool Dirty = true;   // host copy changed since GBufferPass last uploaded / encoded it
 };
 
+// Triangle meshes with constant per-draw materials (pbrh_set_meshes): host copies of the vertex / index buffers and of one
+// pbr_draw (ConstantBufferInstance + index range) per DrawModel call.  When draws are set, GBufferPass rasterizes them
+// (pbr_gbuffer_raster) instead of uploading a GBufferSource; it uploads the arrays once, after each change.
+struct MeshSource {
+    std::vector<pbr_vertex> Vertices;
+    std::vector<uint32_t> Indices;
+    std::vector<pbr_draw> Draws;
+    bool Dirty = false;
+    bool Empty() const { return Draws.empty(); }
+};
+
 class Scene {
 public:
     static constexpr float WorldBound = 1000.0f;   // Scene.h:194
@@ -128,11 +139,13 @@ public:
     void SetSkyBox(std::shared_ptr<SkyBox> s) { mSkyBox = std::move(s); }
     SkyBox* GetSkyBox() const { return mSkyBox.get(); }
     GBufferSource& GBuffer() { return mGBuffer; }
+    MeshSource& Meshes() { return mMeshes; }
 private:
     std::vector<SceneLight> mLights;
     LightOctree mOctreeSceneLight{WorldBound};
     std::shared_ptr<SkyBox> mSkyBox;
     GBufferSource mGBuffer;
+    MeshSource mMeshes;
 };
 
 // The PointLight[] ClusteredPass::Execute commits (DeferredPipeline.cpp:224-241): the lights Scene::CullLight hands out for

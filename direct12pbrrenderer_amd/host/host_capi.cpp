@@ -226,6 +226,7 @@ int pbrh_set_gbuffer(pbrh_renderer* r, const uint32_t* A, const uint32_t* B, con
         g.Height = r->height;
         g.M0.clear(); g.M1.clear(); g.M2.clear();
         g.Dirty = true;
+        r->scene->Meshes().Draws.clear();   // planes replace the meshes
         g.A.assign(A, A + n);
         g.B.assign(B, B + n);
         g.C.assign(C, C + n);
@@ -242,11 +243,27 @@ int pbrh_set_materials(pbrh_renderer* r, const float* m0, const float* m1, const
         g.Height = r->height;
         g.A.clear(); g.B.clear(); g.C.clear();
         g.Dirty = true;
+        r->scene->Meshes().Draws.clear();   // planes replace the meshes
         g.M0.assign(m0, m0 + 4 * n);
         g.M1.assign(m1, m1 + 4 * n);
         g.M2.assign(m2, m2 + 4 * n);
         g.Depth.assign(depth, depth + n);
         g.Stencil.assign(stencil, stencil + n);
+    });
+}
+
+int pbrh_set_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                    const void* draws, uint32_t n_draws) {
+    return guarded(r, [&] {
+        if (!vertices || !indices || !draws || !n_vertices || !n_indices || !n_draws) throw HipException("pbrh_set_meshes: null pointer / empty mesh");
+        if (n_draws > PBR_RASTER_MAX_DRAWS) throw HipException("pbrh_set_meshes: more than PBR_RASTER_MAX_DRAWS draws");
+        MeshSource& m = r->scene->Meshes();
+        const pbr_vertex* v = static_cast<const pbr_vertex*>(vertices);
+        const pbr_draw* d = static_cast<const pbr_draw*>(draws);
+        m.Vertices.assign(v, v + n_vertices);
+        m.Indices.assign(indices, indices + n_indices);
+        m.Draws.assign(d, d + n_draws);
+        m.Dirty = true;
     });
 }
 

@@ -59,6 +59,12 @@ int pbrh_set_gbuffer(pbrh_renderer* r, const uint32_t* A, const uint32_t* B, con
 /* alternative to pbrh_set_gbuffer: the rasterizer's per-pixel material attributes (three float4 planes, see
  * pbr_gbuffer_encode in pbr_hip.h); GBufferPass encodes them on the GPU */
 int pbrh_set_materials(pbrh_renderer* r, const float* m0, const float* m1, const float* m2, const float* depth, const uint8_t* stencil);
+/* constant-material triangle meshes instead of planes: n_vertices pbr_vertex (56 B), n_indices uint32 indices and n_draws pbr_draw
+ * (164 B; include/pbr_hip.h), host arrays copied here and uploaded once by GBufferPass, which then rasterizes them every frame
+ * (pbr_gbuffer_raster, draws in the order given) into GBufferA/B/C and GBufferDepthStencil.  pbrh_set_gbuffer / pbrh_set_materials
+ * drop the meshes again. */
+int pbrh_set_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                    const void* draws, uint32_t n_draws);
 int pbrh_set_initial_luminance(pbrh_renderer* r, float v);
 /* ---- multi-GPU: this renderer's target is the apron-extended tile at (x0, y0) of a full_w x full_h frame;
  * it OWNS the interior rectangle (ix, iy, iw, ih) of its target.  uv / camera ray / ClusterIndex use global pixels, the

@@ -290,6 +290,7 @@ class DeferredFrame:
         self._avg_next = ctx.zeros((1,), torch.float32)
         self.ldr = ctx.zeros((spec.h, spec.w), torch.int32)
         self.gb = None
+        self.mesh = None
         self.tile = Tile(spec.sx0, spec.sy0, spec.sw, spec.sh, spec.full_w, spec.full_h)
         self.halo_transport = halo_transport
         if spec.halo:
@@ -337,6 +338,27 @@ class DeferredFrame:
         """gb_np: dict of numpy planes covering the SHADED rectangle S (sh x sw; the extended rectangle in apron mode)."""
         assert gb_np["A"].shape == (self.spec.sh, self.spec.sw)
         self.gb = {k: self.ctx.upload(v) for k, v in gb_np.items()}
+        self.mesh = None   # uploaded planes replace meshes set before
+
+    def set_meshes(self, vertices, indices, draws):
+        """Geometry instead of uploaded planes: host arrays (structs.VERTEX_DTYPE, uint32 indices, structs.DRAW_DTYPE records) are
+        uploaded once, and every render() rasterizes them (pbr_gbuffer_raster, draws in array order) into the frame's own G-buffer
+        planes of the shaded rectangle S before the cluster, sky and shade passes (until upload_gbuffer replaces them)."""
+        s, ctx = self.spec, self.ctx
+        draws = np.ascontiguousarray(draws)
+        n_tris = int((draws["index_count"] // 3).sum())
+        self.mesh = {"vertices": ctx.upload(vertices), "n_vertices": len(vertices),
+                     "indices": ctx.upload(np.ascontiguousarray(indices, dtype=np.uint32)), "n_indices": len(indices),
+                     "draws": ctx.upload(draws), "n_draws": len(draws), "max_triangles": n_tris,
+                     "scratch": ctx.alloc_raster_scratch(s.sw, s.sh, n_tris)}
+        self.gb = {"A": ctx.zeros((s.sh, s.sw), torch.int32), "B": ctx.zeros((s.sh, s.sw), torch.int32),
+                   "C": ctx.zeros((s.sh, s.sw), torch.int32), "depth": ctx.zeros((s.sh, s.sw), torch.float32),
+                   "stencil": ctx.zeros((s.sh, s.sw), torch.uint8)}
+
+    def rasterize(self):
+        m, gb = self.mesh, self.gb
+        self.ctx.gbuffer_raster(self.g, self.tile, m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"], m["n_draws"],
+                                m["max_triangles"], gb["A"], gb["B"], gb["C"], gb["depth"], gb["stencil"], self.spec.sw, m["scratch"])
 
     def set_prev_luminance(self, v):
         self.avg.fill_(float(v))
@@ -461,6 +483,8 @@ class DeferredFrame:
     def render(self, shade_events=None):
         """One frame: every per-frame dispatch of the reference, in the frame graph's order.
         shade_events: optional list; a (start, end) pair of torch events bracketing the shade launch is appended."""
+        if self.mesh is not None:
+            self.rasterize()
         self.clustered()
         if self.sky is not None:
             self.skybox()

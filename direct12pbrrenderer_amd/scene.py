@@ -7,6 +7,9 @@
 * make_global       <- RenderScheduler::ExecutePipeline, Engine/Source/Renderer/RenderScheduler.cpp:22-38
 * attenuation presets / CaclAttenuationCoefficients <- Engine/Include/Renderer/Scene.h:126-142,
   Engine/Source/Renderer/Scene.cpp:132-165
+* model_matrix      <- SceneObject::PostDeserialized, Engine/Source/Renderer/Scene.cpp:31-36
+* Mesh / MeshScene  <- what DrawModel binds per draw (DeferredPipeline.cpp:138-185): vertex + index buffers and
+  ConstantBufferInstance (gbuffer.hlsl:33-48), the input of pbr_gbuffer_raster
 
 Everything is evaluated in float32 like the reference's Vector/Matrix classes.
 """
@@ -15,7 +18,7 @@ import math
 
 import numpy as np
 
-from .structs import LIGHT_DTYPE, Global, ShPack
+from .structs import DRAW_DTYPE, LIGHT_DTYPE, VERTEX_DTYPE, Global, ShPack
 
 f32 = np.float32
 PI = f32(3.14159265359)
@@ -200,3 +203,166 @@ def scene_file_text(recs, extra_members=True):
                                                 "mScale": v([0.1, 0.1, 0.1])}, "mModelFilePath": "Asset/Model/x.json"}]
         doc["mSkyBoxPath"] = "Asset/SkyBox/none"
     return json.dumps(doc, indent=1)
+
+
+DEG2RAD = PI / f32(180.0)
+
+
+def model_matrix(translation, rotation_deg, scale):
+    """SceneObject::PostDeserialized (Scene.cpp:31-36): FromEulerAngle(rotation in degrees) with its columns scaled by `scale`,
+    plus the translation (the rule host/SceneFile.cpp applies to the scene file's lights)."""
+    r = [float(f32(a) * DEG2RAD) for a in rotation_deg]
+    m = np.eye(4, dtype=f32)
+    m[:3, :3] = from_euler_angle(*r) * np.asarray(scale, dtype=f32)[None, :]
+    m[:3, 3] = np.asarray(translation, dtype=f32)
+    return m
+
+
+# Matrix4x4::Inverse (Engine/Include/Utils/MathLib.h:813-940, the cofactor expansion of MESA's gluInvertMatrix), which the reference
+# evaluates for every draw's InvModel (DeferredPipeline.cpp:173): entry k of the row-major result = its six signed triple
+# products m[a] * m[b] * m[c], summed left to right in float32, times 1 / det.
+_INV_TERMS = {
+    0: ("+--++-", "5.10.15 5.11.14 9.6.15 9.7.14 13.6.11 13.7.10"), 1: ("-++--+", "1.10.15 1.11.14 9.2.15 9.3.14 13.2.11 13.3.10"),
+    2: ("+--++-", "1.6.15 1.7.14 5.2.15 5.3.14 13.2.7 13.3.6"), 3: ("-++--+", "1.6.11 1.7.10 5.2.11 5.3.10 9.2.7 9.3.6"),
+    4: ("-++--+", "4.10.15 4.11.14 8.6.15 8.7.14 12.6.11 12.7.10"), 5: ("+--++-", "0.10.15 0.11.14 8.2.15 8.3.14 12.2.11 12.3.10"),
+    6: ("-++--+", "0.6.15 0.7.14 4.2.15 4.3.14 12.2.7 12.3.6"), 7: ("+--++-", "0.6.11 0.7.10 4.2.11 4.3.10 8.2.7 8.3.6"),
+    8: ("+--++-", "4.9.15 4.11.13 8.5.15 8.7.13 12.5.11 12.7.9"), 9: ("-++--+", "0.9.15 0.11.13 8.1.15 8.3.13 12.1.11 12.3.9"),
+    10: ("+--++-", "0.5.15 0.7.13 4.1.15 4.3.13 12.1.7 12.3.5"), 11: ("-++--+", "0.5.11 0.7.9 4.1.11 4.3.9 8.1.7 8.3.5"),
+    12: ("-++--+", "4.9.14 4.10.13 8.5.14 8.6.13 12.5.10 12.6.9"), 13: ("+--++-", "0.9.14 0.10.13 8.1.14 8.2.13 12.1.10 12.2.9"),
+    14: ("-++--+", "0.5.14 0.6.13 4.1.14 4.2.13 12.1.6 12.2.5"), 15: ("+--++-", "0.5.10 0.6.9 4.1.10 4.2.9 8.1.6 8.2.5"),
+}
+
+
+def inverse(m):
+    """Matrix4x4::Inverse in float32 (the draw's InvModel): cofactors, det = m0 inv0 + m1 inv4 + m2 inv8 + m3 inv12, identity if
+    det == 0, else inv * (1 / det)."""
+    a = [f32(v) for v in np.asarray(m, dtype=f32).reshape(16)]
+    inv = []
+    for k in range(16):
+        signs, terms = _INV_TERMS[k]
+        acc = None
+        for sg, t in zip(signs, terms.split()):
+            i, j, l = (int(x) for x in t.split("."))
+            p = (-a[i] if sg == "-" else a[i]) * a[j] * a[l] if acc is None else a[i] * a[j] * a[l]
+            acc = p if acc is None else (acc + p if sg == "+" else acc - p)
+        inv.append(acc)
+    det = ((a[0] * inv[0] + a[1] * inv[4]) + a[2] * inv[8]) + a[3] * inv[12]
+    if det == 0:
+        return np.eye(4, dtype=f32)
+    inv_det = f32(1.0) / det
+    return np.array([v * inv_det for v in inv], dtype=f32).reshape(4, 4)
+
+
+class Mesh:
+    """One vertex buffer (structs.VERTEX_DTYPE: position, normal, tangent, colour, uv) and its uint32 triangle list."""
+
+    def __init__(self, positions, normals, indices):
+        positions = np.asarray(positions, dtype=f32).reshape(-1, 3)
+        self.vertices = np.zeros(len(positions), dtype=VERTEX_DTYPE)
+        self.vertices["position"] = positions
+        self.vertices["normal"] = np.asarray(normals, dtype=f32).reshape(-1, 3)
+        self.indices = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+
+    @property
+    def n_triangles(self):
+        return len(self.indices) // 3
+
+
+def _orient(positions, tris, outward):
+    """Triangles wound so that (b - a) x (c - a) points along outward(a, b, c): front-facing (clockwise on screen, the
+    DefaultOpaque state) when seen from that side."""
+    p = positions[tris]
+    cr = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    flip = (cr * outward(p)).sum(axis=1) < 0
+    tris = tris.copy()
+    tris[flip, 1], tris[flip, 2] = tris[flip, 2], tris[flip, 1].copy()
+    return tris
+
+
+def uv_sphere(n_lat, n_lon, radius=1.0):
+    """A UV sphere of radius `radius` around the origin: n_lat rings of n_lon quads (fans at the poles), vertex normals =
+    the unit position, every triangle facing outwards."""
+    th = np.linspace(0.0, np.pi, n_lat + 1)
+    ph = np.linspace(0.0, 2.0 * np.pi, n_lon + 1)[:-1]
+    dirs = np.stack([np.sin(th)[:, None] * np.cos(ph)[None, :], np.cos(th)[:, None] * np.ones_like(ph)[None, :],
+                     np.sin(th)[:, None] * np.sin(ph)[None, :]], axis=-1).reshape(-1, 3)
+    vid = np.arange((n_lat + 1) * n_lon).reshape(n_lat + 1, n_lon)
+    tris = []
+    for i in range(n_lat):
+        for j in range(n_lon):
+            a, b, c, d = vid[i, j], vid[i, (j + 1) % n_lon], vid[i + 1, (j + 1) % n_lon], vid[i + 1, j]
+            if i != 0:
+                tris.append((a, b, c))
+            if i != n_lat - 1:
+                tris.append((a, c, d))
+    tris = _orient(dirs, np.array(tris, dtype=np.int64), lambda p: p.mean(axis=1))
+    return Mesh(dirs * radius, dirs, tris)
+
+
+def quad_grid(nx, ny, size=(2.0, 2.0), jitter=0.0, seed=0, normal_sign=1.0):
+    """An nx x ny grid of quads in the z = 0 plane, centred on the origin, `size` wide and high; interior grid points moved
+    by up to `jitter` of a cell (shared by the neighbouring quads: the mesh stays closed).  Triangles face -z (towards a viewer
+    on the -z side looking along +z) with normal_sign 1, +z with -1; vertex normals (0, 0, -normal_sign)."""
+    xs = (np.arange(nx + 1) / nx - 0.5) * size[0]
+    ys = (np.arange(ny + 1) / ny - 0.5) * size[1]
+    p = np.zeros((ny + 1, nx + 1, 3))
+    p[..., 0], p[..., 1] = xs[None, :], ys[:, None]
+    if jitter:
+        rng = np.random.default_rng(seed)
+        d = rng.uniform(-jitter, jitter, (ny - 1, nx - 1, 2))
+        p[1:-1, 1:-1, 0] += d[..., 0] * size[0] / nx
+        p[1:-1, 1:-1, 1] += d[..., 1] * size[1] / ny
+    vid = np.arange((ny + 1) * (nx + 1)).reshape(ny + 1, nx + 1)
+    a, b, c, d = vid[:-1, :-1], vid[:-1, 1:], vid[1:, 1:], vid[1:, :-1]
+    tris = np.stack([np.stack([a, b, c], -1), np.stack([a, c, d], -1)], axis=2).reshape(-1, 3)
+    face = np.array([0.0, 0.0, -float(normal_sign)])
+    tris = _orient(p.reshape(-1, 3), tris, lambda q: np.broadcast_to(face, (len(q), 3)))
+    return Mesh(p.reshape(-1, 3), np.broadcast_to(face, (len(p.reshape(-1, 3)), 3)), tris)
+
+
+class MeshScene:
+    """Draws over shared buffers: add(mesh, model, albedo, emission, roughness, metallic) appends a mesh (or draws one added
+    before again: instance=index) and one pbr_draw; arrays() -> (vertices, indices, draws), the input of pbr_gbuffer_raster."""
+
+    def __init__(self):
+        self._verts, self._idx, self._draws, self._ranges = [], [], [], []
+        self._nv = self._ni = 0
+
+    def add_mesh(self, mesh):
+        self._ranges.append((self._ni, len(mesh.indices), self._nv))
+        self._verts.append(mesh.vertices)
+        self._idx.append(mesh.indices)
+        self._nv += len(mesh.vertices)
+        self._ni += len(mesh.indices)
+        return len(self._ranges) - 1
+
+    def add(self, mesh, model, albedo=(1.0, 1.0, 1.0), emission=0.0, roughness=0.5, metallic=0.0):
+        k = mesh if isinstance(mesh, int) else self.add_mesh(mesh)
+        first, count, base = self._ranges[k]
+        d = np.zeros((), dtype=DRAW_DTYPE)
+        d["Model"] = np.asarray(model, dtype=f32).reshape(16)
+        d["InvModel"] = inverse(np.asarray(model, dtype=f32).reshape(4, 4)).reshape(16)
+        d["Albedo"], d["Emission"], d["Roughness"], d["Metallic"] = albedo, emission, roughness, metallic
+        d["first_index"], d["index_count"], d["base_vertex"] = first, count, base
+        self._draws.append(d)
+        return k
+
+    def arrays(self):
+        return (np.concatenate(self._verts) if self._verts else np.zeros(0, VERTEX_DTYPE),
+                np.concatenate(self._idx).astype(np.uint32) if self._idx else np.zeros(0, np.uint32),
+                np.array(self._draws, dtype=DRAW_DTYPE))
+
+
+def reference_models(fx):
+    """The constant-material models of the reference's scene (Asset/Scene/main.json) from the fixture written by
+    tests/golden/make_sphere_grid.py (fx: the loaded npz): one shared mesh (sphere_Mesh_data.bin) and one draw per model, in file
+    order.  Returns ((vertices, indices, draws), names)."""
+    verts = np.zeros(len(fx["vertices"]), dtype=VERTEX_DTYPE)
+    verts.view(np.float32).reshape(-1, 14)[:] = fx["vertices"]
+    ms = MeshScene()
+    mesh = Mesh(verts["position"], verts["normal"], fx["indices"])
+    mesh.vertices = verts
+    k = ms.add_mesh(mesh)
+    for world, mat in zip(fx["world"], fx["material"]):
+        ms.add(k, world, albedo=tuple(mat[:3]), emission=mat[3], roughness=mat[4], metallic=mat[5])
+    return ms.arrays(), [str(n) for n in fx["name"]]

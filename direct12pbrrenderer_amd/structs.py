@@ -93,6 +93,32 @@ class HaloPeer(C.Structure):
     _fields_ = [("rank", C.c_int32), ("send", C.c_uint32 * 4), ("recv", C.c_uint32 * 4)]
 
 
+class Vertex(C.Structure):
+    """pbr_vertex: VSInput_P3F_N3F_T2F_T2F, DeferredRendering/Shader/global.hlsli:59-66 (56 B)."""
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3), ("tangent", C.c_float * 3), ("color", C.c_float * 3),
+                ("uv", C.c_float * 2)]
+
+
+class Draw(C.Structure):
+    """pbr_draw: ConstantBufferInstance (gbuffer.hlsl:33-48) without the Use*Map flags, plus the draw's index range (164 B)."""
+    _fields_ = [("Model", C.c_float * 16), ("InvModel", C.c_float * 16), ("Albedo", C.c_float * 3), ("Emission", C.c_float),
+                ("Roughness", C.c_float), ("Metallic", C.c_float), ("first_index", C.c_uint32), ("index_count", C.c_uint32),
+                ("base_vertex", C.c_int32)]
+
+
+assert C.sizeof(Vertex) == 56 and C.sizeof(Draw) == 164
+# the same records as numpy arrays (device uploads)
+VERTEX_DTYPE = np.dtype([("position", np.float32, 3), ("normal", np.float32, 3), ("tangent", np.float32, 3),
+                         ("color", np.float32, 3), ("uv", np.float32, 2)])
+DRAW_DTYPE = np.dtype([("Model", np.float32, 16), ("InvModel", np.float32, 16), ("Albedo", np.float32, 3), ("Emission", np.float32),
+                       ("Roughness", np.float32), ("Metallic", np.float32), ("first_index", np.uint32), ("index_count", np.uint32),
+                       ("base_vertex", np.int32)])
+assert VERTEX_DTYPE.itemsize == 56 and DRAW_DTYPE.itemsize == 164
+RASTER_MAX_DRAWS = 65536                              # PBR_RASTER_MAX_DRAWS
+RASTER_MAX_TRIANGLES = 1 << 22                        # PBR_RASTER_MAX_TRIANGLES
+RASTER_MAX_SIZE = 8192                                # PBR_RASTER_MAX_SIZE
+
+
 class CubeF32(C.Structure):
     _fields_ = [("data", C.c_void_p), ("size", C.c_uint32), ("mips", C.c_uint32)]
 

@@ -283,6 +283,64 @@ pbr_status pbr_skybox(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, c
 pbr_status pbr_gbuffer_encode(pbr_ctx* ctx, const float* m0, const float* m1, const float* m2,
                               uint32_t w, uint32_t h, uint32_t pitch, uint32_t* A, uint32_t* B, uint32_t* C);
 
+/* ---- G-buffer rasterization (new): triangle meshes with constant per-draw materials -> the five G-buffer planes ---------- */
+/* VSInput_P3F_N3F_T2F_T2F (DeferredRendering/Shader/global.hlsli:59-66), 56 B: the reference's vertex buffers pass through
+ * unchanged.  The raster reads position and normal only. */
+typedef struct pbr_vertex {
+    float position[3];
+    float normal[3];
+    float tangent[3];
+    float color[3];
+    float uv[2];
+} pbr_vertex;
+/* ConstantBufferInstance (gbuffer.hlsl:33-48) without the Use*Map flags (every draw takes the constant-material branches),
+ * plus the draw's index range: triangles are indices[first_index + 3 i .. + 2] + base_vertex, i < index_count / 3.
+ * Model / InvModel row-major, mul(M, v) = M v (as pbr_global).  164 B. */
+typedef struct pbr_draw {
+    float Model[16];
+    float InvModel[16];
+    float Albedo[3];               /* as authored (gamma space): decode_gamma is applied */
+    float Emission;
+    float Roughness;
+    float Metallic;
+    uint32_t first_index;
+    uint32_t index_count;
+    int32_t  base_vertex;
+} pbr_draw;
+#define PBR_RASTER_MAX_DRAWS     65536u
+#define PBR_RASTER_MAX_TRIANGLES (1u << 22)
+#define PBR_RASTER_MAX_SIZE      8192u   /* full_w, full_h */
+/* Scratch of pbr_gbuffer_raster for a w x h tile and n_triangles triangles: the recommended size (per-bin triangle lists for
+ * about 8 bins per triangle), and the minimum.  Any size from the minimum up gives the same bits.  Bins take list space in raster
+ * order while their list fits (and holds <= 2048 triangles); a bin without a list walks EVERY triangle record: its cost grows with
+ * bins x triangles.  The minimum holds no lists at all — every bin walks every triangle — and is meant for tests and small scenes,
+ * not for large ones (a 4K tile of 4 M triangles would read 32 400 x 4 M records). */
+size_t pbr_gbuffer_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
+size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
+/* GBufferPass::Execute + DrawModel (DeferredPipeline.cpp:138-185) for constant-material draws: gbuffer.hlsl's vertex shader
+ * (position_ws = Model (p, 1), normal_ws = transpose(InvModel) (n, 0), clip = Projection (View position_ws); g->View and
+ * g->Projection), DefaultOpaque's fixed-function state and ps_main's Use*Map == false branches (AO = 0).  Draws run in array order.
+ *   Clears: A = B = C = 0, depth = 1, stencil = 0.  Viewport (0, 0, full_w, full_h), depth range [0, 1].
+ *   Clipping: near plane (z >= 0) in clip space; x / y only outside a guard band of 128 w.  Vertices snap to 1/256 pixel
+ *   (round to nearest even).  Coverage: exact integer edge functions at pixel centres, top-left rule; back faces (counter-
+ *   clockwise in y-down screen space) and zero-area triangles are dropped.  Depth: z / w linear in screen space, clamped to [0, 1],
+ *   test LESS with write; stencil counts the depth-passing fragments (INCR_SAT).  A / B / C: the first fragment in draw order
+ *   that reaches the pixel's nearest depth; its normal interpolated perspective-correctly, encoded as pbr_gbuffer_encode.
+ * tile: the planes hold global pixels (x0 + x, y0 + y) of the full_w x full_h frame, w x h of them at row pitch `pitch` pixels; a
+ * tile is bit-identical to the same region of the whole frame, for every scratch size.
+ * vertices / indices / draws: DEVICE arrays of n_vertices / n_indices / n_draws.  max_triangles: the triangles the draws hold
+ * (sum of index_count / 3), which the scratch is sized for; triangles past it are not drawn.  Guard on device data: a draw
+ * whose range passes n_indices, or a triangle with an index + base_vertex outside [0, n_vertices), is dropped.
+ * Limits (PBR_ERR_INVALID, nothing enqueued): n_draws <= PBR_RASTER_MAX_DRAWS, max_triangles <= PBR_RASTER_MAX_TRIANGLES,
+ * full_w, full_h <= PBR_RASTER_MAX_SIZE; null pointers, zero counts, a tile outside its frame, pitch < w, scratch below
+ * pbr_gbuffer_raster_min_scratch_bytes(w, h, max_triangles), buffers not 4-byte (scratch: 16-byte) aligned are refused.
+ * Asynchronous: six launches on the context's stream, no host synchronisation, no allocation. */
+pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                              void* scratch, size_t scratch_bytes);
+
 /* bloom_prefilter.hlsl:17-60 (DeferredPipeline.cpp:411-427): hdr (w x h) -> out (w>>1 x h>>1). */
 pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h,
                                uint32_t pitch, pbr_half* out, float threshold, float knee);

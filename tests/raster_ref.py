@@ -1,0 +1,203 @@
+"""numpy restatement of pbr_gbuffer_raster (include/pbr_hip.h, direct12pbrrenderer_amd/csrc/gbuffer_raster.hip).
+
+The contract, step by step, in the kernel's operation order: the vertex stage in float32 (sums left to right, no fused
+multiply-add), near / guard-band clipping in clip space, the viewport transform and the 1/256-pixel snap (round to nearest
+even), exact integer edge functions with the top-left rule, z / w interpolated in float64 and rounded once to float32,
+depth LESS, stencil INCR_SAT, and the winner's perspective-correct normal.  The planes are encoded by the oracle's
+gbuffer_encode (oracle/pbr_oracle.cpp), the CPU statement of gbuffer.hlsl::ps_main's outputs.
+
+An exact match with this file shows that two implementations of one reading agree; the GPU tests also check the contract's
+properties against independent truths (tests/test_gpu_raster.py)."""
+import numpy as np
+
+f32, f64 = np.float32, np.float64
+GUARD = f32(128.0)
+
+
+def _row4(m, x, y, z, w):
+    return ((m[0] * x + m[1] * y) + m[2] * z) + m[3] * w
+
+
+def vertex_stage(g, draw, pos, nrm):
+    """gbuffer.hlsl:71-86 on float32 [k, 3] positions / normals -> clip [k, 4], normal_ws [k, 3]."""
+    M = np.asarray(draw["Model"], dtype=f32).reshape(16)
+    IM = np.asarray(draw["InvModel"], dtype=f32).reshape(16)
+    V = np.array(g.View[:], dtype=f32)
+    P = np.array(g.Projection[:], dtype=f32)
+    x, y, z = (np.ascontiguousarray(pos[:, i], dtype=f32) for i in range(3))
+    pw = [_row4(M[4 * r:4 * r + 4], x, y, z, f32(1.0)) for r in range(4)]
+    pv = [_row4(V[4 * r:4 * r + 4], *pw) for r in range(4)]
+    clip = np.stack([np.broadcast_to(_row4(P[4 * r:4 * r + 4], *pv), x.shape) for r in range(4)], axis=1).astype(f32)
+    nx, ny, nz = (np.ascontiguousarray(nrm[:, i], dtype=f32) for i in range(3))
+    nw = np.stack([((IM[i] * nx + IM[4 + i] * ny) + IM[8 + i] * nz) + IM[12 + i] * f32(0.0) for i in range(3)], axis=1).astype(f32)
+    return clip, nw
+
+
+def _plane(v, pl):
+    x, y, z, w = v
+    if pl == 0:
+        return z
+    if pl == 1:
+        return x + GUARD * w
+    if pl == 2:
+        return GUARD * w - x
+    if pl == 3:
+        return y + GUARD * w
+    return GUARD * w - y
+
+
+def clip_polygon(cv):
+    """Sutherland-Hodgman against the near plane, then the guard band's four planes (a plane no vertex is outside of is
+    skipped); a new vertex goes from the inside endpoint of its edge towards the outside one."""
+    poly = [tuple(f32(a) for a in v) for v in cv]
+    for pl in range(5):
+        if len(poly) < 3:
+            break
+        if all(_plane(v, pl) >= 0 for v in poly):
+            continue
+        out = []
+        n = len(poly)
+        for i in range(n):
+            a, b = poly[i], poly[(i + 1) % n]
+            da, db = _plane(a, pl), _plane(b, pl)
+            ia, ib = bool(da >= 0), bool(db >= 0)
+            if ia:
+                out.append(a)
+            if ia != ib:
+                vin, vout, din, dout = (a, b, da, db) if ia else (b, a, db, da)
+                s = din / (din - dout)
+                out.append(tuple(vin[j] + (vout[j] - vin[j]) * s for j in range(4)))
+        poly = out if len(out) <= 8 else []   # more than MAX_POLY vertices (rounding near a plane): dropped
+    return poly
+
+
+def snap_record(cv, half_w, half_h, tile):
+    """clip-space triangle [3, 4] -> (X, Y, Z, (px0, py0, px1, py1)) of its clipped, snapped polygon, or None."""
+    poly = clip_polygon(cv)
+    if len(poly) < 3:
+        return None
+    X, Y, Z = [], [], []
+    for v in poly:
+        xn, yn = v[0] / v[3], v[1] / v[3]
+        if not (v[3] > 0 and abs(xn) <= f32(2.0) * GUARD and abs(yn) <= f32(2.0) * GUARD):
+            return None
+        X.append(int(np.rint(((xn + f32(1.0)) * half_w) * f32(256.0))))
+        Y.append(int(np.rint(((f32(1.0) - yn) * half_h) * f32(256.0))))
+        Z.append(f32(v[2] / v[3]))
+    n = len(X)
+    if not any((X[k] - X[0]) * (Y[k + 1] - Y[0]) - (Y[k] - Y[0]) * (X[k + 1] - X[0]) > 0 for k in range(1, n - 1)):
+        return None
+    px0 = max(-((128 - min(X)) >> 8), tile.x0)
+    px1 = min((max(X) - 128) >> 8, tile.x0 + tile.w - 1)
+    py0 = max(-((128 - min(Y)) >> 8), tile.y0)
+    py1 = min((max(Y) - 128) >> 8, tile.y0 + tile.h - 1)
+    if px0 > px1 or py0 > py1:
+        return None
+    return X, Y, Z, (px0, py0, px1, py1)
+
+
+def setup(g, tile, vertices, indices, draws, max_triangles=None):
+    """Per triangle id (draw order): the raster record (or None) and the resolve record (c[9], n[9], draw)."""
+    half_w, half_h = f32(0.5) * f32(tile.full_w), f32(0.5) * f32(tile.full_h)
+    n_idx, n_vtx = len(indices), len(vertices)
+    recs, cs, ns, ds = [], [], [], []
+    with np.errstate(all="ignore"):
+        for di, d in enumerate(draws):
+            cnt = int(d["index_count"]) // 3
+            first = int(d["first_index"])
+            cs.append(np.zeros((cnt, 9), f32))
+            ns.append(np.zeros((cnt, 9), f32))
+            ds.append(np.full(cnt, di, np.int64))
+            if cnt == 0:
+                continue
+            if first + int(d["index_count"]) > n_idx:
+                recs += [None] * cnt
+                continue
+            idx = indices[first:first + 3 * cnt].astype(np.int64) + int(d["base_vertex"])
+            valid = ((idx >= 0) & (idx < n_vtx)).reshape(cnt, 3).all(axis=1)
+            safe = np.clip(idx, 0, n_vtx - 1)
+            clip, nw = vertex_stage(g, d, vertices["position"][safe], vertices["normal"][safe])
+            clip, nw = clip.reshape(cnt, 3, 4), nw.reshape(cnt, 9)
+            sx = (clip[..., 0] + clip[..., 3]) * half_w
+            sy = (clip[..., 3] - clip[..., 1]) * half_h
+            sw = clip[..., 3]
+            c = cs[-1]
+            for i in range(3):
+                j, k = (i + 1) % 3, (i + 2) % 3
+                c[:, 3 * i + 0] = sy[:, j] * sw[:, k] - sw[:, j] * sy[:, k]
+                c[:, 3 * i + 1] = sw[:, j] * sx[:, k] - sx[:, j] * sw[:, k]
+                c[:, 3 * i + 2] = sx[:, j] * sy[:, k] - sy[:, j] * sx[:, k]
+            c[~valid] = 0
+            ns[-1][valid] = nw[valid]
+            recs += [snap_record(clip[t], half_w, half_h, tile) if valid[t] else None for t in range(cnt)]
+    total = len(recs) if max_triangles is None else min(len(recs), int(max_triangles))
+    cat = (lambda a: np.concatenate(a)[:total]) if cs else (lambda a: np.zeros((0, 9)))
+    return recs[:total], cat(cs), cat(ns), np.concatenate(ds)[:total] if ds else np.zeros(0, np.int64)
+
+
+def _edge(xa, ya, xb, yb, PX, PY):
+    return (xb - xa) * (PY - ya) - (yb - ya) * (PX - xa)
+
+
+def _bias(xa, ya, xb, yb):
+    dx, dy = xb - xa, yb - ya
+    return 0 if (dy < 0 or (dy == 0 and dx > 0)) else 1
+
+
+def rasterize(recs, tile):
+    """Depth, stencil and the winning triangle id (-1: none) of every pixel of the tile, triangles in id order."""
+    h, w = tile.h, tile.w
+    zbuf = np.ones((h, w), f32)
+    sten = np.zeros((h, w), np.int32)
+    win = np.full((h, w), -1, np.int64)
+    for t, r in enumerate(recs):
+        if r is None:
+            continue
+        X, Y, Z, (px0, py0, px1, py1) = r
+        PX = (np.arange(px0, px1 + 1, dtype=np.int64) * 256 + 128)[None, :]
+        PY = (np.arange(py0, py1 + 1, dtype=np.int64) * 256 + 128)[:, None]
+        sl = (slice(py0 - tile.y0, py1 - tile.y0 + 1), slice(px0 - tile.x0, px1 - tile.x0 + 1))
+        zb, st, wn = zbuf[sl], sten[sl], win[sl]
+        for k in range(1, len(X) - 1):
+            X0, Y0, X1, Y1, X2, Y2 = X[0], Y[0], X[k], Y[k], X[k + 1], Y[k + 1]
+            area = (X1 - X0) * (Y2 - Y0) - (Y1 - Y0) * (X2 - X0)
+            if area <= 0:
+                continue
+            w0, w1, w2 = _edge(X1, Y1, X2, Y2, PX, PY), _edge(X2, Y2, X0, Y0, PX, PY), _edge(X0, Y0, X1, Y1, PX, PY)
+            cov = (w0 >= _bias(X1, Y1, X2, Y2)) & (w1 >= _bias(X2, Y2, X0, Y0)) & (w2 >= _bias(X0, Y0, X1, Y1))
+            z0 = f64(Z[0])
+            zd = z0 + (w1.astype(f64) * (f64(Z[k]) - z0) + w2.astype(f64) * (f64(Z[k + 1]) - z0)) / f64(area)
+            z = zd.astype(f32)
+            z = np.where(z > 0, np.where(z < 1, z, f32(1.0)), f32(0.0)).astype(f32)
+            upd = cov & (z < zb)
+            zb[upd] = z[upd]
+            wn[upd] = t
+            st[upd] = np.minimum(st[upd] + 1, 255)
+    return zbuf, sten, win
+
+
+def raster(g, tile, vertices, indices, draws, orc, max_triangles=None):
+    """The five planes pbr_gbuffer_raster writes for this tile: dict A, B, C (uint32), depth (float32), stencil (uint8)."""
+    recs, c, n, dr = setup(g, tile, vertices, indices, draws, max_triangles)
+    zbuf, sten, win = rasterize(recs, tile)
+    h, w = tile.h, tile.w
+    m0, m1, m2 = (np.zeros((h, w, 4), f32) for _ in range(3))
+    ys, xs = np.nonzero(win >= 0)
+    if len(ys):
+        t = win[ys, xs]
+        cc, nn, d = c[t], n[t], draws[dr[t]]
+        fx = (xs + tile.x0).astype(f32) + f32(0.5)
+        fy = (ys + tile.y0).astype(f32) + f32(0.5)
+        with np.errstate(all="ignore"):
+            lam = [(cc[:, 3 * i] * fx + cc[:, 3 * i + 1] * fy) + cc[:, 3 * i + 2] for i in range(3)]
+            inv = f32(1.0) / ((lam[0] + lam[1]) + lam[2])
+            nrm = [((lam[0] * nn[:, j] + lam[1] * nn[:, 3 + j]) + lam[2] * nn[:, 6 + j]) * inv for j in range(3)]
+        alb = np.asarray(d["Albedo"], dtype=f32).reshape(-1, 3)
+        m0[ys, xs] = np.stack([alb[:, 0], alb[:, 1], alb[:, 2], d["Emission"].astype(f32)], axis=1)
+        m1[ys, xs] = np.stack([nrm[0], nrm[1], nrm[2], d["Roughness"].astype(f32)], axis=1)
+        m2[ys, xs, 0] = d["Metallic"].astype(f32)
+    A, B, C = orc.gbuffer_encode(m0, m1, m2)
+    off = win < 0
+    for p in (A, B, C):
+        p[off] = 0
+    return {"A": A, "B": B, "C": C, "depth": zbuf, "stencil": sten.astype(np.uint8)}
