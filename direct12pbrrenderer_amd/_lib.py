@@ -6,7 +6,7 @@ symbol cannot be resolved this module raises — it never substitutes another im
 import ctypes as C
 import os
 
-from .structs import CubeF32, GBuffer, Global, HaloPeer, Tile, View
+from .structs import CubeF32, GBuffer, Global, HaloPeer, Texture2D, Tile, View
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB", os.path.join(_HERE, "libpbr_hip.so"))   # override = experiments only
@@ -54,6 +54,10 @@ SIGNATURES = {
     "pbr_gbuffer_raster_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
                                   _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz]),
+    "pbr_gbuffer_raster_textured_scratch_bytes": (_sz, [_u32, _u32, _u32]),
+    "pbr_gbuffer_raster_textured_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
+    "pbr_gbuffer_raster_textured": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
+                                           _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, C.POINTER(Texture2D), _u32]),
     "pbr_bloom_prefilter": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _f32, _f32]),
     "pbr_blur_h": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),
     "pbr_blur_v": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),

@@ -11,9 +11,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .structs import (BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
+from .structs import (Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, DRAW_DTYPE, VERTEX_DTYPE, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, cube_texels, env_padded_texels)
+                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, TEX_FORMATS, VERTEX_DTYPE, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, cube_texels, env_padded_texels)
 
 
 class PbrError(RuntimeError):
@@ -135,7 +135,7 @@ class PbrContext:
 
     def upload(self, arr):
         arr = np.ascontiguousarray(arr)
-        if arr.dtype in (LIGHT_DTYPE, CLUSTER_DTYPE, VERTEX_DTYPE, DRAW_DTYPE):
+        if arr.dtype in (LIGHT_DTYPE, CLUSTER_DTYPE, VERTEX_DTYPE, DRAW_DTYPE, DRAW_MAPS_DTYPE):
             arr = arr.view(np.uint8)
         if arr.dtype == np.uint32:
             return torch.from_numpy(arr.view(np.int32)).to(self.torch_device)
@@ -264,6 +264,36 @@ class PbrContext:
         self._check(self.lib.pbr_gbuffer_raster(self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices),
                                                 int(n_indices), _ptr(draws), int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc),
                                                 _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch), nbytes))
+
+    def textured_raster_scratch_bytes(self, w, h, n_triangles, minimum=False):
+        """pbr_gbuffer_raster_textured_scratch_bytes (recommended) or, minimum=True, its _min_scratch_bytes for a w x h tile"""
+        fn = self.lib.pbr_gbuffer_raster_textured_min_scratch_bytes if minimum else self.lib.pbr_gbuffer_raster_textured_scratch_bytes
+        return int(fn(int(w), int(h), int(n_triangles)))
+
+    def alloc_textured_raster_scratch(self, w, h, n_triangles, minimum=False, extra=0):
+        """device scratch for gbuffer_raster_textured"""
+        return self.empty((self.textured_raster_scratch_bytes(w, h, n_triangles, minimum) + int(extra),), torch.uint8)
+
+    def upload_texture(self, chain, width, height, mip_levels, fmt):
+        """A texture's mip chain (host bytes in the reference's layout: scene.mip_chain / pack_chain) -> (device tensor,
+        structs.Texture2D describing it).  Keep the tensor alive while the descriptor is in use."""
+        if int(fmt) not in TEX_FORMATS:
+            raise PbrError(f"unknown texture format {fmt}")
+        dev = self.upload(np.ascontiguousarray(chain).view(np.uint8).reshape(-1))
+        return dev, Texture2D(dev.data_ptr(), int(width), int(height), int(mip_levels), int(fmt))
+
+    def gbuffer_raster_textured(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
+                                A, B, Cc, depth, stencil, pitch, scratch, maps, textures, scratch_bytes=None):
+        """pbr_gbuffer_raster_textured: gbuffer_raster plus maps (device DRAW_MAPS_DTYPE records, one per draw) and textures (a
+        sequence of structs.Texture2D, from upload_texture; host side, at most RASTER_MAX_TEXTURES).  Scratch from
+        alloc_textured_raster_scratch."""
+        textures = list(textures)
+        table = (Texture2D * max(len(textures), 1))(*textures)
+        nbytes = scratch.numel() * scratch.element_size() if scratch_bytes is None else int(scratch_bytes)
+        self._check(self.lib.pbr_gbuffer_raster_textured(
+            self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices), int(n_indices), _ptr(draws),
+            int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc), _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch),
+            nbytes, _ptr(maps), table if textures else None, len(textures)))
 
     def bloom_prefilter(self, hdr, w, h, pitch, out, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE):
         self._check(self.lib.pbr_bloom_prefilter(self.h, _ptr(hdr), w, h, pitch, _ptr(out), threshold, knee))

@@ -19,6 +19,12 @@
 // triangle's perspective-correct barycentrics from its 2D homogeneous edge planes (Olano & Greer 1997), so a clipped polygon
 // resolves against the triangle it came from.  Built with -ffp-contract=off: tests/raster_ref.py restates every step in the
 // same operation order.
+//
+// Textured draws (pbr_gbuffer_raster_textured) take the same six launches with a non-empty `Tex` pack on k_rs_setup and
+// k_rs_raster (the empty pack is the constant-material kernel): setup also writes the uv and tangent_ws of the three vertices
+// (RsTexAttr) and drops draws with a bad map index; the resolve adds the perspective-correct uv / tangent, the quad's LOD, up to
+// five trilinear samples (SamplerLinearWrap as pinned in pbr_hip.h) and the normal-map frame, before the same encode.
+// tests/raster_tex_ref.py restates it.
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
 
@@ -27,6 +33,7 @@ using namespace pbr;
 namespace {
 
 #include "gbuffer_encode.hpp"
+#include "texel_decode.hpp"
 
 constexpr uint32_t BIN = 16;               // bin edge in pixels: 256 lanes, one per pixel
 constexpr uint32_t LIST_CAP = 2048;        // longest bin list sorted in LDS
@@ -51,14 +58,21 @@ struct RsAttr {
     uint32_t pad;
 };
 static_assert(sizeof(RsAttr) == 80, "resolve record layout");
+// textured resolve record: uv of vertex i = uv[2i..2i+1], tangent_ws of vertex i = t[3i..3i+2]
+struct RsTexAttr {
+    float uv[6];
+    float t[9];
+    uint32_t pad;
+};
+static_assert(sizeof(RsTexAttr) == 64, "textured resolve record layout");
 
-// scratch layout (byte offsets, 256-aligned); everything up to `pool` is the minimum
+// scratch layout (byte offsets, 256-aligned); everything up to `pool` is the minimum.  The textured layout adds `tex`.
 struct Layout {
-    size_t draw_base, count, cursor, offset, tris, attrs, pool;
+    size_t draw_base, count, cursor, offset, tris, attrs, tex, pool;
     uint32_t nbx, nby;
 };
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline Layout layout(uint32_t w, uint32_t h, uint32_t n_triangles) {
+inline Layout layout(uint32_t w, uint32_t h, uint32_t n_triangles, bool textured = false) {
     Layout L;
     L.nbx = (w + BIN - 1) / BIN;
     L.nby = (h + BIN - 1) / BIN;
@@ -69,7 +83,8 @@ inline Layout layout(uint32_t w, uint32_t h, uint32_t n_triangles) {
     L.offset = L.cursor + align256(bins * 4);
     L.tris = L.offset + align256(bins * 4);
     L.attrs = L.tris + align256((size_t)n_triangles * sizeof(RsTri));
-    L.pool = L.attrs + align256((size_t)n_triangles * sizeof(RsAttr));
+    L.tex = L.attrs + align256((size_t)n_triangles * sizeof(RsAttr));
+    L.pool = L.tex + (textured ? align256((size_t)n_triangles * sizeof(RsTexAttr)) : 0);
     return L;
 }
 
@@ -82,6 +97,21 @@ struct RsParams {
     uint32_t pitch;
     uint32_t pool_cap;                     // entries of the list pool
 };
+
+// the textured kernels' extra arguments
+struct RsSetupTex {
+    const pbr_draw_maps* maps;
+    RsTexAttr* tex;
+    uint32_t n_tex;
+};
+struct RsRasterTex {
+    const pbr_draw_maps* maps;
+    const RsTexAttr* tex;
+    uint32_t n_tex;
+    pbr_texture2d table[PBR_RASTER_MAX_TEXTURES];
+};
+// the one element of a non-empty `Tex` pack
+template <typename T> __device__ __forceinline__ const T& only(const T& t) { return t; }
 
 struct ClipV { float x, y, z, w; };
 
@@ -146,10 +176,13 @@ __global__ __launch_bounds__(1024) void k_rs_prep(const pbr_draw* __restrict__ d
     }
 }
 
+// Tex: empty (constant materials) or RsSetupTex (textured: the uv / tangent record, and the map-index guard)
+template <typename... Tex>
 __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* __restrict__ vtx, const uint32_t* __restrict__ idx,
                                                   const pbr_draw* __restrict__ draws, const uint32_t* __restrict__ draw_base,
                                                   const uint32_t* __restrict__ hdr, RsTri* __restrict__ tris,
-                                                  RsAttr* __restrict__ attrs, uint32_t* __restrict__ bin_count) {
+                                                  RsAttr* __restrict__ attrs, uint32_t* __restrict__ bin_count, Tex... tex) {
+    constexpr bool TEX = sizeof...(Tex) != 0;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= hdr[0]) return;
     uint32_t lo = 0, hi = p.n_draws - 1;        // the draw: the last d with draw_base[d] <= t
@@ -166,6 +199,12 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
     // guard (device data): a draw range past n_indices, or an index (+ base_vertex) outside [0, n_vertices): the triangle is dropped
     const uint64_t first = (uint64_t)d.first_index + 3ull * (t - draw_base[lo]);
     bool ok = (uint64_t)d.first_index + d.index_count <= p.n_indices;
+    if constexpr (TEX) {
+        // and a draw with a map index past the texture table
+        const RsSetupTex& tx = only(tex...);
+        const pbr_draw_maps m = tx.maps[lo];
+        for (const uint32_t k : {m.albedo, m.normal, m.roughness, m.metallic, m.ao}) ok = ok && (k == PBR_NO_MAP || k < tx.n_tex);
+    }
     int64_t vi[3] = {0, 0, 0};
     for (int k = 0; k < 3 && ok; k++) {
         vi[k] = (int64_t)idx[first + k] + d.base_vertex;
@@ -202,6 +241,25 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
         }
     }
     attrs[t] = at;
+    if constexpr (TEX) {
+        // gbuffer.hlsl:80-84: tangent_ws = transpose(InvModel) (t, 0) (the normal's rule), uv as given; computed after the resolve
+        // record is stored, so the two records are not live at once
+        RsTexAttr ta;
+        for (int i = 0; i < 6; i++) ta.uv[i] = 0.0f;
+        for (int i = 0; i < 9; i++) ta.t[i] = 0.0f;
+        ta.pad = 0;
+        if (ok) {
+            for (int k = 0; k < 3; k++) {
+                const pbr_vertex& v = vtx[vi[k]];
+                for (int i = 0; i < 3; i++)
+                    ta.t[3 * k + i] = ((d.InvModel[i] * v.tangent[0] + d.InvModel[4 + i] * v.tangent[1]) + d.InvModel[8 + i] * v.tangent[2]) +
+                                      d.InvModel[12 + i] * 0.0f;
+                ta.uv[2 * k] = v.uv[0];
+                ta.uv[2 * k + 1] = v.uv[1];
+            }
+        }
+        only(tex...).tex[t] = ta;
+    }
     if (ok) {
         // clip against the near plane and, outside the guard band, its four planes (Sutherland-Hodgman; a plane no vertex is
         // outside of is skipped).  A new vertex is computed from its edge's inside endpoint towards the outside one, so two
@@ -327,11 +385,87 @@ __device__ __forceinline__ int64_t edge_bias(int32_t xa, int32_t ya, int32_t xb,
     return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1;
 }
 
+// ---- the textured resolve's sampler (pbr_hip.h: SamplerLinearWrap as pinned there) ----
+// the texture table and both decode tables, staged in LDS by the block
+struct TexLds {
+    pbr_texture2d tex[PBR_RASTER_MAX_TEXTURES];
+    float dec[512];                        // [0, 256): kUnorm8, [256, 512): kSrgb8
+};
+__device__ __forceinline__ TexLds& tex_lds() {
+    __shared__ TexLds tl;
+    return tl;
+}
+// a texel coordinate's floor wrapped into [0, n) (non-negative modulo; fl is integral, so fmodf is exact)
+__device__ __forceinline__ uint32_t wrap_texel(float fl, uint32_t n) {
+    const float fn = (float)n;
+    float m = fmodf(fl, fn);
+    if (m < 0.0f) m += fn;
+    return m >= 0.0f && m < fn ? (uint32_t)m : 0u;   // (a non-finite coordinate reads texel 0)
+}
+__device__ __forceinline__ float tex_lerp(float a, float b, float f) { return f == 0.0f ? a : fmaf(b, f, a * (1.0f - f)); }
+// NC channels (.x, or .xyz) of texel i of a texture, decoded
+template <int NC>
+__device__ __forceinline__ void texel(const pbr_texture2d& t, const float* dec, size_t i, float* out) {
+    if (t.format == PBR_TEX_R8_UNORM) {
+        out[0] = dec[static_cast<const uint8_t*>(t.texels)[i]];
+        if (NC == 3) { out[1] = 0.0f; out[2] = 0.0f; }
+        return;
+    }
+    const uint32_t w = static_cast<const uint32_t*>(t.texels)[i];
+    const float* tab = t.format == PBR_TEX_B8G8R8A8_UNORM_SRGB ? dec + 256 : dec;
+    const uint32_t rs = t.format == PBR_TEX_R8G8B8A8_UNORM ? 0u : 16u;   // BGRA: red is byte 2, blue byte 0
+    out[0] = tab[(w >> rs) & 255u];
+    if (NC == 3) {
+        out[1] = tab[(w >> 8) & 255u];
+        out[2] = tab[(w >> (16u - rs)) & 255u];
+    }
+}
+// bilinear on level l (wrap addressing)
+template <int NC>
+__device__ __forceinline__ void bilinear(const pbr_texture2d& t, const float* dec, uint32_t l, float u, float v, float* out) {
+    size_t off = 0;
+    for (uint32_t i = 0; i < l; i++) off += (size_t)(t.width >> i) * (t.height >> i);
+    const uint32_t wl = t.width >> l, hl = t.height >> l;
+    const float x = u * (float)wl - 0.5f, y = v * (float)hl - 0.5f;
+    const float flx = floorf(x), fly = floorf(y);
+    const float fx = x - flx, fy = y - fly;
+    const uint32_t x0 = wrap_texel(flx, wl), y0 = wrap_texel(fly, hl);
+    const uint32_t x1 = x0 + 1u == wl ? 0u : x0 + 1u, y1 = y0 + 1u == hl ? 0u : y0 + 1u;
+    float c00[NC], c10[NC], c01[NC], c11[NC];
+    texel<NC>(t, dec, off + (size_t)y0 * wl + x0, c00);
+    texel<NC>(t, dec, off + (size_t)y0 * wl + x1, c10);
+    texel<NC>(t, dec, off + (size_t)y1 * wl + x0, c01);
+    texel<NC>(t, dec, off + (size_t)y1 * wl + x1, c11);
+    for (int c = 0; c < NC; c++) out[c] = tex_lerp(tex_lerp(c00[c], c10[c], fx), tex_lerp(c01[c], c11[c], fx), fy);
+}
+// Sample(SamplerLinearWrap, uv) with the quad's uv differences (ddx, ddy): LOD, then trilinear
+template <int NC>
+__device__ __forceinline__ void sample(const pbr_texture2d& t, const float* dec, float u, float v, float dxu, float dxv, float dyu,
+                                       float dyv, float* out) {
+    const float fw = (float)t.width, fh = (float)t.height;
+    const float ax = dxu * fw, ay = dxv * fh, bx = dyu * fw, by = dyv * fh;
+    const float rho = fmaxf(sqrtf(ax * ax + ay * ay), sqrtf(bx * bx + by * by));
+    float lam = rho > 0.0f ? (float)log2((double)rho) : 0.0f;            // 0 or NaN: 0
+    lam = fminf(fmaxf(lam, 0.0f), (float)(t.mip_levels - 1u));
+    const float fl = floorf(lam), f = lam - fl;
+    const uint32_t l = (uint32_t)fl;
+    bilinear<NC>(t, dec, l, u, v, out);
+    if (f != 0.0f) {                       // (a level with weight 0 does not contribute: tex_lerp)
+        float hi[NC];
+        bilinear<NC>(t, dec, min(l + 1u, t.mip_levels - 1u), u, v, hi);
+        for (int c = 0; c < NC; c++) out[c] = tex_lerp(out[c], hi[c], f);
+    }
+}
+
+// Tex: empty (constant materials) or RsRasterTex (textured: the resolve samples the draw's maps)
+template <typename... Tex>
 __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* __restrict__ draws, const uint32_t* __restrict__ hdr,
                                                    const RsTri* __restrict__ tris, const RsAttr* __restrict__ attrs,
                                                    const uint32_t* __restrict__ count, const uint32_t* __restrict__ offset,
                                                    const uint32_t* __restrict__ pool, uint32_t* __restrict__ A, uint32_t* __restrict__ B,
-                                                   uint32_t* __restrict__ C, float* __restrict__ depth, uint8_t* __restrict__ stencil) {
+                                                   uint32_t* __restrict__ C, float* __restrict__ depth, uint8_t* __restrict__ stencil,
+                                                   Tex... tex) {
+    constexpr bool TEX = sizeof...(Tex) != 0;
     __shared__ uint32_t list[LIST_CAP];
     const uint32_t tid = threadIdx.x;
     const uint32_t lx = blockIdx.x * BIN + (tid & (BIN - 1)), ly = blockIdx.y * BIN + tid / BIN;
@@ -365,6 +499,17 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
             }
         }
     };
+
+    if constexpr (TEX) {
+        // the texture table (a uniform loop: no per-lane index into the kernel arguments) and the decode tables into LDS
+        TexLds& tl = tex_lds();
+        const RsRasterTex& tx = only(tex...);
+        for (uint32_t i = 0; i < tx.n_tex; i++)
+            if (tid == 0) tl.tex[i] = tx.table[i];
+        tl.dec[tid] = kUnorm8[tid];
+        tl.dec[256u + tid] = kSrgb8[tid];
+        __syncthreads();
+    }
 
     const uint32_t b = blockIdx.y * p.nbx + blockIdx.x;
     const uint32_t cnt = count[b], off = offset[b];
@@ -419,10 +564,65 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
         const float l2 = (at.c[6] * fx + at.c[7] * fy) + at.c[8];
         const float inv = 1.0f / ((l0 + l1) + l2);
         // gbuffer.hlsl:99-146, the Use*Map == false branches: AO = 0 (the reference's value without an AO map)
-        const float4 a = make_float4(d.Albedo[0], d.Albedo[1], d.Albedo[2], d.Emission);
-        const float4 b = make_float4(((l0 * at.n[0] + l1 * at.n[3]) + l2 * at.n[6]) * inv, ((l0 * at.n[1] + l1 * at.n[4]) + l2 * at.n[7]) * inv,
-                                     ((l0 * at.n[2] + l1 * at.n[5]) + l2 * at.n[8]) * inv, d.Roughness);
-        const float4 c = make_float4(d.Metallic, 0.0f, 0.0f, 0.0f);
+        float4 a = make_float4(d.Albedo[0], d.Albedo[1], d.Albedo[2], d.Emission);
+        float4 b = make_float4(((l0 * at.n[0] + l1 * at.n[3]) + l2 * at.n[6]) * inv, ((l0 * at.n[1] + l1 * at.n[4]) + l2 * at.n[7]) * inv,
+                               ((l0 * at.n[2] + l1 * at.n[5]) + l2 * at.n[8]) * inv, d.Roughness);
+        float4 c = make_float4(d.Metallic, 0.0f, 0.0f, 0.0f);
+        if constexpr (TEX) {
+            const RsRasterTex& tx = only(tex...);
+            const pbr_draw_maps m = tx.maps[at.draw];
+            if ((m.albedo & m.normal & m.roughness & m.metallic & m.ao) != PBR_NO_MAP) {
+                // the Use*Map == true branches (gbuffer.hlsl:62-69,99-141)
+                const TexLds& tl = tex_lds();
+                const RsTexAttr& ta = tx.tex[win];
+                // perspective-correct uv at (fx, fy), from the triangle's planes
+                auto uv_at = [&](float x, float y, float& u, float& v) {
+                    const float k0 = (at.c[0] * x + at.c[1] * y) + at.c[2];
+                    const float k1 = (at.c[3] * x + at.c[4] * y) + at.c[5];
+                    const float k2 = (at.c[6] * x + at.c[7] * y) + at.c[8];
+                    const float r = 1.0f / ((k0 + k1) + k2);
+                    u = ((k0 * ta.uv[0] + k1 * ta.uv[2]) + k2 * ta.uv[4]) * r;
+                    v = ((k0 * ta.uv[1] + k1 * ta.uv[3]) + k2 * ta.uv[5]) * r;
+                };
+                float u, v, u00, v00, u10, v10, u01, v01;
+                uv_at(fx, fy, u, v);
+                // the LOD's differences: the quad (global pixels) around this pixel, this pixel's triangle
+                const float qx = (float)(gx & ~1u) + 0.5f, qy = (float)(gy & ~1u) + 0.5f;
+                uv_at(qx, qy, u00, v00);
+                uv_at(qx + 1.0f, qy, u10, v10);
+                uv_at(qx, qy + 1.0f, u01, v01);
+                const float dxu = u10 - u00, dxv = v10 - v00, dyu = u01 - u00, dyv = v01 - v00;
+                float s[3];
+                if (m.albedo != PBR_NO_MAP) {   // albedo = decode_gamma(sample.rgb): the encode applies decode_gamma
+                    sample<3>(tl.tex[m.albedo], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    a.x = s[0]; a.y = s[1]; a.z = s[2];
+                }
+                if (m.normal != PBR_NO_MAP) {   // sample_normal_texture; the encode's normalize is its normalize
+                    const V3 n = normalize3_exact(v3(b.x, b.y, b.z));
+                    const V3 tg = normalize3_exact(v3(((l0 * ta.t[0] + l1 * ta.t[3]) + l2 * ta.t[6]) * inv,
+                                                      ((l0 * ta.t[1] + l1 * ta.t[4]) + l2 * ta.t[7]) * inv,
+                                                      ((l0 * ta.t[2] + l1 * ta.t[5]) + l2 * ta.t[8]) * inv));
+                    const V3 bt = cross3(n, tg);
+                    sample<3>(tl.tex[m.normal], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    const float tx_ = s[0] * 2.0f - 1.0f, ty_ = s[1] * 2.0f - 1.0f, tz_ = s[2] * 2.0f - 1.0f;
+                    b.x = (tx_ * tg.x + ty_ * bt.x) + tz_ * n.x;
+                    b.y = (tx_ * tg.y + ty_ * bt.y) + tz_ * n.y;
+                    b.z = (tx_ * tg.z + ty_ * bt.z) + tz_ * n.z;
+                }
+                if (m.roughness != PBR_NO_MAP) {
+                    sample<1>(tl.tex[m.roughness], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    b.w = s[0];
+                }
+                if (m.metallic != PBR_NO_MAP) {
+                    sample<1>(tl.tex[m.metallic], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    c.x = s[0];
+                }
+                if (m.ao != PBR_NO_MAP) {
+                    sample<1>(tl.tex[m.ao], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    c.y = s[0];
+                }
+            }
+        }
         PBR_GBUFFER_ENCODE(a, b, c, pa, pb, pc)
         qa = pa; qb = pb; qc = pc;
     }
@@ -436,24 +636,11 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
-    return layout(w, h, n_triangles).pool;
-}
-
-size_t pbr_gbuffer_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
-    const Layout L = layout(w, h, n_triangles);
-    return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
-}
-
-pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                              void* scratch, size_t scratch_bytes) {
+// the checks and launches of both entry points; tx: null for pbr_gbuffer_raster, else the validated texture table
+pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_vertex* vertices, uint32_t n_vertices,
+                  const uint32_t* indices, uint32_t n_indices, const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                  uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch, void* scratch,
+                  size_t scratch_bytes, const RsRasterTex* tx) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, g && tile && vertices && indices && draws && A && B && C && depth && stencil && scratch,
                 "pbr_gbuffer_raster: null pointer");
@@ -467,8 +654,9 @@ pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile*
     PBR_REQUIRE(ctx, ((pbr::addr(vertices) | pbr::addr(indices) | pbr::addr(draws) | pbr::addr(A) | pbr::addr(B) | pbr::addr(C) |
                        pbr::addr(depth)) & 3u) == 0 && (pbr::addr(scratch) & 15u) == 0,
                 "pbr_gbuffer_raster: unaligned buffer");
-    const Layout L = layout(tile->w, tile->h, max_triangles);
-    PBR_REQUIRE(ctx, scratch_bytes >= L.pool, "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_min_scratch_bytes");
+    const Layout L = layout(tile->w, tile->h, max_triangles, tx != nullptr);
+    PBR_REQUIRE(ctx, scratch_bytes >= L.pool, tx ? "pbr_gbuffer_raster_textured: scratch below pbr_gbuffer_raster_textured_min_scratch_bytes"
+                                                : "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_min_scratch_bytes");
 
     RsParams p;
     for (int i = 0; i < 16; i++) { p.View[i] = g->View[i]; p.Projection[i] = g->Projection[i]; }
@@ -489,6 +677,7 @@ pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile*
     uint32_t* offset = reinterpret_cast<uint32_t*>(s + L.offset);
     RsTri* tris = reinterpret_cast<RsTri*>(s + L.tris);
     RsAttr* attrs = reinterpret_cast<RsAttr*>(s + L.attrs);
+    RsTexAttr* texattrs = reinterpret_cast<RsTexAttr*>(s + L.tex);
     uint32_t* pool = reinterpret_cast<uint32_t*>(s + L.pool);
     const uint32_t n_bins = L.nbx * L.nby;
     const uint32_t tri_blocks = (max_triangles + 255u) / 256u;
@@ -497,15 +686,99 @@ pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile*
     if (pbr_status st = pbr::launched(ctx, "k_rs_clear")) return st;
     hipLaunchKernelGGL(k_rs_prep, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr);
     if (pbr_status st = pbr::launched(ctx, "k_rs_prep")) return st;
-    hipLaunchKernelGGL(k_rs_setup, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, draw_base, hdr, tris, attrs, count);
+    if (tx) {
+        const RsSetupTex st{tx->maps, texattrs, tx->n_tex};
+        hipLaunchKernelGGL(k_rs_setup<RsSetupTex>, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, draw_base, hdr,
+                           tris, attrs, count, st);
+    } else {
+        hipLaunchKernelGGL(k_rs_setup<>, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, draw_base, hdr, tris,
+                           attrs, count);
+    }
     if (pbr_status st = pbr::launched(ctx, "k_rs_setup")) return st;
     hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(64), 0, ctx->stream, count, n_bins, p.pool_cap, offset);
     if (pbr_status st = pbr::launched(ctx, "k_rs_scan")) return st;
     hipLaunchKernelGGL(k_rs_fill, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, hdr, tris, offset, cursor, pool);
     if (pbr_status st = pbr::launched(ctx, "k_rs_fill")) return st;
-    hipLaunchKernelGGL(k_rs_raster, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs, count, offset, pool,
-                       A, B, C, depth, stencil);
+    if (tx) {
+        RsRasterTex rt = *tx;
+        rt.tex = texattrs;
+        hipLaunchKernelGGL(k_rs_raster<RsRasterTex>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs, count,
+                           offset, pool, A, B, C, depth, stencil, rt);
+    } else {
+        hipLaunchKernelGGL(k_rs_raster<>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs, count, offset, pool,
+                           A, B, C, depth, stencil);
+    }
     return pbr::launched(ctx, "k_rs_raster");
+}
+
+// floor(log2(min(w, h))) + 1: the levels of a full chain down to a 1-texel side
+uint32_t max_mip_levels(uint32_t w, uint32_t h) {
+    uint32_t m = min(w, h), n = 0;
+    while (m) { n++; m >>= 1; }
+    return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
+    return layout(w, h, n_triangles).pool;
+}
+
+size_t pbr_gbuffer_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
+    const Layout L = layout(w, h, n_triangles);
+    return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
+}
+
+size_t pbr_gbuffer_raster_textured_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
+    return layout(w, h, n_triangles, true).pool;
+}
+
+size_t pbr_gbuffer_raster_textured_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
+    const Layout L = layout(w, h, n_triangles, true);
+    return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
+}
+
+pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                              void* scratch, size_t scratch_bytes) {
+    return raster(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth, stencil,
+                  pitch, scratch, scratch_bytes, nullptr);
+}
+
+pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                       const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                                       const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                                       uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                                       void* scratch, size_t scratch_bytes,
+                                       const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, maps && (pbr::addr(maps) & 3u) == 0, "pbr_gbuffer_raster_textured: maps null or not 4-byte aligned");
+    PBR_REQUIRE(ctx, n_textures <= PBR_RASTER_MAX_TEXTURES && (textures || n_textures == 0),
+                "pbr_gbuffer_raster_textured: more textures than PBR_RASTER_MAX_TEXTURES, or a null texture table");
+    RsRasterTex tx;
+    tx.maps = maps;
+    tx.tex = nullptr;
+    tx.n_tex = n_textures;
+    for (uint32_t i = 0; i < PBR_RASTER_MAX_TEXTURES; i++) tx.table[i] = pbr_texture2d{nullptr, 0, 0, 0, 0};
+    for (uint32_t i = 0; i < n_textures; i++) {
+        const pbr_texture2d& t = textures[i];
+        const bool r8 = t.format == PBR_TEX_R8_UNORM;
+        PBR_REQUIRE(ctx, r8 || t.format == PBR_TEX_R8G8B8A8_UNORM || t.format == PBR_TEX_B8G8R8A8_UNORM ||
+                    t.format == PBR_TEX_B8G8R8A8_UNORM_SRGB, "pbr_gbuffer_raster_textured: unknown texture format");
+        PBR_REQUIRE(ctx, t.width && t.height && t.width <= PBR_TEX_MAX_SIZE && t.height <= PBR_TEX_MAX_SIZE,
+                    "pbr_gbuffer_raster_textured: texture size zero or above PBR_TEX_MAX_SIZE");
+        PBR_REQUIRE(ctx, t.mip_levels && t.mip_levels <= max_mip_levels(t.width, t.height),
+                    "pbr_gbuffer_raster_textured: mip_levels 0 or above floor(log2(min(w, h))) + 1");
+        PBR_REQUIRE(ctx, t.texels && (r8 || (pbr::addr(t.texels) & 3u) == 0),
+                    "pbr_gbuffer_raster_textured: texels null or not aligned to the texel size");
+        tx.table[i] = t;
+    }
+    return raster(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth, stencil,
+                  pitch, scratch, scratch_bytes, &tx);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@ SIGNATURES = {
     "pbrh_set_gbuffer": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pbrh_set_materials": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pbrh_set_meshes": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32]),
+    "pbrh_set_textured_meshes": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32]),
     "pbrh_set_initial_luminance": (_int, [_vp, C.c_float]),
     "pbrh_set_tile": (_int, [_vp] + [_u32] * 8),
     "pbrh_comm_init": (_int, [_vp, _int, _int, _vp]),
@@ -131,6 +132,21 @@ class HostRenderer:
         i = np.ascontiguousarray(indices, dtype=np.uint32)
         d = np.ascontiguousarray(draws, dtype=DRAW_DTYPE)
         self._check(self.lib.pbrh_set_meshes(self.h, v.ctypes.data, len(v), i.ctypes.data, len(i), d.ctypes.data, len(d)))
+
+    def set_textured_meshes(self, vertices, indices, draws, maps, textures):
+        """set_meshes plus the draws' maps (structs.DRAW_MAPS_DTYPE, one per draw) and their textures: (chain, width, height,
+        mip_levels, format) with the chain's host bytes in the reference's layout (scene.pack_chain).  GBufferPass uploads the chains
+        once and rasterizes through pbr_gbuffer_raster_textured."""
+        from .structs import DRAW_DTYPE, DRAW_MAPS_DTYPE, VERTEX_DTYPE, Texture2D
+        v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
+        i = np.ascontiguousarray(indices, dtype=np.uint32)
+        d = np.ascontiguousarray(draws, dtype=DRAW_DTYPE)
+        m = np.ascontiguousarray(maps, dtype=DRAW_MAPS_DTYPE)
+        chains = [np.ascontiguousarray(t[0]).view(np.uint8) for t in textures]
+        table = (Texture2D * max(len(chains), 1))(*[Texture2D(c.ctypes.data, int(t[1]), int(t[2]), int(t[3]), int(t[4]))
+                                                   for c, t in zip(chains, textures)])
+        self._check(self.lib.pbrh_set_textured_meshes(self.h, v.ctypes.data, len(v), i.ctypes.data, len(i), d.ctypes.data, len(d),
+                                                      m.ctypes.data, C.addressof(table), len(chains)))
 
     def set_initial_luminance(self, v):
         self._check(self.lib.pbrh_set_initial_luminance(self.h, float(v)))

@@ -105,7 +105,19 @@ void GBufferPass::UploadMeshes(FGContext* context, MeshSource& meshes, uint32 w,
     upload(mIndices, meshes.Indices.data(), meshes.Indices.size() * sizeof(uint32_t), sizeof(uint32_t));
     upload(mDraws, meshes.Draws.data(), meshes.Draws.size() * sizeof(pbr_draw), sizeof(pbr_draw));
     mMaxTriangles = (uint32)tris;
-    const size_t scratch = pbr_gbuffer_raster_scratch_bytes(w, h, mMaxTriangles);
+    mMaps.reset();
+    mTextures.clear();
+    mTextureTable.clear();
+    if (meshes.Textured()) {
+        upload(mMaps, meshes.Maps.data(), meshes.Maps.size() * sizeof(pbr_draw_maps), sizeof(pbr_draw_maps));
+        for (const TextureChain& t : meshes.Textures) {
+            mTextures.emplace_back();
+            upload(mTextures.back(), t.Texels.data(), t.Texels.size(), 1);
+            mTextureTable.push_back(pbr_texture2d{mTextures.back()->DevicePtr(), t.Width, t.Height, t.MipLevels, t.Format});
+        }
+    }
+    const size_t scratch = meshes.Textured() ? pbr_gbuffer_raster_textured_scratch_bytes(w, h, mMaxTriangles)
+                                             : pbr_gbuffer_raster_scratch_bytes(w, h, mMaxTriangles);
     if (scratch > 0xffffffffu) throw HipException("GBufferPass: raster scratch larger than 4 GiB");
     mRasterScratch = std::make_unique<DeviceStructuredBuffer>((uint32)scratch, 4);
     meshes.Dirty = false;
@@ -123,7 +135,9 @@ void GBufferPass::Execute(FGContext* context) {
         context->CommandList->RasterGBuffer(&mShadingState, (const pbr_vertex*)mVertices->DevicePtr(), (uint32)meshes.Vertices.size(),
                                             (const uint32_t*)mIndices->DevicePtr(), (uint32)meshes.Indices.size(),
                                             (const pbr_draw*)mDraws->DevicePtr(), (uint32)meshes.Draws.size(), mMaxTriangles,
-                                            a, b, c, ds, mRasterScratch->DevicePtr(), mRasterScratch->Size());
+                                            a, b, c, ds, mRasterScratch->DevicePtr(), mRasterScratch->Size(),
+                                            mMaps ? (const pbr_draw_maps*)mMaps->DevicePtr() : nullptr, mTextureTable.data(),
+                                            (uint32)mTextureTable.size());
         return;
     }
     GBufferSource& src = context->Scene->GBuffer();

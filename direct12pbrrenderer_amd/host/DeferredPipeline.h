@@ -74,6 +74,10 @@ protected:
     std::unique_ptr<DeviceStructuredBuffer> mMaterialPlanes;   // device copy of GBufferSource::M0..M2
     // device copies of MeshSource and the raster's scratch (sized for the render target and the draws' triangles)
     std::unique_ptr<DeviceStructuredBuffer> mVertices, mIndices, mDraws, mRasterScratch;
+    // textured draws: the maps, the texel chains and their descriptors (device pointers into mTextures)
+    std::unique_ptr<DeviceStructuredBuffer> mMaps;
+    std::vector<std::unique_ptr<DeviceStructuredBuffer>> mTextures;
+    std::vector<pbr_texture2d> mTextureTable;
     uint32 mMaxTriangles = 0;
 };
 

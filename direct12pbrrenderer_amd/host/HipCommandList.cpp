@@ -520,7 +520,8 @@ void HipCommandList::EncodeGBuffer(ShadingState* s, const float* m0, const float
 
 void HipCommandList::RasterGBuffer(ShadingState* s, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
                                    const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, DeviceTexture2D* a, DeviceTexture2D* b,
-                                   DeviceTexture2D* c, DeviceTexture2D* ds, void* scratch, size_t scratch_bytes) {
+                                   DeviceTexture2D* c, DeviceTexture2D* ds, void* scratch, size_t scratch_bytes,
+                                   const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32 n_textures) {
     if (!s || s->File() != "gbuffer.hlsl") throw HipException("RasterGBuffer: gbuffer.hlsl shading state expected");
     if (!a || !b || !c || !ds || a->Width() != b->Width() || a->Width() != c->Width() || a->Width() != ds->Width() ||
         a->Height() != b->Height() || a->Height() != c->Height() || a->Height() != ds->Height())
@@ -529,6 +530,13 @@ void HipCommandList::RasterGBuffer(ShadingState* s, const pbr_vertex* vertices, 
     FlushPendingBloom();
     const uint32 w = a->Width(), h = a->Height();
     const pbr_tile tile = mTile.w ? mTile : pbr_tile{0, 0, w, h, w, h};
+    if (maps) {
+        Check(pbr_gbuffer_raster_textured(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
+                                          (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(),
+                                          ds->DepthPlane(), ds->StencilPlane(), w, scratch, scratch_bytes, maps, textures, n_textures),
+              "pbr_gbuffer_raster_textured");
+        return;
+    }
     Check(pbr_gbuffer_raster(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
                              (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(), ds->DepthPlane(),
                              ds->StencilPlane(), w, scratch, scratch_bytes), "pbr_gbuffer_raster");

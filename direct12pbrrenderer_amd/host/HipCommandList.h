@@ -86,11 +86,13 @@ public:
     // device planes) -> GBufferA/B/C of the bound pass
     void EncodeGBuffer(ShadingState* state, const float* m0, const float* m1, const float* m2,
                        DeviceTexture2D* a, DeviceTexture2D* b, DeviceTexture2D* c);
-    // gbuffer.hlsl's vertex + pixel shader with DefaultOpaque's raster state over constant-material draws (pbr_gbuffer_raster):
-    // device vertex / index / draw arrays -> GBufferA/B/C and the depth-stencil target (the tile's rectangle in tile mode)
+    // gbuffer.hlsl's vertex + pixel shader with DefaultOpaque's raster state (pbr_gbuffer_raster): device vertex / index / draw
+    // arrays -> GBufferA/B/C and the depth-stencil target (the tile's rectangle in tile mode).  With maps (device, one per draw)
+    // the draws' texture maps are sampled from the host table of n_textures descriptors (pbr_gbuffer_raster_textured).
     void RasterGBuffer(ShadingState* state, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
                        const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, DeviceTexture2D* a, DeviceTexture2D* b,
-                       DeviceTexture2D* c, DeviceTexture2D* depth_stencil, void* scratch, size_t scratch_bytes);
+                       DeviceTexture2D* c, DeviceTexture2D* depth_stencil, void* scratch, size_t scratch_bytes,
+                       const pbr_draw_maps* maps = nullptr, const pbr_texture2d* textures = nullptr, uint32 n_textures = 0);
     void Present(DeviceTexture2D* tex) { mPresented = tex; }
 
     // Pass-level entry points (not in the reference): a pass whose Execute body is a fixed sequence of dispatches can

@@ -111,12 +111,21 @@ struct GBufferSource {
 // Triangle meshes with constant per-draw materials (pbrh_set_meshes): host copies of the vertex / index buffers and of one
 // pbr_draw (ConstantBufferInstance + index range) per DrawModel call.  When draws are set, GBufferPass rasterizes them
 // (pbr_gbuffer_raster) instead of uploading a GBufferSource; it uploads the arrays once, after each change.
+// pbrh_set_textured_meshes adds one pbr_draw_maps per draw and the host texel chains (the reference's mip layout) they index:
+// GBufferPass then uploads the chains once, after each change, and rasterizes through pbr_gbuffer_raster_textured.
+struct TextureChain {
+    std::vector<uint8_t> Texels;
+    uint32_t Width = 0, Height = 0, MipLevels = 0, Format = 0;
+};
 struct MeshSource {
     std::vector<pbr_vertex> Vertices;
     std::vector<uint32_t> Indices;
     std::vector<pbr_draw> Draws;
+    std::vector<pbr_draw_maps> Maps;        // empty: constant materials only
+    std::vector<TextureChain> Textures;
     bool Dirty = false;
     bool Empty() const { return Draws.empty(); }
+    bool Textured() const { return !Maps.empty(); }
 };
 
 class Scene {

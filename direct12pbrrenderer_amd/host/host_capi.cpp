@@ -3,6 +3,7 @@
 #include "HdrImage.h"
 #include "SceneFile.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -263,6 +264,42 @@ int pbrh_set_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices,
         m.Vertices.assign(v, v + n_vertices);
         m.Indices.assign(indices, indices + n_indices);
         m.Draws.assign(d, d + n_draws);
+        m.Maps.clear();
+        m.Textures.clear();
+        m.Dirty = true;
+    });
+}
+
+int pbrh_set_textured_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                             const void* draws, uint32_t n_draws, const void* maps, const void* texture_table, uint32_t n_textures) {
+    return guarded(r, [&] {
+        const pbr_texture2d* textures = static_cast<const pbr_texture2d*>(texture_table);
+        if (!vertices || !indices || !draws || !maps || !n_vertices || !n_indices || !n_draws || (n_textures && !textures))
+            throw HipException("pbrh_set_textured_meshes: null pointer / empty mesh");
+        if (n_draws > PBR_RASTER_MAX_DRAWS) throw HipException("pbrh_set_textured_meshes: more than PBR_RASTER_MAX_DRAWS draws");
+        if (n_textures > PBR_RASTER_MAX_TEXTURES) throw HipException("pbrh_set_textured_meshes: more than PBR_RASTER_MAX_TEXTURES textures");
+        std::vector<TextureChain> tex(n_textures);
+        for (uint32_t i = 0; i < n_textures; i++) {   // the chain's size from its descriptor (pbr_gbuffer_raster_textured checks the rest)
+            const pbr_texture2d& t = textures[i];
+            const size_t texel = t.format == PBR_TEX_R8_UNORM ? 1 : 4;
+            if (!t.texels || !t.width || !t.height || t.width > PBR_TEX_MAX_SIZE || t.height > PBR_TEX_MAX_SIZE || !t.mip_levels ||
+                (std::min(t.width, t.height) >> (t.mip_levels - 1)) == 0)
+                throw HipException("pbrh_set_textured_meshes: bad texture descriptor");
+            size_t bytes = 0;
+            for (uint32_t l = 0; l < t.mip_levels; l++) bytes += (size_t)(t.width >> l) * (t.height >> l) * texel;
+            const uint8_t* src = static_cast<const uint8_t*>(t.texels);
+            tex[i].Texels.assign(src, src + bytes);
+            tex[i].Width = t.width; tex[i].Height = t.height; tex[i].MipLevels = t.mip_levels; tex[i].Format = t.format;
+        }
+        MeshSource& m = r->scene->Meshes();
+        const pbr_vertex* v = static_cast<const pbr_vertex*>(vertices);
+        const pbr_draw* d = static_cast<const pbr_draw*>(draws);
+        const pbr_draw_maps* mp = static_cast<const pbr_draw_maps*>(maps);
+        m.Vertices.assign(v, v + n_vertices);
+        m.Indices.assign(indices, indices + n_indices);
+        m.Draws.assign(d, d + n_draws);
+        m.Maps.assign(mp, mp + n_draws);
+        m.Textures = std::move(tex);
         m.Dirty = true;
     });
 }

@@ -65,6 +65,11 @@ int pbrh_set_materials(pbrh_renderer* r, const float* m0, const float* m1, const
  * drop the meshes again. */
 int pbrh_set_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
                     const void* draws, uint32_t n_draws);
+/* pbrh_set_meshes plus textures: maps = n_draws pbr_draw_maps (20 B), textures = n_textures descriptors whose `texels` point to
+ * HOST chains in the reference's layout (pbr_texture2d records, include/pbr_hip.h).  Everything is copied here; GBufferPass uploads the
+ * chains once after each change and rasterizes through pbr_gbuffer_raster_textured. */
+int pbrh_set_textured_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                             const void* draws, uint32_t n_draws, const void* maps, const void* textures, uint32_t n_textures);
 int pbrh_set_initial_luminance(pbrh_renderer* r, float v);
 /* ---- multi-GPU: this renderer's target is the apron-extended tile at (x0, y0) of a full_w x full_h frame;
  * it OWNS the interior rectangle (ix, iy, iw, ih) of its target.  uv / camera ray / ClusterIndex use global pixels, the

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .api import PbrContext
-from .structs import (ENV_MIPS, HISTOGRAM_BINS, MAX_VIEWS, GBuffer, Global, Tile, View)
+from .structs import (DRAW_MAPS_DTYPE, ENV_MIPS, HISTOGRAM_BINS, MAX_VIEWS, NO_MAP, GBuffer, Global, Tile, View)
 
 # bloom's cumulative support is ~220 full-res pixels (3 down + 3 up levels of a radius-4 kernel on
 # a 2x pyramid); 256 also keeps every mip of the extended tile on the full frame's texel grid
@@ -340,25 +340,41 @@ class DeferredFrame:
         self.gb = {k: self.ctx.upload(v) for k, v in gb_np.items()}
         self.mesh = None   # uploaded planes replace meshes set before
 
-    def set_meshes(self, vertices, indices, draws):
+    def set_meshes(self, vertices, indices, draws, maps=None, textures=None):
         """Geometry instead of uploaded planes: host arrays (structs.VERTEX_DTYPE, uint32 indices, structs.DRAW_DTYPE records) are
         uploaded once, and every render() rasterizes them (pbr_gbuffer_raster, draws in array order) into the frame's own G-buffer
-        planes of the shaded rectangle S before the cluster, sky and shade passes (until upload_gbuffer replaces them)."""
+        planes of the shaded rectangle S before the cluster, sky and shade passes (until upload_gbuffer replaces them).
+        maps (structs.DRAW_MAPS_DTYPE, one per draw) and textures (the (device tensor, structs.Texture2D) pairs of
+        PbrContext.upload_texture, which the frame holds on to): the draws' texture maps, rasterized by
+        pbr_gbuffer_raster_textured when any draw has one.  Without them, or with every map NO_MAP, the call is the
+        constant-material one."""
         s, ctx = self.spec, self.ctx
         draws = np.ascontiguousarray(draws)
         n_tris = int((draws["index_count"] // 3).sum())
+        textured = maps is not None and bool((np.asarray(maps).view(np.uint32) != NO_MAP).any())
         self.mesh = {"vertices": ctx.upload(vertices), "n_vertices": len(vertices),
                      "indices": ctx.upload(np.ascontiguousarray(indices, dtype=np.uint32)), "n_indices": len(indices),
                      "draws": ctx.upload(draws), "n_draws": len(draws), "max_triangles": n_tris,
-                     "scratch": ctx.alloc_raster_scratch(s.sw, s.sh, n_tris)}
+                     "scratch": (ctx.alloc_textured_raster_scratch if textured else ctx.alloc_raster_scratch)(s.sw, s.sh, n_tris)}
+        if textured:
+            self.mesh["maps"] = ctx.upload(np.ascontiguousarray(maps, dtype=DRAW_MAPS_DTYPE))
+            pairs = list(textures or [])
+            if not all(isinstance(t, tuple) and len(t) == 2 for t in pairs):
+                raise ValueError("set_meshes: textures are (device tensor, Texture2D) pairs (PbrContext.upload_texture)")
+            self.mesh["texture_tensors"] = [t[0] for t in pairs]   # the memory the descriptors point into
+            self.mesh["textures"] = [t[1] for t in pairs]
         self.gb = {"A": ctx.zeros((s.sh, s.sw), torch.int32), "B": ctx.zeros((s.sh, s.sw), torch.int32),
                    "C": ctx.zeros((s.sh, s.sw), torch.int32), "depth": ctx.zeros((s.sh, s.sw), torch.float32),
                    "stencil": ctx.zeros((s.sh, s.sw), torch.uint8)}
 
     def rasterize(self):
         m, gb = self.mesh, self.gb
-        self.ctx.gbuffer_raster(self.g, self.tile, m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"], m["n_draws"],
-                                m["max_triangles"], gb["A"], gb["B"], gb["C"], gb["depth"], gb["stencil"], self.spec.sw, m["scratch"])
+        args = (self.g, self.tile, m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"], m["n_draws"],
+                m["max_triangles"], gb["A"], gb["B"], gb["C"], gb["depth"], gb["stencil"], self.spec.sw, m["scratch"])
+        if "maps" in m:
+            self.ctx.gbuffer_raster_textured(*args, m["maps"], m["textures"])
+        else:
+            self.ctx.gbuffer_raster(*args)
 
     def set_prev_luminance(self, v):
         self.avg.fill_(float(v))

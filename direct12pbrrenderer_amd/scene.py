@@ -18,7 +18,7 @@ import math
 
 import numpy as np
 
-from .structs import DRAW_DTYPE, LIGHT_DTYPE, VERTEX_DTYPE, Global, ShPack
+from .structs import DRAW_DTYPE, DRAW_MAPS_DTYPE, LIGHT_DTYPE, NO_MAP, VERTEX_DTYPE, Global, ShPack
 
 f32 = np.float32
 PI = f32(3.14159265359)
@@ -256,11 +256,15 @@ def inverse(m):
 class Mesh:
     """One vertex buffer (structs.VERTEX_DTYPE: position, normal, tangent, colour, uv) and its uint32 triangle list."""
 
-    def __init__(self, positions, normals, indices):
+    def __init__(self, positions, normals, indices, tangents=None, uvs=None):
         positions = np.asarray(positions, dtype=f32).reshape(-1, 3)
         self.vertices = np.zeros(len(positions), dtype=VERTEX_DTYPE)
         self.vertices["position"] = positions
         self.vertices["normal"] = np.asarray(normals, dtype=f32).reshape(-1, 3)
+        if tangents is not None:
+            self.vertices["tangent"] = np.asarray(tangents, dtype=f32).reshape(-1, 3)
+        if uvs is not None:
+            self.vertices["uv"] = np.asarray(uvs, dtype=f32).reshape(-1, 2)
         self.indices = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
 
     @property
@@ -325,7 +329,7 @@ class MeshScene:
     before again: instance=index) and one pbr_draw; arrays() -> (vertices, indices, draws), the input of pbr_gbuffer_raster."""
 
     def __init__(self):
-        self._verts, self._idx, self._draws, self._ranges = [], [], [], []
+        self._verts, self._idx, self._draws, self._ranges, self._maps = [], [], [], [], []
         self._nv = self._ni = 0
 
     def add_mesh(self, mesh):
@@ -336,8 +340,14 @@ class MeshScene:
         self._ni += len(mesh.indices)
         return len(self._ranges) - 1
 
-    def add(self, mesh, model, albedo=(1.0, 1.0, 1.0), emission=0.0, roughness=0.5, metallic=0.0):
+    def add(self, mesh, model, albedo=(1.0, 1.0, 1.0), emission=0.0, roughness=0.5, metallic=0.0, maps=None):
+        """maps: {"albedo" | "normal" | "roughness" | "metallic" | "ao": texture index} (the Use*Map flags; a map left out takes
+        the constant branch) -> the draw's record of maps()"""
         k = mesh if isinstance(mesh, int) else self.add_mesh(mesh)
+        m = np.full((), NO_MAP, dtype=DRAW_MAPS_DTYPE)
+        for name, t in (maps or {}).items():
+            m[name] = t
+        self._maps.append(m)
         first, count, base = self._ranges[k]
         d = np.zeros((), dtype=DRAW_DTYPE)
         d["Model"] = np.asarray(model, dtype=f32).reshape(16)
@@ -352,17 +362,78 @@ class MeshScene:
                 np.concatenate(self._idx).astype(np.uint32) if self._idx else np.zeros(0, np.uint32),
                 np.array(self._draws, dtype=DRAW_DTYPE))
 
+    def maps(self):
+        """the draws' pbr_draw_maps records (structs.DRAW_MAPS_DTYPE), parallel to arrays()[2]"""
+        return np.array(self._maps, dtype=DRAW_MAPS_DTYPE)
 
-def reference_models(fx):
+
+def mip_chain(level0, mip_levels=None):
+    """A synthetic texture's mip chain: level0 (uint8 [h, w] or [h, w, channels]) and each next level the 2 x 2 box average of the
+    one above ((a + b + c + d + 2) >> 2 on the stored bytes; an odd last row / column is dropped), down to mip_levels levels (all
+    of them by default: floor(log2(min(w, h))) + 1).  The chain is input data: any chain is sampled as given."""
+    lv = [np.ascontiguousarray(level0, dtype=np.uint8)]
+    h, w = lv[0].shape[:2]
+    n = int(np.floor(np.log2(min(w, h)))) + 1 if mip_levels is None else int(mip_levels)
+    for i in range(1, n):
+        a = lv[-1].astype(np.uint32)
+        hh, ww = h >> i, w >> i
+        a = a[:2 * hh, :2 * ww]
+        s = a[0::2, 0::2] + a[1::2, 0::2] + a[0::2, 1::2] + a[1::2, 1::2]
+        lv.append(((s + 2) >> 2).astype(np.uint8))
+    return lv
+
+
+def pack_chain(levels):
+    """mip levels -> the bytes of the reference's layout (levels concatenated from level 0, rows tightly packed)"""
+    return np.concatenate([np.ascontiguousarray(l).reshape(-1) for l in levels])
+
+def reference_models(fx, ms=None):
     """The constant-material models of the reference's scene (Asset/Scene/main.json) from the fixture written by
     tests/golden/make_sphere_grid.py (fx: the loaded npz): one shared mesh (sphere_Mesh_data.bin) and one draw per model, in file
-    order.  Returns ((vertices, indices, draws), names)."""
+    order, appended to ms (a new MeshScene by default).  Returns ((vertices, indices, draws), names)."""
     verts = np.zeros(len(fx["vertices"]), dtype=VERTEX_DTYPE)
     verts.view(np.float32).reshape(-1, 14)[:] = fx["vertices"]
-    ms = MeshScene()
+    ms = MeshScene() if ms is None else ms
     mesh = Mesh(verts["position"], verts["normal"], fx["indices"])
     mesh.vertices = verts
     k = ms.add_mesh(mesh)
     for world, mat in zip(fx["world"], fx["material"]):
         ms.add(k, world, albedo=tuple(mat[:3]), emission=mat[3], roughness=mat[4], metallic=mat[5])
     return ms.arrays(), [str(n) for n in fx["name"]]
+
+
+def add_textured_models(ms, fx):
+    """The textured models of the reference's scene from the fixture written by tests/golden/make_textured_models.py (fx: the
+    loaded npz) appended to MeshScene ms: one mesh per model, one draw per sub-mesh with the model's world matrix, material
+    constants and maps.  Returns (textures, names): textures in table order as dicts of the chain kept in the fixture (levels:
+    uint8 arrays in the stored format, width, height, mips, format), which the draws' map indices point into."""
+    textures, names = [], [str(n) for n in fx["name"]]
+    for n in names:
+        verts = np.zeros(len(fx[f"{n}_vertices"]), dtype=VERTEX_DTYPE)
+        verts.view(np.float32).reshape(-1, 14)[:] = fx[f"{n}_vertices"]
+        mesh = Mesh(verts["position"], verts["normal"], fx[f"{n}_indices"])
+        mesh.vertices = verts
+        mat = fx[f"{n}_material"]
+        maps = {}
+        for k in fx["maps"]:
+            key = f"{n}_{k}_texels"
+            if key not in fx.files:
+                continue
+            w0, h0, _, fmt, w, h, mips = (int(x) for x in fx[f"{n}_{k}_info"])
+            ch = 1 if fmt == 61 else 4
+            data, levels, o = fx[key], [], 0
+            for l in range(mips):
+                sz = (w >> l) * (h >> l) * ch
+                lv = data[o:o + sz].reshape(h >> l, w >> l, ch)
+                levels.append(lv[..., 0] if ch == 1 else lv)
+                o += sz
+            maps[str(k)] = len(textures)
+            textures.append({"levels": levels, "width": w, "height": h, "mips": mips, "format": fmt})
+        subs = fx[f"{n}_submeshes"]
+        k = ms.add_mesh(mesh)
+        first, _, base = ms._ranges[k]
+        for start, count in subs:
+            ms._ranges.append((first + int(start), int(count), base))
+            ms.add(len(ms._ranges) - 1, fx[f"{n}_world"], albedo=tuple(mat[:3]), emission=mat[3], roughness=mat[4], metallic=mat[5],
+                   maps=maps)
+    return textures, names

@@ -119,6 +119,28 @@ RASTER_MAX_TRIANGLES = 1 << 22                        # PBR_RASTER_MAX_TRIANGLES
 RASTER_MAX_SIZE = 8192                                # PBR_RASTER_MAX_SIZE
 
 
+class Texture2D(C.Structure):
+    """pbr_texture2d: a device mip chain in the reference's layout (level i (width >> i) x (height >> i), levels concatenated)
+    and its DXGI format number (24 B)."""
+    _fields_ = [("texels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("mip_levels", C.c_uint32),
+                ("format", C.c_uint32)]
+
+
+assert C.sizeof(Texture2D) == 24
+# pbr_draw_maps: per draw, the texture index of each map, NO_MAP = the constant branch (an array parallel to the draws)
+DRAW_MAPS_DTYPE = np.dtype([("albedo", np.uint32), ("normal", np.uint32), ("roughness", np.uint32), ("metallic", np.uint32),
+                            ("ao", np.uint32)])
+assert DRAW_MAPS_DTYPE.itemsize == 20
+MAP_NAMES = DRAW_MAPS_DTYPE.names
+NO_MAP = 0xFFFFFFFF                                   # PBR_NO_MAP
+RASTER_MAX_TEXTURES = 64                              # PBR_RASTER_MAX_TEXTURES
+TEX_MAX_SIZE = 16384                                  # PBR_TEX_MAX_SIZE
+# DXGI formats the textured raster reads (PBR_TEX_*): number -> (bytes per texel, sRGB)
+TEX_R8G8B8A8_UNORM, TEX_B8G8R8A8_UNORM, TEX_B8G8R8A8_UNORM_SRGB, TEX_R8_UNORM = 28, 87, 91, 61
+TEX_FORMATS = {TEX_R8G8B8A8_UNORM: (4, False), TEX_B8G8R8A8_UNORM: (4, False), TEX_B8G8R8A8_UNORM_SRGB: (4, True),
+               TEX_R8_UNORM: (1, False)}
+
+
 class CubeF32(C.Structure):
     _fields_ = [("data", C.c_void_p), ("size", C.c_uint32), ("mips", C.c_uint32)]
 

@@ -285,7 +285,7 @@ pbr_status pbr_gbuffer_encode(pbr_ctx* ctx, const float* m0, const float* m1, co
 
 /* ---- G-buffer rasterization (new): triangle meshes with constant per-draw materials -> the five G-buffer planes ---------- */
 /* VSInput_P3F_N3F_T2F_T2F (DeferredRendering/Shader/global.hlsli:59-66), 56 B: the reference's vertex buffers pass through
- * unchanged.  The raster reads position and normal only. */
+ * unchanged.  The raster reads position and normal only (the textured raster also tangent and uv). */
 typedef struct pbr_vertex {
     float position[3];
     float normal[3];
@@ -340,6 +340,59 @@ pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile*
                               const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
                               uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
                               void* scratch, size_t scratch_bytes);
+
+/* ---- Textured G-buffer rasterization (new): gbuffer.hlsl's Use*Map == true branches ------------------------------------- */
+/* A 2D texture with its whole mip chain in device memory, as the reference creates it (ResourceDef.cpp:53-66, TextureInfo and
+ * CalculateMipmapLayout, BasicStorage.h:193-233): level i is (width >> i) x (height >> i) texels, rows tightly packed, levels
+ * concatenated from level 0.  format: the DXGI number, one of the four the reference's assets use. */
+#define PBR_TEX_R8G8B8A8_UNORM       28u
+#define PBR_TEX_B8G8R8A8_UNORM       87u
+#define PBR_TEX_B8G8R8A8_UNORM_SRGB  91u
+#define PBR_TEX_R8_UNORM             61u
+#define PBR_TEX_MAX_SIZE             16384u
+typedef struct pbr_texture2d {
+    const void* texels;            /* device; 4-byte aligned for the 4-byte formats */
+    uint32_t width, height;        /* 1 .. PBR_TEX_MAX_SIZE */
+    uint32_t mip_levels;           /* 1 .. floor(log2(min(width, height))) + 1 */
+    uint32_t format;               /* PBR_TEX_* */
+} pbr_texture2d;
+/* The Use*Map flags of ConstantBufferInstance (gbuffer.hlsl:43-47) as texture indices, one record per draw in an array parallel
+ * to the pbr_draw array: PBR_NO_MAP takes the constant branch, any other value is an index into the call's texture table. */
+#define PBR_NO_MAP                   0xffffffffu
+#define PBR_RASTER_MAX_TEXTURES      64u
+typedef struct pbr_draw_maps {
+    uint32_t albedo, normal, roughness, metallic, ao;
+} pbr_draw_maps;
+/* The sampler (SamplerLinearWrap, global.hlsli:21: MIN_MAG_MIP_LINEAR, wrap, MinLOD 0, MaxLOD FLT_MAX, no bias), pinned:
+ *   Decode, before filtering: UNORM8 c -> c / 255 correctly rounded; the colour channels of _SRGB -> the sRGB curve of c / 255
+ *   (x <= 0.04045 ? x / 12.92 : ((x + 0.055) / 1.055)^2.4) evaluated in double and rounded to fp32.  .x is red for every format
+ *   (B8G8R8A8 swizzles); R8 reads as (r, 0, 0, 1).
+ *   LOD, one per 2 x 2 quad and triangle: the quad origin (qx, qy) = (gx & ~1, gy & ~1) in global pixels; the winning
+ *   triangle's perspective-correct uv at the pixel centres (qx + 1/2, qy + 1/2), (qx + 3/2, qy + 1/2), (qx + 1/2, qy + 3/2)
+ *   gives ddx = uv10 - uv00, ddy = uv01 - uv00; per texture rho = max(|ddx * (w, h)|, |ddy * (w, h)|) (fp32, sqrtf), lambda =
+ *   log2(rho) in double rounded to fp32 and clamped to [0, mip_levels - 1]; rho 0 or NaN gives lambda 0.
+ *   Filter: l = floor(lambda), f = lambda - l; bilinear on levels l and min(l + 1, mip_levels - 1), blended by f.  Bilinear at
+ *   texel coordinates (u w_l - 1/2, v h_l - 1/2): floor and fraction, both taps wrapped by non-negative modulo; each lerp is
+ *   f == 0 ? a : fmaf(b, f, a (1 - f)) (x first, then y, then the levels), fp32 weights (not D3D's 8-bit fixed point). */
+size_t pbr_gbuffer_raster_textured_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
+size_t pbr_gbuffer_raster_textured_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
+/* pbr_gbuffer_raster with the pixel shader's map branches (gbuffer.hlsl:88-149): the same arguments and contract, plus
+ *   maps: DEVICE array of n_draws records (the draw's maps); textures: HOST array of n_textures descriptors (copied by value).
+ * Vertex stage adds tangent_ws = transpose(InvModel) (tangent, 0) (the normal's rule) and passes uv through; both are
+ * interpolated perspective-correctly like the normal.  With a map: albedo = decode_gamma(sample.rgb); normal = normalize(ts.x t
+ * + ts.y b + ts.z n) with n = normalize(normal_ws), t = normalize(tangent_ws), b = cross(n, t), ts = sample.rgb * 2 - 1;
+ * roughness, metallic, AO = sample.x.  Without one: the constant (AO 0), bit-identical to pbr_gbuffer_raster.
+ * Guard on device data: a draw with a map index >= n_textures (other than PBR_NO_MAP) is dropped.
+ * Refusals (PBR_ERR_INVALID, nothing enqueued): those of pbr_gbuffer_raster; maps null or not 4-byte aligned; n_textures >
+ * PBR_RASTER_MAX_TEXTURES, or textures null with n_textures > 0; a texture of another format, a zero size or one above
+ * PBR_TEX_MAX_SIZE, mip_levels 0 or above floor(log2(min(w, h))) + 1, null or misaligned texels; scratch below
+ * pbr_gbuffer_raster_textured_min_scratch_bytes. */
+pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                       const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                                       const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                                       uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                                       void* scratch, size_t scratch_bytes,
+                                       const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures);
 
 /* bloom_prefilter.hlsl:17-60 (DeferredPipeline.cpp:411-427): hdr (w x h) -> out (w>>1 x h>>1). */
 pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h,

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Writes tests/golden/textured_models.npz: the textured models of the reference's scene asset (barrel, rock, suitcase, tile) as
+DATA, for pbr_gbuffer_raster_textured.
+
+Build container only (it reads /root/reference, which does not travel to the GPU box):
+
+    python tests/golden/make_textured_models.py
+
+Sources under /root/reference/DeferredRendering:
+  * Asset/Scene/main.json `mSceneModel`: per model its name, translation, rotation (degrees), scale and model file; the model
+    file names the mesh (read as make_sphere_grid.read_mesh does) and the material, whose `mParameterTable` holds the Use*Map
+    flags (missing constants take ConstantBufferInstance's defaults, Engine/Include/Renderer/Pipeline/IPipeline.h:71) and whose
+    `mTexturePath` names one texture asset per map;
+  * each texture's `_data.bin`: a TextureInfo header (Engine/Include/Resource/BasicStorage.h:193-203: uint16 width, height,
+    depth, mips; uint8 DXGI format; 3 pad bytes), a uint32 byte count and the BC1 blocks of every level (level i is
+    (width >> i) x (height >> i) texels, 8 bytes per 4 x 4 block, at least one block).  The reference decompresses them at load
+    time (TextureCompression.cpp TextureDecompressInternal) into the stored format.
+
+Per map, the file keeps the chain from the 32 x 32 level down (the full chains would not fit a committed file), decoded from BC1
+into the stored format's bytes: 28 R8G8B8A8 (R, G, B, A), 87 / 91 B8G8R8A8 (B, G, R, A), 61 R8 (R), with the original size, level
+count and format.  BC1 decode rule (the format's public definition): endpoints RGB565 expanded to 8 bits by bit replication
+((c5 << 3) | (c5 >> 2), (c6 << 2) | (c6 >> 4)); colour0 > colour1: the two middle colours (2 c0 + c1 + 1) // 3 and
+(c0 + 2 c1 + 1) // 3 per channel, alpha 255; otherwise (c0 + c1 + 1) // 2 and transparent black.  For format 91 the decoded
+bytes are stored as they are: no sRGB curve is applied or removed in the decode (whether DirectXTex does so when it decodes
+into an _SRGB format is not pinned).  Levels smaller than a block keep the block's top-left texels.
+
+Models whose mesh or textures are missing from the asset tree (the revolver) are listed in `missing`."""
+import json
+import os
+import struct
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [HERE, os.path.dirname(os.path.dirname(HERE))]
+from make_sphere_grid import REF, load_json, read_mesh  # noqa: E402
+from direct12pbrrenderer_amd import scene  # noqa: E402
+
+OUT = os.path.join(HERE, "textured_models.npz")
+KEEP = 32                                     # the first level kept: 32 x 32 on the square assets
+DEFAULTS = {"Albedo": [1.0, 1.0, 1.0], "Emission": 0.0, "Roughness": 1.0, "Metallic": 0.0}
+# map name in the fixture, material texture key, material flag
+MAPS = [("albedo", "AlbedoMap", "UseAlbedoMap"), ("normal", "NormalMap", "UseNormalMap"),
+        ("roughness", "RoughnessMap", "UseRoughnessMap"), ("metallic", "MetallicMap", "UseMetallicMap"),
+        ("ao", "AmbientOcclusionMap", "UseAmbientOcclusionMap")]
+
+
+def expand565(c):
+    r, g, b = (c >> 11) & 31, (c >> 5) & 63, c & 31
+    return np.stack([(r << 3) | (r >> 2), (g << 2) | (g >> 4), (b << 3) | (b >> 2)], -1).astype(np.int32)
+
+
+def bc1_decode(blocks, w, h):
+    """BC1 blocks (uint8 [n * 8]) of a w x h level -> RGBA uint8 [h, w, 4]"""
+    bw, bh = max(1, (w + 3) // 4), max(1, (h + 3) // 4)
+    b = np.frombuffer(blocks, np.uint8).reshape(bh, bw, 8)
+    c0 = b[..., 0].astype(np.int32) | (b[..., 1].astype(np.int32) << 8)
+    c1 = b[..., 2].astype(np.int32) | (b[..., 3].astype(np.int32) << 8)
+    bits = b[..., 4].astype(np.uint32) | (b[..., 5].astype(np.uint32) << 8) | (b[..., 6].astype(np.uint32) << 16) | \
+        (b[..., 7].astype(np.uint32) << 24)
+    e0, e1 = expand565(c0), expand565(c1)
+    four = (c0 > c1)[..., None]
+    pal = np.zeros((bh, bw, 4, 4), np.int32)
+    pal[..., 0, :3], pal[..., 1, :3] = e0, e1
+    pal[..., 2, :3] = np.where(four, (2 * e0 + e1 + 1) // 3, (e0 + e1 + 1) // 2)
+    pal[..., 3, :3] = np.where(four, (e0 + 2 * e1 + 1) // 3, 0)
+    pal[..., :3, 3] = 255
+    pal[..., 3, 3] = np.where(four[..., 0], 255, 0)
+    out = np.zeros((bh * 4, bw * 4, 4), np.uint8)
+    for k in range(16):
+        idx = (bits >> (2 * k)) & 3
+        px = np.take_along_axis(pal, idx[..., None, None].astype(np.int64).repeat(4, -1), axis=2)[..., 0, :]
+        out[k // 4::4, k % 4::4] = px
+    return out[:h, :w]
+
+
+def read_texture(rel):
+    """the texture asset's stored chain from level KEEP down: (levels as stored-format bytes, width, height, mips, format)"""
+    path = os.path.join(REF, rel.replace("\\", "/"))
+    meta = json.load(open(os.path.splitext(path)[0] + ".json"))
+    data = open(os.path.join(REF, meta["mTexturePath"].replace("\\", "/") + ".bin"), "rb").read()
+    w, h, _, mips, fmt = struct.unpack_from("<HHHHB", data, 0)
+    nbytes = struct.unpack_from("<I", data, 12)[0]
+    assert 16 + nbytes == len(data), "unexpected texture layout"
+    o, levels = 16, []
+    for l in range(mips):
+        lw, lh = w >> l, h >> l
+        size = max(1, (lw + 3) // 4) * max(1, (lh + 3) // 4) * 8
+        if min(lw, lh) <= KEEP:
+            rgba = bc1_decode(data[o:o + size], lw, lh)
+            if fmt == 28:
+                levels.append(rgba)
+            elif fmt in (87, 91):
+                levels.append(rgba[..., [2, 1, 0, 3]])
+            elif fmt == 61:
+                levels.append(rgba[..., 0])
+            else:
+                raise ValueError(f"{rel}: format {fmt}")
+        o += size
+    assert o == len(data), "unexpected texture layout"
+    return levels, w, h, mips, fmt
+
+
+def main():
+    doc = json.load(open(os.path.join(REF, "Asset/Scene/main.json")))
+    out, names, missing = {}, [], []
+    for m in doc["mSceneModel"]:
+        o = m["@SceneObject"]
+        model = load_json(m["mModelFilePath"])
+        mat = load_json(model["mMaterialPath"][0])
+        if not mat.get("mTexturePath"):
+            continue
+        name = o["mName"]
+        try:
+            verts, idx, subs = read_mesh(load_json(model["mMeshPath"])["mMeshPath"])
+            tex = {k: read_texture(mat["mTexturePath"][key]) for k, key, flag in MAPS if mat["mParameterTable"].get(flag)}
+        except FileNotFoundError:
+            missing.append(name)
+            continue
+        p = dict(DEFAULTS, **{k: v for k, v in mat["mParameterTable"].items() if not k.startswith("Use")})
+        t, r, s = ([float(o[k][a]) for a in "xyz"] for k in ("mTranslation", "mRotation", "mScale"))
+        names.append(name)
+        out[f"{name}_vertices"], out[f"{name}_indices"], out[f"{name}_submeshes"] = verts, idx, subs
+        out[f"{name}_world"] = scene.model_matrix(t, r, s)
+        out[f"{name}_material"] = np.float32([*p["Albedo"], p["Emission"], p["Roughness"], p["Metallic"]])
+        out[f"{name}_use"] = np.array([bool(mat["mParameterTable"].get(flag)) for _, _, flag in MAPS])
+        for k, (levels, w, h, mips, fmt) in tex.items():
+            out[f"{name}_{k}_texels"] = scene.pack_chain(levels)
+            # original width, height, levels, format; then the kept chain's width, height, levels
+            out[f"{name}_{k}_info"] = np.uint32([w, h, mips, fmt, levels[0].shape[1], levels[0].shape[0], len(levels)])
+    np.savez_compressed(OUT, name=np.array(names), missing=np.array(missing), maps=np.array([k for k, _, _ in MAPS]), **out)
+    print(f"{OUT}: {names}, missing {missing}, {os.path.getsize(OUT)} bytes")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Times pbr_gbuffer_raster_textured against the constant-material raster (HIP events on the context's stream, after warm-up) and
+writes profiles/raster_tex_ms.txt.
+
+Scene: the reference scene's 33 constant-material models (tests/golden/sphere_grid.npz) plus its four textured models (barrel,
+rock, suitcase, tile; tests/golden/textured_models.npz: their meshes, world matrices and maps) under the reference camera.  The
+fixture keeps only 32 x 32 chains, so the timed textures are synthetic (seeded noise, box-filtered chains) at each map's
+original size, level count and format (barrel 1024^2 x 11 levels, the others 2048^2 x 12).  Rows per size (1440x960,
+3840x2160): the same draws with every map NO_MAP (constant-only) and with the maps (textured), each with the frame's shade
+(pbr_deferred_shade, small IBL, the 8 lights) for scale.
+Usage: python tools/raster_tex_ms.py [--iters N] [--out profiles/raster_tex_ms.txt]"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import common  # noqa: E402
+from direct12pbrrenderer_amd import scene  # noqa: E402
+from direct12pbrrenderer_amd.api import PbrContext  # noqa: E402
+from direct12pbrrenderer_amd.pipeline import DeferredFrame, TileSpec  # noqa: E402
+from direct12pbrrenderer_amd.structs import NO_MAP, TEX_R8_UNORM  # noqa: E402
+from oracle import binding as orc  # noqa: E402
+from raster_ms import timed  # noqa: E402
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "raster_tex_ms.txt"))
+    a = ap.parse_args()
+    ctx = PbrContext(0)
+    rng = np.random.default_rng(2024)
+    sky, env, lut, sh = common.small_ibl(orc)
+    rec = common.reference_scene_lights()
+    lights = np.concatenate([scene.make_lights(rec["translation"][j], rec["color"][j], rec["radius"][j], rec["intensity"][j])
+                             for j in range(len(rec["radius"]))])
+    fx = np.load(os.path.join(ROOT, "tests", "golden", "sphere_grid.npz"))
+    fxt = np.load(os.path.join(ROOT, "tests", "golden", "textured_models.npz"))
+    ms = scene.MeshScene()
+    scene.reference_models(fx, ms)
+    fixture_tex, _ = scene.add_textured_models(ms, fxt)
+    v, i, d = ms.arrays()
+    maps = ms.maps()
+    # the fixture's texture table order, each replaced by a synthetic full-size chain of the original size / levels / format
+    infos = [fxt[f"{n}_{k}_info"] for n in fxt["name"] for k in fxt["maps"] if f"{n}_{k}_info" in fxt.files]
+    assert len(infos) == len(fixture_tex)
+    textures = []
+    for w0, h0, mips0, fmt, *_ in (tuple(int(x) for x in inf) for inf in infos):
+        ch = 1 if fmt == TEX_R8_UNORM else 4
+        lv0 = rng.integers(0, 256, (h0, w0, ch) if ch == 4 else (h0, w0), dtype=np.uint8)
+        textures.append(ctx.upload_texture(scene.pack_chain(scene.mip_chain(lv0, mips0)), w0, h0, mips0, fmt))
+    lines = [f"pbr_gbuffer_raster_textured, {torch.cuda.get_device_name(0)}, HIP events, {a.iters} calls after 5 warm-up calls; "
+             "shade = pbr_deferred_shade of the same frame (8 lights, 16^2 env / 32^2 LUT)",
+             "scene: the 33 constant models + barrel, rock, suitcase, tile (fixture meshes; synthetic textures at the assets' sizes, "
+             "levels and formats: 1024^2 x 11 / 2048^2 x 12)",
+             f"{'row':<16}{'size':>11}{'triangles':>11}{'raster ms':>11}{'shade ms':>10}{'covered':>9}{'textured px':>13}"]
+    for w, h in ((1440, 960), (3840, 2160)):
+        cam = scene.Camera.reference_default(w, h)
+        g = scene.make_global(cam, w, h, sh_pack=sh)
+
+        def dev_half(x):
+            return ctx.upload(np.ascontiguousarray(x, dtype=np.float16).view(np.uint16)).view(torch.float16)
+        for row, mp in (("constant-only", np.full_like(maps, NO_MAP)), ("textured", maps)):
+            fr = DeferredFrame(ctx, TileSpec(0, 0, w, h, w, h, 0), g, lights, dev_half(lut), lut.shape[0], dev_half(env),
+                               common.ENV_SIZE, common.ENV_MIPS)
+            fr.set_meshes(v, i, d, maps=mp, textures=textures)
+            n = fr.mesh["max_triangles"]
+            ms_r = timed(fr.rasterize, a.iters)
+            fr.clustered()
+            ms_s = timed(fr.shade, a.iters)
+            cov = float((fr.gb["stencil"] > 0).float().mean())
+            ao = int(((fr.gb["C"] >> 16) & 255).gt(0).sum())      # pixels whose AO came from a map
+            lines.append(f"{row:<16}{f'{w}x{h}':>11}{n:>11}{ms_r:>11.4f}{ms_s:>10.4f}{cov:>9.3f}{ao:>13}")
+            print(lines[-1], flush=True)
+            del fr
+            torch.cuda.empty_cache()
+    ctx.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    open(a.out, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()
