@@ -54,6 +54,8 @@ SIGNATURES = {
     "pbr_gbuffer_raster_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
                                   _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz]),
+    "pbr_texture2d_bytes": (_sz, [_u32, _u32, _u32, _u32]),
+    "pbr_bc1_decode": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "pbr_gbuffer_raster_textured_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster_textured_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster_textured": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,

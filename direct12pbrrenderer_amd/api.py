@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from .structs import (Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, TEX_FORMATS, VERTEX_DTYPE, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, cube_texels, env_padded_texels)
+                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, cube_texels, env_padded_texels, texture2d_bytes)
 
 
 class PbrError(RuntimeError):
@@ -276,11 +276,35 @@ class PbrContext:
 
     def upload_texture(self, chain, width, height, mip_levels, fmt):
         """A texture's mip chain (host bytes in the reference's layout: scene.mip_chain / pack_chain) -> (device tensor,
-        structs.Texture2D describing it).  Keep the tensor alive while the descriptor is in use."""
-        if int(fmt) not in TEX_FORMATS:
+        structs.Texture2D describing it).  Keep the tensor alive while the descriptor is in use.
+        fmt | structs.TEX_BC1_BLOCKS: the chain is BC1 blocks (the payload of the reference's texture files), kept as they are for
+        the rasterizer to sample in place; its byte count must be structs.texture2d_bytes of the description."""
+        fmt = int(fmt)
+        host = np.ascontiguousarray(chain).view(np.uint8).reshape(-1)
+        if fmt & TEX_BC1_BLOCKS:
+            want = texture2d_bytes(width, height, mip_levels, fmt)
+            if want == 0:
+                raise PbrError(f"bad BC1 texture description: {width} x {height}, {mip_levels} levels, format {fmt:#x}")
+            if host.size != want:
+                raise PbrError(f"BC1 chain of {host.size} bytes, {width} x {height} x {mip_levels} levels takes {want}")
+        elif fmt not in TEX_FORMATS:
             raise PbrError(f"unknown texture format {fmt}")
-        dev = self.upload(np.ascontiguousarray(chain).view(np.uint8).reshape(-1))
-        return dev, Texture2D(dev.data_ptr(), int(width), int(height), int(mip_levels), int(fmt))
+        dev = self.upload(host)
+        return dev, Texture2D(dev.data_ptr(), int(width), int(height), int(mip_levels), fmt)
+
+    def bc1_decode(self, blocks, width, height, mip_levels, stored_format, out=None):
+        """pbr_bc1_decode: a BC1 chain on the device (uint8 tensor, or the (tensor, Texture2D) pair of upload_texture) -> the
+        decoded chain in stored_format as upload_texture returns it: (device tensor, structs.Texture2D)."""
+        if isinstance(blocks, tuple):
+            blocks = blocks[0]
+        nbytes = texture2d_bytes(width, height, mip_levels, int(stored_format))
+        if nbytes == 0 or int(stored_format) & TEX_BC1_BLOCKS:
+            raise PbrError(f"bad texture description: {width} x {height}, {mip_levels} levels, stored format {stored_format}")
+        if blocks.numel() * blocks.element_size() != texture2d_bytes(width, height, mip_levels, int(stored_format) | TEX_BC1_BLOCKS):
+            raise PbrError("bc1_decode: the block tensor's size does not match the description")
+        out = out if out is not None else self.empty((nbytes,), torch.uint8)
+        self._check(self.lib.pbr_bc1_decode(self.h, _ptr(blocks), int(width), int(height), int(mip_levels), int(stored_format), _ptr(out)))
+        return out, Texture2D(out.data_ptr(), int(width), int(height), int(mip_levels), int(stored_format))
 
     def gbuffer_raster_textured(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
                                 A, B, Cc, depth, stencil, pitch, scratch, maps, textures, scratch_bytes=None):

@@ -25,8 +25,12 @@
 // (RsTexAttr) and drops draws with a bad map index; the resolve adds the perspective-correct uv / tangent, the quad's LOD, up to
 // five trilinear samples (SamplerLinearWrap as pinned in pbr_hip.h) and the normal-map frame, before the same encode.
 // tests/raster_tex_ref.py restates it.
+//
+// BC1-resident textures (PBR_TEX_BC1_BLOCKS): a table that holds one runs k_rs_raster<RsRasterTexBc1>, whose bilinear takes its taps
+// from the blocks in place (bc1_decode.hpp); pbr_bc1_decode (k_bc1_decode) is the bulk decode of a whole chain, at the end of the file.
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
+#include <type_traits>
 
 using namespace pbr;
 
@@ -34,6 +38,7 @@ namespace {
 
 #include "gbuffer_encode.hpp"
 #include "texel_decode.hpp"
+#include "bc1_decode.hpp"
 
 constexpr uint32_t BIN = 16;               // bin edge in pixels: 256 lanes, one per pixel
 constexpr uint32_t LIST_CAP = 2048;        // longest bin list sorted in LDS
@@ -110,6 +115,9 @@ struct RsRasterTex {
     uint32_t n_tex;
     pbr_texture2d table[PBR_RASTER_MAX_TEXTURES];
 };
+// the same arguments for a table that holds a BC1-resident texture (PBR_TEX_BC1_BLOCKS): a kernel of its own, picked on the host,
+// so a table of decoded textures keeps the kernel it had
+struct RsRasterTexBc1 : RsRasterTex {};
 // the one element of a non-empty `Tex` pack
 template <typename T> __device__ __forceinline__ const T& only(const T& t) { return t; }
 
@@ -420,11 +428,61 @@ __device__ __forceinline__ void texel(const pbr_texture2d& t, const float* dec, 
         out[2] = tab[(w >> (16u - rs)) & 255u];
     }
 }
-// bilinear on level l (wrap addressing)
+// a palette entry (bc1_decode.hpp: R | G << 8 | B << 16) of a BC1-resident texture, decoded as texel<NC> decodes the stored texel
 template <int NC>
+__device__ __forceinline__ void texel_rgba(uint32_t fmt, const float* dec, uint32_t w, float* out) {
+    const float* tab = fmt == PBR_TEX_B8G8R8A8_UNORM_SRGB ? dec + 256 : dec;
+    out[0] = tab[w & 255u];
+    if (NC == 3) {
+        const bool r8 = fmt == PBR_TEX_R8_UNORM;
+        out[1] = r8 ? 0.0f : tab[(w >> 8) & 255u];
+        out[2] = r8 ? 0.0f : tab[(w >> 16) & 255u];
+    }
+}
+// the four taps of a BC1-resident level of bw x bh blocks at `blocks`: they lie in 1, 2 or 4 blocks; each distinct block is read
+// once (8 bytes) and its palette built once
+template <int NC>
+__device__ __forceinline__ void taps_bc1(const uint2* blocks, uint32_t bw, uint32_t fmt, const float* dec, uint32_t x0, uint32_t y0,
+                                         uint32_t x1, uint32_t y1, float* c00, float* c10, float* c01, float* c11) {
+    const uint32_t bx0 = x0 >> 2, by0 = y0 >> 2, bx1 = x1 >> 2, by1 = y1 >> 2;
+    const bool two_x = bx1 != bx0, two_y = by1 != by0;
+    uint32_t pal[4], bits;
+    auto fetch = [&](uint32_t bx, uint32_t by) {
+        const uint2 b = blocks[(size_t)by * bw + bx];
+        bc1_palette(b.x, pal);
+        bits = b.y;
+    };
+    auto pick = [&](uint32_t x, uint32_t y) { return bc1_texel(pal, bits, x & 3u, y & 3u); };
+    // every tap from the block of (x0, y0) first; a tap in another block is replaced when that block has been read
+    fetch(bx0, by0);
+    uint32_t w00 = pick(x0, y0), w10 = pick(x1, y0), w01 = pick(x0, y1), w11 = pick(x1, y1);
+    if (two_x) {
+        fetch(bx1, by0);
+        w10 = pick(x1, y0);
+        w11 = pick(x1, y1);
+    }
+    if (two_y) {
+        fetch(bx0, by1);
+        w01 = pick(x0, y1);
+        w11 = pick(x1, y1);
+        if (two_x) {
+            fetch(bx1, by1);
+            w11 = pick(x1, y1);
+        }
+    }
+    texel_rgba<NC>(fmt, dec, w00, c00);
+    texel_rgba<NC>(fmt, dec, w10, c10);
+    texel_rgba<NC>(fmt, dec, w01, c01);
+    texel_rgba<NC>(fmt, dec, w11, c11);
+}
+// bilinear on level l (wrap addressing).  BC1: the table may hold BC1-resident textures (the taps come from their blocks; the
+// coordinates, the decode tables and the lerps are the same)
+template <int NC, bool BC1>
 __device__ __forceinline__ void bilinear(const pbr_texture2d& t, const float* dec, uint32_t l, float u, float v, float* out) {
-    size_t off = 0;
-    for (uint32_t i = 0; i < l; i++) off += (size_t)(t.width >> i) * (t.height >> i);
+    const bool blk = BC1 && (t.format & PBR_TEX_BC1_BLOCKS) != 0;
+    size_t off = 0;                        // the level's first texel, or its first block
+    for (uint32_t i = 0; i < l; i++)
+        off += blk ? (size_t)bc1_blocks(t.width >> i) * bc1_blocks(t.height >> i) : (size_t)(t.width >> i) * (t.height >> i);
     const uint32_t wl = t.width >> l, hl = t.height >> l;
     const float x = u * (float)wl - 0.5f, y = v * (float)hl - 0.5f;
     const float flx = floorf(x), fly = floorf(y);
@@ -432,14 +490,18 @@ __device__ __forceinline__ void bilinear(const pbr_texture2d& t, const float* de
     const uint32_t x0 = wrap_texel(flx, wl), y0 = wrap_texel(fly, hl);
     const uint32_t x1 = x0 + 1u == wl ? 0u : x0 + 1u, y1 = y0 + 1u == hl ? 0u : y0 + 1u;
     float c00[NC], c10[NC], c01[NC], c11[NC];
-    texel<NC>(t, dec, off + (size_t)y0 * wl + x0, c00);
-    texel<NC>(t, dec, off + (size_t)y0 * wl + x1, c10);
-    texel<NC>(t, dec, off + (size_t)y1 * wl + x0, c01);
-    texel<NC>(t, dec, off + (size_t)y1 * wl + x1, c11);
+    if (blk) {
+        taps_bc1<NC>(static_cast<const uint2*>(t.texels) + off, bc1_blocks(wl), t.format & 0xffu, dec, x0, y0, x1, y1, c00, c10, c01, c11);
+    } else {
+        texel<NC>(t, dec, off + (size_t)y0 * wl + x0, c00);
+        texel<NC>(t, dec, off + (size_t)y0 * wl + x1, c10);
+        texel<NC>(t, dec, off + (size_t)y1 * wl + x0, c01);
+        texel<NC>(t, dec, off + (size_t)y1 * wl + x1, c11);
+    }
     for (int c = 0; c < NC; c++) out[c] = tex_lerp(tex_lerp(c00[c], c10[c], fx), tex_lerp(c01[c], c11[c], fx), fy);
 }
 // Sample(SamplerLinearWrap, uv) with the quad's uv differences (ddx, ddy): LOD, then trilinear
-template <int NC>
+template <int NC, bool BC1>
 __device__ __forceinline__ void sample(const pbr_texture2d& t, const float* dec, float u, float v, float dxu, float dxv, float dyu,
                                        float dyv, float* out) {
     const float fw = (float)t.width, fh = (float)t.height;
@@ -449,15 +511,16 @@ __device__ __forceinline__ void sample(const pbr_texture2d& t, const float* dec,
     lam = fminf(fmaxf(lam, 0.0f), (float)(t.mip_levels - 1u));
     const float fl = floorf(lam), f = lam - fl;
     const uint32_t l = (uint32_t)fl;
-    bilinear<NC>(t, dec, l, u, v, out);
+    bilinear<NC, BC1>(t, dec, l, u, v, out);
     if (f != 0.0f) {                       // (a level with weight 0 does not contribute: tex_lerp)
         float hi[NC];
-        bilinear<NC>(t, dec, min(l + 1u, t.mip_levels - 1u), u, v, hi);
+        bilinear<NC, BC1>(t, dec, min(l + 1u, t.mip_levels - 1u), u, v, hi);
         for (int c = 0; c < NC; c++) out[c] = tex_lerp(out[c], hi[c], f);
     }
 }
 
-// Tex: empty (constant materials) or RsRasterTex (textured: the resolve samples the draw's maps)
+// Tex: empty (constant materials), RsRasterTex (textured: the resolve samples the draw's maps) or RsRasterTexBc1 (textured, and
+// some of the textures are BC1-resident)
 template <typename... Tex>
 __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* __restrict__ draws, const uint32_t* __restrict__ hdr,
                                                    const RsTri* __restrict__ tris, const RsAttr* __restrict__ attrs,
@@ -466,6 +529,7 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
                                                    uint32_t* __restrict__ C, float* __restrict__ depth, uint8_t* __restrict__ stencil,
                                                    Tex... tex) {
     constexpr bool TEX = sizeof...(Tex) != 0;
+    constexpr bool BC1 = (std::is_same<Tex, RsRasterTexBc1>::value || ...);
     __shared__ uint32_t list[LIST_CAP];
     const uint32_t tid = threadIdx.x;
     const uint32_t lx = blockIdx.x * BIN + (tid & (BIN - 1)), ly = blockIdx.y * BIN + tid / BIN;
@@ -594,7 +658,7 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
                 const float dxu = u10 - u00, dxv = v10 - v00, dyu = u01 - u00, dyv = v01 - v00;
                 float s[3];
                 if (m.albedo != PBR_NO_MAP) {   // albedo = decode_gamma(sample.rgb): the encode applies decode_gamma
-                    sample<3>(tl.tex[m.albedo], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    sample<3, BC1>(tl.tex[m.albedo], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
                     a.x = s[0]; a.y = s[1]; a.z = s[2];
                 }
                 if (m.normal != PBR_NO_MAP) {   // sample_normal_texture; the encode's normalize is its normalize
@@ -603,22 +667,22 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
                                                       ((l0 * ta.t[1] + l1 * ta.t[4]) + l2 * ta.t[7]) * inv,
                                                       ((l0 * ta.t[2] + l1 * ta.t[5]) + l2 * ta.t[8]) * inv));
                     const V3 bt = cross3(n, tg);
-                    sample<3>(tl.tex[m.normal], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    sample<3, BC1>(tl.tex[m.normal], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
                     const float tx_ = s[0] * 2.0f - 1.0f, ty_ = s[1] * 2.0f - 1.0f, tz_ = s[2] * 2.0f - 1.0f;
                     b.x = (tx_ * tg.x + ty_ * bt.x) + tz_ * n.x;
                     b.y = (tx_ * tg.y + ty_ * bt.y) + tz_ * n.y;
                     b.z = (tx_ * tg.z + ty_ * bt.z) + tz_ * n.z;
                 }
                 if (m.roughness != PBR_NO_MAP) {
-                    sample<1>(tl.tex[m.roughness], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    sample<1, BC1>(tl.tex[m.roughness], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
                     b.w = s[0];
                 }
                 if (m.metallic != PBR_NO_MAP) {
-                    sample<1>(tl.tex[m.metallic], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    sample<1, BC1>(tl.tex[m.metallic], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
                     c.x = s[0];
                 }
                 if (m.ao != PBR_NO_MAP) {
-                    sample<1>(tl.tex[m.ao], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
+                    sample<1, BC1>(tl.tex[m.ao], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
                     c.y = s[0];
                 }
             }
@@ -636,11 +700,12 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
     }
 }
 
-// the checks and launches of both entry points; tx: null for pbr_gbuffer_raster, else the validated texture table
+// the checks and launches of both entry points; tx: null for pbr_gbuffer_raster, else the validated texture table (bc1: it holds
+// a BC1-resident texture)
 pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_vertex* vertices, uint32_t n_vertices,
                   const uint32_t* indices, uint32_t n_indices, const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
                   uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch, void* scratch,
-                  size_t scratch_bytes, const RsRasterTex* tx) {
+                  size_t scratch_bytes, const RsRasterTex* tx, bool bc1 = false) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, g && tile && vertices && indices && draws && A && B && C && depth && stencil && scratch,
                 "pbr_gbuffer_raster: null pointer");
@@ -700,10 +765,15 @@ pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const
     hipLaunchKernelGGL(k_rs_fill, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, hdr, tris, offset, cursor, pool);
     if (pbr_status st = pbr::launched(ctx, "k_rs_fill")) return st;
     if (tx) {
-        RsRasterTex rt = *tx;
+        RsRasterTexBc1 rt;
+        static_cast<RsRasterTex&>(rt) = *tx;
         rt.tex = texattrs;
-        hipLaunchKernelGGL(k_rs_raster<RsRasterTex>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs, count,
-                           offset, pool, A, B, C, depth, stencil, rt);
+        if (bc1)
+            hipLaunchKernelGGL(k_rs_raster<RsRasterTexBc1>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs,
+                               count, offset, pool, A, B, C, depth, stencil, rt);
+        else
+            hipLaunchKernelGGL(k_rs_raster<RsRasterTex>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs, count,
+                               offset, pool, A, B, C, depth, stencil, static_cast<const RsRasterTex&>(rt));
     } else {
         hipLaunchKernelGGL(k_rs_raster<>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs, count, offset, pool,
                            A, B, C, depth, stencil);
@@ -716,6 +786,55 @@ uint32_t max_mip_levels(uint32_t w, uint32_t h) {
     uint32_t m = min(w, h), n = 0;
     while (m) { n++; m >>= 1; }
     return n;
+}
+bool stored_format(uint32_t f) {
+    return f == PBR_TEX_R8_UNORM || f == PBR_TEX_R8G8B8A8_UNORM || f == PBR_TEX_B8G8R8A8_UNORM || f == PBR_TEX_B8G8R8A8_UNORM_SRGB;
+}
+bool chain_shape_ok(uint32_t w, uint32_t h, uint32_t mips) {
+    return w && h && w <= PBR_TEX_MAX_SIZE && h <= PBR_TEX_MAX_SIZE && mips && mips <= max_mip_levels(w, h);
+}
+
+// ---- pbr_bc1_decode: every level of a chain in one launch ----
+constexpr uint32_t BC1_MAX_LEVELS = 15;    // floor(log2(PBR_TEX_MAX_SIZE)) + 1
+struct Bc1Levels {
+    uint32_t first_block[BC1_MAX_LEVELS + 1];   // the level's first block in the chain; [mips] = the chain's blocks
+    uint64_t first_texel[BC1_MAX_LEVELS];       // the level's first texel in the decoded chain
+    uint32_t width, height, mips;
+    uint32_t texel_bytes;                       // 4, or 1 (R8)
+    uint32_t bgra;                              // B8G8R8A8[_SRGB]: red and blue swapped in the stored texel
+};
+// lane = block: its palette once, then its rows.  A row that lies whole inside the level and is aligned to its own size is one
+// vector store (16 bytes, R8: 4); the rows of edge blocks of sizes that are no multiple of 4, and unaligned ones, go texel by texel.
+__global__ __launch_bounds__(256) void k_bc1_decode(const uint2* __restrict__ blocks, Bc1Levels L, uint8_t* __restrict__ out) {
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (b >= L.first_block[L.mips]) return;
+    uint32_t l = 0;
+    while (l + 1u < L.mips && b >= L.first_block[l + 1u]) l++;
+    const uint32_t wl = L.width >> l, hl = L.height >> l, bw = bc1_blocks(wl);
+    const uint32_t k = b - L.first_block[l], bx = k % bw, by = k / bw;
+    const uint2 blk = blocks[b];
+    uint32_t pal[4];
+    bc1_palette(blk.x, pal);
+    const uint32_t x0 = 4u * bx, nx = min(4u, wl - x0);
+    for (uint32_t y = 0; y < 4u && 4u * by + y < hl; y++) {
+        uint32_t px[4];
+        for (uint32_t x = 0; x < 4u; x++) px[x] = bc1_texel(pal, blk.y, x, y);
+        uint8_t* row = out + (L.first_texel[l] + (uint64_t)(4u * by + y) * wl + x0) * L.texel_bytes;
+        if (L.texel_bytes == 4u) {
+            for (uint32_t x = 0; x < 4u; x++) px[x] = bc1_stored(px[x], L.bgra != 0);
+            if (nx == 4u && ((uintptr_t)row & 15u) == 0) {
+                *reinterpret_cast<uint4*>(row) = make_uint4(px[0], px[1], px[2], px[3]);
+            } else {
+                for (uint32_t x = 0; x < nx; x++) reinterpret_cast<uint32_t*>(row)[x] = px[x];
+            }
+        } else {
+            if (nx == 4u && ((uintptr_t)row & 3u) == 0) {
+                *reinterpret_cast<uint32_t*>(row) = (px[0] & 255u) | ((px[1] & 255u) << 8) | ((px[2] & 255u) << 16) | (px[3] << 24);
+            } else {
+                for (uint32_t x = 0; x < nx; x++) row[x] = (uint8_t)px[x];
+            }
+        }
+    }
 }
 
 }  // namespace
@@ -764,21 +883,65 @@ pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const 
     tx.tex = nullptr;
     tx.n_tex = n_textures;
     for (uint32_t i = 0; i < PBR_RASTER_MAX_TEXTURES; i++) tx.table[i] = pbr_texture2d{nullptr, 0, 0, 0, 0};
+    bool any_bc1 = false;
     for (uint32_t i = 0; i < n_textures; i++) {
         const pbr_texture2d& t = textures[i];
+        const bool bc1 = (t.format & PBR_TEX_BC1_BLOCKS) != 0;
         const bool r8 = t.format == PBR_TEX_R8_UNORM;
-        PBR_REQUIRE(ctx, r8 || t.format == PBR_TEX_R8G8B8A8_UNORM || t.format == PBR_TEX_B8G8R8A8_UNORM ||
-                    t.format == PBR_TEX_B8G8R8A8_UNORM_SRGB, "pbr_gbuffer_raster_textured: unknown texture format");
+        PBR_REQUIRE(ctx, (t.format & ~(0xffu | PBR_TEX_BC1_BLOCKS)) == 0 && stored_format(t.format & 0xffu),
+                    "pbr_gbuffer_raster_textured: unknown texture format");
         PBR_REQUIRE(ctx, t.width && t.height && t.width <= PBR_TEX_MAX_SIZE && t.height <= PBR_TEX_MAX_SIZE,
                     "pbr_gbuffer_raster_textured: texture size zero or above PBR_TEX_MAX_SIZE");
         PBR_REQUIRE(ctx, t.mip_levels && t.mip_levels <= max_mip_levels(t.width, t.height),
                     "pbr_gbuffer_raster_textured: mip_levels 0 or above floor(log2(min(w, h))) + 1");
-        PBR_REQUIRE(ctx, t.texels && (r8 || (pbr::addr(t.texels) & 3u) == 0),
-                    "pbr_gbuffer_raster_textured: texels null or not aligned to the texel size");
+        PBR_REQUIRE(ctx, t.texels && (r8 || (pbr::addr(t.texels) & (bc1 ? 7u : 3u)) == 0),
+                    "pbr_gbuffer_raster_textured: texels null or not aligned to the texel size (BC1 blocks: 8 bytes)");
+        any_bc1 |= bc1;
         tx.table[i] = t;
     }
     return raster(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth, stencil,
-                  pitch, scratch, scratch_bytes, &tx);
+                  pitch, scratch, scratch_bytes, &tx, any_bc1);
+}
+
+size_t pbr_texture2d_bytes(uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t format) {
+    if ((format & ~(0xffu | PBR_TEX_BC1_BLOCKS)) != 0 || !stored_format(format & 0xffu) || !chain_shape_ok(width, height, mip_levels))
+        return 0;
+    const size_t texel = (format & 0xffu) == PBR_TEX_R8_UNORM ? 1 : 4;
+    size_t bytes = 0;
+    for (uint32_t l = 0; l < mip_levels; l++)
+        bytes += (format & PBR_TEX_BC1_BLOCKS) ? (size_t)bc1_blocks(width >> l) * bc1_blocks(height >> l) * 8
+                                               : (size_t)(width >> l) * (height >> l) * texel;
+    return bytes;
+}
+
+pbr_status pbr_bc1_decode(pbr_ctx* ctx, const void* blocks, uint32_t width, uint32_t height, uint32_t mip_levels,
+                          uint32_t stored, void* out) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, blocks && out, "pbr_bc1_decode: null pointer");
+    PBR_REQUIRE(ctx, stored_format(stored), "pbr_bc1_decode: unknown stored format");
+    PBR_REQUIRE(ctx, width && height && width <= PBR_TEX_MAX_SIZE && height <= PBR_TEX_MAX_SIZE,
+                "pbr_bc1_decode: texture size zero or above PBR_TEX_MAX_SIZE");
+    PBR_REQUIRE(ctx, mip_levels && mip_levels <= max_mip_levels(width, height),
+                "pbr_bc1_decode: mip_levels 0 or above floor(log2(min(w, h))) + 1");
+    PBR_REQUIRE(ctx, (pbr::addr(blocks) & 7u) == 0 && (stored == PBR_TEX_R8_UNORM || (pbr::addr(out) & 3u) == 0),
+                "pbr_bc1_decode: blocks not 8-byte aligned, or out not aligned to the texel size");
+    static_assert((1u << (BC1_MAX_LEVELS - 1)) == PBR_TEX_MAX_SIZE, "levels of the largest chain");
+    Bc1Levels L;
+    L.width = width; L.height = height; L.mips = mip_levels;
+    L.texel_bytes = stored == PBR_TEX_R8_UNORM ? 1u : 4u;
+    L.bgra = stored == PBR_TEX_B8G8R8A8_UNORM || stored == PBR_TEX_B8G8R8A8_UNORM_SRGB;
+    uint64_t nb = 0, nt = 0;
+    for (uint32_t l = 0; l <= BC1_MAX_LEVELS; l++) {
+        L.first_block[l] = (uint32_t)nb;          // (the largest chain holds 4096^2 * 4 / 3 blocks: below 2^32)
+        if (l < BC1_MAX_LEVELS) L.first_texel[l] = nt;
+        if (l < mip_levels) {
+            nb += (uint64_t)bc1_blocks(width >> l) * bc1_blocks(height >> l);
+            nt += (uint64_t)(width >> l) * (height >> l);
+        }
+    }
+    hipLaunchKernelGGL(k_bc1_decode, dim3((uint32_t)((nb + 255u) / 256u)), dim3(256), 0, ctx->stream, static_cast<const uint2*>(blocks), L,
+                       static_cast<uint8_t*>(out));
+    return pbr::launched(ctx, "k_bc1_decode");
 }
 
 }  // extern "C"

@@ -51,6 +51,7 @@ SIGNATURES = {
     "pbrh_dry_run_execution_order": (_int, [_u32, _u32, C.c_char_p, C.c_size_t]),
     "pbrh_probe_binding": (_int, [C.c_char_p, _int, C.c_char_p, _int]),
     "pbrh_parse_hdr": (_int, [_vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_parse_texture_file": (_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None
@@ -82,6 +83,23 @@ def pack_lights(lights):
     n = len(lights)
     return np.ascontiguousarray(np.concatenate([lights["Position"], lights["Color"], lights["Radius"].reshape(n, 1),
                                                 lights["Intensity"].reshape(n, 1)], axis=1).astype(np.float32))
+
+
+def parse_texture_file(data):
+    """One of the reference's serialized textures (the bytes of a texture asset's _data.bin) -> (blocks, width, height, mip_levels,
+    format): the chain's BC1 blocks (uint8) and its description with format = the stored format | structs.TEX_BC1_BLOCKS, as
+    PbrContext.upload_texture and HostRenderer.set_textured_meshes take them.  No decode happens on the CPU."""
+    from .structs import Texture2D
+    lib = load()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    err = C.create_string_buffer(256)
+    t = Texture2D()
+    if lib.pbrh_parse_texture_file(buf.ctypes.data, buf.size, C.addressof(t), None, 0, err, 256) != 0:
+        raise HostError(err.value.decode())
+    blocks = np.zeros(buf.size - 16, dtype=np.uint8)
+    if lib.pbrh_parse_texture_file(buf.ctypes.data, buf.size, C.addressof(t), blocks.ctypes.data, blocks.size, err, 256) != 0:
+        raise HostError(err.value.decode())
+    return blocks, t.width, t.height, t.mip_levels, t.format
 
 
 class HostRenderer:
@@ -135,8 +153,9 @@ class HostRenderer:
 
     def set_textured_meshes(self, vertices, indices, draws, maps, textures):
         """set_meshes plus the draws' maps (structs.DRAW_MAPS_DTYPE, one per draw) and their textures: (chain, width, height,
-        mip_levels, format) with the chain's host bytes in the reference's layout (scene.pack_chain).  GBufferPass uploads the chains
-        once and rasterizes through pbr_gbuffer_raster_textured."""
+        mip_levels, format) with the chain's host bytes in the reference's layout (scene.pack_chain) or, with structs.TEX_BC1_BLOCKS
+        in the format, its BC1 blocks (parse_texture_file), which stay BC1 on the device.  GBufferPass uploads the chains once and
+        rasterizes through pbr_gbuffer_raster_textured."""
         from .structs import DRAW_DTYPE, DRAW_MAPS_DTYPE, VERTEX_DTYPE, Texture2D
         v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
         i = np.ascontiguousarray(indices, dtype=np.uint32)

@@ -110,7 +110,7 @@ void GBufferPass::UploadMeshes(FGContext* context, MeshSource& meshes, uint32 w,
     mTextureTable.clear();
     if (meshes.Textured()) {
         upload(mMaps, meshes.Maps.data(), meshes.Maps.size() * sizeof(pbr_draw_maps), sizeof(pbr_draw_maps));
-        for (const TextureChain& t : meshes.Textures) {
+        for (const TextureChain& t : meshes.Textures) {   // one allocation per chain: BC1 blocks land 8-byte aligned
             mTextures.emplace_back();
             upload(mTextures.back(), t.Texels.data(), t.Texels.size(), 1);
             mTextureTable.push_back(pbr_texture2d{mTextures.back()->DevicePtr(), t.Width, t.Height, t.MipLevels, t.Format});

@@ -2,6 +2,7 @@
 #include "pbr_host.h"
 #include "HdrImage.h"
 #include "SceneFile.h"
+#include "TextureFile.h"
 
 #include <algorithm>
 #include <chrono>
@@ -168,6 +169,24 @@ int pbrh_load_scene_lights(pbrh_renderer* r, const char* scene_json_path) {
 // CPU only: the "mSceneLight" records of a scene file held in memory, as the 8-float records pbrh_set_lights takes
 // (translation, colour, radius, intensity), in file order.  Returns the count (may exceed max_lights), -1 + reason on
 // malformed input or on a light whose object carries a rotation / scale (those go through pbrh_load_scene_lights).
+int pbrh_parse_texture_file(const uint8_t* file, size_t bytes, void* texture, void* blocks, size_t blocks_bytes, char* err, size_t err_len) {
+    try {
+        if (!texture) throw HipException("texture file: null descriptor");
+        pbr_texture2d t = ParseTextureFile(file, bytes);
+        const size_t n = pbr_texture2d_bytes(t.width, t.height, t.mip_levels, t.format);
+        if (blocks) {
+            if (blocks_bytes < n) throw HipException("texture file: output buffer too small");
+            std::memcpy(blocks, t.texels, n);
+        }
+        t.texels = blocks;
+        std::memcpy(texture, &t, sizeof(t));
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
+        return -1;
+    }
+}
+
 int pbrh_parse_scene_lights(const char* json, size_t bytes, float* lights, int max_lights, char* err, size_t err_len) {
     try {
         const std::vector<SceneLightRecord> recs = ParseSceneLights(json, bytes);
@@ -281,12 +300,9 @@ int pbrh_set_textured_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_
         std::vector<TextureChain> tex(n_textures);
         for (uint32_t i = 0; i < n_textures; i++) {   // the chain's size from its descriptor (pbr_gbuffer_raster_textured checks the rest)
             const pbr_texture2d& t = textures[i];
-            const size_t texel = t.format == PBR_TEX_R8_UNORM ? 1 : 4;
-            if (!t.texels || !t.width || !t.height || t.width > PBR_TEX_MAX_SIZE || t.height > PBR_TEX_MAX_SIZE || !t.mip_levels ||
-                (std::min(t.width, t.height) >> (t.mip_levels - 1)) == 0)
-                throw HipException("pbrh_set_textured_meshes: bad texture descriptor");
-            size_t bytes = 0;
-            for (uint32_t l = 0; l < t.mip_levels; l++) bytes += (size_t)(t.width >> l) * (t.height >> l) * texel;
+            // decoded texels or, with PBR_TEX_BC1_BLOCKS, BC1 blocks: either layout's size comes from the library
+            const size_t bytes = pbr_texture2d_bytes(t.width, t.height, t.mip_levels, t.format);
+            if (!t.texels || !bytes) throw HipException("pbrh_set_textured_meshes: bad texture descriptor");
             const uint8_t* src = static_cast<const uint8_t*>(t.texels);
             tex[i].Texels.assign(src, src + bytes);
             tex[i].Width = t.width; tex[i].Height = t.height; tex[i].MipLevels = t.mip_levels; tex[i].Format = t.format;

@@ -47,6 +47,15 @@ int pbrh_set_skybox(pbrh_renderer* r, const float* cube_mip0, uint32_t size);
 int pbrh_load_skybox(pbrh_renderer* r, const char* dir);
 /* CPU only: parse one .hdr file held in memory (header + flat / run-length scanlines) into RGBE texels */
 int pbrh_parse_hdr(const uint8_t* file, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgbe, size_t rgbe_bytes, char* err, size_t err_len);
+/* CPU only, stateless: one of the reference's serialized 2D textures (a texture asset's _data.bin) held in memory: TextureInfo (uint16
+ * width, height, depth, mips; uint8 DXGI format; 3 pad bytes), a uint32 payload byte count at offset 12, the payload (the chain
+ * as BC1 blocks) at offset 16.  *texture (a pbr_texture2d, 24 B) = the description with format = the stored format |
+ * PBR_TEX_BC1_BLOCKS and texels = blocks; the payload is copied to blocks (blocks_bytes >= pbr_texture2d_bytes of the
+ * description; blocks NULL: the description only, texels NULL).  What it fills goes to pbr_gbuffer_raster_textured /
+ * pbrh_set_textured_meshes as it is, or through pbr_bc1_decode.  Returns 0, or -1 + reason in err with nothing written: a
+ * truncated file, a byte count that disagrees with pbr_texture2d_bytes or the file's size, depth != 1, an unknown format, a
+ * buffer too small. */
+int pbrh_parse_texture_file(const uint8_t* file, size_t bytes, void* texture, void* blocks, size_t blocks_bytes, char* err, size_t err_len);
 /* n lights: position[3], color[3], radius, intensity (8 floats each) */
 int pbrh_set_lights(pbrh_renderer* r, const float* lights, int n);
 /* the "mSceneLight" records of a reference scene file (Asset/Scene/main.json: Scene.h:192, ReflectionDef.h:119-149) replace

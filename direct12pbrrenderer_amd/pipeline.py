@@ -345,7 +345,7 @@ class DeferredFrame:
         uploaded once, and every render() rasterizes them (pbr_gbuffer_raster, draws in array order) into the frame's own G-buffer
         planes of the shaded rectangle S before the cluster, sky and shade passes (until upload_gbuffer replaces them).
         maps (structs.DRAW_MAPS_DTYPE, one per draw) and textures (the (device tensor, structs.Texture2D) pairs of
-        PbrContext.upload_texture, which the frame holds on to): the draws' texture maps, rasterized by
+        PbrContext.upload_texture or bc1_decode, BC1-resident ones included, which the frame holds on to): the draws' texture maps, rasterized by
         pbr_gbuffer_raster_textured when any draw has one.  Without them, or with every map NO_MAP, the call is the
         constant-material one."""
         s, ctx = self.spec, self.ctx

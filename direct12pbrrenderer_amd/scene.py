@@ -437,3 +437,19 @@ def add_textured_models(ms, fx):
             ms.add(len(ms._ranges) - 1, fx[f"{n}_world"], albedo=tuple(mat[:3]), emission=mat[3], roughness=mat[4], metallic=mat[5],
                    maps=maps)
     return textures, names
+
+
+def bc1_texture_table(fxb):
+    """The textured models' maps as BC1 chains from the fixture written by tests/golden/make_textured_models_bc1.py (fxb: the
+    loaded npz), in add_textured_models' table order (model by model, the maps in `maps` order), so that the draws' map indices of
+    add_textured_models point into it.  Returns dicts of the kept chain (from the 128 x 128 level down): blocks (uint8, the BC1
+    payload: PbrContext.upload_texture(blocks, width, height, mips, format | structs.TEX_BC1_BLOCKS)), width, height, mips and
+    the stored format."""
+    table = []
+    for n in (str(x) for x in fxb["name"]):
+        for k in (str(x) for x in fxb["maps"]):
+            if f"{n}_{k}_blocks" not in fxb.files:
+                continue
+            _, _, _, fmt, w, h, mips = (int(x) for x in fxb[f"{n}_{k}_info"])
+            table.append({"blocks": fxb[f"{n}_{k}_blocks"], "width": w, "height": h, "mips": mips, "format": fmt})
+    return table

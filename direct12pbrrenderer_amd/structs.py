@@ -121,7 +121,7 @@ RASTER_MAX_SIZE = 8192                                # PBR_RASTER_MAX_SIZE
 
 class Texture2D(C.Structure):
     """pbr_texture2d: a device mip chain in the reference's layout (level i (width >> i) x (height >> i), levels concatenated)
-    and its DXGI format number (24 B)."""
+    and its DXGI format number (24 B); with TEX_BC1_BLOCKS in the format, the chain as BC1 blocks (texture2d_bytes)."""
     _fields_ = [("texels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("mip_levels", C.c_uint32),
                 ("format", C.c_uint32)]
 
@@ -139,6 +139,21 @@ TEX_MAX_SIZE = 16384                                  # PBR_TEX_MAX_SIZE
 TEX_R8G8B8A8_UNORM, TEX_B8G8R8A8_UNORM, TEX_B8G8R8A8_UNORM_SRGB, TEX_R8_UNORM = 28, 87, 91, 61
 TEX_FORMATS = {TEX_R8G8B8A8_UNORM: (4, False), TEX_B8G8R8A8_UNORM: (4, False), TEX_B8G8R8A8_UNORM_SRGB: (4, True),
                TEX_R8_UNORM: (1, False)}
+TEX_BC1_BLOCKS = 0x100                                # PBR_TEX_BC1_BLOCKS: ORed into a format, the chain is held as BC1 blocks
+
+
+def texture2d_bytes(width, height, mip_levels, fmt):
+    """pbr_texture2d_bytes: the bytes of a whole chain, decoded (level i (width >> i) x (height >> i) texels) or, with
+    TEX_BC1_BLOCKS in fmt, BC1 (level i max(1, ((width >> i) + 3) // 4) x max(1, ((height >> i) + 3) // 4) blocks of 8 bytes);
+    0 for a description the library refuses."""
+    width, height, mip_levels, fmt = int(width), int(height), int(mip_levels), int(fmt)
+    if fmt & ~(0xFF | TEX_BC1_BLOCKS) or (fmt & 0xFF) not in TEX_FORMATS:
+        return 0
+    if not (1 <= width <= TEX_MAX_SIZE and 1 <= height <= TEX_MAX_SIZE and 1 <= mip_levels <= min(width, height).bit_length()):
+        return 0
+    if fmt & TEX_BC1_BLOCKS:
+        return sum(max(1, ((width >> l) + 3) // 4) * max(1, ((height >> l) + 3) // 4) * 8 for l in range(mip_levels))
+    return sum((width >> l) * (height >> l) for l in range(mip_levels)) * TEX_FORMATS[fmt][0]
 
 
 class CubeF32(C.Structure):

@@ -350,12 +350,36 @@ pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile*
 #define PBR_TEX_B8G8R8A8_UNORM_SRGB  91u
 #define PBR_TEX_R8_UNORM             61u
 #define PBR_TEX_MAX_SIZE             16384u
+/* BC1-resident chains: PBR_TEX_BC1_BLOCKS ORed into `format` says that `texels` holds the chain as BC1 blocks, the payload of the
+ * reference's *_data.bin texture files byte for byte (what TextureDecompressInternal, TextureCompression.cpp, decodes at load
+ * time), and format & 0xff is the stored format the reference would decode it into.  Level i is max(1, ((width >> i) + 3) / 4) x
+ * max(1, ((height >> i) + 3) / 4) blocks of 8 bytes, row-major within a level, levels concatenated from level 0; texel (x, y) of a
+ * level is texel (x & 3, y & 3) of block (x >> 2, y >> 2), so a level smaller than a block uses the block's top-left texels.
+ * The BC1 decode rule (the format's public definition), pinned: a block is two little-endian uint16 endpoints c0, c1 (RGB565: red
+ * in bits 15-11, green 10-5, blue 4-0) and 16 2-bit indices, texel (x, y) in bits 2 (4 y + x) + 1 .. 2 (4 y + x) of the little-
+ * endian uint32 that follows.  Endpoints expand to 8 bits by bit replication ((c5 << 3) | (c5 >> 2), (c6 << 2) | (c6 >> 4)).
+ * c0 > c1 (as uint16): index 0 = c0, 1 = c1, 2 = (2 c0 + c1 + 1) / 3, 3 = (c0 + 2 c1 + 1) / 3 per channel (integer division), alpha
+ * 255.  Otherwise: 0 = c0, 1 = c1, 2 = (c0 + c1 + 1) / 2, alpha 255, and 3 = transparent black (0, 0, 0, 0).  Stored bytes per
+ * format: 28 R, G, B, A; 87 and 91 B, G, R, A; 61 R.  The decode applies or removes no sRGB curve: format 91's curve is the
+ * sampler's (below), as for a decoded chain. */
+#define PBR_TEX_BC1_BLOCKS           0x100u
 typedef struct pbr_texture2d {
-    const void* texels;            /* device; 4-byte aligned for the 4-byte formats */
+    const void* texels;            /* device; 4-byte aligned for the 4-byte formats; BC1 blocks: 8-byte aligned */
     uint32_t width, height;        /* 1 .. PBR_TEX_MAX_SIZE */
     uint32_t mip_levels;           /* 1 .. floor(log2(min(width, height))) + 1 */
-    uint32_t format;               /* PBR_TEX_* */
+    uint32_t format;               /* PBR_TEX_*, optionally | PBR_TEX_BC1_BLOCKS */
 } pbr_texture2d;
+/* Bytes of a whole chain of either kind (format with or without PBR_TEX_BC1_BLOCKS); 0 for a description pbr_gbuffer_raster_textured
+ * would refuse (a zero size or one above PBR_TEX_MAX_SIZE, mip_levels out of range, an unknown stored format, any other bit of format). */
+size_t pbr_texture2d_bytes(uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t format);
+/* The reference's load-time decode (TextureDecompressInternal) of a whole chain on the GPU: blocks (device, 8-byte aligned, the
+ * BC1 layout above) -> out (device, the uncompressed layout of pbr_texture2d in stored_format, pbr_texture2d_bytes(width, height,
+ * mip_levels, stored_format) bytes; 4-byte aligned for the 4-byte formats), by the rule pinned above.  One asynchronous launch on
+ * the context's stream for all levels, no allocation.  Refusals (PBR_ERR_INVALID, nothing enqueued): a null pointer, misaligned
+ * blocks or out, a zero size or one above PBR_TEX_MAX_SIZE, mip_levels 0 or above floor(log2(min(w, h))) + 1, stored_format not
+ * one of the four (PBR_TEX_BC1_BLOCKS included: the flag describes the input, not the output). */
+pbr_status pbr_bc1_decode(pbr_ctx* ctx, const void* blocks, uint32_t width, uint32_t height, uint32_t mip_levels,
+                          uint32_t stored_format, void* out);
 /* The Use*Map flags of ConstantBufferInstance (gbuffer.hlsl:43-47) as texture indices, one record per draw in an array parallel
  * to the pbr_draw array: PBR_NO_MAP takes the constant branch, any other value is an index into the call's texture table. */
 #define PBR_NO_MAP                   0xffffffffu
@@ -383,9 +407,15 @@ size_t pbr_gbuffer_raster_textured_min_scratch_bytes(uint32_t w, uint32_t h, uin
  * + ts.y b + ts.z n) with n = normalize(normal_ws), t = normalize(tangent_ws), b = cross(n, t), ts = sample.rgb * 2 - 1;
  * roughness, metallic, AO = sample.x.  Without one: the constant (AO 0), bit-identical to pbr_gbuffer_raster.
  * Guard on device data: a draw with a map index >= n_textures (other than PBR_NO_MAP) is dropped.
+ * The table may mix decoded and BC1-resident textures (PBR_TEX_BC1_BLOCKS).  A BC1-resident texture samples exactly as the chain
+ * pbr_bc1_decode produces from it (stored format = format & 0xff) would: the sampler reads each distinct block of a bilinear
+ * footprint once (one 8-byte load), builds its palette once, picks the taps by their indices and then runs the same decode
+ * tables, lerp order and LOD rule, so all five planes are bit-identical.  A table without a BC1 texture runs the kernel it ran
+ * before the flag existed.
  * Refusals (PBR_ERR_INVALID, nothing enqueued): those of pbr_gbuffer_raster; maps null or not 4-byte aligned; n_textures >
- * PBR_RASTER_MAX_TEXTURES, or textures null with n_textures > 0; a texture of another format, a zero size or one above
- * PBR_TEX_MAX_SIZE, mip_levels 0 or above floor(log2(min(w, h))) + 1, null or misaligned texels; scratch below
+ * PBR_RASTER_MAX_TEXTURES, or textures null with n_textures > 0; a texture of another format (with PBR_TEX_BC1_BLOCKS: another
+ * stored format), any other bit set in format, a zero size or one above PBR_TEX_MAX_SIZE, mip_levels 0 or above
+ * floor(log2(min(w, h))) + 1, null or misaligned texels (BC1 blocks: 8 bytes); scratch below
  * pbr_gbuffer_raster_textured_min_scratch_bytes. */
 pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
                                        const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
