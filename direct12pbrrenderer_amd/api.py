@@ -306,6 +306,60 @@ class PbrContext:
         self._check(self.lib.pbr_bc1_decode(self.h, _ptr(blocks), int(width), int(height), int(mip_levels), int(stored_format), _ptr(out)))
         return out, Texture2D(out.data_ptr(), int(width), int(height), int(mip_levels), int(stored_format))
 
+    def texture2d_gen_mips(self, chain, width, height, mip_levels, fmt):
+        """pbr_texture2d_gen_mips: levels 1 .. mip_levels - 1 of the uncompressed chain on the device (uint8 tensor of
+        structs.texture2d_bytes, level 0 filled), in place, by scene.mip_chain's rule."""
+        if isinstance(chain, tuple):
+            chain = chain[0]
+        nbytes = texture2d_bytes(width, height, mip_levels, int(fmt))
+        if nbytes == 0 or int(fmt) & TEX_BC1_BLOCKS:
+            raise PbrError(f"bad texture description: {width} x {height}, {mip_levels} levels, format {fmt}")
+        if chain.numel() * chain.element_size() != nbytes:
+            raise PbrError("texture2d_gen_mips: the chain tensor's size does not match the description")
+        self._check(self.lib.pbr_texture2d_gen_mips(self.h, _ptr(chain), int(width), int(height), int(mip_levels), int(fmt)))
+
+    def bc1_encode(self, texels, width, height, mip_levels, stored_format, out=None):
+        """pbr_bc1_encode, the mirror image of bc1_decode: an uncompressed chain on the device (uint8 tensor, or the (tensor,
+        Texture2D) pair of upload_texture) in stored_format -> its BC1 chain: (device tensor, structs.Texture2D with
+        stored_format | TEX_BC1_BLOCKS), as upload_texture returns a BC1-resident texture."""
+        if isinstance(texels, tuple):
+            texels = texels[0]
+        fmt = int(stored_format)
+        nbytes = texture2d_bytes(width, height, mip_levels, fmt | TEX_BC1_BLOCKS)
+        if nbytes == 0 or fmt & TEX_BC1_BLOCKS:
+            raise PbrError(f"bad texture description: {width} x {height}, {mip_levels} levels, stored format {stored_format}")
+        if texels.numel() * texels.element_size() != texture2d_bytes(width, height, mip_levels, fmt):
+            raise PbrError("bc1_encode: the texel tensor's size does not match the description")
+        out = out if out is not None else self.empty((nbytes,), torch.uint8)
+        if out.numel() * out.element_size() != nbytes:
+            raise PbrError("bc1_encode: the output tensor's size does not match the description")
+        self._check(self.lib.pbr_bc1_encode(self.h, _ptr(texels), int(width), int(height), int(mip_levels), fmt, _ptr(out)))
+        return out, Texture2D(out.data_ptr(), int(width), int(height), int(mip_levels), fmt | TEX_BC1_BLOCKS)
+
+    def import_texture(self, level0, fmt, mip_levels=None, bc1=False):
+        """The reference's ImportTexture from decoded pixels on: host level 0 (uint8 [h, w] for R8, [h, w, 4] for the 4-byte
+        formats, in the stored byte order of fmt) -> upload into a chain-sized buffer, texture2d_gen_mips (all levels by default),
+        and with bc1=True bc1_encode -> the (device tensor, structs.Texture2D) pair DeferredFrame.set_meshes(..., textures=) and
+        gbuffer_raster_textured take."""
+        fmt = int(fmt)
+        if fmt not in TEX_FORMATS:
+            raise PbrError(f"unknown texture format {fmt}")
+        lv0 = np.ascontiguousarray(level0, dtype=np.uint8)
+        want_dims = 2 if TEX_FORMATS[fmt][0] == 1 else 3
+        if lv0.ndim != want_dims or (want_dims == 3 and lv0.shape[2] != 4):
+            raise PbrError(f"import_texture: level 0 of format {fmt} is uint8 {'[h, w]' if want_dims == 2 else '[h, w, 4]'}, got {lv0.shape}")
+        h, w = lv0.shape[:2]
+        mips = min(w, h).bit_length() if mip_levels is None else int(mip_levels)
+        nbytes = texture2d_bytes(w, h, mips, fmt)
+        if nbytes == 0:
+            raise PbrError(f"bad texture description: {w} x {h}, {mips} levels, format {fmt}")
+        chain = self.empty((nbytes,), torch.uint8)
+        chain[:lv0.size].copy_(torch.from_numpy(lv0.reshape(-1)))
+        self.texture2d_gen_mips(chain, w, h, mips, fmt)
+        if bc1:
+            return self.bc1_encode(chain, w, h, mips, fmt)
+        return chain, Texture2D(chain.data_ptr(), w, h, mips, fmt)
+
     def gbuffer_raster_textured(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
                                 A, B, Cc, depth, stencil, pitch, scratch, maps, textures, scratch_bytes=None):
         """pbr_gbuffer_raster_textured: gbuffer_raster plus maps (device DRAW_MAPS_DTYPE records, one per draw) and textures (a

@@ -52,6 +52,8 @@ SIGNATURES = {
     "pbrh_probe_binding": (_int, [C.c_char_p, _int, C.c_char_p, _int]),
     "pbrh_parse_hdr": (_int, [_vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_parse_texture_file": (_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_write_texture_file": (C.c_long, [_vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_import_texture": (C.c_long, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None
@@ -100,6 +102,25 @@ def parse_texture_file(data):
     if lib.pbrh_parse_texture_file(buf.ctypes.data, buf.size, C.addressof(t), blocks.ctypes.data, blocks.size, err, 256) != 0:
         raise HostError(err.value.decode())
     return blocks, t.width, t.height, t.mip_levels, t.format
+
+
+def write_texture_file(blocks, width, height, mip_levels, fmt):
+    """The inverse of parse_texture_file: a BC1 chain (uint8 blocks) and its description (fmt = the stored format |
+    structs.TEX_BC1_BLOCKS) -> the bytes of the reference's serialized texture (TextureInfo, byte count, payload)."""
+    from .structs import Texture2D, texture2d_bytes
+    lib = load()
+    blocks = np.ascontiguousarray(blocks).view(np.uint8).reshape(-1)
+    err = C.create_string_buffer(256)
+    t = Texture2D(blocks.ctypes.data, int(width), int(height), int(mip_levels), int(fmt))
+    need = lib.pbrh_write_texture_file(C.addressof(t), None, 0, err, 256)
+    if need < 0:
+        raise HostError(err.value.decode())
+    if blocks.size != texture2d_bytes(width, height, mip_levels, fmt):
+        raise HostError(f"texture file: {blocks.size} block bytes, the description takes {need - 16}")
+    out = np.zeros(need, dtype=np.uint8)
+    if lib.pbrh_write_texture_file(C.addressof(t), out.ctypes.data, out.size, err, 256) != need:
+        raise HostError(err.value.decode())
+    return out.tobytes()
 
 
 class HostRenderer:
@@ -166,6 +187,23 @@ class HostRenderer:
                                                    for c, t in zip(chains, textures)])
         self._check(self.lib.pbrh_set_textured_meshes(self.h, v.ctypes.data, len(v), i.ctypes.data, len(i), d.ctypes.data, len(d),
                                                       m.ctypes.data, C.addressof(table), len(chains)))
+
+    def import_texture(self, level0, fmt, mip_levels=None):
+        """pbrh_import_texture: host level 0 (uint8 [h, w] for R8, [h, w, 4] otherwise; sizes multiples of 4) -> the bytes of the
+        reference's texture file holding its whole mip chain (all levels by default) as BC1 blocks, made on the GPU."""
+        lv0 = np.ascontiguousarray(level0, dtype=np.uint8)
+        if lv0.ndim != (2 if int(fmt) == 61 else 3) or (lv0.ndim == 3 and lv0.shape[2] != 4):
+            raise HostError(f"import_texture: level 0 of format {fmt} has shape {lv0.shape}")
+        h, w = lv0.shape[:2]
+        mips = min(w, h).bit_length() if mip_levels is None else int(mip_levels)
+        err = C.create_string_buffer(256)
+        need = self.lib.pbrh_import_texture(self.h, None, w, h, int(fmt), mips, None, 0, err, 256)
+        if need < 0:
+            raise HostError(err.value.decode())
+        out = np.zeros(need, dtype=np.uint8)
+        if self.lib.pbrh_import_texture(self.h, lv0.ctypes.data, w, h, int(fmt), mips, out.ctypes.data, out.size, err, 256) != need:
+            raise HostError(err.value.decode())
+        return out.tobytes()
 
     def set_initial_luminance(self, v):
         self._check(self.lib.pbrh_set_initial_luminance(self.h, float(v)))

@@ -30,4 +30,22 @@ pbr_texture2d ParseTextureFile(const uint8_t* file, size_t bytes) {
     return t;
 }
 
+size_t WriteTextureFile(const pbr_texture2d& t, uint8_t* file, size_t bytes) {
+    constexpr size_t HEADER = 16;
+    if (!(t.format & PBR_TEX_BC1_BLOCKS)) throw HipException("texture file: the chain to write is not BC1 blocks (PBR_TEX_BC1_BLOCKS)");
+    const size_t payload = pbr_texture2d_bytes(t.width, t.height, t.mip_levels, t.format);
+    if (!payload) throw HipException("texture file: bad size, level count or format");
+    if (!file) return HEADER + payload;
+    if (!t.texels) throw HipException("texture file: null blocks");
+    if (bytes < HEADER + payload) throw HipException("texture file: output buffer too small");
+    const uint16_t info[4] = {(uint16_t)t.width, (uint16_t)t.height, 1, (uint16_t)t.mip_levels};   // (sizes are <= PBR_TEX_MAX_SIZE)
+    const uint32_t count = (uint32_t)payload;
+    std::memcpy(file, info, sizeof(info));
+    file[8] = (uint8_t)(t.format & 0xffu);
+    file[9] = file[10] = file[11] = 0;
+    std::memcpy(file + 12, &count, sizeof(count));
+    std::memcpy(file + HEADER, t.texels, payload);
+    return HEADER + payload;
+}
+
 }  // namespace MRendererHip

@@ -187,6 +187,50 @@ int pbrh_parse_texture_file(const uint8_t* file, size_t bytes, void* texture, vo
     }
 }
 
+long pbrh_write_texture_file(const void* texture, uint8_t* file, size_t file_bytes, char* err, size_t err_len) {
+    try {
+        if (!texture) throw HipException("texture file: null descriptor");
+        pbr_texture2d t;
+        std::memcpy(&t, texture, sizeof(t));
+        return (long)WriteTextureFile(t, file, file_bytes);
+    } catch (const std::exception& e) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
+        return -1;
+    }
+}
+
+long pbrh_import_texture(pbrh_renderer* r, const void* level0, uint32_t width, uint32_t height, uint32_t stored_format, uint32_t mip_levels,
+                         uint8_t* file_out, size_t file_bytes, char* err, size_t err_len) {
+    try {
+        if (!r) throw HipException("pbrh_import_texture: null renderer");
+        if ((width & 3u) || (height & 3u)) throw HipException("pbrh_import_texture: width and height must be multiples of 4");
+        const size_t chain_bytes = pbr_texture2d_bytes(width, height, mip_levels, stored_format);
+        if (!chain_bytes || (stored_format & PBR_TEX_BC1_BLOCKS)) throw HipException("pbrh_import_texture: bad size, level count or format");
+        pbr_texture2d t{nullptr, width, height, mip_levels, stored_format | PBR_TEX_BC1_BLOCKS};
+        const size_t need = WriteTextureFile(t, nullptr, 0);
+        if (!file_out) return (long)need;
+        if (!level0) throw HipException("pbrh_import_texture: null level 0");
+        if (file_bytes < need) throw HipException("pbrh_import_texture: output buffer too small");
+        const size_t level0_bytes = (size_t)width * height * (stored_format == PBR_TEX_R8_UNORM ? 1 : 4);
+        pbr_ctx* ctx = r->scheduler->CommandList()->Context();
+        DeviceMemory chain(chain_bytes), blocks(need - 16);
+        // (a blocking copy from pageable memory has landed when it returns, so the context's stream, which may be non-blocking, needs no
+        // event to see it: the order LoadCubeMap relies on)
+        ThrowIfFailed(hipMemcpy(chain.Ptr(), level0, level0_bytes, hipMemcpyHostToDevice), "upload level 0");
+        if (pbr_texture2d_gen_mips(ctx, chain.Ptr(), width, height, mip_levels, stored_format) != PBR_OK) throw HipException(pbr_last_error(ctx));
+        if (pbr_bc1_encode(ctx, chain.Ptr(), width, height, mip_levels, stored_format, blocks.Ptr()) != PBR_OK)
+            throw HipException(pbr_last_error(ctx));
+        if (pbr_sync(ctx) != PBR_OK) throw HipException(pbr_last_error(ctx));
+        std::vector<uint8_t> host(need - 16);
+        ThrowIfFailed(hipMemcpy(host.data(), blocks.Ptr(), host.size(), hipMemcpyDeviceToHost), "read blocks");
+        t.texels = host.data();
+        return (long)WriteTextureFile(t, file_out, file_bytes);
+    } catch (const std::exception& e) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
+        return -1;
+    }
+}
+
 int pbrh_parse_scene_lights(const char* json, size_t bytes, float* lights, int max_lights, char* err, size_t err_len) {
     try {
         const std::vector<SceneLightRecord> recs = ParseSceneLights(json, bytes);

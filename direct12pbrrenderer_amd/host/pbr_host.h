@@ -56,6 +56,19 @@ int pbrh_parse_hdr(const uint8_t* file, size_t bytes, uint32_t* w, uint32_t* h, 
  * truncated file, a byte count that disagrees with pbr_texture2d_bytes or the file's size, depth != 1, an unknown format, a
  * buffer too small. */
 int pbrh_parse_texture_file(const uint8_t* file, size_t bytes, void* texture, void* blocks, size_t blocks_bytes, char* err, size_t err_len);
+/* CPU only, stateless: the inverse of pbrh_parse_texture_file, the file half of TextureData::BinarySerialize.  texture = a
+ * pbr_texture2d whose format holds PBR_TEX_BC1_BLOCKS and whose texels point to the chain's blocks on the HOST; file receives
+ * TextureInfo (uint16 width, height, depth 1, mips; uint8 stored format; 3 zero bytes), the uint32 byte count at offset 12 and
+ * the payload at 16.  Returns the file's byte count (file NULL: the size needed, nothing read or written), or -1 + reason in err
+ * with nothing written: a description without the flag or one pbr_texture2d_bytes rejects, null blocks, file_bytes too small. */
+long pbrh_write_texture_file(const void* texture, uint8_t* file, size_t file_bytes, char* err, size_t err_len);
+/* The reference's ResourceLoader::ImportTexture from decoded pixels on (image decoding stays outside): level0 (host, width x height
+ * texels of stored_format, one of the four PBR_TEX_* formats) is uploaded, its chain of mip_levels levels made by
+ * pbr_texture2d_gen_mips and compressed by pbr_bc1_encode on the renderer's context, read back and written to file_out by
+ * pbrh_write_texture_file.  Returns the file's byte count (file_out NULL: the size needed, nothing runs), or -1 + reason in err.
+ * Like the reference (ResourceLoader.cpp:363-367) it refuses a level 0 whose width or height is not a multiple of 4. */
+long pbrh_import_texture(pbrh_renderer* r, const void* level0, uint32_t width, uint32_t height, uint32_t stored_format, uint32_t mip_levels,
+                         uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
 /* n lights: position[3], color[3], radius, intensity (8 floats each) */
 int pbrh_set_lights(pbrh_renderer* r, const float* lights, int n);
 /* the "mSceneLight" records of a reference scene file (Asset/Scene/main.json: Scene.h:192, ReflectionDef.h:119-149) replace

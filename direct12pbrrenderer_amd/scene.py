@@ -439,6 +439,14 @@ def add_textured_models(ms, fx):
     return textures, names
 
 
+def import_texture_table(ctx, textures, bc1=False):
+    """add_textured_models' table brought in through PbrContext.import_texture: each texture's level 0 goes to the device and its
+    chain (as many levels as the table's entry has) is made there by pbr_texture2d_gen_mips and, with bc1=True, compressed by
+    pbr_bc1_encode.  Returns the (device tensor, Texture2D) pairs in table order, as DeferredFrame.set_meshes(..., textures=) takes
+    them.  The levels the table holds below level 0 are not used: the chain is mip_chain's of its level 0."""
+    return [ctx.import_texture(t["levels"][0], t["format"], mip_levels=t["mips"], bc1=bc1) for t in textures]
+
+
 def bc1_texture_table(fxb):
     """The textured models' maps as BC1 chains from the fixture written by tests/golden/make_textured_models_bc1.py (fxb: the
     loaded npz), in add_textured_models' table order (model by model, the maps in `maps` order), so that the draws' map indices of

@@ -380,6 +380,46 @@ size_t pbr_texture2d_bytes(uint32_t width, uint32_t height, uint32_t mip_levels,
  * one of the four (PBR_TEX_BC1_BLOCKS included: the flag describes the input, not the output). */
 pbr_status pbr_bc1_decode(pbr_ctx* ctx, const void* blocks, uint32_t width, uint32_t height, uint32_t mip_levels,
                           uint32_t stored_format, void* out);
+/* ---- Texture import (new): the producing half — ResourceLoader::ImportTexture's GenerateImageMipmaps and TextureCompressor::Compress ---- */
+/* The mip chain of a 2D texture, in place like pbr_cube_gen_mips: texels (device) is a chain in the uncompressed pbr_texture2d layout
+ * of `format` (one of the four stored formats, without PBR_TEX_BC1_BLOCKS; 4-byte aligned for the 4-byte formats) with level 0
+ * filled; levels 1 .. mip_levels - 1 are written.  The rule, pinned (the one of every fixture chain, scene.mip_chain): texel (x, y)
+ * of level l, (width >> l) x (height >> l), is per stored byte (a + b + c + d + 2) >> 2 of the texels (2x, 2y), (2x + 1, 2y),
+ * (2x, 2y + 1), (2x + 1, 2y + 1) of level l - 1 as that level was rounded; an odd last row / column of the level above is dropped;
+ * no sRGB curve is applied or removed (format 91 averages its stored bytes).  Asynchronous on the context's stream, no allocation,
+ * no host synchronisation, at most two launches: one block per 64 x 64 tile of level 0 takes it down levels 1 .. 6 (the 2 x 2
+ * footprints are aligned at every level), a second launch of one block makes levels 7 and up from level 6.  mip_levels == 1 is
+ * valid and enqueues nothing.  Refusals (PBR_ERR_INVALID, nothing enqueued): null or misaligned texels, a zero size or one above
+ * PBR_TEX_MAX_SIZE, mip_levels 0 or above floor(log2(min(w, h))) + 1, format not one of the four (any other bit set included). */
+pbr_status pbr_texture2d_gen_mips(pbr_ctx* ctx, void* texels, uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t format);
+/* The inverse of pbr_bc1_decode, same argument order, same layouts on both sides: texels (device, the uncompressed chain in
+ * stored_format; 4-byte aligned for the 4-byte formats) -> blocks_out (device, 8-byte aligned, the BC1 chain exactly as
+ * PBR_TEX_BC1_BLOCKS defines it: pbr_texture2d_bytes(width, height, mip_levels, stored_format | PBR_TEX_BC1_BLOCKS) bytes).  One
+ * asynchronous launch on the context's stream for all levels, no allocation.  Refusals (PBR_ERR_INVALID, nothing enqueued): those
+ * of pbr_bc1_decode (stored_format | PBR_TEX_BC1_BLOCKS included: the flag describes the output, not the input).
+ * The encoding rule, pinned, all in integers (every intermediate fits a signed 32-bit integer; `/` on possibly negative numerators
+ * is FLOOR division); tests/bc1_encode_ref.py restates it in numpy and the kernel is held to it bit for bit:
+ *   Texel -> (r, g, b): format 28 the stored R, G, B; 87 and 91 the swizzle (stored B, G, R); 61 (r, r, r).  Stored alpha is
+ *   ignored; every emitted texel decodes with alpha 255.  No sRGB curve.
+ *   A block's texels are those of the level that lie inside it (n of them, 1 .. 16: a level smaller than a block, or one whose size
+ *   is no multiple of 4, gives partial blocks, the "top-left texels" of PBR_TEX_BC1_BLOCKS).  A texel outside the level takes no
+ *   part in any minimum, maximum or sum below and gets index 0.
+ *   Start: per channel c, lo_c and hi_c over the block; dom = the channel with the largest hi_c - lo_c (the first of r, g, b on
+ *   ties); cov_c = n sum(x_c x_dom) - sum(x_c) sum(x_dom).  Endpoint A_c = hi_c and B_c = lo_c, exchanged for every channel with
+ *   cov_c < 0.  Quantise (v an 8-bit channel): 5 bits (31 v + 127) / 255 for red and blue, 6 bits (63 v + 127) / 255 for green; the
+ *   RGB565 word is r5 << 11 | g6 << 5 | b5.
+ *   Fit of a pair of RGB565 words: order them so that c0 >= c1 as uint16.  c0 == c1: every index 0, each texel's error its squared
+ *   distance (over r, g, b) to the expanded c0.  Otherwise the four-colour palette of the decode rule above; each texel takes the
+ *   palette entry of least squared distance, the lowest index on ties.  The block's error is the sum over its texels.
+ *   Refine, at most three times: with the weights a = (3, 0, 2, 1)[index], b = 3 - a of the block's texels, Saa = sum(a a), Sbb =
+ *   sum(b b), Sab = sum(a b), Sax_c = sum(a x_c), Sbx_c = sum(b x_c), det = Saa Sbb - Sab Sab.  det == 0: stop.  A_c = clamp((6 (Sbb
+ *   Sax_c - Sab Sbx_c) + det) / (2 det), 0, 255), B_c = clamp((6 (Saa Sbx_c - Sab Sax_c) + det) / (2 det), 0, 255); quantise A and B
+ *   and fit the pair: if its error is strictly smaller than the kept one it replaces c0, c1, the indices and the error, otherwise stop.
+ *   Emit c0, c1 as little-endian uint16 and the sixteen indices in the bit order of the decode rule.  c0 >= c1 always, and with
+ *   c0 == c1 only index 0 occurs: the three-colour mode's transparent index 3 is never emitted.
+ * Parity with DirectXTex's mip filter and BC1 encoder (what the reference's import runs) is not pinned: neither is available. */
+pbr_status pbr_bc1_encode(pbr_ctx* ctx, const void* texels, uint32_t width, uint32_t height, uint32_t mip_levels,
+                          uint32_t stored_format, void* blocks_out);
 /* The Use*Map flags of ConstantBufferInstance (gbuffer.hlsl:43-47) as texture indices, one record per draw in an array parallel
  * to the pbr_draw array: PBR_NO_MAP takes the constant branch, any other value is an index into the call's texture table. */
 #define PBR_NO_MAP                   0xffffffffu
