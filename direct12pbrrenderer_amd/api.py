@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from .structs import (Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, cube_texels, env_padded_texels, texture2d_bytes)
+                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, texture2d_bytes)
 
 
 class PbrError(RuntimeError):
@@ -174,6 +174,25 @@ class PbrContext:
         """Padded copy of a prefiltered env chain — the layout deferred_shade samples (one-shot)."""
         out = out if out is not None else self.empty((env_padded_texels(size, mips), 4), torch.float16)
         self._check(self.lib.pbr_env_pad(self.h, _ptr(env), size, mips, _ptr(out)))
+        return out
+
+    def bc6h_decode_cube(self, faces, size, mip_levels, out=None):
+        """pbr_bc6h_decode_cube: the six BC6H_UF16 face chains of a sky asset -> the fp32 RGBA cube chain every consumer takes
+        (float32 [cube_texels(size, mip_levels), 4], alpha 1).  faces: six device tensors (uint8, structs.bc6h_chain_bytes each) or
+        six device addresses (e.g. into one uploaded file, at host.parse_cubemap_file's offsets), in the order px, nx, py, ny, pz, nz."""
+        faces = list(faces)
+        if len(faces) != 6:
+            raise PbrError(f"bc6h_decode_cube: six faces, got {len(faces)}")
+        nbytes = bc6h_chain_bytes(size, mip_levels)
+        for f in faces:
+            if isinstance(f, torch.Tensor) and nbytes and f.numel() * f.element_size() != nbytes:
+                raise PbrError(f"bc6h_decode_cube: a face of {f.numel() * f.element_size()} bytes, {size}^2 x {mip_levels} levels takes {nbytes}")
+        ptrs = (C.c_void_p * 6)(*[_ptr(f) for f in faces])
+        if out is None:
+            if not nbytes:
+                raise PbrError(f"bad BC6H cube description: {size}^2, {mip_levels} levels")
+            out = self.empty((cube_texels(size, mip_levels), 4), torch.float32)
+        self._check(self.lib.pbr_bc6h_decode_cube(self.h, C.byref(ptrs), int(size), int(mip_levels), _ptr(out)))
         return out
 
     def sh9_project(self, sky, sky_size, sky_mips=1, out=None):

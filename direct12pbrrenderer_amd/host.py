@@ -53,6 +53,10 @@ SIGNATURES = {
     "pbrh_parse_hdr": (_int, [_vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_parse_texture_file": (_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_write_texture_file": (C.c_long, [_vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_parse_cubemap_file": (_int, [_vp, C.c_size_t, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_size_t * 6), _vp, C.c_char_p, C.c_size_t]),
+    "pbrh_write_cubemap_file": (C.c_long, [C.POINTER(_vp * 6), _u32, _u32, _u32, _vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_set_skybox_file": (_int, [_vp, _vp, C.c_size_t, _int]),
+    "pbrh_load_skybox_file": (_int, [_vp, C.c_char_p, _int]),
     "pbrh_import_texture": (C.c_long, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
 }
 
@@ -123,6 +127,47 @@ def write_texture_file(blocks, width, height, mip_levels, fmt):
     return out.tobytes()
 
 
+def parse_cubemap_file(data):
+    """One of the reference's serialized sky cubes (the bytes of a CubeMapResource's data file) -> (size, mip_levels, face_offsets,
+    sh_pack): the byte offset of each face's BC6H_UF16 chain in the file (six ints, each a multiple of 16; a face holds
+    structs.bc6h_chain_bytes(size, mip_levels) bytes; order px, nx, py, ny, pz, nz) and the file's SH2CoefficientsPack as 28 floats.
+    No decode happens on the CPU: upload the file and hand PbrContext.bc6h_decode_cube the six addresses."""
+    lib = load()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    err = C.create_string_buffer(256)
+    size, mips, offsets, sh = _u32(0), _u32(0), (C.c_size_t * 6)(), np.zeros(28, np.float32)
+    if lib.pbrh_parse_cubemap_file(buf.ctypes.data if buf.size else None, buf.size, C.byref(size), C.byref(mips), C.byref(offsets),
+                                   sh.ctypes.data, err, 256) != 0:
+        raise HostError(err.value.decode())
+    return int(size.value), int(mips.value), [int(o) for o in offsets], sh
+
+
+def write_cubemap_file(faces, size, mip_levels, sh_pack, fmt=2):
+    """The inverse of parse_cubemap_file: six face chains of BC6H blocks (uint8, structs.bc6h_chain_bytes(size, mip_levels) each) and
+    the 28 floats of the SH pack -> the bytes of the reference's serialized sky cube.  fmt: the DXGI number written into every
+    TextureInfo, one of the reference's HDR formats (1 .. 18; 2 = R32G32B32A32_FLOAT, what its sky import produces)."""
+    from .structs import bc6h_chain_bytes
+    lib = load()
+    faces = [np.ascontiguousarray(f).view(np.uint8).reshape(-1) for f in faces]
+    if len(faces) != 6:
+        raise HostError(f"cube-map file: six faces, got {len(faces)}")
+    sh = np.ascontiguousarray(sh_pack, dtype=np.float32).reshape(-1)
+    if sh.size != 28:
+        raise HostError(f"cube-map file: the SH pack is 28 floats, got {sh.size}")
+    err = C.create_string_buffer(256)
+    ptrs = (_vp * 6)(*[f.ctypes.data for f in faces])
+    need = lib.pbrh_write_cubemap_file(C.byref(ptrs), int(size), int(mip_levels), int(fmt), sh.ctypes.data, None, 0, err, 256)
+    if need < 0:
+        raise HostError(err.value.decode())
+    for f in faces:
+        if f.size != bc6h_chain_bytes(size, mip_levels):
+            raise HostError(f"cube-map file: a face of {f.size} bytes, the description takes {bc6h_chain_bytes(size, mip_levels)}")
+    out = np.zeros(need, dtype=np.uint8)
+    if lib.pbrh_write_cubemap_file(C.byref(ptrs), int(size), int(mip_levels), int(fmt), sh.ctypes.data, out.ctypes.data, out.size, err, 256) != need:
+        raise HostError(err.value.decode())
+    return out.tobytes()
+
+
 class HostRenderer:
     """One DeferredRenderPipeline + FrameGraph + RenderScheduler (pbrh_renderer).  tile = (full_w, full_h, cols, rows, rank,
     halo) renders one device's tile of a larger frame; otherwise a whole width x height frame."""
@@ -150,6 +195,17 @@ class HostRenderer:
     def set_skybox(self, cube_mip0, size):
         a = np.ascontiguousarray(cube_mip0[:4 * 6 * size * size], dtype=np.float32)
         self._check(self.lib.pbrh_set_skybox(self.h, a.ctypes.data, size))
+
+    def set_skybox_file(self, data, recompute_sh=False):
+        """pbrh_set_skybox_file: the bytes of the reference's serialized sky cube are uploaded as they are and decoded on the GPU
+        (pbr_bc6h_decode_cube) with the file's own levels; SkyBoxSH is the file's pack, or with recompute_sh the projection of the
+        decoded level 0."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        self._check(self.lib.pbrh_set_skybox_file(self.h, buf.ctypes.data if buf.size else None, buf.size, 1 if recompute_sh else 0))
+
+    def load_skybox_file(self, path, recompute_sh=False):
+        """set_skybox_file of a file on disk (pbrh_load_skybox_file)"""
+        self._check(self.lib.pbrh_load_skybox_file(self.h, os.fsencode(path), 1 if recompute_sh else 0))
 
     def set_lights(self, lights):
         p = pack_lights(lights)

@@ -1,0 +1,122 @@
+// CubeMapFile.cpp — see CubeMapFile.h
+#include "CubeMapFile.h"
+
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "FrameGraphResource.h"
+#include "Scene.h"
+
+namespace MRendererHip {
+
+namespace {
+constexpr size_t HEADER = 16;       // TextureInfo (12) + the payload's byte count (4)
+constexpr size_t SH_BYTES = sizeof(pbr_sh_pack);
+static_assert(SH_BYTES == 112, "SH2CoefficientsPack is seven float4");
+bool hdr_format(uint32_t f) { return f >= 1 && f <= 18; }   // R32G32B32A32_TYPELESS .. R32G32_SINT (TextureCompression.cpp:6-10)
+}  // namespace
+
+CubeMapFileInfo ParseCubeMapFile(const uint8_t* file, size_t bytes) {
+    if (!file || bytes < HEADER) throw HipException("cube-map file: truncated header");
+    CubeMapFileInfo out;
+    size_t at = 0, chain = 0;
+    uint16_t first[4] = {};
+    for (int f = 0; f < 6; f++) {
+        const std::string face = "cube-map file: face " + std::to_string(f) + ": ";
+        if (bytes - at < HEADER) throw HipException(face + "truncated header");
+        uint16_t info[4];           // width, height, depth, mips (little-endian, as the reference's writer leaves them)
+        std::memcpy(info, file + at, sizeof(info));
+        const uint8_t format = file[at + 8];
+        uint32_t payload;
+        std::memcpy(&payload, file + at + 12, sizeof(payload));
+        if (f == 0) {
+            if (info[0] != info[1]) throw HipException(face + std::to_string(info[0]) + " x " + std::to_string(info[1]) + " (cube faces are square)");
+            if (info[2] != 1) throw HipException(face + "depth " + std::to_string(info[2]) + " (2D faces only)");
+            if (!hdr_format(format)) throw HipException(face + "format " + std::to_string(format) + " is not one of the reference's HDR formats (1 .. 18)");
+            chain = pbr_bc6h_chain_bytes(info[0], info[3]);
+            if (!chain) throw HipException(face + "bad size or level count (" + std::to_string(info[0]) + ", " + std::to_string(info[3]) + " levels)");
+            std::memcpy(first, info, sizeof(first));
+            out.Size = info[0]; out.MipLevels = info[3]; out.Format = format;
+        } else if (std::memcmp(first, info, sizeof(first)) != 0 || format != out.Format) {
+            throw HipException(face + "its TextureInfo differs from face 0's");
+        }
+        if (payload != chain)
+            throw HipException(face + "payload of " + std::to_string(payload) + " bytes, the BC6H chain takes " + std::to_string(chain));
+        if (bytes - at - HEADER < payload) throw HipException(face + "truncated payload");
+        out.FaceOffset[f] = at + HEADER;
+        at += HEADER + payload;
+    }
+    if (bytes - at < SH_BYTES) throw HipException("cube-map file: truncated SH coefficients");
+    if (bytes - at > SH_BYTES) throw HipException("cube-map file: bytes after the SH coefficients");
+    std::memcpy(&out.SH, file + at, SH_BYTES);
+    return out;
+}
+
+size_t WriteCubeMapFile(const void* const faces[6], uint32_t size, uint32_t mip_levels, uint8_t format, const pbr_sh_pack& sh,
+                        uint8_t* file, size_t bytes) {
+    const size_t chain = pbr_bc6h_chain_bytes(size, mip_levels);
+    if (!chain) throw HipException("cube-map file: bad size or level count");
+    if (!hdr_format(format)) throw HipException("cube-map file: format " + std::to_string(format) + " is not one of the reference's HDR formats (1 .. 18)");
+    const size_t total = 6 * (HEADER + chain) + SH_BYTES;
+    if (!file) return total;
+    if (!faces) throw HipException("cube-map file: null faces");
+    for (int f = 0; f < 6; f++)
+        if (!faces[f]) throw HipException("cube-map file: null face " + std::to_string(f));
+    if (bytes < total) throw HipException("cube-map file: output buffer too small");
+    const uint16_t info[4] = {(uint16_t)size, (uint16_t)size, 1, (uint16_t)mip_levels};   // (size <= PBR_BC6H_MAX_SIZE)
+    const uint32_t count = (uint32_t)chain;
+    size_t at = 0;
+    for (int f = 0; f < 6; f++) {
+        std::memcpy(file + at, info, sizeof(info));
+        file[at + 8] = format;
+        file[at + 9] = file[at + 10] = file[at + 11] = 0;
+        std::memcpy(file + at + 12, &count, sizeof(count));
+        std::memcpy(file + at + HEADER, faces[f], chain);
+        at += HEADER + chain;
+    }
+    std::memcpy(file + at, &sh, SH_BYTES);
+    return total;
+}
+
+std::shared_ptr<SkyBox> SkyBoxFromCubeMapFile(pbr_ctx* ctx, const uint8_t* file, size_t bytes, bool recompute_sh) {
+    const CubeMapFileInfo info = ParseCubeMapFile(file, bytes);
+    auto check = [&](pbr_status st) { if (st != PBR_OK) throw HipException(pbr_last_error(ctx)); };
+    DeviceMemory staged(bytes);     // (hipMalloc is 256-byte aligned, so every payload is 16-byte aligned on the device too)
+    // (a blocking copy from pageable memory has landed when it returns: the context's stream needs no event to see it)
+    ThrowIfFailed(hipMemcpy(staged.Ptr(), file, bytes, hipMemcpyHostToDevice), "upload cube-map file");
+    const void* faces[6];
+    for (int f = 0; f < 6; f++) faces[f] = (const uint8_t*)staged.Ptr() + info.FaceOffset[f];
+    auto sky = std::make_shared<SkyBox>();
+    sky->Cube = std::make_shared<DeviceTexture2DArray>(info.Size, info.MipLevels, ETextureFormat_R32G32B32A32_FLOAT);
+    check(pbr_bc6h_decode_cube(ctx, faces, info.Size, info.MipLevels, (float*)sky->Cube->DevicePtr()));
+    if (recompute_sh) {
+        DeviceStructuredBuffer pack(112, 4);
+        pbr_cube_f32 c{(const float*)sky->Cube->DevicePtr(), info.Size, info.MipLevels};
+        check(pbr_sh9_project(ctx, &c, (float*)pack.DevicePtr()));
+        check(pbr_sync(ctx));
+        ThrowIfFailed(hipMemcpy(&sky->SH, pack.DevicePtr(), 112, hipMemcpyDeviceToHost), "read SH");
+    } else {
+        check(pbr_sync(ctx));       // `staged` is released on return
+        sky->SH = info.SH;
+    }
+    return sky;
+}
+
+std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, bool recompute_sh) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) throw HipException("cube-map file: cannot open " + path);
+    std::vector<uint8_t> data;
+    uint8_t buf[1 << 16];
+    size_t n;
+    while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) data.insert(data.end(), buf, buf + n);
+    std::fclose(f);
+    try {
+        return SkyBoxFromCubeMapFile(ctx, data.data(), data.size(), recompute_sh);
+    } catch (const HipException& e) {
+        throw HipException(path + ": " + e.what());
+    }
+}
+
+}  // namespace MRendererHip

@@ -3,6 +3,7 @@
 #include "HdrImage.h"
 #include "SceneFile.h"
 #include "TextureFile.h"
+#include "CubeMapFile.h"
 
 #include <algorithm>
 #include <chrono>
@@ -134,6 +135,52 @@ int pbrh_load_skybox(pbrh_renderer* r, const char* dir) {
         r->scene->SetSkyBox(LoadCubeMap(r->scheduler->CommandList()->Context(), dir));
         r->pipeline->mPrefilterEnvMapPass->Invalidate();
     });
+}
+
+int pbrh_set_skybox_file(pbrh_renderer* r, const uint8_t* file, size_t bytes, int recompute_sh) {
+    return guarded(r, [&] {
+        r->scene->SetSkyBox(SkyBoxFromCubeMapFile(r->scheduler->CommandList()->Context(), file, bytes, recompute_sh != 0));
+        r->pipeline->mPrefilterEnvMapPass->Invalidate();
+    });
+}
+
+int pbrh_load_skybox_file(pbrh_renderer* r, const char* path, int recompute_sh) {
+    return guarded(r, [&] {
+        if (!path) throw HipException("pbrh_load_skybox_file: null path");
+        r->scene->SetSkyBox(LoadCubeMapFile(r->scheduler->CommandList()->Context(), path, recompute_sh != 0));
+        r->pipeline->mPrefilterEnvMapPass->Invalidate();
+    });
+}
+
+int pbrh_parse_cubemap_file(const uint8_t* file, size_t bytes, uint32_t* size, uint32_t* mips, size_t face_offsets[6], float sh_pack[28],
+                            char* err, size_t err_len) {
+    try {
+        const CubeMapFileInfo info = ParseCubeMapFile(file, bytes);
+        if (size) *size = info.Size;
+        if (mips) *mips = info.MipLevels;
+        if (face_offsets) std::memcpy(face_offsets, info.FaceOffset, sizeof(info.FaceOffset));
+        if (sh_pack) std::memcpy(sh_pack, &info.SH, sizeof(info.SH));
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
+        return -1;
+    }
+}
+
+long pbrh_write_cubemap_file(const void* const faces[6], uint32_t size, uint32_t mip_levels, uint32_t format, const float sh_pack[28],
+                             uint8_t* file, size_t file_bytes, char* err, size_t err_len) {
+    try {
+        if (format > 255u) throw HipException("cube-map file: format " + std::to_string(format) + " is not one of the reference's HDR formats (1 .. 18)");
+        pbr_sh_pack sh{};
+        if (file) {
+            if (!sh_pack) throw HipException("cube-map file: null SH pack");
+            std::memcpy(&sh, sh_pack, sizeof(sh));
+        }
+        return (long)WriteCubeMapFile(faces, size, mip_levels, (uint8_t)format, sh, file, file_bytes);
+    } catch (const std::exception& e) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
+        return -1;
+    }
 }
 
 // CPU only: parse one .hdr file held in memory; *w, *h and (when rgbe != NULL and rgbe_bytes suffices) the expanded

@@ -45,6 +45,29 @@ const char* pbrh_last_error(const pbrh_renderer* r);
 int pbrh_set_skybox(pbrh_renderer* r, const float* cube_mip0, uint32_t size);
 /* LoadCubeMap: <dir>/{px,nx,py,ny,pz,nz}.hdr (Radiance RGBE) -> sky cube + mips + SH9 on the GPU */
 int pbrh_load_skybox(pbrh_renderer* r, const char* dir);
+/* The reference's own sky asset: a CubeMapResource's data file held in memory (pbrh_parse_cubemap_file describes the layout).  The
+ * file is uploaded as it is — 1 byte per texel instead of the 16 of pbrh_set_skybox — and its six BC6H_UF16 chains are decoded in
+ * place on the renderer's context (pbr_bc6h_decode_cube) into the sky cube, with the file's own levels (no box mips are made).
+ * SkyBoxSH is the file's pack, as the reference takes it (ResourceDef.cpp:211); recompute_sh != 0: pbr_sh9_project of the decoded
+ * level 0 instead.  pbrh_load_skybox_file reads the file from disk first. */
+int pbrh_set_skybox_file(pbrh_renderer* r, const uint8_t* file, size_t bytes, int recompute_sh);
+int pbrh_load_skybox_file(pbrh_renderer* r, const char* path, int recompute_sh);
+/* CPU only, stateless: a serialized CubeMapTextureData (ReflectionDef.h:81-84) held in memory: six faces, each TextureInfo (uint16
+ * width, height, depth, mips; uint8 DXGI format; 3 pad bytes), a uint32 payload byte count and the payload (the face's mip chain
+ * as BC6H_UF16 blocks: pbr_bc6h_chain_bytes), then SH2CoefficientsPack as 28 floats in pbr_sh_pack's order.  Fills *size, *mips,
+ * face_offsets (the byte offset of each face's payload in the file, a multiple of 16) and sh_pack; any of them may be NULL.
+ * Returns 0, or -1 + reason in err with nothing written: a truncated file, faces whose TextureInfo differ, width != height,
+ * depth != 1, a format outside the reference's HDR range (DXGI 1 .. 18, TextureCompression.cpp:6-10), a byte count that
+ * disagrees with pbr_bc6h_chain_bytes or with the file's size. */
+int pbrh_parse_cubemap_file(const uint8_t* file, size_t bytes, uint32_t* size, uint32_t* mips, size_t face_offsets[6], float sh_pack[28],
+                            char* err, size_t err_len);
+/* CPU only, stateless: the inverse.  faces = six HOST chains of pbr_bc6h_chain_bytes(size, mip_levels) bytes in the reference's
+ * order px, nx, py, ny, pz, nz; format = the DXGI number written into every TextureInfo (1 .. 18; the reference's skies are
+ * R32G32B32A32_FLOAT, 2).  Returns the file's byte count (file NULL: the size needed, nothing read or written), or -1 + reason in
+ * err with nothing written: a size or level count pbr_bc6h_chain_bytes rejects, a format outside the HDR range, a null face or
+ * pack, file_bytes too small. */
+long pbrh_write_cubemap_file(const void* const faces[6], uint32_t size, uint32_t mip_levels, uint32_t format, const float sh_pack[28],
+                             uint8_t* file, size_t file_bytes, char* err, size_t err_len);
 /* CPU only: parse one .hdr file held in memory (header + flat / run-length scanlines) into RGBE texels */
 int pbrh_parse_hdr(const uint8_t* file, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgbe, size_t rgbe_bytes, char* err, size_t err_len);
 /* CPU only, stateless: one of the reference's serialized 2D textures (a texture asset's _data.bin) held in memory: TextureInfo (uint16

@@ -9,6 +9,7 @@ Multi-GPU: a rank owns an interior tile and shades/blooms it plus an
 `apron` pixels on every side that has a neighbour, so the interior is what a single GPU would
 produce; the only collective is the 256-bin histogram all-reduce between a16 and a17.
 """
+import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
@@ -375,6 +376,25 @@ class DeferredFrame:
             self.ctx.gbuffer_raster_textured(*args, m["maps"], m["textures"])
         else:
             self.ctx.gbuffer_raster(*args)
+
+    def set_sky_file(self, data, recompute_sh=False):
+        """The sky from the bytes of the reference's serialized sky cube (host.parse_cubemap_file): the file is uploaded as it is, its
+        six BC6H_UF16 chains are decoded on the GPU (PbrContext.bc6h_decode_cube) into the cube the sky pass samples, with the file's
+        own levels, and g.SkyBoxSH becomes the file's SH pack (recompute_sh: the projection of the decoded level 0).  The env chain
+        the frame was built with is not touched: prefilter it from self.sky when it should follow.  Returns the 28 floats."""
+        from . import host
+        size, mips, offsets, sh = host.parse_cubemap_file(data)
+        staged = self.ctx.upload(np.frombuffer(bytes(data), dtype=np.uint8).copy())
+        cube = self.ctx.bc6h_decode_cube([staged.data_ptr() + o for o in offsets], size, mips)
+        if recompute_sh:
+            pack = self.ctx.sh9_project(cube, size, mips)
+            self.ctx.sync()
+            sh = pack.cpu().numpy()
+        else:
+            self.ctx.sync()             # `staged` may be released on return
+        C.memmove(C.addressof(self.g.SkyBoxSH), np.ascontiguousarray(sh, dtype=np.float32).ctypes.data, 112)
+        self.sky = (cube, size, mips)
+        return sh
 
     def set_prev_luminance(self, v):
         self.avg.fill_(float(v))

@@ -156,6 +156,19 @@ def texture2d_bytes(width, height, mip_levels, fmt):
     return sum((width >> l) * (height >> l) for l in range(mip_levels)) * TEX_FORMATS[fmt][0]
 
 
+BC6H_MAX_SIZE = 8192                                  # PBR_BC6H_MAX_SIZE
+
+
+def bc6h_chain_bytes(size, mip_levels):
+    """pbr_bc6h_chain_bytes: the bytes of one cube face's mip chain as BC6H blocks (level i max(1, ((size >> i) + 3) // 4)^2 blocks
+    of 16 bytes); 0 for what pbr_bc6h_decode_cube refuses (size 0, not a multiple of 4 or above BC6H_MAX_SIZE, mip_levels 0 or
+    above floor(log2(size)) + 1)."""
+    size, mip_levels = int(size), int(mip_levels)
+    if not (4 <= size <= BC6H_MAX_SIZE) or size % 4 or not (1 <= mip_levels <= size.bit_length()):
+        return 0
+    return sum(max(1, ((size >> l) + 3) // 4) ** 2 * 16 for l in range(mip_levels))
+
+
 class CubeF32(C.Structure):
     _fields_ = [("data", C.c_void_p), ("size", C.c_uint32), ("mips", C.c_uint32)]
 

@@ -192,12 +192,66 @@ pbr_status pbr_rgbe_decode(pbr_ctx* ctx, const uint8_t* rgbe, size_t texels, flo
  * ResourceLoader.cpp:465-507).  cube->data mip 0 must be filled; mips 1.. are written. */
 pbr_status pbr_cube_gen_mips(pbr_ctx* ctx, float* cube_data, uint32_t size, uint32_t mips);
 
+/* ---- BC6H sky cubes (new): the reference's load-time decode of a CubeMapResource ---------------------------------------- */
+/* The reference serializes every HDR texture as DXGI_FORMAT_BC6H_UF16 (TextureCompression.h:13-14, BasicStorage.h:10-11): a sky
+ * asset is six such chains (ResourceDef.cpp:187-219, BasicStorage.cpp:161-188) that DirectX::Decompress expands at load time.
+ * One face's chain, the payload of the file byte for byte: level i is max(1, ((size >> i) + 3) / 4)^2 blocks of 16 bytes,
+ * row-major, levels concatenated from level 0; texel (x, y) of a level is texel (x & 3, y & 3) of block (x >> 2, y >> 2), so a
+ * block that overhangs a level smaller than 4 contributes its top-left texels.  Bytes of one face's chain; 0 for what
+ * pbr_bc6h_decode_cube refuses (size 0, not a multiple of 4 or above PBR_BC6H_MAX_SIZE, mip_levels 0 or above floor(log2(size)) + 1). */
+#define PBR_BC6H_MAX_SIZE 8192u   /* the largest cube pbr_cube_gen_mips, pbr_prefilter_env and pbr_sh9_project take */
+size_t pbr_bc6h_chain_bytes(uint32_t size, uint32_t mip_levels);
+/* face_blocks: HOST array of six DEVICE pointers, 16-byte aligned, one chain each, in the reference's face order px, nx, py, ny,
+ * pz, nz (= +X, -X, +Y, -Y, +Z, -Z of pbr_cube_f32) — six pointers because in the file the chains are separated by 16-byte
+ * headers; every payload of a file uploaded as it is is 16-byte aligned relative to the file's start, so it decodes in place.
+ * out_rgba: DEVICE, 16-byte aligned, the pbr_cube_f32 layout of `size` and `mip_levels` (pbr_cube_texels float4 texels: mips
+ * concatenated, six faces per mip), alpha 1.0f.  One asynchronous launch on the context's stream for all faces and levels, no
+ * allocation, no host synchronisation.  Refusals (PBR_ERR_INVALID, nothing enqueued): a null or misaligned pointer (the array,
+ * any face, out_rgba), size 0, not a multiple of 4 (the reference asserts it: BasicStorage.h:252-260) or above
+ * PBR_BC6H_MAX_SIZE, mip_levels 0 or above floor(log2(size)) + 1.
+ * The decode rule, pinned: the D3D11 BC6H_UF16 definition with DirectXTex's rounding term (what the reference's DirectX::Decompress
+ * runs); tests/bc6h_ref.py restates it in numpy, is held to a third-party decoder on the CPU, and the kernel is held to it bit for bit.
+ *   A block is 128 bits, bit 0 = the LSB of byte 0.  Mode: bits 0-1 if they are 0 or 1, otherwise bits 0-4.  The header follows, its
+ *   fields in this order, LSB first; x[a:b] with a > b stores bit b first, r0[10:11] and r0[10:15] store the HIGH bit first.
+ *   Two regions (endpoint bits, delta bits of r.g.b); the 5-bit partition follows at bits 77-81, 46 index bits from bit 82:
+ *     0x00 10.5.5.5: g2[4] b2[4] b3[4] r0[9:0] g0[9:0] b0[9:0] r1[4:0] g3[4] g2[3:0] g1[4:0] b3[0] g3[3:0] b1[4:0] b3[1] b2[3:0] r2[4:0] b3[2] r3[4:0] b3[3]
+ *     0x01 7.6.6.6:  g2[5] g3[4] g3[5] r0[6:0] b3[0] b3[1] b2[4] g0[6:0] b2[5] b3[2] g2[4] b0[6:0] b3[3] b3[5] b3[4] r1[5:0] g2[3:0] g1[5:0] g3[3:0] b1[5:0] b2[3:0] r2[5:0] r3[5:0]
+ *     0x02 11.5.4.4: r0[9:0] g0[9:0] b0[9:0] r1[4:0] r0[10] g2[3:0] g1[3:0] g0[10] b3[0] g3[3:0] b1[3:0] b0[10] b3[1] b2[3:0] r2[4:0] b3[2] r3[4:0] b3[3]
+ *     0x06 11.4.5.4: r0[9:0] g0[9:0] b0[9:0] r1[3:0] r0[10] g3[4] g2[3:0] g1[4:0] g0[10] g3[3:0] b1[3:0] b0[10] b3[1] b2[3:0] r2[3:0] b3[0] b3[2] r3[3:0] g2[4] b3[3]
+ *     0x0a 11.4.4.5: r0[9:0] g0[9:0] b0[9:0] r1[3:0] r0[10] b2[4] g2[3:0] g1[3:0] g0[10] b3[0] g3[3:0] b1[4:0] b0[10] b2[3:0] r2[3:0] b3[1] b3[2] r3[3:0] b3[4] b3[3]
+ *     0x0e 9.5.5.5:  r0[8:0] b2[4] g0[8:0] g2[4] b0[8:0] b3[4] r1[4:0] g3[4] g2[3:0] g1[4:0] b3[0] g3[3:0] b1[4:0] b3[1] b2[3:0] r2[4:0] b3[2] r3[4:0] b3[3]
+ *     0x12 8.6.5.5:  r0[7:0] g3[4] b2[4] g0[7:0] b3[2] g2[4] b0[7:0] b3[3] b3[4] r1[5:0] g2[3:0] g1[4:0] b3[0] g3[3:0] b1[4:0] b3[1] b2[3:0] r2[5:0] r3[5:0]
+ *     0x16 8.5.6.5:  r0[7:0] b3[0] b2[4] g0[7:0] g2[5] g2[4] b0[7:0] g3[5] b3[4] r1[4:0] g3[4] g2[3:0] g1[5:0] g3[3:0] b1[4:0] b3[1] b2[3:0] r2[4:0] b3[2] r3[4:0] b3[3]
+ *     0x1a 8.5.5.6:  r0[7:0] b3[1] b2[4] g0[7:0] b2[5] g2[4] b0[7:0] b3[5] b3[4] r1[4:0] g3[4] g2[3:0] g1[4:0] b3[0] g3[3:0] b1[5:0] b2[3:0] r2[4:0] b3[2] r3[4:0] b3[3]
+ *     0x1e 6.6.6.6:  r0[5:0] g3[4] b3[0] b3[1] b2[4] g0[5:0] g2[5] b2[5] b3[2] g2[4] b0[5:0] g3[5] b3[3] b3[5] b3[4] r1[5:0] g2[3:0] g1[5:0] g3[3:0] b1[5:0] b2[3:0] r2[5:0] r3[5:0]   (not transformed)
+ *   One region; 63 index bits from bit 65:
+ *     0x03 10.10: r0[9:0] g0[9:0] b0[9:0] r1[9:0] g1[9:0] b1[9:0]   (not transformed)
+ *     0x07 11.9:  r0[9:0] g0[9:0] b0[9:0] r1[8:0] r0[10] g1[8:0] g0[10] b1[8:0] b0[10]
+ *     0x0b 12.8:  r0[9:0] g0[9:0] b0[9:0] r1[7:0] r0[10:11] g1[7:0] g0[10:11] b1[7:0] b0[10:11]
+ *     0x0f 16.4:  r0[9:0] g0[9:0] b0[9:0] r1[3:0] r0[10:15] g1[3:0] g0[10:15] b1[3:0] b0[10:15]
+ *   The 5-bit values 0x13, 0x17, 0x1b, 0x1f are reserved: rgb = 0, alpha 1.
+ *   Transformed modes (all but 0x03 and 0x1e): e_i = (e_0 + signextend(e_i, delta bits)) & (2^endpoint bits - 1), i = 1 .. 3 (one region:
+ *   i = 1).  Unquantize, n = endpoint bits: n >= 15 -> x; x = 0 -> 0; x = 2^n - 1 -> 0xFFFF; otherwise ((x << 15) + 0x4000) >> (n - 1).
+ *   Partitions of the two-region modes, shapes 0 .. 31, texel 0 (row-major) first, '1' = the second endpoint pair e2 / e3:
+ *     0011001100110011 0001000100010001 0111011101110111 0001001100110111 0000000100010011 0011011101111111 0001001101111111 0000000100110111
+ *     0000000000010011 0011011111111111 0000000101111111 0000000000010111 0001011111111111 0000000011111111 0000111111111111 0000000000001111
+ *     0000100011101111 0111000100000000 0000000010001110 0111001100010000 0011000100000000 0000100011001110 0000000010001100 0111001100110001
+ *     0011000100010000 0000100010001100 0110011001100110 0011011001101100 0001011111101000 0000111111110000 0111000110001110 0011100110011100
+ *   Anchor texel of the second region: 15 for shapes 0 .. 16, then 2, 8, 2, 2, 8, 8, 15, 2, 8, 2, 2, 8, 8, 2, 2; texel 0 is always an
+ *   anchor; an anchor's index has one bit fewer (its high bit is 0).  Indices, texels 0 .. 15 in order: 3 bits with the weights 0, 9, 18,
+ *   27, 37, 46, 55, 64 (two regions), 4 bits with 0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64 (one region).
+ *   Interpolate and finish with the region's pair (a, b) and weight w: x = (a (64 - w) + b w + 32) >> 6; half bits = (x * 31) >> 6;
+ *   the fp32 value is that half, exactly (at most 0x7BFF: never inf or NaN).  The + 32 is DirectXTex's BC67_WEIGHT_ROUND.
+ * Parity with a reference-held file is not pinned: the checkout holds none (Asset/SkyBox/HDRWild.json without its data file). */
+pbr_status pbr_bc6h_decode_cube(pbr_ctx* ctx, const void* const face_blocks[6], uint32_t size, uint32_t mip_levels, float* out_rgba);
+
 /* env_map_gen.hlsl:50-105, all PBR_ENV_MIPS dispatches of PreFilterEnvMapPass::Execute
  * (DeferredPipeline.cpp:77-115): mip i is filtered with roughness i/(mips-1).
  * out: half4 cube chain, layout as pbr_cube_f32 with edge `size`.
  * Mips >= 1 are sampled from a half-precision copy of the source chain WHEN THAT COPY IS EXACT — every rgb texel of every
  * source mip survives fp32 -> half -> fp32 bit for bit, which is the case for everything the reference can feed this pass (its
- * sky assets are BC6H_UF16: BasicStorage.h:10-11) — and from the fp32 chain otherwise; decided on the device, the call stays
+ * sky assets are BC6H_UF16, BasicStorage.h:10-11, and pbr_bc6h_decode_cube turns every texel of such an asset into the fp32 image
+ * of a half) — and from the fp32 chain otherwise (e.g. the box mips pbr_cube_gen_mips makes); decided on the device, the call stays
  * asynchronous.  Either way <= 1 fp16 ULP (or 1e-3 relative) from the shader's sequential sum.
  * The per-mip GGX sample tables depend on (size, mips, sky->mips) only: the context keeps the last set on the device, so the FIRST
  * call with a new shape builds and uploads them (a blocking copy, ~0.2 ms of host work) and later calls do not; like every entry
