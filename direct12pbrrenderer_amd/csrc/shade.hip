@@ -13,8 +13,8 @@
 //    fall back to the global list);
 //  * the env chain is sampled from its padded layout (pbr_env_pad): no seam branches, each bilinear row is one
 //    16-byte load;
-//  * with 256 lights the kernel is FP32-VALU-issue-bound (46 packed + 4 transcendental + 2 plain instructions per pair
-//    of lights, ~500 per pixel around the loop), not HBM-bound.
+//  * with 256 lights the kernel is FP32-VALU-issue-bound (46 packed + 4 transcendental instructions per pair of lights and
+//    one compare + one pointer step per WALK_TRIPS pairs, ~430 per pixel around the loop), not HBM-bound.
 #include <cstring>
 #include <type_traits>
 #include "pbr_internal.hpp"
@@ -132,6 +132,11 @@ constexpr int SHADE_ROWS = 8;          // most rows of 256 pixels one block walk
 constexpr int MAX_STAGED_TILES = 12;   // cluster (x,y) tiles whose 8 z-slices may be staged per block
 // staged list: count, pad, 32 u16 indices = 34 halfwords (68 B) per cluster
 constexpr int LIST_STRIDE = 34;         // dwords per staged cluster list: count, pad, 32 entries (8-byte aligned pairs)
+#ifndef SHADE_WALK_TRIPS
+#define SHADE_WALK_TRIPS 2
+#endif
+constexpr int WALK_TRIPS = SHADE_WALK_TRIPS;   // trips (pairs of lights) per pointer step and compare of the staged walk; lists are padded to 2 * WALK_TRIPS entries
+static_assert(WALK_TRIPS == 2 || WALK_TRIPS == 4, "a staging thread converts four entries: the padded length must be a multiple of four that divides 32");
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f2 f2s(float a) { return f2{a, a}; }
@@ -179,7 +184,7 @@ struct alignas(4) H2x2 { H2 a, b; };   // two x-adjacent LUT texels (8 bytes, 4-
 //   4. IBL: SH diffuse + split-sum specular from the padded env chain and the LUT.
 template <bool STAGED_LISTS, int LSTRIDE, bool F32OUT>
 __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* llds, const uint32_t* lists, const uint32_t* mip_off,
-                                            int tile_x0, int tile_y0, int tiles_x, int n_lights, int q_safe, uint32_t px, uint32_t py, float4 row) {
+                                            int n_lights, int q_safe, uint32_t px, uint32_t py, float4 row, float cvv_x, uint32_t col_list) {
     // 32-bit element index (host-checked: pitch * rows * 16 < 2^32): a uniform base + one 32-bit lane offset per access instead of
     // 64-bit address arithmetic for every plane
     const uint32_t gi = __umul24(py, p.pitch) + px;
@@ -188,20 +193,25 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
     const float inv255 = 1.0f / 255.0f;   // UNORM8 -> float
 
     // ---- phase 1: geometry (vs_main :91-121, screen triangle D3D12Device.cpp:167-176; uv from the GLOBAL pixel)
-    const float u = ((float)(p.x0 + px) + 0.5f) / (float)p.full_w;
-    // v, cvv.y and the cluster row depend on the pixel ROW only: evaluated once per block row (k_deferred_shade, the same
-    // expressions) and handed in as row = {v, cvv.y, cluster row} — an IEEE divide, a floor and their neighbours less per pixel
+    // u, ndc_x, cvv.x and the cluster column depend on the pixel COLUMN only, v, cvv.y and the cluster row on the pixel ROW only: a
+    // thread evaluates its column's once (k_deferred_shade: cvv_x, col_list), a block its rows' once per row (row = {InvView[1,4,7] *
+    // cvv.y, the row's part of the list / cluster index}), the same expressions as ever — two IEEE divides, two floors, the clamps
+    // and the index multiplies less per pixel
     V3 pos, view, n;
     float z_vs, roughness, depth_keep;
     {
         const uint32_t b = at(p.B, gi * 4u), c = at(p.C, gi * 4u);
         const float depth_ndc = at(p.depth, gi * 4u);
-        const float ndc_x = 2.0f * u - 1.0f;
-        const V3 cvv = v3(ndc_x * 0.5f * p.near_width, row.y, p.Near);
-        const V3 camera_vec = v3(p.InvView[0] * cvv.x + p.InvView[1] * cvv.y + p.InvView[2] * cvv.z,
-                                 p.InvView[3] * cvv.x + p.InvView[4] * cvv.y + p.InvView[5] * cvv.z,
-                                 p.InvView[6] * cvv.x + p.InvView[7] * cvv.y + p.InvView[8] * cvv.z);
+        // InvView * {cvv.x, cvv.y, Near}, in the order the contracted sum has always had: (I0 cvv.x + [I1 cvv.y]) + I2 Near, the
+        // bracketed product rounded on its own (it is the row's)
+        const V3 camera_vec = v3(__builtin_fmaf(p.InvView[2], p.Near, __builtin_fmaf(p.InvView[0], cvv_x, row.x)),
+                                 __builtin_fmaf(p.InvView[5], p.Near, __builtin_fmaf(p.InvView[3], cvv_x, row.y)),
+                                 __builtin_fmaf(p.InvView[8], p.Near, __builtin_fmaf(p.InvView[6], cvv_x, row.z)));
         roughness = (float)(c & 255u) * inv255;
+        // (1 / 255 is NOT folded into the decode's 2 u - 1, unlike into the albedo's consumers below: the normal's last bit moves NdotH^2,
+        //  which the GGX term t = NdotH^2 (a^4 - 1) + 1 amplifies ~1 / a^4 at a highlight.  Measured: one pixel of the 64 x 64 / 1024-light
+        //  parity frame went from 2.4e-5 to 1.2e-4 of scale from the exact value, the fp32 restatement, which rounds u on its own, staying
+        //  at 3.0e-5; and the compiler packs the two multiplies and the two fmas into one v_pk_mul + one v_pk_fma, so the fold saved nothing)
         n = normalize3(decode_octahedron((float)(b & 255u) * inv255, (float)((b >> 8) & 255u) * inv255));
         // ViewSpaceDepth :74-77, ReconstructWorldPosition :79-83.  Quick form (one v_rcp, <= 2 ulp): the position is continuous in
         // it; the cluster slice, which is not, re-evaluates the exact IEEE sequence wherever it could matter (below)
@@ -222,8 +232,6 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
     // branch around it — with one, the compiler zeroes the 18 accumulator registers on both sides of every branch (36 moves per pixel)
 #ifndef PBR_EXP_NOLOOP   // (PBR_EXP_*: compile-time switches of tools/isa_phase_count.py, which sizes the phases of this function)
     if (STAGED_LISTS || n_lights > 0) {
-        int sx = (int)floorf(u * (float)PBR_CLUSTER_X);
-        int sy = (int)row.z;
         float zc = fminf(fmaxf(z_vs, p.Near), p.Far);
         // Slice index = (int)(Z * logf(zc / Near) / log(Far / Near)), a discontinuous function of the depth: its value must be the
         // shader's / the oracle's to the bit, which takes two IEEE divides and a full-precision logf (~45 instructions).  A quick
@@ -235,11 +243,12 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
         const float t_quick = p.slice_k * __builtin_amdgcn_logf(zc * p.inv_near);
         const float t_frac = t_quick - floorf(t_quick);
         int sz = (int)t_quick;
+#ifndef PBR_EXP_NOEXACT
         if (__any(!(t_frac > 1.0e-4f && t_frac < 1.0f - 1.0e-4f))) {
             zc = fminf(fmaxf(view_space_depth(depth_keep, p.Near, p.Far), p.Near), p.Far);
             sz = (int)((float)PBR_CLUSTER_Z * logf(zc / p.Near) / p.log_far_near);
         }
-        sx = clampi(sx, 0, PBR_CLUSTER_X - 1);
+#endif
         sz = clampi(sz, 0, PBR_CLUSTER_Z - 1);
         // brdf() (brdf.hlsli:47-67) with D, G, the 4 NdotL NdotV denominator AND the attenuation under ONE reciprocal:
         //   D G / max(4 NdotL NdotV, 1e-4) = [a^2/pi * gV] * gl / (T * A),   a = roughness^2 (the shader's `a * a`),
@@ -261,7 +270,7 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
         // 5 waves per SIMD, cycles per wave-instruction per SIMD): v_pk_{fma,mul,add}_f32 4.7 (two lights per instruction),
         // plain v_fma 2.6 / v_mul 3.0, v_max / v_min 4.6, v_rsq / v_rcp 8.5.  Two lights per trip in the halves of packed
         // registers therefore buy ~1.2x per flop, not 2x; the SoA light planes put the same component of both lights into
-        // an adjacent VGPR pair with no moves.  Per trip: 46 packed + 4 transcendental + the loop's compare and pointer step (+ 2 / 4 v_max on the slow paths).
+        // an adjacent VGPR pair with no moves.  Per trip: 46 packed + 4 transcendental (+ 2 / 4 v_max on the slow paths); the loop's compare and pointer step come once per WALK_TRIPS trips.
         // the nine packed sums start at zero: ONE v_pk_mov_b32 per register pair (the compiler writes two v_mov_b32 per pair)
         f2 a1x = zero2(), a1y = zero2(), a1z = zero2(), a2x = zero2(), a2y = zero2(), a2z = zero2(), a3x = zero2(), a3y = zero2(), a3z = zero2();
         const float att_c0 = llds[6 * LSTRIDE], att_c1 = llds[7 * LSTRIDE], att_c2 = llds[8 * LSTRIDE];   // light 0's polynomial (ATT: everyone's)
@@ -320,18 +329,23 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
         };
         const lds_cf* const ltab = (const lds_cf*)llds;      // the staged light planes, as an LDS (address space 3) pointer
         if (STAGED_LISTS) {
-            const uint32_t* my = lists + __mul24(__mul24(__mul24(sy - tile_y0, tiles_x) + (sx - tile_x0), PBR_CLUSTER_Z) + sz, LIST_STRIDE);
-            // staged lists are padded to an even count with the null light (black, far away): no odd tail.  An entry is
+            // (col_list, row.w: the column's and the row's part of the list's dword offset)
+            const uint32_t* my = lists + (__umul24((uint32_t)sz, LIST_STRIDE) + col_list + __float_as_uint(row.w));
+            // staged lists are padded to a multiple of 2 WALK_TRIPS entries with the null light (black, far away): the walk takes WALK_TRIPS trips
+            // per pointer step and compare, and the null light adds +0 to sums that start at +0: every sum keeps its bits.  An entry is
             // the LDS BYTE ADDRESS of the light's first plane (table base + 4 * index), a dword of its own: packed two to a dword
             // the unpacking mask + shift were two more VALU issues per trip
             const int nl = my[0];
             const bool t_ok = __all(ra * ra >= 6.0e-4f) != 0;
             auto walk = [&](auto qs, auto ts, auto au) {
                 int i = 0;
-                do {   // nl >= 2.  One 8-byte LDS read = the two addresses of the trip, each in its own register
-                    const uint2 pair = *reinterpret_cast<const uint2*>(my + 2 + i);   // i even -> 8-byte aligned
-                    light2(qs, ts, (const lds_cf*)(uintptr_t)pair.x, (const lds_cf*)(uintptr_t)pair.y, au);
-                    i += 2;
+                do {   // nl >= 2 WALK_TRIPS, a multiple of it.  One 8-byte LDS read = the two addresses of a trip, each in its own register; the later trips' ride on the DS offset field
+#pragma unroll
+                    for (int k = 0; k < WALK_TRIPS; k++) {
+                        const uint2 pair = *reinterpret_cast<const uint2*>(my + 2 + i + 2 * k);   // i even -> 8-byte aligned
+                        light2(qs, ts, (const lds_cf*)(uintptr_t)pair.x, (const lds_cf*)(uintptr_t)pair.y, au);
+                    }
+                    i += 2 * WALK_TRIPS;
                 } while (i < nl);
                 // (reading the NEXT trip's two entries one trip ahead was measured in round 4: two more live registers push the
                 //  kernel's scratch from 12 to 24 bytes per lane at its 96-VGPR budget, in-frame 0.3356 -> 0.3470 ms; removed —
@@ -343,7 +357,7 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
                 else walk(std::true_type{}, std::false_type{}, std::false_type{});
             } else walk(std::false_type{}, std::false_type{}, std::false_type{});
         } else {
-            const pbr_cluster* cl = p.clusters + (sz + sx * PBR_CLUSTER_Z + sy * PBR_CLUSTER_X * PBR_CLUSTER_Z);
+            const pbr_cluster* cl = p.clusters + ((uint32_t)sz + col_list + __float_as_uint(row.w));
             const int nl = min(max(cl->NumLights, 0), PBR_MAX_LIGHTS_PER_CLUSTER);
             auto idx = [&](int q) { return q < nl ? min(max(cl->LightIndex[q], 0), n_lights - 1) : n_lights; };   // n_lights = the null light
             for (int i = 0; i < nl; i += 2) light2(std::false_type{}, std::false_type{}, ltab + idx(i), ltab + idx(i + 1), std::false_type{});
@@ -356,22 +370,28 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
 
     // ---- phase 3: material terms (planes A and C re-read: L2 hits, keeps them out of the loop's registers)
     const uint32_t a = at(p.A, gi * 4u);
-    const float metallic = (float)((at(p.C, gi * 4u) >> 8) & 255u) * inv255;
-    const V3 albedo = v3((float)(a & 255u) * inv255, (float)((a >> 8) & 255u) * inv255, (float)((a >> 16) & 255u) * inv255);
-    const float emission = (float)(a >> 24) * inv255;
-    const V3 F0 = v3(0.04f + metallic * (albedo.x - 0.04f), 0.04f + metallic * (albedo.y - 0.04f), 0.04f + metallic * (albedo.z - 0.04f));
+    // the albedo bytes are never scaled on their own: 1 / 255 rides on the operation that consumes them
+    const float metal_b = (float)((at(p.C, gi * 4u) >> 8) & 255u), metallic = metal_b * inv255;
+    const V3 albedo_b = v3((float)(a & 255u), (float)((a >> 8) & 255u), (float)((a >> 16) & 255u));
+    const float emission = (float)(a >> 24) * (inv255 * inv255);   // emission / 255: albedo_b * emission = albedo * emission
+    const V3 F0 = v3(__builtin_fmaf(metallic, __builtin_fmaf(albedo_b.x, inv255, -0.04f), 0.04f),
+                     __builtin_fmaf(metallic, __builtin_fmaf(albedo_b.y, inv255, -0.04f), 0.04f),
+                     __builtin_fmaf(metallic, __builtin_fmaf(albedo_b.z, inv255, -0.04f), 0.04f));
     V3 out;
     {
         const float ra = roughness * roughness;
         const float k = (roughness + 1.0f) * (roughness + 1.0f) * 0.125f;
         // a^2 / pi * gV / (4 NdotV), gV = NdotV / max(NdotV (1-k) + k, 1e-6): the light sums S2, S3 carry gl * 4 NdotV
         const float spec_pix = NdotV > 0.0f ? ra * ra * (0.25f * INV_PI_F) * rcp(fmaxf(NdotV * (1.0f - k) + k, EPSILON_F)) : 0.0f;
-        const float kd = (1.0f - metallic) * INV_PI_F;   // Kd*albedo/pi = (1-F0)(1-m) albedo/pi * (1-f5)
-        out.x = (1.0f - F0.x) * (kd * albedo.x * s1x + spec_pix * s3x) + F0.x * spec_pix * s2x;
-        out.y = (1.0f - F0.y) * (kd * albedo.y * s1y + spec_pix * s3y) + F0.y * spec_pix * s2y;
-        out.z = (1.0f - F0.z) * (kd * albedo.z * s1z + spec_pix * s3z) + F0.z * spec_pix * s2z;
+        // Kd*albedo/pi = (1-F0)(1-m) albedo/pi * (1-f5); (1-m)/pi/255 in one operation, its product with the albedo byte serves the
+        // light fold and the SH term
+        const float kd = __builtin_fmaf(metal_b, -(inv255 * inv255 * INV_PI_F), inv255 * INV_PI_F);
+        const V3 kda = v3(kd * albedo_b.x, kd * albedo_b.y, kd * albedo_b.z);
+        out.x = (1.0f - F0.x) * (kda.x * s1x + spec_pix * s3x) + F0.x * spec_pix * s2x;
+        out.y = (1.0f - F0.y) * (kda.y * s1y + spec_pix * s3y) + F0.y * spec_pix * s2y;
+        out.z = (1.0f - F0.z) * (kda.z * s1z + spec_pix * s3z) + F0.z * spec_pix * s2z;
         // emission (Q1: the directional light of :144-156 is computed by the reference but never added)
-        out = out + albedo * emission;
+        out = out + albedo_b * emission;
 
         // ---- phase 4a: EnvironmentDiffuse :23-54
 #ifndef PBR_EXP_NOSH
@@ -384,9 +404,9 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
                          ((s.shb_g[0] * bx + s.shb_g[1] * by + s.shb_g[2] * bz + s.shb_g[3] * bw) + s.shc[1] * cc);
         const float ib = (s.sha_b[0] * n.x + s.sha_b[1] * n.y + s.sha_b[2] * n.z + s.sha_b[3]) +
                          ((s.shb_b[0] * bx + s.shb_b[1] * by + s.shb_b[2] * bz + s.shb_b[3] * bw) + s.shc[2] * cc);
-        out.x += albedo.x * kd * ir;
-        out.y += albedo.y * kd * ig;
-        out.z += albedo.z * kd * ib;
+        out.x += kda.x * ir;
+        out.y += kda.y * ig;
+        out.z += kda.z * ib;
 #endif
     }
 
@@ -623,7 +643,7 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
             // n_cl / 32 rounds.  The prologue is instruction issue, not latency: a new block's waves share their SIMDs with four blocks in
             // the middle of their pixel work, and ~700 prologue instructions per thread were 6 % of a 256-light block's work, 15 % of a
             // single-light one's (block timelines, profiles/r06_i_timeline_*: "staging" 5 - 12 us whether or not the loads are batched).
-            // Entries from the list's (even) length on are never read by the walk: their threads skip the conversion.
+            // Entries from the list's padded length (a multiple of four: one thread's share) on are never read by the walk: their threads skip the conversion.
             struct __attribute__((packed, aligned(4))) Idx4 { int32_t x, y, z, w; };
             const int part = threadIdx.x & 7;
             const float inv_tiles_x = rcp((float)tiles_x);
@@ -635,22 +655,27 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
                 const int cnt = n_lights > 0 ? min(max(cl->NumLights, 0), PBR_MAX_LIGHTS_PER_CLUSTER) : 0;
                 const Idx4 v = *reinterpret_cast<const Idx4*>(cl->LightIndex + 4 * part);
                 uint32_t* l = lists + c * LIST_STRIDE;
-                if (4 * part < max(cnt, 2)) {
+                const int padded = max((cnt + 2 * WALK_TRIPS - 1) & ~(2 * WALK_TRIPS - 1), 2 * WALK_TRIPS);
+                if (4 * part < padded) {   // the thread's four entries lie below the padded count
                     auto entry = [&](int k, int raw) { return lds_base + 4u * (uint32_t)(4 * part + k < cnt ? min(max(raw, 0), n_lights - 1) : n_lights); };   // never index past the staged table
                     uint2* e = reinterpret_cast<uint2*>(l + 2 + 4 * part);   // 136 c + 8 + 16 part bytes: 8-byte aligned
                     e[0] = make_uint2(entry(0, v.x), entry(1, v.y));
                     e[1] = make_uint2(entry(2, v.z), entry(3, v.w));
                 }
-                if (part == 0) *reinterpret_cast<uint2*>(l) = make_uint2((uint32_t)max((cnt + 1) & ~1, 2), 0u);
+                if (part == 0) *reinterpret_cast<uint2*>(l) = make_uint2((uint32_t)padded, 0u);
             }
         }
     }
-    // per-row terms of the block's <= SHADE_ROWS rows (vs_main :91-95, ClusterIndex clustered.hlsli:47): {v, cvv.y, cluster row}
+    // per-row terms of the block's <= SHADE_ROWS rows (vs_main :91-95, ClusterIndex clustered.hlsli:47): InvView's column 1 times cvv.y,
+    // and the row's part of the index of the pixel's list (staged: dwords from `lists`) or cluster (global: clusters from p.clusters)
     __shared__ float4 s_row[SHADE_ROWS];
     if (threadIdx.x < (uint32_t)SHADE_ROWS) {
         const float v = ((float)(p.y0 + y_begin + threadIdx.x) + 0.5f) / (float)p.full_h;
         const float ndc_y = 1.0f - 2.0f * v;
-        s_row[threadIdx.x] = make_float4(v, ndc_y * 0.5f * p.near_height, (float)clampi((int)floorf((1.0f - v) * (float)PBR_CLUSTER_Y), 0, PBR_CLUSTER_Y - 1), 0.0f);
+        const float cvv_y = ndc_y * 0.5f * p.near_height;
+        const int sy = clampi((int)floorf((1.0f - v) * (float)PBR_CLUSTER_Y), 0, PBR_CLUSTER_Y - 1);
+        const uint32_t row_list = STAGED_LISTS ? (uint32_t)((sy - tile_y0) * tiles_x * (PBR_CLUSTER_Z * LIST_STRIDE)) : (uint32_t)(sy * (PBR_CLUSTER_X * PBR_CLUSTER_Z));
+        s_row[threadIdx.x] = make_float4(p.InvView[1] * cvv_y, p.InvView[4] * cvv_y, p.InvView[7] * cvv_y, __uint_as_float(row_list));
     }
     // bit 0: the attenuation floor cannot bind; bit 1: every staged light has the SAME attenuation polynomial (one radius for the
     // whole scene is common), so its three coefficients are per-kernel constants and a trip reads 13 LDS dwords instead of 19
@@ -659,14 +684,21 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
     SHADE_ISTAMP(blockIdx.x, 1, SHADE_NOW());
     SHADE_ISTAMP(blockIdx.x, 3, ((unsigned long long)(y_end - y_begin) << 48) | blockIdx.x);
     const uint32_t px = bx0 + threadIdx.x;
+    // the thread's column (vs_main :91-95, ClusterIndex clustered.hlsli:46; uv from the GLOBAL pixel): cvv.x and the column's part of the
+    // list / cluster index, the counterpart of s_row
+    const float u = ((float)(p.x0 + px) + 0.5f) / (float)p.full_w;
+    const float ndc_x = 2.0f * u - 1.0f;
+    const float cvv_x = ndc_x * 0.5f * p.near_width;
+    const int sx = clampi((int)floorf(u * (float)PBR_CLUSTER_X), 0, PBR_CLUSTER_X - 1);
+    const uint32_t col_list = STAGED_LISTS ? (uint32_t)((sx - tile_x0) * (PBR_CLUSTER_Z * LIST_STRIDE)) : (uint32_t)(sx * PBR_CLUSTER_Z);
 #ifndef PBR_SHADE_TIMING
     if (px >= x_end) return;
     for (uint32_t py = y_begin; py < y_end; py++)
-        shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT>(p, llds, lists, s_mip_off, tile_x0, tile_y0, tiles_x, n_lights, q_safe, px, py, s_row[py - y_begin]);
+        shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
 #else
     if (px < x_end)
         for (uint32_t py = y_begin; py < y_end; py++)
-            shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT>(p, llds, lists, s_mip_off, tile_x0, tile_y0, tiles_x, n_lights, q_safe, px, py, s_row[py - y_begin]);
+            shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
     SHADE_ISTAMP_MAX(blockIdx.x, 2, SHADE_NOW());
 #endif
 }

@@ -1,69 +1,183 @@
-"""Per-phase VALU instruction count of k_deferred_shade<true, 257, false> from the compiler's gfx950 ISA: shade.hip is
-compiled once as shipped and once per PBR_EXP_* switch that removes one phase of shade_pixel; the difference of the kernels'
-static v_* instruction counts is that phase (straight-line per-pixel code: static = executed; the light walk is counted
-separately from its loop body x trips).  No GPU needed.  usage: python tools/isa_phase_count.py [out.md]"""
+"""Instruction-class counts of k_deferred_shade<true, 257, false, NoViews> (the 4K / 256-light instantiation) from the compiler's
+gfx950 ISA.  No GPU needed.
+    python tools/isa_phase_count.py [out.md] [--phases] [--src shade.hip]
+Reported:
+  * the kernel's footer: occupancy, scratch bytes per lane, VGPRs;
+  * every light-walk loop (innermost loops that carry the per-light arithmetic): v_* per TRIP (a trip = one pair of lights = four
+    transcendentals, so an unrolled body is divided by transcendentals / 4), of them packed and transcendental;
+  * the pixel-row body (the loop over a block's rows that encloses the walks): its static v_* count minus the walk loops and minus
+    the rare exact-slice path (sized with -DPBR_EXP_NOEXACT), and from it the executed VALU instructions per pixel row at 16 trips
+    of the as-shipped walk (the cheapest instantiation: attenuation floor hoisted, rough wave, one polynomial).  Every walk
+    instantiation's few instructions outside its loop are in the static count although one runs: an upper bound, alike on both
+    sides of a comparison;
+  * with --phases, per-phase counts: shade.hip compiled once per PBR_EXP_* switch that removes one phase of shade_pixel; the
+    difference of the kernels' static v_* counts is that phase.
+Only instruction CLASSES are counted (v_*, v_pk_*, the transcendental unit's, moves, ds_*, global_*)."""
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "direct12pbrrenderer_amd", "csrc", "shade.hip")
-KERNEL = "_Z16k_deferred_shadeILb1ELi257ELb0EEv11ShadeParamsii10ShadeRects"
+CSRC = os.path.join(ROOT, "direct12pbrrenderer_amd", "csrc")
+SRC = os.path.join(CSRC, "shade.hip")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# k_deferred_shade<true, 257, false, ...>: the template-argument prefix of the mangled name; the last argument (the view table's
+# type) and the parameter list follow it
+PREFIX = "_Z16k_deferred_shadeILb1ELi257ELb0E"
+VIEWS = "NoViews"
+TRIPS = 16   # pairs of lights of a capped (32-entry) list
 
 
-def kernel_isa(defines):
+def compile_isa(defines=(), src=SRC):
     with tempfile.TemporaryDirectory() as d:
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-but-set-variable",
-               "-I" + os.path.join(ROOT, "include"), "-save-temps=obj", "-c", SRC, "-o", os.path.join(d, "shade.o")] + ["-D" + x for x in defines]
+        cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-Wno-unused-function", "-Wno-unused-variable",
+               "-Wno-unused-but-set-variable", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, src, "-o", os.path.join(d, "shade.s")] + ["-D" + x for x in defines]
         subprocess.run(cmd, check=True, capture_output=True)
-        text = open(os.path.join(d, "shade-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
-    a = text.index(KERNEL + ":")
+        return open(os.path.join(d, "shade.s")).read()
+
+
+def kernel(text, prefix=PREFIX, views=VIEWS):
+    """(mangled name, code lines, footer {Occupancy, ScratchSize, NumVgprs}) of the instantiation whose name starts with prefix"""
+    names = [m.group(1) for m in re.finditer(r"^(" + re.escape(prefix) + r"\w*):", text, re.M)]
+    names = [n for n in names if views in n] or names
+    if not names:
+        raise SystemExit(f"no kernel named {prefix}* in the ISA")
+    name = names[0]
+    a = text.index(name + ":")
     b = text.index(".end_amdhsa_kernel", a)
-    return text[a:b].splitlines()
+    code = text[a:text.index(".amdhsa_kernel", a)].splitlines()
+    foot = {k: int(v) for k, v in re.findall(r"^; (Occupancy|ScratchSize|NumVgprs): (\d+)", text[b:b + 2000], re.M)[:3]}
+    return name, code, foot
 
 
 def count(lines):
-    valu = [ln.split()[0] for ln in lines if re.match(r"\s+v_", ln)]
-    trans = sum(1 for v in valu if re.match(r"v_(rcp|rsq|log|exp|sqrt|sin|cos)_", v))
-    pk = sum(1 for v in valu if v.startswith("v_pk_"))
-    mov = sum(1 for v in valu if v.startswith("v_mov_") or v.startswith("v_pk_mov"))
-    return len(valu), trans, pk, mov
+    ops = [ln.split()[0] for ln in lines if re.match(r"\s+[a-z]", ln)]
+    valu = [o for o in ops if o.startswith("v_")]
+    return {"valu": len(valu), "trans": sum(1 for v in valu if re.match(r"v_(rcp|rsq|log|exp|sqrt|sin|cos)_", v)),
+            "packed": sum(1 for v in valu if v.startswith("v_pk_")), "moves": sum(1 for v in valu if v.startswith("v_mov_") or v.startswith("v_pk_mov")),
+            "ds": sum(1 for o in ops if o.startswith("ds_")), "global": sum(1 for o in ops if o.startswith("global_"))}
 
 
-def loops(lines):
-    """(label, VALU count, packed, transcendental) of every innermost loop body (a label that a later s_cbranch jumps back to)."""
+def blocks(lines):
+    """basic blocks of a kernel: (label, the compiler's loop annotation of the block, its lines)"""
     out = []
-    labels = {ln.split(":")[0]: i for i, ln in enumerate(lines) if re.match(r"\.LBB\d+_\d+:", ln)}
-    for i, ln in enumerate(lines):
-        m = re.match(r"\s+s_cbranch_\w+\s+(\.LBB\d+_\d+)", ln)
-        if m and m.group(1) in labels and labels[m.group(1)] < i:
-            body = lines[labels[m.group(1)]:i + 1]
-            if not any(re.match(r"\.LBB\d+_\d+:", b) for b in body[1:]):
-                out.append((m.group(1),) + count(body))
+    for ln in lines:
+        m = re.match(r"(?:\.L|; %)(BB\d+_\d+|bb\.\d+):\s*(;.*)?$", ln)
+        if m:
+            out.append([m.group(1), m.group(2) or "", []])
+        elif out and re.match(r"\s+;", ln) and not out[-1][2]:
+            out[-1][1] += ln   # the annotation goes on over comment-only lines
+        elif out:
+            out[-1][2].append(ln)
     return out
 
 
-base = kernel_isa([])
-total = count(base)
-rows = [("kernel as shipped (static, every path)", total)]
-variants = [("light walk (cluster index + all four instantiations of the list walk + the sums' zeroing)", ["PBR_EXP_NOLOOP"]),
-            ("IBL specular: reflection vector, cube face, two trilinear levels from the footprint layout, their lerps", ["PBR_EXP_NOENV"]),
-            ("split-sum LUT fetch + bilinear", ["PBR_EXP_NOLUT"]),
-            ("SH9 irradiance (EnvironmentDiffuse)", ["PBR_EXP_NOSH"]),
-            ("all of the IBL specular term (env + LUT)", ["PBR_EXP_NOIBL"])]
-doc = ["# k_deferred_shade<true, 257, false>: VALU instructions per phase (static count of the gfx950 ISA)", "",
-       f"whole kernel: {total[0]} v_* instructions ({total[2]} packed, {total[1]} transcendental, {total[3]} moves)", "",
-       "| phase removed (-D switch) | v_* removed | of them packed | transcendental | moves |", "|---|---|---|---|---|"]
-for name, defs in variants:
-    c = count(kernel_isa(defs))
-    doc.append(f"| {name} (`{' '.join(defs)}`) | {total[0] - c[0]} | {total[2] - c[2]} | {total[1] - c[1]} | {total[3] - c[3]} |")
-doc += ["", "innermost loops of the shipped kernel (the list walks; one of them runs per pixel, `trips` = pairs of lights):", "",
-        "| loop | v_* per trip | packed | transcendental | moves |", "|---|---|---|---|---|"]
-for lb, n, t, pk, mv in loops(base):
-    doc.append(f"| {lb} | {n} | {pk} | {t} | {mv} |")
-text = "\n".join(doc) + "\n"
-print(text)
-if len(sys.argv) > 1:
-    open(sys.argv[1], "w").write(text)
+def walks_and_row(lines):
+    """From the compiler's loop annotations: the walk loops (innermost loops with the per-light arithmetic: >= 40 packed
+    instructions), as (label, lines), and the lines of the row loop around them (its child loops included)."""
+    bl = blocks(lines)
+    heads = [(lb, len(re.findall(r"Child Loop", an))) for lb, an, _ in bl if "This Loop Header: Depth=1" in an]
+    if not heads:
+        return [], []
+    row_head = max(heads, key=lambda h: h[1])[0]
+    member = re.compile(r"(Header=|Parent Loop )" + row_head + r"\b")
+    row, inner = [], {}
+    for lb, an, body in bl:
+        if lb == row_head or member.search(an):
+            row += body
+            m = re.search(r"Header=(BB\d+_\d+) Depth=2", an)
+            own = lb if "This Inner Loop Header: Depth=2" in an else (m.group(1) if m else None)
+            if own:
+                inner.setdefault(own, []).extend(body)
+    return [(lb, body) for lb, body in inner.items() if count(body)["packed"] >= 40], row
+
+
+def measure(src=SRC):
+    with ThreadPoolExecutor(2) as ex:
+        shipped, noexact = ex.map(lambda d: kernel(compile_isa(d, src)), [(), ("PBR_EXP_NOEXACT",)])
+    name, code, foot = shipped
+    walks, row = walks_and_row(code)
+    if not walks or not row:
+        raise SystemExit("no light walk / row loop found in " + name)
+    res = {"name": name, "occupancy": foot["Occupancy"], "scratch": foot["ScratchSize"], "vgprs": foot["NumVgprs"], "kernel": count(code), "walks": []}
+    for lb, body in walks:
+        c = count(body)
+        unroll = max(c["trans"] // 4, 1)
+        res["walks"].append({"label": lb, "unroll": unroll, "body": c, "valu_per_trip": c["valu"] / unroll,
+                             "packed_per_trip": c["packed"] / unroll, "trans_per_trip": c["trans"] / unroll})
+    hot = min(res["walks"], key=lambda w: w["valu_per_trip"])
+    in_walks = sum(w["body"]["valu"] for w in res["walks"])
+    res["row_static"] = count(row)["valu"]
+    # the exact-slice path: the row body of the build without it, walks taken out alike
+    code_n = noexact[1]
+    walks_n, row_n = walks_and_row(code_n)
+    res["surround"] = count(row_n)["valu"] - sum(count(b)["valu"] for _, b in walks_n)
+    res["exact_path"] = res["row_static"] - in_walks - res["surround"]
+    res["hot_trip"] = hot["valu_per_trip"]
+    res["row_executed"] = res["surround"] + TRIPS * hot["valu_per_trip"]
+    return res
+
+
+METRICS = [("occupancy", "occupancy (waves per SIMD)"), ("scratch", "scratch bytes per lane"), ("hot_trip", "v_* per trip, as-shipped walk"),
+           ("surround", "v_* per pixel row around the walk (row body - walk loops - exact-slice path)"),
+           ("row_executed", f"executed v_* per pixel row at {TRIPS} trips, as-shipped walk")]
+
+
+def report(res):
+    k = res["kernel"]
+    doc = ["# k_deferred_shade<true, 257, false, NoViews>: instruction classes of the gfx950 ISA (static counts)", "", f"`{res['name']}`", "",
+           f"whole kernel: {k['valu']} v_* ({k['packed']} packed, {k['trans']} transcendental, {k['moves']} moves), {k['ds']} ds_*, {k['global']} global_*; {res['vgprs']} VGPRs", "",
+           "| metric | value |", "|---|---|"]
+    doc += [f"| {text} | {res[key]:g} |" for key, text in METRICS]
+    doc += ["", f"row body: {res['row_static']} v_* static, of them {sum(w['body']['valu'] for w in res['walks'])} in the walk loops and {res['exact_path']} on the exact-slice path", "",
+            "light walks (one of them runs per pixel; a trip = one pair of lights):", "",
+            "| loop | trips per body | v_* per trip | packed per trip | transcendental per trip | moves per body | ds_* per body |", "|---|---|---|---|---|---|---|"]
+    for w in res["walks"]:
+        doc.append(f"| {w['label']} | {w['unroll']} | {w['valu_per_trip']:g} | {w['packed_per_trip']:g} | {w['trans_per_trip']:g} | {w['body']['moves']} | {w['body']['ds']} |")
+    return doc
+
+
+def parse_metrics(md_text):
+    """{metric key: value} of a report written by this tool"""
+    by_text = {text: key for key, text in METRICS}
+    out = {}
+    for m in re.finditer(r"^\| (.+?) \| ([-0-9.e+]+) \|$", md_text, re.M):
+        if m.group(1) in by_text:
+            out[by_text[m.group(1)]] = float(m.group(2))
+    return out
+
+
+def phases(src=SRC):
+    variants = [("light walk (cluster index + every instantiation of the list walk + the sums' zeroing)", "PBR_EXP_NOLOOP"),
+                ("IBL specular: reflection vector, cube face, two trilinear levels from the footprint layout, their lerps", "PBR_EXP_NOENV"),
+                ("split-sum LUT fetch + bilinear", "PBR_EXP_NOLUT"), ("SH9 irradiance (EnvironmentDiffuse)", "PBR_EXP_NOSH"),
+                ("all of the IBL specular term (env + LUT)", "PBR_EXP_NOIBL")]
+    with ThreadPoolExecutor(3) as ex:
+        cs = list(ex.map(lambda d: count(kernel(compile_isa(d, src))[1]), [()] + [(v[1],) for v in variants]))
+    t = cs[0]
+    doc = ["", "phases (static v_* of the whole kernel, every path):", "", "| phase removed (-D switch) | v_* removed | of them packed | transcendental | moves |", "|---|---|---|---|---|"]
+    for (nm, d), c in zip(variants, cs[1:]):
+        doc.append(f"| {nm} (`{d}`) | {t['valu'] - c['valu']} | {t['packed'] - c['packed']} | {t['trans'] - c['trans']} | {t['moves'] - c['moves']} |")
+    return doc
+
+
+def main(argv):
+    args = [a for a in argv if not a.startswith("--")]
+    src = SRC
+    if "--src" in argv:
+        src = argv[argv.index("--src") + 1]
+        args.remove(src)
+    doc = report(measure(src))
+    if "--phases" in argv:
+        doc += phases(src)
+    text = "\n".join(doc) + "\n"
+    print(text)
+    if args:
+        open(args[0], "w").write(text)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

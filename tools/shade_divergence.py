@@ -99,3 +99,13 @@ def per_wave_cols(t, rows, cols=64):
 for rows in (1, 2, 4, 8, 16):
     if ROWS % rows == 0:
         print(f"pairs per wave-iteration, a wave's own 64 x {rows:2d} pixels sorted by front-facing pairs (k_deferred_shade_ff): {per_wave_cols(ftrips, rows):.2f}")
+
+# the walk takes `step` trips per pointer step and compare, its lists padded to 2 * step entries with the null light: the waves
+# whose longest list is not already a multiple run more trips than the pair-padded walk did
+waves = trips.reshape(ROWS, W // 64, 64).max(axis=2)
+live = waves > 0
+for step in (2, 4):
+    padded = (step * np.maximum((n + 2 * step - 1) // (2 * step), 1) * covered).reshape(ROWS, W // 64, 64).max(axis=2)
+    print(f"walk unrolled by {step} (lists padded to {2 * step}): {np.mean(padded[live] > waves[live]):.2%} of the waves gain trips, "
+          f"trips per wave {waves[live].mean():.3f} -> {padded[live].mean():.3f} ({padded[live].sum() / waves[live].sum() - 1:+.2%}); "
+          f"waves at the 16-trip cap: {np.mean(waves[live] == 16):.1%}")
