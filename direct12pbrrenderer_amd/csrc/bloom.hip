@@ -1,25 +1,20 @@
-// bloom.hip — bloom chain on gfx950: soft-knee prefilter, separable 9-tap Gaussian pyramid,
-// upsample-add and merge (bloom_prefilter.hlsl, blur.hlsli, blur_horizontal/vertical.hlsl,
-// bloom_upsample_add.hlsl, bloom_merge.hlsl; schedule BloomPass::Execute,
-// DeferredPipeline.cpp:400-570).
+// bloom.hip — bloom chain on gfx950: soft-knee prefilter, separable 9-tap Gaussian pyramid, upsample-add and merge
+// (bloom_prefilter.hlsl, blur.hlsli, blur_horizontal/vertical.hlsl, bloom_upsample_add.hlsl, bloom_merge.hlsl; schedule
+// BloomPass::Execute, DeferredPipeline.cpp:400-570).  Compiled with -ffp-contract=off and written in the oracle's operation order
+// (fused multiply-adds only where the oracle writes fmaf: sampler lerps and the blur's multiply-accumulate), so every stage is
+// bit-identical to the CPU oracle on the same input; k_blur_up_poly alone is ULP-bounded (see there).
 //
-// This translation unit is compiled with -ffp-contract=off and follows the oracle's operation
-// order (fused multiply-adds only where the oracle writes fmaf: sampler lerps and the blur's
-// multiply-accumulate), so every stage is bit-identical to the CPU oracle on the same input.
-//
-// Two sets of kernels, bit-identical to each other:
-//  * the STAGED kernels below, one per reference dispatch (pbr_bloom_prefilter, pbr_blur_h, pbr_blur_v,
-//    pbr_bloom_upsample_add, pbr_bloom_merge; any image size) — what the host pass graph issues one by one;
-//  * the FUSED kernels further down (k_bloom_prefilter_2x, k_blur_hv), which pbr_bloom / pbr_bloom_histogram use on
-//    an exact 2x pyramid: shared prefilter samples, H + V pass of a level in one kernel, merge + histogram in the last.
-//
-// Layout / mapping of the staged kernels for MI355X:
-//  * H passes keep the reference's 256-texel row groups (one 64-lane wave = 64 consecutive
-//    texels = one 512-byte half4 segment), the bilinear-sampled row is cached in LDS as float4
-//    (264 entries, ds_read_b128, conflict-free) exactly like blur.hlsli's Cache[].
-//  * V passes do NOT use the reference's 1x256 column groups (one texel per 8 KiB-strided row =
-//    64 cache lines per wave); they use 64x16 tiles: lanes run along x, the (16+8) sampled rows
-//    of the tile are staged through LDS, so global accesses stay 512-byte coalesced.
+// Map of the file:
+//  1. STAGED kernels, one per reference dispatch, any image size (k_bloom_prefilter, k_blur_h, k_blur_v, k_bloom_merge), and
+//     k_blur_v_merge = the last V pass + merge + histogram.  H passes keep the reference's 256-texel row groups with the sampled
+//     row in LDS like blur.hlsli's Cache[]; V passes use 64 x 16 tiles staged through LDS (vtile_*), not the reference's 1 x 256
+//     column groups (one texel per 8 KiB-strided row), so that global accesses stay 512-byte coalesced.
+//  2. Pieces the merging kernels share: luminance bin, per-wave histograms (hist_*), the merge rounding (merge_rounded*).
+//  3. FUSED kernels for exact 2x pyramids, bit-identical to the staged ones: k_bloom_prefilter_2x (shared samples), k_blur_hv
+//     (H + V of a level [+ merge + histogram] on a tile) and k_blur_up_poly (large 2x-up levels), with what those two share:
+//     TailRect and its tests, level_args (view selection), level_alpha, wave_sync.
+//  4. Launch: tail_rect / tile_grid / launch_hv (the fused kernels' choice), prefilter_launch, the checks entry points share.
+//  5. C ABI of the staged passes; the schedule (bloom_pass, up_pass_rects); C ABI of the chain.
 #include <type_traits>
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
@@ -44,6 +39,17 @@ struct OutRects {
     int n, ox, oy, pitch;
     int x0[PF_MAX_RECTS], y0[PF_MAX_RECTS], x1[PF_MAX_RECTS], y1[PF_MAX_RECTS], tiles_x[PF_MAX_RECTS], first[PF_MAX_RECTS + 1];
 };
+// bloom_prefilter.hlsl:36-47 — one bilinear sample c through the soft knee (its three IEEE divides): (colour x weight, weight)
+__device__ __forceinline__ float4 soft_knee_sample(F4 c, float threshold, float knee) {
+    const float brightness = fmaxf(c.x, fmaxf(c.y, c.z));
+    float soft = fminf(fmaxf(brightness - threshold + threshold * knee, 0.0f), 2.0f * threshold * knee);
+    soft /= 4.0f * threshold * knee + 0.00001f;
+    const float contribution = fmaxf(soft, brightness - threshold) / fmaxf(brightness, 0.00001f);
+    const float cr = c.x * contribution, cg = c.y * contribution, cb = c.z * contribution;
+    const float wgt = 1.0f / (luminance(cr, cg, cb) + 1.0f);
+    return make_float4(cr * wgt, cg * wgt, cb * wgt, wgt);
+}
+
 __global__ __launch_bounds__(256) void k_bloom_prefilter(const pbr_half* __restrict__ hdr, int w, int h, int pitch,
                                                            pbr_half* __restrict__ out, OutRect rc,
                                                            float tx, float ty, float threshold, float knee) {
@@ -56,15 +62,9 @@ __global__ __launch_bounds__(256) void k_bloom_prefilter(const pbr_half* __restr
     float tr = 0.0f, tg = 0.0f, tb = 0.0f, tw = 0.0f;
 #pragma unroll
     for (int i = 0; i < 5; i++) {
-        const F4 c = sample_2d_h4(hdr, w, h, pitch, u + ox[i] * tx, v + oy[i] * ty);
-        const float brightness = fmaxf(c.x, fmaxf(c.y, c.z));
-        float soft = fminf(fmaxf(brightness - threshold + threshold * knee, 0.0f), 2.0f * threshold * knee);
-        soft /= 4.0f * threshold * knee + 0.00001f;
-        const float contribution = fmaxf(soft, brightness - threshold) / fmaxf(brightness, 0.00001f);
-        const float cr = c.x * contribution, cg = c.y * contribution, cb = c.z * contribution;
-        const float wgt = 1.0f / (luminance(cr, cg, cb) + 1.0f);
-        tr += cr * wgt; tg += cg * wgt; tb += cb * wgt;
-        tw += wgt;
+        const float4 s = soft_knee_sample(sample_2d_h4(hdr, w, h, pitch, u + ox[i] * tx, v + oy[i] * ty), threshold, knee);
+        tr += s.x; tg += s.y; tb += s.z;
+        tw += s.w;
     }
     if (tw > 0.0f) { tr /= tw; tg /= tw; tb /= tw; }
     store_h4(out + 4 * ((size_t)(y + rc.oy) * rc.pitch + (x + rc.ox)), f4(tr, tg, tb, 1.0f));
@@ -74,8 +74,7 @@ __global__ __launch_bounds__(256) void k_bloom_prefilter(const pbr_half* __restr
 // One 256-thread group = 256 consecutive output texels of a row, the bilinear-sampled row cached in LDS
 // (264 float4 entries incl. the 4+4 halo slots) exactly like the shader's Cache[].  A block walks HB_ROWS
 // rows of its column group and software-pipelines them: the four raw taps of row r+1 are in flight while
-// row r is filtered out of a double-buffered cache (one barrier per row).  The stand-alone one-row block
-// was latency-bound (one dependent HBM round trip per 256 outputs, SQ_WAIT_ANY ~50 %).
+// row r is filtered out of a double-buffered cache (one barrier per row); a one-row block is latency-bound.
 constexpr int HB_MAX_ROWS = 8;   // rows per block: chosen per launch so that small pyramid levels still fill the chip
 struct RawTap {   // the four texels of one bilinear sample, still in half precision, + the y weight
     H4 c00, c10, c01, c11;
@@ -157,45 +156,48 @@ __global__ __launch_bounds__(256) void k_blur_h(const pbr_half* __restrict__ in,
 // 64 x 16 output tiles; TR divides 256 so a tile never straddles one of the reference's
 // 256-row groups, which decides whether a halo row uses the group-edge position formula.
 constexpr int VT_W = 64, VT_R = 16;
+// the tile's VT_R + 8 sampled rows y0 - 4 .. y0 + VT_R + 3 at column x into LDS (block (VT_W, 4): thread row threadIdx.y takes every fourth)
+__device__ __forceinline__ void vtile_sample(float4 (*smp)[VT_W], const pbr_half* __restrict__ in, int iw, int ih, int x, int y0, float tx, float ty) {
+    const bool top_edge = (y0 & 255) == 0;
+    const bool bot_edge = ((y0 + VT_R) & 255) == 0;
+    const float uvx = ((float)x + 0.5f) * tx;
+    for (int r = threadIdx.y; r < VT_R + 8; r += 4) {
+        const int j = y0 - 4 + r;   // sampled row (may be outside the image)
+        float vy;
+        if (r < 4 && top_edge) vy = fmaxf(((float)(j + 4) + 0.5f) * ty - 4.0f * ty, 0.0f);                  // Cache[gtid.y], gtid.y < 4
+        else if (r >= VT_R + 4 && bot_edge) vy = fminf(((float)(j - 4) + 0.5f) * ty + 4.0f * ty, 1.0f);   // Cache[gtid.y + 8], gtid.y >= 252
+        else vy = ((float)j + 0.5f) * ty;
+        smp[r][threadIdx.x] = to4(sample_2d_h4(in, iw, ih, iw, uvx, vy));
+    }
+}
+// the nine taps of output row r of the tile, down this thread's column
+__device__ __forceinline__ F4 vtile_gauss9(const float4 (*smp)[VT_W], int r) {
+    F4 v = f4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int i = 0; i < 9; i++) v = fma4(from4(smp[r + i][threadIdx.x]), c_gauss[i], v);
+    return v;
+}
+
 __global__ __launch_bounds__(256) void k_blur_v(const pbr_half* __restrict__ in, int iw, int ih,
                                                  pbr_half* __restrict__ out, int ow, int oh, float tx, float ty) {
     __shared__ float4 smp[VT_R + 8][VT_W];
     const int x = blockIdx.x * VT_W + threadIdx.x;
     const int y0 = blockIdx.y * VT_R;
-    const bool top_edge = (y0 & 255) == 0;
-    const bool bot_edge = ((y0 + VT_R) & 255) == 0;
-    const float uvx = ((float)x + 0.5f) * tx;
-    for (int r = threadIdx.y; r < VT_R + 8; r += 4) {
-        const int j = y0 - 4 + r;   // sampled row (may be outside [0, oh))
-        float vy;
-        if (r < 4 && top_edge) {
-            vy = fmaxf(((float)(j + 4) + 0.5f) * ty - 4.0f * ty, 0.0f);     // Cache[gtid.y], gtid.y < 4
-        } else if (r >= VT_R + 4 && bot_edge) {
-            vy = fminf(((float)(j - 4) + 0.5f) * ty + 4.0f * ty, 1.0f);     // Cache[gtid.y + 8], gtid.y >= 252
-        } else {
-            vy = ((float)j + 0.5f) * ty;
-        }
-        smp[r][threadIdx.x] = to4(sample_2d_h4(in, iw, ih, iw, uvx, vy));
-    }
+    vtile_sample(smp, in, iw, ih, x, y0, tx, ty);
     __syncthreads();
     if (x >= ow) return;
     for (int r = threadIdx.y; r < VT_R; r += 4) {
         const int y = y0 + r;
         if (y >= oh) break;
-        F4 v = f4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll
-        for (int i = 0; i < 9; i++) v = fma4(from4(smp[r + i][threadIdx.x]), c_gauss[i], v);
-        store_h4(out + 4 * ((size_t)y * ow + x), v);
+        store_h4(out + 4 * ((size_t)y * ow + x), vtile_gauss9(smp, r));
     }
 }
 
-// ---------------------------------------------------------------- final three dispatches fused
-// A0 = V(B0) (blur_vertical.hlsl), S += A0 (bloom_merge.hlsl) and — optionally — the luminance
-// histogram of the merged pixel (hdr_luminance_histogram.hlsl:23-59), in one pass over the frame:
-// A0 is never written to HBM (nobody reads it afterwards) and the histogram pass no longer re-reads
-// the HDR buffer.  Every intermediate is rounded exactly where the separate dispatches round
-// (A0 to fp16, then the fp16 sum), so the HDR result is bit-identical to the unfused chain.
-// Persistent blocks walk 64x16 tiles so the per-wave LDS histograms are flushed once per block.
+// ---------------------------------------------------------------- final three dispatches fused: shared pieces, k_blur_v_merge
+// A0 = V(B0) (blur_vertical.hlsl), S += A0 (bloom_merge.hlsl) and — optionally — the luminance histogram of the merged pixel
+// (hdr_luminance_histogram.hlsl:23-59) in one pass over the frame: A0 is never written to HBM and the histogram does not re-read
+// the HDR buffer.  Every intermediate is rounded exactly where the separate dispatches round, so the HDR result is bit-identical
+// to the unfused chain.
 __device__ __forceinline__ uint32_t luminance_bin_exact(float r, float g, float b, float min_log, float inv_range) {
     const float lum = (r * 0.2126f + g * 0.7152f) + b * 0.0722f;
     if (lum < EPSILON_F) return 0u;
@@ -204,48 +206,76 @@ __device__ __forceinline__ uint32_t luminance_bin_exact(float r, float g, float 
     return (uint32_t)floorf(l * 254.0f + 1.0f);
 }
 
+// Per-wave LDS histograms of a block of NT threads (thread t): cleared at the start, summed into the global one at the end.  The
+// caller puts a barrier between the clear, its atomicAdds and the flush.
+template <int NT, int NH, int NB>
+__device__ __forceinline__ void hist_clear(uint32_t (&sh)[NH][NB], int t) {
+    for (int i = t; i < NH * NB; i += NT) (&sh[0][0])[i] = 0u;
+}
+template <int NT, int NH, int NB>
+__device__ __forceinline__ void hist_flush(const uint32_t (&sh)[NH][NB], int t, uint32_t* __restrict__ hist) {
+    static_assert(NT >= NB, "one bin per thread");
+    if (NT == NB || t < NB) {
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < NH; k++) sum += sh[k][t];
+        if (sum) atomicAdd(&hist[t], sum);
+    }
+}
+
+// The merge rounding: the V pass's fp32 result `a` rounded to fp16 as the separate pass would have stored it (A0), then the fp16 sum
+// with the HDR texel.  Two variants of the same roundings, because the form decides the instructions: k_blur_hv and k_blur_v_merge
+// convert component by component (the texel is read and the result written through references: returned by value, the H4 costs
+// k_blur_hv 16 pack instructions); k_blur_up_poly, bound by VALU issue, rounds PAIRS in one v_cvt_pk_f16_f32 and takes the
+// constant alpha's A0 (a0w, already rounded) once per thread.
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+typedef float float2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void merge_rounded(F4 a, const H4& hdr, H4& o) {
+    H4 a0;
+    a0.x = to_half_rn(a.x); a0.y = to_half_rn(a.y); a0.z = to_half_rn(a.z); a0.w = to_half_rn(a.w);
+    const F4 s = h4f(hdr);
+    o.x = to_half_rn(s.x + (float)a0.x); o.y = to_half_rn(s.y + (float)a0.y); o.z = to_half_rn(s.z + (float)a0.z); o.w = to_half_rn(s.w + (float)a0.w);
+}
+// two to_half_rn in one v_cvt_pk_f16_f32 (same rounding); the halves are read back out of the packed register
+__device__ __forceinline__ half2v round_h2(float a, float b) {
+    asm volatile("" : "+v"(a), "+v"(b));
+    float2v f; f.x = a; f.y = b;
+    return __builtin_convertvector(f, half2v);
+}
+struct alignas(8) H4Packed { half2v lo, hi; };
+__device__ __forceinline__ H4Packed merge_rounded_packed(V3 a, float a0w, F4 s) {
+    const half2v a01 = round_h2(a.x, a.y);
+    const h16 a2 = to_half_rn(a.z);
+    H4Packed o;
+    o.lo = round_h2(s.x + (float)a01.x, s.y + (float)a01.y);
+    o.hi = round_h2(s.z + (float)a2, s.w + a0w);
+    return o;
+}
+
 template <bool HIST>
 __global__ __launch_bounds__(256) void k_blur_v_merge(const pbr_half* __restrict__ in, int w, int h, float tx, float ty,
                                                        pbr_half* __restrict__ hdr, int pitch, int tiles_x, int tiles_y,
                                                        int hx0, int hy0, int hx1, int hy1, float min_log, float inv_range,
                                                        uint32_t* __restrict__ hist) {
     __shared__ float4 smp[VT_R + 8][VT_W];
-    __shared__ uint32_t sh_hist[HIST ? 4 : 1][HIST ? PBR_HISTOGRAM_BINS : 1];
+    __shared__ uint32_t sh_hist[HIST ? 4 : 1][HIST ? PBR_HISTOGRAM_BINS : 1];   // persistent blocks: flushed once per block
     const int tid = threadIdx.y * VT_W + threadIdx.x;
-    if (HIST) {
-        for (int i = tid; i < 4 * PBR_HISTOGRAM_BINS; i += 256) (&sh_hist[0][0])[i] = 0u;
-    }
+    if (HIST) hist_clear<256>(sh_hist, tid);
     const int n_tiles = tiles_x * tiles_y;
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int x = (tile % tiles_x) * VT_W + threadIdx.x;
         const int y0 = (tile / tiles_x) * VT_R;
-        const bool top_edge = (y0 & 255) == 0;
-        const bool bot_edge = ((y0 + VT_R) & 255) == 0;
-        const float uvx = ((float)x + 0.5f) * tx;
         __syncthreads();   // previous tile's reads of smp are done (and the histogram clear on the first trip)
-        for (int r = threadIdx.y; r < VT_R + 8; r += 4) {
-            const int j = y0 - 4 + r;
-            float vy;
-            if (r < 4 && top_edge) vy = fmaxf(((float)(j + 4) + 0.5f) * ty - 4.0f * ty, 0.0f);
-            else if (r >= VT_R + 4 && bot_edge) vy = fminf(((float)(j - 4) + 0.5f) * ty + 4.0f * ty, 1.0f);
-            else vy = ((float)j + 0.5f) * ty;
-            smp[r][threadIdx.x] = to4(sample_2d_h4(in, w, h, w, uvx, vy));
-        }
+        vtile_sample(smp, in, w, h, x, y0, tx, ty);
         __syncthreads();
         if (x < w) {
             for (int r = threadIdx.y; r < VT_R; r += 4) {
                 const int y = y0 + r;
                 if (y >= h) break;
-                F4 v = f4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll
-                for (int i = 0; i < 9; i++) v = fma4(from4(smp[r + i][threadIdx.x]), c_gauss[i], v);
-                // A0 texel as the separate pass would have stored it
-                H4 a0;
-                a0.x = to_half_rn(v.x); a0.y = to_half_rn(v.y); a0.z = to_half_rn(v.z); a0.w = to_half_rn(v.w);
+                const F4 v = vtile_gauss9(smp, r);
                 pbr_half* px = hdr + 4 * ((size_t)y * pitch + x);
-                const F4 s = load_h4(px);
                 H4 o;
-                o.x = to_half_rn(s.x + (float)a0.x); o.y = to_half_rn(s.y + (float)a0.y); o.z = to_half_rn(s.z + (float)a0.z); o.w = to_half_rn(s.w + (float)a0.w);
+                merge_rounded(v, *reinterpret_cast<const H4*>(px), o);
                 *reinterpret_cast<H4*>(px) = o;
                 if (HIST) {
                     if (x >= hx0 && x < hx1 && y >= hy0 && y < hy1)
@@ -256,8 +286,7 @@ __global__ __launch_bounds__(256) void k_blur_v_merge(const pbr_half* __restrict
     }
     if (HIST) {
         __syncthreads();
-        const uint32_t s = (sh_hist[0][tid] + sh_hist[1][tid]) + (sh_hist[2][tid] + sh_hist[3][tid]);
-        if (s) atomicAdd(&hist[tid], s);
+        hist_flush<256>(sh_hist, tid, hist);
     }
 }
 
@@ -271,19 +300,15 @@ __global__ __launch_bounds__(256) void k_bloom_merge(pbr_half* __restrict__ hdr,
 }
 
 // =====================================================================================================
-// Fast paths for exact 2x pyramids (every level exactly half the one above, sizes <= 8192).
+// Fused kernels for exact 2x pyramids (every level exactly half the one above, sizes <= 8192).
 //
-// With the fixed-point sampler (pbr_device.hpp::bilinear_coord) every sample position of the bloom chain then
-// snaps to an exact dyadic coordinate: a same-size sample IS the texel, a 2x-down sample is the mean of a 2x2
-// quad (weights 1/2), a 2x-up sample has weights 1/4 | 3/4 — whatever float formula produced the coordinate
-// (the shader's group-edge formulas, `u + offset * texel`, ...).  So a sample is a function of its INTEGER
-// position alone, positions outside the image read the clamped edge texel, and
-//   * the prefilter's five samples per output are shared between neighbouring outputs (evaluated once per
-//     position, 1.16 instead of 5 evaluations per output — they carry the three IEEE divides of the soft knee),
-//   * the V pass's same-size "bilinear" sample is an exact texel of its own column, so H pass + V pass fuse
-//     into one kernel: a thread owns a column, walks down the rows and keeps the last nine H-blurred texels
-//     (rounded to fp16 exactly where the H pass would have stored them) in registers — the H result never
-//     goes to HBM.  The final instance adds the merge and the luminance histogram.
+// With the fixed-point sampler (pbr_device.hpp::bilinear_coord) every sample position of the bloom chain then snaps to an exact
+// dyadic coordinate: a same-size sample IS the texel, a 2x-down sample is the mean of a 2x2 quad, a 2x-up sample has weights
+// 1/4 | 3/4 — whatever float formula produced the coordinate (the shader's group-edge formulas, `u + offset * texel`, ...).  So a
+// sample is a function of its INTEGER position alone, positions outside the image read the clamped edge texel, and
+//   * the prefilter's five samples per output are shared between neighbouring outputs (1.16 instead of 5 evaluations per output),
+//   * the V pass's same-size sample is an exact texel of its own column, so H pass + V pass of a level fuse into one kernel whose
+//     H result (rounded to fp16 exactly where the H pass would have stored it) stays in LDS; the last level adds merge + histogram.
 // Results are bit-identical to the staged kernels above (tests/test_gpu_parity.py), which remain the generic path.
 
 constexpr int PF_TW = 64, PF_TH = 16;
@@ -300,6 +325,8 @@ struct LevelViews {
 template <class VS = NoViews>
 __global__ __launch_bounds__(256) void k_bloom_prefilter_2x(const pbr_half* __restrict__ hdr_, int w, int h, int pitch_, VS vs,
                                                               pbr_half* __restrict__ out_, OutRects rs, float threshold, float knee) {
+    // (the view selection stays in the kernel body, unlike level_args below: behind a helper of either shape this instantiation's
+    //  two-quad loop comes out with 40 register copies more)
     const pbr_half* __restrict__ hdr = hdr_;
     pbr_half* __restrict__ out = out_;
     int pitch = pitch_;
@@ -313,8 +340,7 @@ __global__ __launch_bounds__(256) void k_bloom_prefilter_2x(const pbr_half* __re
     const int bx0 = rc.x0 + (lb % rs.tiles_x[r]) * PF_TW, by0 = rc.y0 + (lb / rs.tiles_x[r]) * PF_TH;   // tiles are laid over the output rect
     const int px0 = bx0 - 1, py0 = by0 - 1;
     // one position = the quad (2p-1, 2p) x (2q-1, 2q), weights 1/2 (position p samples u = p / ow: texel coordinate 2p - 1/2).  The four
-    // texels of the NEXT position of this thread are loaded before the current one is evaluated (its three IEEE divides): eight loads in
-    // flight per thread instead of four (round 4)
+    // texels of the NEXT position of this thread are loaded before the current one is evaluated: eight loads in flight per thread
     struct Quad { H4 a, b, c, d; };
     auto load_quad = [&](int e) {
         const int r = e / (PF_TW + 2), c = e - r * (PF_TW + 2);
@@ -328,14 +354,7 @@ __global__ __launch_bounds__(256) void k_bloom_prefilter_2x(const pbr_half* __re
     constexpr int NPOS = (PF_TH + 2) * (PF_TW + 2);
     auto evaluate = [&](int e, const Quad& t) {
         const int r = e / (PF_TW + 2), c = e - r * (PF_TW + 2);
-        const F4 s = bilerp(h4f(t.a), h4f(t.b), h4f(t.c), h4f(t.d), 0.5f, 0.5f);
-        const float brightness = fmaxf(s.x, fmaxf(s.y, s.z));
-        float soft = fminf(fmaxf(brightness - threshold + threshold * knee, 0.0f), 2.0f * threshold * knee);
-        soft /= 4.0f * threshold * knee + 0.00001f;
-        const float contribution = fmaxf(soft, brightness - threshold) / fmaxf(brightness, 0.00001f);
-        const float cr = s.x * contribution, cg = s.y * contribution, cb = s.z * contribution;
-        const float wgt = 1.0f / (luminance(cr, cg, cb) + 1.0f);
-        pos[r][c] = make_float4(cr * wgt, cg * wgt, cb * wgt, wgt);
+        pos[r][c] = soft_knee_sample(bilerp(h4f(t.a), h4f(t.b), h4f(t.c), h4f(t.d), 0.5f, 0.5f), threshold, knee);
     };
     // two register sets in turn (a copy `cur = nxt` would wait for the next quad's data at the end of every trip)
     Quad qa = load_quad(tid);   // tid < 256 < NPOS
@@ -388,30 +407,6 @@ __device__ __forceinline__ Tap2 load_tap2(const pbr_half* __restrict__ in, int i
     }
     return t;
 }
-template <int MODE>
-__device__ __forceinline__ float4 finish_tap2(const Tap2& t, float fx, float fy) {
-    if (MODE == M_SAME) return to4(h4f(t.c00));
-    // weights are 1/4, 1/2 or 3/4 here — never 0, so lerp4's zero-weight select is dead: same values, fewer instructions
-    const float wx0 = 1.0f - fx, wy0 = 1.0f - fy;
-    const F4 top = fma4(h4f(t.c10), fx, h4f(t.c00) * wx0);
-    const F4 bot = fma4(h4f(t.c11), fx, h4f(t.c01) * wx0);
-    return to4(fma4(bot, fy, top * wy0));
-}
-
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-// two to_half_rn in one v_cvt_pk_f16_f32 (same rounding); the halves are read back out of the packed register
-__device__ __forceinline__ half2v round_h2(float a, float b) {
-    asm volatile("" : "+v"(a), "+v"(b));
-    float2v f; f.x = a; f.y = b;
-    return __builtin_convertvector(f, half2v);
-}
-__device__ __forceinline__ half4v round_h4(F4 v) {
-    half4v r;
-    r.x = to_half_rn(v.x); r.y = to_half_rn(v.y); r.z = to_half_rn(v.z); r.w = to_half_rn(v.w);
-    return r;
-}
 
 // rgb-only variants: inside pbr_bloom the alpha of every chain level is one constant per level (the prefilter writes
 // 1, and every later pass filters a constant field with clamp addressing), so the fused kernels filter three
@@ -421,7 +416,8 @@ __device__ __forceinline__ V3 fma3(V3 a, float s, V3 b) { return v3(__builtin_fm
 template <int MODE>
 __device__ __forceinline__ float4 finish_tap2_rgb(const Tap2& t, float fx, float fy) {
     if (MODE == M_SAME) return make_float4((float)t.c00.x, (float)t.c00.y, (float)t.c00.z, 0.0f);
-    const float wx0 = 1.0f - fx, wy0 = 1.0f - fy;   // weights 1/4, 1/2, 3/4: never 0 (see finish_tap2)
+    // weights are 1/4, 1/2 or 3/4 here — never 0, so lerp4's zero-weight select is dead: same values, fewer instructions
+    const float wx0 = 1.0f - fx, wy0 = 1.0f - fy;
     const V3 top = fma3(h3f(t.c10), fx, h3f(t.c00) * wx0);
     const V3 bot = fma3(h3f(t.c11), fx, h3f(t.c01) * wx0);
     const V3 r = fma3(bot, fy, top * wy0);
@@ -456,6 +452,39 @@ __device__ __forceinline__ float gauss9_const(float c) {   // the nine fused mad
 // A single-GPU frame merges everything; a multi-GPU tile in halo mode merges (and counts) only its interior, which
 // is all its HDR buffer covers beyond a 4-pixel rim.
 struct TailRect { int tx0, ty0, mx0, my0, mx1, my1, bx, by, hx0, hy0, hx1, hy1; };
+__device__ __forceinline__ bool merge_has_x(const TailRect& tr, int x) { return x >= tr.mx0 && x < tr.mx1; }   // the merge rect lies inside the level: implies x < ow
+__device__ __forceinline__ bool merge_has(const TailRect& tr, bool has_x, int y) { return has_x && y >= tr.my0 && y < tr.my1; }
+__device__ __forceinline__ bool hist_has(const TailRect& tr, int x, int y) { return x >= tr.hx0 && x < tr.hx1 && y >= tr.hy0 && y < tr.hy1; }
+
+// what a fused level kernel works on: its own arguments (NoViews), or view blockIdx.y of the view table
+struct LevelArgs { const pbr_half* in; const pbr_half* in2; pbr_half* out; uint32_t* hist; int out_pitch; };
+template <class VS>
+__device__ __forceinline__ LevelArgs level_args(const VS& vs, const pbr_half* in, const pbr_half* in2, pbr_half* out, uint32_t* hist, int out_pitch) {
+    if constexpr (std::is_same_v<VS, NoViews>) return LevelArgs{in, in2, out, hist, out_pitch};
+    else { const int v = blockIdx.y; return LevelArgs{vs.in[v], vs.in2[v], vs.out[v], vs.hist[v], vs.out_pitch[v]}; }
+}
+
+// The level's constant alpha: through the H pass (+ the second input's) and its fp16 store (t), then through the V pass (v).
+// It is read at a texel that the launch's rectangle decides.  With a rectangle (tiled bloom) the producer of `in` was itself run on
+// a rectangle and left texel 0 of the level untouched, so the read is at the merge rect's corner — halved for M_UP, where `in` is
+// the coarser level; without a rectangle that corner is texel 0.  M_SAME / M_DOWN levels are never run on a rectangle: texel 0.
+struct LevelAlpha { h16 t; float v; };
+template <int MODE, bool DUAL>
+__device__ __forceinline__ LevelAlpha level_alpha(const pbr_half* __restrict__ in, int iw, int ih, const pbr_half* __restrict__ in2, int ow, int oh, const TailRect& tr) {
+    const size_t a_at = MODE == M_UP ? (size_t)min(tr.my0 >> 1, ih - 1) * iw + min(tr.mx0 >> 1, iw - 1) : (size_t)0;
+    float alpha_h = gauss9_const((float)reinterpret_cast<const H4*>(in)[a_at].w);
+    if (DUAL) alpha_h = alpha_h + gauss9_const((float)reinterpret_cast<const H4*>(in2)[(size_t)min(tr.my0, oh - 1) * ow + min(tr.mx0, ow - 1)].w);
+    const h16 alpha_t = to_half_rn(alpha_h);
+    return LevelAlpha{alpha_t, gauss9_const((float)alpha_t)};
+}
+
+// Lanes of one wave exchange data through LDS without a block barrier: DS operations of a wave execute in order, but the compiler
+// must be told that other lanes' slots are read (per-thread alias analysis would let it hoist the loads above the store).
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 template <int MODE, bool DUAL, int TAIL, int TH, int NT, class VS = NoViews>   // TAIL 0: store; 1: merge into hdr; 2: merge + histogram
 __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ in_, int iw, int ih,
@@ -464,15 +493,7 @@ __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ 
                                                  int tiles_x, int n_tiles,
                                                  TailRect tr, float min_log, float inv_range, VS vs,
                                                  uint32_t* __restrict__ hist_) {
-    const pbr_half* __restrict__ in = in_;
-    const pbr_half* __restrict__ in2 = in2_;
-    pbr_half* __restrict__ out = out_;
-    uint32_t* __restrict__ hist = hist_;
-    int out_pitch = out_pitch_;
-    if constexpr (!std::is_same_v<VS, NoViews>) {   // LevelViews: view blockIdx.y
-        const int v = blockIdx.y;
-        in = vs.in[v]; in2 = vs.in2[v]; out = vs.out[v]; hist = vs.hist[v]; out_pitch = vs.out_pitch[v];
-    }
+    const auto [in, in2, out, hist, out_pitch] = level_args(vs, in_, in2_, out_, hist_, out_pitch_);
     constexpr int TW = 64, SW = TW + 8, SR = TH + 8;
     constexpr int NW = NT / 64;
     constexpr int PER_T = SR / NW;                      // sampled / H-gaussed rows per wave: rows wv*PER_T .. +PER_T-1
@@ -483,17 +504,8 @@ __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ 
     __shared__ uint32_t sh_hist[TAIL == 2 ? NW : 1][TAIL == 2 ? PBR_HISTOGRAM_BINS : 1];
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);   // wave-uniform: row arithmetic stays on the scalar unit
-    if (TAIL == 2) {
-        for (int i = t; i < NW * PBR_HISTOGRAM_BINS; i += NT) (&sh_hist[0][0])[i] = 0u;
-    }
-    // the level's constant alpha through the H pass (+ the second input's), its fp16 store, and the V pass
-    // (read at a texel the launch's rectangle depends on: with a rectangle (tiled bloom) the producer of `in` was itself run on a
-    //  rectangle and left texel 0 of the level untouched; M_UP: `in` is the coarser level.  No rectangle: texel 0, as ever)
-    const size_t a_at = MODE == M_UP ? (size_t)min(tr.my0 >> 1, ih - 1) * iw + min(tr.mx0 >> 1, iw - 1) : (size_t)0;
-    float alpha_h = gauss9_const((float)reinterpret_cast<const H4*>(in)[a_at].w);
-    if (DUAL) alpha_h = alpha_h + gauss9_const((float)reinterpret_cast<const H4*>(in2)[(size_t)min(tr.my0, oh - 1) * ow + min(tr.mx0, ow - 1)].w);
-    const h16 alpha_t = to_half_rn(alpha_h);
-    const float alpha_v = gauss9_const((float)alpha_t);
+    if (TAIL == 2) hist_clear<NT>(sh_hist, t);
+    const LevelAlpha alpha = level_alpha<MODE, DUAL>(in, iw, ih, in2, ow, oh, tr);
     // 1-D grid over tiles; the histogram instance is launched with fewer blocks than tiles (each walks several) so
     // that the per-block flush of 256 global atomics stays rare
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -501,12 +513,12 @@ __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ 
     const int x = x0 + lane;
     // the HDR texels the merge will need: in flight from the start
     H4 hdr_in[PER_O];
-    const bool in_mx = TAIL != 0 && x >= tr.mx0 && x < tr.mx1;   // merge rect lies inside the level: implies x < ow
+    const bool in_mx = TAIL != 0 && merge_has_x(tr, x);
     if (TAIL != 0) {
 #pragma unroll
         for (int k = 0; k < PER_O; k++) {
             const int y = y0 + wv + NW * k;
-            if (in_mx && y >= tr.my0 && y < tr.my1) hdr_in[k] = *reinterpret_cast<const H4*>(out + 4 * ((size_t)(y - tr.by) * out_pitch + (x - tr.bx)));
+            if (merge_has(tr, in_mx, y)) hdr_in[k] = *reinterpret_cast<const H4*>(out + 4 * ((size_t)(y - tr.by) * out_pitch + (x - tr.bx)));
         }
     }
     // positions: columns x0-4+c (c = 0..71), rows clamp(y0-4+r) (r = 0..SR-1).  Main tap of row k: c = lane; the halo
@@ -516,14 +528,6 @@ __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ 
     const int hk = lane >> 3, hc = 64 + (lane & 7);
     float4* line = sLine[0][wv];
     float4* line2 = sLine[DUAL ? 1 : 0][wv];
-    // lanes of one wave exchange data through `line` without a block barrier: DS operations of a wave execute in
-    // order, but the compiler must be told that other lanes' slots are read (per-thread alias analysis would let it
-    // hoist the loads above the store)
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     {
         Tap2 htap;
         H4 up[DUAL ? PER_T : 1], hup;   // DUAL: the same-size input of bloom_upsample_add, exact texels
@@ -556,7 +560,6 @@ __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ 
 #pragma unroll
                 for (int k = 0; k < PER_T; k++) {
                     // output row first + k = 2m (+1): input rows (i0, i0 + 1) relative to base, second-tap weight 3/4 (1/4)
-                    constexpr int dummy = 0; (void)dummy;
                     const int odd = (P + k) & 1;
                     const int i0 = (P + k + 1) / 2 - P;          // even start: 0,1,1,2,2,3   odd start: 0,0,1,1,2,2
                     const float fyk = odd ? 0.25f : 0.75f, wy0 = 1.0f - fyk;
@@ -602,7 +605,7 @@ __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ 
             if (DUAL) g = g + gauss9_rgb(line2 + lane);   // bloom_upsample_add: lower first, then upper
             wave_sync();
             H4 th;   // the H pass's fp16 store
-            th.x = to_half_rn(g.x); th.y = to_half_rn(g.y); th.z = to_half_rn(g.z); th.w = alpha_t;
+            th.x = to_half_rn(g.x); th.y = to_half_rn(g.y); th.z = to_half_rn(g.z); th.w = alpha.t;
             sT[r0 + k][lane] = th;
         }
     }
@@ -615,18 +618,16 @@ __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ 
         V3 a3 = v3(0.0f, 0.0f, 0.0f);
 #pragma unroll
         for (int i = 0; i < 9; i++) a3 = fma3(h3f(sT[r + i][lane]), c_gauss[i], a3);
-        const F4 a = f4(a3.x, a3.y, a3.z, alpha_v);
+        const F4 a = f4(a3.x, a3.y, a3.z, alpha.v);
         if (TAIL == 0) {
             store_h4(out + 4 * ((size_t)y * out_pitch + x), a);
         } else {
-            if (!(in_mx && y >= tr.my0 && y < tr.my1)) continue;
-            const half4v a0 = round_h4(a);   // A0 texel as the separate V pass would have stored it
-            const F4 s = h4f(hdr_in[k]);
+            if (!(merge_has(tr, in_mx, y))) continue;
             H4 o;
-            o.x = to_half_rn(s.x + (float)a0.x); o.y = to_half_rn(s.y + (float)a0.y); o.z = to_half_rn(s.z + (float)a0.z); o.w = to_half_rn(s.w + (float)a0.w);
+            merge_rounded(a, hdr_in[k], o);
             *reinterpret_cast<H4*>(out + 4 * ((size_t)(y - tr.by) * out_pitch + (x - tr.bx))) = o;
             if (TAIL == 2) {
-                if (x >= tr.hx0 && x < tr.hx1 && y >= tr.hy0 && y < tr.hy1)
+                if (hist_has(tr, x, y))
                     atomicAdd(&sh_hist[wv][luminance_bin_exact((float)o.x, (float)o.y, (float)o.z, min_log, inv_range)], 1u);
             }
         }
@@ -635,12 +636,7 @@ __global__ __launch_bounds__(NT, 4) void k_blur_hv(const pbr_half* __restrict__ 
     }
     if (TAIL == 2) {
         __syncthreads();
-        for (int i = t; i < PBR_HISTOGRAM_BINS; i += NT) {
-            uint32_t sum = 0;
-#pragma unroll
-            for (int w2 = 0; w2 < NW; w2++) sum += sh_hist[w2][i];
-            if (sum) atomicAdd(&hist[i], sum);
-        }
+        hist_flush<NT>(sh_hist, t, hist);
     }
 }
 
@@ -693,15 +689,7 @@ __global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restr
                                                           int tiles_x, int n_tiles,
                                                           TailRect tr, float min_log, float inv_range, VS vs,
                                                           uint32_t* __restrict__ hist_) {
-    const pbr_half* __restrict__ in = in_;
-    const pbr_half* __restrict__ in2 = in2_;
-    pbr_half* __restrict__ out = out_;
-    uint32_t* __restrict__ hist = hist_;
-    int out_pitch = out_pitch_;
-    if constexpr (!std::is_same_v<VS, NoViews>) {   // LevelViews: view blockIdx.y
-        const int v = blockIdx.y;
-        in = vs.in[v]; in2 = vs.in2[v]; out = vs.out[v]; hist = vs.hist[v]; out_pitch = vs.out_pitch[v];
-    }
+    const auto [in, in2, out, hist, out_pitch] = level_args(vs, in_, in2_, out_, hist_, out_pitch_);
     constexpr int TW = 128, NP = TW / 2 + 4, NC = TW / 2 + 6, SR = TH + 8, NT = 512, NW = NT / 64;
     constexpr int NPAIR = TH / 2 + 5;                 // coarse row pairs (m, m + 1) whose two blends (fine rows 2m + 1, 2m + 2) the tile's SR rows need
     constexpr int PPW = (NPAIR + NW - 1) / NW;        // pairs per wave; wave w: pairs w * PPW .. (the last waves may hold fewer, or none)
@@ -712,31 +700,19 @@ __global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restr
     __shared__ H4 sT[SR][TW];
     __shared__ uint32_t sh_hist[TAIL == 2 ? NW : 1][TAIL == 2 ? PBR_HISTOGRAM_BINS : 1];
     // two blocks (2 x 8 waves = the 4 waves per SIMD of the launch bounds) must fit a CU's 160 KiB of LDS: an instantiation that does not
-    // would still build — gfx950 allows one block the whole 160 KiB — and silently run at half the occupancy (ADVICE r04)
+    // would still build — gfx950 allows one block the whole 160 KiB — and silently run at half the occupancy
     static_assert(sizeof(sLineC) + sizeof(sLineU) + sizeof(sT) + sizeof(sh_hist) <= 80 * 1024, "k_blur_up_poly: two blocks per CU no longer fit the LDS");
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int vc = t & 127, vg = __builtin_amdgcn_readfirstlane(t >> 7);
-    if (TAIL == 2) {
-        for (int i = t; i < NW * PBR_HISTOGRAM_BINS; i += NT) (&sh_hist[0][0])[i] = 0u;
-    }
-    // (read at a texel the launch's rectangle depends on: see k_blur_hv)
-    const size_t a_at = (size_t)min(tr.my0 >> 1, ih - 1) * iw + min(tr.mx0 >> 1, iw - 1);
-    float alpha_h = gauss9_const((float)reinterpret_cast<const H4*>(in)[a_at].w);
-    if (DUAL) alpha_h = alpha_h + gauss9_const((float)reinterpret_cast<const H4*>(in2)[(size_t)min(tr.my0, oh - 1) * ow + min(tr.mx0, ow - 1)].w);
-    const h16 alpha_t = to_half_rn(alpha_h);
-    const float alpha_v = gauss9_const((float)alpha_t);
-    const float a0w = (float)to_half_rn(alpha_v);
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
+    if (TAIL == 2) hist_clear<NT>(sh_hist, t);
+    const LevelAlpha alpha = level_alpha<M_UP, DUAL>(in, iw, ih, in2, ow, oh, tr);
+    const float a0w = (float)to_half_rn(alpha.v);
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int x0 = (tr.tx0 + tile % tiles_x) * TW, y0 = (tr.ty0 + tile / tiles_x) * TH;   // (TAIL 0 without a rectangle: tx0 = ty0 = 0)
     const int xv = x0 + vc, rbase = vg * PER_O;
     H4 hdr_in[PER_O];
-    const bool in_mx = TAIL != 0 && xv >= tr.mx0 && xv < tr.mx1;
+    const bool in_mx = TAIL != 0 && merge_has_x(tr, xv);
     char* const hdr_row0 = reinterpret_cast<char*>(out) + (ptrdiff_t)(y0 + rbase - tr.by) * out_pitch * 8;
     const uint32_t hdr_x = (uint32_t)(xv - tr.bx) * 8u;
     const size_t hdr_pitch = (size_t)out_pitch * 8u;
@@ -781,7 +757,7 @@ __global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restr
 #pragma unroll
             for (int k = 0; k < PER_O; k++) {
                 const int y = y0 + rbase + k;
-                if (in_mx && y >= tr.my0 && y < tr.my1) hdr_in[k] = ld_h4(hdr_row0 + k * hdr_pitch, hdr_x);
+                if (merge_has(tr, in_mx, y)) hdr_in[k] = ld_h4(hdr_row0 + k * hdr_pitch, hdr_x);
             }
         }
         if (n_pairs > 0) {
@@ -826,8 +802,8 @@ __global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restr
                             bE = bE + uE; bO = bO + uO;
                         }
                         struct alignas(16) H8 { H4 a, b; } th;   // the H pass's fp16 store, both columns of the lane
-                        th.a.x = to_half_rn(bE.x); th.a.y = to_half_rn(bE.y); th.a.z = to_half_rn(bE.z); th.a.w = alpha_t;
-                        th.b.x = to_half_rn(bO.x); th.b.y = to_half_rn(bO.y); th.b.z = to_half_rn(bO.z); th.b.w = alpha_t;
+                        th.a.x = to_half_rn(bE.x); th.a.y = to_half_rn(bE.y); th.a.z = to_half_rn(bE.z); th.a.w = alpha.t;
+                        th.b.x = to_half_rn(bO.x); th.b.y = to_half_rn(bO.y); th.b.z = to_half_rn(bO.z); th.b.w = alpha.t;
                         *reinterpret_cast<H8*>(&sT[r][2 * lane]) = th;
                     }
                 }
@@ -848,20 +824,15 @@ __global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restr
             V3 a3 = v3(0.0f, 0.0f, 0.0f);
 #pragma unroll
             for (int i = 0; i < 9; i++) a3 = fma3(h3f(win[k + i]), c_gauss[i], a3);
-            const F4 a = f4(a3.x, a3.y, a3.z, alpha_v);
+            const F4 a = f4(a3.x, a3.y, a3.z, alpha.v);
             if (TAIL == 0) {
                 store_h4(out + 4 * ((size_t)y * out_pitch + xv), a);
             } else {
-                if (!(in_mx && y >= tr.my0 && y < tr.my1)) continue;
-                const half2v a01 = round_h2(a3.x, a3.y);
-                const h16 a2 = to_half_rn(a3.z);
-                const F4 s = h4f(hdr_in[k]);
-                struct alignas(8) O4 { half2v lo, hi; } o;
-                o.lo = round_h2(s.x + (float)a01.x, s.y + (float)a01.y);
-                o.hi = round_h2(s.z + (float)a2, s.w + a0w);
-                *reinterpret_cast<O4*>(hdr_row0 + k * hdr_pitch + hdr_x) = o;
+                if (!(merge_has(tr, in_mx, y))) continue;
+                const H4Packed o = merge_rounded_packed(a3, a0w, h4f(hdr_in[k]));
+                *reinterpret_cast<H4Packed*>(hdr_row0 + k * hdr_pitch + hdr_x) = o;
                 if (TAIL == 2) {
-                    if (xv >= tr.hx0 && xv < tr.hx1 && y >= tr.hy0 && y < tr.hy1)
+                    if (hist_has(tr, xv, y))
                         atomicAdd(&sh_hist[wv][luminance_bin_exact((float)o.lo.x, (float)o.lo.y, (float)o.hi.x, min_log, inv_range)], 1u);
                 }
             }
@@ -871,31 +842,51 @@ __global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restr
     }
     if (TAIL == 2) {
         __syncthreads();
-        for (int i = t; i < PBR_HISTOGRAM_BINS; i += NT) {
-            uint32_t sum = 0;
-#pragma unroll
-            for (int w2 = 0; w2 < NW; w2++) sum += sh_hist[w2][i];
-            if (sum) atomicAdd(&hist[i], sum);
-        }
+        hist_flush<NT>(sh_hist, t, hist);
     }
 }
 
-// rows a k_blur_h block pipelines: as many as keep >= ~2048 blocks (8 per CU) in the grid
-static int blur_h_rows(uint32_t ow, uint32_t oh) {
+// ---------------------------------------------------------------- launch
+// k_blur_h of in (+ in2: DUAL) into out (ow x oh).  A block pipelines as many rows as keep >= ~2048 blocks (8 per CU) in the grid
+template <bool DUAL>
+static pbr_status launch_blur_h(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint32_t ih, const pbr_half* in2, uint32_t iw2, uint32_t ih2,
+                                pbr_half* out, uint32_t ow, uint32_t oh) {
     const uint64_t row_blocks = (uint64_t)((ow + 255) / 256) * oh;
     int rows = (int)(row_blocks / 2048);
-    return rows < 1 ? 1 : (rows > HB_MAX_ROWS ? HB_MAX_ROWS : rows);
+    rows = rows < 1 ? 1 : (rows > HB_MAX_ROWS ? HB_MAX_ROWS : rows);
+    hipLaunchKernelGGL(k_blur_h<DUAL>, dim3((ow + 255) / 256, (oh + rows - 1) / rows), dim3(256), 0, ctx->stream, in, (int)iw, (int)ih, in2, (int)iw2, (int)ih2,
+                       out, (int)ow, (int)oh, 1.0f / (float)ow, 1.0f / (float)oh, rows);
+    return launched(ctx, DUAL ? "k_blur_h<dual>" : "k_blur_h");
 }
 
 // fast-path preconditions: the level below is exactly half, and the size keeps every snapped sample coordinate
 // on its dyadic value (coordinate error ~4 * 2^-24 * size must stay below half a 1/256 step)
 static bool exact_half(uint32_t n) { return (n & 1u) == 0u && n <= 8192u; }
 
+// TailRect of a fused level of ow x oh from the launch's three optional rectangles.  rect: histogram rect {x,y,w,h} (default: none);
+// merge_rect: HDR texels to merge (default: the whole level); buf_origin: level coordinates of out[0] (default 0,0).  The first
+// tile (tx0, ty0) depends on the tile size: launch_hv sets it with the kernel it chooses.
+static TailRect tail_rect(uint32_t ow, uint32_t oh, const uint32_t* rect, const uint32_t* merge_rect, const uint32_t* buf_origin) {
+    TailRect tr{};
+    if (rect) { tr.hx0 = (int)rect[0]; tr.hy0 = (int)rect[1]; tr.hx1 = (int)(rect[0] + rect[2]); tr.hy1 = (int)(rect[1] + rect[3]); }
+    tr.mx1 = (int)ow; tr.my1 = (int)oh;
+    if (merge_rect) {
+        tr.mx0 = (int)merge_rect[0]; tr.my0 = (int)merge_rect[1];
+        tr.mx1 = (int)(merge_rect[0] + merge_rect[2]); tr.my1 = (int)(merge_rect[1] + merge_rect[3]);
+    }
+    if (buf_origin) { tr.bx = (int)buf_origin[0]; tr.by = (int)buf_origin[1]; }
+    return tr;
+}
+// the tw x th tiles of the level that intersect the merge rect (a launch without one: every tile of the level)
+struct TileGrid { int tx0, ty0, tiles_x, n; };
+static TileGrid tile_grid(const TailRect& tr, int tw, int th) {
+    const int tx0 = tr.mx0 / tw, ty0 = tr.my0 / th, tiles_x = (tr.mx1 + tw - 1) / tw - tx0;
+    return TileGrid{tx0, ty0, tiles_x, tiles_x * ((tr.my1 + th - 1) / th - ty0)};
+}
+
 // One fused level (k_blur_hv / k_blur_up_poly) of nv views.  lv holds each view's input, second input (DUAL), output, output pitch and
 // histogram.  MV = false: one view, the single-view kernel with view 0's pointers as its own arguments; MV: the view-table instance,
-// grid (blocks, nv), whose kernel choice is the one a single view of the level gets.
-// rect: histogram rect {x,y,w,h}; merge_rect: HDR texels to merge (default: the whole level); buf_origin: level coordinates of out[0]
-// (default 0,0).
+// grid (blocks, nv), whose kernel choice is the one a single view of the level gets.  The rectangles: see tail_rect.
 template <int MODE, bool DUAL, int TAIL, bool MV = false>
 static pbr_status launch_hv(pbr_ctx* ctx, const LevelViews& lv, uint32_t nv, uint32_t iw, uint32_t ih, uint32_t ow, uint32_t oh,
                             const uint32_t* rect, float min_log, float inv_range,
@@ -903,53 +894,43 @@ static pbr_status launch_hv(pbr_ctx* ctx, const LevelViews& lv, uint32_t nv, uin
     using VS = std::conditional_t<MV, LevelViews, NoViews>;
     VS vs{};
     if constexpr (MV) vs = lv;
-    const pbr_half* in = MV ? nullptr : lv.in[0];   // (MV: the pointer arguments are unused)
-    const pbr_half* in2 = MV ? nullptr : lv.in2[0];
-    pbr_half* out = MV ? nullptr : lv.out[0];
-    uint32_t* hist = MV ? nullptr : lv.hist[0];
-    const int out_pitch = MV ? 0 : lv.out_pitch[0];
-    TailRect tr;
-    tr.hx0 = rect ? (int)rect[0] : 0; tr.hy0 = rect ? (int)rect[1] : 0;
-    tr.hx1 = rect ? (int)(rect[0] + rect[2]) : 0; tr.hy1 = rect ? (int)(rect[1] + rect[3]) : 0;
-    tr.mx0 = merge_rect ? (int)merge_rect[0] : 0; tr.my0 = merge_rect ? (int)merge_rect[1] : 0;
-    tr.mx1 = merge_rect ? (int)(merge_rect[0] + merge_rect[2]) : (int)ow; tr.my1 = merge_rect ? (int)(merge_rect[1] + merge_rect[3]) : (int)oh;
-    tr.bx = buf_origin ? (int)buf_origin[0] : 0; tr.by = buf_origin ? (int)buf_origin[1] : 0;
-    // histogram instance: ~1024 blocks that each walk the same number of tiles (an uneven split leaves the chip
-    // half empty for the last round; one block per tile costs 256 contended global atomics per tile)
+    TailRect tr = tail_rect(ow, oh, rect, merge_rect, buf_origin);
+    // the histogram instance runs ~1024 blocks (views: over the whole batch) that each walk the same number of tiles: an uneven split
+    // leaves the chip half empty for the last round, and one block per tile costs 256 contended global atomics per tile
     static const int hist_blocks = pbr::knob_int("PBR_BLOOM_HIST_BLOCKS", 1024);
-    // (views: ~1024 blocks over the whole batch, each walking one view's tiles)
     auto even_blocks = [nv](int n_tiles) { const int per = (n_tiles * (int)nv + hist_blocks - 1) / hist_blocks; return (n_tiles + per - 1) / per; };
+    // every kernel of the level takes the same arguments, 512 threads and a 1-D grid over the tiles of `g` (MV: the pointer arguments are unused)
+    auto launch = [&](auto kernel, const TileGrid& g, const char* label) {
+        tr.tx0 = g.tx0; tr.ty0 = g.ty0;
+        hipLaunchKernelGGL(kernel, dim3(TAIL == 2 ? even_blocks(g.n) : g.n, nv), dim3(512), 0, ctx->stream,
+                           MV ? nullptr : lv.in[0], (int)iw, (int)ih, MV ? nullptr : lv.in2[0], MV ? nullptr : lv.out[0], (int)ow, (int)oh,
+                           MV ? 0 : lv.out_pitch[0], g.tiles_x, g.n, tr, min_log, inv_range, vs, MV ? nullptr : lv.hist[0]);
+        return launched(ctx, label);
+    };
+    // The kernel choice.  2x-up levels big enough to fill the chip with 128 x 32 tiles: k_blur_up_poly (PBR_BLOOM_WIDE=0|1 forces).
+    // Else k_blur_hv: 64 x 32 tiles when the level fills the chip that way; 64 x 16 below, where a level is latency-bound (one tile's
+    // dependent chain + the launch) and 3 H rows per wave, 2 outputs per thread shorten the chain.
     if constexpr (MODE == M_UP) {
-        // 2x-up levels big enough to fill the chip with 128 x 32 tiles: k_blur_up_poly, two columns per lane (PBR_BLOOM_WIDE=0|1 forces)
         static const int wide_forced = pbr::knob_int("PBR_BLOOM_WIDE", -1);
-        const int wtx0 = tr.mx0 / 128, wty0 = tr.my0 / 32;
-        const int wtiles_x = (tr.mx1 + 127) / 128 - wtx0, wn = wtiles_x * ((tr.my1 + 31) / 32 - wty0);
-        if (wide_forced >= 0 ? wide_forced == 1 : (wn >= 400 && !ctx->bloom_shader_order)) {
-            tr.tx0 = wtx0; tr.ty0 = wty0;
-            const int wb = TAIL == 2 ? even_blocks(wn) : wn;
-            hipLaunchKernelGGL((k_blur_up_poly<DUAL, TAIL, 32, VS>), dim3(wb, nv), dim3(512), 0, ctx->stream,
-                               in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, out_pitch, wtiles_x, wn, tr, min_log, inv_range, vs, hist);
-            return launched(ctx, MV ? "k_blur_up_poly<views>" : "k_blur_up_poly");
-        }
+        const TileGrid wide = tile_grid(tr, 128, 32);
+        if (wide_forced >= 0 ? wide_forced == 1 : (wide.n >= 400 && !ctx->bloom_shader_order))
+            return launch(k_blur_up_poly<DUAL, TAIL, 32, VS>, wide, MV ? "k_blur_up_poly<views>" : "k_blur_up_poly");
     }
-    // 64 x 32 tiles (512 threads) when the level is large enough to fill the chip that way, 64 x 16 below
-    const bool big = (uint64_t)((tr.mx1 + 63) / 64 - tr.mx0 / 64) * ((tr.my1 + 31) / 32 - tr.my0 / 32) >= 900;
-    // tiles that intersect the merge rect (TAIL 0 has no rect: every tile of the level)
-    const int th = big ? 32 : 16;
-    tr.tx0 = tr.mx0 / 64; tr.ty0 = tr.my0 / th;
-    const int tiles_x = (tr.mx1 + 63) / 64 - tr.tx0;
-    const int n_tiles = tiles_x * ((tr.my1 + th - 1) / th - tr.ty0);
-    const int blocks = TAIL == 2 ? even_blocks(n_tiles) : n_tiles;
-    if (big) {
-        hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 32, 512, VS>), dim3(blocks, nv), dim3(512), 0, ctx->stream,
-                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, vs, hist);
-    } else {
-        // small levels are latency-bound (one tile's dependent chain + the launch): 64 x 16 tiles on EIGHT waves — 3 H rows per
-        // wave, 2 outputs per thread — shorten the chain; the five small launches of a 4K frame take ~5 us less together
-        hipLaunchKernelGGL((k_blur_hv<MODE, DUAL, TAIL, 16, 512, VS>), dim3(blocks, nv), dim3(512), 0, ctx->stream,
-                           in, (int)iw, (int)ih, in2, out, (int)ow, (int)oh, out_pitch, tiles_x, n_tiles, tr, min_log, inv_range, vs, hist);
+    const TileGrid tall = tile_grid(tr, 64, 32);
+    if (tall.n >= 900) return launch(k_blur_hv<MODE, DUAL, TAIL, 32, 512, VS>, tall, MV ? "k_blur_hv<views>" : "k_blur_hv");
+    return launch(k_blur_hv<MODE, DUAL, TAIL, 16, 512, VS>, tile_grid(tr, 64, 16), MV ? "k_blur_hv<views>" : "k_blur_hv");
+}
+
+// a fused level's view table for n views: io(i) gives view i's input, second input (DUAL; else null), output, output pitch, histogram
+struct LevelIO { const pbr_half* in; const pbr_half* in2; pbr_half* out; int out_pitch; uint32_t* hist; };
+template <class F>
+static LevelViews level_views(uint32_t n, F io) {
+    LevelViews lv{};
+    for (uint32_t i = 0; i < n; i++) {
+        const LevelIO v = io(i);
+        lv.in[i] = v.in; lv.in2[i] = v.in2; lv.out[i] = v.out; lv.out_pitch[i] = v.out_pitch; lv.hist[i] = v.hist;
     }
-    return launched(ctx, MV ? "k_blur_hv<views>" : "k_blur_hv");
+    return lv;
 }
 
 // the shared-sample prefilter's rectangle table (rcs: n output rectangles sharing one destination offset / pitch)
@@ -966,8 +947,6 @@ static OutRects out_rects(const OutRect* rcs, int n) {
     rs.first[n] = blocks;
     return rs;
 }
-
-extern "C" {
 
 static pbr_status prefilter_launch(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
                                    pbr_half* out, const OutRect* rcs, int n, float threshold, float knee) {
@@ -988,13 +967,44 @@ static pbr_status prefilter_launch(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w
     return PBR_OK;
 }
 
+// ---- checks that several entry points share: what is wrong (nullptr: nothing); the caller refuses under its own name (PBR_CHECK)
+// prefilter: the image has a half-res texel, sides <= 65535, pitch >= w
+static const char* prefilter_image_fault(uint32_t w, uint32_t h, uint32_t pitch) {
+    return (w >> 1) >= 1 && (h >> 1) >= 1 && w <= 65535 && h <= 65535 && pitch >= w ? nullptr : "bad size";
+}
+// prefilter: output rectangle q = {x, y, w, h} inside the half-res image, and inside the destination's pitch when placed at column out_x
+static const char* prefilter_rect_fault(const uint32_t q[4], uint32_t w, uint32_t h, uint32_t out_x, uint32_t out_pitch) {
+    if (!(q[2] >= 1 && q[3] >= 1 && q[0] + q[2] <= (w >> 1) && q[1] + q[3] <= (h >> 1))) return "rect outside the half-res image";
+    return out_pitch >= out_x + q[0] + q[2] ? nullptr : "rect does not fit the output pitch";
+}
+static bool prefilter_dest_ok(uint32_t out_pitch, uint32_t out_y) { return out_pitch <= 65535 && out_y <= 65535; }
+// chain: every one of the five mips >= 1 texel (BloomStep < CalculateMaxMipLevels, DeferredPipeline.cpp:343), sides <= 65535, pitch >= w
+static const char* chain_size_fault(uint32_t w, uint32_t h, uint32_t pitch) {
+    if (!((w >> (PBR_BLOOM_MIPS - 1)) >= 1 && (h >> (PBR_BLOOM_MIPS - 1)) >= 1)) return "image too small for 5 mips";
+    return w <= 65535 && h <= 65535 && pitch >= w ? nullptr : "bad size";
+}
+
+// the three prefilter entry points after their checks: n rectangles of the half-res image into out at (out_x, out_y)
+static pbr_status prefilter_rects(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch, pbr_half* out, uint32_t out_pitch,
+                                  uint32_t out_x, uint32_t out_y, const uint32_t (*rects)[4], uint32_t n_rects, float threshold, float knee) {
+    OutRect rcs[PF_MAX_RECTS];
+    for (uint32_t r = 0; r < n_rects; r++) {
+        const uint32_t* q = rects[r];
+        rcs[r] = OutRect{(int)q[0], (int)q[1], (int)(q[0] + q[2]), (int)(q[1] + q[3]), (int)out_x, (int)out_y, (int)out_pitch};
+    }
+    return prefilter_launch(ctx, hdr, w, h, pitch, out, rcs, (int)n_rects, threshold, knee);
+}
+
+// ---------------------------------------------------------------- C ABI: the staged passes
+extern "C" {
+
 pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
                                pbr_half* out, float threshold, float knee) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, hdr && out, "pbr_bloom_prefilter: null pointer");
-    PBR_REQUIRE(ctx, (w >> 1) >= 1 && (h >> 1) >= 1 && w <= 65535 && h <= 65535 && pitch >= w, "pbr_bloom_prefilter: bad size");
-    const OutRect rc{0, 0, (int)(w >> 1), (int)(h >> 1), 0, 0, (int)(w >> 1)};
-    return prefilter_launch(ctx, hdr, w, h, pitch, out, &rc, 1, threshold, knee);
+    PBR_CHECK(ctx, "pbr_bloom_prefilter", prefilter_image_fault(w, h, pitch));
+    const uint32_t whole[4] = {0, 0, w >> 1, h >> 1};   // the whole image into a dense plane
+    return prefilter_rects(ctx, hdr, w, h, pitch, out, w >> 1, 0, 0, &whole, 1, threshold, knee);
 }
 
 pbr_status pbr_bloom_prefilter_rect(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
@@ -1002,11 +1012,10 @@ pbr_status pbr_bloom_prefilter_rect(pbr_ctx* ctx, const pbr_half* hdr, uint32_t 
                                     const uint32_t rect[4], float threshold, float knee) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, hdr && out && rect, "pbr_bloom_prefilter_rect: null pointer");
-    PBR_REQUIRE(ctx, (w >> 1) >= 1 && (h >> 1) >= 1 && w <= 65535 && h <= 65535 && pitch >= w, "pbr_bloom_prefilter_rect: bad size");
-    PBR_REQUIRE(ctx, rect[2] >= 1 && rect[3] >= 1 && rect[0] + rect[2] <= (w >> 1) && rect[1] + rect[3] <= (h >> 1), "pbr_bloom_prefilter_rect: rect outside the half-res image");
-    PBR_REQUIRE(ctx, out_pitch >= out_x + rect[0] + rect[2] && out_pitch <= 65535 && out_y <= 65535, "pbr_bloom_prefilter_rect: rect does not fit the output pitch");
-    const OutRect rc{(int)rect[0], (int)rect[1], (int)(rect[0] + rect[2]), (int)(rect[1] + rect[3]), (int)out_x, (int)out_y, (int)out_pitch};
-    return prefilter_launch(ctx, hdr, w, h, pitch, out, &rc, 1, threshold, knee);
+    PBR_CHECK(ctx, "pbr_bloom_prefilter_rect", prefilter_image_fault(w, h, pitch));
+    PBR_CHECK(ctx, "pbr_bloom_prefilter_rect", prefilter_rect_fault(rect, w, h, out_x, out_pitch));
+    PBR_REQUIRE(ctx, prefilter_dest_ok(out_pitch, out_y), "pbr_bloom_prefilter_rect: rect does not fit the output pitch");
+    return prefilter_rects(ctx, hdr, w, h, pitch, out, out_pitch, out_x, out_y, reinterpret_cast<const uint32_t (*)[4]>(rect), 1, threshold, knee);
 }
 
 pbr_status pbr_bloom_prefilter_rects(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
@@ -1014,26 +1023,18 @@ pbr_status pbr_bloom_prefilter_rects(pbr_ctx* ctx, const pbr_half* hdr, uint32_t
                                      const uint32_t (*rects)[4], uint32_t n_rects, float threshold, float knee) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, hdr && out && rects && n_rects >= 1 && n_rects <= (uint32_t)PF_MAX_RECTS, "pbr_bloom_prefilter_rects: null pointer / 1 .. 5 rectangles");
-    PBR_REQUIRE(ctx, (w >> 1) >= 1 && (h >> 1) >= 1 && w <= 65535 && h <= 65535 && pitch >= w && out_pitch <= 65535 && out_y <= 65535, "pbr_bloom_prefilter_rects: bad size");
-    OutRect rcs[PF_MAX_RECTS];
-    for (uint32_t r = 0; r < n_rects; r++) {
-        const uint32_t* q = rects[r];
-        PBR_REQUIRE(ctx, q[2] >= 1 && q[3] >= 1 && q[0] + q[2] <= (w >> 1) && q[1] + q[3] <= (h >> 1) && out_pitch >= out_x + q[0] + q[2],
-                    "pbr_bloom_prefilter_rects: rectangle outside the half-res image / the output pitch");
-        rcs[r] = OutRect{(int)q[0], (int)q[1], (int)(q[0] + q[2]), (int)(q[1] + q[3]), (int)out_x, (int)out_y, (int)out_pitch};
-    }
-    return prefilter_launch(ctx, hdr, w, h, pitch, out, rcs, (int)n_rects, threshold, knee);
+    PBR_CHECK(ctx, "pbr_bloom_prefilter_rects", prefilter_image_fault(w, h, pitch));
+    PBR_REQUIRE(ctx, prefilter_dest_ok(out_pitch, out_y), "pbr_bloom_prefilter_rects: bad size");
+    for (uint32_t r = 0; r < n_rects; r++)
+        PBR_REQUIRE(ctx, !prefilter_rect_fault(rects[r], w, h, out_x, out_pitch), "pbr_bloom_prefilter_rects: rectangle outside the half-res image / the output pitch");
+    return prefilter_rects(ctx, hdr, w, h, pitch, out, out_pitch, out_x, out_y, rects, n_rects, threshold, knee);
 }
 
 pbr_status pbr_blur_h(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint32_t ih, pbr_half* out, uint32_t ow, uint32_t oh) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, in && out, "pbr_blur_h: null pointer");
     PBR_REQUIRE(ctx, iw && ih && ow && oh && iw <= 65535 && ih <= 65535 && ow <= 65535 && oh <= 65535, "pbr_blur_h: bad size");
-    const float tx = 1.0f / (float)ow, ty = 1.0f / (float)oh;
-    const int rows = blur_h_rows(ow, oh);
-    dim3 grid((ow + 255) / 256, (oh + rows - 1) / rows);
-    hipLaunchKernelGGL(k_blur_h<false>, grid, dim3(256), 0, ctx->stream, in, (int)iw, (int)ih, (const pbr_half*)nullptr, 0, 0, out, (int)ow, (int)oh, tx, ty, rows);
-    return launched(ctx, "k_blur_h");
+    return launch_blur_h<false>(ctx, in, iw, ih, nullptr, 0, 0, out, ow, oh);
 }
 
 pbr_status pbr_blur_v(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint32_t ih, pbr_half* out, uint32_t ow, uint32_t oh) {
@@ -1051,11 +1052,7 @@ pbr_status pbr_bloom_upsample_add(pbr_ctx* ctx, const pbr_half* upper, uint32_t 
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, upper && lower && out, "pbr_bloom_upsample_add: null pointer");
     PBR_REQUIRE(ctx, uw && uh && lw && lh && uw <= 65535 && uh <= 65535, "pbr_bloom_upsample_add: bad size");
-    const float tx = 1.0f / (float)uw, ty = 1.0f / (float)uh;
-    const int rows = blur_h_rows(uw, uh);
-    dim3 grid((uw + 255) / 256, (uh + rows - 1) / rows);
-    hipLaunchKernelGGL(k_blur_h<true>, grid, dim3(256), 0, ctx->stream, lower, (int)lw, (int)lh, upper, (int)uw, (int)uh, out, (int)uw, (int)uh, tx, ty, rows);
-    return launched(ctx, "k_blur_h<dual>");
+    return launch_blur_h<true>(ctx, lower, lw, lh, upper, uw, uh, out, uw, uh);   // bloom_upsample_add.hlsl: lower first, then upper
 }
 
 pbr_status pbr_bloom_merge(pbr_ctx* ctx, pbr_half* hdr, uint32_t pitch, const pbr_half* in, uint32_t w, uint32_t h) {
@@ -1072,12 +1069,15 @@ pbr_status pbr_bloom_up_level(pbr_ctx* ctx, const pbr_half* upper, const pbr_hal
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, lower && out && out != lower && out != upper, "pbr_bloom_up_level: null pointer / out aliases an input");
     PBR_REQUIRE(ctx, lw >= 1 && lh >= 1 && ow == 2 * lw && oh == 2 * lh && exact_half(ow) && exact_half(oh), "pbr_bloom_up_level: out must be exactly twice lower, even, <= 8192");
-    LevelViews lv{};
-    lv.in[0] = lower; lv.in2[0] = upper; lv.out[0] = out; lv.out_pitch[0] = (int)ow;
+    const LevelViews lv = level_views(1, [&](uint32_t) { return LevelIO{lower, upper, out, (int)ow, nullptr}; });
     if (upper) return launch_hv<M_UP, true, 0>(ctx, lv, 1, lw, lh, ow, oh, nullptr, 0.0f, 0.0f);
     return launch_hv<M_UP, false, 0>(ctx, lv, 1, lw, lh, ow, oh, nullptr, 0.0f, 0.0f);
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------- schedule
+// the staged chain's last two dispatches + the histogram: k_blur_v_merge on level 0 of chain B
 static pbr_status bloom_final(pbr_ctx* ctx, const pbr_half* b0, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
                               const uint32_t* hist_rect, float min_log, float inv_range, uint32_t* hist256) {
     const float tx = 1.0f / (float)w, ty = 1.0f / (float)h;
@@ -1094,7 +1094,19 @@ static pbr_status bloom_final(pbr_ctx* ctx, const pbr_half* b0, pbr_half* hdr, u
     return launched(ctx, "k_blur_v_merge");
 }
 
-}  // extern "C"
+// Rectangles {x, y, w, h} of the up-levels 1 .. PBR_BLOOM_MIPS - 1 (level coordinates) that the finished image inside merge0 depends
+// on.  Level 1's result is read by the merge within merge0 / 2 +- 3 texels (nine taps one level-0 texel apart + the bilinear
+// footprint); level l's up-pass reads the level below within +- 4 of its own taps, halved, + the bilinear footprint.  So the
+// rectangle shrinks towards merge0 / 2^l as the remaining filter support does.  Margins are rounded up: a superset costs a tile at most.
+static void up_pass_rects(const uint32_t merge0[4], uint32_t w, uint32_t h, uint32_t need[PBR_BLOOM_MIPS][4]) {
+    int x0 = (int)merge0[0], y0 = (int)merge0[1], x1 = (int)(merge0[0] + merge0[2]), y1 = (int)(merge0[1] + merge0[3]);
+    for (uint32_t l = 1; l < PBR_BLOOM_MIPS; l++) {
+        const int lw = (int)(w >> l), lh = (int)(h >> l);
+        x0 = (x0 - 4) / 2 - 2; y0 = (y0 - 4) / 2 - 2; x1 = (x1 + 4 + 1) / 2 + 2; y1 = (y1 + 4 + 1) / 2 + 2;   // (C division of a negative numerator rounds towards 0: clipped below anyway)
+        x0 = x0 < 0 ? 0 : x0; y0 = y0 < 0 ? 0 : y0; x1 = x1 > lw ? lw : x1; y1 = y1 > lh ? lh : y1;
+        need[l][0] = (uint32_t)x0; need[l][1] = (uint32_t)y0; need[l][2] = (uint32_t)(x1 - x0); need[l][3] = (uint32_t)(y1 - y0);
+    }
+}
 
 // One view of a bloom pass: its HDR target (w x h, pitch), the two chains and its histogram (null: no histogram)
 struct BloomView { pbr_half* hdr; uint32_t pitch; pbr_half* A; pbr_half* B; uint32_t* hist; };
@@ -1111,10 +1123,10 @@ struct BloomView { pbr_half* hdr; uint32_t pitch; pbr_half* A; pbr_half* B; uint
 // are scratch.
 //
 // merge0 (one view, exact level 0 only): the rectangle {x, y, w, h} of level 0 to merge; origin: its level coordinates of hdr[0].  The
-// up-pass of level l is then run only on the tiles of level l the finished image inside merge0 depends on — the rectangle shrinks
-// towards merge0 / 2^l as the remaining filter support does (a tiled frame's bloom works on the tile +- 256 px, but only the DOWN-pass
-// needs that apron in full: SURVEY 8e's "cheaper apron").  Whole tiles are computed, so every texel inside the rectangles is what the
-// full pass computes: the merged interior is bit-identical.  Texels of the up-levels outside them are left as they were.
+// up-pass of level l is then run only on the tiles of level l inside up_pass_rects' rectangle (a tiled frame's bloom works on the
+// tile +- 256 px, but only the DOWN-pass needs that apron in full: SURVEY 8e's "cheaper apron").  Whole tiles are computed, so every
+// texel inside the rectangles is what the full pass computes: the merged interior is bit-identical.  Texels of the up-levels outside
+// them are left as they were.
 template <bool MV>
 static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint32_t w, uint32_t h, bool prefilter, float threshold, float knee,
                              const uint32_t* hist_rect, float min_log, float inv_range, const uint32_t* merge0 = nullptr, const uint32_t* origin = nullptr) {
@@ -1140,8 +1152,7 @@ static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint3
     for (uint32_t k = 0; k < PBR_BLOOM_STEP; k++) {   // downsample
         const uint32_t up = k + 1, lo = k + 2;
         if (exact(up)) {
-            LevelViews lv{};
-            for (uint32_t i = 0; i < n; i++) { lv.in[i] = v[i].A + off(up); lv.out[i] = v[i].A + off(lo); lv.out_pitch[i] = (int)W(lo); }
+            const LevelViews lv = level_views(n, [&](uint32_t i) { return LevelIO{v[i].A + off(up), nullptr, v[i].A + off(lo), (int)W(lo), nullptr}; });
             if ((r = launch_hv<M_DOWN, false, 0, MV>(ctx, lv, n, W(up), H(up), W(lo), H(lo), nullptr, 0.0f, 0.0f))) return r;
         } else {
             for (uint32_t i = 0; i < n; i++) {
@@ -1150,29 +1161,17 @@ static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint3
             }
         }
     }
-    // rectangles of the up-levels (level coordinates): level 1's result is read by the merge within merge0 / 2 +- 3 texels (nine taps one
-    // level-0 texel apart + the bilinear footprint); level l's up-pass reads the level below within +- 4 of its own taps, halved, + the
-    // bilinear footprint.  Margins are rounded up: a superset costs a tile at most
     uint32_t need[PBR_BLOOM_MIPS][4];
     static const bool shrink = pbr::knob_int("PBR_BLOOM_SHRINK", 1) != 0;
     const bool use_need = merge0 != nullptr && shrink;
-    if (use_need) {
-        int x0 = (int)merge0[0], y0 = (int)merge0[1], x1 = (int)(merge0[0] + merge0[2]), y1 = (int)(merge0[1] + merge0[3]);
-        for (uint32_t l = 1; l < PBR_BLOOM_MIPS; l++) {
-            x0 = (x0 - 4) / 2 - 2; y0 = (y0 - 4) / 2 - 2; x1 = (x1 + 4 + 1) / 2 + 2; y1 = (y1 + 4 + 1) / 2 + 2;   // (C division of a negative numerator rounds towards 0: clipped below anyway)
-            const int cx0 = x0 < 0 ? 0 : x0, cy0 = y0 < 0 ? 0 : y0, cx1 = x1 > (int)W(l) ? (int)W(l) : x1, cy1 = y1 > (int)H(l) ? (int)H(l) : y1;
-            need[l][0] = (uint32_t)cx0; need[l][1] = (uint32_t)cy0; need[l][2] = (uint32_t)(cx1 - cx0); need[l][3] = (uint32_t)(cy1 - cy0);
-            x0 = cx0; y0 = cy0; x1 = cx1; y1 = cy1;
-        }
-    }
+    if (use_need) up_pass_rects(merge0, w, h, need);
     bool res_in_b = false;
     uint32_t res_level = PBR_BLOOM_MIPS - 1;
     auto res = [&](uint32_t i) { return (const pbr_half*)(res_in_b ? v[i].B : v[i].A) + off(res_level); };
     for (int k = PBR_BLOOM_STEP - 1; k >= 0; k--) {   // upsample: V(H(lower) + H(upper))
         const uint32_t up = (uint32_t)k + 1;
         if (exact(up)) {
-            LevelViews lv{};
-            for (uint32_t i = 0; i < n; i++) { lv.in[i] = res(i); lv.in2[i] = v[i].A + off(up); lv.out[i] = v[i].B + off(up); lv.out_pitch[i] = (int)W(up); }
+            const LevelViews lv = level_views(n, [&](uint32_t i) { return LevelIO{res(i), v[i].A + off(up), v[i].B + off(up), (int)W(up), nullptr}; });
             if ((r = launch_hv<M_UP, true, 0, MV>(ctx, lv, n, W(up + 1), H(up + 1), W(up), H(up), nullptr, 0.0f, 0.0f,
                                                   use_need ? need[up] : nullptr))) return r;
             res_in_b = true;
@@ -1186,8 +1185,7 @@ static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint3
         res_level = up;
     }
     if (exact(0)) {   // H + V + merge (+ histogram) in one kernel
-        LevelViews lv{};
-        for (uint32_t i = 0; i < n; i++) { lv.in[i] = res(i); lv.out[i] = v[i].hdr; lv.out_pitch[i] = (int)v[i].pitch; lv.hist[i] = v[i].hist; }
+        const LevelViews lv = level_views(n, [&](uint32_t i) { return LevelIO{res(i), nullptr, v[i].hdr, (int)v[i].pitch, v[i].hist}; });
         if constexpr (!MV)
             if (!v[0].hist) return launch_hv<M_UP, false, 1>(ctx, lv, 1, w >> 1, h >> 1, w, h, nullptr, 0.0f, 0.0f, merge0, origin);
         return launch_hv<M_UP, false, 2, MV>(ctx, lv, n, w >> 1, h >> 1, w, h, hist_rect, min_log, inv_range, merge0, origin);
@@ -1200,14 +1198,14 @@ static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint3
     return PBR_OK;
 }
 
+// ---------------------------------------------------------------- C ABI: the chain
 extern "C" {
 
+// pbr_bloom and pbr_bloom_histogram (which therefore refuses a bad size under the name pbr_bloom)
 static pbr_status bloom_impl(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch, pbr_half* A, pbr_half* B,
                              float threshold, float knee, const uint32_t* hist_rect, float min_log, float inv_range, uint32_t* hist256) {
     PBR_REQUIRE(ctx, hdr && A && B, "pbr_bloom: null pointer");
-    // BloomStep < CalculateMaxMipLevels (DeferredPipeline.cpp:343): every level must be >= 1 texel
-    PBR_REQUIRE(ctx, (w >> (PBR_BLOOM_MIPS - 1)) >= 1 && (h >> (PBR_BLOOM_MIPS - 1)) >= 1, "pbr_bloom: image too small for 5 mips");
-    PBR_REQUIRE(ctx, w <= 65535 && h <= 65535 && pitch >= w, "pbr_bloom: bad size");
+    PBR_CHECK(ctx, "pbr_bloom", chain_size_fault(w, h, pitch));
     const BloomView v{hdr, pitch, A, B, hist256};
     return bloom_pass<false>(ctx, &v, 1, w, h, true, threshold, knee, hist_rect, min_log, inv_range);
 }
@@ -1237,8 +1235,7 @@ pbr_status pbr_bloom_histogram_views(pbr_ctx* ctx, const pbr_view* views, uint32
                                      float threshold, float knee, float min_log, float inv_range) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, views_count_ok(views, n), "pbr_bloom_histogram_views: need 1 .. PBR_MAX_VIEWS views");
-    PBR_REQUIRE(ctx, (w >> (PBR_BLOOM_MIPS - 1)) >= 1 && (h >> (PBR_BLOOM_MIPS - 1)) >= 1, "pbr_bloom_histogram_views: image too small for 5 mips");
-    PBR_REQUIRE(ctx, w <= 65535 && h <= 65535, "pbr_bloom_histogram_views: bad size");
+    PBR_CHECK(ctx, "pbr_bloom_histogram_views", chain_size_fault(w, h, w));   // (each view's pitch: below)
     BloomView bv[PBR_MAX_VIEWS];
     for (uint32_t i = 0; i < n; i++) {
         const pbr_view& v = views[i];
@@ -1266,7 +1263,7 @@ pbr_status pbr_bloom_tiled(pbr_ctx* ctx, pbr_half* hdr, uint32_t hdr_pitch, cons
                            float min_log, float inv_range, uint32_t* hist256) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, hdr && hdr_rect && A && B && merge_rect, "pbr_bloom_tiled: null pointer");
-    PBR_REQUIRE(ctx, ew <= 65535 && eh <= 65535 && (ew >> (PBR_BLOOM_MIPS - 1)) >= 1 && (eh >> (PBR_BLOOM_MIPS - 1)) >= 1, "pbr_bloom_tiled: bad size");
+    PBR_REQUIRE(ctx, !chain_size_fault(ew, eh, ew), "pbr_bloom_tiled: bad size");   // (the pitch is hdr_rect's: below)
     PBR_REQUIRE(ctx, hdr_rect[2] >= 1 && hdr_rect[3] >= 1 && hdr_rect[0] + hdr_rect[2] <= ew && hdr_rect[1] + hdr_rect[3] <= eh && hdr_pitch >= hdr_rect[2],
                 "pbr_bloom_tiled: hdr_rect outside the extended tile");
     PBR_REQUIRE(ctx, merge_rect[2] >= 1 && merge_rect[3] >= 1 && merge_rect[0] >= hdr_rect[0] && merge_rect[1] >= hdr_rect[1] &&

@@ -12,7 +12,9 @@ Reported:
     sides of a comparison;
   * with --phases, per-phase counts: shade.hip compiled once per PBR_EXP_* switch that removes one phase of shade_pixel; the
     difference of the kernels' static v_* counts is that phase.
-Only instruction CLASSES are counted (v_*, v_pk_*, the transcendental unit's, moves, ds_*, global_*)."""
+Only instruction CLASSES are counted (v_*, v_pk_*, the transcendental unit's, moves, ds_*, global_*, s_waitcnt, s_barrier, other s_*).
+    python tools/isa_phase_count.py --bloom parent_bloom.hip [out.md]
+compares every kernel instantiation of bloom.hip with those of another copy of the source (see bloom_report below)."""
 import os
 import re
 import subprocess
@@ -31,25 +33,28 @@ VIEWS = "NoViews"
 TRIPS = 16   # pairs of lights of a capped (32-entry) list
 
 
-def compile_isa(defines=(), src=SRC):
+def compile_isa(defines=(), src=SRC, flags=()):
+    """flags: what the Makefile adds for this translation unit (bloom.hip: -ffp-contract=off)"""
     with tempfile.TemporaryDirectory() as d:
         cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-Wno-unused-function", "-Wno-unused-variable",
-               "-Wno-unused-but-set-variable", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, src, "-o", os.path.join(d, "shade.s")] + ["-D" + x for x in defines]
+               "-Wno-unused-but-set-variable", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, src, "-o", os.path.join(d, "shade.s")] + ["-D" + x for x in defines] + list(flags)
         subprocess.run(cmd, check=True, capture_output=True)
         return open(os.path.join(d, "shade.s")).read()
 
 
 def kernel(text, prefix=PREFIX, views=VIEWS):
-    """(mangled name, code lines, footer {Occupancy, ScratchSize, NumVgprs}) of the instantiation whose name starts with prefix"""
+    """(mangled name, code lines, footer {Occupancy, ScratchSize, NumVgprs, TotalNumSgprs, LDSByteSize}) of the instantiation whose
+    name starts with prefix"""
     names = [m.group(1) for m in re.finditer(r"^(" + re.escape(prefix) + r"\w*):", text, re.M)]
-    names = [n for n in names if views in n] or names
+    names = [n for n in names if n == prefix] or [n for n in names if views in n] or names
     if not names:
         raise SystemExit(f"no kernel named {prefix}* in the ISA")
     name = names[0]
     a = text.index(name + ":")
     b = text.index(".end_amdhsa_kernel", a)
     code = text[a:text.index(".amdhsa_kernel", a)].splitlines()
-    foot = {k: int(v) for k, v in re.findall(r"^; (Occupancy|ScratchSize|NumVgprs): (\d+)", text[b:b + 2000], re.M)[:3]}
+    info = text.index("; Kernel info:", b)
+    foot = {k: int(v) for k, v in re.findall(r"^; (Occupancy|ScratchSize|NumVgprs|TotalNumSgprs|LDSByteSize): (\d+)", text[info:info + 1000], re.M)[:5]}
     return name, code, foot
 
 
@@ -58,7 +63,9 @@ def count(lines):
     valu = [o for o in ops if o.startswith("v_")]
     return {"valu": len(valu), "trans": sum(1 for v in valu if re.match(r"v_(rcp|rsq|log|exp|sqrt|sin|cos)_", v)),
             "packed": sum(1 for v in valu if v.startswith("v_pk_")), "moves": sum(1 for v in valu if v.startswith("v_mov_") or v.startswith("v_pk_mov")),
-            "ds": sum(1 for o in ops if o.startswith("ds_")), "global": sum(1 for o in ops if o.startswith("global_"))}
+            "ds": sum(1 for o in ops if o.startswith("ds_")), "global": sum(1 for o in ops if o.startswith("global_")),
+            "waitcnt": ops.count("s_waitcnt"), "barrier": ops.count("s_barrier"),
+            "salu": sum(1 for o in ops if o.startswith("s_") and o not in ("s_waitcnt", "s_barrier"))}
 
 
 def blocks(lines):
@@ -164,7 +171,70 @@ def phases(src=SRC):
     return doc
 
 
+# ---- bloom.hip: resources and instruction classes of EVERY kernel instantiation, for a change that must leave the generated code
+# as it is (profiles/bloom_isa_resources.md, tests/test_bloom_isa_cpu.py):  python tools/isa_phase_count.py --bloom parent_bloom.hip [out.md]
+BLOOM_SRC = os.path.join(CSRC, "bloom.hip")
+BLOOM_FLAGS = ("-ffp-contract=off",)   # the Makefile's flags of bloom.o
+BLOOM_COLS = [("valu", "v_*"), ("ds", "ds_*"), ("global", "global_*"), ("waitcnt", "s_waitcnt"), ("barrier", "s_barrier"), ("salu", "other s_*"),
+              ("vgprs", "VGPR"), ("sgprs", "SGPR"), ("lds", "LDS bytes"), ("scratch", "scratch"), ("occupancy", "occupancy")]
+
+
+def kernel_table(text):
+    """{mangled name: ({column: value}, the kernel's instructions with block labels renumbered)} of every kernel of the ISA"""
+    out = {}
+    for name in re.findall(r"^\s*\.amdhsa_kernel (\w+)", text, re.M):
+        _, code, foot = kernel(text, name)
+        row = {k: v for k, v in count(code).items() if k in dict(BLOOM_COLS)}
+        row.update(vgprs=foot["NumVgprs"], sgprs=foot["TotalNumSgprs"], lds=foot["LDSByteSize"], scratch=foot["ScratchSize"], occupancy=foot["Occupancy"])
+        out[name] = (row, [re.sub(r"BB\d+_", "BB_", ln) for ln in code if re.match(r"\s+[a-z]", ln)])
+    return out
+
+
+def exceeds(new, ref):
+    """the columns in which `new` breaks the condition against `ref`: LDS and occupancy equal, no scratch, registers and the counts of
+    v_*, ds_*, global_*, s_waitcnt and s_barrier no higher (scalar-ALU counts may move)"""
+    return ([c for c in ("lds", "occupancy") if new[c] != ref[c]] + (["scratch"] if new["scratch"] else []) +
+            [c for c in ("vgprs", "sgprs", "valu", "ds", "global", "waitcnt", "barrier") if new[c] > ref[c]])
+
+
+def bloom_report(parent_src, new_src=BLOOM_SRC):
+    with ThreadPoolExecutor(2) as ex:
+        parent, new = ex.map(lambda s: kernel_table(compile_isa((), s, BLOOM_FLAGS)), [parent_src, new_src])
+    same = [n for n in new if n in parent and new[n][1] == parent[n][1]]
+    doc = ["# bloom.hip: every kernel instantiation of the gfx950 ISA, parent commit and this tree (static counts)", "",
+           f"{len(new)} kernels, {len(same)} with the parent's instruction stream byte for byte (`same` below); " +
+           f"kernels of the parent that are gone: {sorted(set(parent) - set(new)) or 'none'}", "",
+           "Mangled template arguments: `k_blur_hv<MODE (1 M_DOWN, 2 M_UP), DUAL, TAIL, TH, NT, views>`, `k_blur_up_poly<DUAL, TAIL, TH, views>`, " +
+           "`Lb0E` / `Lb1E` = false / true, `LiNE` = N.", "",
+           "| kernel | side | " + " | ".join(t for _, t in BLOOM_COLS) + " | same |", "|---" * (len(BLOOM_COLS) + 3) + "|"]
+    for n, (row, _) in new.items():
+        for side, r in (("parent", parent.get(n, (None,))[0]), ("new", row)):
+            if r:
+                note = "yes" if n in same else ("no" if n in parent else "-")
+                doc.append(f"| `{n}` | {side} | " + " | ".join(str(r[k]) for k, _ in BLOOM_COLS) + f" | {note} |")
+    bad = {n: exceeds(new[n][0], parent[n][0]) for n in new if n in parent and exceeds(new[n][0], parent[n][0])}
+    doc += ["", "condition (LDS and occupancy equal, scratch 0, VGPR / SGPR / v_* / ds_* / global_* / s_waitcnt / s_barrier no higher): " +
+            ("held by every kernel" if not bad else f"BROKEN by {bad}")]
+    return doc, bad
+
+
+def parse_bloom_rows(md_text, side="new"):
+    """{mangled name: {column: value}} of the `side` rows of a report written by bloom_report"""
+    out = {}
+    for m in re.finditer(r"^\| `(\w+)` \| " + side + r" \| (.+?) \| \S+ \|$", md_text, re.M):
+        out[m.group(1)] = {k: int(v) for (k, _), v in zip(BLOOM_COLS, m.group(2).split(" | "))}
+    return out
+
+
 def main(argv):
+    if "--bloom" in argv:
+        rest = [a for a in argv if a != "--bloom"]
+        doc, bad = bloom_report(rest[0])
+        text = "\n".join(doc) + "\n"
+        print(text)
+        if len(rest) > 1:
+            open(rest[1], "w").write(text)
+        sys.exit(1 if bad else 0)
     args = [a for a in argv if not a.startswith("--")]
     src = SRC
     if "--src" in argv:
