@@ -103,6 +103,12 @@ class DryContext:
     def deferred_shade_rects(self, *a):
         self._n("deferred_shade_rects")
 
+    def lut_fold_x(self, lut, lut_res, out=None):
+        return self.zeros((int(lut_res), 256, 2), torch.float32)
+
+    def deferred_shade_folded(self, *a):
+        self._n("deferred_shade_rects" if a[-1] is not None and len(a) == 15 else "deferred_shade")
+
     def skybox(self, *a):
         self._n("skybox")
 

@@ -48,6 +48,11 @@ SIGNATURES = {
                                         _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, _vp, _u32]),
     "pbr_deferred_shade_f32": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
                                       _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32]),
+    "pbr_lut_fold_x": (_int, [_vp, _vp, _u32, _vp]),
+    "pbr_deferred_shade_folded": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
+                                         _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32]),
+    "pbr_deferred_shade_rects_folded": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
+                                               _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, _vp, _u32]),
     "pbr_skybox": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(CubeF32), _vp, _u32, _vp, _u32]),
     "pbr_gbuffer_encode": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "pbr_gbuffer_raster_scratch_bytes": (_sz, [_u32, _u32, _u32]),

@@ -241,6 +241,26 @@ class PbrContext:
                                                       _ptr(env), env_size, env_mips, _ptr(clusters), _ptr(lights),
                                                       int(num_lights), _ptr(hdr), hdr_pitch, C.cast(arr, C.c_void_p), len(rects)))
 
+    def lut_fold_x(self, lut, lut_res, out=None):
+        """The x-folded LUT the *_folded shades read (one-shot per LUT): float32 [lut_res, 256, 2], entry [y, rb] = the x-lerps of
+        LUT row y's two channels at roughness byte rb, the very fp32 values deferred_shade computes per pixel."""
+        out = out if out is not None else self.empty((int(lut_res), 256, 2), torch.float32)
+        self._check(self.lib.pbr_lut_fold_x(self.h, _ptr(lut), int(lut_res), _ptr(out)))
+        return out
+
+    def deferred_shade_folded(self, g: Global, tile: Tile, gb, pitch, lut_fold, lut_res, env, env_size, env_mips,
+                              clusters, lights, num_lights, hdr, hdr_pitch, rects=None):
+        """deferred_shade (rects: deferred_shade_rects) with the LUT read from lut_fold_x()'s table: the same bits, fewer instructions."""
+        s = GBuffer(gb["A"].data_ptr(), gb["B"].data_ptr(), gb["C"].data_ptr(), gb["depth"].data_ptr(),
+                    gb["stencil"].data_ptr(), pitch)
+        head = (self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut_fold), lut_res, _ptr(env), env_size, env_mips,
+                _ptr(clusters), _ptr(lights), int(num_lights), _ptr(hdr), hdr_pitch)
+        if rects is None:
+            self._check(self.lib.pbr_deferred_shade_folded(*head))
+        else:
+            arr = self._rects(rects)
+            self._check(self.lib.pbr_deferred_shade_rects_folded(*head, C.cast(arr, C.c_void_p), len(rects)))
+
     def deferred_shade_f32(self, g: Global, tile: Tile, gb, pitch, lut, lut_res, env, env_size, env_mips,
                            clusters, lights, num_lights, hdr_f32, hdr_pitch):
         """Parity probe: deferred_shade with a float32 [h, w, 4] output (the colour before the fp16 store)."""

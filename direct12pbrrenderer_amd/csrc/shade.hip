@@ -38,6 +38,7 @@ struct ShadeParams {
     const uint8_t* stencil;
     uint32_t pitch;
     const pbr_half* lut;
+    const float* lut_fold;   // LUTFOLD instantiations: the x-folded LUT (pbr_lut_fold_x) instead of `lut`
     uint32_t lut_res;
     const pbr_half* env;   // padded layout
     uint32_t env_size, env_mips;
@@ -170,6 +171,43 @@ __device__ __forceinline__ f2 zero2() {
 struct alignas(8) H4x2 { H4 a, b; };   // two x-adjacent half4 texels (16 bytes, 8-byte aligned)
 struct alignas(4) H2x2 { H2 a, b; };   // two x-adjacent LUT texels (8 bytes, 4-byte aligned)
 
+// The x side of the LUT's bilinear sample (clamp addressing, Q5) is a function of the roughness byte and the LUT alone.  lut_x_side:
+// the row pair (xb, xb + 1) always lies inside the row; where the sampler's clamp makes both taps the SAME texel (the first / last
+// half texel) the weight is moved onto it (0 or 1) instead of selecting texels.  Roughness lies in [0, 1] (UNORM8): no NaN / range
+// guard; x.8 fixed-point snap as in pbr_device.hpp::bilinear_coord.  lut_row_pair / lut_x_lerp: the pair of one row and its lerp (two
+// v_fma_mix_f32 per channel).  The pixel evaluates them per sample; pbr_lut_fold_x evaluates the SAME functions once per (row,
+// roughness byte) into the folded table, whose entries are therefore the pixel's own fp32 values.
+struct LutX { int xb; float fx, wx0; };
+__device__ __forceinline__ LutX lut_x_side(float roughness, int lr) {
+    const float xs = snap8(roughness * (float)lr) - 0.5f;
+    const float xfl = floorf(xs);
+    const int xi = (int)xfl;
+    LutX r;
+    r.xb = clampi(xi, 0, max(lr - 2, 0));
+    r.fx = xi < 0 ? 0.0f : (xi > lr - 2 ? 1.0f : xs - xfl);
+    r.wx0 = 1.0f - r.fx;
+    return r;
+}
+__device__ __forceinline__ H2x2 lut_row_pair(const pbr_half* lut_, int lr, int y, int xb) {
+    const H2* lut = reinterpret_cast<const H2*>(lut_);
+    H2x2 lt;
+    if (lr > 1) lt = *reinterpret_cast<const H2x2*>(reinterpret_cast<const char*>(lut) + (__umul24((uint32_t)y, (uint32_t)lr) + (uint32_t)xb) * 4u);   // 32-bit byte offsets: lr <= 16384 (host-checked)
+    else lt.a = lt.b = lut[0];
+    return lt;
+}
+__device__ __forceinline__ float lut_x_lerp(h16 a, h16 b, const LutX& x) { return __builtin_fmaf((float)b, x.fx, __builtin_fmaf((float)a, x.wx0, 0.0f)); }   // two v_fma_mix_f32, see fetch
+
+// pbr_lut_fold_x: entry [y][rb] = the x-lerps of LUT row y's two channels at roughness byte rb, as two floats.  One thread per entry.
+__global__ __launch_bounds__(256) void k_lut_fold_x(const pbr_half* __restrict__ lut, int lr, float* __restrict__ out) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;   // < lr * 256 <= 2^22
+    const int y = (int)(t >> 8);
+    if (y >= lr) return;
+    const float roughness = (float)(t & 255u) * (1.0f / 255.0f);   // the pixel's decode of the C plane's byte
+    const LutX x = lut_x_side(roughness, lr);
+    const H2x2 lt = lut_row_pair(lut, lr, y, x.xb);
+    reinterpret_cast<float2*>(out)[t] = make_float2(lut_x_lerp(lt.a.x, lt.b.x, x), lut_x_lerp(lt.a.y, lt.b.y, x));
+}
+
 // One pixel.  The kernel is bound by VALU ISSUE at 256 lights (SQ_ACTIVE_INST_VALU ~90 % of the launch), so the design
 // constraints are instruction count and instruction class; measured issue costs on gfx950 at this kernel's occupancy of
 // 5 waves per SIMD (tools/valu_rate3.hip -> profiles/r02_valu_rate3.txt, shader-clock cycles per wave-instruction per
@@ -182,7 +220,7 @@ struct alignas(4) H2x2 { H2 a, b; };   // two x-adjacent LUT texels (8 bytes, 4-
 //        S1_c = sum col_c X (1-f5), S2_c = sum col_c X s, S3_c = sum col_c X s f5,   s = NdotL/(T A B)
 //   3. material: re-reads the A/C planes (L2 hits) and folds the sums;
 //   4. IBL: SH diffuse + split-sum specular from the padded env chain and the LUT.
-template <bool STAGED_LISTS, int LSTRIDE, bool F32OUT>
+template <bool STAGED_LISTS, int LSTRIDE, bool F32OUT, bool LUTFOLD>
 __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* llds, const uint32_t* lists, const uint32_t* mip_off,
                                             int n_lights, int q_safe, uint32_t px, uint32_t py, float4 row, float cvv_x, uint32_t col_list) {
     // 32-bit element index (host-checked: pitch * rows * 16 < 2^32): a uniform base + one 32-bit lane offset per access instead of
@@ -478,33 +516,32 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
         const V3 envc = v3(0.5f, 0.5f, 0.5f);
 #endif
 #ifndef PBR_EXP_NOLUT
-        // LUT bilinear with clamp addressing (Q5): one 8-byte pair per row; at the borders both taps are
-        // the same texel, picked out of the pair that stays inside the row
-        // Both coordinates lie in [0, 1] (UNORM8 roughness, clamped N.V): no NaN / range guard; x.8 fixed-point snap as in
-        // pbr_device.hpp::bilinear_coord.  The row pair (xb, xb + 1) always lies inside the row; where the sampler's clamp makes
-        // both taps the SAME texel (the first / last half texel) the weight is moved onto it (0 or 1) instead of selecting texels.
+        // LUT bilinear with clamp addressing (Q5): one 8-byte pair per row (the x side: lut_x_side above).  N.V is clamped to [0, 1]:
+        // no NaN / range guard; x.8 fixed-point snap as in pbr_device.hpp::bilinear_coord.
         const int lr = (int)p.lut_res;
-        const float lrf = (float)lr;
-        const float xs = snap8(roughness * lrf) - 0.5f, ys = snap8(NdotV * lrf) - 0.5f;
-        const float xfl = floorf(xs), yfl = floorf(ys);
-        const int xi = (int)xfl, yi = (int)yfl;
+        const float ys = snap8(NdotV * (float)lr) - 0.5f;
+        const float yfl = floorf(ys);
+        const int yi = (int)yfl;
         const int y0 = clampi(yi, 0, lr - 1), y1 = clampi(yi + 1, 0, lr - 1);
-        const int xb = clampi(xi, 0, max(lr - 2, 0));
-        const float fx = xi < 0 ? 0.0f : (xi > lr - 2 ? 1.0f : xs - xfl), fy = ys - yfl;
-        const H2* lut = reinterpret_cast<const H2*>(p.lut);
-        H2x2 lt0, lt1;
-        if (lr > 1) {
-            const char* lb8 = reinterpret_cast<const char*>(lut);   // 32-bit byte offsets: lr <= 16384 (host-checked)
-            lt0 = *reinterpret_cast<const H2x2*>(lb8 + (__umul24((uint32_t)y0, (uint32_t)lr) + (uint32_t)xb) * 4u);
-            lt1 = *reinterpret_cast<const H2x2*>(lb8 + (__umul24((uint32_t)y1, (uint32_t)lr) + (uint32_t)xb) * 4u);
+        const float fy = ys - yfl, wy0 = 1.0f - fy;
+        float la, lb;
+        if constexpr (LUTFOLD) {
+            // the x-lerps of both rows come ready from the folded table (entry [row][roughness byte], 8 bytes: the same two gathers);
+            // the y-lerp in the association the sampled form's contraction has: fma(X0, wy0, X1 * fy)
+            // the entry's byte offset in its row, 8 x the roughness byte, from the float in hand (byte / 255 rounded: 2040 x it is within
+            // 3e-4 of 8 x byte, so + 0.5 truncates to it): two instructions, like (c & 255) * 8 on the C plane's re-read, which timed the same
+            const uint32_t rb8 = (uint32_t)__builtin_fmaf(roughness, 2040.0f, 0.5f);
+            const char* ft = reinterpret_cast<const char*>(p.lut_fold);
+            const float2 f0 = *reinterpret_cast<const float2*>(ft + (((uint32_t)y0 << 11) | rb8));   // 32-bit byte offsets: lr <= 16384
+            const float2 f1 = *reinterpret_cast<const float2*>(ft + (((uint32_t)y1 << 11) | rb8));
+            la = __builtin_fmaf(f0.x, wy0, f1.x * fy);
+            lb = __builtin_fmaf(f0.y, wy0, f1.y * fy);
         } else {
-            lt0.a = lt0.b = lut[0];
-            lt1 = lt0;
+            const LutX lx = lut_x_side(roughness, lr);
+            const H2x2 lt0 = lut_row_pair(p.lut, lr, y0, lx.xb), lt1 = lut_row_pair(p.lut, lr, y1, lx.xb);
+            la = lut_x_lerp(lt0.a.x, lt0.b.x, lx) * wy0 + lut_x_lerp(lt1.a.x, lt1.b.x, lx) * fy;
+            lb = lut_x_lerp(lt0.a.y, lt0.b.y, lx) * wy0 + lut_x_lerp(lt1.a.y, lt1.b.y, lx) * fy;
         }
-        const float wx0 = 1.0f - fx, wy0 = 1.0f - fy;
-        auto xl = [&](h16 a, h16 b) { return __builtin_fmaf((float)b, fx, __builtin_fmaf((float)a, wx0, 0.0f)); };   // two v_fma_mix_f32, see fetch
-        const float la = xl(lt0.a.x, lt0.b.x) * wy0 + xl(lt1.a.x, lt1.b.x) * fy;
-        const float lb = xl(lt0.a.y, lt0.b.y) * wy0 + xl(lt1.a.y, lt1.b.y) * fy;
 #else
         const float la = 0.5f, lb = 0.25f;
 #endif
@@ -566,7 +603,8 @@ struct ShadeView {
 struct ShadeViews { ShadeView v[PBR_MAX_VIEWS]; };
 static_assert(sizeof(ShadeParams) + sizeof(ShadeViews) + sizeof(ShadeRects) + 16 <= 4096 - 256, "k_deferred_shade<.., ShadeViews>: kernel arguments over 4 KiB");
 
-template <bool STAGED_LISTS, int LSTRIDE, bool F32OUT, class VS = NoViews>
+// LUTFOLD: the split-sum LUT is read from its x-folded table (p.lut_fold, pbr_lut_fold_x) — the same bits with ~30 instructions less per pixel.
+template <bool STAGED_LISTS, int LSTRIDE, bool F32OUT, class VS = NoViews, bool LUTFOLD = false>
 __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade(ShadeParams p_, int n_lights_, int max_clusters, ShadeRects rc, VS vs) {
     constexpr bool MV = !std::is_same_v<VS, NoViews>;   // VS = ShadeViews: view blockIdx.y of vs; NoViews (empty): the single-view kernel
     ShadeParams q;                                      // MV: p_ with the view's fields
@@ -694,11 +732,11 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
 #ifndef PBR_SHADE_TIMING
     if (px >= x_end) return;
     for (uint32_t py = y_begin; py < y_end; py++)
-        shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
+        shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT, LUTFOLD>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
 #else
     if (px < x_end)
         for (uint32_t py = y_begin; py < y_end; py++)
-            shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
+            shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT, LUTFOLD>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
     SHADE_ISTAMP_MAX(blockIdx.x, 2, SHADE_NOW());
 #endif
 }
@@ -746,12 +784,13 @@ static ShadeParams shade_params(const pbr_global* g, const pbr_half* lut, uint32
 }
 
 // The checks of a shade launch return what is wrong (nullptr: nothing).  The LUT and padded env chain every target reads:
-static const char* shade_tables_bad(const pbr_half* lut, uint32_t lut_res, const pbr_half* env, uint32_t env_size, uint32_t env_mips) {
+// (lut: the half2 LUT, or — lut_align 8 — its x-folded table)
+static const char* shade_tables_bad(const void* lut, uint32_t lut_res, const pbr_half* env, uint32_t env_size, uint32_t env_mips, uint32_t lut_align = 4) {
     if (!lut || !env) return "null pointer";
     if (!(lut_res >= 1 && env_size >= 1 && env_mips >= 1 && env_mips <= 16 && (env_size >> (env_mips - 1)) >= 1)) return "bad LUT/env size";
     if (!(lut_res <= 16384 && (uint64_t)pbr_env_padded_texels(env_size, env_mips) * 8u < (1ull << 32)))
         return "LUT larger than 16384^2 or padded env chain of 4 GiB or more (32-bit texture offsets)";
-    if (((uintptr_t)env & 7u) != 0 || ((uintptr_t)lut & 3u) != 0) return "env must be 8-byte and lut 4-byte aligned";
+    if (((uintptr_t)env & 7u) != 0 || ((uintptr_t)lut & (lut_align - 1u)) != 0) return lut_align == 4 ? "env must be 8-byte and lut 4-byte aligned" : "env and the folded LUT must be 8-byte aligned";
     return nullptr;
 }
 
@@ -810,7 +849,7 @@ static ShadeRects shade_schedule(const pbr_ctx* ctx, const uint32_t (*rects)[4],
 
 // One launch of the schedule rc over n_views views (grid: rc's blocks x n_views) of a p.full_w x p.full_h frame whose views hold at most
 // max_lights lights.  VS = NoViews: p is the one view's, num_lights its light count; VS = ShadeViews: every view's own fields come from vs.
-template <bool F32OUT, class VS>
+template <bool F32OUT, bool LUTFOLD, class VS>
 static pbr_status shade_dispatch(pbr_ctx* ctx, const ShadeParams& p, int num_lights, int max_lights, const ShadeRects& rc, uint32_t n_views, const VS& vs) {
     // A block covers 256 x 8 pixels.  It can stage its cluster lists when that rectangle spans at most
     // MAX_STAGED_TILES cluster tiles: a tile is full_w/24 x full_h/16 pixels, +1 per axis for straddling.
@@ -825,16 +864,17 @@ static pbr_status shade_dispatch(pbr_ctx* ctx, const ShadeParams& p, int num_lig
     const int max_clusters = staged ? (int)(span_x * span_y) * PBR_CLUSTER_Z : 0;
     const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t);
     const dim3 grid(rc.first[rc.n], n_views), blk(SHADE_BLOCK);
-    if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, F32OUT, VS>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
-    else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, F32OUT, VS>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
-    else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, F32OUT, VS>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, vs);
-    else hipLaunchKernelGGL((k_deferred_shade<false, PBR_MAX_SCENE_LIGHTS + 1, F32OUT, VS>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, vs);
+    if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
+    else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
+    else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, vs);
+    else hipLaunchKernelGGL((k_deferred_shade<false, PBR_MAX_SCENE_LIGHTS + 1, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, vs);
     return launched(ctx, std::is_same_v<VS, NoViews> ? "k_deferred_shade" : "k_deferred_shade<views>");
 }
 
-template <bool F32OUT>
+// LUTFOLD: `lut` is the x-folded table of the lut_res^2 LUT (pbr_lut_fold_x)
+template <bool F32OUT, bool LUTFOLD = false>
 static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
-                               const pbr_half* lut, uint32_t lut_res,
+                               const void* lut, uint32_t lut_res,
                                const pbr_half* env, uint32_t env_size, uint32_t env_mips,
                                const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
                                pbr_half* hdr, float* hdr_f32, uint32_t hdr_pitch,
@@ -845,7 +885,7 @@ static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile
     PBR_REQUIRE(ctx, tile->w >= 1 && tile->h >= 1 && tile->w <= 65535 && tile->h <= 65535, "pbr_deferred_shade: bad tile size");
     PBR_REQUIRE(ctx, tile->x0 + tile->w <= tile->full_w && tile->y0 + tile->h <= tile->full_h, "pbr_deferred_shade: tile outside frame");
     PBR_CHECK(ctx, who, shade_target_bad(g, *gb, clusters, F32OUT ? (const void*)hdr_f32 : (const void*)hdr, hdr_pitch, tile->w, tile->h, lights, num_lights));
-    PBR_CHECK(ctx, who, shade_tables_bad(lut, lut_res, env, env_size, env_mips));
+    PBR_CHECK(ctx, who, shade_tables_bad(lut, lut_res, env, env_size, env_mips, LUTFOLD ? 8 : 4));
     const uint32_t whole[1][4] = {{0, 0, tile->w, tile->h}};
     if (!rects) { rects = whole; n_rects = 1; }
     PBR_REQUIRE(ctx, n_rects >= 1 && n_rects <= (uint32_t)SHADE_MAX_RECTS, "pbr_deferred_shade: 1 .. 5 rectangles");
@@ -853,11 +893,12 @@ static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile
         const uint32_t* q = rects[r];
         PBR_REQUIRE(ctx, q[2] >= 1 && q[3] >= 1 && q[0] + q[2] <= tile->w && q[1] + q[3] <= tile->h, "pbr_deferred_shade: rectangle outside the tile");
     }
-    ShadeParams p = shade_params(g, lut, lut_res, env, env_size, env_mips);
+    ShadeParams p = shade_params(g, LUTFOLD ? nullptr : (const pbr_half*)lut, lut_res, env, env_size, env_mips);
+    if (LUTFOLD) p.lut_fold = (const float*)lut;
     p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h; p.full_w = tile->full_w; p.full_h = tile->full_h;
     p.A = gb->A; p.B = gb->B; p.C = gb->C; p.depth = gb->depth; p.stencil = gb->stencil; p.pitch = gb->pitch;
     p.clusters = clusters; p.lights = lights; p.hdr = hdr; p.hdr_pitch = hdr_pitch; p.hdr_f32 = hdr_f32;
-    return shade_dispatch<F32OUT>(ctx, p, num_lights, num_lights, shade_schedule(ctx, rects, n_rects, 1), 1, NoViews{});
+    return shade_dispatch<F32OUT, LUTFOLD>(ctx, p, num_lights, num_lights, shade_schedule(ctx, rects, n_rects, 1), 1, NoViews{});
 }
 
 extern "C" {
@@ -879,6 +920,35 @@ pbr_status pbr_deferred_shade_rects(pbr_ctx* ctx, const pbr_global* g, const pbr
                                     pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects) {
     if (ctx && !rects) return pbr::fail(ctx, PBR_ERR_INVALID, "pbr_deferred_shade_rects: null rectangle list");
     return shade_launch<false>(ctx, g, tile, gb, lut, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch, rects, n_rects);
+}
+
+// The x-folded LUT: out_fold[y][rb] (lut_res x 256 entries of two floats) = the x-lerps of LUT row y's two channels at roughness
+// byte rb, exactly the fp32 values the shade's sampled form computes per pixel.  Once per LUT.
+pbr_status pbr_lut_fold_x(pbr_ctx* ctx, const pbr_half* lut, uint32_t lut_res, float* out_fold) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, lut && out_fold, "pbr_lut_fold_x: null pointer");
+    PBR_REQUIRE(ctx, lut_res >= 1 && lut_res <= 16384, "pbr_lut_fold_x: lut_res out of [1, 16384]");
+    PBR_REQUIRE(ctx, ((uintptr_t)lut & 3u) == 0 && ((uintptr_t)out_fold & 7u) == 0, "pbr_lut_fold_x: lut must be 4-byte and the table 8-byte aligned");
+    hipLaunchKernelGGL(k_lut_fold_x, dim3(lut_res), dim3(256), 0, ctx->stream, lut, (int)lut_res, out_fold);
+    return launched(ctx, "k_lut_fold_x");
+}
+
+// pbr_deferred_shade / _rects reading the LUT from its x-folded table: the same pixels to the bit
+pbr_status pbr_deferred_shade_folded(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
+                                     const float* lut_fold, uint32_t lut_res,
+                                     const pbr_half* env, uint32_t env_size, uint32_t env_mips,
+                                     const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
+                                     pbr_half* hdr, uint32_t hdr_pitch) {
+    return shade_launch<false, true>(ctx, g, tile, gb, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch);
+}
+
+pbr_status pbr_deferred_shade_rects_folded(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
+                                           const float* lut_fold, uint32_t lut_res,
+                                           const pbr_half* env, uint32_t env_size, uint32_t env_mips,
+                                           const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
+                                           pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects) {
+    if (ctx && !rects) return pbr::fail(ctx, PBR_ERR_INVALID, "pbr_deferred_shade_rects_folded: null rectangle list");
+    return shade_launch<false, true>(ctx, g, tile, gb, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch, rects, n_rects);
 }
 
 // Parity probe: the same kernel body, storing float4 instead of rounding to the R16G16B16A16_FLOAT target — what the
@@ -927,7 +997,7 @@ pbr_status pbr_deferred_shade_views(pbr_ctx* ctx, const pbr_view* views, uint32_
     ShadeParams p = shade_params(&views[0].g, lut, lut_res, env, env_size, env_mips);
     p.w = p.full_w = w; p.h = p.full_h = h;
     const uint32_t whole[1][4] = {{0, 0, w, h}};
-    return shade_dispatch<false>(ctx, p, 0, max_lights, shade_schedule(ctx, whole, 1, n), n, vs);
+    return shade_dispatch<false, false>(ctx, p, 0, max_lights, shade_schedule(ctx, whole, 1, n), n, vs);
 }
 
 }  // extern "C"

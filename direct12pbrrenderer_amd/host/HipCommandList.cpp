@@ -274,6 +274,7 @@ void HipCommandList::Dispatch(ShadingState* s, uint32 gx, uint32 gy, uint32 gz) 
         if (!out || out->Width() != c.TextureResolution || out->Height() != c.TextureResolution) throw HipException("precompute_brdf: LUT size != TextureResolution");
         ExpectGroups(f, gx, gy, gz, Groups(c.TextureResolution, 8), Groups(c.TextureResolution, 8), 1);
         Check(pbr_brdf_lut(mCtx, c.TextureResolution, (pbr_half*)out->DevicePtr()), "pbr_brdf_lut");
+        mFoldedLut.erase(out);   // the folded table the shade reads is stale now
     } else if (f == "env_map_gen.hlsl") {
         const auto& c = s->Constants<PreFilterEnvMapConstant>();
         auto* sky = dynamic_cast<DeviceTexture2DArray*>(s->Texture("SkyBox").Texture);
@@ -386,12 +387,18 @@ void HipCommandList::DrawScreen(ShadingState* s) {
             padded = std::make_unique<DeviceStructuredBuffer>((uint32)(pbr_env_padded_texels(env->Size(), env->MipLevels()) * 8), 8);
             Check(pbr_env_pad(mCtx, (const pbr_half*)env->DevicePtr(), env->Size(), env->MipLevels(), (pbr_half*)padded->DevicePtr()), "pbr_env_pad");
         }
+        // ... and the LUT from its x-folded table (the x-lerp of every roughness byte, done once)
+        auto& folded = mFoldedLut[lut];
+        if (!folded) {
+            folded = std::make_unique<DeviceStructuredBuffer>(lut->Width() * 256u * 8u, 8);
+            Check(pbr_lut_fold_x(mCtx, (const pbr_half*)lut->DevicePtr(), lut->Width(), (float*)folded->DevicePtr()), "pbr_lut_fold_x");
+        }
         // stencil ref 0, compare LESS: shade where 0 < stencil (DeferredPipeline.h:176-181, .cpp:203)
         if (mStencilRef != 0) throw HipException("deferred_shading: only stencil ref 0 is supported");
-        Check(pbr_deferred_shade(mCtx, &mGlobal, &tile, &gb, (const pbr_half*)lut->DevicePtr(), lut->Width(),
-                                 (const pbr_half*)padded->DevicePtr(), env->Size(), env->MipLevels(),
-                                 (const pbr_cluster*)s->Buffer("Clusters")->DevicePtr(), (const pbr_light*)s->Buffer("PointLights")->DevicePtr(),
-                                 mNumLights, (pbr_half*)mRenderTarget->DevicePtr(), w), "pbr_deferred_shade");
+        Check(pbr_deferred_shade_folded(mCtx, &mGlobal, &tile, &gb, (const float*)folded->DevicePtr(), lut->Width(),
+                                        (const pbr_half*)padded->DevicePtr(), env->Size(), env->MipLevels(),
+                                        (const pbr_cluster*)s->Buffer("Clusters")->DevicePtr(), (const pbr_light*)s->Buffer("PointLights")->DevicePtr(),
+                                        mNumLights, (pbr_half*)mRenderTarget->DevicePtr(), w), "pbr_deferred_shade_folded");
     } else if (f == "hdr_tone_mapping.hlsl") {
         Mip in = MipOf(s->Texture("LuminanceTexture"));
         // multi-GPU: only the interior rectangle is tone-mapped (the apron belongs to the neighbours)

@@ -170,6 +170,8 @@ private:
     // padded copies of prefiltered env chains (pbr_env_pad), keyed by the plain texture; rebuilt after
     // env_map_gen.hlsl rewrites the texture
     std::map<const DeviceTexture2DArray*, std::unique_ptr<DeviceStructuredBuffer>> mPaddedEnv;
+    // x-folded tables of split-sum LUTs (pbr_lut_fold_x), keyed by the LUT texture; rebuilt after precompute_brdf.hlsl rewrites it
+    std::map<const DeviceTexture2D*, std::unique_ptr<DeviceStructuredBuffer>> mFoldedLut;
 };
 
 // RAII twin of the reference's PIXScope(cmd, name) macro (DeferredPipeline.cpp:8)

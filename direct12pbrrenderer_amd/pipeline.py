@@ -273,6 +273,10 @@ class DeferredFrame:
         # env: plain prefiltered chain (pbr_prefilter_env); the shade samples its padded copy (one-shot)
         self.lut, self.lut_res, self.env_size, self.env_mips = lut, lut_res, env_size, env_mips
         self.env = ctx.env_pad(env, env_size, env_mips)
+        # the shade reads the LUT from its x-folded table (one-shot, like the padded env chain); _lut_folded names the LUT it was made
+        # from: a frame whose lut / lut_res is replaced goes back to the sampled LUT until refold_lut()
+        self.lut_fold = None
+        self.refold_lut()
         self.allreduce = allreduce
         ew, eh = spec.ew, spec.eh
         self.clusters = ctx.alloc_clusters()
@@ -412,16 +416,29 @@ class DeferredFrame:
         cube, size, mips = self.sky
         self.ctx.skybox(self.g, self.tile, cube, size, mips, self.gb["stencil"], s.sw, self.hdr, s.sw)
 
-    def shade(self):
+    def refold_lut(self):
+        """Rebuild the x-folded table from self.lut (after the LUT's texels were rewritten in place or the tensor was replaced)."""
+        self.lut_fold = self.ctx.lut_fold_x(self.lut, self.lut_res, out=self.lut_fold if self.lut_fold is not None and self.lut_fold.shape[0] == self.lut_res else None)
+        self._lut_folded = (self.lut.data_ptr(), self.lut_res)
+
+    def _shade(self, rects):
         s = self.spec
-        self.ctx.deferred_shade(self.g, self.tile, self.gb, s.sw, self.lut, self.lut_res, self.env, self.env_size,
-                                self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw)
+        if self._lut_folded == (self.lut.data_ptr(), self.lut_res):
+            self.ctx.deferred_shade_folded(self.g, self.tile, self.gb, s.sw, self.lut_fold, self.lut_res, self.env, self.env_size,
+                                           self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw, rects)
+        elif rects is None:
+            self.ctx.deferred_shade(self.g, self.tile, self.gb, s.sw, self.lut, self.lut_res, self.env, self.env_size,
+                                    self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw)
+        else:
+            self.ctx.deferred_shade_rects(self.g, self.tile, self.gb, s.sw, self.lut, self.lut_res, self.env, self.env_size,
+                                          self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw, rects)
+
+    def shade(self):
+        self._shade(None)
 
     def shade_rects(self, rects):
         """The shade on rectangles (x, y, w, h) of the shaded rectangle S, ONE launch (pbr_deferred_shade_rects)."""
-        s = self.spec
-        self.ctx.deferred_shade_rects(self.g, self.tile, self.gb, s.sw, self.lut, self.lut_res, self.env, self.env_size,
-                                      self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw, rects)
+        self._shade(rects)
 
     def prefilter_l1_rects(self, rects):
         s = self.spec

@@ -310,6 +310,28 @@ pbr_status pbr_deferred_shade_rects(pbr_ctx* ctx, const pbr_global* g, const pbr
                                     const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
                                     pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects);
 
+/* The x-folded split-sum LUT.  The x side of the shade's bilinear LUT sample (coordinate snap, clamps, the lerp of the two taps of a
+ * row) depends on the pixel's roughness BYTE and on the LUT alone: out_fold[(y * 256 + rb) * 2 + {0, 1}] holds, for LUT row y and
+ * roughness byte rb, the fp32 x-lerp of each of the LUT's two channels — evaluated by the very device functions the shade calls per
+ * pixel, so a shade that reads them does the y-lerp alone and gets the same bits.  Once per LUT (lut_res <= 16384);
+ * out_fold: device, lut_res * 256 * 2 floats (1 MiB for a 512^2 LUT, the LUT's own size), 8-byte aligned. */
+pbr_status pbr_lut_fold_x(pbr_ctx* ctx, const pbr_half* lut, uint32_t lut_res, float* out_fold);
+
+/* pbr_deferred_shade / pbr_deferred_shade_rects with the LUT given as pbr_lut_fold_x's table (of a lut_res^2 LUT): the same HDR
+ * target bit for bit, ~33 VALU instructions less per pixel.  Everything else as documented there. */
+pbr_status pbr_deferred_shade_folded(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                     const pbr_gbuffer* gb,
+                                     const float* lut_fold, uint32_t lut_res,
+                                     const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
+                                     const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
+                                     pbr_half* hdr, uint32_t hdr_pitch);
+pbr_status pbr_deferred_shade_rects_folded(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                           const pbr_gbuffer* gb,
+                                           const float* lut_fold, uint32_t lut_res,
+                                           const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
+                                           const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
+                                           pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects);
+
 /* Parity probe (not a product path): the same shade, storing the fp32 colour (float4 per pixel, alpha 1, pitch
  * hdr_pitch pixels, 16-byte aligned) instead of rounding it to the half4 target — the buffer the <= 1e-4 relative
  * L-inf parity bound is stated on. */

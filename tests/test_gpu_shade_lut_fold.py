@@ -1,0 +1,177 @@
+"""The shade that reads the split-sum LUT from its x-folded table (pbr_lut_fold_x -> pbr_deferred_shade_folded / _rects_folded) writes
+the HDR target of pbr_deferred_shade / _rects BIT FOR BIT (compared as int16), both given the same inputs: the table holds the fp32
+x-lerps the sampled form computes per pixel, and the pixel's y-lerp keeps the sampled form's association.
+Shapes: a 1536 x 64 frame (staged lists) whose C plane puts roughness byte x & 255 in column x over the synthetic G-buffer's uniform
+octahedral normals (N.V over [0, 1], its clamp at 0 included), at LUT sizes 1, 2, 32 and 512 (one texel; one pair per row whose both
+halves are border halves; the oracle's size; the product's); a tile of a 4K frame at odd offsets, whole and as two rectangles; a
+256 x 64 frame (global lists); light counts on both strides of the light table."""
+import numpy as np
+import pytest
+import torch
+
+import common
+from direct12pbrrenderer_amd import scene, synth
+from direct12pbrrenderer_amd.api import PbrError
+from direct12pbrrenderer_amd.pipeline import DeferredFrame, TileSpec
+from direct12pbrrenderer_amd.structs import Tile
+
+pytestmark = pytest.mark.gpu
+
+ES, EM = common.ENV_SIZE, common.ENV_MIPS
+FRAME = (0, 0, 1536, 64, 1536, 64)             # x0, y0, w, h, full_w, full_h
+TILE_4K = (1300, 1000, 600, 40, 3840, 2160)    # partial last column block, long and one-row blocks, blocks straddling cluster tiles
+SMALL = (0, 0, 256, 64, 256, 64)               # too small to stage lists: the global-list kernel
+
+
+def dev_half(ctx, arr):
+    return ctx.upload(np.ascontiguousarray(arr, dtype=np.float16).view(np.uint16)).view(torch.float16)
+
+
+@pytest.fixture(scope="module")
+def world(ctx, ibl):
+    """device LUTs (pbr_brdf_lut's, one per size) with their folded tables, the padded env chain, and one scene per shape: made once"""
+    sky, env, lut, sh = ibl
+    w = dict(sh=sh, env_plain=dev_half(ctx, env), lut={}, fold={}, scene={})
+    w["denv"] = ctx.env_pad(w["env_plain"], ES, EM)
+    for lr in (1, 2, 32, 512):
+        # (pbr_brdf_lut starts at 2 x 2: the one-texel LUT is two made-up values)
+        w["lut"][lr] = ctx.brdf_lut(lr) if lr > 1 else dev_half(ctx, np.array([[[0.37, 0.61]]], dtype=np.float16))
+        w["fold"][lr] = ctx.lut_fold_x(w["lut"][lr], lr)
+    for shape in (FRAME, TILE_4K, SMALL):
+        x0, y0, tw, th, fw, fh = shape
+        cam = scene.Camera.reference_default(fw, fh)
+        g = scene.make_global(cam, fw, fh, sh_pack=sh)
+        gb = synth.gbuffer_tile(x0, y0, tw, th, fw, fh, rough_min=0, coverage_mask=(shape != FRAME))
+        if shape == FRAME:   # every roughness byte, in columns
+            gb["C"] = (gb["C"] & np.uint32(0xFFFFFF00)) | (np.arange(tw, dtype=np.uint32) & np.uint32(255))[None, :]
+        w["scene"][shape] = (cam, g, {k: ctx.upload(v) for k, v in gb.items()}, gb["stencil"] > 0)
+    ctx.sync()
+    return w
+
+
+def lights_of(ctx, w, shape, n):
+    """(device lights or None, device cluster table) of n lights for the shape's camera"""
+    cam, g = w["scene"][shape][:2]
+    key = ("lights", shape, n)
+    if key not in w:
+        lights = common.shade_scene(8, 8, n, w["sh"], full=shape[4:])[2]
+        dl = ctx.upload(lights) if n else None
+        cl = ctx.alloc_clusters()
+        ctx.clustered(g, dl, n, cl)
+        w[key] = (dl, cl)
+    return w[key]
+
+
+def both(ctx, w, shape, n_lights, lr, rects=None, prefill=3.0):
+    """(sampled, folded) HDR targets as int16, and the mask of shaded pixels"""
+    x0, y0, tw, th, fw, fh = shape
+    cam, g, gbd, on = w["scene"][shape]
+    dl, cl = lights_of(ctx, w, shape, n_lights)
+    tile = Tile(x0, y0, tw, th, fw, fh)
+    out = []
+    for folded in (False, True):
+        hdr = torch.full((th, tw, 4), prefill, dtype=torch.float16, device=ctx.torch_device)
+        tail = (ES, EM, cl, dl, n_lights, hdr, tw)
+        if folded:
+            ctx.deferred_shade_folded(g, tile, gbd, tw, w["fold"][lr], lr, w["denv"], *tail, rects)
+        elif rects is None:
+            ctx.deferred_shade(g, tile, gbd, tw, w["lut"][lr], lr, w["denv"], *tail)
+        else:
+            ctx.deferred_shade_rects(g, tile, gbd, tw, w["lut"][lr], lr, w["denv"], *tail, rects)
+        out.append(hdr.view(torch.int16).cpu().numpy())
+    return out[0], out[1], on
+
+
+def test_fold_table_is_the_x_lerp(ctx, world):
+    """entry [y, rb] against the x-lerp in double of the same taps and weight (the weight's snap and clamps restated here): the fp32
+    value is two fused operations on fp16 texels, within 2 ulp of fp32 of the exact lerp"""
+    for lr in (1, 2, 32, 512):
+        lut = world["lut"][lr].cpu().view(torch.int16).numpy().view(np.float16).astype(np.float64)   # [lr, lr, 2]
+        fold = world["fold"][lr].cpu().numpy()
+        assert fold.shape == (lr, 256, 2)
+        rough = (np.arange(256, dtype=np.float32) * np.float32(1.0 / 255.0)).astype(np.float32)
+        xs = np.floor((rough * np.float32(lr)).astype(np.float32).astype(np.float64) * 256.0 + 0.5) / 256.0 - 0.5
+        xi = np.floor(xs).astype(np.int64)
+        xb = np.clip(xi, 0, max(lr - 2, 0))
+        fx = np.where(xi < 0, 0.0, np.where(xi > lr - 2, 1.0, xs - np.floor(xs)))
+        a, b = lut[:, xb, :], lut[:, np.minimum(xb + 1, lr - 1), :]
+        want = a * (1.0 - fx)[None, :, None] + b * fx[None, :, None]
+        tol = 2.0 * np.finfo(np.float32).eps * np.maximum(np.abs(a), np.abs(b)) + 1e-30
+        assert (np.abs(fold - want) <= tol).all(), f"lut_res {lr}: a folded entry is not the x-lerp of its row"
+
+
+@pytest.mark.parametrize("lr", [1, 2, 32, 512])
+def test_every_roughness_byte_bit_exact(ctx, world, lr):
+    ref, got, on = both(ctx, world, FRAME, 256, lr)
+    assert on.all() and not np.array_equal(ref[..., :3], np.full_like(ref[..., :3], np.float16(3.0).view(np.int16)))
+    bad = np.argwhere((ref != got).any(axis=2))
+    assert bad.size == 0, f"lut_res {lr}: {len(bad)} pixels differ, first at (y, x) = {tuple(bad[0])}"
+
+
+@pytest.mark.parametrize("n_lights", [0, 1, 7, 256, 300, 1024])
+def test_tile_of_a_4k_frame_bit_exact(ctx, world, n_lights):
+    ref, got, on = both(ctx, world, TILE_4K, n_lights, 32)
+    assert on.sum() > 0.3 * on.size
+    assert np.array_equal(ref, got), f"{n_lights} lights: the folded shade differs from the sampled one"
+    assert np.all(got[~on] == np.float16(3.0).view(np.int16)), "an unshaded pixel was written"
+
+
+def test_rectangles_bit_exact(ctx, world):
+    rects = [(3, 1, 301, 17), (304, 18, 296, 22)]
+    ref, got, on = both(ctx, world, TILE_4K, 256, 512, rects=rects)
+    inside = np.zeros(on.shape, dtype=bool)
+    for x, y, rw, rh in rects:
+        inside[y:y + rh, x:x + rw] = True
+    assert np.array_equal(ref, got)
+    assert np.all(got[~(inside & on)] == np.float16(3.0).view(np.int16)), "a pixel outside the rectangles was written"
+    assert not np.all(got[inside & on] == np.float16(3.0).view(np.int16))
+
+
+@pytest.mark.parametrize("n_lights", [256, 300])
+def test_small_frame_global_lists_bit_exact(ctx, world, n_lights):
+    ref, got, on = both(ctx, world, SMALL, n_lights, 32)
+    assert np.array_equal(ref, got)
+
+
+def test_refusals(ctx, world):
+    cam, g, gbd, on = world["scene"][SMALL]
+    dl, cl = lights_of(ctx, world, SMALL, 256)
+    hdr = ctx.zeros((64, 256, 4), torch.float16)
+    tile = Tile(*SMALL)
+    with pytest.raises(PbrError):
+        ctx.deferred_shade_folded(g, tile, gbd, 256, None, 32, world["denv"], ES, EM, cl, dl, 256, hdr, 256)
+    odd = world["fold"][32].view(-1)[1:]   # 4-byte aligned only
+    with pytest.raises(PbrError):
+        ctx.deferred_shade_folded(g, tile, gbd, 256, odd, 32, world["denv"], ES, EM, cl, dl, 256, hdr, 256)
+    with pytest.raises(PbrError):
+        ctx.deferred_shade_folded(g, tile, gbd, 256, world["fold"][32], 32, world["denv"], ES, EM, cl, dl, 256, hdr, 256, rects=[(0, 0, 300, 8)])
+    with pytest.raises(PbrError):
+        ctx.lut_fold_x(world["lut"][32], 0, out=world["fold"][32])
+    with pytest.raises(PbrError):
+        ctx.lut_fold_x(None, 32, out=world["fold"][32])
+
+
+def test_frame_uses_the_fold_only_for_the_lut_it_was_made_from(ctx, world):
+    """DeferredFrame: its shade equals pbr_deferred_shade's bits; with its LUT replaced it goes back to sampling (the new LUT's bits),
+    and refold_lut() brings the folded table back (the same bits again)"""
+    x0, y0, tw, th, fw, fh = FRAME
+    cam, g, gbd, on = world["scene"][FRAME]
+    lights = common.shade_scene(8, 8, 256, world["sh"], full=(fw, fh))[2]
+    fr = DeferredFrame(ctx, TileSpec(0, 0, tw, th, fw, fh, 0), g, lights, world["lut"][32], 32, world["env_plain"], ES, EM)
+    fr.gb = gbd
+
+    def frame_bits():
+        fr.hdr.fill_(3.0)
+        fr.clustered()
+        fr.shade()
+        return fr.hdr.view(torch.int16).cpu().numpy()
+
+    ref32, _, _ = both(ctx, world, FRAME, 256, 32)
+    ref512, _, _ = both(ctx, world, FRAME, 256, 512)
+    assert fr._lut_folded == (fr.lut.data_ptr(), 32)
+    assert np.array_equal(frame_bits(), ref32)
+    fr.lut, fr.lut_res = world["lut"][512], 512
+    assert np.array_equal(frame_bits(), ref512), "a frame whose LUT was replaced must not read the old LUT's folded table"
+    fr.refold_lut()
+    assert fr.lut_fold.shape[0] == 512 and np.array_equal(frame_bits(), ref512)
+    assert not np.array_equal(ref32, ref512)

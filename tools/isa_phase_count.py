@@ -1,6 +1,8 @@
 """Instruction-class counts of k_deferred_shade<true, 257, false, NoViews> (the 4K / 256-light instantiation) from the compiler's
 gfx950 ISA.  No GPU needed.
-    python tools/isa_phase_count.py [out.md] [--phases] [--src shade.hip]
+    python tools/isa_phase_count.py [out.md] [--phases] [--fold] [--src shade.hip]
+--fold measures k_deferred_shade<true, 257, false, NoViews, true>, the instantiation that reads the LUT from its x-folded table
+(pbr_deferred_shade_folded), and adds the static v_* count of its LUT phase (the kernel minus its -DPBR_EXP_NOLUT build).
 Reported:
   * the kernel's footer: occupancy, scratch bytes per lane, VGPRs;
   * every light-walk loop (innermost loops that carry the per-light arithmetic): v_* per TRIP (a trip = one pair of lights = four
@@ -30,6 +32,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # type) and the parameter list follow it
 PREFIX = "_Z16k_deferred_shadeILb1ELi257ELb0E"
 VIEWS = "NoViews"
+FOLD_ARG = {False: "NoViewsELb0E", True: "NoViewsELb1E"}   # ... NoViews, LUTFOLD>: the sampled-LUT and the folded-LUT instantiation
 TRIPS = 16   # pairs of lights of a capped (32-entry) list
 
 
@@ -42,11 +45,13 @@ def compile_isa(defines=(), src=SRC, flags=()):
         return open(os.path.join(d, "shade.s")).read()
 
 
-def kernel(text, prefix=PREFIX, views=VIEWS):
+def kernel(text, prefix=PREFIX, views=VIEWS, fold=False):
     """(mangled name, code lines, footer {Occupancy, ScratchSize, NumVgprs, TotalNumSgprs, LDSByteSize}) of the instantiation whose
-    name starts with prefix"""
+    name starts with prefix (fold: the folded-LUT one; a source from before that template argument has only the sampled one)"""
     names = [m.group(1) for m in re.finditer(r"^(" + re.escape(prefix) + r"\w*):", text, re.M)]
-    names = [n for n in names if n == prefix] or [n for n in names if views in n] or names
+    if fold and not any(FOLD_ARG[True] in n for n in names):
+        raise SystemExit(f"no folded-LUT instantiation of {prefix}* in the ISA")
+    names = [n for n in names if n == prefix] or [n for n in names if FOLD_ARG[fold] in n] or [n for n in names if views in n] or names
     if not names:
         raise SystemExit(f"no kernel named {prefix}* in the ISA")
     name = names[0]
@@ -102,9 +107,11 @@ def walks_and_row(lines):
     return [(lb, body) for lb, body in inner.items() if count(body)["packed"] >= 40], row
 
 
-def measure(src=SRC):
-    with ThreadPoolExecutor(2) as ex:
-        shipped, noexact = ex.map(lambda d: kernel(compile_isa(d, src)), [(), ("PBR_EXP_NOEXACT",)])
+def measure(src=SRC, fold=False, lut_phase=False):
+    """lut_phase: also the static v_* of the LUT phase (one more compile, -DPBR_EXP_NOLUT)"""
+    builds = [(), ("PBR_EXP_NOEXACT",)] + ([("PBR_EXP_NOLUT",)] if lut_phase else [])
+    with ThreadPoolExecutor(len(builds)) as ex:
+        shipped, noexact, *nolut = ex.map(lambda d: kernel(compile_isa(d, src), fold=fold), builds)
     name, code, foot = shipped
     walks, row = walks_and_row(code)
     if not walks or not row:
@@ -125,20 +132,23 @@ def measure(src=SRC):
     res["exact_path"] = res["row_static"] - in_walks - res["surround"]
     res["hot_trip"] = hot["valu_per_trip"]
     res["row_executed"] = res["surround"] + TRIPS * hot["valu_per_trip"]
+    if nolut:
+        res["lut_phase"] = res["kernel"]["valu"] - count(nolut[0][1])["valu"]
     return res
 
 
 METRICS = [("occupancy", "occupancy (waves per SIMD)"), ("scratch", "scratch bytes per lane"), ("hot_trip", "v_* per trip, as-shipped walk"),
            ("surround", "v_* per pixel row around the walk (row body - walk loops - exact-slice path)"),
            ("row_executed", f"executed v_* per pixel row at {TRIPS} trips, as-shipped walk")]
+LUT_METRIC = ("lut_phase", "v_* of the split-sum LUT phase (kernel - its PBR_EXP_NOLUT build, static)")
 
 
 def report(res):
     k = res["kernel"]
-    doc = ["# k_deferred_shade<true, 257, false, NoViews>: instruction classes of the gfx950 ISA (static counts)", "", f"`{res['name']}`", "",
+    doc = ["# k_deferred_shade<true, 257, false, NoViews" + (", true" if FOLD_ARG[True] in res["name"] else "") + ">: instruction classes of the gfx950 ISA (static counts)", "", f"`{res['name']}`", "",
            f"whole kernel: {k['valu']} v_* ({k['packed']} packed, {k['trans']} transcendental, {k['moves']} moves), {k['ds']} ds_*, {k['global']} global_*; {res['vgprs']} VGPRs", "",
            "| metric | value |", "|---|---|"]
-    doc += [f"| {text} | {res[key]:g} |" for key, text in METRICS]
+    doc += [f"| {text} | {res[key]:g} |" for key, text in METRICS + [LUT_METRIC] if key in res]
     doc += ["", f"row body: {res['row_static']} v_* static, of them {sum(w['body']['valu'] for w in res['walks'])} in the walk loops and {res['exact_path']} on the exact-slice path", "",
             "light walks (one of them runs per pixel; a trip = one pair of lights):", "",
             "| loop | trips per body | v_* per trip | packed per trip | transcendental per trip | moves per body | ds_* per body |", "|---|---|---|---|---|---|---|"]
@@ -149,7 +159,7 @@ def report(res):
 
 def parse_metrics(md_text):
     """{metric key: value} of a report written by this tool"""
-    by_text = {text: key for key, text in METRICS}
+    by_text = {text: key for key, text in METRICS + [LUT_METRIC]}
     out = {}
     for m in re.finditer(r"^\| (.+?) \| ([-0-9.e+]+) \|$", md_text, re.M):
         if m.group(1) in by_text:
@@ -157,13 +167,13 @@ def parse_metrics(md_text):
     return out
 
 
-def phases(src=SRC):
+def phases(src=SRC, fold=False):
     variants = [("light walk (cluster index + every instantiation of the list walk + the sums' zeroing)", "PBR_EXP_NOLOOP"),
                 ("IBL specular: reflection vector, cube face, two trilinear levels from the footprint layout, their lerps", "PBR_EXP_NOENV"),
                 ("split-sum LUT fetch + bilinear", "PBR_EXP_NOLUT"), ("SH9 irradiance (EnvironmentDiffuse)", "PBR_EXP_NOSH"),
                 ("all of the IBL specular term (env + LUT)", "PBR_EXP_NOIBL")]
     with ThreadPoolExecutor(3) as ex:
-        cs = list(ex.map(lambda d: count(kernel(compile_isa(d, src))[1]), [()] + [(v[1],) for v in variants]))
+        cs = list(ex.map(lambda d: count(kernel(compile_isa(d, src), fold=fold)[1]), [()] + [(v[1],) for v in variants]))
     t = cs[0]
     doc = ["", "phases (static v_* of the whole kernel, every path):", "", "| phase removed (-D switch) | v_* removed | of them packed | transcendental | moves |", "|---|---|---|---|---|"]
     for (nm, d), c in zip(variants, cs[1:]):
@@ -240,9 +250,10 @@ def main(argv):
     if "--src" in argv:
         src = argv[argv.index("--src") + 1]
         args.remove(src)
-    doc = report(measure(src))
+    fold = "--fold" in argv
+    doc = report(measure(src, fold=fold, lut_phase=fold))
     if "--phases" in argv:
-        doc += phases(src)
+        doc += phases(src, fold)
     text = "\n".join(doc) + "\n"
     print(text)
     if args:
