@@ -23,7 +23,7 @@ import torch
 
 from direct12pbrrenderer_amd import _lib
 from direct12pbrrenderer_amd.api import PbrContext
-from direct12pbrrenderer_amd.structs import CLUSTER_DTYPE, LIGHT_DTYPE, NUM_CLUSTERS, bloom_chain_texels, cube_texels, env_padded_texels
+from direct12pbrrenderer_amd.structs import CLUSTER_DTYPE, LIGHT_DTYPE, NUM_CLUSTERS, ShadeTables, bloom_chain_texels, cube_texels, env_padded_texels
 
 ENV_MIPS = 5
 
@@ -108,6 +108,20 @@ class DryContext:
 
     def deferred_shade_folded(self, *a):
         self._n("deferred_shade_rects" if a[-1] is not None and len(a) == 15 else "deferred_shade")
+
+    # the shade tables (DeferredFrame's tabled path): the stand-ins count as the dispatches they replace
+    def alloc_shade_tables(self, w, h):
+        return self.zeros((4,), torch.int32), ShadeTables()
+
+    def clustered_tables(self, g, lights, n, clusters, tables):
+        tables.built, tables.num_lights = tables.built | 1, int(n)
+        self._n("clustered")
+
+    def shade_geometry_tables(self, tile, tables):
+        tables.built |= 2
+
+    def deferred_shade_tabled(self, *a):
+        self._n("deferred_shade_rects" if a[-1] is not None and len(a) == 16 else "deferred_shade")
 
     def skybox(self, *a):
         self._n("skybox")

@@ -6,7 +6,7 @@ symbol cannot be resolved this module raises — it never substitutes another im
 import ctypes as C
 import os
 
-from .structs import CubeF32, GBuffer, Global, HaloPeer, Texture2D, Tile, View
+from .structs import CubeF32, GBuffer, Global, HaloPeer, ShadeTables, Texture2D, Tile, View
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB", os.path.join(_HERE, "libpbr_hip.so"))   # override = experiments only
@@ -53,6 +53,13 @@ SIGNATURES = {
                                          _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32]),
     "pbr_deferred_shade_rects_folded": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
                                                _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, _vp, _u32]),
+    "pbr_shade_tables_bytes": (_sz, [_u32, _u32]),
+    "pbr_clustered_tables": (_int, [_vp, C.POINTER(Global), _vp, _int, _vp, C.POINTER(ShadeTables)]),
+    "pbr_shade_geometry_tables": (_int, [_vp, C.POINTER(Tile), C.POINTER(ShadeTables)]),
+    "pbr_deferred_shade_tabled": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
+                                         _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, C.POINTER(ShadeTables)]),
+    "pbr_deferred_shade_rects_tabled": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
+                                               _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, _vp, _u32, C.POINTER(ShadeTables)]),
     "pbr_skybox": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(CubeF32), _vp, _u32, _vp, _u32]),
     "pbr_gbuffer_encode": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "pbr_gbuffer_raster_scratch_bytes": (_sz, [_u32, _u32, _u32]),

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .structs import (Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
+from .structs import (ShadeTables, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
                       NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, texture2d_bytes)
 
@@ -260,6 +260,34 @@ class PbrContext:
         else:
             arr = self._rects(rects)
             self._check(self.lib.pbr_deferred_shade_rects_folded(*head, C.cast(arr, C.c_void_p), len(rects)))
+
+    def alloc_shade_tables(self, w, h):
+        """The shade tables of a w x h tile: (device tensor, ShadeTables descriptor) with neither half built.  The tensor is the memory the
+        descriptor points into: keep both."""
+        n = int(self.lib.pbr_shade_tables_bytes(int(w), int(h)))
+        buf = self.zeros((n // 4,), torch.int32)
+        return buf, ShadeTables(buf.data_ptr(), n, 0, 0, 0, Tile(0, 0, 0, 0, 0, 0))
+
+    def clustered_tables(self, g: Global, lights, n, clusters, tables: ShadeTables):
+        """clustered() that also writes the frame half of the shade tables (light planes, q_safe, staged cluster lists) in the same launch."""
+        self._check(self.lib.pbr_clustered_tables(self.h, C.byref(g), _ptr(lights), int(n), _ptr(clusters), C.byref(tables)))
+
+    def shade_geometry_tables(self, tile: Tile, tables: ShadeTables):
+        """The geometry half of the shade tables (column and row terms of the tile): once per target."""
+        self._check(self.lib.pbr_shade_geometry_tables(self.h, C.byref(tile), C.byref(tables)))
+
+    def deferred_shade_tabled(self, g: Global, tile: Tile, gb, pitch, lut_fold, lut_res, env, env_size, env_mips,
+                              clusters, lights, num_lights, hdr, hdr_pitch, tables: ShadeTables, rects=None):
+        """deferred_shade_folded whose blocks read their prologue from the shade tables (both halves built for this tile and light count)."""
+        s = GBuffer(gb["A"].data_ptr(), gb["B"].data_ptr(), gb["C"].data_ptr(), gb["depth"].data_ptr(),
+                    gb["stencil"].data_ptr(), pitch)
+        head = (self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut_fold), lut_res, _ptr(env), env_size, env_mips,
+                _ptr(clusters), _ptr(lights), int(num_lights), _ptr(hdr), hdr_pitch)
+        if rects is None:
+            self._check(self.lib.pbr_deferred_shade_tabled(*head, C.byref(tables)))
+        else:
+            arr = self._rects(rects)
+            self._check(self.lib.pbr_deferred_shade_rects_tabled(*head, C.cast(arr, C.c_void_p), len(rects), C.byref(tables)))
 
     def deferred_shade_f32(self, g: Global, tile: Tile, gb, pitch, lut, lut_res, env, env_size, env_mips,
                            clusters, lights, num_lights, hdr_f32, hdr_pitch):

@@ -77,22 +77,11 @@ struct ClusterView {
 struct ClusterViews { ClusterView v[PBR_MAX_VIEWS]; };
 static_assert(sizeof(ClusterViews) <= 4096 - 256, "k_cluster_cull<.., ClusterViews>: kernel arguments over 4 KiB");
 
-// grid 3072/4 x block 256 (4 waves, one cluster per wave).  BUILD: both dispatches of ClusteredPass::Execute in one
-// launch — the wave computes its cluster's bounds itself (every lane the same values) instead of reading them back.
-// VS = ClusterViews: view blockIdx.y of `vs` instead of (p_, lights_, n_, clusters_); NoViews (an empty argument): the single-view kernel.
-template <bool BUILD, class VS = NoViews>
-__global__ __launch_bounds__(256) void k_cluster_cull(ClusterParams p_, const pbr_light* __restrict__ lights_, int n_, VS vs,
-                                                        pbr_cluster* __restrict__ clusters_) {
-    constexpr bool MV = !std::is_same_v<VS, NoViews>;
-    const ClusterView* view = nullptr;
-    if constexpr (MV) view = &vs.v[blockIdx.y];
-    const ClusterParams& p = MV ? view->p : p_;
-    const pbr_light* __restrict__ lights = MV ? view->lights : lights_;
-    const int n = MV ? view->n : n_;
-    pbr_cluster* __restrict__ clusters = MV ? view->clusters : clusters_;
-    const int lane = threadIdx.x & 63;
-    const int ci = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (ci >= PBR_NUM_CLUSTERS) return;   // wave-uniform
+// One wave culls cluster ci.  TABLES: it also writes the cluster's list in the shade's staged format into `staged` (34 dwords: padded
+// count, 0, 32 entries of 4 * light index, 4 * n — the null light — from the count on), every dword of it, with plain vector stores.
+template <bool BUILD, bool TABLES>
+__device__ __forceinline__ void cull_cluster(const ClusterParams& p, const pbr_light* __restrict__ lights, int n, pbr_cluster* __restrict__ clusters,
+                                             int ci, int lane, uint32_t* __restrict__ staged) {
     pbr_cluster* c = clusters + ci;
     float mn[3], mx[3];
     int count = 0;
@@ -111,10 +100,73 @@ __global__ __launch_bounds__(256) void k_cluster_cull(ClusterParams p_, const pb
         if (i < n) hit = light_hits(p, lights[i], mn, mx);
         const unsigned long long mask = __ballot(hit);
         const int pos = count + __popcll(mask & ((1ull << lane) - 1ull));
-        if (hit && pos < PBR_MAX_LIGHTS_PER_CLUSTER) c->LightIndex[pos] = i;
+        if (hit && pos < PBR_MAX_LIGHTS_PER_CLUSTER) {
+            c->LightIndex[pos] = i;
+            if (TABLES) staged[2 + pos] = 4u * (uint32_t)i;
+        }
         count = min(count + __popcll(mask), PBR_MAX_LIGHTS_PER_CLUSTER);
     }
     if (lane == 0) c->NumLights = count;
+    if (TABLES) {
+        static_assert(PBR_MAX_LIGHTS_PER_CLUSTER == STAGED_LIST_DWORDS - 2, "staged list: one entry per list slot");
+        if (lane >= count && lane < PBR_MAX_LIGHTS_PER_CLUSTER) staged[2 + lane] = 4u * (uint32_t)n;
+        if (lane == 32) staged[0] = (uint32_t)staged_list_padded(count);
+        if (lane == 33) staged[1] = 0u;
+    }
+}
+
+// grid 3072/4 x block 256 (4 waves, one cluster per wave).  BUILD: both dispatches of ClusteredPass::Execute in one
+// launch — the wave computes its cluster's bounds itself (every lane the same values) instead of reading them back.
+// VS = ClusterViews: view blockIdx.y of `vs` instead of (p_, lights_, n_, clusters_); NoViews (an empty argument): the single-view kernel.
+template <bool BUILD, class VS = NoViews>
+__global__ __launch_bounds__(256) void k_cluster_cull(ClusterParams p_, const pbr_light* __restrict__ lights_, int n_, VS vs,
+                                                        pbr_cluster* __restrict__ clusters_) {
+    constexpr bool MV = !std::is_same_v<VS, NoViews>;
+    const ClusterView* view = nullptr;
+    if constexpr (MV) view = &vs.v[blockIdx.y];
+    const ClusterParams& p = MV ? view->p : p_;
+    const pbr_light* __restrict__ lights = MV ? view->lights : lights_;
+    const int n = MV ? view->n : n_;
+    pbr_cluster* __restrict__ clusters = MV ? view->clusters : clusters_;
+    const int lane = threadIdx.x & 63;
+    const int ci = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ci >= PBR_NUM_CLUSTERS) return;   // wave-uniform
+    cull_cluster<BUILD, false>(p, lights, n, clusters, ci, lane, nullptr);
+}
+
+// pbr_clustered_tables: k_cluster_cull<true> whose waves also write their cluster's staged list, and ONE more block (the grid's
+// last) that writes the frame half's header and light planes — a block of its own, because a cull wave leaves its light loop at 32 hits and
+// does not see every light.  The planes and the two q_safe bits are the expressions of k_deferred_shade's prologue.
+__global__ __launch_bounds__(256) void k_cluster_cull_tables(ClusterParams p, const pbr_light* __restrict__ lights, int n,
+                                                               pbr_cluster* __restrict__ clusters, uint32_t* __restrict__ tables) {
+    if (blockIdx.x < PBR_NUM_CLUSTERS / 4) {
+        const int ci = blockIdx.x * 4 + (threadIdx.x >> 6);
+        cull_cluster<true, true>(p, lights, n, clusters, ci, threadIdx.x & 63, tables + PBR_TABLES_LISTS + ci * STAGED_LIST_DWORDS);
+        return;
+    }
+    const int stride = shade_light_stride(n);
+    float* planes = reinterpret_cast<float*>(tables + PBR_TABLES_PLANES);
+    int my_safe = 1, my_same = 1;
+    const float att0 = n > 0 ? lights[0].C0 : 1.0f, att1 = n > 0 ? lights[0].C1 : 0.0f, att2 = n > 0 ? lights[0].C2 : 0.0f;
+    for (int i = threadIdx.x; i < stride; i += 256) {
+        float v[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (i < n) {
+            const pbr_light l = lights[i];
+            my_safe &= (l.C0 >= EPSILON_F) & (l.C1 >= 0.0f) & (l.C2 >= 0.0f);
+            my_same &= (l.C0 == att0) & (l.C1 == att1) & (l.C2 == att2);
+            v[0] = l.Position[0]; v[1] = l.Position[1]; v[2] = l.Position[2];
+            v[3] = l.Color[0] * l.Intensity; v[4] = l.Color[1] * l.Intensity; v[5] = l.Color[2] * l.Intensity;
+            v[6] = l.C0; v[7] = l.C1; v[8] = l.C2;
+        } else if (i == n) {   // the null light: pads odd lists; black, so its pair lane contributes exactly 0
+            v[0] = v[1] = v[2] = 1.0e15f;
+            v[6] = 1.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < 9; k++) planes[k * stride + i] = v[k];
+    }
+    for (uint32_t d = 9u * (uint32_t)stride + threadIdx.x; d < PBR_TABLES_LISTS - PBR_TABLES_PLANES; d += 256u) planes[d] = 0.0f;   // the image is deterministic
+    const int q_safe = (__syncthreads_and(my_safe) != 0 ? 1 : 0) | (__syncthreads_and(my_same) != 0 ? 2 : 0);
+    if (threadIdx.x < 4) tables[PBR_TABLES_HEADER + threadIdx.x] = threadIdx.x == 0 ? (uint32_t)q_safe : threadIdx.x == 1 ? (uint32_t)n : threadIdx.x == 2 ? (uint32_t)stride : 0u;
 }
 
 static ClusterParams make_params(const pbr_global* g) {
@@ -159,6 +211,21 @@ pbr_status pbr_clustered(pbr_ctx* ctx, const pbr_global* g, const pbr_light* lig
     PBR_CHECK(ctx, "pbr_clustered", cull_args_bad(g, true, lights, n));
     hipLaunchKernelGGL(k_cluster_cull<true>, dim3(PBR_NUM_CLUSTERS / 4), dim3(256), 0, ctx->stream, make_params(g), lights, n, NoViews{}, clusters);
     return launched(ctx, "k_cluster_cull<build>");
+}
+
+size_t pbr_shade_tables_bytes(uint32_t w, uint32_t h) { return ((size_t)PBR_TABLES_GEOM + 2u * (size_t)w + 2u * (size_t)h) * 4u; }
+
+pbr_status pbr_clustered_tables(pbr_ctx* ctx, const pbr_global* g, const pbr_light* lights, int n, pbr_cluster* clusters, pbr_shade_tables* tables) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, g && clusters && tables, "pbr_clustered_tables: null pointer");
+    PBR_CHECK(ctx, "pbr_clustered_tables", cull_args_bad(g, true, lights, n));
+    PBR_REQUIRE(ctx, tables->dev && ((uintptr_t)tables->dev & 15u) == 0 && tables->bytes >= (uint64_t)PBR_TABLES_GEOM * 4u,
+                "pbr_clustered_tables: the tables buffer must be 16-byte aligned and hold pbr_shade_tables_bytes()");
+    tables->built &= ~PBR_TABLES_BUILT_FRAME;
+    hipLaunchKernelGGL(k_cluster_cull_tables, dim3(PBR_NUM_CLUSTERS / 4 + 1), dim3(256), 0, ctx->stream, make_params(g), lights, n, clusters, (uint32_t*)tables->dev);
+    const pbr_status r = launched(ctx, "k_cluster_cull_tables");
+    if (r == PBR_OK) { tables->built |= PBR_TABLES_BUILT_FRAME; tables->num_lights = n; tables->list_pad = 2u * SHADE_WALK_TRIPS; }
+    return r;
 }
 
 pbr_status pbr_clustered_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n) {

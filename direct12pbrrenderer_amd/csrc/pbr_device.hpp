@@ -17,6 +17,21 @@ constexpr float TWO_PI_F = (float)(2.0 * 3.14159265359);
 
 typedef _Float16 h16;
 
+// SHADE_WALK_TRIPS: trips (pairs of lights) per pointer step of the shade's staged walk, defined HERE alone.  shade.hip pads the lists it
+// stages to 2 * SHADE_WALK_TRIPS entries and cluster.hip pads the lists it writes into the shade tables (34 dwords: padded count, 0, 32
+// entries) alike, so a variant build passes -DSHADE_WALK_TRIPS to both units; pbr_clustered_tables records the padding in the tables'
+// descriptor and the tabled shade refuses another.
+#ifndef SHADE_WALK_TRIPS
+#define SHADE_WALK_TRIPS 2
+#endif
+constexpr int STAGED_LIST_DWORDS = 34;
+__host__ __device__ inline int staged_list_padded(int cnt) {
+    const int up = (cnt + 2 * SHADE_WALK_TRIPS - 1) & ~(2 * SHADE_WALK_TRIPS - 1);
+    return up > 2 * SHADE_WALK_TRIPS ? up : 2 * SHADE_WALK_TRIPS;
+}
+// light stride of the shade's nine LDS planes: odd (conflict-free planes), by the light count
+__host__ __device__ inline int shade_light_stride(int n_lights) { return n_lights <= 256 ? 257 : PBR_MAX_SCENE_LIGHTS + 1; }
+
 struct V3 { float x, y, z; };
 __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
 __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }

@@ -133,10 +133,7 @@ constexpr int SHADE_ROWS = 8;          // most rows of 256 pixels one block walk
 constexpr int MAX_STAGED_TILES = 12;   // cluster (x,y) tiles whose 8 z-slices may be staged per block
 // staged list: count, pad, 32 u16 indices = 34 halfwords (68 B) per cluster
 constexpr int LIST_STRIDE = 34;         // dwords per staged cluster list: count, pad, 32 entries (8-byte aligned pairs)
-#ifndef SHADE_WALK_TRIPS
-#define SHADE_WALK_TRIPS 2
-#endif
-constexpr int WALK_TRIPS = SHADE_WALK_TRIPS;   // trips (pairs of lights) per pointer step and compare of the staged walk; lists are padded to 2 * WALK_TRIPS entries
+constexpr int WALK_TRIPS = SHADE_WALK_TRIPS;   // (defined in pbr_device.hpp: the cull pads the shade tables' lists with it too) trips (pairs of lights) per pointer step and compare of the staged walk; lists are padded to 2 * WALK_TRIPS entries
 static_assert(WALK_TRIPS == 2 || WALK_TRIPS == 4, "a staging thread converts four entries: the padded length must be a multiple of four that divides 32");
 
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -741,6 +738,111 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
 #endif
 }
 
+// ---- shade tables (pbr_hip.h: PBR_TABLES_*) ---------------------------------------------------------------------------------------
+// pbr_shade_geometry_tables: per column of the tile {ndc_x * 0.5f, cluster column}, per row {ndc_y * 0.5f, cluster row} — the float expressions of
+// k_deferred_shade's column and row terms (IEEE divide, floor, clamp), which are also those of its tile bounds.  One thread per entry.
+__global__ __launch_bounds__(256) void k_shade_geometry_tables(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t full_w, uint32_t full_h, float2* __restrict__ geom) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t < w) {
+        const float u = ((float)(x0 + t) + 0.5f) / (float)full_w;
+        const float ndc_x = 2.0f * u - 1.0f;
+        const int sx = clampi((int)floorf(u * (float)PBR_CLUSTER_X), 0, PBR_CLUSTER_X - 1);
+        geom[t] = make_float2(ndc_x * 0.5f, __int_as_float(sx));
+    } else if (t < w + h) {
+        const float v = ((float)(y0 + (t - w)) + 0.5f) / (float)full_h;
+        const float ndc_y = 1.0f - 2.0f * v;
+        const int sy = clampi((int)floorf((1.0f - v) * (float)PBR_CLUSTER_Y), 0, PBR_CLUSTER_Y - 1);
+        geom[t] = make_float2(ndc_y * 0.5f, __int_as_float(sy));
+    }
+}
+
+// k_deferred_shade<true, LSTRIDE, false, NoViews, true> with the prologue read from the shade tables: the light planes are a flat copy of the
+// frame half's image, a tile row of the block's cluster lists is one contiguous run of it (the LDS address of the planes is added to the
+// entries on the way), q_safe is the header's, the row and column terms and the block's tile bounds are look-ups in the geometry half.  One
+// barrier.  LDS layout, dynamic LDS size and the row loop are k_deferred_shade's; shade_pixel is called as it is.
+template <int LSTRIDE>
+__global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade_tabled(ShadeParams p, int n_lights, int max_clusters, ShadeRects rc, const uint32_t* __restrict__ tab) {
+    extern __shared__ float4 lds_raw[];
+    __shared__ uint32_t s_mip_off[16];
+    __shared__ float4 s_row[SHADE_ROWS];
+    const unsigned long long t_start = SHADE_NOW();
+    (void)t_start;
+    if (threadIdx.x < 16) s_mip_off[threadIdx.x] = p.env_mip_off[threadIdx.x];
+    float* llds = reinterpret_cast<float*>(lds_raw);
+    uint32_t* lists = reinterpret_cast<uint32_t*>(llds + ((LIGHT_PLANES * LSTRIDE + 1) & ~1));   // 8-byte aligned
+    {   // the planes: 16 bytes per thread and round, the odd dwords behind the last whole 16 by one thread each
+        constexpr int N4 = (LIGHT_PLANES * LSTRIDE) / 4, TAIL = (LIGHT_PLANES * LSTRIDE) & 3;
+        const uint4* src = reinterpret_cast<const uint4*>(tab + PBR_TABLES_PLANES);
+#pragma unroll 1
+        for (int i = threadIdx.x; i < N4; i += SHADE_BLOCK) reinterpret_cast<uint4*>(llds)[i] = src[i];
+        if (threadIdx.x < (uint32_t)TAIL) llds[4 * N4 + threadIdx.x] = __uint_as_float(tab[PBR_TABLES_PLANES + 4 * N4 + threadIdx.x]);
+    }
+    // block -> rectangle -> (column block, row block); wave-uniform scalar arithmetic (as k_deferred_shade)
+    uint32_t r = 0;
+    while (r + 1 < rc.n && blockIdx.x >= rc.first[r + 1]) r++;
+    const uint32_t lb = blockIdx.x - rc.first[r];
+    const uint32_t bx0 = rc.x0[r] + (lb % rc.cols[r]) * SHADE_BLOCK, x_end = rc.x0[r] + rc.w[r];
+    const uint32_t by = lb / rc.cols[r], nb_big = rc.nb_big[r], rows_big = rc.rows_big, rows_small = rc.rows_small;
+    const uint32_t y_begin = rc.y0[r] + (by < nb_big ? by * rows_big : nb_big * rows_big + (by - nb_big) * rows_small);
+    const uint32_t y_end = min(y_begin + (by < nb_big ? rows_big : rows_small), rc.y0[r] + rc.h[r]);
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_cf*)llds;
+    // the cluster tiles of the block's rectangle: the cluster column / row of its corners (monotone in the pixel coordinate); uniform addresses
+    const uint2* cols = reinterpret_cast<const uint2*>(tab + PBR_TABLES_GEOM);
+    const uint2* rows = cols + p.w;
+    const uint32_t bx1 = min(bx0 + SHADE_BLOCK, x_end) - 1;
+    const int tile_x0 = (int)cols[bx0].y, tile_x1 = (int)cols[bx1].y;
+    const int ty_a = (int)rows[y_begin].y, ty_b = (int)rows[y_end - 1].y;
+    const int tile_y0 = min(ty_a, ty_b), tile_y1 = max(ty_a, ty_b);
+    const int tiles_x = tile_x1 - tile_x0 + 1;
+    {
+        // Tile row j of the block = clusters (tile_y0 + j, tile_x0 .. tile_x1, 0 .. 7): tiles_x * 8 lists that follow one another in the image
+        // and in LDS.  16 bytes of a run per thread and round (a run starts 16-byte aligned in the image, 8-byte aligned in LDS); the four
+        // dwords begin at dword 2 * (2 q mod 17) of a list, and its dwords 0 and 1 (count, pad) are not addresses.
+        static_assert(LIST_STRIDE == STAGED_LIST_DWORDS && PBR_CLUSTER_Z * LIST_STRIDE % 4 == 0, "staged run");
+        const int run4 = tiles_x * (PBR_CLUSTER_Z * LIST_STRIDE / 4);
+        const int cap4 = max_clusters * LIST_STRIDE / 4;   // the host sized the LDS for the worst case: never past it
+#pragma unroll 1   // (unrolled and vectorised the two loops were 200 static v_* for a copy that runs one or two rounds)
+        for (int j = 0; j <= tile_y1 - tile_y0; j++) {
+            const uint4* src = reinterpret_cast<const uint4*>(tab + PBR_TABLES_LISTS + ((tile_y0 + j) * PBR_CLUSTER_X + tile_x0) * (PBR_CLUSTER_Z * LIST_STRIDE));
+            uint2* dst = reinterpret_cast<uint2*>(lists) + 2 * (j * run4);
+            const int n4 = min(run4, cap4 - j * run4);
+#pragma unroll 1
+            for (int q = threadIdx.x; q < n4; q += SHADE_BLOCK) {
+                const uint32_t m = (2u * (uint32_t)q) % 17u;
+                const uint32_t lo = m == 0u ? 0u : lds_base, hi = m == 16u ? 0u : lds_base;
+                const uint4 v = src[q];
+                dst[2 * q] = make_uint2(v.x + lo, v.y + lo);
+                dst[2 * q + 1] = make_uint2(v.z + hi, v.w + hi);
+            }
+        }
+    }
+    if (threadIdx.x < (uint32_t)SHADE_ROWS) {
+        const uint2 e = rows[min(y_begin + threadIdx.x, p.h - 1u)];
+        const float cvv_y = __uint_as_float(e.x) * p.near_height;
+        const uint32_t row_list = (uint32_t)(((int)e.y - tile_y0) * tiles_x * (PBR_CLUSTER_Z * LIST_STRIDE));
+        s_row[threadIdx.x] = make_float4(p.InvView[1] * cvv_y, p.InvView[4] * cvv_y, p.InvView[7] * cvv_y, __uint_as_float(row_list));
+    }
+    const int q_safe = (int)tab[PBR_TABLES_HEADER];
+    const uint32_t px = bx0 + threadIdx.x;
+    const uint2 ce = cols[min(px, p.w - 1u)];
+    const float cvv_x = __uint_as_float(ce.x) * p.near_width;
+    const uint32_t col_list = (uint32_t)(((int)ce.y - tile_x0) * (PBR_CLUSTER_Z * LIST_STRIDE));
+    __syncthreads();
+    SHADE_ISTAMP(blockIdx.x, 0, t_start);
+    SHADE_ISTAMP(blockIdx.x, 1, SHADE_NOW());
+    SHADE_ISTAMP(blockIdx.x, 3, ((unsigned long long)(y_end - y_begin) << 48) | blockIdx.x);
+#ifndef PBR_SHADE_TIMING
+    if (px >= x_end) return;
+    for (uint32_t py = y_begin; py < y_end; py++)
+        shade_pixel<true, LSTRIDE, false, true>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
+#else
+    if (px < x_end)
+        for (uint32_t py = y_begin; py < y_end; py++)
+            shade_pixel<true, LSTRIDE, false, true>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
+    SHADE_ISTAMP_MAX(blockIdx.x, 2, SHADE_NOW());
+#endif
+}
+
 extern "C" {
 
 pbr_status pbr_env_pad(pbr_ctx* ctx, const pbr_half* env, uint32_t size, uint32_t mips, pbr_half* out_padded) {
@@ -850,13 +952,14 @@ static ShadeRects shade_schedule(const pbr_ctx* ctx, const uint32_t (*rects)[4],
 // One launch of the schedule rc over n_views views (grid: rc's blocks x n_views) of a p.full_w x p.full_h frame whose views hold at most
 // max_lights lights.  VS = NoViews: p is the one view's, num_lights its light count; VS = ShadeViews: every view's own fields come from vs.
 template <bool F32OUT, bool LUTFOLD, class VS>
-static pbr_status shade_dispatch(pbr_ctx* ctx, const ShadeParams& p, int num_lights, int max_lights, const ShadeRects& rc, uint32_t n_views, const VS& vs) {
+static pbr_status shade_dispatch(pbr_ctx* ctx, const ShadeParams& p, int num_lights, int max_lights, const ShadeRects& rc, uint32_t n_views, const VS& vs,
+                                 const uint32_t* tables = nullptr) {
     // A block covers 256 x 8 pixels.  It can stage its cluster lists when that rectangle spans at most
     // MAX_STAGED_TILES cluster tiles: a tile is full_w/24 x full_h/16 pixels, +1 per axis for straddling.
     // The staged-list decision depends on the frame size alone; the light stride of a batch is its largest view's (a layout, not a result).
     const uint32_t span_x = (uint32_t)((uint64_t)(SHADE_BLOCK - 1) * PBR_CLUSTER_X / p.full_w) + 2;
     const uint32_t span_y = (uint32_t)((uint64_t)(SHADE_ROWS - 1) * PBR_CLUSTER_Y / p.full_h) + 2;
-    const int lstride = max_lights <= 256 ? 257 : PBR_MAX_SCENE_LIGHTS + 1;   // odd strides: no ds_read2 merging of two planes of one light, conflict-free planes
+    const int lstride = shade_light_stride(max_lights);   // odd strides: no ds_read2 merging of two planes of one light, conflict-free planes
     const size_t plane_bytes = (size_t)((LIGHT_PLANES * lstride + 1) & ~1) * sizeof(float);
     // staged lists must also fit the 64 KiB a block may ask for (1 024 lights: 36 KiB of planes leave room for 8 tiles)
     const bool staged = span_x * span_y <= (uint32_t)MAX_STAGED_TILES &&   // (no lights at all: every list is one null pair)
@@ -864,6 +967,13 @@ static pbr_status shade_dispatch(pbr_ctx* ctx, const ShadeParams& p, int num_lig
     const int max_clusters = staged ? (int)(span_x * span_y) * PBR_CLUSTER_Z : 0;
     const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t);
     const dim3 grid(rc.first[rc.n], n_views), blk(SHADE_BLOCK);
+    if constexpr (std::is_same_v<VS, NoViews> && LUTFOLD && !F32OUT) {
+        if (tables && staged) {   // the prologue from the shade tables (not staged: the kernel below reads lights and clusters itself)
+            if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade_tabled<257>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, tables);
+            else hipLaunchKernelGGL((k_deferred_shade_tabled<PBR_MAX_SCENE_LIGHTS + 1>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, tables);
+            return launched(ctx, "k_deferred_shade_tabled");
+        }
+    }
     if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
     else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
     else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, vs);
@@ -878,7 +988,7 @@ static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile
                                const pbr_half* env, uint32_t env_size, uint32_t env_mips,
                                const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
                                pbr_half* hdr, float* hdr_f32, uint32_t hdr_pitch,
-                               const uint32_t (*rects)[4] = nullptr, uint32_t n_rects = 0) {
+                               const uint32_t (*rects)[4] = nullptr, uint32_t n_rects = 0, const pbr_shade_tables* tables = nullptr, bool tabled = false) {
     if (!ctx) return PBR_ERR_INVALID;
     const char* who = "pbr_deferred_shade";
     PBR_REQUIRE(ctx, g && tile && gb, "pbr_deferred_shade: null pointer");
@@ -893,12 +1003,20 @@ static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile
         const uint32_t* q = rects[r];
         PBR_REQUIRE(ctx, q[2] >= 1 && q[3] >= 1 && q[0] + q[2] <= tile->w && q[1] + q[3] <= tile->h, "pbr_deferred_shade: rectangle outside the tile");
     }
+    if (tabled) {   // stale or half-built tables are refused here, on the host: the descriptor names what each half was built for
+        PBR_REQUIRE(ctx, tables && tables->dev, "pbr_deferred_shade_tabled: null tables");
+        PBR_REQUIRE(ctx, (tables->built & PBR_TABLES_BUILT_FRAME) && (tables->built & PBR_TABLES_BUILT_GEOMETRY), "pbr_deferred_shade_tabled: only one half of the tables is built");
+        PBR_REQUIRE(ctx, tables->num_lights == num_lights, "pbr_deferred_shade_tabled: the tables were built for another light count");
+        PBR_REQUIRE(ctx, memcmp(&tables->tile, tile, sizeof(pbr_tile)) == 0, "pbr_deferred_shade_tabled: the tables were built for another tile");
+        PBR_REQUIRE(ctx, tables->list_pad == 2u * WALK_TRIPS, "pbr_deferred_shade_tabled: the cull padded the lists for another walk (SHADE_WALK_TRIPS differs between cluster.hip and shade.hip)");
+        PBR_REQUIRE(ctx, ((uintptr_t)tables->dev & 15u) == 0 && tables->bytes >= pbr_shade_tables_bytes(tile->w, tile->h), "pbr_deferred_shade_tabled: tables buffer misaligned or too small");
+    }
     ShadeParams p = shade_params(g, LUTFOLD ? nullptr : (const pbr_half*)lut, lut_res, env, env_size, env_mips);
     if (LUTFOLD) p.lut_fold = (const float*)lut;
     p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h; p.full_w = tile->full_w; p.full_h = tile->full_h;
     p.A = gb->A; p.B = gb->B; p.C = gb->C; p.depth = gb->depth; p.stencil = gb->stencil; p.pitch = gb->pitch;
     p.clusters = clusters; p.lights = lights; p.hdr = hdr; p.hdr_pitch = hdr_pitch; p.hdr_f32 = hdr_f32;
-    return shade_dispatch<F32OUT, LUTFOLD>(ctx, p, num_lights, num_lights, shade_schedule(ctx, rects, n_rects, 1), 1, NoViews{});
+    return shade_dispatch<F32OUT, LUTFOLD>(ctx, p, num_lights, num_lights, shade_schedule(ctx, rects, n_rects, 1), 1, NoViews{}, tabled ? (const uint32_t*)tables->dev : nullptr);
 }
 
 extern "C" {
@@ -949,6 +1067,40 @@ pbr_status pbr_deferred_shade_rects_folded(pbr_ctx* ctx, const pbr_global* g, co
                                            pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects) {
     if (ctx && !rects) return pbr::fail(ctx, PBR_ERR_INVALID, "pbr_deferred_shade_rects_folded: null rectangle list");
     return shade_launch<false, true>(ctx, g, tile, gb, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch, rects, n_rects);
+}
+
+// The geometry half of the shade tables (pbr_hip.h), once per target
+pbr_status pbr_shade_geometry_tables(pbr_ctx* ctx, const pbr_tile* tile, pbr_shade_tables* tables) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, tile && tables, "pbr_shade_geometry_tables: null pointer");
+    PBR_REQUIRE(ctx, tile->w >= 1 && tile->h >= 1 && tile->w <= 65535 && tile->h <= 65535, "pbr_shade_geometry_tables: bad tile size");
+    PBR_REQUIRE(ctx, tile->x0 + tile->w <= tile->full_w && tile->y0 + tile->h <= tile->full_h, "pbr_shade_geometry_tables: tile outside frame");
+    PBR_REQUIRE(ctx, tables->dev && ((uintptr_t)tables->dev & 15u) == 0 && tables->bytes >= pbr_shade_tables_bytes(tile->w, tile->h),
+                "pbr_shade_geometry_tables: the tables buffer must be 16-byte aligned and hold pbr_shade_tables_bytes(w, h)");
+    tables->built &= ~PBR_TABLES_BUILT_GEOMETRY;
+    hipLaunchKernelGGL(k_shade_geometry_tables, dim3((tile->w + tile->h + 255) / 256), dim3(256), 0, ctx->stream, tile->x0, tile->y0, tile->w, tile->h,
+                       tile->full_w, tile->full_h, reinterpret_cast<float2*>((uint32_t*)tables->dev + PBR_TABLES_GEOM));
+    const pbr_status r = launched(ctx, "k_shade_geometry_tables");
+    if (r == PBR_OK) { tables->built |= PBR_TABLES_BUILT_GEOMETRY; tables->tile = *tile; }
+    return r;
+}
+
+// pbr_deferred_shade_folded / _rects_folded with the block prologue read from the shade tables: the same pixels to the bit
+pbr_status pbr_deferred_shade_tabled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
+                                     const float* lut_fold, uint32_t lut_res,
+                                     const pbr_half* env, uint32_t env_size, uint32_t env_mips,
+                                     const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
+                                     pbr_half* hdr, uint32_t hdr_pitch, const pbr_shade_tables* tables) {
+    return shade_launch<false, true>(ctx, g, tile, gb, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch, nullptr, 0, tables, true);
+}
+
+pbr_status pbr_deferred_shade_rects_tabled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
+                                           const float* lut_fold, uint32_t lut_res,
+                                           const pbr_half* env, uint32_t env_size, uint32_t env_mips,
+                                           const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
+                                           pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects, const pbr_shade_tables* tables) {
+    if (ctx && !rects) return pbr::fail(ctx, PBR_ERR_INVALID, "pbr_deferred_shade_rects_tabled: null rectangle list");
+    return shade_launch<false, true>(ctx, g, tile, gb, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch, rects, n_rects, tables, true);
 }
 
 // Parity probe: the same kernel body, storing float4 instead of rounding to the R16G16B16A16_FLOAT target — what the

@@ -288,11 +288,13 @@ void HipCommandList::Dispatch(ShadingState* s, uint32 gx, uint32 gy, uint32 gz) 
         mPaddedEnv.erase(out);   // the padded copy the shade samples is stale now
     } else if (f == "clustered_compute.hlsl") {
         ExpectGroups(f, gx, gy, gz, 1, 1, 1);
+        StaleShadeTables(s->Buffer("Clusters"));
         Check(pbr_cluster_build(mCtx, &mGlobal, (pbr_cluster*)s->Buffer("Clusters")->DevicePtr()), "pbr_cluster_build");
     } else if (f == "clustered_culling.hlsl") {
         ExpectGroups(f, gx, gy, gz, 1, 1, 1);
         const auto& c = s->Constants<ClusteredShaderConstant>();
         mNumLights = c.NumLight;
+        StaleShadeTables(s->Buffer("Clusters"));
         Check(pbr_cluster_cull(mCtx, &mGlobal, (const pbr_light*)s->Buffer("PointLights")->DevicePtr(), c.NumLight,
                                (pbr_cluster*)s->Buffer("Clusters")->DevicePtr()), "pbr_cluster_cull");
     } else if (f == "bloom_prefilter.hlsl") {
@@ -395,10 +397,24 @@ void HipCommandList::DrawScreen(ShadingState* s) {
         }
         // stencil ref 0, compare LESS: shade where 0 < stencil (DeferredPipeline.h:176-181, .cpp:203)
         if (mStencilRef != 0) throw HipException("deferred_shading: only stencil ref 0 is supported");
-        Check(pbr_deferred_shade_folded(mCtx, &mGlobal, &tile, &gb, (const float*)folded->DevicePtr(), lut->Width(),
-                                        (const pbr_half*)padded->DevicePtr(), env->Size(), env->MipLevels(),
-                                        (const pbr_cluster*)s->Buffer("Clusters")->DevicePtr(), (const pbr_light*)s->Buffer("PointLights")->DevicePtr(),
-                                        mNumLights, (pbr_half*)mRenderTarget->DevicePtr(), w), "pbr_deferred_shade_folded");
+        // ... and its block prologue from the shade tables, when the Clustered pass wrote their frame half for these clusters and lights
+        // (the geometry half: once per tile)
+        auto tables = mShadeTables.find(s->Buffer("Clusters"));
+        if (tables != mShadeTables.end() && (tables->second.desc.built & PBR_TABLES_BUILT_FRAME) && tables->second.desc.num_lights == mNumLights &&
+            tables->second.lights == s->Buffer("PointLights")) {
+            pbr_shade_tables& d = tables->second.desc;
+            if (!(d.built & PBR_TABLES_BUILT_GEOMETRY) || memcmp(&d.tile, &tile, sizeof(tile)) != 0)
+                Check(pbr_shade_geometry_tables(mCtx, &tile, &d), "pbr_shade_geometry_tables");
+            Check(pbr_deferred_shade_tabled(mCtx, &mGlobal, &tile, &gb, (const float*)folded->DevicePtr(), lut->Width(),
+                                            (const pbr_half*)padded->DevicePtr(), env->Size(), env->MipLevels(),
+                                            (const pbr_cluster*)s->Buffer("Clusters")->DevicePtr(), (const pbr_light*)s->Buffer("PointLights")->DevicePtr(),
+                                            mNumLights, (pbr_half*)mRenderTarget->DevicePtr(), w, &d), "pbr_deferred_shade_tabled");
+        } else {
+            Check(pbr_deferred_shade_folded(mCtx, &mGlobal, &tile, &gb, (const float*)folded->DevicePtr(), lut->Width(),
+                                            (const pbr_half*)padded->DevicePtr(), env->Size(), env->MipLevels(),
+                                            (const pbr_cluster*)s->Buffer("Clusters")->DevicePtr(), (const pbr_light*)s->Buffer("PointLights")->DevicePtr(),
+                                            mNumLights, (pbr_half*)mRenderTarget->DevicePtr(), w), "pbr_deferred_shade_folded");
+        }
     } else if (f == "hdr_tone_mapping.hlsl") {
         Mip in = MipOf(s->Texture("LuminanceTexture"));
         // multi-GPU: only the interior rectangle is tone-mapped (the apron belongs to the neighbours)
@@ -426,7 +442,19 @@ void HipCommandList::Clustered(DeviceStructuredBuffer* clusters, DeviceStructure
     mDispatchCount++;
     FlushPendingBloom();
     mNumLights = num_lights;
-    Check(pbr_clustered(mCtx, &mGlobal, (const pbr_light*)point_lights->DevicePtr(), num_lights, (pbr_cluster*)clusters->DevicePtr()), "pbr_clustered");
+    // the same launch also writes the frame half of the shade tables that go with this cluster buffer (sized for any tile: 1.5 MB)
+    ShadeTables& t = mShadeTables[clusters];
+    if (!t.buf) {
+        t.buf = std::make_unique<DeviceStructuredBuffer>((uint32)pbr_shade_tables_bytes(65535, 65535), 16);
+        t.desc = pbr_shade_tables{t.buf->DevicePtr(), pbr_shade_tables_bytes(65535, 65535), 0, 0, 0, {}};
+    }
+    t.lights = point_lights;
+    Check(pbr_clustered_tables(mCtx, &mGlobal, (const pbr_light*)point_lights->DevicePtr(), num_lights, (pbr_cluster*)clusters->DevicePtr(), &t.desc), "pbr_clustered_tables");
+}
+
+void HipCommandList::StaleShadeTables(const DeviceStructuredBuffer* clusters) {
+    auto t = mShadeTables.find(clusters);
+    if (t != mShadeTables.end()) t->second.desc.built &= ~PBR_TABLES_BUILT_FRAME;
 }
 
 void HipCommandList::Bloom(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain, DeviceTexture2D* temp, float threshold, float knee) {

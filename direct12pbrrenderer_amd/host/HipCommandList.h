@@ -172,6 +172,18 @@ private:
     std::map<const DeviceTexture2DArray*, std::unique_ptr<DeviceStructuredBuffer>> mPaddedEnv;
     // x-folded tables of split-sum LUTs (pbr_lut_fold_x), keyed by the LUT texture; rebuilt after precompute_brdf.hlsl rewrites it
     std::map<const DeviceTexture2D*, std::unique_ptr<DeviceStructuredBuffer>> mFoldedLut;
+    // shade tables (pbr_clustered_tables / pbr_shade_geometry_tables), keyed by the cluster buffer whose lists their frame half restates;
+    // a dispatch that rewrites the clusters one by one (clustered_compute / clustered_culling) marks that half stale.  Like mPaddedEnv:
+    // an entry (1.5 MB, sized for any tile) lives as long as the command list, keyed by the buffer's address; and only this class's own
+    // dispatches are tracked — a host upload or copy into the cluster or light buffer between Clustered() and the shade leaves the tabled
+    // shade on the lights and lists of the last Clustered() (the frame graph uploads lights before the Clustered pass)
+    struct ShadeTables {
+        std::unique_ptr<DeviceStructuredBuffer> buf;
+        pbr_shade_tables desc{};
+        const DeviceStructuredBuffer* lights = nullptr;
+    };
+    std::map<const DeviceStructuredBuffer*, ShadeTables> mShadeTables;
+    void StaleShadeTables(const DeviceStructuredBuffer* clusters);
 };
 
 // RAII twin of the reference's PIXScope(cmd, name) macro (DeferredPipeline.cpp:8)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .api import PbrContext
-from .structs import (DRAW_MAPS_DTYPE, ENV_MIPS, HISTOGRAM_BINS, MAX_VIEWS, NO_MAP, GBuffer, Global, Tile, View)
+from .structs import (DRAW_MAPS_DTYPE, ENV_MIPS, HISTOGRAM_BINS, MAX_VIEWS, NO_MAP, TABLES_BUILT_FRAME, TABLES_BUILT_GEOMETRY, GBuffer, Global, Tile, View)
 
 # bloom's cumulative support is ~220 full-res pixels (3 down + 3 up levels of a radius-4 kernel on
 # a 2x pyramid); 256 also keeps every mip of the extended tile on the full frame's texel grid
@@ -297,6 +297,11 @@ class DeferredFrame:
         self.gb = None
         self.mesh = None
         self.tile = Tile(spec.sx0, spec.sy0, spec.sw, spec.sh, spec.full_w, spec.full_h)
+        # the shade tables: the geometry half once per spec, the frame half by every clustered(); the folded shade reads its block
+        # prologue from them (tabled=False: the folded shade derives it per block, the same bits)
+        self.tabled = True
+        self.tables_buf, self.tables = ctx.alloc_shade_tables(spec.sw, spec.sh)
+        ctx.shade_geometry_tables(self.tile, self.tables)
         self.halo_transport = halo_transport
         if spec.halo:
             assert all_specs is not None and halo_transport is not None, "halo mode needs every rank's TileSpec and a transport"
@@ -409,7 +414,10 @@ class DeferredFrame:
         return self.hdr.data_ptr() + 8 * (s.siy * s.sw + s.six)
 
     def clustered(self):
-        self.ctx.clustered(self.g, self.lights, self.n_lights, self.clusters)
+        if self.tabled:
+            self.ctx.clustered_tables(self.g, self.lights, self.n_lights, self.clusters, self.tables)
+        else:
+            self.ctx.clustered(self.g, self.lights, self.n_lights, self.clusters)
 
     def skybox(self):
         s = self.spec
@@ -423,7 +431,12 @@ class DeferredFrame:
 
     def _shade(self, rects):
         s = self.spec
-        if self._lut_folded == (self.lut.data_ptr(), self.lut_res):
+        folded = self._lut_folded == (self.lut.data_ptr(), self.lut_res)
+        # (a shade before the frame's first clustered(), or after its light set was replaced: the folded shade, which derives its prologue)
+        if folded and self.tabled and self.tables.built == TABLES_BUILT_FRAME | TABLES_BUILT_GEOMETRY and self.tables.num_lights == self.n_lights:
+            self.ctx.deferred_shade_tabled(self.g, self.tile, self.gb, s.sw, self.lut_fold, self.lut_res, self.env, self.env_size,
+                                           self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw, self.tables, rects)
+        elif folded:
             self.ctx.deferred_shade_folded(self.g, self.tile, self.gb, s.sw, self.lut_fold, self.lut_res, self.env, self.env_size,
                                            self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw, rects)
         elif rects is None:

@@ -54,6 +54,16 @@ class Tile(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("x0", "y0", "w", "h", "full_w", "full_h")]
 
 
+class ShadeTables(C.Structure):
+    """pbr_shade_tables: the device buffer of the shade tables and the HOST descriptor of what its two halves were built for."""
+    _fields_ = [("dev", C.c_void_p), ("bytes", C.c_uint64), ("built", C.c_uint32), ("num_lights", C.c_int32), ("list_pad", C.c_uint32), ("tile", Tile)]
+
+
+# dword offsets into the shade tables' buffer (include/pbr_hip.h: PBR_TABLES_*)
+TABLES_HEADER, TABLES_PLANES, TABLES_LISTS, TABLES_GEOM = 0, 4, 9232, 113680
+TABLES_BUILT_FRAME, TABLES_BUILT_GEOMETRY = 1, 2
+
+
 class GBuffer(C.Structure):
     """G-buffer planes (gbuffer.hlsl:10-26,144-146; formats DeferredPipeline.h:107-110)."""
     _fields_ = [

@@ -332,6 +332,61 @@ pbr_status pbr_deferred_shade_rects_folded(pbr_ctx* ctx, const pbr_global* g, co
                                            const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
                                            pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects);
 
+/* ---- shade tables: what every block of the shade would otherwise derive again in its prologue ------------------------------
+ * One device buffer of pbr_shade_tables_bytes(w, h) bytes (16-byte aligned) in two halves, and a HOST descriptor that names what
+ * the halves were built for.  Dword offsets into the buffer:
+ *   PBR_TABLES_HEADER  4 dwords: {q_safe, num_lights, light stride, 0}.  q_safe bit 0: every light has C0 >= 1e-6, C1 >= 0, C2 >= 0;
+ *                      bit 1: every light has light 0's attenuation polynomial.  Stride: 257 up to 256 lights, else 1025.
+ *   PBR_TABLES_PLANES  9 planes of `stride` floats (position xyz, Color * Intensity rgb, C0 C1 C2); the null light
+ *                      {1e15, 1e15, 1e15, 0, 0, 0, 1, 0, 0} at index num_lights, zeros behind it.
+ *   PBR_TABLES_LISTS   PBR_NUM_CLUSTERS lists of 34 dwords in the pbr_cluster table's order: padded count, 0, 32 entries.  An entry is
+ *                      4 * light index; entries from the cluster's count on are 4 * num_lights (the null light).  The padded count is
+ *                      the count rounded up to a multiple of list_pad (four as shipped: one step of the shade's walk), at least list_pad.
+ *   PBR_TABLES_GEOM    w columns {ndc_x * 0.5f, cluster column (int)} then h rows {ndc_y * 0.5f, cluster row (int)} of the tile, from
+ *                      the float expressions of the shade itself (IEEE divide, floor, clamp).
+ * The frame half (header, planes, lists) is written by pbr_clustered_tables, the geometry half by pbr_shade_geometry_tables. */
+#define PBR_TABLES_HEADER 0u
+#define PBR_TABLES_PLANES 4u
+#define PBR_TABLES_LISTS  9232u     /* 4 + 9 * 1025 rounded up to four dwords */
+#define PBR_TABLES_GEOM   113680u   /* + 3072 * 34 */
+#define PBR_TABLES_BUILT_FRAME 1u
+#define PBR_TABLES_BUILT_GEOMETRY 2u
+typedef struct pbr_shade_tables {
+    void* dev;           /* the device buffer */
+    uint64_t bytes;      /* its size */
+    uint32_t built;      /* PBR_TABLES_BUILT_* of the halves built so far (0 before the first builder ran) */
+    int32_t num_lights;  /* light count of the frame half */
+    uint32_t list_pad;   /* entries the frame half's list counts are padded to (the shade refuses tables padded for another walk) */
+    pbr_tile tile;       /* tile of the geometry half */
+} pbr_shade_tables;
+size_t pbr_shade_tables_bytes(uint32_t w, uint32_t h);
+
+/* pbr_clustered that also writes the frame half of `tables` (same launch: the wave that culls a cluster writes its staged list,
+ * one more block writes the light planes and the header) and records num_lights in the descriptor.  clusters: as pbr_clustered. */
+pbr_status pbr_clustered_tables(pbr_ctx* ctx, const pbr_global* g, const pbr_light* lights, int num_lights,
+                                pbr_cluster* clusters, pbr_shade_tables* tables);
+
+/* The geometry half of `tables` for `tile` (one-shot per target, like pbr_lut_fold_x per LUT); records the tile in the descriptor. */
+pbr_status pbr_shade_geometry_tables(pbr_ctx* ctx, const pbr_tile* tile, pbr_shade_tables* tables);
+
+/* pbr_deferred_shade_folded / _rects_folded whose blocks copy their light planes, cluster lists, row and column terms from `tables`
+ * instead of deriving them: the same HDR target bit for bit.  PBR_ERR_INVALID unless both halves are built, for this tile and this
+ * num_lights.  `lights` and `clusters` must be the ones pbr_clustered_tables was given; targets too small to stage cluster lists
+ * per block run pbr_deferred_shade_folded's kernel and read them directly. */
+pbr_status pbr_deferred_shade_tabled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                     const pbr_gbuffer* gb,
+                                     const float* lut_fold, uint32_t lut_res,
+                                     const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
+                                     const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
+                                     pbr_half* hdr, uint32_t hdr_pitch, const pbr_shade_tables* tables);
+pbr_status pbr_deferred_shade_rects_tabled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                           const pbr_gbuffer* gb,
+                                           const float* lut_fold, uint32_t lut_res,
+                                           const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
+                                           const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
+                                           pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects,
+                                           const pbr_shade_tables* tables);
+
 /* Parity probe (not a product path): the same shade, storing the fp32 colour (float4 per pixel, alpha 1, pitch
  * hdr_pitch pixels, 16-byte aligned) instead of rounding it to the half4 target — the buffer the <= 1e-4 relative
  * L-inf parity bound is stated on. */

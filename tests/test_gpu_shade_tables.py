@@ -1,0 +1,239 @@
+"""The shade that reads its block prologue from the shade tables (pbr_clustered_tables + pbr_shade_geometry_tables ->
+pbr_deferred_shade_tabled / _rects_tabled) writes the HDR target of pbr_deferred_shade_folded / _rects_folded BIT FOR BIT (compared as
+int16, on untouched prefilled targets), both given the same inputs; and the tables themselves are, bit for bit, a numpy restatement of
+what the prologue derives: the light planes of the light array, the staged lists of the read-back cluster table, the column and row
+terms of the float32 expressions.
+Shapes (those of test_gpu_shade_lut_fold.py): a 1536 x 64 frame (staged lists); a 600 x 40 tile of a 4K frame at (1300, 1000) — partial
+last column block, long and one-row blocks, blocks straddling cluster tiles — whole and as two rectangles; a 256 x 64 frame (global
+lists: the tabled entry falls back to the folded kernel); light counts on both strides of the light table and over the 32-entry cap;
+light sets that switch either q_safe bit off."""
+import numpy as np
+import pytest
+import torch
+
+import common
+from direct12pbrrenderer_amd import scene, synth
+from direct12pbrrenderer_amd.api import PbrError
+from direct12pbrrenderer_amd.pipeline import DeferredFrame, TileSpec
+from direct12pbrrenderer_amd.structs import (CLUSTER_DTYPE, NUM_CLUSTERS, TABLES_GEOM, TABLES_HEADER, TABLES_LISTS, TABLES_PLANES, Tile)
+
+pytestmark = pytest.mark.gpu
+
+ES, EM = common.ENV_SIZE, common.ENV_MIPS
+FRAME = (0, 0, 1536, 64, 1536, 64)             # x0, y0, w, h, full_w, full_h
+TILE_4K = (1300, 1000, 600, 40, 3840, 2160)
+SMALL = (0, 0, 256, 64, 256, 64)
+LR = 32
+PREFILL = np.float16(3.0).view(np.int16)
+
+
+def dev_half(ctx, arr):
+    return ctx.upload(np.ascontiguousarray(arr, dtype=np.float16).view(np.uint16)).view(torch.float16)
+
+
+def light_set(sh, full, n, kind="plain"):
+    lights = common.shade_scene(8, 8, n, sh, full=full)[2].copy()
+    if kind == "two_presets":      # q_safe bit 1 off: two attenuation polynomials in the scene
+        lights["C1"][1::2] += np.float32(0.25)
+    elif kind == "tiny_c0":        # q_safe bit 0 off: one light whose attenuation floor can bind
+        lights["C0"][n // 2] = np.float32(1e-7)
+    return lights
+
+
+@pytest.fixture(scope="module")
+def world(ctx, ibl):
+    sky, env, lut, sh = ibl
+    w = dict(sh=sh, env_plain=dev_half(ctx, env), scene={})
+    w["denv"] = ctx.env_pad(w["env_plain"], ES, EM)
+    w["lut"] = ctx.brdf_lut(LR)
+    w["fold"] = ctx.lut_fold_x(w["lut"], LR)
+    for shape in (FRAME, TILE_4K, SMALL):
+        x0, y0, tw, th, fw, fh = shape
+        cam = scene.Camera.reference_default(fw, fh)
+        g = scene.make_global(cam, fw, fh, sh_pack=sh)
+        gb = synth.gbuffer_tile(x0, y0, tw, th, fw, fh, rough_min=0, coverage_mask=(shape != FRAME))
+        w["scene"][shape] = (cam, g, {k: ctx.upload(v) for k, v in gb.items()}, gb["stencil"] > 0)
+    ctx.sync()
+    return w
+
+
+def culled(ctx, w, shape, n, kind="plain"):
+    """(host lights, device lights or None, device cluster table, tables buffer, tables descriptor) of a light set culled for the shape's
+    camera by pbr_clustered_tables, with the geometry half built for the shape: made once per (shape, n, kind)"""
+    key = ("culled", shape, n, kind)
+    if key not in w:
+        g = w["scene"][shape][1]
+        lights = light_set(w["sh"], shape[4:], n, kind)
+        dl = ctx.upload(lights) if n else None
+        cl = ctx.alloc_clusters()
+        buf, tables = ctx.alloc_shade_tables(shape[2], shape[3])
+        ctx.shade_geometry_tables(Tile(*shape), tables)
+        ctx.clustered_tables(g, dl, n, cl, tables)
+        w[key] = (lights, dl, cl, buf, tables)
+    return w[key]
+
+
+def both(ctx, w, shape, n, kind="plain", rects=None):
+    """(folded, tabled) HDR targets as int16, and the mask of shaded pixels"""
+    x0, y0, tw, th, fw, fh = shape
+    cam, g, gbd, on = w["scene"][shape]
+    lights, dl, cl, buf, tables = culled(ctx, w, shape, n, kind)
+    tile = Tile(*shape)
+    out = []
+    for tabled in (False, True):
+        hdr = torch.full((th, tw, 4), 3.0, dtype=torch.float16, device=ctx.torch_device)
+        head = (g, tile, gbd, tw, w["fold"], LR, w["denv"], ES, EM, cl, dl, n, hdr, tw)
+        if tabled:
+            ctx.deferred_shade_tabled(*head, tables, rects)
+        else:
+            ctx.deferred_shade_folded(*head, rects)
+        out.append(hdr.view(torch.int16).cpu().numpy())
+    return out[0], out[1], on
+
+
+def test_cull_with_tables_writes_the_cluster_table_of_the_plain_cull(ctx, world):
+    g = world["scene"][TILE_4K][1]
+    for n in (0, 300):
+        lights, dl, cl, buf, tables = culled(ctx, world, TILE_4K, n)
+        ref = ctx.alloc_clusters()
+        ctx.clustered(g, dl, n, ref)
+        a = np.frombuffer(cl.cpu().numpy().tobytes(), dtype=CLUSTER_DTYPE)
+        b = np.frombuffer(ref.cpu().numpy().tobytes(), dtype=CLUSTER_DTYPE)
+        assert np.array_equal(a["NumLights"], b["NumLights"]) and a["MinBound"].tobytes() == b["MinBound"].tobytes() and a["MaxBound"].tobytes() == b["MaxBound"].tobytes()
+        for c in np.flatnonzero(a["NumLights"] > 0):
+            assert np.array_equal(a["LightIndex"][c][:a["NumLights"][c]], b["LightIndex"][c][:b["NumLights"][c]])
+
+
+@pytest.mark.parametrize("n,kind", [(0, "plain"), (1, "plain"), (7, "plain"), (256, "plain"), (300, "plain"), (1024, "plain"),
+                                    (256, "two_presets"), (300, "tiny_c0")])
+def test_frame_half_is_the_prologue_restated(ctx, world, n, kind):
+    """header, light planes and staged lists against numpy, bits equal"""
+    lights, dl, cl, buf, tables = culled(ctx, world, TILE_4K, n, kind)
+    img = buf.cpu().numpy().view(np.uint32)
+    stride = 257 if n <= 256 else 1025
+    safe = bool(((lights["C0"] >= np.float32(1e-6)) & (lights["C1"] >= 0) & (lights["C2"] >= 0)).all())
+    same = bool(((lights["C0"] == lights["C0"][0]) & (lights["C1"] == lights["C1"][0]) & (lights["C2"] == lights["C2"][0])).all()) if n else True
+    assert safe == (kind != "tiny_c0") and not (same and kind == "two_presets"), "the light set must switch its q_safe bit off"
+    assert list(img[TABLES_HEADER:TABLES_HEADER + 4]) == [int(safe) | 2 * int(same), n, stride, 0]
+    want = np.zeros((9, stride), dtype=np.float32)
+    if n:
+        want[0:3, :n] = lights["Position"].T
+        want[3:6, :n] = (lights["Color"] * lights["Intensity"][:, None]).astype(np.float32).T
+        want[6, :n], want[7, :n], want[8, :n] = lights["C0"], lights["C1"], lights["C2"]
+    want[0:3, n] = np.float32(1.0e15)
+    want[6, n] = 1.0
+    planes = img[TABLES_PLANES:TABLES_LISTS]
+    assert np.array_equal(planes[:9 * stride], want.reshape(-1).view(np.uint32)), "light planes"
+    assert not planes[9 * stride:].any(), "the image behind the planes is zero"
+    table = np.frombuffer(cl.cpu().numpy().tobytes(), dtype=CLUSTER_DTYPE)
+    cnt = np.clip(table["NumLights"], 0, 32)
+    assert n < 300 or (table["NumLights"] == 32).any(), "300 lights and more: some clusters are at the 32-entry cap"
+    lists = img[TABLES_LISTS:TABLES_GEOM].reshape(NUM_CLUSTERS, 34)
+    assert np.array_equal(lists[:, 0], np.maximum((cnt + 3) & ~3, 4).astype(np.uint32)), "padded counts"
+    assert not lists[:, 1].any()
+    k = np.arange(32)[None, :]
+    assert np.array_equal(lists[:, 2:], np.where(k < cnt[:, None], 4 * table["LightIndex"], 4 * n).astype(np.uint32)), "entries / null entries"
+
+
+def test_geometry_half_is_the_float32_expressions(ctx):
+    """a 4K-sized tile at odd offsets of a frame whose width is no multiple of 24"""
+    x0, y0, tw, th, fw, fh = shape = (13, 7, 3840, 2160, 3877, 2171)
+    buf, tables = ctx.alloc_shade_tables(tw, th)
+    ctx.shade_geometry_tables(Tile(*shape), tables)
+    geom = buf.cpu().numpy().view(np.uint32)[TABLES_GEOM:TABLES_GEOM + 2 * (tw + th)].reshape(-1, 2)
+    f32 = np.float32
+    u = ((x0 + np.arange(tw)).astype(f32) + f32(0.5)) / f32(fw)
+    v = ((y0 + np.arange(th)).astype(f32) + f32(0.5)) / f32(fh)
+    ndc_x, ndc_y = f32(2.0) * u - f32(1.0), f32(1.0) - f32(2.0) * v
+    sx = np.clip(np.floor(u * f32(24.0)).astype(np.int32), 0, 23)
+    sy = np.clip(np.floor((f32(1.0) - v) * f32(16.0)).astype(np.int32), 0, 15)
+    assert u.dtype == f32 and ndc_y.dtype == f32
+    assert np.array_equal(geom[:tw, 0], (ndc_x * f32(0.5)).view(np.uint32)) and np.array_equal(geom[:tw, 1].view(np.int32), sx)
+    assert np.array_equal(geom[tw:, 0], (ndc_y * f32(0.5)).view(np.uint32)) and np.array_equal(geom[tw:, 1].view(np.int32), sy)
+    assert set(sx) == set(range(24)) and set(sy) == set(range(16))
+
+
+def test_staged_frame_bit_exact(ctx, world):
+    ref, got, on = both(ctx, world, FRAME, 256)
+    assert on.all() and not np.all(ref[..., :3] == PREFILL)
+    bad = np.argwhere((ref != got).any(axis=2))
+    assert bad.size == 0, f"{len(bad)} pixels differ, first at (y, x) = {tuple(bad[0])}"
+
+
+@pytest.mark.parametrize("n,kind", [(0, "plain"), (1, "plain"), (7, "plain"), (256, "plain"), (300, "plain"), (1024, "plain"),
+                                    (256, "two_presets"), (300, "tiny_c0")])
+def test_tile_of_a_4k_frame_bit_exact(ctx, world, n, kind):
+    ref, got, on = both(ctx, world, TILE_4K, n, kind)
+    assert on.sum() > 0.3 * on.size and not np.all(ref[on][:, :3] == PREFILL)
+    bad = np.argwhere((ref != got).any(axis=2))
+    assert bad.size == 0, f"{n} lights ({kind}): {len(bad)} pixels differ, first at (y, x) = {tuple(bad[0])}"
+    assert np.all(got[~on] == PREFILL), "an unshaded pixel was written"
+
+
+def test_rectangles_bit_exact(ctx, world):
+    rects = [(3, 1, 301, 17), (304, 18, 296, 22)]
+    ref, got, on = both(ctx, world, TILE_4K, 256, rects=rects)
+    inside = np.zeros(on.shape, dtype=bool)
+    for x, y, rw, rh in rects:
+        inside[y:y + rh, x:x + rw] = True
+    assert np.array_equal(ref, got)
+    assert np.all(got[~(inside & on)] == PREFILL), "a pixel outside the rectangles was written"
+    assert not np.all(got[inside & on] == PREFILL)
+
+
+@pytest.mark.parametrize("n", [256, 300])
+def test_small_frame_falls_back_bit_exact(ctx, world, n):
+    ref, got, on = both(ctx, world, SMALL, n)
+    assert np.array_equal(ref, got) and not np.all(got[on] == PREFILL)
+
+
+def test_refusals(ctx, world):
+    """tables built for another tile, for another light count, and with one half only: PBR_ERR_INVALID each"""
+    cam, g, gbd, on = world["scene"][TILE_4K]
+    lights, dl, cl, buf, tables = culled(ctx, world, TILE_4K, 256)
+    tw, th = TILE_4K[2:4]
+    hdr = ctx.zeros((th, tw, 4), torch.float16)
+
+    def shade(tile, n, t, rects=None):
+        ctx.deferred_shade_tabled(g, tile, gbd, tw, world["fold"], LR, world["denv"], ES, EM, cl, dl, n, hdr, tw, t, rects)
+
+    shade(Tile(*TILE_4K), 256, tables)   # the matching call is accepted
+    with pytest.raises(PbrError, match="another tile"):
+        shade(Tile(1301, 1000, tw, th, 3840, 2160), 256, tables)
+    with pytest.raises(PbrError, match="another light count"):
+        shade(Tile(*TILE_4K), 255, tables)
+    with pytest.raises(PbrError, match="another light count"):
+        shade(Tile(*TILE_4K), 255, tables, rects=[(0, 0, 8, 8)])
+    buf_f, frame_only = ctx.alloc_shade_tables(tw, th)
+    ctx.clustered_tables(g, dl, 256, ctx.alloc_clusters(), frame_only)
+    with pytest.raises(PbrError, match="one half"):
+        shade(Tile(*TILE_4K), 256, frame_only)
+    buf_g, geometry_only = ctx.alloc_shade_tables(tw, th)
+    ctx.shade_geometry_tables(Tile(*TILE_4K), geometry_only)
+    with pytest.raises(PbrError, match="one half"):
+        shade(Tile(*TILE_4K), 256, geometry_only)
+    ctx.sync()
+
+
+@pytest.mark.parametrize("size", [(256, 144), (1440, 960)])
+def test_frame_on_the_tabled_path_writes_the_folded_frame(ctx, world, size):
+    """DeferredFrame: hdr, hist, avg and ldr of three frames, tabled against folded"""
+    fw, fh = size
+    cam, g, lights, gb, tile = common.shade_scene(fw, fh, 256, world["sh"], rough_min=48, coverage_mask=True)
+    frames = []
+    for tabled in (False, True):
+        fr = DeferredFrame(ctx, TileSpec(0, 0, fw, fh, fw, fh, 0), g, lights, world["lut"], LR, world["env_plain"], ES, EM)
+        assert fr.tabled
+        fr.tabled = tabled
+        fr.upload_gbuffer(gb)
+        fr.set_prev_luminance(0.18)
+        frames.append(fr)
+    for i in range(3):
+        got = []
+        for fr in frames:
+            fr.render()
+            ctx.sync()
+            got.append((fr.hdr.view(torch.int16).cpu().numpy(), fr.hist.cpu().numpy(), fr.avg.cpu().numpy().view(np.uint32), fr.ldr_numpy()))
+        for name, a, b in zip(("hdr", "hist", "avg", "ldr"), got[0], got[1]):
+            assert np.array_equal(a, b), f"{fw} x {fh}, frame {i}: {name} differs"
+    assert frames[1].tables.built == 3 and frames[0].tables.built == 2

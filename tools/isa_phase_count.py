@@ -1,6 +1,8 @@
 """Instruction-class counts of k_deferred_shade<true, 257, false, NoViews> (the 4K / 256-light instantiation) from the compiler's
 gfx950 ISA.  No GPU needed.
-    python tools/isa_phase_count.py [out.md] [--phases] [--fold] [--src shade.hip]
+    python tools/isa_phase_count.py [out.md] [--phases] [--fold | --tabled] [--prologue] [--src shade.hip]
+--prologue adds the prologue rows (below) to the report of the sampled or the folded kernel.
+--tabled measures k_deferred_shade_tabled<257> (pbr_deferred_shade_tabled: the folded-LUT kernel with its prologue read from the shade tables).
 --fold measures k_deferred_shade<true, 257, false, NoViews, true>, the instantiation that reads the LUT from its x-folded table
 (pbr_deferred_shade_folded), and adds the static v_* count of its LUT phase (the kernel minus its -DPBR_EXP_NOLUT build).
 Reported:
@@ -12,6 +14,7 @@ Reported:
     of the as-shipped walk (the cheapest instantiation: attenuation floor hoisted, rough wave, one polynomial).  Every walk
     instantiation's few instructions outside its loop are in the static count although one runs: an upper bound, alike on both
     sides of a comparison;
+  * the prologue: the v_* and s_barrier the kernel holds outside the row loop (static; what a block runs once, before it);
   * with --phases, per-phase counts: shade.hip compiled once per PBR_EXP_* switch that removes one phase of shade_pixel; the
     difference of the kernels' static v_* counts is that phase.
 Only instruction CLASSES are counted (v_*, v_pk_*, the transcendental unit's, moves, ds_*, global_*, s_waitcnt, s_barrier, other s_*).
@@ -33,6 +36,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 PREFIX = "_Z16k_deferred_shadeILb1ELi257ELb0E"
 VIEWS = "NoViews"
 FOLD_ARG = {False: "NoViewsELb0E", True: "NoViewsELb1E"}   # ... NoViews, LUTFOLD>: the sampled-LUT and the folded-LUT instantiation
+TABLED_PREFIX = "_Z23k_deferred_shade_tabledILi257EE"   # k_deferred_shade_tabled<257>
 TRIPS = 16   # pairs of lights of a capped (32-entry) list
 
 
@@ -107,11 +111,18 @@ def walks_and_row(lines):
     return [(lb, body) for lb, body in inner.items() if count(body)["packed"] >= 40], row
 
 
-def measure(src=SRC, fold=False, lut_phase=False):
-    """lut_phase: also the static v_* of the LUT phase (one more compile, -DPBR_EXP_NOLUT)"""
+def prologue(lines):
+    """instruction classes of what the kernel holds outside its row loop (the Depth=1 loop that encloses the walks): a block runs that once,
+    before the loop — nothing but s_endpgm follows it"""
+    whole, row = count(lines), count(walks_and_row(lines)[1])
+    return {k: whole[k] - row[k] for k in whole}
+
+
+def measure(src=SRC, fold=False, lut_phase=False, prefix=PREFIX):
+    """lut_phase: also the static v_* of the LUT phase (one more compile, -DPBR_EXP_NOLUT); prefix: the kernel (TABLED_PREFIX: the tabled one)"""
     builds = [(), ("PBR_EXP_NOEXACT",)] + ([("PBR_EXP_NOLUT",)] if lut_phase else [])
     with ThreadPoolExecutor(len(builds)) as ex:
-        shipped, noexact, *nolut = ex.map(lambda d: kernel(compile_isa(d, src), fold=fold), builds)
+        shipped, noexact, *nolut = ex.map(lambda d: kernel(compile_isa(d, src), prefix, fold=fold), builds)
     name, code, foot = shipped
     walks, row = walks_and_row(code)
     if not walks or not row:
@@ -132,6 +143,8 @@ def measure(src=SRC, fold=False, lut_phase=False):
     res["exact_path"] = res["row_static"] - in_walks - res["surround"]
     res["hot_trip"] = hot["valu_per_trip"]
     res["row_executed"] = res["surround"] + TRIPS * hot["valu_per_trip"]
+    pro = prologue(code)
+    res["prologue"], res["prologue_barriers"] = pro["valu"], pro["barrier"]
     if nolut:
         res["lut_phase"] = res["kernel"]["valu"] - count(nolut[0][1])["valu"]
     return res
@@ -141,14 +154,16 @@ METRICS = [("occupancy", "occupancy (waves per SIMD)"), ("scratch", "scratch byt
            ("surround", "v_* per pixel row around the walk (row body - walk loops - exact-slice path)"),
            ("row_executed", f"executed v_* per pixel row at {TRIPS} trips, as-shipped walk")]
 LUT_METRIC = ("lut_phase", "v_* of the split-sum LUT phase (kernel - its PBR_EXP_NOLUT build, static)")
+PROLOGUE_METRICS = [("prologue", "v_* of the prologue (the kernel outside its row loop, static)"), ("prologue_barriers", "s_barrier of the prologue")]
 
 
-def report(res):
+def report(res, with_prologue=False):
     k = res["kernel"]
-    doc = ["# k_deferred_shade<true, 257, false, NoViews" + (", true" if FOLD_ARG[True] in res["name"] else "") + ">: instruction classes of the gfx950 ISA (static counts)", "", f"`{res['name']}`", "",
+    title = "k_deferred_shade_tabled<257>" if res["name"].startswith(TABLED_PREFIX) else "k_deferred_shade<true, 257, false, NoViews" + (", true" if FOLD_ARG[True] in res["name"] else "") + ">"
+    doc = ["# " + title + ": instruction classes of the gfx950 ISA (static counts)", "", f"`{res['name']}`", "",
            f"whole kernel: {k['valu']} v_* ({k['packed']} packed, {k['trans']} transcendental, {k['moves']} moves), {k['ds']} ds_*, {k['global']} global_*; {res['vgprs']} VGPRs", "",
            "| metric | value |", "|---|---|"]
-    doc += [f"| {text} | {res[key]:g} |" for key, text in METRICS + [LUT_METRIC] if key in res]
+    doc += [f"| {text} | {res[key]:g} |" for key, text in METRICS + [LUT_METRIC] + (PROLOGUE_METRICS if with_prologue else []) if key in res]
     doc += ["", f"row body: {res['row_static']} v_* static, of them {sum(w['body']['valu'] for w in res['walks'])} in the walk loops and {res['exact_path']} on the exact-slice path", "",
             "light walks (one of them runs per pixel; a trip = one pair of lights):", "",
             "| loop | trips per body | v_* per trip | packed per trip | transcendental per trip | moves per body | ds_* per body |", "|---|---|---|---|---|---|---|"]
@@ -159,7 +174,7 @@ def report(res):
 
 def parse_metrics(md_text):
     """{metric key: value} of a report written by this tool"""
-    by_text = {text: key for key, text in METRICS + [LUT_METRIC]}
+    by_text = {text: key for key, text in METRICS + [LUT_METRIC] + PROLOGUE_METRICS}
     out = {}
     for m in re.finditer(r"^\| (.+?) \| ([-0-9.e+]+) \|$", md_text, re.M):
         if m.group(1) in by_text:
@@ -251,7 +266,13 @@ def main(argv):
         src = argv[argv.index("--src") + 1]
         args.remove(src)
     fold = "--fold" in argv
-    doc = report(measure(src, fold=fold, lut_phase=fold))
+    if "--tabled" in argv:   # the tabled kernel, and the prologue of the folded one it replaces beside it
+        with ThreadPoolExecutor(2) as ex:
+            tabled, folded = ex.map(lambda a: measure(src, **a), [dict(prefix=TABLED_PREFIX), dict(fold=True)])
+        doc = report(tabled, with_prologue=True)
+        doc += ["", f"the untabled folded kernel `{folded['name']}`: prologue {folded['prologue']} v_*, {folded['prologue_barriers']} s_barrier"]
+    else:
+        doc = report(measure(src, fold=fold, lut_phase=fold), with_prologue="--prologue" in argv)
     if "--phases" in argv:
         doc += phases(src, fold)
     text = "\n".join(doc) + "\n"
