@@ -129,6 +129,10 @@ __device__ __forceinline__ V3 cube_dir_raw(uint32_t face, float u, float v) {
         default: return v3(-u, -v, -1.0f);
     }
 }
+// DIV: sc / ma and tc / ma as the oracle forms them, one IEEE divide each (the sky resolve).  The default — one divide, two
+// multiplies — rounds twice and lands an x.8 snap step beside the oracle on ~1e-4 of the directions of a rotated camera; its callers
+// floor the result at texel centres or are held to the oracle in fp16 ULPs of smooth chains, where that step is invisible.
+template <bool DIV = false>
 __device__ __forceinline__ void cube_face_uv(V3 d, uint32_t& face, float& u, float& v) {
     float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
     float sc, tc, ma;
@@ -145,9 +149,14 @@ __device__ __forceinline__ void cube_face_uv(V3 d, uint32_t& face, float& u, flo
         if (d.z >= 0.0f) { face = 4; sc = d.x;  tc = -d.y; }
         else             { face = 5; sc = -d.x; tc = -d.y; }
     }
-    float inv = 1.0f / ma;   // IEEE divide: u,v feed floor()
-    u = (sc * inv + 1.0f) * 0.5f;
-    v = (tc * inv + 1.0f) * 0.5f;
+    if constexpr (DIV) {
+        u = (sc / ma + 1.0f) * 0.5f;
+        v = (tc / ma + 1.0f) * 0.5f;
+    } else {
+        float inv = 1.0f / ma;   // IEEE divide: u,v feed floor()
+        u = (sc * inv + 1.0f) * 0.5f;
+        v = (tc * inv + 1.0f) * 0.5f;
+    }
 }
 __host__ __device__ __forceinline__ size_t cube_mip_offset(uint32_t size, uint32_t mip) {
     size_t off = 0;
@@ -190,10 +199,10 @@ __device__ __forceinline__ F4 cube_fetch_seamless(int s, uint32_t face, int x, i
     }
     return texel(face, x, y);
 }
-template <class Texel>
+template <bool DIV = false, class Texel>
 __device__ __forceinline__ F4 cube_bilinear(int s, V3 dir, const Texel& texel) {
     uint32_t face; float u, v;
-    cube_face_uv(dir, face, u, v);
+    cube_face_uv<DIV>(dir, face, u, v);
     BilinearCoord cx = bilinear_coord(u, s), cy = bilinear_coord(v, s);
     F4 c00 = cube_fetch_seamless(s, face, cx.i0, cy.i0, texel);
     F4 c10 = cube_fetch_seamless(s, face, cx.i1, cy.i0, texel);
@@ -216,7 +225,7 @@ struct CubeTexelF16 {
     }
 };
 // TextureCube.SampleLevel(LinearClamp, dir, lod): trilinear, lod clamped to [0, mips-1]
-template <class TexelT, class Ptr>
+template <class TexelT, bool DIV = false, class Ptr>
 __device__ __forceinline__ F4 cube_trilinear(Ptr data, uint32_t size, uint32_t mips, V3 dir, float lod) {
     float maxl = (float)(mips - 1);
     lod = (lod == lod) ? lod : 0.0f;
@@ -226,10 +235,10 @@ __device__ __forceinline__ F4 cube_trilinear(Ptr data, uint32_t size, uint32_t m
     uint32_t l1 = min(l0 + 1, mips - 1);
     float f = lod - fl;
     TexelT t0{data + 4 * cube_mip_offset(size, l0), (int)(size >> l0)};
-    F4 a = cube_bilinear((int)(size >> l0), dir, t0);
+    F4 a = cube_bilinear<DIV>((int)(size >> l0), dir, t0);
     if (f == 0.0f || l1 == l0) return a;
     TexelT t1{data + 4 * cube_mip_offset(size, l1), (int)(size >> l1)};
-    F4 b = cube_bilinear((int)(size >> l1), dir, t1);
+    F4 b = cube_bilinear<DIV>((int)(size >> l1), dir, t1);
     return fma4(b, f, a * (1.0f - f));
 }
 

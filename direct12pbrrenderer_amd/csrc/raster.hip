@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_skybox(SkyParams p, const float* __rest
     const float gx = (float)(p.x0 + px), gy = (float)(p.y0 + py);
     const V3 d = sky_ray(p, gx, gy);
     uint32_t face; float fu, fv;
-    cube_face_uv(d, face, fu, fv);
+    cube_face_uv<true>(d, face, fu, fv);
     float u0, v0, ux, vx, uy, vy;
     project_on_face(d, face, u0, v0);
     project_on_face(sky_ray(p, gx + 1.0f, gy), face, ux, vx);
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void k_skybox(SkyParams p, const float* __rest
     const float rx = half_size * sqrtf((ux - u0) * (ux - u0) + (vx - v0) * (vx - v0));
     const float ry = half_size * sqrtf((uy - u0) * (uy - u0) + (vy - v0) * (vy - v0));
     const float lod = log2f(fmaxf(rx, ry));
-    const F4 c = cube_trilinear<CubeTexelF32>(sky, p.sky_size, p.sky_mips, d, lod);
+    const F4 c = cube_trilinear<CubeTexelF32, true>(sky, p.sky_size, p.sky_mips, d, lod);   // the oracle's divides (pbr_device.hpp)
     store_h4(hdr + 4 * ((size_t)py * p.hdr_pitch + px), f4(c.x, c.y, c.z, 1.0f));
 }
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import camera_cases
 import common
 import raster_ref
 from direct12pbrrenderer_amd import scene
@@ -53,11 +54,11 @@ def view_to_world(g):
     return np.array(g.InvView[:], dtype=np.float64).reshape(4, 4)
 
 
-def random_scene(w, h, seed, n=240):
-    """Triangles in front of the reference camera, in four draws with their own model matrices: ordinary ones, slivers,
-    degenerate ones, off-screen ones, ones that cross the near plane or leave the guard band."""
+def random_scene(w, h, seed, n=240, camera="default"):
+    """Triangles in front of the camera (one of camera_cases.CAMERAS; "default" is the reference's), in four draws with their own
+    model matrices: ordinary ones, slivers, degenerate ones, off-screen ones, ones that cross the near plane or leave the guard band."""
     rng = np.random.default_rng(seed)
-    cam = scene.Camera.reference_default(w, h)
+    cam = camera_cases.camera(camera, w, h)
     g = scene.make_global(cam, w, h)
     th = np.tan(float(cam.fov) / 2.0)
     ms = scene.MeshScene()
@@ -93,12 +94,17 @@ def random_scene(w, h, seed, n=240):
     return g, v, i, d
 
 
+# the cases under the reference's camera keep their ids; the cameras that pitch and roll (camera_cases.py) at the small size
+PARITY_CASES = [pytest.param(257, 131, 1, "default", id="257-131-1"), pytest.param(1440, 960, 2, "default", id="1440-960-2")] + \
+               [pytest.param(257, 131, 1, name, id=f"257-131-1-{name}") for name in camera_cases.NON_DEFAULT]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("w,h,seed", [(257, 131, 1), (1440, 960, 2)])
-def test_parity_with_restatement(ctx, orc, w, h, seed):
+@pytest.mark.parametrize("w,h,seed,camera", PARITY_CASES)
+def test_parity_with_restatement(ctx, orc, w, h, seed, camera):
     """All five planes bit-identical to raster_ref on random scenes (slivers, degenerate, off-screen, near-plane crossing,
     guard-band triangles)."""
-    g, v, i, d = random_scene(w, h, seed)
+    g, v, i, d = random_scene(w, h, seed, camera=camera)
     tile = Tile(0, 0, w, h, w, h)
     got = gpu_raster(ctx, g, tile, v, i, d)
     want = raster_ref.raster(g, tile, v, i, d, orc)

@@ -10,7 +10,7 @@ from direct12pbrrenderer_amd import scene
 from direct12pbrrenderer_amd.api import PbrError
 from direct12pbrrenderer_amd.structs import (NO_MAP, TEX_B8G8R8A8_UNORM, TEX_B8G8R8A8_UNORM_SRGB, TEX_R8_UNORM, TEX_R8G8B8A8_UNORM,
                                              Texture2D, Tile)
-from test_gpu_raster import PLANES, gpu_raster, random_scene, same, view_to_world
+from test_gpu_raster import PARITY_CASES, PLANES, gpu_raster, random_scene, same, view_to_world
 
 
 
@@ -53,10 +53,10 @@ def add_tangents_uvs(rng, v, uv_scale):
     v["uv"] = rng.uniform(-uv_scale, uv_scale, (len(v), 2)).astype(np.float32)
 
 
-def textured_scene(w, h, seed):
+def textured_scene(w, h, seed, camera="default"):
     """raster_test's random scene (slivers, near-plane crossings, guard band) with tangents, uvs, and textures of every format,
     square, non-square and non-power-of-two, some with partial chains; draw 0 takes constants only, the others mixes of maps."""
-    g, v, i, d = random_scene(w, h, seed)
+    g, v, i, d = random_scene(w, h, seed, camera=camera)
     rng = np.random.default_rng(seed + 100)
     add_tangents_uvs(rng, v, 6.0)
     texs = [random_texture(rng, 64, 64, TEX_R8G8B8A8_UNORM), random_texture(rng, 37, 21, TEX_B8G8R8A8_UNORM_SRGB),
@@ -88,9 +88,9 @@ def compare(got, want, what=""):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("w,h,seed", [(257, 131, 1), (1440, 960, 2)])
-def test_parity_with_restatement(ctx, orc, w, h, seed):
-    g, v, i, d, maps, texs = textured_scene(w, h, seed)
+@pytest.mark.parametrize("w,h,seed,camera", PARITY_CASES)
+def test_parity_with_restatement(ctx, orc, w, h, seed, camera):
+    g, v, i, d, maps, texs = textured_scene(w, h, seed, camera)
     tile = Tile(0, 0, w, h, w, h)
     got = gpu_raster_tex(ctx, g, tile, v, i, d, maps, texs)
     want = raster_tex_ref.raster_textured(g, tile, v, i, d, maps, texs, orc)
