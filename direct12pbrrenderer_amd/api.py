@@ -195,6 +195,46 @@ class PbrContext:
         self._check(self.lib.pbr_bc6h_decode_cube(self.h, C.byref(ptrs), int(size), int(mip_levels), _ptr(out)))
         return out
 
+    def bc6h_encode_cube(self, cube, size, mip_levels, out=None):
+        """pbr_bc6h_encode_cube, the inverse of bc6h_decode_cube: the fp32 RGBA cube chain (device float32 [cube_texels(size,
+        mip_levels), 4]; alpha ignored) -> six BC6H_UF16 face chains (device uint8, structs.bc6h_chain_bytes each), in the order px, nx,
+        py, ny, pz, nz.  out: six device tensors of that size or six device addresses to write to instead."""
+        nbytes = bc6h_chain_bytes(size, mip_levels)
+        if isinstance(cube, torch.Tensor) and nbytes and cube.numel() * cube.element_size() != 16 * cube_texels(size, mip_levels):
+            raise PbrError(f"bc6h_encode_cube: a cube of {cube.numel() * cube.element_size()} bytes, {size}^2 x {mip_levels} levels takes "
+                           f"{16 * cube_texels(size, mip_levels)}")
+        if out is None:
+            if not nbytes:
+                raise PbrError(f"bad BC6H cube description: {size}^2, {mip_levels} levels")
+            out = [self.empty((nbytes,), torch.uint8) for _ in range(6)]
+        out = list(out)
+        if len(out) != 6:
+            raise PbrError(f"bc6h_encode_cube: six faces, got {len(out)}")
+        for f in out:
+            if isinstance(f, torch.Tensor) and nbytes and f.numel() * f.element_size() != nbytes:
+                raise PbrError(f"bc6h_encode_cube: a face of {f.numel() * f.element_size()} bytes, {size}^2 x {mip_levels} levels takes {nbytes}")
+        ptrs = (C.c_void_p * 6)(*[_ptr(f) for f in out])
+        self._check(self.lib.pbr_bc6h_encode_cube(self.h, _ptr(cube), int(size), int(mip_levels), C.byref(ptrs)))
+        return out
+
+    def import_sky(self, level0, mip_levels=None):
+        """The reference's ImportCubeMap from decoded faces on: level 0 (host float32 [6, size, size, 4] or the flat equivalent) is
+        uploaded, its box mips made (cube_gen_mips), the SH pack projected from the fp32 level 0 — before compression, where the
+        reference computes it — and the chain compressed (bc6h_encode_cube).  Returns (faces, sh_pack): six device uint8 chains and
+        the 28 floats on the device; host.write_cubemap_file of their host copies is the sky's file."""
+        lv0 = np.ascontiguousarray(level0, dtype=np.float32).reshape(-1, 4)
+        size = int(round((len(lv0) // 6) ** 0.5))
+        if 6 * size * size != len(lv0):
+            raise PbrError(f"import_sky: level 0 of {len(lv0)} texels is not six square faces")
+        mips = size.bit_length() if mip_levels is None else int(mip_levels)
+        if not bc6h_chain_bytes(size, mips):
+            raise PbrError(f"bad BC6H cube description: {size}^2, {mips} levels")
+        cube = self.empty((cube_texels(size, mips), 4), torch.float32)
+        cube[:len(lv0)].copy_(torch.from_numpy(lv0))
+        self.cube_gen_mips(cube, size, mips)
+        sh = self.sh9_project(cube, size, mips)
+        return self.bc6h_encode_cube(cube, size, mips), sh
+
     def sh9_project(self, sky, sky_size, sky_mips=1, out=None):
         out = out if out is not None else self.empty((28,), torch.float32)
         c = CubeF32(sky.data_ptr(), sky_size, sky_mips)

@@ -58,6 +58,8 @@ SIGNATURES = {
     "pbrh_set_skybox_file": (_int, [_vp, _vp, C.c_size_t, _int]),
     "pbrh_load_skybox_file": (_int, [_vp, C.c_char_p, _int]),
     "pbrh_import_texture": (C.c_long, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_import_cubemap": (C.c_long, [_vp, _vp, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_import_cubemap_dir": (C.c_long, [_vp, C.c_char_p, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None
@@ -258,6 +260,36 @@ class HostRenderer:
             raise HostError(err.value.decode())
         out = np.zeros(need, dtype=np.uint8)
         if self.lib.pbrh_import_texture(self.h, lv0.ctypes.data, w, h, int(fmt), mips, out.ctypes.data, out.size, err, 256) != need:
+            raise HostError(err.value.decode())
+        return out.tobytes()
+
+    def import_cubemap(self, level0, mip_levels=None):
+        """pbrh_import_cubemap: host level 0 of a sky (float32 [6, size, size, 4] or the flat equivalent, faces px, nx, py, ny, pz, nz)
+        -> the bytes of the reference's serialized sky cube: box mips, the SH pack of the fp32 level 0 and the BC6H_UF16 chains (all
+        levels by default), made on the GPU.  set_skybox_file and DeferredFrame.set_sky_file take them as they are."""
+        lv0 = np.ascontiguousarray(level0, dtype=np.float32).reshape(-1, 4)
+        size = int(round((len(lv0) // 6) ** 0.5))
+        if 6 * size * size != len(lv0):
+            raise HostError(f"import_cubemap: level 0 of {len(lv0)} texels is not six square faces")
+        mips = 0 if mip_levels is None else int(mip_levels)
+        err = C.create_string_buffer(256)
+        need = self.lib.pbrh_import_cubemap(self.h, None, size, mips, None, 0, err, 256)
+        if need < 0:
+            raise HostError(err.value.decode())
+        out = np.zeros(need, dtype=np.uint8)
+        if self.lib.pbrh_import_cubemap(self.h, lv0.ctypes.data, size, mips, out.ctypes.data, out.size, err, 256) != need:
+            raise HostError(err.value.decode())
+        return out.tobytes()
+
+    def import_cubemap_dir(self, path, mip_levels=None):
+        """pbrh_import_cubemap_dir: import_cubemap of <path>/{px,nx,py,ny,pz,nz}.hdr (load_skybox's parse, RGBE expanded on the GPU)"""
+        mips = 0 if mip_levels is None else int(mip_levels)
+        err = C.create_string_buffer(256)
+        need = self.lib.pbrh_import_cubemap_dir(self.h, os.fsencode(path), mips, None, 0, err, 256)
+        if need < 0:
+            raise HostError(err.value.decode())
+        out = np.zeros(need, dtype=np.uint8)
+        if self.lib.pbrh_import_cubemap_dir(self.h, os.fsencode(path), mips, out.ctypes.data, out.size, err, 256) != need:
             raise HostError(err.value.decode())
         return out.tobytes()
 

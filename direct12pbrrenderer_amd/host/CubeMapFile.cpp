@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "FrameGraphResource.h"
+#include "HdrImage.h"
 #include "Scene.h"
 
 namespace MRendererHip {
@@ -117,6 +118,45 @@ std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, b
     } catch (const HipException& e) {
         throw HipException(path + ": " + e.what());
     }
+}
+
+size_t ImportCubeMap(pbr_ctx* ctx, const float* cube_mip0, const HdrImage* rgbe_faces, uint32_t size, uint32_t mip_levels,
+                     uint8_t* file, size_t bytes) {
+    if (mip_levels == 0)
+        for (uint32_t s = size; s; s >>= 1) mip_levels++;
+    const size_t chain = pbr_bc6h_chain_bytes(size, mip_levels);
+    if (!chain) throw HipException("cube-map import: bad size or level count (" + std::to_string(size) + ", " + std::to_string(mip_levels) + " levels)");
+    const size_t total = WriteCubeMapFile(nullptr, size, mip_levels, 2, pbr_sh_pack{}, nullptr, 0);
+    if (!file) return total;
+    if (!cube_mip0 && !rgbe_faces) throw HipException("cube-map import: null level 0");
+    if (bytes < total) throw HipException("cube-map import: output buffer too small");
+    auto check = [&](pbr_status st) { if (st != PBR_OK) throw HipException(pbr_last_error(ctx)); };
+    const size_t face_texels = (size_t)size * size;
+    DeviceMemory cube(pbr_cube_texels(size, mip_levels) * 16), blocks(6 * chain), pack(SH_BYTES);
+    // (a blocking copy from pageable memory has landed when it returns: the context's stream needs no event to see it)
+    if (rgbe_faces) {
+        DeviceMemory staging(6 * face_texels * 4);
+        for (int f = 0; f < 6; f++)
+            ThrowIfFailed(hipMemcpy((uint8_t*)staging.Ptr() + f * face_texels * 4, rgbe_faces[f].Rgbe.data(), face_texels * 4, hipMemcpyHostToDevice), "upload rgbe face");
+        check(pbr_rgbe_decode(ctx, (const uint8_t*)staging.Ptr(), 6 * face_texels, (float*)cube.Ptr()));
+        check(pbr_sync(ctx));       // `staging` is released here
+    } else {
+        ThrowIfFailed(hipMemcpy(cube.Ptr(), cube_mip0, 6 * face_texels * 16, hipMemcpyHostToDevice), "upload level 0");
+    }
+    if (mip_levels > 1) check(pbr_cube_gen_mips(ctx, (float*)cube.Ptr(), size, mip_levels));
+    pbr_cube_f32 c{(const float*)cube.Ptr(), size, mip_levels};
+    check(pbr_sh9_project(ctx, &c, (float*)pack.Ptr()));
+    void* faces_dev[6];             // (hipMalloc is 256-byte aligned and a chain is a multiple of 16 bytes)
+    for (int f = 0; f < 6; f++) faces_dev[f] = (uint8_t*)blocks.Ptr() + f * chain;
+    check(pbr_bc6h_encode_cube(ctx, (const float*)cube.Ptr(), size, mip_levels, faces_dev));
+    check(pbr_sync(ctx));
+    std::vector<uint8_t> host(6 * chain);
+    pbr_sh_pack sh{};
+    ThrowIfFailed(hipMemcpy(host.data(), blocks.Ptr(), host.size(), hipMemcpyDeviceToHost), "read blocks");
+    ThrowIfFailed(hipMemcpy(&sh, pack.Ptr(), SH_BYTES, hipMemcpyDeviceToHost), "read SH");
+    const void* faces_host[6];
+    for (int f = 0; f < 6; f++) faces_host[f] = host.data() + f * chain;
+    return WriteCubeMapFile(faces_host, size, mip_levels, 2, sh, file, bytes);
 }
 
 }  // namespace MRendererHip

@@ -53,4 +53,16 @@ std::shared_ptr<SkyBox> SkyBoxFromCubeMapFile(pbr_ctx* ctx, const uint8_t* file,
 // the same for a file on disk
 std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, bool recompute_sh);
 
+
+// ResourceLoader::ImportCubeMap (ResourceLoader.cpp:279-299) on the GPU, from decoded faces on: level 0 — cube_mip0 (host, 6 x size^2
+// fp32 RGBA) or, when rgbe_faces is given, six parsed .hdr faces expanded by pbr_rgbe_decode — is uploaded, its box mips made
+// (pbr_cube_gen_mips), the SH pack projected from the fp32 level 0 BEFORE compression (where the reference computes it, in the
+// CubeMapTextureData constructor, BasicStorage.h:313), the chain compressed (pbr_bc6h_encode_cube), read back and written by
+// WriteCubeMapFile with format 2.  mip_levels 0 = the full chain.  Returns the file's size; with file == nullptr only the size, and
+// nothing runs.  Blocks until the GPU is done.  Throws HipException: a size or level count pbr_bc6h_chain_bytes rejects, a null
+// level 0, a buffer smaller than the file.
+struct HdrImage;
+size_t ImportCubeMap(pbr_ctx* ctx, const float* cube_mip0, const HdrImage* rgbe_faces, uint32_t size, uint32_t mip_levels,
+                     uint8_t* file, size_t bytes);
+
 }  // namespace MRendererHip

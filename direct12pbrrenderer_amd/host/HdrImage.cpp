@@ -105,16 +105,21 @@ HdrImage LoadHDRImageFile(const std::string& path) {
     }
 }
 
-std::shared_ptr<SkyBox> LoadCubeMap(pbr_ctx* ctx, const std::string& dir) {
+uint32_t LoadCubeMapFaces(const std::string& dir, HdrImage (&faces)[6]) {
     // same face order as the reference (ResourceLoader.cpp:415)
     static const char* const file_names[6] = {"px.hdr", "nx.hdr", "py.hdr", "ny.hdr", "pz.hdr", "nz.hdr"};
-    HdrImage faces[6];
     for (int i = 0; i < 6; i++) {
         faces[i] = LoadHDRImageFile(dir + "/" + file_names[i]);
         if (faces[i].Width != faces[i].Height) throw HipException(std::string(file_names[i]) + ": cube faces must be square");
         if (faces[i].Width != faces[0].Width) throw HipException(std::string(file_names[i]) + ": cube faces differ in size");
         if (faces[i].Width % 4) throw HipException(std::string(file_names[i]) + ": width and height must be a multiple of 4 (ResourceLoader.cpp:399)");
     }
+    return faces[0].Width;
+}
+
+std::shared_ptr<SkyBox> LoadCubeMap(pbr_ctx* ctx, const std::string& dir) {
+    HdrImage faces[6];
+    LoadCubeMapFaces(dir, faces);
     const uint32 size = faces[0].Width;
     uint32 mips = 1;
     while ((size >> mips) >= 1) mips++;

@@ -27,6 +27,9 @@ struct HdrImage {
 HdrImage ParseRadianceHDR(const uint8_t* file, size_t bytes);
 HdrImage LoadHDRImageFile(const std::string& path);
 
+// The file half of LoadCubeMap: the six faces parsed and checked (square, equal, a multiple of 4 texels); returns their size.
+uint32_t LoadCubeMapFaces(const std::string& dir, HdrImage (&faces)[6]);
+
 // LoadCubeMap (ResourceLoader.cpp:408-428): <dir>/{px,nx,py,ny,pz,nz}.hdr -> fp32 RGBA cube with the full box
 // mip chain and its SH9 pack.  Faces must be square, equal, and a multiple of 4 texels (:399-403).
 std::shared_ptr<SkyBox> LoadCubeMap(pbr_ctx* ctx, const std::string& dir);

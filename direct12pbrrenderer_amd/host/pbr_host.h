@@ -68,6 +68,19 @@ int pbrh_parse_cubemap_file(const uint8_t* file, size_t bytes, uint32_t* size, u
  * pack, file_bytes too small. */
 long pbrh_write_cubemap_file(const void* const faces[6], uint32_t size, uint32_t mip_levels, uint32_t format, const float sh_pack[28],
                              uint8_t* file, size_t file_bytes, char* err, size_t err_len);
+/* The reference's ResourceLoader::ImportCubeMap (ResourceLoader.cpp:279-299) from decoded faces on: cube_mip0 (host, 6 * size * size
+ * fp32 RGBA texels, faces px, nx, py, ny, pz, nz) is uploaded and, on the renderer's context and in this order, its box mips are
+ * made (pbr_cube_gen_mips), the SH pack projected from the fp32 level 0 — BEFORE compression, where the reference computes it
+ * (BasicStorage.h:313), not from the decoded blocks — and the chain compressed (pbr_bc6h_encode_cube); the blocks are read back
+ * and written by pbrh_write_cubemap_file with format 2.  pbrh_import_cubemap_dir takes <dir>/{px,nx,py,ny,pz,nz}.hdr instead
+ * (pbrh_load_skybox's parse and pbr_rgbe_decode).  mip_levels 0 = the full chain.  Returns the file's byte count — file_out NULL:
+ * the size needed, and nothing runs on the GPU (the _dir form still reads the six files, for their size) — or -1 + reason in err:
+ * a size or level count pbr_bc6h_chain_bytes rejects, a null level 0, file_bytes too small, an unreadable or unequal face.
+ * What it writes goes to pbrh_set_skybox_file / pbrh_load_skybox_file as it is. */
+long pbrh_import_cubemap(pbrh_renderer* r, const float* cube_mip0, uint32_t size, uint32_t mip_levels,
+                         uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
+long pbrh_import_cubemap_dir(pbrh_renderer* r, const char* dir, uint32_t mip_levels,
+                             uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
 /* CPU only: parse one .hdr file held in memory (header + flat / run-length scanlines) into RGBE texels */
 int pbrh_parse_hdr(const uint8_t* file, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgbe, size_t rgbe_bytes, char* err, size_t err_len);
 /* CPU only, stateless: one of the reference's serialized 2D textures (a texture asset's _data.bin) held in memory: TextureInfo (uint16

@@ -244,6 +244,40 @@ size_t pbr_bc6h_chain_bytes(uint32_t size, uint32_t mip_levels);
  *   the fp32 value is that half, exactly (at most 0x7BFF: never inf or NaN).  The + 32 is DirectXTex's BC67_WEIGHT_ROUND.
  * Parity with a reference-held file is not pinned: the checkout holds none (Asset/SkyBox/HDRWild.json without its data file). */
 pbr_status pbr_bc6h_decode_cube(pbr_ctx* ctx, const void* const face_blocks[6], uint32_t size, uint32_t mip_levels, float* out_rgba);
+/* ---- BC6H sky import (new): the producing half — ResourceLoader::ImportCubeMap's TextureCompressor::Compress to BC6H_UF16 ---- */
+/* The inverse of pbr_bc6h_decode_cube, same layouts on both sides (ResourceLoader.cpp:279-299: LoadCubeMap, CubeMapTextureData,
+ * BinarySerialize, Compress).  cube_rgba: DEVICE, 16-byte aligned, the pbr_cube_f32 chain of `size` and `mip_levels` (mips
+ * concatenated, six faces per mip, fp32 RGBA; alpha is ignored).  face_blocks_out: HOST array of six DEVICE pointers, 16-byte
+ * aligned, each receiving pbr_bc6h_chain_bytes(size, mip_levels) bytes, order px, nx, py, ny, pz, nz; nothing is written outside
+ * those bytes.  One asynchronous launch on the context's stream for all faces and levels, no allocation, no host synchronisation.
+ * Refusals (PBR_ERR_INVALID, nothing enqueued): those of pbr_bc6h_decode_cube — a null or misaligned pointer (the array, any face,
+ * cube_rgba), size 0, not a multiple of 4 or above PBR_BC6H_MAX_SIZE, mip_levels 0 or above floor(log2(size)) + 1.
+ * The encoding rule, pinned, all in integers after the first step (`/` is FLOOR division; per-texel errors fit uint32, block sums
+ * and the least-squares terms are 64-bit); tests/bc6h_encode_ref.py restates it in numpy and the kernel is held to it bit for bit.
+ * Only one-region modes are emitted.
+ *   Half code of a channel value v: h = the IEEE half bit pattern of clamp(v, 0, 65504) rounded to nearest even.  NaN gives 0; any
+ *   v <= 0 gives 0, -0.0 included (the sign bit is cleared); +inf and anything above 65504 give 0x7BFF; subnormal halves stay
+ *   subnormal codes.  Its target in 16-bit endpoint space is t = (64 h + 30) / 31, the least x whose decode finish (31 x) >> 6 is h.
+ *   A block's texels are those of the level that lie inside it (n of them, 1 .. 16: levels of 2 and 1 texels, and of 6 or 3 under a
+ *   size of 12, give partial blocks).  A texel outside the level takes no part in any minimum, maximum, sum or error and gets index 0.
+ *   fit(a, b) of two 16-bit endpoint triples: palette entry k = 0 .. 15 of channel c is p_k,c = ((a_c (64 - w_k) + b_c w_k + 32) >> 6)
+ *   * 31 >> 6 with the 4-bit weights w_k of the decode rule; each texel takes the k of least sum_c (p_k,c - h_c)^2 (distance in
+ *   half-code space), the lowest k on ties; the block's error is the sum over its texels.
+ *   Start: per channel lo_c and hi_c of t over the block; dom = the channel with the largest hi - lo (the first of r, g, b on ties);
+ *   cov_c = n sum(t_c t_dom) - sum(t_c) sum(t_dom); A_c = hi_c and B_c = lo_c, exchanged for every channel with cov_c < 0; fit(A, B).
+ *   Refine, at most twice, at 16 bits: per texel alpha = 64 - w[index], beta = w[index]; Saa = sum(alpha alpha), Sbb = sum(beta beta),
+ *   Sab = sum(alpha beta), Sat_c = sum(alpha t_c), Sbt_c = sum(beta t_c), det = Saa Sbb - Sab Sab.  det == 0: stop.  A'_c =
+ *   clamp((128 (Sbb Sat_c - Sab Sbt_c) + det) / (2 det), 0, 65535), B'_c = clamp((128 (Saa Sbt_c - Sab Sat_c) + det) / (2 det), 0,
+ *   65535); fit(A', B'): if its error is strictly smaller it replaces A, B, the indices and the error, otherwise stop.
+ *   Modes, tried in the order 0x0f (16.4), 0x0b (12.8), 0x07 (11.9), 0x03 (10.10), n = endpoint bits: qa = A >> (16 - n), qb = B >>
+ *   (16 - n); fit the pair unquantized by the decode rule.  If texel 0's index is >= 8, exchange qa and qb and replace every inside
+ *   texel's index by 15 - index (the weights are symmetric: the error is unchanged).  For the three transformed modes the stored
+ *   delta qb - qa must fit the mode's signed delta width in every channel AFTER that exchange, otherwise the mode is no candidate;
+ *   0x03 always is.  The candidate of least error is kept, the earlier one on ties.
+ *   Emit in the bit layout of the decode rule, the delta in two's complement of its width.  The anchor's high bit is always 0, no
+ *   reserved mode is emitted, no texel can decode above 0x7BFF, and a block of one colour is lossless through mode 0x0f.
+ * Two-region modes, BC6H_SF16 and parity with DirectXTex's encoder (what the reference's import runs) are out of scope. */
+pbr_status pbr_bc6h_encode_cube(pbr_ctx* ctx, const float* cube_rgba, uint32_t size, uint32_t mip_levels, void* const face_blocks_out[6]);
 
 /* env_map_gen.hlsl:50-105, all PBR_ENV_MIPS dispatches of PreFilterEnvMapPass::Execute
  * (DeferredPipeline.cpp:77-115): mip i is filtered with roughness i/(mips-1).
