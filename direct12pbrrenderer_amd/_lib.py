@@ -6,7 +6,7 @@ symbol cannot be resolved this module raises — it never substitutes another im
 import ctypes as C
 import os
 
-from .structs import CubeF32, GBuffer, Global, HaloPeer, ShadeTables, Texture2D, Tile, View
+from .structs import CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, ShadeTables, Texture2D, Tile, View
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB", os.path.join(_HERE, "libpbr_hip.so"))   # override = experiments only
@@ -61,6 +61,7 @@ SIGNATURES = {
     "pbr_deferred_shade_rects_tabled": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
                                                _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, _vp, _u32, C.POINTER(ShadeTables)]),
     "pbr_skybox": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(CubeF32), _vp, _u32, _vp, _u32]),
+    "pbr_skybox_bc6h": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(CubeBc6h), _vp, _u32, _vp, _u32]),
     "pbr_gbuffer_encode": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "pbr_gbuffer_raster_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),

@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from .structs import (ShadeTables, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, texture2d_bytes)
+                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, texture2d_bytes)
 
 
 class PbrError(RuntimeError):
@@ -347,6 +347,20 @@ class PbrContext:
         c = CubeF32(sky.data_ptr(), sky_size, sky_mips)
         self._check(self.lib.pbr_skybox(self.h, C.byref(g), C.byref(tile), C.byref(c), _ptr(stencil), pitch,
                                         _ptr(hdr), hdr_pitch))
+
+    def skybox_bc6h(self, g: Global, tile: Tile, faces, size, mip_levels, stencil, pitch, hdr, hdr_pitch):
+        """pbr_skybox_bc6h: the sky pass on a cube that stays resident as BC6H_UF16 blocks, sampled in place — the bits skybox() writes
+        from the cube bc6h_decode_cube makes of the same chains.  faces: six device tensors (uint8, structs.bc6h_chain_bytes each) or
+        six device addresses (16-byte aligned), in the order px, nx, py, ny, pz, nz."""
+        if len(faces) != 6:
+            raise PbrError(f"skybox_bc6h: six faces, got {len(faces)}")
+        nbytes = bc6h_chain_bytes(size, mip_levels)
+        for f in faces:
+            if torch.is_tensor(f) and (not nbytes or f.numel() * f.element_size() != nbytes):
+                raise PbrError(f"skybox_bc6h: a face of {f.numel() * f.element_size()} bytes, {size}^2 x {mip_levels} levels takes {nbytes}")
+        c = CubeBc6h((C.c_void_p * 6)(*[f.data_ptr() if torch.is_tensor(f) else int(f) for f in faces]), int(size), int(mip_levels))
+        self._check(self.lib.pbr_skybox_bc6h(self.h, C.byref(g), C.byref(tile), C.byref(c), _ptr(stencil), pitch,
+                                             _ptr(hdr), hdr_pitch))
 
     def gbuffer_encode(self, m0, m1, m2, w, h, pitch, A, B, Cc):
         """gbuffer.hlsl::ps_main on per-pixel material planes (float4 each) -> RGBA8 G-buffer planes."""

@@ -16,125 +16,14 @@
 
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
+#include "bc6h_decode_block.hpp"     // the mode tables, read_header / endpoints<M>, PARTITION, the anchor and weight constants
 
 namespace {
 
+using namespace bc6h_dec;
+
 constexpr uint32_t BC6H_MAX_LEVELS = 14;    // floor(log2(PBR_BC6H_MAX_SIZE)) + 1
 static_assert((1u << (BC6H_MAX_LEVELS - 1)) == PBR_BC6H_MAX_SIZE, "levels of the largest cube");
-
-// ---- the header of every mode: its fields in file order (LSB first), after the mode bits ----
-enum : uint8_t { R0, G0, B0, R1, G1, B1, R2, G2, B2, R3, G3, B3 };
-// n file bits -> bits lo .. lo + n - 1 of a field, the lowest first (rev: the highest first)
-struct Seg { uint8_t field, lo, n, rev; };
-constexpr Seg H00[] = {{G2, 4, 1, 0}, {B2, 4, 1, 0}, {B3, 4, 1, 0}, {R0, 0, 10, 0}, {G0, 0, 10, 0}, {B0, 0, 10, 0}, {R1, 0, 5, 0}, {G3, 4, 1, 0}, {G2, 0, 4, 0}, {G1, 0, 5, 0}, {B3, 0, 1, 0}, {G3, 0, 4, 0}, {B1, 0, 5, 0}, {B3, 1, 1, 0}, {B2, 0, 4, 0}, {R2, 0, 5, 0}, {B3, 2, 1, 0}, {R3, 0, 5, 0}, {B3, 3, 1, 0}};
-constexpr Seg H01[] = {{G2, 5, 1, 0}, {G3, 4, 2, 0}, {R0, 0, 7, 0}, {B3, 0, 2, 0}, {B2, 4, 1, 0}, {G0, 0, 7, 0}, {B2, 5, 1, 0}, {B3, 2, 1, 0}, {G2, 4, 1, 0}, {B0, 0, 7, 0}, {B3, 3, 1, 0}, {B3, 4, 2, 1}, {R1, 0, 6, 0}, {G2, 0, 4, 0}, {G1, 0, 6, 0}, {G3, 0, 4, 0}, {B1, 0, 6, 0}, {B2, 0, 4, 0}, {R2, 0, 6, 0}, {R3, 0, 6, 0}};
-constexpr Seg H02[] = {{R0, 0, 10, 0}, {G0, 0, 10, 0}, {B0, 0, 10, 0}, {R1, 0, 5, 0}, {R0, 10, 1, 0}, {G2, 0, 4, 0}, {G1, 0, 4, 0}, {G0, 10, 1, 0}, {B3, 0, 1, 0}, {G3, 0, 4, 0}, {B1, 0, 4, 0}, {B0, 10, 1, 0}, {B3, 1, 1, 0}, {B2, 0, 4, 0}, {R2, 0, 5, 0}, {B3, 2, 1, 0}, {R3, 0, 5, 0}, {B3, 3, 1, 0}};
-constexpr Seg H06[] = {{R0, 0, 10, 0}, {G0, 0, 10, 0}, {B0, 0, 10, 0}, {R1, 0, 4, 0}, {R0, 10, 1, 0}, {G3, 4, 1, 0}, {G2, 0, 4, 0}, {G1, 0, 5, 0}, {G0, 10, 1, 0}, {G3, 0, 4, 0}, {B1, 0, 4, 0}, {B0, 10, 1, 0}, {B3, 1, 1, 0}, {B2, 0, 4, 0}, {R2, 0, 4, 0}, {B3, 0, 1, 0}, {B3, 2, 1, 0}, {R3, 0, 4, 0}, {G2, 4, 1, 0}, {B3, 3, 1, 0}};
-constexpr Seg H0A[] = {{R0, 0, 10, 0}, {G0, 0, 10, 0}, {B0, 0, 10, 0}, {R1, 0, 4, 0}, {R0, 10, 1, 0}, {B2, 4, 1, 0}, {G2, 0, 4, 0}, {G1, 0, 4, 0}, {G0, 10, 1, 0}, {B3, 0, 1, 0}, {G3, 0, 4, 0}, {B1, 0, 5, 0}, {B0, 10, 1, 0}, {B2, 0, 4, 0}, {R2, 0, 4, 0}, {B3, 1, 2, 0}, {R3, 0, 4, 0}, {B3, 3, 2, 1}};
-constexpr Seg H0E[] = {{R0, 0, 9, 0}, {B2, 4, 1, 0}, {G0, 0, 9, 0}, {G2, 4, 1, 0}, {B0, 0, 9, 0}, {B3, 4, 1, 0}, {R1, 0, 5, 0}, {G3, 4, 1, 0}, {G2, 0, 4, 0}, {G1, 0, 5, 0}, {B3, 0, 1, 0}, {G3, 0, 4, 0}, {B1, 0, 5, 0}, {B3, 1, 1, 0}, {B2, 0, 4, 0}, {R2, 0, 5, 0}, {B3, 2, 1, 0}, {R3, 0, 5, 0}, {B3, 3, 1, 0}};
-constexpr Seg H12[] = {{R0, 0, 8, 0}, {G3, 4, 1, 0}, {B2, 4, 1, 0}, {G0, 0, 8, 0}, {B3, 2, 1, 0}, {G2, 4, 1, 0}, {B0, 0, 8, 0}, {B3, 3, 2, 0}, {R1, 0, 6, 0}, {G2, 0, 4, 0}, {G1, 0, 5, 0}, {B3, 0, 1, 0}, {G3, 0, 4, 0}, {B1, 0, 5, 0}, {B3, 1, 1, 0}, {B2, 0, 4, 0}, {R2, 0, 6, 0}, {R3, 0, 6, 0}};
-constexpr Seg H16[] = {{R0, 0, 8, 0}, {B3, 0, 1, 0}, {B2, 4, 1, 0}, {G0, 0, 8, 0}, {G2, 4, 2, 1}, {B0, 0, 8, 0}, {G3, 5, 1, 0}, {B3, 4, 1, 0}, {R1, 0, 5, 0}, {G3, 4, 1, 0}, {G2, 0, 4, 0}, {G1, 0, 6, 0}, {G3, 0, 4, 0}, {B1, 0, 5, 0}, {B3, 1, 1, 0}, {B2, 0, 4, 0}, {R2, 0, 5, 0}, {B3, 2, 1, 0}, {R3, 0, 5, 0}, {B3, 3, 1, 0}};
-constexpr Seg H1A[] = {{R0, 0, 8, 0}, {B3, 1, 1, 0}, {B2, 4, 1, 0}, {G0, 0, 8, 0}, {B2, 5, 1, 0}, {G2, 4, 1, 0}, {B0, 0, 8, 0}, {B3, 4, 2, 1}, {R1, 0, 5, 0}, {G3, 4, 1, 0}, {G2, 0, 4, 0}, {G1, 0, 5, 0}, {B3, 0, 1, 0}, {G3, 0, 4, 0}, {B1, 0, 6, 0}, {B2, 0, 4, 0}, {R2, 0, 5, 0}, {B3, 2, 1, 0}, {R3, 0, 5, 0}, {B3, 3, 1, 0}};
-constexpr Seg H1E[] = {{R0, 0, 6, 0}, {G3, 4, 1, 0}, {B3, 0, 2, 0}, {B2, 4, 1, 0}, {G0, 0, 6, 0}, {G2, 5, 1, 0}, {B2, 5, 1, 0}, {B3, 2, 1, 0}, {G2, 4, 1, 0}, {B0, 0, 6, 0}, {G3, 5, 1, 0}, {B3, 3, 1, 0}, {B3, 4, 2, 1}, {R1, 0, 6, 0}, {G2, 0, 4, 0}, {G1, 0, 6, 0}, {G3, 0, 4, 0}, {B1, 0, 6, 0}, {B2, 0, 4, 0}, {R2, 0, 6, 0}, {R3, 0, 6, 0}};
-constexpr Seg H03[] = {{R0, 0, 10, 0}, {G0, 0, 10, 0}, {B0, 0, 10, 0}, {R1, 0, 10, 0}, {G1, 0, 10, 0}, {B1, 0, 10, 0}};
-constexpr Seg H07[] = {{R0, 0, 10, 0}, {G0, 0, 10, 0}, {B0, 0, 10, 0}, {R1, 0, 9, 0}, {R0, 10, 1, 0}, {G1, 0, 9, 0}, {G0, 10, 1, 0}, {B1, 0, 9, 0}, {B0, 10, 1, 0}};
-constexpr Seg H0B[] = {{R0, 0, 10, 0}, {G0, 0, 10, 0}, {B0, 0, 10, 0}, {R1, 0, 8, 0}, {R0, 10, 2, 1}, {G1, 0, 8, 0}, {G0, 10, 2, 1}, {B1, 0, 8, 0}, {B0, 10, 2, 1}};
-constexpr Seg H0F[] = {{R0, 0, 10, 0}, {G0, 0, 10, 0}, {B0, 0, 10, 0}, {R1, 0, 4, 0}, {R0, 10, 6, 1}, {G1, 0, 4, 0}, {G0, 10, 6, 1}, {B1, 0, 4, 0}, {B0, 10, 6, 1}};
-
-struct ModeDesc {
-    uint32_t endpoint_bits, delta_bits[3];
-    bool transformed, two;
-    const Seg* segs;
-    uint32_t count;
-};
-template <uint32_t N>
-constexpr ModeDesc mode_of(uint32_t nb, uint32_t dr, uint32_t dg, uint32_t db, bool transformed, bool two, const Seg (&s)[N]) {
-    return ModeDesc{nb, {dr, dg, db}, transformed, two, s, N};
-}
-constexpr ModeDesc mode_desc(uint32_t mode) {
-    switch (mode) {
-        case 0x00: return mode_of(10, 5, 5, 5, true, true, H00);
-        case 0x01: return mode_of(7, 6, 6, 6, true, true, H01);
-        case 0x02: return mode_of(11, 5, 4, 4, true, true, H02);
-        case 0x06: return mode_of(11, 4, 5, 4, true, true, H06);
-        case 0x0a: return mode_of(11, 4, 4, 5, true, true, H0A);
-        case 0x0e: return mode_of(9, 5, 5, 5, true, true, H0E);
-        case 0x12: return mode_of(8, 6, 5, 5, true, true, H12);
-        case 0x16: return mode_of(8, 5, 6, 5, true, true, H16);
-        case 0x1a: return mode_of(8, 5, 5, 6, true, true, H1A);
-        case 0x1e: return mode_of(6, 6, 6, 6, false, true, H1E);
-        case 0x03: return mode_of(10, 10, 10, 10, false, false, H03);
-        case 0x07: return mode_of(11, 9, 9, 9, true, false, H07);
-        case 0x0b: return mode_of(12, 8, 8, 8, true, false, H0B);
-        default:   return mode_of(16, 4, 4, 4, true, false, H0F);     // 0x0f
-    }
-}
-constexpr uint32_t header_end(uint32_t mode) {
-    const ModeDesc d = mode_desc(mode);
-    uint32_t pos = mode < 2 ? 2 : 5;
-    for (uint32_t i = 0; i < d.count; i++) pos += d.segs[i].n;
-    return pos;
-}
-static_assert(header_end(0x00) == 77 && header_end(0x01) == 77 && header_end(0x02) == 77 && header_end(0x06) == 77 && header_end(0x0a) == 77 &&
-              header_end(0x0e) == 77 && header_end(0x12) == 77 && header_end(0x16) == 77 && header_end(0x1a) == 77 && header_end(0x1e) == 77,
-              "a two-region header ends where the partition starts");
-static_assert(header_end(0x03) == 65 && header_end(0x07) == 65 && header_end(0x0b) == 65 && header_end(0x0f) == 65,
-              "a one-region header ends where the indices start");
-
-// texel t in bit t: set = the second endpoint pair (e2 / e3)
-__constant__ uint16_t PARTITION[32] = {0xcccc, 0x8888, 0xeeee, 0xecc8, 0xc880, 0xfeec, 0xfec8, 0xec80, 0xc800, 0xffec, 0xfe80,
-                                       0xe800, 0xffe8, 0xff00, 0xfff0, 0xf000, 0xf710, 0x008e, 0x7100, 0x08ce, 0x008c, 0x7310,
-                                       0x3100, 0x8cce, 0x088c, 0x3110, 0x6666, 0x366c, 0x17e8, 0x0ff0, 0x718e, 0x399c};
-constexpr uint64_t ANCHOR_16_31 = 0x22882282f882282full;      // region 1's anchor texel of shapes 16 .. 31, a nibble each (0 .. 15: 15)
-constexpr uint64_t WEIGHTS3 = 0x40372e251b120900ull;          // 0, 9, 18, 27, 37, 46, 55, 64: a byte each
-constexpr uint64_t WEIGHTS4_LO = 0x1e1a15110d090400ull;       // 0, 4, 9, 13, 17, 21, 26, 30
-constexpr uint64_t WEIGHTS4_HI = 0x403c37332f2b2622ull;       // 34, 38, 43, 47, 51, 55, 60, 64
-
-// bits POS .. POS + N - 1 of the block
-template <uint32_t POS, uint32_t N>
-__device__ __forceinline__ uint32_t block_bits(uint64_t lo, uint64_t hi) {
-    static_assert(N >= 1 && N <= 16 && POS + N <= 128, "a header field");
-    uint64_t v;
-    if constexpr (POS >= 64) v = hi >> (POS - 64);
-    else if constexpr (POS + N <= 64) v = lo >> POS;
-    else v = (lo >> POS) | (hi << (64 - POS));
-    return (uint32_t)v & ((1u << N) - 1u);
-}
-template <uint32_t M, uint32_t S, uint32_t POS>
-__device__ __forceinline__ void read_header(uint64_t lo, uint64_t hi, uint32_t (&e)[12]) {
-    constexpr ModeDesc D = mode_desc(M);
-    if constexpr (S < D.count) {
-        constexpr Seg g = D.segs[S];
-        uint32_t v = block_bits<POS, g.n>(lo, hi);
-        if constexpr (g.rev != 0) v = __brev(v) >> (32u - g.n);
-        e[g.field] |= v << g.lo;
-        read_header<M, S + 1, POS + g.n>(lo, hi, e);
-    }
-}
-template <uint32_t N>
-__device__ __forceinline__ uint32_t unquantize(uint32_t x) {
-    if constexpr (N >= 15) return x;
-    else return x == 0u ? 0u : x == (1u << N) - 1u ? 0xffffu : ((x << 15) + 0x4000u) >> (N - 1u);
-}
-// a mode's header -> its unquantized endpoints e[3 i + c] (i: e0 .. e3, c: r, g, b); one-region modes leave e2 / e3 zero
-template <uint32_t M>
-__device__ __forceinline__ void endpoints(uint64_t lo, uint64_t hi, uint32_t (&e)[12]) {
-    constexpr ModeDesc D = mode_desc(M);
-    read_header<M, 0, (M < 2 ? 2u : 5u)>(lo, hi, e);
-    constexpr uint32_t mask = (1u << D.endpoint_bits) - 1u, last = D.two ? 3u : 1u;
-    if constexpr (D.transformed) {
-#pragma unroll
-        for (uint32_t i = 1; i <= last; i++) {
-#pragma unroll
-            for (uint32_t c = 0; c < 3u; c++) {
-                const uint32_t sh = 32u - D.delta_bits[c];
-                e[3u * i + c] = (e[c] + (uint32_t)((int32_t)(e[3u * i + c] << sh) >> sh)) & mask;
-            }
-        }
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < 3u * (last + 1u); k++) e[k] = unquantize<D.endpoint_bits>(e[k]);
-}
 
 struct Bc6hCube {
     const uint4* face[6];

@@ -224,16 +224,21 @@ struct CubeTexelF16 {
         return load_h4(base + 4 * (((size_t)f * s + y) * s + x));
     }
 };
-// TextureCube.SampleLevel(LinearClamp, dir, lod): trilinear, lod clamped to [0, mips-1]
-template <class TexelT, bool DIV = false, class Ptr>
-__device__ __forceinline__ F4 cube_trilinear(Ptr data, uint32_t size, uint32_t mips, V3 dir, float lod) {
+// the two levels of a trilinear sample and the weight of the second: lod clamped to [0, mips-1]
+__device__ __forceinline__ void cube_lod_levels(uint32_t mips, float lod, uint32_t& l0, uint32_t& l1, float& f) {
     float maxl = (float)(mips - 1);
     lod = (lod == lod) ? lod : 0.0f;
     lod = snap8(fminf(fmaxf(lod, 0.0f), maxl));   // D3D12_MIP_LOD_FRACTIONAL_BIT_COUNT = 8
     float fl = floorf(lod);
-    uint32_t l0 = (uint32_t)fl;
-    uint32_t l1 = min(l0 + 1, mips - 1);
-    float f = lod - fl;
+    l0 = (uint32_t)fl;
+    l1 = min(l0 + 1, mips - 1);
+    f = lod - fl;
+}
+// TextureCube.SampleLevel(LinearClamp, dir, lod): trilinear, the levels of cube_lod_levels
+template <class TexelT, bool DIV = false, class Ptr>
+__device__ __forceinline__ F4 cube_trilinear(Ptr data, uint32_t size, uint32_t mips, V3 dir, float lod) {
+    uint32_t l0, l1; float f;
+    cube_lod_levels(mips, lod, l0, l1, f);
     TexelT t0{data + 4 * cube_mip_offset(size, l0), (int)(size >> l0)};
     F4 a = cube_bilinear<DIV>((int)(size >> l0), dir, t0);
     if (f == 0.0f || l1 == l0) return a;

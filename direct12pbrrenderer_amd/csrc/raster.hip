@@ -1,5 +1,6 @@
 // raster.hip — the passes and data formats either side of the shade, minus the rasterizer:
 //   k_skybox          skybox.hlsl:12-28         (SkyboxPass::Execute, DeferredPipeline.cpp:59-75)
+//   k_skybox_bc6h     the same pass on a sky resident as the cube-map file's BC6H_UF16 blocks, sampled in place (pbr_skybox_bc6h)
 //   k_gbuffer_encode  gbuffer.hlsl::ps_main :88-149  (GBufferPass::Execute, DeferredPipeline.cpp:138-185)
 //   k_rgbe_decode     Radiance .hdr texels -> fp32 (ResourceLoader::LoadHDRImageFile, ResourceLoader.cpp:381-406)
 // Both are streaming, HBM-bound kernels: one lane per pixel, rows contiguous across the wave.
@@ -7,10 +8,14 @@
 // cube addressing, the gamma/octahedral results feed UNORM8 rounding).
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
+#include "bc6h_decode_block.hpp"
 
 using namespace pbr;
 
 namespace {
+
+constexpr uint32_t BC6H_SKY_MAX_LEVELS = 14;    // floor(log2(PBR_BC6H_MAX_SIZE)) + 1
+static_assert((1u << (BC6H_SKY_MAX_LEVELS - 1)) == PBR_BC6H_MAX_SIZE, "levels of the largest cube");
 
 struct SkyParams {
     float InvView[9];
@@ -46,26 +51,34 @@ __device__ __forceinline__ void project_on_face(V3 d, uint32_t face, float& u, f
     v = tc / ma;
 }
 
+// One sky pixel, whatever form the cube is resident in: SAMPLE(d, lod) is TextureCube.SampleLevel(LinearClamp, d, lod).  A macro so
+// that both kernels hold this text once and k_skybox compiles to what it always did (as a function template it did not: its
+// argument loads were regrouped).
+#define PBR_SKYBOX_PIXEL(p, stencil, hdr, SAMPLE)                                                                   \
+    const uint32_t px = blockIdx.x * 64u + (threadIdx.x & 63u);                                                     \
+    const uint32_t py = blockIdx.y * 4u + (threadIdx.x >> 6);                                                       \
+    if (px >= p.w || py >= p.h) return;                                                                             \
+    if (stencil[(size_t)py * p.pitch + px] != 0) return;   /* geometry: the shade owns this pixel */                \
+    const float gx = (float)(p.x0 + px), gy = (float)(p.y0 + py);                                                   \
+    const V3 d = sky_ray(p, gx, gy);                                                                                \
+    uint32_t face; float fu, fv;                                                                                    \
+    cube_face_uv<true>(d, face, fu, fv);                                                                            \
+    float u0, v0, ux, vx, uy, vy;                                                                                   \
+    project_on_face(d, face, u0, v0);                                                                               \
+    project_on_face(sky_ray(p, gx + 1.0f, gy), face, ux, vx);                                                       \
+    project_on_face(sky_ray(p, gx, gy + 1.0f), face, uy, vy);                                                       \
+    const float half_size = 0.5f * (float)p.sky_size;                                                               \
+    const float rx = half_size * sqrtf((ux - u0) * (ux - u0) + (vx - v0) * (vx - v0));                              \
+    const float ry = half_size * sqrtf((uy - u0) * (uy - u0) + (vy - v0) * (vy - v0));                              \
+    const float lod = log2f(fmaxf(rx, ry));                                                                         \
+    const F4 c = SAMPLE(d, lod);                                                                                    \
+    store_h4(hdr + 4 * ((size_t)py * p.hdr_pitch + px), f4(c.x, c.y, c.z, 1.0f));
+
 __global__ __launch_bounds__(256) void k_skybox(SkyParams p, const float* __restrict__ sky,
                                                 const uint8_t* __restrict__ stencil, pbr_half* __restrict__ hdr) {
-    const uint32_t px = blockIdx.x * 64u + (threadIdx.x & 63u);
-    const uint32_t py = blockIdx.y * 4u + (threadIdx.x >> 6);
-    if (px >= p.w || py >= p.h) return;
-    if (stencil[(size_t)py * p.pitch + px] != 0) return;   // geometry: the shade owns this pixel
-    const float gx = (float)(p.x0 + px), gy = (float)(p.y0 + py);
-    const V3 d = sky_ray(p, gx, gy);
-    uint32_t face; float fu, fv;
-    cube_face_uv<true>(d, face, fu, fv);
-    float u0, v0, ux, vx, uy, vy;
-    project_on_face(d, face, u0, v0);
-    project_on_face(sky_ray(p, gx + 1.0f, gy), face, ux, vx);
-    project_on_face(sky_ray(p, gx, gy + 1.0f), face, uy, vy);
-    const float half_size = 0.5f * (float)p.sky_size;
-    const float rx = half_size * sqrtf((ux - u0) * (ux - u0) + (vx - v0) * (vx - v0));
-    const float ry = half_size * sqrtf((uy - u0) * (uy - u0) + (vy - v0) * (vy - v0));
-    const float lod = log2f(fmaxf(rx, ry));
-    const F4 c = cube_trilinear<CubeTexelF32, true>(sky, p.sky_size, p.sky_mips, d, lod);   // the oracle's divides (pbr_device.hpp)
-    store_h4(hdr + 4 * ((size_t)py * p.hdr_pitch + px), f4(c.x, c.y, c.z, 1.0f));
+#define PBR_SKY_F32(d, lod) cube_trilinear<CubeTexelF32, true>(sky, p.sky_size, p.sky_mips, d, lod)   // the oracle's divides (pbr_device.hpp)
+    PBR_SKYBOX_PIXEL(p, stencil, hdr, PBR_SKY_F32)
+#undef PBR_SKY_F32
 }
 
 // unorm8, decode_gamma, pack_normal: shared with the rasterizer's resolve (gbuffer_raster.hip)
@@ -95,6 +108,104 @@ __global__ __launch_bounds__(256) void k_rgbe_decode(const uint32_t* __restrict_
     }
 }
 
+// ---- the sky resident as the file's BC6H_UF16 blocks (pbr_skybox_bc6h) ----
+// Everything around the texel fetch is k_skybox's: the ray, the face, the LOD, cube_lod_levels, cube_face_uv<true>, bilinear_coord,
+// cube_fetch_seamless, bilerp and the level lerp of cube_trilinear.  A level's four taps lie in 1, 2 or 4 blocks of the centre face or,
+// at a seam, on another face: cube_fetch_seamless runs with a policy that hands back each tap's address (face, x, y) in place of its
+// colour, then every DISTINCT block among the four is read (one 16-byte load) and header-decoded once (bc6h_dec::header: the mode
+// switch, the delta transform, the unquantize) and serves all the taps that lie in it (bc6h_dec::texel: one index, one weight,
+// three interpolations).  The block loop and the level loop are not unrolled, so the kernel holds the fourteen mode headers once;
+// a wave runs every mode its lanes hold.  The block in flight is nine words, the taps' half codes twelve: static indices and
+// selects only, no private array, no LDS.
+struct SkyBc6h {
+    const uint4* face[6];
+    uint32_t face_first[BC6H_SKY_MAX_LEVELS];   // blocks of one face in front of the level
+};
+
+struct CubeTapAddress {     // the texel policy that returns where a tap landed: the bit patterns of face, x, y (moved, never computed with)
+    __device__ __forceinline__ F4 operator()(uint32_t f, int x, int y) const {
+        return f4(__uint_as_float(f), __int_as_float(x), __int_as_float(y), 0.0f);
+    }
+};
+
+__device__ __forceinline__ F4 bc6h_bilinear(const SkyBc6h& L, uint32_t ff, int s, V3 dir) {
+    uint32_t face; float u, v;
+    cube_face_uv<true>(dir, face, u, v);
+    const BilinearCoord cx = bilinear_coord(u, s), cy = bilinear_coord(v, s);
+    const CubeTapAddress where;
+    const F4 a00 = cube_fetch_seamless(s, face, cx.i0, cy.i0, where), a10 = cube_fetch_seamless(s, face, cx.i1, cy.i0, where);
+    const F4 a01 = cube_fetch_seamless(s, face, cx.i0, cy.i1, where), a11 = cube_fetch_seamless(s, face, cx.i1, cy.i1, where);
+    const uint32_t bw = max(1u, ((uint32_t)s + 3u) >> 2);
+    // a tap's block: face << 28 | its number in the level of that face (below 2048^2 = 2^22); its texel in the block
+    uint32_t key[4], tx[4], half[4][3];
+    const F4 addr[4] = {a00, a10, a01, a11};
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) {
+        const uint32_t f = __float_as_uint(addr[j].x), x = __float_as_uint(addr[j].y), y = __float_as_uint(addr[j].z);   // 0 <= x, y < s
+        key[j] = (f << 28) | ((y >> 2) * bw + (x >> 2));
+        tx[j] = 4u * (y & 3u) + (x & 3u);
+        half[j][0] = half[j][1] = half[j][2] = 0u;
+    }
+    uint32_t todo = 15u;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 4u; k++) {
+        if (!((todo >> k) & 1u)) continue;                     // tap k lay in a block an earlier tap read
+        const uint32_t kk = k == 0u ? key[0] : k == 1u ? key[1] : k == 2u ? key[2] : key[3];
+        const uint32_t f = kk >> 28;
+        const uint4* src = f == 0 ? L.face[0] : f == 1 ? L.face[1] : f == 2 ? L.face[2] : f == 3 ? L.face[3] : f == 4 ? L.face[4] : L.face[5];
+        const uint4 q = src[ff + (kk & 0x0fffffffu)];
+        const bc6h_dec::Block B = bc6h_dec::header(q.x, q.y, q.z, q.w);
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) {
+            if (((todo >> j) & 1u) && key[j] == kk) {
+                bc6h_dec::texel(B, tx[j], half[j]);
+                todo &= ~(1u << j);
+            }
+        }
+    }
+    F4 c[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++)
+        c[j] = f4(bc6h_dec::half_to_f32(half[j][0]), bc6h_dec::half_to_f32(half[j][1]), bc6h_dec::half_to_f32(half[j][2]), 1.0f);
+    return bilerp(c[0], c[1], c[2], c[3], cx.f, cy.f);
+}
+
+__device__ __forceinline__ F4 bc6h_trilinear(const SkyBc6h& L, uint32_t size, uint32_t mips, V3 d, float lod) {
+    uint32_t l0, l1; float f;
+    cube_lod_levels(mips, lod, l0, l1, f);
+    const bool one = f == 0.0f || l1 == l0;
+    F4 a = f4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+#pragma unroll 1
+    for (uint32_t i = 0; i < 2u; i++) {
+        const uint32_t l = i == 0u ? l0 : l1;
+        uint32_t ff = 0;
+#pragma unroll
+        for (uint32_t k = 1; k < BC6H_SKY_MAX_LEVELS; k++) ff = l >= k ? L.face_first[k] : ff;   // (static indices: the table stays in scalar registers)
+        const F4 c = bc6h_bilinear(L, ff, (int)(size >> l), d);
+        if (i == 0u) a = c; else b = c;
+        if (one) break;
+    }
+    return one ? a : fma4(b, f, a * (1.0f - f));
+}
+
+__global__ __launch_bounds__(256) void k_skybox_bc6h(SkyParams p, SkyBc6h sky, const uint8_t* __restrict__ stencil, pbr_half* __restrict__ hdr) {
+#define PBR_SKY_BC6H(d, lod) bc6h_trilinear(sky, p.sky_size, p.sky_mips, d, lod)
+    PBR_SKYBOX_PIXEL(p, stencil, hdr, PBR_SKY_BC6H)
+#undef PBR_SKY_BC6H
+}
+
+void fill_sky_params(SkyParams& p, const pbr_global* g, const pbr_tile* tile, uint32_t size, uint32_t mips, uint32_t pitch, uint32_t hdr_pitch) {
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) p.InvView[r * 3 + c] = g->InvView[r * 4 + c];
+    p.near_height = 2.0f * g->Near * tanf(g->Fov / 2.0f);
+    p.near_width = p.near_height * g->Ratio;
+    p.Near = g->Near;
+    p.full_w_f = (float)tile->full_w; p.full_h_f = (float)tile->full_h;
+    p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h;
+    p.sky_size = size; p.sky_mips = mips;
+    p.pitch = pitch; p.hdr_pitch = hdr_pitch;
+}
+
 }  // namespace
 
 extern "C" {
@@ -118,18 +229,36 @@ pbr_status pbr_skybox(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, c
                 "pbr_skybox: bad tile / pitch");
     PBR_REQUIRE(ctx, sky->size && sky->mips && (sky->size >> (sky->mips - 1)) >= 1, "pbr_skybox: bad cube");
     SkyParams p;
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) p.InvView[r * 3 + c] = g->InvView[r * 4 + c];
-    p.near_height = 2.0f * g->Near * tanf(g->Fov / 2.0f);
-    p.near_width = p.near_height * g->Ratio;
-    p.Near = g->Near;
-    p.full_w_f = (float)tile->full_w; p.full_h_f = (float)tile->full_h;
-    p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h;
-    p.sky_size = sky->size; p.sky_mips = sky->mips;
-    p.pitch = pitch; p.hdr_pitch = hdr_pitch;
+    fill_sky_params(p, g, tile, sky->size, sky->mips, pitch, hdr_pitch);
     dim3 grid((tile->w + 63) / 64, (tile->h + 3) / 4);
     hipLaunchKernelGGL(k_skybox, grid, dim3(256), 0, ctx->stream, p, sky->data, stencil, hdr);
     return pbr::launched(ctx, "k_skybox");
+}
+
+pbr_status pbr_skybox_bc6h(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_cube_bc6h* sky,
+                           const uint8_t* stencil, uint32_t pitch, pbr_half* hdr, uint32_t hdr_pitch) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, g && tile && sky && stencil && hdr, "pbr_skybox_bc6h: null pointer");
+    PBR_REQUIRE(ctx, tile->w && tile->h && tile->full_w && tile->full_h && pitch >= tile->w && hdr_pitch >= tile->w,
+                "pbr_skybox_bc6h: bad tile / pitch");
+    PBR_REQUIRE(ctx, pbr_bc6h_chain_bytes(sky->size, sky->mips) != 0,
+                "pbr_skybox_bc6h: size 0, not a multiple of 4 or above PBR_BC6H_MAX_SIZE, or mips 0 or above floor(log2(size)) + 1");
+    SkyBc6h L;
+    for (int f = 0; f < 6; f++) {
+        PBR_REQUIRE(ctx, sky->face_blocks[f], "pbr_skybox_bc6h: null face pointer");
+        PBR_REQUIRE(ctx, (pbr::addr(sky->face_blocks[f]) & 15u) == 0, "pbr_skybox_bc6h: face blocks not 16-byte aligned");
+        L.face[f] = static_cast<const uint4*>(sky->face_blocks[f]);
+    }
+    uint32_t nb = 0;                              // (the largest face chain holds 2048^2 * 4 / 3 blocks: below 2^28)
+    for (uint32_t l = 0; l < BC6H_SKY_MAX_LEVELS; l++) {
+        L.face_first[l] = nb;
+        if (l < sky->mips) { const uint32_t b = (((sky->size >> l) + 3u) / 4u) ? ((sky->size >> l) + 3u) / 4u : 1u; nb += b * b; }
+    }
+    SkyParams p;
+    fill_sky_params(p, g, tile, sky->size, sky->mips, pitch, hdr_pitch);
+    dim3 grid((tile->w + 63) / 64, (tile->h + 3) / 4);
+    hipLaunchKernelGGL(k_skybox_bc6h, grid, dim3(256), 0, ctx->stream, p, L, stencil, hdr);
+    return pbr::launched(ctx, "k_skybox_bc6h");
 }
 
 pbr_status pbr_gbuffer_encode(pbr_ctx* ctx, const float* m0, const float* m1, const float* m2,

@@ -57,6 +57,9 @@ SIGNATURES = {
     "pbrh_write_cubemap_file": (C.c_long, [C.POINTER(_vp * 6), _u32, _u32, _u32, _vp, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_set_skybox_file": (_int, [_vp, _vp, C.c_size_t, _int]),
     "pbrh_load_skybox_file": (_int, [_vp, C.c_char_p, _int]),
+    "pbrh_set_skybox_file_resident": (_int, [_vp, _vp, C.c_size_t, _int]),
+    "pbrh_load_skybox_file_resident": (_int, [_vp, C.c_char_p, _int]),
+    "pbrh_sky_resident_bytes": (C.c_size_t, [_vp]),
     "pbrh_import_texture": (C.c_long, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_import_cubemap": (C.c_long, [_vp, _vp, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_import_cubemap_dir": (C.c_long, [_vp, C.c_char_p, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
@@ -198,16 +201,23 @@ class HostRenderer:
         a = np.ascontiguousarray(cube_mip0[:4 * 6 * size * size], dtype=np.float32)
         self._check(self.lib.pbrh_set_skybox(self.h, a.ctypes.data, size))
 
-    def set_skybox_file(self, data, recompute_sh=False):
+    def set_skybox_file(self, data, recompute_sh=False, resident=False):
         """pbrh_set_skybox_file: the bytes of the reference's serialized sky cube are uploaded as they are and decoded on the GPU
         (pbr_bc6h_decode_cube) with the file's own levels; SkyBoxSH is the file's pack, or with recompute_sh the projection of the
-        decoded level 0."""
+        decoded level 0.  resident (pbrh_set_skybox_file_resident): the uploaded file stays the renderer's sky and the sky pass
+        samples its BC6H blocks in place — the same frames at 1 byte per sky texel instead of 16."""
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        self._check(self.lib.pbrh_set_skybox_file(self.h, buf.ctypes.data if buf.size else None, buf.size, 1 if recompute_sh else 0))
+        fn = self.lib.pbrh_set_skybox_file_resident if resident else self.lib.pbrh_set_skybox_file
+        self._check(fn(self.h, buf.ctypes.data if buf.size else None, buf.size, 1 if recompute_sh else 0))
 
-    def load_skybox_file(self, path, recompute_sh=False):
-        """set_skybox_file of a file on disk (pbrh_load_skybox_file)"""
-        self._check(self.lib.pbrh_load_skybox_file(self.h, os.fsencode(path), 1 if recompute_sh else 0))
+    def load_skybox_file(self, path, recompute_sh=False, resident=False):
+        """set_skybox_file of a file on disk (pbrh_load_skybox_file / pbrh_load_skybox_file_resident)"""
+        fn = self.lib.pbrh_load_skybox_file_resident if resident else self.lib.pbrh_load_skybox_file
+        self._check(fn(self.h, os.fsencode(path), 1 if recompute_sh else 0))
+
+    def sky_resident_bytes(self):
+        """pbrh_sky_resident_bytes: the device bytes the renderer holds for its sky (the decoded cube's or the resident file's)"""
+        return int(self.lib.pbrh_sky_resident_bytes(self.h))
 
     def set_lights(self, lights):
         p = pack_lights(lights)

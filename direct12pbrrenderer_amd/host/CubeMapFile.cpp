@@ -81,8 +81,28 @@ size_t WriteCubeMapFile(const void* const faces[6], uint32_t size, uint32_t mip_
     return total;
 }
 
-std::shared_ptr<SkyBox> SkyBoxFromCubeMapFile(pbr_ctx* ctx, const uint8_t* file, size_t bytes, bool recompute_sh) {
+// resident: the uploaded file IS the sky (SkyBox::Blocks); no decoded cube outlives this call
+static std::shared_ptr<SkyBox> ResidentSkyBox(pbr_ctx* ctx, const uint8_t* file, size_t bytes, const CubeMapFileInfo& info, bool recompute_sh) {
+    auto check = [&](pbr_status st) { if (st != PBR_OK) throw HipException(pbr_last_error(ctx)); };
+    auto sky = std::make_shared<SkyBox>();
+    sky->Blocks = std::make_shared<DeviceBc6hCube>(info.Size, info.MipLevels, file, bytes, info.FaceOffset);
+    sky->SH = info.SH;
+    if (recompute_sh) {             // the projection of the decoded level 0: one level into a transient cube
+        DeviceTexture2DArray level0(info.Size, 1, ETextureFormat_R32G32B32A32_FLOAT);
+        DeviceStructuredBuffer pack(112, 4);
+        const pbr_cube_bc6h b = sky->Blocks->Blocks();
+        check(pbr_bc6h_decode_cube(ctx, b.face_blocks, info.Size, 1, (float*)level0.DevicePtr()));
+        pbr_cube_f32 c{(const float*)level0.DevicePtr(), info.Size, 1};
+        check(pbr_sh9_project(ctx, &c, (float*)pack.DevicePtr()));
+        check(pbr_sync(ctx));       // `level0` is released on return
+        ThrowIfFailed(hipMemcpy(&sky->SH, pack.DevicePtr(), 112, hipMemcpyDeviceToHost), "read SH");
+    }
+    return sky;
+}
+
+std::shared_ptr<SkyBox> SkyBoxFromCubeMapFile(pbr_ctx* ctx, const uint8_t* file, size_t bytes, bool recompute_sh, bool resident) {
     const CubeMapFileInfo info = ParseCubeMapFile(file, bytes);
+    if (resident) return ResidentSkyBox(ctx, file, bytes, info, recompute_sh);
     auto check = [&](pbr_status st) { if (st != PBR_OK) throw HipException(pbr_last_error(ctx)); };
     DeviceMemory staged(bytes);     // (hipMalloc is 256-byte aligned, so every payload is 16-byte aligned on the device too)
     // (a blocking copy from pageable memory has landed when it returns: the context's stream needs no event to see it)
@@ -105,7 +125,7 @@ std::shared_ptr<SkyBox> SkyBoxFromCubeMapFile(pbr_ctx* ctx, const uint8_t* file,
     return sky;
 }
 
-std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, bool recompute_sh) {
+std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, bool recompute_sh, bool resident) {
     FILE* f = std::fopen(path.c_str(), "rb");
     if (!f) throw HipException("cube-map file: cannot open " + path);
     std::vector<uint8_t> data;
@@ -114,7 +134,7 @@ std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, b
     while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) data.insert(data.end(), buf, buf + n);
     std::fclose(f);
     try {
-        return SkyBoxFromCubeMapFile(ctx, data.data(), data.size(), recompute_sh);
+        return SkyBoxFromCubeMapFile(ctx, data.data(), data.size(), recompute_sh, resident);
     } catch (const HipException& e) {
         throw HipException(path + ": " + e.what());
     }

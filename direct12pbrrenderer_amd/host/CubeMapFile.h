@@ -49,9 +49,9 @@ size_t WriteCubeMapFile(const void* const faces[6], uint32_t size, uint32_t mip_
 // CubeMapResource's load (ResourceDef.cpp:187-219) on the GPU: the file is uploaded as it is, its six chains are decoded in place on
 // ctx into an fp32 RGBA cube with the file's own levels (pbr_bc6h_decode_cube), and the SH pack is the file's, as the reference takes
 // it (ResourceDef.cpp:211), or with recompute_sh pbr_sh9_project of the decoded level 0.  Blocks until the GPU is done.
-std::shared_ptr<SkyBox> SkyBoxFromCubeMapFile(pbr_ctx* ctx, const uint8_t* file, size_t bytes, bool recompute_sh);
+std::shared_ptr<SkyBox> SkyBoxFromCubeMapFile(pbr_ctx* ctx, const uint8_t* file, size_t bytes, bool recompute_sh, bool resident = false);
 // the same for a file on disk
-std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, bool recompute_sh);
+std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, bool recompute_sh, bool resident = false);
 
 
 // ResourceLoader::ImportCubeMap (ResourceLoader.cpp:279-299) on the GPU, from decoded faces on: level 0 — cube_mip0 (host, 6 x size^2

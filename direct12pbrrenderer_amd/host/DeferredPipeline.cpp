@@ -46,8 +46,20 @@ void PreFilterEnvMapPass::Execute(FGContext* context) {   // DeferredPipeline.cp
     SkyBox* sky = context->Scene->GetSkyBox();
     if (!sky) return;
     PIXScope(context->CommandList, "Precompute PrefilterEnvMap Pass");
+    // a sky resident as BC6H blocks is decoded into a cube that lives for this pass only (once per sky: the fence below is no frame cost)
+    DeviceTexture* source = sky->Resource();
+    std::unique_ptr<DeviceTexture2DArray> decoded;
+    if (auto* blocks = dynamic_cast<DeviceBc6hCube*>(source)) {
+        decoded = std::make_unique<DeviceTexture2DArray>(blocks->Size(), blocks->MipLevels(), ETextureFormat_R32G32B32A32_FLOAT);
+        context->CommandList->DecodeBc6hCube(blocks, decoded.get());
+        source = decoded.get();
+    }
+    struct Release {      // the commands that read `decoded` are done before it is freed, on every way out
+        HipCommandList* cl; bool wait;
+        ~Release() { if (wait) { try { cl->WaitIdle(); } catch (...) {} } }
+    } release{context->CommandList, decoded != nullptr};
     if (context->CommandList->FusedPasses()) {   // the five dispatches below as one call (same roughness ladder: mip / 4)
-        auto* cube = dynamic_cast<DeviceTexture2DArray*>(sky->Resource());
+        auto* cube = dynamic_cast<DeviceTexture2DArray*>(source);
         if (!cube) throw HipException("PreFilterEnvMapPass: the sky box is not a cube texture");
         context->CommandList->PrefilterEnv(cube, mPrefilterEnvMap.get());
         return;
@@ -56,7 +68,7 @@ void PreFilterEnvMapPass::Execute(FGContext* context) {   // DeferredPipeline.cp
         ShadingState& st = mShadingState[i];
         st.SetShader("env_map_gen.hlsl", true);
         st.SetRWTextureArray("PrefilterEnvMap", mPrefilterEnvMap.get());
-        st.SetTexture("SkyBox", sky->Resource());
+        st.SetTexture("SkyBox", source);
         st.SetConstantBuffer(PreFilterEnvMapConstant{(float)i / (float)(PreFilterEnvMapMipsLevel - 1), i, mSize});
     }
     for (uint32 i = 0; i < PreFilterEnvMapMipsLevel; i++) {

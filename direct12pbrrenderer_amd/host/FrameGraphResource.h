@@ -144,6 +144,30 @@ private:
     DeviceMemory mMem;
 };
 
+// A sky cube resident as the reference's cube-map file, uploaded as it is: six BC6H_UF16 chains (pbr_bc6h_chain_bytes each) at the
+// file's own offsets — 1 byte per texel where the decoded DeviceTexture2DArray holds 16.  The sky pass samples the blocks in place
+// (pbr_skybox_bc6h); the prefilter decodes into a transient cube.
+class DeviceBc6hCube : public DeviceTexture {
+public:
+    DeviceBc6hCube(uint32 size, uint32 mips, const void* file, size_t bytes, const size_t face_offset[6])
+        : mSize(size), mMips(mips), mMem(bytes) {     // (hipMalloc is 256-byte aligned, so every payload is 16-byte aligned on the device too)
+        for (int f = 0; f < 6; f++) mOffset[f] = face_offset[f];
+        if (DeviceMemory::DryRun()) return;
+        // (a blocking copy from pageable memory has landed when it returns: the context's stream needs no event to see it)
+        ThrowIfFailed(hipMemcpy(mMem.Ptr(), file, bytes, hipMemcpyHostToDevice), "upload cube-map file");
+    }
+    uint32 Size() const { return mSize; }
+    uint32 MipLevels() const { return mMips; }
+    const void* Face(int f) const { return (const uint8_t*)mMem.Ptr() + mOffset[f]; }
+    pbr_cube_bc6h Blocks() const { return pbr_cube_bc6h{{Face(0), Face(1), Face(2), Face(3), Face(4), Face(5)}, mSize, mMips}; }
+    void* DevicePtr() const override { return mMem.Ptr(); }
+    size_t Bytes() const override { return mMem.Bytes(); }
+private:
+    uint32 mSize, mMips;
+    size_t mOffset[6];
+    DeviceMemory mMem;
+};
+
 class DeviceStructuredBuffer : public IDeviceResource {
 public:
     DeviceStructuredBuffer(uint32 size, uint32 stride) : mSize(size), mStride(stride), mMem(size) {}

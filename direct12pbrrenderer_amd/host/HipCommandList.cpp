@@ -437,6 +437,14 @@ void HipCommandList::PrefilterEnv(DeviceTexture2DArray* sky, DeviceTexture2DArra
     mPaddedEnv.erase(out);   // the padded copy the shade samples is stale now
 }
 
+void HipCommandList::DecodeBc6hCube(DeviceBc6hCube* blocks, DeviceTexture2DArray* out) {
+    if (!blocks || !out || out->Size() != blocks->Size() || out->MipLevels() != blocks->MipLevels() || out->Format() != ETextureFormat_R32G32B32A32_FLOAT)
+        throw HipException("DecodeBc6hCube: an fp32 cube of the blocks' size and levels expected");
+    FlushPendingBloom();
+    const pbr_cube_bc6h b = blocks->Blocks();
+    Check(pbr_bc6h_decode_cube(mCtx, b.face_blocks, b.size, b.mips, (float*)out->DevicePtr()), "pbr_bc6h_decode_cube");
+}
+
 void HipCommandList::Clustered(DeviceStructuredBuffer* clusters, DeviceStructuredBuffer* point_lights, int32 num_lights) {
     if (!clusters || !point_lights) throw HipException("Clustered: null buffer");
     mDispatchCount++;
@@ -534,10 +542,15 @@ void HipCommandList::DrawMesh(ShadingState* s) {   // D3D12CommandList.cpp DrawM
     FlushPendingBloom();
     if (f != "skybox.hlsl") throw HipException("DrawMesh: " + std::string(f) + " is a raster shader without a kernel in this build");
     if (!mRenderTarget || !mDepthStencil) throw HipException("DrawMesh: render target / depth-stencil not bound (FrameGraph::PreparePass)");
-    auto* sky = dynamic_cast<DeviceTexture2DArray*>(s->Texture("SkyBox").Texture);
-    if (!sky) throw HipException("skybox: SkyBox is not bound to a cube texture");
     const uint32 w = mRenderTarget->Width(), h = mRenderTarget->Height();
     pbr_tile tile = mTile.w ? mTile : pbr_tile{0, 0, w, h, w, h};
+    if (auto* blocks = dynamic_cast<DeviceBc6hCube*>(s->Texture("SkyBox").Texture)) {   // the sky resident as the file's blocks: sampled in place
+        const pbr_cube_bc6h b = blocks->Blocks();
+        Check(pbr_skybox_bc6h(mCtx, &mGlobal, &tile, &b, mDepthStencil->StencilPlane(), w, (pbr_half*)mRenderTarget->DevicePtr(), w), "pbr_skybox_bc6h");
+        return;
+    }
+    auto* sky = dynamic_cast<DeviceTexture2DArray*>(s->Texture("SkyBox").Texture);
+    if (!sky) throw HipException("skybox: SkyBox is not bound to a cube texture");
     pbr_cube_f32 cube{(const float*)sky->DevicePtr(), sky->Size(), sky->MipLevels()};
     Check(pbr_skybox(mCtx, &mGlobal, &tile, &cube, mDepthStencil->StencilPlane(), w, (pbr_half*)mRenderTarget->DevicePtr(), w), "pbr_skybox");
 }

@@ -105,6 +105,8 @@ public:
     // roughness = mip / (mips - 1) for every mip of `out` — what the five constant buffers say; <= 1 fp16 ULP from the
     // dispatch-by-dispatch chain, 6-10 x faster (the per-dispatch kernel keeps the shader's sequential sum)
     void PrefilterEnv(DeviceTexture2DArray* sky, DeviceTexture2DArray* out);
+    // a resident BC6H sky -> the fp32 cube the prefilter takes (pbr_bc6h_decode_cube); a load-time transfer, not a dispatch of the graph
+    void DecodeBc6hCube(DeviceBc6hCube* blocks, DeviceTexture2DArray* out);
     // ClusteredPass::Execute's two dispatches (pbr_clustered)
     void Clustered(DeviceStructuredBuffer* clusters, DeviceStructuredBuffer* point_lights, int32 num_lights);
     // BloomPass::Execute's sixteen dispatches (pbr_bloom); mip_chain / temp are scratch afterwards.  With fused passes the

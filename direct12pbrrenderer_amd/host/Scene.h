@@ -86,11 +86,13 @@ protected:
 };
 
 // CubeMapResource stand-in: fp32 RGBA cube with mips + the SH pack computed at import time
-// (BasicStorage.cpp:201-209 -> SHBaker; here pbr_sh9_project on the GPU).
+// (BasicStorage.cpp:201-209 -> SHBaker; here pbr_sh9_project on the GPU).  Either Cube, or Blocks: the uploaded cube-map file
+// with its face offsets, which stays BC6H on the device (pbrh_set_skybox_file_resident).
 struct SkyBox {
     std::shared_ptr<DeviceTexture2DArray> Cube;
+    std::shared_ptr<DeviceBc6hCube> Blocks;
     pbr_sh_pack SH{};
-    DeviceTexture2DArray* Resource() const { return Cube.get(); }
+    DeviceTexture* Resource() const { return Blocks ? static_cast<DeviceTexture*>(Blocks.get()) : Cube.get(); }
     const pbr_sh_pack& GetSHCoefficients() const { return SH; }
 };
 

@@ -152,6 +152,26 @@ int pbrh_load_skybox_file(pbrh_renderer* r, const char* path, int recompute_sh) 
     });
 }
 
+int pbrh_set_skybox_file_resident(pbrh_renderer* r, const uint8_t* file, size_t bytes, int recompute_sh) {
+    return guarded(r, [&] {
+        r->scene->SetSkyBox(SkyBoxFromCubeMapFile(r->scheduler->CommandList()->Context(), file, bytes, recompute_sh != 0, true));
+        r->pipeline->mPrefilterEnvMapPass->Invalidate();
+    });
+}
+
+int pbrh_load_skybox_file_resident(pbrh_renderer* r, const char* path, int recompute_sh) {
+    return guarded(r, [&] {
+        if (!path) throw HipException("pbrh_load_skybox_file_resident: null path");
+        r->scene->SetSkyBox(LoadCubeMapFile(r->scheduler->CommandList()->Context(), path, recompute_sh != 0, true));
+        r->pipeline->mPrefilterEnvMapPass->Invalidate();
+    });
+}
+
+size_t pbrh_sky_resident_bytes(const pbrh_renderer* r) {
+    if (!r || !r->scene || !r->scene->GetSkyBox() || !r->scene->GetSkyBox()->Resource()) return 0;
+    return r->scene->GetSkyBox()->Resource()->Bytes();
+}
+
 int pbrh_parse_cubemap_file(const uint8_t* file, size_t bytes, uint32_t* size, uint32_t* mips, size_t face_offsets[6], float sh_pack[28],
                             char* err, size_t err_len) {
     try {

@@ -52,6 +52,13 @@ int pbrh_load_skybox(pbrh_renderer* r, const char* dir);
  * level 0 instead.  pbrh_load_skybox_file reads the file from disk first. */
 int pbrh_set_skybox_file(pbrh_renderer* r, const uint8_t* file, size_t bytes, int recompute_sh);
 int pbrh_load_skybox_file(pbrh_renderer* r, const char* path, int recompute_sh);
+/* The same file kept RESIDENT: the uploaded bytes are the renderer's sky, the sky pass samples their BC6H blocks in place
+ * (pbr_skybox_bc6h) and writes the bits it writes from the decoded cube.  No 16-byte-per-texel cube outlives a call: the prefilter pass
+ * decodes into a buffer it releases once its commands are done (once per sky), recompute_sh decodes level 0 into a transient one. */
+int pbrh_set_skybox_file_resident(pbrh_renderer* r, const uint8_t* file, size_t bytes, int recompute_sh);
+int pbrh_load_skybox_file_resident(pbrh_renderer* r, const char* path, int recompute_sh);
+/* the device bytes the renderer holds for its sky: the decoded cube's (16 * pbr_cube_texels) or the resident file's; 0 without a sky */
+size_t pbrh_sky_resident_bytes(const pbrh_renderer* r);
 /* CPU only, stateless: a serialized CubeMapTextureData (ReflectionDef.h:81-84) held in memory: six faces, each TextureInfo (uint16
  * width, height, depth, mips; uint8 DXGI format; 3 pad bytes), a uint32 payload byte count and the payload (the face's mip chain
  * as BC6H_UF16 blocks: pbr_bc6h_chain_bytes), then SH2CoefficientsPack as 28 floats in pbr_sh_pack's order.  Fills *size, *mips,

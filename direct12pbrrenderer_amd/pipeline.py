@@ -256,6 +256,19 @@ class HaloTransport:
         ctx.halo_pack(a1, pitch, rows, fr.halo_peers, fr.halo_n, fr.halo_staging, unpack=True)
 
 
+class ResidentSky:
+    """A sky cube kept as the reference's cube-map file on the device: `staged` is the uploaded file (kept alive here), `faces` the
+    six addresses of its BC6H_UF16 chains in it (px .. nz).  The sky pass samples the blocks in place (PbrContext.skybox_bc6h); the
+    load-time consumers (prefilter_env, sh9_project) take decode()'s transient fp32 cube."""
+
+    def __init__(self, staged, faces, size, mips):
+        self.staged, self.faces, self.size, self.mips = staged, [int(f) for f in faces], int(size), int(mips)
+
+    def decode(self, ctx):
+        """-> a freshly decoded fp32 cube chain (PbrContext.bc6h_decode_cube) that the caller owns"""
+        return ctx.bc6h_decode_cube(self.faces, self.size, self.mips)
+
+
 class DeferredFrame:
     """Owns the device buffers of one rank and runs the per-frame passes through the C ABI."""
 
@@ -386,15 +399,19 @@ class DeferredFrame:
         else:
             self.ctx.gbuffer_raster(*args)
 
-    def set_sky_file(self, data, recompute_sh=False):
+    def set_sky_file(self, data, recompute_sh=False, resident=False):
         """The sky from the bytes of the reference's serialized sky cube (host.parse_cubemap_file): the file is uploaded as it is, its
         six BC6H_UF16 chains are decoded on the GPU (PbrContext.bc6h_decode_cube) into the cube the sky pass samples, with the file's
         own levels, and g.SkyBoxSH becomes the file's SH pack (recompute_sh: the projection of the decoded level 0).  The env chain
-        the frame was built with is not touched: prefilter it from self.sky when it should follow.  Returns the 28 floats."""
+        the frame was built with is not touched: prefilter it from sky_cube() when it should follow.  Returns the 28 floats.
+        resident: the uploaded file stays alive and IS the sky (self.sky: a ResidentSky, the six addresses into it); skybox() samples
+        its blocks in place (PbrContext.skybox_bc6h) to the same bits, at 1 byte per texel instead of 16.  No decoded cube outlives
+        this call: recompute_sh decodes into a transient cube, projects and releases it."""
         from . import host
         size, mips, offsets, sh = host.parse_cubemap_file(data)
         staged = self.ctx.upload(np.frombuffer(bytes(data), dtype=np.uint8).copy())
-        cube = self.ctx.bc6h_decode_cube([staged.data_ptr() + o for o in offsets], size, mips)
+        sky = ResidentSky(staged, [staged.data_ptr() + o for o in offsets], size, mips)
+        cube = None if resident and not recompute_sh else sky.decode(self.ctx)
         if recompute_sh:
             pack = self.ctx.sh9_project(cube, size, mips)
             self.ctx.sync()
@@ -402,8 +419,15 @@ class DeferredFrame:
         else:
             self.ctx.sync()             # `staged` may be released on return
         C.memmove(C.addressof(self.g.SkyBoxSH), np.ascontiguousarray(sh, dtype=np.float32).ctypes.data, 112)
-        self.sky = (cube, size, mips)
+        self.sky = sky if resident else (cube, size, mips)
         return sh
+
+    def sky_cube(self):
+        """-> (cube, size, mips): the sky as the fp32 cube chain prefilter_env and sh9_project take.  Of a resident sky a freshly
+        decoded cube that the caller owns (nothing here keeps it alive); otherwise the frame's own."""
+        if isinstance(self.sky, ResidentSky):
+            return self.sky.decode(self.ctx), self.sky.size, self.sky.mips
+        return self.sky
 
     def set_prev_luminance(self, v):
         self.avg.fill_(float(v))
@@ -421,6 +445,9 @@ class DeferredFrame:
 
     def skybox(self):
         s = self.spec
+        if isinstance(self.sky, ResidentSky):
+            self.ctx.skybox_bc6h(self.g, self.tile, self.sky.faces, self.sky.size, self.sky.mips, self.gb["stencil"], s.sw, self.hdr, s.sw)
+            return
         cube, size, mips = self.sky
         self.ctx.skybox(self.g, self.tile, cube, size, mips, self.gb["stencil"], s.sw, self.hdr, s.sw)
 
@@ -652,7 +679,7 @@ class MultiViewFrame:
 
     def __init__(self, ctx: PbrContext, w, h, globals, lights_per_view, lut, lut_res, env, env_size, env_mips=ENV_MIPS, sky=None):
         """globals: one Global per view; lights_per_view: one LIGHT_DTYPE array per view; env: the plain prefiltered chain (padded
-        here once); sky: optional (cube tensor, size, mips), resolved per view on stencil == 0 pixels before the shade."""
+        here once); sky: optional (cube tensor, size, mips) or a ResidentSky (a DeferredFrame's after set_sky_file(resident=True)), resolved per view on stencil == 0 pixels before the shade."""
         if len(globals) != len(lights_per_view) or not globals:
             raise ValueError("one Global and one light array per view")
         self.ctx, self.w, self.h, self.n = ctx, int(w), int(h), len(globals)
@@ -724,6 +751,11 @@ class MultiViewFrame:
 
     def skybox(self):
         """the sky resolve stays one launch per view"""
+        if isinstance(self.sky, ResidentSky):
+            for v in range(self.n):
+                self.ctx.skybox_bc6h(self.globals[v], self.tile, self.sky.faces, self.sky.size, self.sky.mips, self.gb[v]["stencil"], self.w,
+                                     self.hdrs[v], self.w)
+            return
         cube, size, mips = self.sky
         for v in range(self.n):
             self.ctx.skybox(self.globals[v], self.tile, cube, size, mips, self.gb[v]["stencil"], self.w, self.hdrs[v], self.w)

@@ -183,6 +183,10 @@ class CubeF32(C.Structure):
     _fields_ = [("data", C.c_void_p), ("size", C.c_uint32), ("mips", C.c_uint32)]
 
 
+class CubeBc6h(C.Structure):                          # pbr_cube_bc6h: six DEVICE pointers to BC6H_UF16 chains, order px .. nz
+    _fields_ = [("face_blocks", C.c_void_p * 6), ("size", C.c_uint32), ("mips", C.c_uint32)]
+
+
 # PointLight, DeferredPipeline.h:341-347 (44 B)
 LIGHT_DTYPE = np.dtype([
     ("Position", np.float32, 3), ("Color", np.float32, 3), ("Intensity", np.float32),

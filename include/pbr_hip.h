@@ -439,6 +439,18 @@ pbr_status pbr_deferred_shade_f32(pbr_ctx* ctx, const pbr_global* g, const pbr_t
  * log2 of the larger forward-difference footprint (in mip-0 texels) of the ray on the centre pixel's face. */
 pbr_status pbr_skybox(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_cube_f32* sky,
                       const uint8_t* stencil, uint32_t pitch, pbr_half* hdr, uint32_t hdr_pitch);
+/* The same pass on a sky that stays resident as the file's BC6H_UF16 blocks (1 byte per texel instead of the 16 of pbr_cube_f32): the
+ * blocks are sampled in place, each texel decoded by the rule pinned at pbr_bc6h_decode_cube.  face_blocks: six DEVICE pointers,
+ * 16-byte aligned, one chain of pbr_bc6h_chain_bytes(size, mips) bytes each, order px, nx, py, ny, pz, nz — the addresses
+ * pbr_bc6h_decode_cube takes, e.g. the payloads of a cube-map file uploaded as it is.
+ * The HDR target is bit-identical to pbr_skybox on the cube pbr_bc6h_decode_cube makes of the same chains; pixels with stencil != 0
+ * are untouched.  One asynchronous launch on the context's stream, no allocation, no host synchronisation.
+ * Refusals (PBR_ERR_INVALID, nothing enqueued): those of pbr_skybox (a null pointer, an empty tile, pitch or hdr_pitch below the
+ * tile's width) and those of pbr_bc6h_decode_cube on the chains: a null or non-16-byte-aligned face, size 0, not a multiple of 4 or
+ * above PBR_BC6H_MAX_SIZE, mips 0 or above floor(log2(size)) + 1. */
+typedef struct pbr_cube_bc6h { const void* face_blocks[6]; uint32_t size, mips; } pbr_cube_bc6h;   /* DEVICE pointers, order px … nz */
+pbr_status pbr_skybox_bc6h(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_cube_bc6h* sky,
+                           const uint8_t* stencil, uint32_t pitch, pbr_half* hdr, uint32_t hdr_pitch);
 
 /* gbuffer.hlsl::ps_main :88-149 without the rasterizer / texture fetches: per-pixel material attributes ->
  * G-buffer planes.  m0 = (albedo.rgb as authored (gamma space), emission), m1 = (normal_ws.xyz, roughness),
