@@ -32,6 +32,24 @@ def _ptr(t):
     return C.c_void_p(int(t))
 
 
+def _bc6h_faces(who, faces, size, mip_levels):
+    """the six face chains of a BC6H cube (device tensors of structs.bc6h_chain_bytes each, or device addresses) as a pointer array;
+    a description the library refuses is left to the library"""
+    faces = list(faces)
+    if len(faces) != 6:
+        raise PbrError(f"{who}: six faces, got {len(faces)}")
+    nbytes = bc6h_chain_bytes(size, mip_levels)
+    for f in faces:
+        if isinstance(f, torch.Tensor) and nbytes and f.numel() * f.element_size() != nbytes:
+            raise PbrError(f"{who}: a face of {f.numel() * f.element_size()} bytes, {size}^2 x {mip_levels} levels takes {nbytes}")
+    return (C.c_void_p * 6)(*[_ptr(f) for f in faces])
+
+
+def _gbuffer(gb, pitch):
+    """pbr_gbuffer of a dict with the device tensors A, B, C, depth, stencil"""
+    return GBuffer(gb["A"].data_ptr(), gb["B"].data_ptr(), gb["C"].data_ptr(), gb["depth"].data_ptr(), gb["stencil"].data_ptr(), pitch)
+
+
 class PbrContext:
     """One context per device per host thread (pbr_ctx is not thread-safe)."""
 
@@ -180,16 +198,9 @@ class PbrContext:
         """pbr_bc6h_decode_cube: the six BC6H_UF16 face chains of a sky asset -> the fp32 RGBA cube chain every consumer takes
         (float32 [cube_texels(size, mip_levels), 4], alpha 1).  faces: six device tensors (uint8, structs.bc6h_chain_bytes each) or
         six device addresses (e.g. into one uploaded file, at host.parse_cubemap_file's offsets), in the order px, nx, py, ny, pz, nz."""
-        faces = list(faces)
-        if len(faces) != 6:
-            raise PbrError(f"bc6h_decode_cube: six faces, got {len(faces)}")
-        nbytes = bc6h_chain_bytes(size, mip_levels)
-        for f in faces:
-            if isinstance(f, torch.Tensor) and nbytes and f.numel() * f.element_size() != nbytes:
-                raise PbrError(f"bc6h_decode_cube: a face of {f.numel() * f.element_size()} bytes, {size}^2 x {mip_levels} levels takes {nbytes}")
-        ptrs = (C.c_void_p * 6)(*[_ptr(f) for f in faces])
+        ptrs = _bc6h_faces("bc6h_decode_cube", faces, size, mip_levels)
         if out is None:
-            if not nbytes:
+            if not bc6h_chain_bytes(size, mip_levels):
                 raise PbrError(f"bad BC6H cube description: {size}^2, {mip_levels} levels")
             out = self.empty((cube_texels(size, mip_levels), 4), torch.float32)
         self._check(self.lib.pbr_bc6h_decode_cube(self.h, C.byref(ptrs), int(size), int(mip_levels), _ptr(out)))
@@ -208,12 +219,7 @@ class PbrContext:
                 raise PbrError(f"bad BC6H cube description: {size}^2, {mip_levels} levels")
             out = [self.empty((nbytes,), torch.uint8) for _ in range(6)]
         out = list(out)
-        if len(out) != 6:
-            raise PbrError(f"bc6h_encode_cube: six faces, got {len(out)}")
-        for f in out:
-            if isinstance(f, torch.Tensor) and nbytes and f.numel() * f.element_size() != nbytes:
-                raise PbrError(f"bc6h_encode_cube: a face of {f.numel() * f.element_size()} bytes, {size}^2 x {mip_levels} levels takes {nbytes}")
-        ptrs = (C.c_void_p * 6)(*[_ptr(f) for f in out])
+        ptrs = _bc6h_faces("bc6h_encode_cube", out, size, mip_levels)
         self._check(self.lib.pbr_bc6h_encode_cube(self.h, _ptr(cube), int(size), int(mip_levels), C.byref(ptrs)))
         return out
 
@@ -258,8 +264,7 @@ class PbrContext:
     def deferred_shade(self, g: Global, tile: Tile, gb, pitch, lut, lut_res, env, env_size, env_mips,
                        clusters, lights, num_lights, hdr, hdr_pitch):
         """gb: dict with device tensors A,B,C,depth,stencil; env: the PADDED chain from env_pad()."""
-        s = GBuffer(gb["A"].data_ptr(), gb["B"].data_ptr(), gb["C"].data_ptr(), gb["depth"].data_ptr(),
-                    gb["stencil"].data_ptr(), pitch)
+        s = _gbuffer(gb, pitch)
         self._check(self.lib.pbr_deferred_shade(self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut), lut_res,
                                                 _ptr(env), env_size, env_mips, _ptr(clusters), _ptr(lights),
                                                 int(num_lights), _ptr(hdr), hdr_pitch))
@@ -274,8 +279,7 @@ class PbrContext:
     def deferred_shade_rects(self, g: Global, tile: Tile, gb, pitch, lut, lut_res, env, env_size, env_mips,
                              clusters, lights, num_lights, hdr, hdr_pitch, rects):
         """deferred_shade on up to 5 rectangles (tile-local x, y, w, h) of the tile in one launch."""
-        s = GBuffer(gb["A"].data_ptr(), gb["B"].data_ptr(), gb["C"].data_ptr(), gb["depth"].data_ptr(),
-                    gb["stencil"].data_ptr(), pitch)
+        s = _gbuffer(gb, pitch)
         arr = self._rects(rects)
         self._check(self.lib.pbr_deferred_shade_rects(self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut), lut_res,
                                                       _ptr(env), env_size, env_mips, _ptr(clusters), _ptr(lights),
@@ -291,8 +295,7 @@ class PbrContext:
     def deferred_shade_folded(self, g: Global, tile: Tile, gb, pitch, lut_fold, lut_res, env, env_size, env_mips,
                               clusters, lights, num_lights, hdr, hdr_pitch, rects=None):
         """deferred_shade (rects: deferred_shade_rects) with the LUT read from lut_fold_x()'s table: the same bits, fewer instructions."""
-        s = GBuffer(gb["A"].data_ptr(), gb["B"].data_ptr(), gb["C"].data_ptr(), gb["depth"].data_ptr(),
-                    gb["stencil"].data_ptr(), pitch)
+        s = _gbuffer(gb, pitch)
         head = (self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut_fold), lut_res, _ptr(env), env_size, env_mips,
                 _ptr(clusters), _ptr(lights), int(num_lights), _ptr(hdr), hdr_pitch)
         if rects is None:
@@ -319,8 +322,7 @@ class PbrContext:
     def deferred_shade_tabled(self, g: Global, tile: Tile, gb, pitch, lut_fold, lut_res, env, env_size, env_mips,
                               clusters, lights, num_lights, hdr, hdr_pitch, tables: ShadeTables, rects=None):
         """deferred_shade_folded whose blocks read their prologue from the shade tables (both halves built for this tile and light count)."""
-        s = GBuffer(gb["A"].data_ptr(), gb["B"].data_ptr(), gb["C"].data_ptr(), gb["depth"].data_ptr(),
-                    gb["stencil"].data_ptr(), pitch)
+        s = _gbuffer(gb, pitch)
         head = (self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut_fold), lut_res, _ptr(env), env_size, env_mips,
                 _ptr(clusters), _ptr(lights), int(num_lights), _ptr(hdr), hdr_pitch)
         if rects is None:
@@ -332,8 +334,7 @@ class PbrContext:
     def deferred_shade_f32(self, g: Global, tile: Tile, gb, pitch, lut, lut_res, env, env_size, env_mips,
                            clusters, lights, num_lights, hdr_f32, hdr_pitch):
         """Parity probe: deferred_shade with a float32 [h, w, 4] output (the colour before the fp16 store)."""
-        s = GBuffer(gb["A"].data_ptr(), gb["B"].data_ptr(), gb["C"].data_ptr(), gb["depth"].data_ptr(),
-                    gb["stencil"].data_ptr(), pitch)
+        s = _gbuffer(gb, pitch)
         self._check(self.lib.pbr_deferred_shade_f32(self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut), lut_res,
                                                     _ptr(env), env_size, env_mips, _ptr(clusters), _ptr(lights),
                                                     int(num_lights), _ptr(hdr_f32), hdr_pitch))
@@ -352,13 +353,7 @@ class PbrContext:
         """pbr_skybox_bc6h: the sky pass on a cube that stays resident as BC6H_UF16 blocks, sampled in place — the bits skybox() writes
         from the cube bc6h_decode_cube makes of the same chains.  faces: six device tensors (uint8, structs.bc6h_chain_bytes each) or
         six device addresses (16-byte aligned), in the order px, nx, py, ny, pz, nz."""
-        if len(faces) != 6:
-            raise PbrError(f"skybox_bc6h: six faces, got {len(faces)}")
-        nbytes = bc6h_chain_bytes(size, mip_levels)
-        for f in faces:
-            if torch.is_tensor(f) and (not nbytes or f.numel() * f.element_size() != nbytes):
-                raise PbrError(f"skybox_bc6h: a face of {f.numel() * f.element_size()} bytes, {size}^2 x {mip_levels} levels takes {nbytes}")
-        c = CubeBc6h((C.c_void_p * 6)(*[f.data_ptr() if torch.is_tensor(f) else int(f) for f in faces]), int(size), int(mip_levels))
+        c = CubeBc6h(_bc6h_faces("skybox_bc6h", faces, size, mip_levels), int(size), int(mip_levels))
         self._check(self.lib.pbr_skybox_bc6h(self.h, C.byref(g), C.byref(tile), C.byref(c), _ptr(stencil), pitch,
                                              _ptr(hdr), hdr_pitch))
 

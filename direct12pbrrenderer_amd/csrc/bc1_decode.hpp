@@ -1,13 +1,11 @@
 // bc1_decode.hpp — the BC1 block decode pinned in include/pbr_hip.h (PBR_TEX_BC1_BLOCKS), shared by the textured raster's sampler
-// (BC1-resident textures, read in place) and the bulk decoder (pbr_bc1_decode), both in gbuffer_raster.hip.
+// (BC1-resident textures, read in place: gbuffer_raster.hip) and, in texture2d.hip, the bulk decoder (pbr_bc1_decode) and the encoder's
+// fit (pbr_bc1_encode).  The block decode only: where a block lies in a chain is tex_chain.hpp's.
 // A block is 8 bytes, read as two little-endian words: `endpoints` = c0 | c1 << 16 (RGB565 each) and `bits` = 16 2-bit palette
 // indices, texel (x, y) of the block at bit 2 (4 y + x).  A palette entry is R | G << 8 | B << 16 | A << 24 whatever the stored
 // format: the callers swizzle (the sampler when it picks channels, the bulk decoder when it stores).
 // tests/bc1_ref.py restates the rule in numpy, independently of this file.
 #pragma once
-
-// blocks across (or down) a level of n texels: at least one
-__host__ __device__ inline uint32_t bc1_blocks(uint32_t n) { return n > 4u ? (n + 3u) >> 2 : 1u; }
 
 // an RGB565 endpoint's channels expanded to 8 bits by bit replication
 __device__ __forceinline__ void bc1_expand565(uint32_t c, uint32_t& r, uint32_t& g, uint32_t& b) {

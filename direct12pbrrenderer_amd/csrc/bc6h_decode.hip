@@ -16,22 +16,14 @@
 
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
-#include "bc6h_decode_block.hpp"     // the mode tables, read_header / endpoints<M>, PARTITION, the anchor and weight constants
+#include "tex_chain.hpp"
+#include "bc6h_decode_block.hpp"     // the mode switch, the per-texel weight and the partition tables, shared with the in-place sky resolve
 
 namespace {
 
 using namespace bc6h_dec;
 
-constexpr uint32_t BC6H_MAX_LEVELS = 14;    // floor(log2(PBR_BC6H_MAX_SIZE)) + 1
-static_assert((1u << (BC6H_MAX_LEVELS - 1)) == PBR_BC6H_MAX_SIZE, "levels of the largest cube");
-
-struct Bc6hCube {
-    const uint4* face[6];
-    uint32_t face_first[BC6H_MAX_LEVELS + 1];   // blocks of one face in front of the level; [mips] = one face's blocks
-    uint32_t first_texel[BC6H_MAX_LEVELS];      // pbr_cube_mip_offset of the level
-    uint32_t size, mips;
-    uint32_t lanes;                             // 6 x one face's blocks
-};
+using Bc6hCube = bc6h_chain::Cube<const uint4*>;
 
 // lane = block; the lanes of a level are face after face, the face's blocks row-major
 __global__ __launch_bounds__(256) void k_bc6h_decode_cube(Bc6hCube L, float4* __restrict__ out) {
@@ -39,7 +31,7 @@ __global__ __launch_bounds__(256) void k_bc6h_decode_cube(Bc6hCube L, float4* __
     if (g >= L.lanes) return;
     uint32_t l = 0, ff = 0, ft = 0;
 #pragma unroll
-    for (uint32_t k = 1; k < BC6H_MAX_LEVELS; k++) {          // (static indices: the table stays in scalar registers)
+    for (uint32_t k = 1; k < bc6h_chain::MAX_LEVELS; k++) {          // (static indices: the table stays in scalar registers)
         if (k < L.mips && g >= 6u * L.face_first[k]) { l = k; ff = L.face_first[k]; ft = L.first_texel[k]; }
     }
     const uint32_t s = L.size >> l, bw = max(1u, (s + 3u) >> 2), nb = bw * bw;
@@ -49,39 +41,17 @@ __global__ __launch_bounds__(256) void k_bc6h_decode_cube(Bc6hCube L, float4* __
     const uint64_t lo = q.x | ((uint64_t)q.y << 32), hi = q.z | ((uint64_t)q.w << 32);
 
     uint32_t e[12] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    const uint32_t mode = (q.x & 2u) ? q.x & 31u : q.x & 3u;
-    bool two = false;
-    switch (mode) {
-        case 0x00: endpoints<0x00>(lo, hi, e); two = true; break;
-        case 0x01: endpoints<0x01>(lo, hi, e); two = true; break;
-        case 0x02: endpoints<0x02>(lo, hi, e); two = true; break;
-        case 0x06: endpoints<0x06>(lo, hi, e); two = true; break;
-        case 0x0a: endpoints<0x0a>(lo, hi, e); two = true; break;
-        case 0x0e: endpoints<0x0e>(lo, hi, e); two = true; break;
-        case 0x12: endpoints<0x12>(lo, hi, e); two = true; break;
-        case 0x16: endpoints<0x16>(lo, hi, e); two = true; break;
-        case 0x1a: endpoints<0x1a>(lo, hi, e); two = true; break;
-        case 0x1e: endpoints<0x1e>(lo, hi, e); two = true; break;
-        case 0x03: endpoints<0x03>(lo, hi, e); break;
-        case 0x07: endpoints<0x07>(lo, hi, e); break;
-        case 0x0b: endpoints<0x0b>(lo, hi, e); break;
-        case 0x0f: endpoints<0x0f>(lo, hi, e); break;
-        default: break;                                       // 0x13, 0x17, 0x1b, 0x1f are reserved: every endpoint 0, rgb = 0
-    }
-
-    // indices: 3 bits from block bit 82 (two regions) or 4 bits from bit 65, an anchor texel one bit fewer; all in `hi`
+    const bool two = mode_endpoints(lo, hi, e);
+    // (the three lines of bc6h_dec::header(), kept here as text: from a shared function, by reference or by value, both this kernel's
+    // and k_skybox_bc6h's instruction streams came out different)
     const uint32_t shape = (uint32_t)(hi >> 13) & 31u;        // bits 77 .. 81
     const uint32_t pattern = two ? (uint32_t)PARTITION[shape] : 0u;
     const uint32_t anchor = !two ? 16u : shape < 16u ? 15u : (uint32_t)(ANCHOR_16_31 >> (4u * (shape - 16u))) & 15u;
-    const uint32_t ib = two ? 3u : 4u, base = two ? 18u : 1u;
     float4* dst = out + ft + ((size_t)f * s + 4u * by) * s + 4u * bx;
 #pragma unroll
     for (uint32_t t = 0; t < 16u; t++) {
         const uint32_t x = t & 3u, y = t >> 2;
-        const uint32_t start = base + ib * t - (t > 0u ? 1u : 0u) - (t > anchor ? 1u : 0u);
-        const uint32_t width = ib - ((t == 0u || t == anchor) ? 1u : 0u);
-        const uint32_t idx = (uint32_t)(hi >> start) & ((1u << width) - 1u);
-        const uint32_t w = (uint32_t)((two ? WEIGHTS3 : idx < 8u ? WEIGHTS4_LO : WEIGHTS4_HI) >> (8u * (idx & 7u))) & 255u;
+        const uint32_t w = texel_weight(hi, two, anchor, t);
         const bool second = (pattern >> t) & 1u;
         float c[3];
 #pragma unroll
@@ -95,47 +65,21 @@ __global__ __launch_bounds__(256) void k_bc6h_decode_cube(Bc6hCube L, float4* __
     }
 }
 
-uint32_t max_levels(uint32_t size) {
-    uint32_t n = 0;
-    while (size) { n++; size >>= 1; }
-    return n;
-}
-uint32_t level_blocks(uint32_t s) { const uint32_t b = (s + 3u) / 4u; return b ? b : 1u; }
-bool chain_ok(uint32_t size, uint32_t mip_levels) {
-    return size >= 4u && size <= PBR_BC6H_MAX_SIZE && (size & 3u) == 0 && mip_levels >= 1u && mip_levels <= max_levels(size);
-}
-
 }  // namespace
 
 extern "C" {
 
-size_t pbr_bc6h_chain_bytes(uint32_t size, uint32_t mip_levels) {
-    if (!chain_ok(size, mip_levels)) return 0;
-    size_t blocks = 0;
-    for (uint32_t l = 0; l < mip_levels; l++) blocks += (size_t)level_blocks(size >> l) * level_blocks(size >> l);
-    return 16u * blocks;
-}
+size_t pbr_bc6h_chain_bytes(uint32_t size, uint32_t mip_levels) { return bc6h_chain::chain_bytes(size, mip_levels); }
 
 pbr_status pbr_bc6h_decode_cube(pbr_ctx* ctx, const void* const face_blocks[6], uint32_t size, uint32_t mip_levels, float* out_rgba) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, face_blocks && out_rgba, "pbr_bc6h_decode_cube: null pointer");
-    PBR_REQUIRE(ctx, chain_ok(size, mip_levels),
-                "pbr_bc6h_decode_cube: size 0, not a multiple of 4 or above PBR_BC6H_MAX_SIZE, or mip_levels 0 or above floor(log2(size)) + 1");
+    PBR_CHECK(ctx, "pbr_bc6h_decode_cube", bc6h_chain::refusal(size, mip_levels));
     PBR_REQUIRE(ctx, (pbr::addr(out_rgba) & 15u) == 0, "pbr_bc6h_decode_cube: out_rgba not 16-byte aligned");
+    PBR_CHECK(ctx, "pbr_bc6h_decode_cube", bc6h_chain::faces_refusal(face_blocks));
     Bc6hCube L;
-    for (int f = 0; f < 6; f++) {
-        PBR_REQUIRE(ctx, face_blocks[f], "pbr_bc6h_decode_cube: null face pointer");
-        PBR_REQUIRE(ctx, (pbr::addr(face_blocks[f]) & 15u) == 0, "pbr_bc6h_decode_cube: face blocks not 16-byte aligned");
-        L.face[f] = static_cast<const uint4*>(face_blocks[f]);
-    }
-    L.size = size; L.mips = mip_levels;
-    uint32_t nb = 0;                              // (the largest face chain holds 2048^2 * 4 / 3 blocks, the cube 8192^2 * 8 texels: below 2^32)
-    for (uint32_t l = 0; l <= BC6H_MAX_LEVELS; l++) {
-        L.face_first[l] = nb;
-        if (l < BC6H_MAX_LEVELS) L.first_texel[l] = (uint32_t)pbr::cube_mip_offset(size, l < mip_levels ? l : mip_levels);
-        if (l < mip_levels) nb += level_blocks(size >> l) * level_blocks(size >> l);
-    }
-    L.lanes = 6u * nb;
+    for (int f = 0; f < 6; f++) L.face[f] = static_cast<const uint4*>(face_blocks[f]);
+    bc6h_chain::fill(L, size, mip_levels);
     hipLaunchKernelGGL(k_bc6h_decode_cube, dim3((L.lanes + 255u) / 256u), dim3(256), 0, ctx->stream, L, reinterpret_cast<float4*>(out_rgba));
     return pbr::launched(ctx, "k_bc6h_decode_cube");
 }

@@ -1,6 +1,6 @@
 // bc6h_decode_block.hpp — the BC6H_UF16 decode rule pinned in include/pbr_hip.h in the two forms its users need:
-//   per block   the mode tables, read_header / endpoints<M>, the partition, anchor and weight constants: k_bc6h_decode_cube
-//               (bc6h_decode.hip) expands whole blocks with them
+//   per block   the mode tables, read_header / endpoints<M>, and the two steps both forms share — mode_endpoints() (the mode
+//               switch) and texel_weight() —: k_bc6h_decode_cube (bc6h_decode.hip) expands whole blocks with them
 //   per texel   header(): the 16 bytes of a block -> a Block (its unquantized endpoints packed two to a word, the index word, the
 //               partition pattern and anchor); texel(): a Block and a texel number -> three half codes; half_to_f32(): the fp32 value.
 //               The in-place sky resolve (k_skybox_bc6h, raster.hip) runs header() once per distinct block of a footprint and texel()
@@ -153,21 +153,9 @@ BC6H_DEC_FN void endpoints(uint64_t lo, uint64_t hi, uint32_t (&e)[12]) {
     for (uint32_t k = 0; k < 3u * (last + 1u); k++) e[k] = unquantize<D.endpoint_bits>(e[k]);
 }
 
-// ---- per texel ----
-// One block ready for texel(): the unquantized endpoints (<= 0xffff each) two to a word — pair[c] = e0 | e1 << 16, pair[3 + c] =
-// e2 | e3 << 16 (c: r, g, b) —, the upper 64 bits of the block (every index bit lies there) and meta = the partition pattern (bits
-// 0 .. 15, texel t in bit t; 0 for one region) | anchor << 16 (16: none) | two regions << 24.  Nine words.
-struct Block {
-    uint32_t pair[6];
-    uint32_t hi_lo, hi_hi;
-    uint32_t meta;
-};
-
-// the 16 bytes of a block (bit 0 of the block = bit 0 of x) -> Block: the mode's header once, whatever texels are asked for later
-BC6H_DEC_FN Block header(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
-    const uint64_t lo = x | ((uint64_t)y << 32), hi = z | ((uint64_t)w << 32);
-    uint32_t e[12] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    const uint32_t mode = (x & 2u) ? x & 31u : x & 3u;
+// the mode switch: the block's header -> e (zero on entry) by its mode's rule; returns whether the mode has two regions
+BC6H_DEC_FN bool mode_endpoints(uint64_t lo, uint64_t hi, uint32_t (&e)[12]) {
+    const uint32_t x = (uint32_t)lo, mode = (x & 2u) ? x & 31u : x & 3u;
     bool two = false;
     switch (mode) {
         case 0x00: endpoints<0x00>(lo, hi, e); two = true; break;
@@ -186,6 +174,33 @@ BC6H_DEC_FN Block header(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
         case 0x0f: endpoints<0x0f>(lo, hi, e); break;
         default: break;                                       // 0x13, 0x17, 0x1b, 0x1f are reserved: every endpoint 0, rgb = 0
     }
+    return two;
+}
+// texel t's interpolation weight (two: nonzero for two regions, a word as texel() holds it; anchor: region 1's anchor texel, 16 for none).  Indices: 3 bits from
+// block bit 82 (two regions) or 4 bits from bit 65, an anchor texel one bit fewer; all in `hi`
+BC6H_DEC_FN uint32_t texel_weight(uint64_t hi, uint32_t two, uint32_t anchor, uint32_t t) {
+    const uint32_t ib = two ? 3u : 4u, base = two ? 18u : 1u;
+    const uint32_t start = base + ib * t - (t > 0u ? 1u : 0u) - (t > anchor ? 1u : 0u);
+    const uint32_t width = ib - ((t == 0u || t == anchor) ? 1u : 0u);
+    const uint32_t idx = (uint32_t)(hi >> start) & ((1u << width) - 1u);
+    return (uint32_t)((two ? WEIGHTS3 : idx < 8u ? WEIGHTS4_LO : WEIGHTS4_HI) >> (8u * (idx & 7u))) & 255u;
+}
+
+// ---- per texel ----
+// One block ready for texel(): the unquantized endpoints (<= 0xffff each) two to a word — pair[c] = e0 | e1 << 16, pair[3 + c] =
+// e2 | e3 << 16 (c: r, g, b) —, the upper 64 bits of the block (every index bit lies there) and meta = the partition pattern (bits
+// 0 .. 15, texel t in bit t; 0 for one region) | anchor << 16 (16: none) | two regions << 24.  Nine words.
+struct Block {
+    uint32_t pair[6];
+    uint32_t hi_lo, hi_hi;
+    uint32_t meta;
+};
+
+// the 16 bytes of a block (bit 0 of the block = bit 0 of x) -> Block: the mode's header once, whatever texels are asked for later
+BC6H_DEC_FN Block header(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+    const uint64_t lo = x | ((uint64_t)y << 32), hi = z | ((uint64_t)w << 32);
+    uint32_t e[12] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    const bool two = mode_endpoints(lo, hi, e);
     const uint32_t shape = (uint32_t)(hi >> 13) & 31u;        // bits 77 .. 81
     const uint32_t pattern = two ? (uint32_t)PARTITION[shape] : 0u;
     const uint32_t anchor = !two ? 16u : shape < 16u ? 15u : (uint32_t)(ANCHOR_16_31 >> (4u * (shape - 16u))) & 15u;
@@ -203,14 +218,9 @@ BC6H_DEC_FN Block header(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
 // texel t (0 .. 15, row-major: x = t & 3, y = t >> 2) of a block -> its three half codes (<= 0x7bff)
 BC6H_DEC_FN void texel(const Block& b, uint32_t t, uint32_t (&half)[3]) {
     const uint64_t hi = b.hi_lo | ((uint64_t)b.hi_hi << 32);
-    const bool two = (b.meta >> 24) != 0u;
+    const uint32_t two = b.meta >> 24;
     const uint32_t anchor = (b.meta >> 16) & 31u;
-    // indices: 3 bits from block bit 82 (two regions) or 4 bits from bit 65, an anchor texel one bit fewer; all in `hi`
-    const uint32_t ib = two ? 3u : 4u, base = two ? 18u : 1u;
-    const uint32_t start = base + ib * t - (t > 0u ? 1u : 0u) - (t > anchor ? 1u : 0u);
-    const uint32_t width = ib - ((t == 0u || t == anchor) ? 1u : 0u);
-    const uint32_t idx = (uint32_t)(hi >> start) & ((1u << width) - 1u);
-    const uint32_t w = (uint32_t)((two ? WEIGHTS3 : idx < 8u ? WEIGHTS4_LO : WEIGHTS4_HI) >> (8u * (idx & 7u))) & 255u;
+    const uint32_t w = texel_weight(hi, two, anchor, t);
     const bool second = ((b.meta >> t) & 1u) != 0u;
     BC6H_DEC_UNROLL
     for (uint32_t c = 0; c < 3u; c++) {

@@ -20,7 +20,6 @@
 
 namespace {
 
-static_assert((1u << (bc6h_enc::MAX_LEVELS - 1)) == PBR_BC6H_MAX_SIZE, "levels of the largest cube");
 static_assert(sizeof(bc6h_enc::Texel) == 16 && sizeof(bc6h_enc::Block) == 16, "a texel and a block are 16-byte accesses");
 
 __global__ __launch_bounds__(256) void k_bc6h_encode_cube(bc6h_enc::Cube L, const bc6h_enc::Texel* __restrict__ cube) {
@@ -36,16 +35,12 @@ extern "C" {
 pbr_status pbr_bc6h_encode_cube(pbr_ctx* ctx, const float* cube_rgba, uint32_t size, uint32_t mip_levels, void* const face_blocks_out[6]) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, face_blocks_out && cube_rgba, "pbr_bc6h_encode_cube: null pointer");
-    PBR_REQUIRE(ctx, pbr_bc6h_chain_bytes(size, mip_levels) != 0,
-                "pbr_bc6h_encode_cube: size 0, not a multiple of 4 or above PBR_BC6H_MAX_SIZE, or mip_levels 0 or above floor(log2(size)) + 1");
+    PBR_CHECK(ctx, "pbr_bc6h_encode_cube", bc6h_chain::refusal(size, mip_levels));
     PBR_REQUIRE(ctx, (pbr::addr(cube_rgba) & 15u) == 0, "pbr_bc6h_encode_cube: cube_rgba not 16-byte aligned");
+    PBR_CHECK(ctx, "pbr_bc6h_encode_cube", bc6h_chain::faces_refusal(face_blocks_out));
     bc6h_enc::Cube L;
-    for (int f = 0; f < 6; f++) {
-        PBR_REQUIRE(ctx, face_blocks_out[f], "pbr_bc6h_encode_cube: null face pointer");
-        PBR_REQUIRE(ctx, (pbr::addr(face_blocks_out[f]) & 15u) == 0, "pbr_bc6h_encode_cube: face blocks not 16-byte aligned");
-        L.face[f] = face_blocks_out[f];
-    }
-    bc6h_enc::fill_levels(L, size, mip_levels);
+    for (int f = 0; f < 6; f++) L.face[f] = face_blocks_out[f];
+    bc6h_chain::fill(L, size, mip_levels);
     hipLaunchKernelGGL(k_bc6h_encode_cube, dim3((L.lanes + 255u) / 256u), dim3(256), 0, ctx->stream, L,
                        reinterpret_cast<const bc6h_enc::Texel*>(cube_rgba));
     return pbr::launched(ctx, "k_bc6h_encode_cube");

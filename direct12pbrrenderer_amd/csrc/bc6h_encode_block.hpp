@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <cstring>
 
+#include "tex_chain.hpp"
+
 #if defined(__HIPCC__)
 #define BC6H_FN __host__ __device__ __forceinline__
 #define BC6H_UNROLL _Pragma("unroll")
@@ -17,20 +19,14 @@
 
 namespace bc6h_enc {
 
-constexpr uint32_t MAX_LEVELS = 14;                         // floor(log2(PBR_BC6H_MAX_SIZE)) + 1
+using bc6h_chain::MAX_LEVELS;
 constexpr uint64_t WEIGHTS4_LO = 0x1e1a15110d090400ull;     // 0, 4, 9, 13, 17, 21, 26, 30: a byte each
 constexpr uint64_t WEIGHTS4_HI = 0x403c37332f2b2622ull;     // 34, 38, 43, 47, 51, 55, 60, 64
 
 struct alignas(16) Texel { float x, y, z, w; };                        // a float4 of the pbr_cube_f32 chain
 struct alignas(16) Block { uint32_t x, y, z, w; };                     // 16 bytes, bit 0 of the block = bit 0 of x
 
-struct Cube {
-    void* face[6];
-    uint32_t face_first[MAX_LEVELS + 1];   // blocks of one face in front of the level; [mips] = one face's blocks
-    uint32_t first_texel[MAX_LEVELS];      // pbr_cube_mip_offset of the level
-    uint32_t size, mips;
-    uint32_t lanes;                        // 6 x one face's blocks
-};
+using Cube = bc6h_chain::Cube<void*>;                                  // the launch's level table: bc6h_chain::fill makes it
 
 BC6H_FN uint32_t weight(uint32_t k) {
     return (uint32_t)((k < 8u ? WEIGHTS4_LO : WEIGHTS4_HI) >> (8u * (k & 7u))) & 255u;
@@ -262,22 +258,6 @@ BC6H_FN void encode_lane(const Cube& L, uint32_t g, const Texel* cube) {
     const Block b = encode_block(h, valid);
     void* base = f == 0u ? L.face[0] : f == 1u ? L.face[1] : f == 2u ? L.face[2] : f == 3u ? L.face[3] : f == 4u ? L.face[4] : L.face[5];
     static_cast<Block*>(base)[ff + r] = b;
-}
-
-// the launch's level table (host): the chain of `size` and `mip_levels` as pbr_bc6h_chain_bytes and pbr_cube_mip_offset lay it out
-inline void fill_levels(Cube& L, uint32_t size, uint32_t mip_levels) {
-    L.size = size; L.mips = mip_levels;
-    uint32_t nb = 0, nt = 0;                // (the largest face chain holds 2048^2 * 4 / 3 blocks, the cube 8192^2 * 8 texels: below 2^32)
-    for (uint32_t l = 0; l <= MAX_LEVELS; l++) {
-        L.face_first[l] = nb;
-        if (l < MAX_LEVELS) L.first_texel[l] = nt;
-        if (l < mip_levels) {
-            const uint32_t s = size >> l, bw = s + 3u >= 4u ? (s + 3u) >> 2 : 1u;
-            nb += bw * bw;
-            nt += 6u * s * s;
-        }
-    }
-    L.lanes = 6u * nb;
 }
 
 }  // namespace bc6h_enc

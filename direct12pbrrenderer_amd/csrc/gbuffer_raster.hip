@@ -27,9 +27,11 @@
 // tests/raster_tex_ref.py restates it.
 //
 // BC1-resident textures (PBR_TEX_BC1_BLOCKS): a table that holds one runs k_rs_raster<RsRasterTexBc1>, whose bilinear takes its taps
-// from the blocks in place (bc1_decode.hpp); pbr_bc1_decode (k_bc1_decode) is the bulk decode of a whole chain, at the end of the file.
+// from the blocks in place (bc1_decode.hpp).  The bulk decode of a whole chain (pbr_bc1_decode) is texture2d.hip's; the texture table's
+// descriptions are checked by tex_chain.hpp.
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
+#include "tex_chain.hpp"
 #include <type_traits>
 
 using namespace pbr;
@@ -39,6 +41,7 @@ namespace {
 #include "gbuffer_encode.hpp"
 #include "texel_decode.hpp"
 #include "bc1_decode.hpp"
+using tex2d::bc1_blocks;
 
 constexpr uint32_t BIN = 16;               // bin edge in pixels: 256 lanes, one per pixel
 constexpr uint32_t LIST_CAP = 2048;        // longest bin list sorted in LDS
@@ -781,62 +784,6 @@ pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const
     return pbr::launched(ctx, "k_rs_raster");
 }
 
-// floor(log2(min(w, h))) + 1: the levels of a full chain down to a 1-texel side
-uint32_t max_mip_levels(uint32_t w, uint32_t h) {
-    uint32_t m = min(w, h), n = 0;
-    while (m) { n++; m >>= 1; }
-    return n;
-}
-bool stored_format(uint32_t f) {
-    return f == PBR_TEX_R8_UNORM || f == PBR_TEX_R8G8B8A8_UNORM || f == PBR_TEX_B8G8R8A8_UNORM || f == PBR_TEX_B8G8R8A8_UNORM_SRGB;
-}
-bool chain_shape_ok(uint32_t w, uint32_t h, uint32_t mips) {
-    return w && h && w <= PBR_TEX_MAX_SIZE && h <= PBR_TEX_MAX_SIZE && mips && mips <= max_mip_levels(w, h);
-}
-
-// ---- pbr_bc1_decode: every level of a chain in one launch ----
-constexpr uint32_t BC1_MAX_LEVELS = 15;    // floor(log2(PBR_TEX_MAX_SIZE)) + 1
-struct Bc1Levels {
-    uint32_t first_block[BC1_MAX_LEVELS + 1];   // the level's first block in the chain; [mips] = the chain's blocks
-    uint64_t first_texel[BC1_MAX_LEVELS];       // the level's first texel in the decoded chain
-    uint32_t width, height, mips;
-    uint32_t texel_bytes;                       // 4, or 1 (R8)
-    uint32_t bgra;                              // B8G8R8A8[_SRGB]: red and blue swapped in the stored texel
-};
-// lane = block: its palette once, then its rows.  A row that lies whole inside the level and is aligned to its own size is one
-// vector store (16 bytes, R8: 4); the rows of edge blocks of sizes that are no multiple of 4, and unaligned ones, go texel by texel.
-__global__ __launch_bounds__(256) void k_bc1_decode(const uint2* __restrict__ blocks, Bc1Levels L, uint8_t* __restrict__ out) {
-    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
-    if (b >= L.first_block[L.mips]) return;
-    uint32_t l = 0;
-    while (l + 1u < L.mips && b >= L.first_block[l + 1u]) l++;
-    const uint32_t wl = L.width >> l, hl = L.height >> l, bw = bc1_blocks(wl);
-    const uint32_t k = b - L.first_block[l], bx = k % bw, by = k / bw;
-    const uint2 blk = blocks[b];
-    uint32_t pal[4];
-    bc1_palette(blk.x, pal);
-    const uint32_t x0 = 4u * bx, nx = min(4u, wl - x0);
-    for (uint32_t y = 0; y < 4u && 4u * by + y < hl; y++) {
-        uint32_t px[4];
-        for (uint32_t x = 0; x < 4u; x++) px[x] = bc1_texel(pal, blk.y, x, y);
-        uint8_t* row = out + (L.first_texel[l] + (uint64_t)(4u * by + y) * wl + x0) * L.texel_bytes;
-        if (L.texel_bytes == 4u) {
-            for (uint32_t x = 0; x < 4u; x++) px[x] = bc1_stored(px[x], L.bgra != 0);
-            if (nx == 4u && ((uintptr_t)row & 15u) == 0) {
-                *reinterpret_cast<uint4*>(row) = make_uint4(px[0], px[1], px[2], px[3]);
-            } else {
-                for (uint32_t x = 0; x < nx; x++) reinterpret_cast<uint32_t*>(row)[x] = px[x];
-            }
-        } else {
-            if (nx == 4u && ((uintptr_t)row & 3u) == 0) {
-                *reinterpret_cast<uint32_t*>(row) = (px[0] & 255u) | ((px[1] & 255u) << 8) | ((px[2] & 255u) << 16) | (px[3] << 24);
-            } else {
-                for (uint32_t x = 0; x < nx; x++) row[x] = (uint8_t)px[x];
-            }
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -886,62 +833,14 @@ pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const 
     bool any_bc1 = false;
     for (uint32_t i = 0; i < n_textures; i++) {
         const pbr_texture2d& t = textures[i];
-        const bool bc1 = (t.format & PBR_TEX_BC1_BLOCKS) != 0;
-        const bool r8 = t.format == PBR_TEX_R8_UNORM;
-        PBR_REQUIRE(ctx, (t.format & ~(0xffu | PBR_TEX_BC1_BLOCKS)) == 0 && stored_format(t.format & 0xffu),
-                    "pbr_gbuffer_raster_textured: unknown texture format");
-        PBR_REQUIRE(ctx, t.width && t.height && t.width <= PBR_TEX_MAX_SIZE && t.height <= PBR_TEX_MAX_SIZE,
-                    "pbr_gbuffer_raster_textured: texture size zero or above PBR_TEX_MAX_SIZE");
-        PBR_REQUIRE(ctx, t.mip_levels && t.mip_levels <= max_mip_levels(t.width, t.height),
-                    "pbr_gbuffer_raster_textured: mip_levels 0 or above floor(log2(min(w, h))) + 1");
-        PBR_REQUIRE(ctx, t.texels && (r8 || (pbr::addr(t.texels) & (bc1 ? 7u : 3u)) == 0),
+        PBR_CHECK(ctx, "pbr_gbuffer_raster_textured", tex2d::refusal(t.width, t.height, t.mip_levels, t.format, true));
+        PBR_REQUIRE(ctx, t.texels && tex2d::aligned(t.texels, t.format),
                     "pbr_gbuffer_raster_textured: texels null or not aligned to the texel size (BC1 blocks: 8 bytes)");
-        any_bc1 |= bc1;
+        any_bc1 |= (t.format & PBR_TEX_BC1_BLOCKS) != 0;
         tx.table[i] = t;
     }
     return raster(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth, stencil,
                   pitch, scratch, scratch_bytes, &tx, any_bc1);
-}
-
-size_t pbr_texture2d_bytes(uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t format) {
-    if ((format & ~(0xffu | PBR_TEX_BC1_BLOCKS)) != 0 || !stored_format(format & 0xffu) || !chain_shape_ok(width, height, mip_levels))
-        return 0;
-    const size_t texel = (format & 0xffu) == PBR_TEX_R8_UNORM ? 1 : 4;
-    size_t bytes = 0;
-    for (uint32_t l = 0; l < mip_levels; l++)
-        bytes += (format & PBR_TEX_BC1_BLOCKS) ? (size_t)bc1_blocks(width >> l) * bc1_blocks(height >> l) * 8
-                                               : (size_t)(width >> l) * (height >> l) * texel;
-    return bytes;
-}
-
-pbr_status pbr_bc1_decode(pbr_ctx* ctx, const void* blocks, uint32_t width, uint32_t height, uint32_t mip_levels,
-                          uint32_t stored, void* out) {
-    if (!ctx) return PBR_ERR_INVALID;
-    PBR_REQUIRE(ctx, blocks && out, "pbr_bc1_decode: null pointer");
-    PBR_REQUIRE(ctx, stored_format(stored), "pbr_bc1_decode: unknown stored format");
-    PBR_REQUIRE(ctx, width && height && width <= PBR_TEX_MAX_SIZE && height <= PBR_TEX_MAX_SIZE,
-                "pbr_bc1_decode: texture size zero or above PBR_TEX_MAX_SIZE");
-    PBR_REQUIRE(ctx, mip_levels && mip_levels <= max_mip_levels(width, height),
-                "pbr_bc1_decode: mip_levels 0 or above floor(log2(min(w, h))) + 1");
-    PBR_REQUIRE(ctx, (pbr::addr(blocks) & 7u) == 0 && (stored == PBR_TEX_R8_UNORM || (pbr::addr(out) & 3u) == 0),
-                "pbr_bc1_decode: blocks not 8-byte aligned, or out not aligned to the texel size");
-    static_assert((1u << (BC1_MAX_LEVELS - 1)) == PBR_TEX_MAX_SIZE, "levels of the largest chain");
-    Bc1Levels L;
-    L.width = width; L.height = height; L.mips = mip_levels;
-    L.texel_bytes = stored == PBR_TEX_R8_UNORM ? 1u : 4u;
-    L.bgra = stored == PBR_TEX_B8G8R8A8_UNORM || stored == PBR_TEX_B8G8R8A8_UNORM_SRGB;
-    uint64_t nb = 0, nt = 0;
-    for (uint32_t l = 0; l <= BC1_MAX_LEVELS; l++) {
-        L.first_block[l] = (uint32_t)nb;          // (the largest chain holds 4096^2 * 4 / 3 blocks: below 2^32)
-        if (l < BC1_MAX_LEVELS) L.first_texel[l] = nt;
-        if (l < mip_levels) {
-            nb += (uint64_t)bc1_blocks(width >> l) * bc1_blocks(height >> l);
-            nt += (uint64_t)(width >> l) * (height >> l);
-        }
-    }
-    hipLaunchKernelGGL(k_bc1_decode, dim3((uint32_t)((nb + 255u) / 256u)), dim3(256), 0, ctx->stream, static_cast<const uint2*>(blocks), L,
-                       static_cast<uint8_t*>(out));
-    return pbr::launched(ctx, "k_bc1_decode");
 }
 
 }  // extern "C"

@@ -8,14 +8,12 @@
 // cube addressing, the gamma/octahedral results feed UNORM8 rounding).
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
+#include "tex_chain.hpp"
 #include "bc6h_decode_block.hpp"
 
 using namespace pbr;
 
 namespace {
-
-constexpr uint32_t BC6H_SKY_MAX_LEVELS = 14;    // floor(log2(PBR_BC6H_MAX_SIZE)) + 1
-static_assert((1u << (BC6H_SKY_MAX_LEVELS - 1)) == PBR_BC6H_MAX_SIZE, "levels of the largest cube");
 
 struct SkyParams {
     float InvView[9];
@@ -119,7 +117,7 @@ __global__ __launch_bounds__(256) void k_rgbe_decode(const uint32_t* __restrict_
 // selects only, no private array, no LDS.
 struct SkyBc6h {
     const uint4* face[6];
-    uint32_t face_first[BC6H_SKY_MAX_LEVELS];   // blocks of one face in front of the level
+    uint32_t face_first[bc6h_chain::MAX_LEVELS];   // blocks of one face in front of the level: the head of bc6h_chain::Cube's table
 };
 
 struct CubeTapAddress {     // the texel policy that returns where a tap landed: the bit patterns of face, x, y (moved, never computed with)
@@ -180,7 +178,7 @@ __device__ __forceinline__ F4 bc6h_trilinear(const SkyBc6h& L, uint32_t size, ui
         const uint32_t l = i == 0u ? l0 : l1;
         uint32_t ff = 0;
 #pragma unroll
-        for (uint32_t k = 1; k < BC6H_SKY_MAX_LEVELS; k++) ff = l >= k ? L.face_first[k] : ff;   // (static indices: the table stays in scalar registers)
+        for (uint32_t k = 1; k < bc6h_chain::MAX_LEVELS; k++) ff = l >= k ? L.face_first[k] : ff;   // (static indices: the table stays in scalar registers)
         const F4 c = bc6h_bilinear(L, ff, (int)(size >> l), d);
         if (i == 0u) a = c; else b = c;
         if (one) break;
@@ -241,19 +239,13 @@ pbr_status pbr_skybox_bc6h(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* ti
     PBR_REQUIRE(ctx, g && tile && sky && stencil && hdr, "pbr_skybox_bc6h: null pointer");
     PBR_REQUIRE(ctx, tile->w && tile->h && tile->full_w && tile->full_h && pitch >= tile->w && hdr_pitch >= tile->w,
                 "pbr_skybox_bc6h: bad tile / pitch");
-    PBR_REQUIRE(ctx, pbr_bc6h_chain_bytes(sky->size, sky->mips) != 0,
-                "pbr_skybox_bc6h: size 0, not a multiple of 4 or above PBR_BC6H_MAX_SIZE, or mips 0 or above floor(log2(size)) + 1");
+    PBR_CHECK(ctx, "pbr_skybox_bc6h", bc6h_chain::refusal(sky->size, sky->mips));
+    PBR_CHECK(ctx, "pbr_skybox_bc6h", bc6h_chain::faces_refusal(sky->face_blocks));
+    bc6h_chain::Cube<const uint4*> T;             // (a face's blocks in front of a level are below 2^28: bc6h_bilinear's key)
+    bc6h_chain::fill(T, sky->size, sky->mips);
     SkyBc6h L;
-    for (int f = 0; f < 6; f++) {
-        PBR_REQUIRE(ctx, sky->face_blocks[f], "pbr_skybox_bc6h: null face pointer");
-        PBR_REQUIRE(ctx, (pbr::addr(sky->face_blocks[f]) & 15u) == 0, "pbr_skybox_bc6h: face blocks not 16-byte aligned");
-        L.face[f] = static_cast<const uint4*>(sky->face_blocks[f]);
-    }
-    uint32_t nb = 0;                              // (the largest face chain holds 2048^2 * 4 / 3 blocks: below 2^28)
-    for (uint32_t l = 0; l < BC6H_SKY_MAX_LEVELS; l++) {
-        L.face_first[l] = nb;
-        if (l < sky->mips) { const uint32_t b = (((sky->size >> l) + 3u) / 4u) ? ((sky->size >> l) + 3u) / 4u : 1u; nb += b * b; }
-    }
+    for (int f = 0; f < 6; f++) L.face[f] = static_cast<const uint4*>(sky->face_blocks[f]);
+    for (uint32_t l = 0; l < bc6h_chain::MAX_LEVELS; l++) L.face_first[l] = T.face_first[l];
     SkyParams p;
     fill_sky_params(p, g, tile, sky->size, sky->mips, pitch, hdr_pitch);
     dim3 grid((tile->w + 63) / 64, (tile->h + 3) / 4);

@@ -1,6 +1,6 @@
-// texture_import.hip — the producing half of the texture path (include/pbr_hip.h, "Texture import"): what the reference does when it
-// imports an image (ResourceLoader::ImportTexture, ResourceLoader.cpp:252-277): GenerateImageMipmaps (:465-507) and
-// TextureCompressor::Compress (TextureCompression.cpp:52-113, DirectX::Compress to BC1).
+// texture2d.hip — the chain of a 2D texture in both directions (include/pbr_hip.h, "Texture import" and PBR_TEX_BC1_BLOCKS).  The producing
+// half is what the reference does when it imports an image (ResourceLoader::ImportTexture, ResourceLoader.cpp:252-277):
+// GenerateImageMipmaps (:465-507) and TextureCompressor::Compress (TextureCompression.cpp:52-113, DirectX::Compress to BC1).
 //   pbr_texture2d_gen_mips  the 2 x 2 box chain of a 2D texture in place, by the rule of scene.mip_chain.  k_tex_mips_tile: one block
 //                           per 64 x 64 tile of level 0 takes it down levels 1 .. 6, each level's tile kept in LDS for the next
 //                           (the 2 x 2 footprints are aligned at every level, so a tile never needs a neighbour's texels);
@@ -11,29 +11,23 @@
 //                           texels sit in sixteen registers as r | g << 8 | b << 16; each of its four rows is one 16-byte load
 //                           (R8: 4 bytes), contiguous across the wave; no LDS and no cross-lane traffic.  The rule is pinned in the
 //                           header, all in integers; tests/bc1_encode_ref.py restates it.
+//   pbr_bc1_decode          the bulk decode of a whole BC1 chain, every level in one launch, lane = block (k_bc1_decode; the block
+//                           rule is bc1_decode.hpp's, which the rasterizer's in-place sampler shares); pbr_texture2d_bytes beside it.
+// Chain geometry — levels, offsets, block counts, refusals, the level table of the two lane = block kernels — is tex_chain.hpp's.
 // Parity with DirectXTex's filter and encoder is not pinned (neither can run here): DESIGN.md section 7.
 #include <cstdint>
 
 #include "pbr_internal.hpp"
+#include "tex_chain.hpp"
 #include "bc1_decode.hpp"
 
 namespace {
 
-constexpr uint32_t TEX_MAX_LEVELS = 15;    // floor(log2(PBR_TEX_MAX_SIZE)) + 1
-static_assert((1u << (TEX_MAX_LEVELS - 1)) == PBR_TEX_MAX_SIZE, "levels of the largest chain");
-
-uint32_t max_mip_levels(uint32_t w, uint32_t h) {
-    uint32_t m = w < h ? w : h, n = 0;
-    while (m) { n++; m >>= 1; }
-    return n;
-}
-bool stored_format(uint32_t f) {
-    return f == PBR_TEX_R8_UNORM || f == PBR_TEX_R8G8B8A8_UNORM || f == PBR_TEX_B8G8R8A8_UNORM || f == PBR_TEX_B8G8R8A8_UNORM_SRGB;
-}
+using tex2d::bc1_blocks;
 
 // ---- pbr_texture2d_gen_mips ----
 struct MipLevels {
-    uint64_t first_texel[TEX_MAX_LEVELS];   // the level's first texel in the chain
+    uint64_t first_texel[tex2d::MAX_LEVELS];   // the level's first texel in the chain
     uint32_t width, height, mips;
 };
 constexpr uint32_t MIP_TILE_LEVELS = 6;     // a 64 x 64 tile of level 0 ends in one texel of level 6
@@ -140,14 +134,6 @@ __global__ __launch_bounds__(256) void k_tex_mips_top(uint8_t* chain, MipLevels 
 }
 
 // ---- pbr_bc1_encode ----
-struct EncLevels {
-    uint32_t first_block[TEX_MAX_LEVELS + 1];   // the level's first block in the chain; [mips] = the chain's blocks
-    uint64_t first_texel[TEX_MAX_LEVELS];       // the level's first texel in the uncompressed chain
-    uint32_t width, height, mips;
-    uint32_t texel_bytes;                       // 4, or 1 (R8)
-    uint32_t bgra;                              // B8G8R8A8[_SRGB]: red and blue swapped in the stored texel
-};
-
 __device__ __forceinline__ int floor_div(int n, int d) {      // d > 0
     const int q = n / d;
     return (n < 0 && q * d != n) ? q - 1 : q;
@@ -186,11 +172,10 @@ __device__ __forceinline__ void bc1_fit(const uint32_t (&px)[16], uint32_t valid
 }
 
 // lane = block
-__global__ __launch_bounds__(256) void k_bc1_encode(const uint8_t* __restrict__ texels, EncLevels L, uint2* __restrict__ blocks) {
+__global__ __launch_bounds__(256) void k_bc1_encode(const uint8_t* __restrict__ texels, tex2d::Levels L, uint2* __restrict__ blocks) {
     const uint32_t bi = blockIdx.x * 256u + threadIdx.x;
     if (bi >= L.first_block[L.mips]) return;
-    uint32_t l = 0;
-    while (l + 1u < L.mips && bi >= L.first_block[l + 1u]) l++;
+    const uint32_t l = tex2d::level_of_block(L, bi);
     const uint32_t wl = L.width >> l, hl = L.height >> l, bw = bc1_blocks(wl);
     const uint32_t k = bi - L.first_block[l], bx = k % bw, by = k / bw;
     const uint32_t x0 = 4u * bx, y0 = 4u * by, nx = min(4u, wl - x0), ny = min(4u, hl - y0);
@@ -285,12 +270,38 @@ __global__ __launch_bounds__(256) void k_bc1_encode(const uint8_t* __restrict__ 
     blocks[bi] = make_uint2(c0 | (c1 << 16), bits);
 }
 
-// the description checks shared by both entry points (those of pbr_bc1_decode); nullptr: nothing wrong
-const char* chain_refusal(uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t format) {
-    if (!stored_format(format)) return "unknown stored format";
-    if (!width || !height || width > PBR_TEX_MAX_SIZE || height > PBR_TEX_MAX_SIZE) return "texture size zero or above PBR_TEX_MAX_SIZE";
-    if (!mip_levels || mip_levels > max_mip_levels(width, height)) return "mip_levels 0 or above floor(log2(min(w, h))) + 1";
-    return nullptr;
+// ---- pbr_bc1_decode: every level of a chain in one launch ----
+// lane = block: its palette once, then its rows.  A row that lies whole inside the level and is aligned to its own size is one
+// vector store (16 bytes, R8: 4); the rows of edge blocks of sizes that are no multiple of 4, and unaligned ones, go texel by texel.
+__global__ __launch_bounds__(256) void k_bc1_decode(const uint2* __restrict__ blocks, tex2d::Levels L, uint8_t* __restrict__ out) {
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (b >= L.first_block[L.mips]) return;
+    const uint32_t l = tex2d::level_of_block(L, b);
+    const uint32_t wl = L.width >> l, hl = L.height >> l, bw = bc1_blocks(wl);
+    const uint32_t k = b - L.first_block[l], bx = k % bw, by = k / bw;
+    const uint2 blk = blocks[b];
+    uint32_t pal[4];
+    bc1_palette(blk.x, pal);
+    const uint32_t x0 = 4u * bx, nx = min(4u, wl - x0);
+    for (uint32_t y = 0; y < 4u && 4u * by + y < hl; y++) {
+        uint32_t px[4];
+        for (uint32_t x = 0; x < 4u; x++) px[x] = bc1_texel(pal, blk.y, x, y);
+        uint8_t* row = out + (L.first_texel[l] + (uint64_t)(4u * by + y) * wl + x0) * L.texel_bytes;
+        if (L.texel_bytes == 4u) {
+            for (uint32_t x = 0; x < 4u; x++) px[x] = bc1_stored(px[x], L.bgra != 0);
+            if (nx == 4u && ((uintptr_t)row & 15u) == 0) {
+                *reinterpret_cast<uint4*>(row) = make_uint4(px[0], px[1], px[2], px[3]);
+            } else {
+                for (uint32_t x = 0; x < nx; x++) reinterpret_cast<uint32_t*>(row)[x] = px[x];
+            }
+        } else {
+            if (nx == 4u && ((uintptr_t)row & 3u) == 0) {
+                *reinterpret_cast<uint32_t*>(row) = (px[0] & 255u) | ((px[1] & 255u) << 8) | ((px[2] & 255u) << 16) | (px[3] << 24);
+            } else {
+                for (uint32_t x = 0; x < nx; x++) row[x] = (uint8_t)px[x];
+            }
+        }
+    }
 }
 
 }  // namespace
@@ -300,16 +311,14 @@ extern "C" {
 pbr_status pbr_texture2d_gen_mips(pbr_ctx* ctx, void* texels, uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t format) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, texels, "pbr_texture2d_gen_mips: null pointer");
-    PBR_CHECK(ctx, "pbr_texture2d_gen_mips", chain_refusal(width, height, mip_levels, format));
-    PBR_REQUIRE(ctx, format == PBR_TEX_R8_UNORM || (pbr::addr(texels) & 3u) == 0, "pbr_texture2d_gen_mips: texels not aligned to the texel size");
+    PBR_CHECK(ctx, "pbr_texture2d_gen_mips", tex2d::refusal(width, height, mip_levels, format));
+    PBR_REQUIRE(ctx, tex2d::aligned(texels, format), "pbr_texture2d_gen_mips: texels not aligned to the texel size");
     if (mip_levels == 1) return PBR_OK;
-    MipLevels L;
+    tex2d::Levels T;
+    tex2d::fill(T, width, height, mip_levels, format);
+    MipLevels L;                           // (the texel half of the table: its kernels' argument keeps its layout)
     L.width = width; L.height = height; L.mips = mip_levels;
-    uint64_t nt = 0;
-    for (uint32_t l = 0; l < TEX_MAX_LEVELS; l++) {
-        L.first_texel[l] = nt;
-        if (l < mip_levels) nt += (uint64_t)(width >> l) * (height >> l);
-    }
+    for (uint32_t l = 0; l < tex2d::MAX_LEVELS; l++) L.first_texel[l] = T.first_texel[l];
     uint8_t* chain = static_cast<uint8_t*>(texels);
     const dim3 grid((width + 63u) / 64u, (height + 63u) / 64u);
     if (format == PBR_TEX_R8_UNORM) hipLaunchKernelGGL(k_tex_mips_tile<1>, grid, dim3(256), 0, ctx->stream, chain, L);
@@ -327,25 +336,34 @@ pbr_status pbr_bc1_encode(pbr_ctx* ctx, const void* texels, uint32_t width, uint
                           uint32_t stored, void* blocks_out) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, texels && blocks_out, "pbr_bc1_encode: null pointer");
-    PBR_CHECK(ctx, "pbr_bc1_encode", chain_refusal(width, height, mip_levels, stored));
-    PBR_REQUIRE(ctx, (pbr::addr(blocks_out) & 7u) == 0 && (stored == PBR_TEX_R8_UNORM || (pbr::addr(texels) & 3u) == 0),
+    PBR_CHECK(ctx, "pbr_bc1_encode", tex2d::refusal(width, height, mip_levels, stored));
+    PBR_REQUIRE(ctx, tex2d::aligned(blocks_out, PBR_TEX_BC1_BLOCKS) && tex2d::aligned(texels, stored),
                 "pbr_bc1_encode: blocks_out not 8-byte aligned, or texels not aligned to the texel size");
-    EncLevels L;
-    L.width = width; L.height = height; L.mips = mip_levels;
-    L.texel_bytes = stored == PBR_TEX_R8_UNORM ? 1u : 4u;
-    L.bgra = stored == PBR_TEX_B8G8R8A8_UNORM || stored == PBR_TEX_B8G8R8A8_UNORM_SRGB;
-    uint64_t nb = 0, nt = 0;
-    for (uint32_t l = 0; l <= TEX_MAX_LEVELS; l++) {
-        L.first_block[l] = (uint32_t)nb;          // (the largest chain holds 4096^2 * 4 / 3 blocks: below 2^32)
-        if (l < TEX_MAX_LEVELS) L.first_texel[l] = nt;
-        if (l < mip_levels) {
-            nb += (uint64_t)bc1_blocks(width >> l) * bc1_blocks(height >> l);
-            nt += (uint64_t)(width >> l) * (height >> l);
-        }
-    }
-    hipLaunchKernelGGL(k_bc1_encode, dim3((uint32_t)((nb + 255u) / 256u)), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(texels), L,
+    tex2d::Levels L;
+    tex2d::fill(L, width, height, mip_levels, stored);
+    const uint32_t nb = L.first_block[mip_levels];
+    hipLaunchKernelGGL(k_bc1_encode, dim3((nb + 255u) / 256u), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(texels), L,
                        static_cast<uint2*>(blocks_out));
     return pbr::launched(ctx, "k_bc1_encode");
+}
+
+size_t pbr_texture2d_bytes(uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t format) {
+    return tex2d::chain_bytes(width, height, mip_levels, format);
+}
+
+pbr_status pbr_bc1_decode(pbr_ctx* ctx, const void* blocks, uint32_t width, uint32_t height, uint32_t mip_levels,
+                          uint32_t stored, void* out) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, blocks && out, "pbr_bc1_decode: null pointer");
+    PBR_CHECK(ctx, "pbr_bc1_decode", tex2d::refusal(width, height, mip_levels, stored));
+    PBR_REQUIRE(ctx, tex2d::aligned(blocks, PBR_TEX_BC1_BLOCKS) && tex2d::aligned(out, stored),
+                "pbr_bc1_decode: blocks not 8-byte aligned, or out not aligned to the texel size");
+    tex2d::Levels L;
+    tex2d::fill(L, width, height, mip_levels, stored);
+    const uint32_t nb = L.first_block[mip_levels];
+    hipLaunchKernelGGL(k_bc1_decode, dim3((nb + 255u) / 256u), dim3(256), 0, ctx->stream, static_cast<const uint2*>(blocks), L,
+                       static_cast<uint8_t*>(out));
+    return pbr::launched(ctx, "k_bc1_decode");
 }
 
 }  // extern "C"

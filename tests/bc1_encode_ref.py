@@ -1,5 +1,5 @@
 """numpy restatement of the BC1 encoding rule pinned in include/pbr_hip.h (pbr_bc1_encode), written from the header text and
-independently of csrc/texture_import.hip; the decode side (palette, chain sizes) is tests/bc1_ref.py.
+independently of csrc/texture2d.hip; the decode side (palette, chain sizes) is tests/bc1_ref.py.
 
 Everything is integer arithmetic (int64 here; the header states that 32 bits suffice), `//` is floor division as the header
 demands, and a texel outside its level takes no part in any minimum, maximum or sum and gets index 0."""

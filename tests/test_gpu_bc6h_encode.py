@@ -35,10 +35,12 @@ def rgba(level0_rgb):
 
 
 def level0_of(name, smooth):
-    """the six test cubes' level 0, float32 [6, s, s, 4], and their level counts; specials scattered into one face"""
+    """the seven test cubes' level 0, float32 [6, s, s, 4], and their level counts; specials scattered into one face"""
     rng = np.random.default_rng(20)
     if name == "4^2 x 3":
         lv, mips = rgba((rng.random((6, 4, 4, 3)) ** 4 * 200).astype(np.float32)), 3
+    elif name == "8^2 x 4":
+        lv, mips = rgba((rng.random((6, 8, 8, 3)) ** 4 * 200).astype(np.float32)), 4
     elif name == "12^2 x 4":
         lv, mips = rgba(smooth[:, :12, :12]), 4
     elif name == "32^2 x 6":
@@ -91,9 +93,9 @@ def encode_with_guards(ctx, cube, size, mips):
     return [g[16:16 + n] for g in got], all((g[:16] == FILL).all() and (g[16 + n:] == FILL).all() for g in got)
 
 
-@pytest.mark.parametrize("name", ["4^2 x 3", "12^2 x 4", "32^2 x 6", "64^2 x 7", "64^2 x 1", "256^2 x 9"])
+@pytest.mark.parametrize("name", ["4^2 x 3", "8^2 x 4", "12^2 x 4", "32^2 x 6", "64^2 x 7", "64^2 x 1", "256^2 x 9"])
 def test_encode_equals_the_restatement(ctx, smooth, name):
-    """every block of all six faces equals tests/bc6h_encode_ref.py byte for byte: partial blocks (levels of 2 and 1, of 6 and 3), the
+    """every block of all six faces equals tests/bc6h_encode_ref.py byte for byte: partial blocks (levels of 2 and 1 below 4 and below 8, of 6 and 3), the
     smooth fixture, noise whose waves straddle faces and levels, a single-level chain and one larger heavy-tailed cube (more than one
     workgroup per level), NaN, +-inf, negatives, -0.0, 1e9, 65504, rounding ties and subnormal halves scattered into one face; nothing
     is written outside the six chains"""

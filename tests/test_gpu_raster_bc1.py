@@ -73,7 +73,8 @@ def test_bc1_decode_equals_the_restatement(ctx):
     table = fixture_table()
     assert len(table) == 20 and {t["format"] for t in table} == set(FORMATS)
     rng = np.random.default_rng(11)
-    for w, h, mips in ((1, 1, 1), (13, 7, 3), (7, 13, 3), (37, 21, 5), (50, 19, 5), (128, 32, 4), (5, 70, 3), (258, 130, 8)):
+    for w, h, mips in ((1, 1, 1), (13, 7, 3), (7, 13, 3), (37, 21, 5), (50, 19, 5), (128, 32, 4), (5, 70, 3), (258, 130, 8), (20, 12, 3),
+                       (9, 5, 3)):
         table += [random_bc1(rng, w, h, fmt, mips) for fmt in FORMATS]
     pairs = upload_bc1(ctx, table)
     decoded = decode_on_gpu(ctx, pairs, table)

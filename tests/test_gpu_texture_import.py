@@ -81,6 +81,9 @@ def encode_cases():
         cases.append(("odd", fmt, scene.mip_chain(random_level0(rng, 37, 21, fmt))))
         cases.append(("12 -> 6 -> 3", fmt, scene.mip_chain(stored_level0(gradient_noise_image(35, 12, 12), fmt), 3)))
         cases.append(("one level", fmt, scene.mip_chain(stored_level0(noise_image(36, 50, 19), fmt), 1)))
+    # three levels of sides that are no multiple of 4, down to one block (20 -> 10 -> 5) and down to a row of two texels (9 x 5 -> 2 x 1)
+    cases.append(("20 x 12 x 3", 61, scene.mip_chain(random_level0(rng, 20, 12, 61), 3)))
+    cases.append(("9 x 5 x 3", 87, scene.mip_chain(random_level0(rng, 9, 5, 87), 3)))
     return cases
 
 
@@ -88,7 +91,7 @@ def test_bc1_encode_equals_the_restatement_and_decodes_to_it(ctx):
     """pbr_bc1_encode == tests/bc1_encode_ref.py, bit for bit (partial blocks included), nothing written past the blocks; and
     pbr_bc1_decode of the GPU's blocks is bc1_ref's decode of the restatement's"""
     cases = encode_cases()
-    assert len(cases) == 20 + 5 * len(FORMATS) and {c[1] for c in cases[:20]} == set(FORMATS) and all(len(c[2]) == 8 for c in cases[:20])
+    assert len(cases) == 20 + 5 * len(FORMATS) + 2 and {c[1] for c in cases[:20]} == set(FORMATS) and all(len(c[2]) == 8 for c in cases[:20])
     for what, fmt, levels in cases:
         h, w = levels[0].shape[:2]
         mips = len(levels)

@@ -17,11 +17,9 @@ int main(int argc, char** argv) {
     uint32_t head[2];
     if (std::fread(head, 4, 2, in) != 2) { std::fprintf(stderr, "truncated header\n"); return 2; }
     const uint32_t size = head[0], mips = head[1];
-    uint32_t max_levels = 0;
-    for (uint32_t s = size; s; s >>= 1) max_levels++;
-    if (size < 4 || size > 8192 || (size & 3u) || mips < 1 || mips > max_levels) { std::fprintf(stderr, "bad cube description\n"); return 2; }
+    if (!bc6h_chain::chain_ok(size, mips)) { std::fprintf(stderr, "bad cube description\n"); return 2; }
     bc6h_enc::Cube L;
-    bc6h_enc::fill_levels(L, size, mips);
+    bc6h_chain::fill(L, size, mips);
     const size_t texels = (size_t)L.first_texel[mips - 1] + 6u * (size_t)(size >> (mips - 1)) * (size >> (mips - 1));
     std::vector<bc6h_enc::Texel> cube(texels);
     if (std::fread(cube.data(), 16, texels, in) != texels) { std::fprintf(stderr, "truncated cube\n"); return 2; }
