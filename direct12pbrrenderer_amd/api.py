@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from .structs import (ShadeTables, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, texture2d_bytes)
+                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, texture2d_bytes)
 
 
 class PbrError(RuntimeError):
@@ -206,10 +206,11 @@ class PbrContext:
         self._check(self.lib.pbr_bc6h_decode_cube(self.h, C.byref(ptrs), int(size), int(mip_levels), _ptr(out)))
         return out
 
-    def bc6h_encode_cube(self, cube, size, mip_levels, out=None):
-        """pbr_bc6h_encode_cube, the inverse of bc6h_decode_cube: the fp32 RGBA cube chain (device float32 [cube_texels(size,
+    def bc6h_encode_cube(self, cube, size, mip_levels, out=None, two_region=False):
+        """pbr_bc6h_encode_cube_ex, the inverse of bc6h_decode_cube: the fp32 RGBA cube chain (device float32 [cube_texels(size,
         mip_levels), 4]; alpha ignored) -> six BC6H_UF16 face chains (device uint8, structs.bc6h_chain_bytes each), in the order px, nx,
-        py, ny, pz, nz.  out: six device tensors of that size or six device addresses to write to instead."""
+        py, ny, pz, nz.  out: six device tensors of that size or six device addresses to write to instead.  two_region: the ten
+        two-region modes are candidates as well (PBR_BC6H_ENCODE_TWO_REGION); without it the four one-region modes, as before."""
         nbytes = bc6h_chain_bytes(size, mip_levels)
         if isinstance(cube, torch.Tensor) and nbytes and cube.numel() * cube.element_size() != 16 * cube_texels(size, mip_levels):
             raise PbrError(f"bc6h_encode_cube: a cube of {cube.numel() * cube.element_size()} bytes, {size}^2 x {mip_levels} levels takes "
@@ -220,14 +221,15 @@ class PbrContext:
             out = [self.empty((nbytes,), torch.uint8) for _ in range(6)]
         out = list(out)
         ptrs = _bc6h_faces("bc6h_encode_cube", out, size, mip_levels)
-        self._check(self.lib.pbr_bc6h_encode_cube(self.h, _ptr(cube), int(size), int(mip_levels), C.byref(ptrs)))
+        self._check(self.lib.pbr_bc6h_encode_cube_ex(self.h, _ptr(cube), int(size), int(mip_levels), C.byref(ptrs),
+                                                     BC6H_ENCODE_TWO_REGION if two_region else 0))
         return out
 
-    def import_sky(self, level0, mip_levels=None):
+    def import_sky(self, level0, mip_levels=None, two_region=False):
         """The reference's ImportCubeMap from decoded faces on: level 0 (host float32 [6, size, size, 4] or the flat equivalent) is
         uploaded, its box mips made (cube_gen_mips), the SH pack projected from the fp32 level 0 — before compression, where the
         reference computes it — and the chain compressed (bc6h_encode_cube).  Returns (faces, sh_pack): six device uint8 chains and
-        the 28 floats on the device; host.write_cubemap_file of their host copies is the sky's file."""
+        the 28 floats on the device; host.write_cubemap_file of their host copies is the sky's file.  two_region: bc6h_encode_cube's."""
         lv0 = np.ascontiguousarray(level0, dtype=np.float32).reshape(-1, 4)
         size = int(round((len(lv0) // 6) ** 0.5))
         if 6 * size * size != len(lv0):
@@ -239,7 +241,7 @@ class PbrContext:
         cube[:len(lv0)].copy_(torch.from_numpy(lv0))
         self.cube_gen_mips(cube, size, mips)
         sh = self.sh9_project(cube, size, mips)
-        return self.bc6h_encode_cube(cube, size, mips), sh
+        return self.bc6h_encode_cube(cube, size, mips, two_region=two_region), sh
 
     def sh9_project(self, sky, sky_size, sky_mips=1, out=None):
         out = out if out is not None else self.empty((28,), torch.float32)

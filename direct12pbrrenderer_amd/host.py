@@ -8,6 +8,8 @@ import os
 
 import numpy as np
 
+from .structs import BC6H_ENCODE_TWO_REGION
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpbr_host.so")
 _u32, _vp, _int = C.c_uint32, C.c_void_p, C.c_int
@@ -63,6 +65,8 @@ SIGNATURES = {
     "pbrh_import_texture": (C.c_long, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_import_cubemap": (C.c_long, [_vp, _vp, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_import_cubemap_dir": (C.c_long, [_vp, C.c_char_p, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_import_cubemap_ex": (C.c_long, [_vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_import_cubemap_dir_ex": (C.c_long, [_vp, C.c_char_p, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None
@@ -273,33 +277,34 @@ class HostRenderer:
             raise HostError(err.value.decode())
         return out.tobytes()
 
-    def import_cubemap(self, level0, mip_levels=None):
-        """pbrh_import_cubemap: host level 0 of a sky (float32 [6, size, size, 4] or the flat equivalent, faces px, nx, py, ny, pz, nz)
+    def import_cubemap(self, level0, mip_levels=None, two_region=False):
+        """pbrh_import_cubemap_ex: host level 0 of a sky (float32 [6, size, size, 4] or the flat equivalent, faces px, nx, py, ny, pz, nz)
         -> the bytes of the reference's serialized sky cube: box mips, the SH pack of the fp32 level 0 and the BC6H_UF16 chains (all
-        levels by default), made on the GPU.  set_skybox_file and DeferredFrame.set_sky_file take them as they are."""
+        levels by default), made on the GPU.  set_skybox_file and DeferredFrame.set_sky_file take them as they are.  two_region: the
+        compression may use the ten two-region modes as well (PBR_BC6H_ENCODE_TWO_REGION); the file is read like any other."""
         lv0 = np.ascontiguousarray(level0, dtype=np.float32).reshape(-1, 4)
         size = int(round((len(lv0) // 6) ** 0.5))
         if 6 * size * size != len(lv0):
             raise HostError(f"import_cubemap: level 0 of {len(lv0)} texels is not six square faces")
-        mips = 0 if mip_levels is None else int(mip_levels)
+        mips, flags = 0 if mip_levels is None else int(mip_levels), BC6H_ENCODE_TWO_REGION if two_region else 0
         err = C.create_string_buffer(256)
-        need = self.lib.pbrh_import_cubemap(self.h, None, size, mips, None, 0, err, 256)
+        need = self.lib.pbrh_import_cubemap_ex(self.h, None, size, mips, flags, None, 0, err, 256)
         if need < 0:
             raise HostError(err.value.decode())
         out = np.zeros(need, dtype=np.uint8)
-        if self.lib.pbrh_import_cubemap(self.h, lv0.ctypes.data, size, mips, out.ctypes.data, out.size, err, 256) != need:
+        if self.lib.pbrh_import_cubemap_ex(self.h, lv0.ctypes.data, size, mips, flags, out.ctypes.data, out.size, err, 256) != need:
             raise HostError(err.value.decode())
         return out.tobytes()
 
-    def import_cubemap_dir(self, path, mip_levels=None):
-        """pbrh_import_cubemap_dir: import_cubemap of <path>/{px,nx,py,ny,pz,nz}.hdr (load_skybox's parse, RGBE expanded on the GPU)"""
-        mips = 0 if mip_levels is None else int(mip_levels)
+    def import_cubemap_dir(self, path, mip_levels=None, two_region=False):
+        """pbrh_import_cubemap_dir_ex: import_cubemap of <path>/{px,nx,py,ny,pz,nz}.hdr (load_skybox's parse, RGBE expanded on the GPU)"""
+        mips, flags = 0 if mip_levels is None else int(mip_levels), BC6H_ENCODE_TWO_REGION if two_region else 0
         err = C.create_string_buffer(256)
-        need = self.lib.pbrh_import_cubemap_dir(self.h, os.fsencode(path), mips, None, 0, err, 256)
+        need = self.lib.pbrh_import_cubemap_dir_ex(self.h, os.fsencode(path), mips, flags, None, 0, err, 256)
         if need < 0:
             raise HostError(err.value.decode())
         out = np.zeros(need, dtype=np.uint8)
-        if self.lib.pbrh_import_cubemap_dir(self.h, os.fsencode(path), mips, out.ctypes.data, out.size, err, 256) != need:
+        if self.lib.pbrh_import_cubemap_dir_ex(self.h, os.fsencode(path), mips, flags, out.ctypes.data, out.size, err, 256) != need:
             raise HostError(err.value.decode())
         return out.tobytes()
 

@@ -141,7 +141,8 @@ std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, b
 }
 
 size_t ImportCubeMap(pbr_ctx* ctx, const float* cube_mip0, const HdrImage* rgbe_faces, uint32_t size, uint32_t mip_levels,
-                     uint8_t* file, size_t bytes) {
+                     uint8_t* file, size_t bytes, uint32_t flags) {
+    if (flags & ~PBR_BC6H_ENCODE_TWO_REGION) throw HipException("cube-map import: unknown flag");
     if (mip_levels == 0)
         for (uint32_t s = size; s; s >>= 1) mip_levels++;
     const size_t chain = pbr_bc6h_chain_bytes(size, mip_levels);
@@ -168,7 +169,7 @@ size_t ImportCubeMap(pbr_ctx* ctx, const float* cube_mip0, const HdrImage* rgbe_
     check(pbr_sh9_project(ctx, &c, (float*)pack.Ptr()));
     void* faces_dev[6];             // (hipMalloc is 256-byte aligned and a chain is a multiple of 16 bytes)
     for (int f = 0; f < 6; f++) faces_dev[f] = (uint8_t*)blocks.Ptr() + f * chain;
-    check(pbr_bc6h_encode_cube(ctx, (const float*)cube.Ptr(), size, mip_levels, faces_dev));
+    check(pbr_bc6h_encode_cube_ex(ctx, (const float*)cube.Ptr(), size, mip_levels, faces_dev, flags));
     check(pbr_sync(ctx));
     std::vector<uint8_t> host(6 * chain);
     pbr_sh_pack sh{};

@@ -57,12 +57,12 @@ std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, b
 // ResourceLoader::ImportCubeMap (ResourceLoader.cpp:279-299) on the GPU, from decoded faces on: level 0 — cube_mip0 (host, 6 x size^2
 // fp32 RGBA) or, when rgbe_faces is given, six parsed .hdr faces expanded by pbr_rgbe_decode — is uploaded, its box mips made
 // (pbr_cube_gen_mips), the SH pack projected from the fp32 level 0 BEFORE compression (where the reference computes it, in the
-// CubeMapTextureData constructor, BasicStorage.h:313), the chain compressed (pbr_bc6h_encode_cube), read back and written by
-// WriteCubeMapFile with format 2.  mip_levels 0 = the full chain.  Returns the file's size; with file == nullptr only the size, and
-// nothing runs.  Blocks until the GPU is done.  Throws HipException: a size or level count pbr_bc6h_chain_bytes rejects, a null
-// level 0, a buffer smaller than the file.
+// CubeMapTextureData constructor, BasicStorage.h:313), the chain compressed (pbr_bc6h_encode_cube_ex with `flags`: 0, or
+// PBR_BC6H_ENCODE_TWO_REGION for the two-region modes as well), read back and written by WriteCubeMapFile with format 2.
+// mip_levels 0 = the full chain.  Returns the file's size; with file == nullptr only the size, and nothing runs.  Blocks until the GPU is done.  Throws HipException: a size or level count pbr_bc6h_chain_bytes rejects, a null
+// level 0, a buffer smaller than the file, an unknown flag.
 struct HdrImage;
 size_t ImportCubeMap(pbr_ctx* ctx, const float* cube_mip0, const HdrImage* rgbe_faces, uint32_t size, uint32_t mip_levels,
-                     uint8_t* file, size_t bytes);
+                     uint8_t* file, size_t bytes, uint32_t flags = 0);
 
 }  // namespace MRendererHip

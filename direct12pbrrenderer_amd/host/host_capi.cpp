@@ -205,10 +205,15 @@ long pbrh_write_cubemap_file(const void* const faces[6], uint32_t size, uint32_t
 
 long pbrh_import_cubemap(pbrh_renderer* r, const float* cube_mip0, uint32_t size, uint32_t mip_levels, uint8_t* file_out, size_t file_bytes,
                          char* err, size_t err_len) {
+    return pbrh_import_cubemap_ex(r, cube_mip0, size, mip_levels, 0u, file_out, file_bytes, err, err_len);
+}
+
+long pbrh_import_cubemap_ex(pbrh_renderer* r, const float* cube_mip0, uint32_t size, uint32_t mip_levels, uint32_t flags, uint8_t* file_out,
+                            size_t file_bytes, char* err, size_t err_len) {
     try {
         if (!r) throw HipException("pbrh_import_cubemap: null renderer");
         if (file_out && !cube_mip0) throw HipException("pbrh_import_cubemap: null level 0");
-        return (long)ImportCubeMap(r->scheduler->CommandList()->Context(), cube_mip0, nullptr, size, mip_levels, file_out, file_bytes);
+        return (long)ImportCubeMap(r->scheduler->CommandList()->Context(), cube_mip0, nullptr, size, mip_levels, file_out, file_bytes, flags);
     } catch (const std::exception& e) {
         if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
         return -1;
@@ -216,12 +221,17 @@ long pbrh_import_cubemap(pbrh_renderer* r, const float* cube_mip0, uint32_t size
 }
 
 long pbrh_import_cubemap_dir(pbrh_renderer* r, const char* dir, uint32_t mip_levels, uint8_t* file_out, size_t file_bytes, char* err, size_t err_len) {
+    return pbrh_import_cubemap_dir_ex(r, dir, mip_levels, 0u, file_out, file_bytes, err, err_len);
+}
+
+long pbrh_import_cubemap_dir_ex(pbrh_renderer* r, const char* dir, uint32_t mip_levels, uint32_t flags, uint8_t* file_out, size_t file_bytes,
+                                char* err, size_t err_len) {
     try {
         if (!r) throw HipException("pbrh_import_cubemap_dir: null renderer");
         if (!dir) throw HipException("pbrh_import_cubemap_dir: null directory");
         HdrImage faces[6];
         const uint32_t size = LoadCubeMapFaces(dir, faces);
-        return (long)ImportCubeMap(r->scheduler->CommandList()->Context(), nullptr, faces, size, mip_levels, file_out, file_bytes);
+        return (long)ImportCubeMap(r->scheduler->CommandList()->Context(), nullptr, faces, size, mip_levels, file_out, file_bytes, flags);
     } catch (const std::exception& e) {
         if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
         return -1;

@@ -88,6 +88,13 @@ long pbrh_import_cubemap(pbrh_renderer* r, const float* cube_mip0, uint32_t size
                          uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
 long pbrh_import_cubemap_dir(pbrh_renderer* r, const char* dir, uint32_t mip_levels,
                              uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
+/* The same two with the flags of pbr_bc6h_encode_cube_ex: 0 is the call above, PBR_BC6H_ENCODE_TWO_REGION lets the compression use
+ * the ten two-region modes as well (an ordinary cube-map file either way: every reader decodes all fourteen modes); any other bit
+ * is refused, the size query included. */
+long pbrh_import_cubemap_ex(pbrh_renderer* r, const float* cube_mip0, uint32_t size, uint32_t mip_levels, uint32_t flags,
+                            uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
+long pbrh_import_cubemap_dir_ex(pbrh_renderer* r, const char* dir, uint32_t mip_levels, uint32_t flags,
+                                uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
 /* CPU only: parse one .hdr file held in memory (header + flat / run-length scanlines) into RGBE texels */
 int pbrh_parse_hdr(const uint8_t* file, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgbe, size_t rgbe_bytes, char* err, size_t err_len);
 /* CPU only, stateless: one of the reference's serialized 2D textures (a texture asset's _data.bin) held in memory: TextureInfo (uint16

@@ -169,6 +169,9 @@ def texture2d_bytes(width, height, mip_levels, fmt):
 BC6H_MAX_SIZE = 8192                                  # PBR_BC6H_MAX_SIZE
 
 
+BC6H_ENCODE_TWO_REGION = 1     # PBR_BC6H_ENCODE_TWO_REGION: pbr_bc6h_encode_cube_ex may use the ten two-region modes as well
+
+
 def bc6h_chain_bytes(size, mip_levels):
     """pbr_bc6h_chain_bytes: the bytes of one cube face's mip chain as BC6H blocks (level i max(1, ((size >> i) + 3) // 4)^2 blocks
     of 16 bytes); 0 for what pbr_bc6h_decode_cube refuses (size 0, not a multiple of 4 or above BC6H_MAX_SIZE, mip_levels 0 or

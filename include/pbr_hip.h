@@ -254,7 +254,7 @@ pbr_status pbr_bc6h_decode_cube(pbr_ctx* ctx, const void* const face_blocks[6], 
  * cube_rgba), size 0, not a multiple of 4 or above PBR_BC6H_MAX_SIZE, mip_levels 0 or above floor(log2(size)) + 1.
  * The encoding rule, pinned, all in integers after the first step (`/` is FLOOR division; per-texel errors fit uint32, block sums
  * and the least-squares terms are 64-bit); tests/bc6h_encode_ref.py restates it in numpy and the kernel is held to it bit for bit.
- * Only one-region modes are emitted.
+ * Only one-region modes are emitted (the two-region ones: pbr_bc6h_encode_cube_ex below).
  *   Half code of a channel value v: h = the IEEE half bit pattern of clamp(v, 0, 65504) rounded to nearest even.  NaN gives 0; any
  *   v <= 0 gives 0, -0.0 included (the sign bit is cleared); +inf and anything above 65504 give 0x7BFF; subnormal halves stay
  *   subnormal codes.  Its target in 16-bit endpoint space is t = (64 h + 30) / 31, the least x whose decode finish (31 x) >> 6 is h.
@@ -276,8 +276,43 @@ pbr_status pbr_bc6h_decode_cube(pbr_ctx* ctx, const void* const face_blocks[6], 
  *   0x03 always is.  The candidate of least error is kept, the earlier one on ties.
  *   Emit in the bit layout of the decode rule, the delta in two's complement of its width.  The anchor's high bit is always 0, no
  *   reserved mode is emitted, no texel can decode above 0x7BFF, and a block of one colour is lossless through mode 0x0f.
- * Two-region modes, BC6H_SF16 and parity with DirectXTex's encoder (what the reference's import runs) are out of scope. */
+ * BC6H_SF16 and parity with DirectXTex's encoder (what the reference's import runs) are out of scope; the two-region modes are
+ * behind pbr_bc6h_encode_cube_ex's flag. */
 pbr_status pbr_bc6h_encode_cube(pbr_ctx* ctx, const float* cube_rgba, uint32_t size, uint32_t mip_levels, void* const face_blocks_out[6]);
+/* pbr_bc6h_encode_cube with flags.  flags == 0: the same kernel, the same bytes.  PBR_BC6H_ENCODE_TWO_REGION: a block may also take one
+ * of the ten two-region modes, by the rule below (a second kernel, k_bc6h_encode_cube2; one launch as well).  Any other bit is
+ * refused (PBR_ERR_INVALID, nothing enqueued), as is everything pbr_bc6h_encode_cube refuses.  What it writes is read by
+ * pbr_bc6h_decode_cube and pbr_skybox_bc6h like any other chain.
+ * The two-region rule, pinned; it extends the rule above and reuses its pieces unchanged (half code, t, partial blocks, the start,
+ * the refinement formulas, "strictly smaller replaces, the earlier keeps a tie"); all integers, `/` is FLOOR division;
+ * tests/bc6h_encode2_ref.py restates it in numpy and the kernel is held to it bit for bit.
+ *   1. The one-region result: the rule above as it is.  If its error is 0 it is emitted and nothing below runs.
+ *   2. fit3(a, b, mask): fit with the 3-bit weights 0, 9, 18, 27, 37, 46, 55, 64 (palette entries k = 0 .. 7) over the texels of
+ *      `mask` — a region of a shape, intersected with the level —, the lowest k on ties, the same distance; its error is the sum
+ *      over those texels.
+ *   3. Shape search, shapes 0 .. 31 in order.  For each of the shape's two regions: over its texels inside the level, the start of
+ *      the rule above (lo and hi of t, dom, the covariance signs, n = the number of those texels) gives (A, B), and the region's
+ *      estimate is fit3(A, B, region)'s error.  A region with no texel inside the level has A = B = 0 and estimate 0.  The shape's
+ *      estimate is the sum of the two; the shape of least estimate is chosen, the lowest number on ties.  (Region 0 is never empty:
+ *      texel 0 is in it and inside every level.)
+ *   4. Refinement of the chosen shape, region by region: the start's fit3, then at most two refinements at 16 bits by the formulas
+ *      above with alpha = 64 - w3[index], beta = w3[index] and the sums over the region's texels; det == 0 stops that region; a
+ *      refinement replaces the region's pair, indices and error only if the region's error falls strictly, otherwise that region
+ *      stops.  A region 1 with no texel inside the level then takes region 0's pair (e2 = e0, e3 = e1).
+ *   5. Modes, tried in the order 0x00, 0x01, 0x02, 0x06, 0x0a, 0x0e, 0x12, 0x16, 0x1a, 0x1e, n = the mode's endpoint bits: all four
+ *      endpoints >> (16 - n); each region fit3 on its pair unquantized by the decode rule; the candidate's error is the sum of the
+ *      two.  Region 0: if texel 0's index is >= 4, e0 and e1 are exchanged and the index of every texel of region 0 inside the level
+ *      becomes 7 - index.  Region 1: the same with the shape's anchor texel and e2, e3 (an anchor outside the level has index 0 and
+ *      never exchanges).  For the nine transformed modes the stored deltas e1 - e0, e2 - e0, e3 - e0, taken AFTER the exchanges,
+ *      must each fit the signed width of their channel in that mode, otherwise the mode is no candidate; 0x1e always is.
+ *   6. The one-region result stays unless a two-region candidate's error is strictly smaller; among those the earlier keeps a tie.
+ *   7. Emit in the bit layout of the decode rule: the header, the shape at bits 77 .. 81, 46 index bits from bit 82 (both anchors
+ *      store two bits, the other texels three; a texel outside the level 0), the deltas in two's complement of their width.
+ *   No reserved mode is emitted, no texel decodes above 0x7BFF, both anchors' high bits are 0.  One shape is searched past the
+ *   estimate; BC6H_SF16 and parity with DirectXTex's encoder stay out of scope. */
+#define PBR_BC6H_ENCODE_TWO_REGION 1u
+pbr_status pbr_bc6h_encode_cube_ex(pbr_ctx* ctx, const float* cube_rgba, uint32_t size, uint32_t mip_levels, void* const face_blocks_out[6],
+                                   uint32_t flags);
 
 /* env_map_gen.hlsl:50-105, all PBR_ENV_MIPS dispatches of PreFilterEnvMapPass::Execute
  * (DeferredPipeline.cpp:77-115): mip i is filtered with roughness i/(mips-1).

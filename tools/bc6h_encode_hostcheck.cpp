@@ -1,7 +1,8 @@
 // bc6h_encode_hostcheck.cpp — the body of k_bc6h_encode_cube (csrc/bc6h_encode_block.hpp) compiled for the host, lane after lane, in a
 // program of its own: built with -fsanitize=address,undefined and compared with tests/bc6h_encode_ref.py by tests/test_bc6h_encode_cpu.py
 // (and by hand: tools/README.md).  Input file: uint32 size, uint32 mip_levels, the pbr_cube_f32 chain as fp32 RGBA.  Output file: the
-// six face chains one after the other.  Every buffer is exactly as large as the entry point's contract says, so an access outside it
+// six face chains one after the other.  A third argument `two_region` runs the lane of k_bc6h_encode_cube2 (PBR_BC6H_ENCODE_TWO_REGION,
+// compared with tests/bc6h_encode2_ref.py by tests/test_bc6h_encode2_cpu.py).  Every buffer is exactly as large as the entry point's contract says, so an access outside it
 // is an ASan report.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o bc6h_encode_hostcheck tools/bc6h_encode_hostcheck.cpp
 #include <cstdio>
@@ -11,7 +12,8 @@
 #include "../direct12pbrrenderer_amd/csrc/bc6h_encode_block.hpp"
 
 int main(int argc, char** argv) {
-    if (argc != 3) { std::fprintf(stderr, "usage: %s cube.bin blocks.bin\n", argv[0]); return 2; }
+    const bool two = argc == 4 && std::strcmp(argv[3], "two_region") == 0;
+    if (argc != 3 && !two) { std::fprintf(stderr, "usage: %s cube.bin blocks.bin [two_region]\n", argv[0]); return 2; }
     FILE* in = std::fopen(argv[1], "rb");
     if (!in) { std::fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
     uint32_t head[2];
@@ -30,7 +32,10 @@ int main(int argc, char** argv) {
         faces[f].assign(face_blocks, bc6h_enc::Block{0x5a5a5a5au, 0x5a5a5a5au, 0x5a5a5a5au, 0x5a5a5a5au});
         L.face[f] = faces[f].data();
     }
-    for (uint32_t g = 0; g < L.lanes; g++) bc6h_enc::encode_lane(L, g, cube.data());
+    for (uint32_t g = 0; g < L.lanes; g++) {
+        if (two) bc6h_enc::encode_lane<true>(L, g, cube.data());
+        else bc6h_enc::encode_lane(L, g, cube.data());
+    }
     FILE* out = std::fopen(argv[2], "wb");
     if (!out) { std::fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
     for (int f = 0; f < 6; f++)

@@ -6,6 +6,8 @@ Frames: 1440x960 and 3840x2160, stencil all zero (every pixel is sky), the refer
 Cubes: 2048^2 x 12 and 512^2 x 10, two kinds of content each:
   synth    synth.env_cube's 512^2 sky (gradient, sun lobe, 5 % noise; above 512^2 the faces are tiled), box mips from
            pbr_cube_gen_mips, compressed by pbr_bc6h_encode_cube: the importer's files, four one-region modes;
+  synth2   the same cube compressed with PBR_BC6H_ENCODE_TWO_REGION: the importer's files with the flag, the mode mix of a real
+           two-region encoder;
   random   seeded random bytes: every mode, partition and reserved code in every wave — the worst case for a kernel that runs every
            mode header its wave holds.
 Per row the median of three windows of --iters calls (HIP events, 5 warm-up calls per window), the two targets compared bit for bit
@@ -94,14 +96,14 @@ def main():
     for size, mips in (tuple(int(x) for x in c.split("x")) for c in a.cubes.split(",")):
         n = bc6h_chain_bytes(size, mips)
         texels = cube_texels(size, mips)
-        for content in ("synth", "random"):
-            if content == "synth":
+        for content in ("synth", "synth2", "random"):
+            if content != "random":
                 cube = ctx.empty((texels, 4), torch.float32)
                 e = min(size, SYNTH_EDGE)
                 lv = synth0 if e == SYNTH_EDGE else torch.from_numpy(synth.env_cube(e, 1).reshape(6, e, e, 4))
                 cube[:6 * size * size].copy_(lv.repeat(1, size // e, size // e, 1).reshape(-1, 4))
                 ctx.cube_gen_mips(cube, size, mips)
-                faces = ctx.bc6h_encode_cube(cube, size, mips)
+                faces = ctx.bc6h_encode_cube(cube, size, mips, two_region=content == "synth2")
                 ctx.sync()
                 del cube
             else:
