@@ -73,6 +73,9 @@ SIGNATURES = {
     "pbr_bc6h_decode_cube": (_int, [_vp, C.POINTER(_vp * 6), _u32, _u32, _vp]),
     "pbr_bc6h_encode_cube": (_int, [_vp, _vp, _u32, _u32, C.POINTER(_vp * 6)]),
     "pbr_bc6h_encode_cube_ex": (_int, [_vp, _vp, _u32, _u32, C.POINTER(_vp * 6), _u32]),
+    "pbr_equirect_to_cube": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32, _u32]),
+    "pbr_equirect_default_size": (_u32, [_u32]),
+    "pbr_equirect_default_samples": (_u32, [_u32, _u32]),
     "pbr_texture2d_gen_mips": (_int, [_vp, _vp, _u32, _u32, _u32, _u32]),
     "pbr_bc1_encode": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "pbr_gbuffer_raster_textured_scratch_bytes": (_sz, [_u32, _u32, _u32]),

@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from .structs import (ShadeTables, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, texture2d_bytes)
+                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
 
 
 class PbrError(RuntimeError):
@@ -239,6 +239,45 @@ class PbrContext:
             raise PbrError(f"bad BC6H cube description: {size}^2, {mips} levels")
         cube = self.empty((cube_texels(size, mips), 4), torch.float32)
         cube[:len(lv0)].copy_(torch.from_numpy(lv0))
+        self.cube_gen_mips(cube, size, mips)
+        sh = self.sh9_project(cube, size, mips)
+        return self.bc6h_encode_cube(cube, size, mips, two_region=two_region), sh
+
+    def equirect_to_cube(self, pano, pw, ph, size, samples=1, rgbe=False, out=None):
+        """pbr_equirect_to_cube: an equirectangular panorama (device; float32 [ph, pw, 4], or with rgbe uint8 [ph, pw, 4] Radiance
+        texels, decoded where they are fetched) -> level 0 of a sky cube, device float32 [6 size^2, 4], faces px, nx, py, ny, pz, nz,
+        alpha 1: bilinear taps (longitude wraps, latitude clamps), samples^2 sub-samples per texel, samples one of 1, 2, 4, 8.  out: a
+        device float32 tensor of at least 6 size^2 texels (a cube chain, say) whose level 0 is written instead."""
+        if isinstance(pano, torch.Tensor) and pano.numel() * pano.element_size() != int(pw) * int(ph) * (4 if rgbe else 16):
+            raise PbrError(f"equirect_to_cube: a panorama of {pano.numel() * pano.element_size()} bytes, {pw} x {ph} "
+                           f"{'RGBE' if rgbe else 'fp32'} texels take {int(pw) * int(ph) * (4 if rgbe else 16)}")
+        if out is None:
+            if not 1 <= int(size) <= BC6H_MAX_SIZE:
+                raise PbrError(f"equirect_to_cube: size {size} is not 1 .. {BC6H_MAX_SIZE}")
+            out = self.empty((6 * int(size) * int(size), 4), torch.float32)
+        elif isinstance(out, torch.Tensor) and out.numel() * out.element_size() < 96 * int(size) * int(size):
+            raise PbrError(f"equirect_to_cube: out holds {out.numel() * out.element_size()} bytes, level 0 of size {size} takes {96 * int(size) * int(size)}")
+        self._check(self.lib.pbr_equirect_to_cube(self.h, _ptr(pano), int(pw), int(ph), _ptr(out), int(size), int(samples),
+                                                  EQUIRECT_SRC_RGBE if rgbe else 0))
+        return out
+
+    def import_sky_equirect(self, pano_host, size=None, samples=None, mip_levels=None, two_region=False):
+        """import_sky with equirect_to_cube in front: one equirectangular panorama (host float32 [ph, pw, 4], or uint8 [ph, pw, 4]
+        Radiance RGBE texels, which are uploaded as they are and sampled in place) is resampled into level 0, then the box mips, the SH
+        pack of the fp32 level 0 and the BC6H_UF16 chains as import_sky makes them.  size / samples None: the default rules
+        (structs.equirect_default_size / equirect_default_samples).  Returns (faces, sh_pack) exactly as import_sky does."""
+        pano = np.ascontiguousarray(pano_host)
+        if pano.ndim != 3 or pano.shape[2] != 4 or pano.dtype not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise PbrError(f"import_sky_equirect: a panorama is float32 or uint8 [ph, pw, 4], got {pano.dtype} {pano.shape}")
+        ph, pw = pano.shape[:2]
+        size = equirect_default_size(pw) if size is None else int(size)
+        samples = equirect_default_samples(pw, size) if samples is None else int(samples)
+        mips = size.bit_length() if mip_levels is None else int(mip_levels)
+        if not bc6h_chain_bytes(size, mips):
+            raise PbrError(f"bad BC6H cube description: {size}^2, {mips} levels")
+        cube = self.empty((cube_texels(size, mips), 4), torch.float32)
+        dev = self.upload(pano)
+        self.equirect_to_cube(dev, pw, ph, size, samples, rgbe=pano.dtype == np.uint8, out=cube)
         self.cube_gen_mips(cube, size, mips)
         sh = self.sh9_project(cube, size, mips)
         return self.bc6h_encode_cube(cube, size, mips, two_region=two_region), sh

@@ -156,3 +156,30 @@ inline size_t chain_bytes(uint32_t size, uint32_t mip_levels) {
 }
 
 }  // namespace bc6h_chain
+
+// the geometry of pbr_equirect_to_cube (equirect.hip): what it refuses, and the cube size and sub-sample count an import picks when its
+// caller names none (pbr_equirect_default_size / _samples; structs.py restates both)
+namespace equirect {
+
+// the largest power of two <= pw / 4 — a face spans a quarter of the panorama's width, so level 0 is no finer than its source —
+// clamped to [4, PBR_BC6H_MAX_SIZE]
+inline uint32_t default_size(uint32_t pw) {
+    uint32_t s = 4u;
+    while (s < PBR_BC6H_MAX_SIZE && 2u * s <= pw / 4u) s *= 2u;
+    return s;
+}
+// the smallest of 1, 2, 4, 8 with 4 size samples >= pw (every panorama column of the equator under at least one sub-sample); 8 if none is
+inline uint32_t default_samples(uint32_t pw, uint32_t size) {
+    for (uint32_t s = 1u; s < 8u; s *= 2u)
+        if ((uint64_t)4u * size * s >= pw) return s;
+    return 8u;
+}
+// what is wrong with a call's description; nullptr: nothing
+inline const char* refusal(uint32_t pw, uint32_t ph, uint32_t size, uint32_t samples) {
+    if (!pw || !ph || pw > PBR_EQUIRECT_MAX_W || ph > PBR_EQUIRECT_MAX_H) return "panorama size zero or above PBR_EQUIRECT_MAX_W x PBR_EQUIRECT_MAX_H";
+    if (!size || size > PBR_BC6H_MAX_SIZE) return "size zero or above PBR_BC6H_MAX_SIZE";
+    if (samples != 1u && samples != 2u && samples != 4u && samples != 8u) return "samples not 1, 2, 4 or 8";
+    return nullptr;
+}
+
+}  // namespace equirect

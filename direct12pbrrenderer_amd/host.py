@@ -67,6 +67,9 @@ SIGNATURES = {
     "pbrh_import_cubemap_dir": (C.c_long, [_vp, C.c_char_p, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_import_cubemap_ex": (C.c_long, [_vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "pbrh_import_cubemap_dir_ex": (C.c_long, [_vp, C.c_char_p, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_import_cubemap_equirect": (C.c_long, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_import_cubemap_hdr": (C.c_long, [_vp, C.c_char_p, _u32, _u32, _u32, _u32, _vp, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "pbrh_load_skybox_equirect": (_int, [_vp, C.c_char_p, _u32, _u32]),
 }
 
 _lib = None
@@ -307,6 +310,42 @@ class HostRenderer:
         if self.lib.pbrh_import_cubemap_dir_ex(self.h, os.fsencode(path), mips, flags, out.ctypes.data, out.size, err, 256) != need:
             raise HostError(err.value.decode())
         return out.tobytes()
+
+    def import_cubemap_equirect(self, pano, size=None, samples=None, mip_levels=None, two_region=False):
+        """pbrh_import_cubemap_equirect: import_cubemap of ONE equirectangular panorama (host float32 [ph, pw, 4], row 0 the top),
+        resampled into level 0 on the GPU (PbrContext.equirect_to_cube's rule) at `size` with samples^2 sub-samples a texel; None for
+        either: the default rule (structs.equirect_default_size / equirect_default_samples)."""
+        p = np.ascontiguousarray(pano, dtype=np.float32)
+        if p.ndim != 3 or p.shape[2] != 4:
+            raise HostError(f"import_cubemap_equirect: a panorama is float32 [ph, pw, 4], got {p.shape}")
+        ph, pw = p.shape[:2]
+        args = (pw, ph, int(size or 0), int(samples or 0), 0 if mip_levels is None else int(mip_levels), BC6H_ENCODE_TWO_REGION if two_region else 0)
+        err = C.create_string_buffer(256)
+        need = self.lib.pbrh_import_cubemap_equirect(self.h, None, *args, None, 0, err, 256)
+        if need < 0:
+            raise HostError(err.value.decode())
+        out = np.zeros(need, dtype=np.uint8)
+        if self.lib.pbrh_import_cubemap_equirect(self.h, p.ctypes.data, *args, out.ctypes.data, out.size, err, 256) != need:
+            raise HostError(err.value.decode())
+        return out.tobytes()
+
+    def import_cubemap_hdr(self, path, size=None, samples=None, mip_levels=None, two_region=False):
+        """pbrh_import_cubemap_hdr: import_cubemap_equirect of one Radiance .hdr file of any aspect ratio; its RGBE texels are uploaded
+        as they are and decoded where the kernel fetches them"""
+        args = (int(size or 0), int(samples or 0), 0 if mip_levels is None else int(mip_levels), BC6H_ENCODE_TWO_REGION if two_region else 0)
+        err = C.create_string_buffer(256)
+        need = self.lib.pbrh_import_cubemap_hdr(self.h, os.fsencode(path), *args, None, 0, err, 256)
+        if need < 0:
+            raise HostError(err.value.decode())
+        out = np.zeros(need, dtype=np.uint8)
+        if self.lib.pbrh_import_cubemap_hdr(self.h, os.fsencode(path), *args, out.ctypes.data, out.size, err, 256) != need:
+            raise HostError(err.value.decode())
+        return out.tobytes()
+
+    def load_skybox_equirect(self, path, size=None, samples=None):
+        """pbrh_load_skybox_equirect: load_skybox for one equirectangular .hdr — the fp32 sky with box mips and SH9, level 0 resampled
+        from the file's RGBE texels on the GPU; None: the default rule for the size / the sub-sample count"""
+        self._check(self.lib.pbrh_load_skybox_equirect(self.h, os.fsencode(path), int(size or 0), int(samples or 0)))
 
     def set_initial_luminance(self, v):
         self._check(self.lib.pbrh_set_initial_luminance(self.h, float(v)))

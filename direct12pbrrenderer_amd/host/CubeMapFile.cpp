@@ -141,21 +141,29 @@ std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, b
 }
 
 size_t ImportCubeMap(pbr_ctx* ctx, const float* cube_mip0, const HdrImage* rgbe_faces, uint32_t size, uint32_t mip_levels,
-                     uint8_t* file, size_t bytes, uint32_t flags) {
+                     uint8_t* file, size_t bytes, uint32_t flags, const Panorama* pano, uint32_t samples) {
     if (flags & ~PBR_BC6H_ENCODE_TWO_REGION) throw HipException("cube-map import: unknown flag");
+    if (pano) {
+        if (!pano->Width || !pano->Height || pano->Width > PBR_EQUIRECT_MAX_W || pano->Height > PBR_EQUIRECT_MAX_H)
+            throw HipException("cube-map import: a panorama of " + std::to_string(pano->Width) + " x " + std::to_string(pano->Height) + " texels");
+        EquirectDefaults(*pano, size, samples);
+        if (samples != 1 && samples != 2 && samples != 4 && samples != 8) throw HipException("cube-map import: samples not 0, 1, 2, 4 or 8");
+    }
     if (mip_levels == 0)
         for (uint32_t s = size; s; s >>= 1) mip_levels++;
     const size_t chain = pbr_bc6h_chain_bytes(size, mip_levels);
     if (!chain) throw HipException("cube-map import: bad size or level count (" + std::to_string(size) + ", " + std::to_string(mip_levels) + " levels)");
     const size_t total = WriteCubeMapFile(nullptr, size, mip_levels, 2, pbr_sh_pack{}, nullptr, 0);
     if (!file) return total;
-    if (!cube_mip0 && !rgbe_faces) throw HipException("cube-map import: null level 0");
+    if (!cube_mip0 && !rgbe_faces && !(pano && pano->Texels)) throw HipException("cube-map import: null level 0");
     if (bytes < total) throw HipException("cube-map import: output buffer too small");
     auto check = [&](pbr_status st) { if (st != PBR_OK) throw HipException(pbr_last_error(ctx)); };
     const size_t face_texels = (size_t)size * size;
     DeviceMemory cube(pbr_cube_texels(size, mip_levels) * 16), blocks(6 * chain), pack(SH_BYTES);
     // (a blocking copy from pageable memory has landed when it returns: the context's stream needs no event to see it)
-    if (rgbe_faces) {
+    if (pano) {
+        PanoramaToCube(ctx, *pano, (float*)cube.Ptr(), size, samples);
+    } else if (rgbe_faces) {
         DeviceMemory staging(6 * face_texels * 4);
         for (int f = 0; f < 6; f++)
             ThrowIfFailed(hipMemcpy((uint8_t*)staging.Ptr() + f * face_texels * 4, rgbe_faces[f].Rgbe.data(), face_texels * 4, hipMemcpyHostToDevice), "upload rgbe face");

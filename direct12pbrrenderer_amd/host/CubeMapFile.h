@@ -61,8 +61,12 @@ std::shared_ptr<SkyBox> LoadCubeMapFile(pbr_ctx* ctx, const std::string& path, b
 // PBR_BC6H_ENCODE_TWO_REGION for the two-region modes as well), read back and written by WriteCubeMapFile with format 2.
 // mip_levels 0 = the full chain.  Returns the file's size; with file == nullptr only the size, and nothing runs.  Blocks until the GPU is done.  Throws HipException: a size or level count pbr_bc6h_chain_bytes rejects, a null
 // level 0, a buffer smaller than the file, an unknown flag.
+// pano: a third kind of level-0 source (not the reference's, which takes faces only) — an equirectangular panorama, uploaded as it is
+// and resampled into level 0 by pbr_equirect_to_cube with `samples`^2 sub-samples a texel; size 0 / samples 0: the default rules
+// (EquirectDefaults).  The size query reads pano's Width only (Texels may be null).  Everything after level 0 is the same.
 struct HdrImage;
+struct Panorama;
 size_t ImportCubeMap(pbr_ctx* ctx, const float* cube_mip0, const HdrImage* rgbe_faces, uint32_t size, uint32_t mip_levels,
-                     uint8_t* file, size_t bytes, uint32_t flags = 0);
+                     uint8_t* file, size_t bytes, uint32_t flags = 0, const Panorama* pano = nullptr, uint32_t samples = 0);
 
 }  // namespace MRendererHip

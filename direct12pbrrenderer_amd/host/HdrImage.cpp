@@ -140,4 +140,43 @@ std::shared_ptr<SkyBox> LoadCubeMap(pbr_ctx* ctx, const std::string& dir) {
     return sky;
 }
 
+void EquirectDefaults(const Panorama& pano, uint32_t& size, uint32_t& samples) {
+    if (!size) size = pbr_equirect_default_size(pano.Width);
+    if (!samples) samples = pbr_equirect_default_samples(pano.Width, size);
+}
+
+void PanoramaToCube(pbr_ctx* ctx, const Panorama& pano, float* cube_level0, uint32_t size, uint32_t samples) {
+    if (!pano.Texels) throw HipException("equirect: null panorama");
+    if (!pano.Width || !pano.Height || pano.Width > PBR_EQUIRECT_MAX_W || pano.Height > PBR_EQUIRECT_MAX_H)
+        throw HipException("equirect: a panorama of " + std::to_string(pano.Width) + " x " + std::to_string(pano.Height) + " texels (1 .. " +
+                           std::to_string(PBR_EQUIRECT_MAX_W) + " x 1 .. " + std::to_string(PBR_EQUIRECT_MAX_H) + ")");
+    const size_t bytes = (size_t)pano.Width * pano.Height * (pano.Rgbe ? 4 : 16);
+    DeviceMemory staged(bytes);
+    // (a blocking copy from pageable memory has landed when it returns: the context's stream needs no event to see it)
+    ThrowIfFailed(hipMemcpy(staged.Ptr(), pano.Texels, bytes, hipMemcpyHostToDevice), "upload panorama");
+    if (pbr_equirect_to_cube(ctx, staged.Ptr(), pano.Width, pano.Height, cube_level0, size, samples, pano.Rgbe ? PBR_EQUIRECT_SRC_RGBE : 0u) != PBR_OK)
+        throw HipException(pbr_last_error(ctx));
+    if (pbr_sync(ctx) != PBR_OK) throw HipException(pbr_last_error(ctx));   // `staged` is released on return
+}
+
+std::shared_ptr<SkyBox> LoadEquirectSkyBox(pbr_ctx* ctx, const std::string& hdr_path, uint32_t size, uint32_t samples) {
+    const HdrImage img = LoadHDRImageFile(hdr_path);
+    const Panorama pano{img.Rgbe.data(), img.Width, img.Height, true};
+    EquirectDefaults(pano, size, samples);
+    if (!size || size > PBR_BC6H_MAX_SIZE) throw HipException("equirect: cube size " + std::to_string(size) + " (1 .. " + std::to_string(PBR_BC6H_MAX_SIZE) + ")");
+    uint32 mips = 1;
+    while ((size >> mips) >= 1) mips++;
+    auto sky = std::make_shared<SkyBox>();
+    sky->Cube = std::make_shared<DeviceTexture2DArray>(size, mips, ETextureFormat_R32G32B32A32_FLOAT);
+    PanoramaToCube(ctx, pano, (float*)sky->Cube->DevicePtr(), size, samples);
+    auto check = [&](pbr_status st) { if (st != PBR_OK) throw HipException(pbr_last_error(ctx)); };
+    check(pbr_cube_gen_mips(ctx, (float*)sky->Cube->DevicePtr(), size, mips));
+    DeviceStructuredBuffer pack(112, 4);
+    pbr_cube_f32 c{(const float*)sky->Cube->DevicePtr(), size, mips};
+    check(pbr_sh9_project(ctx, &c, (float*)pack.DevicePtr()));
+    check(pbr_sync(ctx));   // pack is released on return
+    ThrowIfFailed(hipMemcpy(&sky->SH, pack.DevicePtr(), 112, hipMemcpyDeviceToHost), "read SH");
+    return sky;
+}
+
 }  // namespace MRendererHip

@@ -34,4 +34,21 @@ uint32_t LoadCubeMapFaces(const std::string& dir, HdrImage (&faces)[6]);
 // mip chain and its SH9 pack.  Faces must be square, equal, and a multiple of 4 texels (:399-403).
 std::shared_ptr<SkyBox> LoadCubeMap(pbr_ctx* ctx, const std::string& dir);
 
+// An equirectangular (latitude-longitude) panorama in host memory as the source of a cube's level 0: Width x Height texels, rows top
+// to bottom, fp32 RGBA (16 bytes a texel) or, with Rgbe, Radiance texels (4 bytes) that the kernel decodes where it fetches them.
+// The reference takes faces only; the resampling rule is pbr_equirect_to_cube's (include/pbr_hip.h).
+struct Panorama {
+    const void* Texels = nullptr;
+    uint32_t Width = 0, Height = 0;
+    bool Rgbe = false;
+};
+// size 0 / samples 0 -> what the default rules pick for the panorama (pbr_equirect_default_size / _samples)
+void EquirectDefaults(const Panorama& pano, uint32_t& size, uint32_t& samples);
+// Uploads the panorama as it is and resamples it into cube_level0 (device, 6 size^2 float4) on ctx.  Blocks until the GPU is done
+// (the uploaded copy is released on return).  Throws HipException with pbr_equirect_to_cube's reason for what it refuses.
+void PanoramaToCube(pbr_ctx* ctx, const Panorama& pano, float* cube_level0, uint32_t size, uint32_t samples);
+// LoadCubeMap for one equirectangular .hdr of any aspect ratio: its RGBE texels are uploaded and sampled in place into a cube of
+// `size` (0: the default rule) with `samples`^2 sub-samples a texel (0: the default rule), then the full box mip chain and the SH9 pack.
+std::shared_ptr<SkyBox> LoadEquirectSkyBox(pbr_ctx* ctx, const std::string& hdr_path, uint32_t size, uint32_t samples);
+
 }  // namespace MRendererHip

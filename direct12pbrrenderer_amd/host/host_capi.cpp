@@ -137,6 +137,14 @@ int pbrh_load_skybox(pbrh_renderer* r, const char* dir) {
     });
 }
 
+int pbrh_load_skybox_equirect(pbrh_renderer* r, const char* hdr_path, uint32_t size, uint32_t samples) {
+    return guarded(r, [&] {
+        if (!hdr_path) throw HipException("pbrh_load_skybox_equirect: null path");
+        r->scene->SetSkyBox(LoadEquirectSkyBox(r->scheduler->CommandList()->Context(), hdr_path, size, samples));
+        r->pipeline->mPrefilterEnvMapPass->Invalidate();
+    });
+}
+
 int pbrh_set_skybox_file(pbrh_renderer* r, const uint8_t* file, size_t bytes, int recompute_sh) {
     return guarded(r, [&] {
         r->scene->SetSkyBox(SkyBoxFromCubeMapFile(r->scheduler->CommandList()->Context(), file, bytes, recompute_sh != 0));
@@ -232,6 +240,33 @@ long pbrh_import_cubemap_dir_ex(pbrh_renderer* r, const char* dir, uint32_t mip_
         HdrImage faces[6];
         const uint32_t size = LoadCubeMapFaces(dir, faces);
         return (long)ImportCubeMap(r->scheduler->CommandList()->Context(), nullptr, faces, size, mip_levels, file_out, file_bytes, flags);
+    } catch (const std::exception& e) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
+        return -1;
+    }
+}
+
+long pbrh_import_cubemap_equirect(pbrh_renderer* r, const float* pano, uint32_t pw, uint32_t ph, uint32_t size, uint32_t samples, uint32_t mip_levels,
+                                  uint32_t flags, uint8_t* file_out, size_t file_bytes, char* err, size_t err_len) {
+    try {
+        if (!r) throw HipException("pbrh_import_cubemap_equirect: null renderer");
+        if (file_out && !pano) throw HipException("pbrh_import_cubemap_equirect: null panorama");
+        const Panorama src{pano, pw, ph, false};
+        return (long)ImportCubeMap(r->scheduler->CommandList()->Context(), nullptr, nullptr, size, mip_levels, file_out, file_bytes, flags, &src, samples);
+    } catch (const std::exception& e) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
+        return -1;
+    }
+}
+
+long pbrh_import_cubemap_hdr(pbrh_renderer* r, const char* hdr_path, uint32_t size, uint32_t samples, uint32_t mip_levels, uint32_t flags,
+                             uint8_t* file_out, size_t file_bytes, char* err, size_t err_len) {
+    try {
+        if (!r) throw HipException("pbrh_import_cubemap_hdr: null renderer");
+        if (!hdr_path) throw HipException("pbrh_import_cubemap_hdr: null path");
+        const HdrImage img = LoadHDRImageFile(hdr_path);
+        const Panorama src{img.Rgbe.data(), img.Width, img.Height, true};
+        return (long)ImportCubeMap(r->scheduler->CommandList()->Context(), nullptr, nullptr, size, mip_levels, file_out, file_bytes, flags, &src, samples);
     } catch (const std::exception& e) {
         if (err && err_len) std::snprintf(err, err_len, "%s", e.what());
         return -1;

@@ -45,6 +45,9 @@ const char* pbrh_last_error(const pbrh_renderer* r);
 int pbrh_set_skybox(pbrh_renderer* r, const float* cube_mip0, uint32_t size);
 /* LoadCubeMap: <dir>/{px,nx,py,ny,pz,nz}.hdr (Radiance RGBE) -> sky cube + mips + SH9 on the GPU */
 int pbrh_load_skybox(pbrh_renderer* r, const char* dir);
+/* pbrh_load_skybox for ONE equirectangular .hdr: resampled into an fp32 cube of `size` with samples^2 sub-samples a texel
+ * (pbr_equirect_to_cube on the file's RGBE texels; 0 = the default rule for either), then box mips + SH9 on the GPU */
+int pbrh_load_skybox_equirect(pbrh_renderer* r, const char* hdr_path, uint32_t size, uint32_t samples);
 /* The reference's own sky asset: a CubeMapResource's data file held in memory (pbrh_parse_cubemap_file describes the layout).  The
  * file is uploaded as it is — 1 byte per texel instead of the 16 of pbrh_set_skybox — and its six BC6H_UF16 chains are decoded in
  * place on the renderer's context (pbr_bc6h_decode_cube) into the sky cube, with the file's own levels (no box mips are made).
@@ -95,6 +98,18 @@ long pbrh_import_cubemap_ex(pbrh_renderer* r, const float* cube_mip0, uint32_t s
                             uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
 long pbrh_import_cubemap_dir_ex(pbrh_renderer* r, const char* dir, uint32_t mip_levels, uint32_t flags,
                                 uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
+/* The same import from ONE equirectangular (latitude-longitude) panorama instead of six faces — not the reference's, which takes
+ * faces only: level 0 is resampled on the GPU by pbr_equirect_to_cube (its rule: include/pbr_hip.h) into a cube of `size` with
+ * samples^2 sub-samples a texel, and everything after level 0 is pbrh_import_cubemap_dir_ex's: the same mips, SH pack, flags, file
+ * and size query by a NULL file_out.  size 0 / samples 0: the default rules (pbr_equirect_default_size / _samples of the panorama's
+ * width).  _equirect takes pano, host fp32 RGBA, ph rows of pw texels, row 0 the top (the size query reads pw only: pano may be
+ * NULL); _hdr takes one Radiance .hdr file of any aspect ratio, whose RGBE texels are uploaded as they are (4 bytes a texel) and
+ * decoded where the kernel fetches them (the size query still reads the file, for its width).  -1 + reason in err: what the import
+ * above refuses, a panorama above PBR_EQUIRECT_MAX_W x PBR_EQUIRECT_MAX_H, samples not 0, 1, 2, 4 or 8, an unreadable file. */
+long pbrh_import_cubemap_equirect(pbrh_renderer* r, const float* pano, uint32_t pw, uint32_t ph, uint32_t size, uint32_t samples,
+                                  uint32_t mip_levels, uint32_t flags, uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
+long pbrh_import_cubemap_hdr(pbrh_renderer* r, const char* hdr_path, uint32_t size, uint32_t samples, uint32_t mip_levels, uint32_t flags,
+                             uint8_t* file_out, size_t file_bytes, char* err, size_t err_len);
 /* CPU only: parse one .hdr file held in memory (header + flat / run-length scanlines) into RGBE texels */
 int pbrh_parse_hdr(const uint8_t* file, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgbe, size_t rgbe_bytes, char* err, size_t err_len);
 /* CPU only, stateless: one of the reference's serialized 2D textures (a texture asset's _data.bin) held in memory: TextureInfo (uint16

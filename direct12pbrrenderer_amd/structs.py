@@ -182,6 +182,22 @@ def bc6h_chain_bytes(size, mip_levels):
     return sum(max(1, ((size >> l) + 3) // 4) ** 2 * 16 for l in range(mip_levels))
 
 
+EQUIRECT_MAX_W, EQUIRECT_MAX_H = 16384, 8192          # PBR_EQUIRECT_MAX_W / _H
+EQUIRECT_SRC_RGBE = 1          # PBR_EQUIRECT_SRC_RGBE: the panorama is Radiance RGBE texels (4 bytes), decoded where they are fetched
+
+
+def equirect_default_size(pw):
+    """pbr_equirect_default_size: the cube size an import picks for a panorama pw texels wide — the largest power of two <= pw / 4
+    (a face spans a quarter of the width), clamped to [4, BC6H_MAX_SIZE]"""
+    q = int(pw) // 4
+    return min(max(1 << (q.bit_length() - 1) if q else 0, 4), BC6H_MAX_SIZE)
+
+
+def equirect_default_samples(pw, size):
+    """pbr_equirect_default_samples: the smallest of 1, 2, 4, 8 with 4 size samples >= pw, and 8 if none is"""
+    return next((s for s in (1, 2, 4) if 4 * int(size) * s >= int(pw)), 8)
+
+
 class CubeF32(C.Structure):
     _fields_ = [("data", C.c_void_p), ("size", C.c_uint32), ("mips", C.c_uint32)]
 

@@ -314,6 +314,51 @@ pbr_status pbr_bc6h_encode_cube(pbr_ctx* ctx, const float* cube_rgba, uint32_t s
 pbr_status pbr_bc6h_encode_cube_ex(pbr_ctx* ctx, const float* cube_rgba, uint32_t size, uint32_t mip_levels, void* const face_blocks_out[6],
                                    uint32_t flags);
 
+/* ---- Equirectangular panoramas (new): one latitude-longitude HDR image -> level 0 of a sky cube ------------------------------- */
+/* The reference imports a sky from six face images only (ResourceLoader.cpp:408-428); nearly every HDR sky in circulation is one
+ * equirectangular .hdr.  pbr_equirect_to_cube resamples such a panorama into level 0 of a pbr_cube_f32, the step in front of
+ * pbr_cube_gen_mips, pbr_sh9_project and pbr_bc6h_encode_cube_ex.
+ * pano: DEVICE, ph rows of pw texels, tightly packed, row 0 the top (+Y): fp32 RGBA (16 bytes a texel, 16-byte aligned; alpha is not
+ * read) or, with PBR_EQUIRECT_SRC_RGBE, Radiance RGBE texels (4 bytes, 4-byte aligned) that are decoded by pbr_rgbe_decode's rule
+ * where they are fetched: that decode is exact, so the output equals bit for bit that of the fp32 image pbr_rgbe_decode makes of the
+ * same bytes, and no 16-byte-per-texel copy of the panorama exists (8192 x 4096: 134 MB instead of 537 MB).
+ * cube_level0: DEVICE, 16-byte aligned, six faces px, nx, py, ny, pz, nz of size^2 float4 each (level 0 of a pbr_cube_f32); alpha
+ * is written as 1.0f; nothing is written outside those 6 size^2 texels.  size need not be a multiple of 4 or a power of two (those
+ * are demands of the later steps).  One asynchronous launch on the context's stream for all six faces, no allocation, no host
+ * synchronisation.
+ * Refusals (PBR_ERR_INVALID, nothing enqueued, the reason in pbr_last_error): a null pointer; pw, ph or size zero; pw above
+ * PBR_EQUIRECT_MAX_W or ph above PBR_EQUIRECT_MAX_H; size above PBR_BC6H_MAX_SIZE; samples not one of 1, 2, 4, 8; any flag bit other
+ * than PBR_EQUIRECT_SRC_RGBE; cube_level0 not 16-byte aligned; pano not aligned to its texel.
+ * The rule, pinned (this project's own: nothing of DirectXTex is involved); all arithmetic is fp32, every operation written below
+ * rounds once and none is fused except where fmaf says so; tests/equirect_ref.py restates it in numpy in float64 and float32 and the
+ * kernel is held to the float64 form within a derived bound (tests/equirect_cases.py).  n = size * samples.  For output texel
+ * (face f, x, y) and sub-sample (i, j), 0 <= i, j < samples, j the outer loop:
+ *   1. Face coordinates from integers, one rounding each: a = float(2 (x samples + i) + 1 - n) / float(n), b likewise from y and j.
+ *      (Not 2 (...) / size - 1: its cancellation makes the longitude ill-conditioned beside the poles.)
+ *   2. Direction d = the cube's own face mapping, not normalised: f = 0 .. 5: (1, -b, -a), (-1, -b, a), (a, 1, b), (a, -1, -b),
+ *      (a, -b, 1), (-a, -b, -1).
+ *   3. Angles: lambda = atan2f(d.x, d.z), and 0 when d.x and d.z are both zero (of either sign); theta = atan2f(sqrtf(d.x d.x +
+ *      d.z d.z), d.y) (not acos, which loses half the bits at the poles).  The panorama's centre column looks along +Z, its columns
+ *      advance towards +X (to the right for a camera looking down +Z with +Y up in this left-handed frame), row 0 is +Y.
+ *   4. Panorama coordinates: s = (lambda * I2 + 0.5f) * float(pw) - 0.5f, t = (theta * I1) * float(ph) - 0.5f with I2 and I1 the fp32
+ *      values nearest 1 / (2 pi) and 1 / pi.
+ *   5. Taps: x0 = floor(s), fx = s - x0, y0 = floor(t), fy = t - y0; columns x0 mod pw and (x0 + 1) mod pw (longitude wraps), rows
+ *      clamp(y0, 0, ph - 1) and clamp(y0 + 1, 0, ph - 1) (latitude clamps: no tap crosses a pole).
+ *   6. Sample, per channel r, g, b: three lerps fmaf(w, q - p, p) — row y0 along x with fx, row y0 + 1 along x with fx, then those
+ *      two along y with fy.  The taps are used as they are: non-finite and negative texels follow IEEE (a zero weight does not
+ *      switch a tap off: 0 * inf is NaN), nothing is clamped.
+ *   7. Texel: the samples^2 samples are added in the order above (starting from 0), then multiplied by 1 / samples^2, which is exact.
+ * atan2f is the device library's (OpenCL allows it 6 ulp), so the kernel is held to the rule within a bound, not bit for bit. */
+#define PBR_EQUIRECT_MAX_W 16384u
+#define PBR_EQUIRECT_MAX_H 8192u
+#define PBR_EQUIRECT_SRC_RGBE 1u   /* pano is Radiance RGBE texels (4 bytes) instead of fp32 RGBA (16 bytes) */
+pbr_status pbr_equirect_to_cube(pbr_ctx* ctx, const void* pano, uint32_t pw, uint32_t ph,
+                                float* cube_level0, uint32_t size, uint32_t samples, uint32_t flags);
+/* What an import picks when its caller names no cube size or sub-sample count (pure host functions): the largest power of two
+ * <= pw / 4 clamped to [4, PBR_BC6H_MAX_SIZE]; the smallest of 1, 2, 4, 8 with 4 size samples >= pw, and 8 if none is. */
+uint32_t pbr_equirect_default_size(uint32_t pw);
+uint32_t pbr_equirect_default_samples(uint32_t pw, uint32_t size);
+
 /* env_map_gen.hlsl:50-105, all PBR_ENV_MIPS dispatches of PreFilterEnvMapPass::Execute
  * (DeferredPipeline.cpp:77-115): mip i is filtered with roughness i/(mips-1).
  * out: half4 cube chain, layout as pbr_cube_f32 with edge `size`.
