@@ -1,0 +1,330 @@
+"""The exposure kernels (csrc/exposure.hip, and the histogram tails of csrc/bloom.hip) under the float64 truth of
+tests/exposure_truth.py: every half value, every load path and ragged edge, the content paths of hist_count, every fused histogram
+tail, the average's three entry points and the tone-map's, and constant frames end to end.  The bands, caps and case sets are
+exposure_truth's; tests/test_exposure_truth_cpu.py holds the CPU oracle to the same assertions.  `-s` prints the measured figures."""
+import numpy as np
+import pytest
+import torch
+
+import exposure_truth as et
+from direct12pbrrenderer_amd.structs import MAX_VIEWS, View
+
+pytestmark = pytest.mark.gpu
+
+PAD = np.float16(8.0)                 # bin 255: nothing a patterned frame holds, so a read outside the view shows
+SENTINEL = np.uint32(0x5A17C0DE)      # alpha 0x5A: nothing the tone-map writes
+
+
+def dev_half(ctx, arr):
+    return ctx.upload(np.ascontiguousarray(arr, dtype=np.float16).view(np.uint16)).view(torch.float16)
+
+
+def u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+def cell(ctx, value):
+    return ctx.upload(np.array([value], dtype=np.float32))
+
+
+def placed(ctx, frame, pitch, lead, pad=PAD):
+    """frame [h, w, 4] as a view of a buffer of `pad`: `lead` pixels, a row of padding, the rows at `pitch`, a row of padding.
+    Returns (tensor to keep alive, device address of the view)."""
+    h, w = frame.shape[:2]
+    buf = np.full((lead + (h + 2) * pitch, 4), pad, dtype=np.float16)
+    rows = buf[lead + pitch:lead + pitch + h * pitch].reshape(h, pitch, 4)
+    rows[:, :w] = frame
+    t = dev_half(ctx, buf)
+    return t, t.data_ptr() + 8 * (lead + pitch)
+
+
+def gpu_histogram(ctx, frame, pitch=None, lead=0, times=1, min_log=et.MIN_LOG, log_range=et.LOG_RANGE):
+    h, w = frame.shape[:2]
+    keep, view = placed(ctx, frame, pitch or w, lead)
+    hist = ctx.zeros((256,), torch.int32)
+    inv_range = float(np.float32(1.0) / np.float32(log_range))
+    for _ in range(times):
+        ctx.lum_histogram(view, w, h, pitch or w, hist, min_log, inv_range)
+    return u32(hist), (view % 16 == 0) and w % 2 == 0 and (pitch or w) % 2 == 0
+
+
+# ------------------------------------------------------------------------------------------------------ histogram: pbr_lum_histogram
+@pytest.mark.parametrize("case", ["grey", "triples"])
+def test_histogram_every_half_value(ctx, case):
+    """every half bit pattern as a grey pixel, and 65 536 log-uniform colour triples: the 256 counts are the float64 counts exactly,
+    twice into the same bins (the pass adds)"""
+    img, replaced, closest = et.all_halves_grey() if case == "grey" else et.colour_triples()
+    print(f"{case}: {replaced} replaced, closest edge kept {closest:.3e} bins")
+    got, vec2 = gpu_histogram(ctx, img, times=2)
+    assert vec2
+    et.check_histogram(got, img, times=2)
+    got, vec2 = gpu_histogram(ctx, img, lead=1)                       # the same values through the scalar loads
+    assert not vec2
+    et.check_histogram(got, img)
+
+
+def test_histogram_other_range(ctx):
+    for build in (et.all_halves_grey, et.colour_triples):
+        img = build(min_log=-6.0, log_range=8.0)[0]
+        et.check_histogram(gpu_histogram(ctx, img, min_log=-6.0, log_range=8.0)[0], img, -6.0, 8.0)
+
+
+# (w, h, pitch, lead pixels, the load path the host's rule gives it).  (2, 1, 2, 0) is 16-byte aligned with even w and pitch, so it is a
+# one-pair vec2 frame; (2, 1, 2, 1) is its scalar twin.  (514, 5, 600, 2): two units per row, the second with one live lane, and an odd
+# unit count, so the second unit of the last trip is past the end.  2048 x 1026 > 512 blocks x 4096 pixels: a second grid-stride trip.
+SHAPES = [(1, 1, 1, 0, False), (2, 1, 2, 0, True), (2, 1, 2, 1, False), (255, 3, 255, 0, False), (256, 3, 256, 1, False),
+          (65535, 1, 65535, 0, False), (1, 65535, 1, 0, False), (510, 5, 510, 0, True), (514, 5, 600, 2, True),
+          (65534, 1, 65534, 0, True), (2048, 1026, 2048, 0, True), (2047, 1026, 2050, 0, False)]
+
+
+@pytest.mark.parametrize("w,h,pitch,lead,want_vec2", SHAPES)
+def test_histogram_load_paths_and_ragged_edges(ctx, w, h, pitch, lead, want_vec2):
+    yy, xx = np.mgrid[0:h, 0:w]
+    frame = et.grey_frame((xx * 7 + yy * 13) % 255)                    # bins 0 .. 254; the padding around the view is bin 255
+    got, vec2 = gpu_histogram(ctx, frame, pitch, lead)
+    assert vec2 == want_vec2
+    et.check_histogram(got, frame)
+
+
+@pytest.mark.parametrize("w,h", [(514, 5), (333, 7)])
+def test_hist_count_content_paths(ctx, w, h):
+    """hist_count chooses by content: one leader round (constant, black), two (two bins), two rounds + the per-lane rest (three bins,
+    64 bins in a wave) — on a vec2 and a scalar shape whose last unit of a row has inactive lanes"""
+    yy, xx = np.mgrid[0:h, 0:w]
+    patterns = {
+        "constant": np.full((h, w), 120), "black": np.zeros((h, w), int),
+        "two by column": np.array([60, 61])[xx % 2], "two by pair": np.array([3, 254])[(xx // 2) % 2],
+        "three": np.array([10, 128, 250])[xx % 3], "three by pair": np.array([0, 128, 250])[(xx // 2) % 3],
+        "64 in a wave": 100 + xx % 64, "64 by pair": 100 + (xx // 2) % 64, "black but one": np.where((xx == w - 1) & (yy == h - 1), 200, 0),
+    }
+    for name, bins in patterns.items():
+        frame = et.grey_frame(bins)
+        try:
+            et.check_histogram(gpu_histogram(ctx, frame)[0], frame)
+        except AssertionError as e:
+            raise AssertionError(f"{name}: {e}") from None
+
+
+# ------------------------------------------------------------------------------------------------------ histogram: the bloom tails
+@pytest.fixture(scope="module")
+def finite_grey():
+    img = et.finite_halves_grey()[0]
+    return img, et.image_bins(img)[0]
+
+
+def tail_rects(w, h):
+    """the whole frame, the last pixel, an interior rectangle whose edges are multiples of no tile size (16, 32, 64, 128)"""
+    return [(0, 0, w, h), (w - 1, h - 1, 1, 1), (37, 21, w - 37 - 29, h - 21 - 19)]
+
+
+# The API does not say which kernel ran, so each size relies on the rules of bloom_pass / launch_hv (csrc/bloom.hip):
+# * an odd width or height at level 0 is no exact half: the staged tail k_blur_v_merge<true> (302 x 178 is even both ways and would
+#   take k_blur_hv; 303 x 179 is used);
+# * an exact level 0 takes k_blur_up_poly when 128 x 32 tiles number >= 400 and the shader-order switch is off: 2560 x 640 is 20 x 20;
+# * else k_blur_hv with 64 x 32 tiles when those number >= 900, with 64 x 16 tiles below: 256 x 256 takes 64 x 16; under the
+#   shader-order switch 2560 x 640 would be 40 x 20 = 800 tiles of 64 x 32 and still take 64 x 16, so 1920 x 960 (30 x 30 = 900) is
+#   used for the 64 x 32 instance.
+TAILS = {"k_blur_v_merge": (303, 179, False), "k_blur_hv 64x16": (256, 256, False), "k_blur_up_poly": (2560, 640, False),
+         "k_blur_hv 64x32": (1920, 960, True)}
+
+
+@pytest.mark.parametrize("tail", list(TAILS))
+def test_bloom_tail_histograms(ctx, finite_grey, tail):
+    """threshold 1e30: the soft knee gives every finite texel the contribution 0, the pyramid is zeros and the merged pixel is the HDR
+    texel itself — the tail's histogram is fed exact values.  (Colour only: alpha receives the pyramid's constant alpha, which the
+    prefilter writes whatever the threshold, and the luminance does not read it.)"""
+    w, h, shader_order = TAILS[tail]
+    img, bins = et.tile_to(finite_grey[0], w, h), et.tile_to(finite_grey[1][..., None], w, h)[..., 0]
+    hdr = dev_half(ctx, img)
+    orig = hdr.clone()
+    ca, cb = ctx.alloc_bloom_chain(w, h), ctx.alloc_bloom_chain(w, h)
+    ctx.set_bloom_shader_order(shader_order)
+    try:
+        for rect in tail_rects(w, h):
+            x, y, rw, rh = rect
+            hist = ctx.zeros((256,), torch.int32)
+            ctx.bloom_histogram(hdr, w, h, w, ca, cb, rect, hist, threshold=1e30)
+            assert bool((hdr[..., :3] == orig[..., :3]).all()), f"{rect}: the HDR colour changed"
+            want = et.hist_of(bins[y:y + rh, x:x + rw])
+            assert np.array_equal(u32(hist), want), f"{rect}: bins {np.nonzero(u32(hist) != want)[0][:8].tolist()} differ from truth"
+            plain = ctx.zeros((256,), torch.int32)
+            ctx.lum_histogram(hdr.data_ptr() + 8 * (y * w + x), rw, rh, w, plain)
+            assert np.array_equal(u32(hist), u32(plain)), f"{rect}: differs from pbr_lum_histogram"
+    finally:
+        ctx.set_bloom_shader_order(False)
+
+
+def test_bloom_tail_histogram_views(ctx, finite_grey):
+    """the view-table instance (k_blur_hv<views>, 64 x 16 tiles at 256 x 256): two views, the second the first one transposed"""
+    w = h = 256
+    imgs = [finite_grey[0], np.ascontiguousarray(finite_grey[0].transpose(1, 0, 2)[::-1])]
+    hdrs = [dev_half(ctx, i) for i in imgs]
+    origs = [t.clone() for t in hdrs]
+    chains = [(ctx.alloc_bloom_chain(w, h), ctx.alloc_bloom_chain(w, h)) for _ in imgs]
+    hists = [ctx.zeros((256,), torch.int32) for _ in imgs]
+    views = (View * 2)()
+    for i in range(2):
+        views[i].hdr, views[i].hdr_pitch = hdrs[i].data_ptr(), w
+        views[i].chain_a, views[i].chain_b = chains[i][0].data_ptr(), chains[i][1].data_ptr()
+        views[i].hist256 = hists[i].data_ptr()
+    ctx.bloom_histogram_views(views, 2, w, h, threshold=1e30)
+    for i in range(2):
+        assert bool((hdrs[i][..., :3] == origs[i][..., :3]).all())
+        et.check_histogram(u32(hists[i]), imgs[i])
+
+
+# ------------------------------------------------------------------------------------------------------ average
+@pytest.fixture(scope="module")
+def average_cases():
+    return et.average_histograms()
+
+
+def run_averages(ctx, cases, dt, prev):
+    """the adapted luminance of every case through pbr_lum_average, pbr_lum_average_views and pbr_average_tonemap: three uint32 bit arrays"""
+    hists = ctx.upload(np.stack([h for h, _ in cases]))
+    single, fused = [], []
+    tiny = dev_half(ctx, np.ones((2, 2, 4), np.float16))
+    ldr = ctx.zeros((2, 2), torch.int32)
+    for i, (_, count) in enumerate(cases):
+        a = cell(ctx, prev)
+        work = hists[i].clone()
+        ctx.lum_average(work, count, dt, a)
+        single.append(a)
+        assert int(work.abs().sum()) == 0 if i == 0 else True
+        a_in, a_out = cell(ctx, prev), cell(ctx, -1.0)
+        ctx.average_tonemap(hists[i], count, dt, a_in, a_out, None, tiny, 2, 2, 2, ldr, 2)
+        fused.append(a_out)
+    by_count = {}
+    for i, (_, count) in enumerate(cases):
+        by_count.setdefault(count, []).append(i)
+    viewed = [None] * len(cases)
+    for count, idx in by_count.items():                                # one pixel count per call, MAX_VIEWS views at a time
+        for k in range(0, len(idx), MAX_VIEWS):
+            part = idx[k:k + MAX_VIEWS]
+            views = (View * len(part))()
+            work = [hists[i].clone() for i in part]
+            cells = [cell(ctx, prev) for _ in part]
+            for j in range(len(part)):
+                views[j].hist256, views[j].avg, views[j].g.DeltaTime = work[j].data_ptr(), cells[j].data_ptr(), dt
+            ctx.lum_average_views(views, len(part), count)
+            for j, i in enumerate(part):
+                viewed[i] = cells[j]
+    return [u32(torch.cat(x)) for x in (single, viewed, fused)]
+
+
+@pytest.mark.parametrize("dt,prev", [(1e9, 0.0), (1.0 / 60.0, 0.18)])
+def test_average_against_truth(ctx, average_cases, dt, prev):
+    """dt = 1e9, prev = 0: the result names the bin (adjacent bins differ by 3.3 %), which must be average_truth's wherever the
+    truncation is decided; dt = 1/60, prev = 0.18: the blend within blend_bound of the float64 value.  The three entry points agree
+    bit for bit."""
+    single, viewed, fused = run_averages(ctx, average_cases, dt, prev)
+    assert np.array_equal(single, viewed) and np.array_equal(single, fused)
+    amb, worst = 0, 0.0
+    for (hist, count), got in zip(average_cases, single.view(np.float32)):
+        a, rel = et.check_average(got, hist, count, dt, prev)
+        amb, worst = amb + a, max(worst, rel)
+    print(f"average dt={dt:g}: {amb} of {len(average_cases)} ambiguous, worst relative error {worst:.3e}")
+    assert amb <= et.AVERAGE_CAP * len(average_cases)
+
+
+# ------------------------------------------------------------------------------------------------------ tone-map
+def tonemap_layout(path):
+    """(w, hdr pitch, hdr lead pixels, out pitch, out lead words, aligned path expected) of paths (a) .. (f)"""
+    return {"a aligned": (256, 256, 0, 256, 0, True), "b out_pitch 257": (256, 256, 0, 257, 0, False),
+            "c hdr one pixel in": (256, 260, 1, 256, 0, False), "d ldr one word in": (256, 256, 0, 260, 1, False),
+            "e w 255": (255, 256, 0, 256, 0, True), "f w 1": (1, 256, 0, 256, 0, True)}[path]
+
+
+class LdrTarget:
+    """an LDR buffer of SENTINEL with a w x h view at out_pitch, `lead` words plus one padding row in"""
+
+    def __init__(self, ctx, w, h, out_pitch, lead):
+        self.w, self.h, self.pitch, self.start = w, h, out_pitch, lead + out_pitch
+        self.t = ctx.upload(np.full(lead + (h + 2) * out_pitch, SENTINEL, dtype=np.uint32))
+        self.ptr = self.t.data_ptr() + 4 * self.start
+
+    def image(self):
+        """the view's pixels, after asserting that nothing else was written"""
+        flat = u32(self.t)
+        rows = flat[self.start:self.start + self.h * self.pitch].reshape(self.h, self.pitch)
+        assert np.all(flat[:self.start] == SENTINEL) and np.all(flat[self.start + self.h * self.pitch:] == SENTINEL), "write outside the view"
+        assert np.all(rows[:, self.w:] == SENTINEL), "write past a row's end"
+        return rows[:, :self.w].copy()
+
+
+@pytest.fixture(scope="module")
+def rgb_image():
+    return et.all_halves_rgb()
+
+
+@pytest.mark.parametrize("path", ["a aligned", "b out_pitch 257", "c hdr one pixel in", "d ldr one word in", "e w 255", "f w 1"])
+def test_tonemap_every_half_value(ctx, rgb_image, path):
+    """every half value in every channel at six adapted luminances, through the packed path, the scalar path and the scalar last pixel
+    of an odd row: each byte floor(v) wherever v is unambiguous and never more than 1 off, alpha 255, a non-finite channel 0 with its
+    pixel's and its pair's other channels right, monotone, and nothing written outside the view"""
+    w, pitch, lead, out_pitch, out_lead, want_aligned = tonemap_layout(path)
+    frame = np.ascontiguousarray(rgb_image[:, :w])
+    h = frame.shape[0]
+    keep, view = placed(ctx, frame, pitch, lead, pad=np.float16(np.nan))
+    left = cases = 0
+    worst = 0.0
+    for avg in et.TONEMAP_LUMS:
+        out = LdrTarget(ctx, w, h, out_pitch, out_lead)
+        assert ((view % 16 == 0) and (out.ptr % 8 == 0) and pitch % 2 == 0 and out_pitch % 2 == 0) == want_aligned
+        ctx.tonemap(view, w, h, pitch, cell(ctx, avg), out.ptr, out_pitch)
+        got = out.image()
+        st = et.check_ldr(got, frame, avg)
+        if w == 256:
+            et.check_monotone(got)
+        left, cases, worst = left + st["left_out"], cases + st["cases"], max(worst, st["max_excess"])
+    print(f"tonemap {path}: {left} of {cases} left out, max excess {worst:.3e} LSB")
+    assert left <= et.TONEMAP_CAP * cases
+
+
+def test_tonemap_views_and_average_tonemap(ctx, rgb_image):
+    """pbr_tonemap_views with an aligned and an unaligned view at different luminances, and the tone-map half of pbr_average_tonemap at
+    the luminance its own average half produces"""
+    w = h = 256
+    layouts = [(256, 0, 256, 0, 0.18), (260, 1, 257, 1, 50.0)]
+    keeps, outs, cells = [], [], []
+    views = (View * 2)()
+    for i, (pitch, lead, out_pitch, out_lead, avg) in enumerate(layouts):
+        keep, view = placed(ctx, rgb_image, pitch, lead, pad=np.float16(np.nan))
+        out = LdrTarget(ctx, w, h, out_pitch, out_lead)
+        c = cell(ctx, avg)
+        keeps.append(keep); outs.append(out); cells.append(c)
+        views[i].hdr, views[i].hdr_pitch, views[i].avg, views[i].rgba8, views[i].out_pitch = view, pitch, c.data_ptr(), out.ptr, out_pitch
+    ctx.tonemap_views(views, 2, w, h)
+    for out, (_, _, _, _, avg) in zip(outs, layouts):
+        et.check_ldr(out.image(), rgb_image, avg)
+    hist = np.zeros(256, np.uint32)
+    hist[120], hist[121] = 1000, 3000                                  # average bin 120.75 -> bin 120
+    for pitch, lead, out_pitch, out_lead, _ in layouts:
+        keep, view = placed(ctx, rgb_image, pitch, lead, pad=np.float16(np.nan))
+        out = LdrTarget(ctx, w, h, out_pitch, out_lead)
+        a_out = cell(ctx, -1.0)
+        ctx.average_tonemap(ctx.upload(hist), 4000, 1e9, cell(ctx, 0.0), a_out, None, view, w, h, pitch, out.ptr, out_pitch)
+        avg = float(a_out.cpu()[0])
+        et.check_average(avg, hist, 4000, 1e9, 0.0)
+        et.check_ldr(out.image(), rgb_image, avg)
+
+
+# ------------------------------------------------------------------------------------------------------ end to end
+@pytest.mark.parametrize("b", [1, 2, 64, 128, 254, 255])
+def test_constant_frame_end_to_end(ctx, b):
+    """a constant grey frame of known luminance L through histogram + average (dt = 1e9, prev = 0): the adapted luminance is the lower
+    edge of L's bin, inside [L 2^(-12/254), L] (b = 255: luminance 8, clamped to the top bin's value), and the tone-map at that
+    luminance is tonemap_truth's"""
+    frame = et.grey_frame(np.full((64, 64), b))
+    hdr = dev_half(ctx, frame)
+    hist = ctx.zeros((256,), torch.int32)
+    ctx.lum_histogram(hdr, 64, 64, 64, hist)
+    et.check_histogram(u32(hist), frame)
+    avg = cell(ctx, 0.0)
+    ctx.lum_average(hist, 64 * 64, 1e9, avg)
+    got = float(avg.cpu()[0])
+    lo, hi = et.end_to_end_range(b)
+    assert lo <= got <= hi, (b, got, lo, hi)
+    out = LdrTarget(ctx, 64, 64, 64, 0)
+    ctx.tonemap(hdr, 64, 64, 64, avg, out.ptr, 64)
+    et.check_ldr(out.image(), frame, got)
