@@ -418,9 +418,11 @@ __device__ __forceinline__ void shade_pixel(const ShadeParams& p, const float* l
         const float k = (roughness + 1.0f) * (roughness + 1.0f) * 0.125f;
         // a^2 / pi * gV / (4 NdotV), gV = NdotV / max(NdotV (1-k) + k, 1e-6): the light sums S2, S3 carry gl * 4 NdotV
         const float spec_pix = NdotV > 0.0f ? ra * ra * (0.25f * INV_PI_F) * rcp(fmaxf(NdotV * (1.0f - k) + k, EPSILON_F)) : 0.0f;
-        // Kd*albedo/pi = (1-F0)(1-m) albedo/pi * (1-f5); (1-m)/pi/255 in one operation, its product with the albedo byte serves the
-        // light fold and the SH term
-        const float kd = __builtin_fmaf(metal_b, -(inv255 * inv255 * INV_PI_F), inv255 * INV_PI_F);
+        // Kd*albedo/pi = (1-F0)(1-m) albedo/pi * (1-f5); (1-m)/pi/255 = (255 - byte) / (255^2 pi): the difference of the bytes is exact,
+        // so a metal (byte 255) has kd = 0 as the shader's 1 - metallic has, and a near-metal the relative accuracy of every other
+        // pixel.  (As fma(byte, -k1, k0) the two rounded constants left -7.1e-11 at byte 255 — a negative half subnormal in the target
+        // — and 255 times the relative error at byte 254.)  Its product with the albedo byte serves the light fold and the SH term
+        const float kd = (255.0f - metal_b) * (inv255 * inv255 * INV_PI_F);
         const V3 kda = v3(kd * albedo_b.x, kd * albedo_b.y, kd * albedo_b.z);
         out.x = (1.0f - F0.x) * (kda.x * s1x + spec_pix * s3x) + F0.x * spec_pix * s2x;
         out.y = (1.0f - F0.y) * (kda.y * s1y + spec_pix * s3y) + F0.y * spec_pix * s2y;
