@@ -6,7 +6,7 @@ symbol cannot be resolved this module raises — it never substitutes another im
 import ctypes as C
 import os
 
-from .structs import CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, ShadeTables, Texture2D, Tile, View
+from .structs import CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, ShadeDesc, ShadeTables, Texture2D, Tile, View
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB", os.path.join(_HERE, "libpbr_hip.so"))   # override = experiments only
@@ -42,24 +42,12 @@ SIGNATURES = {
     "pbr_cluster_build": (_int, [_vp, C.POINTER(Global), _vp]),
     "pbr_cluster_cull": (_int, [_vp, C.POINTER(Global), _vp, _int, _vp]),
     "pbr_clustered": (_int, [_vp, C.POINTER(Global), _vp, _int, _vp]),
-    "pbr_deferred_shade": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
-                                  _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32]),
-    "pbr_deferred_shade_rects": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
-                                        _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, _vp, _u32]),
-    "pbr_deferred_shade_f32": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
-                                      _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32]),
+    "pbr_deferred_shade": (_int, [_vp, C.POINTER(ShadeDesc)]),
+    "pbr_deferred_shade_f32": (_int, [_vp, C.POINTER(ShadeDesc), _vp]),
     "pbr_lut_fold_x": (_int, [_vp, _vp, _u32, _vp]),
-    "pbr_deferred_shade_folded": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
-                                         _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32]),
-    "pbr_deferred_shade_rects_folded": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
-                                               _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, _vp, _u32]),
     "pbr_shade_tables_bytes": (_sz, [_u32, _u32]),
     "pbr_clustered_tables": (_int, [_vp, C.POINTER(Global), _vp, _int, _vp, C.POINTER(ShadeTables)]),
     "pbr_shade_geometry_tables": (_int, [_vp, C.POINTER(Tile), C.POINTER(ShadeTables)]),
-    "pbr_deferred_shade_tabled": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
-                                         _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, C.POINTER(ShadeTables)]),
-    "pbr_deferred_shade_rects_tabled": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(GBuffer),
-                                               _vp, _u32, _vp, _u32, _u32, _vp, _vp, _int, _vp, _u32, _vp, _u32, C.POINTER(ShadeTables)]),
     "pbr_skybox": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(CubeF32), _vp, _u32, _vp, _u32]),
     "pbr_skybox_bc6h": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), C.POINTER(CubeBc6h), _vp, _u32, _vp, _u32]),
     "pbr_gbuffer_encode": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),

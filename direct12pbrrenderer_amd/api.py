@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .structs import (ShadeTables, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
+from .structs import (ShadeDesc, ShadeTables, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
                       NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
 
@@ -302,13 +302,19 @@ class PbrContext:
         """cluster_build + cluster_cull in one launch (ClusteredPass::Execute)."""
         self._check(self.lib.pbr_clustered(self.h, C.byref(g), _ptr(lights), int(n), _ptr(clusters)))
 
-    def deferred_shade(self, g: Global, tile: Tile, gb, pitch, lut, lut_res, env, env_size, env_mips,
-                       clusters, lights, num_lights, hdr, hdr_pitch):
-        """gb: dict with device tensors A,B,C,depth,stencil; env: the PADDED chain from env_pad()."""
+    def _shade(self, g, tile, gb, pitch, lut, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, hdr_pitch,
+               rects=None, tables=None, hdr_f32=None):
+        """ONE pbr_deferred_shade (hdr_f32: pbr_deferred_shade_f32) call of a ShadeDesc; the G-buffer struct and the rectangle array live
+        until it returns"""
         s = _gbuffer(gb, pitch)
-        self._check(self.lib.pbr_deferred_shade(self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut), lut_res,
-                                                _ptr(env), env_size, env_mips, _ptr(clusters), _ptr(lights),
-                                                int(num_lights), _ptr(hdr), hdr_pitch))
+        arr = self._rects(rects) if rects is not None else None
+        d = ShadeDesc(C.addressof(g), C.addressof(tile), C.addressof(s), _ptr(lut), _ptr(lut_fold), _ptr(env), _ptr(clusters), _ptr(lights), _ptr(hdr),
+                      C.addressof(arr) if arr is not None else None, C.addressof(tables) if tables is not None else None,
+                      lut_res, env_size, env_mips, int(num_lights), hdr_pitch, len(arr) if arr is not None else 0)
+        if hdr_f32 is None:
+            self._check(self.lib.pbr_deferred_shade(self.h, C.byref(d)))
+        else:
+            self._check(self.lib.pbr_deferred_shade_f32(self.h, C.byref(d), _ptr(hdr_f32)))
 
     @staticmethod
     def _rects(rects):
@@ -317,14 +323,15 @@ class PbrContext:
             arr[i] = (C.c_uint32 * 4)(*[int(v) for v in r])
         return arr
 
+    def deferred_shade(self, g: Global, tile: Tile, gb, pitch, lut, lut_res, env, env_size, env_mips,
+                       clusters, lights, num_lights, hdr, hdr_pitch):
+        """gb: dict with device tensors A,B,C,depth,stencil; env: the PADDED chain from env_pad()."""
+        self._shade(g, tile, gb, pitch, lut, None, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, hdr_pitch)
+
     def deferred_shade_rects(self, g: Global, tile: Tile, gb, pitch, lut, lut_res, env, env_size, env_mips,
                              clusters, lights, num_lights, hdr, hdr_pitch, rects):
         """deferred_shade on up to 5 rectangles (tile-local x, y, w, h) of the tile in one launch."""
-        s = _gbuffer(gb, pitch)
-        arr = self._rects(rects)
-        self._check(self.lib.pbr_deferred_shade_rects(self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut), lut_res,
-                                                      _ptr(env), env_size, env_mips, _ptr(clusters), _ptr(lights),
-                                                      int(num_lights), _ptr(hdr), hdr_pitch, C.cast(arr, C.c_void_p), len(rects)))
+        self._shade(g, tile, gb, pitch, lut, None, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, hdr_pitch, rects)
 
     def lut_fold_x(self, lut, lut_res, out=None):
         """The x-folded LUT the *_folded shades read (one-shot per LUT): float32 [lut_res, 256, 2], entry [y, rb] = the x-lerps of
@@ -336,14 +343,7 @@ class PbrContext:
     def deferred_shade_folded(self, g: Global, tile: Tile, gb, pitch, lut_fold, lut_res, env, env_size, env_mips,
                               clusters, lights, num_lights, hdr, hdr_pitch, rects=None):
         """deferred_shade (rects: deferred_shade_rects) with the LUT read from lut_fold_x()'s table: the same bits, fewer instructions."""
-        s = _gbuffer(gb, pitch)
-        head = (self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut_fold), lut_res, _ptr(env), env_size, env_mips,
-                _ptr(clusters), _ptr(lights), int(num_lights), _ptr(hdr), hdr_pitch)
-        if rects is None:
-            self._check(self.lib.pbr_deferred_shade_folded(*head))
-        else:
-            arr = self._rects(rects)
-            self._check(self.lib.pbr_deferred_shade_rects_folded(*head, C.cast(arr, C.c_void_p), len(rects)))
+        self._shade(g, tile, gb, pitch, None, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, hdr_pitch, rects)
 
     def alloc_shade_tables(self, w, h):
         """The shade tables of a w x h tile: (device tensor, ShadeTables descriptor) with neither half built.  The tensor is the memory the
@@ -363,22 +363,12 @@ class PbrContext:
     def deferred_shade_tabled(self, g: Global, tile: Tile, gb, pitch, lut_fold, lut_res, env, env_size, env_mips,
                               clusters, lights, num_lights, hdr, hdr_pitch, tables: ShadeTables, rects=None):
         """deferred_shade_folded whose blocks read their prologue from the shade tables (both halves built for this tile and light count)."""
-        s = _gbuffer(gb, pitch)
-        head = (self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut_fold), lut_res, _ptr(env), env_size, env_mips,
-                _ptr(clusters), _ptr(lights), int(num_lights), _ptr(hdr), hdr_pitch)
-        if rects is None:
-            self._check(self.lib.pbr_deferred_shade_tabled(*head, C.byref(tables)))
-        else:
-            arr = self._rects(rects)
-            self._check(self.lib.pbr_deferred_shade_rects_tabled(*head, C.cast(arr, C.c_void_p), len(rects), C.byref(tables)))
+        self._shade(g, tile, gb, pitch, None, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, hdr_pitch, rects, tables)
 
     def deferred_shade_f32(self, g: Global, tile: Tile, gb, pitch, lut, lut_res, env, env_size, env_mips,
                            clusters, lights, num_lights, hdr_f32, hdr_pitch):
         """Parity probe: deferred_shade with a float32 [h, w, 4] output (the colour before the fp16 store)."""
-        s = _gbuffer(gb, pitch)
-        self._check(self.lib.pbr_deferred_shade_f32(self.h, C.byref(g), C.byref(tile), C.byref(s), _ptr(lut), lut_res,
-                                                    _ptr(env), env_size, env_mips, _ptr(clusters), _ptr(lights),
-                                                    int(num_lights), _ptr(hdr_f32), hdr_pitch))
+        self._shade(g, tile, gb, pitch, lut, None, lut_res, env, env_size, env_mips, clusters, lights, num_lights, None, hdr_pitch, hdr_f32=hdr_f32)
 
     def rgbe_decode(self, rgbe, out):
         """rgbe: uint8 device tensor [..., 4] (Radiance texels); out: float32 [..., 4]."""

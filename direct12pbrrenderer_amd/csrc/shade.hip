@@ -983,63 +983,56 @@ static pbr_status shade_dispatch(pbr_ctx* ctx, const ShadeParams& p, int num_lig
     return launched(ctx, std::is_same_v<VS, NoViews> ? "k_deferred_shade" : "k_deferred_shade<views>");
 }
 
-// LUTFOLD: `lut` is the x-folded table of the lut_res^2 LUT (pbr_lut_fold_x)
-template <bool F32OUT, bool LUTFOLD = false>
-static pbr_status shade_launch(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
-                               const void* lut, uint32_t lut_res,
-                               const pbr_half* env, uint32_t env_size, uint32_t env_mips,
-                               const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                               pbr_half* hdr, float* hdr_f32, uint32_t hdr_pitch,
-                               const uint32_t (*rects)[4] = nullptr, uint32_t n_rects = 0, const pbr_shade_tables* tables = nullptr, bool tabled = false) {
-    if (!ctx) return PBR_ERR_INVALID;
-    const char* who = "pbr_deferred_shade";
-    PBR_REQUIRE(ctx, g && tile && gb, "pbr_deferred_shade: null pointer");
-    PBR_REQUIRE(ctx, tile->w >= 1 && tile->h >= 1 && tile->w <= 65535 && tile->h <= 65535, "pbr_deferred_shade: bad tile size");
-    PBR_REQUIRE(ctx, tile->x0 + tile->w <= tile->full_w && tile->y0 + tile->h <= tile->full_h, "pbr_deferred_shade: tile outside frame");
-    PBR_CHECK(ctx, who, shade_target_bad(g, *gb, clusters, F32OUT ? (const void*)hdr_f32 : (const void*)hdr, hdr_pitch, tile->w, tile->h, lights, num_lights));
-    PBR_CHECK(ctx, who, shade_tables_bad(lut, lut_res, env, env_size, env_mips, LUTFOLD ? 8 : 4));
+// The shade tables of a launch: stale or half-built tables are refused here, on the host (the descriptor names what each half was built for)
+static const char* shade_prologue_bad(const pbr_shade_tables* t, const pbr_tile* tile, int num_lights) {
+    if (!t->dev) return "null tables";
+    if (!((t->built & PBR_TABLES_BUILT_FRAME) && (t->built & PBR_TABLES_BUILT_GEOMETRY))) return "only one half of the tables is built";
+    if (t->num_lights != num_lights) return "the tables were built for another light count";
+    if (memcmp(&t->tile, tile, sizeof(pbr_tile)) != 0) return "the tables were built for another tile";
+    if (t->list_pad != 2u * WALK_TRIPS) return "the cull padded the lists for another walk (SHADE_WALK_TRIPS differs between cluster.hip and shade.hip)";
+    if (((uintptr_t)t->dev & 15u) != 0 || t->bytes < pbr_shade_tables_bytes(tile->w, tile->h)) return "tables buffer misaligned or too small";
+    return nullptr;
+}
+
+// One single-view launch of the descriptor d (pbr_hip.h), checked; refusals go out under `who`, the entry point that was called.
+// LUTFOLD: d.lut_fold is read, else d.lut.  F32OUT: the probe, which writes hdr_f32 (pitch d.hdr_pitch) and leaves d.hdr alone.
+template <bool F32OUT, bool LUTFOLD>
+static pbr_status shade_launch(pbr_ctx* ctx, const char* who, const pbr_shade_desc& d, float* hdr_f32 = nullptr) {
+    const pbr_tile* tile = d.tile;
+    PBR_CHECK(ctx, who, d.g && tile && d.gb ? nullptr : "null pointer");
+    PBR_CHECK(ctx, who, d.rects || d.n_rects == 0 ? nullptr : "null rectangle list");
+    PBR_CHECK(ctx, who, tile->w >= 1 && tile->h >= 1 && tile->w <= 65535 && tile->h <= 65535 ? nullptr : "bad tile size");
+    PBR_CHECK(ctx, who, tile->x0 + tile->w <= tile->full_w && tile->y0 + tile->h <= tile->full_h ? nullptr : "tile outside frame");
+    PBR_CHECK(ctx, who, shade_target_bad(d.g, *d.gb, d.clusters, F32OUT ? (const void*)hdr_f32 : (const void*)d.hdr, d.hdr_pitch, tile->w, tile->h, d.lights, d.num_lights));
+    PBR_CHECK(ctx, who, shade_tables_bad(LUTFOLD ? (const void*)d.lut_fold : (const void*)d.lut, d.lut_res, d.env_padded, d.env_size, d.env_mips, LUTFOLD ? 8 : 4));
     const uint32_t whole[1][4] = {{0, 0, tile->w, tile->h}};
-    if (!rects) { rects = whole; n_rects = 1; }
-    PBR_REQUIRE(ctx, n_rects >= 1 && n_rects <= (uint32_t)SHADE_MAX_RECTS, "pbr_deferred_shade: 1 .. 5 rectangles");
+    const uint32_t (*rects)[4] = d.rects ? d.rects : whole;
+    const uint32_t n_rects = d.rects ? d.n_rects : 1;
+    PBR_CHECK(ctx, who, n_rects >= 1 && n_rects <= (uint32_t)SHADE_MAX_RECTS ? nullptr : "1 .. 5 rectangles");
     for (uint32_t r = 0; r < n_rects; r++) {
         const uint32_t* q = rects[r];
-        PBR_REQUIRE(ctx, q[2] >= 1 && q[3] >= 1 && q[0] + q[2] <= tile->w && q[1] + q[3] <= tile->h, "pbr_deferred_shade: rectangle outside the tile");
+        PBR_CHECK(ctx, who, q[2] >= 1 && q[3] >= 1 && q[0] + q[2] <= tile->w && q[1] + q[3] <= tile->h ? nullptr : "rectangle outside the tile");
     }
-    if (tabled) {   // stale or half-built tables are refused here, on the host: the descriptor names what each half was built for
-        PBR_REQUIRE(ctx, tables && tables->dev, "pbr_deferred_shade_tabled: null tables");
-        PBR_REQUIRE(ctx, (tables->built & PBR_TABLES_BUILT_FRAME) && (tables->built & PBR_TABLES_BUILT_GEOMETRY), "pbr_deferred_shade_tabled: only one half of the tables is built");
-        PBR_REQUIRE(ctx, tables->num_lights == num_lights, "pbr_deferred_shade_tabled: the tables were built for another light count");
-        PBR_REQUIRE(ctx, memcmp(&tables->tile, tile, sizeof(pbr_tile)) == 0, "pbr_deferred_shade_tabled: the tables were built for another tile");
-        PBR_REQUIRE(ctx, tables->list_pad == 2u * WALK_TRIPS, "pbr_deferred_shade_tabled: the cull padded the lists for another walk (SHADE_WALK_TRIPS differs between cluster.hip and shade.hip)");
-        PBR_REQUIRE(ctx, ((uintptr_t)tables->dev & 15u) == 0 && tables->bytes >= pbr_shade_tables_bytes(tile->w, tile->h), "pbr_deferred_shade_tabled: tables buffer misaligned or too small");
-    }
-    ShadeParams p = shade_params(g, LUTFOLD ? nullptr : (const pbr_half*)lut, lut_res, env, env_size, env_mips);
-    if (LUTFOLD) p.lut_fold = (const float*)lut;
+    if (d.tables) PBR_CHECK(ctx, who, shade_prologue_bad(d.tables, tile, d.num_lights));
+    ShadeParams p = shade_params(d.g, LUTFOLD ? nullptr : d.lut, d.lut_res, d.env_padded, d.env_size, d.env_mips);
+    if (LUTFOLD) p.lut_fold = d.lut_fold;
     p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h; p.full_w = tile->full_w; p.full_h = tile->full_h;
-    p.A = gb->A; p.B = gb->B; p.C = gb->C; p.depth = gb->depth; p.stencil = gb->stencil; p.pitch = gb->pitch;
-    p.clusters = clusters; p.lights = lights; p.hdr = hdr; p.hdr_pitch = hdr_pitch; p.hdr_f32 = hdr_f32;
-    return shade_dispatch<F32OUT, LUTFOLD>(ctx, p, num_lights, num_lights, shade_schedule(ctx, rects, n_rects, 1), 1, NoViews{}, tabled ? (const uint32_t*)tables->dev : nullptr);
+    p.A = d.gb->A; p.B = d.gb->B; p.C = d.gb->C; p.depth = d.gb->depth; p.stencil = d.gb->stencil; p.pitch = d.gb->pitch;
+    p.clusters = d.clusters; p.lights = d.lights; p.hdr = d.hdr; p.hdr_pitch = d.hdr_pitch; p.hdr_f32 = hdr_f32;
+    return shade_dispatch<F32OUT, LUTFOLD>(ctx, p, d.num_lights, d.num_lights, shade_schedule(ctx, rects, n_rects, 1), 1, NoViews{},
+                                           d.tables ? (const uint32_t*)d.tables->dev : nullptr);
 }
 
 extern "C" {
 
-pbr_status pbr_deferred_shade(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
-                              const pbr_half* lut, uint32_t lut_res,
-                              const pbr_half* env, uint32_t env_size, uint32_t env_mips,
-                              const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                              pbr_half* hdr, uint32_t hdr_pitch) {
-    return shade_launch<false>(ctx, g, tile, gb, lut, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch);
-}
-
-// The same pass on up to 5 rectangles of the tile (tile-local {x, y, w, h}) in ONE launch; pixels outside are left
-// untouched.  Multi-GPU overlap: the tile's border ring first, its core while the ring's bloom strips travel.
-pbr_status pbr_deferred_shade_rects(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
-                                    const pbr_half* lut, uint32_t lut_res,
-                                    const pbr_half* env, uint32_t env_size, uint32_t env_mips,
-                                    const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                    pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects) {
-    if (ctx && !rects) return pbr::fail(ctx, PBR_ERR_INVALID, "pbr_deferred_shade_rects: null rectangle list");
-    return shade_launch<false>(ctx, g, tile, gb, lut, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch, rects, n_rects);
+pbr_status pbr_deferred_shade(pbr_ctx* ctx, const pbr_shade_desc* d) {
+    if (!ctx) return PBR_ERR_INVALID;
+    const char* who = "pbr_deferred_shade";
+    PBR_CHECK(ctx, who, d ? nullptr : "null descriptor");
+    PBR_CHECK(ctx, who, !d->lut != !d->lut_fold ? nullptr : "exactly one of lut and lut_fold");
+    PBR_CHECK(ctx, who, !d->tables || d->lut_fold ? nullptr : "tables need lut_fold");
+    // (the sampled form is named first: the kernels stand in the code object in the order their launches are instantiated)
+    return d->lut ? shade_launch<false, false>(ctx, who, *d) : shade_launch<false, true>(ctx, who, *d);
 }
 
 // The x-folded LUT: out_fold[y][rb] (lut_res x 256 entries of two floats) = the x-lerps of LUT row y's two channels at roughness
@@ -1051,24 +1044,6 @@ pbr_status pbr_lut_fold_x(pbr_ctx* ctx, const pbr_half* lut, uint32_t lut_res, f
     PBR_REQUIRE(ctx, ((uintptr_t)lut & 3u) == 0 && ((uintptr_t)out_fold & 7u) == 0, "pbr_lut_fold_x: lut must be 4-byte and the table 8-byte aligned");
     hipLaunchKernelGGL(k_lut_fold_x, dim3(lut_res), dim3(256), 0, ctx->stream, lut, (int)lut_res, out_fold);
     return launched(ctx, "k_lut_fold_x");
-}
-
-// pbr_deferred_shade / _rects reading the LUT from its x-folded table: the same pixels to the bit
-pbr_status pbr_deferred_shade_folded(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
-                                     const float* lut_fold, uint32_t lut_res,
-                                     const pbr_half* env, uint32_t env_size, uint32_t env_mips,
-                                     const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                     pbr_half* hdr, uint32_t hdr_pitch) {
-    return shade_launch<false, true>(ctx, g, tile, gb, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch);
-}
-
-pbr_status pbr_deferred_shade_rects_folded(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
-                                           const float* lut_fold, uint32_t lut_res,
-                                           const pbr_half* env, uint32_t env_size, uint32_t env_mips,
-                                           const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                           pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects) {
-    if (ctx && !rects) return pbr::fail(ctx, PBR_ERR_INVALID, "pbr_deferred_shade_rects_folded: null rectangle list");
-    return shade_launch<false, true>(ctx, g, tile, gb, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch, rects, n_rects);
 }
 
 // The geometry half of the shade tables (pbr_hip.h), once per target
@@ -1087,33 +1062,15 @@ pbr_status pbr_shade_geometry_tables(pbr_ctx* ctx, const pbr_tile* tile, pbr_sha
     return r;
 }
 
-// pbr_deferred_shade_folded / _rects_folded with the block prologue read from the shade tables: the same pixels to the bit
-pbr_status pbr_deferred_shade_tabled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
-                                     const float* lut_fold, uint32_t lut_res,
-                                     const pbr_half* env, uint32_t env_size, uint32_t env_mips,
-                                     const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                     pbr_half* hdr, uint32_t hdr_pitch, const pbr_shade_tables* tables) {
-    return shade_launch<false, true>(ctx, g, tile, gb, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch, nullptr, 0, tables, true);
-}
-
-pbr_status pbr_deferred_shade_rects_tabled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
-                                           const float* lut_fold, uint32_t lut_res,
-                                           const pbr_half* env, uint32_t env_size, uint32_t env_mips,
-                                           const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                           pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects, const pbr_shade_tables* tables) {
-    if (ctx && !rects) return pbr::fail(ctx, PBR_ERR_INVALID, "pbr_deferred_shade_rects_tabled: null rectangle list");
-    return shade_launch<false, true>(ctx, g, tile, gb, lut_fold, lut_res, env, env_size, env_mips, clusters, lights, num_lights, hdr, nullptr, hdr_pitch, rects, n_rects, tables, true);
-}
-
 // Parity probe: the same kernel body, storing float4 instead of rounding to the R16G16B16A16_FLOAT target — what the
-// <= 1e-4 relative L-inf bound of the shaded buffer is stated on.  Not a product path.
-pbr_status pbr_deferred_shade_f32(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_gbuffer* gb,
-                                  const pbr_half* lut, uint32_t lut_res,
-                                  const pbr_half* env, uint32_t env_size, uint32_t env_mips,
-                                  const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                  float* hdr_f32, uint32_t hdr_pitch) {
-    if (ctx && hdr_f32 && ((uintptr_t)hdr_f32 & 15u) != 0) return pbr::fail(ctx, PBR_ERR_INVALID, "pbr_deferred_shade_f32: output must be 16-byte aligned");
-    return shade_launch<true>(ctx, g, tile, gb, lut, lut_res, env, env_size, env_mips, clusters, lights, num_lights, nullptr, hdr_f32, hdr_pitch);
+// <= 1e-4 relative L-inf bound of the shaded buffer is stated on.  Not a product path: the sampled whole-tile shade alone.
+pbr_status pbr_deferred_shade_f32(pbr_ctx* ctx, const pbr_shade_desc* d, float* hdr_f32) {
+    if (!ctx) return PBR_ERR_INVALID;
+    const char* who = "pbr_deferred_shade_f32";
+    PBR_CHECK(ctx, who, d ? nullptr : "null descriptor");
+    PBR_CHECK(ctx, who, !d->lut_fold && !d->tables && !d->rects && d->n_rects == 0 && !d->hdr ? nullptr : "the probe takes lut alone: no lut_fold, tables, rects or hdr");
+    PBR_CHECK(ctx, who, ((uintptr_t)hdr_f32 & 15u) == 0 ? nullptr : "output must be 16-byte aligned");
+    return shade_launch<true, false>(ctx, who, *d, hdr_f32);
 }
 
 // DeferredShadingPass::Execute for up to PBR_MAX_VIEWS whole frames in ONE launch.  Per view exactly pbr_deferred_shade's pixels: the

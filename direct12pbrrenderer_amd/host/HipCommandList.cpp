@@ -399,22 +399,22 @@ void HipCommandList::DrawScreen(ShadingState* s) {
         if (mStencilRef != 0) throw HipException("deferred_shading: only stencil ref 0 is supported");
         // ... and its block prologue from the shade tables, when the Clustered pass wrote their frame half for these clusters and lights
         // (the geometry half: once per tile)
+        pbr_shade_desc d{};
+        d.g = &mGlobal; d.tile = &tile; d.gb = &gb;
+        d.lut_fold = (const float*)folded->DevicePtr(); d.lut_res = lut->Width();
+        d.env_padded = (const pbr_half*)padded->DevicePtr(); d.env_size = env->Size(); d.env_mips = env->MipLevels();
+        d.clusters = (const pbr_cluster*)s->Buffer("Clusters")->DevicePtr();
+        d.lights = (const pbr_light*)s->Buffer("PointLights")->DevicePtr(); d.num_lights = mNumLights;
+        d.hdr = (pbr_half*)mRenderTarget->DevicePtr(); d.hdr_pitch = w;
         auto tables = mShadeTables.find(s->Buffer("Clusters"));
         if (tables != mShadeTables.end() && (tables->second.desc.built & PBR_TABLES_BUILT_FRAME) && tables->second.desc.num_lights == mNumLights &&
             tables->second.lights == s->Buffer("PointLights")) {
-            pbr_shade_tables& d = tables->second.desc;
-            if (!(d.built & PBR_TABLES_BUILT_GEOMETRY) || memcmp(&d.tile, &tile, sizeof(tile)) != 0)
-                Check(pbr_shade_geometry_tables(mCtx, &tile, &d), "pbr_shade_geometry_tables");
-            Check(pbr_deferred_shade_tabled(mCtx, &mGlobal, &tile, &gb, (const float*)folded->DevicePtr(), lut->Width(),
-                                            (const pbr_half*)padded->DevicePtr(), env->Size(), env->MipLevels(),
-                                            (const pbr_cluster*)s->Buffer("Clusters")->DevicePtr(), (const pbr_light*)s->Buffer("PointLights")->DevicePtr(),
-                                            mNumLights, (pbr_half*)mRenderTarget->DevicePtr(), w, &d), "pbr_deferred_shade_tabled");
-        } else {
-            Check(pbr_deferred_shade_folded(mCtx, &mGlobal, &tile, &gb, (const float*)folded->DevicePtr(), lut->Width(),
-                                            (const pbr_half*)padded->DevicePtr(), env->Size(), env->MipLevels(),
-                                            (const pbr_cluster*)s->Buffer("Clusters")->DevicePtr(), (const pbr_light*)s->Buffer("PointLights")->DevicePtr(),
-                                            mNumLights, (pbr_half*)mRenderTarget->DevicePtr(), w), "pbr_deferred_shade_folded");
+            pbr_shade_tables& t = tables->second.desc;
+            if (!(t.built & PBR_TABLES_BUILT_GEOMETRY) || memcmp(&t.tile, &tile, sizeof(tile)) != 0)
+                Check(pbr_shade_geometry_tables(mCtx, &tile, &t), "pbr_shade_geometry_tables");
+            d.tables = &t;
         }
+        Check(pbr_deferred_shade(mCtx, &d), "pbr_deferred_shade");
     } else if (f == "hdr_tone_mapping.hlsl") {
         Mip in = MipOf(s->Texture("LuminanceTexture"));
         // multi-GPU: only the interior rectangle is tone-mapped (the apron belongs to the neighbours)

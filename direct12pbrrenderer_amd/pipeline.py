@@ -459,25 +459,25 @@ class DeferredFrame:
     def _shade(self, rects):
         s = self.spec
         folded = self._lut_folded == (self.lut.data_ptr(), self.lut_res)
+
+        def args(lut):
+            return (self.g, self.tile, self.gb, s.sw, lut, self.lut_res, self.env, self.env_size, self.env_mips, self.clusters, self.lights,
+                    self.n_lights, self.hdr, s.sw)
         # (a shade before the frame's first clustered(), or after its light set was replaced: the folded shade, which derives its prologue)
         if folded and self.tabled and self.tables.built == TABLES_BUILT_FRAME | TABLES_BUILT_GEOMETRY and self.tables.num_lights == self.n_lights:
-            self.ctx.deferred_shade_tabled(self.g, self.tile, self.gb, s.sw, self.lut_fold, self.lut_res, self.env, self.env_size,
-                                           self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw, self.tables, rects)
+            self.ctx.deferred_shade_tabled(*args(self.lut_fold), self.tables, rects)
         elif folded:
-            self.ctx.deferred_shade_folded(self.g, self.tile, self.gb, s.sw, self.lut_fold, self.lut_res, self.env, self.env_size,
-                                           self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw, rects)
+            self.ctx.deferred_shade_folded(*args(self.lut_fold), rects)
         elif rects is None:
-            self.ctx.deferred_shade(self.g, self.tile, self.gb, s.sw, self.lut, self.lut_res, self.env, self.env_size,
-                                    self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw)
+            self.ctx.deferred_shade(*args(self.lut))
         else:
-            self.ctx.deferred_shade_rects(self.g, self.tile, self.gb, s.sw, self.lut, self.lut_res, self.env, self.env_size,
-                                          self.env_mips, self.clusters, self.lights, self.n_lights, self.hdr, s.sw, rects)
+            self.ctx.deferred_shade_rects(*args(self.lut), rects)
 
     def shade(self):
         self._shade(None)
 
     def shade_rects(self, rects):
-        """The shade on rectangles (x, y, w, h) of the shaded rectangle S, ONE launch (pbr_deferred_shade_rects)."""
+        """The shade on rectangles (x, y, w, h) of the shaded rectangle S, ONE launch (pbr_deferred_shade with a rectangle list)."""
         self._shade(rects)
 
     def prefilter_l1_rects(self, rects):

@@ -76,6 +76,14 @@ class GBuffer(C.Structure):
     ]
 
 
+class ShadeDesc(C.Structure):
+    """pbr_shade_desc: one single-view shade launch (include/pbr_hip.h); pointers first, then the 32-bit fields: no padding.
+    g, tile, gb and tables are HOST addresses (ctypes.addressof of a Global, Tile, GBuffer, ShadeTables the caller keeps alive)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("g", "tile", "gb", "lut", "lut_fold", "env_padded", "clusters", "lights", "hdr", "rects", "tables")]
+                + [("lut_res", C.c_uint32), ("env_size", C.c_uint32), ("env_mips", C.c_uint32), ("num_lights", C.c_int32),
+                   ("hdr_pitch", C.c_uint32), ("n_rects", C.c_uint32)])
+
+
 MAX_VIEWS = 16                                        # PBR_MAX_VIEWS (include/pbr_hip.h)
 
 

@@ -399,52 +399,12 @@ pbr_status pbr_cluster_cull(pbr_ctx* ctx, const pbr_global* g, const pbr_light* 
 pbr_status pbr_clustered(pbr_ctx* ctx, const pbr_global* g, const pbr_light* lights, int num_lights,
                          pbr_cluster* clusters);
 
-/* deferred_shading.hlsl:91-192 full-screen pass, stencil-masked (DeferredPipeline.cpp:187-206).
- * gb: HOST struct of device planes.  lut: res x res half2.  env_padded: the PADDED half4 cube chain
- * produced by pbr_env_pad (the fixed-function seamless-cube addressing, done once instead of per tap).
- * lights / num_lights: the PointLights buffer the cluster lists index (num_lights <= 1024; the
- * kernel stages exactly num_lights records into LDS, indices are clamped to that range).
- * hdr: tile-local w x h half4, pitch hdr_pitch pixels; untouched where stencil == 0.
- * Limits (32-bit offsets inside the kernel, PBR_ERR_INVALID beyond them): pitch x tile rows x 16 bytes < 4 GiB per plane,
- * lut_res <= 16384, padded env chain < 4 GiB (env_size <= 4096 with a full mip chain). */
-pbr_status pbr_deferred_shade(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                              const pbr_gbuffer* gb,
-                              const pbr_half* lut, uint32_t lut_res,
-                              const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
-                              const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                              pbr_half* hdr, uint32_t hdr_pitch);
-
-/* pbr_deferred_shade on up to 5 rectangles of the tile (tile-local {x, y, w, h}) in ONE launch; pixels outside are left
- * untouched.  The overlapped multi-GPU frame shades the tile's border ring first (<= 4 rectangles), starts the halo
- * exchange of its bloom strips, and shades the core while they travel. */
-pbr_status pbr_deferred_shade_rects(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                    const pbr_gbuffer* gb,
-                                    const pbr_half* lut, uint32_t lut_res,
-                                    const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
-                                    const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                    pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects);
-
 /* The x-folded split-sum LUT.  The x side of the shade's bilinear LUT sample (coordinate snap, clamps, the lerp of the two taps of a
  * row) depends on the pixel's roughness BYTE and on the LUT alone: out_fold[(y * 256 + rb) * 2 + {0, 1}] holds, for LUT row y and
  * roughness byte rb, the fp32 x-lerp of each of the LUT's two channels — evaluated by the very device functions the shade calls per
  * pixel, so a shade that reads them does the y-lerp alone and gets the same bits.  Once per LUT (lut_res <= 16384);
  * out_fold: device, lut_res * 256 * 2 floats (1 MiB for a 512^2 LUT, the LUT's own size), 8-byte aligned. */
 pbr_status pbr_lut_fold_x(pbr_ctx* ctx, const pbr_half* lut, uint32_t lut_res, float* out_fold);
-
-/* pbr_deferred_shade / pbr_deferred_shade_rects with the LUT given as pbr_lut_fold_x's table (of a lut_res^2 LUT): the same HDR
- * target bit for bit, ~33 VALU instructions less per pixel.  Everything else as documented there. */
-pbr_status pbr_deferred_shade_folded(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                     const pbr_gbuffer* gb,
-                                     const float* lut_fold, uint32_t lut_res,
-                                     const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
-                                     const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                     pbr_half* hdr, uint32_t hdr_pitch);
-pbr_status pbr_deferred_shade_rects_folded(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                           const pbr_gbuffer* gb,
-                                           const float* lut_fold, uint32_t lut_res,
-                                           const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
-                                           const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                           pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects);
 
 /* ---- shade tables: what every block of the shade would otherwise derive again in its prologue ------------------------------
  * One device buffer of pbr_shade_tables_bytes(w, h) bytes (16-byte aligned) in two halves, and a HOST descriptor that names what
@@ -483,33 +443,48 @@ pbr_status pbr_clustered_tables(pbr_ctx* ctx, const pbr_global* g, const pbr_lig
 /* The geometry half of `tables` for `tile` (one-shot per target, like pbr_lut_fold_x per LUT); records the tile in the descriptor. */
 pbr_status pbr_shade_geometry_tables(pbr_ctx* ctx, const pbr_tile* tile, pbr_shade_tables* tables);
 
-/* pbr_deferred_shade_folded / _rects_folded whose blocks copy their light planes, cluster lists, row and column terms from `tables`
- * instead of deriving them: the same HDR target bit for bit.  PBR_ERR_INVALID unless both halves are built, for this tile and this
- * num_lights.  `lights` and `clusters` must be the ones pbr_clustered_tables was given; targets too small to stage cluster lists
- * per block run pbr_deferred_shade_folded's kernel and read them directly. */
-pbr_status pbr_deferred_shade_tabled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                     const pbr_gbuffer* gb,
-                                     const float* lut_fold, uint32_t lut_res,
-                                     const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
-                                     const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                     pbr_half* hdr, uint32_t hdr_pitch, const pbr_shade_tables* tables);
-pbr_status pbr_deferred_shade_rects_tabled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                           const pbr_gbuffer* gb,
-                                           const float* lut_fold, uint32_t lut_res,
-                                           const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
-                                           const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                           pbr_half* hdr, uint32_t hdr_pitch, const uint32_t (*rects)[4], uint32_t n_rects,
-                                           const pbr_shade_tables* tables);
+/* deferred_shading.hlsl:91-192 full-screen pass, stencil-masked (DeferredPipeline.cpp:187-206): ONE launch described by a HOST struct
+ * (pointers first, then the 32-bit fields: no padding).
+ * gb: HOST struct of device planes.  env_padded: the PADDED half4 cube chain produced by pbr_env_pad (the fixed-function seamless-cube
+ * addressing, done once instead of per tap).
+ * lut / lut_fold: exactly one is set.  lut: the lut_res x lut_res half2 LUT, sampled per pixel.  lut_fold: pbr_lut_fold_x's table of that
+ * LUT (8-byte aligned): the same HDR target bit for bit, ~33 VALU instructions less per pixel.
+ * lights / num_lights: the PointLights buffer the cluster lists index (num_lights <= 1024; the kernel stages exactly num_lights records
+ * into LDS, indices are clamped to that range).
+ * hdr: tile-local w x h half4, pitch hdr_pitch pixels; untouched where stencil == 0.
+ * rects / n_rects: NULL, 0 shades the whole tile; else 1 .. 5 rectangles of it (tile-local {x, y, w, h}), pixels outside are left
+ * untouched.  The overlapped multi-GPU frame shades the tile's border ring first (<= 4 rectangles), starts the halo exchange of its
+ * bloom strips, and shades the core while they travel.
+ * tables: NULL, or the shade tables (needs lut_fold): the blocks copy their light planes, cluster lists, row and column terms from them
+ * instead of deriving them, the same HDR target bit for bit.  PBR_ERR_INVALID unless both halves are built, for this tile and this
+ * num_lights.  `lights` and `clusters` must be the ones pbr_clustered_tables was given; targets too small to stage cluster lists per
+ * block run the kernel that reads them directly.
+ * Limits (32-bit offsets inside the kernel, PBR_ERR_INVALID beyond them): pitch x tile rows x 16 bytes < 4 GiB per plane,
+ * lut_res <= 16384, padded env chain < 4 GiB (env_size <= 4096 with a full mip chain). */
+typedef struct pbr_shade_desc {
+    const pbr_global* g;
+    const pbr_tile* tile;
+    const pbr_gbuffer* gb;
+    const pbr_half* lut;
+    const float* lut_fold;
+    const pbr_half* env_padded;
+    const pbr_cluster* clusters;
+    const pbr_light* lights;
+    pbr_half* hdr;
+    const uint32_t (*rects)[4];
+    const pbr_shade_tables* tables;
+    uint32_t lut_res;
+    uint32_t env_size, env_mips;
+    int32_t num_lights;
+    uint32_t hdr_pitch;
+    uint32_t n_rects;
+} pbr_shade_desc;
+pbr_status pbr_deferred_shade(pbr_ctx* ctx, const pbr_shade_desc* d);
 
-/* Parity probe (not a product path): the same shade, storing the fp32 colour (float4 per pixel, alpha 1, pitch
- * hdr_pitch pixels, 16-byte aligned) instead of rounding it to the half4 target — the buffer the <= 1e-4 relative
- * L-inf parity bound is stated on. */
-pbr_status pbr_deferred_shade_f32(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                  const pbr_gbuffer* gb,
-                                  const pbr_half* lut, uint32_t lut_res,
-                                  const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips,
-                                  const pbr_cluster* clusters, const pbr_light* lights, int num_lights,
-                                  float* hdr_f32, uint32_t hdr_pitch);
+/* Parity probe (not a product path): the same shade, storing the fp32 colour (float4 per pixel, alpha 1, pitch d->hdr_pitch pixels,
+ * 16-byte aligned) instead of rounding it to the half4 target — the buffer the <= 1e-4 relative L-inf parity bound is stated on.
+ * d->hdr must be NULL; lut_fold, tables and rects are refused (the probe is the sampled whole-tile shade). */
+pbr_status pbr_deferred_shade_f32(pbr_ctx* ctx, const pbr_shade_desc* d, float* hdr_f32);
 
 /* ---- SURVEY 8f "next" rows: the two raster passes either side of the shade, minus rasterization ---- */
 /* skybox.hlsl:12-28 (SkyboxPass::Execute, DeferredPipeline.cpp:59-75): the sky sphere is drawn at the far

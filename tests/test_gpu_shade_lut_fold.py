@@ -1,5 +1,5 @@
-"""The shade that reads the split-sum LUT from its x-folded table (pbr_lut_fold_x -> pbr_deferred_shade_folded / _rects_folded) writes
-the HDR target of pbr_deferred_shade / _rects BIT FOR BIT (compared as int16), both given the same inputs: the table holds the fp32
+"""The shade that reads the split-sum LUT from its x-folded table (pbr_lut_fold_x -> pbr_deferred_shade with lut_fold) writes
+the HDR target of pbr_deferred_shade with lut BIT FOR BIT (compared as int16), both given the same inputs: the table holds the fp32
 x-lerps the sampled form computes per pixel, and the pixel's y-lerp keeps the sampled form's association.
 Shapes: a 1536 x 64 frame (staged lists) whose C plane puts roughness byte x & 255 in column x over the synthetic G-buffer's uniform
 octahedral normals (N.V over [0, 1], its clamp at 0 included), at LUT sizes 1, 2, 32 and 512 (one texel; one pair per row whose both

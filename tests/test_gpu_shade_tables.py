@@ -1,5 +1,5 @@
 """The shade that reads its block prologue from the shade tables (pbr_clustered_tables + pbr_shade_geometry_tables ->
-pbr_deferred_shade_tabled / _rects_tabled) writes the HDR target of pbr_deferred_shade_folded / _rects_folded BIT FOR BIT (compared as
+pbr_deferred_shade with tables) writes the HDR target of pbr_deferred_shade with lut_fold alone BIT FOR BIT (compared as
 int16, on untouched prefilled targets), both given the same inputs; and the tables themselves are, bit for bit, a numpy restatement of
 what the prologue derives: the light planes of the light array, the staged lists of the read-back cluster table, the column and row
 terms of the float32 expressions.

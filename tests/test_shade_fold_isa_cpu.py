@@ -1,4 +1,4 @@
-"""The folded-LUT instantiation k_deferred_shade<true, 257, false, NoViews, true> (pbr_deferred_shade_folded) keeps the resources and
+"""The folded-LUT instantiation k_deferred_shade<true, 257, false, NoViews, true> (pbr_deferred_shade with lut_fold) keeps the resources and
 the walk of the sampled one and stays at the instruction counts profiles/shade_lut_fold_isa.md records for its row body and its LUT
 phase; the row body is below the sampled kernel's recorded count (profiles/shade_isa_counts_after.md) — that difference is what the
 table is for.  No GPU; needs hipcc."""

@@ -1,4 +1,4 @@
-"""k_deferred_shade_tabled<257> (pbr_deferred_shade_tabled) keeps the resources and the row body of the folded kernel it replaces
+"""k_deferred_shade_tabled<257> (pbr_deferred_shade with tables) keeps the resources and the row body of the folded kernel it replaces
 (profiles/shade_lut_fold_isa.md) and a prologue — the instructions outside its row loop, which a block runs once — no longer than
 profiles/shade_tables_isa.md records and at most HALF the folded kernel's own, compiled in the same run: below that the tables have
 lost their point.  No GPU; needs hipcc."""

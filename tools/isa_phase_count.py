@@ -2,9 +2,9 @@
 gfx950 ISA.  No GPU needed.
     python tools/isa_phase_count.py [out.md] [--phases] [--fold | --tabled] [--prologue] [--src shade.hip]
 --prologue adds the prologue rows (below) to the report of the sampled or the folded kernel.
---tabled measures k_deferred_shade_tabled<257> (pbr_deferred_shade_tabled: the folded-LUT kernel with its prologue read from the shade tables).
+--tabled measures k_deferred_shade_tabled<257> (pbr_deferred_shade with tables: the folded-LUT kernel with its prologue read from the shade tables).
 --fold measures k_deferred_shade<true, 257, false, NoViews, true>, the instantiation that reads the LUT from its x-folded table
-(pbr_deferred_shade_folded), and adds the static v_* count of its LUT phase (the kernel minus its -DPBR_EXP_NOLUT build).
+(pbr_deferred_shade with lut_fold), and adds the static v_* count of its LUT phase (the kernel minus its -DPBR_EXP_NOLUT build).
 Reported:
   * the kernel's footer: occupancy, scratch bytes per lane, VGPRs;
   * every light-walk loop (innermost loops that carry the per-light arithmetic): v_* per TRIP (a trip = one pair of lights = four
