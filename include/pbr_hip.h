@@ -718,7 +718,9 @@ pbr_status pbr_bloom_merge(pbr_ctx* ctx, pbr_half* hdr, uint32_t pitch, const pb
  * — the fused kernel pbr_bloom runs for such a level pair, exposed for stage-level tests and hosts that fuse the pair.  The H
  * result is rounded to fp16 where the first dispatch stores it.  Levels of >= 400 tiles of 128 x 32 texels take the polyphase
  * form of the 2x-up blur (csrc/bloom.hip: k_blur_up_poly): <= 1 fp16 ULP from the two staged calls (SURVEY 8c's bloom-stage
- * tolerance), not bit-identical; smaller levels are bit-identical.  Sizes must be even and <= 8192; out must not alias an input. */
+ * tolerance), not bit-identical; smaller levels are bit-identical.  Sizes must be even and <= 8192; out must not alias an input.
+ * Alpha is taken as ONE constant per input plane (read at texel 0 of `lower` and of `upper`) and pushed through the same operations
+ * once: every texel of an input must carry the same alpha — true of every level inside pbr_bloom, whose prefilter writes alpha 1. */
 pbr_status pbr_bloom_up_level(pbr_ctx* ctx, const pbr_half* upper, const pbr_half* lower, uint32_t lw, uint32_t lh,
                               pbr_half* out, uint32_t ow, uint32_t oh);
 /* BloomPass::Execute (DeferredPipeline.cpp:400-570), all 16 dispatches.  hdr is bit-identical to the sequence of stage calls

@@ -1,0 +1,374 @@
+"""The CPU oracle's bloom under the float64 truth of tests/bloom_truth.py, the truth under exact rational arithmetic, the premise of
+the fused kernels' integer taps at every size they are launched for, the polyphase kernel's algebra, and the proof that the
+assertions are not slack: injected defects are rejected.  No GPU.  `-s` prints the measured figures."""
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import bloom_truth as bt
+
+F32 = np.float32
+
+
+def stage_cases(shapes):
+    return [pytest.param(s, k, id=f"{s[0]}x{s[1]}-{s[2]}x{s[3]}-{k}") for i, s in enumerate(shapes) for k in bt.kinds_for(i)]
+
+
+# ------------------------------------------------------------------------------------------------------ the oracle's stages
+@pytest.mark.parametrize("shape,kind", stage_cases(bt.BLUR_H_SHAPES))
+def test_oracle_blur_h(orc, shape, kind):
+    iw, ih, ow, oh = shape
+    img = bt.plane(kind, iw, ih)
+    t, m = bt.blur_h(img, ow, oh)
+    r = bt.check_stage(orc.blur_h(img, ow, oh), t, bt.band(bt.K_BLUR, m), f"blur_h {shape} {kind}")
+    print(f"blur_h {shape} {kind}: undecided {r['undecided']:.4%}, worst {r['worst']:.3f} of the band")
+
+
+@pytest.mark.parametrize("shape,kind", stage_cases(bt.BLUR_V_SHAPES))
+def test_oracle_blur_v(orc, shape, kind):
+    iw, ih, ow, oh = shape
+    img = bt.plane(kind, iw, ih)
+    t, m = bt.blur_v(img, ow, oh)
+    r = bt.check_stage(orc.blur_v(img, ow, oh), t, bt.band(bt.K_BLUR, m), f"blur_v {shape} {kind}")
+    print(f"blur_v {shape} {kind}: undecided {r['undecided']:.4%}, worst {r['worst']:.3f} of the band")
+
+
+@pytest.mark.parametrize("lw,lh", bt.UP_SHAPES + [(22, 11)])
+@pytest.mark.parametrize("kind", ["noise", "subnormal", "bright"])
+def test_oracle_upsample_add(orc, lw, lh, kind):
+    """(22, 11) -> 45 x 22 is the pair that is no exact double"""
+    uw, uh = (45, 22) if (lw, lh) == (22, 11) else (2 * lw, 2 * lh)
+    upper, lower = bt.plane(kind, uw, uh, seed=1), bt.plane(kind, lw, lh, seed=2)
+    t, m = bt.upsample_add(upper, lower)
+    r = bt.check_stage(orc.bloom_upsample_add(upper, lower), t, bt.band(bt.K_DUAL, m), f"upsample_add {lw}x{lh} {kind}")
+    if kind == "bright":
+        assert np.isinf(bt.rn_half(t)[..., :3]).all()           # two planes near 60 000: the store overflows, as the truth's does
+    print(f"upsample_add {lw}x{lh} {kind}: undecided {r['undecided']:.4%}, worst {r['worst']:.3f}")
+
+
+@pytest.mark.parametrize("kind", bt.KINDS)
+def test_oracle_merge(orc, kind):
+    w, h = 67, 9
+    hdr, src = bt.plane(kind, w, h, seed=3), bt.plane(kind, w, h, seed=4)
+    t, m = bt.merge(hdr, src)
+    r = bt.check_stage(orc.bloom_merge(hdr.copy(), src), t, bt.band(bt.K_MERGE, m), f"merge {kind}")
+    if kind == "bright":
+        assert np.isinf(bt.rn_half(t)).all()
+    print(f"merge {kind}: undecided {r['undecided']:.4%}, worst {r['worst']:.3f}")
+
+
+@pytest.mark.parametrize("w,h", bt.PREFILTER_SHAPES)
+@pytest.mark.parametrize("threshold,knee", bt.PREFILTER_PARAMS)
+def test_oracle_prefilter(orc, w, h, threshold, knee):
+    for kind in bt.KINDS:
+        img = bt.plane(kind, w, h, step=4)
+        t, m = bt.prefilter(img, threshold, knee)
+        r = bt.check_stage(orc.bloom_prefilter(img, threshold, knee), t, bt.U * m, f"prefilter {w}x{h} ({threshold}, {knee}) {kind}")
+        print(f"prefilter {w}x{h} ({threshold}, {knee}) {kind}: undecided {r['undecided']:.4%}, worst {r['worst']:.3f} of the band")
+
+
+CHAIN_KINDS = ("noise", "smooth", "black", "subnormal")
+
+
+@pytest.fixture(scope="module")
+def chain_intervals():
+    """(image, lo, hi) per chain case, computed once"""
+    cache = {}
+
+    def get(w, h, kind):
+        if (w, h, kind) not in cache:
+            img = bt.plane(kind, w, h)
+            cache[(w, h, kind)] = (img, *bt.chain(img))
+        return cache[(w, h, kind)]
+    return get
+
+
+@pytest.mark.parametrize("w,h", bt.CHAIN_SHAPES)
+@pytest.mark.parametrize("kind", CHAIN_KINDS)
+def test_oracle_chain(orc, chain_intervals, w, h, kind):
+    img, lo, hi = chain_intervals(w, h, kind)
+    got = img.copy()
+    orc.bloom(got)
+    r = bt.check_chain(got, lo, hi, f"chain {w}x{h} {kind}")
+    print(f"chain {w}x{h} {kind}: interval at most {r['width']} wide, {r['degenerate']:.2%} degenerate")
+
+
+def test_up_level_truth_is_the_two_stages(orc):
+    """up_level: the H stage, its half store, the V stage — the oracle's two calls land in both bands, DUAL and not"""
+    lower, upper = bt.plane("noise", 32, 16, seed=5), bt.plane("noise", 64, 32, seed=6)
+    for up in (upper, None):
+        (th, mh), (tv, mv), k = bt.up_level(up, lower, 64, 32)
+        b = orc.bloom_upsample_add(up, lower) if up is not None else orc.blur_h(lower, 64, 32)
+        bt.check_stage(b, th, bt.band(k, mh), "up_level H")
+        if np.array_equal(b.view(np.uint16), bt.rn_half(th).view(np.uint16)):      # else the V truth is of another input
+            bt.check_stage(orc.blur_v(b, 64, 32), tv, bt.band(bt.K_BLUR, mv), "up_level V")
+
+
+# ------------------------------------------------------------------------------------------------------ the truth closes on itself
+def _frac(x):
+    return Fraction(float(x))
+
+
+def _sample_frac(img, u, v):
+    """one bilinear sample of img (Fractions [h][w]) at float32 (u, v): the coordinate is the specification, the rest exact"""
+    h, w = len(img), len(img[0])
+    (i0,), (i1,), (fx,) = bt.sample_coord(np.array([u], dtype=F32), w)
+    (j0,), (j1,), (fy,) = bt.sample_coord(np.array([v], dtype=F32), h)
+    fx, fy = _frac(fx), _frac(fy)
+    lerp = lambda a, b, f: a if f == 0 else a * (1 - f) + b * f   # noqa: E731
+    return lerp(lerp(img[j0][i0], img[j0][i1], fx), lerp(img[j1][i0], img[j1][i1], fx), fy)
+
+
+@pytest.mark.parametrize("ow,oh", [(8, 8), (4, 4), (16, 16), (5, 11)])
+def test_blur_truth_against_rational_arithmetic(ow, oh):
+    """blur.hlsli:24-55 transcribed thread by thread (one 256-thread group, halo slots and all) in exact rationals on an 8 x 8
+    source: the float64 truth is within 1e-13 relative, for H and (transposed) V"""
+    src = bt.plane("noise", 8, 8, seed=7)
+    tx, ty = F32(1.0) / F32(ow), F32(1.0) / F32(oh)
+    for chan in (0, 2):
+        img = [[_frac(src[y, x, chan]) for x in range(8)] for y in range(8)]
+        want = np.zeros((oh, ow))
+        for y in range(oh):
+            uvy = (F32(y) + F32(0.5)) * ty
+            cache = [None] * bt.CACHE
+            for t in range(bt.GROUP):
+                uvx = (F32(t) + F32(0.5)) * tx
+                if t < 4:
+                    cache[t] = _sample_frac(img, max(uvx - F32(4.0) * tx, F32(0.0)), uvy)
+                if t >= 252:
+                    cache[t + 8] = _sample_frac(img, min(uvx + F32(4.0) * tx, F32(1.0)), uvy)
+                if t < ow + 4:                                  # later threads feed no output of this image
+                    cache[t + 4] = _sample_frac(img, uvx, uvy)
+            for x in range(ow):
+                want[y, x] = float(sum(_frac(bt.GAUSS32[i]) * cache[x + i] for i in range(9)))
+        got_h = bt.blur_h(src, ow, oh)[0][..., chan]
+        assert (np.abs(got_h - want) <= 1e-13 * np.abs(want)).all()
+        got_v = bt.blur_v(np.ascontiguousarray(src.transpose(1, 0, 2)), oh, ow)[0][..., chan]
+        assert (np.abs(got_v.T - want) <= 1e-13 * np.abs(want)).all()
+
+
+@pytest.mark.parametrize("threshold,knee", bt.PREFILTER_PARAMS)
+def test_prefilter_truth_against_rational_arithmetic(threshold, knee):
+    """bloom_prefilter.hlsl:17-60 in exact rationals on the 16 texels of an 8 x 8 source"""
+    src = bt.plane("noise", 8, 8, seed=8)
+    src[2:4, 2:6, :3] *= np.float16(0.25)                       # some texels below the knee as well
+    img = [[tuple(_frac(src[y, x, c]) for c in range(3)) for x in range(8)] for y in range(8)]
+    planes = [[[px[c] for px in row] for row in img] for c in range(3)]
+    th, kn, eps = _frac(F32(threshold)), _frac(F32(knee)), _frac(F32(0.00001))
+    luma = [_frac(F32(c)) for c in (0.2126, 0.7152, 0.0722)]
+    tx = ty = F32(1.0) / F32(4)
+    got = bt.prefilter(src, threshold, knee)[0]
+    for y in range(4):
+        for x in range(4):
+            u, v = F32(x) * tx, F32(y) * ty
+            total, total_w = [Fraction(0)] * 3, Fraction(0)
+            for ox, oy in ((0, 0), (-1, -1), (-1, 1), (1, -1), (1, 1)):
+                c = [_sample_frac(p, u + F32(ox) * tx, v + F32(oy) * ty) for p in planes]
+                br = max(c)
+                soft = min(max(br - th + th * kn, Fraction(0)), 2 * th * kn) / (4 * th * kn + eps)
+                con = max(soft, br - th) / max(br, eps)
+                col = [k * con for k in c]
+                wgt = 1 / (sum(a * b for a, b in zip(col, luma)) + 1)
+                total = [a + k * wgt for a, k in zip(total, col)]
+                total_w += wgt
+            want = [float(a / total_w) for a in total]
+            assert (np.abs(got[y, x, :3] - want) <= 1e-13 * np.abs(want)).all(), (x, y)
+            assert got[y, x, 3] == 1.0
+
+
+# ------------------------------------------------------------------------------------------------------ the fused kernels' premise
+def test_integer_taps_are_what_the_shader_coordinate_snaps_to_at_every_exact_size():
+    """csrc/bloom.hip launches the fused kernels where a level is an exact half / double and at most 8192 a side, and hard-codes
+    tap1d's taps.  For every such size the shader's float32 coordinate of every Cache[] entry that an output taps (halo slots and the
+    threads past the edge of a partial group included) must snap to exactly those taps — as a function of the texels: canonical_taps."""
+    for n in range(1, 8193):
+        modes = [(bt.M_SAME, n, n)] + ([(bt.M_DOWN, n, n // 2), (bt.M_UP, n // 2, n)] if n % 2 == 0 else [])
+        for mode, in_size, out_size in modes:
+            cc = bt.cache_coords(out_size)
+            groups = cc.shape[0]
+            pos = (np.arange(groups)[:, None] * bt.GROUP - bt.HALO + np.arange(bt.CACHE)[None, :])
+            used = pos <= out_size - 1 + bt.HALO                # entries past the last output's tap +4 feed nothing
+            got = bt.canonical_taps(*bt.sample_coord(cc[used], in_size))
+            want = bt.canonical_taps(*bt.tap1d(mode, pos[used], in_size))
+            for g, w_, name in zip(got, want, ("i0", "i1", "f")):
+                bad = np.nonzero(g != w_)[0]
+                assert bad.size == 0, f"mode {mode} {in_size} -> {out_size}: {name} differs at position {pos[used][bad[0]]}: {g[bad[0]]} != {w_[bad[0]]}"
+            # the axis that is not blurred: plain (x + 0.5f) * tx
+            p = np.arange(out_size)
+            got = bt.canonical_taps(*bt.sample_coord(bt.plain_coords(out_size), in_size))
+            want = bt.canonical_taps(*bt.tap1d(mode, p, in_size))
+            assert all(np.array_equal(g, w_) for g, w_ in zip(got, want)), (mode, in_size, out_size)
+
+
+def test_prefilter_samples_are_quad_means_at_every_exact_size():
+    """k_bloom_prefilter_2x: position p + off of an even image of at most 8192 samples the quad (2(p + off) - 1, 2(p + off)), weight 1/2"""
+    for w in range(2, 8193, 2):
+        ow = w // 2
+        tx = F32(1.0) / F32(ow)
+        p = np.arange(ow)
+        for off in (-1, 0, 1):
+            i0, i1, f = bt.canonical_taps(*bt.sample_coord(p.astype(F32) * tx + F32(off) * tx, w))
+            a = 2 * (p + off) - 1
+            e0, e1, ef = bt.canonical_taps(np.clip(a, 0, w - 1), np.clip(a + 1, 0, w - 1), np.full(ow, 0.5))
+            assert np.array_equal(i0, e0) and np.array_equal(i1, e1) and np.array_equal(f, ef), (w, off)
+
+
+# ------------------------------------------------------------------------------------------------------ the polyphase algebra
+def test_polyphase_coefficients_sum_like_the_nine_weights():
+    pe = bt.poly_coefficients().astype(np.float64)
+    assert abs(pe.sum() - 0.9999) < 4 * bt.U and np.all(pe > 0)
+
+
+@pytest.mark.parametrize("lw,lh", bt.UP_SHAPES)
+@pytest.mark.parametrize("dual", [True, False])
+def test_polyphase_form_is_the_same_linear_map(lw, lh, dual):
+    """two six-tap filters with recomputed E(j) on clamped coarse taps, then the 1/4 | 3/4 row blend (+ the same-size nine taps):
+    the fp32 value is within the stage band of the truth before the store already, and the stored half meets the stage assertion —
+    the coefficient formula, and clamping taps = clamping sample positions"""
+    ow, oh = 2 * lw, 2 * lh
+    for kind in ("noise", "subnormal"):
+        lower = bt.plane(kind, lw, lh, seed=9)
+        upper = bt.plane(kind, ow, oh, seed=10) if dual else None
+        (t, m), _, k = bt.up_level(upper, lower, ow, oh)
+        got = bt.poly_up_h(lower, upper)
+        err = np.abs(got.astype(np.float64) - t)
+        assert (err <= bt.band(k, m)).all(), f"{float((err / np.maximum(bt.band(k, m), 1e-300)).max()):.2f} of the band"
+        r = bt.check_stage(got.astype(np.float16), t, bt.band(k, m), f"poly model {lw}x{lh} dual={dual}")
+        print(f"poly model {lw}x{lh} dual={dual} {kind}: fp32 error at most {float((err[m > 0] / bt.band(k, m)[m > 0]).max()):.3f} of the band, "
+              f"undecided {r['undecided']:.4%}")
+
+
+# ------------------------------------------------------------------------------------------------------ injected defects
+def rejected(got_t, t, b, at_least=1):
+    """the stage assertion rejects RN_half(got_t); returns how many values lie outside"""
+    got = bt.rn_half(got_t)
+    with pytest.raises(AssertionError, match="outside the band"):
+        bt.check_stage(got, t, b)
+    lo, hi = bt.stage_interval(t, b)
+    g = got.astype(np.float64)
+    n = int((~((lo.astype(np.float64) <= g) & (g <= hi.astype(np.float64)))).sum())
+    assert n >= at_least, n
+    return n
+
+
+def _weights(i, delta=0.0, factor=1.0):
+    w = bt.GAUSS.copy()
+    w[i] = w[i] * factor + delta
+    return w
+
+
+def test_the_truth_itself_passes():
+    img = bt.plane("noise", 128, 64)
+    t, m = bt.blur_h(img, 64, 32)
+    assert bt.check_stage(bt.rn_half(t), t, bt.band(bt.K_BLUR, m))["worst"] == 0.0
+
+
+BLUR_DEFECTS = {
+    "weight 2 off by 1e-4": dict(weights=_weights(2, 1e-4)),
+    "weight 6 off by 2e-5": dict(weights=_weights(6, 2e-5)),
+    "centre weight off by a factor of 2^-13": dict(weights=_weights(4, factor=1.0 + 2.0 ** -13)),
+    "wrap addressing": dict(wrap=True),
+}
+
+
+@pytest.mark.parametrize("defect", list(BLUR_DEFECTS))
+@pytest.mark.parametrize("shape", [(128, 64, 64, 32), (64, 32, 64, 32), (32, 16, 64, 32)], ids=["down", "same", "up"])
+def test_blur_defects_are_rejected(defect, shape):
+    iw, ih, ow, oh = shape
+    img = bt.plane("noise", iw, ih)
+    for fn in (bt.blur_h, bt.blur_v):
+        t, m = fn(img, ow, oh)
+        n = rejected(fn(img, ow, oh, **BLUR_DEFECTS[defect])[0], t, bt.band(bt.K_BLUR, m), at_least=40)
+        print(f"{defect} {fn.__name__} {shape}: {n} of {t.size} values rejected")
+
+
+def test_taps_shifted_by_one_texel_are_rejected():
+    img = bt.plane("noise", 64, 32)
+    t, m = bt.blur_h(img, 64, 32)
+    shifted = img[:, np.clip(np.arange(64) + 1, 0, 63)]
+    assert rejected(bt.blur_h(shifted, 64, 32)[0], t, bt.band(bt.K_BLUR, m)) > t.size // 2
+
+
+def test_swapped_quarter_weights_are_rejected():
+    img = bt.plane("noise", 32, 16)
+    for fn in (bt.blur_h, bt.blur_v):
+        t, m = fn(img, 64, 32)
+        assert rejected(fn(img, 64, 32, swap=True)[0], t, bt.band(bt.K_BLUR, m)) > t.size // 2
+
+
+HALO_SEAM = (1027, 3, 513, 2)   # five of the seams' sixteen halo coordinates snap elsewhere
+
+
+def test_halo_from_the_neighbouring_groups_coordinate_is_rejected():
+    """the halo slots hold max(uv - 4 tx, 0) / min(uv + 4 tx, 1) of the group's own first and last threads; the neighbouring group's
+    ((x -+ 4) + 0.5f) * tx is another float32 number, and at a size that is no exact half it snaps elsewhere at some seam"""
+    iw, ih, ow, oh = HALO_SEAM
+    img = bt.plane("noise", iw, ih)
+    tx = F32(1.0) / F32(ow)
+    cc = bt.cache_coords(ow)
+    x = (np.arange(cc.shape[0])[:, None] * bt.GROUP - bt.HALO + np.arange(bt.CACHE)[None, :]).astype(F32)
+    wrong = cc.copy()
+    wrong[1:, :bt.HALO] = ((x + F32(0.5)) * tx)[1:, :bt.HALO]
+    wrong[:-1, bt.HALO + bt.GROUP:] = ((x + F32(0.5)) * tx)[:-1, bt.HALO + bt.GROUP:]
+    assert not np.array_equal(wrong, cc)
+    t, m = bt.blur_h(img, ow, oh)
+    n = rejected(bt.blur_h(img, ow, oh, cache=wrong)[0], t, bt.band(bt.K_BLUR, m))
+    print(f"halo from the neighbour at {HALO_SEAM}: {n} values rejected")
+
+
+def test_prefilter_defects_are_rejected():
+    img = bt.plane("noise", 128, 64)
+    t, m = bt.prefilter(img)
+    n1 = rejected(bt.prefilter(img, half_texel=True)[0], t, bt.U * m, at_least=1000)
+    n2 = rejected(bt.prefilter(img, luma=bt.LUMA[[1, 0, 2]])[0], t, bt.U * m, at_least=1000)
+    n3 = rejected(bt.prefilter(img, knee=0.5 + 2.0 ** -12)[0], t, bt.U * m, at_least=100)
+    print(f"prefilter: +0.5 {n1}, luminance coefficients permuted {n2}, knee off by 2^-12 {n3} of {t.size} rejected")
+
+
+def test_skipped_half_store_and_per_addend_rounding_are_rejected():
+    lower, upper = bt.plane("noise", 32, 16, seed=5), bt.plane("noise", 64, 32, seed=6)
+    (th, mh), (tv, mv), k = bt.up_level(upper, lower, 64, 32)
+    n1 = rejected(bt.blur_v(th, 64, 32)[0], tv, bt.band(bt.K_BLUR, mv), at_least=40)              # V of the unrounded H result
+    tl, tu = bt.blur_h(lower, 64, 32)[0], bt.blur_h(upper, 64, 32)[0]
+    per_addend = bt.rn_half(tl).astype(np.float64) + bt.rn_half(tu).astype(np.float64)
+    n2 = rejected(per_addend, th, bt.band(k, mh), at_least=40)
+    print(f"H -> V store skipped: {n1}; DUAL sum rounded per addend: {n2} of {th.size} rejected")
+
+
+def test_chain_with_one_v_pass_replaced_by_a_copy_is_rejected(chain_intervals):
+    img, lo, hi = chain_intervals(256, 128, "noise")
+    assert bt.check_chain(bt.run_chain(img, bt.Ops(0)), lo, hi)["width"] <= bt.CHAIN_WIDTH_CAP      # the rounded truth lies inside
+
+    class NoV(bt.Ops):
+        calls = 0
+
+        def blur_v(self, src, ow, oh):
+            self.calls += 1
+            return np.asarray(src, dtype=np.float16) if self.calls == 5 else super().blur_v(src, ow, oh)   # the V pass of up-level 2
+    with pytest.raises(AssertionError, match="outside the chain interval"):
+        bt.check_chain(bt.run_chain(img, NoV(0)), lo, hi)
+
+
+# ------------------------------------------------------------------------------------------------------ the conditions, on the truth alone
+def test_conditions_hold_on_every_case_set(chain_intervals):
+    worst = 0.0
+    for fn, shapes in ((bt.blur_h, bt.BLUR_H_SHAPES), (bt.blur_v, bt.BLUR_V_SHAPES)):
+        for i, (iw, ih, ow, oh) in enumerate(shapes):
+            for kind in bt.kinds_for(i):
+                t, m = fn(bt.plane(kind, iw, ih), ow, oh)
+                worst = max(worst, bt.stage_conditions(t, bt.band(bt.K_BLUR, m), f"{fn.__name__} {iw}x{ih} {kind}")[2])
+    for w, h in bt.PREFILTER_SHAPES:
+        for th, kn in bt.PREFILTER_PARAMS:
+            for kind in bt.KINDS:
+                t, m = bt.prefilter(bt.plane(kind, w, h, step=4), th, kn)
+                worst = max(worst, bt.stage_conditions(t, bt.U * m, f"prefilter {w}x{h} ({th}, {kn}) {kind}")[2])
+    for lw, lh in bt.UP_SHAPES:
+        for dual in (True, False):
+            (t, m), (tv, mv), k = bt.up_level(bt.plane("noise", 2 * lw, 2 * lh, seed=10) if dual else None, bt.plane("noise", lw, lh, seed=9), 2 * lw, 2 * lh)
+            worst = max(worst, bt.stage_conditions(t, bt.band(k, m), "up H")[2], bt.stage_conditions(tv, bt.band(bt.K_BLUR, mv), "up V")[2])
+    print(f"largest undecided share of a stage case: {worst:.4%}")
+    for w, h in bt.CHAIN_SHAPES:
+        for kind in CHAIN_KINDS:
+            _, lo, hi = chain_intervals(w, h, kind)
+            print(f"chain {w}x{h} {kind}:", bt.chain_conditions(lo, hi, f"chain {w}x{h} {kind}"))
