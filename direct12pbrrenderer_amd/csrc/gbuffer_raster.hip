@@ -6,7 +6,8 @@
 // launches on the caller's scratch:
 //   k_rs_clear   zero the per-bin counters
 //   k_rs_prep    one block: the first triangle of every draw (exclusive scan of index_count / 3) and the triangle count
-//   k_rs_setup   lane = triangle: vertex stage, near / guard-band clip, viewport, 16.8 snap, cull, bounding box; bin counts
+//   k_rs_setup   lane = triangle: vertex stage, near / guard-band clip, viewport, 16.8 snap, cull, bounding box, the resolve's
+//                planes; bin counts
 //   k_rs_scan    one wave: every bin's list offset in the pool, in raster order; a list that does not fit takes none
 //   k_rs_fill    lane = triangle: its id into the list of every bin its box touches (any order: k_rs_raster sorts)
 //   k_rs_raster  block = 16 x 16-pixel bin, lane = pixel: depth, stencil and the winning triangle in registers while the bin's
@@ -17,8 +18,11 @@
 // Coverage: exact 64-bit integer edge functions on 16.8 fixed-point vertices at pixel centres, top-left rule.  Depth: z / w of
 // the snapped vertices interpolated linearly in screen space (fp64, rounded once to fp32), clamped to [0, 1].  Normals: the
 // triangle's perspective-correct barycentrics from its 2D homogeneous edge planes (Olano & Greer 1997), so a clipped polygon
-// resolves against the triangle it came from.  Built with -ffp-contract=off: tests/raster_ref.py restates every step in the
-// same operation order.
+// resolves against the triangle it came from.  The planes are formed in fp64 about an integer pixel origin near the triangle (the
+// centre of its snapped polygon's bounding box within the frame) and rounded once to fp32; the resolve evaluates them at the pixel's
+// exact offset from that origin, so their accuracy does not depend on where in the frame the triangle lies.  Built with
+// -ffp-contract=off: tests/raster_ref.py restates every step in the same operation order; tests/raster_truth.py holds the
+// interpolated attributes to an fp64 statement of the contract.
 //
 // Textured draws (pbr_gbuffer_raster_textured) take the same six launches with a non-empty `Tex` pack on k_rs_setup and
 // k_rs_raster (the empty pack is the constant-material kernel): setup also writes the uv and tangent_ws of the three vertices
@@ -58,12 +62,13 @@ struct alignas(16) RsTri {
     float Z[MAX_POLY];
 };
 static_assert(sizeof(RsTri) == 112, "raster record layout");
-// resolve record: lambda_i(px, py) = (c[3i] * px + c[3i+1] * py) + c[3i+2] (screen pixels), normal_ws of vertex i = n[3i..3i+2]
+// resolve record: lambda_i(px, py) = (c[3i] * (px - ox) + c[3i+1] * (py - oy)) + c[3i+2] (screen pixels; the origin is a function
+// of the triangle and the frame, never of the tile), normal_ws of vertex i = n[3i..3i+2]
 struct RsAttr {
     float c[9];
     float n[9];
     uint32_t draw;
-    uint32_t pad;
+    uint32_t origin;                       // ox | oy << 16, each in [0, PBR_RASTER_MAX_SIZE]
 };
 static_assert(sizeof(RsAttr) == 80, "resolve record layout");
 // textured resolve record: uv of vertex i = uv[2i..2i+1], tangent_ws of vertex i = t[3i..3i+2]
@@ -99,6 +104,7 @@ inline Layout layout(uint32_t w, uint32_t h, uint32_t n_triangles, bool textured
 struct RsParams {
     float View[16], Projection[16];
     float half_w, half_h;
+    uint32_t full_w, full_h;
     uint32_t x0, y0, w, h;
     uint32_t nbx;
     uint32_t n_vertices, n_indices, n_draws;
@@ -204,9 +210,11 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
     const pbr_draw& d = draws[lo];
     RsTri rec;
     rec.n = 0; rec.lo = 0; rec.hi = 0; rec.pad = 0;
-    RsAttr at;
-    for (int i = 0; i < 9; i++) { at.c[i] = 0.0f; at.n[i] = 0.0f; }
-    at.draw = lo; at.pad = 0;
+    // the resolve record is stored in two halves: the normals and the draw after the vertex stage, the planes and their origin once
+    // the polygon is snapped (zero for a triangle that draws nothing), so the two are not live at once
+    float an[9], ac[9];
+    for (int i = 0; i < 9; i++) { an[i] = 0.0f; ac[i] = 0.0f; }
+    uint32_t origin = 0;
     // guard (device data): a draw range past n_indices, or an index (+ base_vertex) outside [0, n_vertices): the triangle is dropped
     const uint64_t first = (uint64_t)d.first_index + 3ull * (t - draw_base[lo]);
     bool ok = (uint64_t)d.first_index + d.index_count <= p.n_indices;
@@ -234,24 +242,12 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
             c[k].z = row4(p.Projection + 8, pv[0], pv[1], pv[2], pv[3]);
             c[k].w = row4(p.Projection + 12, pv[0], pv[1], pv[2], pv[3]);
             for (int i = 0; i < 3; i++)
-                at.n[3 * k + i] = ((d.InvModel[i] * v.normal[0] + d.InvModel[4 + i] * v.normal[1]) + d.InvModel[8 + i] * v.normal[2]) +
+                an[3 * k + i] = ((d.InvModel[i] * v.normal[0] + d.InvModel[4 + i] * v.normal[1]) + d.InvModel[8 + i] * v.normal[2]) +
                                   d.InvModel[12 + i] * 0.0f;
         }
-        // the triangle's 2D homogeneous screen vertices (sx / w, sy / w = the viewport transform) and their edge planes
-        float sx[3], sy[3], sw[3];
-        for (int k = 0; k < 3; k++) {
-            sx[k] = (c[k].x + c[k].w) * p.half_w;
-            sy[k] = (c[k].w - c[k].y) * p.half_h;
-            sw[k] = c[k].w;
-        }
-        for (int i = 0; i < 3; i++) {
-            const int j = (i + 1) % 3, k = (i + 2) % 3;
-            at.c[3 * i + 0] = sy[j] * sw[k] - sw[j] * sy[k];
-            at.c[3 * i + 1] = sw[j] * sx[k] - sx[j] * sw[k];
-            at.c[3 * i + 2] = sx[j] * sy[k] - sy[j] * sx[k];
-        }
     }
-    attrs[t] = at;
+    for (int i = 0; i < 9; i++) attrs[t].n[i] = an[i];
+    attrs[t].draw = lo;
     if constexpr (TEX) {
         // gbuffer.hlsl:80-84: tangent_ws = transpose(InvModel) (t, 0) (the normal's rule), uv as given; computed after the resolve
         // record is stored, so the two records are not live at once
@@ -330,6 +326,24 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
                 x0 = min(x0, rec.X[i]); x1 = max(x1, rec.X[i]);
                 y0 = min(y0, rec.Y[i]); y1 = max(y1, rec.Y[i]);
             }
+            // the resolve's origin: the centre of the polygon's bounding box within the frame, floored to a pixel
+            const int32_t fw8 = (int32_t)(p.full_w << 8), fh8 = (int32_t)(p.full_h << 8);
+            const int32_t ox = (min(max(x0, 0), fw8) + min(max(x1, 0), fw8)) >> 9, oy = (min(max(y0, 0), fh8) + min(max(y1, 0), fh8)) >> 9;
+            // the triangle's 2D homogeneous screen vertices (sx / w, sy / w = the viewport transform) about that origin and their
+            // edge planes, in fp64 (the translation cancels what the products would otherwise have to), each rounded once
+            double sx[3], sy[3], sw[3];
+            for (int k = 0; k < 3; k++) {
+                sw[k] = (double)c[k].w;
+                sx[k] = ((double)c[k].x + sw[k]) * (double)p.half_w - (double)ox * sw[k];
+                sy[k] = (sw[k] - (double)c[k].y) * (double)p.half_h - (double)oy * sw[k];
+            }
+            for (int i = 0; i < 3; i++) {
+                const int j = (i + 1) % 3, k = (i + 2) % 3;
+                ac[3 * i + 0] = (float)(sy[j] * sw[k] - sw[j] * sy[k]);
+                ac[3 * i + 1] = (float)(sw[j] * sx[k] - sx[j] * sw[k]);
+                ac[3 * i + 2] = (float)(sx[j] * sy[k] - sy[j] * sx[k]);
+            }
+            origin = (uint32_t)ox | ((uint32_t)oy << 16);
             // pixels whose centre (256 x + 128) lies in [x0, x1], clamped to the tile
             const int64_t px0 = max(-((128 - (int64_t)x0) >> 8), (int64_t)p.x0), px1 = min(((int64_t)x1 - 128) >> 8, (int64_t)(p.x0 + p.w) - 1);
             const int64_t py0 = max(-((128 - (int64_t)y0) >> 8), (int64_t)p.y0), py1 = min(((int64_t)y1 - 128) >> 8, (int64_t)(p.y0 + p.h) - 1);
@@ -343,6 +357,8 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
             }
         }
     }
+    for (int i = 0; i < 9; i++) attrs[t].c[i] = ac[i];
+    attrs[t].origin = origin;
     tris[t] = rec;
 }
 
@@ -625,7 +641,9 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
     if (win != NONE) {
         const RsAttr& at = attrs[win];
         const pbr_draw& d = draws[at.draw];
-        const float fx = (float)gx + 0.5f, fy = (float)gy + 0.5f;
+        // the pixel centre's offset from the triangle's origin: exact
+        const int32_t ox = (int32_t)(at.origin & 0xffffu), oy = (int32_t)(at.origin >> 16);
+        const float fx = (float)((int32_t)gx - ox) + 0.5f, fy = (float)((int32_t)gy - oy) + 0.5f;
         const float l0 = (at.c[0] * fx + at.c[1] * fy) + at.c[2];
         const float l1 = (at.c[3] * fx + at.c[4] * fy) + at.c[5];
         const float l2 = (at.c[6] * fx + at.c[7] * fy) + at.c[8];
@@ -642,7 +660,7 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
                 // the Use*Map == true branches (gbuffer.hlsl:62-69,99-141)
                 const TexLds& tl = tex_lds();
                 const RsTexAttr& ta = tx.tex[win];
-                // perspective-correct uv at (fx, fy), from the triangle's planes
+                // perspective-correct uv at an offset from the origin, from the triangle's planes
                 auto uv_at = [&](float x, float y, float& u, float& v) {
                     const float k0 = (at.c[0] * x + at.c[1] * y) + at.c[2];
                     const float k1 = (at.c[3] * x + at.c[4] * y) + at.c[5];
@@ -654,7 +672,7 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
                 float u, v, u00, v00, u10, v10, u01, v01;
                 uv_at(fx, fy, u, v);
                 // the LOD's differences: the quad (global pixels) around this pixel, this pixel's triangle
-                const float qx = (float)(gx & ~1u) + 0.5f, qy = (float)(gy & ~1u) + 0.5f;
+                const float qx = (float)((int32_t)(gx & ~1u) - ox) + 0.5f, qy = (float)((int32_t)(gy & ~1u) - oy) + 0.5f;
                 uv_at(qx, qy, u00, v00);
                 uv_at(qx + 1.0f, qy, u10, v10);
                 uv_at(qx, qy + 1.0f, u01, v01);
@@ -730,6 +748,7 @@ pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const
     for (int i = 0; i < 16; i++) { p.View[i] = g->View[i]; p.Projection[i] = g->Projection[i]; }
     p.half_w = 0.5f * (float)tile->full_w;
     p.half_h = 0.5f * (float)tile->full_h;
+    p.full_w = tile->full_w; p.full_h = tile->full_h;
     p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h;
     p.nbx = L.nbx;
     p.n_vertices = n_vertices; p.n_indices = n_indices; p.n_draws = n_draws;

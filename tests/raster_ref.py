@@ -3,11 +3,13 @@
 The contract, step by step, in the kernel's operation order: the vertex stage in float32 (sums left to right, no fused
 multiply-add), near / guard-band clipping in clip space, the viewport transform and the 1/256-pixel snap (round to nearest
 even), exact integer edge functions with the top-left rule, z / w interpolated in float64 and rounded once to float32,
-depth LESS, stencil INCR_SAT, and the winner's perspective-correct normal.  The planes are encoded by the oracle's
+depth LESS, stencil INCR_SAT, and the winner's perspective-correct normal from edge planes formed in float64 about the
+triangle's pixel origin, rounded once to float32 and evaluated at the pixel's offset from it.  The planes are encoded by the oracle's
 gbuffer_encode (oracle/pbr_oracle.cpp), the CPU statement of gbuffer.hlsl::ps_main's outputs.
 
 An exact match with this file shows that two implementations of one reading agree; the GPU tests also check the contract's
-properties against independent truths (tests/test_gpu_raster.py)."""
+properties against independent truths (tests/test_gpu_raster.py), and tests/raster_truth.py holds the interpolated attributes
+of this file and of the kernel to a float64 statement of the contract."""
 import numpy as np
 
 f32, f64 = np.float32, np.float64
@@ -96,11 +98,35 @@ def snap_record(cv, half_w, half_h, tile):
     return X, Y, Z, (px0, py0, px1, py1)
 
 
+def origin(X, Y, full_w, full_h):
+    """The resolve's pixel origin of a snapped polygon: the centre of its bounding box within the frame, floored to a pixel."""
+    cx = lambda v: min(max(v, 0), full_w << 8)
+    cy = lambda v: min(max(v, 0), full_h << 8)
+    return (cx(min(X)) + cx(max(X))) >> 9, (cy(min(Y)) + cy(max(Y))) >> 9
+
+
+def planes(clip, half_w, half_h, ox, oy):
+    """clip [3, 4] float32 -> c[9] float32: the edge planes of the 2D homogeneous screen triangle about (ox, oy), formed in
+    float64 (sums left to right, no fused multiply-add) and rounded once."""
+    cl = clip.astype(f64)
+    sw = cl[:, 3]
+    sx = (cl[:, 0] + sw) * f64(half_w) - f64(ox) * sw
+    sy = (sw - cl[:, 1]) * f64(half_h) - f64(oy) * sw
+    c = np.zeros(9, f32)
+    for i in range(3):
+        j, k = (i + 1) % 3, (i + 2) % 3
+        c[3 * i + 0] = f32(sy[j] * sw[k] - sw[j] * sy[k])
+        c[3 * i + 1] = f32(sw[j] * sx[k] - sx[j] * sw[k])
+        c[3 * i + 2] = f32(sx[j] * sy[k] - sy[j] * sx[k])
+    return c
+
+
 def setup(g, tile, vertices, indices, draws, max_triangles=None):
-    """Per triangle id (draw order): the raster record (or None) and the resolve record (c[9], n[9], draw)."""
+    """Per triangle id (draw order): the raster record (or None), the resolve record (c[9], n[9], draw) and the planes' pixel
+    origin [t, 2].  A triangle without a raster record covers no pixel: its planes stay zero here."""
     half_w, half_h = f32(0.5) * f32(tile.full_w), f32(0.5) * f32(tile.full_h)
     n_idx, n_vtx = len(indices), len(vertices)
-    recs, cs, ns, ds = [], [], [], []
+    recs, cs, ns, ds, os_ = [], [], [], [], []
     with np.errstate(all="ignore"):
         for di, d in enumerate(draws):
             cnt = int(d["index_count"]) // 3
@@ -108,6 +134,7 @@ def setup(g, tile, vertices, indices, draws, max_triangles=None):
             cs.append(np.zeros((cnt, 9), f32))
             ns.append(np.zeros((cnt, 9), f32))
             ds.append(np.full(cnt, di, np.int64))
+            os_.append(np.zeros((cnt, 2), np.int64))
             if cnt == 0:
                 continue
             if first + int(d["index_count"]) > n_idx:
@@ -118,21 +145,18 @@ def setup(g, tile, vertices, indices, draws, max_triangles=None):
             safe = np.clip(idx, 0, n_vtx - 1)
             clip, nw = vertex_stage(g, d, vertices["position"][safe], vertices["normal"][safe])
             clip, nw = clip.reshape(cnt, 3, 4), nw.reshape(cnt, 9)
-            sx = (clip[..., 0] + clip[..., 3]) * half_w
-            sy = (clip[..., 3] - clip[..., 1]) * half_h
-            sw = clip[..., 3]
-            c = cs[-1]
-            for i in range(3):
-                j, k = (i + 1) % 3, (i + 2) % 3
-                c[:, 3 * i + 0] = sy[:, j] * sw[:, k] - sw[:, j] * sy[:, k]
-                c[:, 3 * i + 1] = sw[:, j] * sx[:, k] - sx[:, j] * sw[:, k]
-                c[:, 3 * i + 2] = sx[:, j] * sy[:, k] - sy[:, j] * sx[:, k]
-            c[~valid] = 0
             ns[-1][valid] = nw[valid]
-            recs += [snap_record(clip[t], half_w, half_h, tile) if valid[t] else None for t in range(cnt)]
+            new = [snap_record(clip[t], half_w, half_h, tile) if valid[t] else None for t in range(cnt)]
+            for t, r in enumerate(new):
+                if r is not None:
+                    ox, oy = origin(r[0], r[1], int(tile.full_w), int(tile.full_h))
+                    cs[-1][t] = planes(clip[t], half_w, half_h, ox, oy)
+                    os_[-1][t] = ox, oy
+            recs += new
     total = len(recs) if max_triangles is None else min(len(recs), int(max_triangles))
     cat = (lambda a: np.concatenate(a)[:total]) if cs else (lambda a: np.zeros((0, 9)))
-    return recs[:total], cat(cs), cat(ns), np.concatenate(ds)[:total] if ds else np.zeros(0, np.int64)
+    return (recs[:total], cat(cs), cat(ns), np.concatenate(ds)[:total] if ds else np.zeros(0, np.int64),
+            np.concatenate(os_)[:total] if os_ else np.zeros((0, 2), np.int64))
 
 
 def _edge(xa, ya, xb, yb, PX, PY):
@@ -176,9 +200,10 @@ def rasterize(recs, tile):
     return zbuf, sten, win
 
 
-def raster(g, tile, vertices, indices, draws, orc, max_triangles=None):
-    """The five planes pbr_gbuffer_raster writes for this tile: dict A, B, C (uint32), depth (float32), stencil (uint8)."""
-    recs, c, n, dr = setup(g, tile, vertices, indices, draws, max_triangles)
+def raster(g, tile, vertices, indices, draws, orc, max_triangles=None, taps=None):
+    """The five planes pbr_gbuffer_raster writes for this tile: dict A, B, C (uint32), depth (float32), stencil (uint8).
+    taps: a dict that receives the covered pixels (ys, xs), their winner (t) and the interpolated normal before the encode (nrm)."""
+    recs, c, n, dr, org = setup(g, tile, vertices, indices, draws, max_triangles)
     zbuf, sten, win = rasterize(recs, tile)
     h, w = tile.h, tile.w
     m0, m1, m2 = (np.zeros((h, w, 4), f32) for _ in range(3))
@@ -186,12 +211,14 @@ def raster(g, tile, vertices, indices, draws, orc, max_triangles=None):
     if len(ys):
         t = win[ys, xs]
         cc, nn, d = c[t], n[t], draws[dr[t]]
-        fx = (xs + tile.x0).astype(f32) + f32(0.5)
-        fy = (ys + tile.y0).astype(f32) + f32(0.5)
+        fx = (xs + tile.x0 - org[t, 0]).astype(f32) + f32(0.5)      # the offset from the triangle's origin: exact
+        fy = (ys + tile.y0 - org[t, 1]).astype(f32) + f32(0.5)
         with np.errstate(all="ignore"):
             lam = [(cc[:, 3 * i] * fx + cc[:, 3 * i + 1] * fy) + cc[:, 3 * i + 2] for i in range(3)]
             inv = f32(1.0) / ((lam[0] + lam[1]) + lam[2])
             nrm = [((lam[0] * nn[:, j] + lam[1] * nn[:, 3 + j]) + lam[2] * nn[:, 6 + j]) * inv for j in range(3)]
+        if taps is not None:
+            taps.update(ys=ys, xs=xs, t=t, nrm=np.stack(nrm, axis=1))
         alb = np.asarray(d["Albedo"], dtype=f32).reshape(-1, 3)
         m0[ys, xs] = np.stack([alb[:, 0], alb[:, 1], alb[:, 2], d["Emission"].astype(f32)], axis=1)
         m1[ys, xs] = np.stack([nrm[0], nrm[1], nrm[2], d["Roughness"].astype(f32)], axis=1)

@@ -2,8 +2,9 @@
 
 The geometry (vertex stage, clipping, snap, coverage, depth, stencil, the winner) is tests/raster_ref.py's.  On top of it, in the
 kernel's operation order: tangent_ws by the normal's rule and uv per vertex, their perspective-correct interpolation from the
-same homogeneous planes, the quad's LOD, the trilinear samples of SamplerLinearWrap as pinned in the header, the normal-map
-frame, and the oracle's gbuffer_encode.  Fused multiply-adds (the sampler's lerps) are evaluated exactly (fma32).
+same homogeneous planes (about the triangle's pixel origin, raster_ref.planes), the quad's LOD, the trilinear samples of
+SamplerLinearWrap as pinned in the header, the normal-map frame, and the oracle's gbuffer_encode.  Fused multiply-adds
+(the sampler's lerps) are evaluated exactly (fma32).
 
 A texture here is a dict: levels (uint8 arrays, [h_l, w_l, 4] in memory byte order for the 4-byte formats, [h_l, w_l] for R8),
 width, height, mips, format (the DXGI number)."""
@@ -152,9 +153,11 @@ def _normalize(x, y, z):
     return x * r, y * r, z * r
 
 
-def raster_textured(g, tile, vertices, indices, draws, maps, textures, orc, max_triangles=None):
-    """The five planes pbr_gbuffer_raster_textured writes for this tile (textures: the texture dicts, in table order)."""
-    recs, c, n, dr = raster_ref.setup(g, tile, vertices, indices, draws, max_triangles)
+def raster_textured(g, tile, vertices, indices, draws, maps, textures, orc, max_triangles=None, taps=None):
+    """The five planes pbr_gbuffer_raster_textured writes for this tile (textures: the texture dicts, in table order).
+    taps: a dict that receives the covered pixels (ys, xs), their winner (t), the interpolated normal (nrm), tangent (tan) and uv
+    (u, v) before any map is applied, and the quad's uv differences (dxu, dxv, dyu, dyv)."""
+    recs, c, n, dr, org = raster_ref.setup(g, tile, vertices, indices, draws, max_triangles)
     uv, tg, good = tex_setup(vertices, indices, draws, maps, len(textures), max_triangles)
     recs = [r if good[t] else None for t, r in enumerate(recs)]
     c, n = c.copy(), n.copy()
@@ -167,7 +170,8 @@ def raster_textured(g, tile, vertices, indices, draws, maps, textures, orc, max_
         t = win[ys, xs]
         cc, nn, tt, uu, d, mp = c[t], n[t], tg[t], uv[t], draws[dr[t]], maps[dr[t]]
         gx, gy = xs + tile.x0, ys + tile.y0
-        fx, fy = gx.astype(f32) + f32(0.5), gy.astype(f32) + f32(0.5)
+        ox, oy = org[t, 0], org[t, 1]          # positions are offsets from the triangle's origin: exact
+        fx, fy = (gx - ox).astype(f32) + f32(0.5), (gy - oy).astype(f32) + f32(0.5)
 
         def planes(px, py):
             lam = [(cc[:, 3 * i] * px + cc[:, 3 * i + 1] * py) + cc[:, 3 * i + 2] for i in range(3)]
@@ -184,7 +188,7 @@ def raster_textured(g, tile, vertices, indices, draws, maps, textures, orc, max_
             metal = d["Metallic"].astype(f32).copy()
             ao = np.zeros(len(t), f32)
             u, v = interp(lam, inv, uu, 0, 2), interp(lam, inv, uu, 1, 2)
-            qx, qy = (gx & ~1).astype(f32) + f32(0.5), (gy & ~1).astype(f32) + f32(0.5)
+            qx, qy = ((gx & ~1) - ox).astype(f32) + f32(0.5), ((gy & ~1) - oy).astype(f32) + f32(0.5)
             l00, i00 = planes(qx, qy)
             l10, i10 = planes(qx + f32(1.0), qy)
             l01, i01 = planes(qx, qy + f32(1.0))
@@ -192,6 +196,9 @@ def raster_textured(g, tile, vertices, indices, draws, maps, textures, orc, max_
             u10, v10 = interp(l10, i10, uu, 0, 2), interp(l10, i10, uu, 1, 2)
             u01, v01 = interp(l01, i01, uu, 0, 2), interp(l01, i01, uu, 1, 2)
             dxu, dxv, dyu, dyv = u10 - u00, v10 - v00, u01 - u00, v01 - v00
+            if taps is not None:
+                taps.update(ys=ys, xs=xs, t=t, nrm=np.stack(nrm, axis=1), tan=np.stack([interp(lam, inv, tt, j, 3) for j in range(3)], axis=1),
+                            u=u, v=v, dxu=dxu, dxv=dxv, dyu=dyu, dyv=dyv)
             decs = [decode_levels(tx) for tx in textures]
 
             def sampled(name):
