@@ -90,6 +90,8 @@ SIGNATURES = {
     "pbr_bloom_histogram_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _u32, _f32, _f32, _f32, _f32]),
     "pbr_lum_average_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _f32, _f32]),
     "pbr_tonemap_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _u32]),
+    "pbr_skybox_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _u32, C.POINTER(CubeF32)]),
+    "pbr_skybox_bc6h_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _u32, C.POINTER(CubeBc6h)]),
     "pbr_comm_unique_id": (_int, [_vp]),
     "pbr_comm_init": (_int, [_vp, _int, _int, _vp]),
     "pbr_allreduce_hist": (_int, [_vp, _vp]),

@@ -604,6 +604,16 @@ class PbrContext:
     def tonemap_views(self, views, n, w, h):
         self._check(self.lib.pbr_tonemap_views(self.h, views, n, w, h))
 
+    def skybox_views(self, views, n, w, h, sky, sky_size, sky_mips):
+        """pbr_skybox_views: skybox() of every view (g, gb.stencil, hdr) in one launch"""
+        c = CubeF32(sky.data_ptr(), sky_size, sky_mips)
+        self._check(self.lib.pbr_skybox_views(self.h, views, int(n), int(w), int(h), C.byref(c)))
+
+    def skybox_bc6h_views(self, views, n, w, h, faces, size, mip_levels):
+        """pbr_skybox_bc6h_views: skybox_bc6h() of every view in one launch; faces as skybox_bc6h takes them"""
+        c = CubeBc6h(_bc6h_faces("skybox_bc6h_views", faces, size, mip_levels), int(size), int(mip_levels))
+        self._check(self.lib.pbr_skybox_bc6h_views(self.h, views, int(n), int(w), int(h), C.byref(c)))
+
     def membench_read(self, buf, sink, blocks):
         """One streaming-read pass over `buf` (measurement aid: the device's achievable HBM-read bandwidth)."""
         self._check(self.lib.pbr_membench_read(self.h, _ptr(buf), buf.numel() * buf.element_size(), _ptr(sink), blocks))

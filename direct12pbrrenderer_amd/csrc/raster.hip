@@ -10,6 +10,7 @@
 #include "pbr_device.hpp"
 #include "tex_chain.hpp"
 #include "bc6h_decode_block.hpp"
+#include <type_traits>
 
 using namespace pbr;
 
@@ -72,8 +73,30 @@ __device__ __forceinline__ void project_on_face(V3 d, uint32_t face, float& u, f
     const F4 c = SAMPLE(d, lod);                                                                                    \
     store_h4(hdr + 4 * ((size_t)py * p.hdr_pitch + px), f4(c.x, c.y, c.z, 1.0f));
 
+// pbr_skybox_views / pbr_skybox_bc6h_views: grid (.., .., views); view blockIdx.z's camera terms, stencil plane and HDR target from
+// the view table, in place of p's and the arguments'.  NoViews (empty, last in the argument block: it moves no argument): the
+// single-view kernel.
+struct SkyView {
+    float InvView[9];
+    float near_width, near_height, Near;
+    const uint8_t* stencil;
+    pbr_half* hdr;
+    uint32_t pitch, hdr_pitch;
+};
+struct SkyViews { SkyView v[PBR_MAX_VIEWS]; };
+#define PBR_SKY_TAKE_VIEW(VS, vs, p, stencil, hdr)                                                                  \
+    if constexpr (!std::is_same_v<VS, NoViews>) {                                                                   \
+        const SkyView& view = vs.v[blockIdx.z];                                                                     \
+        for (int i = 0; i < 9; i++) p.InvView[i] = view.InvView[i];                                                 \
+        p.near_width = view.near_width; p.near_height = view.near_height; p.Near = view.Near;                       \
+        p.pitch = view.pitch; p.hdr_pitch = view.hdr_pitch;                                                         \
+        stencil = view.stencil; hdr = view.hdr;                                                                     \
+    }
+
+template <class VS>
 __global__ __launch_bounds__(256) void k_skybox(SkyParams p, const float* __restrict__ sky,
-                                                const uint8_t* __restrict__ stencil, pbr_half* __restrict__ hdr) {
+                                                const uint8_t* __restrict__ stencil, pbr_half* __restrict__ hdr, VS vs) {
+    PBR_SKY_TAKE_VIEW(VS, vs, p, stencil, hdr)
 #define PBR_SKY_F32(d, lod) cube_trilinear<CubeTexelF32, true>(sky, p.sky_size, p.sky_mips, d, lod)   // the oracle's divides (pbr_device.hpp)
     PBR_SKYBOX_PIXEL(p, stencil, hdr, PBR_SKY_F32)
 #undef PBR_SKY_F32
@@ -186,7 +209,12 @@ __device__ __forceinline__ F4 bc6h_trilinear(const SkyBc6h& L, uint32_t size, ui
     return one ? a : fma4(b, f, a * (1.0f - f));
 }
 
-__global__ __launch_bounds__(256) void k_skybox_bc6h(SkyParams p, SkyBc6h sky, const uint8_t* __restrict__ stencil, pbr_half* __restrict__ hdr) {
+static_assert(sizeof(SkyParams) + sizeof(SkyBc6h) + 2 * 8 + sizeof(SkyViews) <= 4096 - 256, "k_skybox<SkyViews>, k_skybox_bc6h<SkyViews>: kernel arguments over 4 KiB");
+
+template <class VS>
+__global__ __launch_bounds__(256) void k_skybox_bc6h(SkyParams p, SkyBc6h sky, const uint8_t* __restrict__ stencil, pbr_half* __restrict__ hdr,
+                                                     VS vs) {
+    PBR_SKY_TAKE_VIEW(VS, vs, p, stencil, hdr)
 #define PBR_SKY_BC6H(d, lod) bc6h_trilinear(sky, p.sky_size, p.sky_mips, d, lod)
     PBR_SKYBOX_PIXEL(p, stencil, hdr, PBR_SKY_BC6H)
 #undef PBR_SKY_BC6H
@@ -202,6 +230,40 @@ void fill_sky_params(SkyParams& p, const pbr_global* g, const pbr_tile* tile, ui
     p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h;
     p.sky_size = size; p.sky_mips = mips;
     p.pitch = pitch; p.hdr_pitch = hdr_pitch;
+}
+
+// the views of a sky resolve, checked (nullptr: usable; the caller refuses under its own name), as the kernels' table; p: what the
+// views share (whole w x h frames, the cube's size)
+const char* fill_sky_views(SkyParams& p, SkyViews& vs, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h, uint32_t size, uint32_t mips) {
+    if (!views_count_ok(views, n)) return "need 1 .. PBR_MAX_VIEWS views";
+    if (!(w && h)) return "bad size";
+    const pbr_tile tile{0, 0, w, h, w, h};
+    for (uint32_t i = 0; i < n; i++) {
+        const pbr_view& v = views[i];
+        if (!(v.gb.stencil && v.hdr)) return "null pointer in a view";
+        if (!(v.gb.pitch >= w && v.hdr_pitch >= w)) return "a view's pitch < width";
+        fill_sky_params(p, &v.g, &tile, size, mips, v.gb.pitch, v.hdr_pitch);
+        SkyView& s = vs.v[i];
+        for (int k = 0; k < 9; k++) s.InvView[k] = p.InvView[k];
+        s.near_width = p.near_width; s.near_height = p.near_height; s.Near = p.Near;
+        s.stencil = v.gb.stencil; s.hdr = v.hdr;
+        s.pitch = v.gb.pitch; s.hdr_pitch = v.hdr_pitch;
+    }
+    if (!views_disjoint(views, n, 1, [&](const pbr_view& v, int, uintptr_t& lo, uintptr_t& hi) {
+            lo = addr(v.hdr); hi = lo + ((size_t)(h - 1) * v.hdr_pitch + w) * 8; }))
+        return "two views' HDR targets overlap";
+    return nullptr;
+}
+
+// the resident cube, checked (nullptr: usable), as k_skybox_bc6h takes it
+const char* fill_sky_bc6h(SkyBc6h& L, const pbr_cube_bc6h* sky) {
+    if (const char* why = bc6h_chain::refusal(sky->size, sky->mips)) return why;
+    if (const char* why = bc6h_chain::faces_refusal(sky->face_blocks)) return why;
+    bc6h_chain::Cube<const uint4*> T;             // (a face's blocks in front of a level are below 2^28: bc6h_bilinear's key)
+    bc6h_chain::fill(T, sky->size, sky->mips);
+    for (int f = 0; f < 6; f++) L.face[f] = static_cast<const uint4*>(sky->face_blocks[f]);
+    for (uint32_t l = 0; l < bc6h_chain::MAX_LEVELS; l++) L.face_first[l] = T.face_first[l];
+    return nullptr;
 }
 
 }  // namespace
@@ -229,8 +291,20 @@ pbr_status pbr_skybox(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, c
     SkyParams p;
     fill_sky_params(p, g, tile, sky->size, sky->mips, pitch, hdr_pitch);
     dim3 grid((tile->w + 63) / 64, (tile->h + 3) / 4);
-    hipLaunchKernelGGL(k_skybox, grid, dim3(256), 0, ctx->stream, p, sky->data, stencil, hdr);
+    hipLaunchKernelGGL(k_skybox<NoViews>, grid, dim3(256), 0, ctx->stream, p, sky->data, stencil, hdr, NoViews{});
     return pbr::launched(ctx, "k_skybox");
+}
+
+pbr_status pbr_skybox_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h, const pbr_cube_f32* sky) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, sky && sky->data, "pbr_skybox_views: null pointer");
+    PBR_REQUIRE(ctx, sky->size && sky->mips && (sky->size >> (sky->mips - 1)) >= 1, "pbr_skybox_views: bad cube");
+    SkyParams p;
+    SkyViews vs{};
+    PBR_CHECK(ctx, "pbr_skybox_views", fill_sky_views(p, vs, views, n, w, h, sky->size, sky->mips));
+    dim3 grid((w + 63) / 64, (h + 3) / 4, n);
+    hipLaunchKernelGGL(k_skybox<SkyViews>, grid, dim3(256), 0, ctx->stream, p, sky->data, (const uint8_t*)nullptr, (pbr_half*)nullptr, vs);
+    return pbr::launched(ctx, "k_skybox<views>");
 }
 
 pbr_status pbr_skybox_bc6h(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_cube_bc6h* sky,
@@ -239,18 +313,26 @@ pbr_status pbr_skybox_bc6h(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* ti
     PBR_REQUIRE(ctx, g && tile && sky && stencil && hdr, "pbr_skybox_bc6h: null pointer");
     PBR_REQUIRE(ctx, tile->w && tile->h && tile->full_w && tile->full_h && pitch >= tile->w && hdr_pitch >= tile->w,
                 "pbr_skybox_bc6h: bad tile / pitch");
-    PBR_CHECK(ctx, "pbr_skybox_bc6h", bc6h_chain::refusal(sky->size, sky->mips));
-    PBR_CHECK(ctx, "pbr_skybox_bc6h", bc6h_chain::faces_refusal(sky->face_blocks));
-    bc6h_chain::Cube<const uint4*> T;             // (a face's blocks in front of a level are below 2^28: bc6h_bilinear's key)
-    bc6h_chain::fill(T, sky->size, sky->mips);
     SkyBc6h L;
-    for (int f = 0; f < 6; f++) L.face[f] = static_cast<const uint4*>(sky->face_blocks[f]);
-    for (uint32_t l = 0; l < bc6h_chain::MAX_LEVELS; l++) L.face_first[l] = T.face_first[l];
+    PBR_CHECK(ctx, "pbr_skybox_bc6h", fill_sky_bc6h(L, sky));
     SkyParams p;
     fill_sky_params(p, g, tile, sky->size, sky->mips, pitch, hdr_pitch);
     dim3 grid((tile->w + 63) / 64, (tile->h + 3) / 4);
-    hipLaunchKernelGGL(k_skybox_bc6h, grid, dim3(256), 0, ctx->stream, p, L, stencil, hdr);
+    hipLaunchKernelGGL(k_skybox_bc6h<NoViews>, grid, dim3(256), 0, ctx->stream, p, L, stencil, hdr, NoViews{});
     return pbr::launched(ctx, "k_skybox_bc6h");
+}
+
+pbr_status pbr_skybox_bc6h_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h, const pbr_cube_bc6h* sky) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, sky, "pbr_skybox_bc6h_views: null pointer");
+    SkyBc6h L;
+    PBR_CHECK(ctx, "pbr_skybox_bc6h_views", fill_sky_bc6h(L, sky));
+    SkyParams p;
+    SkyViews vs{};
+    PBR_CHECK(ctx, "pbr_skybox_bc6h_views", fill_sky_views(p, vs, views, n, w, h, sky->size, sky->mips));
+    dim3 grid((w + 63) / 64, (h + 3) / 4, n);
+    hipLaunchKernelGGL(k_skybox_bc6h<SkyViews>, grid, dim3(256), 0, ctx->stream, p, L, (const uint8_t*)nullptr, (pbr_half*)nullptr, vs);
+    return pbr::launched(ctx, "k_skybox_bc6h<views>");
 }
 
 pbr_status pbr_gbuffer_encode(pbr_ctx* ctx, const float* m0, const float* m1, const float* m2,

@@ -750,15 +750,12 @@ class MultiViewFrame:
             self.ctx.clustered_views(arr, n)
 
     def skybox(self):
-        """the sky resolve stays one launch per view"""
-        if isinstance(self.sky, ResidentSky):
-            for v in range(self.n):
-                self.ctx.skybox_bc6h(self.globals[v], self.tile, self.sky.faces, self.sky.size, self.sky.mips, self.gb[v]["stencil"], self.w,
-                                     self.hdrs[v], self.w)
-            return
-        cube, size, mips = self.sky
-        for v in range(self.n):
-            self.ctx.skybox(self.globals[v], self.tile, cube, size, mips, self.gb[v]["stencil"], self.w, self.hdrs[v], self.w)
+        for arr, n, _ in self._calls():
+            if isinstance(self.sky, ResidentSky):
+                self.ctx.skybox_bc6h_views(arr, n, self.w, self.h, self.sky.faces, self.sky.size, self.sky.mips)
+            else:
+                cube, size, mips = self.sky
+                self.ctx.skybox_views(arr, n, self.w, self.h, cube, size, mips)
 
     def shade(self):
         for arr, n, _ in self._calls():

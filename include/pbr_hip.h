@@ -826,6 +826,15 @@ pbr_status pbr_lum_average_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n
 /* hdr_tone_mapping.hlsl (DeferredPipeline.cpp:320-336) per view: pbr_tonemap(hdr, avg -> rgba8) of the whole frame. */
 pbr_status pbr_tonemap_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h);
 
+/* ---- multi-view sky resolve (new): the sky of N views per launch -------------------------------------------------------- */
+/* SkyboxPass::Execute per view: pbr_skybox / pbr_skybox_bc6h of the whole w x h frame under views[v].g, on the pixels with
+ * views[v].gb.stencil == 0 (pitch gb.pitch), into views[v].hdr (pitch hdr_pitch); the other fields of a view are not read and may be
+ * null.  One launch (the view in the grid).  Every view's HDR target is bit-identical to its single-view call's; pixels with
+ * stencil != 0 are untouched.  Refusals (PBR_ERR_INVALID, nothing enqueued): n == 0 or n > PBR_MAX_VIEWS, a null pointer the call
+ * uses, a view's gb.pitch or hdr_pitch < w, two views whose HDR targets overlap, and every limit of the single-view call. */
+pbr_status pbr_skybox_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h, const pbr_cube_f32* sky);
+pbr_status pbr_skybox_bc6h_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h, const pbr_cube_bc6h* sky);
+
 /* ---- multi-GPU (new) -------------------------------------------------------------- */
 /* RCCL communicator over the ranks of one node.  unique_id: 128 bytes from
  * pbr_comm_unique_id() on rank 0, broadcast by the caller (e.g. torch.distributed store). */
