@@ -70,6 +70,11 @@ SIGNATURES = {
     "pbr_gbuffer_raster_textured_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster_textured": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
                                            _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, C.POINTER(Texture2D), _u32]),
+    "pbr_draw_bounds": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "pbr_gbuffer_raster_culled": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
+                                         _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _vp]),
+    "pbr_gbuffer_raster_textured_culled": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
+                                                  _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, C.POINTER(Texture2D), _u32, _vp, _vp]),
     "pbr_bloom_prefilter": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _f32, _f32]),
     "pbr_blur_h": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),
     "pbr_blur_v": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),

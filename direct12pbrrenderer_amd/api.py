@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from .structs import (ShadeDesc, ShadeTables, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
+                      NUM_CLUSTERS, AABB_DTYPE, CullStats, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
 
 
 class PbrError(RuntimeError):
@@ -153,7 +153,7 @@ class PbrContext:
 
     def upload(self, arr):
         arr = np.ascontiguousarray(arr)
-        if arr.dtype in (LIGHT_DTYPE, CLUSTER_DTYPE, VERTEX_DTYPE, DRAW_DTYPE, DRAW_MAPS_DTYPE):
+        if arr.dtype in (LIGHT_DTYPE, CLUSTER_DTYPE, VERTEX_DTYPE, DRAW_DTYPE, DRAW_MAPS_DTYPE, AABB_DTYPE):
             arr = arr.view(np.uint8)
         if arr.dtype == np.uint32:
             return torch.from_numpy(arr.view(np.int32)).to(self.torch_device)
@@ -519,6 +519,47 @@ class PbrContext:
             self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices), int(n_indices), _ptr(draws),
             int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc), _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch),
             nbytes, _ptr(maps), table if textures else None, len(textures)))
+
+    # ---- model culling ---------------------------------------------------------------------------
+    def draw_bounds(self, vertices, n_vertices, indices, n_indices, draws, n_draws, out=None):
+        """pbr_draw_bounds: the draws' local boxes (device structs.AABB_DTYPE records as a [n_draws, 6] float32 tensor: min, max)
+        from the device buffers the raster takes; asynchronous.  The host twin is scene.MeshScene.bounds / scene.draw_bounds."""
+        out = out if out is not None else self.empty((int(n_draws), 6), torch.float32)
+        self._check(self.lib.pbr_draw_bounds(self.h, _ptr(vertices), int(n_vertices), _ptr(indices), int(n_indices), _ptr(draws),
+                                             int(n_draws), _ptr(out)))
+        return out
+
+    def alloc_cull_stats(self):
+        """device pbr_cull_stats (4 x uint32 as int32) for the culled calls; read it back with read_cull_stats"""
+        return self.zeros((4,), torch.int32)
+
+    def read_cull_stats(self, stats):
+        """structs.CullStats of a device record the culled calls wrote (synchronises)"""
+        v = stats.cpu().numpy().view(np.uint32)
+        return CullStats(int(v[0]), int(v[1]), int(v[2]), int(v[3]))
+
+    def gbuffer_raster_culled(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
+                              A, B, Cc, depth, stencil, pitch, scratch, bounds, stats=None, scratch_bytes=None):
+        """pbr_gbuffer_raster_culled: gbuffer_raster plus bounds (device AABB_DTYPE records, one per draw: draw_bounds) and stats
+        (device, alloc_cull_stats; None: not recorded).  A draw whose world box lies outside the widened tile's frustum is not set
+        up; the planes are bit-identical to gbuffer_raster's."""
+        nbytes = scratch.numel() * scratch.element_size() if scratch_bytes is None else int(scratch_bytes)
+        self._check(self.lib.pbr_gbuffer_raster_culled(
+            self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices), int(n_indices), _ptr(draws),
+            int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc), _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch),
+            nbytes, _ptr(bounds), _ptr(stats)))
+
+    def gbuffer_raster_textured_culled(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws,
+                                       max_triangles, A, B, Cc, depth, stencil, pitch, scratch, maps, textures, bounds, stats=None,
+                                       scratch_bytes=None):
+        """pbr_gbuffer_raster_textured_culled: gbuffer_raster_textured plus bounds and stats as gbuffer_raster_culled takes them"""
+        textures = list(textures)
+        table = (Texture2D * max(len(textures), 1))(*textures)
+        nbytes = scratch.numel() * scratch.element_size() if scratch_bytes is None else int(scratch_bytes)
+        self._check(self.lib.pbr_gbuffer_raster_textured_culled(
+            self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices), int(n_indices), _ptr(draws),
+            int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc), _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch),
+            nbytes, _ptr(maps), table if textures else None, len(textures), _ptr(bounds), _ptr(stats)))
 
     def bloom_prefilter(self, hdr, w, h, pitch, out, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE):
         self._check(self.lib.pbr_bloom_prefilter(self.h, _ptr(hdr), w, h, pitch, _ptr(out), threshold, knee))

@@ -33,9 +33,16 @@
 // BC1-resident textures (PBR_TEX_BC1_BLOCKS): a table that holds one runs k_rs_raster<RsRasterTexBc1>, whose bilinear takes its taps
 // from the blocks in place (bc1_decode.hpp).  The bulk decode of a whole chain (pbr_bc1_decode) is texture2d.hip's; the texture table's
 // descriptions are checked by tex_chain.hpp.
+//
+// Model culling (pbr_gbuffer_raster_culled, pbr_gbuffer_raster_textured_culled): Scene::CullModel on the device.  The same six
+// launches with a non-empty `Cull` pack on k_rs_prep (the empty pack is the kernel without it): a draw whose world box lies outside
+// one of the six planes of the widened tile (the rule pinned in pbr_hip.h) gets no triangles in the scan, so neither k_rs_setup
+// nor k_rs_fill ever sees it.  The planes are formed on the host in fp64 per call; nothing is read back.  k_rs_bounds
+// (pbr_draw_bounds) makes the draws' local boxes from the buffers the raster takes.  tests/raster_cull_ref.py restates both.
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
 #include "tex_chain.hpp"
+#include <cfloat>
 #include <type_traits>
 
 using namespace pbr;
@@ -127,7 +134,13 @@ struct RsRasterTex {
 // the same arguments for a table that holds a BC1-resident texture (PBR_TEX_BC1_BLOCKS): a kernel of its own, picked on the host,
 // so a table of decoded textures keeps the kernel it had
 struct RsRasterTexBc1 : RsRasterTex {};
-// the one element of a non-empty `Tex` pack
+// k_rs_prep's extra argument in the culled calls
+struct RsCull {
+    const pbr_aabb* bounds;
+    pbr_cull_stats* stats;                 // may be null
+    float planes[24];                      // left, right, bottom, top, near, far: inside <=> dot(p, (x, 1)) >= 0
+};
+// the one element of a non-empty `Tex` / `Cull` pack
 template <typename T> __device__ __forceinline__ const T& only(const T& t) { return t; }
 
 struct ClipV { float x, y, z, w; };
@@ -171,25 +184,155 @@ __global__ __launch_bounds__(256) void k_rs_clear(uint32_t* __restrict__ count, 
     }
 }
 
+// the model cull of pbr_hip.h, operation for operation: true = the draw's world box lies outside one of the six planes by more than
+// the slack.  Every comparison is written so that a NaN keeps the draw.
+__device__ __forceinline__ bool draw_culled(const pbr_draw& d, const pbr_aabb& b, const float* __restrict__ planes) {
+    const float* M = d.Model;
+    bool can = M[12] == 0.0f && M[13] == 0.0f && M[14] == 0.0f && M[15] == 1.0f;
+    float c[3], e[3], cw[3], ew[3];
+    for (int i = 0; i < 3; i++) {
+        can = can && b.min[i] <= b.max[i] && fabsf(b.min[i]) <= FLT_MAX && fabsf(b.max[i]) <= FLT_MAX;
+        c[i] = (b.min[i] + b.max[i]) * 0.5f;
+        e[i] = (b.max[i] - b.min[i]) * 0.5f;
+    }
+    for (int i = 0; i < 3; i++) {
+        cw[i] = ((M[4 * i] * c[0] + M[4 * i + 1] * c[1]) + M[4 * i + 2] * c[2]) + M[4 * i + 3];
+        ew[i] = (fabsf(M[4 * i]) * e[0] + fabsf(M[4 * i + 1]) * e[1]) + fabsf(M[4 * i + 2]) * e[2];
+    }
+    bool out = false;
+    for (int k = 0; k < 6; k++) {
+        const float* p = planes + 4 * k;
+        const float dist = ((p[0] * cw[0] + p[1] * cw[1]) + p[2] * cw[2]) + p[3];
+        const float h = (fabsf(p[0] * ew[0]) + fabsf(p[1] * ew[1])) + fabsf(p[2] * ew[2]);
+        const float S = (((fabsf(p[0] * cw[0]) + fabsf(p[1] * cw[1])) + fabsf(p[2] * cw[2])) + fabsf(p[3])) + h;
+        out = out || dist < -(h + 0x1p-16f * S);
+    }
+    return can && out;
+}
+
 // draw_base[d] = first triangle id of draw d (index_count / 3 triangles each, in draw order), clamped to max_tris;
 // hdr[0] = the number of triangles rasterized (ids >= max_tris are not)
+// Cull: empty, or RsCull (a culled draw has no triangles; thread 0 writes the call's pbr_cull_stats).  The culled variant parks each
+// draw's count in draw_base[d] between the test and the two passes of the scan, so the test runs once per draw.
+template <typename... Cull>
 __global__ __launch_bounds__(1024) void k_rs_prep(const pbr_draw* __restrict__ draws, uint32_t n_draws, uint32_t max_tris,
-                                                  uint32_t* __restrict__ draw_base, uint32_t* __restrict__ hdr) {
+                                                  uint32_t* __restrict__ draw_base, uint32_t* __restrict__ hdr, Cull... cull) {
+    constexpr bool CULL = sizeof...(Cull) != 0;
     __shared__ uint64_t lds[1024];
     const uint32_t per = (n_draws + 1023u) / 1024u;
     const uint32_t b = min(threadIdx.x * per, n_draws), e = min(b + per, n_draws);
     uint64_t s = 0;
-    for (uint32_t d = b; d < e; d++) s += draws[d].index_count / 3u;
-    uint64_t total;
-    uint64_t run = block_scan_1024(s, lds, total);
-    for (uint32_t d = b; d < e; d++) {
-        draw_base[d] = (uint32_t)min(run, (uint64_t)max_tris);
-        run += draws[d].index_count / 3u;
+    if constexpr (CULL) {
+        __shared__ unsigned long long gone[2];       // culled draws, culled triangles
+        const RsCull& cl = only(cull...);
+        if (threadIdx.x == 0) { gone[0] = 0; gone[1] = 0; }
+        // the test, draw = k * 1024 + thread: neighbouring lanes read neighbouring records and share their cache lines (a thread's own
+        // range [b, e) puts the lanes of one load `per` records apart)
+        uint32_t nd = 0;
+        uint64_t nt = 0;
+        for (uint32_t d = threadIdx.x; d < n_draws; d += 1024u) {
+            uint32_t n = draws[d].index_count / 3u;
+            if (draw_culled(draws[d], cl.bounds[d], cl.planes)) {
+                nd++;
+                nt += n;
+                n = 0;
+            }
+            draw_base[d] = n;
+        }
+        __syncthreads();                                   // the parked counts are read by other threads of the block
+        for (uint32_t d = b; d < e; d++) s += draw_base[d];
+        uint64_t total;
+        uint64_t run = block_scan_1024(s, lds, total);
+        if (nd) {
+            atomicAdd(&gone[0], (unsigned long long)nd);
+            atomicAdd(&gone[1], (unsigned long long)nt);
+        }
+        for (uint32_t d = b; d < e; d++) {
+            const uint32_t n = draw_base[d];
+            draw_base[d] = (uint32_t)min(run, (uint64_t)max_tris);
+            run += n;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t n = (uint32_t)min(total, (uint64_t)max_tris);
+            draw_base[n_draws] = n;
+            hdr[0] = n;
+            if (cl.stats) {
+                pbr_cull_stats st;
+                st.draws_culled = (uint32_t)gone[0];
+                st.draws_drawn = n_draws - st.draws_culled;
+                st.triangles_drawn = n;
+                st.triangles_culled = (uint32_t)min(gone[1], 0xffffffffull);
+                *cl.stats = st;
+            }
+        }
+    } else {
+        for (uint32_t d = b; d < e; d++) s += draws[d].index_count / 3u;
+        uint64_t total;
+        uint64_t run = block_scan_1024(s, lds, total);
+        for (uint32_t d = b; d < e; d++) {
+            draw_base[d] = (uint32_t)min(run, (uint64_t)max_tris);
+            run += draws[d].index_count / 3u;
+        }
+        if (threadIdx.x == 0) {
+            const uint32_t n = (uint32_t)min(total, (uint64_t)max_tris);
+            draw_base[n_draws] = n;
+            hdr[0] = n;
+        }
     }
+}
+
+// pbr_draw_bounds: block = draw, lane = triangle (strided).  min / max run on an order-preserving integer key of the float
+// (-0 below +0; a NaN position takes no part), so the result does not depend on the order of the reduction.
+__device__ __forceinline__ uint32_t bound_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float bound_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+__global__ __launch_bounds__(256) void k_rs_bounds(const pbr_vertex* __restrict__ vtx, uint32_t n_vertices, const uint32_t* __restrict__ idx,
+                                                   uint32_t n_indices, const pbr_draw* __restrict__ draws, pbr_aabb* __restrict__ out) {
+    __shared__ uint32_t part[4][6];
+    const pbr_draw& d = draws[blockIdx.x];
+    const uint32_t first = d.first_index, count = d.index_count;
+    const int64_t base = d.base_vertex;
+    uint32_t lo[3], hi[3];
+    for (int i = 0; i < 3; i++) { lo[i] = bound_key(FLT_MAX); hi[i] = bound_key(-FLT_MAX); }
+    // the guards of k_rs_setup: a range past n_indices is skipped whole, a triangle with an index outside the vertex buffer is dropped
+    if ((uint64_t)first + count <= n_indices) {
+        for (uint32_t t = threadIdx.x; t < count / 3u; t += 256u) {
+            int64_t vi[3];
+            bool ok = true;
+            for (int k = 0; k < 3; k++) {
+                vi[k] = (int64_t)idx[(uint64_t)first + 3ull * t + k] + base;
+                ok = ok && vi[k] >= 0 && vi[k] < (int64_t)n_vertices;
+            }
+            if (!ok) continue;
+            for (int k = 0; k < 3; k++)
+                for (int i = 0; i < 3; i++) {
+                    const float v = vtx[vi[k]].position[i];
+                    if (v == v) {
+                        lo[i] = min(lo[i], bound_key(v));
+                        hi[i] = max(hi[i], bound_key(v));
+                    }
+                }
+        }
+    }
+    for (int i = 0; i < 3; i++)
+        for (uint32_t off = 32; off > 0; off >>= 1) {
+            lo[i] = min(lo[i], (uint32_t)__shfl_down((int)lo[i], off));
+            hi[i] = max(hi[i], (uint32_t)__shfl_down((int)hi[i], off));
+        }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0)
+        for (int i = 0; i < 3; i++) { part[wave][i] = lo[i]; part[wave][3 + i] = hi[i]; }
+    __syncthreads();
     if (threadIdx.x == 0) {
-        const uint32_t n = (uint32_t)min(total, (uint64_t)max_tris);
-        draw_base[n_draws] = n;
-        hdr[0] = n;
+        pbr_aabb r;
+        for (int i = 0; i < 3; i++) {
+            r.min[i] = bound_unkey(min(min(part[0][i], part[1][i]), min(part[2][i], part[3][i])));
+            r.max[i] = bound_unkey(max(max(part[0][3 + i], part[1][3 + i]), max(part[2][3 + i], part[3][3 + i])));
+        }
+        out[blockIdx.x] = r;
     }
 }
 
@@ -721,12 +864,36 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
     }
 }
 
-// the checks and launches of both entry points; tx: null for pbr_gbuffer_raster, else the validated texture table (bc1: it holds
-// a BC1-resident texture)
+// the six planes of the model cull (pbr_hip.h) in fp64 from the fp32 matrices, each rounded once
+void cull_planes(const pbr_global* g, const pbr_tile* tile, float* out) {
+    double r[4][4];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            const float* P = g->Projection + 4 * i;
+            const float* V = g->View + j;
+            r[i][j] = (((double)P[0] * (double)V[0] + (double)P[1] * (double)V[4]) + (double)P[2] * (double)V[8]) + (double)P[3] * (double)V[12];
+        }
+    const double fw = (double)tile->full_w, fh = (double)tile->full_h;
+    const double xl = 2.0 * ((double)tile->x0 - 1.0) / fw - 1.0;
+    const double xr = 2.0 * (((double)tile->x0 + (double)tile->w) + 1.0) / fw - 1.0;
+    const double yt = 1.0 - 2.0 * ((double)tile->y0 - 1.0) / fh;       // k_rs_setup's viewport: y = (1 - y_ndc) full_h / 2
+    const double yb = 1.0 - 2.0 * (((double)tile->y0 + (double)tile->h) + 1.0) / fh;
+    for (int j = 0; j < 4; j++) {
+        out[0 + j] = (float)(r[0][j] - xl * r[3][j]);
+        out[4 + j] = (float)(xr * r[3][j] - r[0][j]);
+        out[8 + j] = (float)(r[1][j] - yb * r[3][j]);
+        out[12 + j] = (float)(yt * r[3][j] - r[1][j]);
+        out[16 + j] = (float)(r[3][j] + r[2][j]);
+        out[20 + j] = (float)(r[3][j] - r[2][j]);
+    }
+}
+
+// the checks and launches of the four entry points; tx: null for pbr_gbuffer_raster, else the validated texture table (bc1: it holds
+// a BC1-resident texture); cull: null, or the culled calls' bounds and stats (the planes are filled here)
 pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_vertex* vertices, uint32_t n_vertices,
                   const uint32_t* indices, uint32_t n_indices, const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
                   uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch, void* scratch,
-                  size_t scratch_bytes, const RsRasterTex* tx, bool bc1 = false) {
+                  size_t scratch_bytes, const RsRasterTex* tx, bool bc1 = false, RsCull* cull = nullptr) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, g && tile && vertices && indices && draws && A && B && C && depth && stencil && scratch,
                 "pbr_gbuffer_raster: null pointer");
@@ -740,6 +907,10 @@ pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const
     PBR_REQUIRE(ctx, ((pbr::addr(vertices) | pbr::addr(indices) | pbr::addr(draws) | pbr::addr(A) | pbr::addr(B) | pbr::addr(C) |
                        pbr::addr(depth)) & 3u) == 0 && (pbr::addr(scratch) & 15u) == 0,
                 "pbr_gbuffer_raster: unaligned buffer");
+    if (cull) {
+        PBR_REQUIRE(ctx, cull->bounds && (pbr::addr(cull->bounds) & 3u) == 0, "pbr_gbuffer_raster_culled: bounds null or not 4-byte aligned");
+        PBR_REQUIRE(ctx, (pbr::addr(cull->stats) & 3u) == 0, "pbr_gbuffer_raster_culled: stats not 4-byte aligned");
+    }
     const Layout L = layout(tile->w, tile->h, max_triangles, tx != nullptr);
     PBR_REQUIRE(ctx, scratch_bytes >= L.pool, tx ? "pbr_gbuffer_raster_textured: scratch below pbr_gbuffer_raster_textured_min_scratch_bytes"
                                                 : "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_min_scratch_bytes");
@@ -754,7 +925,9 @@ pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const
     p.n_vertices = n_vertices; p.n_indices = n_indices; p.n_draws = n_draws;
     p.pitch = pitch;
     const size_t pool_entries = (scratch_bytes - L.pool) / 4;
-    p.pool_cap = (uint32_t)min(pool_entries, (size_t)0xfffffffeu);
+    // (not min(): on the host HIP's min(size_t, size_t) is min(int, int), which made every capacity 0xfffffffe: no list was ever
+    // refused for space, and a pool too small for the lists, the minimum scratch's empty one first of all, was written past its end)
+    p.pool_cap = pool_entries < (size_t)0xfffffffeu ? (uint32_t)pool_entries : 0xfffffffeu;
 
     char* s = static_cast<char*>(scratch);
     uint32_t* hdr = reinterpret_cast<uint32_t*>(s);
@@ -771,7 +944,12 @@ pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const
 
     hipLaunchKernelGGL(k_rs_clear, dim3(min((n_bins + 255u) / 256u, 1024u)), dim3(256), 0, ctx->stream, count, cursor, n_bins);
     if (pbr_status st = pbr::launched(ctx, "k_rs_clear")) return st;
-    hipLaunchKernelGGL(k_rs_prep, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr);
+    if (cull) {
+        cull_planes(g, tile, cull->planes);
+        hipLaunchKernelGGL(k_rs_prep<RsCull>, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr, *cull);
+    } else {
+        hipLaunchKernelGGL(k_rs_prep<>, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr);
+    }
     if (pbr_status st = pbr::launched(ctx, "k_rs_prep")) return st;
     if (tx) {
         const RsSetupTex st{tx->maps, texattrs, tx->n_tex};
@@ -834,12 +1012,14 @@ pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile*
                   pitch, scratch, scratch_bytes, nullptr);
 }
 
-pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                       const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                                       const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                                       uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                                       void* scratch, size_t scratch_bytes,
-                                       const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures) {
+namespace {
+// pbr_gbuffer_raster_textured, with or without the model cull
+pbr_status raster_textured(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                           const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                           const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                           uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                           void* scratch, size_t scratch_bytes,
+                           const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures, RsCull* cull) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, maps && (pbr::addr(maps) & 3u) == 0, "pbr_gbuffer_raster_textured: maps null or not 4-byte aligned");
     PBR_REQUIRE(ctx, n_textures <= PBR_RASTER_MAX_TEXTURES && (textures || n_textures == 0),
@@ -859,7 +1039,52 @@ pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const 
         tx.table[i] = t;
     }
     return raster(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth, stencil,
-                  pitch, scratch, scratch_bytes, &tx, any_bc1);
+                  pitch, scratch, scratch_bytes, &tx, any_bc1, cull);
+}
+}  // namespace
+
+pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                       const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                                       const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                                       uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                                       void* scratch, size_t scratch_bytes,
+                                       const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures) {
+    return raster_textured(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth,
+                           stencil, pitch, scratch, scratch_bytes, maps, textures, n_textures, nullptr);
+}
+
+pbr_status pbr_gbuffer_raster_culled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                     const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                                     const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                                     uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                                     void* scratch, size_t scratch_bytes, const pbr_aabb* bounds, pbr_cull_stats* stats) {
+    RsCull cull{bounds, stats, {}};
+    return raster(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth, stencil,
+                  pitch, scratch, scratch_bytes, nullptr, false, &cull);
+}
+
+pbr_status pbr_gbuffer_raster_textured_culled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                                              void* scratch, size_t scratch_bytes,
+                                              const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures,
+                                              const pbr_aabb* bounds, pbr_cull_stats* stats) {
+    RsCull cull{bounds, stats, {}};
+    return raster_textured(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth,
+                           stencil, pitch, scratch, scratch_bytes, maps, textures, n_textures, &cull);
+}
+
+pbr_status pbr_draw_bounds(pbr_ctx* ctx, const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                           const pbr_draw* draws, uint32_t n_draws, pbr_aabb* out) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, vertices && indices && draws && out, "pbr_draw_bounds: null pointer");
+    PBR_REQUIRE(ctx, n_vertices && n_indices && n_draws && n_draws <= PBR_RASTER_MAX_DRAWS,
+                "pbr_draw_bounds: empty vertex / index / draw list, or more draws than PBR_RASTER_MAX_DRAWS");
+    PBR_REQUIRE(ctx, ((pbr::addr(vertices) | pbr::addr(indices) | pbr::addr(draws) | pbr::addr(out)) & 3u) == 0,
+                "pbr_draw_bounds: unaligned buffer");
+    hipLaunchKernelGGL(k_rs_bounds, dim3(n_draws), dim3(256), 0, ctx->stream, vertices, n_vertices, indices, n_indices, draws, out);
+    return pbr::launched(ctx, "k_rs_bounds");
 }
 
 }  // extern "C"

@@ -30,6 +30,8 @@ SIGNATURES = {
     "pbrh_set_materials": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pbrh_set_meshes": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32]),
     "pbrh_set_textured_meshes": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _u32]),
+    "pbrh_set_model_culling": (_int, [_vp, _int]),
+    "pbrh_culling_status": (_int, [_vp, C.POINTER(_u32 * 4)]),
     "pbrh_set_initial_luminance": (_int, [_vp, C.c_float]),
     "pbrh_set_tile": (_int, [_vp] + [_u32] * 8),
     "pbrh_comm_init": (_int, [_vp, _int, _int, _vp]),
@@ -262,6 +264,18 @@ class HostRenderer:
                                                    for c, t in zip(chains, textures)])
         self._check(self.lib.pbrh_set_textured_meshes(self.h, v.ctypes.data, len(v), i.ctypes.data, len(i), d.ctypes.data, len(d),
                                                       m.ctypes.data, C.addressof(table), len(chains)))
+
+    def set_model_culling(self, on=True):
+        """pbrh_set_model_culling: GBufferPass culls the meshes' draws against the frustum on the device (the reference's
+        Scene::CullModel; bounds made on the GPU at upload).  The frame is bit-identical; default off."""
+        self._check(self.lib.pbrh_set_model_culling(self.h, 1 if on else 0))
+
+    def culling_status(self):
+        """pbrh_culling_status: (draws drawn, draws culled, triangles drawn, triangles culled) of the last frame rendered with
+        culling on — the reference's mCullingStatus; synchronises"""
+        out = (C.c_uint32 * 4)()
+        self._check(self.lib.pbrh_culling_status(self.h, C.byref(out)))
+        return tuple(int(x) for x in out)
 
     def import_texture(self, level0, fmt, mip_levels=None):
         """pbrh_import_texture: host level 0 (uint8 [h, w] for R8, [h, w, 4] otherwise; sizes multiples of 4) -> the bytes of the

@@ -132,7 +132,26 @@ void GBufferPass::UploadMeshes(FGContext* context, MeshSource& meshes, uint32 w,
                                              : pbr_gbuffer_raster_scratch_bytes(w, h, mMaxTriangles);
     if (scratch > 0xffffffffu) throw HipException("GBufferPass: raster scratch larger than 4 GiB");
     mRasterScratch = std::make_unique<DeviceStructuredBuffer>((uint32)scratch, 4);
+    mBounds.reset();
+    mCullStats.reset();
+    if (meshes.Cull) {   // the AABB the reference's mesh files carry, made from the buffers just uploaded
+        mBounds = std::make_unique<DeviceStructuredBuffer>((uint32)(meshes.Draws.size() * sizeof(pbr_aabb)), (uint32)sizeof(pbr_aabb));
+        mCullStats = std::make_unique<DeviceStructuredBuffer>((uint32)sizeof(pbr_cull_stats), (uint32)sizeof(pbr_cull_stats));
+        const pbr_cull_stats zero{0, 0, 0, 0};
+        mCullStats->Commit(&zero, sizeof(zero));
+        context->CommandList->DrawBounds((const pbr_vertex*)mVertices->DevicePtr(), (uint32)meshes.Vertices.size(),
+                                         (const uint32_t*)mIndices->DevicePtr(), (uint32)meshes.Indices.size(),
+                                         (const pbr_draw*)mDraws->DevicePtr(), (uint32)meshes.Draws.size(), (pbr_aabb*)mBounds->DevicePtr());
+    }
     meshes.Dirty = false;
+}
+
+void GBufferPass::CullingStatus(uint32_t out[4]) const {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!mCullStats) return;
+    pbr_cull_stats st;
+    ThrowIfFailed(hipMemcpy(&st, mCullStats->DevicePtr(), sizeof(st), hipMemcpyDeviceToHost), "read culling status");
+    out[0] = st.draws_drawn; out[1] = st.draws_culled; out[2] = st.triangles_drawn; out[3] = st.triangles_culled;
 }
 
 void GBufferPass::Execute(FGContext* context) {
@@ -149,7 +168,10 @@ void GBufferPass::Execute(FGContext* context) {
                                             (const pbr_draw*)mDraws->DevicePtr(), (uint32)meshes.Draws.size(), mMaxTriangles,
                                             a, b, c, ds, mRasterScratch->DevicePtr(), mRasterScratch->Size(),
                                             mMaps ? (const pbr_draw_maps*)mMaps->DevicePtr() : nullptr, mTextureTable.data(),
-                                            (uint32)mTextureTable.size());
+                                            (uint32)mTextureTable.size(),
+                                            // Scene::CullModel + mCullingStatus (:141-150), on the device
+                                            mBounds ? (const pbr_aabb*)mBounds->DevicePtr() : nullptr,
+                                            mCullStats ? (pbr_cull_stats*)mCullStats->DevicePtr() : nullptr);
         return;
     }
     GBufferSource& src = context->Scene->GBuffer();

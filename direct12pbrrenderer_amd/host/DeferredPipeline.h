@@ -68,6 +68,9 @@ public:
     explicit GBufferPass(RenderSize s);
     const char* Name() const override { return "GBuffer"; }
     void Execute(FGContext* context) override;
+    // mCullingStatus (DeferredPipeline.h:96-100) of the last Execute with model culling on, read back from the device here (the
+    // caller has drained the command list): NumDrawCall, NumCulled, triangles drawn, triangles culled; zeros without culling
+    void CullingStatus(uint32_t out[4]) const;
 protected:
     void UploadMeshes(FGContext* context, MeshSource& meshes, uint32 w, uint32 h);
     ShadingState mShadingState;
@@ -79,6 +82,8 @@ protected:
     std::vector<std::unique_ptr<DeviceStructuredBuffer>> mTextures;
     std::vector<pbr_texture2d> mTextureTable;
     uint32 mMaxTriangles = 0;
+    // model culling: the draws' local boxes (pbr_draw_bounds at upload) and the device pbr_cull_stats every Execute rewrites
+    std::unique_ptr<DeviceStructuredBuffer> mBounds, mCullStats;
 };
 
 class DeferredShadingPass : public GraphicsPass {   // :139-190

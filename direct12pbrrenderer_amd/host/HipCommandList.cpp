@@ -569,7 +569,8 @@ void HipCommandList::EncodeGBuffer(ShadingState* s, const float* m0, const float
 void HipCommandList::RasterGBuffer(ShadingState* s, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
                                    const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, DeviceTexture2D* a, DeviceTexture2D* b,
                                    DeviceTexture2D* c, DeviceTexture2D* ds, void* scratch, size_t scratch_bytes,
-                                   const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32 n_textures) {
+                                   const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32 n_textures,
+                                   const pbr_aabb* bounds, pbr_cull_stats* stats) {
     if (!s || s->File() != "gbuffer.hlsl") throw HipException("RasterGBuffer: gbuffer.hlsl shading state expected");
     if (!a || !b || !c || !ds || a->Width() != b->Width() || a->Width() != c->Width() || a->Width() != ds->Width() ||
         a->Height() != b->Height() || a->Height() != c->Height() || a->Height() != ds->Height())
@@ -578,6 +579,20 @@ void HipCommandList::RasterGBuffer(ShadingState* s, const pbr_vertex* vertices, 
     FlushPendingBloom();
     const uint32 w = a->Width(), h = a->Height();
     const pbr_tile tile = mTile.w ? mTile : pbr_tile{0, 0, w, h, w, h};
+    if (bounds) {
+        if (maps)
+            Check(pbr_gbuffer_raster_textured_culled(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws,
+                                                     max_triangles, (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(),
+                                                     (uint32_t*)c->DevicePtr(), ds->DepthPlane(), ds->StencilPlane(), w, scratch,
+                                                     scratch_bytes, maps, textures, n_textures, bounds, stats),
+                  "pbr_gbuffer_raster_textured_culled");
+        else
+            Check(pbr_gbuffer_raster_culled(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
+                                            (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(),
+                                            ds->DepthPlane(), ds->StencilPlane(), w, scratch, scratch_bytes, bounds, stats),
+                  "pbr_gbuffer_raster_culled");
+        return;
+    }
     if (maps) {
         Check(pbr_gbuffer_raster_textured(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
                                           (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(),
@@ -588,6 +603,11 @@ void HipCommandList::RasterGBuffer(ShadingState* s, const pbr_vertex* vertices, 
     Check(pbr_gbuffer_raster(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
                              (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(), ds->DepthPlane(),
                              ds->StencilPlane(), w, scratch, scratch_bytes), "pbr_gbuffer_raster");
+}
+
+void HipCommandList::DrawBounds(const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
+                                const pbr_draw* draws, uint32 n_draws, pbr_aabb* out) {
+    Check(pbr_draw_bounds(mCtx, vertices, n_vertices, indices, n_indices, draws, n_draws, out), "pbr_draw_bounds");
 }
 
 }  // namespace MRendererHip

@@ -92,7 +92,13 @@ public:
     void RasterGBuffer(ShadingState* state, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
                        const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, DeviceTexture2D* a, DeviceTexture2D* b,
                        DeviceTexture2D* c, DeviceTexture2D* depth_stencil, void* scratch, size_t scratch_bytes,
-                       const pbr_draw_maps* maps = nullptr, const pbr_texture2d* textures = nullptr, uint32 n_textures = 0);
+                       const pbr_draw_maps* maps = nullptr, const pbr_texture2d* textures = nullptr, uint32 n_textures = 0,
+                       const pbr_aabb* bounds = nullptr, pbr_cull_stats* stats = nullptr);
+    // With bounds (device, one per draw) the draws are culled on the device against the target's frustum first
+    // (pbr_gbuffer_raster_culled / _textured_culled; the planes are bit-identical) and stats (device, may be null) is written.
+    // DrawBounds: the draws' local boxes from the uploaded buffers (pbr_draw_bounds), not a per-frame dispatch.
+    void DrawBounds(const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
+                    const pbr_draw* draws, uint32 n_draws, pbr_aabb* out);
     void Present(DeviceTexture2D* tex) { mPresented = tex; }
 
     // Pass-level entry points (not in the reference): a pass whose Execute body is a fixed sequence of dispatches can

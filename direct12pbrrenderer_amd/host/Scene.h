@@ -128,6 +128,7 @@ struct MeshSource {
     std::vector<pbr_draw_maps> Maps;        // empty: constant materials only
     std::vector<TextureChain> Textures;
     bool Dirty = false;
+    bool Cull = false;                      // pbrh_set_model_culling: GBufferPass culls the draws on the device (Scene::CullModel)
     bool Empty() const { return Draws.empty(); }
     bool Textured() const { return !Maps.empty(); }
 };

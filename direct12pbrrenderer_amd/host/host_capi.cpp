@@ -501,6 +501,24 @@ int pbrh_set_textured_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_
     });
 }
 
+int pbrh_set_model_culling(pbrh_renderer* r, int on) {
+    return guarded(r, [&] {
+        MeshSource& m = r->scene->Meshes();
+        if (m.Cull != (on != 0)) {
+            m.Cull = on != 0;
+            m.Dirty = true;   // GBufferPass makes (or drops) the bounds with its next upload
+        }
+    });
+}
+
+int pbrh_culling_status(pbrh_renderer* r, uint32_t out[4]) {
+    return guarded(r, [&] {
+        if (!out) throw HipException("pbrh_culling_status: null pointer");
+        r->scheduler->CommandList()->WaitIdle();
+        r->pipeline->mGBufferPass->CullingStatus(out);
+    });
+}
+
 int pbrh_set_initial_luminance(pbrh_renderer* r, float v) {
     return guarded(r, [&] { r->pipeline->mAutoExposurePass->SetInitialLuminance(v); });
 }

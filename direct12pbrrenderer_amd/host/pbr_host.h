@@ -157,6 +157,14 @@ int pbrh_set_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices,
  * chains once after each change and rasterizes through pbr_gbuffer_raster_textured. */
 int pbrh_set_textured_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
                              const void* draws, uint32_t n_draws, const void* maps, const void* textures, uint32_t n_textures);
+/* Scene::CullModel for the meshes (default off): GBufferPass computes the draws' bounds on the GPU when it uploads the meshes
+ * (pbr_draw_bounds) and rasterizes through pbr_gbuffer_raster_culled / pbr_gbuffer_raster_textured_culled: draws outside the
+ * target's frustum are not set up; the frame is bit-identical.  Works with pbrh_set_meshes and pbrh_set_textured_meshes, before or
+ * after them. */
+int pbrh_set_model_culling(pbrh_renderer* r, int on);
+/* GBufferPass's mCullingStatus of the last frame rendered with culling on: out = {NumDrawCall, NumCulled, triangles drawn, triangles
+ * culled} (zeros with culling off).  The copy and the synchronisation happen here, not per frame. */
+int pbrh_culling_status(pbrh_renderer* r, uint32_t out[4]);
 int pbrh_set_initial_luminance(pbrh_renderer* r, float v);
 /* ---- multi-GPU: this renderer's target is the apron-extended tile at (x0, y0) of a full_w x full_h frame;
  * it OWNS the interior rectangle (ix, iy, iw, ih) of its target.  uv / camera ray / ClusterIndex use global pixels, the

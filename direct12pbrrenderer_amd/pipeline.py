@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .api import PbrContext
-from .structs import (DRAW_MAPS_DTYPE, ENV_MIPS, HISTOGRAM_BINS, MAX_VIEWS, NO_MAP, TABLES_BUILT_FRAME, TABLES_BUILT_GEOMETRY, GBuffer, Global, Tile, View)
+from .structs import (AABB_DTYPE, DRAW_MAPS_DTYPE, ENV_MIPS, HISTOGRAM_BINS, MAX_VIEWS, NO_MAP, TABLES_BUILT_FRAME, TABLES_BUILT_GEOMETRY, GBuffer, Global, Tile, View)
 
 # bloom's cumulative support is ~220 full-res pixels (3 down + 3 up levels of a radius-4 kernel on
 # a 2x pyramid); 256 also keeps every mip of the extended tile on the full frame's texel grid
@@ -363,14 +363,17 @@ class DeferredFrame:
         self.gb = {k: self.ctx.upload(v) for k, v in gb_np.items()}
         self.mesh = None   # uploaded planes replace meshes set before
 
-    def set_meshes(self, vertices, indices, draws, maps=None, textures=None):
+    def set_meshes(self, vertices, indices, draws, maps=None, textures=None, cull=False, bounds=None):
         """Geometry instead of uploaded planes: host arrays (structs.VERTEX_DTYPE, uint32 indices, structs.DRAW_DTYPE records) are
         uploaded once, and every render() rasterizes them (pbr_gbuffer_raster, draws in array order) into the frame's own G-buffer
         planes of the shaded rectangle S before the cluster, sky and shade passes (until upload_gbuffer replaces them).
         maps (structs.DRAW_MAPS_DTYPE, one per draw) and textures (the (device tensor, structs.Texture2D) pairs of
         PbrContext.upload_texture or bc1_decode, BC1-resident ones included, which the frame holds on to): the draws' texture maps, rasterized by
         pbr_gbuffer_raster_textured when any draw has one.  Without them, or with every map NO_MAP, the call is the
-        constant-material one."""
+        constant-material one.
+        cull: every render() culls the draws against the frustum of the shaded rectangle on the device (pbr_gbuffer_raster_culled /
+        pbr_gbuffer_raster_textured_culled; the G-buffer is bit-identical) and records cull_stats().  bounds: the draws' local boxes
+        (structs.AABB_DTYPE, one per draw; every vertex of a draw inside its box); without them pbr_draw_bounds makes them here, once."""
         s, ctx = self.spec, self.ctx
         draws = np.ascontiguousarray(draws)
         n_tris = int((draws["index_count"] // 3).sum())
@@ -386,6 +389,16 @@ class DeferredFrame:
                 raise ValueError("set_meshes: textures are (device tensor, Texture2D) pairs (PbrContext.upload_texture)")
             self.mesh["texture_tensors"] = [t[0] for t in pairs]   # the memory the descriptors point into
             self.mesh["textures"] = [t[1] for t in pairs]
+        if cull:
+            m = self.mesh
+            if bounds is None:
+                m["bounds"] = ctx.draw_bounds(m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"], m["n_draws"])
+            else:
+                b = np.ascontiguousarray(bounds, dtype=AABB_DTYPE)
+                if len(b) != len(draws):
+                    raise ValueError("set_meshes: one bound per draw")
+                m["bounds"] = ctx.upload(b)
+            m["cull_stats"] = ctx.alloc_cull_stats()
         self.gb = {"A": ctx.zeros((s.sh, s.sw), torch.int32), "B": ctx.zeros((s.sh, s.sw), torch.int32),
                    "C": ctx.zeros((s.sh, s.sw), torch.int32), "depth": ctx.zeros((s.sh, s.sw), torch.float32),
                    "stencil": ctx.zeros((s.sh, s.sw), torch.uint8)}
@@ -394,10 +407,22 @@ class DeferredFrame:
         m, gb = self.mesh, self.gb
         args = (self.g, self.tile, m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"], m["n_draws"],
                 m["max_triangles"], gb["A"], gb["B"], gb["C"], gb["depth"], gb["stencil"], self.spec.sw, m["scratch"])
-        if "maps" in m:
+        if "bounds" in m:
+            if "maps" in m:
+                self.ctx.gbuffer_raster_textured_culled(*args, m["maps"], m["textures"], m["bounds"], m["cull_stats"])
+            else:
+                self.ctx.gbuffer_raster_culled(*args, m["bounds"], m["cull_stats"])
+        elif "maps" in m:
             self.ctx.gbuffer_raster_textured(*args, m["maps"], m["textures"])
         else:
             self.ctx.gbuffer_raster(*args)
+
+    def cull_stats(self):
+        """structs.CullStats of the last render() of meshes set with cull=True (draws drawn / culled, triangles drawn / culled:
+        the reference's mCullingStatus); synchronises"""
+        if not self.mesh or "cull_stats" not in self.mesh:
+            raise ValueError("cull_stats: set_meshes(..., cull=True) first")
+        return self.ctx.read_cull_stats(self.mesh["cull_stats"])
 
     def set_sky_file(self, data, recompute_sh=False, resident=False):
         """The sky from the bytes of the reference's serialized sky cube (host.parse_cubemap_file): the file is uploaded as it is, its

@@ -18,7 +18,7 @@ import math
 
 import numpy as np
 
-from .structs import DRAW_DTYPE, DRAW_MAPS_DTYPE, LIGHT_DTYPE, NO_MAP, VERTEX_DTYPE, Global, ShPack
+from .structs import AABB_DTYPE, DRAW_DTYPE, DRAW_MAPS_DTYPE, LIGHT_DTYPE, NO_MAP, VERTEX_DTYPE, Global, ShPack
 
 f32 = np.float32
 PI = f32(3.14159265359)
@@ -324,6 +324,45 @@ def quad_grid(nx, ny, size=(2.0, 2.0), jitter=0.0, seed=0, normal_sign=1.0):
     return Mesh(p.reshape(-1, 3), np.broadcast_to(face, (len(p.reshape(-1, 3)), 3)), tris)
 
 
+def _bound_key(a):
+    """float32 -> an order-preserving uint32 key (-0 below +0), the order pbr_draw_bounds takes its min / max in"""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    return u ^ np.where(u >> np.uint32(31), np.uint32(0xFFFFFFFF), np.uint32(0x80000000))
+
+
+def _bound_unkey(k):
+    k = np.asarray(k, dtype=np.uint32)
+    return (k ^ np.where(k >> np.uint32(31), np.uint32(0x80000000), np.uint32(0xFFFFFFFF))).view(np.float32)
+
+
+def draw_bounds(vertices, indices, draws):
+    """The host twin of pbr_draw_bounds: structs.AABB_DTYPE records, the exact min / max over the positions of each draw's triangles
+    under the raster's guards (a range past the index buffer is skipped whole, a triangle with an index + base_vertex outside the
+    vertex buffer is dropped; a NaN position takes no part); a draw without a valid triangle gets the inverted box (+FLT_MAX,
+    -FLT_MAX), which the cull never culls."""
+    vertices, indices, draws = np.asarray(vertices), np.asarray(indices, dtype=np.uint32), np.asarray(draws)
+    out = np.zeros(len(draws), dtype=AABB_DTYPE)
+    fmax = np.finfo(np.float32).max
+    out["min"], out["max"] = fmax, -fmax
+    pos = np.ascontiguousarray(vertices["position"], dtype=np.float32).reshape(-1, 3)
+    for k, d in enumerate(draws):
+        first, count, base = int(d["first_index"]), int(d["index_count"]), int(d["base_vertex"])
+        if count < 3 or first + count > len(indices):
+            continue
+        vi = indices[first:first + 3 * (count // 3)].astype(np.int64).reshape(-1, 3) + base
+        vi = vi[((vi >= 0) & (vi < len(pos))).all(axis=1)].reshape(-1)
+        if not len(vi):
+            continue
+        p = pos[vi]
+        key = _bound_key(p)
+        ok = ~np.isnan(p)
+        lo = np.where(ok, key, _bound_key(np.float32(fmax))).min(axis=0)
+        hi = np.where(ok, key, _bound_key(np.float32(-fmax))).max(axis=0)
+        out[k]["min"] = _bound_unkey(np.minimum(lo, _bound_key(np.float32(fmax))))
+        out[k]["max"] = _bound_unkey(np.maximum(hi, _bound_key(np.float32(-fmax))))
+    return out
+
+
 class MeshScene:
     """Draws over shared buffers: add(mesh, model, albedo, emission, roughness, metallic) appends a mesh (or draws one added
     before again: instance=index) and one pbr_draw; arrays() -> (vertices, indices, draws), the input of pbr_gbuffer_raster."""
@@ -361,6 +400,11 @@ class MeshScene:
         return (np.concatenate(self._verts) if self._verts else np.zeros(0, VERTEX_DTYPE),
                 np.concatenate(self._idx).astype(np.uint32) if self._idx else np.zeros(0, np.uint32),
                 np.array(self._draws, dtype=DRAW_DTYPE))
+
+    def bounds(self):
+        """the draws' local boxes (structs.AABB_DTYPE), parallel to arrays()[2]: draw_bounds of arrays(), the host twin of
+        pbr_draw_bounds"""
+        return draw_bounds(*self.arrays())
 
     def maps(self):
         """the draws' pbr_draw_maps records (structs.DRAW_MAPS_DTYPE), parallel to arrays()[2]"""

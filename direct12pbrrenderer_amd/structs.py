@@ -132,6 +132,21 @@ DRAW_DTYPE = np.dtype([("Model", np.float32, 16), ("InvModel", np.float32, 16), 
                        ("Roughness", np.float32), ("Metallic", np.float32), ("first_index", np.uint32), ("index_count", np.uint32),
                        ("base_vertex", np.int32)])
 assert VERTEX_DTYPE.itemsize == 56 and DRAW_DTYPE.itemsize == 164
+# pbr_aabb: a draw's bound in its local (vertex) space, one per draw (an array parallel to the draws)
+AABB_DTYPE = np.dtype([("min", np.float32, 3), ("max", np.float32, 3)])
+assert AABB_DTYPE.itemsize == 24
+
+
+class CullStats(C.Structure):
+    """pbr_cull_stats: the reference's mCullingStatus (NumDrawCall, NumCulled) and the triangles either way (16 B)."""
+    _fields_ = [("draws_drawn", C.c_uint32), ("draws_culled", C.c_uint32), ("triangles_drawn", C.c_uint32),
+                ("triangles_culled", C.c_uint32)]
+
+    def astuple(self):
+        return (self.draws_drawn, self.draws_culled, self.triangles_drawn, self.triangles_culled)
+
+
+assert C.sizeof(CullStats) == 16
 RASTER_MAX_DRAWS = 65536                              # PBR_RASTER_MAX_DRAWS
 RASTER_MAX_TRIANGLES = 1 << 22                        # PBR_RASTER_MAX_TRIANGLES
 RASTER_MAX_SIZE = 8192                                # PBR_RASTER_MAX_SIZE

@@ -702,6 +702,61 @@ pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const 
                                        void* scratch, size_t scratch_bytes,
                                        const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures);
 
+/* ---- Model culling (new): Scene::CullModel + GBufferPass's mCullingStatus (DeferredPipeline.cpp:138-153) on the device ---------- */
+/* A draw's bound in its local (vertex) space, 24 B; one per draw, parallel to the pbr_draw array. */
+typedef struct pbr_aabb {
+    float min[3], max[3];
+} pbr_aabb;
+/* mCullingStatus: draws_drawn = NumDrawCall, draws_culled = NumCulled; triangles_drawn = the triangles the call rasterizes (at most
+ * max_triangles), triangles_culled = the sum of index_count / 3 over the culled draws (saturating at 2^32 - 1). */
+typedef struct pbr_cull_stats {
+    uint32_t draws_drawn, draws_culled, triangles_drawn, triangles_culled;
+} pbr_cull_stats;
+/* The bounds of each draw from the buffers the raster takes (the counterpart of the AABB the reference's mesh files carry):
+ * out[d] = the exact min / max over the positions of the triangles of draw d, under the device-data guards of pbr_gbuffer_raster (a
+ * range past n_indices is skipped whole; a triangle with an index + base_vertex outside [0, n_vertices) is dropped).  A draw with no
+ * valid triangle gets the inverted box (min = +FLT_MAX, max = -FLT_MAX), which is never culled.  min / max are exact, so the result
+ * is a function of the data alone.  vertices / indices / draws / out: DEVICE, 4-byte aligned.  One asynchronous launch on the
+ * context's stream (one block per draw), no allocation.  Refusals (PBR_ERR_INVALID, nothing enqueued): a null or misaligned
+ * pointer, a zero count, n_draws > PBR_RASTER_MAX_DRAWS. */
+pbr_status pbr_draw_bounds(pbr_ctx* ctx, const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                           const pbr_draw* draws, uint32_t n_draws, pbr_aabb* out);
+/* pbr_gbuffer_raster / pbr_gbuffer_raster_textured with the model cull: the same arguments and contract, plus bounds (DEVICE, one
+ * pbr_aabb per draw) and stats (DEVICE, may be NULL; written by the call's second launch).  A culled draw contributes no triangle:
+ * it is neither set up nor binned.  max_triangles keeps its meaning (the sum over ALL draws); scratch sizes do not change.
+ * The rule, pinned (tests/raster_cull_ref.py restates it; DESIGN.md derives it), fp32 unless stated, no contraction:
+ *   World box of draw d (the box of all eight corners, centre / extent form; M = draws[d].Model):
+ *     c = (min + max) * 0.5, e = (max - min) * 0.5
+ *     cw_i = ((M[4i] c.x + M[4i+1] c.y) + M[4i+2] c.z) + M[4i+3],  ew_i = (|M[4i]| e.x + |M[4i+1]| e.y) + |M[4i+2]| e.z   (i = 0, 1, 2)
+ *   Planes: six, in world space, formed on the host in fp64 from the fp32 g->Projection and g->View and rounded once to fp32.
+ *     PV = Projection . View, each element ((p0 v0 + p1 v1) + p2 v2) + p3 v3, rows r0 .. r3.  The side planes are those of the TILE
+ *     widened by one pixel on every side: xl = 2 (x0 - 1) / full_w - 1, xr = 2 (x0 + w + 1) / full_w - 1, yt = 1 - 2 (y0 - 1) / full_h,
+ *     yb = 1 - 2 (y0 + h + 1) / full_h.  left r0 - xl r3, right xr r3 - r0, bottom r1 - yb r3, top yt r3 - r1, near r3 + r2 (the
+ *     reference's, MathLib.h:1037; wider than the rasterizer's z >= 0), far r3 - r2.
+ *   Test (FrustumVolume::Contains(AABB), MathLib.h:1057-1080, plus a slack), per plane p:
+ *     d = ((p.x cw.x + p.y cw.y) + p.z cw.z) + p.w,  h = (|p.x ew.x| + |p.y ew.y|) + |p.z ew.z|,
+ *     S = (((|p.x cw.x| + |p.y cw.y|) + |p.z cw.z|) + |p.w|) + h
+ *     the draw is culled if and only if d < -(h + 2^-16 S) for some plane; a NaN anywhere keeps the draw.
+ *   Never culled: a draw whose box is inverted (min > max on an axis) or not finite, or whose Model's last row is not exactly (0, 0, 0, 1).
+ * Deviation from the reference: its AABB operator* (MathLib.cpp:5-10) transforms Min and Max only, which under-covers a rotated
+ * model, and it culls against the whole frame's frustum.  Neither is copied.
+ * THE INVARIANT: provided every vertex of every triangle of draw d lies in bounds[d] (pbr_draw_bounds gives such bounds), the five
+ * planes are bit-identical to the same call without bounds, for every camera, tile, scratch size and texture format.
+ * Refusals (PBR_ERR_INVALID, nothing enqueued): those of the call without bounds; bounds null or not 4-byte aligned; stats non-null
+ * and not 4-byte aligned.  Asynchronous: the same six launches, no host synchronisation, no allocation. */
+pbr_status pbr_gbuffer_raster_culled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                     const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                                     const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                                     uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                                     void* scratch, size_t scratch_bytes, const pbr_aabb* bounds, pbr_cull_stats* stats);
+pbr_status pbr_gbuffer_raster_textured_culled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
+                                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
+                                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
+                                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
+                                              void* scratch, size_t scratch_bytes,
+                                              const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures,
+                                              const pbr_aabb* bounds, pbr_cull_stats* stats);
+
 /* bloom_prefilter.hlsl:17-60 (DeferredPipeline.cpp:411-427): hdr (w x h) -> out (w>>1 x h>>1). */
 pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h,
                                uint32_t pitch, pbr_half* out, float threshold, float knee);

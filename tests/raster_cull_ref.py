@@ -1,0 +1,171 @@
+"""The model cull of pbr_gbuffer_raster_culled (include/pbr_hip.h, DESIGN.md "Model culling") restated in numpy: the six planes in
+float64 rounded once to float32, the world box and the test in float32 in the pinned operation order — and the same geometry in
+float64 (the exact planes, the eight corners), which the fp32 rule is held to in test_raster_cull_cpu.py.
+
+The switches (widen, two_corner, flip, frame_planes) restate the defects the tests inject; the defaults are the rule."""
+import numpy as np
+
+f32 = np.float32
+SLACK = f32(2.0 ** -16)
+PLANES = ("left", "right", "bottom", "top", "near", "far")
+INVERTED = (np.full(3, np.finfo(f32).max, f32), np.full(3, -np.finfo(f32).max, f32))
+
+
+def _pv64(projection, view):
+    """Projection . View in float64 from the fp32 matrices, each element ((p0 v0 + p1 v1) + p2 v2) + p3 v3"""
+    P = np.asarray(projection, f32).reshape(4, 4).astype(np.float64)
+    V = np.asarray(view, f32).reshape(4, 4).astype(np.float64)
+    pv = np.zeros((4, 4))
+    for i in range(4):
+        for j in range(4):
+            pv[i, j] = ((P[i, 0] * V[0, j] + P[i, 1] * V[1, j]) + P[i, 2] * V[2, j]) + P[i, 3] * V[3, j]
+    return pv
+
+
+def planes64(projection, view, tile, widen=1.0, frame_planes=False):
+    """[6, 4] float64, left right bottom top near far, inside <=> dot(p, (x, 1)) >= 0; tile = (x0, y0, w, h, full_w, full_h).
+    The side planes are the tile's, widened by `widen` pixels (frame_planes: the whole frame's instead)."""
+    x0, y0, w, h, fw, fh = (float(v) for v in tile)
+    if frame_planes:
+        x0, y0, w, h = 0.0, 0.0, fw, fh
+    r = _pv64(projection, view)
+    xl = 2.0 * (x0 - widen) / fw - 1.0
+    xr = 2.0 * (x0 + w + widen) / fw - 1.0
+    yt = 1.0 - 2.0 * (y0 - widen) / fh          # screen y grows downwards: y = (1 - y_ndc) full_h / 2
+    yb = 1.0 - 2.0 * (y0 + h + widen) / fh
+    return np.stack([r[0] - xl * r[3], xr * r[3] - r[0], r[1] - yb * r[3], yt * r[3] - r[1], r[3] + r[2], r[3] - r[2]])
+
+
+def planes32(projection, view, tile, **kw):
+    return planes64(projection, view, tile, **kw).astype(f32)
+
+
+def tile_tuple(tile):
+    """a structs.Tile or a 6-tuple -> the tuple"""
+    return tuple(tile) if isinstance(tile, (tuple, list)) else (tile.x0, tile.y0, tile.w, tile.h, tile.full_w, tile.full_h)
+
+
+def two_corner_box(model, bmin, bmax):
+    """(min, max) [n, 3] float32 of the reference's AABB operator* (MathLib.cpp:5-10): Model min and Model max, sorted per axis"""
+    M = np.asarray(model, f32).reshape(-1, 4, 4)
+    lo, hi = np.asarray(bmin, f32).reshape(-1, 3), np.asarray(bmax, f32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        a = ((M[:, :3, 0] * lo[:, 0:1] + M[:, :3, 1] * lo[:, 1:2]) + M[:, :3, 2] * lo[:, 2:3]) + M[:, :3, 3]
+        b = ((M[:, :3, 0] * hi[:, 0:1] + M[:, :3, 1] * hi[:, 1:2]) + M[:, :3, 2] * hi[:, 2:3]) + M[:, :3, 3]
+    return np.minimum(a, b).astype(f32), np.maximum(a, b).astype(f32)
+
+
+def world_box(model, bmin, bmax, two_corner=False):
+    """(cw, ew) [n, 3] float32 of draws with Model [n, 16] and local boxes bmin / bmax [n, 3]; two_corner: the box of Model min and
+    Model max alone (the reference's AABB operator*), the defect"""
+    M = np.asarray(model, f32).reshape(-1, 4, 4)
+    lo, hi = np.asarray(bmin, f32).reshape(-1, 3), np.asarray(bmax, f32).reshape(-1, 3)
+    half = f32(0.5)
+    with np.errstate(all="ignore"):
+        if two_corner:
+            wlo, whi = two_corner_box(model, bmin, bmax)
+            return (wlo + whi) * half, (whi - wlo) * half
+        c, e = (lo + hi) * half, (hi - lo) * half
+        cw = ((M[:, :3, 0] * c[:, 0:1] + M[:, :3, 1] * c[:, 1:2]) + M[:, :3, 2] * c[:, 2:3]) + M[:, :3, 3]
+        A = np.abs(M[:, :3, :3])
+        ew = (A[:, :, 0] * e[:, 0:1] + A[:, :, 1] * e[:, 1:2]) + A[:, :, 2] * e[:, 2:3]
+    return cw.astype(f32), ew.astype(f32)
+
+
+def cullable(model, bmin, bmax):
+    """[n] bool: the draws the rule may cull at all — a finite, non-inverted box and an affine Model (last row exactly 0 0 0 1)"""
+    M = np.asarray(model, f32).reshape(-1, 16)
+    lo, hi = np.asarray(bmin, f32).reshape(-1, 3), np.asarray(bmax, f32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        box = (np.isfinite(lo) & np.isfinite(hi) & (lo <= hi)).all(axis=1)
+    return box & (M[:, 12] == 0) & (M[:, 13] == 0) & (M[:, 14] == 0) & (M[:, 15] == 1)
+
+
+def plane_terms(planes, cw, ew):
+    """(d, h, S) [n, 6] float32 in the pinned order"""
+    p = np.asarray(planes, f32).reshape(1, 6, 4)
+    cw, ew = cw[:, None, :], ew[:, None, :]
+    with np.errstate(all="ignore"):
+        d = ((p[..., 0] * cw[..., 0] + p[..., 1] * cw[..., 1]) + p[..., 2] * cw[..., 2]) + p[..., 3]
+        h = (np.abs(p[..., 0] * ew[..., 0]) + np.abs(p[..., 1] * ew[..., 1])) + np.abs(p[..., 2] * ew[..., 2])
+        S = (((np.abs(p[..., 0] * cw[..., 0]) + np.abs(p[..., 1] * cw[..., 1])) + np.abs(p[..., 2] * cw[..., 2])) + np.abs(p[..., 3])) + h
+    return d.astype(f32), h.astype(f32), S.astype(f32)
+
+
+def culled_by(planes, model, bmin, bmax, two_corner=False, slack=SLACK):
+    """[n, 6] bool: plane k culls draw i (d < -(h + slack S); a NaN keeps the draw), and S [n, 6]"""
+    cw, ew = world_box(model, bmin, bmax, two_corner=two_corner)
+    d, h, S = plane_terms(planes, cw, ew)
+    with np.errstate(all="ignore"):
+        out = d < -(h + f32(slack) * S)
+    return out & cullable(model, bmin, bmax)[:, None], S
+
+
+def cull(projection, view, tile, draws, bounds, widen=1.0, two_corner=False, flip=None, frame_planes=False):
+    """[n] bool, the culled draws of structs.DRAW_DTYPE records `draws` with structs.AABB_DTYPE records `bounds`.
+    flip: the index of a plane whose sign is flipped (a defect)."""
+    p = planes32(projection, view, tile_tuple(tile), widen=widen, frame_planes=frame_planes)
+    if flip is not None:
+        p[flip] = -p[flip]
+    by, _ = culled_by(p, draws["Model"], bounds["min"], bounds["max"], two_corner=two_corner)
+    return by.any(axis=1)
+
+
+def stats(draws, culled):
+    """pbr_cull_stats of a call whose max_triangles is the sum over all draws: (draws_drawn, draws_culled, triangles_drawn,
+    triangles_culled)"""
+    tris = (np.asarray(draws["index_count"]).astype(np.int64) // 3)
+    culled = np.asarray(culled, bool)
+    return (int((~culled).sum()), int(culled.sum()), int(tris[~culled].sum()), int(tris[culled].sum()))
+
+
+def remove_culled(draws, culled):
+    return np.ascontiguousarray(draws[~np.asarray(culled, bool)])
+
+
+# ---- the same geometry in float64
+def corners64(model, bmin, bmax):
+    """[n, 8, 3]: Model applied to the eight corners of each box, float64"""
+    M = np.asarray(model, f32).reshape(-1, 4, 4).astype(np.float64)
+    lo, hi = np.asarray(bmin, f32).reshape(-1, 3).astype(np.float64), np.asarray(bmax, f32).reshape(-1, 3).astype(np.float64)
+    pick = np.array([[(k >> a) & 1 for a in range(3)] for k in range(8)], dtype=bool)          # [8, 3]
+    loc = np.where(pick[None], hi[:, None, :], lo[:, None, :])                                     # [n, 8, 3]
+    return np.einsum("nij,nkj->nki", M[:, :3, :3], loc) + M[:, None, :3, 3]
+
+
+def distances64(planes_f64, corners):
+    """[n, 8, 6]: signed plane values dot(p, (corner, 1)) in float64"""
+    p = np.asarray(planes_f64, np.float64)
+    return np.einsum("nki,pi->nkp", corners, p[:, :3]) + p[None, None, :, 3]
+
+
+# ---- the reference's own cull (Scene::CullModel): FrustumVolume::FromMatrix(Projection View) . Contains(Model * AABB), fp32, with
+# the two-corner box of MathLib.cpp:5-10 and the whole frame's frustum — restated as tests/light_cull_ref.py restates the lights'
+def reference_culled(projection, view, draws, bounds):
+    import light_cull_ref as lc
+    vp = lc.matmul44(np.asarray(projection, f32).reshape(4, 4), np.asarray(view, f32).reshape(4, 4))
+    planes = lc.frustum_planes(vp)
+    wlo, whi = two_corner_box(draws["Model"], bounds["min"], bounds["max"])
+    out = np.zeros(len(draws), bool)
+    for i in range(len(draws)):
+        out[i] = not lc.frustum_contains(planes, wlo[i], whi[i])
+    return out
+
+
+# ---- host twin of pbr_draw_bounds, the brute-force form (scene.MeshScene.bounds is the vectorised one)
+def draw_bounds_loop(vertices, indices, draws):
+    from direct12pbrrenderer_amd.structs import AABB_DTYPE
+    out = np.zeros(len(draws), AABB_DTYPE)
+    nv, ni = len(vertices), len(indices)
+    for k, d in enumerate(draws):
+        lo, hi = INVERTED[0].copy(), INVERTED[1].copy()
+        first, count, base = int(d["first_index"]), int(d["index_count"]), int(d["base_vertex"])
+        if first + count <= ni:
+            for t in range(count // 3):
+                vi = [int(indices[first + 3 * t + j]) + base for j in range(3)]
+                if all(0 <= v < nv for v in vi):
+                    for v in vi:
+                        lo = np.minimum(lo, vertices["position"][v])
+                        hi = np.maximum(hi, vertices["position"][v])
+        out[k]["min"], out[k]["max"] = lo, hi
+    return out

@@ -1,0 +1,393 @@
+"""Model culling on the GPU: pbr_draw_bounds against scene.draw_bounds bit for bit; pbr_gbuffer_raster_culled and
+pbr_gbuffer_raster_textured_culled against the unculled calls bit for bit, with pbr_cull_stats equal to the counts of the numpy rule
+(tests/raster_cull_ref.py); bounds that never cull, stats == null, the refusals, DeferredFrame.set_meshes(cull=True) and the host
+graph's GBufferPass."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import camera_cases
+import common
+import raster_cull_ref as rc
+from direct12pbrrenderer_amd import scene
+from direct12pbrrenderer_amd.api import PbrError
+from direct12pbrrenderer_amd.structs import AABB_DTYPE, NO_MAP, TEX_R8G8B8A8_UNORM, TEX_R8_UNORM, Tile
+from test_gpu_raster import PLANES, same
+from test_raster_cull_cpu import unproject
+
+GUARD_ROWS = 3
+POISON = 0x5A
+
+
+# ---- pbr_draw_bounds
+def gpu_bounds(ctx, v, i, d):
+    out = ctx.draw_bounds(ctx.upload(v), len(v), ctx.upload(i), len(i), ctx.upload(d), len(d))
+    ctx.sync()
+    return out.cpu().numpy().reshape(-1).view(AABB_DTYPE)
+
+
+def bounds_scene(n_draws):
+    """n_draws draws over three meshes (a sphere, a jittered grid, a larger sphere of more than 256 triangles) with base_vertex
+    offsets; vertex 3 holds -0"""
+    ms = scene.MeshScene()
+    ks = [ms.add_mesh(scene.uv_sphere(5, 7, radius=1.5)), ms.add_mesh(scene.quad_grid(4, 3, size=(3.0, 2.0), jitter=0.2, seed=3)),
+          ms.add_mesh(scene.uv_sphere(14, 16, radius=0.7))]
+    for k in range(n_draws):
+        ms.add(ks[k % 3], scene.model_matrix((k % 7, 0, 0), (0, 0, 0), (1, 1, 1)))
+    v, i, d = ms.arrays()
+    v["position"][3] = (0.0, -0.0, 0.0)
+    return v, i, d
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_draws", [1, 3, 1025])
+def test_draw_bounds_bit_for_bit(ctx, n_draws):
+    v, i, d = bounds_scene(n_draws)
+    assert n_draws < 3 or (d["base_vertex"][:3] != d["base_vertex"][0]).any()
+    got, want = gpu_bounds(ctx, v, i, d), scene.draw_bounds(v, i, d)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert (want["min"] <= want["max"]).all() and (want["min"] < want["max"]).any(axis=1).all()
+
+
+@pytest.mark.gpu
+def test_draw_bounds_guards(ctx):
+    """a range past n_indices, an out-of-range index (its triangle alone is dropped), index_count < 3"""
+    v, i, d = bounds_scene(3)
+    d = np.concatenate([d, d])
+    d[3]["first_index"], d[3]["index_count"] = len(i) - 3, 6           # passes n_indices: skipped whole
+    d[4]["base_vertex"] = d[4]["base_vertex"] - 2                       # the triangles naming the mesh's first vertices leave the buffer ...
+    i = i.copy()
+    i[int(d[5]["first_index"]) + 4] = 0x7FFFFFF0                        # ... and one index of draw 5's second triangle is far out of range
+    d[2]["index_count"] = 2                                             # no triangle
+    got, want = gpu_bounds(ctx, v, i, d), scene.draw_bounds(v, i, d)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    for k in (2, 3):
+        assert (got[k]["min"] == rc.INVERTED[0]).all() and (got[k]["max"] == rc.INVERTED[1]).all()
+    assert (got[5]["min"] <= got[5]["max"]).all() and (got[1]["min"] <= got[1]["max"]).all()
+
+
+# ---- the culled calls against the unculled ones
+class Buffers:
+    """a scene on the device, and both calls into guarded planes"""
+
+    def __init__(self, ctx, v, i, d, b, maps=None, textures=None):
+        self.ctx, self.d, self.b = ctx, d, b
+        self.n = int((d["index_count"] // 3).sum())
+        self.dev = (ctx.upload(v), len(v), ctx.upload(i), len(i), ctx.upload(d), len(d), self.n)
+        self.db = ctx.upload(b)
+        self.maps = None if maps is None else ctx.upload(maps)
+        self.textures = textures
+
+    def run(self, g, tile, culled, minimum=False, pitch=None, stats=True):
+        """(planes of the tile, stats tuple or None); the rows around the tile and the columns past its width must stay untouched"""
+        ctx = self.ctx
+        pitch = pitch or tile.w
+        rows = tile.h + 2 * GUARD_ROWS
+        kinds = (torch.int32, torch.int32, torch.int32, torch.float32, torch.uint8)
+        bufs = [ctx.empty((rows, pitch), k) for k in kinds]
+        for t in bufs:
+            t.view(torch.uint8).fill_(POISON)
+        ptrs = [t.data_ptr() + GUARD_ROWS * pitch * t.element_size() for t in bufs]
+        textured = self.maps is not None
+        scratch = (ctx.alloc_textured_raster_scratch if textured else ctx.alloc_raster_scratch)(tile.w, tile.h, self.n, minimum=minimum)
+        st = ctx.alloc_cull_stats() if (culled and stats) else None
+        tail = ((self.maps, self.textures) if textured else ()) + ((self.db, st) if culled else ())
+        fn = {(False, False): ctx.gbuffer_raster, (False, True): ctx.gbuffer_raster_culled,
+              (True, False): ctx.gbuffer_raster_textured, (True, True): ctx.gbuffer_raster_textured_culled}[(textured, culled)]
+        fn(g, tile, *self.dev, *ptrs, pitch, scratch, *tail)
+        ctx.sync()
+        out = {}
+        for name, t in zip(PLANES, bufs):
+            a = t.cpu().numpy()
+            raw = a.view(np.uint8).reshape(rows, -1)
+            assert (raw[:GUARD_ROWS] == POISON).all() and (raw[-GUARD_ROWS:] == POISON).all(), name
+            assert (a[GUARD_ROWS:-GUARD_ROWS, tile.w:].view(np.uint8) == POISON).all(), name
+            out[name] = np.ascontiguousarray(a[GUARD_ROWS:-GUARD_ROWS, :tile.w])
+        return out, (ctx.read_cull_stats(st).astuple() if st is not None else None)
+
+    def check(self, g, tile, **kw):
+        """both calls: the same planes, and the stats the rule gives; returns (planes, culled mask)"""
+        plain, _ = self.run(g, tile, False, **kw)
+        culled, st = self.run(g, tile, True, **kw)
+        same(plain, culled)
+        mask = rc.cull(g.Projection[:], g.View[:], tile, self.d, self.b)
+        assert st == rc.stats(self.d, mask), (st, rc.stats(self.d, mask))
+        return culled, mask
+
+
+def eye_of(g):
+    return np.array(g.InvView[:], np.float64).reshape(4, 4)[:3, 3]
+
+
+def sphere_at(g, ndc_xy, depth=0.97, size=0.06):
+    """a Model that puts a unit mesh at the ndc point, scaled with its distance from the eye"""
+    p = unproject(g, np.array([[ndc_xy[0], ndc_xy[1], depth]]))[0]
+    s = size * np.linalg.norm(p - eye_of(g))
+    return scene.model_matrix(p, (20, 30 + 100 * ndc_xy[0], 40), (s, 1.3 * s, 0.8 * s))
+
+
+INSIDE = [(x, y) for y in (-0.7, 0.0, 0.7) for x in (-0.8, -0.3, 0.3, 0.8)]
+OUTSIDE = [(-2.5, 0.2), (2.6, -0.3), (0.1, 2.4), (-0.2, -2.7), (3.0, 3.0)]
+
+
+def cull_scene(kind, g):
+    """all / none / first_last / alt-N: draws of one small sphere inside the frame and outside it (to the sides, behind the camera)"""
+    ms = scene.MeshScene()
+    small = kind.startswith("alt")
+    k = ms.add_mesh(scene.uv_sphere(3, 4) if small else scene.uv_sphere(6, 8))
+    if kind == "all":
+        where = INSIDE
+    elif kind == "none":
+        where = OUTSIDE
+    elif kind == "first_last":
+        where = OUTSIDE[:1] + INSIDE + OUTSIDE[1:2]
+    else:
+        n = int(kind.split("-")[1])
+        where = [OUTSIDE[j % len(OUTSIDE)] if j % 2 == 0 else (-0.9 + 1.8 * ((j // 2) % 32) / 31, -0.85 + 1.7 * ((j // 64) % 17) / 16)
+                 for j in range(n)]
+    for j, xy in enumerate(where):
+        ms.add(k, sphere_at(g, xy, size=0.03 if small else 0.06), albedo=(0.3 + 0.02 * (j % 30), 0.5, 0.6), roughness=(j % 10) / 10,
+               metallic=(j % 7) / 7)
+    if kind == "none":      # and one behind the camera
+        ahead = unproject(g, np.array([[0.0, 0.0, 0.9]]))[0] - eye_of(g)
+        ms.add(k, scene.model_matrix(eye_of(g) - 4 * ahead / np.linalg.norm(ahead), (0, 0, 0), (1, 1, 1)))
+    v, i, d = ms.arrays()
+    return v, i, d, ms.bounds()
+
+
+FRAMES = [(70, 45, [(0, 0, 70, 45)]), (256, 144, [(0, 0, 256, 144)]),
+          (256, 192, [(0, 0, 128, 96), (128, 0, 128, 96), (0, 96, 128, 96), (128, 96, 128, 96)])]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("camera", camera_cases.NAMES)
+@pytest.mark.parametrize("kind", ["all", "none", "first_last", "alt-1025", "alt-2049"])
+def test_culled_call_matches_unculled(ctx, kind, camera):
+    """whole frames of 70 x 45 and 256 x 144 and the four 128 x 96 tiles of a 256 x 192 frame (pitch > w, guard rows), minimum and
+    recommended scratch: the five planes bit for bit, the stats the rule's"""
+    for fw, fh, tiles in FRAMES:
+        g = camera_cases.make_global(camera, fw, fh)[1]
+        v, i, d, b = cull_scene(kind, g)
+        bufs = Buffers(ctx, v, i, d, b)
+        for (x0, y0, tw, th) in tiles:
+            tile = Tile(x0, y0, tw, th, fw, fh)
+            whole = (tw, th) == (fw, fh)
+            for minimum in (True, False):
+                planes, mask = bufs.check(g, tile, minimum=minimum, pitch=tw if whole else tw + 5)
+            if not whole:
+                assert mask.any()
+                continue
+            if kind == "all":
+                assert not mask.any() and (planes["stencil"] > 0).any()
+            elif kind == "none":
+                assert mask.all()
+                assert not planes["stencil"].any() and (planes["depth"] == 1.0).all() and not planes["A"].any() \
+                    and not planes["B"].any() and not planes["C"].any()
+            elif kind == "first_last":
+                assert mask[0] and mask[-1] and not mask[1:-1].any() and (planes["stencil"] > 0).any()
+            else:
+                assert mask[0::2].all() and not mask[1::2].any() and (planes["stencil"] > 0).any()
+
+
+def textured_cull_scene(ctx, g, bc1):
+    v, i, d, b = cull_scene("first_last", g)
+    rng = np.random.default_rng(3)
+    t = rng.normal(size=(len(v), 3))
+    v["tangent"] = (t / np.linalg.norm(t, axis=1, keepdims=True)).astype(np.float32)
+    v["uv"] = rng.uniform(-3, 3, (len(v), 2)).astype(np.float32)
+    pairs = [ctx.import_texture(rng.integers(0, 256, (16, 16, 4), dtype=np.uint8), TEX_R8G8B8A8_UNORM, bc1=bc1),
+             ctx.import_texture(rng.integers(0, 256, (8, 16), dtype=np.uint8), TEX_R8_UNORM, bc1=bc1)]
+    maps = np.full(len(d), NO_MAP, dtype=scene.DRAW_MAPS_DTYPE)
+    maps["albedo"][::2] = 0
+    maps["roughness"][1::3] = 1
+    maps["ao"][0] = 99              # culled, and it carries a map index past the table: dropped either way
+    maps["metallic"][3] = 77        # kept by the cull, dropped by the guard in both calls
+    return v, i, d, b, maps, pairs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bc1", [False, True], ids=["decoded", "bc1"])
+def test_textured_culled_call_matches_unculled(ctx, bc1):
+    fw, fh = 256, 144
+    g = camera_cases.make_global("pitch_roll", fw, fh)[1]
+    v, i, d, b, maps, pairs = textured_cull_scene(ctx, g, bc1)
+    bufs = Buffers(ctx, v, i, d, b, maps=maps, textures=[p[1] for p in pairs])
+    for rect, pitch in (((0, 0, fw, fh), fw), ((64, 32, 128, 96), 133)):
+        for minimum in (True, False):
+            planes, mask = bufs.check(g, Tile(*rect, fw, fh), minimum=minimum, pitch=pitch)
+        assert mask[0] and not mask[3] and (planes["stencil"] > 0).any()
+    # the maps are sampled: the same scene through the constant-material call gives other planes
+    plain = Buffers(ctx, v, i, d, b).run(g, Tile(0, 0, fw, fh, fw, fh), True)[0]
+    assert not np.array_equal(plain["A"], bufs.run(g, Tile(0, 0, fw, fh, fw, fh), True)[0]["A"])
+    del pairs
+
+
+@pytest.mark.gpu
+def test_bounds_that_never_cull(ctx):
+    """inverted and NaN boxes and a projective Model never cull, wherever the draw is"""
+    fw, fh = 256, 144
+    g = camera_cases.make_global("default", fw, fh)[1]
+    v, i, d, b = cull_scene("none", g)
+    tile = Tile(0, 0, fw, fh, fw, fh)
+    assert rc.cull(g.Projection[:], g.View[:], tile, d, b).all()
+    b[0]["min"], b[0]["max"] = rc.INVERTED
+    b[1]["min"][1] = np.nan
+    b[2]["max"][2] = np.inf
+    d["Model"][3][12] = 1e-6
+    d["Model"][4][15] = 1.0000001
+    bufs = Buffers(ctx, v, i, d, b)
+    planes, mask = bufs.check(g, tile)
+    assert not mask[:5].any() and mask[5:].all()
+    _, st = bufs.run(g, tile, True)
+    assert st[1] == len(d) - 5
+
+
+@pytest.mark.gpu
+def test_stats_may_be_null(ctx):
+    fw, fh = 70, 45
+    g = camera_cases.make_global("roll_only", fw, fh)[1]
+    bufs = Buffers(ctx, *cull_scene("first_last", g))
+    tile = Tile(0, 0, fw, fh, fw, fh)
+    with_stats, st = bufs.run(g, tile, True)
+    without, none = bufs.run(g, tile, True, stats=False)
+    assert none is None and st[1] == 2
+    same(with_stats, without)
+
+
+@pytest.mark.gpu
+def test_refusals_enqueue_nothing(ctx):
+    w, h = 64, 48
+    g = camera_cases.make_global("default", w, h)[1]
+    v, i, d, b = cull_scene("first_last", g)
+    n = int((d["index_count"] // 3).sum())
+    dv, di, dd, db = ctx.upload(v), ctx.upload(i), ctx.upload(d), ctx.upload(b)
+    planes = [ctx.empty((h, w), torch.int32).fill_(0x5A5A5A5A) for _ in range(3)] + \
+             [ctx.empty((h, w), torch.float32).fill_(-7.0), ctx.empty((h, w), torch.uint8).fill_(0xA5)]
+    stats = ctx.empty((8,), torch.int32).fill_(0x11223344)
+    scratch = ctx.alloc_raster_scratch(w, h, n)
+    tile = Tile(0, 0, w, h, w, h)
+    ok = dict(g=g, tile=tile, vertices=dv, n_vertices=len(v), indices=di, n_indices=len(i), draws=dd, n_draws=len(d), max_triangles=n,
+              A=planes[0], B=planes[1], Cc=planes[2], depth=planes[3], stencil=planes[4], pitch=w, scratch=scratch, bounds=db, stats=stats)
+    bad = [dict(bounds=0), dict(bounds=db.data_ptr() + 2), dict(stats=stats.data_ptr() + 2), dict(stats=stats.data_ptr() + 1),
+           # every refusal of the unculled call
+           dict(vertices=0), dict(stencil=0), dict(n_indices=0), dict(n_draws=0), dict(max_triangles=0), dict(pitch=w - 1),
+           dict(tile=Tile(10, 0, w, h, w, h)), dict(tile=Tile(0, 0, w, h, 9000, h)), dict(n_draws=70000),
+           dict(max_triangles=(1 << 22) + 1), dict(scratch_bytes=ctx.raster_scratch_bytes(w, h, n, minimum=True) - 1)]
+    for k in bad:
+        with pytest.raises(PbrError, match="pbr_gbuffer_raster"):
+            ctx.gbuffer_raster_culled(**dict(ok, **k))
+    # the textured call: its own refusals and the cull's
+    tscratch = ctx.alloc_textured_raster_scratch(w, h, n)
+    maps = ctx.upload(np.full(len(d), NO_MAP, dtype=scene.DRAW_MAPS_DTYPE))
+    tok = dict(ok, scratch=tscratch, maps=maps, textures=[])
+    for k in (dict(bounds=0), dict(bounds=db.data_ptr() + 2), dict(stats=stats.data_ptr() + 2), dict(maps=None), dict(scratch=scratch),
+              dict(pitch=w - 1)):
+        with pytest.raises(PbrError, match="pbr_gbuffer_raster"):
+            ctx.gbuffer_raster_textured_culled(**dict(tok, **k))
+    for k in (dict(out=0), dict(vertices=0), dict(n_draws=0), dict(n_draws=70000), dict(n_vertices=0)):
+        args = dict(vertices=dv, n_vertices=len(v), indices=di, n_indices=len(i), draws=dd, n_draws=len(d), out=db)
+        args.update(k)
+        with pytest.raises(PbrError, match="pbr_draw_bounds"):
+            ctx.draw_bounds(**args)
+    ctx.sync()
+    assert all((p.cpu().numpy().view(np.uint32) == 0x5A5A5A5A).all() for p in planes[:3])
+    assert (planes[3].cpu().numpy() == -7.0).all() and (planes[4].cpu().numpy() == 0xA5).all()
+    assert (stats.cpu().numpy() == 0x11223344).all()
+    assert np.array_equal(db.cpu().numpy().reshape(-1).view(AABB_DTYPE).view(np.uint32), b.view(np.uint32))
+    # valid calls still run
+    ctx.gbuffer_raster_culled(**ok)
+    ctx.gbuffer_raster_textured_culled(**tok)
+    ctx.sync()
+    assert (planes[4].cpu().numpy() <= 8).all() and tuple(stats.cpu().numpy()[:2]) == (len(d) - 2, 2)
+
+
+# ---- whole frames
+def reference_models():
+    fx = np.load(os.path.join(common.ROOT, "tests", "golden", "sphere_grid.npz"))
+    (v, i, d), names = scene.reference_models(fx)
+    rec = common.reference_scene_lights()
+    lights = np.concatenate([scene.make_lights(rec["translation"][j], rec["color"][j], rec["radius"][j], rec["intensity"][j])
+                             for j in range(len(rec["radius"]))])
+    return v, i, d, lights
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("yaw", [0.0, 0.5, 1.5707964], ids=["reference", "yawed29", "yawed90"])
+def test_deferred_frame_with_culling(ctx, orc, yaw):
+    """the fixture scene at 360 x 240 through DeferredFrame.set_meshes(cull=True): HDR and LDR bit-identical to cull=False,
+    cull_stats() the rule's; the yawed cameras lose draws (at 90 degrees all of them: the planes are the clears)"""
+    from direct12pbrrenderer_amd.pipeline import DeferredFrame, TileSpec
+    w, h = 360, 240
+    sky, env, lut, sh = common.small_ibl(orc)
+    cam = scene.Camera.reference_default(w, h)
+    cam.rotate(0.0, yaw, 0.0)
+    g = scene.make_global(cam, w, h, sh_pack=sh)
+    v, i, d, lights = reference_models()
+    mask = rc.cull(g.Projection[:], g.View[:], (0, 0, w, h, w, h), d, scene.draw_bounds(v, i, d))   # on the CPU first
+    if yaw:
+        assert mask.sum() > 0 and ((~mask).sum() > 0) == (yaw < 1.0)
+
+    def half(a):
+        return ctx.upload(np.ascontiguousarray(a, dtype=np.float16).view(np.uint16)).view(torch.float16)
+
+    def frame(**kw):
+        fr = DeferredFrame(ctx, TileSpec(0, 0, w, h, w, h, 0), g, lights, half(lut), lut.shape[0], half(env), common.ENV_SIZE,
+                           common.ENV_MIPS)
+        fr.set_meshes(v, i, d, **kw)
+        fr.set_prev_luminance(0.18)
+        fr.render()
+        ctx.sync()
+        return fr
+    a, b = frame(), frame(cull=True)
+    c = frame(cull=True, bounds=scene.draw_bounds(v, i, d))
+    assert (a.gb["stencil"].cpu().numpy() > 0).any() == bool((~mask).any())
+    for fr in (b, c):
+        for k in PLANES:
+            assert torch.equal(a.gb[k], fr.gb[k]), k
+        assert np.array_equal(a.hdr.cpu().view(torch.int16).numpy(), fr.hdr.cpu().view(torch.int16).numpy())
+        assert np.array_equal(a.ldr_numpy(), fr.ldr_numpy())
+        st = fr.cull_stats()
+        assert st.astuple() == rc.stats(d, mask)
+        assert st.draws_culled > 0 or not yaw
+    with pytest.raises(ValueError):
+        a.cull_stats()
+
+
+@pytest.mark.gpu
+def test_host_graph_with_culling(ctx):
+    """pbrh_set_model_culling: GBufferPass's frame with culling on is the frame with culling off, and pbrh_culling_status gives the
+    rule's counts for the host's camera"""
+    import ctypes as C
+    from direct12pbrrenderer_amd import synth
+    from direct12pbrrenderer_amd.host import HostRenderer
+    from direct12pbrrenderer_amd.structs import Global
+    W, H, ENV, LUT = 360, 240, 32, 64
+    v, i, d, lights = reference_models()
+    frames = []
+    for on in (False, True):
+        r = HostRenderer(0, W, H, ENV, LUT)
+        try:
+            r.set_skybox(synth.env_cube(ENV), ENV)
+            r.set_lights(lights)
+            if on:
+                r.set_model_culling(True)
+            r.set_meshes(v, i, d)
+            r.set_initial_luminance(0.18)
+            r.render(1.0 / 60.0)
+            out = {k: r.read(n, (H, W), np.uint32) for k, n in (("A", "GBufferA"), ("B", "GBufferB"), ("C", "GBufferC"))}
+            out["hdr"] = r.read("DeferredShadingRT", (H, W, 4), np.float16).view(np.uint16)
+            out["ldr"] = r.read("ToneMappedTexture", (H, W), np.uint32)
+            status = r.culling_status()
+            g_host = Global()
+            assert r.lib.pbrh_get_global(r.h, C.byref(g_host)) == 0
+            frames.append((out, status))
+        finally:
+            r.close()
+    (off, st_off), (on_, st_on) = frames
+    for k in off:
+        assert np.array_equal(off[k], on_[k]), k
+    assert (off["A"] != 0).any()
+    mask = rc.cull(g_host.Projection[:], g_host.View[:], (0, 0, W, H, W, H), d, scene.draw_bounds(v, i, d))
+    assert st_off == (0, 0, 0, 0) and st_on == rc.stats(d, mask)
