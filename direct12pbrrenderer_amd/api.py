@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from .structs import (ShadeDesc, ShadeTables, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
-                      NUM_CLUSTERS, AABB_DTYPE, CullStats, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
+                      NUM_CLUSTERS, AABB_DTYPE, CullStats, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
 
 
 class PbrError(RuntimeError):
@@ -654,6 +654,21 @@ class PbrContext:
         """pbr_skybox_bc6h_views: skybox_bc6h() of every view in one launch; faces as skybox_bc6h takes them"""
         c = CubeBc6h(_bc6h_faces("skybox_bc6h_views", faces, size, mip_levels), int(size), int(mip_levels))
         self._check(self.lib.pbr_skybox_bc6h_views(self.h, views, int(n), int(w), int(h), C.byref(c)))
+
+    # ---- anti-aliasing: an integer edge filter on RGBA8 images (include/pbr_hip.h, "Anti-aliasing")
+    def fxaa(self, src, w, h, src_pitch, dst, dst_pitch):
+        """pbr_fxaa: src -> dst, two RGBA8 device images (tensors or addresses) of w x h pixels, pitches in pixels.  dst must not overlap
+        src; what the library refuses (a null pointer, an empty image, a pitch below w, an overlap) raises PbrError"""
+        self._check(self.lib.pbr_fxaa(self.h, _ptr(src), int(w), int(h), int(src_pitch), _ptr(dst), int(dst_pitch)))
+
+    def fxaa_batch(self, images, w, h):
+        """pbr_fxaa_batch: images = up to MAX_VIEWS (src, src_pitch, dst, dst_pitch) tuples of equal-sized images, filtered in ONE launch;
+        every dst gets the bits of its own fxaa() call"""
+        images = list(images)
+        arr = (FxaaImage * max(len(images), 1))()
+        for i, (src, src_pitch, dst, dst_pitch) in enumerate(images):
+            arr[i] = FxaaImage(_ptr(src), int(src_pitch), _ptr(dst), int(dst_pitch))
+        self._check(self.lib.pbr_fxaa_batch(self.h, arr, len(images), int(w), int(h)))
 
     def membench_read(self, buf, sink, blocks):
         """One streaming-read pass over `buf` (measurement aid: the device's achievable HBM-read bandwidth)."""

@@ -43,6 +43,8 @@ SIGNATURES = {
     "pbrh_capture_histogram": (_int, [_vp, _int]),
     "pbrh_captured_histogram": (_int, [_vp, _vp]),
     "pbrh_set_fused": (_int, [_vp, _int]),
+    "pbrh_set_antialiasing": (_int, [_vp, _int]),
+    "pbrh_presented": (_int, [_vp, C.c_char_p, C.c_size_t]),
     "pbrh_render_n": (_int, [_vp, _int, C.c_float, C.POINTER(C.c_double)]),
     "pbrh_render": (_int, [_vp, C.c_float]),
     "pbrh_execution_order": (_int, [_vp, C.c_char_p, C.c_size_t]),
@@ -366,6 +368,18 @@ class HostRenderer:
 
     def set_fused(self, on):
         self._check(self.lib.pbrh_set_fused(self.h, 1 if on else 0))
+
+    def set_antialiasing(self, on=True):
+        """pbrh_set_antialiasing: AntiAliasPass (the integer edge filter pbr_fxaa) between ToneMapping and Present.  It writes the
+        texture "AntiAliasedTexture" (read(name, (h, w), np.uint32)), which becomes the presented one; "ToneMappedTexture" stays
+        what it is.  Off by default.  A tile renderer and one with an overlapped tail refuse (HostError)."""
+        self._check(self.lib.pbrh_set_antialiasing(self.h, 1 if on else 0))
+
+    def presented(self):
+        """the name of the frame-graph texture the present pass shows"""
+        buf = C.create_string_buffer(128)
+        self._check(self.lib.pbrh_presented(self.h, buf, 128))
+        return buf.value.decode()
 
     def set_frames_in_flight(self, k):
         self._check(self.lib.pbrh_set_frames_in_flight(self.h, int(k)))

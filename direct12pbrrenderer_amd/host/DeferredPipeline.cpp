@@ -28,8 +28,20 @@ std::vector<IRenderPass*> DeferredRenderPipeline::Setup() {
     mBloomPass = std::make_unique<BloomPass>(mHaloChain);
     mClusteredPass = std::make_unique<ClusteredPass>();
     mPresentPass->SetFinalTexture(DeferredPipelineResource::ToneMappedTexture);
-    return {mPrefilterEnvMapPass.get(), mPrecomputeBRDFPass.get(), mClusteredPass.get(), mGBufferPass.get(),
-            mDeferredShadingPass.get(), mSkyboxPass.get(), mAutoExposurePass.get(), mToneMappingPass.get(), mBloomPass.get(), mPresentPass.get()};
+    mPasses = {mPrefilterEnvMapPass.get(), mPrecomputeBRDFPass.get(), mClusteredPass.get(), mGBufferPass.get(),
+               mDeferredShadingPass.get(), mSkyboxPass.get(), mAutoExposurePass.get(), mToneMappingPass.get(), mBloomPass.get(), mPresentPass.get()};
+    mAntiAliasing = false;
+    return mPasses;
+}
+
+std::vector<IRenderPass*> DeferredRenderPipeline::SetAntiAliasing(bool on) {
+    if (mPasses.empty()) throw HipException("DeferredRenderPipeline::SetAntiAliasing: Setup() first");
+    if (on && !mAntiAliasPass) mAntiAliasPass = std::make_unique<AntiAliasPass>();
+    mAntiAliasing = on;
+    mPresentPass->SetFinalTexture(on ? DeferredPipelineResource::AntiAliasedTexture : DeferredPipelineResource::ToneMappedTexture);
+    std::vector<IRenderPass*> passes = mPasses;
+    if (on) passes.insert(passes.end() - 1, mAntiAliasPass.get());   // in front of Present, the list's last
+    return passes;
 }
 
 // ----------------------------------------------------------------------------------- IBL precompute
@@ -337,6 +349,21 @@ void ToneMappingPass::Execute(FGContext* context) {   // DeferredPipeline.cpp:32
     mToneMappingRender.SetRWStructuredBuffer("AverageLuminance", avg_luminance);
     mToneMappingRender.SetTexture("LuminanceTexture", input_tex);
     context->CommandList->DrawScreen(&mToneMappingRender);
+}
+
+// ----------------------------------------------------------------------------------- anti-aliasing (not in the reference)
+AntiAliasPass::AntiAliasPass() {
+    ReadResource(DeferredPipelineResource::ToneMappedTexture);
+    // declared to the frame graph by FrameGraph::Recompile (AntiAliasPass::Target), not through the process-wide description table
+    WriteResource(DeferredPipelineResource::AntiAliasedTexture);
+    mAntiAliasRender.SetShader(Shader, false);
+}
+
+void AntiAliasPass::Execute(FGContext* context) {
+    PIXScope(context->CommandList, "Anti-Aliasing Pass");
+    auto* input_tex = As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::ToneMappedTexture));
+    mAntiAliasRender.SetTexture("InputTexture", input_tex);
+    context->CommandList->DrawScreen(&mAntiAliasRender);
 }
 
 // ----------------------------------------------------------------------------------- bloom

@@ -29,6 +29,8 @@ struct DeferredPipelineResource {   // DeferredPipeline.h:9-32
     inline static FGResourceId PointLights = FGResourceIDs::Instance()->NameToID("ClusteredLights");
     inline static FGResourceId LuminanceHistogram = FGResourceIDs::Instance()->NameToID("LuminanceHistogram");
     inline static FGResourceId AverageLuminance = FGResourceIDs::Instance()->NameToID("AverageLuminance");
+    // not in the reference: the target of AntiAliasPass, declared (and allocated) only while anti-aliasing is on
+    inline static FGResourceId AntiAliasedTexture = FGResourceIDs::Instance()->NameToID("AntiAliasedTexture");
 };
 
 // render size (GD3D12Device->Width()/Height() in the reference; App.h:77-78 defaults 1440x960)
@@ -160,6 +162,21 @@ protected:
     ShadingState mToneMappingRender;
 };
 
+// Not in the reference, which has no anti-aliasing: the integer edge filter pbr_fxaa on the tone-mapped target, into a texture of its
+// own that becomes the presented one.  Part of the pipeline only while DeferredRenderPipeline::SetAntiAliasing is on.
+class AntiAliasPass : public GraphicsPass {
+public:
+    static constexpr const char* Shader = "fxaa.hip";   // the binding-table row's name: no shader file of the reference
+    AntiAliasPass();
+    const char* Name() const override { return "AntiAlias"; }
+    void Execute(FGContext* context) override;
+    static FGTransientTextureDescription Target(RenderSize s) {
+        return FGTransientTextureDescription{(uint16)s.Width, (uint16)s.Height, 1, ETextureFormat_R8G8B8A8_UNORM, ETexture2DFlag_AllowRenderTarget};
+    }
+protected:
+    ShadingState mAntiAliasRender;
+};
+
 class DeferredRenderPipeline : public IRenderPipeline {   // :463-481, DeferredPipeline.cpp:17-44
 public:
     DeferredRenderPipeline(RenderSize size, uint32 env_size = PreFilterEnvMapPass::PreFilterEnvMapSize, uint32 lut_res = PrecomputeBRDFPass::TextureResolution)
@@ -170,6 +187,11 @@ public:
         : mSize(RenderSize{layout.Shaded.w, layout.Shaded.h}), mEnvSize(env_size), mLutRes(lut_res),
           mHaloChain(layout.Halo ? RenderSize{layout.Bloom.w, layout.Bloom.h} : RenderSize{0, 0}) {}
     std::vector<IRenderPass*> Setup() override;
+    // The pass list with (on) or without AntiAliasPass between ToneMapping and Present, and the present pass re-pointed at the
+    // texture it shows; for FrameGraph::Recompile, after Setup.  Off (the default): exactly Setup()'s list.
+    std::vector<IRenderPass*> SetAntiAliasing(bool on);
+    bool AntiAliasing() const { return mAntiAliasing; }
+    RenderSize Size() const { return mSize; }
 
     std::unique_ptr<GBufferPass> mGBufferPass;
     std::unique_ptr<DeferredShadingPass> mDeferredShadingPass;
@@ -180,7 +202,10 @@ public:
     std::unique_ptr<AutoExposurePass> mAutoExposurePass;
     std::unique_ptr<ToneMappingPass> mToneMappingPass;
     std::unique_ptr<ClusteredPass> mClusteredPass;
+    std::unique_ptr<AntiAliasPass> mAntiAliasPass;   // null until anti-aliasing is first turned on
 private:
+    std::vector<IRenderPass*> mPasses;   // Setup()'s list
+    bool mAntiAliasing = false;
     RenderSize mSize;
     uint32 mEnvSize, mLutRes;
     RenderSize mHaloChain{0, 0};

@@ -87,6 +87,15 @@ void FrameGraph::Compile() {
         if (lc.Valid) mFGResourceAllocator.AllocateTransientResource(lc.ResourceId, Describe(lc.ResourceId));
 }
 
+void FrameGraph::Recompile(const std::vector<IRenderPass*>& passes, const Declared& declared) {
+    mParser.Parse(passes, mRenderPipeline->mPresentPass.get());
+    mPipelinePasses = passes;
+    mDescriptions.resize(FGResourceIDs::Instance()->NumResources());
+    for (const auto& d : declared) mDescriptions.at(d.first) = d.second;
+    for (auto& lc : mParser.GetResourceLifecycle())
+        if (lc.Valid) mFGResourceAllocator.AllocateIfMissing(lc.ResourceId, Describe(lc.ResourceId));
+}
+
 void FrameGraph::DoubleBufferResources(const std::vector<FGResourceId>& ids) {
     for (FGResourceId id : ids) mFGResourceAllocator.DoubleBuffer(id, Describe(id));
     mDoubleBuffered = !ids.empty();

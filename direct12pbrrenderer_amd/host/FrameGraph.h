@@ -28,6 +28,12 @@ public:
     FrameGraph(const FrameGraph&) = delete;
     void Setup();     // construct the passes (IRenderPipeline::Setup)
     void Compile();   // execution order + transient resource allocation
+    // A changed pass list after Compile (a pass added or taken out: DeferredRenderPipeline::SetAntiAliasing): the execution order is
+    // parsed again, the transient resources the new passes declare are allocated, and every resource that exists keeps its memory
+    // and its contents.  declared: the descriptions of the new passes' resources (the description table is a process-wide
+    // singleton that another renderer may have reset since).
+    using Declared = std::vector<std::pair<FGResourceId, FGResourceDescriptionTable::Description>>;
+    void Recompile(const std::vector<IRenderPass*>& passes, const Declared& declared);
     void Execute(HipCommandList* cmd, Scene* scene, Camera* camera);
     // Frames alternate between two instances of these transient resources (the overlapped frame tail: the HDR target and the
     // luminance histogram of frame i are still read on the side stream while frame i + 1 is shaded).  Call after Compile.

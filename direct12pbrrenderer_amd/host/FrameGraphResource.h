@@ -272,6 +272,10 @@ public:
         mParity = 0;
     }
     void AllocateTransientResource(FGResourceId id, const FGResourceDescriptionTable::Description& d) { mTransient[id] = Make(d); }
+    // FrameGraph::Recompile: what is allocated stays as it is, contents included
+    void AllocateIfMissing(FGResourceId id, const FGResourceDescriptionTable::Description& d) {
+        if (!mTransient.at(id)) mTransient[id] = Make(d);
+    }
     // A second instance of a transient resource: frames alternate between the two (SetParity), so that work of frame i that is
     // still in flight on another stream — the overlapped frame tail — does not see frame i + 1 write the same memory.  Not in
     // the reference (its frames are strictly serial).

@@ -27,6 +27,8 @@ static const std::vector<ShaderReflection>& Reflections() {
         {"hdr_luminance_histogram.hlsl", true, {"LuminanceTexture"}, {}, {}, {"LuminanceHistogram"}, sizeof(LuminanceHistogramConstant)},
         {"hdr_average_histogram.hlsl", true, {}, {}, {}, {"LuminanceHistogram", "AverageLuminance"}, sizeof(AverageLuminanceConstant)},
         {"hdr_tone_mapping.hlsl", false, {"LuminanceTexture"}, {}, {}, {"AverageLuminance"}, 0},
+        // not a shader file of the reference (it has no anti-aliasing): AntiAliasPass's row, the integer edge filter of csrc/fxaa.hip
+        {"fxaa.hip", false, {"InputTexture"}, {}, {}, {}, 0},
         // raster shaders of the reference: out of scope; known so that SetShader succeeds
         {"gbuffer.hlsl", false, {}, {}, {}, {}, 0},
         {"skybox.hlsl", false, {"SkyBox"}, {}, {}, {}, 0},
@@ -423,6 +425,14 @@ void HipCommandList::DrawScreen(ShadingState* s) {
         Check(pbr_tonemap(mCtx, in.ptr + 4 * ((size_t)r.y * in.w + r.x), r.w, r.h, in.w, (const float*)s->Buffer("AverageLuminance")->DevicePtr(),
                           (uint32_t*)mRenderTarget->DevicePtr() + (size_t)r.y * mRenderTarget->Width() + r.x, mRenderTarget->Width()), "pbr_tonemap");
         EndTail();
+    } else if (f == "fxaa.hip") {
+        auto* in = dynamic_cast<DeviceTexture2D*>(s->Texture("InputTexture").Texture);
+        if (!in) throw HipException("fxaa: bad texture binding");
+        // the filter reads up to 25 pixels around a pixel: a tile of a larger frame would need an LDR apron from its neighbours
+        if (mTile.w || mInterior.w || mTailOverlap) throw HipException("fxaa: whole frames on the frame's own stream only (no tile, no overlapped tail)");
+        if (in->Width() != mRenderTarget->Width() || in->Height() != mRenderTarget->Height()) throw HipException("fxaa: source and target sizes differ");
+        Check(pbr_fxaa(mCtx, (const uint32_t*)in->DevicePtr(), in->Width(), in->Height(), in->Width(), (uint32_t*)mRenderTarget->DevicePtr(),
+                       mRenderTarget->Width()), "pbr_fxaa");
     } else {
         throw HipException("DrawScreen: " + std::string(f) + " is not a full-screen kernel of this build");
     }

@@ -134,6 +134,7 @@ public:
 
     pbr_ctx* Context() const { return mCtx; }
     uint32 DispatchCount() const { return mDispatchCount; }
+    bool TileSet() const { return mTile.w != 0 || mInterior.w != 0; }
     DeviceTexture2D* Presented() const { return mPresented; }
     // the light count the last clustered_culling dispatch was given (the HIP shade stages exactly that many records)
     int32 NumLights() const { return mNumLights; }

@@ -141,7 +141,8 @@ public:
     PresentPass() : mFinalTexture(InvalidFGResourceId) {}
     const char* Name() const override { return "Present"; }
     void Execute(FGContext* context) override;
-    void SetFinalTexture(FGResourceId id) {
+    void SetFinalTexture(FGResourceId id) {   // may be called again: the pass then reads the new texture only
+        mInputResources.clear();
         mFinalTexture = id;
         ReadResource(id);
     }

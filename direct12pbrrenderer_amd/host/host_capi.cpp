@@ -22,6 +22,7 @@ struct pbrh_renderer {
     std::unique_ptr<Camera> camera;
     uint32 width = 0, height = 0;
     float time = 0.0f;
+    bool tile = false;   // made by pbrh_create_tile: one device's part of a larger frame
     std::string err;
 };
 
@@ -69,6 +70,7 @@ pbrh_renderer* pbrh_create_tile(int device, uint32_t full_w, uint32_t full_h, ui
         FGResourceDescriptionTable::Instance()->Reset();
         r->width = layout.Shaded.w;
         r->height = layout.Shaded.h;
+        r->tile = true;
         r->pipeline = std::make_unique<DeferredRenderPipeline>(layout, env_size, lut_res);
         r->scheduler = std::make_unique<RenderScheduler>(r->pipeline.get(), device, r->width, r->height);
         r->scene = std::make_unique<Scene>();
@@ -526,6 +528,7 @@ int pbrh_set_initial_luminance(pbrh_renderer* r, float v) {
 int pbrh_set_tile(pbrh_renderer* r, uint32_t x0, uint32_t y0, uint32_t full_w, uint32_t full_h,
                   uint32_t ix, uint32_t iy, uint32_t iw, uint32_t ih) {
     return guarded(r, [&] {
+        if (r->pipeline->AntiAliasing()) throw HipException("pbrh_set_tile: anti-aliasing is on, and it filters whole frames only");
         if (x0 + r->width > full_w || y0 + r->height > full_h) throw HipException("pbrh_set_tile: the target does not fit the frame");
         if (iw == 0 || ih == 0 || ix + iw > r->width || iy + ih > r->height) throw HipException("pbrh_set_tile: interior outside the target");
         HipCommandList* cmd = r->scheduler->CommandList();
@@ -576,6 +579,7 @@ int pbrh_set_frames_in_flight(pbrh_renderer* r, int k) {
 int pbrh_set_tail_overlap(pbrh_renderer* r, int on) {
     return guarded(r, [&] {
         HipCommandList* cmd = r->scheduler->CommandList();
+        if (on && r->pipeline->AntiAliasing()) throw HipException("pbrh_set_tail_overlap: anti-aliasing is on, and it follows the tone-map on the frame's own stream");
         cmd->SetTailOverlap(on);
         if (on) r->scheduler->GetFrameGraph()->DoubleBufferResources({DeferredPipelineResource::DeferredShadingRT, DeferredPipelineResource::LuminanceHistogram});
     });
@@ -599,6 +603,22 @@ int pbrh_render(pbrh_renderer* r, float dt) {
     return guarded(r, [&] {
         r->time += dt;
         r->scheduler->ExecutePipeline(r->scene.get(), r->camera.get(), dt, r->time);
+    });
+}
+
+// AntiAliasPass (pbr_fxaa) between ToneMapping and Present, writing the frame-graph texture "AntiAliasedTexture", which becomes the
+// presented one; off (the default) the pass list, the execution order and every resource are what they are without this call.
+// Every resource that exists keeps its contents across the switch.  Refused for a tile of a larger frame and with an overlapped tail.
+int pbrh_set_antialiasing(pbrh_renderer* r, int on) {
+    return guarded(r, [&] {
+        if ((on != 0) == r->pipeline->AntiAliasing()) return;
+        HipCommandList* cmd = r->scheduler->CommandList();
+        if (on && (r->tile || cmd->TileSet()))
+            throw HipException("pbrh_set_antialiasing: this renderer draws a tile of a larger frame; the filter reads up to 25 pixels beyond a tile and runs on whole frames only");
+        if (on && cmd->TailOverlap()) throw HipException("pbrh_set_antialiasing: the overlapped tail tone-maps on the side stream; turn it off first");
+        cmd->WaitIdle();
+        const std::vector<IRenderPass*> passes = r->pipeline->SetAntiAliasing(on != 0);
+        r->scheduler->GetFrameGraph()->Recompile(passes, {{DeferredPipelineResource::AntiAliasedTexture, AntiAliasPass::Target(r->pipeline->Size())}});
     });
 }
 
@@ -629,6 +649,16 @@ int pbrh_execution_order(pbrh_renderer* r, char* buf, size_t len) {
             s += p->Name();
         }
         std::snprintf(buf, len, "%s", s.c_str());
+    });
+}
+
+// the name of the frame-graph texture the present pass shows: "ToneMappedTexture", or "AntiAliasedTexture" with anti-aliasing on
+int pbrh_presented(pbrh_renderer* r, char* buf, size_t len) {
+    return guarded(r, [&] {
+        const auto& order = r->scheduler->GetFrameGraph()->ExecutionOrder();
+        auto* present = order.empty() ? nullptr : dynamic_cast<PresentPass*>(order.back());
+        if (!present || !buf || !len) throw HipException("pbrh_presented: no present pass");
+        std::snprintf(buf, len, "%s", std::string(FGResourceIDs::Instance()->IdToName(present->FinalTexture())).c_str());
     });
 }
 

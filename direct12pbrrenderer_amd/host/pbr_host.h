@@ -185,6 +185,14 @@ int pbrh_captured_histogram(pbrh_renderer* r, uint32_t* dst256);
  * The per-frame passes give the same frame bit for bit either way; the fused env chain is within 1 fp16 ULP of the five
  * dispatches (tests/test_host_graph.py).  May be switched between frames. */
 int pbrh_set_fused(pbrh_renderer* r, int on);
+/* Anti-aliasing (not in the reference): on adds AntiAliasPass (pbr_fxaa, the integer edge filter of include/pbr_hip.h) between
+ * ToneMapping and Present; it writes the frame-graph texture "AntiAliasedTexture" (RGBA8, readable through pbrh_read), which becomes
+ * the presented one, and ToneMappedTexture stays what it is.  Off by default; off, the execution order, the dispatch count and every
+ * resource are those of a renderer that never heard of it.  -1 for a renderer made by pbrh_create_tile or given pbrh_set_tile (the
+ * filter reads 25 pixels beyond a tile) and while the overlapped tail is on. */
+int pbrh_set_antialiasing(pbrh_renderer* r, int on);
+/* the name of the frame-graph texture the present pass shows ("ToneMappedTexture"; "AntiAliasedTexture" with anti-aliasing on) */
+int pbrh_presented(pbrh_renderer* r, char* buf, size_t len);
 /* n frames; *ms_per_frame = average wall time per frame (every frame ends with the per-frame fence wait) */
 int pbrh_render_n(pbrh_renderer* r, int n, float delta_time, double* ms_per_frame);
 /* one frame through RenderScheduler::ExecutePipeline; blocks until the GPU is done */

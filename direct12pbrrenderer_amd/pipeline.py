@@ -307,6 +307,7 @@ class DeferredFrame:
         self._hist_next = ctx.zeros((HISTOGRAM_BINS,), torch.int32)
         self._avg_next = ctx.zeros((1,), torch.float32)
         self.ldr = ctx.zeros((spec.h, spec.w), torch.int32)
+        self.ldr_aa = None   # the anti-aliased target: allocated by the first antialias()
         self.gb = None
         self.mesh = None
         self.tile = Tile(spec.sx0, spec.sy0, spec.sw, spec.sh, spec.full_w, spec.full_h)
@@ -591,6 +592,22 @@ class DeferredFrame:
         self.avg, self._avg_next = self._avg_next, self.avg
         self.hist, self._hist_next = self._hist_next, self.hist
 
+    def antialias(self):
+        """The anti-aliasing pass (pbr_fxaa) on the tone-mapped target: ldr -> ldr_aa, a second RGBA8 target of the same size (read
+        it with ldr_aa_numpy()); ldr is not touched.  Whole frames only: the filter of a tile of a larger frame would need an LDR
+        apron of 25 pixels from the neighbouring tiles."""
+        s = self.spec
+        self._whole_frame_or_raise()
+        if self.ldr_aa is None:
+            self.ldr_aa = self.ctx.zeros((s.h, s.w), torch.int32)
+        self.ctx.fxaa(self.ldr, s.w, s.h, s.w, self.ldr_aa, s.w)
+
+    def _whole_frame_or_raise(self):
+        s = self.spec
+        if (s.x0, s.y0, s.w, s.h) != (0, 0, s.full_w, s.full_h):
+            raise ValueError(f"antialias: this frame is the tile ({s.x0}, {s.y0}, {s.w}, {s.h}) of a {s.full_w} x {s.full_h} frame; the filter "
+                             "reads up to 25 pixels beyond a tile and runs on whole frames only")
+
     def exposure_and_tonemap(self):
         if self.fused_exposure:
             self.average_tonemap()
@@ -598,9 +615,19 @@ class DeferredFrame:
             self.average()
             self.tonemap()
 
-    def render(self, shade_events=None):
+    def render(self, shade_events=None, antialias=False):
         """One frame: every per-frame dispatch of the reference, in the frame graph's order.
-        shade_events: optional list; a (start, end) pair of torch events bracketing the shade launch is appended."""
+        shade_events: optional list; a (start, end) pair of torch events bracketing the shade launch is appended.
+        antialias: antialias() behind the tone-map, on the stream the tone-map ran on; ldr is what it is without."""
+        if antialias:
+            self._whole_frame_or_raise()
+            if self._tail_overlap:
+                raise ValueError("render(antialias=True): the overlapped tail tone-maps on the side stream; call antialias() after finish()")
+        self._render(shade_events)
+        if antialias:
+            self.antialias()
+
+    def _render(self, shade_events):
         if self.mesh is not None:
             self.rasterize()
         self.clustered()
@@ -695,6 +722,11 @@ class DeferredFrame:
     def ldr_numpy(self):
         return self.ldr.cpu().numpy().view(np.uint32)
 
+    def ldr_aa_numpy(self):
+        if self.ldr_aa is None:
+            raise ValueError("ldr_aa_numpy: antialias() or render(antialias=True) first")
+        return self.ldr_aa.cpu().numpy().view(np.uint32)
+
 
 class MultiViewFrame:
     """N camera views of one scene, w x h whole frames each, rendered as ONE chain of launches per MAX_VIEWS views (the pbr_*_views
@@ -720,6 +752,7 @@ class MultiViewFrame:
         self.hist = [ctx.zeros((HISTOGRAM_BINS,), torch.int32) for _ in range(self.n)]
         self.avg = [ctx.zeros((1,), torch.float32) for _ in range(self.n)]
         self.ldr = [ctx.zeros((self.h, self.w), torch.int32) for _ in range(self.n)]
+        self.ldr_aa = None   # the anti-aliased targets: allocated by the first antialias()
         self.gb = None
         self.tile = Tile(0, 0, self.w, self.h, self.w, self.h)
         self.globals = list(globals)
@@ -798,8 +831,15 @@ class MultiViewFrame:
         for arr, n, _ in self._calls():
             self.ctx.tonemap_views(arr, n, self.w, self.h)
 
-    def render(self):
-        """One frame of every view: clustered -> [sky] -> shade -> bloom + histogram -> average -> tone-map."""
+    def antialias(self):
+        """The anti-aliasing pass on every view's tone-mapped target, ldr[v] -> ldr_aa[v]: one pbr_fxaa_batch call per MAX_VIEWS views"""
+        if self.ldr_aa is None:
+            self.ldr_aa = [self.ctx.zeros((self.h, self.w), torch.int32) for _ in range(self.n)]
+        for b0 in range(0, self.n, MAX_VIEWS):
+            self.ctx.fxaa_batch([(self.ldr[v], self.w, self.ldr_aa[v], self.w) for v in range(b0, min(b0 + MAX_VIEWS, self.n))], self.w, self.h)
+
+    def render(self, antialias=False):
+        """One frame of every view: clustered -> [sky] -> shade -> bloom + histogram -> average -> tone-map [-> anti-aliasing]."""
         self.clustered()
         if self.sky is not None:
             self.skybox()
@@ -807,6 +847,8 @@ class MultiViewFrame:
         self.bloom_histogram()
         self.average()
         self.tonemap()
+        if antialias:
+            self.antialias()
 
     # ---- read-back helpers for tests
     def hdr(self, v):
@@ -815,3 +857,8 @@ class MultiViewFrame:
 
     def ldr_numpy(self, v):
         return self.ldr[v].cpu().numpy().view(np.uint32)
+
+    def ldr_aa_numpy(self, v):
+        if self.ldr_aa is None:
+            raise ValueError("ldr_aa_numpy: antialias() or render(antialias=True) first")
+        return self.ldr_aa[v].cpu().numpy().view(np.uint32)

@@ -106,6 +106,11 @@ class View(C.Structure):
     ]
 
 
+class FxaaImage(C.Structure):
+    """pbr_fxaa_image: one image of a pbr_fxaa_batch call (device pointers, pitches in pixels)."""
+    _fields_ = [("src", C.c_void_p), ("src_pitch", C.c_uint32), ("dst", C.c_void_p), ("dst_pitch", C.c_uint32)]
+
+
 class HaloPeer(C.Structure):
     """pbr_halo_peer: rectangles {x, y, w, h} of the level-1 plane exchanged with rank `rank`."""
     _fields_ = [("rank", C.c_int32), ("send", C.c_uint32 * 4), ("recv", C.c_uint32 * 4)]

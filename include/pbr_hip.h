@@ -890,6 +890,50 @@ pbr_status pbr_tonemap_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, ui
 pbr_status pbr_skybox_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h, const pbr_cube_f32* sky);
 pbr_status pbr_skybox_bc6h_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h, const pbr_cube_bc6h* sky);
 
+/* ---- Anti-aliasing (new): an edge filter on the tone-mapped RGBA8 target ------------------------------------------------------ */
+/* The reference has no anti-aliasing of any kind, and the rasterizer resolves one sample per pixel: every silhouette is a staircase.
+ * pbr_fxaa is a post-process filter of FXAA's structure (local-contrast test, edge orientation, a walk along the edge to its two ends,
+ * a sub-pixel blend across it) under an all-integer rule that is this project's own, pinned here, restated in tests/fxaa_ref.py and
+ * compiled for the host from the kernel's own text (csrc/fxaa_pixel.hpp, tools/fxaa_hostcheck.cpp).  The kernel is bit-identical to the
+ * restatement on every pixel: nothing is floating point, so there is no tolerance.  It reads the RGBA8 image (R in the low byte) and
+ * writes another one; it needs nothing from the G-buffer and sits after everything the reference defines.
+ *
+ * THE RULE.  Every read of a pixel outside [0, w) x [0, h) takes the nearest pixel inside (each coordinate clamped on its own).
+ *   Luma        L = 77 R + 150 G + 29 B, an integer in 0 .. 65 280.
+ *   Contrast    at pixel M with the 4-neighbours N, S, W, E (N is y - 1): hi, lo = max, min of the five lumas, range = hi - lo.
+ *               range < max(4080, hi >> 3): M is not an edge pixel, its four bytes are copied.
+ *   Orientation with the corners NW, NE, SW, SE:  eh = |NW + SW - 2W| + 2 |N + S - 2M| + |NE + SE - 2E|,
+ *               ev = |NW + NE - 2N| + 2 |W + E - 2M| + |SW + SE - 2S|.  The edge is horizontal iff eh >= ev.  The pair across it is
+ *               (a, b) = (N, S) for a horizontal edge, (W, E) for a vertical one; the walk runs along x resp. along y.
+ *   Side        a if |a - M| >= |b - M|, else b.  nb = that neighbour, g = the larger absolute difference, P2 = L(M) + L(nb),
+ *               m_lt = L(M) < L(nb).
+ *   Walk        separately in the negative and the positive direction along the edge, over the offsets
+ *               k = 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24 in that order:  e = L(m_k) + L(nb_k) - P2, m_k the pixel k steps
+ *               along the edge from M (clamped), nb_k its neighbour on the chosen side (clamped).  Stop at the first k with
+ *               2 |e| >= g; if none stops, keep k = 24 and that last e.  Results (kn, en) and (kp, ep).
+ *   Edge offset kn < kp: dst = kn, good = (en < 0) != m_lt; otherwise dst = kp, good = (ep < 0) != m_lt.
+ *               off8 = good ? 128 - (256 dst) / (kn + kp) : 0, the division floored.
+ *   Sub-pixel   A = 2 (N + S + W + E) + NW + NE + SW + SE;  t = min(256, 256 |A - 12M| / (12 range)) floored;
+ *               s = (t t (768 - 2t)) >> 16;  sub8 = (3 s s) >> 10, in 0 .. 192.
+ *   Output      f8 = max(off8, sub8); R, G, B: out = (c_M (256 - f8) + c_nb f8 + 128) >> 8; alpha is M's, unchanged.
+ * Choices the rule leaves to no one: ties go to "horizontal" (eh == ev), to side a (|a - M| == |b - M|) and to the positive walk
+ * (kn == kp); g may be 0 (then both walks stop at k = 1); a pixel reads at most 24 pixels along one axis and 1 along the other.
+ *
+ * src, dst: device, 4-byte aligned, w x h pixels with pitches (in pixels) >= w; 16-byte accesses are used where a pointer and its
+ * pitch are 16-byte multiples.  Refusals (PBR_ERR_INVALID, nothing enqueued): a null pointer, w or h of 0 (or above 65 535), a pitch
+ * below w, and dst overlapping src: the filter cannot run in place. */
+pbr_status pbr_fxaa(pbr_ctx* ctx, const uint32_t* src, uint32_t w, uint32_t h, uint32_t src_pitch, uint32_t* dst, uint32_t dst_pitch);
+/* n <= PBR_MAX_VIEWS equal-sized images in ONE launch (the image index in the grid, the table by value in the kernel arguments):
+ * each dst is bit-identical to its single call's.  Further refusals: n of 0 or above PBR_MAX_VIEWS, and any dst overlapping any
+ * image's src or another dst (sources may alias each other). */
+typedef struct pbr_fxaa_image {
+    const uint32_t* src;
+    uint32_t        src_pitch;
+    uint32_t*       dst;
+    uint32_t        dst_pitch;
+} pbr_fxaa_image;
+pbr_status pbr_fxaa_batch(pbr_ctx* ctx, const pbr_fxaa_image* images, uint32_t n, uint32_t w, uint32_t h);
+
 /* ---- multi-GPU (new) -------------------------------------------------------------- */
 /* RCCL communicator over the ranks of one node.  unique_id: 128 bytes from
  * pbr_comm_unique_id() on rank 0, broadcast by the caller (e.g. torch.distributed store). */
