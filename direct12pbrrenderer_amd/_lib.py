@@ -6,7 +6,7 @@ symbol cannot be resolved this module raises — it never substitutes another im
 import ctypes as C
 import os
 
-from .structs import CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, ShadeDesc, ShadeTables, Texture2D, Tile, View
+from .structs import Aabb, CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, ShadeDesc, ShadeTables, SunDesc, Texture2D, Tile, View
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB", os.path.join(_HERE, "libpbr_hip.so"))   # override = experiments only
@@ -99,6 +99,8 @@ SIGNATURES = {
     "pbr_skybox_bc6h_views": (_int, [_vp, C.POINTER(View), _u32, _u32, _u32, C.POINTER(CubeBc6h)]),
     "pbr_fxaa": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32]),
     "pbr_fxaa_batch": (_int, [_vp, C.POINTER(FxaaImage), _u32, _u32, _u32]),
+    "pbr_sun_light": (_int, [_vp, C.POINTER(SunDesc)]),
+    "pbr_sun_fit": (_int, [C.POINTER(_f32 * 3), C.POINTER(Aabb), _u32, _u32, C.POINTER(Global), C.POINTER(_f32 * 16)]),
     "pbr_comm_unique_id": (_int, [_vp]),
     "pbr_comm_init": (_int, [_vp, _int, _int, _vp]),
     "pbr_allreduce_hist": (_int, [_vp, _vp]),

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .structs import (ShadeDesc, ShadeTables, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
+from .structs import (Aabb, ShadeDesc, ShadeTables, Sun, SunDesc, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
                       NUM_CLUSTERS, AABB_DTYPE, CullStats, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
 
@@ -670,6 +670,21 @@ class PbrContext:
             arr[i] = FxaaImage(_ptr(src), int(src_pitch), _ptr(dst), int(dst_pitch))
         self._check(self.lib.pbr_fxaa_batch(self.h, arr, len(images), int(w), int(h)))
 
+    # ---- sun light with a shadow map (include/pbr_hip.h, "Sun light with a shadow map")
+    def sun_light(self, g: Global, tile: Tile, gb, pitch, sun: Sun, hdr, hdr_pitch, shadow_depth=None, map_w=0, map_h=0, map_pitch=None,
+                  contrib_f32=None):
+        """pbr_sun_light: the directional light `sun` (structs.Sun, make_sun) added to the fp16 target hdr where the G-buffer gb (dict of
+        device tensors A, B, C, depth, stencil) holds geometry; shadow_depth: the depth plane of a gbuffer_raster call under sun_fit's
+        light camera (None: no shadows).  contrib_f32 (float32 [h, hdr_pitch, 4], hdr None): the parity probe, the contribution alone."""
+        s = _gbuffer(gb, pitch)
+        d = SunDesc(C.addressof(g), C.addressof(tile), C.addressof(s), C.addressof(sun), _ptr(shadow_depth), _ptr(hdr), _ptr(contrib_f32),
+                    int(map_w), int(map_h), int(map_w if map_pitch is None else map_pitch), int(hdr_pitch))
+        self._check(self.lib.pbr_sun_light(self.h, C.byref(d)))
+
+    def sun_fit(self, direction, box_min, box_max, map_w, map_h):
+        """pbr_sun_fit (host only): see the module's sun_fit"""
+        return sun_fit(direction, box_min, box_max, map_w, map_h)
+
     def membench_read(self, buf, sink, blocks):
         """One streaming-read pass over `buf` (measurement aid: the device's achievable HBM-read bandwidth)."""
         self._check(self.lib.pbr_membench_read(self.h, _ptr(buf), buf.numel() * buf.element_size(), _ptr(sink), blocks))
@@ -720,6 +735,29 @@ def comm_unique_id() -> bytes:
     if st != 0:
         raise PbrError(f"pbr_comm_unique_id failed: status {st}")
     return buf.raw
+
+
+def sun_fit(direction, box_min, box_max, map_w, map_h):
+    """pbr_sun_fit: (light Global, LightViewProj as 16 floats) of the orthographic light camera that looks along -direction and holds
+    the world box [box_min, box_max] with one map texel of margin in x / y and 1 % in depth.  Host only: no context, no GPU."""
+    lib = _lib.load()
+    g, m = Global(), (C.c_float * 16)()
+    box = Aabb((C.c_float * 3)(*[float(v) for v in box_min]), (C.c_float * 3)(*[float(v) for v in box_max]))
+    st = lib.pbr_sun_fit(C.byref((C.c_float * 3)(*[float(v) for v in direction])), C.byref(box), int(map_w), int(map_h), C.byref(g), C.byref(m))
+    if st != 0:
+        raise PbrError(f"pbr_sun_fit refused (status {st}): direction {tuple(direction)}, box {tuple(box_min)} .. {tuple(box_max)}, map {map_w} x {map_h}")
+    return g, [float(v) for v in m]
+
+
+def make_sun(direction, luminance, light_view_proj=None, bias=(0.0, 0.0), pcf=3):
+    """structs.Sun: direction normalised in double and rounded to float32, luminance a scalar or three channels, light_view_proj 16
+    floats (None: the identity, for a light without a map)."""
+    d = np.asarray(direction, dtype=np.float64).reshape(3)
+    d = d / np.sqrt(float((d * d).sum()))
+    lum = np.broadcast_to(np.asarray(luminance, dtype=np.float32), (3,))
+    m = np.eye(4, dtype=np.float32).reshape(16) if light_view_proj is None else np.asarray(light_view_proj, dtype=np.float32).reshape(16)
+    return Sun((C.c_float * 3)(*[float(np.float32(v)) for v in d]), (C.c_float * 3)(*[float(v) for v in lum]),
+               (C.c_float * 16)(*[float(v) for v in m]), float(bias[0]), float(bias[1]), int(pcf))
 
 
 HIST_BINS = HISTOGRAM_BINS

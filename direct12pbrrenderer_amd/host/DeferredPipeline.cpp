@@ -2,6 +2,9 @@
 // dispatch with the reference's group counts (Engine/Source/Renderer/Pipeline/DeferredPipeline.cpp).
 #include "DeferredPipeline.h"
 
+#include <cfloat>
+#include <cmath>
+
 namespace MRendererHip {
 
 static inline uint32 CalculateDispatchSize(uint32 texture_size, uint32 thread_group_size) {
@@ -31,7 +34,59 @@ std::vector<IRenderPass*> DeferredRenderPipeline::Setup() {
     mPasses = {mPrefilterEnvMapPass.get(), mPrecomputeBRDFPass.get(), mClusteredPass.get(), mGBufferPass.get(),
                mDeferredShadingPass.get(), mSkyboxPass.get(), mAutoExposurePass.get(), mToneMappingPass.get(), mBloomPass.get(), mPresentPass.get()};
     mAntiAliasing = false;
+    mSunShadowPass.reset();
+    mSunLightPass.reset();
     return mPasses;
+}
+
+std::vector<IRenderPass*> DeferredRenderPipeline::Compose() const {
+    std::vector<IRenderPass*> passes = mPasses;
+    if (mSunShadowPass) passes.insert(passes.end() - 1, mSunShadowPass.get());   // in front of Present, the list's last
+    if (mSunLightPass) passes.insert(passes.end() - 1, mSunLightPass.get());
+    if (mAntiAliasing) passes.insert(passes.end() - 1, mAntiAliasPass.get());
+    return passes;
+}
+
+std::vector<IRenderPass*> DeferredRenderPipeline::SetSunLight(bool on, const SunSettings& sun) {
+    if (mPasses.empty()) throw HipException("DeferredRenderPipeline::SetSunLight: Setup() first");
+    if (mSunPending) throw HipException("DeferredRenderPipeline::SetSunLight: CommitSunLight or RollbackSunLight first");
+    // everything that can refuse comes before anything is changed
+    const double x = sun.Direction[0], y = sun.Direction[1], z = sun.Direction[2], len = std::sqrt((x * x + y * y) + z * z);
+    if (on && (!(len > 0.0) || !std::isfinite(len))) throw HipException("SetSunLight: the direction is zero or not finite");
+    // the passes the frame graph still points at stay alive (and the settings they read stay as they are) until CommitSunLight
+    mOldSunShadowPass = std::move(mSunShadowPass);
+    mOldSunLightPass = std::move(mSunLightPass);
+    mOldSun = mSun;
+    mSunPending = true;
+    mBloomPass->ClearRunAfter();
+    if (on) {
+        const uint64_t serial = mSun.Serial + 1;
+        mSun = sun;
+        mSun.Serial = serial;
+        mSun.Direction[0] = (float)(x / len); mSun.Direction[1] = (float)(y / len); mSun.Direction[2] = (float)(z / len);
+        if (mSun.Shadows) mSunShadowPass = std::make_unique<SunShadowPass>(mGBufferPass.get(), &mSun);
+        mSunLightPass = std::make_unique<SunLightPass>(&mSun, mSun.Shadows);
+        mBloomPass->RunAfter(mSunLightPass.get());
+    }
+    return Compose();
+}
+
+void DeferredRenderPipeline::CommitSunLight() {
+    mOldSunShadowPass.reset();
+    mOldSunLightPass.reset();
+    mSunPending = false;
+}
+
+std::vector<IRenderPass*> DeferredRenderPipeline::RollbackSunLight() {
+    if (mSunPending) {
+        mSunShadowPass = std::move(mOldSunShadowPass);
+        mSunLightPass = std::move(mOldSunLightPass);
+        mSun = mOldSun;
+        mBloomPass->ClearRunAfter();
+        if (mSunLightPass) mBloomPass->RunAfter(mSunLightPass.get());
+        mSunPending = false;
+    }
+    return Compose();
 }
 
 std::vector<IRenderPass*> DeferredRenderPipeline::SetAntiAliasing(bool on) {
@@ -39,9 +94,7 @@ std::vector<IRenderPass*> DeferredRenderPipeline::SetAntiAliasing(bool on) {
     if (on && !mAntiAliasPass) mAntiAliasPass = std::make_unique<AntiAliasPass>();
     mAntiAliasing = on;
     mPresentPass->SetFinalTexture(on ? DeferredPipelineResource::AntiAliasedTexture : DeferredPipelineResource::ToneMappedTexture);
-    std::vector<IRenderPass*> passes = mPasses;
-    if (on) passes.insert(passes.end() - 1, mAntiAliasPass.get());   // in front of Present, the list's last
-    return passes;
+    return Compose();
 }
 
 // ----------------------------------------------------------------------------------- IBL precompute
@@ -156,6 +209,7 @@ void GBufferPass::UploadMeshes(FGContext* context, MeshSource& meshes, uint32 w,
                                          (const pbr_draw*)mDraws->DevicePtr(), (uint32)meshes.Draws.size(), (pbr_aabb*)mBounds->DevicePtr());
     }
     meshes.Dirty = false;
+    mUploads++;
 }
 
 void GBufferPass::CullingStatus(uint32_t out[4]) const {
@@ -364,6 +418,111 @@ void AntiAliasPass::Execute(FGContext* context) {
     auto* input_tex = As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::ToneMappedTexture));
     mAntiAliasRender.SetTexture("InputTexture", input_tex);
     context->CommandList->DrawScreen(&mAntiAliasRender);
+}
+
+// ----------------------------------------------------------------------------------- sun light (not in the reference)
+SunShadowPass::SunShadowPass(const GBufferPass* gbuffer, SunSettings* sun) : mGBuffer(gbuffer), mSun(sun) {
+    // declared to the frame graph by FrameGraph::Recompile (SunShadowPass::Target), not through the process-wide description table
+    WriteResource(DeferredPipelineResource::SunShadowDepth);
+    RunAfter(gbuffer);   // GBufferPass uploads the meshes this pass rasterizes
+    mShadingState.SetShader("gbuffer.hlsl", false);
+}
+
+bool SunShadowPass::WorldBox(const MeshSource& meshes, pbr_aabb* out) {
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    bool any = false;
+    const size_t n_idx = meshes.Indices.size(), n_vtx = meshes.Vertices.size();
+    for (const pbr_draw& d : meshes.Draws) {
+        if (d.index_count < 3 || (uint64_t)d.first_index + d.index_count > n_idx) continue;
+        float mn[3], mx[3];
+        bool valid = false;
+        for (uint32 t = 0; t < d.index_count / 3u; t++) {
+            int64_t vi[3];
+            bool ok = true;
+            for (int k = 0; k < 3; k++) {
+                vi[k] = (int64_t)meshes.Indices[d.first_index + 3u * t + k] + d.base_vertex;
+                ok = ok && vi[k] >= 0 && vi[k] < (int64_t)n_vtx;
+            }
+            if (!ok) continue;
+            for (int k = 0; k < 3; k++)
+                for (int c = 0; c < 3; c++) {
+                    const float p = meshes.Vertices[(size_t)vi[k]].position[c];
+                    if (p != p) continue;
+                    if (!valid) { for (int q = 0; q < 3; q++) { mn[q] = FLT_MAX; mx[q] = -FLT_MAX; } valid = true; }
+                    if (p < mn[c]) mn[c] = p;
+                    if (p > mx[c]) mx[c] = p;
+                }
+        }
+        if (!valid || mn[0] > mx[0] || mn[1] > mx[1] || mn[2] > mx[2]) continue;
+        for (int corner = 0; corner < 8; corner++) {
+            const double x = (corner & 1) ? mx[0] : mn[0], y = (corner & 2) ? mx[1] : mn[1], z = (corner & 4) ? mx[2] : mn[2];
+            for (int r = 0; r < 3; r++) {
+                const float* m = d.Model + 4 * r;
+                const double w = (((double)m[0] * x + (double)m[1] * y) + (double)m[2] * z) + (double)m[3];
+                lo[r] = any ? std::min(lo[r], w) : w;
+                hi[r] = any ? std::max(hi[r], w) : w;
+            }
+            any = true;
+        }
+    }
+    if (!any) return false;
+    for (int r = 0; r < 3; r++) {
+        out->min[r] = std::nextafterf((float)lo[r], -INFINITY);
+        out->max[r] = std::nextafterf((float)hi[r], INFINITY);
+    }
+    return true;
+}
+
+void SunShadowPass::Execute(FGContext* context) {
+    MeshSource& meshes = context->Scene->Meshes();
+    if (meshes.Empty()) throw HipException("SunShadowPass: a shadowed sun needs meshes (pbrh_set_meshes); set the sun without shadows for uploaded planes");
+    if (mUploadsSeen == mGBuffer->Uploads() && mSerialSeen == mSun->Serial) return;   // the map on the device is this scene's under this sun
+    PIXScope(context->CommandList, "Sun Shadow Pass");
+    auto* target = As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::SunShadowDepth));
+    const uint32 n = target->Width();
+    if (context->CommandList->FramesInFlight() > 1) context->CommandList->WaitIdle();   // earlier frames still read the map
+    pbr_aabb box;
+    if (!WorldBox(meshes, &box)) throw HipException("SunShadowPass: the meshes hold no valid triangle to fit the light's camera around");
+    pbr_global light_g;
+    if (pbr_sun_fit(mSun->Direction, &box, n, n, &light_g, mSun->LightViewProj) != PBR_OK) throw HipException("SunShadowPass: pbr_sun_fit refused the box or the map size");
+    const size_t plane = (size_t)n * n * 4, scratch = pbr_gbuffer_raster_scratch_bytes(n, n, mGBuffer->MaxTriangles());
+    if (3 * plane > 0xffffffffu || scratch > 0xffffffffu) throw HipException("SunShadowPass: shadow raster buffers larger than 4 GiB");
+    if (!mPlanes || mPlanes->Size() != 3 * plane) mPlanes = std::make_unique<DeviceStructuredBuffer>((uint32)(3 * plane), 4);
+    if (!mRasterScratch || mRasterScratch->Size() != scratch) mRasterScratch = std::make_unique<DeviceStructuredBuffer>((uint32)scratch, 4);
+    uint32_t* p = (uint32_t*)mPlanes->DevicePtr();
+    context->CommandList->RasterShadowMap(&mShadingState, &light_g, mGBuffer->Vertices(), (uint32)meshes.Vertices.size(), mGBuffer->Indices(),
+                                          (uint32)meshes.Indices.size(), mGBuffer->Draws(), (uint32)meshes.Draws.size(), mGBuffer->MaxTriangles(),
+                                          p, p + (size_t)n * n, p + 2 * (size_t)n * n, target, mRasterScratch->DevicePtr(), mRasterScratch->Size());
+    mUploadsSeen = mGBuffer->Uploads();
+    mSerialSeen = mSun->Serial;
+}
+
+SunLightPass::SunLightPass(SunSettings* sun, bool shadows) : mSun(sun), mShadows(shadows) {
+    ReadResource(DeferredPipelineResource::GBufferA);
+    ReadResource(DeferredPipelineResource::GBufferB);
+    ReadResource(DeferredPipelineResource::GBufferC);
+    // an input that DeferredShading and the sky resolve write: this pass runs after both (and after GBuffer)
+    ReadResource(DeferredPipelineResource::DepthStencil);
+    if (shadows) ReadResource(DeferredPipelineResource::SunShadowDepth);
+    // read-modify-write, declared as a write only: a read would put the pass behind Bloom, the target's last writer.  Bloom, which
+    // declares no reads, is held behind this pass by an order edge (DeferredRenderPipeline::SetSunLight)
+    WriteResource(DeferredPipelineResource::DeferredShadingRT);
+    mShadingState.SetShader(Shader, false);
+}
+
+void SunLightPass::Execute(FGContext* context) {
+    PIXScope(context->CommandList, "Sun Light Pass");
+    auto tex = [&](FGResourceId id) { return As<DeviceTexture>(GetTransientResource(context, id)); };
+    mShadingState.SetTexture("GBufferA", tex(DeferredPipelineResource::GBufferA));
+    mShadingState.SetTexture("GBufferB", tex(DeferredPipelineResource::GBufferB));
+    mShadingState.SetTexture("GBufferC", tex(DeferredPipelineResource::GBufferC));
+    mShadingState.SetTexture("DepthStencil", tex(DeferredPipelineResource::DepthStencil));
+    pbr_sun sun{};
+    for (int k = 0; k < 3; k++) { sun.Direction[k] = mSun->Direction[k]; sun.Luminance[k] = mSun->Luminance[k]; }
+    for (int k = 0; k < 16; k++) sun.LightViewProj[k] = mShadows ? mSun->LightViewProj[k] : (k % 5 == 0 ? 1.0f : 0.0f);
+    sun.bias_const = mSun->BiasConst; sun.bias_slope = mSun->BiasSlope; sun.pcf = mSun->Pcf;
+    mShadingState.SetConstantBuffer(sun);
+    context->CommandList->SunLight(&mShadingState, mShadows ? As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::SunShadowDepth)) : nullptr);
 }
 
 // ----------------------------------------------------------------------------------- bloom

@@ -31,6 +31,8 @@ struct DeferredPipelineResource {   // DeferredPipeline.h:9-32
     inline static FGResourceId AverageLuminance = FGResourceIDs::Instance()->NameToID("AverageLuminance");
     // not in the reference: the target of AntiAliasPass, declared (and allocated) only while anti-aliasing is on
     inline static FGResourceId AntiAliasedTexture = FGResourceIDs::Instance()->NameToID("AntiAliasedTexture");
+    // not in the reference: the sun's shadow map, the depth-stencil target of SunShadowPass; declared only while a shadowed sun is set
+    inline static FGResourceId SunShadowDepth = FGResourceIDs::Instance()->NameToID("SunShadowDepth");
 };
 
 // render size (GD3D12Device->Width()/Height() in the reference; App.h:77-78 defaults 1440x960)
@@ -73,7 +75,14 @@ public:
     // mCullingStatus (DeferredPipeline.h:96-100) of the last Execute with model culling on, read back from the device here (the
     // caller has drained the command list): NumDrawCall, NumCulled, triangles drawn, triangles culled; zeros without culling
     void CullingStatus(uint32_t out[4]) const;
+    // the device copies of the scene's meshes, for SunShadowPass (which runs after this pass); Uploads() counts UploadMeshes calls
+    const pbr_vertex* Vertices() const { return mVertices ? (const pbr_vertex*)mVertices->DevicePtr() : nullptr; }
+    const uint32_t* Indices() const { return mIndices ? (const uint32_t*)mIndices->DevicePtr() : nullptr; }
+    const pbr_draw* Draws() const { return mDraws ? (const pbr_draw*)mDraws->DevicePtr() : nullptr; }
+    uint32 MaxTriangles() const { return mMaxTriangles; }
+    uint64_t Uploads() const { return mUploads; }
 protected:
+    uint64_t mUploads = 0;
     void UploadMeshes(FGContext* context, MeshSource& meshes, uint32 w, uint32 h);
     ShadingState mShadingState;
     std::unique_ptr<DeviceStructuredBuffer> mMaterialPlanes;   // device copy of GBufferSource::M0..M2
@@ -177,6 +186,53 @@ protected:
     ShadingState mAntiAliasRender;
 };
 
+// Not in the reference, which computes a directional light (deferred_shading.hlsl:144-156) and never adds it, and has no shadows: the sun
+// of pbr_sun_light.  SunShadowPass rasterizes the scene's meshes (GBufferPass's device copies: it runs after that pass) under the
+// orthographic light camera pbr_sun_fit fits around the draws' world boxes, into the frame-graph texture SunShadowDepth — once per
+// mesh upload / sun change, not per frame; SunLightPass adds the light to DeferredShadingRT after DeferredShading and the sky resolve
+// and before Bloom.  Both are part of the pipeline only while DeferredRenderPipeline::SetSunLight has a sun.
+struct SunSettings {
+    float Direction[3] = {0, 1, 0};   // normalised by SetSunLight (double, rounded once)
+    float Luminance[3] = {0, 0, 0};
+    uint32 MapSize = 2048, Pcf = 3;
+    float BiasConst = 0, BiasSlope = 0;
+    bool Shadows = true;
+    uint64_t Serial = 0;              // bumped by every SetSunLight: the map is rasterized again
+    float LightViewProj[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // written by SunShadowPass
+};
+
+class SunShadowPass : public GraphicsPass {
+public:
+    SunShadowPass(const GBufferPass* gbuffer, SunSettings* sun);
+    const char* Name() const override { return "SunShadow"; }
+    void Execute(FGContext* context) override;
+    static FGTransientTextureDescription Target(uint32 map_size) {
+        return FGTransientTextureDescription{(uint16)map_size, (uint16)map_size, 1, ETextureFormat_DepthStencil, ETexture2DFlag_AllowDepthStencil};
+    }
+    // the union of the draws' world boxes (the exact local min / max of each draw's valid triangles through its Model, in double,
+    // rounded outwards): scene.world_box of the Python side, operation for operation.  false: no valid triangle
+    static bool WorldBox(const MeshSource& meshes, pbr_aabb* out);
+protected:
+    const GBufferPass* mGBuffer;
+    SunSettings* mSun;
+    ShadingState mShadingState;
+    // the raster's scratch and the A / B / C planes it writes and nobody reads (17 B per texel with the target's depth and stencil)
+    std::unique_ptr<DeviceStructuredBuffer> mPlanes, mRasterScratch;
+    uint64_t mUploadsSeen = ~0ull, mSerialSeen = ~0ull;
+};
+
+class SunLightPass : public GraphicsPass {
+public:
+    static constexpr const char* Shader = "sun_light.hip";   // the binding-table row's name: no shader file of the reference
+    SunLightPass(SunSettings* sun, bool shadows);
+    const char* Name() const override { return "SunLight"; }
+    void Execute(FGContext* context) override;
+protected:
+    SunSettings* mSun;
+    bool mShadows;
+    ShadingState mShadingState;
+};
+
 class DeferredRenderPipeline : public IRenderPipeline {   // :463-481, DeferredPipeline.cpp:17-44
 public:
     DeferredRenderPipeline(RenderSize size, uint32 env_size = PreFilterEnvMapPass::PreFilterEnvMapSize, uint32 lut_res = PrecomputeBRDFPass::TextureResolution)
@@ -191,6 +247,16 @@ public:
     // texture it shows; for FrameGraph::Recompile, after Setup.  Off (the default): exactly Setup()'s list.
     std::vector<IRenderPass*> SetAntiAliasing(bool on);
     bool AntiAliasing() const { return mAntiAliasing; }
+    // The pass list with (on) or without SunShadowPass (shadows) and SunLightPass, for FrameGraph::Recompile; Bloom gets its order edge
+    // behind SunLight, or loses it.  Off (the default): exactly Setup()'s list (with AntiAliasPass if that is on).
+    // A failed call changes nothing.  A successful one keeps the passes it replaces alive — the frame graph still points at them —
+    // until the caller has recompiled the graph with the returned list and calls CommitSunLight; if the recompile fails,
+    // RollbackSunLight puts the earlier sun (or none) back and returns its list to recompile with.
+    std::vector<IRenderPass*> SetSunLight(bool on, const SunSettings& sun = SunSettings{});
+    void CommitSunLight();
+    std::vector<IRenderPass*> RollbackSunLight();
+    bool SunLight() const { return mSunLightPass != nullptr; }
+    const SunSettings& Sun() const { return mSun; }
     RenderSize Size() const { return mSize; }
 
     std::unique_ptr<GBufferPass> mGBufferPass;
@@ -203,8 +269,15 @@ public:
     std::unique_ptr<ToneMappingPass> mToneMappingPass;
     std::unique_ptr<ClusteredPass> mClusteredPass;
     std::unique_ptr<AntiAliasPass> mAntiAliasPass;   // null until anti-aliasing is first turned on
+    std::unique_ptr<SunShadowPass> mSunShadowPass;   // null without a shadowed sun
+    std::unique_ptr<SunLightPass> mSunLightPass;     // null without a sun
 private:
     std::vector<IRenderPass*> mPasses;   // Setup()'s list
+    std::vector<IRenderPass*> Compose() const;   // Setup()'s list + the optional passes that are on, Present last
+    SunSettings mSun, mOldSun;
+    std::unique_ptr<SunShadowPass> mOldSunShadowPass;   // between SetSunLight and CommitSunLight / RollbackSunLight
+    std::unique_ptr<SunLightPass> mOldSunLightPass;
+    bool mSunPending = false;
     bool mAntiAliasing = false;
     RenderSize mSize;
     uint32 mEnvSize, mLutRes;

@@ -14,6 +14,8 @@ namespace MRendererHip {
 
 bool FGExecutionParser::IsDependsOn(const IRenderPass* lhs, const IRenderPass* rhs) {
     if (lhs == rhs) return false;
+    for (const IRenderPass* before : lhs->GetRunAfter())   // an explicit edge (IRenderPass::RunAfter): none in the reference's list
+        if (before == rhs) return true;
     for (FGResourceId in : lhs->GetInputResources())
         for (FGResourceId out : rhs->GetOutputResources())
             if (in == out) return true;
@@ -95,6 +97,8 @@ void FrameGraph::Recompile(const std::vector<IRenderPass*>& passes, const Declar
     for (auto& lc : mParser.GetResourceLifecycle())
         if (lc.Valid) mFGResourceAllocator.AllocateIfMissing(lc.ResourceId, Describe(lc.ResourceId));
 }
+
+void FrameGraph::Reallocate(FGResourceId id) { mFGResourceAllocator.AllocateTransientResource(id, Describe(id)); }
 
 void FrameGraph::DoubleBufferResources(const std::vector<FGResourceId>& ids) {
     for (FGResourceId id : ids) mFGResourceAllocator.DoubleBuffer(id, Describe(id));

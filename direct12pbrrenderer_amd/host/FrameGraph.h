@@ -34,6 +34,11 @@ public:
     // singleton that another renderer may have reset since).
     using Declared = std::vector<std::pair<FGResourceId, FGResourceDescriptionTable::Description>>;
     void Recompile(const std::vector<IRenderPass*>& passes, const Declared& declared);
+    // a transient resource whose description Recompile replaced (the sun's shadow map at another size) is allocated anew
+    void Reallocate(FGResourceId id);
+    // a transient resource no pass of the graph uses any more is freed (nullptr from FindTransient afterwards)
+    void Release(FGResourceId id) { mFGResourceAllocator.Release(id); }
+    IDeviceResource* FindTransient(FGResourceId id) { return mFGResourceAllocator.Allocated(id) ? mFGResourceAllocator.GetResource(id) : nullptr; }
     void Execute(HipCommandList* cmd, Scene* scene, Camera* camera);
     // Frames alternate between two instances of these transient resources (the overlapped frame tail: the HDR target and the
     // luminance histogram of frame i are still read on the side stream while frame i + 1 is shaded).  Call after Compile.

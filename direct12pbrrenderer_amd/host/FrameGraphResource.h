@@ -276,6 +276,9 @@ public:
     void AllocateIfMissing(FGResourceId id, const FGResourceDescriptionTable::Description& d) {
         if (!mTransient.at(id)) mTransient[id] = Make(d);
     }
+    // a resource no pass of the recompiled graph uses any more (the sun's shadow map after the sun is cleared) gives its memory back
+    void Release(FGResourceId id) { mTransient.at(id) = nullptr; mSecond.at(id) = nullptr; }
+    bool Allocated(FGResourceId id) const { return mTransient.at(id) != nullptr; }
     // A second instance of a transient resource: frames alternate between the two (SetParity), so that work of frame i that is
     // still in flight on another stream — the overlapped frame tail — does not see frame i + 1 write the same memory.  Not in
     // the reference (its frames are strictly serial).

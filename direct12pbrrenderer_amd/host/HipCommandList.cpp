@@ -29,6 +29,8 @@ static const std::vector<ShaderReflection>& Reflections() {
         {"hdr_tone_mapping.hlsl", false, {"LuminanceTexture"}, {}, {}, {"AverageLuminance"}, 0},
         // not a shader file of the reference (it has no anti-aliasing): AntiAliasPass's row, the integer edge filter of csrc/fxaa.hip
         {"fxaa.hip", false, {"InputTexture"}, {}, {}, {}, 0},
+        // not a shader file of the reference (it drops its directional light): SunLightPass's row, pbr_sun_light of csrc/sun.hip
+        {"sun_light.hip", false, {"GBufferA", "GBufferB", "GBufferC", "DepthStencil"}, {}, {}, {}, sizeof(pbr_sun)},
         // raster shaders of the reference: out of scope; known so that SetShader succeeds
         {"gbuffer.hlsl", false, {}, {}, {}, {}, 0},
         {"skybox.hlsl", false, {"SkyBox"}, {}, {}, {}, 0},
@@ -613,6 +615,43 @@ void HipCommandList::RasterGBuffer(ShadingState* s, const pbr_vertex* vertices, 
     Check(pbr_gbuffer_raster(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
                              (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(), ds->DepthPlane(),
                              ds->StencilPlane(), w, scratch, scratch_bytes), "pbr_gbuffer_raster");
+}
+
+void HipCommandList::RasterShadowMap(ShadingState* s, const pbr_global* light_g, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices,
+                                     uint32 n_indices, const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, uint32_t* a, uint32_t* b,
+                                     uint32_t* c, DeviceTexture2D* target, void* scratch, size_t scratch_bytes) {
+    if (!s || s->File() != "gbuffer.hlsl") throw HipException("RasterShadowMap: gbuffer.hlsl shading state expected");
+    if (!light_g || !vertices || !indices || !draws || !a || !b || !c || !target || !target->StencilPlane())
+        throw HipException("RasterShadowMap: null buffer, or the target is no depth-stencil texture");
+    mDispatchCount++;
+    FlushPendingBloom();
+    const uint32 w = target->Width(), h = target->Height();
+    const pbr_tile tile{0, 0, w, h, w, h};   // the whole map, whatever tile of the frame this device draws
+    Check(pbr_gbuffer_raster(mCtx, light_g, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, a, b, c,
+                             target->DepthPlane(), target->StencilPlane(), w, scratch, scratch_bytes), "pbr_gbuffer_raster (shadow map)");
+}
+
+void HipCommandList::SunLight(ShadingState* s, DeviceTexture2D* shadow_map) {
+    if (!s || s->File() != "sun_light.hip") throw HipException("SunLight: sun_light.hip shading state expected");
+    mDispatchCount++;
+    FlushPendingBloom();
+    if (!mRenderTarget) throw HipException("SunLight: no render target bound (FrameGraph::PreparePass)");
+    auto tex = [&](const char* n) { return dynamic_cast<DeviceTexture2D*>(s->Texture(n).Texture); };
+    DeviceTexture2D *a = tex("GBufferA"), *b = tex("GBufferB"), *c = tex("GBufferC"), *ds = tex("DepthStencil");
+    if (!a || !b || !c || !ds) throw HipException("sun_light: bad texture bindings");
+    const uint32 w = mRenderTarget->Width(), h = mRenderTarget->Height();
+    const pbr_gbuffer gb{(const uint32_t*)a->DevicePtr(), (const uint32_t*)b->DevicePtr(), (const uint32_t*)c->DevicePtr(), ds->DepthPlane(),
+                         ds->StencilPlane(), w};
+    const pbr_tile tile = mTile.w ? mTile : pbr_tile{0, 0, w, h, w, h};
+    const pbr_sun& sun = s->Constants<pbr_sun>();
+    pbr_sun_desc d{};
+    d.g = &mGlobal; d.tile = &tile; d.gb = &gb; d.sun = &sun;
+    d.hdr = (pbr_half*)mRenderTarget->DevicePtr(); d.hdr_pitch = w;
+    if (shadow_map) {
+        d.shadow_depth = shadow_map->DepthPlane();
+        d.map_w = d.map_pitch = shadow_map->Width(); d.map_h = shadow_map->Height();
+    }
+    Check(pbr_sun_light(mCtx, &d), "pbr_sun_light");
 }
 
 void HipCommandList::DrawBounds(const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,

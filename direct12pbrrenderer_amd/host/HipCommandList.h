@@ -99,6 +99,13 @@ public:
     // DrawBounds: the draws' local boxes from the uploaded buffers (pbr_draw_bounds), not a per-frame dispatch.
     void DrawBounds(const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
                     const pbr_draw* draws, uint32 n_draws, pbr_aabb* out);
+    // SunShadowPass: pbr_gbuffer_raster of the scene's meshes under the light's camera (pbr_sun_fit's pbr_global) into a depth-stencil
+    // target of the map's size — always the whole map, in tile mode too — and three scratch colour planes nobody reads.
+    void RasterShadowMap(ShadingState* state, const pbr_global* light_g, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices,
+                         uint32 n_indices, const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, uint32_t* a, uint32_t* b, uint32_t* c,
+                         DeviceTexture2D* target, void* scratch, size_t scratch_bytes);
+    // SunLightPass: pbr_sun_light (the pbr_sun in `state`'s constants) into the bound render target; shadow_map null: no shadows
+    void SunLight(ShadingState* state, DeviceTexture2D* shadow_map);
     void Present(DeviceTexture2D* tex) { mPresented = tex; }
 
     // Pass-level entry points (not in the reference): a pass whose Execute body is a fixed sequence of dispatches can

@@ -105,6 +105,13 @@ public:
     const std::vector<FGResourceId>& GetInputResources() const { return mInputResources; }
     const std::vector<FGResourceId>& GetOutputResources() const { return mOutputResources; }
     virtual const char* Name() const = 0;
+    // An order edge no resource states (not in the reference): this pass runs after `pass`.  FGExecutionParser treats it like a read of
+    // something `pass` writes.  For passes that update a target in place BETWEEN two of its writers (SunLightPass adds to
+    // DeferredShadingRT after DeferredShading and before Bloom, which declares no reads): reading the target would order the pass
+    // behind every writer.  No pass of the reference's list has such an edge, so its order is what it was.
+    void RunAfter(const IRenderPass* pass) { if (std::find(mRunAfter.begin(), mRunAfter.end(), pass) == mRunAfter.end()) mRunAfter.push_back(pass); }
+    void ClearRunAfter() { mRunAfter.clear(); }
+    const std::vector<const IRenderPass*>& GetRunAfter() const { return mRunAfter; }
 
 protected:
     void ReadResource(FGResourceId id) {
@@ -134,6 +141,7 @@ protected:
 
     std::vector<FGResourceId> mInputResources;
     std::vector<FGResourceId> mOutputResources;
+    std::vector<const IRenderPass*> mRunAfter;
 };
 
 class PresentPass : public IRenderPass {

@@ -529,6 +529,7 @@ int pbrh_set_tile(pbrh_renderer* r, uint32_t x0, uint32_t y0, uint32_t full_w, u
                   uint32_t ix, uint32_t iy, uint32_t iw, uint32_t ih) {
     return guarded(r, [&] {
         if (r->pipeline->AntiAliasing()) throw HipException("pbrh_set_tile: anti-aliasing is on, and it filters whole frames only");
+        if (r->pipeline->SunLight()) throw HipException("pbrh_set_tile: a sun light is set, and the host graph's sun pass runs on whole frames only");
         if (x0 + r->width > full_w || y0 + r->height > full_h) throw HipException("pbrh_set_tile: the target does not fit the frame");
         if (iw == 0 || ih == 0 || ix + iw > r->width || iy + ih > r->height) throw HipException("pbrh_set_tile: interior outside the target");
         HipCommandList* cmd = r->scheduler->CommandList();
@@ -580,6 +581,7 @@ int pbrh_set_tail_overlap(pbrh_renderer* r, int on) {
     return guarded(r, [&] {
         HipCommandList* cmd = r->scheduler->CommandList();
         if (on && r->pipeline->AntiAliasing()) throw HipException("pbrh_set_tail_overlap: anti-aliasing is on, and it follows the tone-map on the frame's own stream");
+        if (on && r->pipeline->SunLight()) throw HipException("pbrh_set_tail_overlap: a sun light is set; clear it first");
         cmd->SetTailOverlap(on);
         if (on) r->scheduler->GetFrameGraph()->DoubleBufferResources({DeferredPipelineResource::DeferredShadingRT, DeferredPipelineResource::LuminanceHistogram});
     });
@@ -620,6 +622,59 @@ int pbrh_set_antialiasing(pbrh_renderer* r, int on) {
         const std::vector<IRenderPass*> passes = r->pipeline->SetAntiAliasing(on != 0);
         r->scheduler->GetFrameGraph()->Recompile(passes, {{DeferredPipelineResource::AntiAliasedTexture, AntiAliasPass::Target(r->pipeline->Size())}});
     });
+}
+
+// SunShadowPass (with shadows; needs pbrh_set_meshes) after GBuffer and SunLightPass between DeferredShading and Bloom; off (the
+// default, and after pbrh_clear_sun_light) the pass list, the execution order and every resource are what they are without these
+// calls.  Refused for a tile of a larger frame and with an overlapped tail (pbr_host.h says why).
+static void set_sun(pbrh_renderer* r, bool on, const SunSettings& sun) {
+    HipCommandList* cmd = r->scheduler->CommandList();
+    if (on && (r->tile || cmd->TileSet())) throw HipException("pbrh_set_sun_light: this renderer draws a tile of a larger frame; the sun pass of the host graph runs on whole frames only");
+    if (on && cmd->TailOverlap()) throw HipException("pbrh_set_sun_light: the overlapped tail double-buffers the HDR target; turn it off first");
+    if (!on && !r->pipeline->SunLight()) return;
+    cmd->WaitIdle();
+    FrameGraph* graph = r->scheduler->GetFrameGraph();
+    const FGResourceId map = DeferredPipelineResource::SunShadowDepth;
+    const bool had_map = r->pipeline->SunLight() && r->pipeline->Sun().Shadows;
+    const uint32 old_size = r->pipeline->Sun().MapSize;
+    const std::vector<IRenderPass*> passes = r->pipeline->SetSunLight(on, sun);   // refuses before it changes anything
+    try {
+        FrameGraph::Declared declared;
+        if (on && sun.Shadows) declared.push_back({map, SunShadowPass::Target(sun.MapSize)});
+        graph->Recompile(passes, declared);
+        // the map a pass of the new graph writes has the size asked for now, whatever an earlier sun left; without such a pass it is freed
+        auto* tex = dynamic_cast<DeviceTexture2D*>(graph->FindTransient(map));
+        if (!(on && sun.Shadows)) graph->Release(map);
+        else if (!tex || tex->Width() != sun.MapSize || tex->Height() != sun.MapSize) graph->Reallocate(map);
+    } catch (...) {   // the earlier graph, with the passes it was parsed from (still alive) and the earlier map
+        FrameGraph::Declared before;
+        if (had_map) before.push_back({map, SunShadowPass::Target(old_size)});
+        graph->Recompile(r->pipeline->RollbackSunLight(), before);
+        throw;
+    }
+    r->pipeline->CommitSunLight();
+}
+
+int pbrh_set_sun_light(pbrh_renderer* r, const float dir[3], const float luminance[3], uint32_t map_size, uint32_t pcf, float bias_const,
+                       float bias_slope, int shadows) {
+    return guarded(r, [&] {
+        if (!dir || !luminance) throw HipException("pbrh_set_sun_light: null pointer");
+        if (pcf != 1 && pcf != 3) throw HipException("pbrh_set_sun_light: pcf must be 1 or 3");
+        if (shadows && (map_size < 3 || map_size > PBR_RASTER_MAX_SIZE)) throw HipException("pbrh_set_sun_light: map size outside [3, PBR_RASTER_MAX_SIZE]");
+        SunSettings s;
+        for (int k = 0; k < 3; k++) {
+            if (!std::isfinite(dir[k]) || !std::isfinite(luminance[k])) throw HipException("pbrh_set_sun_light: direction or luminance not finite");
+            s.Direction[k] = dir[k]; s.Luminance[k] = luminance[k];
+        }
+        if (dir[0] == 0.0f && dir[1] == 0.0f && dir[2] == 0.0f) throw HipException("pbrh_set_sun_light: the direction is zero");
+        if (!std::isfinite(bias_const) || !std::isfinite(bias_slope)) throw HipException("pbrh_set_sun_light: bias not finite");
+        s.MapSize = map_size; s.Pcf = pcf; s.BiasConst = bias_const; s.BiasSlope = bias_slope; s.Shadows = shadows != 0;
+        set_sun(r, true, s);
+    });
+}
+
+int pbrh_clear_sun_light(pbrh_renderer* r) {
+    return guarded(r, [&] { set_sun(r, false, SunSettings{}); });
 }
 
 int pbrh_set_fused(pbrh_renderer* r, int on) {

@@ -191,6 +191,23 @@ int pbrh_set_fused(pbrh_renderer* r, int on);
  * resource are those of a renderer that never heard of it.  -1 for a renderer made by pbrh_create_tile or given pbrh_set_tile (the
  * filter reads 25 pixels beyond a tile) and while the overlapped tail is on. */
 int pbrh_set_antialiasing(pbrh_renderer* r, int on);
+/* Sun light with a shadow map (not in the reference, which computes a directional light and never adds it): SunLightPass (pbr_sun_light
+ * of include/pbr_hip.h) between DeferredShading (and the sky resolve) and Bloom, adding into DeferredShadingRT; with shadows != 0 also
+ * SunShadowPass after GBuffer, which needs pbrh_set_meshes: it fits the light's orthographic camera (pbr_sun_fit) around the union of
+ * the draws' world boxes and rasterizes the meshes (pbr_gbuffer_raster, the constant-material call) into the frame-graph texture
+ * "SunShadowDepth" (map_size^2, D32 readable through pbrh_read) — once per mesh upload / pbrh_set_sun_light, not per frame; 17 B per
+ * texel with the scratch planes it ignores, 71 MB at 2048^2.  dir: world space, from the surface towards the light (normalised here);
+ * luminance: three channels; pcf 1 or 3; the biases in light-clip depth units (DeferredFrame.SUN_BIAS of the Python side: 5e-4, 4e-3).
+ * Off by default; off, and after pbrh_clear_sun_light, the execution order, the dispatch count and the resources are those of a
+ * renderer that never heard of it.  -1: a renderer made by pbrh_create_tile or given pbrh_set_tile — the kernel takes a tile and a
+ * tile would be bit-identical to the frame, but every device would rasterize the whole map and nothing here verifies that
+ * arrangement, so it is refused rather than left untested —, an overlapped tail, pcf not 1 or 3, a map size outside
+ * [3, PBR_RASTER_MAX_SIZE], non-finite arguments, a zero direction.  A refused call changes nothing: a sun set by an earlier call stays
+ * as it was, with its map.  A shadowed sun without meshes fails at the next pbrh_render.  SunShadowDepth always has the size of the
+ * last successful call; pbrh_clear_sun_light and a sun without shadows free it (and the pass's scratch planes). */
+int pbrh_set_sun_light(pbrh_renderer* r, const float dir[3], const float luminance[3], uint32_t map_size, uint32_t pcf, float bias_const,
+                       float bias_slope, int shadows);
+int pbrh_clear_sun_light(pbrh_renderer* r);
 /* the name of the frame-graph texture the present pass shows ("ToneMappedTexture"; "AntiAliasedTexture" with anti-aliasing on) */
 int pbrh_presented(pbrh_renderer* r, char* buf, size_t len);
 /* n frames; *ms_per_frame = average wall time per frame (every frame ends with the per-frame fence wait) */

@@ -15,7 +15,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from .api import PbrContext
+from .api import PbrContext, make_sun, sun_fit
+from .scene import draw_bounds, world_box
 from .structs import (AABB_DTYPE, DRAW_MAPS_DTYPE, ENV_MIPS, HISTOGRAM_BINS, MAX_VIEWS, NO_MAP, TABLES_BUILT_FRAME, TABLES_BUILT_GEOMETRY, GBuffer, Global, Tile, View)
 
 # bloom's cumulative support is ~220 full-res pixels (3 down + 3 up levels of a radius-4 kernel on
@@ -310,6 +311,9 @@ class DeferredFrame:
         self.ldr_aa = None   # the anti-aliased target: allocated by the first antialias()
         self.gb = None
         self.mesh = None
+        self.sun = None               # set_sun: the directional light pass between the shade and the bloom; None = today's frame
+        self._sun_map_stale = True
+        self._sun_planes = None
         self.tile = Tile(spec.sx0, spec.sy0, spec.sw, spec.sh, spec.full_w, spec.full_h)
         # the shade tables: the geometry half once per spec, the frame half by every clustered(); the folded shade reads its block
         # prologue from them (tabled=False: the folded shade derives it per block, the same bits)
@@ -383,6 +387,13 @@ class DeferredFrame:
                      "indices": ctx.upload(np.ascontiguousarray(indices, dtype=np.uint32)), "n_indices": len(indices),
                      "draws": ctx.upload(draws), "n_draws": len(draws), "max_triangles": n_tris,
                      "scratch": (ctx.alloc_textured_raster_scratch if textured else ctx.alloc_raster_scratch)(s.sw, s.sh, n_tris)}
+        # For the sun's light camera (set_sun fits it around the draws' world boxes) the frame keeps REFERENCES to the caller's host
+        # arrays — no copy where they already are numpy arrays of the records' types, which is what scene.MeshScene.arrays() hands
+        # out — so a frame that never sets a sun holds the caller's arrays alive and nothing more; the world box is computed from
+        # them by the first shadowed sun, once per set_meshes (_sun_world_box).
+        self.mesh["host"] = (np.asarray(vertices), np.asarray(indices), draws, None if bounds is None else np.asarray(bounds, dtype=AABB_DTYPE))
+        self.mesh["world_box"] = None
+        self._sun_map_stale = True
         if textured:
             self.mesh["maps"] = ctx.upload(np.ascontiguousarray(maps, dtype=DRAW_MAPS_DTYPE))
             pairs = list(textures or [])
@@ -417,6 +428,95 @@ class DeferredFrame:
             self.ctx.gbuffer_raster_textured(*args, m["maps"], m["textures"])
         else:
             self.ctx.gbuffer_raster(*args)
+
+    # Default shadow bias (bias_const, bias_slope), in light-clip depth units, for the default 2048^2 map.  A receiver plane tilted by
+    # theta against the light changes its light depth by tan(theta) per unit across the map, and pcf 3 compares against taps up to two
+    # texels away: acne needs bias > ~1.5 (E / 2048) tan(theta) / span for a fitted box of extent E and depth span `span`.  1 - NdotL
+    # grows with the tilt (0.17 at 34 degrees, 0.5 at 60), so the slope term carries most of it and the constant stays small, which
+    # keeps peter-panning (bias x span in world units of depth) small on surfaces that face the light.  Looked at on the tests' ground-
+    # and-box scene (tests/test_gpu_sun_frame.py: sun 34 degrees off the ground's normal, E = 13.5, span = 9.4) with the float64 rule
+    # at a 256^2 map, whose texel is 8 x the default map's: a total bias of 5.4e-3 still leaves acne on 4 314 of 9 377 open ground
+    # pixels (vis down to 0.85), 8e-3 leaves none; that is 1.0e-3 at 2048^2.  These defaults give 1.2e-3 there and 2.5e-3 at 60
+    # degrees, where the same estimate asks for 2.5e-3; the contact shadow then starts 1 cm from a caster's foot on that scene.
+    SUN_BIAS = (5e-4, 4e-3)
+
+    def set_sun(self, direction, luminance=100.0, map_size=2048, pcf=3, bias=SUN_BIAS, shadows=True, depth_map=None, light_view_proj=None):
+        """A directional light with a shadow map, added to the HDR target after the shade (and the sky resolve) and before the bloom
+        (pbr_sun_light); set_sun(None) switches it off, and without a sun every launch and output bit of the frame is what it was.
+        direction: world space, from the surface towards the light (normalised here); luminance: a scalar or three channels (the
+        reference's unused directional light is direction (1, 1, 1), 100 nits).  shadows with meshes (set_meshes): the light's
+        orthographic camera is fitted (pbr_sun_fit) around the union of the draws' world boxes and the next render() rasterizes the
+        map_size^2 shadow map with pbr_gbuffer_raster — once per set_meshes / set_sun, not per frame; refresh_shadow_map() asks for
+        it again (moved draws).  The pass writes a map-sized scratch G-buffer whose A / B / C / stencil planes are ignored: 17 bytes
+        per texel, 71 MB at 2048^2.  Without meshes (uploaded planes) shadows must be False, or the map is handed in: depth_map =
+        (device float32 tensor, map_w, map_h, map_pitch) with its light_view_proj (16 floats)."""
+        if direction is None:
+            self.sun = None
+            return
+        if self.split is not None:
+            raise ValueError("set_sun: the overlapped halo frame interleaves the shade with the bloom; use the plain frame order")
+        sun = {"direction": np.asarray(direction, dtype=np.float64), "luminance": luminance, "pcf": int(pcf), "bias": (float(bias[0]), float(bias[1])),
+               "map": None, "map_size": int(map_size), "fit": False, "struct": None}
+        if depth_map is not None:
+            if light_view_proj is None:
+                raise ValueError("set_sun: a depth map needs its light_view_proj")
+            sun["map"] = tuple(depth_map)
+            sun["struct"] = make_sun(sun["direction"], luminance, light_view_proj, sun["bias"], pcf)
+        elif shadows:
+            if self.mesh is None:
+                raise ValueError("set_sun: shadows need meshes (set_meshes) or an explicit depth_map; pass shadows=False for an unshadowed sun")
+            sun["fit"] = True
+        else:
+            sun["struct"] = make_sun(sun["direction"], luminance, None, sun["bias"], pcf)
+        self.sun = sun
+        self._sun_map_stale = True
+
+    def refresh_shadow_map(self):
+        """the next render() rasterizes the sun's shadow map again (the draws moved)"""
+        self._sun_map_stale = True
+
+    def shadow_map(self):
+        """(depth tensor, map_w, map_h, map_pitch, light_view_proj as 16 floats) of the sun's shadow map as the last sun_light() used
+        it; None without a map"""
+        if self.sun is None or self.sun["map"] is None:
+            return None
+        return (*self.sun["map"], list(self.sun["struct"].LightViewProj))
+
+    def shadow_pass(self):
+        """fit the light camera around the draws' world boxes and rasterize the shadow map (the unculled constant-material raster)"""
+        sun, m, ctx = self.sun, self.mesh, self.ctx
+        if m["world_box"] is None:      # once per set_meshes: the host twin of pbr_draw_bounds walks every index
+            vertices, indices, draws, bounds = m["host"]
+            m["world_box"] = world_box(draws, bounds if bounds is not None else draw_bounds(vertices, indices, draws))
+            if m["world_box"] is None:
+                raise ValueError("set_sun: the meshes hold no valid triangle to fit the light's camera around")
+        box = m["world_box"]
+        n = sun["map_size"]
+        d = sun["direction"] / np.sqrt(float((sun["direction"] ** 2).sum()))
+        light_g, lvp = sun_fit(d.astype(np.float32), box[0], box[1], n, n)
+        # the map-sized scratch G-buffer and raster scratch live on the FRAME, keyed by map size and triangle count: another luminance,
+        # bias or direction allocates nothing.  A / B / C / stencil and the scratch are kept for the next raster (refresh_shadow_map)
+        sm = self._sun_planes
+        if sm is None or sm["n"] != n or sm["tris"] != m["max_triangles"]:
+            sm = {"n": n, "tris": m["max_triangles"], "A": ctx.zeros((n, n), torch.int32), "B": ctx.zeros((n, n), torch.int32),
+                  "C": ctx.zeros((n, n), torch.int32), "depth": ctx.zeros((n, n), torch.float32), "stencil": ctx.zeros((n, n), torch.uint8),
+                  "scratch": ctx.alloc_raster_scratch(n, n, m["max_triangles"])}
+            self._sun_planes = sm
+        ctx.gbuffer_raster(light_g, Tile(0, 0, n, n, n, n), m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"], m["n_draws"],
+                           m["max_triangles"], sm["A"], sm["B"], sm["C"], sm["depth"], sm["stencil"], n, sm["scratch"])
+        sun["light_g"], sun["map"] = light_g, (sm["depth"], n, n, n)
+        sun["struct"] = make_sun(sun["direction"], sun["luminance"], lvp, sun["bias"], sun["pcf"])
+
+    def sun_light(self):
+        """pbr_sun_light on the shaded rectangle (after shade(), before the bloom); the shadow map first if it is stale"""
+        sun, s = self.sun, self.spec
+        if sun["fit"] and self._sun_map_stale:
+            if self.mesh is None:
+                raise ValueError("sun_light: the meshes the shadow map was to be made from were replaced by uploaded planes")
+            self.shadow_pass()
+        self._sun_map_stale = False
+        depth, mw, mh, mp = sun["map"] if sun["map"] is not None else (None, 0, 0, 0)
+        self.ctx.sun_light(self.g, self.tile, self.gb, s.sw, sun["struct"], self.hdr, s.sw, depth, mw, mh, mp)
 
     def cull_stats(self):
         """structs.CullStats of the last render() of meshes set with cull=True (draws drawn / culled, triangles drawn / culled:
@@ -654,6 +754,8 @@ class DeferredFrame:
             self.shade()
             e1.record()
             shade_events.append((e0, e1))
+        if self.sun is not None:
+            self.sun_light()
         if self._tail_overlap == "bloom":
             # everything behind the shade — the bloom chain (8 launches, HBM / latency-bound), average, tone-map — on the context's
             # high-priority side stream, beside the NEXT frame's cluster pass and shade (FP32-issue-bound), which write the other

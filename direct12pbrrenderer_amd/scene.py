@@ -363,6 +363,26 @@ def draw_bounds(vertices, indices, draws):
     return out
 
 
+def world_box(draws, bounds):
+    """(min, max) float32: the union over the draws of the world box of each local box's eight corners through the draw's Model
+    (float64, rounded outwards) — what the sun's light camera is fitted around (api.sun_fit).  A draw with the inverted box (no valid
+    triangle) takes no part; None if no draw does."""
+    lo, hi = None, None
+    for d, b in zip(np.asarray(draws), np.asarray(bounds)):
+        mn, mx = b["min"].astype(np.float64), b["max"].astype(np.float64)
+        if (mn > mx).any():
+            continue
+        m = np.asarray(d["Model"], dtype=np.float64).reshape(4, 4)
+        c = np.array([[(mx if i & 1 else mn)[0], (mx if i & 2 else mn)[1], (mx if i & 4 else mn)[2]] for i in range(8)])
+        # sums left to right, as the C++ host's SunShadowPass::WorldBox forms them: the two give the same box to the bit
+        w = np.stack([((m[r, 0] * c[:, 0] + m[r, 1] * c[:, 1]) + m[r, 2] * c[:, 2]) + m[r, 3] for r in range(3)], axis=1)
+        lo = w.min(axis=0) if lo is None else np.minimum(lo, w.min(axis=0))
+        hi = w.max(axis=0) if hi is None else np.maximum(hi, w.max(axis=0))
+    if lo is None:
+        return None
+    return (np.nextafter(lo.astype(f32), f32(-np.inf)), np.nextafter(hi.astype(f32), f32(np.inf)))
+
+
 class MeshScene:
     """Draws over shared buffers: add(mesh, model, albedo, emission, roughness, metallic) appends a mesh (or draws one added
     before again: instance=index) and one pbr_draw; arrays() -> (vertices, indices, draws), the input of pbr_gbuffer_raster."""

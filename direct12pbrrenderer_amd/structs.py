@@ -111,6 +111,27 @@ class FxaaImage(C.Structure):
     _fields_ = [("src", C.c_void_p), ("src_pitch", C.c_uint32), ("dst", C.c_void_p), ("dst_pitch", C.c_uint32)]
 
 
+class Sun(C.Structure):
+    """pbr_sun: the directional light of pbr_sun_light (HOST struct, 100 B): Direction is unit, from the surface towards the light."""
+    _fields_ = [("Direction", C.c_float * 3), ("Luminance", C.c_float * 3), ("LightViewProj", C.c_float * 16),
+                ("bias_const", C.c_float), ("bias_slope", C.c_float), ("pcf", C.c_uint32)]
+
+
+class SunDesc(C.Structure):
+    """pbr_sun_desc: one pbr_sun_light launch; pointers first, then the 32-bit fields: no padding.  g, tile, gb and sun are HOST
+    addresses (ctypes.addressof of a Global, Tile, GBuffer, Sun the caller keeps alive); exactly one of hdr / contrib_f32."""
+    _fields_ = ([(n, C.c_void_p) for n in ("g", "tile", "gb", "sun", "shadow_depth", "hdr", "contrib_f32")]
+                + [(n, C.c_uint32) for n in ("map_w", "map_h", "map_pitch", "hdr_pitch")])
+
+
+assert C.sizeof(Sun) == 100 and C.sizeof(SunDesc) == 72
+
+
+class Aabb(C.Structure):
+    """pbr_aabb as a HOST struct (pbr_sun_fit's world box); AABB_DTYPE is the same record for device arrays."""
+    _fields_ = [("min", C.c_float * 3), ("max", C.c_float * 3)]
+
+
 class HaloPeer(C.Structure):
     """pbr_halo_peer: rectangles {x, y, w, h} of the level-1 plane exchanged with rank `rank`."""
     _fields_ = [("rank", C.c_int32), ("send", C.c_uint32 * 4), ("recv", C.c_uint32 * 4)]

@@ -934,6 +934,104 @@ typedef struct pbr_fxaa_image {
 } pbr_fxaa_image;
 pbr_status pbr_fxaa_batch(pbr_ctx* ctx, const pbr_fxaa_image* images, uint32_t n, uint32_t w, uint32_t h);
 
+/* ---- Sun light with a shadow map (new): a directional light added to the HDR target after the shade ---------------------------- */
+/* The reference evaluates a directional light (deferred_shading.hlsl:144-156: dl_light_dir = normalize(1, 1, 1), 100 nits, through
+ * brdf()) and never adds it, and it has no shadow code.  pbr_sun_light is that light as a pass of its own: it reads the
+ * G-buffer the shade read, evaluates brdf() for one direction, looks the receiver up in a shadow map — the DEPTH PLANE of a
+ * pbr_gbuffer_raster call under an orthographic light camera (pbr_sun_fit) — and adds the result to the fp16 HDR target, between the
+ * shade (and the sky resolve) and the bloom.  Left out: multi-view frames, a depth-only shadow raster (the shadow pass writes and
+ * ignores the A / B / C / stencil planes, 17 B per texel), cascades, point-light shadows.
+ *
+ * THE RULE.  All arithmetic is fp32 with no contraction, in the order written (brackets first, otherwise left to right); every divide
+ * and square root is the IEEE correctly rounded one — NO operation of this pass goes to the quick hardware units (v_rcp / v_rsq / v_log /
+ * v_exp): its comparisons decide pixels, the pass is bound by its memory traffic, and tests/sun_truth.py restates it bit for bit.
+ * Per pixel (x, y) of the tile with stencil > 0; every other pixel of hdr is untouched, bit for bit.  (gx, gy) = (x0 + x, y0 + y).
+ *   Host, once per call: near_height = (float)(2.0 * (double)Near * tan((double)Fov / 2.0)), near_width = near_height * Ratio.
+ *   (These are the shade's expressions for position_ws and view_ws, each operation IEEE: the shade itself takes near_height from the
+ *   host's tanf, z_vs and 1 / Near from v_rcp and the camera vector from fused multiply-adds, so its receiver position may differ
+ *   from this pass's in the last place or two — far inside either pass's tolerance, and of no consequence to the shadow test, which
+ *   only this pass makes.)
+ *   Material   albedo_c = byte_c(A) / 255 as byte * (1.0f / 255.0f) (c = r, g, b in bits 0-7, 8-15, 16-23; emission takes no part),
+ *              roughness = byte0(C) * (1.0f / 255.0f), metallic = byte1(C) * (1.0f / 255.0f).
+ *   Normal     e = (byte0(B), byte1(B)) * (1.0f / 255.0f); d = (e.x * 2 - 1, e.y * 2 - 1, 1 - |d.x| - |d.y|); if d.z < 0:
+ *              (d.x, d.y) = (sign(d.x) * (1 - |d.y|), sign(d.y) * (1 - |d.x|)) from the old d.x, d.y, sign(0) = 1 (global.hlsli:85-115);
+ *              N = d / sqrt(dot(d, d)), dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z.
+ *   Position   u = (gx + 0.5) / full_w, v = (gy + 0.5) / full_h; cvv = ((2 u - 1) * 0.5 * near_width, (1 - 2 v) * 0.5 * near_height);
+ *              camera_vec_i = (InvView[i][0] * cvv.x + InvView[i][1] * cvv.y) + InvView[i][2] * Near   (vs_main :91-121);
+ *              z_vs = (Near * Far) / (Far - depth * (Far - Near)); position_ws = CameraPos + camera_vec * (z_vs / Near);
+ *              w = CameraPos - position_ws; view_ws = w / sqrt(dot(w, w)).
+ *   Radiance   L = Direction, NdotL = dot(N, L).  Not (NdotL > 0): the pixel is untouched and reads no shadow tap.
+ *              Otherwise c = brdf * Luminance * NdotL per channel, brdf.hlsli:47-67 literally:
+ *              h = L + view_ws; H = h / sqrt(dot(h, h)); NdotV = max(dot(N, view_ws), 0); NdotH = max(dot(N, H), 0);
+ *              F0_c = 0.04 + (albedo_c - 0.04) * metallic; p = max(1 - NdotL, 1e-6); p5 = ((p * p) * (p * p)) * p (pow(p, 5) as
+ *              multiplies); F_c = F0_c + (1 - F0_c) * p5; a = roughness * roughness; t = (NdotH * NdotH) * (a * a - 1) + 1;
+ *              D = (a * a) / max((PI * t) * t, 1e-6); k = ((roughness + 1) * (roughness + 1)) * 0.125;
+ *              G = (NdotV / max(NdotV * (1 - k) + k, 1e-6)) * (NdotL / max(NdotL * (1 - k) + k, 1e-6));
+ *              Kd_c = (1 - F_c) * (1 - metallic); brdf_c = (Kd_c * albedo_c) * INV_PI + ((F_c * D) * G) / max((4 * NdotL) * NdotV, 0.0001);
+ *              c_c = (brdf_c * Luminance_c) * NdotL.   PI = 3.14159265359f, INV_PI = 0.31830988618f (global.hlsli:4-7).
+ *   Shadow     M = LightViewProj; q_i = ((M[i][0] * P.x + M[i][1] * P.y) + M[i][2] * P.z) + M[i][3], i = 0, 1, 2, P = position_ws;
+ *              zr = q.z - (bias_const + bias_slope * (1 - NdotL));
+ *              su = ((q.x + 1) * 0.5) * map_w - 0.5, sv = ((1 - q.y) * 0.5) * map_h - 0.5   (texel (ix, iy) has its centre at (ix, iy)).
+ *   Taps       t(ix, iy) = 1 if (ix, iy) lies outside [0, map_w) x [0, map_h) or zr <= shadow_depth[iy * map_pitch + ix], else 0
+ *              (a tie is lit: the map's own surface, stored with the same depth, is not shadowed by itself at zero bias).
+ *              ix = floor(su), iy = floor(sv), wx = su - floor(su), wy = sv - floor(sv).
+ *              B(i, j) = the bilinear footprint whose origin is texel (ix + i, iy + j), ALWAYS with the weights wx, wy of (su, sv):
+ *              B = l(l(t00, t10, wx), l(t01, t11, wx), wy), l(a, b, w) = a + (b - a) * w, x first.
+ *   Visibility shadow_depth == NULL: vis = 1.  A receiver with not (0 <= q.z <= 1), or with not (-2 <= su < map_w + 1 and
+ *              -2 <= sv < map_h + 1) (every tap of either footprint set is then outside the map; NaN coordinates land here): vis = 1,
+ *              no tap is read.  pcf == 1: vis = B(0, 0).  pcf == 3: vis = s * (1.0f / 9.0f), s = the sum of B(i, j) from 0 in the order
+ *              j = -1, 0, 1 outer, i = -1, 0, 1 inner; the 4 x 4 taps are read once, lerped along x per tap row, then along y.
+ *   Target     vis == 0: the pixel's bits are left alone.  Otherwise hdr.rgb = RN_half(float(hdr.rgb) + c * vis), the product rounded
+ *              to fp32 before the sum; alpha's bits are kept.
+ *   Probe      with contrib_f32 (float4 per pixel, tile-local, pitch hdr_pitch) EVERY pixel of the tile is written: (c * vis, 1) where
+ *              stencil > 0 and NdotL > 0 (vis == 0 included), (0, 0, 0, 0) elsewhere; hdr must be NULL.
+ * Direction must be finite and unit: |dot(d, d) - 1| <= 1e-4 in double.  LightViewProj must be affine: finite entries and row 3
+ * exactly (0, 0, 0, 1).  Luminance and the biases must be finite.  g: InvView (its 3 x 3 part), CameraPos, Ratio, Near, Far, Fov are read
+ * and must be finite (0 < Near < Far).
+ * Refusals (PBR_ERR_INVALID, nothing enqueued): a null pointer (d, g, tile, gb, a G-buffer plane, sun); both or neither of hdr /
+ * contrib_f32; an empty tile or one outside its frame; gb->pitch or hdr_pitch below the tile's width, map_pitch below map_w (with a
+ * map); pcf not 1 or 3; the conditions on the sun above; with a map, map_w or map_h of 0 or above PBR_RASTER_MAX_SIZE; planes not
+ * aligned to their element (hdr 8 bytes, contrib_f32 16, the rest 4); pitch x rows x 16 bytes (the G-buffer's and the target's) or
+ * map_pitch x map_h x 4 bytes of 4 GiB or more (32-bit offsets, as for the shade); a non-finite camera.
+ * ONE asynchronous launch on the context's stream, no allocation, no host synchronisation. */
+typedef struct pbr_sun {            /* HOST struct */
+    float Direction[3];             /* unit, world space, from the surface TOWARDS the light (dl_light_dir) */
+    float Luminance[3];             /* light_luminance, deferred_shading.hlsl:146 */
+    float LightViewProj[16];        /* world -> light clip, row-major, M*v; must be affine (row 3 == 0,0,0,1) */
+    float bias_const, bias_slope;   /* in light-clip depth units */
+    uint32_t pcf;                   /* 1 or 3 */
+} pbr_sun;
+typedef struct pbr_sun_desc {       /* pointers first, as pbr_shade_desc */
+    const pbr_global* g; const pbr_tile* tile; const pbr_gbuffer* gb;
+    const pbr_sun* sun;
+    const float* shadow_depth;      /* map_w x map_h D32 plane, the depth plane of a pbr_gbuffer_raster call; NULL = no shadows */
+    pbr_half* hdr;                  /* read-modify-write, tile-local, pitch hdr_pitch */
+    float* contrib_f32;             /* parity probe: float4 per pixel, the contribution alone; exactly one of hdr / contrib_f32 */
+    uint32_t map_w, map_h, map_pitch, hdr_pitch;
+} pbr_sun_desc;
+pbr_status pbr_sun_light(pbr_ctx* ctx, const pbr_sun_desc* d);
+/* Host only, no ctx, no GPU: the light's pbr_global — View, InvView, Projection, InvProjection, Resolution; the rest zero — of an
+ * orthographic light camera around a world-space box, and the matching LightViewProj.  The shadow pass is pbr_gbuffer_raster with
+ * light_g, the tile {0, 0, map_w, map_h, map_w, map_h} and a scratch G-buffer of the map's size; its depth plane is the map.
+ * THE RULE, in double unless stated, sums left to right; every matrix entry is rounded once to fp32:
+ *   d = dir / |dir|.  z = -d (the light looks along -dir, left-handed like the reference's camera: +z into the scene);
+ *   up = (0, 1, 0), or (1, 0, 0) when |d.y| > 0.999; x = cross(up, z) / |cross(up, z)|; y = cross(z, x).
+ *   View = rows (x, 0), (y, 0), (z, 0), (0, 0, 0, 1) — the light's eye is the world origin, an orthographic camera has no position;
+ *   InvView = its transpose.
+ *   Extents: the min / max over the box's eight corners (each coordinate from min or max) of dot(x, p), dot(y, p), dot(z, p) ->
+ *   l, r, b, t, n, f.  An extent below 1e-6 is replaced by 1e-6 about its centre.  x and y are widened by one texel of the FINAL map
+ *   on each side: e = (r - l) / (map_w - 2), l -= e, r += e (y with map_h), so the corners lie within [-1 + 2 / map_w, 1 - 2 / map_w];
+ *   z by 1 % of its span on each side: s = 0.01 * (f - n), n -= s, f += s, so the corners' depth lies within [0.01 / 1.02, 1.01 / 1.02].
+ *   Projection (D3D orthographic, z in [0, 1]) = rows (2 / (r - l), 0, 0, -(r + l) / (r - l)), (0, 2 / (t - b), 0, -(t + b) / (t - b)),
+ *   (0, 0, 1 / (f - n), -n / (f - n)), (0, 0, 0, 1); InvProjection = rows ((r - l) / 2, 0, 0, (r + l) / 2), (0, (t - b) / 2, 0,
+ *   (t + b) / 2), (0, 0, f - n, n), (0, 0, 0, 1).  Resolution = (map_w, map_h).
+ *   light_view_proj = the product, in double, of the fp32-ROUNDED Projection and View (what the raster's vertex stage multiplies by),
+ *   rounded once; its row 3 is exactly (0, 0, 0, 1).
+ * Refusals (PBR_ERR_INVALID): a null pointer, a non-finite or zero dir, a non-finite or inverted box (min > max), map_w or map_h
+ * below 3 or above PBR_RASTER_MAX_SIZE. */
+pbr_status pbr_sun_fit(const float dir[3], const pbr_aabb* world_box, uint32_t map_w, uint32_t map_h,
+                       pbr_global* light_g, float light_view_proj[16]);
+
 /* ---- multi-GPU (new) -------------------------------------------------------------- */
 /* RCCL communicator over the ranks of one node.  unique_id: 128 bytes from
  * pbr_comm_unique_id() on rank 0, broadcast by the caller (e.g. torch.distributed store). */
