@@ -6,7 +6,7 @@ symbol cannot be resolved this module raises — it never substitutes another im
 import ctypes as C
 import os
 
-from .structs import Aabb, CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, ShadeDesc, ShadeTables, SunDesc, Texture2D, Tile, View
+from .structs import Aabb, CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, RasterDesc, ShadeDesc, ShadeTables, SunDesc, Tile, View
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB", os.path.join(_HERE, "libpbr_hip.so"))   # override = experiments only
@@ -53,8 +53,7 @@ SIGNATURES = {
     "pbr_gbuffer_encode": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "pbr_gbuffer_raster_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
-    "pbr_gbuffer_raster": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
-                                  _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz]),
+    "pbr_gbuffer_raster": (_int, [_vp, C.POINTER(RasterDesc)]),
     "pbr_texture2d_bytes": (_sz, [_u32, _u32, _u32, _u32]),
     "pbr_bc1_decode": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "pbr_bc6h_chain_bytes": (_sz, [_u32, _u32]),
@@ -68,13 +67,7 @@ SIGNATURES = {
     "pbr_bc1_encode": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "pbr_gbuffer_raster_textured_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster_textured_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
-    "pbr_gbuffer_raster_textured": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
-                                           _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, C.POINTER(Texture2D), _u32]),
     "pbr_draw_bounds": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp]),
-    "pbr_gbuffer_raster_culled": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
-                                         _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _vp]),
-    "pbr_gbuffer_raster_textured_culled": (_int, [_vp, C.POINTER(Global), C.POINTER(Tile), _vp, _u32, _vp, _u32, _vp, _u32, _u32,
-                                                  _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, C.POINTER(Texture2D), _u32, _vp, _vp]),
     "pbr_bloom_prefilter": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _f32, _f32]),
     "pbr_blur_h": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),
     "pbr_blur_v": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .structs import (Aabb, ShadeDesc, ShadeTables, Sun, SunDesc, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
+from .structs import (Aabb, RasterDesc, ShadeDesc, ShadeTables, Sun, SunDesc, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
                       NUM_CLUSTERS, AABB_DTYPE, CullStats, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
 
@@ -30,6 +30,13 @@ def _ptr(t):
             raise PbrError("expected a contiguous tensor")
         return C.c_void_p(t.data_ptr())
     return C.c_void_p(int(t))
+
+
+def _some(name, t):
+    """t, a device buffer the textured and culled raster forwards cannot do without: in the descriptor a null one selects another raster"""
+    if t is None or not _ptr(t).value:
+        raise PbrError(f"pbr_gbuffer_raster: {name} null")
+    return t
 
 
 def _bc6h_faces(who, faces, size, mip_levels):
@@ -404,13 +411,18 @@ class PbrContext:
         return self.empty((self.raster_scratch_bytes(w, h, n_triangles, minimum) + int(extra),), torch.uint8)
 
     def gbuffer_raster(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
-                       A, B, Cc, depth, stencil, pitch, scratch, scratch_bytes=None):
-        """pbr_gbuffer_raster: draws (device structs.DRAW_DTYPE records) of the vertex / index buffers (device VERTEX_DTYPE records,
-        uint32 indices) -> the tile's five G-buffer planes.  max_triangles = sum of index_count // 3; scratch from alloc_raster_scratch."""
+                       A, B, Cc, depth, stencil, pitch, scratch, scratch_bytes=None, *, maps=None, textures=None, bounds=None, stats=None):
+        """pbr_gbuffer_raster, the one call that fills a RasterDesc: draws (device structs.DRAW_DTYPE records) of the vertex / index
+        buffers (device VERTEX_DTYPE records, uint32 indices) -> the tile's five G-buffer planes.  max_triangles = sum of
+        index_count // 3; scratch from alloc_raster_scratch.  maps, textures, bounds, stats: as gbuffer_raster_textured and
+        gbuffer_raster_culled describe them; with maps the scratch is alloc_textured_raster_scratch's."""
+        textures = list(textures or ())
+        table = (Texture2D * len(textures))(*textures)
         nbytes = scratch.numel() * scratch.element_size() if scratch_bytes is None else int(scratch_bytes)
-        self._check(self.lib.pbr_gbuffer_raster(self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices),
-                                                int(n_indices), _ptr(draws), int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc),
-                                                _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch), nbytes))
+        d = RasterDesc(C.addressof(g), C.addressof(tile), _ptr(vertices), _ptr(indices), _ptr(draws), _ptr(A), _ptr(B), _ptr(Cc),
+                       _ptr(depth), _ptr(stencil), _ptr(scratch), nbytes, _ptr(maps), C.addressof(table) if textures else None, _ptr(bounds),
+                       _ptr(stats), int(n_vertices), int(n_indices), int(n_draws), int(max_triangles), int(pitch), len(textures))
+        self._check(self.lib.pbr_gbuffer_raster(self.h, C.byref(d)))
 
     def textured_raster_scratch_bytes(self, w, h, n_triangles, minimum=False):
         """pbr_gbuffer_raster_textured_scratch_bytes (recommended) or, minimum=True, its _min_scratch_bytes for a w x h tile"""
@@ -509,16 +521,11 @@ class PbrContext:
 
     def gbuffer_raster_textured(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
                                 A, B, Cc, depth, stencil, pitch, scratch, maps, textures, scratch_bytes=None):
-        """pbr_gbuffer_raster_textured: gbuffer_raster plus maps (device DRAW_MAPS_DTYPE records, one per draw) and textures (a
+        """pbr_gbuffer_raster with maps: gbuffer_raster plus maps (device DRAW_MAPS_DTYPE records, one per draw) and textures (a
         sequence of structs.Texture2D, from upload_texture; host side, at most RASTER_MAX_TEXTURES).  Scratch from
         alloc_textured_raster_scratch."""
-        textures = list(textures)
-        table = (Texture2D * max(len(textures), 1))(*textures)
-        nbytes = scratch.numel() * scratch.element_size() if scratch_bytes is None else int(scratch_bytes)
-        self._check(self.lib.pbr_gbuffer_raster_textured(
-            self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices), int(n_indices), _ptr(draws),
-            int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc), _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch),
-            nbytes, _ptr(maps), table if textures else None, len(textures)))
+        self.gbuffer_raster(g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, Cc, depth, stencil,
+                            pitch, scratch, scratch_bytes, maps=_some("maps", maps), textures=textures)
 
     # ---- model culling ---------------------------------------------------------------------------
     def draw_bounds(self, vertices, n_vertices, indices, n_indices, draws, n_draws, out=None):
@@ -540,26 +547,19 @@ class PbrContext:
 
     def gbuffer_raster_culled(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
                               A, B, Cc, depth, stencil, pitch, scratch, bounds, stats=None, scratch_bytes=None):
-        """pbr_gbuffer_raster_culled: gbuffer_raster plus bounds (device AABB_DTYPE records, one per draw: draw_bounds) and stats
+        """pbr_gbuffer_raster with bounds: gbuffer_raster plus bounds (device AABB_DTYPE records, one per draw: draw_bounds) and stats
         (device, alloc_cull_stats; None: not recorded).  A draw whose world box lies outside the widened tile's frustum is not set
         up; the planes are bit-identical to gbuffer_raster's."""
-        nbytes = scratch.numel() * scratch.element_size() if scratch_bytes is None else int(scratch_bytes)
-        self._check(self.lib.pbr_gbuffer_raster_culled(
-            self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices), int(n_indices), _ptr(draws),
-            int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc), _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch),
-            nbytes, _ptr(bounds), _ptr(stats)))
+        self.gbuffer_raster(g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, Cc, depth, stencil,
+                            pitch, scratch, scratch_bytes, bounds=_some("bounds", bounds), stats=stats)
 
     def gbuffer_raster_textured_culled(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws,
                                        max_triangles, A, B, Cc, depth, stencil, pitch, scratch, maps, textures, bounds, stats=None,
                                        scratch_bytes=None):
-        """pbr_gbuffer_raster_textured_culled: gbuffer_raster_textured plus bounds and stats as gbuffer_raster_culled takes them"""
-        textures = list(textures)
-        table = (Texture2D * max(len(textures), 1))(*textures)
-        nbytes = scratch.numel() * scratch.element_size() if scratch_bytes is None else int(scratch_bytes)
-        self._check(self.lib.pbr_gbuffer_raster_textured_culled(
-            self.h, C.byref(g), C.byref(tile), _ptr(vertices), int(n_vertices), _ptr(indices), int(n_indices), _ptr(draws),
-            int(n_draws), int(max_triangles), _ptr(A), _ptr(B), _ptr(Cc), _ptr(depth), _ptr(stencil), int(pitch), _ptr(scratch),
-            nbytes, _ptr(maps), table if textures else None, len(textures), _ptr(bounds), _ptr(stats)))
+        """pbr_gbuffer_raster with maps and bounds: gbuffer_raster_textured plus bounds and stats as gbuffer_raster_culled takes them"""
+        self.gbuffer_raster(g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, Cc, depth, stencil,
+                            pitch, scratch, scratch_bytes, maps=_some("maps", maps), textures=textures, bounds=_some("bounds", bounds),
+                            stats=stats)
 
     def bloom_prefilter(self, hdr, w, h, pitch, out, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE):
         self._check(self.lib.pbr_bloom_prefilter(self.h, _ptr(hdr), w, h, pitch, _ptr(out), threshold, knee))

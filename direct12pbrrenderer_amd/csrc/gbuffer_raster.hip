@@ -24,7 +24,7 @@
 // -ffp-contract=off: tests/raster_ref.py restates every step in the same operation order; tests/raster_truth.py holds the
 // interpolated attributes to an fp64 statement of the contract.
 //
-// Textured draws (pbr_gbuffer_raster_textured) take the same six launches with a non-empty `Tex` pack on k_rs_setup and
+// Textured draws (pbr_raster_desc.maps set) take the same six launches with a non-empty `Tex` pack on k_rs_setup and
 // k_rs_raster (the empty pack is the constant-material kernel): setup also writes the uv and tangent_ws of the three vertices
 // (RsTexAttr) and drops draws with a bad map index; the resolve adds the perspective-correct uv / tangent, the quad's LOD, up to
 // five trilinear samples (SamplerLinearWrap as pinned in pbr_hip.h) and the normal-map frame, before the same encode.
@@ -34,7 +34,7 @@
 // from the blocks in place (bc1_decode.hpp).  The bulk decode of a whole chain (pbr_bc1_decode) is texture2d.hip's; the texture table's
 // descriptions are checked by tex_chain.hpp.
 //
-// Model culling (pbr_gbuffer_raster_culled, pbr_gbuffer_raster_textured_culled): Scene::CullModel on the device.  The same six
+// Model culling (pbr_raster_desc.bounds set, with or without maps): Scene::CullModel on the device.  The same six
 // launches with a non-empty `Cull` pack on k_rs_prep (the empty pack is the kernel without it): a draw whose world box lies outside
 // one of the six planes of the widened tile (the rule pinned in pbr_hip.h) gets no triangles in the scan, so neither k_rs_setup
 // nor k_rs_fill ever sees it.  The planes are formed on the host in fp64 per call; nothing is read back.  k_rs_bounds
@@ -888,13 +888,36 @@ void cull_planes(const pbr_global* g, const pbr_tile* tile, float* out) {
     }
 }
 
-// the checks and launches of the four entry points; tx: null for pbr_gbuffer_raster, else the validated texture table (bc1: it holds
-// a BC1-resident texture); cull: null, or the culled calls' bounds and stats (the planes are filled here)
-pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const pbr_vertex* vertices, uint32_t n_vertices,
-                  const uint32_t* indices, uint32_t n_indices, const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                  uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch, void* scratch,
-                  size_t scratch_bytes, const RsRasterTex* tx, bool bc1 = false, RsCull* cull = nullptr) {
+// pbr_gbuffer_raster: the checks and the six launches.  tx: null without d->maps, else the validated texture table (bc1: it holds a
+// BC1-resident texture); cull: null without d->bounds, else the bounds and stats (the planes are filled here)
+static_assert(sizeof(pbr_raster_desc) == 152, "descriptor layout: no padding");
+pbr_status raster(pbr_ctx* ctx, const pbr_raster_desc* d) {
     if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, d, "pbr_gbuffer_raster: null descriptor");
+    const auto [g, tile, vertices, indices, draws, A, B, C, depth, stencil, scratch, scratch_bytes, maps, textures, bounds, stats,
+                n_vertices, n_indices, n_draws, max_triangles, pitch, n_textures] = *d;
+    PBR_REQUIRE(ctx, maps || (!textures && n_textures == 0), "pbr_gbuffer_raster: textures or n_textures without maps");
+    PBR_REQUIRE(ctx, bounds || !stats, "pbr_gbuffer_raster: stats without bounds");
+    RsRasterTex table;
+    const RsRasterTex* tx = maps ? &table : nullptr;
+    bool bc1 = false;
+    if (tx) {
+        PBR_REQUIRE(ctx, (pbr::addr(maps) & 3u) == 0, "pbr_gbuffer_raster: maps not 4-byte aligned");
+        PBR_REQUIRE(ctx, n_textures <= PBR_RASTER_MAX_TEXTURES && (textures || n_textures == 0),
+                    "pbr_gbuffer_raster: more textures than PBR_RASTER_MAX_TEXTURES, or a null texture table");
+        table.maps = maps;
+        table.tex = nullptr;
+        table.n_tex = n_textures;
+        for (uint32_t i = 0; i < PBR_RASTER_MAX_TEXTURES; i++) table.table[i] = pbr_texture2d{nullptr, 0, 0, 0, 0};
+        for (uint32_t i = 0; i < n_textures; i++) {
+            const pbr_texture2d& t = textures[i];
+            PBR_CHECK(ctx, "pbr_gbuffer_raster", tex2d::refusal(t.width, t.height, t.mip_levels, t.format, true));
+            PBR_REQUIRE(ctx, t.texels && tex2d::aligned(t.texels, t.format),
+                        "pbr_gbuffer_raster: texels null or not aligned to the texel size (BC1 blocks: 8 bytes)");
+            bc1 |= (t.format & PBR_TEX_BC1_BLOCKS) != 0;
+            table.table[i] = t;
+        }
+    }
     PBR_REQUIRE(ctx, g && tile && vertices && indices && draws && A && B && C && depth && stencil && scratch,
                 "pbr_gbuffer_raster: null pointer");
     PBR_REQUIRE(ctx, n_vertices && n_indices && n_draws && max_triangles, "pbr_gbuffer_raster: empty vertex / index / draw list");
@@ -907,12 +930,12 @@ pbr_status raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile, const
     PBR_REQUIRE(ctx, ((pbr::addr(vertices) | pbr::addr(indices) | pbr::addr(draws) | pbr::addr(A) | pbr::addr(B) | pbr::addr(C) |
                        pbr::addr(depth)) & 3u) == 0 && (pbr::addr(scratch) & 15u) == 0,
                 "pbr_gbuffer_raster: unaligned buffer");
-    if (cull) {
-        PBR_REQUIRE(ctx, cull->bounds && (pbr::addr(cull->bounds) & 3u) == 0, "pbr_gbuffer_raster_culled: bounds null or not 4-byte aligned");
-        PBR_REQUIRE(ctx, (pbr::addr(cull->stats) & 3u) == 0, "pbr_gbuffer_raster_culled: stats not 4-byte aligned");
-    }
+    PBR_REQUIRE(ctx, (pbr::addr(bounds) & 3u) == 0, "pbr_gbuffer_raster: bounds not 4-byte aligned");
+    PBR_REQUIRE(ctx, (pbr::addr(stats) & 3u) == 0, "pbr_gbuffer_raster: stats not 4-byte aligned");
+    RsCull cull_pack{bounds, stats, {}};
+    RsCull* cull = bounds ? &cull_pack : nullptr;
     const Layout L = layout(tile->w, tile->h, max_triangles, tx != nullptr);
-    PBR_REQUIRE(ctx, scratch_bytes >= L.pool, tx ? "pbr_gbuffer_raster_textured: scratch below pbr_gbuffer_raster_textured_min_scratch_bytes"
+    PBR_REQUIRE(ctx, scratch_bytes >= L.pool, tx ? "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_textured_min_scratch_bytes"
                                                 : "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_min_scratch_bytes");
 
     RsParams p;
@@ -1003,77 +1026,7 @@ size_t pbr_gbuffer_raster_textured_scratch_bytes(uint32_t w, uint32_t h, uint32_
     return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
 }
 
-pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                              void* scratch, size_t scratch_bytes) {
-    return raster(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth, stencil,
-                  pitch, scratch, scratch_bytes, nullptr);
-}
-
-namespace {
-// pbr_gbuffer_raster_textured, with or without the model cull
-pbr_status raster_textured(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                           const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                           const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                           uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                           void* scratch, size_t scratch_bytes,
-                           const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures, RsCull* cull) {
-    if (!ctx) return PBR_ERR_INVALID;
-    PBR_REQUIRE(ctx, maps && (pbr::addr(maps) & 3u) == 0, "pbr_gbuffer_raster_textured: maps null or not 4-byte aligned");
-    PBR_REQUIRE(ctx, n_textures <= PBR_RASTER_MAX_TEXTURES && (textures || n_textures == 0),
-                "pbr_gbuffer_raster_textured: more textures than PBR_RASTER_MAX_TEXTURES, or a null texture table");
-    RsRasterTex tx;
-    tx.maps = maps;
-    tx.tex = nullptr;
-    tx.n_tex = n_textures;
-    for (uint32_t i = 0; i < PBR_RASTER_MAX_TEXTURES; i++) tx.table[i] = pbr_texture2d{nullptr, 0, 0, 0, 0};
-    bool any_bc1 = false;
-    for (uint32_t i = 0; i < n_textures; i++) {
-        const pbr_texture2d& t = textures[i];
-        PBR_CHECK(ctx, "pbr_gbuffer_raster_textured", tex2d::refusal(t.width, t.height, t.mip_levels, t.format, true));
-        PBR_REQUIRE(ctx, t.texels && tex2d::aligned(t.texels, t.format),
-                    "pbr_gbuffer_raster_textured: texels null or not aligned to the texel size (BC1 blocks: 8 bytes)");
-        any_bc1 |= (t.format & PBR_TEX_BC1_BLOCKS) != 0;
-        tx.table[i] = t;
-    }
-    return raster(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth, stencil,
-                  pitch, scratch, scratch_bytes, &tx, any_bc1, cull);
-}
-}  // namespace
-
-pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                       const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                                       const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                                       uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                                       void* scratch, size_t scratch_bytes,
-                                       const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures) {
-    return raster_textured(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth,
-                           stencil, pitch, scratch, scratch_bytes, maps, textures, n_textures, nullptr);
-}
-
-pbr_status pbr_gbuffer_raster_culled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                     const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                                     const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                                     uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                                     void* scratch, size_t scratch_bytes, const pbr_aabb* bounds, pbr_cull_stats* stats) {
-    RsCull cull{bounds, stats, {}};
-    return raster(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth, stencil,
-                  pitch, scratch, scratch_bytes, nullptr, false, &cull);
-}
-
-pbr_status pbr_gbuffer_raster_textured_culled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                                              void* scratch, size_t scratch_bytes,
-                                              const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures,
-                                              const pbr_aabb* bounds, pbr_cull_stats* stats) {
-    RsCull cull{bounds, stats, {}};
-    return raster_textured(ctx, g, tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, A, B, C, depth,
-                           stencil, pitch, scratch, scratch_bytes, maps, textures, n_textures, &cull);
-}
+pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_raster_desc* d) { return raster(ctx, d); }
 
 pbr_status pbr_draw_bounds(pbr_ctx* ctx, const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
                            const pbr_draw* draws, uint32_t n_draws, pbr_aabb* out) {

@@ -3,7 +3,7 @@
 // the chain kernels take as an argument.
 //   tex2d       the chain of a pbr_texture2d, as texels of a stored format or as BC1 blocks (PBR_TEX_BC1_BLOCKS): texture2d.hip
 //               (pbr_texture2d_gen_mips, pbr_bc1_encode, pbr_bc1_decode, pbr_texture2d_bytes) and the texture table of
-//               pbr_gbuffer_raster_textured (gbuffer_raster.hip)
+//               pbr_gbuffer_raster with maps (gbuffer_raster.hip)
 //   bc6h_chain  the six BC6H_UF16 face chains of a sky cube beside the pbr_cube_f32 chain: bc6h_decode.hip, bc6h_encode.hip
 //               (bc6h_encode_block.hpp) and the resident sky (pbr_skybox_bc6h, raster.hip)
 // Plain C++: hipcc compiles it for gfx950, tools/tex_chain_hostcheck.cpp for the host, where it runs under ASan / UBSan against the

@@ -257,7 +257,7 @@ class HostRenderer:
         """set_meshes plus the draws' maps (structs.DRAW_MAPS_DTYPE, one per draw) and their textures: (chain, width, height,
         mip_levels, format) with the chain's host bytes in the reference's layout (scene.pack_chain) or, with structs.TEX_BC1_BLOCKS
         in the format, its BC1 blocks (parse_texture_file), which stay BC1 on the device.  GBufferPass uploads the chains once and
-        rasterizes through pbr_gbuffer_raster_textured."""
+        rasterizes through pbr_gbuffer_raster with maps."""
         from .structs import DRAW_DTYPE, DRAW_MAPS_DTYPE, VERTEX_DTYPE, Texture2D
         v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
         i = np.ascontiguousarray(indices, dtype=np.uint32)

@@ -220,6 +220,26 @@ void GBufferPass::CullingStatus(uint32_t out[4]) const {
     out[0] = st.draws_drawn; out[1] = st.draws_culled; out[2] = st.triangles_drawn; out[3] = st.triangles_culled;
 }
 
+pbr_raster_desc GBufferPass::RasterInputs() const {
+    pbr_raster_desc d{};
+    if (!mRasterScratch) return d;
+    auto count = [](const DeviceStructuredBuffer& b) { return b.Size() / b.Stride(); };
+    d.vertices = (const pbr_vertex*)mVertices->DevicePtr(); d.n_vertices = count(*mVertices);
+    d.indices = (const uint32_t*)mIndices->DevicePtr(); d.n_indices = count(*mIndices);
+    d.draws = (const pbr_draw*)mDraws->DevicePtr(); d.n_draws = count(*mDraws);
+    d.max_triangles = mMaxTriangles;
+    d.scratch = mRasterScratch->DevicePtr(); d.scratch_bytes = mRasterScratch->Size();
+    if (mMaps) {
+        d.maps = (const pbr_draw_maps*)mMaps->DevicePtr();
+        d.textures = mTextureTable.empty() ? nullptr : mTextureTable.data(); d.n_textures = (uint32)mTextureTable.size();
+    }
+    if (mBounds) {   // Scene::CullModel + mCullingStatus (:141-150), on the device
+        d.bounds = (const pbr_aabb*)mBounds->DevicePtr();
+        d.stats = (pbr_cull_stats*)mCullStats->DevicePtr();
+    }
+    return d;
+}
+
 void GBufferPass::Execute(FGContext* context) {
     PIXScope(context->CommandList, "Gbuffer Pass");
     MeshSource& meshes = context->Scene->Meshes();
@@ -229,15 +249,7 @@ void GBufferPass::Execute(FGContext* context) {
         auto* c = As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::GBufferC));
         auto* ds = As<DeviceTexture2D>(GetTransientResource(context, DeferredPipelineResource::DepthStencil));
         if (meshes.Dirty || !mRasterScratch) UploadMeshes(context, meshes, a->Width(), a->Height());
-        context->CommandList->RasterGBuffer(&mShadingState, (const pbr_vertex*)mVertices->DevicePtr(), (uint32)meshes.Vertices.size(),
-                                            (const uint32_t*)mIndices->DevicePtr(), (uint32)meshes.Indices.size(),
-                                            (const pbr_draw*)mDraws->DevicePtr(), (uint32)meshes.Draws.size(), mMaxTriangles,
-                                            a, b, c, ds, mRasterScratch->DevicePtr(), mRasterScratch->Size(),
-                                            mMaps ? (const pbr_draw_maps*)mMaps->DevicePtr() : nullptr, mTextureTable.data(),
-                                            (uint32)mTextureTable.size(),
-                                            // Scene::CullModel + mCullingStatus (:141-150), on the device
-                                            mBounds ? (const pbr_aabb*)mBounds->DevicePtr() : nullptr,
-                                            mCullStats ? (pbr_cull_stats*)mCullStats->DevicePtr() : nullptr);
+        context->CommandList->RasterGBuffer(&mShadingState, RasterInputs(), a, b, c, ds);
         return;
     }
     GBufferSource& src = context->Scene->GBuffer();
@@ -485,14 +497,15 @@ void SunShadowPass::Execute(FGContext* context) {
     if (!WorldBox(meshes, &box)) throw HipException("SunShadowPass: the meshes hold no valid triangle to fit the light's camera around");
     pbr_global light_g;
     if (pbr_sun_fit(mSun->Direction, &box, n, n, &light_g, mSun->LightViewProj) != PBR_OK) throw HipException("SunShadowPass: pbr_sun_fit refused the box or the map size");
-    const size_t plane = (size_t)n * n * 4, scratch = pbr_gbuffer_raster_scratch_bytes(n, n, mGBuffer->MaxTriangles());
+    pbr_raster_desc d = mGBuffer->RasterInputs();   // the unculled constant-material raster of the same buffers
+    d.maps = nullptr; d.textures = nullptr; d.n_textures = 0; d.bounds = nullptr; d.stats = nullptr;
+    const size_t plane = (size_t)n * n * 4, scratch = pbr_gbuffer_raster_scratch_bytes(n, n, d.max_triangles);
     if (3 * plane > 0xffffffffu || scratch > 0xffffffffu) throw HipException("SunShadowPass: shadow raster buffers larger than 4 GiB");
     if (!mPlanes || mPlanes->Size() != 3 * plane) mPlanes = std::make_unique<DeviceStructuredBuffer>((uint32)(3 * plane), 4);
     if (!mRasterScratch || mRasterScratch->Size() != scratch) mRasterScratch = std::make_unique<DeviceStructuredBuffer>((uint32)scratch, 4);
     uint32_t* p = (uint32_t*)mPlanes->DevicePtr();
-    context->CommandList->RasterShadowMap(&mShadingState, &light_g, mGBuffer->Vertices(), (uint32)meshes.Vertices.size(), mGBuffer->Indices(),
-                                          (uint32)meshes.Indices.size(), mGBuffer->Draws(), (uint32)meshes.Draws.size(), mGBuffer->MaxTriangles(),
-                                          p, p + (size_t)n * n, p + 2 * (size_t)n * n, target, mRasterScratch->DevicePtr(), mRasterScratch->Size());
+    d.scratch = mRasterScratch->DevicePtr(); d.scratch_bytes = mRasterScratch->Size();
+    context->CommandList->RasterShadowMap(&mShadingState, &light_g, d, p, p + (size_t)n * n, p + 2 * (size_t)n * n, target);
     mUploadsSeen = mGBuffer->Uploads();
     mSerialSeen = mSun->Serial;
 }

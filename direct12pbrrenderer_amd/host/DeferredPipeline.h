@@ -75,11 +75,10 @@ public:
     // mCullingStatus (DeferredPipeline.h:96-100) of the last Execute with model culling on, read back from the device here (the
     // caller has drained the command list): NumDrawCall, NumCulled, triangles drawn, triangles culled; zeros without culling
     void CullingStatus(uint32_t out[4]) const;
-    // the device copies of the scene's meshes, for SunShadowPass (which runs after this pass); Uploads() counts UploadMeshes calls
-    const pbr_vertex* Vertices() const { return mVertices ? (const pbr_vertex*)mVertices->DevicePtr() : nullptr; }
-    const uint32_t* Indices() const { return mIndices ? (const uint32_t*)mIndices->DevicePtr() : nullptr; }
-    const pbr_draw* Draws() const { return mDraws ? (const pbr_draw*)mDraws->DevicePtr() : nullptr; }
-    uint32 MaxTriangles() const { return mMaxTriangles; }
+    // the input half of a pbr_raster_desc from the device copies of the scene's meshes (all null before the first upload): geometry,
+    // counts, maps and table, bounds and stats, scratch.  For Execute and for SunShadowPass (which runs after this pass, clears the
+    // map and cull fields and puts in its own scratch); Uploads() counts UploadMeshes calls
+    pbr_raster_desc RasterInputs() const;
     uint64_t Uploads() const { return mUploads; }
 protected:
     uint64_t mUploads = 0;

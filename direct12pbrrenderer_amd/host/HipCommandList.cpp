@@ -578,11 +578,8 @@ void HipCommandList::EncodeGBuffer(ShadingState* s, const float* m0, const float
                              (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr()), "pbr_gbuffer_encode");
 }
 
-void HipCommandList::RasterGBuffer(ShadingState* s, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
-                                   const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, DeviceTexture2D* a, DeviceTexture2D* b,
-                                   DeviceTexture2D* c, DeviceTexture2D* ds, void* scratch, size_t scratch_bytes,
-                                   const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32 n_textures,
-                                   const pbr_aabb* bounds, pbr_cull_stats* stats) {
+void HipCommandList::RasterGBuffer(ShadingState* s, pbr_raster_desc d, DeviceTexture2D* a, DeviceTexture2D* b, DeviceTexture2D* c,
+                                   DeviceTexture2D* ds) {
     if (!s || s->File() != "gbuffer.hlsl") throw HipException("RasterGBuffer: gbuffer.hlsl shading state expected");
     if (!a || !b || !c || !ds || a->Width() != b->Width() || a->Width() != c->Width() || a->Width() != ds->Width() ||
         a->Height() != b->Height() || a->Height() != c->Height() || a->Height() != ds->Height())
@@ -591,44 +588,27 @@ void HipCommandList::RasterGBuffer(ShadingState* s, const pbr_vertex* vertices, 
     FlushPendingBloom();
     const uint32 w = a->Width(), h = a->Height();
     const pbr_tile tile = mTile.w ? mTile : pbr_tile{0, 0, w, h, w, h};
-    if (bounds) {
-        if (maps)
-            Check(pbr_gbuffer_raster_textured_culled(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws,
-                                                     max_triangles, (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(),
-                                                     (uint32_t*)c->DevicePtr(), ds->DepthPlane(), ds->StencilPlane(), w, scratch,
-                                                     scratch_bytes, maps, textures, n_textures, bounds, stats),
-                  "pbr_gbuffer_raster_textured_culled");
-        else
-            Check(pbr_gbuffer_raster_culled(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
-                                            (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(),
-                                            ds->DepthPlane(), ds->StencilPlane(), w, scratch, scratch_bytes, bounds, stats),
-                  "pbr_gbuffer_raster_culled");
-        return;
-    }
-    if (maps) {
-        Check(pbr_gbuffer_raster_textured(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
-                                          (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(),
-                                          ds->DepthPlane(), ds->StencilPlane(), w, scratch, scratch_bytes, maps, textures, n_textures),
-              "pbr_gbuffer_raster_textured");
-        return;
-    }
-    Check(pbr_gbuffer_raster(mCtx, &mGlobal, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
-                             (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(), ds->DepthPlane(),
-                             ds->StencilPlane(), w, scratch, scratch_bytes), "pbr_gbuffer_raster");
+    Raster(d, &mGlobal, tile, (uint32_t*)a->DevicePtr(), (uint32_t*)b->DevicePtr(), (uint32_t*)c->DevicePtr(), ds, "pbr_gbuffer_raster");
 }
 
-void HipCommandList::RasterShadowMap(ShadingState* s, const pbr_global* light_g, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices,
-                                     uint32 n_indices, const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, uint32_t* a, uint32_t* b,
-                                     uint32_t* c, DeviceTexture2D* target, void* scratch, size_t scratch_bytes) {
+void HipCommandList::RasterShadowMap(ShadingState* s, const pbr_global* light_g, pbr_raster_desc d, uint32_t* a, uint32_t* b, uint32_t* c,
+                                     DeviceTexture2D* target) {
     if (!s || s->File() != "gbuffer.hlsl") throw HipException("RasterShadowMap: gbuffer.hlsl shading state expected");
-    if (!light_g || !vertices || !indices || !draws || !a || !b || !c || !target || !target->StencilPlane())
+    if (!light_g || !d.vertices || !d.indices || !d.draws || !a || !b || !c || !target || !target->StencilPlane())
         throw HipException("RasterShadowMap: null buffer, or the target is no depth-stencil texture");
     mDispatchCount++;
     FlushPendingBloom();
     const uint32 w = target->Width(), h = target->Height();
     const pbr_tile tile{0, 0, w, h, w, h};   // the whole map, whatever tile of the frame this device draws
-    Check(pbr_gbuffer_raster(mCtx, light_g, &tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, a, b, c,
-                             target->DepthPlane(), target->StencilPlane(), w, scratch, scratch_bytes), "pbr_gbuffer_raster (shadow map)");
+    Raster(d, light_g, tile, a, b, c, target, "pbr_gbuffer_raster (shadow map)");
+}
+
+void HipCommandList::Raster(pbr_raster_desc& d, const pbr_global* g, const pbr_tile& tile, uint32_t* a, uint32_t* b, uint32_t* c,
+                            DeviceTexture2D* ds, const char* what) {
+    d.g = g; d.tile = &tile;
+    d.A = a; d.B = b; d.C = c; d.depth = ds->DepthPlane(); d.stencil = ds->StencilPlane();
+    d.pitch = ds->Width();
+    Check(pbr_gbuffer_raster(mCtx, &d), what);
 }
 
 void HipCommandList::SunLight(ShadingState* s, DeviceTexture2D* shadow_map) {

@@ -86,24 +86,20 @@ public:
     // device planes) -> GBufferA/B/C of the bound pass
     void EncodeGBuffer(ShadingState* state, const float* m0, const float* m1, const float* m2,
                        DeviceTexture2D* a, DeviceTexture2D* b, DeviceTexture2D* c);
-    // gbuffer.hlsl's vertex + pixel shader with DefaultOpaque's raster state (pbr_gbuffer_raster): device vertex / index / draw
-    // arrays -> GBufferA/B/C and the depth-stencil target (the tile's rectangle in tile mode).  With maps (device, one per draw)
-    // the draws' texture maps are sampled from the host table of n_textures descriptors (pbr_gbuffer_raster_textured).
-    void RasterGBuffer(ShadingState* state, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
-                       const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, DeviceTexture2D* a, DeviceTexture2D* b,
-                       DeviceTexture2D* c, DeviceTexture2D* depth_stencil, void* scratch, size_t scratch_bytes,
-                       const pbr_draw_maps* maps = nullptr, const pbr_texture2d* textures = nullptr, uint32 n_textures = 0,
-                       const pbr_aabb* bounds = nullptr, pbr_cull_stats* stats = nullptr);
-    // With bounds (device, one per draw) the draws are culled on the device against the target's frustum first
-    // (pbr_gbuffer_raster_culled / _textured_culled; the planes are bit-identical) and stats (device, may be null) is written.
+    // gbuffer.hlsl's vertex + pixel shader with DefaultOpaque's raster state (pbr_gbuffer_raster): desc holds the device vertex /
+    // index / draw arrays, the scratch and the optional fields (GBufferPass::RasterInputs); g, tile, the planes and pitch are filled here
+    // -> GBufferA/B/C and the depth-stencil target (the tile's rectangle in tile mode).  With desc.maps (device, one per draw) the
+    // draws' texture maps are sampled from the host table desc.textures.  With desc.bounds (device, one per draw) the draws are
+    // culled on the device against the target's frustum first (the planes are bit-identical) and desc.stats (device, may be null) is written.
+    void RasterGBuffer(ShadingState* state, pbr_raster_desc desc, DeviceTexture2D* a, DeviceTexture2D* b, DeviceTexture2D* c,
+                       DeviceTexture2D* depth_stencil);
     // DrawBounds: the draws' local boxes from the uploaded buffers (pbr_draw_bounds), not a per-frame dispatch.
     void DrawBounds(const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices, uint32 n_indices,
                     const pbr_draw* draws, uint32 n_draws, pbr_aabb* out);
     // SunShadowPass: pbr_gbuffer_raster of the scene's meshes under the light's camera (pbr_sun_fit's pbr_global) into a depth-stencil
     // target of the map's size — always the whole map, in tile mode too — and three scratch colour planes nobody reads.
-    void RasterShadowMap(ShadingState* state, const pbr_global* light_g, const pbr_vertex* vertices, uint32 n_vertices, const uint32_t* indices,
-                         uint32 n_indices, const pbr_draw* draws, uint32 n_draws, uint32 max_triangles, uint32_t* a, uint32_t* b, uint32_t* c,
-                         DeviceTexture2D* target, void* scratch, size_t scratch_bytes);
+    void RasterShadowMap(ShadingState* state, const pbr_global* light_g, pbr_raster_desc desc, uint32_t* a, uint32_t* b, uint32_t* c,
+                         DeviceTexture2D* target);
     // SunLightPass: pbr_sun_light (the pbr_sun in `state`'s constants) into the bound render target; shadow_map null: no shadows
     void SunLight(ShadingState* state, DeviceTexture2D* shadow_map);
     void Present(DeviceTexture2D* tex) { mPresented = tex; }
@@ -155,6 +151,9 @@ private:
         DeviceTexture2D *Hdr = nullptr, *MipChain = nullptr, *Temp = nullptr;
         float Threshold = 0, Knee = 0;
     };
+    // the one pbr_gbuffer_raster call of RasterGBuffer and RasterShadowMap: camera, tile, planes and pitch into d
+    void Raster(pbr_raster_desc& d, const pbr_global* g, const pbr_tile& tile, uint32_t* a, uint32_t* b, uint32_t* c, DeviceTexture2D* ds,
+                const char* what);
     void FlushPendingBloom(uint32_t* hist = nullptr, float min_log = 0.0f, float inv_range = 0.0f);
     void IssueBloomTiled(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain, DeviceTexture2D* temp, uint32_t* hist, float min_log, float inv_range);
 

@@ -114,7 +114,7 @@ struct GBufferSource {
 // pbr_draw (ConstantBufferInstance + index range) per DrawModel call.  When draws are set, GBufferPass rasterizes them
 // (pbr_gbuffer_raster) instead of uploading a GBufferSource; it uploads the arrays once, after each change.
 // pbrh_set_textured_meshes adds one pbr_draw_maps per draw and the host texel chains (the reference's mip layout) they index:
-// GBufferPass then uploads the chains once, after each change, and rasterizes through pbr_gbuffer_raster_textured.
+// GBufferPass then uploads the chains once, after each change, and rasterizes through pbr_gbuffer_raster with maps.
 // A chain is decoded texels or, with PBR_TEX_BC1_BLOCKS in Format, the BC1 blocks of the reference's texture file (TextureFile.h),
 // which stay BC1 on the device: Texels holds pbr_texture2d_bytes(Width, Height, MipLevels, Format) bytes either way.
 struct TextureChain {

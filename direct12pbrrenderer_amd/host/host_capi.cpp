@@ -481,7 +481,7 @@ int pbrh_set_textured_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_
         if (n_draws > PBR_RASTER_MAX_DRAWS) throw HipException("pbrh_set_textured_meshes: more than PBR_RASTER_MAX_DRAWS draws");
         if (n_textures > PBR_RASTER_MAX_TEXTURES) throw HipException("pbrh_set_textured_meshes: more than PBR_RASTER_MAX_TEXTURES textures");
         std::vector<TextureChain> tex(n_textures);
-        for (uint32_t i = 0; i < n_textures; i++) {   // the chain's size from its descriptor (pbr_gbuffer_raster_textured checks the rest)
+        for (uint32_t i = 0; i < n_textures; i++) {   // the chain's size from its descriptor (pbr_gbuffer_raster with maps checks the rest)
             const pbr_texture2d& t = textures[i];
             // decoded texels or, with PBR_TEX_BC1_BLOCKS, BC1 blocks: either layout's size comes from the library
             const size_t bytes = pbr_texture2d_bytes(t.width, t.height, t.mip_levels, t.format);

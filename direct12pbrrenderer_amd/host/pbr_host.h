@@ -116,7 +116,7 @@ int pbrh_parse_hdr(const uint8_t* file, size_t bytes, uint32_t* w, uint32_t* h, 
  * width, height, depth, mips; uint8 DXGI format; 3 pad bytes), a uint32 payload byte count at offset 12, the payload (the chain
  * as BC1 blocks) at offset 16.  *texture (a pbr_texture2d, 24 B) = the description with format = the stored format |
  * PBR_TEX_BC1_BLOCKS and texels = blocks; the payload is copied to blocks (blocks_bytes >= pbr_texture2d_bytes of the
- * description; blocks NULL: the description only, texels NULL).  What it fills goes to pbr_gbuffer_raster_textured /
+ * description; blocks NULL: the description only, texels NULL).  What it fills goes to pbr_raster_desc.textures /
  * pbrh_set_textured_meshes as it is, or through pbr_bc1_decode.  Returns 0, or -1 + reason in err with nothing written: a
  * truncated file, a byte count that disagrees with pbr_texture2d_bytes or the file's size, depth != 1, an unknown format, a
  * buffer too small. */
@@ -154,11 +154,11 @@ int pbrh_set_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices,
                     const void* draws, uint32_t n_draws);
 /* pbrh_set_meshes plus textures: maps = n_draws pbr_draw_maps (20 B), textures = n_textures descriptors whose `texels` point to
  * HOST chains in the reference's layout (pbr_texture2d records, include/pbr_hip.h).  Everything is copied here; GBufferPass uploads the
- * chains once after each change and rasterizes through pbr_gbuffer_raster_textured. */
+ * chains once after each change and rasterizes through pbr_gbuffer_raster with maps. */
 int pbrh_set_textured_meshes(pbrh_renderer* r, const void* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
                              const void* draws, uint32_t n_draws, const void* maps, const void* textures, uint32_t n_textures);
 /* Scene::CullModel for the meshes (default off): GBufferPass computes the draws' bounds on the GPU when it uploads the meshes
- * (pbr_draw_bounds) and rasterizes through pbr_gbuffer_raster_culled / pbr_gbuffer_raster_textured_culled: draws outside the
+ * (pbr_draw_bounds) and rasterizes through pbr_gbuffer_raster with bounds: draws outside the
  * target's frustum are not set up; the frame is bit-identical.  Works with pbrh_set_meshes and pbrh_set_textured_meshes, before or
  * after them. */
 int pbrh_set_model_culling(pbrh_renderer* r, int on);

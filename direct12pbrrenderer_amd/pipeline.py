@@ -374,10 +374,10 @@ class DeferredFrame:
         planes of the shaded rectangle S before the cluster, sky and shade passes (until upload_gbuffer replaces them).
         maps (structs.DRAW_MAPS_DTYPE, one per draw) and textures (the (device tensor, structs.Texture2D) pairs of
         PbrContext.upload_texture or bc1_decode, BC1-resident ones included, which the frame holds on to): the draws' texture maps, rasterized by
-        pbr_gbuffer_raster_textured when any draw has one.  Without them, or with every map NO_MAP, the call is the
+        pbr_gbuffer_raster's `maps` when any draw has one.  Without them, or with every map NO_MAP, the call is the
         constant-material one.
-        cull: every render() culls the draws against the frustum of the shaded rectangle on the device (pbr_gbuffer_raster_culled /
-        pbr_gbuffer_raster_textured_culled; the G-buffer is bit-identical) and records cull_stats().  bounds: the draws' local boxes
+        cull: every render() culls the draws against the frustum of the shaded rectangle on the device (pbr_gbuffer_raster's
+        `bounds`; the G-buffer is bit-identical) and records cull_stats().  bounds: the draws' local boxes
         (structs.AABB_DTYPE, one per draw; every vertex of a draw inside its box); without them pbr_draw_bounds makes them here, once."""
         s, ctx = self.spec, self.ctx
         draws = np.ascontiguousarray(draws)
@@ -411,23 +411,24 @@ class DeferredFrame:
                     raise ValueError("set_meshes: one bound per draw")
                 m["bounds"] = ctx.upload(b)
             m["cull_stats"] = ctx.alloc_cull_stats()
-        self.gb = {"A": ctx.zeros((s.sh, s.sw), torch.int32), "B": ctx.zeros((s.sh, s.sw), torch.int32),
-                   "C": ctx.zeros((s.sh, s.sw), torch.int32), "depth": ctx.zeros((s.sh, s.sw), torch.float32),
-                   "stencil": ctx.zeros((s.sh, s.sw), torch.uint8)}
+        self.gb = self._planes(s.sh, s.sw)
+
+    def _planes(self, h, w):
+        """the five planes of an h x w G-buffer, zeroed"""
+        z = self.ctx.zeros
+        return {"A": z((h, w), torch.int32), "B": z((h, w), torch.int32), "C": z((h, w), torch.int32), "depth": z((h, w), torch.float32),
+                "stencil": z((h, w), torch.uint8)}
+
+    def _raster(self, g, tile, gb, pitch, scratch, **optional):
+        """pbr_gbuffer_raster of the meshes under camera g into the planes gb; optional: gbuffer_raster's maps, textures, bounds, stats"""
+        m = self.mesh
+        self.ctx.gbuffer_raster(g, tile, m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"], m["n_draws"],
+                                m["max_triangles"], gb["A"], gb["B"], gb["C"], gb["depth"], gb["stencil"], pitch, scratch, **optional)
 
     def rasterize(self):
-        m, gb = self.mesh, self.gb
-        args = (self.g, self.tile, m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"], m["n_draws"],
-                m["max_triangles"], gb["A"], gb["B"], gb["C"], gb["depth"], gb["stencil"], self.spec.sw, m["scratch"])
-        if "bounds" in m:
-            if "maps" in m:
-                self.ctx.gbuffer_raster_textured_culled(*args, m["maps"], m["textures"], m["bounds"], m["cull_stats"])
-            else:
-                self.ctx.gbuffer_raster_culled(*args, m["bounds"], m["cull_stats"])
-        elif "maps" in m:
-            self.ctx.gbuffer_raster_textured(*args, m["maps"], m["textures"])
-        else:
-            self.ctx.gbuffer_raster(*args)
+        m = self.mesh
+        self._raster(self.g, self.tile, self.gb, self.spec.sw, m["scratch"], maps=m.get("maps"), textures=m.get("textures"),
+                     bounds=m.get("bounds"), stats=m.get("cull_stats"))
 
     # Default shadow bias (bias_const, bias_slope), in light-clip depth units, for the default 2048^2 map.  A receiver plane tilted by
     # theta against the light changes its light depth by tan(theta) per unit across the map, and pcf 3 compares against taps up to two
@@ -498,12 +499,9 @@ class DeferredFrame:
         # bias or direction allocates nothing.  A / B / C / stencil and the scratch are kept for the next raster (refresh_shadow_map)
         sm = self._sun_planes
         if sm is None or sm["n"] != n or sm["tris"] != m["max_triangles"]:
-            sm = {"n": n, "tris": m["max_triangles"], "A": ctx.zeros((n, n), torch.int32), "B": ctx.zeros((n, n), torch.int32),
-                  "C": ctx.zeros((n, n), torch.int32), "depth": ctx.zeros((n, n), torch.float32), "stencil": ctx.zeros((n, n), torch.uint8),
-                  "scratch": ctx.alloc_raster_scratch(n, n, m["max_triangles"])}
+            sm = dict(self._planes(n, n), n=n, tris=m["max_triangles"], scratch=ctx.alloc_raster_scratch(n, n, m["max_triangles"]))
             self._sun_planes = sm
-        ctx.gbuffer_raster(light_g, Tile(0, 0, n, n, n, n), m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"], m["n_draws"],
-                           m["max_triangles"], sm["A"], sm["B"], sm["C"], sm["depth"], sm["stencil"], n, sm["scratch"])
+        self._raster(light_g, Tile(0, 0, n, n, n, n), sm, n, sm["scratch"])
         sun["light_g"], sun["map"] = light_g, (sm["depth"], n, n, n)
         sun["struct"] = make_sun(sun["direction"], sun["luminance"], lvp, sun["bias"], sun["pcf"])
 

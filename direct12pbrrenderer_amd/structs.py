@@ -84,6 +84,15 @@ class ShadeDesc(C.Structure):
                    ("hdr_pitch", C.c_uint32), ("n_rects", C.c_uint32)])
 
 
+class RasterDesc(C.Structure):
+    """pbr_raster_desc: one G-buffer raster call (include/pbr_hip.h); 8-byte fields first, then the 32-bit ones: no padding.
+    g, tile and textures are HOST addresses (of a Global, a Tile and a Texture2D array the caller keeps alive); maps, textures and
+    n_textures unset: the constant-material raster; bounds and stats unset: no model cull."""
+    _fields_ = ([(n, C.c_void_p) for n in ("g", "tile", "vertices", "indices", "draws", "A", "B", "C", "depth", "stencil", "scratch")]
+                + [("scratch_bytes", C.c_size_t)] + [(n, C.c_void_p) for n in ("maps", "textures", "bounds", "stats")]
+                + [(n, C.c_uint32) for n in ("n_vertices", "n_indices", "n_draws", "max_triangles", "pitch", "n_textures")])
+
+
 MAX_VIEWS = 16                                        # PBR_MAX_VIEWS (include/pbr_hip.h)
 
 

@@ -549,7 +549,9 @@ typedef struct pbr_draw {
  * not for large ones (a 4K tile of 4 M triangles would read 32 400 x 4 M records). */
 size_t pbr_gbuffer_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
 size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
-/* GBufferPass::Execute + DrawModel (DeferredPipeline.cpp:138-185) for constant-material draws: gbuffer.hlsl's vertex shader
+/* pbr_gbuffer_raster, ONE call described by a HOST struct, pbr_raster_desc; both are declared below, after the types of the optional
+ * fields.  This block is the contract of every call; the two after it say what `maps` and `bounds` add.
+ * GBufferPass::Execute + DrawModel (DeferredPipeline.cpp:138-185) for constant-material draws: gbuffer.hlsl's vertex shader
  * (position_ws = Model (p, 1), normal_ws = transpose(InvModel) (n, 0), clip = Projection (View position_ws); g->View and
  * g->Projection), DefaultOpaque's fixed-function state and ps_main's Use*Map == false branches (AO = 0).  Draws run in array order.
  *   Clears: A = B = C = 0, depth = 1, stencil = 0.  Viewport (0, 0, full_w, full_h), depth range [0, 1].
@@ -558,7 +560,7 @@ size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_t
  *   clockwise in y-down screen space) and zero-area triangles are dropped.  Depth: z / w linear in screen space, clamped to [0, 1],
  *   test LESS with write; stencil counts the depth-passing fragments (INCR_SAT).  A / B / C: the first fragment in draw order
  *   that reaches the pixel's nearest depth; its normal interpolated perspective-correctly, encoded as pbr_gbuffer_encode.
- *   Accuracy of the interpolated attributes (the normal here; tangent and uv of the textured call): the barycentrics come from the
+ *   Accuracy of the interpolated attributes (the normal here; tangent and uv with d->maps): the barycentrics come from the
  *   triangle's 2D homogeneous edge planes, formed in fp64 about an integer pixel origin within the triangle's on-screen bounding box and
  *   rounded once to fp32, evaluated in fp32 at the pixel's exact offset from that origin.  Their error is a few 2^-24 of sum |lambda_i|
  *   (4-5 at the median, about 20 at worst for well-shaped triangles; the bound per pixel is derived in tests/raster_truth.py) and does
@@ -572,12 +574,7 @@ size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_t
  * Limits (PBR_ERR_INVALID, nothing enqueued): n_draws <= PBR_RASTER_MAX_DRAWS, max_triangles <= PBR_RASTER_MAX_TRIANGLES,
  * full_w, full_h <= PBR_RASTER_MAX_SIZE; null pointers, zero counts, a tile outside its frame, pitch < w, scratch below
  * pbr_gbuffer_raster_min_scratch_bytes(w, h, max_triangles), buffers not 4-byte (scratch: 16-byte) aligned are refused.
- * Asynchronous: six launches on the context's stream, no host synchronisation, no allocation. */
-pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                              void* scratch, size_t scratch_bytes);
+ * A null descriptor is refused too.  Asynchronous: six launches on the context's stream, no host synchronisation, no allocation. */
 
 /* ---- Textured G-buffer rasterization (new): gbuffer.hlsl's Use*Map == true branches ------------------------------------- */
 /* A 2D texture with its whole mip chain in device memory, as the reference creates it (ResourceDef.cpp:53-66, TextureInfo and
@@ -607,7 +604,7 @@ typedef struct pbr_texture2d {
     uint32_t mip_levels;           /* 1 .. floor(log2(min(width, height))) + 1 */
     uint32_t format;               /* PBR_TEX_*, optionally | PBR_TEX_BC1_BLOCKS */
 } pbr_texture2d;
-/* Bytes of a whole chain of either kind (format with or without PBR_TEX_BC1_BLOCKS); 0 for a description pbr_gbuffer_raster_textured
+/* Bytes of a whole chain of either kind (format with or without PBR_TEX_BC1_BLOCKS); 0 for a description pbr_gbuffer_raster
  * would refuse (a zero size or one above PBR_TEX_MAX_SIZE, mip_levels out of range, an unknown stored format, any other bit of format). */
 size_t pbr_texture2d_bytes(uint32_t width, uint32_t height, uint32_t mip_levels, uint32_t format);
 /* The reference's load-time decode (TextureDecompressInternal) of a whole chain on the GPU: blocks (device, 8-byte aligned, the
@@ -678,29 +675,25 @@ typedef struct pbr_draw_maps {
  *   f == 0 ? a : fmaf(b, f, a (1 - f)) (x first, then y, then the levels), fp32 weights (not D3D's 8-bit fixed point). */
 size_t pbr_gbuffer_raster_textured_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
 size_t pbr_gbuffer_raster_textured_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
-/* pbr_gbuffer_raster with the pixel shader's map branches (gbuffer.hlsl:88-149): the same arguments and contract, plus
+/* pbr_gbuffer_raster with maps != NULL: the pixel shader's map branches (gbuffer.hlsl:88-149), the same contract, plus
  *   maps: DEVICE array of n_draws records (the draw's maps); textures: HOST array of n_textures descriptors (copied by value).
+ *   scratch is laid out, and its minimum sized, by the two _textured_ functions above.
  * Vertex stage adds tangent_ws = transpose(InvModel) (tangent, 0) (the normal's rule) and passes uv through; both are
  * interpolated perspective-correctly like the normal.  With a map: albedo = decode_gamma(sample.rgb); normal = normalize(ts.x t
  * + ts.y b + ts.z n) with n = normalize(normal_ws), t = normalize(tangent_ws), b = cross(n, t), ts = sample.rgb * 2 - 1;
- * roughness, metallic, AO = sample.x.  Without one: the constant (AO 0), bit-identical to pbr_gbuffer_raster.
+ * roughness, metallic, AO = sample.x.  Without one: the constant (AO 0), bit-identical to the call with maps == NULL.
  * Guard on device data: a draw with a map index >= n_textures (other than PBR_NO_MAP) is dropped.
  * The table may mix decoded and BC1-resident textures (PBR_TEX_BC1_BLOCKS).  A BC1-resident texture samples exactly as the chain
  * pbr_bc1_decode produces from it (stored format = format & 0xff) would: the sampler reads each distinct block of a bilinear
  * footprint once (one 8-byte load), builds its palette once, picks the taps by their indices and then runs the same decode
  * tables, lerp order and LOD rule, so all five planes are bit-identical.  A table without a BC1 texture runs the kernel it ran
  * before the flag existed.
- * Refusals (PBR_ERR_INVALID, nothing enqueued): those of pbr_gbuffer_raster; maps null or not 4-byte aligned; n_textures >
+ * Refusals (PBR_ERR_INVALID, nothing enqueued): those of the call without maps; maps not 4-byte aligned; n_textures >
  * PBR_RASTER_MAX_TEXTURES, or textures null with n_textures > 0; a texture of another format (with PBR_TEX_BC1_BLOCKS: another
  * stored format), any other bit set in format, a zero size or one above PBR_TEX_MAX_SIZE, mip_levels 0 or above
  * floor(log2(min(w, h))) + 1, null or misaligned texels (BC1 blocks: 8 bytes); scratch below
- * pbr_gbuffer_raster_textured_min_scratch_bytes. */
-pbr_status pbr_gbuffer_raster_textured(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                       const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                                       const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                                       uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                                       void* scratch, size_t scratch_bytes,
-                                       const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures);
+ * pbr_gbuffer_raster_textured_min_scratch_bytes.  With maps == NULL (the constant-material raster): textures non-null or
+ * n_textures != 0. */
 
 /* ---- Model culling (new): Scene::CullModel + GBufferPass's mCullingStatus (DeferredPipeline.cpp:138-153) on the device ---------- */
 /* A draw's bound in its local (vertex) space, 24 B; one per draw, parallel to the pbr_draw array. */
@@ -721,7 +714,7 @@ typedef struct pbr_cull_stats {
  * pointer, a zero count, n_draws > PBR_RASTER_MAX_DRAWS. */
 pbr_status pbr_draw_bounds(pbr_ctx* ctx, const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
                            const pbr_draw* draws, uint32_t n_draws, pbr_aabb* out);
-/* pbr_gbuffer_raster / pbr_gbuffer_raster_textured with the model cull: the same arguments and contract, plus bounds (DEVICE, one
+/* pbr_gbuffer_raster with bounds != NULL, with or without maps: the model cull, the same contract, plus bounds (DEVICE, one
  * pbr_aabb per draw) and stats (DEVICE, may be NULL; written by the call's second launch).  A culled draw contributes no triangle:
  * it is neither set up nor binned.  max_triangles keeps its meaning (the sum over ALL draws); scratch sizes do not change.
  * The rule, pinned (tests/raster_cull_ref.py restates it; DESIGN.md derives it), fp32 unless stated, no contraction:
@@ -742,20 +735,31 @@ pbr_status pbr_draw_bounds(pbr_ctx* ctx, const pbr_vertex* vertices, uint32_t n_
  * model, and it culls against the whole frame's frustum.  Neither is copied.
  * THE INVARIANT: provided every vertex of every triangle of draw d lies in bounds[d] (pbr_draw_bounds gives such bounds), the five
  * planes are bit-identical to the same call without bounds, for every camera, tile, scratch size and texture format.
- * Refusals (PBR_ERR_INVALID, nothing enqueued): those of the call without bounds; bounds null or not 4-byte aligned; stats non-null
- * and not 4-byte aligned.  Asynchronous: the same six launches, no host synchronisation, no allocation. */
-pbr_status pbr_gbuffer_raster_culled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                     const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                                     const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                                     uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                                     void* scratch, size_t scratch_bytes, const pbr_aabb* bounds, pbr_cull_stats* stats);
-pbr_status pbr_gbuffer_raster_textured_culled(pbr_ctx* ctx, const pbr_global* g, const pbr_tile* tile,
-                                              const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
-                                              const pbr_draw* draws, uint32_t n_draws, uint32_t max_triangles,
-                                              uint32_t* A, uint32_t* B, uint32_t* C, float* depth, uint8_t* stencil, uint32_t pitch,
-                                              void* scratch, size_t scratch_bytes,
-                                              const pbr_draw_maps* maps, const pbr_texture2d* textures, uint32_t n_textures,
-                                              const pbr_aabb* bounds, pbr_cull_stats* stats);
+ * Refusals (PBR_ERR_INVALID, nothing enqueued): those of the call without bounds; bounds not 4-byte aligned; stats non-null and
+ * not 4-byte aligned, or non-null while bounds is NULL.  Asynchronous: the same six launches, no host synchronisation, no allocation. */
+/* The descriptor: 8-byte fields first, then the 32-bit ones (152 bytes, no padding), as pbr_shade_desc. */
+typedef struct pbr_raster_desc {
+    const pbr_global* g;
+    const pbr_tile* tile;
+    const pbr_vertex* vertices;
+    const uint32_t* indices;
+    const pbr_draw* draws;
+    uint32_t* A;
+    uint32_t* B;
+    uint32_t* C;
+    float* depth;
+    uint8_t* stencil;
+    void* scratch;
+    size_t scratch_bytes;
+    const pbr_draw_maps* maps;         /* maps, textures NULL and n_textures 0: the constant-material raster */
+    const pbr_texture2d* textures;
+    const pbr_aabb* bounds;            /* bounds, stats NULL: no model cull */
+    pbr_cull_stats* stats;
+    uint32_t n_vertices, n_indices, n_draws, max_triangles;
+    uint32_t pitch;
+    uint32_t n_textures;
+} pbr_raster_desc;
+pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_raster_desc* d);
 
 /* bloom_prefilter.hlsl:17-60 (DeferredPipeline.cpp:411-427): hdr (w x h) -> out (w>>1 x h>>1). */
 pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h,

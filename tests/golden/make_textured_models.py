@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes tests/golden/textured_models.npz: the textured models of the reference's scene asset (barrel, rock, suitcase, tile) as
-DATA, for pbr_gbuffer_raster_textured.
+DATA, for pbr_gbuffer_raster with maps.
 
 Build container only (it reads /root/reference, which does not travel to the GPU box):
 

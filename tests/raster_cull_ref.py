@@ -1,4 +1,4 @@
-"""The model cull of pbr_gbuffer_raster_culled (include/pbr_hip.h, DESIGN.md "Model culling") restated in numpy: the six planes in
+"""The model cull of pbr_gbuffer_raster with bounds (include/pbr_hip.h, DESIGN.md "Model culling") restated in numpy: the six planes in
 float64 rounded once to float32, the world box and the test in float32 in the pinned operation order — and the same geometry in
 float64 (the exact planes, the eight corners), which the fp32 rule is held to in test_raster_cull_cpu.py.
 

@@ -1,4 +1,4 @@
-"""numpy restatement of pbr_gbuffer_raster_textured (include/pbr_hip.h, direct12pbrrenderer_amd/csrc/gbuffer_raster.hip).
+"""numpy restatement of pbr_gbuffer_raster with maps (include/pbr_hip.h, direct12pbrrenderer_amd/csrc/gbuffer_raster.hip).
 
 The geometry (vertex stage, clipping, snap, coverage, depth, stencil, the winner) is tests/raster_ref.py's.  On top of it, in the
 kernel's operation order: tangent_ws by the normal's rule and uv per vertex, their perspective-correct interpolation from the
@@ -154,7 +154,7 @@ def _normalize(x, y, z):
 
 
 def raster_textured(g, tile, vertices, indices, draws, maps, textures, orc, max_triangles=None, taps=None):
-    """The five planes pbr_gbuffer_raster_textured writes for this tile (textures: the texture dicts, in table order).
+    """The five planes pbr_gbuffer_raster with maps writes for this tile (textures: the texture dicts, in table order).
     taps: a dict that receives the covered pixels (ys, xs), their winner (t), the interpolated normal (nrm), tangent (tan) and uv
     (u, v) before any map is applied, and the quad's uv differences (dxu, dxv, dyu, dyv)."""
     recs, c, n, dr, org = raster_ref.setup(g, tile, vertices, indices, draws, max_triangles)

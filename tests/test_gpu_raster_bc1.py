@@ -1,5 +1,5 @@
 """BC1-resident textures on the GPU (include/pbr_hip.h: PBR_TEX_BC1_BLOCKS): pbr_bc1_decode against the numpy restatement
-(tests/bc1_ref.py) bit for bit, and pbr_gbuffer_raster_textured sampling BC1 blocks in place against the same call on the decoded
+(tests/bc1_ref.py) bit for bit, and pbr_gbuffer_raster with maps sampling BC1 blocks in place against the same call on the decoded
 chains — all five planes bit-identical — plus the CPU restatement of the raster, tiles, scratch sizes, refusals, DeferredFrame and
 the C++ host graph.  Reads tests/golden/ only."""
 import os
@@ -179,19 +179,21 @@ def test_refusals_enqueue_nothing(ctx):
         f.update(kw)
         return Texture2D(f["texels"], f["width"], f["height"], f["mip_levels"], f["format"])
 
-    cases = [[bad(format=29 | TEX_BC1_BLOCKS)], [bad(format=TEX_BC1_BLOCKS)],                 # the flag with an unknown stored format
-             [bad(texels=base + 4)], [bad(texels=base + 1)],                                   # BC1 texels not 8-byte aligned
-             [bad(format=TEX_B8G8R8A8_UNORM | 0x200)], [bad(format=TEX_B8G8R8A8_UNORM | TEX_BC1_BLOCKS | 0x10000)],
-             [bad(format=TEX_R8_UNORM | TEX_BC1_BLOCKS | 0x80000000)],                         # any other bit of format
-             [bad(width=0)], [bad(mip_levels=5)], [bad(texels=0)], [good, bad(format=0x1FF)]]
+    fmt, texels = "unknown texture format", "texels null or not aligned"
+    cases = [([bad(format=29 | TEX_BC1_BLOCKS)], fmt), ([bad(format=TEX_BC1_BLOCKS)], fmt),   # the flag with an unknown stored format
+             ([bad(texels=base + 4)], texels), ([bad(texels=base + 1)], texels),               # BC1 texels not 8-byte aligned
+             ([bad(format=TEX_B8G8R8A8_UNORM | 0x200)], fmt), ([bad(format=TEX_B8G8R8A8_UNORM | TEX_BC1_BLOCKS | 0x10000)], fmt),
+             ([bad(format=TEX_R8_UNORM | TEX_BC1_BLOCKS | 0x80000000)], fmt),                  # any other bit of format
+             ([bad(width=0)], "texture size zero or above"), ([bad(mip_levels=5)], "mip_levels 0 or above"), ([bad(texels=0)], texels),
+             ([good, bad(format=0x1FF)], fmt)]
     n = 2
     planes = [ctx.zeros((h, w), torch.int32) for _ in range(3)] + [ctx.zeros((h, w), torch.float32), ctx.zeros((h, w), torch.uint8)]
     for p in planes:
         p.fill_(7)
     scratch = ctx.alloc_textured_raster_scratch(w, h, n)
     dv, di, dd, dm = ctx.upload(v), ctx.upload(i), ctx.upload(d), ctx.upload(ms.maps())
-    for descs in cases:
-        with pytest.raises(PbrError, match="pbr_gbuffer_raster_textured"):
+    for descs, why in cases:
+        with pytest.raises(PbrError, match="pbr_gbuffer_raster: " + why):
             ctx.gbuffer_raster_textured(g, tile, dv, len(v), di, len(i), dd, len(d), n, *planes, w, scratch, dm, descs)
     # pbr_bc1_decode's own refusals: the output stays as it was
     out = ctx.zeros((texture2d_bytes(16, 8, 4, TEX_B8G8R8A8_UNORM) + 8,), torch.uint8)

@@ -1,5 +1,5 @@
-"""Model culling on the GPU: pbr_draw_bounds against scene.draw_bounds bit for bit; pbr_gbuffer_raster_culled and
-pbr_gbuffer_raster_textured_culled against the unculled calls bit for bit, with pbr_cull_stats equal to the counts of the numpy rule
+"""Model culling on the GPU: pbr_draw_bounds against scene.draw_bounds bit for bit; pbr_gbuffer_raster with bounds (with and
+without maps) against the unculled calls bit for bit, with pbr_cull_stats equal to the counts of the numpy rule
 (tests/raster_cull_ref.py); bounds that never cull, stats == null, the refusals, DeferredFrame.set_meshes(cull=True) and the host
 graph's GBufferPass."""
 import os

@@ -1,4 +1,4 @@
-"""pbr_gbuffer_raster_textured on the GPU: parity with the numpy restatement (tests/raster_tex_ref.py) on random textured scenes,
+"""pbr_gbuffer_raster with maps on the GPU: parity with the numpy restatement (tests/raster_tex_ref.py) on random textured scenes,
 and the sampler's contract against independent truths — no maps equals pbr_gbuffer_raster, mip level selection, wrap
 periodicity, an analytic normal-map frame, the C channels — plus tiles, scratch sizes and refusals."""
 import numpy as np
@@ -272,16 +272,18 @@ def test_refusals_enqueue_nothing(ctx):
         f.update(kw)
         return Texture2D(f["texels"], f["width"], f["height"], f["mip_levels"], f["format"])
 
-    cases = [[bad(format=29)], [bad(format=0)], [bad(width=0)], [bad(height=0)], [bad(width=16385, height=16385)],
-             [bad(mip_levels=0)], [bad(mip_levels=5)], [bad(texels=0)], [bad(texels=base + 2)], [good] * 65]
+    fmt, size, mips, texels = "unknown texture format", "texture size zero or above", "mip_levels 0 or above", "texels null or not aligned"
+    cases = [([bad(format=29)], fmt), ([bad(format=0)], fmt), ([bad(width=0)], size), ([bad(height=0)], size),
+             ([bad(width=16385, height=16385)], size), ([bad(mip_levels=0)], mips), ([bad(mip_levels=5)], mips), ([bad(texels=0)], texels),
+             ([bad(texels=base + 2)], texels), ([good] * 65, "more textures than")]
     n = 2
     planes = [ctx.zeros((h, w), torch.int32) for _ in range(3)] + [ctx.zeros((h, w), torch.float32), ctx.zeros((h, w), torch.uint8)]
     for p in planes:
         p.fill_(7)
     scratch = ctx.alloc_textured_raster_scratch(w, h, n)
     dv, di, dd, dm = ctx.upload(v), ctx.upload(i), ctx.upload(d), ctx.upload(ms.maps())
-    for descs in cases:
-        with pytest.raises(PbrError, match="pbr_gbuffer_raster_textured"):
+    for descs, why in cases:
+        with pytest.raises(PbrError, match="pbr_gbuffer_raster: " + why):
             ctx.gbuffer_raster_textured(g, tile, dv, len(v), di, len(i), dd, len(d), n, *planes, w, scratch, dm, descs)
     with pytest.raises(PbrError):        # scratch of the constant raster is below the textured minimum
         small = ctx.alloc_raster_scratch(w, h, n, minimum=True)
@@ -400,7 +402,7 @@ def test_reference_scene_raster_and_shade(ctx, orc):
 @pytest.mark.gpu
 def test_host_graph_textured_meshes(ctx, orc):
     """pbrh_set_textured_meshes: the C++ pass graph's GBufferPass rasterizes the reference scene with its hero models through
-    pbr_gbuffer_raster_textured; its G-buffer planes equal the direct C call's with the host's camera."""
+    pbr_gbuffer_raster with maps; its G-buffer planes equal the direct C call's with the host's camera."""
     import ctypes as C
     from direct12pbrrenderer_amd import synth
     from direct12pbrrenderer_amd.host import HostRenderer

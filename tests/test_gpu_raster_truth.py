@@ -1,4 +1,4 @@
-"""pbr_gbuffer_raster / pbr_gbuffer_raster_textured against the float64 truth of the interpolated attributes
+"""pbr_gbuffer_raster (without and with maps) against the float64 truth of the interpolated attributes
 (tests/raster_truth.py): one tile of at most 64 x 64 pixels and a few hundred small triangles per case, at frame sizes up to
 PBR_RASTER_MAX_SIZE with the tile in the frame's far corner, where planes formed or evaluated in float32 at absolute pixel positions
 lose the barycentrics.  The normal's bytes must be admissible under the truth's band (the byte rule of raster_truth); the level a

@@ -1,4 +1,4 @@
-"""The model cull of pbr_gbuffer_raster_culled on the CPU (tests/raster_cull_ref.py restates the rule pinned in pbr_hip.h):
+"""The model cull of pbr_gbuffer_raster with bounds on the CPU (tests/raster_cull_ref.py restates the rule pinned in pbr_hip.h):
 soundness of the fp32 rule against the float64 geometry, bit-identity of the raster oracle's planes with the culled draws removed,
 the defects the rule must not have, MeshScene.bounds() against a loop, and the relation to the reference's own cull."""
 import os

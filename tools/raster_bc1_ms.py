@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times pbr_gbuffer_raster_textured with BC1-resident textures against the same textures decoded by pbr_bc1_decode (HIP events on
+"""Times pbr_gbuffer_raster with maps with BC1-resident textures against the same textures decoded by pbr_bc1_decode (HIP events on
 the context's stream, after warm-up) and writes profiles/raster_bc1_ms.txt.
 
 Scene and camera: those of tools/raster_tex_ms.py (the reference scene's 33 constant-material models plus barrel, rock, suitcase
@@ -98,7 +98,7 @@ def main():
     bytes_bc1 = sum(texture2d_bytes(w0, h0, m0, fmt | TEX_BC1_BLOCKS) for w0, h0, m0, fmt in infos)
     bytes_dec = sum(texture2d_bytes(*inf) for inf in infos)
 
-    lines = [f"pbr_gbuffer_raster_textured, BC1-resident against decoded-resident textures, {torch.cuda.get_device_name(0)}, HIP events, "
+    lines = [f"pbr_gbuffer_raster with maps, BC1-resident against decoded-resident textures, {torch.cuda.get_device_name(0)}, HIP events, "
              f"{a.iters} calls after 5 warm-up calls",
              "scene: the 33 constant models + barrel, rock, suitcase, tile (fixture meshes; 20 maps of seeded random BC1 blocks at the "
              "assets' sizes, levels and stored formats: 1024^2 x 11 / 2048^2 x 12); the planes of the two rows are equal (checked)",

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times pbr_gbuffer_raster_culled / pbr_gbuffer_raster_textured_culled against the unculled calls and writes
+"""Times pbr_gbuffer_raster with bounds against the unculled calls and writes
 profiles/raster_cull_ms.txt.
 
 Each round is a fresh process.  In a round every scene is warmed up for both calls, then blocks of `--iters` culled calls and

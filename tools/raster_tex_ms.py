@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times pbr_gbuffer_raster_textured against the constant-material raster (HIP events on the context's stream, after warm-up) and
+"""Times pbr_gbuffer_raster with maps against the constant-material raster (HIP events on the context's stream, after warm-up) and
 writes profiles/raster_tex_ms.txt.
 
 Scene: the reference scene's 33 constant-material models (tests/golden/sphere_grid.npz) plus its four textured models (barrel,
@@ -52,7 +52,7 @@ def main():
         ch = 1 if fmt == TEX_R8_UNORM else 4
         lv0 = rng.integers(0, 256, (h0, w0, ch) if ch == 4 else (h0, w0), dtype=np.uint8)
         textures.append(ctx.upload_texture(scene.pack_chain(scene.mip_chain(lv0, mips0)), w0, h0, mips0, fmt))
-    lines = [f"pbr_gbuffer_raster_textured, {torch.cuda.get_device_name(0)}, HIP events, {a.iters} calls after 5 warm-up calls; "
+    lines = [f"pbr_gbuffer_raster with maps, {torch.cuda.get_device_name(0)}, HIP events, {a.iters} calls after 5 warm-up calls; "
              "shade = pbr_deferred_shade of the same frame (8 lights, 16^2 env / 32^2 LUT)",
              "scene: the 33 constant models + barrel, rock, suitcase, tile (fixture meshes; synthetic textures at the assets' sizes, "
              "levels and formats: 1024^2 x 11 / 2048^2 x 12)",

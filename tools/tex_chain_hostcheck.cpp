@@ -9,7 +9,7 @@
 //       2d W H MIPS FORMAT bytes N align A stored STORED_WHY|ok texel_bytes T bgra B
 //         first_block  the sixteen entries          first_texel  the fifteen entries
 //         search       level_of_block at first_block[l] - 1 and at first_block[l], for l = 1 .. MIPS - 1
-//     `refused` is the check of pbr_texture2d_bytes and pbr_gbuffer_raster_textured (the flag allowed), `stored` that of
+//     `refused` is the check of pbr_texture2d_bytes and pbr_gbuffer_raster with maps (the flag allowed), `stored` that of
 //     pbr_texture2d_gen_mips, pbr_bc1_encode and pbr_bc1_decode (a stored format alone); A is the alignment tex2d::aligned asks for.
 //   cube SIZE MIPS
 //       cube SIZE MIPS refused: WHY
