@@ -111,13 +111,17 @@ class Truth:
         p00, p10, p01 = (self.attribute(x, y, uv) for x, y in self.quad())
         return p10 - p00, p01 - p00
 
-    def lod(self, uv, tex_w, tex_h, mips):
-        ddx, ddy = self.uv_differences(uv)
+    def footprint(self, ddx, ddy, tex_w, tex_h):
+        """rho: the longer of the quad's two uv differences, in mip-0 texels"""
         size = np.array([tex_w, tex_h], f64)
-        rho = np.maximum(np.hypot(*(ddx * size).T), np.hypot(*(ddy * size).T))
+        return np.maximum(np.hypot(*(ddx * size).T), np.hypot(*(ddy * size).T))
+
+    def lod(self, uv, tex_w, tex_h, mips, clamp=True):
+        """lambda [k], clamped to the chain; clamp=False: as log2 gives it (tests/sampler_truth.py clamps the ends of its interval)"""
+        rho = self.footprint(*self.uv_differences(uv), tex_w, tex_h)
         with np.errstate(divide="ignore"):
             lam = np.where(rho > 0, np.log2(np.where(rho > 0, rho, 1.0)), 0.0)
-        return np.clip(lam, 0.0, mips - 1.0)
+        return np.clip(lam, 0.0, mips - 1.0) if clamp else lam
 
     def here(self, attr):
         return self.attribute(self.gx, self.gy, attr)
@@ -162,8 +166,9 @@ class Band:
         eye = np.broadcast_to(np.eye(3), (len(self.t.gx), 3, 3))
         return self.here(eye)[1] / U
 
-    def lod(self, uv, tex_w, tex_h, mips):
-        """(lod, band) [k]"""
+    def lod(self, uv, tex_w, tex_h, mips, clamp=True):
+        """(lod, band) [k]: the clamped lod with the band of the unclamped one; clamp=False: the unclamped lod with its band, for a
+        caller that clamps the two ends of lod +- band itself (under magnification the clamped ends coincide)"""
         (p00, e00), (p10, e10), (p01, e01) = (self.attribute(x, y, uv) for x, y in self.t.quad())
         size = np.array([tex_w, tex_h], f64)
         rhos, drhos = [], []
@@ -181,7 +186,7 @@ class Band:
         with np.errstate(divide="ignore", invalid="ignore"):
             lam = np.where(rho > 0, np.log2(np.where(rho > 0, rho, 1.0)), 0.0)
             band = np.where(rho > drho, drho / (np.where(rho > 0, rho, 1.0) * np.log(2.0)), np.inf) + U * np.maximum(np.abs(lam), 1.0)
-        return np.clip(lam, 0.0, mips - 1.0), SECOND_ORDER * band
+        return (np.clip(lam, 0.0, mips - 1.0) if clamp else lam), SECOND_ORDER * band
 
 
 # ---- the normal's encode, as far as the byte rule needs it
@@ -467,17 +472,23 @@ def tangent_blocks():
     return constant_blocks([TANGENT_RGB_565] * 3, 4)
 
 
-def mapped_normal(n, dn, t, dt, rgb=TANGENT_RGB):
+def mapped_normal(n, dn, t, dt, rgb=TANGENT_RGB, ts=None, dts=None):
     """the normal-map frame in float64: n, t [k, 3] the interpolated normal and tangent with their bands -> (normal before the encode,
     its band).  Normalising a vector of length L with component bands e moves each component by at most 2 |e|_2 / L; the
     cross product of two unit vectors by the sum of theirs; the kernel's own float32 steps (two normalizes, the cross, the three-term
-    sums) add 16 u."""
-    ts = np.array(rgb, f64) / 255.0 * 2.0 - 1.0
+    sums) add 16 u.  The tangent-space vector is the constant colour rgb, or per pixel ts [k, 3] (= 2 sample - 1) with its band dts:
+    the frame vectors are unit (b at most), so the band gains |dts_x| + |dts_y| + |dts_z|."""
     ln, lt = np.linalg.norm(n, axis=1, keepdims=True), np.linalg.norm(t, axis=1, keepdims=True)
     nu, tu = n / ln, t / lt
     en = 2 * np.linalg.norm(dn, axis=1, keepdims=True) / ln
     et = 2 * np.linalg.norm(dt, axis=1, keepdims=True) / lt
     b = np.cross(nu, tu)
-    out = ts[0] * tu + ts[1] * b + ts[2] * nu
-    band = abs(ts[0]) * et + abs(ts[1]) * 2 * (en + et) + abs(ts[2]) * en + 16 * U
+    if ts is None:
+        ts = np.array(rgb, f64) / 255.0 * 2.0 - 1.0
+        out = ts[0] * tu + ts[1] * b + ts[2] * nu
+        band = abs(ts[0]) * et + abs(ts[1]) * 2 * (en + et) + abs(ts[2]) * en + 16 * U
+        return out, np.broadcast_to(band, out.shape)
+    ts, a = np.asarray(ts, f64), np.abs(ts)
+    out = ts[:, 0:1] * tu + ts[:, 1:2] * b + ts[:, 2:3] * nu
+    band = a[:, 0:1] * et + a[:, 1:2] * 2 * (en + et) + a[:, 2:3] * en + 16 * U + np.abs(dts).sum(axis=1, keepdims=True)
     return out, np.broadcast_to(band, out.shape)
