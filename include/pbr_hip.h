@@ -566,6 +566,13 @@ size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_t
  *   (4-5 at the median, about 20 at worst for well-shaped triangles; the bound per pixel is derived in tests/raster_truth.py) and does
  *   not depend on where the tile or the triangle lies in the frame, up to PBR_RASTER_MAX_SIZE; the origin is a function of the
  *   triangle and the frame only, so tiles stay bit-identical to the frame.
+ *   Accuracy of coverage and depth: against the real-number geometry of the float32 clip coordinates (homogeneous edge functions, the
+ *   near-plane line, depth = sum lambda_i z_i / det) a pixel's verdict can differ only within delta of a line, delta = the line's ends'
+ *   displacement along its normal at the pixel's foot point: the snap's 1/512 pixel per axis, 3 * 2^-24 (|x / w| + 1) full_w / 2 of the
+ *   projection, and a float32 intersection for an end on the near plane or the guard band (2.8e-3 pixel for an unclipped triangle);
+ *   depth lies within |d depth / dx| e_x + |d depth / dy| e_y + a few 2^-24 of that geometry's.  The bound is derived and evaluated
+ *   per pixel in tests/raster_cover_truth.py; measured there, verdicts differ up to 0.28 delta from a line and depth uses up to 0.95 of
+ *   its band (numpy restatement and MI355X alike).
  * tile: the planes hold global pixels (x0 + x, y0 + y) of the full_w x full_h frame, w x h of them at row pitch `pitch` pixels; a
  * tile is bit-identical to the same region of the whole frame, for every scratch size.
  * vertices / indices / draws: DEVICE arrays of n_vertices / n_indices / n_draws.  max_triangles: the triangles the draws hold
