@@ -6,7 +6,7 @@ symbol cannot be resolved this module raises — it never substitutes another im
 import ctypes as C
 import os
 
-from .structs import Aabb, CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, RasterDesc, ShadeDesc, ShadeTables, SunDesc, Tile, View
+from .structs import Aabb, CubeBc6h, CubeF32, DepthRasterDesc, FxaaImage, GBuffer, Global, HaloPeer, RasterDesc, ShadeDesc, ShadeTables, SunDesc, Tile, View
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB", os.path.join(_HERE, "libpbr_hip.so"))   # override = experiments only
@@ -54,6 +54,9 @@ SIGNATURES = {
     "pbr_gbuffer_raster_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster": (_int, [_vp, C.POINTER(RasterDesc)]),
+    "pbr_depth_raster_scratch_bytes": (_sz, [_u32, _u32, _u32]),
+    "pbr_depth_raster_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
+    "pbr_depth_raster": (_int, [_vp, C.POINTER(DepthRasterDesc)]),
     "pbr_texture2d_bytes": (_sz, [_u32, _u32, _u32, _u32]),
     "pbr_bc1_decode": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "pbr_bc6h_chain_bytes": (_sz, [_u32, _u32]),

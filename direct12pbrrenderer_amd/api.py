@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .structs import (Aabb, RasterDesc, ShadeDesc, ShadeTables, Sun, SunDesc, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
+from .structs import (Aabb, DepthRasterDesc, RasterDesc, ShadeDesc, ShadeTables, Sun, SunDesc, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
                       NUM_CLUSTERS, AABB_DTYPE, CullStats, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
 
@@ -423,6 +423,25 @@ class PbrContext:
                        _ptr(depth), _ptr(stencil), _ptr(scratch), nbytes, _ptr(maps), C.addressof(table) if textures else None, _ptr(bounds),
                        _ptr(stats), int(n_vertices), int(n_indices), int(n_draws), int(max_triangles), int(pitch), len(textures))
         self._check(self.lib.pbr_gbuffer_raster(self.h, C.byref(d)))
+
+    def depth_raster_scratch_bytes(self, w, h, n_triangles, minimum=False):
+        """pbr_depth_raster_scratch_bytes (recommended) or, minimum=True, pbr_depth_raster_min_scratch_bytes for a w x h tile"""
+        fn = self.lib.pbr_depth_raster_min_scratch_bytes if minimum else self.lib.pbr_depth_raster_scratch_bytes
+        return int(fn(int(w), int(h), int(n_triangles)))
+
+    def alloc_depth_raster_scratch(self, w, h, n_triangles, minimum=False, extra=0):
+        """device scratch for depth_raster: gbuffer_raster's without the 80-byte resolve record per triangle"""
+        return self.empty((self.depth_raster_scratch_bytes(w, h, n_triangles, minimum) + int(extra),), torch.uint8)
+
+    def depth_raster(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, depth, pitch,
+                     scratch, scratch_bytes=None, *, bounds=None, stats=None):
+        """pbr_depth_raster: the depth plane of gbuffer_raster (without maps), bit for bit, and nothing else — a shadow map or a
+        depth pre-pass at 4 bytes per texel.  The arguments are gbuffer_raster's without the other four planes; scratch from
+        alloc_depth_raster_scratch; bounds and stats as gbuffer_raster_culled takes them."""
+        nbytes = scratch.numel() * scratch.element_size() if scratch_bytes is None else int(scratch_bytes)
+        d = DepthRasterDesc(C.addressof(g), C.addressof(tile), _ptr(vertices), _ptr(indices), _ptr(draws), _ptr(depth), _ptr(scratch), nbytes,
+                            _ptr(bounds), _ptr(stats), int(n_vertices), int(n_indices), int(n_draws), int(max_triangles), int(pitch), 0)
+        self._check(self.lib.pbr_depth_raster(self.h, C.byref(d)))
 
     def textured_raster_scratch_bytes(self, w, h, n_triangles, minimum=False):
         """pbr_gbuffer_raster_textured_scratch_bytes (recommended) or, minimum=True, its _min_scratch_bytes for a w x h tile"""

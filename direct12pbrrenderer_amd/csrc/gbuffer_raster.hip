@@ -39,6 +39,18 @@
 // one of the six planes of the widened tile (the rule pinned in pbr_hip.h) gets no triangles in the scan, so neither k_rs_setup
 // nor k_rs_fill ever sees it.  The planes are formed on the host in fp64 per call; nothing is read back.  k_rs_bounds
 // (pbr_draw_bounds) makes the draws' local boxes from the buffers the raster takes.  tests/raster_cull_ref.py restates both.
+//
+// The depth-only raster (pbr_depth_raster): the depth plane of the chain above and nothing else, in six launches of its own on a
+// scratch without the resolve records.  The stored depth is min(1, min over the covering fragments of z), a minimum over a totally
+// ordered set (z is clamped to [0, 1], a NaN to 0, and is never -0), so it does not depend on the order of the fragments:
+//   k_rs_clear, k_rs_prep   as above
+//   k_rs_setup<RsSetupDepth>  the same vertex stage, clip, snap, cull and box (the same text), without the normals, the draw id, the
+//                fp64 planes and every store to the resolve record; a box of more than COOP_BINS bins is counted by the whole wave
+//   k_rs_scan_depth         one block: a list is refused for lack of pool space only, never for its length
+//   k_rs_fill_depth         k_rs_fill, a box of more than COOP_BINS bins by the whole wave
+//   k_rs_depth   block = bin, lane = pixel: the bin's list walked from the pool, unsorted, DEPTH_CHUNK raster records at a time staged
+//                in LDS; the fragment's coverage and depth expressions are k_rs_raster's; only a bin without a list walks every
+//                triangle record
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
 #include "tex_chain.hpp"
@@ -56,6 +68,8 @@ using tex2d::bc1_blocks;
 
 constexpr uint32_t BIN = 16;               // bin edge in pixels: 256 lanes, one per pixel
 constexpr uint32_t LIST_CAP = 2048;        // longest bin list sorted in LDS
+constexpr uint32_t DEPTH_CHUNK = 128;      // depth chain: raster records staged in LDS per round of a bin's list
+constexpr uint32_t COOP_BINS = 64;         // depth chain: a box of more bins than this is binned by its whole wave
 constexpr float GUARD = 128.0f;            // guard band: |x|, |y| <= GUARD * w (clip space) needs no x / y clipping
 constexpr uint32_t MAX_POLY = 8;           // a triangle clipped by five planes
 constexpr uint32_t NONE = 0xffffffffu;
@@ -86,13 +100,14 @@ struct RsTexAttr {
 };
 static_assert(sizeof(RsTexAttr) == 64, "textured resolve record layout");
 
-// scratch layout (byte offsets, 256-aligned); everything up to `pool` is the minimum.  The textured layout adds `tex`.
+// scratch layout (byte offsets, 256-aligned); everything up to `pool` is the minimum.  The textured layout adds `tex`; the depth-only
+// layout (resolve = false) has no `attrs`.
 struct Layout {
     size_t draw_base, count, cursor, offset, tris, attrs, tex, pool;
     uint32_t nbx, nby;
 };
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline Layout layout(uint32_t w, uint32_t h, uint32_t n_triangles, bool textured = false) {
+inline Layout layout(uint32_t w, uint32_t h, uint32_t n_triangles, bool textured = false, bool resolve = true) {
     Layout L;
     L.nbx = (w + BIN - 1) / BIN;
     L.nby = (h + BIN - 1) / BIN;
@@ -103,7 +118,7 @@ inline Layout layout(uint32_t w, uint32_t h, uint32_t n_triangles, bool textured
     L.offset = L.cursor + align256(bins * 4);
     L.tris = L.offset + align256(bins * 4);
     L.attrs = L.tris + align256((size_t)n_triangles * sizeof(RsTri));
-    L.tex = L.attrs + align256((size_t)n_triangles * sizeof(RsAttr));
+    L.tex = L.attrs + (resolve ? align256((size_t)n_triangles * sizeof(RsAttr)) : 0);
     L.pool = L.tex + (textured ? align256((size_t)n_triangles * sizeof(RsTexAttr)) : 0);
     return L;
 }
@@ -134,6 +149,8 @@ struct RsRasterTex {
 // the same arguments for a table that holds a BC1-resident texture (PBR_TEX_BC1_BLOCKS): a kernel of its own, picked on the host,
 // so a table of decoded textures keeps the kernel it had
 struct RsRasterTexBc1 : RsRasterTex {};
+// k_rs_setup's pack in the depth-only chain: no resolve record at all (attrs is null)
+struct RsSetupDepth {};
 // k_rs_prep's extra argument in the culled calls
 struct RsCull {
     const pbr_aabb* bounds;
@@ -336,13 +353,37 @@ __global__ __launch_bounds__(256) void k_rs_bounds(const pbr_vertex* __restrict_
     }
 }
 
-// Tex: empty (constant materials) or RsSetupTex (textured: the uv / tangent record, and the map-index guard)
+// Depth chain: f(bin, id) for every bin of the lane's box [bx0, bx1] x [by0, by1] (`has`: the lane has one).  A box of at most
+// COOP_BINS bins is walked by its lane; a larger one by the 64 lanes of the wave, one such box after the other, so a triangle that
+// fills a 2048^2 map costs 256 rounds of 64 atomics, not 16 384 atomics of one lane.  Every lane of the wave that has not left the
+// kernel calls this at the same point; the lanes that have (triangle ids past the count) take no part, so the walk strides by the
+// number of lanes that are here, each at its rank among them.
+template <typename F>
+__device__ __forceinline__ void bins_by_wave(bool has, uint32_t bx0, uint32_t by0, uint32_t bx1, uint32_t by1, uint32_t nbx, uint32_t id,
+                                             F f) {
+    const bool big = has && (bx1 - bx0 + 1u) * (by1 - by0 + 1u) > COOP_BINS;
+    if (has && !big)
+        for (uint32_t by = by0; by <= by1; by++)
+            for (uint32_t bx = bx0; bx <= bx1; bx++) f(by * nbx + bx, id);
+    const unsigned long long here = __ballot(1);
+    const uint32_t lanes = (uint32_t)__popcll(here), rank = (uint32_t)__popcll(here & ((1ull << (threadIdx.x & 63u)) - 1ull));
+    for (unsigned long long m = __ballot(big); m; m &= m - 1ull) {
+        const int src = __ffsll(m) - 1;
+        const uint32_t x0 = __shfl(bx0, src), y0 = __shfl(by0, src), x1 = __shfl(bx1, src), y1 = __shfl(by1, src), sid = __shfl(id, src);
+        const uint32_t nx = x1 - x0 + 1u, total = nx * (y1 - y0 + 1u);
+        for (uint32_t i = rank; i < total; i += lanes) f((y0 + i / nx) * nbx + (x0 + i % nx), sid);
+    }
+}
+
+// Tex: empty (constant materials), RsSetupTex (textured: the uv / tangent record, and the map-index guard) or RsSetupDepth (the
+// depth-only chain: the raster record and the bin counts only)
 template <typename... Tex>
 __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* __restrict__ vtx, const uint32_t* __restrict__ idx,
                                                   const pbr_draw* __restrict__ draws, const uint32_t* __restrict__ draw_base,
                                                   const uint32_t* __restrict__ hdr, RsTri* __restrict__ tris,
                                                   RsAttr* __restrict__ attrs, uint32_t* __restrict__ bin_count, Tex... tex) {
-    constexpr bool TEX = sizeof...(Tex) != 0;
+    constexpr bool DEPTH = (std::is_same<Tex, RsSetupDepth>::value || ...);
+    constexpr bool TEX = sizeof...(Tex) != 0 && !DEPTH;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= hdr[0]) return;
     uint32_t lo = 0, hi = p.n_draws - 1;        // the draw: the last d with draw_base[d] <= t
@@ -358,6 +399,9 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
     float an[9], ac[9];
     for (int i = 0; i < 9; i++) { an[i] = 0.0f; ac[i] = 0.0f; }
     uint32_t origin = 0;
+    // depth chain: the box in bins, counted by bins_by_wave once the lanes have come together again
+    bool binned = false;
+    uint32_t bx0 = 0, by0 = 0, bx1 = 0, by1 = 0;
     // guard (device data): a draw range past n_indices, or an index (+ base_vertex) outside [0, n_vertices): the triangle is dropped
     const uint64_t first = (uint64_t)d.first_index + 3ull * (t - draw_base[lo]);
     bool ok = (uint64_t)d.first_index + d.index_count <= p.n_indices;
@@ -384,13 +428,16 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
             c[k].y = row4(p.Projection + 4, pv[0], pv[1], pv[2], pv[3]);
             c[k].z = row4(p.Projection + 8, pv[0], pv[1], pv[2], pv[3]);
             c[k].w = row4(p.Projection + 12, pv[0], pv[1], pv[2], pv[3]);
-            for (int i = 0; i < 3; i++)
-                an[3 * k + i] = ((d.InvModel[i] * v.normal[0] + d.InvModel[4 + i] * v.normal[1]) + d.InvModel[8 + i] * v.normal[2]) +
-                                  d.InvModel[12 + i] * 0.0f;
+            if constexpr (!DEPTH)
+                for (int i = 0; i < 3; i++)
+                    an[3 * k + i] = ((d.InvModel[i] * v.normal[0] + d.InvModel[4 + i] * v.normal[1]) + d.InvModel[8 + i] * v.normal[2]) +
+                                      d.InvModel[12 + i] * 0.0f;
         }
     }
-    for (int i = 0; i < 9; i++) attrs[t].n[i] = an[i];
-    attrs[t].draw = lo;
+    if constexpr (!DEPTH) {
+        for (int i = 0; i < 9; i++) attrs[t].n[i] = an[i];
+        attrs[t].draw = lo;
+    }
     if constexpr (TEX) {
         // gbuffer.hlsl:80-84: tangent_ws = transpose(InvModel) (t, 0) (the normal's rule), uv as given; computed after the resolve
         // record is stored, so the two records are not live at once
@@ -469,24 +516,26 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
                 x0 = min(x0, rec.X[i]); x1 = max(x1, rec.X[i]);
                 y0 = min(y0, rec.Y[i]); y1 = max(y1, rec.Y[i]);
             }
-            // the resolve's origin: the centre of the polygon's bounding box within the frame, floored to a pixel
-            const int32_t fw8 = (int32_t)(p.full_w << 8), fh8 = (int32_t)(p.full_h << 8);
-            const int32_t ox = (min(max(x0, 0), fw8) + min(max(x1, 0), fw8)) >> 9, oy = (min(max(y0, 0), fh8) + min(max(y1, 0), fh8)) >> 9;
-            // the triangle's 2D homogeneous screen vertices (sx / w, sy / w = the viewport transform) about that origin and their
-            // edge planes, in fp64 (the translation cancels what the products would otherwise have to), each rounded once
-            double sx[3], sy[3], sw[3];
-            for (int k = 0; k < 3; k++) {
-                sw[k] = (double)c[k].w;
-                sx[k] = ((double)c[k].x + sw[k]) * (double)p.half_w - (double)ox * sw[k];
-                sy[k] = (sw[k] - (double)c[k].y) * (double)p.half_h - (double)oy * sw[k];
+            if constexpr (!DEPTH) {
+                // the resolve's origin: the centre of the polygon's bounding box within the frame, floored to a pixel
+                const int32_t fw8 = (int32_t)(p.full_w << 8), fh8 = (int32_t)(p.full_h << 8);
+                const int32_t ox = (min(max(x0, 0), fw8) + min(max(x1, 0), fw8)) >> 9, oy = (min(max(y0, 0), fh8) + min(max(y1, 0), fh8)) >> 9;
+                // the triangle's 2D homogeneous screen vertices (sx / w, sy / w = the viewport transform) about that origin and their
+                // edge planes, in fp64 (the translation cancels what the products would otherwise have to), each rounded once
+                double sx[3], sy[3], sw[3];
+                for (int k = 0; k < 3; k++) {
+                    sw[k] = (double)c[k].w;
+                    sx[k] = ((double)c[k].x + sw[k]) * (double)p.half_w - (double)ox * sw[k];
+                    sy[k] = (sw[k] - (double)c[k].y) * (double)p.half_h - (double)oy * sw[k];
+                }
+                for (int i = 0; i < 3; i++) {
+                    const int j = (i + 1) % 3, k = (i + 2) % 3;
+                    ac[3 * i + 0] = (float)(sy[j] * sw[k] - sw[j] * sy[k]);
+                    ac[3 * i + 1] = (float)(sw[j] * sx[k] - sx[j] * sw[k]);
+                    ac[3 * i + 2] = (float)(sx[j] * sy[k] - sy[j] * sx[k]);
+                }
+                origin = (uint32_t)ox | ((uint32_t)oy << 16);
             }
-            for (int i = 0; i < 3; i++) {
-                const int j = (i + 1) % 3, k = (i + 2) % 3;
-                ac[3 * i + 0] = (float)(sy[j] * sw[k] - sw[j] * sy[k]);
-                ac[3 * i + 1] = (float)(sw[j] * sx[k] - sx[j] * sw[k]);
-                ac[3 * i + 2] = (float)(sx[j] * sy[k] - sy[j] * sx[k]);
-            }
-            origin = (uint32_t)ox | ((uint32_t)oy << 16);
             // pixels whose centre (256 x + 128) lies in [x0, x1], clamped to the tile
             const int64_t px0 = max(-((128 - (int64_t)x0) >> 8), (int64_t)p.x0), px1 = min(((int64_t)x1 - 128) >> 8, (int64_t)(p.x0 + p.w) - 1);
             const int64_t py0 = max(-((128 - (int64_t)y0) >> 8), (int64_t)p.y0), py1 = min(((int64_t)y1 - 128) >> 8, (int64_t)(p.y0 + p.h) - 1);
@@ -494,14 +543,24 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
                 rec.n = n;
                 rec.lo = (uint32_t)px0 | ((uint32_t)py0 << 16);
                 rec.hi = (uint32_t)px1 | ((uint32_t)py1 << 16);
-                for (uint32_t by = ((uint32_t)py0 - p.y0) / BIN; by <= ((uint32_t)py1 - p.y0) / BIN; by++)
-                    for (uint32_t bx = ((uint32_t)px0 - p.x0) / BIN; bx <= ((uint32_t)px1 - p.x0) / BIN; bx++)
-                        atomicAdd(&bin_count[by * p.nbx + bx], 1u);
+                if constexpr (DEPTH) {
+                    binned = true;
+                    bx0 = ((uint32_t)px0 - p.x0) / BIN; bx1 = ((uint32_t)px1 - p.x0) / BIN;
+                    by0 = ((uint32_t)py0 - p.y0) / BIN; by1 = ((uint32_t)py1 - p.y0) / BIN;
+                } else {
+                    for (uint32_t by = ((uint32_t)py0 - p.y0) / BIN; by <= ((uint32_t)py1 - p.y0) / BIN; by++)
+                        for (uint32_t bx = ((uint32_t)px0 - p.x0) / BIN; bx <= ((uint32_t)px1 - p.x0) / BIN; bx++)
+                            atomicAdd(&bin_count[by * p.nbx + bx], 1u);
+                }
             }
         }
     }
-    for (int i = 0; i < 9; i++) attrs[t].c[i] = ac[i];
-    attrs[t].origin = origin;
+    if constexpr (DEPTH) {
+        bins_by_wave(binned, bx0, by0, bx1, by1, p.nbx, t, [&](uint32_t b, uint32_t) { atomicAdd(&bin_count[b], 1u); });
+    } else {
+        for (int i = 0; i < 9; i++) attrs[t].c[i] = ac[i];
+        attrs[t].origin = origin;
+    }
     tris[t] = rec;
 }
 
@@ -543,6 +602,39 @@ __global__ __launch_bounds__(256) void k_rs_fill(RsParams p, const uint32_t* __r
             const uint32_t b = by * p.nbx + bx, off = offset[b];
             if (off != NONE) pool[off + atomicAdd(&cursor[b], 1u)] = t;
         }
+}
+
+// the depth chain's k_rs_scan: a minimum does not need its list sorted in LDS, so no list is too long, and which bins go without
+// a list changes no bit, so the scan is a plain prefix sum by one block: bins in raster order take the pool's next entries until a
+// list would end past the pool; that bin and the bins after it get NONE
+__global__ __launch_bounds__(1024) void k_rs_scan_depth(const uint32_t* __restrict__ count, uint32_t n_bins, uint32_t pool_cap,
+                                                        uint32_t* __restrict__ offset) {
+    __shared__ uint64_t lds[1024];
+    const uint32_t per = (n_bins + 1023u) / 1024u;
+    const uint32_t b = min(threadIdx.x * per, n_bins), e = min(b + per, n_bins);
+    uint64_t s = 0;
+    for (uint32_t i = b; i < e; i++) s += count[i];
+    uint64_t total;
+    uint64_t run = block_scan_1024(s, lds, total);
+    for (uint32_t i = b; i < e; i++) {
+        const uint32_t c = count[i];
+        run += c;
+        offset[i] = run <= pool_cap ? (uint32_t)(run - c) : NONE;
+    }
+}
+
+// the depth chain's k_rs_fill: the same entries (in any order: a minimum does not care), a large box by the whole wave
+__global__ __launch_bounds__(256) void k_rs_fill_depth(RsParams p, const uint32_t* __restrict__ hdr, const RsTri* __restrict__ tris,
+                                                       const uint32_t* __restrict__ offset, uint32_t* __restrict__ cursor,
+                                                       uint32_t* __restrict__ pool) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= hdr[0]) return;
+    const RsTri& r = tris[t];
+    const uint32_t px0 = (r.lo & 0xffffu) - p.x0, py0 = (r.lo >> 16) - p.y0, px1 = (r.hi & 0xffffu) - p.x0, py1 = (r.hi >> 16) - p.y0;
+    bins_by_wave(r.n != 0, px0 / BIN, py0 / BIN, px1 / BIN, py1 / BIN, p.nbx, t, [&](uint32_t b, uint32_t id) {
+        const uint32_t off = offset[b];
+        if (off != NONE) pool[off + atomicAdd(&cursor[b], 1u)] = id;
+    });
 }
 
 // edge a -> b at P: (Xb - Xa)(PY - Ya) - (Yb - Ya)(PX - Xa); > 0 inside a front-facing triangle.  On the edge (0) a pixel centre is
@@ -864,6 +956,84 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
     }
 }
 
+// The depth-only raster: block = bin, lane = pixel, the depth in a register.  Per fragment k_rs_raster's coverage and depth
+// expressions, then the minimum: the fragments of a pixel may come in any order, so the bin's list is walked as k_rs_fill_depth
+// left it, from the pool, whatever its length: DEPTH_CHUNK raster records at a time are copied into LDS by all 256 lanes (16 bytes
+// each, coalesced) and read from there by every lane at the same address, instead of one dependent scalar load from memory per
+// triangle.  A wave holds four rows of the bin and skips a triangle whose pixel box (RsTri::lo / hi) misses them: a covered pixel's
+// centre lies in a fan triangle, so inside the polygon's bounding box, so in the pixel box; the skip cannot change a bit.  A bin
+// without a list (the pool was full) walks every triangle record and tests its box, as k_rs_raster's fallback does.
+__global__ __launch_bounds__(256) void k_rs_depth(RsParams p, const uint32_t* __restrict__ hdr, const RsTri* __restrict__ tris,
+                                                  const uint32_t* __restrict__ count, const uint32_t* __restrict__ offset,
+                                                  const uint32_t* __restrict__ pool, float* __restrict__ depth) {
+    __shared__ uint32_t list[256];
+    __shared__ RsTri recs[DEPTH_CHUNK];
+    static_assert(sizeof(RsTri) % sizeof(uint4) == 0 && alignof(RsTri) >= alignof(uint4), "raster records are copied 16 bytes at a time");
+    constexpr uint32_t PARTS = sizeof(RsTri) / sizeof(uint4);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lx = blockIdx.x * BIN + (tid & (BIN - 1)), ly = blockIdx.y * BIN + tid / BIN;
+    const bool inside = lx < p.w && ly < p.h;
+    const int64_t PX = (int64_t)(p.x0 + lx) * 256 + 128, PY = (int64_t)(p.y0 + ly) * 256 + 128;
+    // the rows of this wave (global pixels): lanes 64 w .. 64 w + 63 are rows 4 w .. 4 w + 3 of the bin
+    const uint32_t wy0 = p.y0 + blockIdx.y * BIN + (tid >> 6) * 4u, wy1 = wy0 + 3u;
+    float zbuf = 1.0f;
+
+    // one triangle (the same record for every lane of the block), every fan triangle of its polygon
+    auto fragment = [&](const RsTri& r) {
+        if ((r.lo >> 16) > wy1 || (r.hi >> 16) < wy0) return;
+        const uint32_t n = r.n;
+        const int32_t X0 = r.X[0], Y0 = r.Y[0];
+        const float Z0 = r.Z[0];
+        for (uint32_t k = 1; k + 1 < n; k++) {
+            const int32_t X1 = r.X[k], Y1 = r.Y[k], X2 = r.X[k + 1], Y2 = r.Y[k + 1];
+            const int64_t area = (int64_t)(X1 - X0) * (Y2 - Y0) - (int64_t)(Y1 - Y0) * (X2 - X0);
+            if (area <= 0) continue;             // back-facing or zero area
+            const int64_t w0 = edge_fn(X1, Y1, X2, Y2, PX, PY), w1 = edge_fn(X2, Y2, X0, Y0, PX, PY), w2 = edge_fn(X0, Y0, X1, Y1, PX, PY);
+            if (inside && w0 >= edge_bias(X1, Y1, X2, Y2) && w1 >= edge_bias(X2, Y2, X0, Y0) && w2 >= edge_bias(X0, Y0, X1, Y1)) {
+                const double z0 = (double)Z0;
+                const double zd = z0 + ((double)w1 * ((double)r.Z[k] - z0) + (double)w2 * ((double)r.Z[k + 1] - z0)) / (double)area;
+                float z = (float)zd;
+                z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;
+                if (z < zbuf) zbuf = z;          // the minimum: LESS without a winner
+            }
+        }
+    };
+
+    const uint32_t b = blockIdx.y * p.nbx + blockIdx.x;
+    const uint32_t cnt = count[b], off = offset[b];
+    if (cnt != 0) {
+        if (off != NONE) {
+            for (uint32_t base = 0; base < cnt; base += DEPTH_CHUNK) {
+                const uint32_t m = min(DEPTH_CHUNK, cnt - base);
+                for (uint32_t q = tid; q < m * PARTS; q += 256u)
+                    reinterpret_cast<uint4*>(recs)[q] = reinterpret_cast<const uint4*>(tris + pool[off + base + q / PARTS])[q % PARTS];
+                __syncthreads();
+                for (uint32_t j = 0; j < m; j++) fragment(recs[j]);
+                __syncthreads();
+            }
+        } else {
+            const uint32_t rx0 = p.x0 + blockIdx.x * BIN, ry0 = p.y0 + blockIdx.y * BIN;
+            const uint32_t rx1 = min(rx0 + BIN, p.x0 + p.w) - 1u, ry1 = min(ry0 + BIN, p.y0 + p.h) - 1u;
+            const uint32_t total = hdr[0];
+            for (uint32_t base = 0; base < total; base += 256u) {
+                const uint32_t t = base + tid;
+                uint32_t hit = 0;
+                if (t < total) {
+                    const RsTri& r = tris[t];
+                    hit = r.n != 0 && (r.lo & 0xffffu) <= rx1 && (r.hi & 0xffffu) >= rx0 && (r.lo >> 16) <= ry1 && (r.hi >> 16) >= ry0;
+                }
+                list[tid] = hit;
+                __syncthreads();
+                const uint32_t m = min(256u, total - base);
+                for (uint32_t j = 0; j < m; j++)
+                    if (list[j]) fragment(tris[base + j]);
+                __syncthreads();
+            }
+        }
+    }
+    if (inside) depth[(size_t)ly * p.pitch + lx] = zbuf;
+}
+
 // the six planes of the model cull (pbr_hip.h) in fp64 from the fp32 matrices, each rounded once
 void cull_planes(const pbr_global* g, const pbr_tile* tile, float* out) {
     double r[4][4];
@@ -886,6 +1056,25 @@ void cull_planes(const pbr_global* g, const pbr_tile* tile, float* out) {
         out[16 + j] = (float)(r[3][j] + r[2][j]);
         out[20 + j] = (float)(r[3][j] - r[2][j]);
     }
+}
+
+// the kernels' parameters of either chain; the pool is what the scratch holds past the layout's minimum
+RsParams params(const pbr_global* g, const pbr_tile* tile, const Layout& L, uint32_t n_vertices, uint32_t n_indices, uint32_t n_draws,
+                uint32_t pitch, size_t scratch_bytes) {
+    RsParams p;
+    for (int i = 0; i < 16; i++) { p.View[i] = g->View[i]; p.Projection[i] = g->Projection[i]; }
+    p.half_w = 0.5f * (float)tile->full_w;
+    p.half_h = 0.5f * (float)tile->full_h;
+    p.full_w = tile->full_w; p.full_h = tile->full_h;
+    p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h;
+    p.nbx = L.nbx;
+    p.n_vertices = n_vertices; p.n_indices = n_indices; p.n_draws = n_draws;
+    p.pitch = pitch;
+    const size_t pool_entries = (scratch_bytes - L.pool) / 4;
+    // (not min(): on the host HIP's min(size_t, size_t) is min(int, int), which made every capacity 0xfffffffe: no list was ever
+    // refused for space, and a pool too small for the lists, the minimum scratch's empty one first of all, was written past its end)
+    p.pool_cap = pool_entries < (size_t)0xfffffffeu ? (uint32_t)pool_entries : 0xfffffffeu;
+    return p;
 }
 
 // pbr_gbuffer_raster: the checks and the six launches.  tx: null without d->maps, else the validated texture table (bc1: it holds a
@@ -938,19 +1127,7 @@ pbr_status raster(pbr_ctx* ctx, const pbr_raster_desc* d) {
     PBR_REQUIRE(ctx, scratch_bytes >= L.pool, tx ? "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_textured_min_scratch_bytes"
                                                 : "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_min_scratch_bytes");
 
-    RsParams p;
-    for (int i = 0; i < 16; i++) { p.View[i] = g->View[i]; p.Projection[i] = g->Projection[i]; }
-    p.half_w = 0.5f * (float)tile->full_w;
-    p.half_h = 0.5f * (float)tile->full_h;
-    p.full_w = tile->full_w; p.full_h = tile->full_h;
-    p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h;
-    p.nbx = L.nbx;
-    p.n_vertices = n_vertices; p.n_indices = n_indices; p.n_draws = n_draws;
-    p.pitch = pitch;
-    const size_t pool_entries = (scratch_bytes - L.pool) / 4;
-    // (not min(): on the host HIP's min(size_t, size_t) is min(int, int), which made every capacity 0xfffffffe: no list was ever
-    // refused for space, and a pool too small for the lists, the minimum scratch's empty one first of all, was written past its end)
-    p.pool_cap = pool_entries < (size_t)0xfffffffeu ? (uint32_t)pool_entries : 0xfffffffeu;
+    const RsParams p = params(g, tile, L, n_vertices, n_indices, n_draws, pitch, scratch_bytes);
 
     char* s = static_cast<char*>(scratch);
     uint32_t* hdr = reinterpret_cast<uint32_t*>(s);
@@ -1004,6 +1181,63 @@ pbr_status raster(pbr_ctx* ctx, const pbr_raster_desc* d) {
     return pbr::launched(ctx, "k_rs_raster");
 }
 
+// pbr_depth_raster: pbr_gbuffer_raster's checks (without the planes it does not take) and the depth chain's six launches
+static_assert(sizeof(pbr_depth_raster_desc) == 104, "descriptor layout: no padding");
+pbr_status depth_raster(pbr_ctx* ctx, const pbr_depth_raster_desc* d) {
+    if (!ctx) return PBR_ERR_INVALID;
+    PBR_REQUIRE(ctx, d, "pbr_depth_raster: null descriptor");
+    const auto [g, tile, vertices, indices, draws, depth, scratch, scratch_bytes, bounds, stats, n_vertices, n_indices, n_draws,
+                max_triangles, pitch, reserved] = *d;
+    PBR_REQUIRE(ctx, reserved == 0, "pbr_depth_raster: reserved is not 0");
+    PBR_REQUIRE(ctx, bounds || !stats, "pbr_depth_raster: stats without bounds");
+    PBR_REQUIRE(ctx, g && tile && vertices && indices && draws && depth && scratch, "pbr_depth_raster: null pointer");
+    PBR_REQUIRE(ctx, n_vertices && n_indices && n_draws && max_triangles, "pbr_depth_raster: empty vertex / index / draw list");
+    PBR_REQUIRE(ctx, n_draws <= PBR_RASTER_MAX_DRAWS && max_triangles <= PBR_RASTER_MAX_TRIANGLES,
+                "pbr_depth_raster: more draws or triangles than the limits");
+    PBR_REQUIRE(ctx, tile->w && tile->h && tile->full_w && tile->full_h && tile->full_w <= PBR_RASTER_MAX_SIZE &&
+                tile->full_h <= PBR_RASTER_MAX_SIZE && (uint64_t)tile->x0 + tile->w <= tile->full_w &&
+                (uint64_t)tile->y0 + tile->h <= tile->full_h, "pbr_depth_raster: bad tile");
+    PBR_REQUIRE(ctx, pitch >= tile->w, "pbr_depth_raster: pitch < tile width");
+    PBR_REQUIRE(ctx, ((pbr::addr(vertices) | pbr::addr(indices) | pbr::addr(draws) | pbr::addr(depth)) & 3u) == 0 &&
+                (pbr::addr(scratch) & 15u) == 0, "pbr_depth_raster: unaligned buffer");
+    PBR_REQUIRE(ctx, (pbr::addr(bounds) & 3u) == 0, "pbr_depth_raster: bounds not 4-byte aligned");
+    PBR_REQUIRE(ctx, (pbr::addr(stats) & 3u) == 0, "pbr_depth_raster: stats not 4-byte aligned");
+    const Layout L = layout(tile->w, tile->h, max_triangles, false, false);
+    PBR_REQUIRE(ctx, scratch_bytes >= L.pool, "pbr_depth_raster: scratch below pbr_depth_raster_min_scratch_bytes");
+    const RsParams p = params(g, tile, L, n_vertices, n_indices, n_draws, pitch, scratch_bytes);
+
+    char* s = static_cast<char*>(scratch);
+    uint32_t* hdr = reinterpret_cast<uint32_t*>(s);
+    uint32_t* draw_base = reinterpret_cast<uint32_t*>(s + L.draw_base);
+    uint32_t* count = reinterpret_cast<uint32_t*>(s + L.count);
+    uint32_t* cursor = reinterpret_cast<uint32_t*>(s + L.cursor);
+    uint32_t* offset = reinterpret_cast<uint32_t*>(s + L.offset);
+    RsTri* tris = reinterpret_cast<RsTri*>(s + L.tris);
+    uint32_t* pool = reinterpret_cast<uint32_t*>(s + L.pool);
+    const uint32_t n_bins = L.nbx * L.nby;
+    const uint32_t tri_blocks = (max_triangles + 255u) / 256u;
+
+    hipLaunchKernelGGL(k_rs_clear, dim3(min((n_bins + 255u) / 256u, 1024u)), dim3(256), 0, ctx->stream, count, cursor, n_bins);
+    if (pbr_status st = pbr::launched(ctx, "k_rs_clear")) return st;
+    if (bounds) {
+        RsCull cull{bounds, stats, {}};
+        cull_planes(g, tile, cull.planes);
+        hipLaunchKernelGGL(k_rs_prep<RsCull>, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr, cull);
+    } else {
+        hipLaunchKernelGGL(k_rs_prep<>, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr);
+    }
+    if (pbr_status st = pbr::launched(ctx, "k_rs_prep")) return st;
+    hipLaunchKernelGGL(k_rs_setup<RsSetupDepth>, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, draw_base, hdr,
+                       tris, static_cast<RsAttr*>(nullptr), count, RsSetupDepth{});
+    if (pbr_status st = pbr::launched(ctx, "k_rs_setup")) return st;
+    hipLaunchKernelGGL(k_rs_scan_depth, dim3(1), dim3(1024), 0, ctx->stream, count, n_bins, p.pool_cap, offset);
+    if (pbr_status st = pbr::launched(ctx, "k_rs_scan_depth")) return st;
+    hipLaunchKernelGGL(k_rs_fill_depth, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, hdr, tris, offset, cursor, pool);
+    if (pbr_status st = pbr::launched(ctx, "k_rs_fill_depth")) return st;
+    hipLaunchKernelGGL(k_rs_depth, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, hdr, tris, count, offset, pool, depth);
+    return pbr::launched(ctx, "k_rs_depth");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1027,6 +1261,17 @@ size_t pbr_gbuffer_raster_textured_scratch_bytes(uint32_t w, uint32_t h, uint32_
 }
 
 pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_raster_desc* d) { return raster(ctx, d); }
+
+size_t pbr_depth_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
+    return layout(w, h, n_triangles, false, false).pool;
+}
+
+size_t pbr_depth_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
+    const Layout L = layout(w, h, n_triangles, false, false);
+    return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
+}
+
+pbr_status pbr_depth_raster(pbr_ctx* ctx, const pbr_depth_raster_desc* d) { return depth_raster(ctx, d); }
 
 pbr_status pbr_draw_bounds(pbr_ctx* ctx, const pbr_vertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices,
                            const pbr_draw* draws, uint32_t n_draws, pbr_aabb* out) {

@@ -47,6 +47,7 @@ SIGNATURES = {
     "pbrh_presented": (_int, [_vp, C.c_char_p, C.c_size_t]),
     "pbrh_set_sun_light": (_int, [_vp, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_uint32, C.c_uint32, C.c_float, C.c_float, _int]),
     "pbrh_clear_sun_light": (_int, [_vp]),
+    "pbrh_set_sun_shadow_depth_only": (_int, [_vp, _int]),
     "pbrh_render_n": (_int, [_vp, _int, C.c_float, C.POINTER(C.c_double)]),
     "pbrh_render": (_int, [_vp, C.c_float]),
     "pbrh_execution_order": (_int, [_vp, C.c_char_p, C.c_size_t]),
@@ -377,13 +378,16 @@ class HostRenderer:
         what it is.  Off by default.  A tile renderer and one with an overlapped tail refuse (HostError)."""
         self._check(self.lib.pbrh_set_antialiasing(self.h, 1 if on else 0))
 
-    def set_sun_light(self, direction, luminance=100.0, map_size=2048, pcf=3, bias=(5e-4, 4e-3), shadows=True):
+    def set_sun_light(self, direction, luminance=100.0, map_size=2048, pcf=3, bias=(5e-4, 4e-3), shadows=True, depth_only=False):
         """pbrh_set_sun_light: SunLightPass (pbr_sun_light) between DeferredShading and Bloom and, with shadows, SunShadowPass after
         GBuffer (needs set_meshes; the map is the frame-graph texture "SunShadowDepth", rasterized once per mesh upload / call).
-        direction None: pbrh_clear_sun_light.  The arguments are DeferredFrame.set_sun's; tiles and an overlapped tail refuse."""
+        direction None: pbrh_clear_sun_light.  The arguments are DeferredFrame.set_sun's; tiles and an overlapped tail refuse.
+        depth_only (pbrh_set_sun_shadow_depth_only): SunShadowPass makes the same map with pbr_depth_raster, still in one dispatch,
+        without the map-sized scratch planes."""
         if direction is None:
             self._check(self.lib.pbrh_clear_sun_light(self.h))
             return
+        self._check(self.lib.pbrh_set_sun_shadow_depth_only(self.h, 1 if depth_only else 0))
         lum = np.broadcast_to(np.asarray(luminance, dtype=np.float32), (3,))
         self._check(self.lib.pbrh_set_sun_light(self.h, C.byref((C.c_float * 3)(*[float(v) for v in direction])),
                                                 C.byref((C.c_float * 3)(*[float(v) for v in lum])), int(map_size), int(pcf), float(bias[0]),

@@ -498,6 +498,21 @@ void SunShadowPass::Execute(FGContext* context) {
     pbr_global light_g;
     if (pbr_sun_fit(mSun->Direction, &box, n, n, &light_g, mSun->LightViewProj) != PBR_OK) throw HipException("SunShadowPass: pbr_sun_fit refused the box or the map size");
     pbr_raster_desc d = mGBuffer->RasterInputs();   // the unculled constant-material raster of the same buffers
+    if (mSun->DepthOnly) {
+        // one dispatch either way: the depth plane alone, from the same buffers, on the depth raster's smaller scratch
+        const size_t scratch = pbr_depth_raster_scratch_bytes(n, n, d.max_triangles);
+        if (scratch > 0xffffffffu) throw HipException("SunShadowPass: shadow raster scratch larger than 4 GiB");
+        mPlanes.reset();
+        if (!mRasterScratch || mRasterScratch->Size() != scratch) mRasterScratch = std::make_unique<DeviceStructuredBuffer>((uint32)scratch, 4);
+        pbr_depth_raster_desc dd{};
+        dd.vertices = d.vertices; dd.indices = d.indices; dd.draws = d.draws;
+        dd.n_vertices = d.n_vertices; dd.n_indices = d.n_indices; dd.n_draws = d.n_draws; dd.max_triangles = d.max_triangles;
+        dd.scratch = mRasterScratch->DevicePtr(); dd.scratch_bytes = mRasterScratch->Size();
+        context->CommandList->RasterShadowDepth(&mShadingState, &light_g, dd, target);
+        mUploadsSeen = mGBuffer->Uploads();
+        mSerialSeen = mSun->Serial;
+        return;
+    }
     d.maps = nullptr; d.textures = nullptr; d.n_textures = 0; d.bounds = nullptr; d.stats = nullptr;
     const size_t plane = (size_t)n * n * 4, scratch = pbr_gbuffer_raster_scratch_bytes(n, n, d.max_triangles);
     if (3 * plane > 0xffffffffu || scratch > 0xffffffffu) throw HipException("SunShadowPass: shadow raster buffers larger than 4 GiB");

@@ -196,6 +196,7 @@ struct SunSettings {
     uint32 MapSize = 2048, Pcf = 3;
     float BiasConst = 0, BiasSlope = 0;
     bool Shadows = true;
+    bool DepthOnly = false;           // the map by pbr_depth_raster (the same bits, no scratch planes) instead of pbr_gbuffer_raster
     uint64_t Serial = 0;              // bumped by every SetSunLight: the map is rasterized again
     float LightViewProj[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // written by SunShadowPass
 };
@@ -215,7 +216,8 @@ protected:
     const GBufferPass* mGBuffer;
     SunSettings* mSun;
     ShadingState mShadingState;
-    // the raster's scratch and the A / B / C planes it writes and nobody reads (17 B per texel with the target's depth and stencil)
+    // the raster's scratch and the A / B / C planes it writes and nobody reads (17 B per texel with the target's depth and stencil);
+    // with SunSettings::DepthOnly there are no planes, and the scratch is the depth raster's
     std::unique_ptr<DeviceStructuredBuffer> mPlanes, mRasterScratch;
     uint64_t mUploadsSeen = ~0ull, mSerialSeen = ~0ull;
 };

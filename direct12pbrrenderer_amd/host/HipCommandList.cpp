@@ -603,6 +603,20 @@ void HipCommandList::RasterShadowMap(ShadingState* s, const pbr_global* light_g,
     Raster(d, light_g, tile, a, b, c, target, "pbr_gbuffer_raster (shadow map)");
 }
 
+void HipCommandList::RasterShadowDepth(ShadingState* s, const pbr_global* light_g, pbr_depth_raster_desc d, DeviceTexture2D* target) {
+    if (!s || s->File() != "gbuffer.hlsl") throw HipException("RasterShadowDepth: gbuffer.hlsl shading state expected");
+    if (!light_g || !d.vertices || !d.indices || !d.draws || !target || !target->DepthPlane())
+        throw HipException("RasterShadowDepth: null buffer, or the target is no depth-stencil texture");
+    mDispatchCount++;
+    FlushPendingBloom();
+    const uint32 w = target->Width(), h = target->Height();
+    const pbr_tile tile{0, 0, w, h, w, h};   // the whole map, whatever tile of the frame this device draws
+    d.g = light_g; d.tile = &tile;
+    d.depth = target->DepthPlane();
+    d.pitch = w;
+    Check(pbr_depth_raster(mCtx, &d), "pbr_depth_raster (shadow map)");
+}
+
 void HipCommandList::Raster(pbr_raster_desc& d, const pbr_global* g, const pbr_tile& tile, uint32_t* a, uint32_t* b, uint32_t* c,
                             DeviceTexture2D* ds, const char* what) {
     d.g = g; d.tile = &tile;

@@ -100,6 +100,9 @@ public:
     // target of the map's size — always the whole map, in tile mode too — and three scratch colour planes nobody reads.
     void RasterShadowMap(ShadingState* state, const pbr_global* light_g, pbr_raster_desc desc, uint32_t* a, uint32_t* b, uint32_t* c,
                          DeviceTexture2D* target);
+    // SunShadowPass with SunSettings::DepthOnly: pbr_depth_raster of the same meshes under the same camera into the target's depth
+    // plane alone (the same bits); no scratch planes, and the target's stencil plane is not written
+    void RasterShadowDepth(ShadingState* state, const pbr_global* light_g, pbr_depth_raster_desc desc, DeviceTexture2D* target);
     // SunLightPass: pbr_sun_light (the pbr_sun in `state`'s constants) into the bound render target; shadow_map null: no shadows
     void SunLight(ShadingState* state, DeviceTexture2D* shadow_map);
     void Present(DeviceTexture2D* tex) { mPresented = tex; }

@@ -23,6 +23,7 @@ struct pbrh_renderer {
     uint32 width = 0, height = 0;
     float time = 0.0f;
     bool tile = false;   // made by pbrh_create_tile: one device's part of a larger frame
+    bool sun_depth_only = false;   // pbrh_set_sun_shadow_depth_only: the shadow pass of the suns set from now on
     std::string err;
 };
 
@@ -669,7 +670,15 @@ int pbrh_set_sun_light(pbrh_renderer* r, const float dir[3], const float luminan
         if (dir[0] == 0.0f && dir[1] == 0.0f && dir[2] == 0.0f) throw HipException("pbrh_set_sun_light: the direction is zero");
         if (!std::isfinite(bias_const) || !std::isfinite(bias_slope)) throw HipException("pbrh_set_sun_light: bias not finite");
         s.MapSize = map_size; s.Pcf = pcf; s.BiasConst = bias_const; s.BiasSlope = bias_slope; s.Shadows = shadows != 0;
+        s.DepthOnly = r->sun_depth_only;
         set_sun(r, true, s);
+    });
+}
+
+int pbrh_set_sun_shadow_depth_only(pbrh_renderer* r, int on) {
+    return guarded(r, [&] {
+        if (!r) throw HipException("pbrh_set_sun_shadow_depth_only: null renderer");
+        r->sun_depth_only = on != 0;
     });
 }
 

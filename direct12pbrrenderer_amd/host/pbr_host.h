@@ -196,7 +196,7 @@ int pbrh_set_antialiasing(pbrh_renderer* r, int on);
  * SunShadowPass after GBuffer, which needs pbrh_set_meshes: it fits the light's orthographic camera (pbr_sun_fit) around the union of
  * the draws' world boxes and rasterizes the meshes (pbr_gbuffer_raster, the constant-material call) into the frame-graph texture
  * "SunShadowDepth" (map_size^2, D32 readable through pbrh_read) — once per mesh upload / pbrh_set_sun_light, not per frame; 17 B per
- * texel with the scratch planes it ignores, 71 MB at 2048^2.  dir: world space, from the surface towards the light (normalised here);
+ * texel with the scratch planes it ignores, 71 MB at 2048^2 (pbrh_set_sun_shadow_depth_only, below: 4 B per texel, the same bits).  dir: world space, from the surface towards the light (normalised here);
  * luminance: three channels; pcf 1 or 3; the biases in light-clip depth units (DeferredFrame.SUN_BIAS of the Python side: 5e-4, 4e-3).
  * Off by default; off, and after pbrh_clear_sun_light, the execution order, the dispatch count and the resources are those of a
  * renderer that never heard of it.  -1: a renderer made by pbrh_create_tile or given pbrh_set_tile — the kernel takes a tile and a
@@ -208,6 +208,12 @@ int pbrh_set_antialiasing(pbrh_renderer* r, int on);
 int pbrh_set_sun_light(pbrh_renderer* r, const float dir[3], const float luminance[3], uint32_t map_size, uint32_t pcf, float bias_const,
                        float bias_slope, int shadows);
 int pbrh_clear_sun_light(pbrh_renderer* r);
+/* The shadow pass of every sun set AFTER this call (pbrh_set_sun_light reads the switch; a sun already set keeps its pass): on != 0,
+ * SunShadowPass rasterizes the map with pbr_depth_raster instead of pbr_gbuffer_raster — still one dispatch, the same pass order and
+ * dispatch count, "SunShadowDepth" with the same name, size and depth bits (pbr_depth_raster's contract) —, without the three
+ * map-sized scratch planes and on the depth raster's smaller scratch: 4 B per texel written instead of 17.  The texture's stencil
+ * plane is then not written.  Off by default.  -1 for a null renderer only. */
+int pbrh_set_sun_shadow_depth_only(pbrh_renderer* r, int on);
 /* the name of the frame-graph texture the present pass shows ("ToneMappedTexture"; "AntiAliasedTexture" with anti-aliasing on) */
 int pbrh_presented(pbrh_renderer* r, char* buf, size_t len);
 /* n frames; *ms_per_frame = average wall time per frame (every frame ends with the per-frame fence wait) */

@@ -441,7 +441,8 @@ class DeferredFrame:
     # degrees, where the same estimate asks for 2.5e-3; the contact shadow then starts 1 cm from a caster's foot on that scene.
     SUN_BIAS = (5e-4, 4e-3)
 
-    def set_sun(self, direction, luminance=100.0, map_size=2048, pcf=3, bias=SUN_BIAS, shadows=True, depth_map=None, light_view_proj=None):
+    def set_sun(self, direction, luminance=100.0, map_size=2048, pcf=3, bias=SUN_BIAS, shadows=True, depth_map=None, light_view_proj=None,
+                depth_only=False):
         """A directional light with a shadow map, added to the HDR target after the shade (and the sky resolve) and before the bloom
         (pbr_sun_light); set_sun(None) switches it off, and without a sun every launch and output bit of the frame is what it was.
         direction: world space, from the surface towards the light (normalised here); luminance: a scalar or three channels (the
@@ -449,7 +450,8 @@ class DeferredFrame:
         orthographic camera is fitted (pbr_sun_fit) around the union of the draws' world boxes and the next render() rasterizes the
         map_size^2 shadow map with pbr_gbuffer_raster — once per set_meshes / set_sun, not per frame; refresh_shadow_map() asks for
         it again (moved draws).  The pass writes a map-sized scratch G-buffer whose A / B / C / stencil planes are ignored: 17 bytes
-        per texel, 71 MB at 2048^2.  Without meshes (uploaded planes) shadows must be False, or the map is handed in: depth_map =
+        per texel, 71 MB at 2048^2.  depth_only=True makes the same map, bit for bit, with pbr_depth_raster instead: the depth plane
+        alone, 4 bytes per texel (17 MB at 2048^2), and a raster scratch without the 80-byte resolve record per triangle.  Without meshes (uploaded planes) shadows must be False, or the map is handed in: depth_map =
         (device float32 tensor, map_w, map_h, map_pitch) with its light_view_proj (16 floats)."""
         if direction is None:
             self.sun = None
@@ -457,7 +459,7 @@ class DeferredFrame:
         if self.split is not None:
             raise ValueError("set_sun: the overlapped halo frame interleaves the shade with the bloom; use the plain frame order")
         sun = {"direction": np.asarray(direction, dtype=np.float64), "luminance": luminance, "pcf": int(pcf), "bias": (float(bias[0]), float(bias[1])),
-               "map": None, "map_size": int(map_size), "fit": False, "struct": None}
+               "map": None, "map_size": int(map_size), "fit": False, "struct": None, "depth_only": bool(depth_only)}
         if depth_map is not None:
             if light_view_proj is None:
                 raise ValueError("set_sun: a depth map needs its light_view_proj")
@@ -497,11 +499,20 @@ class DeferredFrame:
         light_g, lvp = sun_fit(d.astype(np.float32), box[0], box[1], n, n)
         # the map-sized scratch G-buffer and raster scratch live on the FRAME, keyed by map size and triangle count: another luminance,
         # bias or direction allocates nothing.  A / B / C / stencil and the scratch are kept for the next raster (refresh_shadow_map)
-        sm = self._sun_planes
-        if sm is None or sm["n"] != n or sm["tris"] != m["max_triangles"]:
-            sm = dict(self._planes(n, n), n=n, tris=m["max_triangles"], scratch=ctx.alloc_raster_scratch(n, n, m["max_triangles"]))
+        # (a depth-only sun keeps the depth plane and the depth raster's smaller scratch, nothing else)
+        sm, only = self._sun_planes, sun["depth_only"]
+        if sm is None or sm["n"] != n or sm["tris"] != m["max_triangles"] or sm["depth_only"] != only:
+            if only:
+                sm = dict(depth=ctx.empty((n, n), torch.float32), scratch=ctx.alloc_depth_raster_scratch(n, n, m["max_triangles"]))
+            else:
+                sm = dict(self._planes(n, n), scratch=ctx.alloc_raster_scratch(n, n, m["max_triangles"]))
+            sm.update(n=n, tris=m["max_triangles"], depth_only=only)
             self._sun_planes = sm
-        self._raster(light_g, Tile(0, 0, n, n, n, n), sm, n, sm["scratch"])
+        if only:
+            ctx.depth_raster(light_g, Tile(0, 0, n, n, n, n), m["vertices"], m["n_vertices"], m["indices"], m["n_indices"], m["draws"],
+                             m["n_draws"], m["max_triangles"], sm["depth"], n, sm["scratch"])
+        else:
+            self._raster(light_g, Tile(0, 0, n, n, n, n), sm, n, sm["scratch"])
         sun["light_g"], sun["map"] = light_g, (sm["depth"], n, n, n)
         sun["struct"] = make_sun(sun["direction"], sun["luminance"], lvp, sun["bias"], sun["pcf"])
 

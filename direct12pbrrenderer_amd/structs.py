@@ -93,6 +93,15 @@ class RasterDesc(C.Structure):
                 + [(n, C.c_uint32) for n in ("n_vertices", "n_indices", "n_draws", "max_triangles", "pitch", "n_textures")])
 
 
+class DepthRasterDesc(C.Structure):
+    """pbr_depth_raster_desc: one depth-only raster call (include/pbr_hip.h); 8-byte fields first, then the 32-bit ones: no padding.
+    g and tile are HOST addresses (of a Global and a Tile the caller keeps alive); bounds and stats unset: no model cull; reserved
+    stays 0."""
+    _fields_ = ([(n, C.c_void_p) for n in ("g", "tile", "vertices", "indices", "draws", "depth", "scratch")]
+                + [("scratch_bytes", C.c_size_t)] + [(n, C.c_void_p) for n in ("bounds", "stats")]
+                + [(n, C.c_uint32) for n in ("n_vertices", "n_indices", "n_draws", "max_triangles", "pitch", "reserved")])
+
+
 MAX_VIEWS = 16                                        # PBR_MAX_VIEWS (include/pbr_hip.h)
 
 

@@ -768,6 +768,46 @@ typedef struct pbr_raster_desc {
 } pbr_raster_desc;
 pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_raster_desc* d);
 
+/* ---- Depth-only rasterization (new): the depth plane of pbr_gbuffer_raster and nothing else ---------------------------------- */
+/* What a shadow map or a depth pre-pass needs: 4 B per texel instead of the five planes' 17, and a scratch without the 80-byte
+ * resolve record per triangle.  THE CONTRACT: for every input that pbr_gbuffer_raster accepts with maps == NULL, the depth plane
+ * written here is BIT-IDENTICAL to the depth plane of that call — for every camera (perspective, or pbr_sun_fit's orthographic one),
+ * every tile (own origin, ragged size, pitch > w), with or without bounds, and every scratch size from the minimum up; with bounds,
+ * *stats is equal too.  Every pixel of the tile is written, 1.0 where nothing covers it; nothing outside the tile is touched.
+ * There is no textured variant: gbuffer.hlsl has no clip / discard, so maps cannot change depth.
+ * Why the bits agree: pbr_gbuffer_raster stores min(1, min over the covering fragments of z) — z is clamped to [0, 1], a NaN becomes
+ * 0 and -0 never occurs, the plane starts at 1 and the test is LESS — a minimum over a totally ordered set, the same in any order.
+ * This call shares the vertex stage, clip, snap, face test and bounding box with that call (one text), evaluates its coverage
+ * and depth expressions per fragment and takes the minimum; it keeps no winner, counts no stencil, sorts no list, and walks a bin's
+ * list whatever its length (the G-buffer call falls back to every triangle for a list of more than 2048).
+ * Scratch: the G-buffer call's layout without the resolve records, so pbr_depth_raster_min_scratch_bytes(w, h, n) is at least 80 n
+ * below pbr_gbuffer_raster_min_scratch_bytes(w, h, n); pbr_depth_raster_scratch_bytes is the recommended size (the same pool rule:
+ * lists for about 8 bins per triangle).  Bins take list space in raster order until a list would end past the pool; that bin and
+ * the bins after it have no list and walk every triangle record (which bins those are changes no bit).
+ * Refusals (PBR_ERR_INVALID, nothing enqueued), those of pbr_gbuffer_raster: a null descriptor or pointer (bounds and stats may be
+ * NULL), zero counts, n_draws > PBR_RASTER_MAX_DRAWS, max_triangles > PBR_RASTER_MAX_TRIANGLES, a bad tile, pitch < w, buffers not
+ * 4-byte (scratch: 16-byte) aligned, stats without bounds, scratch below pbr_depth_raster_min_scratch_bytes(w, h, max_triangles);
+ * and reserved != 0.  Asynchronous: six launches on the context's stream, no host synchronisation, no allocation. */
+/* 8-byte fields first, then the 32-bit ones (104 bytes, no padding), as pbr_raster_desc. */
+typedef struct pbr_depth_raster_desc {
+    const pbr_global* g;
+    const pbr_tile* tile;
+    const pbr_vertex* vertices;
+    const uint32_t* indices;
+    const pbr_draw* draws;
+    float* depth;
+    void* scratch;
+    size_t scratch_bytes;
+    const pbr_aabb* bounds;            /* bounds, stats NULL: no model cull */
+    pbr_cull_stats* stats;
+    uint32_t n_vertices, n_indices, n_draws, max_triangles;
+    uint32_t pitch;
+    uint32_t reserved;                 /* must be 0 */
+} pbr_depth_raster_desc;
+pbr_status pbr_depth_raster(pbr_ctx* ctx, const pbr_depth_raster_desc* d);
+size_t pbr_depth_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
+size_t pbr_depth_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
+
 /* bloom_prefilter.hlsl:17-60 (DeferredPipeline.cpp:411-427): hdr (w x h) -> out (w>>1 x h>>1). */
 pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h,
                                uint32_t pitch, pbr_half* out, float threshold, float knee);
@@ -950,8 +990,9 @@ pbr_status pbr_fxaa_batch(pbr_ctx* ctx, const pbr_fxaa_image* images, uint32_t n
  * brdf()) and never adds it, and it has no shadow code.  pbr_sun_light is that light as a pass of its own: it reads the
  * G-buffer the shade read, evaluates brdf() for one direction, looks the receiver up in a shadow map — the DEPTH PLANE of a
  * pbr_gbuffer_raster call under an orthographic light camera (pbr_sun_fit) — and adds the result to the fp16 HDR target, between the
- * shade (and the sky resolve) and the bloom.  Left out: multi-view frames, a depth-only shadow raster (the shadow pass writes and
- * ignores the A / B / C / stencil planes, 17 B per texel), cascades, point-light shadows.
+ * shade (and the sky resolve) and the bloom.  pbr_depth_raster writes the same depth plane, bit for bit, without the A / B / C /
+ * stencil planes the shadow pass otherwise writes and ignores (17 B per texel); the callers choose (DeferredFrame.set_sun(depth_only=),
+ * pbrh_set_sun_shadow_depth_only).  Left out: multi-view frames, cascades, point-light shadows.
  *
  * THE RULE.  All arithmetic is fp32 with no contraction, in the order written (brackets first, otherwise left to right); every divide
  * and square root is the IEEE correctly rounded one — NO operation of this pass goes to the quick hardware units (v_rcp / v_rsq / v_log /
@@ -1015,7 +1056,7 @@ typedef struct pbr_sun {            /* HOST struct */
 typedef struct pbr_sun_desc {       /* pointers first, as pbr_shade_desc */
     const pbr_global* g; const pbr_tile* tile; const pbr_gbuffer* gb;
     const pbr_sun* sun;
-    const float* shadow_depth;      /* map_w x map_h D32 plane, the depth plane of a pbr_gbuffer_raster call; NULL = no shadows */
+    const float* shadow_depth;      /* map_w x map_h D32 plane: pbr_gbuffer_raster's depth plane or pbr_depth_raster's; NULL = no shadows */
     pbr_half* hdr;                  /* read-modify-write, tile-local, pitch hdr_pitch */
     float* contrib_f32;             /* parity probe: float4 per pixel, the contribution alone; exactly one of hdr / contrib_f32 */
     uint32_t map_w, map_h, map_pitch, hdr_pitch;
