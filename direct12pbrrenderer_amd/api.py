@@ -401,14 +401,19 @@ class PbrContext:
                                                 _ptr(A), _ptr(B), _ptr(Cc)))
 
     # ---- G-buffer rasterization ----------------------------------------------------------------
+    def _raster_scratch(self, call, w, h, n_triangles, minimum, extra=None):
+        """pbr_<call>_scratch_bytes (recommended) or, minimum, pbr_<call>_min_scratch_bytes for a w x h tile; with extra, a device
+        tensor of that many bytes and `extra` more (uint8; 256-byte aligned like every torch allocation)"""
+        nbytes = int(getattr(self.lib, f"pbr_{call}_{'min_' if minimum else ''}scratch_bytes")(int(w), int(h), int(n_triangles)))
+        return nbytes if extra is None else self.empty((nbytes + int(extra),), torch.uint8)
+
     def raster_scratch_bytes(self, w, h, n_triangles, minimum=False):
         """pbr_gbuffer_raster_scratch_bytes (recommended) or, minimum=True, pbr_gbuffer_raster_min_scratch_bytes for a w x h tile"""
-        fn = self.lib.pbr_gbuffer_raster_min_scratch_bytes if minimum else self.lib.pbr_gbuffer_raster_scratch_bytes
-        return int(fn(int(w), int(h), int(n_triangles)))
+        return self._raster_scratch("gbuffer_raster", w, h, n_triangles, minimum)
 
     def alloc_raster_scratch(self, w, h, n_triangles, minimum=False, extra=0):
-        """device scratch for gbuffer_raster (uint8; 256-byte aligned like every torch allocation)"""
-        return self.empty((self.raster_scratch_bytes(w, h, n_triangles, minimum) + int(extra),), torch.uint8)
+        """device scratch for gbuffer_raster"""
+        return self._raster_scratch("gbuffer_raster", w, h, n_triangles, minimum, extra)
 
     def gbuffer_raster(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles,
                        A, B, Cc, depth, stencil, pitch, scratch, scratch_bytes=None, *, maps=None, textures=None, bounds=None, stats=None):
@@ -426,12 +431,11 @@ class PbrContext:
 
     def depth_raster_scratch_bytes(self, w, h, n_triangles, minimum=False):
         """pbr_depth_raster_scratch_bytes (recommended) or, minimum=True, pbr_depth_raster_min_scratch_bytes for a w x h tile"""
-        fn = self.lib.pbr_depth_raster_min_scratch_bytes if minimum else self.lib.pbr_depth_raster_scratch_bytes
-        return int(fn(int(w), int(h), int(n_triangles)))
+        return self._raster_scratch("depth_raster", w, h, n_triangles, minimum)
 
     def alloc_depth_raster_scratch(self, w, h, n_triangles, minimum=False, extra=0):
         """device scratch for depth_raster: gbuffer_raster's without the 80-byte resolve record per triangle"""
-        return self.empty((self.depth_raster_scratch_bytes(w, h, n_triangles, minimum) + int(extra),), torch.uint8)
+        return self._raster_scratch("depth_raster", w, h, n_triangles, minimum, extra)
 
     def depth_raster(self, g: Global, tile: Tile, vertices, n_vertices, indices, n_indices, draws, n_draws, max_triangles, depth, pitch,
                      scratch, scratch_bytes=None, *, bounds=None, stats=None):
@@ -445,12 +449,11 @@ class PbrContext:
 
     def textured_raster_scratch_bytes(self, w, h, n_triangles, minimum=False):
         """pbr_gbuffer_raster_textured_scratch_bytes (recommended) or, minimum=True, its _min_scratch_bytes for a w x h tile"""
-        fn = self.lib.pbr_gbuffer_raster_textured_min_scratch_bytes if minimum else self.lib.pbr_gbuffer_raster_textured_scratch_bytes
-        return int(fn(int(w), int(h), int(n_triangles)))
+        return self._raster_scratch("gbuffer_raster_textured", w, h, n_triangles, minimum)
 
     def alloc_textured_raster_scratch(self, w, h, n_triangles, minimum=False, extra=0):
         """device scratch for gbuffer_raster_textured"""
-        return self.empty((self.textured_raster_scratch_bytes(w, h, n_triangles, minimum) + int(extra),), torch.uint8)
+        return self._raster_scratch("gbuffer_raster_textured", w, h, n_triangles, minimum, extra)
 
     def upload_texture(self, chain, width, height, mip_levels, fmt):
         """A texture's mip chain (host bytes in the reference's layout: scene.mip_chain / pack_chain) -> (device tensor,

@@ -1,5 +1,5 @@
 // bc1_decode.hpp — the BC1 block decode pinned in include/pbr_hip.h (PBR_TEX_BC1_BLOCKS), shared by the textured raster's sampler
-// (BC1-resident textures, read in place: gbuffer_raster.hip) and, in texture2d.hip, the bulk decoder (pbr_bc1_decode) and the encoder's
+// (BC1-resident textures, read in place: tex_sampler.hpp) and, in texture2d.hip, the bulk decoder (pbr_bc1_decode) and the encoder's
 // fit (pbr_bc1_encode).  The block decode only: where a block lies in a chain is tex_chain.hpp's.
 // A block is 8 bytes, read as two little-endian words: `endpoints` = c0 | c1 << 16 (RGB565 each) and `bits` = 16 2-bit palette
 // indices, texel (x, y) of the block at bit 2 (4 y + x).  A palette entry is R | G << 8 | B << 16 | A << 24 whatever the stored

@@ -1,56 +1,48 @@
-// gbuffer_raster.hip — GBufferPass::Execute + DrawModel (DeferredPipeline.cpp:138-185) with constant per-draw materials:
-// gbuffer.hlsl's vertex shader (:71-86), the fixed-function stages of DefaultOpaque (back faces culled, FrontCounterClockwise =
-// FALSE; depth LESS with write; stencil ALWAYS, INCR_SAT on depth pass) and ps_main's Use*Map == false branches (:88-149).
+// gbuffer_raster.hip — GBufferPass::Execute + DrawModel (DeferredPipeline.cpp:138-185): gbuffer.hlsl's vertex shader (:71-86), the
+// fixed-function stages of DefaultOpaque (back faces culled, FrontCounterClockwise = FALSE; depth LESS with write; stencil ALWAYS,
+// INCR_SAT on depth pass) and ps_main (:88-149), as a sort-middle pipeline in the style of Laine & Karras ("High-Performance Software
+// Rasterization on GPUs", HPG 2011) on the caller's scratch; and the depth-only raster, which writes that pipeline's depth plane alone.
 //
-// A sort-middle pipeline in the style of Laine & Karras ("High-Performance Software Rasterization on GPUs", HPG 2011), six
-// launches on the caller's scratch:
-//   k_rs_clear   zero the per-bin counters
-//   k_rs_prep    one block: the first triangle of every draw (exclusive scan of index_count / 3) and the triangle count
-//   k_rs_setup   lane = triangle: vertex stage, near / guard-band clip, viewport, 16.8 snap, cull, bounding box, the resolve's
-//                planes; bin counts
-//   k_rs_scan    one wave: every bin's list offset in the pool, in raster order; a list that does not fit takes none
-//   k_rs_fill    lane = triangle: its id into the list of every bin its box touches (any order: k_rs_raster sorts)
-//   k_rs_raster  block = 16 x 16-pixel bin, lane = pixel: depth, stencil and the winning triangle in registers while the bin's
-//                triangles are walked in draw order, then the winner's attributes and the G-buffer encode (gbuffer_encode.hpp)
-// A bin whose list is not in the pool (or is longer than LIST_CAP) walks every triangle record in draw order instead and tests
-// its box: the same triangles in the same order, so the same bits, only slower.
+// The rules.  Coverage: exact 64-bit integer edge functions on 16.8 fixed-point vertices at pixel centres, top-left rule.  Depth: z / w
+// of the snapped vertices interpolated linearly in screen space (fp64, rounded once to fp32), clamped to [0, 1].  Normals: the
+// triangle's perspective-correct barycentrics from its 2D homogeneous edge planes (Olano & Greer 1997), so a clipped polygon resolves
+// against the triangle it came from; the planes are formed in fp64 about an integer pixel origin near the triangle (the centre of its
+// snapped polygon's bounding box within the frame) and rounded once to fp32, and the resolve evaluates them at the pixel's exact offset
+// from that origin, so their accuracy does not depend on where in the frame the triangle lies.  Built with -ffp-contract=off:
+// tests/raster_ref.py (raster_tex_ref.py, raster_cull_ref.py) restates every step in the same operation order; tests/raster_truth.py,
+// raster_cover_truth.py and sampler_truth.py hold the results to fp64 statements of the contract.
 //
-// Coverage: exact 64-bit integer edge functions on 16.8 fixed-point vertices at pixel centres, top-left rule.  Depth: z / w of
-// the snapped vertices interpolated linearly in screen space (fp64, rounded once to fp32), clamped to [0, 1].  Normals: the
-// triangle's perspective-correct barycentrics from its 2D homogeneous edge planes (Olano & Greer 1997), so a clipped polygon
-// resolves against the triangle it came from.  The planes are formed in fp64 about an integer pixel origin near the triangle (the
-// centre of its snapped polygon's bounding box within the frame) and rounded once to fp32; the resolve evaluates them at the pixel's
-// exact offset from that origin, so their accuracy does not depend on where in the frame the triangle lies.  Built with
-// -ffp-contract=off: tests/raster_ref.py restates every step in the same operation order; tests/raster_truth.py holds the
-// interpolated attributes to an fp64 statement of the contract.
-//
-// Textured draws (pbr_raster_desc.maps set) take the same six launches with a non-empty `Tex` pack on k_rs_setup and
-// k_rs_raster (the empty pack is the constant-material kernel): setup also writes the uv and tangent_ws of the three vertices
-// (RsTexAttr) and drops draws with a bad map index; the resolve adds the perspective-correct uv / tangent, the quad's LOD, up to
-// five trilinear samples (SamplerLinearWrap as pinned in pbr_hip.h) and the normal-map frame, before the same encode.
-// tests/raster_tex_ref.py restates it.
-//
-// BC1-resident textures (PBR_TEX_BC1_BLOCKS): a table that holds one runs k_rs_raster<RsRasterTexBc1>, whose bilinear takes its taps
-// from the blocks in place (bc1_decode.hpp).  The bulk decode of a whole chain (pbr_bc1_decode) is texture2d.hip's; the texture table's
-// descriptions are checked by tex_chain.hpp.
-//
-// Model culling (pbr_raster_desc.bounds set, with or without maps): Scene::CullModel on the device.  The same six
-// launches with a non-empty `Cull` pack on k_rs_prep (the empty pack is the kernel without it): a draw whose world box lies outside
-// one of the six planes of the widened tile (the rule pinned in pbr_hip.h) gets no triangles in the scan, so neither k_rs_setup
-// nor k_rs_fill ever sees it.  The planes are formed on the host in fp64 per call; nothing is read back.  k_rs_bounds
-// (pbr_draw_bounds) makes the draws' local boxes from the buffers the raster takes.  tests/raster_cull_ref.py restates both.
-//
-// The depth-only raster (pbr_depth_raster): the depth plane of the chain above and nothing else, in six launches of its own on a
-// scratch without the resolve records.  The stored depth is min(1, min over the covering fragments of z), a minimum over a totally
-// ordered set (z is clamped to [0, 1], a NaN to 0, and is never -0), so it does not depend on the order of the fragments:
-//   k_rs_clear, k_rs_prep   as above
-//   k_rs_setup<RsSetupDepth>  the same vertex stage, clip, snap, cull and box (the same text), without the normals, the draw id, the
-//                fp64 planes and every store to the resolve record; a box of more than COOP_BINS bins is counted by the whole wave
-//   k_rs_scan_depth         one block: a list is refused for lack of pool space only, never for its length
-//   k_rs_fill_depth         k_rs_fill, a box of more than COOP_BINS bins by the whole wave
-//   k_rs_depth   block = bin, lane = pixel: the bin's list walked from the pool, unsorted, DEPTH_CHUNK raster records at a time staged
-//                in LDS; the fragment's coverage and depth expressions are k_rs_raster's; only a bin without a list walks every
-//                triangle record
+// The file, in order; every piece that two kernels or two entry points use is stated once:
+//   records and layout   RsTri (the clipped, snapped polygon), RsAttr / RsTexAttr (the resolve's records), the scratch Layout, RsParams,
+//                        the argument packs that select a kernel variant (empty pack = the constant-material / unculled kernel)
+//   k_rs_clear           zero the per-bin counters
+//   k_rs_prep            one block: the first triangle of every draw (exclusive scan of index_count / 3) and the triangle count.  Pack
+//                        RsCull = the model cull (pbr_raster_desc.bounds; Scene::CullModel on the device): a draw whose world box lies
+//                        outside one of the six planes of the widened tile (pinned in pbr_hip.h; formed on the host in fp64 per call by
+//                        cull_planes) gets no triangles in the scan, so no later kernel sees it.  k_rs_bounds (pbr_draw_bounds) makes
+//                        the draws' local boxes.
+//   walk_bins<COOP>      the bin walk of setup (counts) and fill (appends): per lane, or, depth chain, a box of more than COOP_BINS bins
+//                        by the whole wave
+//   k_rs_setup           lane = triangle: vertex stage, near / guard-band clip, viewport, 16.8 snap, cull, bounding box, bin counts; the
+//                        resolve's planes.  Pack RsSetupTex: also the uv / tangent record, and draws with a bad map index dropped;
+//                        pack RsSetupDepth: the raster record and the bin counts only
+//   k_rs_scan            one wave: every bin's list offset in the pool, in raster order; a list that does not fit, or is longer than
+//                        LIST_CAP, takes none.  k_rs_scan_depth: a block-wide prefix sum; a list is refused for lack of space only
+//   k_rs_fill[_depth]    lane = triangle: its id into the list of every bin its box touches (append_id, in any order), by either walk
+//   the bin kernels' shared pieces   RS_BIN_PIXEL, RS_FOR_EACH_FRAGMENT (the coverage and depth rule of BOTH chains: pbr_depth_raster's
+//                        bit-exactness contract rests on it), every_record (a bin without a list walks every triangle record in draw
+//                        order and tests its box: the same triangles in the same order, so the same bits, only slower), RsWeights
+//   k_rs_raster          block = 16 x 16-pixel bin, lane = pixel: the bin's list sorted in LDS (draw order), depth, stencil and the
+//                        winning triangle in registers, then the winner's attributes and the G-buffer encode (gbuffer_encode.hpp).
+//                        Packs RsRasterTex / RsRasterTexBc1 (pbr_raster_desc.maps; a table that holds a PBR_TEX_BC1_BLOCKS texture): the
+//                        perspective-correct uv / tangent, the quad's LOD, up to five trilinear samples (tex_sampler.hpp; BC1 taps from
+//                        the blocks in place, bc1_decode.hpp) and the normal-map frame before the same encode
+//   k_rs_depth           block = bin, lane = pixel: min(1, min over the covering fragments of z), a minimum over a totally ordered set
+//                        (z is clamped, a NaN is 0, -0 never occurs), so the list is walked unsorted from the pool, whatever its
+//                        length, DEPTH_CHUNK raster records at a time staged in LDS
+//   the host side        RsCall (the fields both descriptors have), cull_refusal / call_refusal (the shared checks; each entry point
+//                        refuses under its own name), params, Carve (the scratch by its layout), launch_clear_prep; raster() and
+//                        depth_raster(): their own checks and their six launches; the exports
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
 #include "tex_chain.hpp"
@@ -65,6 +57,7 @@ namespace {
 #include "texel_decode.hpp"
 #include "bc1_decode.hpp"
 using tex2d::bc1_blocks;
+#include "tex_sampler.hpp"
 
 constexpr uint32_t BIN = 16;               // bin edge in pixels: 256 lanes, one per pixel
 constexpr uint32_t LIST_CAP = 2048;        // longest bin list sorted in LDS
@@ -166,6 +159,10 @@ struct ClipV { float x, y, z, w; };
 __device__ __forceinline__ float row4(const float* m, float x, float y, float z, float w) {
     return ((m[0] * x + m[1] * y) + m[2] * z) + m[3] * w;
 }
+// component i of transpose(InvModel) (v, 0), summed left to right: gbuffer.hlsl's rule for a normal and for a tangent
+__device__ __forceinline__ float inv_transpose3(const float* im, int i, const float* v) {
+    return ((im[i] * v[0] + im[4 + i] * v[1]) + im[8 + i] * v[2]) + im[12 + i] * 0.0f;
+}
 // clip planes: 0 near (z >= 0), 1-4 the guard band (x >= -G w, x <= G w, y >= -G w, y <= G w); inside <=> d >= 0
 __device__ __forceinline__ float plane_d(const ClipV& v, uint32_t pl) {
     switch (pl) {
@@ -230,23 +227,23 @@ __device__ __forceinline__ bool draw_culled(const pbr_draw& d, const pbr_aabb& b
 // draw_base[d] = first triangle id of draw d (index_count / 3 triangles each, in draw order), clamped to max_tris;
 // hdr[0] = the number of triangles rasterized (ids >= max_tris are not)
 // Cull: empty, or RsCull (a culled draw has no triangles; thread 0 writes the call's pbr_cull_stats).  The culled variant parks each
-// draw's count in draw_base[d] between the test and the two passes of the scan, so the test runs once per draw.
+// draw's count in draw_base[d] between the test and the two passes of the scan, so the test runs once per draw; the scan itself is
+// one text, with the per-draw count (`count`) as the only difference.
 template <typename... Cull>
 __global__ __launch_bounds__(1024) void k_rs_prep(const pbr_draw* __restrict__ draws, uint32_t n_draws, uint32_t max_tris,
                                                   uint32_t* __restrict__ draw_base, uint32_t* __restrict__ hdr, Cull... cull) {
     constexpr bool CULL = sizeof...(Cull) != 0;
     __shared__ uint64_t lds[1024];
+    __shared__ unsigned long long gone[2];           // culled draws, culled triangles (CULL only)
     const uint32_t per = (n_draws + 1023u) / 1024u;
     const uint32_t b = min(threadIdx.x * per, n_draws), e = min(b + per, n_draws);
-    uint64_t s = 0;
+    uint32_t nd = 0;
+    uint64_t nt = 0;
     if constexpr (CULL) {
-        __shared__ unsigned long long gone[2];       // culled draws, culled triangles
         const RsCull& cl = only(cull...);
         if (threadIdx.x == 0) { gone[0] = 0; gone[1] = 0; }
         // the test, draw = k * 1024 + thread: neighbouring lanes read neighbouring records and share their cache lines (a thread's own
         // range [b, e) puts the lanes of one load `per` records apart)
-        uint32_t nd = 0;
-        uint64_t nt = 0;
         for (uint32_t d = threadIdx.x; d < n_draws; d += 1024u) {
             uint32_t n = draws[d].index_count / 3u;
             if (draw_culled(draws[d], cl.bounds[d], cl.planes)) {
@@ -257,23 +254,31 @@ __global__ __launch_bounds__(1024) void k_rs_prep(const pbr_draw* __restrict__ d
             draw_base[d] = n;
         }
         __syncthreads();                                   // the parked counts are read by other threads of the block
-        for (uint32_t d = b; d < e; d++) s += draw_base[d];
-        uint64_t total;
-        uint64_t run = block_scan_1024(s, lds, total);
+    }
+    const auto count = [&](uint32_t d) -> uint32_t {
+        if constexpr (CULL) return draw_base[d]; else return draws[d].index_count / 3u;
+    };
+    uint64_t s = 0;
+    for (uint32_t d = b; d < e; d++) s += count(d);
+    uint64_t total;
+    uint64_t run = block_scan_1024(s, lds, total);
+    if constexpr (CULL)
         if (nd) {
             atomicAdd(&gone[0], (unsigned long long)nd);
             atomicAdd(&gone[1], (unsigned long long)nt);
         }
-        for (uint32_t d = b; d < e; d++) {
-            const uint32_t n = draw_base[d];
-            draw_base[d] = (uint32_t)min(run, (uint64_t)max_tris);
-            run += n;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t n = (uint32_t)min(total, (uint64_t)max_tris);
-            draw_base[n_draws] = n;
-            hdr[0] = n;
+    for (uint32_t d = b; d < e; d++) {
+        const uint32_t n = count(d);
+        draw_base[d] = (uint32_t)min(run, (uint64_t)max_tris);
+        run += n;
+    }
+    if constexpr (CULL) __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t n = (uint32_t)min(total, (uint64_t)max_tris);
+        draw_base[n_draws] = n;
+        hdr[0] = n;
+        if constexpr (CULL) {
+            const RsCull& cl = only(cull...);
             if (cl.stats) {
                 pbr_cull_stats st;
                 st.draws_culled = (uint32_t)gone[0];
@@ -282,19 +287,6 @@ __global__ __launch_bounds__(1024) void k_rs_prep(const pbr_draw* __restrict__ d
                 st.triangles_culled = (uint32_t)min(gone[1], 0xffffffffull);
                 *cl.stats = st;
             }
-        }
-    } else {
-        for (uint32_t d = b; d < e; d++) s += draws[d].index_count / 3u;
-        uint64_t total;
-        uint64_t run = block_scan_1024(s, lds, total);
-        for (uint32_t d = b; d < e; d++) {
-            draw_base[d] = (uint32_t)min(run, (uint64_t)max_tris);
-            run += draws[d].index_count / 3u;
-        }
-        if (threadIdx.x == 0) {
-            const uint32_t n = (uint32_t)min(total, (uint64_t)max_tris);
-            draw_base[n_draws] = n;
-            hdr[0] = n;
         }
     }
 }
@@ -353,25 +345,28 @@ __global__ __launch_bounds__(256) void k_rs_bounds(const pbr_vertex* __restrict_
     }
 }
 
-// Depth chain: f(bin, id) for every bin of the lane's box [bx0, bx1] x [by0, by1] (`has`: the lane has one).  A box of at most
-// COOP_BINS bins is walked by its lane; a larger one by the 64 lanes of the wave, one such box after the other, so a triangle that
-// fills a 2048^2 map costs 256 rounds of 64 atomics, not 16 384 atomics of one lane.  Every lane of the wave that has not left the
-// kernel calls this at the same point; the lanes that have (triangle ids past the count) take no part, so the walk strides by the
-// number of lanes that are here, each at its rank among them.
-template <typename F>
-__device__ __forceinline__ void bins_by_wave(bool has, uint32_t bx0, uint32_t by0, uint32_t bx1, uint32_t by1, uint32_t nbx, uint32_t id,
-                                             F f) {
-    const bool big = has && (bx1 - bx0 + 1u) * (by1 - by0 + 1u) > COOP_BINS;
+// The bin walk of k_rs_setup (f counts) and of the fill kernels (f appends): f(bin, id) for every bin of the lane's box
+// [bx0, bx1] x [by0, by1] (`has`: the lane has one).  Two forms, one call shape:
+//   COOP = false (the G-buffer chain): each lane walks its own box;
+//   COOP = true (the depth chain): a box of at most COOP_BINS bins is walked by its lane; a larger one by the 64 lanes of the wave, one
+//   such box after the other, so a triangle that fills a 2048^2 map costs 256 rounds of 64 atomics, not 16 384 atomics of one lane.
+//   Every lane of the wave that has not left the kernel calls this at the same point; the lanes that have (triangle ids past the
+//   count) take no part, so the walk strides by the number of lanes that are here, each at its rank among them.
+template <bool COOP, typename F>
+__device__ __forceinline__ void walk_bins(bool has, uint32_t bx0, uint32_t by0, uint32_t bx1, uint32_t by1, uint32_t nbx, uint32_t id, F f) {
+    const bool big = COOP && has && (bx1 - bx0 + 1u) * (by1 - by0 + 1u) > COOP_BINS;
     if (has && !big)
         for (uint32_t by = by0; by <= by1; by++)
             for (uint32_t bx = bx0; bx <= bx1; bx++) f(by * nbx + bx, id);
-    const unsigned long long here = __ballot(1);
-    const uint32_t lanes = (uint32_t)__popcll(here), rank = (uint32_t)__popcll(here & ((1ull << (threadIdx.x & 63u)) - 1ull));
-    for (unsigned long long m = __ballot(big); m; m &= m - 1ull) {
-        const int src = __ffsll(m) - 1;
-        const uint32_t x0 = __shfl(bx0, src), y0 = __shfl(by0, src), x1 = __shfl(bx1, src), y1 = __shfl(by1, src), sid = __shfl(id, src);
-        const uint32_t nx = x1 - x0 + 1u, total = nx * (y1 - y0 + 1u);
-        for (uint32_t i = rank; i < total; i += lanes) f((y0 + i / nx) * nbx + (x0 + i % nx), sid);
+    if constexpr (COOP) {
+        const unsigned long long here = __ballot(1);
+        const uint32_t lanes = (uint32_t)__popcll(here), rank = (uint32_t)__popcll(here & ((1ull << (threadIdx.x & 63u)) - 1ull));
+        for (unsigned long long m = __ballot(big); m; m &= m - 1ull) {
+            const int src = __ffsll(m) - 1;
+            const uint32_t x0 = __shfl(bx0, src), y0 = __shfl(by0, src), x1 = __shfl(bx1, src), y1 = __shfl(by1, src), sid = __shfl(id, src);
+            const uint32_t nx = x1 - x0 + 1u, total = nx * (y1 - y0 + 1u);
+            for (uint32_t i = rank; i < total; i += lanes) f((y0 + i / nx) * nbx + (x0 + i % nx), sid);
+        }
     }
 }
 
@@ -399,9 +394,10 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
     float an[9], ac[9];
     for (int i = 0; i < 9; i++) { an[i] = 0.0f; ac[i] = 0.0f; }
     uint32_t origin = 0;
-    // depth chain: the box in bins, counted by bins_by_wave once the lanes have come together again
+    // the bin counts: the box in bins (`binned`: the triangle has one) and what walk_bins does with each bin of it
     bool binned = false;
     uint32_t bx0 = 0, by0 = 0, bx1 = 0, by1 = 0;
+    const auto count_bin = [&](uint32_t b, uint32_t) { atomicAdd(&bin_count[b], 1u); };
     // guard (device data): a draw range past n_indices, or an index (+ base_vertex) outside [0, n_vertices): the triangle is dropped
     const uint64_t first = (uint64_t)d.first_index + 3ull * (t - draw_base[lo]);
     bool ok = (uint64_t)d.first_index + d.index_count <= p.n_indices;
@@ -429,9 +425,7 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
             c[k].z = row4(p.Projection + 8, pv[0], pv[1], pv[2], pv[3]);
             c[k].w = row4(p.Projection + 12, pv[0], pv[1], pv[2], pv[3]);
             if constexpr (!DEPTH)
-                for (int i = 0; i < 3; i++)
-                    an[3 * k + i] = ((d.InvModel[i] * v.normal[0] + d.InvModel[4 + i] * v.normal[1]) + d.InvModel[8 + i] * v.normal[2]) +
-                                      d.InvModel[12 + i] * 0.0f;
+                for (int i = 0; i < 3; i++) an[3 * k + i] = inv_transpose3(d.InvModel, i, v.normal);
         }
     }
     if constexpr (!DEPTH) {
@@ -448,9 +442,7 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
         if (ok) {
             for (int k = 0; k < 3; k++) {
                 const pbr_vertex& v = vtx[vi[k]];
-                for (int i = 0; i < 3; i++)
-                    ta.t[3 * k + i] = ((d.InvModel[i] * v.tangent[0] + d.InvModel[4 + i] * v.tangent[1]) + d.InvModel[8 + i] * v.tangent[2]) +
-                                      d.InvModel[12 + i] * 0.0f;
+                for (int i = 0; i < 3; i++) ta.t[3 * k + i] = inv_transpose3(d.InvModel, i, v.tangent);
                 ta.uv[2 * k] = v.uv[0];
                 ta.uv[2 * k + 1] = v.uv[1];
             }
@@ -543,20 +535,17 @@ __global__ __launch_bounds__(256) void k_rs_setup(RsParams p, const pbr_vertex* 
                 rec.n = n;
                 rec.lo = (uint32_t)px0 | ((uint32_t)py0 << 16);
                 rec.hi = (uint32_t)px1 | ((uint32_t)py1 << 16);
-                if constexpr (DEPTH) {
-                    binned = true;
-                    bx0 = ((uint32_t)px0 - p.x0) / BIN; bx1 = ((uint32_t)px1 - p.x0) / BIN;
-                    by0 = ((uint32_t)py0 - p.y0) / BIN; by1 = ((uint32_t)py1 - p.y0) / BIN;
-                } else {
-                    for (uint32_t by = ((uint32_t)py0 - p.y0) / BIN; by <= ((uint32_t)py1 - p.y0) / BIN; by++)
-                        for (uint32_t bx = ((uint32_t)px0 - p.x0) / BIN; bx <= ((uint32_t)px1 - p.x0) / BIN; bx++)
-                            atomicAdd(&bin_count[by * p.nbx + bx], 1u);
-                }
+                binned = true;
+                bx0 = ((uint32_t)px0 - p.x0) / BIN; bx1 = ((uint32_t)px1 - p.x0) / BIN;
+                by0 = ((uint32_t)py0 - p.y0) / BIN; by1 = ((uint32_t)py1 - p.y0) / BIN;
+                // each lane on its own: here.  (One call site for both forms, after the lanes have come together, costs these two
+                // instantiations vector instructions and waits; the walk itself is stated once.)
+                if constexpr (!DEPTH) walk_bins<false>(true, bx0, by0, bx1, by1, p.nbx, t, count_bin);
             }
         }
     }
     if constexpr (DEPTH) {
-        bins_by_wave(binned, bx0, by0, bx1, by1, p.nbx, t, [&](uint32_t b, uint32_t) { atomicAdd(&bin_count[b], 1u); });
+        walk_bins<true>(binned, bx0, by0, bx1, by1, p.nbx, t, count_bin);      // by the wave: once the lanes have come together again
     } else {
         for (int i = 0; i < 9; i++) attrs[t].c[i] = ac[i];
         attrs[t].origin = origin;
@@ -589,6 +578,15 @@ __global__ __launch_bounds__(64) void k_rs_scan(const uint32_t* __restrict__ cou
     }
 }
 
+// what the fill kernels do with each bin of a triangle's box: the triangle's id into the bin's list, if the bin has one
+__device__ __forceinline__ void append_id(const uint32_t* __restrict__ offset, uint32_t* __restrict__ cursor, uint32_t* __restrict__ pool,
+                                          uint32_t b, uint32_t id) {
+    const uint32_t off = offset[b];
+    if (off != NONE) pool[off + atomicAdd(&cursor[b], 1u)] = id;
+}
+
+// lane = triangle: its id into the list of every bin its box touches (in any order: k_rs_raster sorts).  k_rs_fill_depth is this
+// kernel with the other form of the walk; as one body with two instantiations this one's entry code moved (profiles/raster_isa_resources.md)
 __global__ __launch_bounds__(256) void k_rs_fill(RsParams p, const uint32_t* __restrict__ hdr, const RsTri* __restrict__ tris,
                                                  const uint32_t* __restrict__ offset, uint32_t* __restrict__ cursor,
                                                  uint32_t* __restrict__ pool) {
@@ -597,11 +595,8 @@ __global__ __launch_bounds__(256) void k_rs_fill(RsParams p, const uint32_t* __r
     const RsTri& r = tris[t];
     if (r.n == 0) return;
     const uint32_t px0 = (r.lo & 0xffffu) - p.x0, py0 = (r.lo >> 16) - p.y0, px1 = (r.hi & 0xffffu) - p.x0, py1 = (r.hi >> 16) - p.y0;
-    for (uint32_t by = py0 / BIN; by <= py1 / BIN; by++)
-        for (uint32_t bx = px0 / BIN; bx <= px1 / BIN; bx++) {
-            const uint32_t b = by * p.nbx + bx, off = offset[b];
-            if (off != NONE) pool[off + atomicAdd(&cursor[b], 1u)] = t;
-        }
+    walk_bins<false>(true, px0 / BIN, py0 / BIN, px1 / BIN, py1 / BIN, p.nbx, t,
+                     [&](uint32_t b, uint32_t id) { append_id(offset, cursor, pool, b, id); });
 }
 
 // the depth chain's k_rs_scan: a minimum does not need its list sorted in LDS, so no list is too long, and which bins go without
@@ -631,10 +626,8 @@ __global__ __launch_bounds__(256) void k_rs_fill_depth(RsParams p, const uint32_
     if (t >= hdr[0]) return;
     const RsTri& r = tris[t];
     const uint32_t px0 = (r.lo & 0xffffu) - p.x0, py0 = (r.lo >> 16) - p.y0, px1 = (r.hi & 0xffffu) - p.x0, py1 = (r.hi >> 16) - p.y0;
-    bins_by_wave(r.n != 0, px0 / BIN, py0 / BIN, px1 / BIN, py1 / BIN, p.nbx, t, [&](uint32_t b, uint32_t id) {
-        const uint32_t off = offset[b];
-        if (off != NONE) pool[off + atomicAdd(&cursor[b], 1u)] = id;
-    });
+    walk_bins<true>(r.n != 0, px0 / BIN, py0 / BIN, px1 / BIN, py1 / BIN, p.nbx, t,
+                    [&](uint32_t b, uint32_t id) { append_id(offset, cursor, pool, b, id); });
 }
 
 // edge a -> b at P: (Xb - Xa)(PY - Ya) - (Yb - Ya)(PX - Xa); > 0 inside a front-facing triangle.  On the edge (0) a pixel centre is
@@ -647,130 +640,76 @@ __device__ __forceinline__ int64_t edge_bias(int32_t xa, int32_t ya, int32_t xb,
     return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1;
 }
 
-// ---- the textured resolve's sampler (pbr_hip.h: SamplerLinearWrap as pinned there) ----
-// the texture table and both decode tables, staged in LDS by the block
-struct TexLds {
-    pbr_texture2d tex[PBR_RASTER_MAX_TEXTURES];
-    float dec[512];                        // [0, 256): kUnorm8, [256, 512): kSrgb8
-};
-__device__ __forceinline__ TexLds& tex_lds() {
-    __shared__ TexLds tl;
-    return tl;
-}
-// a texel coordinate's floor wrapped into [0, n) (non-negative modulo; fl is integral, so fmodf is exact)
-__device__ __forceinline__ uint32_t wrap_texel(float fl, uint32_t n) {
-    const float fn = (float)n;
-    float m = fmodf(fl, fn);
-    if (m < 0.0f) m += fn;
-    return m >= 0.0f && m < fn ? (uint32_t)m : 0u;   // (a non-finite coordinate reads texel 0)
-}
-__device__ __forceinline__ float tex_lerp(float a, float b, float f) { return f == 0.0f ? a : fmaf(b, f, a * (1.0f - f)); }
-// NC channels (.x, or .xyz) of texel i of a texture, decoded
-template <int NC>
-__device__ __forceinline__ void texel(const pbr_texture2d& t, const float* dec, size_t i, float* out) {
-    if (t.format == PBR_TEX_R8_UNORM) {
-        out[0] = dec[static_cast<const uint8_t*>(t.texels)[i]];
-        if (NC == 3) { out[1] = 0.0f; out[2] = 0.0f; }
-        return;
+// ---- what the two bin kernels (k_rs_raster, k_rs_depth: block = bin, lane = pixel) share, each piece stated once ----
+// The pixel and the fragment rule are macros that expand to the text the kernels had, not functions: as a struct and a function template
+// taking a lambda they cost k_rs_depth a vector instruction and k_rs_raster<> two SGPRs (profiles/raster_isa_resources.md);
+// raster.hip's PBR_SKYBOX_PIXEL is a macro for the same reason.  Both leave lx, ly, inside, gx, gy, PX, PY in the kernel's scope.
+// the lane's pixel: in the tile (lx, ly; `inside`: the tile is ragged), in the frame (gx, gy), and its centre in 16.8 fixed point
+#define RS_BIN_PIXEL(p, tid)                                                                                                \
+    const uint32_t lx = blockIdx.x * BIN + ((tid) & (BIN - 1)), ly = blockIdx.y * BIN + (tid) / BIN;                        \
+    const bool inside = lx < (p).w && ly < (p).h;                                                                           \
+    [[maybe_unused]] const uint32_t gx = (p).x0 + lx, gy = (p).y0 + ly;                                                     \
+    const int64_t PX = (int64_t)((p).x0 + lx) * 256 + 128, PY = (int64_t)((p).y0 + ly) * 256 + 128
+// THE FRAGMENT RULE, for both chains (pbr_depth_raster's contract is that its depth plane is pbr_gbuffer_raster's bit for bit):
+// the statements `...` run, with `z`, for every fragment of raster record r (the same record for every lane of the block) at
+// RS_BIN_PIXEL's pixel: every fan triangle of the polygon, front-facing and of non-zero area; the three edge functions with the
+// top-left bias; depth interpolated in fp64, rounded once, clamped to [0, 1] (a NaN to 0).
+#define RS_FOR_EACH_FRAGMENT(r, z, ...)                                                                                     \
+    {                                                                                                                       \
+        const uint32_t n = (r).n;                                                                                           \
+        const int32_t X0 = (r).X[0], Y0 = (r).Y[0];                                                                         \
+        const float Z0 = (r).Z[0];                                                                                          \
+        for (uint32_t k = 1; k + 1 < n; k++) {                                                                              \
+            const int32_t X1 = (r).X[k], Y1 = (r).Y[k], X2 = (r).X[k + 1], Y2 = (r).Y[k + 1];                               \
+            const int64_t area = (int64_t)(X1 - X0) * (Y2 - Y0) - (int64_t)(Y1 - Y0) * (X2 - X0);                           \
+            if (area <= 0) continue; /* back-facing or zero area */                                                         \
+            const int64_t w0 = edge_fn(X1, Y1, X2, Y2, PX, PY), w1 = edge_fn(X2, Y2, X0, Y0, PX, PY),                       \
+                          w2 = edge_fn(X0, Y0, X1, Y1, PX, PY);                                                             \
+            if (inside && w0 >= edge_bias(X1, Y1, X2, Y2) && w1 >= edge_bias(X2, Y2, X0, Y0) && w2 >= edge_bias(X0, Y0, X1, Y1)) { \
+                const double z0 = (double)Z0;                                                                               \
+                const double zd = z0 + ((double)w1 * ((double)(r).Z[k] - z0) + (double)w2 * ((double)(r).Z[k + 1] - z0)) / (double)area; \
+                float z = (float)zd;                                                                                        \
+                z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;                                                                \
+                __VA_ARGS__                                                                                                 \
+            }                                                                                                               \
+        }                                                                                                                   \
     }
-    const uint32_t w = static_cast<const uint32_t*>(t.texels)[i];
-    const float* tab = t.format == PBR_TEX_B8G8R8A8_UNORM_SRGB ? dec + 256 : dec;
-    const uint32_t rs = t.format == PBR_TEX_R8G8B8A8_UNORM ? 0u : 16u;   // BGRA: red is byte 2, blue byte 0
-    out[0] = tab[(w >> rs) & 255u];
-    if (NC == 3) {
-        out[1] = tab[(w >> 8) & 255u];
-        out[2] = tab[(w >> (16u - rs)) & 255u];
-    }
-}
-// a palette entry (bc1_decode.hpp: R | G << 8 | B << 16) of a BC1-resident texture, decoded as texel<NC> decodes the stored texel
-template <int NC>
-__device__ __forceinline__ void texel_rgba(uint32_t fmt, const float* dec, uint32_t w, float* out) {
-    const float* tab = fmt == PBR_TEX_B8G8R8A8_UNORM_SRGB ? dec + 256 : dec;
-    out[0] = tab[w & 255u];
-    if (NC == 3) {
-        const bool r8 = fmt == PBR_TEX_R8_UNORM;
-        out[1] = r8 ? 0.0f : tab[(w >> 8) & 255u];
-        out[2] = r8 ? 0.0f : tab[(w >> 16) & 255u];
-    }
-}
-// the four taps of a BC1-resident level of bw x bh blocks at `blocks`: they lie in 1, 2 or 4 blocks; each distinct block is read
-// once (8 bytes) and its palette built once
-template <int NC>
-__device__ __forceinline__ void taps_bc1(const uint2* blocks, uint32_t bw, uint32_t fmt, const float* dec, uint32_t x0, uint32_t y0,
-                                         uint32_t x1, uint32_t y1, float* c00, float* c10, float* c01, float* c11) {
-    const uint32_t bx0 = x0 >> 2, by0 = y0 >> 2, bx1 = x1 >> 2, by1 = y1 >> 2;
-    const bool two_x = bx1 != bx0, two_y = by1 != by0;
-    uint32_t pal[4], bits;
-    auto fetch = [&](uint32_t bx, uint32_t by) {
-        const uint2 b = blocks[(size_t)by * bw + bx];
-        bc1_palette(b.x, pal);
-        bits = b.y;
-    };
-    auto pick = [&](uint32_t x, uint32_t y) { return bc1_texel(pal, bits, x & 3u, y & 3u); };
-    // every tap from the block of (x0, y0) first; a tap in another block is replaced when that block has been read
-    fetch(bx0, by0);
-    uint32_t w00 = pick(x0, y0), w10 = pick(x1, y0), w01 = pick(x0, y1), w11 = pick(x1, y1);
-    if (two_x) {
-        fetch(bx1, by0);
-        w10 = pick(x1, y0);
-        w11 = pick(x1, y1);
-    }
-    if (two_y) {
-        fetch(bx0, by1);
-        w01 = pick(x0, y1);
-        w11 = pick(x1, y1);
-        if (two_x) {
-            fetch(bx1, by1);
-            w11 = pick(x1, y1);
+// THE FALLBACK WALK of a bin without a list: every triangle record in draw order, 256 box tests at a time through list[0 .. 255],
+// f(t) for each record whose pixel box touches the bin (t is uniform across the block)
+template <typename F>
+__device__ __forceinline__ void every_record(const RsParams& p, const uint32_t* __restrict__ hdr, const RsTri* __restrict__ tris,
+                                             uint32_t* list, uint32_t tid, F f) {
+    const uint32_t rx0 = p.x0 + blockIdx.x * BIN, ry0 = p.y0 + blockIdx.y * BIN;
+    const uint32_t rx1 = min(rx0 + BIN, p.x0 + p.w) - 1u, ry1 = min(ry0 + BIN, p.y0 + p.h) - 1u;
+    const uint32_t total = hdr[0];
+    for (uint32_t base = 0; base < total; base += 256u) {
+        const uint32_t t = base + tid;
+        uint32_t hit = 0;
+        if (t < total) {
+            const RsTri& r = tris[t];
+            hit = r.n != 0 && (r.lo & 0xffffu) <= rx1 && (r.hi & 0xffffu) >= rx0 && (r.lo >> 16) <= ry1 && (r.hi >> 16) >= ry0;
         }
+        list[tid] = hit;
+        __syncthreads();
+        const uint32_t m = min(256u, total - base);
+        for (uint32_t j = 0; j < m; j++)
+            if (list[j]) f(base + j);
+        __syncthreads();
     }
-    texel_rgba<NC>(fmt, dec, w00, c00);
-    texel_rgba<NC>(fmt, dec, w10, c10);
-    texel_rgba<NC>(fmt, dec, w01, c01);
-    texel_rgba<NC>(fmt, dec, w11, c11);
 }
-// bilinear on level l (wrap addressing).  BC1: the table may hold BC1-resident textures (the taps come from their blocks; the
-// coordinates, the decode tables and the lerps are the same)
-template <int NC, bool BC1>
-__device__ __forceinline__ void bilinear(const pbr_texture2d& t, const float* dec, uint32_t l, float u, float v, float* out) {
-    const bool blk = BC1 && (t.format & PBR_TEX_BC1_BLOCKS) != 0;
-    size_t off = 0;                        // the level's first texel, or its first block
-    for (uint32_t i = 0; i < l; i++)
-        off += blk ? (size_t)bc1_blocks(t.width >> i) * bc1_blocks(t.height >> i) : (size_t)(t.width >> i) * (t.height >> i);
-    const uint32_t wl = t.width >> l, hl = t.height >> l;
-    const float x = u * (float)wl - 0.5f, y = v * (float)hl - 0.5f;
-    const float flx = floorf(x), fly = floorf(y);
-    const float fx = x - flx, fy = y - fly;
-    const uint32_t x0 = wrap_texel(flx, wl), y0 = wrap_texel(fly, hl);
-    const uint32_t x1 = x0 + 1u == wl ? 0u : x0 + 1u, y1 = y0 + 1u == hl ? 0u : y0 + 1u;
-    float c00[NC], c10[NC], c01[NC], c11[NC];
-    if (blk) {
-        taps_bc1<NC>(static_cast<const uint2*>(t.texels) + off, bc1_blocks(wl), t.format & 0xffu, dec, x0, y0, x1, y1, c00, c10, c01, c11);
-    } else {
-        texel<NC>(t, dec, off + (size_t)y0 * wl + x0, c00);
-        texel<NC>(t, dec, off + (size_t)y0 * wl + x1, c10);
-        texel<NC>(t, dec, off + (size_t)y1 * wl + x0, c01);
-        texel<NC>(t, dec, off + (size_t)y1 * wl + x1, c11);
-    }
-    for (int c = 0; c < NC; c++) out[c] = tex_lerp(tex_lerp(c00[c], c10[c], fx), tex_lerp(c01[c], c11[c], fx), fy);
-}
-// Sample(SamplerLinearWrap, uv) with the quad's uv differences (ddx, ddy): LOD, then trilinear
-template <int NC, bool BC1>
-__device__ __forceinline__ void sample(const pbr_texture2d& t, const float* dec, float u, float v, float dxu, float dxv, float dyu,
-                                       float dyv, float* out) {
-    const float fw = (float)t.width, fh = (float)t.height;
-    const float ax = dxu * fw, ay = dxv * fh, bx = dyu * fw, by = dyv * fh;
-    const float rho = fmaxf(sqrtf(ax * ax + ay * ay), sqrtf(bx * bx + by * by));
-    float lam = rho > 0.0f ? (float)log2((double)rho) : 0.0f;            // 0 or NaN: 0
-    lam = fminf(fmaxf(lam, 0.0f), (float)(t.mip_levels - 1u));
-    const float fl = floorf(lam), f = lam - fl;
-    const uint32_t l = (uint32_t)fl;
-    bilinear<NC, BC1>(t, dec, l, u, v, out);
-    if (f != 0.0f) {                       // (a level with weight 0 does not contribute: tex_lerp)
-        float hi[NC];
-        bilinear<NC, BC1>(t, dec, min(l + 1u, t.mip_levels - 1u), u, v, hi);
-        for (int c = 0; c < NC; c++) out[c] = tex_lerp(out[c], hi[c], f);
-    }
+// the barycentric planes of a resolve record at offset (x, y) from its origin, and what they interpolate: attribute values a0, a1, a2
+// of the three vertices -> ((l0 a0 + l1 a1) + l2 a2) * inv, perspective-correct
+struct RsWeights {
+    float l0, l1, l2, inv;
+    __device__ __forceinline__ float operator()(float a0, float a1, float a2) const { return ((l0 * a0 + l1 * a1) + l2 * a2) * inv; }
+};
+__device__ __forceinline__ RsWeights weights_at(const float* c, float x, float y) {
+    RsWeights w;
+    w.l0 = (c[0] * x + c[1] * y) + c[2];
+    w.l1 = (c[3] * x + c[4] * y) + c[5];
+    w.l2 = (c[6] * x + c[7] * y) + c[8];
+    w.inv = 1.0f / ((w.l0 + w.l1) + w.l2);
+    return w;
 }
 
 // Tex: empty (constant materials), RsRasterTex (textured: the resolve samples the draw's maps) or RsRasterTexBc1 (textured, and
@@ -786,36 +725,19 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
     constexpr bool BC1 = (std::is_same<Tex, RsRasterTexBc1>::value || ...);
     __shared__ uint32_t list[LIST_CAP];
     const uint32_t tid = threadIdx.x;
-    const uint32_t lx = blockIdx.x * BIN + (tid & (BIN - 1)), ly = blockIdx.y * BIN + tid / BIN;
-    const bool inside = lx < p.w && ly < p.h;
-    const uint32_t gx = p.x0 + lx, gy = p.y0 + ly;
-    const int64_t PX = (int64_t)gx * 256 + 128, PY = (int64_t)gy * 256 + 128;
+    RS_BIN_PIXEL(p, tid);
     float zbuf = 1.0f;
     uint32_t sten = 0, win = NONE;
 
-    // one triangle, every fan triangle of its polygon (t is uniform across the block)
+    // one triangle (t is uniform across the block): depth LESS with write, the winner, stencil INCR_SAT on depth pass
     auto fragment = [&](uint32_t t) {
         const RsTri& r = tris[t];
-        const uint32_t n = r.n;
-        const int32_t X0 = r.X[0], Y0 = r.Y[0];
-        const float Z0 = r.Z[0];
-        for (uint32_t k = 1; k + 1 < n; k++) {
-            const int32_t X1 = r.X[k], Y1 = r.Y[k], X2 = r.X[k + 1], Y2 = r.Y[k + 1];
-            const int64_t area = (int64_t)(X1 - X0) * (Y2 - Y0) - (int64_t)(Y1 - Y0) * (X2 - X0);
-            if (area <= 0) continue;             // back-facing or zero area
-            const int64_t w0 = edge_fn(X1, Y1, X2, Y2, PX, PY), w1 = edge_fn(X2, Y2, X0, Y0, PX, PY), w2 = edge_fn(X0, Y0, X1, Y1, PX, PY);
-            if (inside && w0 >= edge_bias(X1, Y1, X2, Y2) && w1 >= edge_bias(X2, Y2, X0, Y0) && w2 >= edge_bias(X0, Y0, X1, Y1)) {
-                const double z0 = (double)Z0;
-                const double zd = z0 + ((double)w1 * ((double)r.Z[k] - z0) + (double)w2 * ((double)r.Z[k + 1] - z0)) / (double)area;
-                float z = (float)zd;
-                z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;
-                if (z < zbuf) {                  // LESS: strictly nearer than every earlier fragment
-                    zbuf = z;
-                    win = t;
-                    sten = sten < 255u ? sten + 1u : 255u;   // INCR_SAT
-                }
-            }
-        }
+        RS_FOR_EACH_FRAGMENT(r, z,
+            if (z < zbuf) {                      // LESS: strictly nearer than every earlier fragment
+                zbuf = z;
+                win = t;
+                sten = sten < 255u ? sten + 1u : 255u;   // INCR_SAT
+            })
     };
 
     if constexpr (TEX) {
@@ -851,24 +773,7 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
                 }
             for (uint32_t i = 0; i < cnt; i++) fragment(__builtin_amdgcn_readfirstlane(list[i]));
         } else {
-            // fallback: every triangle record in draw order, 256 box tests at a time
-            const uint32_t rx0 = p.x0 + blockIdx.x * BIN, ry0 = p.y0 + blockIdx.y * BIN;
-            const uint32_t rx1 = min(rx0 + BIN, p.x0 + p.w) - 1u, ry1 = min(ry0 + BIN, p.y0 + p.h) - 1u;
-            const uint32_t total = hdr[0];
-            for (uint32_t base = 0; base < total; base += 256u) {
-                const uint32_t t = base + tid;
-                uint32_t hit = 0;
-                if (t < total) {
-                    const RsTri& r = tris[t];
-                    hit = r.n != 0 && (r.lo & 0xffffu) <= rx1 && (r.hi & 0xffffu) >= rx0 && (r.lo >> 16) <= ry1 && (r.hi >> 16) >= ry0;
-                }
-                list[tid] = hit;
-                __syncthreads();
-                const uint32_t m = min(256u, total - base);
-                for (uint32_t j = 0; j < m; j++)
-                    if (list[j]) fragment(base + j);
-                __syncthreads();
-            }
+            every_record(p, hdr, tris, list, tid, fragment);
         }
     }
     // resolve: the winner's perspective-correct normal and its draw's constants -> ps_main's outputs
@@ -879,14 +784,10 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
         // the pixel centre's offset from the triangle's origin: exact
         const int32_t ox = (int32_t)(at.origin & 0xffffu), oy = (int32_t)(at.origin >> 16);
         const float fx = (float)((int32_t)gx - ox) + 0.5f, fy = (float)((int32_t)gy - oy) + 0.5f;
-        const float l0 = (at.c[0] * fx + at.c[1] * fy) + at.c[2];
-        const float l1 = (at.c[3] * fx + at.c[4] * fy) + at.c[5];
-        const float l2 = (at.c[6] * fx + at.c[7] * fy) + at.c[8];
-        const float inv = 1.0f / ((l0 + l1) + l2);
+        const RsWeights l = weights_at(at.c, fx, fy);
         // gbuffer.hlsl:99-146, the Use*Map == false branches: AO = 0 (the reference's value without an AO map)
         float4 a = make_float4(d.Albedo[0], d.Albedo[1], d.Albedo[2], d.Emission);
-        float4 b = make_float4(((l0 * at.n[0] + l1 * at.n[3]) + l2 * at.n[6]) * inv, ((l0 * at.n[1] + l1 * at.n[4]) + l2 * at.n[7]) * inv,
-                               ((l0 * at.n[2] + l1 * at.n[5]) + l2 * at.n[8]) * inv, d.Roughness);
+        float4 b = make_float4(l(at.n[0], at.n[3], at.n[6]), l(at.n[1], at.n[4], at.n[7]), l(at.n[2], at.n[5], at.n[8]), d.Roughness);
         float4 c = make_float4(d.Metallic, 0.0f, 0.0f, 0.0f);
         if constexpr (TEX) {
             const RsRasterTex& tx = only(tex...);
@@ -897,12 +798,9 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
                 const RsTexAttr& ta = tx.tex[win];
                 // perspective-correct uv at an offset from the origin, from the triangle's planes
                 auto uv_at = [&](float x, float y, float& u, float& v) {
-                    const float k0 = (at.c[0] * x + at.c[1] * y) + at.c[2];
-                    const float k1 = (at.c[3] * x + at.c[4] * y) + at.c[5];
-                    const float k2 = (at.c[6] * x + at.c[7] * y) + at.c[8];
-                    const float r = 1.0f / ((k0 + k1) + k2);
-                    u = ((k0 * ta.uv[0] + k1 * ta.uv[2]) + k2 * ta.uv[4]) * r;
-                    v = ((k0 * ta.uv[1] + k1 * ta.uv[3]) + k2 * ta.uv[5]) * r;
+                    const RsWeights k = weights_at(at.c, x, y);
+                    u = k(ta.uv[0], ta.uv[2], ta.uv[4]);
+                    v = k(ta.uv[1], ta.uv[3], ta.uv[5]);
                 };
                 float u, v, u00, v00, u10, v10, u01, v01;
                 uv_at(fx, fy, u, v);
@@ -919,9 +817,7 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
                 }
                 if (m.normal != PBR_NO_MAP) {   // sample_normal_texture; the encode's normalize is its normalize
                     const V3 n = normalize3_exact(v3(b.x, b.y, b.z));
-                    const V3 tg = normalize3_exact(v3(((l0 * ta.t[0] + l1 * ta.t[3]) + l2 * ta.t[6]) * inv,
-                                                      ((l0 * ta.t[1] + l1 * ta.t[4]) + l2 * ta.t[7]) * inv,
-                                                      ((l0 * ta.t[2] + l1 * ta.t[5]) + l2 * ta.t[8]) * inv));
+                    const V3 tg = normalize3_exact(v3(l(ta.t[0], ta.t[3], ta.t[6]), l(ta.t[1], ta.t[4], ta.t[7]), l(ta.t[2], ta.t[5], ta.t[8])));
                     const V3 bt = cross3(n, tg);
                     sample<3, BC1>(tl.tex[m.normal], tl.dec, u, v, dxu, dxv, dyu, dyv, s);
                     const float tx_ = s[0] * 2.0f - 1.0f, ty_ = s[1] * 2.0f - 1.0f, tz_ = s[2] * 2.0f - 1.0f;
@@ -956,13 +852,13 @@ __global__ __launch_bounds__(256) void k_rs_raster(RsParams p, const pbr_draw* _
     }
 }
 
-// The depth-only raster: block = bin, lane = pixel, the depth in a register.  Per fragment k_rs_raster's coverage and depth
-// expressions, then the minimum: the fragments of a pixel may come in any order, so the bin's list is walked as k_rs_fill_depth
+// The depth-only raster: block = bin, lane = pixel, the depth in a register.  Per fragment the rule k_rs_raster applies
+// (RS_FOR_EACH_FRAGMENT), then the minimum: the fragments of a pixel may come in any order, so the bin's list is walked as k_rs_fill_depth
 // left it, from the pool, whatever its length: DEPTH_CHUNK raster records at a time are copied into LDS by all 256 lanes (16 bytes
 // each, coalesced) and read from there by every lane at the same address, instead of one dependent scalar load from memory per
 // triangle.  A wave holds four rows of the bin and skips a triangle whose pixel box (RsTri::lo / hi) misses them: a covered pixel's
 // centre lies in a fan triangle, so inside the polygon's bounding box, so in the pixel box; the skip cannot change a bit.  A bin
-// without a list (the pool was full) walks every triangle record and tests its box, as k_rs_raster's fallback does.
+// without a list (the pool was full) walks every triangle record and tests its box (every_record).
 __global__ __launch_bounds__(256) void k_rs_depth(RsParams p, const uint32_t* __restrict__ hdr, const RsTri* __restrict__ tris,
                                                   const uint32_t* __restrict__ count, const uint32_t* __restrict__ offset,
                                                   const uint32_t* __restrict__ pool, float* __restrict__ depth) {
@@ -971,32 +867,15 @@ __global__ __launch_bounds__(256) void k_rs_depth(RsParams p, const uint32_t* __
     static_assert(sizeof(RsTri) % sizeof(uint4) == 0 && alignof(RsTri) >= alignof(uint4), "raster records are copied 16 bytes at a time");
     constexpr uint32_t PARTS = sizeof(RsTri) / sizeof(uint4);
     const uint32_t tid = threadIdx.x;
-    const uint32_t lx = blockIdx.x * BIN + (tid & (BIN - 1)), ly = blockIdx.y * BIN + tid / BIN;
-    const bool inside = lx < p.w && ly < p.h;
-    const int64_t PX = (int64_t)(p.x0 + lx) * 256 + 128, PY = (int64_t)(p.y0 + ly) * 256 + 128;
+    RS_BIN_PIXEL(p, tid);
     // the rows of this wave (global pixels): lanes 64 w .. 64 w + 63 are rows 4 w .. 4 w + 3 of the bin
     const uint32_t wy0 = p.y0 + blockIdx.y * BIN + (tid >> 6) * 4u, wy1 = wy0 + 3u;
     float zbuf = 1.0f;
 
-    // one triangle (the same record for every lane of the block), every fan triangle of its polygon
+    // one triangle (the same record for every lane of the block), unless its rows miss this wave's: the minimum, LESS without a winner
     auto fragment = [&](const RsTri& r) {
         if ((r.lo >> 16) > wy1 || (r.hi >> 16) < wy0) return;
-        const uint32_t n = r.n;
-        const int32_t X0 = r.X[0], Y0 = r.Y[0];
-        const float Z0 = r.Z[0];
-        for (uint32_t k = 1; k + 1 < n; k++) {
-            const int32_t X1 = r.X[k], Y1 = r.Y[k], X2 = r.X[k + 1], Y2 = r.Y[k + 1];
-            const int64_t area = (int64_t)(X1 - X0) * (Y2 - Y0) - (int64_t)(Y1 - Y0) * (X2 - X0);
-            if (area <= 0) continue;             // back-facing or zero area
-            const int64_t w0 = edge_fn(X1, Y1, X2, Y2, PX, PY), w1 = edge_fn(X2, Y2, X0, Y0, PX, PY), w2 = edge_fn(X0, Y0, X1, Y1, PX, PY);
-            if (inside && w0 >= edge_bias(X1, Y1, X2, Y2) && w1 >= edge_bias(X2, Y2, X0, Y0) && w2 >= edge_bias(X0, Y0, X1, Y1)) {
-                const double z0 = (double)Z0;
-                const double zd = z0 + ((double)w1 * ((double)r.Z[k] - z0) + (double)w2 * ((double)r.Z[k + 1] - z0)) / (double)area;
-                float z = (float)zd;
-                z = z > 0.0f ? (z < 1.0f ? z : 1.0f) : 0.0f;
-                if (z < zbuf) zbuf = z;          // the minimum: LESS without a winner
-            }
-        }
+        RS_FOR_EACH_FRAGMENT(r, z, if (z < zbuf) zbuf = z;)
     };
 
     const uint32_t b = blockIdx.y * p.nbx + blockIdx.x;
@@ -1012,23 +891,7 @@ __global__ __launch_bounds__(256) void k_rs_depth(RsParams p, const uint32_t* __
                 __syncthreads();
             }
         } else {
-            const uint32_t rx0 = p.x0 + blockIdx.x * BIN, ry0 = p.y0 + blockIdx.y * BIN;
-            const uint32_t rx1 = min(rx0 + BIN, p.x0 + p.w) - 1u, ry1 = min(ry0 + BIN, p.y0 + p.h) - 1u;
-            const uint32_t total = hdr[0];
-            for (uint32_t base = 0; base < total; base += 256u) {
-                const uint32_t t = base + tid;
-                uint32_t hit = 0;
-                if (t < total) {
-                    const RsTri& r = tris[t];
-                    hit = r.n != 0 && (r.lo & 0xffffu) <= rx1 && (r.hi & 0xffffu) >= rx0 && (r.lo >> 16) <= ry1 && (r.hi >> 16) >= ry0;
-                }
-                list[tid] = hit;
-                __syncthreads();
-                const uint32_t m = min(256u, total - base);
-                for (uint32_t j = 0; j < m; j++)
-                    if (list[j]) fragment(tris[base + j]);
-                __syncthreads();
-            }
+            every_record(p, hdr, tris, list, tid, [&](uint32_t t) { fragment(tris[t]); });
         }
     }
     if (inside) depth[(size_t)ly * p.pitch + lx] = zbuf;
@@ -1058,35 +921,95 @@ void cull_planes(const pbr_global* g, const pbr_tile* tile, float* out) {
     }
 }
 
+// ---- the host side.  What the two descriptors share is exactly pbr_depth_raster_desc (pbr_raster_desc adds four planes and the
+// texture fields): pbr_gbuffer_raster fills one from its own, and the checks, the parameters, the scratch carve and the first two
+// launches take that. ----
+using RsCall = pbr_depth_raster_desc;
+static_assert(sizeof(pbr_raster_desc) == 152 && sizeof(pbr_depth_raster_desc) == 104, "descriptor layouts: no padding");
+
+// What is wrong with the fields both entry points take (nullptr: nothing); the caller refuses under its own name (PBR_CHECK).
+// own_null: one of the caller's other targets is null; own_addr: their addresses ORed, those that must be 4-byte aligned.
+const char* cull_refusal(const RsCall& c) { return c.bounds || !c.stats ? nullptr : "stats without bounds"; }
+const char* call_refusal(const RsCall& c, bool own_null, uintptr_t own_addr) {
+    const pbr_tile* tile = c.tile;
+    if (!(c.g && tile && c.vertices && c.indices && c.draws && c.depth && c.scratch) || own_null) return "null pointer";
+    if (!(c.n_vertices && c.n_indices && c.n_draws && c.max_triangles)) return "empty vertex / index / draw list";
+    if (!(c.n_draws <= PBR_RASTER_MAX_DRAWS && c.max_triangles <= PBR_RASTER_MAX_TRIANGLES)) return "more draws or triangles than the limits";
+    if (!(tile->w && tile->h && tile->full_w && tile->full_h && tile->full_w <= PBR_RASTER_MAX_SIZE && tile->full_h <= PBR_RASTER_MAX_SIZE &&
+          (uint64_t)tile->x0 + tile->w <= tile->full_w && (uint64_t)tile->y0 + tile->h <= tile->full_h))
+        return "bad tile";
+    if (!(c.pitch >= tile->w)) return "pitch < tile width";
+    if (((pbr::addr(c.vertices) | pbr::addr(c.indices) | pbr::addr(c.draws) | pbr::addr(c.depth) | own_addr) & 3u) != 0 ||
+        (pbr::addr(c.scratch) & 15u) != 0)
+        return "unaligned buffer";
+    if ((pbr::addr(c.bounds) & 3u) != 0) return "bounds not 4-byte aligned";
+    if ((pbr::addr(c.stats) & 3u) != 0) return "stats not 4-byte aligned";
+    return nullptr;
+}
+
 // the kernels' parameters of either chain; the pool is what the scratch holds past the layout's minimum
-RsParams params(const pbr_global* g, const pbr_tile* tile, const Layout& L, uint32_t n_vertices, uint32_t n_indices, uint32_t n_draws,
-                uint32_t pitch, size_t scratch_bytes) {
+RsParams params(const RsCall& c, const Layout& L) {
     RsParams p;
-    for (int i = 0; i < 16; i++) { p.View[i] = g->View[i]; p.Projection[i] = g->Projection[i]; }
-    p.half_w = 0.5f * (float)tile->full_w;
-    p.half_h = 0.5f * (float)tile->full_h;
-    p.full_w = tile->full_w; p.full_h = tile->full_h;
-    p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h;
+    for (int i = 0; i < 16; i++) { p.View[i] = c.g->View[i]; p.Projection[i] = c.g->Projection[i]; }
+    p.half_w = 0.5f * (float)c.tile->full_w;
+    p.half_h = 0.5f * (float)c.tile->full_h;
+    p.full_w = c.tile->full_w; p.full_h = c.tile->full_h;
+    p.x0 = c.tile->x0; p.y0 = c.tile->y0; p.w = c.tile->w; p.h = c.tile->h;
     p.nbx = L.nbx;
-    p.n_vertices = n_vertices; p.n_indices = n_indices; p.n_draws = n_draws;
-    p.pitch = pitch;
-    const size_t pool_entries = (scratch_bytes - L.pool) / 4;
+    p.n_vertices = c.n_vertices; p.n_indices = c.n_indices; p.n_draws = c.n_draws;
+    p.pitch = c.pitch;
+    const size_t pool_entries = (c.scratch_bytes - L.pool) / 4;
     // (not min(): on the host HIP's min(size_t, size_t) is min(int, int), which made every capacity 0xfffffffe: no list was ever
     // refused for space, and a pool too small for the lists, the minimum scratch's empty one first of all, was written past its end)
     p.pool_cap = pool_entries < (size_t)0xfffffffeu ? (uint32_t)pool_entries : 0xfffffffeu;
     return p;
 }
 
+// the scratch, carved by its layout (attrs and tex: only where the layout has them), and the two grid sizes of a chain
+struct Carve {
+    uint32_t *hdr, *draw_base, *count, *cursor, *offset, *pool;
+    RsTri* tris;
+    RsAttr* attrs;
+    RsTexAttr* tex;
+    uint32_t n_bins, tri_blocks;
+    Carve(const RsCall& c, const Layout& L) {
+        char* s = static_cast<char*>(c.scratch);
+        const auto words = [s](size_t at) { return reinterpret_cast<uint32_t*>(s + at); };
+        hdr = words(0); draw_base = words(L.draw_base); count = words(L.count); cursor = words(L.cursor); offset = words(L.offset);
+        pool = words(L.pool);
+        tris = reinterpret_cast<RsTri*>(s + L.tris);
+        attrs = reinterpret_cast<RsAttr*>(s + L.attrs);
+        tex = reinterpret_cast<RsTexAttr*>(s + L.tex);
+        n_bins = L.nbx * L.nby;
+        tri_blocks = (c.max_triangles + 255u) / 256u;
+    }
+};
+
+// the first two launches of either chain: k_rs_clear, and k_rs_prep with the model cull (c.bounds set: the planes are formed here) or without
+pbr_status launch_clear_prep(pbr_ctx* ctx, const RsCall& c, const Carve& S) {
+    hipLaunchKernelGGL(k_rs_clear, dim3(min((S.n_bins + 255u) / 256u, 1024u)), dim3(256), 0, ctx->stream, S.count, S.cursor, S.n_bins);
+    if (pbr_status st = pbr::launched(ctx, "k_rs_clear")) return st;
+    if (c.bounds) {
+        RsCull cull{c.bounds, c.stats, {}};
+        cull_planes(c.g, c.tile, cull.planes);
+        hipLaunchKernelGGL(k_rs_prep<RsCull>, dim3(1), dim3(1024), 0, ctx->stream, c.draws, c.n_draws, c.max_triangles, S.draw_base, S.hdr, cull);
+    } else {
+        hipLaunchKernelGGL(k_rs_prep<>, dim3(1), dim3(1024), 0, ctx->stream, c.draws, c.n_draws, c.max_triangles, S.draw_base, S.hdr);
+    }
+    return pbr::launched(ctx, "k_rs_prep");
+}
+
 // pbr_gbuffer_raster: the checks and the six launches.  tx: null without d->maps, else the validated texture table (bc1: it holds a
-// BC1-resident texture); cull: null without d->bounds, else the bounds and stats (the planes are filled here)
-static_assert(sizeof(pbr_raster_desc) == 152, "descriptor layout: no padding");
+// BC1-resident texture)
 pbr_status raster(pbr_ctx* ctx, const pbr_raster_desc* d) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, d, "pbr_gbuffer_raster: null descriptor");
     const auto [g, tile, vertices, indices, draws, A, B, C, depth, stencil, scratch, scratch_bytes, maps, textures, bounds, stats,
                 n_vertices, n_indices, n_draws, max_triangles, pitch, n_textures] = *d;
+    const RsCall c{g, tile, vertices, indices, draws, depth, scratch, scratch_bytes, bounds, stats, n_vertices, n_indices, n_draws,
+                   max_triangles, pitch, 0};
     PBR_REQUIRE(ctx, maps || (!textures && n_textures == 0), "pbr_gbuffer_raster: textures or n_textures without maps");
-    PBR_REQUIRE(ctx, bounds || !stats, "pbr_gbuffer_raster: stats without bounds");
+    PBR_CHECK(ctx, "pbr_gbuffer_raster", cull_refusal(c));
     RsRasterTex table;
     const RsRasterTex* tx = maps ? &table : nullptr;
     bool bc1 = false;
@@ -1107,168 +1030,91 @@ pbr_status raster(pbr_ctx* ctx, const pbr_raster_desc* d) {
             table.table[i] = t;
         }
     }
-    PBR_REQUIRE(ctx, g && tile && vertices && indices && draws && A && B && C && depth && stencil && scratch,
-                "pbr_gbuffer_raster: null pointer");
-    PBR_REQUIRE(ctx, n_vertices && n_indices && n_draws && max_triangles, "pbr_gbuffer_raster: empty vertex / index / draw list");
-    PBR_REQUIRE(ctx, n_draws <= PBR_RASTER_MAX_DRAWS && max_triangles <= PBR_RASTER_MAX_TRIANGLES,
-                "pbr_gbuffer_raster: more draws or triangles than the limits");
-    PBR_REQUIRE(ctx, tile->w && tile->h && tile->full_w && tile->full_h && tile->full_w <= PBR_RASTER_MAX_SIZE &&
-                tile->full_h <= PBR_RASTER_MAX_SIZE && (uint64_t)tile->x0 + tile->w <= tile->full_w &&
-                (uint64_t)tile->y0 + tile->h <= tile->full_h, "pbr_gbuffer_raster: bad tile");
-    PBR_REQUIRE(ctx, pitch >= tile->w, "pbr_gbuffer_raster: pitch < tile width");
-    PBR_REQUIRE(ctx, ((pbr::addr(vertices) | pbr::addr(indices) | pbr::addr(draws) | pbr::addr(A) | pbr::addr(B) | pbr::addr(C) |
-                       pbr::addr(depth)) & 3u) == 0 && (pbr::addr(scratch) & 15u) == 0,
-                "pbr_gbuffer_raster: unaligned buffer");
-    PBR_REQUIRE(ctx, (pbr::addr(bounds) & 3u) == 0, "pbr_gbuffer_raster: bounds not 4-byte aligned");
-    PBR_REQUIRE(ctx, (pbr::addr(stats) & 3u) == 0, "pbr_gbuffer_raster: stats not 4-byte aligned");
-    RsCull cull_pack{bounds, stats, {}};
-    RsCull* cull = bounds ? &cull_pack : nullptr;
+    PBR_CHECK(ctx, "pbr_gbuffer_raster", call_refusal(c, !(A && B && C && stencil), pbr::addr(A) | pbr::addr(B) | pbr::addr(C)));
     const Layout L = layout(tile->w, tile->h, max_triangles, tx != nullptr);
     PBR_REQUIRE(ctx, scratch_bytes >= L.pool, tx ? "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_textured_min_scratch_bytes"
                                                 : "pbr_gbuffer_raster: scratch below pbr_gbuffer_raster_min_scratch_bytes");
+    const RsParams p = params(c, L);
+    const Carve S(c, L);
 
-    const RsParams p = params(g, tile, L, n_vertices, n_indices, n_draws, pitch, scratch_bytes);
-
-    char* s = static_cast<char*>(scratch);
-    uint32_t* hdr = reinterpret_cast<uint32_t*>(s);
-    uint32_t* draw_base = reinterpret_cast<uint32_t*>(s + L.draw_base);
-    uint32_t* count = reinterpret_cast<uint32_t*>(s + L.count);
-    uint32_t* cursor = reinterpret_cast<uint32_t*>(s + L.cursor);
-    uint32_t* offset = reinterpret_cast<uint32_t*>(s + L.offset);
-    RsTri* tris = reinterpret_cast<RsTri*>(s + L.tris);
-    RsAttr* attrs = reinterpret_cast<RsAttr*>(s + L.attrs);
-    RsTexAttr* texattrs = reinterpret_cast<RsTexAttr*>(s + L.tex);
-    uint32_t* pool = reinterpret_cast<uint32_t*>(s + L.pool);
-    const uint32_t n_bins = L.nbx * L.nby;
-    const uint32_t tri_blocks = (max_triangles + 255u) / 256u;
-
-    hipLaunchKernelGGL(k_rs_clear, dim3(min((n_bins + 255u) / 256u, 1024u)), dim3(256), 0, ctx->stream, count, cursor, n_bins);
-    if (pbr_status st = pbr::launched(ctx, "k_rs_clear")) return st;
-    if (cull) {
-        cull_planes(g, tile, cull->planes);
-        hipLaunchKernelGGL(k_rs_prep<RsCull>, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr, *cull);
-    } else {
-        hipLaunchKernelGGL(k_rs_prep<>, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr);
-    }
-    if (pbr_status st = pbr::launched(ctx, "k_rs_prep")) return st;
+    if (pbr_status st = launch_clear_prep(ctx, c, S)) return st;
     if (tx) {
-        const RsSetupTex st{tx->maps, texattrs, tx->n_tex};
-        hipLaunchKernelGGL(k_rs_setup<RsSetupTex>, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, draw_base, hdr,
-                           tris, attrs, count, st);
+        const RsSetupTex st{tx->maps, S.tex, tx->n_tex};
+        hipLaunchKernelGGL(k_rs_setup<RsSetupTex>, dim3(S.tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, S.draw_base,
+                           S.hdr, S.tris, S.attrs, S.count, st);
     } else {
-        hipLaunchKernelGGL(k_rs_setup<>, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, draw_base, hdr, tris,
-                           attrs, count);
+        hipLaunchKernelGGL(k_rs_setup<>, dim3(S.tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, S.draw_base, S.hdr,
+                           S.tris, S.attrs, S.count);
     }
     if (pbr_status st = pbr::launched(ctx, "k_rs_setup")) return st;
-    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(64), 0, ctx->stream, count, n_bins, p.pool_cap, offset);
+    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(64), 0, ctx->stream, S.count, S.n_bins, p.pool_cap, S.offset);
     if (pbr_status st = pbr::launched(ctx, "k_rs_scan")) return st;
-    hipLaunchKernelGGL(k_rs_fill, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, hdr, tris, offset, cursor, pool);
+    hipLaunchKernelGGL(k_rs_fill, dim3(S.tri_blocks), dim3(256), 0, ctx->stream, p, S.hdr, S.tris, S.offset, S.cursor, S.pool);
     if (pbr_status st = pbr::launched(ctx, "k_rs_fill")) return st;
     if (tx) {
         RsRasterTexBc1 rt;
         static_cast<RsRasterTex&>(rt) = *tx;
-        rt.tex = texattrs;
+        rt.tex = S.tex;
         if (bc1)
-            hipLaunchKernelGGL(k_rs_raster<RsRasterTexBc1>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs,
-                               count, offset, pool, A, B, C, depth, stencil, rt);
+            hipLaunchKernelGGL(k_rs_raster<RsRasterTexBc1>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, S.hdr, S.tris, S.attrs,
+                               S.count, S.offset, S.pool, A, B, C, depth, stencil, rt);
         else
-            hipLaunchKernelGGL(k_rs_raster<RsRasterTex>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs, count,
-                               offset, pool, A, B, C, depth, stencil, static_cast<const RsRasterTex&>(rt));
+            hipLaunchKernelGGL(k_rs_raster<RsRasterTex>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, S.hdr, S.tris, S.attrs,
+                               S.count, S.offset, S.pool, A, B, C, depth, stencil, static_cast<const RsRasterTex&>(rt));
     } else {
-        hipLaunchKernelGGL(k_rs_raster<>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, hdr, tris, attrs, count, offset, pool,
-                           A, B, C, depth, stencil);
+        hipLaunchKernelGGL(k_rs_raster<>, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, draws, S.hdr, S.tris, S.attrs, S.count, S.offset,
+                           S.pool, A, B, C, depth, stencil);
     }
     return pbr::launched(ctx, "k_rs_raster");
 }
 
 // pbr_depth_raster: pbr_gbuffer_raster's checks (without the planes it does not take) and the depth chain's six launches
-static_assert(sizeof(pbr_depth_raster_desc) == 104, "descriptor layout: no padding");
 pbr_status depth_raster(pbr_ctx* ctx, const pbr_depth_raster_desc* d) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, d, "pbr_depth_raster: null descriptor");
-    const auto [g, tile, vertices, indices, draws, depth, scratch, scratch_bytes, bounds, stats, n_vertices, n_indices, n_draws,
-                max_triangles, pitch, reserved] = *d;
-    PBR_REQUIRE(ctx, reserved == 0, "pbr_depth_raster: reserved is not 0");
-    PBR_REQUIRE(ctx, bounds || !stats, "pbr_depth_raster: stats without bounds");
-    PBR_REQUIRE(ctx, g && tile && vertices && indices && draws && depth && scratch, "pbr_depth_raster: null pointer");
-    PBR_REQUIRE(ctx, n_vertices && n_indices && n_draws && max_triangles, "pbr_depth_raster: empty vertex / index / draw list");
-    PBR_REQUIRE(ctx, n_draws <= PBR_RASTER_MAX_DRAWS && max_triangles <= PBR_RASTER_MAX_TRIANGLES,
-                "pbr_depth_raster: more draws or triangles than the limits");
-    PBR_REQUIRE(ctx, tile->w && tile->h && tile->full_w && tile->full_h && tile->full_w <= PBR_RASTER_MAX_SIZE &&
-                tile->full_h <= PBR_RASTER_MAX_SIZE && (uint64_t)tile->x0 + tile->w <= tile->full_w &&
-                (uint64_t)tile->y0 + tile->h <= tile->full_h, "pbr_depth_raster: bad tile");
-    PBR_REQUIRE(ctx, pitch >= tile->w, "pbr_depth_raster: pitch < tile width");
-    PBR_REQUIRE(ctx, ((pbr::addr(vertices) | pbr::addr(indices) | pbr::addr(draws) | pbr::addr(depth)) & 3u) == 0 &&
-                (pbr::addr(scratch) & 15u) == 0, "pbr_depth_raster: unaligned buffer");
-    PBR_REQUIRE(ctx, (pbr::addr(bounds) & 3u) == 0, "pbr_depth_raster: bounds not 4-byte aligned");
-    PBR_REQUIRE(ctx, (pbr::addr(stats) & 3u) == 0, "pbr_depth_raster: stats not 4-byte aligned");
-    const Layout L = layout(tile->w, tile->h, max_triangles, false, false);
-    PBR_REQUIRE(ctx, scratch_bytes >= L.pool, "pbr_depth_raster: scratch below pbr_depth_raster_min_scratch_bytes");
-    const RsParams p = params(g, tile, L, n_vertices, n_indices, n_draws, pitch, scratch_bytes);
+    const RsCall& c = *d;
+    PBR_REQUIRE(ctx, c.reserved == 0, "pbr_depth_raster: reserved is not 0");
+    PBR_CHECK(ctx, "pbr_depth_raster", cull_refusal(c));
+    PBR_CHECK(ctx, "pbr_depth_raster", call_refusal(c, false, 0));
+    const Layout L = layout(c.tile->w, c.tile->h, c.max_triangles, false, false);
+    PBR_REQUIRE(ctx, c.scratch_bytes >= L.pool, "pbr_depth_raster: scratch below pbr_depth_raster_min_scratch_bytes");
+    const RsParams p = params(c, L);
+    const Carve S(c, L);
 
-    char* s = static_cast<char*>(scratch);
-    uint32_t* hdr = reinterpret_cast<uint32_t*>(s);
-    uint32_t* draw_base = reinterpret_cast<uint32_t*>(s + L.draw_base);
-    uint32_t* count = reinterpret_cast<uint32_t*>(s + L.count);
-    uint32_t* cursor = reinterpret_cast<uint32_t*>(s + L.cursor);
-    uint32_t* offset = reinterpret_cast<uint32_t*>(s + L.offset);
-    RsTri* tris = reinterpret_cast<RsTri*>(s + L.tris);
-    uint32_t* pool = reinterpret_cast<uint32_t*>(s + L.pool);
-    const uint32_t n_bins = L.nbx * L.nby;
-    const uint32_t tri_blocks = (max_triangles + 255u) / 256u;
-
-    hipLaunchKernelGGL(k_rs_clear, dim3(min((n_bins + 255u) / 256u, 1024u)), dim3(256), 0, ctx->stream, count, cursor, n_bins);
-    if (pbr_status st = pbr::launched(ctx, "k_rs_clear")) return st;
-    if (bounds) {
-        RsCull cull{bounds, stats, {}};
-        cull_planes(g, tile, cull.planes);
-        hipLaunchKernelGGL(k_rs_prep<RsCull>, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr, cull);
-    } else {
-        hipLaunchKernelGGL(k_rs_prep<>, dim3(1), dim3(1024), 0, ctx->stream, draws, n_draws, max_triangles, draw_base, hdr);
-    }
-    if (pbr_status st = pbr::launched(ctx, "k_rs_prep")) return st;
-    hipLaunchKernelGGL(k_rs_setup<RsSetupDepth>, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, vertices, indices, draws, draw_base, hdr,
-                       tris, static_cast<RsAttr*>(nullptr), count, RsSetupDepth{});
+    if (pbr_status st = launch_clear_prep(ctx, c, S)) return st;
+    hipLaunchKernelGGL(k_rs_setup<RsSetupDepth>, dim3(S.tri_blocks), dim3(256), 0, ctx->stream, p, c.vertices, c.indices, c.draws, S.draw_base,
+                       S.hdr, S.tris, static_cast<RsAttr*>(nullptr), S.count, RsSetupDepth{});
     if (pbr_status st = pbr::launched(ctx, "k_rs_setup")) return st;
-    hipLaunchKernelGGL(k_rs_scan_depth, dim3(1), dim3(1024), 0, ctx->stream, count, n_bins, p.pool_cap, offset);
+    hipLaunchKernelGGL(k_rs_scan_depth, dim3(1), dim3(1024), 0, ctx->stream, S.count, S.n_bins, p.pool_cap, S.offset);
     if (pbr_status st = pbr::launched(ctx, "k_rs_scan_depth")) return st;
-    hipLaunchKernelGGL(k_rs_fill_depth, dim3(tri_blocks), dim3(256), 0, ctx->stream, p, hdr, tris, offset, cursor, pool);
+    hipLaunchKernelGGL(k_rs_fill_depth, dim3(S.tri_blocks), dim3(256), 0, ctx->stream, p, S.hdr, S.tris, S.offset, S.cursor, S.pool);
     if (pbr_status st = pbr::launched(ctx, "k_rs_fill_depth")) return st;
-    hipLaunchKernelGGL(k_rs_depth, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, hdr, tris, count, offset, pool, depth);
+    hipLaunchKernelGGL(k_rs_depth, dim3(L.nbx, L.nby), dim3(256), 0, ctx->stream, p, S.hdr, S.tris, S.count, S.offset, S.pool, c.depth);
     return pbr::launched(ctx, "k_rs_depth");
+}
+
+// the recommended scratch of a layout: its minimum and a pool of 8 entries per triangle and 4 per bin
+size_t recommended(const Layout& L, uint32_t n_triangles) {
+    return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
-    return layout(w, h, n_triangles).pool;
-}
+size_t pbr_gbuffer_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) { return layout(w, h, n_triangles).pool; }
+size_t pbr_gbuffer_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) { return recommended(layout(w, h, n_triangles), n_triangles); }
 
-size_t pbr_gbuffer_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
-    const Layout L = layout(w, h, n_triangles);
-    return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
-}
-
-size_t pbr_gbuffer_raster_textured_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
-    return layout(w, h, n_triangles, true).pool;
-}
-
+size_t pbr_gbuffer_raster_textured_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) { return layout(w, h, n_triangles, true).pool; }
 size_t pbr_gbuffer_raster_textured_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
-    const Layout L = layout(w, h, n_triangles, true);
-    return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
+    return recommended(layout(w, h, n_triangles, true), n_triangles);
 }
 
 pbr_status pbr_gbuffer_raster(pbr_ctx* ctx, const pbr_raster_desc* d) { return raster(ctx, d); }
 
-size_t pbr_depth_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
-    return layout(w, h, n_triangles, false, false).pool;
-}
-
+size_t pbr_depth_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) { return layout(w, h, n_triangles, false, false).pool; }
 size_t pbr_depth_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles) {
-    const Layout L = layout(w, h, n_triangles, false, false);
-    return L.pool + align256(((size_t)8 * n_triangles + (size_t)4 * L.nbx * L.nby) * 4);
+    return recommended(layout(w, h, n_triangles, false, false), n_triangles);
 }
 
 pbr_status pbr_depth_raster(pbr_ctx* ctx, const pbr_depth_raster_desc* d) { return depth_raster(ctx, d); }

@@ -18,8 +18,10 @@ Reported:
   * with --phases, per-phase counts: shade.hip compiled once per PBR_EXP_* switch that removes one phase of shade_pixel; the
     difference of the kernels' static v_* counts is that phase.
 Only instruction CLASSES are counted (v_*, v_pk_*, the transcendental unit's, moves, ds_*, global_*, s_waitcnt, s_barrier, other s_*).
-    python tools/isa_phase_count.py --bloom parent_bloom.hip [out.md]
-compares every kernel instantiation of bloom.hip with those of another copy of the source (see bloom_report below)."""
+    python tools/isa_phase_count.py --bloom parent_bloom.hip [out.md] [--src gbuffer_raster.hip] [--flags "-ffp-contract=off"] [--also-with PBR_DEBUG_KNOBS]
+compares every kernel instantiation of a translation unit (bloom.hip unless --src names another; --flags: what the Makefile adds for
+it, bloom.hip's by default) with those of another copy of the source, which includes the headers that lie beside it (see bloom_report
+below); --also-with adds the same table for the build with that macro defined."""
 import os
 import re
 import subprocess
@@ -196,8 +198,9 @@ def phases(src=SRC, fold=False):
     return doc
 
 
-# ---- bloom.hip: resources and instruction classes of EVERY kernel instantiation, for a change that must leave the generated code
-# as it is (profiles/bloom_isa_resources.md, tests/test_bloom_isa_cpu.py):  python tools/isa_phase_count.py --bloom parent_bloom.hip [out.md]
+# ---- bloom.hip, or the unit --src names: resources and instruction classes of EVERY kernel instantiation, for a change that must leave the
+# generated code as it is (profiles/bloom_isa_resources.md, tests/test_bloom_isa_cpu.py; profiles/raster_isa_resources.md):
+#   python tools/isa_phase_count.py --bloom parent_bloom.hip [out.md]
 BLOOM_SRC = os.path.join(CSRC, "bloom.hip")
 BLOOM_FLAGS = ("-ffp-contract=off",)   # the Makefile's flags of bloom.o
 BLOOM_COLS = [("valu", "v_*"), ("ds", "ds_*"), ("global", "global_*"), ("waitcnt", "s_waitcnt"), ("barrier", "s_barrier"), ("salu", "other s_*"),
@@ -216,29 +219,32 @@ def kernel_table(text):
 
 
 def exceeds(new, ref):
-    """the columns in which `new` breaks the condition against `ref`: LDS and occupancy equal, no scratch, registers and the counts of
-    v_*, ds_*, global_*, s_waitcnt and s_barrier no higher (scalar-ALU counts may move)"""
-    return ([c for c in ("lds", "occupancy") if new[c] != ref[c]] + (["scratch"] if new["scratch"] else []) +
-            [c for c in ("vgprs", "sgprs", "valu", "ds", "global", "waitcnt", "barrier") if new[c] > ref[c]])
+    """the columns in which `new` breaks the condition against `ref`: LDS and occupancy equal, scratch (none in bloom.hip; k_rs_setup's
+    clip arrays in gbuffer_raster.hip), registers and the counts of v_*, ds_*, global_*, s_waitcnt and s_barrier no higher (scalar-ALU
+    counts may move)"""
+    return ([c for c in ("lds", "occupancy") if new[c] != ref[c]] +
+            [c for c in ("scratch", "vgprs", "sgprs", "valu", "ds", "global", "waitcnt", "barrier") if new[c] > ref[c]])
 
 
-def bloom_report(parent_src, new_src=BLOOM_SRC):
+def bloom_report(parent_src, new_src=BLOOM_SRC, flags=BLOOM_FLAGS, defines=()):
     with ThreadPoolExecutor(2) as ex:
-        parent, new = ex.map(lambda s: kernel_table(compile_isa((), s, BLOOM_FLAGS)), [parent_src, new_src])
+        parent, new = ex.map(lambda s: kernel_table(compile_isa(defines, s, flags)), [parent_src, new_src])
     same = [n for n in new if n in parent and new[n][1] == parent[n][1]]
-    doc = ["# bloom.hip: every kernel instantiation of the gfx950 ISA, parent commit and this tree (static counts)", "",
+    unit = os.path.basename(new_src)
+    doc = [f"# {unit}{''.join(' -D' + d for d in defines)}: every kernel instantiation of the gfx950 ISA, parent commit and this tree (static counts)", "",
            f"{len(new)} kernels, {len(same)} with the parent's instruction stream byte for byte (`same` below); " +
-           f"kernels of the parent that are gone: {sorted(set(parent) - set(new)) or 'none'}", "",
-           "Mangled template arguments: `k_blur_hv<MODE (1 M_DOWN, 2 M_UP), DUAL, TAIL, TH, NT, views>`, `k_blur_up_poly<DUAL, TAIL, TH, views>`, " +
-           "`Lb0E` / `Lb1E` = false / true, `LiNE` = N.", "",
-           "| kernel | side | " + " | ".join(t for _, t in BLOOM_COLS) + " | same |", "|---" * (len(BLOOM_COLS) + 3) + "|"]
+           f"kernels of the parent that are gone: {sorted(set(parent) - set(new)) or 'none'}", ""]
+    if unit == "bloom.hip":
+        doc += ["Mangled template arguments: `k_blur_hv<MODE (1 M_DOWN, 2 M_UP), DUAL, TAIL, TH, NT, views>`, `k_blur_up_poly<DUAL, TAIL, TH, views>`, " +
+                "`Lb0E` / `Lb1E` = false / true, `LiNE` = N.", ""]
+    doc += ["| kernel | side | " + " | ".join(t for _, t in BLOOM_COLS) + " | same |", "|---" * (len(BLOOM_COLS) + 3) + "|"]
     for n, (row, _) in new.items():
         for side, r in (("parent", parent.get(n, (None,))[0]), ("new", row)):
             if r:
                 note = "yes" if n in same else ("no" if n in parent else "-")
                 doc.append(f"| `{n}` | {side} | " + " | ".join(str(r[k]) for k, _ in BLOOM_COLS) + f" | {note} |")
     bad = {n: exceeds(new[n][0], parent[n][0]) for n in new if n in parent and exceeds(new[n][0], parent[n][0])}
-    doc += ["", "condition (LDS and occupancy equal, scratch 0, VGPR / SGPR / v_* / ds_* / global_* / s_waitcnt / s_barrier no higher): " +
+    doc += ["", "condition (LDS and occupancy equal, scratch / VGPR / SGPR / v_* / ds_* / global_* / s_waitcnt / s_barrier no higher): " +
             ("held by every kernel" if not bad else f"BROKEN by {bad}")]
     return doc, bad
 
@@ -254,7 +260,17 @@ def parse_bloom_rows(md_text, side="new"):
 def main(argv):
     if "--bloom" in argv:
         rest = [a for a in argv if a != "--bloom"]
-        doc, bad = bloom_report(rest[0])
+        opt = {}
+        for name in ("--src", "--flags", "--also-with"):
+            if name in rest:
+                k = rest.index(name)
+                opt[name] = rest[k + 1]
+                del rest[k:k + 2]
+        src, flags = opt.get("--src", BLOOM_SRC), tuple(opt["--flags"].split()) if "--flags" in opt else BLOOM_FLAGS
+        doc, bad = bloom_report(rest[0], src, flags)
+        if "--also-with" in opt:
+            more, bad_more = bloom_report(rest[0], src, flags, (opt["--also-with"],))
+            doc, bad = doc + [""] + more, dict(bad, **{n + " -D" + opt["--also-with"]: c for n, c in bad_more.items()})
         text = "\n".join(doc) + "\n"
         print(text)
         if len(rest) > 1:
