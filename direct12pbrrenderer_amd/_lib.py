@@ -31,6 +31,7 @@ SIGNATURES = {
     "pbr_ctx_side_end": (_int, [_vp]),
     "pbr_ctx_side_join": (_int, [_vp]),
     "pbr_last_error": (C.c_char_p, [_vp]),
+    "pbr_launch_log": (C.c_uint64, [_vp, _vp, _u32]),
     "pbr_sync": (_int, [_vp]),
     "pbr_brdf_lut": (_int, [_vp, _u32, _vp]),
     "pbr_rgbe_decode": (_int, [_vp, _vp, C.c_size_t, _vp]),

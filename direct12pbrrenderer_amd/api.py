@@ -20,6 +20,9 @@ class PbrError(RuntimeError):
     pass
 
 
+LAUNCH_LOG = 64   # PBR_LAUNCH_LOG (include/pbr_hip.h): the launches whose labels a context keeps
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -92,6 +95,20 @@ class PbrContext:
         if st != 0:
             msg = self.lib.pbr_last_error(self.h)
             raise PbrError(f"status {st}: {msg.decode() if msg else '?'}")
+
+    def launch_log(self, last=LAUNCH_LOG):
+        """pbr_launch_log: (launches since the context was created, the labels of the last min(last, 64, that many), oldest first).
+        Which kernel an entry point chose is read here, e.g. count before, call, labels of the count's increase."""
+        out = (C.c_char_p * LAUNCH_LOG)()
+        total = int(self.lib.pbr_launch_log(self.h, C.cast(out, C.c_void_p), min(int(last), LAUNCH_LOG)))
+        return total, [out[i].decode() for i in range(min(total, int(last), LAUNCH_LOG))]
+
+    def launches_of(self, call):
+        """run call() and return the labels of the kernels it launched (at most the last 64)"""
+        before = self.launch_log(0)[0]
+        call()
+        total = self.launch_log(0)[0]
+        return self.launch_log(total - before)[1]
 
     def side_begin(self):
         """Calls until side_end() enqueue on the context's high-priority side stream (after all earlier work)."""

@@ -917,8 +917,8 @@ static pbr_status launch_hv(pbr_ctx* ctx, const LevelViews& lv, uint32_t nv, uin
             return launch(k_blur_up_poly<DUAL, TAIL, 32, VS>, wide, MV ? "k_blur_up_poly<views>" : "k_blur_up_poly");
     }
     const TileGrid tall = tile_grid(tr, 64, 32);
-    if (tall.n >= 900) return launch(k_blur_hv<MODE, DUAL, TAIL, 32, 512, VS>, tall, MV ? "k_blur_hv<views>" : "k_blur_hv");
-    return launch(k_blur_hv<MODE, DUAL, TAIL, 16, 512, VS>, tile_grid(tr, 64, 16), MV ? "k_blur_hv<views>" : "k_blur_hv");
+    if (tall.n >= 900) return launch(k_blur_hv<MODE, DUAL, TAIL, 32, 512, VS>, tall, MV ? "k_blur_hv/32<views>" : "k_blur_hv/32");
+    return launch(k_blur_hv<MODE, DUAL, TAIL, 16, 512, VS>, tile_grid(tr, 64, 16), MV ? "k_blur_hv/16<views>" : "k_blur_hv/16");
 }
 
 // a fused level's view table for n views: io(i) gives view i's input, second input (DUAL; else null), output, output pitch, histogram
@@ -1125,8 +1125,11 @@ struct BloomView { pbr_half* hdr; uint32_t pitch; pbr_half* A; pbr_half* B; uint
 // merge0 (one view, exact level 0 only): the rectangle {x, y, w, h} of level 0 to merge; origin: its level coordinates of hdr[0].  The
 // up-pass of level l is then run only on the tiles of level l inside up_pass_rects' rectangle (a tiled frame's bloom works on the
 // tile +- 256 px, but only the DOWN-pass needs that apron in full: SURVEY 8e's "cheaper apron").  Whole tiles are computed, so every
-// texel inside the rectangles is what the full pass computes: the merged interior is bit-identical.  Texels of the up-levels outside
-// them are left as they were.
+// texel inside the rectangles is what the SAME kernel computes on the whole level: the merged interior is bit-identical to the full
+// up-pass where both select the same kernels.  launch_hv chooses by the tiles of the rectangle — the work the launch really has —
+// so a level can take k_blur_hv on its rectangle where the whole level takes k_blur_up_poly (level 1 of a 2432 x 2672 extended tile;
+// tests/bloom_truth.py up_kernel says where); then both results lie inside the pyramid's float64 interval and differ by at most one
+// half step per stage (tests/test_gpu_bloom_tiled_truth.py).  Texels of the up-levels outside the rectangles are left as they were.
 template <bool MV>
 static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint32_t w, uint32_t h, bool prefilter, float threshold, float knee,
                              const uint32_t* hist_rect, float min_log, float inv_range, const uint32_t* merge0 = nullptr, const uint32_t* origin = nullptr) {

@@ -154,6 +154,14 @@ void* pbr_ctx_get_stream(const pbr_ctx* ctx) { return ctx ? (void*)ctx->stream :
 
 const char* pbr_last_error(const pbr_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
+uint64_t pbr_launch_log(const pbr_ctx* ctx, const char** out, uint32_t cap) {
+    if (!ctx) return 0;
+    uint64_t n = ctx->launch_count < (uint64_t)PBR_LAUNCH_LOG ? ctx->launch_count : (uint64_t)PBR_LAUNCH_LOG;
+    if (n > cap) n = cap;
+    for (uint64_t i = 0; out && i < n; i++) out[i] = ctx->launch_log[(ctx->launch_count - n + i) % PBR_LAUNCH_LOG];
+    return ctx->launch_count;
+}
+
 pbr_status pbr_sync(pbr_ctx* ctx) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -33,6 +33,9 @@ struct pbr_ctx {
     std::vector<uint32_t> side_cu_mask;   // pbr_ctx_set_cu_masks: the side stream's CUs (empty: all, high priority)
     bool bloom_shader_order = false;      // pbr_ctx_set_bloom_shader_order: large 2x-up bloom levels in the shader's operation order (bit-exact)
     int cu_count = 0;                     // compute units of the device (the shade sizes its blocks by the resident-block count)
+    // pbr_launch_log: the labels of the last PBR_LAUNCH_LOG launches (string literals, a ring) and how many launches there were
+    const char* launch_log[PBR_LAUNCH_LOG] = {};
+    uint64_t launch_count = 0;
 };
 
 namespace pbr {
@@ -52,8 +55,9 @@ inline pbr_status hip_fail(pbr_ctx* ctx, hipError_t e, const char* where) {
     }
     return PBR_ERR_HIP;
 }
-// after a kernel launch
+// after a kernel launch; `where` is a string literal: the launch log keeps the pointer
 inline pbr_status launched(pbr_ctx* ctx, const char* where) {
+    ctx->launch_log[ctx->launch_count++ % PBR_LAUNCH_LOG] = where;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(ctx, e, where);
     return PBR_OK;

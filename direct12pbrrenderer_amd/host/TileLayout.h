@@ -2,7 +2,7 @@
 // renders one frame on one device).  Pure host arithmetic, no device calls.
 //
 // A frame of FullW x FullH pixels is cut into Cols x Rows equal tiles; rank r owns tile (r % Cols, r / Cols): its
-// INTERIOR.  Bloom's cumulative support is ~220 full-res pixels, so the bloom pyramid of a tile runs on the extended
+// INTERIOR.  Bloom's cumulative support is 195 full-res pixels (tests/test_bloom_truth_cpu.py), so the bloom pyramid of a tile runs on the extended
 // rectangle E = interior + Apron on every side that has a neighbour (clipped to the frame).  Two ways to fill E:
 //   apron mode : the device shades all of E (S == E) — no data-path collective, 42 % extra pixels on an inner cfg5 tile;
 //   halo  mode : the device shades S = interior + 4 px (what the bloom prefilter's five taps reach: full-res pixels

@@ -19,8 +19,10 @@ from .api import PbrContext, make_sun, sun_fit
 from .scene import draw_bounds, world_box
 from .structs import (AABB_DTYPE, DRAW_MAPS_DTYPE, ENV_MIPS, HISTOGRAM_BINS, MAX_VIEWS, NO_MAP, TABLES_BUILT_FRAME, TABLES_BUILT_GEOMETRY, GBuffer, Global, Tile, View)
 
-# bloom's cumulative support is ~220 full-res pixels (3 down + 3 up levels of a radius-4 kernel on
-# a 2x pyramid); 256 also keeps every mip of the extended tile on the full frame's texel grid
+# bloom's cumulative support: a pixel of an interior whose edges are multiples of 16 depends on level-1 texels
+# up to 192 full-res pixels outside it, 195 with the prefilter's reads (3 down + 3 up levels of a radius-4
+# kernel on a 2x pyramid; 202 / 205 at any alignment: tests/test_bloom_truth_cpu.py derives both from the
+# kernels' integer taps); 256 also keeps every mip of the extended tile on the full frame's texel grid
 # (multiple of 16 = 2^(BLOOM_MIPS-1)).
 DEFAULT_APRON = 256
 # halo mode: the bloom prefilter of a half-res texel reads full-res pixels 2x-3 .. 2x+2 (five taps one half-res

@@ -164,6 +164,13 @@ pbr_status  pbr_ctx_side_join(pbr_ctx* ctx);
  * costs the polyphase form's gain (~2 % of a 4K frame). */
 pbr_status  pbr_ctx_set_bloom_shader_order(pbr_ctx* ctx, int on);
 const char* pbr_last_error(const pbr_ctx* ctx);
+/* Which kernels ran: the context keeps the labels of its last PBR_LAUNCH_LOG kernel launches (host side only: no allocation, nothing
+ * on the device).  Returns the number of launches since the context was created and stores the labels of the last
+ * min(cap, PBR_LAUNCH_LOG, that number) of them in out, oldest first (out may be null: the count alone).  A label is the kernel's
+ * name, with the instance where an entry point chooses between several: "k_blur_hv/16" and "k_blur_hv/32" (the tile height),
+ * "k_blur_up_poly", "k_blur_hv/16<views>" ...; the strings are static. */
+#define PBR_LAUNCH_LOG 64
+uint64_t    pbr_launch_log(const pbr_ctx* ctx, const char** out, uint32_t cap);
 /* blocks until everything enqueued through the context is done: its stream AND side-stream work not joined yet */
 pbr_status  pbr_sync(pbr_ctx* ctx);
 const char* pbr_version(void);

@@ -95,6 +95,24 @@ Measured (the undecided shares are the truth's own; noise / smooth / black / sub
   So the "<= 1 fp16 ULP per stage, <= 2 end to end" allowance of tests/test_gpu_parity.py is sound: where the polyphase kernel and
   the oracle differ, both are admissible roundings of the same truth.
   The fused kernels' premise (tap1d's integer taps, the prefilter's quad means) holds at every size 1 .. 8192 they are launched for.
+
+The tiled pass (pbr_bloom_tiled, the multi-GPU path).  tiled_chain is the same interval propagation started from a GIVEN level 1 of
+the extended tile E and merged over merge_rect; no new band.  What the kernels add to that — the up-pass on rectangles, the kernel
+chosen by the rectangle's tiles, the first tile, buf_origin — is restated as integers: up_pass_rects (the rule of csrc/bloom.hip),
+up_pass_dependency (the exact rectangles from tap1d's taps), up_kernel / tiled_kernels (launch_hv's choice).  Proven on the CPU
+(tests/test_bloom_truth_cpu.py): the rule's rectangles contain the exact ones with 1 .. 2 texels to spare per side at level 1 and
+2 .. 3 at levels 2 .. 4, for every residue mod 32 of origin and size; an interior pixel depends on level-1 texels at most 192 pixels
+outside an interior aligned to 16, 195 with the prefilter's reads (202 / 205 at any alignment), under the apron of 256; behind that
+apron a rank's float64 values are the frame's own, bit for bit (and stay so down to an apron of 144 / 160 on the two noise frames
+tried: the half stores in between swallow what the far taps contribute).
+Measured on the MI355X (tests/test_gpu_bloom_tiled_truth.py): TILED_SMALL and TILED_BIG intervals at most 2 wide, 0.9 .. 1.6 %
+undecided; every merged value inside, shrunk and whole up-pass alike.  2432 x 2672 (level 1: k_blur_hv/16 on the rectangle,
+k_blur_up_poly on the whole level): 371 of 16 588 800 merged values differ between the two, by at most 2 half steps, all where the
+interval is not degenerate; the other three big cases select the same kernels either way and are bit-identical.  The tail's histogram
+equals pbr_lum_histogram on the merged window exactly; against the float64 bins of the stored output it differs by 0 .. 1 pixel on
+the small cases and 10 .. 43 of 1.6 .. 8.3 M on the big ones, every one of them among the 2 .. 5 in ten thousand pixels that
+exposure_truth calls ambiguous (within its derived band of a bin edge) and counted in the bin on the other side of that edge —
+which is what check_tiled asserts: exact where the truth decides.
 """
 import numpy as np
 
@@ -406,6 +424,57 @@ def run_chain(img, ops):
     return ops.merge(img, ops.blur_v(ops.blur_h(a[1], w, h), w, h))
 
 
+def up_pass_from_level1(level1, ops, ew, eh, after_up=None):
+    """run_chain between its prefilter and level 0: the three down levels and the three up levels of an ew x eh frame whose level 1
+    [eh / 2, ew / 2, 4] is given.  Returns the finished level 1.  after_up(level, result) -> result exists for the defect tests."""
+    a = {1: np.ascontiguousarray(level1, dtype=np.float16)}
+    assert a[1].shape[:2] == (eh >> 1, ew >> 1)
+    for l in (1, 2, 3):
+        ow, oh = ew >> (l + 1), eh >> (l + 1)
+        a[l + 1] = ops.blur_v(ops.blur_h(a[l], ow, oh), ow, oh)
+    for l in (3, 2, 1):
+        a[l] = ops.blur_v(ops.upsample_add(a[l], a[l + 1]), ew >> l, eh >> l)
+        if after_up is not None:
+            a[l] = after_up(l, a[l])
+    return a[1]
+
+
+def run_from_level1(level1, ops, ew, eh, after_up=None):
+    """run_chain after its prefilter and before its merge: what the merge adds, [eh, ew, 4] half"""
+    return ops.blur_v(ops.blur_h(up_pass_from_level1(level1, ops, ew, eh, after_up), ew, eh), ew, eh)
+
+
+def level0_truth(level1):
+    """the float64 truth T of what the merge adds, in front of its half store, every earlier stage being its rounded truth"""
+    eh, ew = 2 * level1.shape[0], 2 * level1.shape[1]
+    ops = Ops(0)
+    return blur_v(ops.blur_h(up_pass_from_level1(level1, ops, ew, eh), ew, eh), ew, eh)[0]
+
+
+def window(img, rect, origin=(0, 0)):
+    """the texels of rect = (x, y, w, h) of an image whose texel [0, 0] sits at `origin`"""
+    x, y, w, h = rect
+    return img[y - origin[1]:y - origin[1] + h, x - origin[0]:x - origin[0] + w]
+
+
+def tiled_chain(level1, hdr, hdr_rect, merge_rect, ops=None):
+    """pbr_bloom_tiled (csrc/bloom.hip): BloomPass::Execute minus its prefilter on the extended tile E whose half level-1 plane
+    [eh / 2, ew / 2, 4] is GIVEN, merged into the HDR texels of merge_rect = (x, y, w, h) of E.  hdr [h, w, 4] holds hdr_rect of E.
+    Returns (lo, hi) over merge_rect: the chain's interval propagation, nothing new in it — the pyramid is that of E (clamped at
+    E's edges, every level whole), the bands are K_BLUR, K_DUAL and K_MERGE.  That the kernels run the up-pass on rectangles only
+    is their business: up_pass_dependency says which texels the merged rectangle reads.  With `ops` one run of those stage
+    functions instead of the two ends."""
+    level1 = np.ascontiguousarray(level1, dtype=np.float16)
+    assert (level1.astype(np.float32) >= 0).all() and (np.asarray(hdr).astype(np.float32) >= 0).all()
+    eh, ew = 2 * level1.shape[0], 2 * level1.shape[1]
+    mine = window(np.asarray(hdr), merge_rect, hdr_rect[:2])
+    assert mine.shape[:2] == (merge_rect[3], merge_rect[2]), "merge_rect outside hdr_rect"
+
+    def run(o):
+        return o.merge(mine, window(run_from_level1(level1, o, ew, eh), merge_rect))
+    return run(ops) if ops is not None else (run(Ops(-1)), run(Ops(+1)))
+
+
 def chain(img, threshold=THRESHOLD, knee=KNEE):
     """(lo, hi): the halves between which every implementation that meets the per-stage bands must land, per texel.  Every stage
     after the prefilter is monotone in its input (positive weights, clamp addressing, RN_half, the sums), the prefilter's input is
@@ -486,6 +555,35 @@ def check_chain(got, lo, hi, what=""):
     return {"width": width, "degenerate": deg}
 
 
+def output_histogram(image):
+    """exposure_truth's 256 float64 counts of a stored image [h, w, 4]"""
+    import exposure_truth as et
+    return et.hist_of(et.image_bins(image)[0]).astype(np.int64)
+
+
+def check_tiled(case, before, after, hist, lo, hi, what=""):
+    """One pbr_bloom_tiled call under the truth.  before / after: the HDR buffer [rows of hdr_rect, hdr_pitch, 4] as uint16 bits;
+    hist: the 256 counts the call added to zeros (None: a call without histogram); lo, hi: tiled_chain's interval.  The merged
+    rectangle inside the interval at every texel and channel; every other texel of the buffer, the pitch padding included, keeps
+    its bits; the histogram's sum is the rectangle's area and its counts are exposure_truth's bins of the stored output — exactly
+    for every pixel that truth decides; a pixel within its band of a bin edge (two or three in ten thousand of these outputs) may
+    be counted on either side (exposure_truth.check_histogram_of_output).  Returns check_chain's figures and those two counts."""
+    (hx, hy, hw, hh), (mx, my, mw, mh) = case.hdr_rect, case.merge_rect
+    assert before.shape == after.shape == (hh, case.hdr_pitch, 4) and before.dtype == after.dtype == np.uint16
+    rows, cols = slice(my - hy, my - hy + mh), slice(mx - hx, mx - hx + mw)
+    got = np.ascontiguousarray(after[rows, cols]).view(np.float16)
+    r = check_chain(got, lo, hi, what)
+    kept = after == before
+    kept[rows, cols] = True
+    assert kept.all(), f"{what}: {int((~kept).sum())} values outside the merged rectangle changed; first at {tuple(np.argwhere(~kept)[0])}"
+    if hist is not None:
+        h = np.asarray(hist).astype(np.int64).reshape(-1) & 0xFFFFFFFF
+        assert int(h.sum()) == mw * mh, f"{what}: the histogram counts {int(h.sum())} pixels, the merged rectangle has {mw * mh}"
+        import exposure_truth as et
+        r["ambiguous"], r["other side"] = et.check_histogram_of_output(h, got)
+    return r
+
+
 # ------------------------------------------------------------------------------------------------------------------ the polyphase form
 def poly_coefficients():
     """k_blur_up_poly's six coefficients E(-3 .. 2), recomputed: float64 sums of the nine decimal weights, rounded once to fp32"""
@@ -547,6 +645,95 @@ def canonical_taps(i0, i1, f):
     return i0, np.where(one, i0, i1), np.where(one, 0.0, f)
 
 
+# ------------------------------------------------------------------------------------------------------------------ the tiled schedule
+MIPS = 5                             # PBR_BLOOM_MIPS: levels 0 .. 4
+
+
+def _cdiv(a, b):
+    """C's integer division: towards zero"""
+    return -((-a) // b) if a < 0 else a // b
+
+
+def up_pass_rects(merge_rect, ew, eh):
+    """csrc/bloom.hip up_pass_rects, restated with C's truncating division: {level: (x, y, w, h)} for levels 1 .. 4, the rectangles
+    the up-pass of a tiled frame is run on (levels 1 .. 3 have an up-pass; level 4's entry is computed and not used)"""
+    x0, y0, x1, y1 = merge_rect[0], merge_rect[1], merge_rect[0] + merge_rect[2], merge_rect[1] + merge_rect[3]
+    need = {}
+    for l in range(1, MIPS):
+        lw, lh = ew >> l, eh >> l
+        x0, y0, x1, y1 = _cdiv(x0 - 4, 2) - 2, _cdiv(y0 - 4, 2) - 2, _cdiv(x1 + 4 + 1, 2) + 2, _cdiv(y1 + 4 + 1, 2) + 2
+        x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, lw), min(y1, lh)
+        need[l] = (x0, y0, x1 - x0, y1 - y0)
+    return need
+
+
+def _reads(mode, lo, hi, in_size):
+    """[first, last + 1) of the input texels that the outputs lo .. hi - 1 of a nine-tap pass read along one axis: positions
+    lo - 4 .. hi + 3 (any integer: tap1d clamps the texel, as the sampler does), a tap of weight 0 or a repeated index left out"""
+    i0, i1, _ = canonical_taps(*tap1d(mode, np.arange(lo - 4, hi + 4), in_size))
+    return int(min(i0.min(), i1.min())), int(max(i0.max(), i1.max())) + 1
+
+
+def axis_dependency(lo, hi, size):
+    """up_pass_dependency along one axis: merged texels lo .. hi - 1 of a level 0 of `size` texels -> ({level: range of the
+    up-pass output read}, {level: range of the down-pass result read}), ranges [first, last + 1)"""
+    up, down = {}, {}
+    up[1] = _reads(M_UP, lo, hi, size >> 1)                        # level 0's H + V reads level 1's up-pass result
+    for l in (1, 2, 3):                                            # up-level l: nine same-size taps on A l, nine 2x-up taps on the level below
+        down[l] = _reads(M_SAME, *up[l], size >> l)
+        below = _reads(M_UP, *up[l], size >> (l + 1))
+        if l < 3:
+            up[l + 1] = below
+        else:
+            down[4] = below                                        # level 4 has no up-pass: its down-pass result is read
+    for l in (3, 2, 1):                                            # the down-pass of level l + 1 reads A l
+        r = _reads(M_DOWN, *down[l + 1], size >> l)
+        down[l] = (min(down[l][0], r[0]), max(down[l][1], r[1]))
+    return up, down
+
+
+def up_pass_dependency(merge_rect, ew, eh):
+    """The exact rectangles, from tap1d's integer taps with clamping: ({level 1 .. 3: (x, y, w, h) of the up-pass output that the
+    merged rectangle reads, directly or through the levels above}, {level 1 .. 4: the down-pass result read, by the up-pass and by
+    the down-pass of the levels below}).  H and V are separable, so a rectangle is the product of the two axes' ranges."""
+    ux, dx = axis_dependency(merge_rect[0], merge_rect[0] + merge_rect[2], ew)
+    uy, dy = axis_dependency(merge_rect[1], merge_rect[1] + merge_rect[3], eh)
+    box = lambda a, b: (a[0], b[0], a[1] - a[0], b[1] - b[0])   # noqa: E731
+    return {l: box(ux[l], uy[l]) for l in ux}, {l: box(dx[l], dy[l]) for l in dx}
+
+
+PREFILTER_READS = (-3, 2)            # half-res texel x reads the full-res pixels 2x - 3 .. 2x + 2 (five taps of 2 x 2 quads)
+
+
+def tile_grid(rect, tw, th):
+    """csrc/bloom.hip tile_grid: the tw x th tiles of a level that intersect rect -> (first tile (tx0, ty0), number of tiles)"""
+    x, y, w, h = rect
+    tx0, ty0 = x // tw, y // th
+    return (tx0, ty0), (-(-(x + w) // tw) - tx0) * (-(-(y + h) // th) - ty0)
+
+
+def up_kernel(rect, shader_order=False):
+    """launch_hv's choice for a 2x-up level run on rect = (x, y, w, h) (a whole level: (0, 0, w, h)): the launch-log label, the
+    first tile and the number of tiles.  128 x 32 tiles >= 400 and the shader-order switch off: k_blur_up_poly; else 64 x 32 tiles
+    >= 900: k_blur_hv/32; else k_blur_hv/16 (64 x 16 tiles)."""
+    first, n = tile_grid(rect, 128, 32)
+    if n >= 400 and not shader_order:
+        return "k_blur_up_poly", first, n
+    first, n = tile_grid(rect, 64, 32)
+    if n >= 900:
+        return "k_blur_hv/32", first, n
+    return ("k_blur_hv/16", *tile_grid(rect, 64, 16))
+
+
+def tiled_kernels(merge_rect, ew, eh, shader_order=False, shrink=True):
+    """[(level, label, first tile, tiles)] of the four 2x-up launches of pbr_bloom_tiled, levels 3, 2, 1, 0 in launch order; shrink
+    False: the up-pass on whole levels (the knobs build's PBR_BLOOM_SHRINK=0)"""
+    need = up_pass_rects(merge_rect, ew, eh)
+    rects = {l: need[l] if shrink else (0, 0, ew >> l, eh >> l) for l in (3, 2, 1)}
+    rects[0] = tuple(merge_rect)
+    return [(l, *up_kernel(rects[l], shader_order)) for l in (3, 2, 1, 0)]
+
+
 # ------------------------------------------------------------------------------------------------------------------ case sets
 def _synth():
     from direct12pbrrenderer_amd import synth
@@ -589,3 +776,59 @@ UP_SHAPES = [(32, 16), (48, 16), (5, 20), (200, 152)]
 def kinds_for(shape_index):
     """every shape sees noise; the first three also the smooth, black, subnormal and bright planes"""
     return KINDS if shape_index < 3 else ("noise",)
+
+
+class Tiled:
+    """one pbr_bloom_tiled call: the extended tile, the HDR buffer's rectangle and pitch, the merged rectangle, with or without the
+    histogram, the kind of its two input planes"""
+
+    def __init__(self, ew, eh, hdr_rect, hdr_pitch, merge_rect, kind, hist=True, shader_order=False):
+        self.ew, self.eh, self.hdr_rect, self.hdr_pitch, self.merge_rect = ew, eh, tuple(hdr_rect), hdr_pitch, tuple(merge_rect)
+        self.kind, self.hist, self.shader_order = kind, hist, shader_order
+        assert ew % 16 == 0 and eh % 16 == 0 and hdr_pitch >= hdr_rect[2]
+
+    @property
+    def id(self):
+        return f"{self.ew}x{self.eh}-{'_'.join(str(v) for v in self.merge_rect)}-{self.kind}" + ("-shader_order" if self.shader_order else "") + ("" if self.hist else "-nohist")
+
+    def inputs(self):
+        """(level 1 of E, the HDR texels of hdr_rect): non-negative planes with constant alpha, as chain requires, scaled by powers
+        of two so that the merged luminance spreads over the histogram's bins instead of sitting in its last one (the planes reach
+        8, with impulses 400, and the range ends at 4): level 1 by 2^-6 — the pyramid then adds 0.06 .. 0.5 —, the HDR rows by
+        2^-1 .. 2^-10 in ten bands, so the rectangle has rows that the HDR texel dominates and rows that the pyramid does"""
+        level1, hdr = plane(self.kind, self.ew >> 1, self.eh >> 1, seed=21), plane(self.kind, self.hdr_rect[2], self.hdr_rect[3], seed=22)
+        rows = hdr.shape[0]
+        level1[..., :3] = (level1[..., :3].astype(np.float32) * F32(2.0 ** -6)).astype(np.float16)
+        hdr[..., :3] = (hdr[..., :3].astype(np.float32) * np.exp2(-(1.0 + np.arange(rows) * 10 // rows)).astype(F32)[:, None, None]).astype(np.float16)
+        return level1, hdr
+
+    def truth(self):
+        return tiled_chain(*self.inputs(), self.hdr_rect, self.merge_rect)
+
+
+# E 128 .. 400 on a side; merge rectangles at even origins that are multiples of no tile size (16, 32, 64, 128) unless they touch
+# E's corner; hdr_rect larger than merge_rect and hdr_pitch larger than its width (odd ones too).  In order: a plain interior; the
+# bottom-right corner of E; 8 x 8; no histogram; the top-left corner; a tall E and an odd-sized rectangle; a wide rectangle one
+# texel inside hdr_rect's left edge; a level 4 of odd size (16 * 23 = 368 -> 23) and a narrow rectangle
+TILED_SMALL = [
+    Tiled(256, 128, (20, 10, 200, 100), 203, (34, 18, 150, 70), "noise"),
+    Tiled(400, 304, (0, 0, 400, 304), 402, (2, 6, 398, 298), "smooth"),
+    Tiled(128, 128, (50, 60, 30, 40), 37, (66, 70, 8, 8), "noise"),
+    Tiled(320, 176, (6, 2, 300, 170), 301, (38, 22, 222, 100), "smooth", hist=False),
+    Tiled(400, 128, (0, 0, 260, 90), 264, (0, 0, 130, 74), "noise"),
+    Tiled(144, 400, (10, 100, 120, 250), 128, (42, 134, 71, 183), "smooth"),
+    Tiled(272, 208, (16, 16, 240, 176), 250, (18, 50, 236, 100), "noise"),
+    Tiled(368, 384, (128, 64, 130, 258), 131, (130, 66, 126, 254), "smooth"),
+]
+# the benchmark's rank shapes (the strong-scaling tile of 7680 x 4320 on 2 x 4, the weak-scaling rank in the bottom row, a wide low
+# tile), as halo mode calls them: hdr_rect = the interior + 4 shaded pixels.  The kernels tiled_kernels gives them:
+#   2432 x 2672: level 1 k_blur_hv/16 on the rectangle and k_blur_up_poly on the whole level; level 0 poly, first tile (2, 8)
+#   3232 x 3312: level 1 poly, first tile (0, 3); level 0 poly, 2112 tiles, first tile (2, 8); under the shader-order switch
+#                level 1 k_blur_hv/32 (23 x 49 tiles) and level 0 k_blur_hv/32
+#   2816 x 896:  level 1 k_blur_hv/16, first tile (1, 3); level 0 poly, 441 tiles, first tile (1, 3)
+TILED_BIG = [
+    Tiled(2432, 2672, (252, 252, 1928, 2168), 1936, (256, 256, 1920, 2160), "noise"),
+    Tiled(3232, 3312, (252, 252, 2728, 3060), 2730, (256, 256, 2720, 3056), "smooth"),
+    Tiled(2816, 896, (132, 108, 2568, 648), 2570, (136, 112, 2560, 640), "noise"),
+    Tiled(3232, 3312, (252, 252, 2728, 3060), 2730, (256, 256, 2720, 3056), "smooth", shader_order=True),
+]

@@ -122,6 +122,40 @@ def check_histogram(got_hist, image, min_log=MIN_LOG, log_range=LOG_RANGE, times
     assert bad.size == 0, f"bins {bad[:8].tolist()}: got {got[bad[:8]].tolist()}, want {want[bad[:8]].tolist()} ({bad.size} bins differ)"
 
 
+def bin_choices(image, min_log=MIN_LOG, log_range=LOG_RANGE):
+    """(lowest, highest) bin per pixel in which a histogram inside the derived band may count it: equal wherever the truth decides,
+    the two bins on either side of the edge for a pixel bin_truth calls ambiguous (0 and 1 for one at the dark threshold)"""
+    bins, amb, _ = image_bins(image, min_log, log_range)
+    r, g, b = (np.asarray(image[..., c]).astype(np.float64) for c in range(3))
+    with np.errstate(all="ignore"):
+        lum = 0.2126 * r + 0.7152 * g + 0.0722 * b
+        k = np.clip(np.rint((np.log2(np.where(lum < EPSILON, 1.0, lum)) - min_log) / log_range * 254.0 + 1.0), 2.0, 255.0)
+    k = np.where(np.isfinite(k), k, 2.0).astype(np.int64)
+    edge = amb & ((bins == k) | (bins == k - 1))
+    dark = amb & ~edge                                               # at the dark threshold: below it bin 0, above it bin 1
+    assert (bins[dark] <= 1).all()
+    return np.where(edge, k - 1, np.where(dark, 0, bins)), np.where(edge, k, np.where(dark, 1, bins))
+
+
+def check_histogram_of_output(got_hist, image, min_log=MIN_LOG, log_range=LOG_RANGE):
+    """got_hist against the float64 bins of an image nobody settled (a kernel's output): every pixel the truth decides is counted in
+    its bin, every ambiguous one in one of the two bins at its edge — decided exactly, bin by bin from 0 up: x pixels of those
+    between b and b + 1 are counted in b + 1, and 0 <= x <= their number must hold at every b.  An image without ambiguous pixels
+    must give the float64 counts exactly.  Returns (ambiguous pixels, pixels counted on the other side of their edge than float64)."""
+    lo, hi = bin_choices(image, min_log, log_range)
+    fixed = hist_of(lo[lo == hi]).astype(np.int64)
+    flex = hist_of(lo[lo != hi]).astype(np.int64)
+    assert ((hi - lo) >= 0).all() and ((hi - lo) <= 1).all() and flex[255] == 0
+    got = np.asarray(got_hist).astype(np.int64).reshape(-1) & 0xFFFFFFFF
+    want = hist_of(image_bins(image, min_log, log_range)[0]).astype(np.int64)
+    x = 0
+    for b in range(256):
+        x = fixed[b] + flex[b] + x - got[b]                          # of the pixels between b and b + 1, those counted in b + 1
+        assert 0 <= x <= flex[b], (f"bin {b}: got {got[b]}, the truth decides {fixed[b]} and leaves {flex[b]} to bins {b} | {b + 1}; "
+                                   f"float64 counts {want[max(b - 1, 0):b + 2].tolist()}, got {got[max(b - 1, 0):b + 2].tolist()}")
+    return int(flex.sum()), int(np.abs(got - want).sum()) // 2
+
+
 # ---------------------------------------------------------------------------------------------------------------- tone-map
 ACES = (2.51, 0.03, 2.43, 0.59, 0.14)   # hdr_tone_mapping.hlsl:27-36
 

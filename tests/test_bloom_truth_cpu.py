@@ -1,6 +1,7 @@
 """The CPU oracle's bloom under the float64 truth of tests/bloom_truth.py, the truth under exact rational arithmetic, the premise of
-the fused kernels' integer taps at every size they are launched for, the polyphase kernel's algebra, and the proof that the
-assertions are not slack: injected defects are rejected.  No GPU.  `-s` prints the measured figures."""
+the fused kernels' integer taps at every size they are launched for, the polyphase kernel's algebra, what the tiled pass rests on
+(the up-pass rectangles' margins, the apron, a rank's float64 values behind it) and the proof that the assertions are not slack:
+injected defects, wrong tiled passes among them, are rejected.  No GPU.  `-s` prints the measured figures."""
 from fractions import Fraction
 
 import numpy as np
@@ -372,3 +373,204 @@ def test_conditions_hold_on_every_case_set(chain_intervals):
         for kind in CHAIN_KINDS:
             _, lo, hi = chain_intervals(w, h, kind)
             print(f"chain {w}x{h} {kind}:", bt.chain_conditions(lo, hi, f"chain {w}x{h} {kind}"))
+
+
+# ------------------------------------------------------------------------------------------------------ the tiled pass: what the tiling rests on
+def _contains(outer, inner):
+    return outer[0] <= inner[0] and outer[1] <= inner[1] and inner[0] + inner[2] <= outer[0] + outer[2] and inner[1] + inner[3] <= outer[1] + outer[3]
+
+
+def _intervals(size, spanning):
+    """[first, last + 1) along one axis of `size` texels: every residue mod 32 of the origin with every residue of the length, short
+    ones at the low end (origin 0: touching it) or spanning the axis but for the two residues"""
+    return [(a, size - n + 1) if spanning else (a, a + n) for a in range(32) for n in range(1, 33)]
+
+
+def test_up_pass_rectangles_contain_what_the_merged_rectangle_reads():
+    """up_pass_rects (the margins of csrc/bloom.hip, restated) against up_pass_dependency (tap1d's integer taps propagated through
+    level 0's H + V and the three up-levels): at every level the rule's rectangle contains the exact one.  The rule and the taps are
+    the same on both axes, so an interval is tried on x with its mirror image (the high end, touching it) on y."""
+    slack = {l: [99, 0] for l in (1, 2, 3, 4)}
+    cases = 0
+    for e, spanning in ((128, False), (8192, False), (400, True), (3232, True)):
+        for a, b in _intervals(e, spanning):
+            for rect in ((a, e - b, b - a, b - a),):
+                need = bt.up_pass_rects(rect, e, e)
+                up, down = bt.up_pass_dependency(rect, e, e)
+                cases += 1
+                for l, dep in ((1, up[1]), (2, up[2]), (3, up[3]), (4, down[4])):
+                    assert _contains(need[l], dep), f"E {e}, merge {rect}, level {l}: the up-pass runs on {need[l]}, the merged rectangle reads {dep}"
+                    size = e >> l
+                    for lo_side, (n0, d0) in ((True, (need[l][0], dep[0])), (True, (need[l][1], dep[1])),
+                                              (False, (need[l][0] + need[l][2], dep[0] + dep[2])), (False, (need[l][1] + need[l][3], dep[1] + dep[3]))):
+                        if (n0 > 0) if lo_side else (n0 < size):     # a side clipped at the level's edge has no margin to measure
+                            sp = d0 - n0 if lo_side else n0 - d0
+                            slack[l] = [min(slack[l][0], sp), max(slack[l][1], sp)]
+    print(f"{cases} rectangles; texels to spare per side, smallest .. largest: " + ", ".join(f"level {l}: {v[0]} .. {v[1]}" for l, v in slack.items()))
+
+
+def _reach(lo, hi, size=16384):
+    """how many level-0 pixels below lo and above hi - 1 the merged texels lo .. hi - 1 depend on, far from the frame's edges:
+    (through level 1 alone, with the prefilter's reads, what the interior's own level-1 texels need of the prefilter)"""
+    _, down = bt.axis_dependency(lo, hi, size)
+    l1 = (lo - 2 * down[1][0], 2 * down[1][1] - hi)
+    pf = (lo - (2 * down[1][0] + bt.PREFILTER_READS[0]), 2 * (down[1][1] - 1) + bt.PREFILTER_READS[1] + 1 - hi)
+    own = (lo - (2 * (lo // 2) + bt.PREFILTER_READS[0]), 2 * ((hi - 1) // 2) + bt.PREFILTER_READS[1] + 1 - hi)
+    return l1, pf, own
+
+
+def test_the_apron_covers_what_an_interior_pixel_depends_on():
+    """DEFAULT_APRON against the pyramid's exact support: the furthest level-0 pixel that any pixel of an interior lo .. hi - 1
+    depends on, through tap1d's taps down to level 4 and back and the prefilter's reads, for every lo and hi mod 32 (tile layouts
+    use multiples of 16).  And HALO_SHADE_APRON: the shaded pixels beyond the interior that its own level-1 texels need."""
+    from direct12pbrrenderer_amd.pipeline import DEFAULT_APRON, HALO_SHADE_APRON
+    # the prefilter's reads, from the sampler: position p + off, off = -1 .. 1, is the quad (2 (p + off) - 1, 2 (p + off))
+    w = 4096
+    p = np.arange(8, w // 2 - 8)
+    taps = [bt.sample_coord(p.astype(F32) * (F32(1.0) / F32(w // 2)) + F32(off) * (F32(1.0) / F32(w // 2)), w) for off in (-1, 0, 1)]
+    assert (min(int((t[0] - 2 * p).min()) for t in taps), max(int((t[1] - 2 * p).max()) for t in taps)) == bt.PREFILTER_READS
+    worst = {"level 1": 0, "prefilter": 0, "own": 0, "level 1, multiples of 16": 0, "prefilter, multiples of 16": 0}
+    for r in range(32):
+        for s in range(32):
+            l1, pf, own = _reach(4096 + r, 8192 + s)
+            worst["level 1"], worst["prefilter"] = max(worst["level 1"], *l1), max(worst["prefilter"], *pf)
+            if r % 2 == 0 and s % 2 == 0:                            # a level-1 texel is a whole 2 x 2 quad of the interior
+                worst["own"] = max(worst["own"], *own)
+            if r % 16 == 0 and s % 16 == 0:
+                worst["level 1, multiples of 16"] = max(worst["level 1, multiples of 16"], *l1)
+                worst["prefilter, multiples of 16"] = max(worst["prefilter, multiples of 16"], *pf)
+    print("furthest level-0 pixel an interior pixel depends on:", worst)
+    assert worst["prefilter"] <= DEFAULT_APRON and worst["level 1"] <= DEFAULT_APRON
+    assert worst["own"] <= HALO_SHADE_APRON
+    assert (worst["level 1, multiples of 16"], worst["prefilter, multiples of 16"]) == BLOOM_SUPPORT
+
+
+BLOOM_SUPPORT = (192, 195)           # what pipeline.py's comment on DEFAULT_APRON states: level-1 texels as pixels, with the prefilter's reads
+
+
+@pytest.mark.parametrize("w,h,world,layout", [(1024, 640, 4, (2, 2)), (1536, 320, 3, (3, 1))], ids=["2x2", "3x1"])
+def test_a_rank_behind_its_apron_computes_the_frames_own_float64_values(w, h, world, layout):
+    """Each rank's extended tile E (tile_for_rank, the default apron) holds the window of the frame's level 1; the float64 truth of
+    level 0's H + V on E equals that of the whole frame on the rank's interior EXACTLY: every level of E sits on the frame's texel
+    grid, so these are the same float64 operations on the same values.  Smaller aprons are tried for the figure alone."""
+    from direct12pbrrenderer_amd.pipeline import DEFAULT_APRON, tile_for_rank
+    level1 = bt.rn_half(bt.prefilter(bt.plane("noise", w, h, seed=30))[0])
+    whole = bt.level0_truth(level1)
+
+    def equal(apron):
+        for rank in range(world):
+            t = tile_for_rank(rank, world, w // layout[0], h // layout[1], apron, layout)
+            mine = bt.level0_truth(level1[t.ey0 // 2:t.ey1 // 2, t.ex0 // 2:t.ex1 // 2])
+            if not np.array_equal(mine[t.iy:t.iy + t.h, t.ix:t.ix + t.w], whole[t.y0:t.y0 + t.h, t.x0:t.x0 + t.w]):
+                return False
+        return True
+    assert equal(DEFAULT_APRON)
+    smallest = DEFAULT_APRON
+    while smallest > 16 and equal(smallest - 16):
+        smallest -= 16
+    print(f"{w}x{h} cut {layout[0]}x{layout[1]}: the interiors' float64 values are the frame's down to an apron of {smallest}")
+
+
+# ------------------------------------------------------------------------------------------------------ the tiled pass: the check can fail
+@pytest.fixture(scope="module")
+def tiled_truths():
+    cache = {}
+
+    def get(i):
+        if i not in cache:
+            cache[i] = bt.TILED_SMALL[i].truth()
+        return cache[i]
+    return get
+
+
+def tiled_model(case, defect=None):
+    """pbr_bloom_tiled in numpy, every stage its rounded truth: (the HDR buffer before, after, the histogram).  defect: one of
+    TILED_DEFECTS, the wrong pass of that name."""
+    (hx, hy, hw, hh), (mx, my, mw, mh) = case.hdr_rect, case.merge_rect
+    level1, hdr = case.inputs()
+    before = np.full((hh, case.hdr_pitch, 4), 0x7E5A, dtype=np.uint16)
+    before[:, :hw] = hdr.view(np.uint16)
+    up, _ = bt.up_pass_dependency(case.merge_rect, case.ew, case.eh)
+
+    def poisoned_outside(rect):
+        def hook(level, res):
+            if level != 2:
+                return res
+            out = np.full_like(res, np.float16(-65504.0))
+            x, y, w_, h_ = rect
+            out[y:y + h_, x:x + w_] = res[y:y + h_, x:x + w_]
+            return out
+        return hook
+    hook = None
+    if defect == "level 2 computed on exactly what is read":                 # no defect: the dependency is sufficient
+        hook = poisoned_outside(up[2])
+    elif defect == "level 2's rectangle one texel short":
+        x, y, w_, h_ = up[2]
+        assert x > 0
+        hook = poisoned_outside((x + 1, y, w_ - 1, h_))
+    elif defect == "level 0 reads chain A":                                   # where the given level 1 lives, not the up-pass result
+        hook = lambda level, res: level1 if level == 1 else res   # noqa: E731
+    ops = bt.Ops(0)
+    add = bt.window(bt.run_from_level1(level1, ops, case.ew, case.eh, hook), case.merge_rect)
+    rows, cols = slice(my - hy, my - hy + mh), slice(mx - hx, mx - hx + mw)
+    after = before.copy()
+    if defect == "merge shifted by one texel":                               # buf_origin dropped on one axis
+        cols_w = slice(cols.start - 1, cols.stop - 1)
+        after[rows, cols_w] = ops.merge(before[rows, cols_w].view(np.float16), add).view(np.uint16)
+    else:
+        after[rows, cols] = ops.merge(before[rows, cols].view(np.float16), add).view(np.uint16)
+    if defect == "first tile row skipped":                                    # ty0 off by one: 16-row tiles
+        first = slice(rows.start, rows.start + (my // 16 + 1) * 16 - my)
+        after[first, cols] = before[first, cols]
+    counted = after[:, :hw] if defect == "histogram of hdr_rect" else after[rows, cols]
+    hist = bt.output_histogram(np.ascontiguousarray(counted).view(np.float16)) if case.hist else None
+    if defect == "one pixel in the next bin but one":
+        b = int(np.argmax(hist))
+        hist[b] -= 1
+        hist[b + 2] += 1
+    return before, after, hist
+
+
+TILED_DEFECTS = {"merge shifted by one texel": "outside the chain interval", "histogram of hdr_rect": "the histogram counts",
+                 "one pixel in the next bin but one": "the truth decides",
+                 "level 2's rectangle one texel short": "outside the chain interval", "level 0 reads chain A": "outside the chain interval",
+                 "first tile row skipped": "outside the chain interval"}
+
+
+@pytest.mark.parametrize("i", range(len(bt.TILED_SMALL)), ids=[c.id for c in bt.TILED_SMALL])
+def test_tiled_truth_conditions_and_the_model_passes(tiled_truths, i):
+    """chain_conditions on every TILED_SMALL truth (check_tiled asserts them), and the rounded truth itself passes — also when
+    level 2 holds poison outside the exact rectangle up_pass_dependency gives: that rectangle is sufficient"""
+    case = bt.TILED_SMALL[i]
+    lo, hi = tiled_truths(i)
+    r = bt.check_tiled(case, *tiled_model(case), lo, hi, case.id)
+    before, after, hist = tiled_model(case, "level 2 computed on exactly what is read")
+    assert np.array_equal(after, tiled_model(case)[1])
+    print(f"{case.id}: interval at most {r['width']} wide, {r['degenerate']:.2%} degenerate")
+
+
+@pytest.mark.parametrize("defect", list(TILED_DEFECTS))
+def test_tiled_defects_are_rejected(tiled_truths, defect):
+    case = bt.TILED_SMALL[0]
+    with pytest.raises(AssertionError, match=TILED_DEFECTS[defect]):
+        bt.check_tiled(case, *tiled_model(case, defect), *tiled_truths(0), defect)
+
+
+def test_a_write_outside_the_merged_rectangle_is_rejected(tiled_truths):
+    case = bt.TILED_SMALL[0]
+    before, after, hist = tiled_model(case)
+    after[0, case.hdr_pitch - 1, 2] ^= 1                                      # the pitch padding
+    with pytest.raises(AssertionError, match="outside the merged rectangle changed"):
+        bt.check_tiled(case, before, after, hist, *tiled_truths(0))
+
+
+def test_up_kernel_restates_the_table_of_the_benchmarks_rank_shapes():
+    """the kernels tiled_kernels gives the TILED_BIG cases, spelled out: a change of launch_hv's thresholds or of the margins shows here
+    and, on the GPU, against the launch log"""
+    rows = {c.id: (bt.tiled_kernels(c.merge_rect, c.ew, c.eh, c.shader_order), bt.tiled_kernels(c.merge_rect, c.ew, c.eh, c.shader_order, shrink=False)) for c in bt.TILED_BIG}
+    a, b, c, d = (rows[k.id] for k in bt.TILED_BIG)
+    assert a[0][2:] == [(1, "k_blur_hv/16", (1, 7), 1173), (0, "k_blur_up_poly", (2, 8), 1020)] and a[1][2] == (1, "k_blur_up_poly", (0, 0), 420)
+    assert b[0][2:] == [(1, "k_blur_up_poly", (0, 3), 588), (0, "k_blur_up_poly", (2, 8), 2112)] and b[1][2] == (1, "k_blur_up_poly", (0, 0), 676)
+    assert c[0][2:] == [(1, "k_blur_hv/16", (1, 3), 441), (0, "k_blur_up_poly", (1, 3), 441)] and c[1][2][1] == "k_blur_hv/16"
+    assert d[0][2:] == [(1, "k_blur_hv/32", (1, 3), 1127), (0, "k_blur_hv/32", (4, 8), 4128)] and d[1][2][1] == "k_blur_hv/32"
+    assert all(k[1] == "k_blur_hv/16" for r in rows.values() for k in r[0][:2] + r[1][:2])   # levels 3 and 2 are small everywhere

@@ -184,3 +184,36 @@ def test_end_to_end_constant_frames(orc):
         lo, hi = et.end_to_end_range(b)
         assert lo <= avg <= hi, (b, avg, lo, hi)
         et.check_ldr(orc.tonemap(frame, avg), frame, avg)
+
+
+# ------------------------------------------------------------------------------------------------------ a kernel's output, not settled
+def test_histogram_of_an_output_is_exact_where_the_truth_decides():
+    """check_histogram_of_output on every positive finite grey half: the float64 counts pass; an ambiguous pixel counted on the other
+    side of its edge passes and is reported; a pixel the truth decides counted in the next bin is rejected, and so is an ambiguous
+    pixel counted anywhere but at its edge"""
+    p = et._halves(np.arange(1, 0x7C00))
+    p = p[:p.size // 256 * 256]
+    img = et._image(p, p, p)
+    bins, amb, _ = et.image_bins(img)
+    lo, hi = et.bin_choices(img)
+    assert amb.any() and ((lo != hi) == amb).all() and ((bins == lo) | (bins == hi)).all()
+    want = et.hist_of(bins).astype(np.int64)
+    assert et.check_histogram_of_output(want, img) == (int(amb.sum()), 0)
+    b = int(bins[amb][0])
+    other = int((lo + hi)[amb][0]) - b
+    moved = want.copy()
+    moved[b] -= 1
+    moved[other] += 1
+    assert et.check_histogram_of_output(moved, img) == (int(amb.sum()), 1)
+    far = want.copy()
+    far[b] -= 1
+    far[b + 3] += 1
+    with pytest.raises(AssertionError, match="the truth decides"):
+        et.check_histogram_of_output(far, img)
+    flex = et.hist_of(lo[amb])                                       # an edge no ambiguous pixel sits at: bins d | d + 1 both populated, decided
+    d = next(k for k in range(2, 254) if flex[k] == 0 and want[k] > 0)
+    wrong = want.copy()
+    wrong[d] -= 1
+    wrong[d + 1] += 1
+    with pytest.raises(AssertionError, match="the truth decides"):
+        et.check_histogram_of_output(wrong, img)

@@ -117,7 +117,7 @@ def tail_rects(w, h):
     return [(0, 0, w, h), (w - 1, h - 1, 1, 1), (37, 21, w - 37 - 29, h - 21 - 19)]
 
 
-# The API does not say which kernel ran, so each size relies on the rules of bloom_pass / launch_hv (csrc/bloom.hip):
+# Each size is chosen by the rules of bloom_pass / launch_hv (csrc/bloom.hip), and the launch log says which kernel ran:
 # * an odd width or height at level 0 is no exact half: the staged tail k_blur_v_merge<true> (302 x 178 is even both ways and would
 #   take k_blur_hv; 303 x 179 is used);
 # * an exact level 0 takes k_blur_up_poly when 128 x 32 tiles number >= 400 and the shader-order switch is off: 2560 x 640 is 20 x 20;
@@ -126,6 +126,7 @@ def tail_rects(w, h):
 #   used for the 64 x 32 instance.
 TAILS = {"k_blur_v_merge": (303, 179, False), "k_blur_hv 64x16": (256, 256, False), "k_blur_up_poly": (2560, 640, False),
          "k_blur_hv 64x32": (1920, 960, True)}
+TAIL_LABELS = {"k_blur_v_merge": "k_blur_v_merge", "k_blur_hv 64x16": "k_blur_hv/16", "k_blur_up_poly": "k_blur_up_poly", "k_blur_hv 64x32": "k_blur_hv/32"}
 
 
 @pytest.mark.parametrize("tail", list(TAILS))
@@ -143,7 +144,8 @@ def test_bloom_tail_histograms(ctx, finite_grey, tail):
         for rect in tail_rects(w, h):
             x, y, rw, rh = rect
             hist = ctx.zeros((256,), torch.int32)
-            ctx.bloom_histogram(hdr, w, h, w, ca, cb, rect, hist, threshold=1e30)
+            ran = ctx.launches_of(lambda: ctx.bloom_histogram(hdr, w, h, w, ca, cb, rect, hist, threshold=1e30))
+            assert ran[-1] == TAIL_LABELS[tail], ran
             assert bool((hdr[..., :3] == orig[..., :3]).all()), f"{rect}: the HDR colour changed"
             want = et.hist_of(bins[y:y + rh, x:x + rw])
             assert np.array_equal(u32(hist), want), f"{rect}: bins {np.nonzero(u32(hist) != want)[0][:8].tolist()} differ from truth"
