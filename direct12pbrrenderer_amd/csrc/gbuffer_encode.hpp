@@ -1,11 +1,10 @@
 // gbuffer_encode.hpp — gbuffer.hlsl::ps_main's output encode (gbuffer.hlsl:144-146), shared by k_gbuffer_encode (raster.hip,
 // per-pixel material planes) and k_rs_raster (gbuffer_raster.hip, constant per-draw materials).  Both translation units are
 // built with -ffp-contract=off: the gamma / octahedral results feed UNORM8 rounding.
-// Included inside each user's anonymous namespace, after pbr_device.hpp and `using namespace pbr`.
+// Included inside each user's anonymous namespace, after pbr_device.hpp (sign_custom) and `using namespace pbr`.
 #pragma once
 
 __device__ __forceinline__ uint32_t unorm8(float x) { return (uint32_t)floorf(saturatef(x) * 255.0f + 0.5f); }
-__device__ __forceinline__ float sign_custom(float x) { return x < 0.0f ? -1.0f : 1.0f; }
 // decode_gamma (global.hlsli:73-77): pow(c, 2.2) the way the shader compiler lowers it, exp2(2.2 * log2(c)) on
 // the transcendental unit (v_log_f32 / v_exp_f32, 1 ULP each).  The result only feeds an 8-bit UNORM target:
 // relative error < 1e-6 moves a value across a rounding boundary on ~1e-4 of the texels (by one step).

@@ -118,6 +118,33 @@ __device__ __forceinline__ F4 sample_2d_h4(const pbr_half* img, int w, int h, in
     return bilerp(c00, c10, c01, c11, cx.f, cy.f);
 }
 
+// ViewSpaceDepth (deferred_shading.hlsl:74-77): Near Far / (Far - d (Far - Near)).  The denominator cancels (d -> 1:
+// Far - d (Far - Near) is ~Far / z_vs), so ONE rounding more or less in it moves z_vs by ~z_vs / Near ulps — enough to
+// push a pixel across a cluster-slice boundary and hand it another light list.  Evaluated operation by operation (no
+// fused multiply-add), with IEEE division, exactly as the oracle: the slice index is then a function of the depth texel.
+__device__ __forceinline__ float view_space_depth(float d, float near_z, float far_z) {
+#pragma clang fp contract(off)
+    const float num = near_z * far_z;
+    const float range = far_z - near_z;
+    const float prod = d * range;
+    const float den = far_z - prod;
+    return num / den;
+}
+
+__device__ __forceinline__ float sign_custom(float x) { return x < 0.0f ? -1.0f : 1.0f; }   // global.hlsli:85-88 (Q22)
+
+// global.hlsli:101-115
+__device__ __forceinline__ V3 decode_octahedron(float u, float v) {
+    V3 d = v3(u * 2.0f - 1.0f, v * 2.0f - 1.0f, 0.0f);
+    d.z = 1.0f - fabsf(d.x) - fabsf(d.y);
+    if (d.z < 0.0f) {
+        float nx = sign_custom(d.x) * (1.0f - fabsf(d.y));
+        float ny = sign_custom(d.y) * (1.0f - fabsf(d.x));
+        d.x = nx; d.y = ny;
+    }
+    return d;
+}
+
 // ---- cube addressing: env_map_gen.hlsl:20-44 and its D3D inverse -----------------------------
 __device__ __forceinline__ V3 cube_dir_raw(uint32_t face, float u, float v) {
     switch (face) {

@@ -98,6 +98,14 @@ inline bool views_disjoint(const pbr_view* v, uint32_t n, int n_out, F range) {
     return true;
 }
 inline uintptr_t addr(const void* p) { return (uintptr_t)p; }
+// The camera of g as the screen-space kernels take it: the 3x3 part of InvView (row-major) and the near plane's size,
+// 2 Near tan(Fov/2) high and Ratio times that wide (vs_main :94-95), in float with the host's libm.
+inline void camera_near_plane(const pbr_global* g, float inv_view[9], float& near_width, float& near_height) {
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) inv_view[r * 3 + c] = g->InvView[r * 4 + c];
+    near_height = 2.0f * g->Near * tanf(g->Fov / 2.0f);
+    near_width = near_height * g->Ratio;
+}
 // the view argument of a single-view kernel instantiation: empty; placed in a padding hole of the argument block, it moves no argument
 struct NoViews {};
 

@@ -221,10 +221,7 @@ __global__ __launch_bounds__(256) void k_skybox_bc6h(SkyParams p, SkyBc6h sky, c
 }
 
 void fill_sky_params(SkyParams& p, const pbr_global* g, const pbr_tile* tile, uint32_t size, uint32_t mips, uint32_t pitch, uint32_t hdr_pitch) {
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) p.InvView[r * 3 + c] = g->InvView[r * 4 + c];
-    p.near_height = 2.0f * g->Near * tanf(g->Fov / 2.0f);
-    p.near_width = p.near_height * g->Ratio;
+    camera_near_plane(g, p.InvView, p.near_width, p.near_height);
     p.Near = g->Near;
     p.full_w_f = (float)tile->full_w; p.full_h_f = (float)tile->full_h;
     p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h;

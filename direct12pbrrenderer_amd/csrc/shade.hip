@@ -50,40 +50,13 @@ struct ShadeParams {
     float* hdr_f32;        // F32OUT instantiations only (pbr_deferred_shade_f32): the colour BEFORE the fp16 store
 };
 
-// ViewSpaceDepth (deferred_shading.hlsl:74-77): Near Far / (Far - d (Far - Near)).  The denominator cancels (d -> 1:
-// Far - d (Far - Near) is ~Far / z_vs), so ONE rounding more or less in it moves z_vs by ~z_vs / Near ulps — enough to
-// push a pixel across a cluster-slice boundary and hand it another light list.  Evaluated operation by operation (no
-// fused multiply-add), with IEEE division, exactly as the oracle: the slice index is then a function of the depth texel.
-__device__ __forceinline__ float view_space_depth(float d, float near_z, float far_z) {
-#pragma clang fp contract(off)
-    const float range = far_z - near_z;
-    const float prod = d * range;
-    const float den = far_z - prod;
-    const float num = near_z * far_z;
-    return num / den;
-}
-
-// the same expression with v_rcp for the division (<= 2 ulp from the IEEE result): for consumers that are continuous in z_vs
+// ViewSpaceDepth (pbr_device.hpp: view_space_depth, the exact form) with v_rcp for the division (<= 2 ulp from the IEEE result): for consumers that are continuous in z_vs
 __device__ __forceinline__ float view_space_depth_quick(float d, float near_z, float far_z) {
 #pragma clang fp contract(off)
     const float range = far_z - near_z;
     const float prod = d * range;
     const float den = far_z - prod;
     return (near_z * far_z) * rcp(den);
-}
-
-__device__ __forceinline__ float sign_custom(float x) { return x < 0.0f ? -1.0f : 1.0f; }   // global.hlsli:85-88 (Q22)
-
-// global.hlsli:101-115
-__device__ __forceinline__ V3 decode_octahedron(float u, float v) {
-    V3 d = v3(u * 2.0f - 1.0f, v * 2.0f - 1.0f, 0.0f);
-    d.z = 1.0f - fabsf(d.x) - fabsf(d.y);
-    if (d.z < 0.0f) {
-        float nx = sign_custom(d.x) * (1.0f - fabsf(d.y));
-        float ny = sign_custom(d.y) * (1.0f - fabsf(d.x));
-        d.x = nx; d.y = ny;
-    }
-    return d;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -576,9 +549,75 @@ extern "C" int pbr_debug_shade_stamps_reset() {
 #define SHADE_NOW() 0ull
 #endif
 
+// ---- what the shade kernels' prologues share -----------------------------------------------------------------------------------------
+// The block's pixels, as the locals both kernels name: columns [bx0, min(bx0 + SHADE_BLOCK, x_end)), rows [y_begin, y_end) of the tile.
+// block -> rectangle -> (column block, row block); wave-uniform scalar arithmetic.  Two-zone schedule: the first nb_big block rows walk
+// rows_big rows each, the rest rows_small — the short blocks are dispatched last and fill the tail of the launch (a 4K frame is only ~3.2
+// waves of resident blocks).  A macro: as a function returning the four it reordered every shade kernel.
+#define SHADE_BLOCK_SPAN(rc)                                                                                                             \
+    uint32_t r = 0;                                                                                                                      \
+    while (r + 1 < rc.n && blockIdx.x >= rc.first[r + 1]) r++;                                                                           \
+    const uint32_t lb = blockIdx.x - rc.first[r];                                                                                        \
+    const uint32_t bx0 = rc.x0[r] + (lb % rc.cols[r]) * SHADE_BLOCK, x_end = rc.x0[r] + rc.w[r];                                         \
+    const uint32_t by = lb / rc.cols[r], nb_big = rc.nb_big[r], rows_big = rc.rows_big, rows_small = rc.rows_small;                      \
+    const uint32_t y_begin = rc.y0[r] + (by < nb_big ? by * rows_big : nb_big * rows_big + (by - nb_big) * rows_small);                  \
+    const uint32_t y_end = min(y_begin + (by < nb_big ? rows_big : rows_small), rc.y0[r] + rc.h[r])
+
+// The dynamic LDS of a block, as the locals both kernels name: 9 planes * LSTRIDE floats of light data (llds), then (staged lists)
+// max_clusters * 136 B of light lists (lists, 8-byte aligned); lds_base: the planes' LDS byte address, < 64 KiB: the whole light table
+// (<= 9 x 1025 floats) stays addressable in 16 bits
+#define SHADE_LDS_CARVE(LSTRIDE)                                                                          \
+    extern __shared__ float4 lds_raw[];                                                                   \
+    float* const llds = reinterpret_cast<float*>(lds_raw);                                                \
+    uint32_t* const lists = reinterpret_cast<uint32_t*>(llds + ((LIGHT_PLANES * LSTRIDE + 1) & ~1));      \
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_cf*)llds
+
+// The column term of global pixel column gx and the row term of global pixel row gy of a full_w x full_h frame (vs_main :91-95,
+// ClusterIndex clustered.hlsli:46-47; uv from the GLOBAL pixel): half the NDC coordinate (times the near plane's size: cvv) and the cluster
+// column / row — IEEE divide, floor, clamp.  Monotone in the pixel coordinate, so a rectangle's corners bound its cluster tiles.
+// k_shade_geometry_tables stores exactly these; the tabled kernel reads them back, the computed one evaluates them: bit-exact by construction.
+struct alignas(8) AxisTerm { float half_ndc; int cluster; };   // (also an entry of the geometry tables)
+__device__ __forceinline__ AxisTerm shade_column_term(uint32_t gx, uint32_t full_w) {
+    const float u = ((float)gx + 0.5f) / (float)full_w;
+    const float ndc_x = 2.0f * u - 1.0f;
+    return AxisTerm{ndc_x * 0.5f, clampi((int)floorf(u * (float)PBR_CLUSTER_X), 0, PBR_CLUSTER_X - 1)};
+}
+__device__ __forceinline__ AxisTerm shade_row_term(uint32_t gy, uint32_t full_h) {
+    const float v = ((float)gy + 0.5f) / (float)full_h;
+    const float ndc_y = 1.0f - 2.0f * v;
+    return AxisTerm{ndc_y * 0.5f, clampi((int)floorf((1.0f - v) * (float)PBR_CLUSTER_Y), 0, PBR_CLUSTER_Y - 1)};
+}
+// A row's s_row entry and a column's col_list from their terms: InvView's column 1 times cvv.y, and the row's / the column's part of the
+// index of the pixel's list (staged: dwords from `lists`, relative to the block's first tile) or cluster (global: clusters from p.clusters)
+template <bool STAGED_LISTS>
+__device__ __forceinline__ float4 shade_row_entry(const ShadeParams& p, AxisTerm row, int tile_y0, int tiles_x) {
+    const float cvv_y = row.half_ndc * p.near_height;
+    const uint32_t row_list = STAGED_LISTS ? (uint32_t)((row.cluster - tile_y0) * tiles_x * (PBR_CLUSTER_Z * LIST_STRIDE)) : (uint32_t)(row.cluster * (PBR_CLUSTER_X * PBR_CLUSTER_Z));
+    return make_float4(p.InvView[1] * cvv_y, p.InvView[4] * cvv_y, p.InvView[7] * cvv_y, __uint_as_float(row_list));
+}
+template <bool STAGED_LISTS>
+__device__ __forceinline__ uint32_t shade_col_list(int cluster, int tile_x0) {
+    return STAGED_LISTS ? (uint32_t)((cluster - tile_x0) * (PBR_CLUSTER_Z * LIST_STRIDE)) : (uint32_t)(cluster * PBR_CLUSTER_Z);
+}
+
+// The block's rows, once its tables are staged, over the locals both kernels name; ...: shade_pixel's template arguments.  The stamps are no-ops
+// in the product build, whose threads right of x_end leave the kernel at once; in the timing build k_deferred_shade's "tables staged" stamp
+// follows the thread's column term.  A macro: as a function, or reading the span's members at the uses, it cost the staged kernels two more
+// s_waitcnt in the row loop and the fp32 probe 8 bytes of scratch.
+#define SHADE_ROW_LOOP(...)                                                                                                         \
+    do {                                                                                                                            \
+        (void)t_start;                                                                                                              \
+        SHADE_ISTAMP(blockIdx.x, 0, t_start);                                                                                       \
+        SHADE_ISTAMP(blockIdx.x, 1, SHADE_NOW());                                                                                   \
+        SHADE_ISTAMP(blockIdx.x, 3, ((unsigned long long)(y_end - y_begin) << 48) | blockIdx.x);                                    \
+        if (px < x_end)                                                                                                             \
+            for (uint32_t py = y_begin; py < y_end; py++)                                                                           \
+                shade_pixel<__VA_ARGS__>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list); \
+        SHADE_ISTAMP_MAX(blockIdx.x, 2, SHADE_NOW());                                                                               \
+    } while (0)
+
 // grid: rc.first[rc.n] blocks of 256 threads, dispatched in index order (the hardware's dispatcher is the work queue: a software queue
 // of persistent blocks was built and measured in round 6 and lost to it at every size — EXPERIMENTS.md).
-// dynamic LDS: 9 planes * LSTRIDE floats of light data, then (STAGED_LISTS) max_clusters * 136 B of light lists.
 #ifndef SHADE_MIN_WAVES
 #define SHADE_MIN_WAVES 5   // 96 VGPRs; 2 dwords of scratch per lane are spilled OUTSIDE the light loop.  Best of 4..8 measured (tools/probe_shade.py)
 #endif
@@ -621,13 +660,10 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
     }
     const ShadeParams& p = MV ? q : p_;
     const int n_lights = MV ? n_views_lights : n_lights_;
-    extern __shared__ float4 lds_raw[];
     __shared__ uint32_t s_mip_off[16];
     const unsigned long long t_start = SHADE_NOW();
-    (void)t_start;
     if (threadIdx.x < 16) s_mip_off[threadIdx.x] = p_.env_mip_off[threadIdx.x];   // (p_: a per-lane index into the local copy would live in scratch)
-    float* llds = reinterpret_cast<float*>(lds_raw);
-    uint32_t* lists = reinterpret_cast<uint32_t*>(llds + ((LIGHT_PLANES * LSTRIDE + 1) & ~1));   // 8-byte aligned
+    SHADE_LDS_CARVE(LSTRIDE);
     int my_safe = 1, my_same = 1;
     const float att0 = n_lights > 0 ? p.lights[0].C0 : 1.0f, att1 = n_lights > 0 ? p.lights[0].C1 : 0.0f, att2 = n_lights > 0 ? p.lights[0].C2 : 0.0f;
     if (threadIdx.x == 0) {   // the null light: pads odd lists; black, so its pair lane contributes exactly 0
@@ -649,24 +685,13 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
         llds[7 * LSTRIDE + i] = l.C1;
         llds[8 * LSTRIDE + i] = l.C2;
     }
-    // block -> rectangle -> (column block, row block); wave-uniform scalar arithmetic
-    uint32_t r = 0;
-    while (r + 1 < rc.n && blockIdx.x >= rc.first[r + 1]) r++;
-    const uint32_t lb = blockIdx.x - rc.first[r];
-    const uint32_t bx0 = rc.x0[r] + (lb % rc.cols[r]) * SHADE_BLOCK, x_end = rc.x0[r] + rc.w[r];
-    // two-zone schedule: the first nb_big block rows walk rows_big rows each, the rest rows_small — the short
-    // blocks are dispatched last and fill the tail of the launch (a 4K frame is only ~3.2 waves of resident blocks)
-    const uint32_t by = lb / rc.cols[r], nb_big = rc.nb_big[r], rows_big = rc.rows_big, rows_small = rc.rows_small;
-    const uint32_t y_begin = rc.y0[r] + (by < nb_big ? by * rows_big : nb_big * rows_big + (by - nb_big) * rows_small);
-    const uint32_t y_end = min(y_begin + (by < nb_big ? rows_big : rows_small), rc.y0[r] + rc.h[r]);
+    SHADE_BLOCK_SPAN(rc);
     int tile_x0 = 0, tile_y0 = 0, tiles_x = 1;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_cf*)llds;   // < 64 KiB: the whole light table (<= 9 x 1025 floats) stays addressable in 16 bits
     if (STAGED_LISTS) {
-        // cluster (x,y) tiles the block's pixel rectangle can fall into — same arithmetic as the per-pixel
-        // ClusterIndex (floor(u*24), floor((1-v)*16)); monotone in the pixel coordinate, so the corners bound it
+        // cluster (x,y) tiles the block's pixel rectangle can fall into: the cluster column / row of its corners
         const uint32_t bx1 = min(bx0 + SHADE_BLOCK, x_end) - 1;
-        auto tx = [&](uint32_t x) { return clampi((int)floorf((((float)(p.x0 + x) + 0.5f) / (float)p.full_w) * (float)PBR_CLUSTER_X), 0, PBR_CLUSTER_X - 1); };
-        auto ty = [&](uint32_t y) { return clampi((int)floorf((1.0f - ((float)(p.y0 + y) + 0.5f) / (float)p.full_h) * (float)PBR_CLUSTER_Y), 0, PBR_CLUSTER_Y - 1); };
+        auto tx = [&](uint32_t x) { return shade_column_term(p.x0 + x, p.full_w).cluster; };
+        auto ty = [&](uint32_t y) { return shade_row_term(p.y0 + y, p.full_h).cluster; };
         tile_x0 = tx(bx0);
         const int tile_x1 = tx(bx1);
         const int ty_a = ty(y_begin), ty_b = ty(y_end - 1);
@@ -703,59 +728,26 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
             }
         }
     }
-    // per-row terms of the block's <= SHADE_ROWS rows (vs_main :91-95, ClusterIndex clustered.hlsli:47): InvView's column 1 times cvv.y,
-    // and the row's part of the index of the pixel's list (staged: dwords from `lists`) or cluster (global: clusters from p.clusters)
-    __shared__ float4 s_row[SHADE_ROWS];
-    if (threadIdx.x < (uint32_t)SHADE_ROWS) {
-        const float v = ((float)(p.y0 + y_begin + threadIdx.x) + 0.5f) / (float)p.full_h;
-        const float ndc_y = 1.0f - 2.0f * v;
-        const float cvv_y = ndc_y * 0.5f * p.near_height;
-        const int sy = clampi((int)floorf((1.0f - v) * (float)PBR_CLUSTER_Y), 0, PBR_CLUSTER_Y - 1);
-        const uint32_t row_list = STAGED_LISTS ? (uint32_t)((sy - tile_y0) * tiles_x * (PBR_CLUSTER_Z * LIST_STRIDE)) : (uint32_t)(sy * (PBR_CLUSTER_X * PBR_CLUSTER_Z));
-        s_row[threadIdx.x] = make_float4(p.InvView[1] * cvv_y, p.InvView[4] * cvv_y, p.InvView[7] * cvv_y, __uint_as_float(row_list));
-    }
+    __shared__ float4 s_row[SHADE_ROWS];   // the block's <= SHADE_ROWS rows
+    if (threadIdx.x < (uint32_t)SHADE_ROWS)
+        s_row[threadIdx.x] = shade_row_entry<STAGED_LISTS>(p, shade_row_term(p.y0 + y_begin + threadIdx.x, p.full_h), tile_y0, tiles_x);
     // bit 0: the attenuation floor cannot bind; bit 1: every staged light has the SAME attenuation polynomial (one radius for the
     // whole scene is common), so its three coefficients are per-kernel constants and a trip reads 13 LDS dwords instead of 19
     const int q_safe = (__syncthreads_and(my_safe) != 0 ? 1 : 0) | (__syncthreads_and(my_same) != 0 ? 2 : 0);
-    SHADE_ISTAMP(blockIdx.x, 0, t_start);
-    SHADE_ISTAMP(blockIdx.x, 1, SHADE_NOW());
-    SHADE_ISTAMP(blockIdx.x, 3, ((unsigned long long)(y_end - y_begin) << 48) | blockIdx.x);
     const uint32_t px = bx0 + threadIdx.x;
-    // the thread's column (vs_main :91-95, ClusterIndex clustered.hlsli:46; uv from the GLOBAL pixel): cvv.x and the column's part of the
-    // list / cluster index, the counterpart of s_row
-    const float u = ((float)(p.x0 + px) + 0.5f) / (float)p.full_w;
-    const float ndc_x = 2.0f * u - 1.0f;
-    const float cvv_x = ndc_x * 0.5f * p.near_width;
-    const int sx = clampi((int)floorf(u * (float)PBR_CLUSTER_X), 0, PBR_CLUSTER_X - 1);
-    const uint32_t col_list = STAGED_LISTS ? (uint32_t)((sx - tile_x0) * (PBR_CLUSTER_Z * LIST_STRIDE)) : (uint32_t)(sx * PBR_CLUSTER_Z);
-#ifndef PBR_SHADE_TIMING
-    if (px >= x_end) return;
-    for (uint32_t py = y_begin; py < y_end; py++)
-        shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT, LUTFOLD>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
-#else
-    if (px < x_end)
-        for (uint32_t py = y_begin; py < y_end; py++)
-            shade_pixel<STAGED_LISTS, LSTRIDE, F32OUT, LUTFOLD>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
-    SHADE_ISTAMP_MAX(blockIdx.x, 2, SHADE_NOW());
-#endif
+    const AxisTerm col = shade_column_term(p.x0 + px, p.full_w);
+    const float cvv_x = col.half_ndc * p.near_width;
+    const uint32_t col_list = shade_col_list<STAGED_LISTS>(col.cluster, tile_x0);
+    SHADE_ROW_LOOP(STAGED_LISTS, LSTRIDE, F32OUT, LUTFOLD);
 }
 
 // ---- shade tables (pbr_hip.h: PBR_TABLES_*) ---------------------------------------------------------------------------------------
-// pbr_shade_geometry_tables: per column of the tile {ndc_x * 0.5f, cluster column}, per row {ndc_y * 0.5f, cluster row} — the float expressions of
-// k_deferred_shade's column and row terms (IEEE divide, floor, clamp), which are also those of its tile bounds.  One thread per entry.
+// pbr_shade_geometry_tables: per column of the tile its shade_column_term, per row its shade_row_term, {half ndc, cluster}.  One thread per entry.
 __global__ __launch_bounds__(256) void k_shade_geometry_tables(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t full_w, uint32_t full_h, float2* __restrict__ geom) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < w) {
-        const float u = ((float)(x0 + t) + 0.5f) / (float)full_w;
-        const float ndc_x = 2.0f * u - 1.0f;
-        const int sx = clampi((int)floorf(u * (float)PBR_CLUSTER_X), 0, PBR_CLUSTER_X - 1);
-        geom[t] = make_float2(ndc_x * 0.5f, __int_as_float(sx));
-    } else if (t < w + h) {
-        const float v = ((float)(y0 + (t - w)) + 0.5f) / (float)full_h;
-        const float ndc_y = 1.0f - 2.0f * v;
-        const int sy = clampi((int)floorf((1.0f - v) * (float)PBR_CLUSTER_Y), 0, PBR_CLUSTER_Y - 1);
-        geom[t] = make_float2(ndc_y * 0.5f, __int_as_float(sy));
-    }
+    AxisTerm* entry = reinterpret_cast<AxisTerm*>(geom);
+    if (t < w) entry[t] = shade_column_term(x0 + t, full_w);
+    else if (t < w + h) entry[t] = shade_row_term(y0 + (t - w), full_h);
 }
 
 // k_deferred_shade<true, LSTRIDE, false, NoViews, true> with the prologue read from the shade tables: the light planes are a flat copy of the
@@ -764,14 +756,11 @@ __global__ __launch_bounds__(256) void k_shade_geometry_tables(uint32_t x0, uint
 // barrier.  LDS layout, dynamic LDS size and the row loop are k_deferred_shade's; shade_pixel is called as it is.
 template <int LSTRIDE>
 __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade_tabled(ShadeParams p, int n_lights, int max_clusters, ShadeRects rc, const uint32_t* __restrict__ tab) {
-    extern __shared__ float4 lds_raw[];
     __shared__ uint32_t s_mip_off[16];
     __shared__ float4 s_row[SHADE_ROWS];
     const unsigned long long t_start = SHADE_NOW();
-    (void)t_start;
     if (threadIdx.x < 16) s_mip_off[threadIdx.x] = p.env_mip_off[threadIdx.x];
-    float* llds = reinterpret_cast<float*>(lds_raw);
-    uint32_t* lists = reinterpret_cast<uint32_t*>(llds + ((LIGHT_PLANES * LSTRIDE + 1) & ~1));   // 8-byte aligned
+    SHADE_LDS_CARVE(LSTRIDE);
     {   // the planes: 16 bytes per thread and round, the odd dwords behind the last whole 16 by one thread each
         constexpr int N4 = (LIGHT_PLANES * LSTRIDE) / 4, TAIL = (LIGHT_PLANES * LSTRIDE) & 3;
         const uint4* src = reinterpret_cast<const uint4*>(tab + PBR_TABLES_PLANES);
@@ -779,21 +768,13 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
         for (int i = threadIdx.x; i < N4; i += SHADE_BLOCK) reinterpret_cast<uint4*>(llds)[i] = src[i];
         if (threadIdx.x < (uint32_t)TAIL) llds[4 * N4 + threadIdx.x] = __uint_as_float(tab[PBR_TABLES_PLANES + 4 * N4 + threadIdx.x]);
     }
-    // block -> rectangle -> (column block, row block); wave-uniform scalar arithmetic (as k_deferred_shade)
-    uint32_t r = 0;
-    while (r + 1 < rc.n && blockIdx.x >= rc.first[r + 1]) r++;
-    const uint32_t lb = blockIdx.x - rc.first[r];
-    const uint32_t bx0 = rc.x0[r] + (lb % rc.cols[r]) * SHADE_BLOCK, x_end = rc.x0[r] + rc.w[r];
-    const uint32_t by = lb / rc.cols[r], nb_big = rc.nb_big[r], rows_big = rc.rows_big, rows_small = rc.rows_small;
-    const uint32_t y_begin = rc.y0[r] + (by < nb_big ? by * rows_big : nb_big * rows_big + (by - nb_big) * rows_small);
-    const uint32_t y_end = min(y_begin + (by < nb_big ? rows_big : rows_small), rc.y0[r] + rc.h[r]);
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_cf*)llds;
+    SHADE_BLOCK_SPAN(rc);
     // the cluster tiles of the block's rectangle: the cluster column / row of its corners (monotone in the pixel coordinate); uniform addresses
-    const uint2* cols = reinterpret_cast<const uint2*>(tab + PBR_TABLES_GEOM);
-    const uint2* rows = cols + p.w;
+    const AxisTerm* cols = reinterpret_cast<const AxisTerm*>(tab + PBR_TABLES_GEOM);
+    const AxisTerm* rows = cols + p.w;
     const uint32_t bx1 = min(bx0 + SHADE_BLOCK, x_end) - 1;
-    const int tile_x0 = (int)cols[bx0].y, tile_x1 = (int)cols[bx1].y;
-    const int ty_a = (int)rows[y_begin].y, ty_b = (int)rows[y_end - 1].y;
+    const int tile_x0 = cols[bx0].cluster, tile_x1 = cols[bx1].cluster;
+    const int ty_a = rows[y_begin].cluster, ty_b = rows[y_end - 1].cluster;
     const int tile_y0 = min(ty_a, ty_b), tile_y1 = max(ty_a, ty_b);
     const int tiles_x = tile_x1 - tile_x0 + 1;
     {
@@ -818,31 +799,14 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_deferred_shade
             }
         }
     }
-    if (threadIdx.x < (uint32_t)SHADE_ROWS) {
-        const uint2 e = rows[min(y_begin + threadIdx.x, p.h - 1u)];
-        const float cvv_y = __uint_as_float(e.x) * p.near_height;
-        const uint32_t row_list = (uint32_t)(((int)e.y - tile_y0) * tiles_x * (PBR_CLUSTER_Z * LIST_STRIDE));
-        s_row[threadIdx.x] = make_float4(p.InvView[1] * cvv_y, p.InvView[4] * cvv_y, p.InvView[7] * cvv_y, __uint_as_float(row_list));
-    }
+    if (threadIdx.x < (uint32_t)SHADE_ROWS) s_row[threadIdx.x] = shade_row_entry<true>(p, rows[min(y_begin + threadIdx.x, p.h - 1u)], tile_y0, tiles_x);
     const int q_safe = (int)tab[PBR_TABLES_HEADER];
     const uint32_t px = bx0 + threadIdx.x;
-    const uint2 ce = cols[min(px, p.w - 1u)];
-    const float cvv_x = __uint_as_float(ce.x) * p.near_width;
-    const uint32_t col_list = (uint32_t)(((int)ce.y - tile_x0) * (PBR_CLUSTER_Z * LIST_STRIDE));
+    const AxisTerm col = cols[min(px, p.w - 1u)];
+    const float cvv_x = col.half_ndc * p.near_width;
+    const uint32_t col_list = shade_col_list<true>(col.cluster, tile_x0);
     __syncthreads();
-    SHADE_ISTAMP(blockIdx.x, 0, t_start);
-    SHADE_ISTAMP(blockIdx.x, 1, SHADE_NOW());
-    SHADE_ISTAMP(blockIdx.x, 3, ((unsigned long long)(y_end - y_begin) << 48) | blockIdx.x);
-#ifndef PBR_SHADE_TIMING
-    if (px >= x_end) return;
-    for (uint32_t py = y_begin; py < y_end; py++)
-        shade_pixel<true, LSTRIDE, false, true>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
-#else
-    if (px < x_end)
-        for (uint32_t py = y_begin; py < y_end; py++)
-            shade_pixel<true, LSTRIDE, false, true>(p, llds, lists, s_mip_off, n_lights, q_safe, px, py, s_row[py - y_begin], cvv_x, col_list);
-    SHADE_ISTAMP_MAX(blockIdx.x, 2, SHADE_NOW());
-#endif
+    SHADE_ROW_LOOP(true, LSTRIDE, false, true);
 }
 
 extern "C" {
@@ -864,30 +828,40 @@ pbr_status pbr_env_pad(pbr_ctx* ctx, const pbr_half* env, uint32_t size, uint32_
 
 }  // extern "C"
 
-// the camera's part of ShadeParams (host libm, once per call)
-static void camera_params(const pbr_global* g, ShadeParams& p) {
-    p.sh = g->SkyBoxSH;
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) p.InvView[r * 3 + c] = g->InvView[r * 4 + c];
+// The camera fields and the target fields, which ShadeParams and ShadeView name alike, are each filled by one text (the kernel's arguments
+// keep the two layouts: as shared sub-structs they moved the staged kernels' scalar loads, one s_waitcnt more).  Host libm, once per call.
+template <class P>
+static void camera_params(const pbr_global* g, P& p) {
+    camera_near_plane(g, p.InvView, p.near_width, p.near_height);
     for (int i = 0; i < 3; i++) p.CameraPos[i] = g->CameraPos[i];
     p.Near = g->Near; p.Far = g->Far;
-    p.near_height = 2.0f * g->Near * tanf(g->Fov / 2.0f);
-    p.near_width = p.near_height * g->Ratio;
     p.log_far_near = logf(g->Far / g->Near);
     p.inv_near = (float)(1.0 / (double)g->Near);
     p.slice_k = (float)((double)PBR_CLUSTER_Z / log2((double)g->Far / (double)g->Near));
+}
+template <class P>
+static void target_params(P& p, const pbr_gbuffer& gb, const pbr_cluster* clusters, const pbr_light* lights, pbr_half* hdr, uint32_t hdr_pitch) {
+    p.A = gb.A; p.B = gb.B; p.C = gb.C; p.depth = gb.depth; p.stencil = gb.stencil; p.pitch = gb.pitch;
+    p.clusters = clusters; p.lights = lights; p.hdr = hdr; p.hdr_pitch = hdr_pitch;
 }
 
 // what every target of a launch shares: the camera of g (a view table replaces it per view), LUT and padded env chain; the rest is zero
 static ShadeParams shade_params(const pbr_global* g, const pbr_half* lut, uint32_t lut_res, const pbr_half* env, uint32_t env_size, uint32_t env_mips) {
     ShadeParams p{};
     camera_params(g, p);
+    p.sh = g->SkyBoxSH;
     p.lut = lut; p.lut_res = lut_res; p.env = env; p.env_size = env_size; p.env_mips = env_mips;
     for (uint32_t m = 0; m < 16; m++) p.env_mip_off[m] = (uint32_t)env_padded_mip_offset(env_size, m < env_mips ? m : env_mips - 1);
     return p;
 }
 
-// The checks of a shade launch return what is wrong (nullptr: nothing).  The LUT and padded env chain every target reads:
+// The checks of a shade launch return what is wrong (nullptr: nothing).  The tile:
+static const char* shade_tile_bad(const pbr_tile* tile) {
+    if (!(tile->w >= 1 && tile->h >= 1 && tile->w <= 65535 && tile->h <= 65535)) return "bad tile size";
+    if (!(tile->x0 + tile->w <= tile->full_w && tile->y0 + tile->h <= tile->full_h)) return "tile outside frame";
+    return nullptr;
+}
+// The LUT and padded env chain every target reads:
 // (lut: the half2 LUT, or — lut_align 8 — its x-folded table)
 static const char* shade_tables_bad(const void* lut, uint32_t lut_res, const pbr_half* env, uint32_t env_size, uint32_t env_mips, uint32_t lut_align = 4) {
     if (!lut || !env) return "null pointer";
@@ -969,17 +943,18 @@ static pbr_status shade_dispatch(pbr_ctx* ctx, const ShadeParams& p, int num_lig
     const int max_clusters = staged ? (int)(span_x * span_y) * PBR_CLUSTER_Z : 0;
     const size_t lds = plane_bytes + (size_t)max_clusters * LIST_STRIDE * sizeof(uint32_t);
     const dim3 grid(rc.first[rc.n], n_views), blk(SHADE_BLOCK);
+    // one choice by (staged, stride) for both kernels; launch(staged, stride) gets them as integral constants
+    auto pick = [&](auto launch) {
+        auto by_stride = [&](auto st) { if (lstride == 257) launch(st, std::integral_constant<int, 257>{}); else launch(st, std::integral_constant<int, PBR_MAX_SCENE_LIGHTS + 1>{}); };
+        if (staged) by_stride(std::true_type{}); else by_stride(std::false_type{});
+    };
     if constexpr (std::is_same_v<VS, NoViews> && LUTFOLD && !F32OUT) {
         if (tables && staged) {   // the prologue from the shade tables (not staged: the kernel below reads lights and clusters itself)
-            if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade_tabled<257>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, tables);
-            else hipLaunchKernelGGL((k_deferred_shade_tabled<PBR_MAX_SCENE_LIGHTS + 1>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, tables);
+            pick([&](auto, auto stride) { hipLaunchKernelGGL((k_deferred_shade_tabled<stride.value>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, tables); });
             return launched(ctx, "k_deferred_shade_tabled");
         }
     }
-    if (staged && lstride == 257) hipLaunchKernelGGL((k_deferred_shade<true, 257, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
-    else if (staged) hipLaunchKernelGGL((k_deferred_shade<true, PBR_MAX_SCENE_LIGHTS + 1, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs);
-    else if (lstride == 257) hipLaunchKernelGGL((k_deferred_shade<false, 257, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, vs);
-    else hipLaunchKernelGGL((k_deferred_shade<false, PBR_MAX_SCENE_LIGHTS + 1, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, 0, rc, vs);
+    pick([&](auto st, auto stride) { hipLaunchKernelGGL((k_deferred_shade<st.value, stride.value, F32OUT, VS, LUTFOLD>), grid, blk, lds, ctx->stream, p, num_lights, max_clusters, rc, vs); });
     return launched(ctx, std::is_same_v<VS, NoViews> ? "k_deferred_shade" : "k_deferred_shade<views>");
 }
 
@@ -1001,8 +976,7 @@ static pbr_status shade_launch(pbr_ctx* ctx, const char* who, const pbr_shade_de
     const pbr_tile* tile = d.tile;
     PBR_CHECK(ctx, who, d.g && tile && d.gb ? nullptr : "null pointer");
     PBR_CHECK(ctx, who, d.rects || d.n_rects == 0 ? nullptr : "null rectangle list");
-    PBR_CHECK(ctx, who, tile->w >= 1 && tile->h >= 1 && tile->w <= 65535 && tile->h <= 65535 ? nullptr : "bad tile size");
-    PBR_CHECK(ctx, who, tile->x0 + tile->w <= tile->full_w && tile->y0 + tile->h <= tile->full_h ? nullptr : "tile outside frame");
+    PBR_CHECK(ctx, who, shade_tile_bad(tile));
     PBR_CHECK(ctx, who, shade_target_bad(d.g, *d.gb, d.clusters, F32OUT ? (const void*)hdr_f32 : (const void*)d.hdr, d.hdr_pitch, tile->w, tile->h, d.lights, d.num_lights));
     PBR_CHECK(ctx, who, shade_tables_bad(LUTFOLD ? (const void*)d.lut_fold : (const void*)d.lut, d.lut_res, d.env_padded, d.env_size, d.env_mips, LUTFOLD ? 8 : 4));
     const uint32_t whole[1][4] = {{0, 0, tile->w, tile->h}};
@@ -1017,8 +991,8 @@ static pbr_status shade_launch(pbr_ctx* ctx, const char* who, const pbr_shade_de
     ShadeParams p = shade_params(d.g, LUTFOLD ? nullptr : d.lut, d.lut_res, d.env_padded, d.env_size, d.env_mips);
     if (LUTFOLD) p.lut_fold = d.lut_fold;
     p.x0 = tile->x0; p.y0 = tile->y0; p.w = tile->w; p.h = tile->h; p.full_w = tile->full_w; p.full_h = tile->full_h;
-    p.A = d.gb->A; p.B = d.gb->B; p.C = d.gb->C; p.depth = d.gb->depth; p.stencil = d.gb->stencil; p.pitch = d.gb->pitch;
-    p.clusters = d.clusters; p.lights = d.lights; p.hdr = d.hdr; p.hdr_pitch = d.hdr_pitch; p.hdr_f32 = hdr_f32;
+    target_params(p, *d.gb, d.clusters, d.lights, d.hdr, d.hdr_pitch);
+    p.hdr_f32 = hdr_f32;
     return shade_dispatch<F32OUT, LUTFOLD>(ctx, p, d.num_lights, d.num_lights, shade_schedule(ctx, rects, n_rects, 1), 1, NoViews{},
                                            d.tables ? (const uint32_t*)d.tables->dev : nullptr);
 }
@@ -1050,8 +1024,7 @@ pbr_status pbr_lut_fold_x(pbr_ctx* ctx, const pbr_half* lut, uint32_t lut_res, f
 pbr_status pbr_shade_geometry_tables(pbr_ctx* ctx, const pbr_tile* tile, pbr_shade_tables* tables) {
     if (!ctx) return PBR_ERR_INVALID;
     PBR_REQUIRE(ctx, tile && tables, "pbr_shade_geometry_tables: null pointer");
-    PBR_REQUIRE(ctx, tile->w >= 1 && tile->h >= 1 && tile->w <= 65535 && tile->h <= 65535, "pbr_shade_geometry_tables: bad tile size");
-    PBR_REQUIRE(ctx, tile->x0 + tile->w <= tile->full_w && tile->y0 + tile->h <= tile->full_h, "pbr_shade_geometry_tables: tile outside frame");
+    PBR_CHECK(ctx, "pbr_shade_geometry_tables", shade_tile_bad(tile));
     PBR_REQUIRE(ctx, tables->dev && ((uintptr_t)tables->dev & 15u) == 0 && tables->bytes >= pbr_shade_tables_bytes(tile->w, tile->h),
                 "pbr_shade_geometry_tables: the tables buffer must be 16-byte aligned and hold pbr_shade_tables_bytes(w, h)");
     tables->built &= ~PBR_TABLES_BUILT_GEOMETRY;
@@ -1091,15 +1064,9 @@ pbr_status pbr_deferred_shade_views(pbr_ctx* ctx, const pbr_view* views, uint32_
         const pbr_view& v = views[i];
         PBR_CHECK(ctx, who, shade_target_bad(&v.g, v.gb, v.clusters, v.hdr, v.hdr_pitch, w, h, v.lights, v.num_lights));
         PBR_REQUIRE(ctx, memcmp(&v.g.SkyBoxSH, &views[0].g.SkyBoxSH, sizeof(pbr_sh_pack)) == 0, "pbr_deferred_shade_views: SkyBoxSH differs between views");
-        ShadeParams c;
-        camera_params(&v.g, c);
-        ShadeView& d = vs.v[i];
-        for (int k = 0; k < 9; k++) d.InvView[k] = c.InvView[k];
-        for (int k = 0; k < 3; k++) d.CameraPos[k] = c.CameraPos[k];
-        d.Near = c.Near; d.Far = c.Far; d.near_width = c.near_width; d.near_height = c.near_height;
-        d.log_far_near = c.log_far_near; d.inv_near = c.inv_near; d.slice_k = c.slice_k;
-        d.A = v.gb.A; d.B = v.gb.B; d.C = v.gb.C; d.depth = v.gb.depth; d.stencil = v.gb.stencil; d.pitch = v.gb.pitch;
-        d.clusters = v.clusters; d.lights = v.lights; d.hdr = v.hdr; d.hdr_pitch = v.hdr_pitch; d.n_lights = v.num_lights;
+        camera_params(&v.g, vs.v[i]);
+        target_params(vs.v[i], v.gb, v.clusters, v.lights, v.hdr, v.hdr_pitch);
+        vs.v[i].n_lights = v.num_lights;
         max_lights = v.num_lights > max_lights ? v.num_lights : max_lights;
     }
     PBR_REQUIRE(ctx, views_disjoint(views, n, 1, [&](const pbr_view& v, int, uintptr_t& lo, uintptr_t& hi) {

@@ -1,8 +1,7 @@
 // sun.hip — pbr_sun_light: a directional light with a shadow map, added to the HDR target after the shade, and pbr_sun_fit, the
 // orthographic light camera around a world box (host only).  The rule is pinned in include/pbr_hip.h and restated in
 // tests/sun_truth.py; this unit is built with -ffp-contract=off and uses IEEE divides and square roots only, so the restatement
-// is bit for bit.  The small device functions the shade has of its own (decode_octahedron, the view-space depth) are restated
-// here: shade.hip's generated code is pinned by tests and stays untouched.
+// is bit for bit.
 #include <cmath>
 #include "pbr_device.hpp"
 #include "pbr_internal.hpp"
@@ -26,7 +25,6 @@ struct SunParams {
 
 __device__ __forceinline__ float dot_lr(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ V3 unit_exact(V3 v) { const float l = sqrtf(dot_lr(v, v)); return v3(v.x / l, v.y / l, v.z / l); }
-__device__ __forceinline__ float sign1(float x) { return x < 0.0f ? -1.0f : 1.0f; }   // global.hlsli:85-88
 __device__ __forceinline__ float lerp_t(float a, float b, float w) { return a + (b - a) * w; }
 
 // one tap: lit outside the map, and where the receiver is not behind the stored depth (a tie is lit)
@@ -79,14 +77,7 @@ __global__ __launch_bounds__(256) void k_sun_light(const SunParams p) {
         if (p.stencil[gi] != 0) {
             const uint32_t a = p.A[gi], b = p.B[gi], c = p.C[gi];
             const float depth = p.depth[gi];
-            // normal: global.hlsli:101-115
-            V3 d = v3(((float)(b & 255u) * inv255) * 2.0f - 1.0f, ((float)((b >> 8) & 255u) * inv255) * 2.0f - 1.0f, 0.0f);
-            d.z = 1.0f - fabsf(d.x) - fabsf(d.y);
-            if (d.z < 0.0f) {
-                const float nx = sign1(d.x) * (1.0f - fabsf(d.y)), ny = sign1(d.y) * (1.0f - fabsf(d.x));
-                d.x = nx; d.y = ny;
-            }
-            const V3 N = unit_exact(d);
+            const V3 N = unit_exact(decode_octahedron((float)(b & 255u) * inv255, (float)((b >> 8) & 255u) * inv255));
             const V3 L = v3(p.L[0], p.L[1], p.L[2]);
             const float NdotL = dot_lr(N, L);
             if (NdotL > 0.0f) {
@@ -97,7 +88,7 @@ __global__ __launch_bounds__(256) void k_sun_light(const SunParams p) {
                 const V3 cv = v3((p.InvView[0] * cvv_x + p.InvView[1] * cvv_y) + p.InvView[2] * p.Near,
                                  (p.InvView[3] * cvv_x + p.InvView[4] * cvv_y) + p.InvView[5] * p.Near,
                                  (p.InvView[6] * cvv_x + p.InvView[7] * cvv_y) + p.InvView[8] * p.Near);
-                const float z_vs = (p.Near * p.Far) / (p.Far - depth * (p.Far - p.Near));
+                const float z_vs = view_space_depth(depth, p.Near, p.Far);
                 const float zs = z_vs / p.Near;
                 const V3 cam = v3(p.CameraPos[0], p.CameraPos[1], p.CameraPos[2]);
                 const V3 P = v3(cam.x + cv.x * zs, cam.y + cv.y * zs, cam.z + cv.z * zs);
@@ -201,7 +192,7 @@ pbr_status pbr_sun_light(pbr_ctx* ctx, const pbr_sun_desc* d) {
         for (int c = 0; c < 3; c++) p.InvView[r * 3 + c] = g.InvView[r * 4 + c];
     for (int i = 0; i < 3; i++) { p.CameraPos[i] = g.CameraPos[i]; p.L[i] = s.Direction[i]; p.Lum[i] = s.Luminance[i]; }
     p.Near = g.Near; p.Far = g.Far;
-    p.near_height = (float)(2.0 * (double)g.Near * std::tan((double)g.Fov / 2.0));
+    p.near_height = (float)(2.0 * (double)g.Near * std::tan((double)g.Fov / 2.0));   // its own, not pbr::camera_near_plane: the double-precision tan is pinned by tests/sun_truth.py
     p.near_width = p.near_height * g.Ratio;
     for (int i = 0; i < 12; i++) p.M[i] = M[i];
     p.bias_const = s.bias_const; p.bias_slope = s.bias_slope;

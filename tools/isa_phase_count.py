@@ -21,7 +21,9 @@ Only instruction CLASSES are counted (v_*, v_pk_*, the transcendental unit's, mo
     python tools/isa_phase_count.py --bloom parent_bloom.hip [out.md] [--src gbuffer_raster.hip] [--flags "-ffp-contract=off"] [--also-with PBR_DEBUG_KNOBS]
 compares every kernel instantiation of a translation unit (bloom.hip unless --src names another; --flags: what the Makefile adds for
 it, bloom.hip's by default) with those of another copy of the source, which includes the headers that lie beside it (see bloom_report
-below); --also-with adds the same table for the build with that macro defined."""
+below); --also-with adds the same table for the build with that macro defined.
+    python tools/isa_phase_count.py --shade parent_shade.hip [out.md]
+the same for shade.hip, product and knobs build (shade_report below)."""
 import os
 import re
 import subprocess
@@ -249,6 +251,20 @@ def bloom_report(parent_src, new_src=BLOOM_SRC, flags=BLOOM_FLAGS, defines=()):
     return doc, bad
 
 
+SHADE_BUILDS = ((), ("PBR_DEBUG_KNOBS",))   # the Makefile's shade.o and shade.k.o: no flags of the unit's own
+
+
+def shade_report(parent_src):
+    """bloom_report for shade.hip (profiles/shade_isa_resources.md, tests/test_shade_isa_resources_cpu.py): the product build's table,
+    then the knobs build's"""
+    doc, bad = [], {}
+    for defines in SHADE_BUILDS:
+        more, bad_more = bloom_report(parent_src, SRC, (), defines)
+        doc += ([""] if doc else []) + more
+        bad.update({n + "".join(" -D" + d for d in defines): c for n, c in bad_more.items()})
+    return doc, bad
+
+
 def parse_bloom_rows(md_text, side="new"):
     """{mangled name: {column: value}} of the `side` rows of a report written by bloom_report"""
     out = {}
@@ -258,6 +274,14 @@ def parse_bloom_rows(md_text, side="new"):
 
 
 def main(argv):
+    if "--shade" in argv:   # python tools/isa_phase_count.py --shade parent_shade.hip [out.md]
+        rest = [a for a in argv if a != "--shade"]
+        doc, bad = shade_report(rest[0])
+        text = "\n".join(doc) + "\n"
+        print(text)
+        if len(rest) > 1:
+            open(rest[1], "w").write(text)
+        sys.exit(1 if bad else 0)
     if "--bloom" in argv:
         rest = [a for a in argv if a != "--bloom"]
         opt = {}
