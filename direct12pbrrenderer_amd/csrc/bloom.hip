@@ -12,9 +12,10 @@
 //  2. Pieces the merging kernels share: luminance bin, per-wave histograms (hist_*), the merge rounding (merge_rounded*).
 //  3. FUSED kernels for exact 2x pyramids, bit-identical to the staged ones: k_bloom_prefilter_2x (shared samples), k_blur_hv
 //     (H + V of a level [+ merge + histogram] on a tile) and k_blur_up_poly (large 2x-up levels), with what those two share:
-//     TailRect and its tests, level_args (view selection), level_alpha, wave_sync.
+//     TailRect and its tests, level_args (view selection), level_alpha, wave_sync; and k_bloom_small_end, which computes pyramid
+//     levels 4 and 3 inside level 2's up-pass launch (per tile, in LDS, on the region the tile taps) in k_blur_hv's operation order.
 //  4. Launch: tail_rect / tile_grid / launch_hv (the fused kernels' choice), prefilter_launch, the checks entry points share.
-//  5. C ABI of the staged passes; the schedule (bloom_pass, up_pass_rects); C ABI of the chain.
+//  5. C ABI of the staged passes; the schedule (bloom_pass, up_pass_rects; when the small end is folded: there); C ABI of the chain.
 #include <type_traits>
 #include "pbr_internal.hpp"
 #include "pbr_device.hpp"
@@ -846,6 +847,171 @@ __global__ __launch_bounds__(512, 4) void k_blur_up_poly(const pbr_half* __restr
     }
 }
 
+// ---------------------------------------------------------------- the pyramid's small end inside one up-pass launch: k_bloom_small_end
+// One block = one 64 x 16 tile of an up-pass (k_blur_hv<M_UP, true, 0, 16>'s), with the DEPTH smaller levels under it recomputed in LDS
+// on the region the tile depends on, so that their launches go: no block waits for another.
+//   DEPTH 1: the tile is level 3's; the level-4 texels it taps (what k_blur_hv<M_DOWN> of level 3 -> 4 stores) come first.
+//   DEPTH 2: the tile is level 2's; level 4, then level 3's up-pass result on the region the tile taps, then the tile.
+// `a_lo` is chain A of the level that is downsampled (level 3), `a_mid` chain A of level 2 (DEPTH 2), `out` chain B of the tile's level.
+// The regions follow from tap1d<M_UP> (a tile origin is a multiple of 64 x 16): positions x0 - 4 .. x0 + 67 tap the 38 columns
+// x0 / 2 - 3 .. of the level below, rows y0 - 4 .. y0 + 19 its 14 rows y0 / 2 - 3 ..; a 38 x 14 region at (32 n - 3, 8 m - 3) taps the
+// 24 x 12 texels at (16 n - 4, 4 m - 4) of the level below it.  A region may hang over its level's edge: those texels are computed like
+// the others (taps clamp as in k_blur_hv: columns by tap index, rows by position) and never read, because every tap index is clamped.
+// Every stage is k_blur_hv's three steps with a block barrier between them — samples (finish_tap2_rgb; the same-size input's texels
+// stay fp16: exact), H gauss + the fp16 rounding of the H pass's store, V gauss + the fp16 rounding of the level's store — in the same
+// operation order on the same operands, so every value is what the separate launches compute.
+namespace small_end {
+constexpr int NT = 512, TW = 64, TH = 16;
+constexpr int R1W = 38, R1H = 14;   // the region under a tile: 72 x 24 positions from an even origin tap n / 2 + 2 texels
+constexpr int R2W = 24, R2H = 12;   // the region under that: 46 x 22 positions from an odd origin tap n / 2 + 1 texels
+}  // namespace small_end
+// the nine taps down a fp16 column / along a fp16 row: k_blur_hv's V pass, and its second H input
+__device__ __forceinline__ V3 gauss9_h(const H4* c, int stride) {
+    V3 v = v3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int i = 0; i < 9; i++) v = fma3(h3f(c[i * stride]), c_gauss[i], v);
+    return v;
+}
+// level_alpha on values: the input's alpha (and the second input's) through the H pass, its fp16 store and the V pass
+template <bool DUAL>
+__device__ __forceinline__ LevelAlpha level_alpha_of(float in_w, float in2_w) {
+    float alpha_h = gauss9_const(in_w);
+    if (DUAL) alpha_h = alpha_h + gauss9_const(in2_w);
+    const h16 alpha_t = to_half_rn(alpha_h);
+    return LevelAlpha{alpha_t, gauss9_const((float)alpha_t)};
+}
+// samples of a MODE level at positions (px0 + c, clamp(py0 + r)), c < SW, r < SR, of the output level (height oh): the input level
+// (iw x ih) is `src`, whose texel (x, y) is src[(y - sy0) * spitch + (x - sx0)] (global: the level itself; LDS: a region of it)
+template <int MODE, int SW, int SR>
+__device__ __forceinline__ void se_sample(float4* sS, const H4* src, int spitch, int sx0, int sy0, int iw, int ih, int px0, int py0, int oh, int t) {
+    constexpr int N = SW * SR, TRIPS = (N + small_end::NT - 1) / small_end::NT;
+    Tap2 tp[TRIPS];
+    float fx[TRIPS], fy[TRIPS];
+#pragma unroll
+    for (int k = 0; k < TRIPS; k++) {
+        const int e = min(t + k * small_end::NT, N - 1);
+        const int r = e / SW, c = e - r * SW;
+        int ax0, ax1, ay0, ay1;
+        tap1d<MODE>(px0 + c, iw, ax0, ax1, fx[k]);
+        tap1d<MODE>(clampi(py0 + r, 0, oh - 1), ih, ay0, ay1, fy[k]);
+        const int o0 = (ay0 - sy0) * spitch - sx0, o1 = (ay1 - sy0) * spitch - sx0;
+        tp[k].c00 = src[o0 + ax0]; tp[k].c10 = src[o0 + ax1]; tp[k].c01 = src[o1 + ax0]; tp[k].c11 = src[o1 + ax1];
+    }
+#pragma unroll
+    for (int k = 0; k < TRIPS; k++) {
+        const int e = t + k * small_end::NT;
+        if (e < N) sS[e] = finish_tap2_rgb<MODE>(tp[k], fx[k], fy[k]);
+    }
+}
+// the same-size second input (ow x oh, global) at the same positions, clamped to the level both ways: exact texels
+template <int SW, int SR>
+__device__ __forceinline__ void se_second(H4* sU, const pbr_half* __restrict__ in2, int ow, int oh, int px0, int py0, int t) {
+    constexpr int N = SW * SR, TRIPS = (N + small_end::NT - 1) / small_end::NT;
+    H4 u[TRIPS];
+#pragma unroll
+    for (int k = 0; k < TRIPS; k++) {
+        const int e = min(t + k * small_end::NT, N - 1);
+        const int r = e / SW, c = e - r * SW;
+        u[k] = reinterpret_cast<const H4*>(in2)[(size_t)clampi(py0 + r, 0, oh - 1) * ow + clampi(px0 + c, 0, ow - 1)];
+    }
+#pragma unroll
+    for (int k = 0; k < TRIPS; k++) {
+        const int e = t + k * small_end::NT;
+        if (e < N) sU[e] = u[k];
+    }
+}
+// H gauss of RW x SR outputs from (RW + 8) x SR samples (+ the second input's), rounded to fp16 where the H pass stores
+template <bool DUAL, int RW, int SR>
+__device__ __forceinline__ void se_hpass(H4* sT, const float4* sS, const H4* sU, h16 alpha_t, int t) {
+    for (int e = t; e < RW * SR; e += small_end::NT) {
+        const int r = e / RW, c = e - r * RW;
+        V3 g = gauss9_rgb(sS + r * (RW + 8) + c);
+        if (DUAL) g = g + gauss9_h(sU + r * (RW + 8) + c, 1);   // bloom_upsample_add: lower first, then upper
+        H4 th;
+        th.x = to_half_rn(g.x); th.y = to_half_rn(g.y); th.z = to_half_rn(g.z); th.w = alpha_t;
+        sT[e] = th;
+    }
+}
+// V gauss of RW x RH outputs from RW x (RH + 8) fp16 rows into an LDS region, rounded to fp16 where the level is stored
+template <int RW, int RH>
+__device__ __forceinline__ void se_vpass(H4* sL, const H4* sT, float alpha_v, int t) {
+    for (int e = t; e < RW * RH; e += small_end::NT) {
+        const V3 a = gauss9_h(sT + e, RW);
+        H4 o;
+        o.x = to_half_rn(a.x); o.y = to_half_rn(a.y); o.z = to_half_rn(a.z); o.w = to_half_rn(alpha_v);
+        sL[e] = o;
+    }
+}
+
+template <int DEPTH>
+__global__ __launch_bounds__(small_end::NT, 4) void k_bloom_small_end(const pbr_half* __restrict__ a_lo, int lw, int lh,      // chain A level 3
+                                                                    const pbr_half* __restrict__ a_mid,                     // chain A level 2 (DEPTH 2)
+                                                                    pbr_half* __restrict__ out, int ow, int oh, int tiles_x) {
+    using namespace small_end;
+    static_assert(DEPTH == 1 || DEPTH == 2, "one or two levels under the tile");
+    // the tile's samples; the region of the level below it; (DEPTH 2) the region below that.  R1 is the level the down pass makes.
+    constexpr int S0W = TW + 8, S0R = TH + 8;
+    constexpr int S1W = R1W + 8, S1R = R1H + 8, S2W = R2W + 8, S2R = R2H + 8;   // samples 46 x 22 and 32 x 20
+    static_assert(R1W == (TW + 8) / 2 + 2 && R1H == (TH + 8) / 2 + 2 && R2W == S1W / 2 + 1 && R2H == S1R / 2 + 1, "regions of a 64 x 16 tile");
+    constexpr int NS = S0W * S0R;                                       // the largest stage is the tile's own
+    constexpr int NU_MID = DEPTH == 2 ? S1W * S1R : 1;
+    __shared__ float4 sS[NS];                                           // samples of a stage's first input
+    __shared__ H4 sU[NS];                                               // the tile stage's second input
+    __shared__ H4 sUmid[NU_MID];                                        // DEPTH 2: the middle stage's second input
+    __shared__ H4 sT[TW * S0R];                                         // a stage's H result
+    __shared__ H4 sR1[R1W * R1H];                                       // the finished region under the tile
+    __shared__ H4 sR2[DEPTH == 2 ? R2W * R2H : 1];                      // DEPTH 2: the level-4 region
+    static_assert(sizeof(sS) + sizeof(sU) + sizeof(sUmid) + sizeof(sT) + sizeof(sR1) + sizeof(sR2) <= 80 * 1024, "k_bloom_small_end: two blocks per CU");
+    const int t = threadIdx.x;
+    const int x0 = ((int)blockIdx.x % tiles_x) * TW, y0 = ((int)blockIdx.x / tiles_x) * TH;
+    const int r1x = (x0 >> 1) - 3, r1y = (y0 >> 1) - 3;                 // origin of the region under the tile
+    const int w4 = lw >> 1, h4 = lh >> 1;                               // level 4
+    // the constant alpha of every level on the way (level_alpha): level 4 from chain A level 3, then each up-pass from the stored
+    // alpha of the level below and chain A of its own level
+    const float lo_w = (float)reinterpret_cast<const H4*>(a_lo)[0].w;
+    const LevelAlpha al4 = level_alpha_of<false>(lo_w, 0.0f);
+    const LevelAlpha al3 = level_alpha_of<true>((float)to_half_rn(al4.v), lo_w);
+    if constexpr (DEPTH == 1) {
+        // ---- level 4 on R1 (the tile is level 3's: ow x oh = lw x lh), from chain A level 3 in global memory
+        se_sample<M_DOWN, S1W, S1R>(sS, reinterpret_cast<const H4*>(a_lo), lw, 0, 0, lw, lh, r1x - 4, r1y - 4, h4, t);
+        se_second<S0W, S0R>(sU, a_lo, ow, oh, x0 - 4, y0 - 4, t);
+        __syncthreads();
+        se_hpass<false, R1W, S1R>(sT, sS, nullptr, al4.t, t);
+        __syncthreads();
+        se_vpass<R1W, R1H>(sR1, sT, al4.v, t);
+        __syncthreads();
+    } else {
+        const int r2x = (x0 >> 2) - 4, r2y = (y0 >> 2) - 4;             // origin of the level-4 region
+        se_sample<M_DOWN, S2W, S2R>(sS, reinterpret_cast<const H4*>(a_lo), lw, 0, 0, lw, lh, r2x - 4, r2y - 4, h4, t);
+        se_second<S1W, S1R>(sUmid, a_lo, lw, lh, r1x - 4, r1y - 4, t);
+        se_second<S0W, S0R>(sU, a_mid, ow, oh, x0 - 4, y0 - 4, t);
+        __syncthreads();
+        se_hpass<false, R2W, S2R>(sT, sS, nullptr, al4.t, t);
+        __syncthreads();
+        se_vpass<R2W, R2H>(sR2, sT, al4.v, t);
+        __syncthreads();
+        // ---- level 3's up-pass on R1: level 4 from sR2, chain A level 3 from sUmid
+        se_sample<M_UP, S1W, S1R>(sS, sR2, R2W, r2x, r2y, w4, h4, r1x - 4, r1y - 4, lh, t);
+        __syncthreads();
+        se_hpass<true, R1W, S1R>(sT, sS, sUmid, al3.t, t);
+        __syncthreads();
+        se_vpass<R1W, R1H>(sR1, sT, al3.v, t);
+        __syncthreads();
+    }
+    // ---- the tile: k_blur_hv<M_UP, true, 0, 16> with the level below from sR1
+    const LevelAlpha al = DEPTH == 1 ? al3 : level_alpha_of<true>((float)to_half_rn(al3.v), (float)reinterpret_cast<const H4*>(a_mid)[0].w);
+    se_sample<M_UP, S0W, S0R>(sS, sR1, R1W, r1x, r1y, ow >> 1, oh >> 1, x0 - 4, y0 - 4, oh, t);
+    __syncthreads();
+    se_hpass<true, TW, S0R>(sT, sS, sU, al.t, t);
+    __syncthreads();
+    for (int e = t; e < TW * TH; e += NT) {
+        const int x = x0 + (e & (TW - 1)), y = y0 + e / TW;
+        if (x >= ow || y >= oh) continue;
+        const V3 a = gauss9_h(sT + e, TW);
+        store_h4(out + 4 * ((size_t)y * ow + x), f4(a.x, a.y, a.z, al.v));
+    }
+}
+
 // ---------------------------------------------------------------- launch
 // k_blur_h of in (+ in2: DUAL) into out (ow x oh).  A block pipelines as many rows as keep >= ~2048 blocks (8 per CU) in the grid
 template <bool DUAL>
@@ -1152,8 +1318,32 @@ static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint3
                 if ((r = prefilter_launch(ctx, v[i].hdr, w, h, v[i].pitch, v[i].A + off(1), &whole, 1, threshold, knee))) return r;
         }
     }
+    // The small end in one launch (k_bloom_small_end; PBR_BLOOM_SMALL_END = 0 | 1 | 2 levels folded): one view of whole frames whose
+    // levels 1 - 3 are exact halves, and whose folded up-passes would each take k_blur_hv/16, the kernel it restates bit for bit.
+    // Depth 2 skips the down pass 3 -> 4 and level 3's up-pass, and level 2's up-pass reads chain A levels 3 and 2; depth 1 skips
+    // the down pass alone.  Chain A level 4 (and chain B level 3) are then not written.  The product takes depth 2 (the measured keep:
+    // EXPERIMENTS.md), and today's launches where level 2 is large enough for another kernel.
+    static const int small_end_knob = pbr::knob_int("PBR_BLOOM_SMALL_END", 2);
+    static const int wide_forced = pbr::knob_int("PBR_BLOOM_WIDE", -1);
+    auto takes_hv16 = [&](uint32_t l) {   // launch_hv's choice for the whole level, whatever the shader-order switch says
+        const TailRect whole = tail_rect(W(l), H(l), nullptr, nullptr, nullptr);
+        return wide_forced != 1 && tile_grid(whole, 128, 32).n < 400 && tile_grid(whole, 64, 32).n < 900;
+    };
+    int small_end = 0;
+    if (!MV && n == 1 && merge0 == nullptr && PBR_BLOOM_STEP == 3 && exact(1) && exact(2) && exact(3) && takes_hv16(3)) {
+        small_end = small_end_knob == 2 ? (takes_hv16(2) ? 2 : 0) : (small_end_knob == 1 ? 1 : 0);
+    }
+    auto launch_small_end = [&](uint32_t l) {   // the up-pass of level l (3: depth 1; 2: depth 2) into chain B
+        const int tiles_x = (int)((W(l) + 63) / 64), tiles = tiles_x * (int)((H(l) + 15) / 16);
+        if (l == 3) hipLaunchKernelGGL(k_bloom_small_end<1>, dim3(tiles), dim3(small_end::NT), 0, ctx->stream, (const pbr_half*)(v[0].A + off(3)), (int)W(3), (int)H(3),
+                                       (const pbr_half*)nullptr, v[0].B + off(3), (int)W(3), (int)H(3), tiles_x);
+        else hipLaunchKernelGGL(k_bloom_small_end<2>, dim3(tiles), dim3(small_end::NT), 0, ctx->stream, (const pbr_half*)(v[0].A + off(3)), (int)W(3), (int)H(3),
+                                (const pbr_half*)(v[0].A + off(2)), v[0].B + off(2), (int)W(2), (int)H(2), tiles_x);
+        return launched(ctx, l == 3 ? "k_bloom_small_end/1" : "k_bloom_small_end/2");
+    };
     for (uint32_t k = 0; k < PBR_BLOOM_STEP; k++) {   // downsample
         const uint32_t up = k + 1, lo = k + 2;
+        if (small_end && lo == PBR_BLOOM_MIPS - 1) break;   // level 4 is computed where it is used
         if (exact(up)) {
             const LevelViews lv = level_views(n, [&](uint32_t i) { return LevelIO{v[i].A + off(up), nullptr, v[i].A + off(lo), (int)W(lo), nullptr}; });
             if ((r = launch_hv<M_DOWN, false, 0, MV>(ctx, lv, n, W(up), H(up), W(lo), H(lo), nullptr, 0.0f, 0.0f))) return r;
@@ -1173,7 +1363,10 @@ static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint3
     auto res = [&](uint32_t i) { return (const pbr_half*)(res_in_b ? v[i].B : v[i].A) + off(res_level); };
     for (int k = PBR_BLOOM_STEP - 1; k >= 0; k--) {   // upsample: V(H(lower) + H(upper))
         const uint32_t up = (uint32_t)k + 1;
-        if (exact(up)) {
+        if (small_end && up + (uint32_t)small_end >= PBR_BLOOM_MIPS - 1) {   // depth 1: level 3; depth 2: level 3 (nothing to launch) and level 2
+            if (up + (uint32_t)small_end == PBR_BLOOM_MIPS - 1 && (r = launch_small_end(up))) return r;
+            res_in_b = true;
+        } else if (exact(up)) {
             const LevelViews lv = level_views(n, [&](uint32_t i) { return LevelIO{res(i), v[i].A + off(up), v[i].B + off(up), (int)W(up), nullptr}; });
             if ((r = launch_hv<M_UP, true, 0, MV>(ctx, lv, n, W(up + 1), H(up + 1), W(up), H(up), nullptr, 0.0f, 0.0f,
                                                   use_need ? need[up] : nullptr))) return r;
