@@ -6,7 +6,7 @@ symbol cannot be resolved this module raises — it never substitutes another im
 import ctypes as C
 import os
 
-from .structs import Aabb, CubeBc6h, CubeF32, DepthRasterDesc, FxaaImage, GBuffer, Global, HaloPeer, RasterDesc, ShadeDesc, ShadeTables, SunDesc, Tile, View
+from .structs import Aabb, BloomDesc, BloomPrefilterDesc, CubeBc6h, CubeF32, DepthRasterDesc, FxaaImage, GBuffer, Global, HaloPeer, RasterDesc, ShadeDesc, ShadeTables, SunDesc, Tile, View
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB", os.path.join(_HERE, "libpbr_hip.so"))   # override = experiments only
@@ -72,17 +72,13 @@ SIGNATURES = {
     "pbr_gbuffer_raster_textured_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_gbuffer_raster_textured_min_scratch_bytes": (_sz, [_u32, _u32, _u32]),
     "pbr_draw_bounds": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp]),
-    "pbr_bloom_prefilter": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _f32, _f32]),
+    "pbr_bloom_prefilter": (_int, [_vp, C.POINTER(BloomPrefilterDesc)]),
     "pbr_blur_h": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),
     "pbr_blur_v": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),
     "pbr_bloom_upsample_add": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp]),
     "pbr_bloom_up_level": (_int, [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32]),
     "pbr_bloom_merge": (_int, [_vp, _vp, _u32, _vp, _u32, _u32]),
-    "pbr_bloom": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _f32, _f32]),
-    "pbr_bloom_prefilter_rect": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _u32, _u32, C.POINTER(_u32 * 4), _f32, _f32]),
-    "pbr_bloom_prefilter_rects": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _u32, _u32, _vp, _u32, _f32, _f32]),
-    "pbr_bloom_tiled": (_int, [_vp, _vp, _u32, C.POINTER(_u32 * 4), _u32, _u32, _vp, _vp, C.POINTER(_u32 * 4), _f32, _f32, _vp]),
-    "pbr_bloom_histogram": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _f32, _f32, C.POINTER(_u32 * 4), _f32, _f32, _vp]),
+    "pbr_bloom": (_int, [_vp, C.POINTER(BloomDesc)]),
     "pbr_lum_histogram": (_int, [_vp, _vp, _u32, _u32, _u32, _f32, _f32, _vp]),
     "pbr_lum_average": (_int, [_vp, _vp, _u32, _f32, _f32, _f32, _vp]),
     "pbr_tonemap": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32]),

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .structs import (Aabb, DepthRasterDesc, RasterDesc, ShadeDesc, ShadeTables, Sun, SunDesc, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
+from .structs import (Aabb, BloomDesc, BloomPrefilterDesc, DepthRasterDesc, RasterDesc, ShadeDesc, ShadeTables, Sun, SunDesc, Texture2D, BLOOM_KNEE, BLOOM_THRESHOLD, CLUSTER_DTYPE, ENV_MIPS, HISTOGRAM_BINS,
                       INV_LOG_LUMINANCE_RANGE, LIGHT_DTYPE, LOG_LUMINANCE_RANGE, MIN_LOG_LUMINANCE,
                       NUM_CLUSTERS, AABB_DTYPE, CullStats, DRAW_DTYPE, DRAW_MAPS_DTYPE, BC6H_ENCODE_TWO_REGION, BC6H_MAX_SIZE, EQUIRECT_SRC_RGBE, TEX_BC1_BLOCKS, TEX_FORMATS, VERTEX_DTYPE, CubeBc6h, CubeF32, FxaaImage, GBuffer, Global, HaloPeer, Tile, View, bloom_chain_texels, bc6h_chain_bytes, cube_texels, env_padded_texels, equirect_default_samples, equirect_default_size, texture2d_bytes)
 
@@ -600,8 +600,15 @@ class PbrContext:
                             pitch, scratch, scratch_bytes, maps=_some("maps", maps), textures=textures, bounds=_some("bounds", bounds),
                             stats=stats)
 
+    def _bloom_prefilter(self, hdr, w, h, pitch, out, threshold, knee, out_pitch=0, out_x=0, out_y=0, rects=None):
+        """ONE pbr_bloom_prefilter call of a BloomPrefilterDesc; the rectangle array lives until it returns"""
+        arr = self._rects(rects) if rects is not None else None
+        d = BloomPrefilterDesc(_ptr(hdr), _ptr(out), C.addressof(arr) if arr is not None else None, int(w), int(h), int(pitch),
+                               int(out_pitch), int(out_x), int(out_y), len(arr) if arr is not None else 0, float(threshold), float(knee))
+        self._check(self.lib.pbr_bloom_prefilter(self.h, C.byref(d)))
+
     def bloom_prefilter(self, hdr, w, h, pitch, out, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE):
-        self._check(self.lib.pbr_bloom_prefilter(self.h, _ptr(hdr), w, h, pitch, _ptr(out), threshold, knee))
+        self._bloom_prefilter(hdr, w, h, pitch, out, threshold, knee)
 
     def blur_h(self, src, iw, ih, out, ow, oh):
         self._check(self.lib.pbr_blur_h(self.h, _ptr(src), iw, ih, _ptr(out), ow, oh))
@@ -622,34 +629,33 @@ class PbrContext:
     def alloc_bloom_chain(self, w, h):
         return self.zeros((bloom_chain_texels(w, h), 4), torch.float16)
 
+    def _bloom(self, hdr, w, h, hdr_pitch, chain_a, chain_b, threshold=0.0, knee=0.0, hdr_rect=None, merge_rect=None, hist_rect=None, hist=None,
+               min_log=0.0, inv_range=0.0):
+        """ONE pbr_bloom call of a BloomDesc; the rectangle arrays live until it returns"""
+        rects = [self._rects([r]) if r is not None else None for r in (hdr_rect, merge_rect, hist_rect)]
+        d = BloomDesc(_ptr(hdr), _ptr(chain_a), _ptr(chain_b), _ptr(hist), *[C.addressof(r) if r is not None else None for r in rects],
+                      int(w), int(h), int(hdr_pitch), float(threshold), float(knee), float(min_log), float(inv_range))
+        self._check(self.lib.pbr_bloom(self.h, C.byref(d)))
+
     def bloom(self, hdr, w, h, pitch, chain_a, chain_b, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE):
-        self._check(self.lib.pbr_bloom(self.h, _ptr(hdr), w, h, pitch, _ptr(chain_a), _ptr(chain_b), threshold, knee))
+        self._bloom(hdr, w, h, pitch, chain_a, chain_b, threshold, knee)
 
     def bloom_histogram(self, hdr, w, h, pitch, chain_a, chain_b, rect, hist, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE,
                         min_log=MIN_LOG_LUMINANCE, inv_range=INV_LOG_LUMINANCE_RANGE):
         """bloom + luminance histogram of rect=(x,y,w,h) in one pass (adds into hist)."""
-        r = (C.c_uint32 * 4)(*[int(v) for v in rect])
-        self._check(self.lib.pbr_bloom_histogram(self.h, _ptr(hdr), w, h, pitch, _ptr(chain_a), _ptr(chain_b), threshold, knee,
-                                                 C.byref(r), min_log, inv_range, _ptr(hist)))
+        self._bloom(hdr, w, h, pitch, chain_a, chain_b, threshold, knee, hist_rect=rect, hist=hist, min_log=min_log, inv_range=inv_range)
 
     def bloom_prefilter_rect(self, hdr, w, h, pitch, out, out_pitch, out_x, out_y, rect, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE):
         """bloom_prefilter on the half-res outputs rect=(x,y,w,h) of the image, stored at (out_x + x, out_y + y) of `out`."""
-        r = (C.c_uint32 * 4)(*[int(v) for v in rect])
-        self._check(self.lib.pbr_bloom_prefilter_rect(self.h, _ptr(hdr), w, h, pitch, _ptr(out), out_pitch, out_x, out_y,
-                                                      C.byref(r), threshold, knee))
+        self._bloom_prefilter(hdr, w, h, pitch, out, threshold, knee, out_pitch, out_x, out_y, [rect])
 
     def bloom_prefilter_rects(self, hdr, w, h, pitch, out, out_pitch, out_x, out_y, rects, threshold=BLOOM_THRESHOLD, knee=BLOOM_KNEE):
-        arr = self._rects(rects)
-        self._check(self.lib.pbr_bloom_prefilter_rects(self.h, _ptr(hdr), w, h, pitch, _ptr(out), out_pitch, out_x, out_y,
-                                                       C.cast(arr, C.c_void_p), len(rects), threshold, knee))
+        self._bloom_prefilter(hdr, w, h, pitch, out, threshold, knee, out_pitch, out_x, out_y, rects)
 
     def bloom_tiled(self, hdr, hdr_pitch, hdr_rect, ew, eh, chain_a, chain_b, merge_rect, hist=None,
                     min_log=MIN_LOG_LUMINANCE, inv_range=INV_LOG_LUMINANCE_RANGE):
         """Bloom levels 1..4 on the extended tile (level 1 of chain_a already complete) + merge/histogram of merge_rect."""
-        hr = (C.c_uint32 * 4)(*[int(v) for v in hdr_rect])
-        mr = (C.c_uint32 * 4)(*[int(v) for v in merge_rect])
-        self._check(self.lib.pbr_bloom_tiled(self.h, _ptr(hdr), hdr_pitch, C.byref(hr), ew, eh, _ptr(chain_a), _ptr(chain_b),
-                                             C.byref(mr), min_log, inv_range, _ptr(hist)))
+        self._bloom(hdr, ew, eh, hdr_pitch, chain_a, chain_b, hdr_rect=hdr_rect, merge_rect=merge_rect, hist=hist, min_log=min_log, inv_range=inv_range)
 
     def lum_histogram(self, hdr, w, h, pitch, hist, min_log=MIN_LOG_LUMINANCE, inv_range=INV_LOG_LUMINANCE_RANGE):
         self._check(self.lib.pbr_lum_histogram(self.h, _ptr(hdr), w, h, pitch, min_log, inv_range, _ptr(hist)))

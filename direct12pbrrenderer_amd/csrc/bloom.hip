@@ -1050,6 +1050,18 @@ static TileGrid tile_grid(const TailRect& tr, int tw, int th) {
     return TileGrid{tx0, ty0, tiles_x, tiles_x * ((tr.my1 + th - 1) / th - ty0)};
 }
 
+// The kernel choice of a fused level, from the tiles of its merge rect.  2x-up levels big enough to fill the chip with 128 x 32 tiles:
+// k_blur_up_poly.  Else k_blur_hv: 64 x 32 tiles when the level fills the chip that way; 64 x 16 below, where a level is latency-bound
+// (one tile's dependent chain + the launch) and 3 H rows per wave, 2 outputs per thread shorten the chain.  Whether the polyphase
+// kernel is taken never, by that size or always is the caller's: launch_hv and bloom_pass read PBR_BLOOM_WIDE=0|1 differently.
+enum LevelKernel { K_POLY, K_HV32, K_HV16 };
+enum PolyRule { POLY_NEVER, POLY_BY_SIZE, POLY_ALWAYS };
+static LevelKernel level_kernel(const TailRect& tr, PolyRule poly) {
+    if (poly == POLY_ALWAYS || (poly == POLY_BY_SIZE && tile_grid(tr, 128, 32).n >= 400)) return K_POLY;
+    return tile_grid(tr, 64, 32).n >= 900 ? K_HV32 : K_HV16;
+}
+static int wide_forced() { static const int v = pbr::knob_int("PBR_BLOOM_WIDE", -1); return v; }
+
 // One fused level (k_blur_hv / k_blur_up_poly) of nv views.  lv holds each view's input, second input (DUAL), output, output pitch and
 // histogram.  MV = false: one view, the single-view kernel with view 0's pointers as its own arguments; MV: the view-table instance,
 // grid (blocks, nv), whose kernel choice is the one a single view of the level gets.  The rectangles: see tail_rect.
@@ -1073,17 +1085,14 @@ static pbr_status launch_hv(pbr_ctx* ctx, const LevelViews& lv, uint32_t nv, uin
                            MV ? 0 : lv.out_pitch[0], g.tiles_x, g.n, tr, min_log, inv_range, vs, MV ? nullptr : lv.hist[0]);
         return launched(ctx, label);
     };
-    // The kernel choice.  2x-up levels big enough to fill the chip with 128 x 32 tiles: k_blur_up_poly (PBR_BLOOM_WIDE=0|1 forces).
-    // Else k_blur_hv: 64 x 32 tiles when the level fills the chip that way; 64 x 16 below, where a level is latency-bound (one tile's
-    // dependent chain + the launch) and 3 H rows per wave, 2 outputs per thread shorten the chain.
-    if constexpr (MODE == M_UP) {
-        static const int wide_forced = pbr::knob_int("PBR_BLOOM_WIDE", -1);
-        const TileGrid wide = tile_grid(tr, 128, 32);
-        if (wide_forced >= 0 ? wide_forced == 1 : (wide.n >= 400 && !ctx->bloom_shader_order))
-            return launch(k_blur_up_poly<DUAL, TAIL, 32, VS>, wide, MV ? "k_blur_up_poly<views>" : "k_blur_up_poly");
-    }
-    const TileGrid tall = tile_grid(tr, 64, 32);
-    if (tall.n >= 900) return launch(k_blur_hv<MODE, DUAL, TAIL, 32, 512, VS>, tall, MV ? "k_blur_hv/32<views>" : "k_blur_hv/32");
+    // The kernel choice (level_kernel).  Only 2x-up levels have a polyphase kernel; PBR_BLOOM_WIDE=0|1 forces it off or on, and the
+    // shader-order switch turns it off.
+    const PolyRule poly = MODE != M_UP ? POLY_NEVER : wide_forced() >= 0 ? (wide_forced() == 1 ? POLY_ALWAYS : POLY_NEVER)
+                        : ctx->bloom_shader_order ? POLY_NEVER : POLY_BY_SIZE;
+    const LevelKernel k = level_kernel(tr, poly);
+    if constexpr (MODE == M_UP)
+        if (k == K_POLY) return launch(k_blur_up_poly<DUAL, TAIL, 32, VS>, tile_grid(tr, 128, 32), MV ? "k_blur_up_poly<views>" : "k_blur_up_poly");
+    if (k == K_HV32) return launch(k_blur_hv<MODE, DUAL, TAIL, 32, 512, VS>, tile_grid(tr, 64, 32), MV ? "k_blur_hv/32<views>" : "k_blur_hv/32");
     return launch(k_blur_hv<MODE, DUAL, TAIL, 16, 512, VS>, tile_grid(tr, 64, 16), MV ? "k_blur_hv/16<views>" : "k_blur_hv/16");
 }
 
@@ -1133,67 +1142,42 @@ static pbr_status prefilter_launch(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w
     return PBR_OK;
 }
 
-// ---- checks that several entry points share: what is wrong (nullptr: nothing); the caller refuses under its own name (PBR_CHECK)
-// prefilter: the image has a half-res texel, sides <= 65535, pitch >= w
-static const char* prefilter_image_fault(uint32_t w, uint32_t h, uint32_t pitch) {
-    return (w >> 1) >= 1 && (h >> 1) >= 1 && w <= 65535 && h <= 65535 && pitch >= w ? nullptr : "bad size";
-}
+// ---- checks with more than one reason, or more than one caller: what is wrong (nullptr: nothing); the caller refuses under its own name (PBR_CHECK)
 // prefilter: output rectangle q = {x, y, w, h} inside the half-res image, and inside the destination's pitch when placed at column out_x
 static const char* prefilter_rect_fault(const uint32_t q[4], uint32_t w, uint32_t h, uint32_t out_x, uint32_t out_pitch) {
     if (!(q[2] >= 1 && q[3] >= 1 && q[0] + q[2] <= (w >> 1) && q[1] + q[3] <= (h >> 1))) return "rect outside the half-res image";
     return out_pitch >= out_x + q[0] + q[2] ? nullptr : "rect does not fit the output pitch";
 }
-static bool prefilter_dest_ok(uint32_t out_pitch, uint32_t out_y) { return out_pitch <= 65535 && out_y <= 65535; }
 // chain: every one of the five mips >= 1 texel (BloomStep < CalculateMaxMipLevels, DeferredPipeline.cpp:343), sides <= 65535, pitch >= w
 static const char* chain_size_fault(uint32_t w, uint32_t h, uint32_t pitch) {
     if (!((w >> (PBR_BLOOM_MIPS - 1)) >= 1 && (h >> (PBR_BLOOM_MIPS - 1)) >= 1)) return "image too small for 5 mips";
     return w <= 65535 && h <= 65535 && pitch >= w ? nullptr : "bad size";
 }
 
-// the three prefilter entry points after their checks: n rectangles of the half-res image into out at (out_x, out_y)
-static pbr_status prefilter_rects(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch, pbr_half* out, uint32_t out_pitch,
-                                  uint32_t out_x, uint32_t out_y, const uint32_t (*rects)[4], uint32_t n_rects, float threshold, float knee) {
-    OutRect rcs[PF_MAX_RECTS];
-    for (uint32_t r = 0; r < n_rects; r++) {
-        const uint32_t* q = rects[r];
-        rcs[r] = OutRect{(int)q[0], (int)q[1], (int)(q[0] + q[2]), (int)(q[1] + q[3]), (int)out_x, (int)out_y, (int)out_pitch};
-    }
-    return prefilter_launch(ctx, hdr, w, h, pitch, out, rcs, (int)n_rects, threshold, knee);
-}
-
 // ---------------------------------------------------------------- C ABI: the staged passes
 extern "C" {
 
-pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
-                               pbr_half* out, float threshold, float knee) {
+pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_bloom_prefilter_desc* d) {
     if (!ctx) return PBR_ERR_INVALID;
-    PBR_REQUIRE(ctx, hdr && out, "pbr_bloom_prefilter: null pointer");
-    PBR_CHECK(ctx, "pbr_bloom_prefilter", prefilter_image_fault(w, h, pitch));
-    const uint32_t whole[4] = {0, 0, w >> 1, h >> 1};   // the whole image into a dense plane
-    return prefilter_rects(ctx, hdr, w, h, pitch, out, w >> 1, 0, 0, &whole, 1, threshold, knee);
-}
-
-pbr_status pbr_bloom_prefilter_rect(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
-                                    pbr_half* out, uint32_t out_pitch, uint32_t out_x, uint32_t out_y,
-                                    const uint32_t rect[4], float threshold, float knee) {
-    if (!ctx) return PBR_ERR_INVALID;
-    PBR_REQUIRE(ctx, hdr && out && rect, "pbr_bloom_prefilter_rect: null pointer");
-    PBR_CHECK(ctx, "pbr_bloom_prefilter_rect", prefilter_image_fault(w, h, pitch));
-    PBR_CHECK(ctx, "pbr_bloom_prefilter_rect", prefilter_rect_fault(rect, w, h, out_x, out_pitch));
-    PBR_REQUIRE(ctx, prefilter_dest_ok(out_pitch, out_y), "pbr_bloom_prefilter_rect: rect does not fit the output pitch");
-    return prefilter_rects(ctx, hdr, w, h, pitch, out, out_pitch, out_x, out_y, reinterpret_cast<const uint32_t (*)[4]>(rect), 1, threshold, knee);
-}
-
-pbr_status pbr_bloom_prefilter_rects(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
-                                     pbr_half* out, uint32_t out_pitch, uint32_t out_x, uint32_t out_y,
-                                     const uint32_t (*rects)[4], uint32_t n_rects, float threshold, float knee) {
-    if (!ctx) return PBR_ERR_INVALID;
-    PBR_REQUIRE(ctx, hdr && out && rects && n_rects >= 1 && n_rects <= (uint32_t)PF_MAX_RECTS, "pbr_bloom_prefilter_rects: null pointer / 1 .. 5 rectangles");
-    PBR_CHECK(ctx, "pbr_bloom_prefilter_rects", prefilter_image_fault(w, h, pitch));
-    PBR_REQUIRE(ctx, prefilter_dest_ok(out_pitch, out_y), "pbr_bloom_prefilter_rects: bad size");
-    for (uint32_t r = 0; r < n_rects; r++)
-        PBR_REQUIRE(ctx, !prefilter_rect_fault(rects[r], w, h, out_x, out_pitch), "pbr_bloom_prefilter_rects: rectangle outside the half-res image / the output pitch");
-    return prefilter_rects(ctx, hdr, w, h, pitch, out, out_pitch, out_x, out_y, rects, n_rects, threshold, knee);
+    PBR_REQUIRE(ctx, d, "pbr_bloom_prefilter: null descriptor");
+    PBR_REQUIRE(ctx, d->reserved == 0, "pbr_bloom_prefilter: reserved must be 0");
+    PBR_REQUIRE(ctx, d->hdr && d->out, "pbr_bloom_prefilter: null pointer");
+    // no rectangles: the whole half-res image into a dense plane, as the one rectangle it is
+    const uint32_t w = d->w, h = d->h, whole[1][4] = {{0, 0, w >> 1, h >> 1}};
+    const bool dense = !d->rects && d->n_rects == 0;
+    const uint32_t (*rects)[4] = dense ? whole : d->rects;
+    const uint32_t n = dense ? 1 : d->n_rects, out_pitch = dense ? w >> 1 : d->out_pitch;
+    PBR_REQUIRE(ctx, rects && n >= 1 && n <= (uint32_t)PF_MAX_RECTS, "pbr_bloom_prefilter: null pointer / 1 .. 5 rectangles");
+    PBR_REQUIRE(ctx, (w >> 1) >= 1 && (h >> 1) >= 1 && w <= 65535 && h <= 65535 && d->pitch >= w, "pbr_bloom_prefilter: bad size");
+    PBR_REQUIRE(ctx, !dense || (!d->out_pitch && !d->out_x && !d->out_y), "pbr_bloom_prefilter: out_pitch, out_x and out_y must be 0 without rects");
+    PBR_REQUIRE(ctx, out_pitch <= 65535 && d->out_y <= 65535, "pbr_bloom_prefilter: bad size");
+    OutRect rcs[PF_MAX_RECTS];
+    for (uint32_t r = 0; r < n; r++) {
+        const uint32_t* q = rects[r];
+        PBR_CHECK(ctx, "pbr_bloom_prefilter", prefilter_rect_fault(q, w, h, d->out_x, out_pitch));
+        rcs[r] = OutRect{(int)q[0], (int)q[1], (int)(q[0] + q[2]), (int)(q[1] + q[3]), (int)d->out_x, (int)d->out_y, (int)out_pitch};
+    }
+    return prefilter_launch(ctx, d->hdr, w, h, d->pitch, d->out, rcs, (int)n, d->threshold, d->knee);
 }
 
 pbr_status pbr_blur_h(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint32_t ih, pbr_half* out, uint32_t ow, uint32_t oh) {
@@ -1324,10 +1308,9 @@ static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint3
     // the down pass alone.  Chain A level 4 (and chain B level 3) are then not written.  The product takes depth 2 (the measured keep:
     // EXPERIMENTS.md), and today's launches where level 2 is large enough for another kernel.
     static const int small_end_knob = pbr::knob_int("PBR_BLOOM_SMALL_END", 2);
-    static const int wide_forced = pbr::knob_int("PBR_BLOOM_WIDE", -1);
-    auto takes_hv16 = [&](uint32_t l) {   // launch_hv's choice for the whole level, whatever the shader-order switch says
-        const TailRect whole = tail_rect(W(l), H(l), nullptr, nullptr, nullptr);
-        return wide_forced != 1 && tile_grid(whole, 128, 32).n < 400 && tile_grid(whole, 64, 32).n < 900;
+    // the whole level's kernel as shipped is k_blur_hv/16: whatever the shader-order switch says, and PBR_BLOOM_WIDE=0 counts as unset
+    auto takes_hv16 = [&](uint32_t l) {
+        return level_kernel(tail_rect(W(l), H(l), nullptr, nullptr, nullptr), wide_forced() == 1 ? POLY_ALWAYS : POLY_BY_SIZE) == K_HV16;
     };
     int small_end = 0;
     if (!MV && n == 1 && merge0 == nullptr && PBR_BLOOM_STEP == 3 && exact(1) && exact(2) && exact(3) && takes_hv16(3)) {
@@ -1397,35 +1380,41 @@ static pbr_status bloom_pass(pbr_ctx* ctx, const BloomView* v, uint32_t n, uint3
 // ---------------------------------------------------------------- C ABI: the chain
 extern "C" {
 
-// pbr_bloom and pbr_bloom_histogram (which therefore refuses a bad size under the name pbr_bloom)
-static pbr_status bloom_impl(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch, pbr_half* A, pbr_half* B,
-                             float threshold, float knee, const uint32_t* hist_rect, float min_log, float inv_range, uint32_t* hist256) {
-    PBR_REQUIRE(ctx, hdr && A && B, "pbr_bloom: null pointer");
-    PBR_CHECK(ctx, "pbr_bloom", chain_size_fault(w, h, pitch));
-    const BloomView v{hdr, pitch, A, B, hist256};
-    return bloom_pass<false>(ctx, &v, 1, w, h, true, threshold, knee, hist_rect, min_log, inv_range);
-}
-
-// BloomPass::Execute
-pbr_status pbr_bloom(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
-                     pbr_half* A, pbr_half* B, float threshold, float knee) {
+// Whole-image form (hdr_rect == NULL): BloomPass::Execute, with hist_rect + hist256 followed by AutoExposurePass::Execute's histogram
+// dispatch on hist_rect.  Tiled form, the multi-GPU halo path (SURVEY 8e option 2): BloomPass::Execute minus the prefilter on the
+// extended rectangle E (w x h) of a tile, merged (+ counted) inside merge_rect only; hdr covers hdr_rect of E (include/pbr_hip.h).
+pbr_status pbr_bloom(pbr_ctx* ctx, const pbr_bloom_desc* d) {
     if (!ctx) return PBR_ERR_INVALID;
-    return bloom_impl(ctx, hdr, w, h, pitch, A, B, threshold, knee, nullptr, 0.0f, 0.0f, nullptr);
+    PBR_REQUIRE(ctx, d, "pbr_bloom: null descriptor");
+    PBR_REQUIRE(ctx, d->reserved == 0, "pbr_bloom: reserved must be 0");
+    const BloomView v{d->hdr, d->hdr_pitch, d->chain_a, d->chain_b, d->hist256};
+    const uint32_t w = d->w, h = d->h;
+    if (!d->hdr_rect) {
+        const uint32_t* rect = d->hist_rect;
+        PBR_REQUIRE(ctx, !d->merge_rect, "pbr_bloom: merge_rect without hdr_rect");
+        PBR_REQUIRE(ctx, !rect || d->hist256, "pbr_bloom: hist_rect without hist256");
+        PBR_REQUIRE(ctx, rect || !d->hist256, "pbr_bloom: hist256 without hist_rect");
+        PBR_REQUIRE(ctx, !rect || (rect[2] >= 1 && rect[3] >= 1 && rect[0] + rect[2] <= w && rect[1] + rect[3] <= h), "pbr_bloom: rect outside the image");
+        PBR_REQUIRE(ctx, v.hdr && v.A && v.B, "pbr_bloom: null pointer");
+        PBR_CHECK(ctx, "pbr_bloom", chain_size_fault(w, h, v.pitch));
+        return bloom_pass<false>(ctx, &v, 1, w, h, true, d->threshold, d->knee, rect, d->min_log, d->inv_range);
+    }
+    const uint32_t *hdr_rect = d->hdr_rect, *merge_rect = d->merge_rect;
+    PBR_REQUIRE(ctx, !d->hist_rect, "pbr_bloom: hist_rect in the tiled form (the histogram counts merge_rect)");
+    PBR_REQUIRE(ctx, v.hdr && v.A && v.B && merge_rect, "pbr_bloom: null pointer");
+    PBR_REQUIRE(ctx, !chain_size_fault(w, h, w), "pbr_bloom: bad size");   // (the pitch is hdr_rect's: below)
+    PBR_REQUIRE(ctx, hdr_rect[2] >= 1 && hdr_rect[3] >= 1 && hdr_rect[0] + hdr_rect[2] <= w && hdr_rect[1] + hdr_rect[3] <= h && v.pitch >= hdr_rect[2],
+                "pbr_bloom: hdr_rect outside the extended tile");
+    PBR_REQUIRE(ctx, merge_rect[2] >= 1 && merge_rect[3] >= 1 && merge_rect[0] >= hdr_rect[0] && merge_rect[1] >= hdr_rect[1] &&
+                     merge_rect[0] + merge_rect[2] <= hdr_rect[0] + hdr_rect[2] && merge_rect[1] + merge_rect[3] <= hdr_rect[1] + hdr_rect[3],
+                "pbr_bloom: merge_rect outside hdr_rect");
+    if (!exact_half(w) || !exact_half(h))
+        return pbr::fail(ctx, PBR_ERR_UNSUPPORTED, "pbr_bloom: the extended tile must be even and <= 8192 on a side");
+    return bloom_pass<false>(ctx, &v, 1, w, h, false, 0.0f, 0.0f, merge_rect, d->min_log, d->inv_range, merge_rect, hdr_rect);
 }
 
-// BloomPass::Execute followed by the luminance-histogram dispatch of AutoExposurePass::Execute on the pixels of `rect` = {x, y, w, h}
-// of the bloomed image.
-pbr_status pbr_bloom_histogram(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
-                               pbr_half* A, pbr_half* B, float threshold, float knee,
-                               const uint32_t rect[4], float min_log, float inv_range, uint32_t* hist256) {
-    if (!ctx) return PBR_ERR_INVALID;
-    PBR_REQUIRE(ctx, rect && hist256, "pbr_bloom_histogram: null pointer");
-    PBR_REQUIRE(ctx, rect[2] >= 1 && rect[3] >= 1 && rect[0] + rect[2] <= w && rect[1] + rect[3] <= h, "pbr_bloom_histogram: rect outside the image");
-    return bloom_impl(ctx, hdr, w, h, pitch, A, B, threshold, knee, rect, min_log, inv_range, hist256);
-}
-
-// pbr_bloom_histogram for up to PBR_MAX_VIEWS whole frames of one size: every level takes the kernel a single view of that size takes
-// (bloom_pass); fused levels run all views in one launch, staged levels (not an exact half, e.g. 1920x1080 from level 3 down) run the
+// pbr_bloom's whole-image form with the whole-frame histogram, for up to PBR_MAX_VIEWS frames of one size: every level takes the kernel a
+// single view of that size takes (bloom_pass); fused levels run all views in one launch, staged levels (not an exact half, e.g. 1920x1080 from level 3 down) run the
 // single-view staged kernels once per view.
 pbr_status pbr_bloom_histogram_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h,
                                      float threshold, float knee, float min_log, float inv_range) {
@@ -1448,28 +1437,6 @@ pbr_status pbr_bloom_histogram_views(pbr_ctx* ctx, const pbr_view* views, uint32
                 "pbr_bloom_histogram_views: two views share an HDR target, a bloom chain or a histogram");
     const uint32_t rect[4] = {0, 0, w, h};
     return bloom_pass<true>(ctx, bv, n, w, h, true, threshold, knee, rect, min_log, inv_range);
-}
-
-// Multi-GPU halo path (SURVEY 8e option 2): BloomPass::Execute minus the prefilter, on the extended rectangle E
-// (ew x eh) of a tile whose level 1 (chain A) is already filled — the interior by pbr_bloom_prefilter_rect, the
-// rest by the neighbours' level 1 — and with the final merge (+ histogram) restricted to merge_rect, the part of E
-// this rank owns.  hdr covers hdr_rect = {x, y, w, h} of E only (hdr[0] = texel (x, y), pitch hdr_pitch).
-pbr_status pbr_bloom_tiled(pbr_ctx* ctx, pbr_half* hdr, uint32_t hdr_pitch, const uint32_t hdr_rect[4],
-                           uint32_t ew, uint32_t eh, pbr_half* A, pbr_half* B, const uint32_t merge_rect[4],
-                           float min_log, float inv_range, uint32_t* hist256) {
-    if (!ctx) return PBR_ERR_INVALID;
-    PBR_REQUIRE(ctx, hdr && hdr_rect && A && B && merge_rect, "pbr_bloom_tiled: null pointer");
-    PBR_REQUIRE(ctx, !chain_size_fault(ew, eh, ew), "pbr_bloom_tiled: bad size");   // (the pitch is hdr_rect's: below)
-    PBR_REQUIRE(ctx, hdr_rect[2] >= 1 && hdr_rect[3] >= 1 && hdr_rect[0] + hdr_rect[2] <= ew && hdr_rect[1] + hdr_rect[3] <= eh && hdr_pitch >= hdr_rect[2],
-                "pbr_bloom_tiled: hdr_rect outside the extended tile");
-    PBR_REQUIRE(ctx, merge_rect[2] >= 1 && merge_rect[3] >= 1 && merge_rect[0] >= hdr_rect[0] && merge_rect[1] >= hdr_rect[1] &&
-                     merge_rect[0] + merge_rect[2] <= hdr_rect[0] + hdr_rect[2] && merge_rect[1] + merge_rect[3] <= hdr_rect[1] + hdr_rect[3],
-                "pbr_bloom_tiled: merge_rect outside hdr_rect");
-    if (!exact_half(ew) || !exact_half(eh))
-        return pbr::fail(ctx, PBR_ERR_UNSUPPORTED, "pbr_bloom_tiled: the extended tile must be even and <= 8192 on a side");
-    const BloomView v{hdr, hdr_pitch, A, B, hist256};
-    const uint32_t origin[2] = {hdr_rect[0], hdr_rect[1]};
-    return bloom_pass<false>(ctx, &v, 1, ew, eh, false, 0.0f, 0.0f, merge_rect, min_log, inv_range, merge_rect, origin);
 }
 
 }  // extern "C"

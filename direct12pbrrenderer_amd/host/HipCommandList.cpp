@@ -308,7 +308,8 @@ void HipCommandList::Dispatch(ShadingState* s, uint32 gx, uint32 gy, uint32 gz) 
         // the reference sizes this grid by the FULL resolution (quirk Q9); the kernel covers the half-res output
         ExpectGroups(f, gx, gy, gz, Groups(in.w, 16), Groups(in.h, 16), 1);
         if (out.w != (in.w >> 1) || out.h != (in.h >> 1)) throw HipException("bloom_prefilter: output is not the half-res mip");
-        Check(pbr_bloom_prefilter(mCtx, in.ptr, in.w, in.h, in.w, out.ptr, c.Threshold, c.Knee), "pbr_bloom_prefilter");
+        const pbr_bloom_prefilter_desc d{in.ptr, out.ptr, nullptr, in.w, in.h, in.w, 0, 0, 0, 0, c.Threshold, c.Knee, 0};   // no rectangles: the whole mip
+        Check(pbr_bloom_prefilter(mCtx, &d), "pbr_bloom_prefilter");
     } else if (f == "blur_horizontal.hlsl" || f == "blur_vertical.hlsl") {
         Mip in = MipOf(s->Texture("InputTexture")), out = MipOf(s->RWTexture("OutputTexture"));
         (void)s->Constants<BlurConstant>();   // TexelSize = 1/output size; recomputed identically inside the C ABI
@@ -338,7 +339,7 @@ void HipCommandList::Dispatch(ShadingState* s, uint32 gx, uint32 gy, uint32 gz) 
         if (r.x + r.w > in.w || r.y + r.h > in.h || c.TextureWidth != r.w || c.TextureHeight != r.h)
             throw HipException("hdr_luminance_histogram: TextureWidth/Height must be the interior rectangle's size");
         const TextureBinding& lum = s->Texture("LuminanceTexture");
-        if (mPendingBloom.What != PendingBloom::None && lum.Texture == mPendingBloom.Hdr && lum.MipSlice <= 0) {
+        if (mPendingBloom.Hdr && lum.Texture == mPendingBloom.Hdr && lum.MipSlice <= 0) {
             // the bloom held back by Bloom / BloomHalo wrote this very texture: count the histogram in its last kernel
             FlushPendingBloom(hist, c.MinLogLuminance, c.InvLogLuminanceRange);
         } else {
@@ -477,6 +478,14 @@ void HipCommandList::StaleShadeTables(const DeviceStructuredBuffer* clusters) {
     if (t != mShadeTables.end()) t->second.desc.built &= ~PBR_TABLES_BUILT_FRAME;
 }
 
+// what both forms of pbr_bloom take: the target and its pitch, the two chains, the pyramid's size (w x h)
+static pbr_bloom_desc BloomDesc(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain, DeviceTexture2D* temp, uint32 w, uint32 h) {
+    pbr_bloom_desc d{};
+    d.hdr = (pbr_half*)hdr->DevicePtr(); d.hdr_pitch = hdr->Width(); d.w = w; d.h = h;
+    d.chain_a = (pbr_half*)mip_chain->DevicePtr(); d.chain_b = (pbr_half*)temp->DevicePtr();
+    return d;
+}
+
 void HipCommandList::Bloom(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain, DeviceTexture2D* temp, float threshold, float knee) {
     if (!hdr || !mip_chain || !temp) throw HipException("Bloom: null texture");
     if (mip_chain->Width() != hdr->Width() || mip_chain->Height() != hdr->Height() || temp->Width() != hdr->Width() || temp->Height() != hdr->Height())
@@ -484,33 +493,22 @@ void HipCommandList::Bloom(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain, Dev
     mDispatchCount++;
     FlushPendingBloom();
     if (mTailOverlap == 2) BeginTail();
-    mPendingBloom = PendingBloom{PendingBloom::Whole, hdr, mip_chain, temp, threshold, knee};
+    mPendingBloom = PendingBloom{hdr, BloomDesc(hdr, mip_chain, temp, hdr->Width(), hdr->Height())};
+    mPendingBloom.Desc.threshold = threshold; mPendingBloom.Desc.knee = knee;
     if (!mFusedPasses) FlushPendingBloom();
 }
 
 void HipCommandList::FlushPendingBloom(uint32_t* hist, float min_log, float inv_range) {
-    const PendingBloom p = mPendingBloom;
+    PendingBloom p = mPendingBloom;
     mPendingBloom = PendingBloom{};
-    if (p.What == PendingBloom::Whole) {
-        pbr_half *hdr = (pbr_half*)p.Hdr->DevicePtr(), *a = (pbr_half*)p.MipChain->DevicePtr(), *b = (pbr_half*)p.Temp->DevicePtr();
-        const uint32 w = p.Hdr->Width(), h = p.Hdr->Height();
-        if (hist) {
-            const Rect r = mInterior.w ? mInterior : Rect{0, 0, w, h};
-            const uint32_t rect[4] = {r.x, r.y, r.w, r.h};
-            Check(pbr_bloom_histogram(mCtx, hdr, w, h, w, a, b, p.Threshold, p.Knee, rect, min_log, inv_range, hist), "pbr_bloom_histogram");
-        } else {
-            Check(pbr_bloom(mCtx, hdr, w, h, w, a, b, p.Threshold, p.Knee), "pbr_bloom");
-        }
-    } else if (p.What == PendingBloom::Tiled) {
-        IssueBloomTiled(p.Hdr, p.MipChain, p.Temp, hist, min_log, inv_range);
-    }
-}
-
-void HipCommandList::IssueBloomTiled(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain, DeviceTexture2D* temp, uint32_t* hist, float min_log, float inv_range) {
-    const PixelRect s = mLayout.ShadedInBloom(), i = mLayout.InteriorInBloom();
-    const uint32_t hdr_rect[4] = {s.x, s.y, s.w, s.h}, merge_rect[4] = {i.x, i.y, i.w, i.h};
-    Check(pbr_bloom_tiled(mCtx, (pbr_half*)hdr->DevicePtr(), hdr->Width(), hdr_rect, mLayout.Bloom.w, mLayout.Bloom.h, (pbr_half*)mip_chain->DevicePtr(),
-                          (pbr_half*)temp->DevicePtr(), merge_rect, min_log, inv_range, hist), "pbr_bloom_tiled");
+    if (!p.Hdr) return;
+    pbr_bloom_desc& d = p.Desc;
+    const Rect r = mInterior.w ? mInterior : Rect{0, 0, d.w, d.h};
+    const uint32_t interior[4] = {r.x, r.y, r.w, r.h};
+    if (p.Tiled) { d.hdr_rect = p.HdrRect; d.merge_rect = p.MergeRect; }   // (the histogram counts merge_rect)
+    else if (hist) d.hist_rect = interior;
+    d.hist256 = hist; d.min_log = min_log; d.inv_range = inv_range;
+    Check(pbr_bloom(mCtx, &d), "pbr_bloom");
 }
 
 void HipCommandList::HaloExchange(DeviceTexture2D* mip_chain) {
@@ -538,12 +536,13 @@ void HipCommandList::BloomHalo(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain,
     mDispatchCount++;
     FlushPendingBloom();
     // level-1 texels of the interior, written into the level-1 plane of E
-    const PixelRect s = l.ShadedInBloom(), i = l.InteriorInShaded();
-    const uint32_t rect[4] = {i.x / 2, i.y / 2, i.w / 2, i.h / 2};
-    Check(pbr_bloom_prefilter_rect(mCtx, (pbr_half*)hdr->DevicePtr(), hdr->Width(), hdr->Height(), hdr->Width(), (pbr_half*)mip_chain->MipPtr(1),
-                                   l.Bloom.w / 2, s.x / 2, s.y / 2, rect, threshold, knee), "pbr_bloom_prefilter_rect");
+    const PixelRect s = l.ShadedInBloom(), i = l.InteriorInShaded(), m = l.InteriorInBloom();
+    const uint32_t rect[1][4] = {{i.x / 2, i.y / 2, i.w / 2, i.h / 2}};
+    const pbr_bloom_prefilter_desc pf{(pbr_half*)hdr->DevicePtr(), (pbr_half*)mip_chain->MipPtr(1), rect, hdr->Width(), hdr->Height(), hdr->Width(),
+                                      l.Bloom.w / 2, s.x / 2, s.y / 2, 1, threshold, knee, 0};   // (out: pitch, x, y; one rectangle)
+    Check(pbr_bloom_prefilter(mCtx, &pf), "pbr_bloom_prefilter");
     HaloExchange(mip_chain);
-    mPendingBloom = PendingBloom{PendingBloom::Tiled, hdr, mip_chain, temp, threshold, knee};
+    mPendingBloom = PendingBloom{hdr, BloomDesc(hdr, mip_chain, temp, l.Bloom.w, l.Bloom.h), true, {s.x, s.y, s.w, s.h}, {m.x, m.y, m.w, m.h}};
     if (!mFusedPasses) FlushPendingBloom();
 }
 

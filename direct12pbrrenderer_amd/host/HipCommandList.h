@@ -123,12 +123,12 @@ public:
     void Clustered(DeviceStructuredBuffer* clusters, DeviceStructuredBuffer* point_lights, int32 num_lights);
     // BloomPass::Execute's sixteen dispatches (pbr_bloom); mip_chain / temp are scratch afterwards.  With fused passes the
     // call is held back until the next command: when that is the luminance histogram of the same texture, both become ONE
-    // pbr_bloom_histogram (the histogram is counted by the bloom's last kernel: one full read of the HDR target saved) —
-    // a command list is free to merge adjacent commands as long as every consumer sees the same results.
+    // pbr_bloom with its histogram fields set (the histogram is counted by the bloom's last kernel: one full read of the HDR target
+    // saved) — a command list is free to merge adjacent commands as long as every consumer sees the same results.
     void Bloom(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain, DeviceTexture2D* temp, float threshold, float knee);
     // Halo mode (SURVEY 8e option 2) — what BloomPass::Execute issues on a tile whose bloom pyramid runs on the extended
-    // rectangle E: level-1 texels of the interior (pbr_bloom_prefilter_rect) -> the rest of E's level 1 from the neighbours
-    // (HaloExchange) -> levels 1..4 on E and the merge into the interior (pbr_bloom_tiled; held back like Bloom when fused).
+    // rectangle E: level-1 texels of the interior (pbr_bloom_prefilter with one rectangle) -> the rest of E's level 1 from the neighbours
+    // (HaloExchange) -> levels 1..4 on E and the merge into the interior (pbr_bloom's tiled form; held back like Bloom when fused).
     // hdr covers S; mip_chain / temp are E-sized.
     void BloomHalo(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain, DeviceTexture2D* temp, float threshold, float knee);
 
@@ -148,17 +148,18 @@ public:
 private:
     void Check(pbr_status st, const char* what);
     void HaloExchange(DeviceTexture2D* mip_chain);
-    // the bloom call held back by Bloom / BloomHalo: issued with the histogram (hist != nullptr) or on its own
+    // the pbr_bloom call held back by Bloom / BloomHalo (Hdr: the texture it writes; nullptr: none), issued with the histogram
+    // (hist != nullptr) or on its own.  Tiled: HdrRect and MergeRect are the descriptor's; its rectangle pointers are set where it is issued
     struct PendingBloom {
-        enum Kind { None, Whole, Tiled } What = None;
-        DeviceTexture2D *Hdr = nullptr, *MipChain = nullptr, *Temp = nullptr;
-        float Threshold = 0, Knee = 0;
+        DeviceTexture2D* Hdr = nullptr;
+        pbr_bloom_desc Desc{};
+        bool Tiled = false;
+        uint32_t HdrRect[4] = {}, MergeRect[4] = {};
     };
     // the one pbr_gbuffer_raster call of RasterGBuffer and RasterShadowMap: camera, tile, planes and pitch into d
     void Raster(pbr_raster_desc& d, const pbr_global* g, const pbr_tile& tile, uint32_t* a, uint32_t* b, uint32_t* c, DeviceTexture2D* ds,
                 const char* what);
     void FlushPendingBloom(uint32_t* hist = nullptr, float min_log = 0.0f, float inv_range = 0.0f);
-    void IssueBloomTiled(DeviceTexture2D* hdr, DeviceTexture2D* mip_chain, DeviceTexture2D* temp, uint32_t* hist, float min_log, float inv_range);
 
     pbr_ctx* mCtx = nullptr;
     ConstantBufferGlobal mGlobal{};

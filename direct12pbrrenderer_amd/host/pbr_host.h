@@ -18,7 +18,7 @@ pbrh_renderer* pbrh_create(int hip_device, uint32_t width, uint32_t height, uint
  * average divides by the full frame's pixel count.  halo = 0 (apron mode): the device shades interior + 256 px and blooms
  * that.  halo = 1: it shades interior + 4 px; BloomPass::Execute computes the interior's half-res level, receives the rest
  * of the extended rectangle's half-res level from the neighbouring devices (pbr_halo_exchange over the communicator of
- * pbrh_comm_init) and runs the pyramid on the extended rectangle (pbr_bloom_tiled). */
+ * pbrh_comm_init) and runs the pyramid on the extended rectangle (pbr_bloom's tiled form). */
 pbrh_renderer* pbrh_create_tile(int hip_device, uint32_t full_w, uint32_t full_h, uint32_t cols, uint32_t rows, uint32_t rank, int halo,
                                 uint32_t env_size, uint32_t lut_res, char* err, size_t err_len);
 /* CPU only: the layout arithmetic behind pbrh_create_tile.  rects = interior, shaded, bloom rectangle (x, y, w, h each, in
@@ -181,7 +181,7 @@ int pbrh_set_external_histogram(pbrh_renderer* r, const uint32_t* counts256);
 int pbrh_capture_histogram(pbrh_renderer* r, int on);
 int pbrh_captured_histogram(pbrh_renderer* r, uint32_t* dst256);
 /* on: ClusteredPass, BloomPass and the one-shot PreFilterEnvMapPass hand their fixed dispatch sequences over as one call each
- * (pbr_clustered, pbr_bloom[_histogram], pbr_prefilter_env); off (default): every reference dispatch is issued one by one.
+ * (pbr_clustered, pbr_bloom, pbr_prefilter_env); off (default): every reference dispatch is issued one by one.
  * The per-frame passes give the same frame bit for bit either way; the fused env chain is within 1 fp16 ULP of the five
  * dispatches (tests/test_host_graph.py).  May be switched between frames. */
 int pbrh_set_fused(pbrh_renderer* r, int on);

@@ -200,7 +200,7 @@ def halo_plan(rank, world, specs):
 
 class HaloTransport:
     """How the level-1 strips travel between ranks in halo mode.  `exchange(frame)` is enqueued between
-    pbr_bloom_prefilter_rect and pbr_bloom_tiled.
+    pbr_bloom_prefilter's rectangles and pbr_bloom's tiled form.
       "capi"  : pbr_halo_exchange — RCCL send/recv on the context's own communicator (pbr_comm_init);
       "torch" : pbr_halo_pack + torch.distributed P2P (RCCL with the nccl backend) + unpack;
       "host"  : like "torch" but through host copies — gloo rehearsals with several ranks on one GPU."""

@@ -102,6 +102,23 @@ class DepthRasterDesc(C.Structure):
                 + [(n, C.c_uint32) for n in ("n_vertices", "n_indices", "n_draws", "max_triangles", "pitch", "reserved")])
 
 
+class BloomDesc(C.Structure):
+    """pbr_bloom_desc: one pbr_bloom call (include/pbr_hip.h); pointers first, then the 32-bit fields: no padding.  The three
+    rectangles are HOST addresses of uint32[4] arrays the caller keeps alive; hdr_rect unset: the whole-image form; reserved stays 0."""
+    _fields_ = ([(n, C.c_void_p) for n in ("hdr", "chain_a", "chain_b", "hist256", "hdr_rect", "merge_rect", "hist_rect")]
+                + [(n, C.c_uint32) for n in ("w", "h", "hdr_pitch")]
+                + [(n, C.c_float) for n in ("threshold", "knee", "min_log", "inv_range")] + [("reserved", C.c_uint32)])
+
+
+class BloomPrefilterDesc(C.Structure):
+    """pbr_bloom_prefilter_desc: one pbr_bloom_prefilter call (include/pbr_hip.h); pointers first, then the 32-bit fields: no padding.
+    rects is the HOST address of a uint32[n_rects][4] array the caller keeps alive; unset with n_rects 0: the whole image into a
+    dense plane; reserved stays 0."""
+    _fields_ = ([(n, C.c_void_p) for n in ("hdr", "out", "rects")]
+                + [(n, C.c_uint32) for n in ("w", "h", "pitch", "out_pitch", "out_x", "out_y", "n_rects")]
+                + [(n, C.c_float) for n in ("threshold", "knee")] + [("reserved", C.c_uint32)])
+
+
 MAX_VIEWS = 16                                        # PBR_MAX_VIEWS (include/pbr_hip.h)
 
 

@@ -815,9 +815,26 @@ pbr_status pbr_depth_raster(pbr_ctx* ctx, const pbr_depth_raster_desc* d);
 size_t pbr_depth_raster_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
 size_t pbr_depth_raster_min_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_triangles);
 
-/* bloom_prefilter.hlsl:17-60 (DeferredPipeline.cpp:411-427): hdr (w x h) -> out (w>>1 x h>>1). */
-pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h,
-                               uint32_t pitch, pbr_half* out, float threshold, float knee);
+/* bloom_prefilter.hlsl:17-60 (DeferredPipeline.cpp:411-427), ONE call described by a HOST struct (pointers first, then the 32-bit
+ * fields: 64 bytes, no padding).  hdr: the w x h image, pitch `pitch` pixels.
+ * rects == NULL and n_rects == 0: hdr -> out (w>>1 x h>>1), a dense plane; out_pitch, out_x and out_y must be 0.
+ * Otherwise 1 .. 5 rectangles {x, y, w, h} of the half-res image (multi-GPU halo path): their texels are computed and stored at
+ * out[(out_y + y) * out_pitch + (out_x + x)] — a tile writes the level-1 texels of its interior, or of the four bands of its border
+ * ring in one launch, into the level-1 plane of its extended rectangle.  Texels outside the rectangles are left as they were.
+ * Refusals (PBR_ERR_INVALID, nothing enqueued), in this order: a null descriptor; reserved != 0; hdr or out NULL ("null pointer");
+ * rects NULL with n_rects != 0, rects with n_rects outside 1 .. 5 ("null pointer / 1 .. 5 rectangles"); no half-res texel, a side above
+ * 65535, pitch < w ("bad size"); the dense form with out_pitch, out_x or out_y set; out_pitch or out_y above 65535 ("bad size"); then
+ * the first faulty rectangle: "rect outside the half-res image", or "rect does not fit the output pitch" (out_pitch < out_x + x + w). */
+typedef struct pbr_bloom_prefilter_desc {
+    const pbr_half* hdr;
+    pbr_half* out;
+    const uint32_t (*rects)[4];
+    uint32_t w, h, pitch;
+    uint32_t out_pitch, out_x, out_y, n_rects;
+    float threshold, knee;
+    uint32_t reserved;                 /* must be 0 */
+} pbr_bloom_prefilter_desc;
+pbr_status pbr_bloom_prefilter(pbr_ctx* ctx, const pbr_bloom_prefilter_desc* d);
 /* blur_horizontal.hlsl / blur.hlsli:24-55: in (iw x ih) sampled bilinearly at the texel
  * centres of out (ow x oh), 9 taps one OUTPUT texel apart in x. */
 pbr_status pbr_blur_h(pbr_ctx* ctx, const pbr_half* in, uint32_t iw, uint32_t ih,
@@ -842,42 +859,42 @@ pbr_status pbr_bloom_merge(pbr_ctx* ctx, pbr_half* hdr, uint32_t pitch, const pb
  * once: every texel of an input must carry the same alpha — true of every level inside pbr_bloom, whose prefilter writes alpha 1. */
 pbr_status pbr_bloom_up_level(pbr_ctx* ctx, const pbr_half* upper, const pbr_half* lower, uint32_t lw, uint32_t lh,
                               pbr_half* out, uint32_t ow, uint32_t oh);
-/* BloomPass::Execute (DeferredPipeline.cpp:400-570), all 16 dispatches.  hdr is bit-identical to the sequence of stage calls
- * above for frames below ~1.6 Mpixel; from there on the large 2x-up levels run in polyphase form (pbr_bloom_up_level) and hdr
- * is within 2 fp16 ULP of that sequence (>= 99.9 % of the texels identical).  chain_a / chain_b: pbr_bloom_chain_texels(w,h) half4 texels each (BloomMipchain /
- * BloomTempTexture) — SCRATCH: their contents after the call are unspecified.  (Wherever a level is exactly half
- * the one above and at most 8192 wide/high, the H and V pass of that level pair run as one kernel and the H result
- * is never written; elsewhere the staged kernels run.  Level 0 of chain_a — the V blur the merge consumes — is
- * never written.) */
-pbr_status pbr_bloom(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
-                     pbr_half* chain_a, pbr_half* chain_b, float threshold, float knee);
-
-/* bloom_prefilter.hlsl on part of the image (multi-GPU halo path): the half-res outputs rect = {x, y, w, h} of the
- * w x h image `hdr` are computed and stored at out[(out_y + y) * out_pitch + (out_x + x)] — a tile writes the level-1
- * texels of its interior into the level-1 plane of its extended rectangle. */
-pbr_status pbr_bloom_prefilter_rect(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
-                                    pbr_half* out, uint32_t out_pitch, uint32_t out_x, uint32_t out_y,
-                                    const uint32_t rect[4], float threshold, float knee);
-/* the same for up to 5 rectangles in one launch (the four bands of a tile's border ring) */
-pbr_status pbr_bloom_prefilter_rects(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
-                                     pbr_half* out, uint32_t out_pitch, uint32_t out_x, uint32_t out_y,
-                                     const uint32_t (*rects)[4], uint32_t n_rects, float threshold, float knee);
-/* BloomPass::Execute minus its first dispatch, on the extended rectangle E (ew x eh, a multiple of 16 and <= 8192 on
- * a side) of a tile: level 1 of chain_a (offset pbr_bloom_level_offset(ew, eh, 1)) must hold the prefiltered image of
- * ALL of E — the interior from pbr_bloom_prefilter_rect, the rest from the neighbouring tiles (pbr_halo_exchange).
- * Runs the 3 + 3 level pairs on E and merges (DeferredPipeline.cpp:521-570) only merge_rect = {x, y, w, h} of E into
- * hdr, which covers hdr_rect of E (hdr[0] = texel (hdr_rect.x, hdr_rect.y), pitch hdr_pitch pixels).  hist256 != NULL:
- * the luminance histogram of the merged pixels is added (pbr_lum_histogram).  Chains are scratch. */
-pbr_status pbr_bloom_tiled(pbr_ctx* ctx, pbr_half* hdr, uint32_t hdr_pitch, const uint32_t hdr_rect[4],
-                           uint32_t ew, uint32_t eh, pbr_half* chain_a, pbr_half* chain_b, const uint32_t merge_rect[4],
-                           float min_log, float inv_range, uint32_t* hist256);
-
-/* pbr_bloom + the luminance histogram (pbr_lum_histogram) of rect = {x, y, w, h} of the bloomed
- * image, accumulated inside the final bloom kernel (saves one full read of the HDR buffer).
- * ADDS into hist256 like the separate pass. */
-pbr_status pbr_bloom_histogram(pbr_ctx* ctx, pbr_half* hdr, uint32_t w, uint32_t h, uint32_t pitch,
-                               pbr_half* chain_a, pbr_half* chain_b, float threshold, float knee,
-                               const uint32_t rect[4], float min_log, float inv_range, uint32_t* hist256);
+/* BloomPass::Execute (DeferredPipeline.cpp:400-570), ONE call described by a HOST struct (pointers first, then the 32-bit fields: 88
+ * bytes, no padding).  The rectangles are HOST arrays {x, y, w, h}.  chain_a / chain_b: pbr_bloom_chain_texels(w, h) half4 texels each
+ * (BloomMipchain / BloomTempTexture) — SCRATCH: their contents after the call are unspecified.  (Wherever a level is exactly half the
+ * one above and at most 8192 wide/high, the H and V pass of that level pair run as one kernel and the H result is never written;
+ * elsewhere the staged kernels run.  Level 0 of chain_a — the V blur the merge consumes — is never written.)
+ * WHOLE-IMAGE FORM, hdr_rect == NULL: all 16 dispatches on hdr, the w x h image (pitch hdr_pitch pixels).  hdr is bit-identical to
+ * the sequence of stage calls above for frames below ~1.6 Mpixel; from there on the large 2x-up levels run in polyphase form
+ * (pbr_bloom_up_level) and hdr is within 2 fp16 ULP of that sequence (>= 99.9 % of the texels identical).  hist_rect and hist256,
+ * both set or both NULL: the luminance histogram (pbr_lum_histogram, min_log, inv_range) of hist_rect of the bloomed image, accumulated
+ * inside the final bloom kernel (saves one full read of the HDR buffer); it ADDS into hist256 like the separate pass.
+ * TILED FORM, hdr_rect != NULL: BloomPass::Execute minus its first dispatch, on the extended rectangle E (w x h, a multiple of 16 and
+ * <= 8192 on a side) of a tile: level 1 of chain_a (offset pbr_bloom_level_offset(w, h, 1)) must hold the prefiltered image of ALL
+ * of E — the interior from pbr_bloom_prefilter, the rest from the neighbouring tiles (pbr_halo_exchange); threshold and knee are
+ * ignored.  Runs the 3 + 3 level pairs on E and merges (DeferredPipeline.cpp:521-570) only merge_rect of E into hdr, which covers
+ * hdr_rect of E (hdr[0] = texel (hdr_rect.x, hdr_rect.y), pitch hdr_pitch pixels).  hist256 != NULL: the histogram of the merged
+ * pixels is added.
+ * Refusals (PBR_ERR_INVALID unless stated, nothing enqueued), in this order: a null descriptor; reserved != 0.  Whole-image form:
+ * "merge_rect without hdr_rect"; "hist_rect without hist256" and "hist256 without hist_rect"; hist_rect empty or "rect outside the
+ * image"; hdr or a chain NULL ("null pointer"); "image too small for 5 mips"; a side above 65535 or hdr_pitch < w ("bad size").
+ * Tiled form: "hist_rect in the tiled form" (the histogram counts merge_rect); hdr, a chain or merge_rect NULL ("null pointer"); E too
+ * small for 5 mips or above 65535 ("bad size"); "hdr_rect outside the extended tile" (or hdr_pitch below its width); "merge_rect
+ * outside hdr_rect"; PBR_ERR_UNSUPPORTED for E odd or above 8192 on a side. */
+typedef struct pbr_bloom_desc {
+    pbr_half* hdr;
+    pbr_half* chain_a;
+    pbr_half* chain_b;
+    uint32_t* hist256;
+    const uint32_t* hdr_rect;          /* NULL: the whole-image form */
+    const uint32_t* merge_rect;        /* tiled form only */
+    const uint32_t* hist_rect;         /* whole-image form only */
+    uint32_t w, h, hdr_pitch;
+    float threshold, knee;
+    float min_log, inv_range;
+    uint32_t reserved;                 /* must be 0 */
+} pbr_bloom_desc;
+pbr_status pbr_bloom(pbr_ctx* ctx, const pbr_bloom_desc* d);
 
 /* hdr_luminance_histogram.hlsl:23-59 (DeferredPipeline.cpp:276-298): ADDS into hist256. */
 pbr_status pbr_lum_histogram(pbr_ctx* ctx, const pbr_half* hdr, uint32_t w, uint32_t h,
@@ -930,8 +947,8 @@ pbr_status pbr_clustered_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n);
 pbr_status pbr_deferred_shade_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h,
                                     const pbr_half* lut, uint32_t lut_res,
                                     const pbr_half* env_padded, uint32_t env_size, uint32_t env_mips);
-/* BloomPass::Execute (DeferredPipeline.cpp:400-570) + the histogram dispatch (:276-298) per view: pbr_bloom_histogram of the
- * whole frame (hdr, chain_a, chain_b -> hist256, which it ADDS into). */
+/* BloomPass::Execute (DeferredPipeline.cpp:400-570) + the histogram dispatch (:276-298) per view: pbr_bloom's whole-image form with
+ * the whole frame as hist_rect (hdr, chain_a, chain_b -> hist256, which it ADDS into). */
 pbr_status pbr_bloom_histogram_views(pbr_ctx* ctx, const pbr_view* views, uint32_t n, uint32_t w, uint32_t h,
                                      float threshold, float knee, float min_log, float inv_range);
 /* hdr_average_histogram.hlsl (DeferredPipeline.cpp:300-317) per view: pbr_lum_average(hist256, pixel_count, g.DeltaTime, avg). */

@@ -1,12 +1,17 @@
-"""The entry-point code of bloom.hip that no other test calls directly: what each bloom entry point refuses, and under which name,
-and the rectangle forms of the prefilter against the whole-image call.  The expected messages are the ones the C ABI has given
-since these entry points were added (include/pbr_hip.h documents the refusals); a refused call enqueues nothing."""
+"""The entry-point code of bloom.hip that no other test calls directly: what pbr_bloom, pbr_bloom_prefilter and pbr_bloom_up_level
+refuse, and with which reason, and the rectangle forms of the prefilter against the whole-image call.  The reasons after the name are
+the ones the C ABI gave when each of the six PbrContext methods had an entry point of its own (include/pbr_hip.h documents the
+refusals; a faulty rectangle among several is now reported with the text a single one gets); the combinations of descriptor fields
+that no method can build are refused too.  A refused call enqueues nothing."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
 
 from direct12pbrrenderer_amd import synth
 from direct12pbrrenderer_amd.api import PbrError
+from direct12pbrrenderer_amd.structs import BloomDesc, BloomPrefilterDesc
 
 pytestmark = pytest.mark.gpu
 
@@ -31,29 +36,61 @@ def buf(ctx):
 def _bad_calls(ctx, b):
     hdr, a, c, out, hist = b
     good = (8, 8, 16, 8)   # a rectangle inside the 80 x 36 half-res image of 160 x 72
+    p = {"hdr": hdr.data_ptr(), "chain_a": a.data_ptr(), "chain_b": c.data_ptr(), "out": out.data_ptr(), "hist256": hist.data_ptr()}
+    whole, shaded, one = (C.c_uint32 * 4)(0, 0, 64, 64), (C.c_uint32 * 4)(16, 16, 64, 64), ((C.c_uint32 * 4) * 1)((C.c_uint32 * 4)(*good))
+    at = C.addressof
+
+    def raw_bloom(w, h, pitch, *pointers, **fields):   # descriptors no PbrContext method builds, given to the library as they are
+        d = BloomDesc(w=w, h=h, hdr_pitch=pitch, **{k: p[k] for k in pointers}, **fields)
+        return lambda keep=(whole, shaded): ctx._check(ctx.lib.pbr_bloom(ctx.h, C.byref(d)))   # (the descriptor holds the rectangles' addresses)
+
+    def raw_prefilter(w, h, pitch, **fields):
+        d = BloomPrefilterDesc(hdr=p["hdr"], out=p["out"], w=w, h=h, pitch=pitch, **fields)
+        return lambda keep=one: ctx._check(ctx.lib.pbr_bloom_prefilter(ctx.h, C.byref(d)))
+
     return {
+        "bloom null descriptor": (lambda: ctx._check(ctx.lib.pbr_bloom(ctx.h, None)), "status -1: pbr_bloom: null descriptor"),
+        "bloom merge_rect without hdr_rect": (raw_bloom(64, 64, 64, "hdr", "chain_a", "chain_b", merge_rect=at(whole)),
+                                              "status -1: pbr_bloom: merge_rect without hdr_rect"),
+        "bloom hist_rect without hist256": (raw_bloom(64, 64, 64, "hdr", "chain_a", "chain_b", hist_rect=at(whole)),
+                                            "status -1: pbr_bloom: hist_rect without hist256"),
+        "bloom hist256 without hist_rect": (raw_bloom(64, 64, 64, "hdr", "chain_a", "chain_b", "hist256"),
+                                            "status -1: pbr_bloom: hist256 without hist_rect"),
+        "bloom hist_rect in the tiled form": (raw_bloom(160, 96, 64, "hdr", "chain_a", "chain_b", "hist256", hdr_rect=at(shaded), merge_rect=at(shaded),
+                                                        hist_rect=at(shaded)),
+                                              "status -1: pbr_bloom: hist_rect in the tiled form (the histogram counts merge_rect)"),
+        "bloom reserved set": (raw_bloom(64, 64, 64, "hdr", "chain_a", "chain_b", reserved=1), "status -1: pbr_bloom: reserved must be 0"),
+        "prefilter null descriptor": (lambda: ctx._check(ctx.lib.pbr_bloom_prefilter(ctx.h, None)), "status -1: pbr_bloom_prefilter: null descriptor"),
+        "prefilter n_rects without rects": (raw_prefilter(160, 72, 160, out_pitch=96, n_rects=1),
+                                            "status -1: pbr_bloom_prefilter: null pointer / 1 .. 5 rectangles"),
+        "prefilter rects with n_rects 0": (raw_prefilter(160, 72, 160, out_pitch=96, rects=at(one)),
+                                           "status -1: pbr_bloom_prefilter: null pointer / 1 .. 5 rectangles"),
+        "prefilter dense plane with an offset": (raw_prefilter(160, 72, 160, out_x=4),
+                                                 "status -1: pbr_bloom_prefilter: out_pitch, out_x and out_y must be 0 without rects"),
+        "prefilter dense plane with a pitch": (raw_prefilter(160, 72, 160, out_pitch=80),
+                                               "status -1: pbr_bloom_prefilter: out_pitch, out_x and out_y must be 0 without rects"),
+        "prefilter reserved set": (raw_prefilter(160, 72, 160, reserved=1), "status -1: pbr_bloom_prefilter: reserved must be 0"),
         "bloom 8x8": (lambda: ctx.bloom(hdr, 8, 8, 8, a, c), "status -1: pbr_bloom: image too small for 5 mips"),
-        # pbr_bloom_histogram checks its sizes in the code it shares with pbr_bloom, under that name
         "bloom_histogram 8x8": (lambda: ctx.bloom_histogram(hdr, 8, 8, 8, a, c, (0, 0, 8, 8), hist),
                                 "status -1: pbr_bloom: image too small for 5 mips"),
         "bloom_histogram rect past the image": (lambda: ctx.bloom_histogram(hdr, 64, 64, 64, a, c, (1, 0, 64, 64), hist),
-                                                "status -1: pbr_bloom_histogram: rect outside the image"),
+                                                "status -1: pbr_bloom: rect outside the image"),
         "bloom_prefilter pitch < w": (lambda: ctx.bloom_prefilter(hdr, 64, 64, 63, out), "status -1: pbr_bloom_prefilter: bad size"),
         "bloom_prefilter_rect rect past the half-res image": (lambda: ctx.bloom_prefilter_rect(hdr, 160, 72, 160, out, 96, 0, 0, (70, 8, 11, 8)),
-                                                              "status -1: pbr_bloom_prefilter_rect: rect outside the half-res image"),
+                                                              "status -1: pbr_bloom_prefilter: rect outside the half-res image"),
         "bloom_prefilter_rect out_pitch too small": (lambda: ctx.bloom_prefilter_rect(hdr, 160, 72, 160, out, 30, 7, 0, good),
-                                                     "status -1: pbr_bloom_prefilter_rect: rect does not fit the output pitch"),
+                                                     "status -1: pbr_bloom_prefilter: rect does not fit the output pitch"),
         "bloom_prefilter_rects 0 rectangles": (lambda: ctx.bloom_prefilter_rects(hdr, 160, 72, 160, out, 96, 0, 0, []),
-                                               "status -1: pbr_bloom_prefilter_rects: null pointer / 1 .. 5 rectangles"),
+                                               "status -1: pbr_bloom_prefilter: null pointer / 1 .. 5 rectangles"),
         "bloom_prefilter_rects 6 rectangles": (lambda: ctx.bloom_prefilter_rects(hdr, 160, 72, 160, out, 96, 0, 0, [good] * 6),
-                                               "status -1: pbr_bloom_prefilter_rects: null pointer / 1 .. 5 rectangles"),
+                                               "status -1: pbr_bloom_prefilter: null pointer / 1 .. 5 rectangles"),
         "bloom_prefilter_rects one bad rectangle among good ones": (
             lambda: ctx.bloom_prefilter_rects(hdr, 160, 72, 160, out, 96, 0, 0, [good, (8, 30, 16, 7), good]),
-            "status -1: pbr_bloom_prefilter_rects: rectangle outside the half-res image / the output pitch"),
+            "status -1: pbr_bloom_prefilter: rect outside the half-res image"),
         "bloom_tiled merge_rect outside hdr_rect": (lambda: ctx.bloom_tiled(hdr, 64, (16, 16, 64, 64), 160, 96, a, c, (15, 16, 64, 64), hist),
-                                                    "status -1: pbr_bloom_tiled: merge_rect outside hdr_rect"),
+                                                    "status -1: pbr_bloom: merge_rect outside hdr_rect"),
         "bloom_tiled odd extended size": (lambda: ctx.bloom_tiled(hdr, 64, (16, 16, 64, 64), 161, 96, a, c, (16, 16, 64, 64), hist),
-                                          "status -4: pbr_bloom_tiled: the extended tile must be even and <= 8192 on a side"),
+                                          "status -4: pbr_bloom: the extended tile must be even and <= 8192 on a side"),
         "bloom_up_level out not twice lower": (lambda: ctx.bloom_up_level(a, c, 40, 18, out, 80, 38),
                                                "status -1: pbr_bloom_up_level: out must be exactly twice lower, even, <= 8192"),
         "bloom_up_level out aliases an input": (lambda: ctx.bloom_up_level(a, c, 40, 18, a, 80, 36),
@@ -112,3 +149,11 @@ def test_prefilter_rects_in_three_bands_give_the_same_bits(ctx, whole):
     dst = _poisoned(ctx)
     ctx.bloom_prefilter_rects(hdr, w, h, w, dst, OUT_PITCH, OUT_X, OUT_Y, BANDS)
     assert np.array_equal(bits(dst), _expected_window(full))
+
+
+def test_prefilter_without_rects_is_the_one_rectangle_of_the_whole_image(ctx, whole):
+    """rects == NULL, n_rects == 0 (bloom_prefilter) against the same call with the rectangle {0, 0, w >> 1, h >> 1} and out_pitch w >> 1"""
+    w, h, hdr, full = whole
+    dst = dev_half(ctx, np.full((h // 2, w // 2, 4), POISON, dtype=np.float16))
+    ctx.bloom_prefilter_rect(hdr, w, h, w, dst, w // 2, 0, 0, (0, 0, w // 2, h // 2))
+    assert np.array_equal(bits(dst), full)
